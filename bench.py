@@ -33,6 +33,12 @@ The JSON line also carries
                  (~22 s; --cpu-anchors 256 = the full wireframe; if it does not finish within --cpu-timeout, 32 anchors;
                  sequences are independent, so the sample is faithful) -- `sample` says which; `first_divergence` names the first (sequence, step) at
                  which the GPU's tokens leave the oracle's, with the oracle's own top-2 margin there and the tolerance.
+
+--dump-outputs DIR writes what the timed step returned in its LAST timed step -- `predict`, the greedy edge-index tokens
+(N x F x T; at N > 1 the gathered batch) -- as DIR/predict.npy in float32 (float64 if a token does not fit float32 exactly).
+Inputs and weights are generated from fixed seeds, so two builds given the same arguments can be compared output for output.
+Above DUMP_LIMIT_BYTES the file holds a fixed, seeded sample of the (wireframe, anchor) rows and DIR/predict_rows.npy their
+flat row indices.
 """
 import argparse
 import ctypes
@@ -53,6 +59,8 @@ E_SIZES, E_PROBS, E_SEED = (64, 128, 256, 512, 1024), (.3, .3, .2, .1, .1), 2024
 CAT_NAMES = ["gemm_f32_kernels", "attention_kernels", "layernorm_kernel", "pointer_kernels", "row_ops", "unused",
              "gemm_bf16x3_kernel"]
 PEAK_BF16_MFMA_TFLOPS = 2500.0   # MI355X_MICROARCH.md: v_mfma_f32_32x32x16_bf16 dense; the split product spends 6 of them per fp32 product
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 4096   # --dump-outputs: all files together, .npy headers included
+DUMP_SAMPLE_SEED = 2024
 
 
 def alg_flops_per_wireframe(n, T, E=512, FF=1024, layers=6, in_dim=100, F=None):
@@ -111,6 +119,25 @@ def timed(step_fn, fence, warmup, steps):
         out = step_fn()
     fence()
     return time.perf_counter() - t0, out
+
+
+def dump_outputs(dirname, name, arr):
+    """`arr` (numpy, last axis = one row of output) as dirname/<name>.npy in float32, or float64 when float32 would not hold
+    it exactly; above DUMP_LIMIT_BYTES a fixed, seeded sample of its rows plus dirname/<name>_rows.npy (their flat indices)."""
+    import numpy as np
+    exact32 = arr.dtype == np.float32 or (arr.dtype.kind in "iu" and (arr.size == 0 or int(np.abs(arr).max()) < 2 ** 24))
+    out = arr.astype(np.float32 if exact32 else np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    written = [os.path.join(dirname, name + ".npy")]
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        rows = out.reshape(-1, out.shape[-1])
+        keep = DUMP_LIMIT_BYTES // (rows.shape[1] * rows.itemsize + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.shape[0], size=keep, replace=False))
+        out = rows[idx]
+        written.append(os.path.join(dirname, name + "_rows.npy"))
+        np.save(written[1], idx.astype(np.float64))
+    np.save(written[0], out)
+    return written
 
 
 def profile_once(lib, L, run_once):
@@ -438,8 +465,10 @@ def dry_rank(args, rank, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps of the main line (>= 1); ms_per_step = their mean")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--config", default="B", choices=["B", "E"],
                     help="B: 256-edge wireframes (BASELINE configs 2/3, the headline); E: ours-perspective.yml with "
                          "num_lines=1024, ragged 64..1024-edge wireframes (BASELINE config 5)")
@@ -490,6 +519,8 @@ def main():
                     help="N > 1 on a ONE-GPU box: all ranks share device 0 and gloo is the collective backend (RCCL refuses two ranks "
                          "on one device).  Runs every line of the N-rank code path; the figures are NOT a measurement (the line says so)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     t_start = time.perf_counter()
 
     # ---- launch contract: `--gpus N` is what runs, or nothing does ---------------------------------------------------
@@ -650,6 +681,9 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:   # (copied now: the lines below run the same model again)
+        for path in dump_outputs(args.dump_outputs, "predict", pred.cpu().numpy()):
+            sys.stderr.write("bench.py: wrote %s\n" % path)
 
     # decode steps actually executed (the reference semantics run T-1 with these weights)
     local = pred[rank * W:(rank + 1) * W] if multi else pred

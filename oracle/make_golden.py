@@ -1,7 +1,11 @@
 """ORACLE TOOLING (build container only): pin `oracle/refpath.py` against the *imported reference* and
 write the golden vectors under `tests/golden/`.
 
-Run:  python oracle/make_golden.py [--only NAME ...] [--skip-slow]
+Run:  python oracle/make_golden.py [--only NAME ...] [--skip-slow] [--cpu-pinned]
+
+tests/golden/<case>.npz are what the GPU parity tests compare against (within their tolerance), captured on the
+host's default CPU path.  The CPU oracle test compares bit for bit, which only holds on one numeric path: it reads
+tests/golden/cpu_pinned/<case>.npz, written with --cpu-pinned (oracle/cpu_numerics.py).
 
 For every case in `oracle/golden_cases.py` it
   1. builds the reference model class from /root/reference (imported, never copied), loads the
@@ -23,7 +27,14 @@ import time
 import types
 
 import numpy as np
-import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import cpu_numerics  # noqa: E402
+
+CPU_PINNED = "--cpu-pinned" in sys.argv
+if CPU_PINNED:   # (before torch loads)
+    cpu_numerics.pin()
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -154,14 +165,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
     ap.add_argument("--skip-slow", action="store_true")
+    ap.add_argument("--cpu-pinned", action="store_true",
+                    help="capture on the pinned CPU path of oracle/cpu_numerics.py into tests/golden/cpu_pinned/ (the vectors of "
+                         "the bit-exact CPU oracle test: --skip-slow, then --only seq_full_A64_gain4 seq_full_D216_extramask)")
     args = ap.parse_args()
     if not os.path.isdir(REFERENCE):
         raise SystemExit("make_golden.py needs /root/reference (build container only)")
-    torch.set_num_threads(max(1, os.cpu_count() or 1))
+    if not args.cpu_pinned:
+        torch.set_num_threads(max(1, os.cpu_count() or 1))
     ref_models = _import_reference()
     sys.path.insert(0, ROOT)
     from oracle.golden_cases import CASES
-    outdir = os.path.join(ROOT, "tests", "golden")
+    outdir = os.path.join(ROOT, "tests", "golden", *(["cpu_pinned"] if args.cpu_pinned else []))
     os.makedirs(outdir, exist_ok=True)
     for case in CASES:
         if args.only and case["name"] not in args.only:

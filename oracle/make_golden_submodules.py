@@ -16,7 +16,12 @@ import sys
 import types
 
 import numpy as np
-import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import cpu_numerics  # noqa: E402
+
+cpu_numerics.pin()   # before torch loads: the goldens are captured on the path the tests run on
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)

@@ -3,13 +3,17 @@ import os
 import sys
 import types
 
-import numpy as np
-import pytest
-import torch
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from oracle import cpu_numerics  # noqa: E402
+
+cpu_numerics.pin()   # before torch loads: tests/golden/cpu_pinned/ is bit-exact on this path on any host
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
+import torch  # noqa: E402
+
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
@@ -46,8 +50,10 @@ def token_ns():
     return types.SimpleNamespace(PAD=0, SOS=1, SEP=2, EOS=3, DIR0=4, DIR1=5, len=4, face_type_offset=1)
 
 
-def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+def load_golden(name, cpu_pinned=False):
+    """`cpu_pinned`: the same case captured on the pinned CPU path (oracle/cpu_numerics.py), for the bit-exact CPU oracle
+    test; the default files are the capture the GPU parity tests compare against within their tolerance."""
+    z = np.load(os.path.join(GOLDEN, "cpu_pinned" if cpu_pinned else "", name + ".npz"))
     case = json.loads(bytes(z["case"]).decode())
     return case, z
 

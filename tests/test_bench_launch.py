@@ -82,3 +82,30 @@ def test_compact_line_sheds_optional_blocks_rather_than_grow():
     line = bench.compact_line(full)
     d = json.loads(line)
     assert len(line) < 4096 and "other_configs" not in d and "roofline" in d and "cpu_baseline" in d
+
+
+def test_steps_below_one_is_refused():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT, env=_env(),
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 2 and "--steps" in p.stderr and not p.stdout.strip()
+
+
+def test_dump_outputs_writes_exact_tokens_and_a_bounded_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: integer tokens come back exactly as float32; above the size limit a fixed sample of rows is written
+    with their flat indices, the same rows on every call, all files together within the limit."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    pred = np.random.default_rng(0).integers(0, 1030, size=(3, 40, 37)).astype(np.int64)
+    paths = bench.dump_outputs(str(tmp_path / "full"), "predict", pred)
+    got = np.load(paths[0])
+    assert len(paths) == 1 and got.dtype == np.float32 and np.array_equal(got, pred)
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 37 * 4 + 16 * 8)
+    a = bench.dump_outputs(str(tmp_path / "a"), "predict", pred)
+    b = bench.dump_outputs(str(tmp_path / "b"), "predict", pred)
+    rows, idx = np.load(a[0]), np.load(a[1])
+    assert rows.shape == (16, 37) and idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(rows, pred.reshape(-1, 37)[idx.astype(np.int64)])
+    assert np.array_equal(np.load(b[0]), rows) and np.array_equal(np.load(b[1]), idx)
+    assert rows.nbytes + idx.nbytes <= bench.DUMP_LIMIT_BYTES

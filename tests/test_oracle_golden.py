@@ -6,11 +6,12 @@ import pytest
 import torch
 
 from conftest import case_weights_and_batch, ctor_kwargs, golden_names, load_golden
-from oracle import refpath
+from oracle import cpu_numerics, refpath
 
 
 def _check(name):
-    case, z = load_golden(name)
+    assert cpu_numerics.is_pinned(), "torch was loaded before tests/conftest.py pinned the CPU path (oracle/cpu_numerics.py)"
+    case, z = load_golden(name, cpu_pinned=True)
     sd, batch = case_weights_and_batch(case)
     trace = {}
     extra = batch.pop("extra_mask", None)

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, batch_to, build_model, case_weights_and_batch, load_golden, token_ns
+from oracle import cpu_numerics
 from oracle import make_golden_submodules as G
 
 TOL_REL = 2e-5   # fp32 blocks, outputs O(1..10): well inside the path's 2.5e-5-relative logit bar
@@ -32,6 +33,7 @@ def _fixture():
 # ---- CPU: the oracle restatements are pinned to the reference-generated vectors -------------------------------------
 @pytest.mark.parametrize("name", [n for n, c in G.CASES.items() if c["kind"] in ("decoder", "encoder", "select_next")])
 def test_oracle_restatement_matches_reference_vectors(name):
+    assert cpu_numerics.is_pinned(), "torch was loaded before tests/conftest.py pinned the CPU path (oracle/cpu_numerics.py)"
     from faceformer_amd.synth import make_module_state
     z, cases = _fixture()
     c = cases[name]
