@@ -59,7 +59,7 @@ def _mha(query, key, value, sd, prefix, num_head, key_padding_mask=None, attn_ma
 def embed_edges(sd, coord, num_token):
     """reference embedding.py:23-38: token rows ++ MLP(flattened points)."""
     n = coord.size(0)
-    token = torch.arange(num_token, dtype=torch.long)
+    token = torch.arange(num_token, dtype=torch.long, device=coord.device)
     token_embed = F.embedding(token, sd["val_enc.embedding_token.weight"])
     token_embed = token_embed.unsqueeze(0).expand(n, num_token, -1)
     h = F.linear(coord.flatten(-2, -1), sd["val_enc.embedding_value.0.weight"],
@@ -239,7 +239,7 @@ def _dims(sd):
 @torch.no_grad()
 def parallel_forward_eval(sd, inputs, num_head=8, max_face_length=None, trace=None,
                           anchor_limit=None, stop_rule=True, num_anchors=None, extra_mask=None,
-                          normalize_before=True, activation="relu"):
+                          normalize_before=True, activation="relu", forced=None, steps=None, seqs=None):
     """SurfaceFormer_Parallel.forward_eval (reference model_para.py:181-241).
 
     `trace`: optional dict; receives 'logits' (list of BxS tensors per step) and 'memory'.
@@ -252,6 +252,10 @@ def parallel_forward_eval(sd, inputs, num_head=8, max_face_length=None, trace=No
     `normalize_before` / `activation`: the constructor arguments the reference hands to its layers (model_para.py:14-19,
     33-45; no reference config changes them): post-norm layers (transformer.py:148-162, 211-233; `encoder.norm` is then
     None, model_para.py:36) and gelu feed-forward layers.
+    `forced` / `steps` / `seqs`: teacher forcing, ONLY for the tests -- see `_forced_path`.  The sequences of a forced run are
+    independent of one another, so `seqs` (indices into the N*F rows) evaluates a subset; F stays the batch-global
+    max(num_input) (or `num_anchors`).  `predict` is then [len(seqs), T] and trace['logits'] holds the subset's rows.
+    Every tensor is created on the device of the inputs; the dtype follows the state_dict (float64 gives the fp64 truth).
     """
     num_model, n_enc, n_dec, num_token = _dims(sd)
     run_encoder, run_decoder = _stacks(sd, num_head, n_enc, n_dec, normalize_before, activation)
@@ -280,41 +284,78 @@ def parallel_forward_eval(sd, inputs, num_head=8, max_face_length=None, trace=No
         max_num_edges = anchors.size(2)
     query_pos_embed = query_pos_embed.transpose(0, 1)
     predicts = anchors.flatten(1, 2)
+    path, n_steps, seqs = _forced_path(forced, steps, seqs, T, predicts.size(1), label.device)
+    if path is not None:
+        if anchor_limit is not None:
+            raise ValueError("anchor_limit and forced exclude each other")
+        predicts = path[:, :1].transpose(0, 1)
 
     memory = run_encoder(source, input_mask, pos_embed)
     if trace is not None:
         trace["memory"] = memory.transpose(0, 1).clone()
         trace["logits"] = []
         trace["counts"] = []
-    memory = memory.repeat_interleave(max_num_edges, 1)
-    input_mask = input_mask.repeat_interleave(max_num_edges, 0)
+    if seqs is None:
+        memory = memory.repeat_interleave(max_num_edges, 1)
+        input_mask = input_mask.repeat_interleave(max_num_edges, 0)
+    else:                       # the same rows as repeat_interleave(F) followed by [seqs], without the whole N*F copy
+        memory = memory.index_select(1, seqs // max_num_edges)
+        input_mask = input_mask.index_select(0, seqs // max_num_edges)
     if extra_mask is not None:  # [N*F, L] bool, per sequence; special-token columns are never masked
         extra_mask = torch.cat([torch.zeros((extra_mask.size(0), num_token)).type_as(extra_mask), extra_mask], dim=1)
+        if seqs is not None:
+            extra_mask = extra_mask.index_select(0, seqs)
 
-    for step in range(T - 1):
+    for step in range(n_steps):
         target = predicts.unsqueeze(-1).repeat(1, 1, num_model)
         tgt = torch.gather(memory, 0, target)
         pointer = run_decoder(tgt, memory, input_mask, pos_embed, query_pos_embed[: step + 1])
         pointer = F.linear(pointer, sd["project.weight"], sd["project.bias"])
         next_token, logit = select_next(memory, pointer, input_mask, extra_mask)
+        if path is not None:
+            next_token = path[:, step + 1].unsqueeze(0)
         if trace is not None:
             trace["logits"].append(logit.clone())
         predicts = torch.cat((predicts, next_token), dim=0)
         if trace is not None:
             trace["counts"].append(int((next_token >= num_token).sum()))
-        if stop_rule and torch.all(next_token < num_token):
+        if path is None and stop_rule and torch.all(next_token < num_token):
             break
 
     predicts = torch.cat(
         (predicts, torch.zeros(T - predicts.size(0), predicts.size(1)).type_as(predicts)), dim=0)
-    inputs["predict"] = predicts.transpose(0, 1).view(-1, max_num_edges, T)
+    inputs["predict"] = predicts.transpose(0, 1).view(-1, max_num_edges, T) if seqs is None else predicts.transpose(0, 1)
     return inputs
+
+
+def _forced_path(forced, steps, seqs, T, rows, device):
+    """Teacher forcing (tests only).  `forced`: a token path shaped like `predict` ([N, F, T] / [N, T], first column
+    included: anchors or SOS); the loop feeds these tokens instead of its argmax, runs exactly `steps` steps (default
+    T - 1) with no stop rule and records the masked logits of every step.  `seqs`: optional subset of the rows of the
+    flattened path.  Returns (path [rows', T] long on `device` or None, number of steps, seqs as a long tensor or None)."""
+    if forced is None:
+        if steps is not None or seqs is not None:
+            raise ValueError("steps / seqs need a forced path")
+        return None, T - 1, None
+    path = torch.as_tensor(forced).reshape(-1, T).to(device=device, dtype=torch.long)
+    if path.size(0) != rows:
+        raise ValueError("forced path has %d rows, the batch %d" % (path.size(0), rows))
+    n_steps = T - 1 if steps is None else int(steps)
+    if not 0 < n_steps <= T - 1:
+        raise ValueError("steps must lie in 1..%d, got %d" % (T - 1, n_steps))
+    if seqs is not None:
+        seqs = torch.as_tensor(seqs, dtype=torch.long).reshape(-1).to(device)
+        path = path.index_select(0, seqs)
+    return path, n_steps, seqs
 
 
 @torch.no_grad()
 def seq2seq_forward_eval(sd, inputs, num_head=8, label_seq_length=None, token_sos=1, token_eos=3,
-                         trace=None, extra_mask=None, normalize_before=True, activation="relu"):
-    """SurfaceFormer.forward_eval (reference model.py:169-219); `normalize_before` / `activation` as above (model.py:14-18)."""
+                         trace=None, extra_mask=None, normalize_before=True, activation="relu", forced=None, steps=None,
+                         seqs=None):
+    """SurfaceFormer.forward_eval (reference model.py:169-219); `normalize_before` / `activation` as above (model.py:14-18).
+    `forced` / `steps` / `seqs` (tests only): teacher forcing as in `parallel_forward_eval`, with no EOS stop; `seqs` selects
+    wireframes (one sequence each)."""
     num_model, n_enc, n_dec, num_token = _dims(sd)
     run_encoder, run_decoder = _stacks(sd, num_head, n_enc, n_dec, normalize_before, activation)
     inp, input_mask, label = inputs["input"], inputs["input_mask"], inputs["label"]
@@ -338,18 +379,29 @@ def seq2seq_forward_eval(sd, inputs, num_head=8, label_seq_length=None, token_so
         trace["memory"] = memory.transpose(0, 1).clone()
         trace["logits"] = []
 
-    predicts = torch.full((1, batch_size), token_sos, dtype=torch.long)
+    predicts = torch.full((1, batch_size), token_sos, dtype=torch.long, device=memory.device)
+    path, n_steps, seqs = _forced_path(forced, steps, seqs, T, batch_size, memory.device)
+    if path is not None:
+        predicts = path[:, :1].transpose(0, 1)
+        if seqs is not None:
+            memory = memory.index_select(1, seqs)
+            input_mask = input_mask.index_select(0, seqs)
+            extra_mask = extra_mask.index_select(0, seqs) if extra_mask is not None else None
     eos_found = 0
     pointer = None
-    for step in range(T - 1):
+    for step in range(n_steps):
         target = predicts.unsqueeze(-1).repeat(1, 1, num_model)
         tgt = torch.gather(memory, 0, target)
         pointer = run_decoder(tgt, memory, input_mask, pos_embed, query_pos_embed[: step + 1])
         pointer = F.linear(pointer, sd["project.weight"], sd["project.bias"])
         next_token, logit = select_next(memory, pointer, input_mask, extra_mask)
+        if path is not None:
+            next_token = path[:, step + 1].unsqueeze(0)
         if trace is not None:
             trace["logits"].append(logit.clone())
         predicts = torch.cat((predicts, next_token), dim=0)
+        if path is not None:
+            continue
         eos_found += next_token.eq(token_eos).sum().item()
         if eos_found == batch_size:
             break

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import batch_to, build_model, case_weights_and_batch, golden_names, load_golden, token_ns
+from oracle.golden_cases import FULL as FULL_DIMS
 
 pytestmark = pytest.mark.gpu
 
@@ -1057,27 +1058,165 @@ def test_cli_single_sequence_model_batched_run_writes_the_one_sample_files(hip_l
     assert short == [1, 2, 3]
 
 
-@pytest.mark.parametrize("name", ["par_small_gain4", "par_full_n40_gain4", "par_full_n40_default"])
-def test_error_against_fp64_truth_is_fp32_class(hip_lib, name):
-    """Whose logits are closer to exact arithmetic?  The oracle restated in float64 is the truth; the
-    HIP path's first-step logits must be no further from it than a small multiple of the distance of
-    the reference's own fp32 CPU logits (both are fp32 evaluations with different summation orders)."""
+# ---- every row, every step against fp64 truth ------------------------------------------------------------------------------------
+# The goldens store the logits of a few rows only; every other row is held to its tokens alone.  Here the oracle runs in float64
+# on the GPU, teacher-forced along the HIP's own tokens (oracle/refpath.py: forced=), so that every live logit of every row at
+# every executed step has an exact-arithmetic counterpart, and oracle/truth.py holds the trace to
+#   (a) |hip - truth| <= tol of the step (FROZEN_FRACTION x tol for the E = 512 models), and
+#   (b) |hip - truth| <= factor x e_ref(s) + 1e-6 x scale_s, e_ref(s) = the reference's own fp32 error at step s: over the golden's
+#       stored rows whose prefix equals the HIP's, or (fresh case) over 16 rows of a teacher-forced fp32 oracle run on the host.
+TRUTH_GOLDENS = ["par_small_gain4", "par_full_n40_gain4", "par_full_n40_default", "par_small_ragged300", "par_full_B256_default",
+                 "par_full_B256_gain4", "par_full_C4x256_gain4", "par_full_E1024_gain4", "par_full_E512_T38_gain4",
+                 "par_full_E1024_T38_gain4", "fresh_full_ragged5"]
+# a fresh full-width ragged batch: dedup width buckets, 64-row tile tails and a one-edge wireframe at E = 512
+TRUTH_FRESH = {"fresh_full_ragged5": dict(kind="parallel", model=dict(FULL_DIMS, L=256, seq_len=10), recipe="gain4", wseed=78,
+                                          n_edges=[255, 1, 64, 129, 200], seeds=[90, 91, 92, 93, 94])}
+TRUTH_FORMS = {"package default": {}, "f32 MFMA only": dict(x3_min_rows=0), "fp16x2 from 1 row": dict(x3_min_rows=1, split_kind="fp16x2")}
+TRUTH_REF_FACTOR = 4.0
+TRUTH_ROW_EXCEPTIONS = {
+    # name: {row: (tol multiple, ref factor)} -- single named rows; every other row of the golden keeps 1 x tol and 4 x e_ref.
+    # par_small_ragged300, row 141 (wireframe 0, anchor 141): 1.29 tol / 6.96 e_ref at step 1, in every engine form (the
+    # encoder output is bit-equal across them).  Traced in profiles/fp64_truth_ragged300_row141.txt (tools/truth_row_probe.py):
+    # the excess is in the encoder output's row 141 (relative error 1.06e-5, the largest of the batch; median 8.9e-7); an fp64
+    # decoder fed the HIP's encoder output is 1.09 tol there, the HIP decoder adds 0.2; no tile position stands out (position 13
+    # of the 64-row tiles: 1.29, every other position <= 0.28).  The reference's own fp32 arithmetic has the mirror image:
+    # 1.36 tol at row 18 (step 2), where the HIP is 0.24, and 0.15 at row 141; apart from that one row each is <= 0.53.  Pinned
+    # by tests/test_oracle_forced.py against the HIP rows stored in tests/golden/par_small_ragged300_hip_rows.npz.
+    "par_small_ragged300": {141: (1.4, 7.0)},
+}
+TRUTH_CHUNK = 256           # sequences per oracle call: bounds the repeated memory (S x 256 x E fp64) and its K|V re-projections
+_TRUTH_CACHE = {}           # name -> {(wireframe, token path) -> fp64 logits [steps, S]}: the forms mostly decode the same paths
+
+
+def _truth_case(name):
+    if name in TRUTH_FRESH:
+        return dict(TRUTH_FRESH[name], name=name), None
+    return load_golden(name)
+
+
+def _truth_along(name, case, sd, batch, hip):
+    """fp64 logits [steps, B, S] of the oracle teacher-forced along hip['predict'], on the GPU, in chunks of TRUTH_CHUNK
+    sequences; rows with the same wireframe and token path (padding anchors) are evaluated once.  Returns (truth, seconds, peak
+    bytes of the oracle's own allocations)."""
     from oracle import refpath
-    case, z = load_golden(name)
+    import time
+    pred, steps = hip["predict"], hip["steps"]
+    B, T = pred.shape
+    F = max(int(n) for n in batch["num_input"])
+    keys = np.concatenate([(np.arange(B) // F)[:, None], pred[:, : steps + 1]], axis=1)
+    uniq, first, inv = np.unique(keys, axis=0, return_index=True, return_inverse=True)
+    cache = _TRUTH_CACHE.setdefault(name, {})
+    for other in [k for k in _TRUTH_CACHE if k != name]:
+        del _TRUTH_CACHE[other]
+    todo = [i for i in range(len(uniq)) if uniq[i].tobytes() not in cache]
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    if todo:
+        sd64 = {k: (v.to("cuda", torch.float64) if v.is_floating_point() else v.to("cuda")) for k, v in sd.items()}
+        b64 = {k: (v.to("cuda", torch.float64 if v.is_floating_point() else v.dtype) if torch.is_tensor(v) else v)
+               for k, v in batch.items()}
+        forced = torch.from_numpy(pred).to("cuda")
+        for c in range(0, len(todo), TRUTH_CHUNK):
+            part = [todo[i] for i in range(c, min(c + TRUTH_CHUNK, len(todo)))]
+            rows = first[part]
+            tr = {}
+            refpath.parallel_forward_eval(sd64, dict(b64), num_head=case["model"]["H"], trace=tr, forced=forced, steps=steps,
+                                          seqs=torch.from_numpy(rows).to("cuda"), num_anchors=F)
+            got = torch.stack(tr["logits"], dim=1).cpu().numpy()                 # [rows, steps, S]
+            for j, i in enumerate(part):
+                cache[uniq[i].tobytes()] = got[j]
+        del sd64, b64, forced
+    torch.cuda.synchronize()
+    secs, peak = time.perf_counter() - t0, torch.cuda.max_memory_allocated() - base
+    per_key = np.stack([cache[u.tobytes()] for u in uniq])                      # [unique, steps, S]
+    return per_key[inv.reshape(-1)].transpose(1, 0, 2), secs, peak
+
+
+def _e_ref(name, case, z, sd, batch, hip, truth):
+    """The reference's own fp32 error against the truth, per step (NaN where no row of the reference's is comparable)."""
+    steps = hip["steps"]
+    e = np.full(steps, np.nan)
+    pred = hip["predict"]
+    if z is not None:
+        gold = z["predict"].reshape(pred.shape)
+        for s in range(min(steps, int(z["steps"]))):
+            for ri, b in enumerate(z["logit_rows"]):
+                if np.array_equal(gold[b, : s + 1], pred[b, : s + 1]):
+                    ref, t = z["logits"][s, ri], truth[s, b]
+                    live = t > np.finfo(np.float64).min
+                    e[s] = np.fmax(e[s], np.abs(ref.astype(np.float64) - t)[live].max())
+        return e
+    from oracle import refpath
+    rows = np.unique(np.linspace(0, pred.shape[0] - 1, 16).round().astype(np.int64))
+    tr = {}
+    refpath.parallel_forward_eval(sd, dict(batch), num_head=case["model"]["H"], trace=tr, forced=torch.from_numpy(pred),
+                                  steps=steps, seqs=torch.from_numpy(rows), num_anchors=max(int(n) for n in batch["num_input"]))
+    ref = torch.stack(tr["logits"]).numpy()                                      # [steps, 16, S] fp32 on the host
+    t = truth[:, rows]
+    live = t > np.finfo(np.float64).min
+    return np.where(live, np.abs(ref.astype(np.float64) - t), 0.0).max(axis=(1, 2))
+
+
+def _truth_params():
+    out = []
+    for name in TRUTH_GOLDENS:
+        out += [(name, "package default"), (name, "f32 MFMA only")]
+        if name == "par_full_B256_gain4":
+            out.append((name, "fp16x2 from 1 row"))
+    return out
+
+
+@pytest.mark.parametrize("name,form", _truth_params())
+def test_error_against_fp64_truth_is_fp32_class(hip_lib, name, form):
+    """Whose logits are closer to exact arithmetic?  The oracle restated in float64 and teacher-forced along the HIP's tokens is
+    the truth; every live logit of every row at every step must be within the bar of the step, and no further from the truth
+    than a small multiple of the distance of the reference's own fp32 logits (both are fp32 evaluations with different
+    summation orders).  The HIP's argmax / best / second / steps must be consistent with its logits, and its tokens must be
+    the truth's wherever the truth's margin is decisive."""
+    from oracle import truth as TR
+    case, z = _truth_case(name)
     sd, batch = case_weights_and_batch(case)
-    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
-    b64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in batch.items()}
-    tr64 = {}
-    refpath.parallel_forward_eval(sd64, b64, num_head=case["model"]["H"], trace=tr64)
-    truth = tr64["logits"][0].numpy()                       # step 0: identical prefixes by construction
-    rows = z["logit_rows"]
-    ref32 = z["logits"][0]                                   # reference fp32 (golden), selected rows
     model = build_model(case, sd, "cuda")
+    for k, v in TRUTH_FORMS[form].items():
+        setattr(model, k, v)
     out = run_traced(model, case, batch_to(batch, "cuda"))
-    hip = out["logits"][0].cpu().numpy()[rows]
-    live = ref32 > np.finfo(np.float32).min
-    err_ref = np.abs(ref32.astype(np.float64) - truth[rows])[live].max()
-    err_hip = np.abs(hip.astype(np.float64) - truth[rows])[live].max()
-    scale = np.abs(truth[rows][live]).max()
-    print(name, "max |logit| %.1f  err(reference fp32) %.3g  err(HIP) %.3g" % (scale, err_ref, err_hip))
-    assert err_hip <= 4.0 * err_ref + 1e-6 * scale
+    T = case["model"]["seq_len"]
+    hip = dict(predict=out["predict"].cpu().numpy().reshape(-1, T), steps=int(out["steps"]), logits=out["logits"].cpu().numpy(),
+               best=out["best"].cpu().numpy(), second=out["second"].cpu().numpy())
+    truth, secs, peak = _truth_along(name, case, sd, batch, hip)
+    frac = FROZEN_FRACTION if "_full_" in name else 1.0
+    tol = np.array([frac * _tol(truth[s]) for s in range(hip["steps"])])
+    e_ref = _e_ref(name, case, z, sd, batch, hip, truth)
+    assert np.isfinite(e_ref[0]), "no reference row to measure the fp32 class at step 0"
+    factor = TRUTH_REF_FACTOR
+    first = TR.anchor_column("parallel", batch["num_input"], max(int(n) for n in batch["num_input"]))
+    st = TR.check_trace_against_truth(hip, truth, tol, e_ref=e_ref, ref_factor=factor, first_column=first,
+                                      row_exceptions=TRUTH_ROW_EXCEPTIONS.get(name))
+    if name == "par_small_ragged300":     # the stored HIP rows the CPU test reads are still what the HIP computes
+        fx = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "par_small_ragged300_hip_rows.npz"))
+        assert np.array_equal(hip["predict"][fx["rows"]], fx["predict"])
+        assert np.abs(hip["logits"][: hip["steps"]][:, fx["rows"]] - fx["logits"]).max(axis=(0, 2)).max() <= 0.05 * tol.min()
+    print(name, form, st, "oracle %.1f s, peak %.2f GB" % (secs, peak / 1e9))
+    path = os.environ.get("FF_PARITY_MARGINS")
+    if path:
+        with open(path, "a") as f:
+            f.write("%-26s %-18s worst_over_tol %.3f x %.1f at step %d row %d  worst_over_e_ref %.2f at step %d row %d (factor %.1f, "
+                    "%d of %d steps)  truth_decisive_tokens_equal %d  near_ties %d  fp64_oracle %.1f s peak %.2f GB\n" % (
+                        name, form, st["worst_over_tol"], frac, st["worst_at"][0], st["worst_at"][1], st["worst_over_ref"],
+                        st["worst_ref_at"][0], st["worst_ref_at"][1], factor, int(np.isfinite(e_ref).sum()), hip["steps"],
+                        st["tokens_checked"], st["tokens_skipped"], secs, peak / 1e9))
+    if name == "par_full_B256_gain4" and form == "package default":
+        # the gap this closes: one live logit of an unstored row (37), step 20, moved by 1e-4 of the logit scale (4 x the bar,
+        # the lowest live logit so that the row's argmax / best / second stay): the golden comparison cannot see it, this can
+        s, b = 20, 37
+        assert b not in z["logit_rows"] and s < hip["steps"]
+        row = hip["logits"][s, b]
+        k = int(np.argmin(np.where(row > np.finfo(np.float32).min, row, np.inf)))
+        scale = _tol(truth[s]) / LOGIT_TOL * LOGIT_SCALE
+        bumped = out["logits"].clone()
+        bumped[s, b, k] += 1e-4 * scale
+        compare_with_golden(case, z, dict(out, logits=bumped))
+        with pytest.raises(AssertionError, match=r"bar \(a\): step 20 row 37"):
+            TR.check_trace_against_truth(dict(hip, logits=bumped.cpu().numpy()), truth, tol, e_ref=e_ref, ref_factor=factor)
