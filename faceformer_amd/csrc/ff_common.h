@@ -107,6 +107,12 @@ struct ff_pointer_sync {
   float* next_stats;  // [B, E/32, 2] or null: (mean, M2) per 32-column segment of the rows written to next_rows -- the
                       // LayerNorm statistics the folded layer-0 projection of the NEXT step consumes (ff_gemm_f32_ln)
   int logits_ready;   // 1: `logits` already holds the raw dot products (the engine's folded project + pointer GEMM): p is not read
+  // FF_RETIRE_FINISHED: launch row b decodes sequence slot[b] (an index into next_tok / best / second / extra_mask rows; logits,
+  // next_rows and next_stats stay in launch order), fin[seq] its finish position (> fin_j: none yet).  count_ge counts the
+  // unfinished sequences only; a token in [term_lo, term_hi) records fin[seq] = fin_j, the position this launch writes.
+  const int* slot;
+  int* fin;
+  int fin_j, term_lo, term_hi;
 };
 int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, int E, const unsigned char* mask,
                            const int* kv_len, const unsigned char* extra_mask, int ldextra, int B, int seqs_per_group,

@@ -683,7 +683,13 @@ struct PointerArgs {
   int* host_slot;   // host-mapped pinned int: the last sequence to arrive stores the launch's counter there (system scope)
   int host_which;   // 0: count_ge, 1: count_eq
   float* next_stats;  // [B, E/32, 2] or null: LayerNorm segment statistics of the appended rows (E % 32 == 0)
+  // FF_RETIRE_FINISHED (null / 0 otherwise): launch row b is sequence slot[b] of next_tok / best / second / extra; the logits,
+  // next_rows and next_stats rows stay in launch order.  fin[slot[b]] is the sequence's finish position (fin_j + 1.. = none yet):
+  // count_ge counts unfinished sequences only, and a token in [term_lo, term_hi) sets fin to fin_j (the position written).
+  const int* slot;
+  int* fin; int fin_j, term_lo, term_hi;
 };
+__device__ __forceinline__ int ff_pointer_seq(const PointerArgs& a, int b) { return a.slot ? a.slot[b] : b; }
 
 // Stop-rule counters of the (up to four) sequences a 256-thread block has finished, by ONE thread of the block: one atomic per
 // counter and block instead of one per sequence (4096 sequences of a 16-wireframe micro-batch adding to one address, plus the
@@ -695,6 +701,13 @@ __device__ __forceinline__ void ff_pointer_count_block(const PointerArgs& a, int
   int nge = 0, neq = 0;
   for (int i = 0; i < nvalid; ++i) {
     const int idx = toks[i];
+    if (a.fin) {
+      // (a sequence lives in one slot of one micro-batch: only this thread touches its fin entry during the launch)
+      int* fp = a.fin + ff_pointer_seq(a, b0 + i);
+      const int f = __hip_atomic_load(fp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (f < a.fin_j) continue;   // finished before this position: neither counted nor re-recorded
+      if (idx >= a.term_lo && idx < a.term_hi) __hip_atomic_store(fp, a.fin_j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     if (a.count_ge && idx >= a.ge_bound) ++nge;
     if (a.count_eq && idx == a.eq_value) {
       bool first = true;
@@ -722,7 +735,8 @@ __device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b
   int kv = a.S;
   if (a.kv_len) { const int k = ff_ldw(a.kv_len + w); kv = k < kv ? k : kv; }
   const unsigned char* mrow = a.mask ? a.mask + (size_t)w * a.S : nullptr;
-  const unsigned char* erow = a.extra ? a.extra + (size_t)b * a.ldextra : nullptr;
+  const int seq = ff_pointer_seq(a, b);
+  const unsigned char* erow = a.extra ? a.extra + (size_t)seq * a.ldextra : nullptr;
   float* lrow = a.logits + (size_t)b * a.ldlogits;
   const float FILL = -3.402823466e+38f;  // -FLT_MAX = torch.finfo(float32).min (reference utils.py:16-20)
   float b1 = -INFINITY, b2 = -INFINITY;
@@ -747,9 +761,9 @@ __device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b
   }
   if (i1 == 0x7fffffff) { i1 = 0; b1 = FILL; }
   if (lane == 0) {
-    ff_st4i(a.next_tok + b, i1);
-    if (a.best) ff_st4(a.best + b, b1);
-    if (a.second) ff_st4(a.second + b, b2);
+    ff_st4i(a.next_tok + seq, i1);
+    if (a.best) ff_st4(a.best + seq, b1);
+    if (a.second) ff_st4(a.second + seq, b2);
   }
   if (a.next_rows) {
     const float* src = a.memory + ((size_t)w * a.S + i1) * a.E;

@@ -13,6 +13,11 @@
 //                               the active rows of step t are the first t*Bc rows: every GEMM of
 //                               the step is one dense [t*Bc, K] x [K, N] product)
 // Sequences b of a micro-batch belong to wireframe w0 + b / F; nothing is replicated per sequence.
+//
+// FF_RETIRE_FINISHED (opt-in, parallel variant): a micro-batch decodes a SLOT set -- slot i of the chunk holds sequence
+// slot[i] (a chunk-local index of the plan above; tokens, traces, extra-mask rows and finish positions stay in that original
+// order) -- and every sync_every steps the host drops the finished sequences from it (compact_chunks below).  The slots of a
+// chunk keep the w = i / Fc structure with a smaller Fc, so attention, masks and kv_len are addressed as before.
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -44,9 +49,14 @@ size_t bump_bytes(size_t count, size_t elem) { return ff_align_up(count * elem, 
 // ---- small kernels -----------------------------------------------------------------------------
 // Start tokens of one micro-batch: sequence i belongs to wireframe i / Fc of the chunk and is its compact
 // sequence f = f0 + i % Fc.
+// With a slot map (FF_RETIRE_FINISHED) it also writes the start token of slot s's sequence to tok_slot[s], s < nslots.
 __global__ void init_tokens_kernel(int* tok, int Bc, int Fc, int f0, const int* num_input, int variant,
-                                   int pad_tok, int sos) {
+                                   int pad_tok, int sos, const int* slot = nullptr, int* tok_slot = nullptr, int nslots = 0) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot && i < nslots) {
+    const int k = slot[i], f = f0 + k % Fc;
+    tok_slot[i] = f < num_input[k / Fc] ? f : pad_tok;
+  }
   if (i >= Bc) return;
   if (variant == FF_PARALLEL) {
     // anchors = arange(F) per wireframe, WITHOUT the +num_token offset (reference quirk C-3,
@@ -84,7 +94,8 @@ __global__ void steps_kernel(const int* __restrict__ cnt_ge, const int* __restri
 // it writes the rows whose compact sequence lives in [f0, f0 + Fc) of its wireframes.
 __global__ void finalize_chunk_kernel(const int* __restrict__ tok_all, int Btot, int T, const int* __restrict__ steps_p,
                                       const int* __restrict__ num_input, int dedup, int F, int w0, int nw, int Fc,
-                                      int f0, int b0, int64_t* __restrict__ predict, int* __restrict__ seq_of_row) {
+                                      int f0, int b0, int64_t* __restrict__ predict, int* __restrict__ seq_of_row,
+                                      const int* __restrict__ fin) {
   const int steps = *steps_p;
   const size_t total = (size_t)nw * F * T;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -95,7 +106,8 @@ __global__ void finalize_chunk_kernel(const int* __restrict__ tok_all, int Btot,
     if (f < f0 || f >= f0 + Fc) continue;
     const int seq = b0 + wl * Fc + (f - f0);
     const size_t row = (size_t)(w0 + wl) * F + fo;
-    predict[row * T + j] = (j <= steps) ? (int64_t)tok_all[(size_t)j * Btot + seq] : (int64_t)0;
+    const int last = fin ? (fin[seq] < steps ? fin[seq] : steps) : steps;   // FF_RETIRE_FINISHED: up to the finish position
+    predict[row * T + j] = (j <= last) ? (int64_t)tok_all[(size_t)j * Btot + seq] : (int64_t)0;
     if (seq_of_row && j == 0) seq_of_row[row] = seq;
   }
 }
@@ -163,6 +175,7 @@ struct DecodeBuffers {
   int *seen;              // [Btot] FF_STOP_EACH_EOS: the sequence has produced an EOS
   int *cnt_tot;           // [T] per-step totals (steps_kernel)
   int *steps_dev;
+  int *fin, *slot_all, *perm_all;   // FF_RETIRE_FINISHED: finish positions [Btot] (when not host-mapped), slot maps [Btot]
 };
 
 // A micro-batch is a contiguous range [b0, b0 + Bc) of the COMPACT sequence index: nw >= 1 consecutive
@@ -170,6 +183,8 @@ struct DecodeBuffers {
 // padding-anchor de-duplication the compact width of every wireframe is F and b = w*F + f as in the reference.
 struct Chunk {
   int w0, nw, Fc, f0, b0, Bc, sid;
+  int Fl, Bl;    // FF_RETIRE_FINISHED: slots per wireframe / in all of the chunk now (Bl = nw * Fl <= Bc; 0: nothing left)
+  int *slot, *perm;   // ... device [Bc]: chunk-local sequence of every slot; the compaction's gather indices
   float* x0;     // [T, Bc, E]
   float* qkv0;   // [T, Bc, 3E] or null
   float* x0stat; // [Bc, E/32, 2] statistics of the rows the last pointer launch appended to x0, or null
@@ -178,6 +193,8 @@ struct Chunk {
 
 // Compact width of wireframe w: its num_input real anchors plus ONE padding-anchor sequence when it has fewer
 // than F (the reference decodes F - num_input identical copies of it, model_para.py:204-205).
+inline bool retiring(const ff_decode_params* p) { return p->variant == FF_PARALLEL && (p->flags & FF_RETIRE_FINISHED); }
+
 inline int compact_width(const ff_decode_params* p, const int* num_input_host, int w) {
   if (p->variant != FF_PARALLEL || !(p->flags & FF_DEDUP_PAD_ANCHORS) || !num_input_host) return p->F;
   int n = num_input_host[w];
@@ -219,6 +236,7 @@ void plan_chunks(const ff_decode_params* p, const int* num_input_host, int ns, s
       c.b0 = b0; c.Bc = nw * c.Fc;
       c.sid = (int)(out ? out->size() % (size_t)ns : 0);
       c.x0 = nullptr; c.qkv0 = nullptr; c.x0stat = nullptr; c.pg = nullptr; c.pc = nullptr;
+      c.Fl = c.Fc; c.Bl = c.Bc; c.slot = nullptr; c.perm = nullptr;
       b0 += c.Bc;
       mx = c.Bc > mx ? c.Bc : mx;
       ++nc;
@@ -302,6 +320,11 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
   b.seen = bp.take<int>(Btot);
   b.cnt_tot = bp.take<int>(T);
   b.steps_dev = bp.take<int>(4);
+  if (retiring(p)) {
+    b.fin = bp.take<int>(Btot);
+    b.slot_all = bp.take<int>(Btot);
+    b.perm_all = bp.take<int>(Btot);
+  }
   if (out) *out = b;
   return bp.off;
 }
@@ -553,6 +576,8 @@ struct StreamPool {
   hipEvent_t chk_ev[FF_MAX_STREAMS];      // stop-rule check: per-stream progress marks
   int* hpin;                                // host-mapped pinned counters [step][micro-batch], written by the pointer launches
   int* hpin_dev;                            // ... the device-visible address of the same memory
+  int* stage;                               // FF_RETIRE_FINISHED: pinned staging of the slot-map uploads (grown on demand)
+  size_t stage_cap;
   int created;
   bool events;
 };
@@ -696,6 +721,14 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
   FF_CHECK_ARG(T - 1 <= m->qpos_len, "ff_decode: T-1=%d exceeds the query position table (%d rows)", T - 1, m->qpos_len);
   FF_CHECK_ARG(p->variant != FF_PARALLEL || F <= S, "ff_decode: F=%d anchors exceed S=%d", F, S);
   FF_CHECK_ARG(!(p->flags & FF_RETURN_POINTER) || pointer_out, "ff_decode: pointer_out required");
+  const bool retire = retiring(p);
+  if (p->flags & FF_RETIRE_FINISHED) {
+    FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode: FF_RETIRE_FINISHED is a parallel-variant option");
+    FF_CHECK_ARG(!(p->flags & (FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn,
+                 "ff_decode: FF_RETIRE_FINISHED excludes FF_RETURN_POINTER, FF_NO_STOP and a stop_fn");
+    FF_CHECK_ARG(num_input_host, "ff_decode: FF_RETIRE_FINISHED needs num_input_host");
+    FF_CHECK_ARG(p->term_lo < p->term_hi, "ff_decode: empty terminator range [%d, %d)", p->term_lo, p->term_hi);
+  }
   // every padding-anchor sequence has its own row of an extra mask: no de-duplication then
   ff_decode_params prm_local = *p;
   if (extra_mask) prm_local.flags &= ~FF_DEDUP_PAD_ANCHORS;
@@ -721,6 +754,7 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
     const bool one = c.nw == 1 && buf.pg_all != nullptr;
     c.pg = one ? buf.pg_all + ci * (size_t)(p->L + m->num_token) * E : nullptr;
     c.pc = one ? buf.pc_all + ci * (size_t)((p->L + m->num_token + 3) & ~3) : nullptr;
+    if (retire) { c.slot = buf.slot_all + c.b0; c.perm = buf.perm_all + c.b0; }
   }
   const int ns = ns_req < (int)chunks.size() ? ns_req : (int)chunks.size();
   const bool forked = ns > 1;
@@ -734,6 +768,56 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
   FF_CHECK_ARG(busy, "ff_decode: no current device");
   std::lock_guard<std::mutex> one_decode_per_device(*busy);
   FF_RETURN_IF(pool_get(forked ? ns : 0, &pool));   // (also owns the pinned counter buffer / events of the stop check)
+
+  // ---- FF_RETIRE_FINISHED: the initial slot sets (host side) -------------------------------------------------------------------
+  // fin[seq] = 0 for the sequences whose start token already ends them (the padding anchors and anchors term_lo.. of the model:
+  // reference quirk C-3) and for the surplus padding copies of narrow wireframes; T (none yet) for the others.  Every chunk starts
+  // with its live sequences only: per wireframe the live ones in order, then finished ones of the same wireframe up to the
+  // chunk's widest live count.
+  std::vector<int> hfin;                       // host copy of the finish positions (pageable; filled from fin_host at check points)
+  std::vector<std::vector<int>> hslot;         // per chunk: the chunk-local sequence of every slot
+  int* fin_host = nullptr;                     // host address of the finish positions when they are host-mapped, else null
+  int* fin_dev = buf.fin;
+  const bool lagged_ = (size_t)T * (size_t)nch <= (size_t)kn.pinned;
+  if (retire) {
+    if (lagged_ && (size_t)T * nch + (size_t)Btot <= (size_t)kn.pinned) {
+      fin_host = pool->hpin + (size_t)T * nch;
+      fin_dev = pool->hpin_dev + (size_t)T * nch;
+    }
+    if (pool->stage_cap < 2 * (size_t)Btot) {   // (no upload of an earlier decode is in flight: it synchronised before returning)
+      if (pool->stage) FF_CHECK_HIP(hipHostFree(pool->stage));
+      pool->stage = nullptr; pool->stage_cap = 0;
+      FF_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&pool->stage), sizeof(int) * 2 * (size_t)Btot, hipHostMallocDefault));
+      pool->stage_cap = 2 * (size_t)Btot;
+    }
+    hfin.assign((size_t)Btot, T);
+    hslot.resize(chunks.size());
+    for (Chunk& c : chunks) {
+      std::vector<std::vector<int>> live((size_t)c.nw), dead((size_t)c.nw);
+      int fl = 0;
+      for (int wl = 0; wl < c.nw; ++wl) {
+        const int w = c.w0 + wl, n = num_input_host[w], cw = compact_width(p, num_input_host, w);
+        for (int f = 0; f < c.Fc; ++f) {
+          const int fc = c.f0 + f, k = wl * c.Fc + f;
+          const int start = fc < n ? fc : m->num_token - 1;
+          const bool dead_now = fc >= cw || (start >= p->term_lo && start < p->term_hi);
+          if (dead_now) hfin[(size_t)c.b0 + k] = 0;
+          (dead_now ? dead : live)[(size_t)wl].push_back(k);
+        }
+        fl = (int)live[(size_t)wl].size() > fl ? (int)live[(size_t)wl].size() : fl;
+      }
+      std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
+      for (int wl = 0; wl < c.nw; ++wl) {
+        std::vector<int> order = live[(size_t)wl];
+        order.insert(order.end(), dead[(size_t)wl].begin(), dead[(size_t)wl].end());
+        hs.insert(hs.end(), order.begin(), order.begin() + fl);
+      }
+      c.Fl = fl; c.Bl = c.nw * fl;
+    }
+    if (lagged_) memset(pool->hpin, 0, sizeof(int) * (size_t)T * nch);   // (counters of launches a finished chunk never makes)
+    if (fin_host) memcpy(fin_host, hfin.data(), sizeof(int) * (size_t)Btot);
+  }
+  std::vector<int> slots_per_step;
   if (forked)
     for (int s = 0; s < ns; ++s) sts[s] = pool->side[s];
   auto sync_all = [&]() -> int {
@@ -759,6 +843,19 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
     // cnt_ge | cnt_eq | arrive | seen are consecutive in the workspace (layout_decode): ONE fill
     FF_CHECK_HIP(hipMemsetAsync(buf.cnt_ge, 0, (size_t)(reinterpret_cast<char*>(buf.seen + Btot) - reinterpret_cast<char*>(buf.cnt_ge)),
                                 main_st));
+    if (retire) {   // initial slot maps (and finish positions when they live in the workspace), from the pinned staging area
+      int* st_slot = pool->stage;
+      int* st_fin = pool->stage + Btot;
+      for (const Chunk& c : chunks) {
+        const std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
+        if (!hs.empty()) memcpy(st_slot + c.b0, hs.data(), sizeof(int) * hs.size());
+      }
+      FF_CHECK_HIP(hipMemcpyAsync(buf.slot_all, st_slot, sizeof(int) * (size_t)Btot, hipMemcpyHostToDevice, main_st));
+      if (!fin_host) {
+        memcpy(st_fin, hfin.data(), sizeof(int) * (size_t)Btot);
+        FF_CHECK_HIP(hipMemcpyAsync(buf.fin, st_fin, sizeof(int) * (size_t)Btot, hipMemcpyHostToDevice, main_st));
+      }
+    }
     if (forked) {  // fork
       FF_CHECK_HIP(hipEventRecord(pool->fork_ev, main_st));
       for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipStreamWaitEvent(sts[s], pool->fork_ev, 0));
@@ -782,12 +879,14 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
     }
     // start tokens (anchors / SOS) and first decoder input rows of every micro-batch
     for (const Chunk& c : chunks) {
+      // (retirement: the start tokens of the slots go to the chunk's perm area, free until its first compaction)
       hipLaunchKernelGGL(init_tokens_kernel, dim3(ff_cdiv(c.Bc, 256)), dim3(256), 0, sts[c.sid], buf.tok_all + c.b0,
                          c.Bc, c.Fc, c.f0, num_input ? num_input + c.w0 : nullptr, p->variant, m->num_token - 1,
-                         p->tok_sos);
+                         p->tok_sos, c.slot, c.perm, c.slot ? c.Bl : 0);
       FF_CHECK_LAUNCH();
-      FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E,
-                                  sts[c.sid]));
+      if (c.Bl > 0)
+        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, c.slot ? c.perm : buf.tok_all + c.b0, c.Bl, c.Fl, c.x0, E,
+                                    sts[c.sid]));
     }
 
     // ---- greedy loop -----------------------------------------------------------------------------------
@@ -802,7 +901,7 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
     // 2 * sync_every - 1 steps late; those surplus steps are dropped by the finalize kernels (exact results).
     bool stopped = false;
     int pending_enq = 0;   // > 0: events covering steps [0, pending_enq) are in flight
-    const bool lagged = (size_t)T * (size_t)nch <= (size_t)kn.pinned;
+    const bool lagged = lagged_;
     std::vector<int> tot;
     auto host_totals = [&](const int* per_chunk, int n) -> const int* {   // [n][nch] -> per-step totals
       tot.assign((size_t)n, 0);
@@ -823,16 +922,22 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
     };
     auto enqueue_step = [&](int step) -> int {
       const int t = step + 1;
-      for (const Chunk& c : chunks) {
+      int nslots = 0;
+      for (const Chunk& c0 : chunks) {
+        if (c0.Bl == 0) continue;   // (retirement: nothing of this micro-batch is left)
+        nslots += c0.Bl;
+        Chunk c = c0;               // the slot set decoded now: Fc / Bc = the live widths (unchanged without retirement)
+        c.Fc = c0.Fl; c.Bc = c0.Bl;
         hipStream_t st = sts[c.sid];
         const Scratch& sc = buf.scr[c.sid];
         const size_t trow = (size_t)step * ((size_t)N * F) + c.b0;  // traces: step stride N*F (caller sizes them so)
-        const size_t slot = (size_t)step * nch + (size_t)(&c - chunks.data());
+        const size_t slot = (size_t)step * nch + (size_t)(&c0 - chunks.data());
         const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bc);
-        float* logits_dst = trace_logits ? trace_logits + trow * S : sc.logits;
+        // (retirement: the logits rows are in slot order; a traced step scatters them to the sequences' rows below)
+        float* logits_dst = (trace_logits && !retire) ? trace_logits + trow * S : sc.logits;
         ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, lagged ? buf.arrive + slot : nullptr,
                               lagged ? pool->hpin_dev + slot : nullptr, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
-                              folded_head ? 1 : 0};
+                              folded_head ? 1 : 0, c.slot, retire ? fin_dev + c.b0 : nullptr, t, p->term_lo, p->term_hi};
         auto pointer_head = [&]() -> int {
           return ff_pointer_argmax_sync(
               folded_head ? nullptr : sc.p, E, memory + (size_t)c.w0 * S * E, S, E, mask + (size_t)c.w0 * S, kv_len + c.w0,
@@ -840,11 +945,90 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
               buf.tok_all + (size_t)t * Btot + c.b0, trace_best ? trace_best + trow : nullptr,
               trace_second ? trace_second + trow : nullptr, logits_dst, S,
               c.x0 + (size_t)t * c.Bc * E, E, buf.cnt_ge + slot, m->num_token, buf.cnt_eq + slot, p->tok_eos,
-              (each_eos || lagged || c.x0stat || folded_head) ? &psync : nullptr, st);
+              (each_eos || lagged || c.x0stat || folded_head || retire) ? &psync : nullptr, st);
         };
         FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, mask, kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
         FF_RETURN_IF(pointer_head());
+        if (retire && trace_logits)
+          FF_RETURN_IF(ff_permute_rows(sc.logits, c.Bc, nullptr, trace_logits + trow * S, c0.Bc, c.slot, 1, c.Bc, S, st));
       }
+      slots_per_step.push_back(nslots);
+      return FF_OK;
+    };
+    // FF_RETIRE_FINISHED check point: sequences whose finish position is <= bound leave their micro-batch.  `bound` is a position
+    // whose step is already enqueued, and only finish positions <= bound are looked at (later ones may or may not be visible
+    // yet): the decision does not depend on timing.  A chunk is compacted when it loses at least retire_min_shrink of its slots.
+    // x0 (positions 0..enq), qkv0 (0..enq-1) and the appended rows' statistics are gathered into the stream's scratch in the new
+    // slot order and copied back; the maps come from the pinned staging area, whose previous uploads have completed (every check
+    // point first waits for events recorded behind them, or drains the streams).  Returns the number of live sequences left.
+    auto compact_chunks = [&](int bound, long* live_left) -> int {
+      *live_left = 0;
+      size_t soff = 0;
+      for (Chunk& c : chunks) {
+        if (c.Bl == 0) continue;
+        std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
+        std::vector<int> perm;
+        int fl = 0;
+        std::vector<std::vector<int>> live((size_t)c.nw), done((size_t)c.nw);
+        for (int wl = 0; wl < c.nw; ++wl) {
+          for (int k = 0; k < c.Fl; ++k) {
+            const int i = wl * c.Fl + k, f = hfin[(size_t)c.b0 + hs[(size_t)i]];
+            (f > bound ? live : done)[(size_t)wl].push_back(i);
+          }
+          *live_left += (long)live[(size_t)wl].size();
+          fl = (int)live[(size_t)wl].size() > fl ? (int)live[(size_t)wl].size() : fl;
+        }
+        const int shrink = c.Bl - c.nw * fl;
+        if (shrink == 0 || (double)shrink < (double)p->retire_min_shrink * c.Bl) continue;
+        for (int wl = 0; wl < c.nw; ++wl) {
+          std::vector<int> order = live[(size_t)wl];
+          order.insert(order.end(), done[(size_t)wl].begin(), done[(size_t)wl].end());
+          perm.insert(perm.end(), order.begin(), order.begin() + fl);
+        }
+        const int nb = c.nw * fl;
+        hipStream_t st = sts[c.sid];
+        if (nb > 0) {
+          int* sp = pool->stage + soff;
+          int* ss = sp + nb;
+          soff += 2 * (size_t)nb;
+          for (int i = 0; i < nb; ++i) { sp[i] = perm[(size_t)i]; ss[i] = hs[(size_t)perm[(size_t)i]]; }
+          FF_CHECK_HIP(hipMemcpyAsync(c.perm, sp, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, st));
+          const Scratch& sc = buf.scr[c.sid];
+          FF_RETURN_IF(ff_permute_rows(c.x0, c.Bl, c.perm, sc.x, nb, nullptr, enq + 1, nb, E, st));
+          FF_CHECK_HIP(hipMemcpyAsync(c.x0, sc.x, sizeof(float) * (size_t)(enq + 1) * nb * E, hipMemcpyDeviceToDevice, st));
+          if (c.qkv0) {
+            FF_RETURN_IF(ff_permute_rows(c.qkv0, c.Bl, c.perm, sc.qkv, nb, nullptr, enq, nb, 3 * E, st));
+            FF_CHECK_HIP(hipMemcpyAsync(c.qkv0, sc.qkv, sizeof(float) * (size_t)enq * nb * 3 * E, hipMemcpyDeviceToDevice, st));
+          }
+          if (c.x0stat) {
+            FF_RETURN_IF(ff_permute_rows(c.x0stat, c.Bl, c.perm, sc.y, nb, nullptr, 1, nb, E / 16, st));
+            FF_CHECK_HIP(hipMemcpyAsync(c.x0stat, sc.y, sizeof(float) * (size_t)nb * (E / 16), hipMemcpyDeviceToDevice, st));
+          }
+          // the new slot map: perm and slot are adjacent in the staging area, the device slot map is behind the gather above
+          FF_CHECK_HIP(hipMemcpyAsync(c.slot, ss, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, st));
+        }
+        std::vector<int> nhs((size_t)nb);
+        for (int i = 0; i < nb; ++i) nhs[(size_t)i] = hs[(size_t)perm[(size_t)i]];
+        hs.swap(nhs);
+        c.Fl = fl; c.Bl = nb;
+      }
+      return FF_OK;
+    };
+    // retirement at a check point: finish positions <= bound, read from host-mapped memory (behind the events just waited for)
+    // or -- when they live in the workspace -- after draining the streams (bound = enq - 1: step `bound` is enqueued either way)
+    auto retire_at = [&](int bound, bool drained) -> int {
+      if (fin_host) {
+        const volatile int* v = fin_host;
+        for (int i = 0; i < Btot; ++i) hfin[(size_t)i] = v[i];
+      } else {
+        if (!drained) FF_RETURN_IF(sync_all());
+        FF_CHECK_HIP(hipMemcpyAsync(hfin.data(), buf.fin, sizeof(int) * (size_t)Btot, hipMemcpyDeviceToHost, main_st));
+        FF_CHECK_HIP(hipStreamSynchronize(main_st));
+        bound = enq - 1;
+      }
+      long live = 0;
+      FF_RETURN_IF(compact_chunks(bound, &live));
+      if (live == 0) stopped = true;   // (the steps_kernel finds the step with no unfinished sequence among those enqueued)
       return FF_OK;
     };
     for (int step = 0; step < max_steps && !stopped;) {
@@ -856,6 +1040,7 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
           if (pending_enq > 0) {
             for (int s_ = 0; s_ < ns; ++s_) FF_CHECK_HIP(hipEventSynchronize(pool->chk_ev[s_]));
             stopped = eval_counts(host_totals(pool->hpin, pending_enq), pending_enq);
+            if (!stopped && retire) FF_RETURN_IF(retire_at(pending_enq, false));
             pending_enq = 0;
           }
           if (!stopped) {
@@ -874,12 +1059,16 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
                                         sizeof(int) * hcnt.size(), hipMemcpyDeviceToHost, main_st));
             FF_CHECK_HIP(hipStreamSynchronize(main_st));
             stopped = eval_counts(host_totals(hcnt.data(), n_eval), n_eval);
+            if (!stopped && retire) FF_RETURN_IF(retire_at(enq - 1, true));
           }
         }
       }
     }
     if (pending_enq > 0)   // the slots are reused by the next call
       for (int s_ = 0; s_ < ns; ++s_) FF_CHECK_HIP(hipEventSynchronize(pool->chk_ev[s_]));
+    if (p->slots_per_step) {
+      for (int s_ = 0; s_ < T - 1; ++s_) p->slots_per_step[s_] = s_ < (int)slots_per_step.size() ? slots_per_step[(size_t)s_] : 0;
+    }
     if (dbg_timing) {
       const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
       FF_RETURN_IF(sync_all());
@@ -914,7 +1103,8 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
       const long total = (long)c.nw * F * T;
       const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
       hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
-                         num_input, dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, predict, seq_of_row);
+                         num_input, dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, predict, seq_of_row,
+                         retire ? fin_dev : nullptr);
       FF_CHECK_LAUNCH();
     }
     int steps = 0;

@@ -31,7 +31,8 @@ __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane
   if (a.kv_len) { const int k = a.kv_len[w]; kv = k < kv ? k : kv; }
   const float* mem = a.memory + (size_t)w * a.S * a.E;
   const unsigned char* mrow = a.mask ? a.mask + (size_t)w * a.S : nullptr;
-  const unsigned char* erow = a.extra ? a.extra + (size_t)b * a.ldextra : nullptr;
+  const int seq = ff_pointer_seq(a, b);
+  const unsigned char* erow = a.extra ? a.extra + (size_t)seq * a.ldextra : nullptr;
 
   const float FILL = -FLT_MAX;  // torch.finfo(float32).min (reference utils.py:16-20)
   float best = -INFINITY, second = -INFINITY;
@@ -99,9 +100,9 @@ __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane
   }
   if (best == -INFINITY) { best = FILL; best_idx = 0; }  // S == 0 cannot happen; defensive
   if (lane == 0) {
-    a.next_tok[b] = best_idx;
-    if (a.best) a.best[b] = best;
-    if (a.second) a.second[b] = second;
+    a.next_tok[seq] = best_idx;
+    if (a.best) a.best[seq] = best;
+    if (a.second) a.second[seq] = second;
   }
   if (a.next_rows) {
     const float* src = mem + (size_t)best_idx * a.E;
@@ -178,7 +179,9 @@ int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, 
                 next_tok, best, second, logits, ldlogits, next_rows, ldnext,
                 count_ge, ge_bound, count_eq, eq_value,
                 sync ? sync->seen : nullptr, sync ? sync->arrive : nullptr, sync ? sync->host_slot : nullptr,
-                sync ? sync->host_which : 0, sync ? sync->next_stats : nullptr};
+                sync ? sync->host_which : 0, sync ? sync->next_stats : nullptr,
+                sync ? sync->slot : nullptr, sync ? sync->fin : nullptr, sync ? sync->fin_j : 0,
+                sync ? sync->term_lo : 0, sync ? sync->term_hi : 0};
   FF_CHECK_ARG(!a.arrive || (a.host_slot && (a.host_which ? count_eq : count_ge)), "ff_pointer_argmax: counter hand-over without a counter");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ff_cdiv(B, 4)), block(256);

@@ -397,6 +397,47 @@ extern "C" int ff_gather_rows(const float* memory, int S, int E, const int* tok,
   return FF_OK;
 }
 
+// ---- row permutation of the FF_RETIRE_FINISHED compaction ----------------------------------------------------------------
+// dst[(j * dst_rows + di(i)) * W + c] = src[(j * src_rows + si(i)) * W + c]: one wave per (position, row), 16-byte loads and
+// stores when the rows allow them (the engine's x0 / qkv0 rows: 512 / 1536 floats).  Bandwidth-bound; no reuse.
+template <bool VEC>
+__global__ __launch_bounds__(256) void permute_rows_kernel(const float* __restrict__ src, int src_rows, const int* __restrict__ src_idx,
+                                                           float* __restrict__ dst, int dst_rows, const int* __restrict__ dst_idx,
+                                                           int npos, int rows, int width) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (r >= (long long)npos * rows) return;
+  const int j = (int)(r / rows), i = (int)(r % rows);
+  const int si = src_idx ? src_idx[i] : i, di = dst_idx ? dst_idx[i] : i;
+  const float* s = src + ((size_t)j * src_rows + si) * width;
+  float* d = dst + ((size_t)j * dst_rows + di) * width;
+  if (VEC) {
+    for (int vi = lane; vi < (width >> 2); vi += 64)
+      *reinterpret_cast<f32x4*>(d + vi * 4) = *reinterpret_cast<const f32x4*>(s + vi * 4);
+  } else {
+    for (int c = lane; c < width; c += 64) d[c] = s[c];
+  }
+}
+
+extern "C" int ff_permute_rows(const float* src, int src_rows, const int* src_idx, float* dst, int dst_rows, const int* dst_idx,
+                               int npos, int rows, int width, ff_stream_t stream) {
+  if (npos == 0 || rows == 0 || width == 0) return FF_OK;
+  FF_CHECK_ARG(npos > 0 && rows > 0 && width > 0 && src_rows > 0 && dst_rows > 0 && (src_idx || rows <= src_rows) &&
+                   (dst_idx || rows <= dst_rows), "ff_permute_rows: bad sizes npos=%d rows=%d width=%d", npos, rows, width);
+  FF_CHECK_ARG(src && dst, "ff_permute_rows: null pointer");
+  const bool vec = (width & 3) == 0 && ff_aligned16(src) && ff_aligned16(dst);
+  const long long nr = (long long)npos * rows;
+  FF_CHECK_ARG(nr / 4 < (1LL << 31), "ff_permute_rows: too many rows");
+  FFProfScope prof(FF_CAT_ROWOP, (double)nr * width * 8.0, (hipStream_t)stream);
+  const dim3 grid((unsigned)((nr + 3) / 4)), block(256);
+  if (vec) hipLaunchKernelGGL(permute_rows_kernel<true>, grid, block, 0, (hipStream_t)stream, src, src_rows, src_idx, dst, dst_rows,
+                              dst_idx, npos, rows, width);
+  else hipLaunchKernelGGL(permute_rows_kernel<false>, grid, block, 0, (hipStream_t)stream, src, src_rows, src_idx, dst, dst_rows,
+                          dst_idx, npos, rows, width);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
 // ---- embedding assembly: token rows ++ edge rows ------------------------------------------------
 __global__ __launch_bounds__(256) void assemble_embedding_kernel(
     const float* __restrict__ tok_embed, int num_token, const float* __restrict__ edge, int ld_edge,

@@ -208,6 +208,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
     stop_each_eos: single-sequence model only -- None = the module's own `stop_each_eos`; True / False = this call's rule,
         passed down as an argument (the module attribute is NOT touched: other host threads may be decoding with the model)."""
     from .models import SurfaceFormer_Parallel
+    if getattr(model, "retire_finished", False):
+        raise ValueError("decode_sharded does not implement retire_finished (the batch-global stop rule counts every sequence)")
     rank, world = dist_mod.get_rank(group), dist_mod.get_world_size(group)
     parallel = isinstance(model, SurfaceFormer_Parallel)
     variant = _L.FF_PARALLEL if parallel else _L.FF_SEQ2SEQ

@@ -20,7 +20,7 @@ from collections import Counter
 
 import numpy as np
 
-__all__ = ["parse_parallel_faces", "parse_faces", "unique_faces_with_majority_type", "face_metrics",
+__all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_with_majority_type", "face_metrics",
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record"]
 
@@ -62,6 +62,34 @@ def _parallel_rows(rows, token, num_edges):
         if idx:
             faces.append((face_type, idx))
     return faces
+
+
+def retired_view(predict, token, return_steps=False):
+    """What the parallel decode with finished-loop retirement (FF_RETIRE_FINISHED) returns, as a function of the reference's
+    `predict` of the same batch ([..., T]; every row of the batch, padding anchors included):
+      fin[r]  first position j >= 0 of row r holding a face-type token (face_type_offset <= t < len), the start token included;
+              T when there is none;
+      s       the first position j >= 1 at which no row with fin >= j holds an edge token (>= len): the reference's stop rule
+              over the unfinished rows (never later than the reference's own stop); T - 1 when there is none;
+      out[r, j] = predict[r, j] for j <= min(fin[r], s), 0 after.
+    parse_parallel_faces reads nothing after fin[r], so the faces equal the reference's except where a finished row's later edge
+    tokens kept the reference's loop going while an unfinished row had stopped selecting edges.
+    Returns a new int64 array of predict's shape (and s with return_steps=True)."""
+    p = np.asarray(predict, dtype=np.int64)
+    shape = p.shape
+    rows = p.reshape(-1, shape[-1])
+    T = rows.shape[1]
+    off, ntok = _tok(token, "face_type_offset", 1), _tok(token, "len", 4)
+    term = (rows >= off) & (rows < ntok)
+    fin = np.where(term.any(axis=1), term.argmax(axis=1), T)
+    steps = T - 1
+    for j in range(1, T):
+        if not ((rows[:, j] >= ntok) & (fin >= j)).any():
+            steps = j
+            break
+    keep = np.arange(T)[None, :] <= np.minimum(fin, steps)[:, None]
+    out = np.where(keep, rows, 0).reshape(shape)
+    return (out, steps) if return_steps else out
 
 
 def apply_own_stop_rule(predict, token, parallel, eos=None):

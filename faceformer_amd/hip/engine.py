@@ -11,6 +11,8 @@ import operator
 
 _VERSION_OF = operator.attrgetter("_version")
 
+RETIRE_MIN_SHRINK = 0.125   # retire=True: a check point compacts a micro-batch that loses at least this fraction of its slots
+
 DEFAULT_FLAGS = (_L.FF_REUSE_LAYER0_QKV | _L.FF_LAST_LAYER_LAST_ROW | _L.FF_DEDUP_PAD_ANCHORS
                  | _L.FF_FUSE_LAYERNORM)
 
@@ -298,9 +300,15 @@ class PathEngine:
     def decode(self, memory, mask_u8, kv_len, variant, T, F=1, num_input=None, extra_mask=None,
                chunk_wireframes=0, chunk_seqs=0, num_streams=1, sync_every=4, flags=DEFAULT_FLAGS,
                tok_sos=1, tok_eos=3, x3_min_rows=0, chunk_max_seqs=0, ln_fuse_max_rows=0,
-               trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None):
+               trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
+               retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
-        tensors indexed like predict's rows])."""
+        tensors indexed like predict's rows], slots_per_step, slot_rows).
+
+        retire=True (parallel variant, FF_RETIRE_FINISHED): a sequence is finished from the first position holding a token in
+        term_range = (lo, hi); the stop rule looks at unfinished sequences only, `predict` is zero after min(finish position,
+        stop step) -- faces.retired_view of the default decode -- and finished sequences leave their micro-batch at the check
+        points.  slot_rows = sum over executed steps of (step + 1) * slots: the decoder rows the call computed."""
         _dev(memory, "memory")
         self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
         N, S, E = memory.shape
@@ -312,6 +320,20 @@ class PathEngine:
         prm.chunk_max_seqs = int(chunk_max_seqs)
         prm.ln_fuse_max_rows = int(ln_fuse_max_rows)
         prm.flags = flags | (_L.FF_RETURN_POINTER if return_pointer else 0) | (_L.FF_NO_STOP if no_stop else 0)
+        if retire:
+            if variant != _L.FF_PARALLEL:
+                raise ValueError("retire=True is a parallel-variant option")
+            if return_pointer or no_stop or stop_callback is not None:
+                raise ValueError("retire=True excludes return_pointer, no_stop and stop_callback")
+            if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
+                raise ValueError("retire=True needs term_range = (lo, hi) with lo < hi")
+            if num_input is None and staged_num_input is None:
+                raise ValueError("retire=True needs num_input")
+            prm.flags |= _L.FF_RETIRE_FINISHED
+            if extra_mask is None:     # (retirement supersedes the padding-anchor de-duplication: both on)
+                prm.flags |= _L.FF_DEDUP_PAD_ANCHORS
+            prm.term_lo, prm.term_hi = int(term_range[0]), int(term_range[1])
+            prm.retire_min_shrink = float(retire_min_shrink)
         if return_pointer or extra_mask is not None:   # (every padding-anchor row has its own extra-mask row)
             prm.flags &= ~_L.FF_DEDUP_PAD_ANCHORS
         prm.tok_sos, prm.tok_eos = tok_sos, tok_eos
@@ -357,6 +379,8 @@ class PathEngine:
             prm.stop_fn = C.cast(cb, C.c_void_p)
         steps = C.c_int(0)
         counts = (C.c_int * max(T - 1, 1))()
+        slots = (C.c_int * max(T - 1, 1))()
+        prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
         with torch.cuda.device(dev):
             _L.check(self._lib.ff_decode(
                 C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), _p(ni), ni_host,
@@ -364,8 +388,9 @@ class PathEngine:
                 _p(rows), _p(ws), ws.numel(), _stream()), "ff_decode")
         if cb_error:
             raise cb_error[0]
+        sps = [int(v) for v in slots]
         out = {"predict": predict, "steps": steps.value, "step_counts": list(counts)[: steps.value],
-               "seq_of_row": rows}
+               "seq_of_row": rows, "slots_per_step": sps, "slot_rows": sum((s + 1) * v for s, v in enumerate(sps))}
         if return_pointer:
             out["pointer"] = pointer[: steps.value]
         if trace:

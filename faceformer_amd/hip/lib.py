@@ -17,7 +17,8 @@ FF_FUSE_LAYERNORM = 32
 FF_STOP_EACH_EOS = 512
 FF_NO_L0_FOLD = 1024
 FF_NO_POINTER_FOLD = 2048
-FF_ABI_VERSION = 103   # include/faceformer_hip.h: the struct layouts below are this version's
+FF_RETIRE_FINISHED = 4096
+FF_ABI_VERSION = 104   # include/faceformer_hip.h: the struct layouts below are this version's
 
 fptr = C.c_void_p  # device pointers travel as integers
 
@@ -122,6 +123,8 @@ class DecodeParams(C.Structure):
         ("tok_sos", C.c_int), ("tok_eos", C.c_int),
         ("x3_min_rows", C.c_int), ("chunk_max_seqs", C.c_int), ("ln_fuse_max_rows", C.c_int),
         ("stop_fn", C.c_void_p), ("stop_user", C.c_void_p),
+        ("term_lo", C.c_int), ("term_hi", C.c_int), ("retire_min_shrink", C.c_float),
+        ("slots_per_step", C.POINTER(C.c_int)),
     ]
 
 
@@ -176,6 +179,7 @@ SIGNATURES = {
     "ff_pointer_argmax": (C.c_int, [fptr, C.c_int, fptr, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int,
                                     C.c_int, C.c_int, fptr, fptr, fptr, fptr, C.c_int, fptr, C.c_int,
                                     fptr, C.c_int, fptr, C.c_int, fptr]),
+    "ff_permute_rows": (C.c_int, [fptr, C.c_int, fptr, fptr, C.c_int, fptr, C.c_int, C.c_int, C.c_int, fptr]),
     "ff_gather_rows": (C.c_int, [fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, fptr, C.c_int, fptr]),
     "ff_assemble_embedding": (C.c_int, [fptr, C.c_int, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr,
                                         fptr]),

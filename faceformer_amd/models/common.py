@@ -59,6 +59,9 @@ class SurfaceFormerBase(nn.Module):
                                        # (the queue never drains: free at every step, tools/run_sync_probe.sh); a decode
                                        # that stops at step s executes s + k ... s + 2k - 1 steps
         self.sharded_sync_every = 2    # ... period of the batch-global rule in dist.decode_sharded (a host all-reduce per check)
+        self.retire_finished = False   # parallel model: a face loop stops being decoded once it has produced its face-type token;
+                                       # `predict` is then faces.retired_view of the reference's (same faces: DESIGN.md 10).
+                                       # Not with dist.decode_sharded or the single-sequence model (ValueError)
         # Decoder projections of launches with at least this many rows (q|k|v; linear1 from 7/4 x, the 512-column ones from
         # 11/4 x as many) run as 3 x bf16 split products on the bf16 matrix cores: fp32-accurate (error vs fp64 = an fp32 dot
         # product's, tests/test_hip_ops.py), LayerNorm folding included (ff_gemm_x3_ln), and 1.3-1.6x the f32-MFMA kernel

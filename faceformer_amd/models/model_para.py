@@ -12,6 +12,7 @@ last layer and the output projection are evaluated for the newest position only.
 """
 import torch
 
+from .. import faces as _faces
 from ..hip import lib as _L
 from .common import SurfaceFormerBase
 
@@ -38,7 +39,11 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         label = inputs["label"]
         T = self.max_face_length
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
-            return self._forward_eval_modules(inputs, parallel=True)
+            inputs = self._forward_eval_modules(inputs, parallel=True)
+            if self.retire_finished:         # (that loop decodes every sequence; the result is the same function of its tokens)
+                inputs["predict"] = torch.as_tensor(_faces.retired_view(inputs["predict"].cpu().numpy(), self.token),
+                                                    device=inputs["predict"].device)
+            return inputs
         if label.size(2) < T - 1:
             raise ValueError("label has %d positions but max_face_length-1=%d query positions are "
                              "needed" % (label.size(2), T - 1))
@@ -70,12 +75,14 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs,
                          num_streams=self.num_streams, sync_every=self.sync_every,
-                         flags=self.decode_flags, x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, extra_mask=extra)
+                         flags=self.decode_flags, x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, extra_mask=extra,
+                         retire=self.retire_finished, term_range=(int(self.token.face_type_offset), int(self.token.len)))
         pred = out["predict"].view(N, F, T)
         if order is not None:
             inv = torch.empty(N, dtype=torch.long, device=pred.device)
             inv[torch.tensor(order, device=pred.device)] = torch.arange(N, device=pred.device)
             pred = pred.index_select(0, inv)
         inputs["predict"] = pred
-        self.last_decode_stats = {"decoded_seqs": sum(min(F, n + 1) for n in num_input), "rows": N * F}
+        self.last_decode_stats = {"decoded_seqs": sum(min(F, n + 1) for n in num_input), "rows": N * F,
+                                  "slot_rows": out["slot_rows"], "steps": out["steps"]}
         return inputs

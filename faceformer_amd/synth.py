@@ -17,7 +17,7 @@ import zlib
 import numpy as np
 import torch
 
-RECIPES = ("default", "gain4", "bias05")
+RECIPES = ("default", "gain4", "bias05", "stagger")
 
 
 def state_dict_spec(kind, num_lines, seq_len, num_model=512, num_feedforward=1024,
@@ -81,6 +81,8 @@ def make_state_dict(spec, recipe="default", seed=0):
     """
     if recipe not in RECIPES:
         raise ValueError("unknown weight recipe %r" % (recipe,))
+    if recipe == "stagger":
+        return _stagger(spec, seed)
     sd = {}
     for name, shape, role in spec:
         g = _rng(name, seed)
@@ -110,6 +112,31 @@ def make_state_dict(spec, recipe="default", seed=0):
             else:
                 w = np.zeros(shape)
         sd[name] = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+    return sd
+
+
+STAGGER_TOKEN_GAIN = 8.0   # 'stagger': how far the face-type token rows stand out along the shared direction u
+STAGGER_PULL = 20.0        # ... and how strongly project.bias pulls every pointer query towards u (tuned on the CPU oracle)
+
+
+def _stagger(spec, seed):
+    """'stagger': the 'gain4' weights plus a uniform pull towards the face-type tokens, so that sequences of one wireframe end
+    their loops at staggered steps (as trained weights would) instead of almost never: the token-embedding rows 1..3 get a
+    large component along one unit direction u, which survives the encoder into their memory rows, and project.bias is a
+    multiple of u, which adds about the same amount to the logits of those three keys at every step.  A sequence finishes
+    at the first step at which that pull beats its best edge.  Test and timing weights for finished-loop retirement
+    (tools/bench_retire.py); existing recipes are unchanged."""
+    sd = make_state_dict(spec, "gain4", seed)
+    tok, proj_b = sd.get("val_enc.embedding_token.weight"), sd.get("project.bias")
+    if tok is None or proj_b is None:
+        return sd
+    E = tok.shape[1]
+    u = _rng("stagger.u", seed).standard_normal(E)
+    u = torch.from_numpy(u / np.linalg.norm(u)).to(torch.float32)
+    tok = tok.clone()
+    tok[1:4] += STAGGER_TOKEN_GAIN * u * float(np.sqrt(E)) / 4.0
+    sd["val_enc.embedding_token.weight"] = tok
+    sd["project.bias"] = (proj_b + STAGGER_PULL * u).contiguous()
     return sd
 
 

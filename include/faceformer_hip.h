@@ -38,10 +38,11 @@ enum ff_status {
 #define FF_HEAD_DIM 64   /* attention head width of the MFMA kernels (reference: 512 / 8); other widths: ff_attention_general */
 #define FF_MAX_LAYERS 16
 
-/* Library version (major*10000 + minor*100 + patch).  103: ff_attention_general / ff_attn_general_desc added (round 6).  101: the struct layouts of this header (round 5: ff_decode_params lost
+/* Library version (major*10000 + minor*100 + patch).  104: FF_RETIRE_FINISHED, ff_decode_params.term_lo / term_hi /
+ * retire_min_shrink / slots_per_step, ff_permute_rows.  103: ff_attention_general / ff_attn_general_desc added (round 6).  101: the struct layouts of this header (round 5: ff_decode_params lost
  * chain_max_rows / flow_min_rows, FF_STOP_EACH_EOS added; round 4: ff_layer_weights grew by the ln*_planes / ln*_csum
  * pointers).  A caller built against another header must refuse to run: hip/lib.py asserts equality with FF_ABI_VERSION. */
-#define FF_ABI_VERSION 103
+#define FF_ABI_VERSION 104
 int ff_version(void);
 /* Thread-local text of the last error returned by this library ("" if none). */
 const char* ff_last_error(void);
@@ -459,6 +460,12 @@ enum ff_decode_flags {
                                 ff_decode_workspace_bytes must see the same flags */
   FF_NO_POINTER_FOLD = 2048, /* this call: decoder.norm + project and the pointer's dot products as two launches also for
                                 one-wireframe micro-batches (knob FF_POINTER_FOLD = 0, per call; changes the workspace layout) */
+  FF_RETIRE_FINISHED = 4096, /* parallel variant, opt-in: a sequence is FINISHED from the first position holding a token in
+                                [term_lo, term_hi) (the start token included); the stop rule counts unfinished sequences only,
+                                `predict` is zero after min(finish position, stop step), and every sync_every steps the engine
+                                compacts each micro-batch to its live sequences.  Works with and without
+                                FF_DEDUP_PAD_ANCHORS (the package sets both).
+                                Not with FF_SEQ2SEQ, FF_RETURN_POINTER, FF_NO_STOP or a stop_fn (FF_ERR_ARG) */
   FF_STOP_EACH_EOS = 512     /* seq2seq variant: the per-step counter counts a sequence's FIRST EOS only, so the cumulative
                                 rule "count == N" fires at the first step by which EVERY wireframe has produced an EOS -- the
                                 rule a caller needs when the records of a batch must equal those of one-wireframe decodes
@@ -502,6 +509,12 @@ typedef struct ff_decode_params {
                            `predict` then keeps every step that was executed (as with FF_NO_STOP): the caller zero-pads
                            after the step its global rule names */
   void* stop_user;      /* first argument of stop_fn */
+  /* FF_RETIRE_FINISHED only (ignored otherwise): */
+  int term_lo, term_hi; /* a token t with term_lo <= t < term_hi ends its sequence (the model: face_type_offset, len) */
+  float retire_min_shrink; /* a check point compacts a micro-batch only when it loses at least this fraction of its slots
+                              (<= 0: whenever one can go; the package passes 0.125) */
+  int* slots_per_step;  /* optional HOST int[T-1] (any flags): sequence slots computed at every executed step, summed over the
+                           micro-batches; 0 after the last one */
 } ff_decode_params;
 
 /* Greedy pointer decode (a5-a12 of SURVEY.md 8a).
@@ -525,6 +538,12 @@ typedef struct ff_decode_params {
  * Stop rules reproduced exactly: parallel = first step whose tokens are all < num_token
  * (model_para.py:232); seq2seq = cumulative EOS count == N (model.py:207-210). */
 size_t ff_decode_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host);
+/* Row permutation of the FF_RETIRE_FINISHED compaction (op-tested through this entry): for every position j < npos and row
+ * i < rows, dst[(j * dst_rows + di(i)) * width + c] = src[(j * src_rows + si(i)) * width + c], c < width, with si(i) = src_idx[i]
+ * (or i when src_idx is NULL) and di(i) = dst_idx[i] (or i).  dst and src must not overlap.  16-byte loads when width % 4 == 0
+ * and both bases are 16-byte aligned. */
+int ff_permute_rows(const float* src, int src_rows, const int* src_idx, float* dst, int dst_rows, const int* dst_idx,
+                    int npos, int rows, int width, ff_stream_t stream);
 int ff_decode(const ff_model* m, const ff_decode_params* p,
               const float* memory, const unsigned char* mask, const int* kv_len,
               const int* num_input, const int* num_input_host, const unsigned char* extra_mask,

@@ -66,10 +66,14 @@ def record_of(cfg, raw, item, pred, parallel):
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
-def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None):
+def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
+             retire_finished=False):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
-    rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint."""
+    rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
+    retire_finished: the parallel model stops decoding a face loop once it has ended (models/common.py retire_finished)."""
+    if retire_finished and cfg.model_class != "SurfaceFormer_Parallel":
+        raise ValueError("--retire-finished applies to SurfaceFormer_Parallel only")
     model_class = getattr(models, cfg.model_class)
     dataset_class = getattr(D, cfg.dataset_class)
     if model is None:
@@ -77,6 +81,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         sd, _ = load_lightning_checkpoint(ckpt_path)
         model.load_state_dict(sd)
         model = model.eval().to(device)
+    if retire_finished:
+        model.retire_finished = True
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -133,6 +139,8 @@ if __name__ == "__main__":
     parser = get_parser()
     parser.add_argument("--batch-size", type=int, default=1,
                         help="samples per model(batch) call (the reference's test loader is fixed at 1); the records do not depend on it")
+    parser.add_argument("--retire-finished", action="store_true",
+                        help="parallel model: stop decoding a face loop once it has produced its face-type token (DESIGN.md 10)")
     args = parser.parse_args()
     cfg = get_cfg(args)
     if args.test_ckpt == "":
@@ -146,6 +154,7 @@ if __name__ == "__main__":
         torch.cuda.set_device(local_rank)
         device = "cuda:%d" % local_rank
         dist_mod.init_process_group("nccl", device_id=torch.device(device))
-    run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod)
+    run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
+             retire_finished=args.retire_finished)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
