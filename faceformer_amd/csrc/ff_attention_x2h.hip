@@ -13,9 +13,14 @@
 // 148 480 bytes per pair -- and reach LDS by one linear LDS-DMA copy per block.  Queries and the softmax weights are split in
 // registers.  Work: the pair's query tiles are dealt round-robin to the 8 waves of its c blocks (whole tiles: no partial records).
 //
-// Range: fp16 has five exponent bits.  q, k, v are projections of LayerNorm output (bounded by sqrt(E) ||w_n||_2 + |b_n|; the engine
-// checks the bounds when it binds the planes), the weights are in [0, 1].  Rows past a group's kv_len are zero in the planes and
-// masked by the additive bias.
+// Range: fp16 has five exponent bits.  Every split operand -- k, v and q * scale * log2(e), the weights in [0, 1] -- must stay below
+// 65504; the engine holds them below 6e4 (faceformer_amd/hip/engine.py: fp16_operand_bounds): cross-attention keys
+// (memory + pos) Wk^T + bk, values memory Wv^T + bv and scaled queries (LN2(x) + qpos) Wq^T + bq, each bounded from the weights, the
+// LayerNorm gammas / betas and the position tables.  Floor: both terms keep an absolute resolution of 2^-36 (fp16's subnormal spacing
+// 2^-24 of the second term at 2^11), so below a row maximum of 2^-14 (x1 subnormal throughout) the error relative to the row grows as
+// ~2^-38 / max |row|: measured within 5e-6 of max |v| down to max |v| = 2^-18, ~1e-4 at 2^-24 (tests/test_hip_ops.py).  Keys in
+// [kv_len, nk) are split as they are (finite values: no effect, the bias masks them); keys past nk are zero in the planes.
+// More than 65535 (group, head) pairs: ff_attention_split_kv launches slices of at most 65535 (grid.y).
 #include <atomic>
 
 #include "ff_common.h"
@@ -50,8 +55,8 @@ __device__ __forceinline__ void split_h2(float x0, float x1, unsigned& p1, unsig
 // ---- K | V of every (group, head) pair -> the planes (once per batch and layer) ----------------------------------------------------
 __global__ __launch_bounds__(256) void kv_split_kernel(const float* __restrict__ k, const float* __restrict__ v, int ldk, int ldv,
                                                        int num_heads, int nk, int k_group_stride, int k_stride,
-                                                       unsigned char* __restrict__ planes, long long plane_stride) {
-  const int pair = blockIdx.y, g = pair / num_heads, h = pair % num_heads;
+                                                       unsigned char* __restrict__ planes, long long plane_stride, int pair0) {
+  const int pair = pair0 + (int)blockIdx.y, g = pair / num_heads, h = pair % num_heads;
   unsigned char* out = planes + (size_t)pair * plane_stride;
   const float* kb = k + (size_t)g * k_group_stride * ldk + h * FF_HEAD_DIM;
   const float* vb = v + (size_t)g * k_group_stride * ldv + h * FF_HEAD_DIM;
@@ -276,9 +281,14 @@ extern "C" int ff_attention_split_kv(const float* k, const float* v, int ldk, in
                "ff_attention_split_kv: bad arguments (1 <= nk <= %d)", XK_KEYS);
   FF_CHECK_ARG(ldk >= num_heads * FF_HEAD_DIM && ldv >= num_heads * FF_HEAD_DIM && ff_aligned16(planes),
                "ff_attention_split_kv: ld smaller than num_heads * 64, or planes not 16-byte aligned");
-  FF_CHECK_ARG((long)num_groups * num_heads <= 65535, "ff_attention_split_kv: at most 65535 (group, head) pairs per call");
-  hipLaunchKernelGGL(kv_split_kernel, dim3(9, num_groups * num_heads), dim3(256), 0, (hipStream_t)stream, k, v, ldk, ldv, num_heads, nk,
-                     k_group_stride, k_stride, static_cast<unsigned char*>(planes), (long long)XK_PLANE_BYTES);
-  FF_CHECK_LAUNCH();
+  const long pairs = (long)num_groups * num_heads;
+  FF_CHECK_ARG(pairs < 2147483647L, "ff_attention_split_kv: too many (group, head) pairs");
+  // grid.y holds at most 65535 blocks: a batch with more (group, head) pairs (8192 wireframes x 8 heads) is split in slices
+  for (long pair0 = 0; pair0 < pairs; pair0 += 65535) {
+    const int np = (int)(pairs - pair0 < 65535 ? pairs - pair0 : 65535);
+    hipLaunchKernelGGL(kv_split_kernel, dim3(9, np), dim3(256), 0, (hipStream_t)stream, k, v, ldk, ldv, num_heads, nk, k_group_stride,
+                       k_stride, static_cast<unsigned char*>(planes), (long long)XK_PLANE_BYTES, (int)pair0);
+    FF_CHECK_LAUNCH();
+  }
   return FF_OK;
 }

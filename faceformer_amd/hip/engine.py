@@ -24,6 +24,66 @@ def _kv_len_from_mask(mask_u8):
     return ((mask_u8 == 0).to(torch.int32) * idx).amax(dim=1).to(torch.int32).contiguous()
 
 
+FP16_LIM = 6.0e4     # bound every operand of the "2 x fp16" products must stay below (fp16's largest finite value is 65504)
+ATTN_Q_SCALE = 0.125 * 1.4426950408889634   # the 2 x fp16 attention kernel splits q * scale * log2(e) (ff_attention_x2h.hip)
+
+
+def fp16_operand_bounds(tensors, n_dec, E, weights=0.0):
+    """A-priori bounds of every operand the split-kind "fp16x2" decode feeds to fp16 terms, by operand class (CPU or GPU tensors).
+
+    A LayerNorm output is y = gamma * n + beta with ||n||_2 <= sqrt(E), so a projection of it is bounded row by row:
+        |(y + t) . W_n + b_n| <= sqrt(E) ||W_n * gamma||_2 + max over t |W_n . (beta + t) + b_n|      (Cauchy-Schwarz)
+    for t ranging over the rows of a position table added to y (or t = 0).  The classes:
+      weights                  max |w| of the planes (`weights`: the caller's; raw and LayerNorm-folded weights)
+      LayerNorm outputs        y of the un-folded steps (into linear1 and the self-attention v rows): max |gamma| sqrt(E) + max |beta|
+      LayerNorm + query pos    yq = y + qpos of the un-folded steps (into the self-attention q|k rows and the cross-attention q)
+      self-attention values    v = LN1(x) Wv^T + bv: the attention output is a convex mixture of v rows (into the self out-projection)
+      feed-forward hidden      relu(LN3(x) W1^T + b1) (into linear2)
+      cross-attention values   v = memory Wv^T + bv, memory = the encoder's final LayerNorm (the K|V planes; into the cross out-projection)
+      cross-attention keys     k = (memory + pos) Wk^T + bk (the K|V planes)
+      cross-attention queries  q = (LN2(x) + qpos) Wq^T + bq, times 0.125 log2(e): the kernel splits the scaled q
+    Returns {class: bound}.  The LayerNorm-folded weights are W * gamma / W . beta + b: the same bounds (up to rounding).  The
+    folded steps' normalise-first form multiplies n itself (|n_i| <= sqrt(E)); their epilogue form feeds the raw residual rows at
+    2^-6 (exact; 4.2e6 before fp16's range) -- the residual stream has no a-priori bound and is not one of these classes."""
+    root = float(E) ** 0.5
+
+    def bound(W, gamma, beta, b, table=None):
+        W, gamma, beta, b = (t.detach().double() for t in (W, gamma, beta, b))
+        off = W @ beta + b                                                  # [N]
+        if table is not None:
+            off = (off[:, None] + W @ table.detach().double().t()).abs().amax(dim=1)
+        return float(((W * gamma).norm(dim=1) * root + off.abs()).max())
+
+    def ln_bound(gamma, beta, table=None):
+        gamma, beta = gamma.detach().double(), beta.detach().double()
+        shift = beta.abs() if table is None else (beta[None, :] + table.detach().double()).abs().amax(dim=0)
+        return float((gamma.abs() * root + shift).max())
+
+    worst = {"weights": float(weights)}
+
+    def put(name, v):
+        worst[name] = max(worst.get(name, 0.0), v)
+    ge, be = tensors["encoder.norm.weight"], tensors["encoder.norm.bias"]
+    pos, qpos = tensors["pos_enc.pos_embed.weight"], tensors["query_pos_enc.pos_embed.weight"]
+    for i in range(n_dec):
+        p = "decoder.layers.%d." % i
+        g1, b1 = tensors[p + "norm1.weight"], tensors[p + "norm1.bias"]
+        g2, b2 = tensors[p + "norm2.weight"], tensors[p + "norm2.bias"]
+        g3, b3 = tensors[p + "norm3.weight"], tensors[p + "norm3.bias"]
+        Ws, bs = tensors[p + "self_attn.in_proj_weight"], tensors[p + "self_attn.in_proj_bias"]
+        Wc, bc = tensors[p + "multihead_attn.in_proj_weight"], tensors[p + "multihead_attn.in_proj_bias"]
+        for g_, b_ in ((g1, b1), (g2, b2), (g3, b3)):
+            put("LayerNorm outputs", ln_bound(g_, b_))
+        for g_, b_ in ((g1, b1), (g2, b2)):
+            put("LayerNorm + query pos", ln_bound(g_, b_, qpos))
+        put("self-attention values", bound(Ws[2 * E:], g1, b1, bs[2 * E:]))
+        put("feed-forward hidden", bound(tensors[p + "linear1.weight"], g3, b3, tensors[p + "linear1.bias"]))
+        put("cross-attention values", bound(Wc[2 * E:], ge, be, bc[2 * E:]))
+        put("cross-attention keys", bound(Wc[E:2 * E], ge, be, bc[E:2 * E], pos))
+        put("cross-attention queries", ATTN_Q_SCALE * bound(Wc[:E], g2, b2, bc[:E], qpos))
+    return worst
+
+
 class PathEngine:
     """Encoder + greedy pointer decode of one model instance on one ROCm device.
 
@@ -111,8 +171,9 @@ class PathEngine:
                     ("proj",), tensors["project.weight"], tensors["project.bias"],
                     tensors["decoder.norm.weight"], tensors["decoder.norm.bias"], None, 0)
         # Split planes (x3_min_rows > 0): of the raw weights (steps that launch their LayerNorms) and of the LayerNorm-folded ones.
-        # A model whose operand bounds leave fp16's range gets the bf16 terms instead of the fp16 ones (with a warning): the
-        # range of bf16 is fp32's.  `requested_kind` is what the caller asked for, `split_kind` what was bound.
+        # A model whose operand bounds (fp16_operand_bounds: every operand class, folded or not) leave fp16's range gets the bf16
+        # terms instead of the fp16 ones (with a warning): the range of bf16 is fp32's.  `requested_kind` is what the caller asked
+        # for, `split_kind` what was bound.
         self.requested_kind = split_kind
         if bf16_split_planes:
             self._make_planes(m, tensors, n_dec, E, split_kind, ln_in_epilogue)
@@ -174,37 +235,13 @@ class PathEngine:
                         setattr(m.dec[i], cfield, cs.data_ptr())
 
     def _check_fp16_range(self, tensors, n_dec, E):
-        """fp16 has five exponent bits: every operand of a "2 x fp16" product must stay below 65504 in magnitude.  Weights are
-        checked directly.  The activations are bounded a priori: LayerNorm-normalised rows by sqrt(E); the raw rows of the
-        epilogue form are fed at 2^-6 (< 4.2e6); the attention outputs by max |v| <= sqrt(E) ||Wv_n||_2 + |b_n| (a row of a
-        softmax-weighted mean of value rows; v = LN(.) Wv'^T + b or memory Wv^T + b, memory being LayerNorm output as well),
-        the feed-forward hidden rows by sqrt(E) ||W1'_n||_2 + |b1_n| (Cauchy-Schwarz, gamma / beta folded in).  A model
-        whose bounds do not fit gets the bf16 terms instead (the caller warns).  Returns "" or the offending bounds."""
-        lim = 6.0e4
-        root = float(E) ** 0.5
-
-        def bound(W, b):
-            return float((W.detach().double().norm(dim=1) * root + b.detach().double().abs()).max())
-        worst = {"weights": max(float(t.float().abs().max()) for (_i, f), t in self._planes.items() if t.dim() == 4)}
-        for i in range(n_dec):
-            p = "decoder.layers.%d." % i
-            for name, key in (("self-attention values", (i, 1)), ("feed-forward hidden", (i, 3))):
-                if key in self._folded:
-                    Wf, bf, _ = self._folded[key]
-                    Wv = Wf[2 * E:] if key[1] == 1 else Wf
-                    bv = bf[2 * E:] if key[1] == 1 else bf
-                    worst[name] = max(worst.get(name, 0.0), bound(Wv, bv))
-            # memory = gamma * n + beta with ||n||_2 <= sqrt(E) (the encoder's final LayerNorm): v_n = n . (W_n * gamma) + W_n . beta + b_n
-            Wc, bc = tensors[p + "multihead_attn.in_proj_weight"][2 * E:], tensors[p + "multihead_attn.in_proj_bias"][2 * E:]
-            ge, be = tensors["encoder.norm.weight"], tensors["encoder.norm.bias"]
-            with torch.no_grad():
-                worst["cross-attention values"] = max(worst.get("cross-attention values", 0.0), bound(Wc * ge, Wc @ be + bc))
-            for nm in ("norm1", "norm2", "norm3"):     # un-folded steps: y = gamma * n + beta goes through the planes of the raw weight
-                g_, b_ = tensors[p + nm + ".weight"], tensors[p + nm + ".bias"]
-                worst["LayerNorm outputs"] = max(worst.get("LayerNorm outputs", 0.0),
-                                                 float(g_.detach().abs().max()) * root + float(b_.detach().abs().max()))
+        """fp16 has five exponent bits: every operand of a "2 x fp16" product must stay below FP16_LIM in magnitude
+        (fp16_operand_bounds).  A model whose bounds do not fit gets the bf16 terms instead (the caller warns).  Returns "" or the
+        offending bounds."""
+        weights = max(float(t.float().abs().max()) for (_i, f), t in self._planes.items() if t.dim() == 4)
+        worst = fp16_operand_bounds(tensors, n_dec, E, weights)
         self.fp16_operand_bounds = worst
-        bad = {k: v for k, v in worst.items() if not v < lim}
+        bad = {k: v for k, v in worst.items() if not v < FP16_LIM}
         return ", ".join("%s <= %.3g" % kv for kv in sorted(bad.items()))
 
     def _fold(self, key, W, bias, gamma, beta, pos, pos_cols):

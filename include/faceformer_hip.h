@@ -200,7 +200,12 @@ int ff_gemm_x3_ln(const ff_gemm_ln_desc* desc, const void* w_planes, int plane_r
  * dot product of that length accumulates anyway: against fp64 the result is as close as ff_gemm_f32's (op tests compare the three;
  * emulation: profiles/r06/fp16_split_error_table.txt).  fp16 has five exponent bits: every |a| must be < 65504 (weights: checked
  * by the caller when it makes the planes).  LayerNorm-normalised rows are bounded by sqrt(K); the epilogue form (w_colsum) feeds
- * the RAW rows at 2^-6 (|x| < 4.2e6, exact scaling).  Planes: ff_split_weight_fp16x2, [2][K/16][N][16] fp16,
+ * the RAW rows at 2^-6 (|x| < 4.2e6, exact scaling).  The engine bounds every other operand class of the decode a priori and
+ * binds the bf16 terms when one reaches 6e4: LayerNorm outputs, LayerNorm output + query position, self-attention values,
+ * feed-forward hidden rows, cross-attention keys / values / scaled queries (faceformer_amd/hip/engine.py: fp16_operand_bounds).
+ * Floor: both terms keep an absolute resolution of 2^-36 (fp16's subnormal spacing at 2^11): for rows whose max |a| is below
+ * 2^-14 the error relative to |A| |W|^T grows as 2^-36 / max |a| -- measured at 1.5x the f32 kernel's down to max |a| = 2^-12,
+ * several times it at 2^-18 (tests/test_hip_ops.py).  Planes: ff_split_weight_fp16x2, [2][K/16][N][16] fp16,
  * ff_split_weight_fp16x2_bytes(N, K) bytes.  Arguments, restrictions and replaced call sites as ff_gemm_x3 / ff_gemm_x3_ln. */
 size_t ff_split_weight_fp16x2_bytes(int N, int K);
 int ff_split_weight_fp16x2(const float* W, int ldw, int N, int K, void* planes, ff_stream_t stream);
@@ -265,7 +270,8 @@ typedef struct ff_attn_desc {
 /* K | V of every (group, head) pair -> two fp16 planes each, in the layout the 2 x fp16 attention kernel copies into LDS
  * (ff_attention_planes_bytes(num_groups, num_heads) bytes: 148 480 per pair).  k / v / ldk / ldv / nk / k_group_stride / k_stride as in
  * ff_attn_desc; 1 <= nk <= 288.  Made once per batch and layer by ff_decode (cross-attention keys are the encoder memory:
- * reference transformer.py:248-250); every |k|, |v| must be below 65504 (fp16's range). */
+ * reference transformer.py:248-250); every |k|, |v| must be below 65504 (fp16's range; floor: an absolute resolution of 2^-36, see
+ * ff_attention_x2h.hip).  Any number of (group, head) pairs: more than 65535 are split in slices of one launch each. */
 size_t ff_attention_planes_bytes(int num_groups, int num_heads);
 int ff_attention_split_kv(const float* k, const float* v, int ldk, int ldv, int num_groups, int num_heads, int nk,
                           int k_group_stride, int k_stride, void* planes, ff_stream_t stream);

@@ -567,6 +567,42 @@ def test_gemm_x2h_error_is_fp32_class_over_operand_scales(ops, scale_a, scale_w)
     assert e_h < 1.5 * e_f + 2.0 ** -24 and r_h < 1.5 * r_f + 2.0 ** -26, (float(e_h), float(e_f), float(r_h), float(r_f))
 
 
+def rows_with_max(rows, cols, row_max, seed):
+    """randn rows scaled so that max |row| is exactly row_max (a power of two or a value fp32 holds exactly)."""
+    x = rnd(rows, cols, seed=seed).double()
+    x = x * (row_max / x.abs().amax(dim=1, keepdim=True))
+    x[torch.arange(rows), x.abs().argmax(dim=1)] = torch.sign(x[torch.arange(rows), x.abs().argmax(dim=1)]) * row_max
+    return x.float()
+
+
+FP16_LIM = 6.0e4          # faceformer_amd.hip.engine.FP16_LIM: the bound the engine holds every split operand to
+FP16_FLOOR = 2.0 ** -18   # row maximum below which the 2 x fp16 error leaves fp32 class (ff_attention_x2h.hip, "Range")
+
+
+@pytest.mark.parametrize("row_max", [FP16_LIM, 2.0 ** -12, 2.0 ** -18, 2.0 ** -24])
+def test_gemm_x2h_at_the_range_limit_and_the_small_magnitude_floor(ops, row_max):
+    """Every row of A at max |a| = row_max exactly.  At the engine's limit (6e4) and down to 2^-12 the 2 x fp16 product stays
+    within 1.5x the f32 kernel's error relative to |A| |W|^T.  Below, x1 = fp16(a) is subnormal and both terms keep an absolute
+    resolution of 2^-36 (fp16's subnormal spacing 2^-24 of the second term at 2^11): the error is bounded by 2^-35 sum |w|
+    per output, and at 2^-18 it is measurably past the f32 class (the floor the range comments state)."""
+    M, N, K = 512, 512, 512
+    a = rows_with_max(M, K, row_max, seed=31)
+    w = (torch.rand(N, K, generator=torch.Generator().manual_seed(22)) * 2 - 1) * 0.05
+    ref = a.double() @ w.double().t()
+    den = a.double().abs() @ w.double().abs().t()
+    got = ops.linear_x3(a.cuda(), ops.split_weight(w.cuda(), "fp16x2"), None).cpu().double()
+    f32 = ops.linear(a.cuda(), w.cuda(), None).cpu().double()
+    assert torch.isfinite(got).all()
+    e_h, e_f = ((got - ref).abs() / den).max(), ((f32 - ref).abs() / den).max()
+    r_h, r_f = (((got - ref) / den) ** 2).mean().sqrt(), (((f32 - ref) / den) ** 2).mean().sqrt()
+    floor = 2.0 ** -35 * w.double().abs().sum(dim=1)[None, :] + 2.0 ** -22 * den
+    assert bool(((got - ref).abs() <= floor).all()), float(((got - ref).abs() / floor).max())
+    if row_max >= 2.0 ** -12:
+        assert e_h < 1.5 * e_f + 2.0 ** -24 and r_h < 1.5 * r_f + 2.0 ** -26, (float(e_h), float(e_f), float(r_h), float(r_f))
+    else:
+        assert r_h > 4 * r_f, (float(r_h), float(r_f))    # the floor is real: the test above would catch a change of it
+
+
 def test_gemm_x2h_epilogue_form_takes_raw_rows_beyond_fp16_range(hip_lib, ops):
     """The LayerNorm-in-the-epilogue form multiplies the RAW rows; the fp16 kernel feeds them at 2^-6 (exact), so rows of
     magnitude 2e5 -- far outside fp16's 65504 -- come out finite and as accurate as the normalise-first form."""
@@ -701,6 +737,112 @@ def test_attention_cross_shared_kv(ops, attn_algo, t, F, W, S):
     ref = ref_attention(qd, kd, vd, mask)                          # [W,H,t*F,64]
     ref = ref.view(W, H, t, F, 64).permute(2, 0, 3, 1, 4).reshape(t * B, E)
     assert rel_err(out, ref) < 5e-6
+
+
+# ---- the 2 x fp16 attention at fp16's range limits ----------------------------------------------------------------------------------
+def _x2h_attention(ops, q, k, v, G, H, nq, nk, kv_len=None, mask=None):
+    old = ops.set_attention_algo(4)      # attention() splits K | V itself and the x2h kernel takes every eligible launch
+    try:
+        return ops.attention(q.cuda(), k.cuda(), v.cuda(), G, H, nq, nk, q_group_stride=nq, q_inner=nq, q_outer_stride=0,
+                             k_group_stride=nk, k_stride=1, kv_len=None if kv_len is None else kv_len.cuda(),
+                             key_mask=None if mask is None else mask.to(torch.uint8).cuda())
+    finally:
+        ops.set_attention_algo(old)
+
+
+def _per_row_error(out, q, k, v, G, H, nq, nk, mask=None):
+    """(error of every (query row, head) relative to the max |v| of its keys, fp32-class bar of that row): 5e-6, times the
+    score magnitude 0.125 max_j sum_d |q_d k_jd| where it exceeds 1 (an error of the scores moves the output by |v| times it)."""
+    qd = q.double().view(G, nq, H, 64).transpose(1, 2)
+    kd = k.double().view(G, nk, H, 64).transpose(1, 2)
+    vd = v.double().view(G, nk, H, 64).transpose(1, 2)
+    ref = ref_attention(qd, kd, vd, mask)                                      # [G, H, nq, 64]
+    got = out.cpu().double().view(G, nq, H, 64).transpose(1, 2)
+    live = torch.ones(G, nk, dtype=torch.bool) if mask is None else ~mask
+    vmax = (vd.abs().amax(dim=-1) * live[:, None, :]).amax(dim=-1)           # [G, H]
+    cond = 0.125 * ((qd.abs() @ kd.abs().transpose(-1, -2)) * live[:, None, None, :]).amax(dim=-1)   # [G, H, nq]
+    err = (got - ref).abs().amax(dim=-1) / vmax[..., None]
+    return err, 5e-6 * cond.clamp(min=1.0)
+
+
+_X2H_SCALES = [2.0 ** -16, 2.0 ** -14, 2.0 ** -10, 1.0, 1e3, 3e4, 6.0e4]
+
+
+@pytest.mark.parametrize("which,row_max", [(w, s) for w in "qkv" for s in _X2H_SCALES] + [("qkv", 6.0e4)])
+def test_attention_x2h_is_fp32_class_over_operand_scale(ops, which, row_max):
+    """q, k, v (one at a time, then all three) with every row's max |x| set exactly, from 2^-16 to the engine's limit 6e4, through
+    split_kv + the 2 x fp16 kernel against fp64: every (query, head) row within the fp32-class bar relative to that row's max |v|
+    (a whole-tensor maximum would hide one bad row).  Masked keys and a short kv_len on one group."""
+    G, H, nq, nk = 3, 2, 70, 100
+    E = H * 64
+    q, k, v = (rows_with_max(n, E, row_max if c in which else 1.0, seed=40 + i)
+               for i, (c, n) in enumerate((("q", G * nq), ("k", G * nk), ("v", G * nk))))
+    mask = torch.zeros(G, nk, dtype=torch.bool)
+    mask[1, 60:] = True
+    mask[2, 5] = True
+    kv_len = torch.tensor([nk, 60, nk], dtype=torch.int32)
+    out = _x2h_attention(ops, q, k, v, G, H, nq, nk, kv_len, mask)
+    assert torch.isfinite(out).all()
+    err, bar = _per_row_error(out, q, k, v, G, H, nq, nk, mask)
+    bad = err > bar
+    assert not bad.any(), (float((err / bar).max()), [tuple(i) for i in bad.nonzero()[:4].tolist()])
+
+
+@pytest.mark.parametrize("row_max", [2.0 ** -18, 2.0 ** -20, 2.0 ** -24])
+def test_attention_x2h_small_magnitude_floor(ops, row_max):
+    """Below max |v| = 2^-14 the fp16 terms of v are subnormal and keep an absolute resolution of 2^-36: the error relative to
+    max |v| grows as ~2^-38 / max |v|.  Pinned: inside fp32 class (5e-6) down to 2^-18, past it by 2^-24, and the absolute
+    error within 2^-34 everywhere (the range comments of ff_attention_x2h.hip and faceformer_hip.h state this floor)."""
+    G, H, nq, nk = 2, 2, 64, 100
+    E = H * 64
+    q, k, v = rnd(G * nq, E, seed=50), rnd(G * nk, E, seed=51), rows_with_max(G * nk, E, row_max, seed=52)
+    out = _x2h_attention(ops, q, k, v, G, H, nq, nk)
+    err, _ = _per_row_error(out, q, k, v, G, H, nq, nk)
+    assert float(err.max()) * row_max < 2.0 ** -34, float(err.max())
+    if row_max >= FP16_FLOOR:
+        assert float(err.max()) <= 5e-6, float(err.max())
+    if row_max <= 2.0 ** -24:
+        assert float(err.max()) > 5e-6, float(err.max())
+
+
+@pytest.mark.parametrize("nk", [1, 31, 32, 33, 287, 288, 289])
+def test_attention_x2h_key_count_edges_and_rows_past_kv_len(ops, nk):
+    """Key counts at the plane layout's edges (one key, 32-key tiles +-1, the 288-key capacity) with key masks and kv_len < nk:
+    fp32 class per row against fp64, and the K / V rows past kv_len have no effect at all (other values there, bit-equal output).
+    nk = 289 does not fit the planes: the same call takes the f32 kernels and meets the same bar."""
+    G, H, nq = 4, 2, 40
+    E = H * 64
+    q, k, v = rnd(G * nq, E, seed=60), rnd(G * nk, E, seed=61), rnd(G * nk, E, seed=62)
+    kv_len = torch.tensor([nk, max(1, nk - 1), max(1, nk // 2), max(1, nk - 32)], dtype=torch.int32)
+    mask = torch.arange(nk)[None, :] >= kv_len[:, None]
+    if nk > 2:
+        mask[0, 1] = True
+    if kv_len[3] > 1:
+        mask[3, 0] = True
+    out = _x2h_attention(ops, q, k, v, G, H, nq, nk, kv_len, mask)
+    err, bar = _per_row_error(out, q, k, v, G, H, nq, nk, mask)
+    assert bool((err <= bar).all()), float((err / bar).max())
+    past = (torch.arange(nk)[None, :] >= kv_len[:, None]).reshape(-1)
+    if past.any():
+        k2, v2 = k.clone(), v.clone()
+        k2[past] = rnd(int(past.sum()), E, seed=63, scale=300.0)
+        v2[past] = rnd(int(past.sum()), E, seed=64, scale=300.0)
+        assert torch.equal(_x2h_attention(ops, q, k2, v2, G, H, nq, nk, kv_len, mask), out)
+
+
+def test_attention_x2h_more_than_65535_head_pairs(ops):
+    """8193 groups x 8 heads = 65544 (group, head) pairs, more than one launch's grid.y: split_kv covers them in slices (it
+    rejected the call before) and the 2 x fp16 kernel reads every pair's planes -- checked on every row against fp64."""
+    G, H, nq, nk = 8193, 8, 2, 5
+    E = H * 64
+    q, k, v = rnd(G * nq, E, seed=70), rnd(G * nk, E, seed=71), rnd(G * nk, E, seed=72)
+    kv_len = torch.tensor([nk - (g % 3) for g in range(G)], dtype=torch.int32)
+    mask = torch.arange(nk)[None, :] >= kv_len[:, None]
+    out = _x2h_attention(ops, q, k, v, G, H, nq, nk, kv_len, mask)
+    torch.cuda.empty_cache()
+    err, bar = _per_row_error(out, q, k, v, G, H, nq, nk, mask)
+    assert bool((err <= bar).all()), (float((err / bar).max()), (err > bar).nonzero()[:4].tolist())
+    assert float(err[-1].max()) <= 5e-6     # the last wireframe: pairs 65536..65543
 
 
 def test_attention_online_softmax_rescale_branch(ops, attn_algo):
