@@ -21,6 +21,10 @@
 // ~2^-38 / max |row|: measured within 5e-6 of max |v| down to max |v| = 2^-18, ~1e-4 at 2^-24 (tests/test_hip_ops.py).  Keys in
 // [kv_len, nk) are split as they are (finite values: no effect, the bias masks them); keys past nk are zero in the planes.
 // More than 65535 (group, head) pairs: ff_attention_split_kv launches slices of at most 65535 (grid.y).
+//
+// One term (NT = 1, ff_attn_desc.kv_terms = 1, the split kind "fp16"): the same kernel on the FIRST planes only, fp16(k) and fp16(v) --
+// fp16(q scale) fp16(K)^T in one MFMA chain (times log2 e in fp32), fp32 online softmax, fp16(P) fp16(V): 8 MFMAs per 32 x 32 item instead of 24.  Only
+// K1 and V1t are copied (75 KB of LDS instead of 146 KB).
 #include <atomic>
 
 #include "ff_common.h"
@@ -39,9 +43,24 @@ constexpr int XK_VROW = 584;                       // bytes of a V^T row (288 + 
 constexpr int XK_K_BYTES = XK_KEYS * XK_KROW;      // 36 864
 constexpr int XK_V_BYTES = 64 * XK_VROW;           // 37 376
 constexpr int XK_PLANE_BYTES = 2 * XK_K_BYTES + 2 * XK_V_BYTES;   // 148 480 = 145 KB
-constexpr int XK_LDS_BYTES = XK_PLANE_BYTES + XK_KEYS * 4;
 constexpr int XK_NW = 8;
 static_assert(XK_PLANE_BYTES % 1024 == 0, "the planes are copied in 1 KB wave-instructions");
+// one term: K1 (36 KB) and V1t rounded up to whole 1 KB copies (the last one reads 512 bytes of V2t' -- in the pair's planes -- into
+// LDS that is never read)
+constexpr int XK_V1_COPY = (XK_V_BYTES + 1023) / 1024 * 1024;   // 37 888
+constexpr int XK_PLANE1_BYTES = XK_K_BYTES + XK_V1_COPY;          // 74 752
+static_assert(XK_K_BYTES % 1024 == 0, "K1 is copied in 1 KB wave-instructions");
+// LDS image of the kernel: planes, then the key bias
+template <int NT> constexpr int xk_lds_planes() { return NT == 1 ? XK_PLANE1_BYTES : XK_PLANE_BYTES; }
+template <int NT> constexpr int xk_lds_bytes() { return xk_lds_planes<NT>() + XK_KEYS * 4; }
+// offset of V1t in the LDS image
+template <int NT> constexpr int xk_v_lds() { return NT == 1 ? XK_K_BYTES : 2 * XK_K_BYTES; }
+// Blocks per CU of the one-term kernel.  Two fit its LDS image, but they measured no faster than one (config B 33.13 vs 33.25 ms,
+// C128 2597 vs 2601 ms, inside the run-to-run spread: profiles/fp16/variants_ab.txt): one block, as the two-term kernel.
+#ifndef XK_H1_BLOCKS
+#define XK_H1_BLOCKS 1
+#endif
+template <int NT> constexpr int xk_blocks_per_cu() { return NT == 1 ? XK_H1_BLOCKS : 1; }
 
 // x (two floats) -> packed fp16 pairs of the two terms (second term at 2^11)
 __device__ __forceinline__ void split_h2(float x0, float x1, unsigned& p1, unsigned& p2) {
@@ -104,12 +123,15 @@ __device__ __forceinline__ u32x2 xk_read8(unsigned addr) {
   return v;
 }
 
-__global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_desc d, const unsigned char* __restrict__ planes,
-                                                                       long long plane_stride, int P, int c, int q_tiles) {
+template <int NT>
+__global__ __launch_bounds__(64 * XK_NW, (xk_blocks_per_cu<NT>())) void attention_x2h_kernel(ff_attn_desc d,
+    const unsigned char* __restrict__ planes, long long plane_stride, int P, int c, int q_tiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  float* const Ms = reinterpret_cast<float*>(lds + XK_PLANE_BYTES);   // additive key bias: 0 or -inf
+  constexpr int VL = xk_v_lds<NT>();
+  float* const Ms = reinterpret_cast<float*>(lds + xk_lds_planes<NT>());   // additive key bias: 0 or -inf
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
-  const float qscale = d.scale * 1.4426950408889634f;
+  // (one term: q is rounded as fp16(q scale), the contract's operand; the log2(e) of the exp2 softmax goes onto the fp32 scores)
+  const float qscale = NT == 1 ? d.scale : d.scale * 1.4426950408889634f;
   const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) unsigned char*)lds;
   const int nblk = gridDim.x;
   const int rank = (P <= nblk) ? blockIdx.x / P : 0;
@@ -121,9 +143,11 @@ __global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_de
     if (d.key_mask && tid < XK_KEYS && tid < d.nk) mbyte = d.key_mask[(size_t)g * d.mask_stride + tid];
     {   // the pair's planes: one linear copy, 1 KB per wave-instruction
       const unsigned char* src = planes + (size_t)pair * plane_stride;
-      for (int q = wave; q < XK_PLANE_BYTES / 1024; q += XK_NW)
-        __builtin_amdgcn_global_load_lds(src + (size_t)q * 1024 + lane * 16,
+      for (int q = wave; q < xk_lds_planes<NT>() / 1024; q += XK_NW) {   // (one term: K1, then V1t from its place in the planes)
+        const size_t from = (NT == 1 && q >= XK_K_BYTES / 1024) ? (size_t)q * 1024 + XK_K_BYTES : (size_t)q * 1024;
+        __builtin_amdgcn_global_load_lds(src + from + lane * 16,
                                          (__attribute__((address_space(3))) void*)(lds + q * 1024), 16, 0, 0);
+      }
     }
     if (tid < XK_KEYS) Ms[tid] = (tid >= nk || mbyte != 0) ? -INFINITY : 0.f;
     __syncthreads();   // (waits for the LDS-DMA: it counts in vmcnt)
@@ -148,7 +172,7 @@ __global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_de
           split_h2(b.x * qscale, b.y * qscale, p1[2], p2[2]);
           split_h2(b.z * qscale, b.w * qscale, p1[3], p2[3]);
           q1[ks] = u32x4{p1[0], p1[1], p1[2], p1[3]};
-          q2[ks] = u32x4{p2[0], p2[1], p2[2], p2[3]};
+          q2[ks] = u32x4{p2[0], p2[1], p2[2], p2[3]};   // (one term: unused, removed by the compiler)
         }
       }
       float m_run = -INFINITY, l_run = 0.f;
@@ -167,6 +191,11 @@ __global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_de
         for (int ks = 0; ks < 4; ++ks) {
           const unsigned off = (((unsigned)(2 * ks + half)) ^ sw) << 4;
           u32x4 k1 = xk_read16(ka + off);
+          if (NT == 1) {
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(k1)::"memory");
+            sm = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, k1), __builtin_bit_cast(f16x8, q1[ks]), sm, 0, 0, 0);
+            continue;
+          }
           u32x4 k2 = xk_read16(ka + XK_K_BYTES + off);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(k1), "+v"(k2)::"memory");   // (ties the fragments to the wait: the MFMAs stay behind it)
           sm = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, k1), __builtin_bit_cast(f16x8, q1[ks]), sm, 0, 0, 0);
@@ -179,7 +208,7 @@ __global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_de
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const float bias = Ms[kt * 32 + 8 * (e >> 2) + 4 * half + (e & 3)];
-          s[e] = sm[e] + ss[e] * (1.0f / 2048.0f) + bias;
+          s[e] = (NT == 1 ? sm[e] * 1.4426950408889634f : sm[e] + ss[e] * (1.0f / 2048.0f)) + bias;
           tmax = fmaxf(tmax, s[e]);
         }
         tmax = ff_halves_max(tmax);
@@ -193,7 +222,10 @@ __global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_de
         m_run = m_new;
         if (!__all(alpha == 1.0f)) {
 #pragma unroll
-          for (int e = 0; e < 16; ++e) { om[0][e] *= alpha; om[1][e] *= alpha; os[0][e] *= alpha; os[1][e] *= alpha; }
+          for (int e = 0; e < 16; ++e) {
+            om[0][e] *= alpha; om[1][e] *= alpha;
+            if (NT == 2) { os[0][e] *= alpha; os[1][e] *= alpha; }
+          }
         }
         // ---- weights -> fp16 terms: step st takes registers 8 st .. 8 st + 7 (keys 16 st + 4 half + r and 16 st + 8 + 4 half + r) ----
         u32x4 p1[2], p2[2];
@@ -208,10 +240,16 @@ __global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_de
         // ---- O^T += V^T P^T ----
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          const unsigned va = lds0 + 2 * XK_K_BYTES + (dt * 32 + l32) * XK_VROW + (kt * 32 + 4 * half) * 2;
+          const unsigned va = lds0 + VL + (dt * 32 + l32) * XK_VROW + (kt * 32 + 4 * half) * 2;
 #pragma unroll
           for (int st = 0; st < 2; ++st) {
             u32x2 v1a = xk_read8(va + 32 * st), v1b = xk_read8(va + 32 * st + 16);
+            if (NT == 1) {
+              asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v1a), "+v"(v1b)::"memory");
+              const u32x4 v1 = u32x4{v1a.x, v1a.y, v1b.x, v1b.y};
+              om[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, v1), __builtin_bit_cast(f16x8, p1[st]), om[dt], 0, 0, 0);
+              continue;
+            }
             u32x2 v2a = xk_read8(va + XK_V_BYTES + 32 * st), v2b = xk_read8(va + XK_V_BYTES + 32 * st + 16);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v1a), "+v"(v1b), "+v"(v2a), "+v"(v2b)::"memory");
             const u32x4 v1 = u32x4{v1a.x, v1a.y, v1b.x, v1b.y}, v2 = u32x4{v2a.x, v2a.y, v2b.x, v2b.y};
@@ -232,7 +270,7 @@ __global__ __launch_bounds__(64 * XK_NW, 1) void attention_x2h_kernel(ff_attn_de
           for (int g4 = 0; g4 < 4; ++g4) {
             f32x4 a;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] = (om[dt][g4 * 4 + r] + os[dt][g4 * 4 + r] * (1.0f / 2048.0f)) * inv;
+            for (int r = 0; r < 4; ++r) a[r] = (NT == 1 ? om[dt][g4 * 4 + r] : om[dt][g4 * 4 + r] + os[dt][g4 * 4 + r] * (1.0f / 2048.0f)) * inv;
             ff_st16(op + dt * 32 + 8 * g4, a);
           }
       }
@@ -247,27 +285,36 @@ size_t ff_attention_planes_stride() { return (size_t)XK_PLANE_BYTES; }
 bool ff_attention_x2h_ok(const ff_attn_desc& d) { return d.nk > 0 && d.nk <= XK_KEYS && !d.causal; }
 
 // (internal: ff_attention hands eligible launches with planes over)
-int ff_attention_x2h_launch(const ff_attn_desc& d, const void* planes, long long plane_stride, hipStream_t st) {
+namespace {
+template <int NT>
+int x2h_launch(const ff_attn_desc& d, const void* planes, long long plane_stride, hipStream_t st) {
   static std::atomic<bool> attr_done[16] = {};
   int dev = 0;
   FF_CHECK_HIP(hipGetDevice(&dev));
   if (dev < 0 || dev >= 16 || !attr_done[dev].load(std::memory_order_acquire)) {
-    FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x2h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     XK_LDS_BYTES));
+    FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x2h_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     xk_lds_bytes<NT>()));
     if (dev >= 0 && dev < 16) attr_done[dev].store(true, std::memory_order_release);
   }
   const long gh = (long)d.num_groups * d.num_heads;
   FF_CHECK_ARG(gh < 2147483647L, "ff_attention: too many (group, head) pairs");
-  const int P = (int)gh, cus = ff_num_cus(), qt32 = ff_cdiv(d.nq, 32);
-  int c = P <= cus ? cus / P : 1;
+  // block slots: xk_blocks_per_cu per CU (one for both kernels, see XK_H1_BLOCKS)
+  const int P = (int)gh, slots = ff_num_cus() * xk_blocks_per_cu<NT>(), qt32 = ff_cdiv(d.nq, 32);
+  int c = P <= slots ? slots / P : 1;
   const int cmax = ff_cdiv(qt32, XK_NW);   // blocks beyond one query tile per wave are idle
   if (c > cmax) c = cmax;
   if (c < 1) c = 1;
-  const int nblocks = P <= cus ? P * c : cus;
-  hipLaunchKernelGGL(attention_x2h_kernel, dim3(nblocks), dim3(64 * XK_NW), XK_LDS_BYTES, st, d,
+  const int nblocks = P <= slots ? P * c : slots;
+  hipLaunchKernelGGL(attention_x2h_kernel<NT>, dim3(nblocks), dim3(64 * XK_NW), xk_lds_bytes<NT>(), st, d,
                      static_cast<const unsigned char*>(planes), plane_stride, P, c, qt32);
   FF_CHECK_LAUNCH();
   return FF_OK;
+}
+}  // namespace
+
+int ff_attention_x2h_launch(const ff_attn_desc& d, const void* planes, long long plane_stride, hipStream_t st) {
+  FF_CHECK_ARG(d.kv_terms >= 0 && d.kv_terms <= 2, "ff_attention: kv_terms=%d (0 / 2 both planes, 1 the first)", d.kv_terms);
+  return d.kv_terms == 1 ? x2h_launch<1>(d, planes, plane_stride, st) : x2h_launch<2>(d, planes, plane_stride, st);
 }
 
 extern "C" size_t ff_attention_planes_bytes(int num_groups, int num_heads) {

@@ -121,7 +121,8 @@ int check_model(const ff_model* m) {
                    m->num_dec_layers <= FF_MAX_LAYERS, "model: bad layer counts");
   FF_CHECK_ARG(m->in_dim > 0 && (m->in_dim & 3) == 0, "model: in_dim=%d must be a multiple of 4", m->in_dim);
   FF_CHECK_ARG(m->num_token > 0, "model: num_token");
-  FF_CHECK_ARG(m->split_kind == 0 || m->split_kind == 1, "model: split_kind=%d (0 = bf16 x 3 planes, 1 = fp16 x 2 planes)", m->split_kind);
+  FF_CHECK_ARG(m->split_kind >= 0 && m->split_kind <= 2, "model: split_kind=%d (0 = bf16 x 3 planes, 1 = fp16 x 2 planes, 2 = one fp16 plane)",
+               m->split_kind);
   return FF_OK;
 }
 
@@ -150,8 +151,9 @@ int gemm_or_x3(const ff_model* m, const ff_decode_params* prm, const void* plane
                const float* W, int ldw, const float* bias, const float* res, int ldr, float* C, int ldc, int M,
                int N, int K, int act, hipStream_t st) {
   if (planes && x3_wins(prm, M, N, K, lda) && (!A2 || (n_split % 128) == 0))
-    return m->split_kind == 1 ? ff_gemm_x2h(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st)
-                              : ff_gemm_x3(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st);
+    return m->split_kind == 2 ? ff_gemm_h1(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st)
+           : m->split_kind == 1 ? ff_gemm_x2h(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st)
+                                : ff_gemm_x3(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st);
   return gemm(A, lda, A2, n_split, W, ldw, bias, res, ldr, C, ldc, M, N, K, act, st);
 }
 
@@ -287,8 +289,9 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
   b.mem_pos = bp.take<float>((size_t)p->N * S * E);
   for (int l = 0; l < m->num_dec_layers; ++l) b.kvc[l] = bp.take<float>((size_t)p->N * S * 2 * E);
   // the package default's cross-attention runs on the fp16 matrix cores as well (ff_attention_x2h.hip): K | V of every (wireframe,
-  // head) pair split once per batch into fp16 planes, 145 KB per pair and layer (key sets of at most 288 rows)
-  const bool planes = kn.x2h_attn && m->split_kind == 1 && p->x3_min_rows > 0 && S <= 288 && m->dec[0].in_proj_planes != nullptr;
+  // head) pair split once per batch into fp16 planes, 145 KB per pair and layer (key sets of at most 288 rows); the one-term kind
+  // ("fp16", split_kind 2) uses the same planes and reads their first terms only
+  const bool planes = kn.x2h_attn && (m->split_kind == 1 || m->split_kind == 2) && p->x3_min_rows > 0 && S <= 288 && m->dec[0].in_proj_planes != nullptr;
   for (int l = 0; l < m->num_dec_layers; ++l)
     b.kvp[l] = planes ? bp.take<unsigned char>(ff_attention_planes_bytes(p->N, m->H)) : nullptr;
   b.x0_all = bp.take<float>((size_t)T * Btot * E);
@@ -399,8 +402,9 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
     d.row_table = table; d.ld_row_table = ldt; d.row_div = Bc; d.row_cols = tcols;
     d.ln_stats_out = st_out;
     if (planes && x3_wins(prm, M, N, K, lda) && (!st_in || K == 512) && (!table || (tcols & 3) == 0))
-      return m->split_kind == 1 ? ff_gemm_x2h_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st)
-                                : ff_gemm_x3_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st);
+      return m->split_kind == 2 ? ff_gemm_h1_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st)
+             : m->split_kind == 1 ? ff_gemm_x2h_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st)
+                                  : ff_gemm_x3_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st);
     return ff_gemm_f32_ln(&d, st);
   };
 
@@ -519,6 +523,7 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
       d.scale = 0.125f;
       if (bufs.kvp[l] && x3_wins(prm, R, 3 * E, E, E))   // (the steps whose projections take the split products)
         d.kv_planes = bufs.kvp[l] + (size_t)ck.w0 * H * (ff_attention_planes_bytes(1, H) / H);
+      d.kv_terms = m->split_kind == 2 ? 1 : 0;
       FF_RETURN_IF(ff_attention(&d, st));
     }
     if (fuse) {

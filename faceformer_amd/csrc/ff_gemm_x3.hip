@@ -125,8 +125,10 @@ __global__ void split_weight_kernel(const float* __restrict__ W, int ldw, int N,
   }
 }
 
-// fp16 terms of the same layout ([plane][k / 16][row][k % 16], two planes): w1 = fp16(w), w2' = fp16((w - w1) 2^11)
-__global__ void split_weight_fp16_kernel(const float* __restrict__ W, int ldw, int N, int K, unsigned short* __restrict__ P) {
+// fp16 terms of the same layout ([plane][k / 16][row][k % 16], two planes): w1 = fp16(w), w2' = fp16((w - w1) 2^11);
+// nplanes = 1 writes w1 alone (the operand of the one-term kind "fp16": ff_split_weight_fp16)
+__global__ void split_weight_fp16_kernel(const float* __restrict__ W, int ldw, int N, int K, unsigned short* __restrict__ P,
+                                         int nplanes) {
   typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   const size_t n2 = (size_t)N * (K / 2);
@@ -139,7 +141,7 @@ __global__ void split_weight_fp16_kernel(const float* __restrict__ W, int ldw, i
     const size_t plane = (size_t)N * K / 2;
     const size_t at = ((c >> 4) * (size_t)N + row) * 8 + ((c & 15) >> 1);
     o[at] = __builtin_bit_cast(unsigned, h);
-    o[plane + at] = __builtin_bit_cast(unsigned, l);
+    if (nplanes == 2) o[plane + at] = __builtin_bit_cast(unsigned, l);
   }
 }
 
@@ -204,8 +206,17 @@ constexpr int X3_BN = 128, X3_BK = 16;
 #ifndef X3_RING_F32
 #define X3_RING_F32 3
 #endif
+// One fp16 term (NT = 1, the opt-in split kind "fp16"): a slice is one 8 KB slot (4 KB of rows + 4 KB of ONE weight plane) and
+// two MFMAs per wave -- a third of the fp16x2 loop's matrix-core time per slice, so more slices must be in flight to cover the
+// same DMA round trip.  Measured in the fp16 decode (profiles/fp16/variants_ab.txt): three slots are 3.4 % (config B) / 3.6 % (C128)
+// slower than four, six the same as four within the run-to-run spread (+0.8 % / -0.6 %): four slots, 32 KB per block.
+#ifndef X3_RING_1
+#define X3_RING_1 4
+#endif
 template <int MODE, int NT>
-constexpr int x3_ring() { return NT == 3 ? 3 : (MODE == 1 ? X3_RING_H1 : (MODE == 3 ? X3_RING_H3 : X3_RING_H)); }
+constexpr int x3_ring() {
+  return NT == 3 ? 3 : (NT == 1 ? X3_RING_1 : (MODE == 1 ? X3_RING_H1 : (MODE == 3 ? X3_RING_H3 : X3_RING_H)));
+}
 constexpr int X3_STAT_BYTES = 16384;   // MODE 1: one 4 KB patch per wave (32 rows x 16 segments x (mean, M2))
 
 // BM: 128 (4 x 1 waves) or 64 (2 x 2 waves).  MODE: 0 plain, 1 LayerNorm consumer (rows normalised before the split),
@@ -220,6 +231,9 @@ constexpr int X3_STAT_BYTES = 16384;   // MODE 1: one 4 KB patch per wave (32 ro
 #ifndef X3_LN_H_BLOCKS      // blocks per CU of the LayerNorm-consuming fp16 form (MODE 1, NT 2).  Round 6 tried 3 (168 registers, spills on the
 #define X3_LN_H_BLOCKS 2    // tile-change paths only; 52 KB of LDS each): +5 % on the isolated launch, -1.5 % on config B / C128 end to end -- stays at 2 (199 registers)
 #endif
+// NT = 1: no second accumulator set and a third of the fragment registers, but FOUR blocks per CU (128 registers) do not fit:
+// the compiler spills 156-533 registers per form (MODE 0 / 2 / 3), inside the K loop.  At the other kinds' 168 / 256 registers
+// (three blocks; two for the LayerNorm consumers) the forms spill 0-19 registers -- outside the MFMA runs (tools/check_x3_asm.py).
 template <int MODE, int NT>
 constexpr int x3_blocks_per_cu() { return MODE == 3 ? 2 : (MODE == 1 ? (NT == 2 ? X3_LN_H_BLOCKS : 2) : 3); }
 template <int BM, int MODE, int NT>
@@ -231,9 +245,11 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
   constexpr int NP = NPA + NT;              // DMA pieces per wave and slice
   constexpr int A_REG = BM * 64, SLOT = A_REG + NT * BN * 32;
   constexpr int RING = x3_ring<MODE, NT>();
-  constexpr int NPROD = NT == 3 ? 6 : 3;    // partial products per fp32 product
+  constexpr int NPROD = NT == 3 ? 6 : (NT == 2 ? 3 : 1);    // partial products per fp32 product
   constexpr int NMF = NPROD * NI;           // MFMAs per wave and slice
   constexpr int NRD = 2 + NT * NI;          // fragment reads per wave and slice
+  constexpr int NG = NMF > NRD ? NMF : NRD; // issue gaps per slice: one per MFMA (NT = 1: more reads than MFMAs -- the extra gaps
+                                            // carry reads, conversions and DMA pieces without a matrix-core instruction)
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -448,6 +464,15 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
         x0 = x3_fmul(x3_fsub(x0, mean_s), rstd_s);
         x1 = x3_fmul(x3_fsub(x1, mean_s), rstd_s);
       }
+      if (NT == 1) {     // one fp16 term: fp16(x), round to nearest (MODE 3: of the raw row at 2^-6, as below)
+        if (MODE == 3) {
+          x0 = x3_fmul(x0, 0.015625f);
+          x1 = x3_fmul(x1, 0.015625f);
+        }
+        p1_[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, f16x2));
+        asm volatile("" : "+v"(p1_[q]));
+        return;
+      }
       if (NT == 2) {     // fp16 terms: x1 = fp16(x) (round to nearest), residual exact in fp32
         if (MODE == 3) {   // RAW (un-normalised) rows: 2^-6 keeps |x| up to 4.2e6 inside fp16's range (undone, exactly, per tile)
           x0 = x3_fmul(x0, 0.015625f);
@@ -481,6 +506,7 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
       r_[q][0] = x3_fsub(x0, __builtin_bit_cast(float, p1_[q] << 16));
       r_[q][1] = x3_fsub(x1, __builtin_bit_cast(float, p1_[q] & 0xffff0000u));
       asm volatile("" : "+v"(p1_[q]), "+v"(r_[q][0]), "+v"(r_[q][1]));
+    } else if (NT == 1) {   // (nothing: one term)
     } else if (NT == 2) {   // second term, scaled by 2^11 (exact)
 #if defined(X3_EXP_NOSPLIT)
       p2_[q] = __builtin_bit_cast(unsigned, r_[q][0]);
@@ -507,7 +533,7 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
   };
   auto split_collect = [&](u32x4 (&dst)[3]) {
     dst[0] = u32x4{p1_[0], p1_[1], p1_[2], p1_[3]};
-    dst[1] = u32x4{p2_[0], p2_[1], p2_[2], p2_[3]};
+    if (NT >= 2) dst[1] = u32x4{p2_[0], p2_[1], p2_[2], p2_[3]};
     if (NT == 3) dst[2] = u32x4{p3_[0], p3_[1], p3_[2], p3_[3]};
   };
 
@@ -537,7 +563,8 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
     for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {   // (fp16 terms: the small products were accumulated at 2^11 times their weight)
-        if (NT == 2 && MODE == 3) acc[ni][e] = acc[ni][e] * 64.0f + accs[ni][e] * (64.0f / 2048.0f);   // (... and the rows at 2^-6)
+        if (NT == 1) { if (MODE == 3) acc[ni][e] *= 64.0f; }   // (one term: one accumulator; MODE 3 rows at 2^-6)
+        else if (NT == 2 && MODE == 3) acc[ni][e] = acc[ni][e] * 64.0f + accs[ni][e] * (64.0f / 2048.0f);   // (... and the rows at 2^-6)
         else acc[ni][e] += NT == 2 ? accs[ni][e] * (1.0f / 2048.0f) : accs[ni][e];
         accs[ni][e] = 0.f;
       }
@@ -747,9 +774,9 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
   constexpr int PA[6] = {NT == 3 ? 2 : 1, NT == 3 ? 1 : 0, 0, 1, 0, 0}, PB[6] = {0, 1, NT == 3 ? 2 : 0, 0, 1, 0};
   // where the split steps and the DMA pieces go among the MFMA gaps
   constexpr int SP0 = NI == 4 ? 5 : 3;            // first split step (the two row reads are the oldest of SP0 + 1 reads)
-  constexpr int SPG = (8 + (NMF - SP0) - 1) / (NMF - SP0);   // split steps per gap (1 with six products, 3 with three)
+  constexpr int SPG = (8 + (NG - SP0) - 1) / (NG - SP0);   // split steps per gap (1 with six products, 3 with three, 8 with one)
   constexpr int SPC = SP0 + (8 + SPG - 1) / SPG;  // gap behind which the split is complete
-  constexpr int DM0 = NI == 4 ? NRD : NMF - NP;   // first DMA piece
+  constexpr int DM0 = NI == 4 ? NRD : NG - NP;    // first DMA piece
   int s0 = 0, s1 = 1;   // ring slots of slice s, s + 1  (slice s + RING goes to slot s0)
   const int total = 2 * (u1 - u0);
 #ifdef X3_EXP_STAMP
@@ -771,13 +798,16 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
       }
       // NMF MFMAs of slice s; in their gaps: the reads of slice s + 1 (one per gap), the split of its rows, the DMA of s + 3
 #pragma unroll
-      for (int i = 0; i < NMF; ++i) {
+      for (int i = 0; i < NG; ++i) {
 #if defined(X3_EXP_MFMA_ORDER)     // probe: the x1 y1 products between the two small ones (same-accumulator MFMAs four apart, not two)
         const int t = NT == 2 ? (i / NI == 1 ? 2 : (i / NI == 2 ? 1 : 0)) : i / NI, ni = i % NI;
 #else
         const int t = i / NI, ni = i % NI;
 #endif
-        if (NT == 3) {
+        if (NT == 1) {     // one product per slice and column tile: a single accumulator chain
+          if (i < NMF) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[u][0][ni]),
+                                                                        __builtin_bit_cast(f16x8, af[u][0]), acc[ni], 0, 0, 0);
+        } else if (NT == 3) {
           if (t < 5) accs[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[u][PB[t]][ni]),
                                                                         __builtin_bit_cast(bf16x8, af[u][PA[t]]), accs[ni], 0, 0, 0);
           else acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[u][PB[t]][ni]),
@@ -811,10 +841,10 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
         }
         if (i == SPC) split_collect(af[u ^ 1]);
         if (i >= DM0 && i < DM0 + NP) issue_piece(i - DM0, s0);
-        if (i == NMF - 1) advance();
+        if (i == NG - 1) advance();
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (SPC >= NMF) split_collect(af[u ^ 1]);
+      if (SPC >= NG) split_collect(af[u ^ 1]);
 #ifdef X3_EXP_STAMP
       if (stamping) st_t1 = __builtin_readcyclecounter();
 #endif
@@ -1537,7 +1567,13 @@ int x3_launch(X3Args g, int mode, hipStream_t st, bool f32 = false, int bn = X3_
     return dma_f32_launch_mode<BM, 0>(g, (int)grid, st);
   }
   FFProfScope prof(FF_CAT_GEMM_X3, 2.0 * M * N * K, st);
-  ff_prof_add_bytes(FF_CAT_GEMM_X3, 4.0 * (double)M * K + 2.0 * (g.nt == 2 ? 2 : 3) * (double)N * K + 4.0 * (double)M * N * (g.res ? 2 : 1));
+  ff_prof_add_bytes(FF_CAT_GEMM_X3, 4.0 * (double)M * K + 2.0 * g.nt * (double)N * K + 4.0 * (double)M * N * (g.res ? 2 : 1));
+  if (g.nt == 1) {
+    if (mode == 1) return x3_launch_mode<BM, 1, 1>(g, (int)grid, st);
+    if (mode == 2) return x3_launch_mode<BM, 2, 1>(g, (int)grid, st);
+    if (mode == 3) return x3_launch_mode<BM, 3, 1>(g, (int)grid, st);
+    return x3_launch_mode<BM, 0, 1>(g, (int)grid, st);
+  }
   if (g.nt == 2) {
     if (mode == 1) return x3_launch_mode<BM, 1, 2>(g, (int)grid, st);
     if (mode == 2) return x3_launch_mode<BM, 2, 2>(g, (int)grid, st);
@@ -1615,7 +1651,20 @@ extern "C" int ff_split_weight_fp16x2(const float* W, int ldw, int N, int K, voi
   const size_t n2 = (size_t)N * (K / 2);
   const int grid = (int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096);
   hipLaunchKernelGGL(split_weight_fp16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K,
-                     static_cast<unsigned short*>(planes));
+                     static_cast<unsigned short*>(planes), 2);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+extern "C" size_t ff_split_weight_fp16_bytes(int N, int K) { return (size_t)N * K * sizeof(unsigned short); }
+
+extern "C" int ff_split_weight_fp16(const float* W, int ldw, int N, int K, void* plane, ff_stream_t stream) {
+  FF_CHECK_ARG(W && plane && N > 0 && K > 0 && (K & 15) == 0 && ldw >= K, "ff_split_weight_fp16: bad arguments (K %% 16)");
+  FF_CHECK_ARG(ff_aligned16(plane), "ff_split_weight_fp16: the plane must be 16-byte aligned");
+  const size_t n2 = (size_t)N * (K / 2);
+  const int grid = (int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096);
+  hipLaunchKernelGGL(split_weight_fp16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K,
+                     static_cast<unsigned short*>(plane), 1);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
@@ -1673,6 +1722,12 @@ extern "C" int ff_gemm_x2h(const float* A, int lda, const float* A2, int n_split
                            int K, int act, ff_stream_t stream) {
   return gemm_split_plain(2, "ff_gemm_x2h", A, lda, A2, n_split, w_planes, bias, residual, ldr, C, ldc, M, N, K, act, stream);
 }
+// one fp16 product (split kind "fp16"): reads plane 0 only -- ff_split_weight_fp16's plane, or the first plane of ff_split_weight_fp16x2's
+extern "C" int ff_gemm_h1(const float* A, int lda, const float* A2, int n_split, const void* w_plane,
+                          const float* bias, const float* residual, int ldr, float* C, int ldc, int M, int N,
+                          int K, int act, ff_stream_t stream) {
+  return gemm_split_plain(1, "ff_gemm_h1", A, lda, A2, n_split, w_plane, bias, residual, ldr, C, ldc, M, N, K, act, stream);
+}
 
 // x3_ln_linear -- why the consumer's normalisation may move into the epilogue.  LN(x) W'^T = rstd (x W'^T - mean s), s = the row
 // sums of W': the K loop then is the PLAIN loop (no statistics patch in LDS, no normalising VALU work), and the row statistics
@@ -1725,4 +1780,8 @@ extern "C" int ff_gemm_x3_ln(const ff_gemm_ln_desc* d, const void* w_planes, int
 extern "C" int ff_gemm_x2h_ln(const ff_gemm_ln_desc* d, const void* w_planes, int plane_rows, int row0, const float* w_colsum,
                               ff_stream_t stream) {
   return gemm_split_ln(2, d, w_planes, plane_rows, row0, w_colsum, stream);
+}
+extern "C" int ff_gemm_h1_ln(const ff_gemm_ln_desc* d, const void* w_plane, int plane_rows, int row0, const float* w_colsum,
+                             ff_stream_t stream) {
+  return gemm_split_ln(1, d, w_plane, plane_rows, row0, w_colsum, stream);
 }

@@ -177,12 +177,12 @@ class PathEngine:
         self.requested_kind = split_kind
         if bf16_split_planes:
             self._make_planes(m, tensors, n_dec, E, split_kind, ln_in_epilogue)
-            if split_kind == "fp16x2":
+            if split_kind in ("fp16x2", "fp16"):   # (both kinds feed the same operand classes to fp16 terms: the same bounds)
                 bad = self._check_fp16_range(tensors, n_dec, E)
                 if bad:
                     import warnings
-                    warnings.warn("faceformer_amd: split_kind='fp16x2' needs every operand of the split products inside fp16's range; "
-                                  "this model's bounds are not (%s) -- binding the bf16x3 planes instead" % bad)
+                    warnings.warn("faceformer_amd: split_kind=%r needs every operand of the split products inside fp16's range; "
+                                  "this model's bounds are not (%s) -- binding the bf16x3 planes instead" % (split_kind, bad))
                     self.split_kind = "bf16x3"
                     self._planes = {}
                     self._make_planes(m, tensors, n_dec, E, "bf16x3", ln_in_epilogue)
@@ -201,8 +201,8 @@ class PathEngine:
             _L.check(self._lib.ff_gemm_prepare_stream(_stream()), "ff_gemm_prepare_stream")
 
     def _make_planes(self, m, tensors, n_dec, E, kind, ln_in_epilogue):
-        """Split planes of the decoder projections: three exact bf16 planes per weight (+1.5x their bytes) or two fp16 planes
-        (+1x), split once here -- ff_decode then runs the large steps' projections on the 16-bit matrix cores (x3_min_rows);
+        """Split planes of the decoder projections: three exact bf16 planes per weight (+1.5x their bytes), two fp16 planes
+        (+1x) or one fp16 plane (kind "fp16", +0.5x), split once here -- ff_decode then runs the large steps' projections on the 16-bit matrix cores (x3_min_rows);
         re-bound after in-place weight updates (pointers_current)."""
         for i in range(n_dec):
             for field, name in (("in_proj_planes", "self_attn.in_proj_weight"), ("lin1_planes", "linear1.weight"),

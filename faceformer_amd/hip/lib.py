@@ -18,7 +18,7 @@ FF_STOP_EACH_EOS = 512
 FF_NO_L0_FOLD = 1024
 FF_NO_POINTER_FOLD = 2048
 FF_RETIRE_FINISHED = 4096
-FF_ABI_VERSION = 104   # include/faceformer_hip.h: the struct layouts below are this version's
+FF_ABI_VERSION = 105   # include/faceformer_hip.h: the struct layouts below are this version's
 
 fptr = C.c_void_p  # device pointers travel as integers
 
@@ -41,6 +41,7 @@ class AttnDesc(C.Structure):
         ("causal", C.c_int),
         ("scale", C.c_float),
         ("kv_planes", fptr),
+        ("kv_terms", C.c_int),
     ]
 
 
@@ -166,6 +167,11 @@ SIGNATURES = {
     "ff_gemm_x2h": (C.c_int, [fptr, C.c_int, fptr, C.c_int, fptr, fptr, fptr, C.c_int, fptr, C.c_int,
                               C.c_int, C.c_int, C.c_int, C.c_int, fptr]),
     "ff_gemm_x2h_ln": (C.c_int, [C.POINTER(GemmLnDesc), fptr, C.c_int, C.c_int, fptr, fptr]),
+    "ff_split_weight_fp16_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ff_split_weight_fp16": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, fptr, fptr]),
+    "ff_gemm_h1": (C.c_int, [fptr, C.c_int, fptr, C.c_int, fptr, fptr, fptr, C.c_int, fptr, C.c_int,
+                             C.c_int, C.c_int, C.c_int, C.c_int, fptr]),
+    "ff_gemm_h1_ln": (C.c_int, [C.POINTER(GemmLnDesc), fptr, C.c_int, C.c_int, fptr, fptr]),
     "ff_set_x3_tuning": (C.c_int, [C.c_int]),
     "ff_attention": (C.c_int, [C.POINTER(AttnDesc), fptr]),
     "ff_attention_general": (C.c_int, [C.POINTER(AttnGeneralDesc), fptr]),

@@ -161,7 +161,8 @@ def linear_ln(x, weight, bias=None, act=0, residual=None, stats_in=None, eps=1e-
 @_on_tensor_device
 def linear_x3_ln(x, planes, bias=None, act=0, residual=None, stats_in=None, eps=1e-5, row_table=None, row_div=1,
                  row_cols=0, want_stats=False, out=None, row0=0, rows=0, colsum=None):
-    """ff_gemm_x3_ln: linear_ln() on the bf16 matrix cores with fp32 accuracy; `planes` = split_weight(folded weight).
+    """ff_gemm_x3_ln: linear_ln() on the bf16 matrix cores with fp32 accuracy; `planes` = split_weight(folded weight) (fp16 planes:
+    ff_gemm_x2h_ln, or ff_gemm_h1_ln -- one fp16 product -- for the one plane of kind "fp16").
     row0 / rows: use only weight rows [row0, row0 + rows) of the planes (bias, table and output then have `rows` columns).
     colsum ([plane rows] row sums of the folded weight): apply the normalisation in the epilogue (plain K loop)."""
     _check_planes(planes, "planes")
@@ -194,7 +195,7 @@ def linear_x3_ln(x, planes, bias=None, act=0, residual=None, stats_in=None, eps=
     if colsum is not None:
         _dev(colsum, "colsum")
     lib = _L.load()
-    fn, who = (lib.ff_gemm_x2h_ln, "ff_gemm_x2h_ln") if planes.dtype == torch.float16 else (lib.ff_gemm_x3_ln, "ff_gemm_x3_ln")
+    fn, who = _split_fn(planes, lib, "_ln")
     _L.check(fn(C.byref(d), planes.data_ptr(), plane_rows, row0, _p(colsum), _stream()), who)
     return (out, stats) if want_stats else out
 
@@ -240,10 +241,11 @@ _attn_algo = 0      # what set_attention_algo() last set: 4 makes attention() sp
 @_on_tensor_device
 def attention(q, k, v, num_groups, num_heads, nq, nk, q_group_stride, q_inner, q_outer_stride,
               k_group_stride, k_stride, kv_len=None, key_mask=None, causal=False, scale=0.125,
-              out=None, kv_planes=None):
+              out=None, kv_planes=None, kv_terms=0):
     """Raw descriptor-level attention (see ff_attn_desc).  q/k/v/out are 2-D row tensors (views
     into wider buffers are fine: the leading dimension is taken from stride(0)).  kv_planes: split_kv(k, v, ...) of the same
-    K | V -- eligible launches then run on the fp16 matrix cores."""
+    K | V -- eligible launches then run on the fp16 matrix cores; kv_terms=1 uses their first planes only (one fp16 term per operand,
+    the split kind "fp16")."""
     _dev(q, "q"), _dev(k, "k"), _dev(v, "v")
     if kv_planes is None and _attn_algo == 4 and 0 < nk <= 288 and not causal:
         kv_planes = split_kv(k, v, num_groups, num_heads, nk, k_group_stride, k_stride)
@@ -264,6 +266,7 @@ def attention(q, k, v, num_groups, num_heads, nq, nk, q_group_stride, q_inner, q
     d.causal = 1 if causal else 0
     d.scale = scale
     d.kv_planes = _p(kv_planes)
+    d.kv_terms = kv_terms
     _L.check(_L.load().ff_attention(C.byref(d), _stream()), "ff_attention")
     return out
 
@@ -406,24 +409,28 @@ def set_gemm_tuning(min_units=2, two_per_cu_units=2048, fix_tenths=25, small_max
                                           int(small_max_rows)), "ff_set_gemm_tuning")
 
 
-SPLIT_KINDS = {"bf16x3": 0, "fp16x2": 1}     # ff_model.split_kind
+SPLIT_KINDS = {"bf16x3": 0, "fp16x2": 1, "fp16": 2}     # ff_model.split_kind ("fp16": one fp16 product, opt-in)
 
 
 @_on_tensor_device
 def split_weight(weight, kind="bf16x3"):
     """[N, K] fp32 matrix -> its split planes in the K-blocked layout [terms, K/16, N, 16]: three bf16 planes ("bf16x3",
-    planes_to_matrix(planes) == weight up to 2^-25 relative) or two fp16 planes ("fp16x2": w1 = fp16(w), w2' = fp16((w - w1) 2^11),
-    22 mantissa bits; |w| must be < 65504)."""
+    planes_to_matrix(planes) == weight up to 2^-25 relative), two fp16 planes ("fp16x2": w1 = fp16(w), w2' = fp16((w - w1) 2^11),
+    22 mantissa bits; |w| must be < 65504) or ONE fp16 plane ("fp16": fp16(w), plane 0 of "fp16x2"; one fp16 product)."""
     weight, ldw = _rows(weight, "weight")
     N, K = weight.shape
     if K % 16:
         raise ValueError("split_weight: K must be a multiple of 16")
+    if kind == "fp16":
+        planes = torch.empty((1, K // 16, N, 16), device=weight.device, dtype=torch.float16)
+        _L.check(_L.load().ff_split_weight_fp16(_p(weight), ldw, N, K, planes.data_ptr(), _stream()), "ff_split_weight_fp16")
+        return planes
     if kind == "fp16x2":
         planes = torch.empty((2, K // 16, N, 16), device=weight.device, dtype=torch.float16)
         _L.check(_L.load().ff_split_weight_fp16x2(_p(weight), ldw, N, K, planes.data_ptr(), _stream()), "ff_split_weight_fp16x2")
         return planes
     if kind != "bf16x3":
-        raise ValueError("split_weight: kind must be 'bf16x3' or 'fp16x2'")
+        raise ValueError("split_weight: kind must be one of %s" % sorted(SPLIT_KINDS))
     planes = torch.empty((3, K // 16, N, 16), device=weight.device, dtype=torch.bfloat16)
     _L.check(_L.load().ff_split_weight_bf16x3(_p(weight), ldw, N, K, planes.data_ptr(), _stream()),
              "ff_split_weight_bf16x3")
@@ -434,20 +441,30 @@ def planes_to_matrix(planes):
     """Inverse of split_weight (fp64 sum of the terms), [rows, K]."""
     kb, rows = planes.size(1), planes.size(2)
     p = planes.double()
-    total = p[0] + p[1] / 2048.0 if planes.dtype == torch.float16 else p.sum(0)
+    if planes.dtype == torch.float16:
+        total = p[0] if planes.size(0) == 1 else p[0] + p[1] / 2048.0   # (one plane: kind "fp16", fp16(w) itself)
+    else:
+        total = p.sum(0)
     return total.permute(1, 0, 2).reshape(rows, kb * 16)
 
 
 def _check_planes(p, what):
-    ok = (p.dtype == torch.bfloat16 and p.size(0) == 3) or (p.dtype == torch.float16 and p.size(0) == 2)
+    ok = (p.dtype == torch.bfloat16 and p.size(0) == 3) or (p.dtype == torch.float16 and p.size(0) in (1, 2))
     if not ok or p.dim() != 4 or p.size(3) != 16 or not p.is_contiguous():
-        raise ValueError("linear_x3: %s must be a contiguous [3, K/16, rows, 16] bf16 or [2, K/16, rows, 16] fp16 tensor "
+        raise ValueError("linear_x3: %s must be a contiguous [3, K/16, rows, 16] bf16 or [2 or 1, K/16, rows, 16] fp16 tensor "
                          "(split_weight)" % what)
+
+
+def _split_fn(planes, lib, suffix=""):
+    """The kernel entry point of a plane set: ff_gemm_x3 (bf16 x 3), ff_gemm_x2h (fp16 x 2) or ff_gemm_h1 (one fp16 plane)."""
+    name = "ff_gemm_x3" if planes.dtype == torch.bfloat16 else ("ff_gemm_h1" if planes.size(0) == 1 else "ff_gemm_x2h")
+    return getattr(lib, name + suffix), name + suffix
 
 
 @_on_tensor_device
 def linear_x3(x, planes, bias=None, act=0, residual=None, x2=None, n_split=0, out=None):
-    """linear() on the bf16 matrix cores with fp32 accuracy; `planes` comes from split_weight()."""
+    """linear() on the bf16 matrix cores with fp32 accuracy; `planes` comes from split_weight() (one fp16 plane, kind "fp16":
+    ff_gemm_h1, one fp16 product with fp32 accumulation)."""
     _check_planes(planes, "planes")
     N, K = planes.size(2), planes.size(1) * 16
     x, lda = _rows(x, "x")
@@ -467,7 +484,7 @@ def linear_x3(x, planes, bias=None, act=0, residual=None, x2=None, n_split=0, ou
     if bias is not None:
         _dev(bias, "bias")
     lib = _L.load()
-    fn, who = (lib.ff_gemm_x2h, "ff_gemm_x2h") if planes.dtype == torch.float16 else (lib.ff_gemm_x3, "ff_gemm_x3")
+    fn, who = _split_fn(planes, lib)
     _L.check(fn(_p(x), lda, _p(x2), n_split, planes.data_ptr(), _p(bias), _p(residual), ldr,
                 _p(out), ldc, M, N, K, act, _stream()), who)
     return out

@@ -75,7 +75,9 @@ class SurfaceFormerBase(nn.Module):
         # so nothing un-normalised ever meets fp16's range).
         self.x3_ln_in_epilogue = None
         # how those projections split an fp32 operand: "bf16x3" (three bf16 terms, six products) or "fp16x2" (two fp16 terms, three
-        # products: half the matrix-core work; the engine checks at bind time that the model's operand bounds fit fp16's range)
+        # products: half the matrix-core work; the engine checks at bind time that the model's operand bounds fit fp16's range).
+        # "fp16" (opt-in, main.py --fp16): ONE fp16 product with fp32 accumulation, the reference's 16-bit GPU arithmetic -- for
+        # these projections and the cross-attention only; same range check and bf16x3 fallback
         self.split_kind = SPLIT_KIND_DEFAULT
         self._engine_obj = None
 

@@ -38,11 +38,12 @@ enum ff_status {
 #define FF_HEAD_DIM 64   /* attention head width of the MFMA kernels (reference: 512 / 8); other widths: ff_attention_general */
 #define FF_MAX_LAYERS 16
 
-/* Library version (major*10000 + minor*100 + patch).  104: FF_RETIRE_FINISHED, ff_decode_params.term_lo / term_hi /
+/* Library version (major*10000 + minor*100 + patch).  105: the one-term fp16 kind -- ff_model.split_kind = 2,
+ * ff_split_weight_fp16(_bytes), ff_gemm_h1(_ln), ff_attn_desc.kv_terms (appended).  104: FF_RETIRE_FINISHED, ff_decode_params.term_lo / term_hi /
  * retire_min_shrink / slots_per_step, ff_permute_rows.  103: ff_attention_general / ff_attn_general_desc added (round 6).  101: the struct layouts of this header (round 5: ff_decode_params lost
  * chain_max_rows / flow_min_rows, FF_STOP_EACH_EOS added; round 4: ff_layer_weights grew by the ln*_planes / ln*_csum
  * pointers).  A caller built against another header must refuse to run: hip/lib.py asserts equality with FF_ABI_VERSION. */
-#define FF_ABI_VERSION 104
+#define FF_ABI_VERSION 105
 int ff_version(void);
 /* Thread-local text of the last error returned by this library ("" if none). */
 const char* ff_last_error(void);
@@ -215,6 +216,21 @@ int ff_gemm_x2h(const float* A, int lda, const float* A2, int n_split, const voi
 int ff_gemm_x2h_ln(const ff_gemm_ln_desc* desc, const void* w_planes, int plane_rows, int row0, const float* w_colsum,
                    ff_stream_t stream);
 
+/* "fp16" (ABI 105, opt-in): ONE fp16 product per fp32 product -- the arithmetic of a 16-bit autocast decode, not an fp32 one.  Both
+ * operands are rounded to nearest fp16 (the weight when its plane is made, the activation rows in registers; the epilogue form
+ * (w_colsum) converts the RAW rows at 2^-6 as ff_gemm_x2h_ln does), one v_mfma_f32_32x32x16_f16 chain per output tile accumulates
+ * in fp32, no second term and no recombination.  Error: that of the fp16-rounded operands (2^-11 relative per operand) plus an
+ * fp32 accumulation.  Same range rule as "2 x fp16" (every |a| < 65504).  Plane: ff_split_weight_fp16, [1][K/16][N][16] fp16 =
+ * plane 0 of ff_split_weight_fp16x2 (either buffer may be passed: only its first N * K halfs are read),
+ * ff_split_weight_fp16_bytes(N, K) bytes.  Arguments, restrictions and replaced call sites as ff_gemm_x3 / ff_gemm_x3_ln. */
+size_t ff_split_weight_fp16_bytes(int N, int K);
+int ff_split_weight_fp16(const float* W, int ldw, int N, int K, void* plane, ff_stream_t stream);
+int ff_gemm_h1(const float* A, int lda, const float* A2, int n_split, const void* w_plane,
+               const float* bias, const float* residual, int ldr, float* C, int ldc,
+               int M, int N, int K, int act, ff_stream_t stream);
+int ff_gemm_h1_ln(const ff_gemm_ln_desc* desc, const void* w_plane, int plane_rows, int row0, const float* w_colsum,
+                  ff_stream_t stream);
+
 /* Launch shape of the 3 x bf16 kernel (process-wide; tests and tools/): 0 = the default -- whole tiles, and when the tile
  * count is not a multiple of the CU count the remaining tiles cut into 2 / 4 / 8 K-pieces, one piece per CU, summed by the
  * block that holds the tile's last piece in ascending piece order --, 1 = whole tiles only, 2 = equal K-unit ranges per
@@ -265,6 +281,9 @@ typedef struct ff_attn_desc {
   const void* kv_planes;  /* optional (round 6): the fp16 planes of k / v made by ff_attention_split_kv for exactly these groups, heads
                              and nk -- launches that qualify (nk <= 288, no causal mask, enough query tiles) then run on the fp16 matrix
                              cores with fp32 accuracy ("2 x fp16": ff_attention_x2h.hip); NULL: the f32 kernels */
+  int kv_terms;           /* ABI 105: terms of the planes the fp16 kernel uses.  0 (or 2) = both (today's "2 x fp16"); 1 = the FIRST K and V
+                             planes only (fp16(k), fp16(v)) with the query and the softmax weights rounded to ONE fp16 term each --
+                             the split kind "fp16": fp16(q scale) fp16(K)^T, fp32 softmax, fp16(P) fp16(V), fp32 accumulation */
 } ff_attn_desc;
 
 /* K | V of every (group, head) pair -> two fp16 planes each, in the layout the 2 x fp16 attention kernel copies into LDS
@@ -432,7 +451,9 @@ typedef struct ff_model {
   const float *proj_w, *proj_b;        /* project [E, E], [E] */
   const float *proj_fold_w, *proj_fold_b; /* optional: decoder.norm folded into project (ff_fold_layernorm_linear) */
   int split_kind;          /* what the `*_planes` of the decoder layers hold: 0 = three bf16 planes (ff_split_weight_bf16x3, six
-                              products per fp32 product), 1 = two fp16 planes (ff_split_weight_fp16x2, three products; round 6) */
+                              products per fp32 product), 1 = two fp16 planes (ff_split_weight_fp16x2, three products; round 6),
+                              2 = ONE fp16 plane (ff_split_weight_fp16, one fp16 product: ff_gemm_h1; ABI 105) -- the cross-attention
+                              then runs the one-term fp16 kernel (ff_attn_desc.kv_terms = 1) */
 } ff_model;
 
 /* Encoder (a1-a4 of SURVEY.md 8a): embedding MLP + token rows, 6 pre-norm layers, final LayerNorm.

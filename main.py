@@ -66,12 +66,23 @@ def record_of(cfg, raw, item, pred, parallel):
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
+def configure_model(model, retire_finished=False, fp16=False):
+    """The CLI's decode options on a built model: retirement of finished face loops, and the opt-in one-fp16-product
+    projections and cross-attention (split_kind "fp16").  Without them the model keeps its defaults."""
+    if retire_finished:
+        model.retire_finished = True
+    if fp16:
+        model.split_kind = "fp16"
+    return model
+
+
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
-             retire_finished=False):
+             retire_finished=False, fp16=False):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
-    retire_finished: the parallel model stops decoding a face loop once it has ended (models/common.py retire_finished)."""
+    retire_finished: the parallel model stops decoding a face loop once it has ended (models/common.py retire_finished).
+    fp16: the decoder's large projections and its cross-attention take one fp16 product each (split_kind "fp16")."""
     if retire_finished and cfg.model_class != "SurfaceFormer_Parallel":
         raise ValueError("--retire-finished applies to SurfaceFormer_Parallel only")
     model_class = getattr(models, cfg.model_class)
@@ -81,8 +92,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         sd, _ = load_lightning_checkpoint(ckpt_path)
         model.load_state_dict(sd)
         model = model.eval().to(device)
-    if retire_finished:
-        model.retire_finished = True
+    configure_model(model, retire_finished, fp16)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -135,13 +145,21 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     return out_dir
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = get_parser()
     parser.add_argument("--batch-size", type=int, default=1,
                         help="samples per model(batch) call (the reference's test loader is fixed at 1); the records do not depend on it")
     parser.add_argument("--retire-finished", action="store_true",
                         help="parallel model: stop decoding a face loop once it has produced its face-type token (DESIGN.md 10)")
-    args = parser.parse_args()
+    parser.add_argument("--fp16", action="store_true",
+                        help="decode the decoder's large projections and its cross-attention with ONE fp16 product each, fp32 "
+                             "accumulation (split_kind 'fp16', DESIGN.md 11): the arithmetic of the reference's 16-bit GPU decode. "
+                             "cfg.trainer.precision is NOT read for this -- honouring it by default would change today's records")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     cfg = get_cfg(args)
     if args.test_ckpt == "":
         raise SystemExit("only --test_ckpt (greedy decode + JSON dump) is implemented; training, "
@@ -155,6 +173,10 @@ if __name__ == "__main__":
         device = "cuda:%d" % local_rank
         dist_mod.init_process_group("nccl", device_id=torch.device(device))
     run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
-             retire_finished=args.retire_finished)
+             retire_finished=args.retire_finished, fp16=args.fp16)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
