@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """Throughput of the greedy pointer-decode path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run measures the headline alone: it sets up, runs W warm-up and K timed steps, writes --dump-outputs if asked and
+prints the result line (contract keys, `config`, the analytic `path_roofline`).  Everything else described below -- the
+package-default line, the kernel rooflines and the clock probe, the live PMC traffic passes, `other_configs`, the CPU
+baseline, at N > 1 the one-wireframe weak line and the JSON gather, and `bench_detail.json` -- runs only with --full (the
+--no-* options then drop single legs of it).
 
 Metric (BASELINE.json): decoded edges/s = pointer selections per second on 256-edge wireframes.
 One "step" = one pass of the hot path over one batch per GPU: encoder + all greedy decode steps +
@@ -10,8 +16,8 @@ output packing (+ the RCCL all-gather of the predicted loops when N > 1).
 
 N = 1 (the headline): BASELINE config 2 ("B"): configs/ours.yml with model.num_lines=256, ONE synthetic 256-edge
 wireframe (F=256 anchor sequences x 36 steps = 9216 selections), default-xavier synthetic weights (never stops early),
-fp32, every product on the f32 matrix cores.  The same run also measures, with a few timed passes each, the other
-BASELINE configurations that fit one GPU and reports them under `other_configs` (each with its own roofline):
+fp32, every product on the f32 matrix cores.  With --full the same run also measures, with a few timed passes each, the
+other BASELINE configurations that fit one GPU and reports them under `other_configs` (each with its own roofline):
     C128  config 3's per-GPU share: 128 of the 1024 256-edge wireframes                    (configs/ours.yml)
     E32   config 5's per-GPU share: 32 ragged 64..1024-edge wireframes                     (configs/ours-perspective.yml)
     D     config 4: seq2seq+coedge.yml, one 216-edge wireframe, extra pointer mask operand (SurfaceFormer, 258 steps)
@@ -21,9 +27,10 @@ N > 1: BASELINE config 3 itself: every rank decodes its share of the 1024-wirefr
 GPU (at N < 8 the batch is 128 N wireframes: weak scaling of config 3's per-GPU workload) -- through
 `faceformer_amd.dist.decode_sharded(local_shard=True)`: batch-global F, no local stop, all-reduced stop counters, the
 GLOBAL stop rule, RCCL all-gather of the int32 tokens inside the timed step.  The N = 1 reference of that series is
-`other_configs.C128` of the N = 1 line.  `weak_one_wireframe_per_gpu` carries the one-wireframe-per-GPU line as well.
+`other_configs.C128` of the N = 1 line.  With --full, `weak_one_wireframe_per_gpu` carries the one-wireframe-per-GPU line
+as well.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     : the dominant kernel family (the f32-MFMA GEMM): algorithmic flops (2MNK summed over its launches of one
                  step) / its summed duration, measured with HIP events on the launch stream by the library's profiling
                  hooks, NET of the event bracket (ff_profile_bracket_us: the interval an event pair reports around an
@@ -298,11 +305,11 @@ ROOF_KEYS = ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "
 LINE_LIMIT = 4096
 
 
-def compact_line(result):
+def compact_line(result, detail=True):
     """The ONE line the driver parses (last line of stdout), kept under LINE_LIMIT bytes: the contract keys, a compact
     `roofline` and `cpu_baseline`, and {value, ms_per_step, frac} for the package default and each other configuration.
     Notes, bracket variants, per-category tables and the full `other_configs` live in bench_detail.json (and on
-    the stderr line tagged "bench_detail")."""
+    the stderr line tagged "bench_detail"); `detail` = False (a plain run, which writes neither) leaves out the pointer."""
     out = _pick(result, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                          "vs_baseline", "dtype", "data"))
     cfg = dict(result.get("config") or {})
@@ -356,7 +363,8 @@ def compact_line(result):
             out[k] = _pick(result[k], ("value", "ms_per_step", "steps"))
     if "scaling_series" in result:
         out["scaling_series"] = {k: _cut(v, 120) for k, v in result["scaling_series"].items() if k != "note"}
-    out["detail"] = "bench_detail.json beside bench.py (also gpurun_out/bench_detail.json and the stderr line tagged bench_detail)"
+    if detail:
+        out["detail"] = "bench_detail.json beside bench.py and the stderr line tagged bench_detail"
     out = _sig(out)
     line = json.dumps(out, separators=(",", ":"))
     if len(line) >= LINE_LIMIT:    # never let the driver's record go unparsed again: shed the optional blocks
@@ -368,20 +376,20 @@ def compact_line(result):
     return line
 
 
-def emit(result):
+def emit(result, detail=True):
     """stdout carries exactly ONE line, the compact one (the driver's record lost the 25 KB line of round 4, and a long earlier
-    stdout line could push the compact one out of whatever window the driver keeps).  Everything else goes to
-    bench_detail.json beside this script, to gpurun_out/bench_detail.json (merged back from a GPU box) and to stderr."""
-    for path in (os.path.join(ROOT, "bench_detail.json"), os.path.join(ROOT, "gpurun_out", "bench_detail.json")):
+    stdout line could push the compact one out of whatever window the driver keeps).  With `detail` (--full) the whole
+    record also goes to bench_detail.json beside this script and to stderr."""
+    if detail:
+        path = os.path.join(ROOT, "bench_detail.json")
         try:
-            os.makedirs(os.path.dirname(path), exist_ok=True)
             with open(path, "w") as f:
                 json.dump(result, f, indent=1)
         except OSError as e:   # a read-only checkout must not cost the bench line
             sys.stderr.write("bench.py: %s not written (%s)\n" % (path, e))
-    sys.stderr.write("bench_detail: " + json.dumps(result) + "\n")
-    sys.stderr.flush()
-    print(compact_line(result), flush=True)
+        sys.stderr.write("bench_detail: " + json.dumps(result) + "\n")
+        sys.stderr.flush()
+    print(compact_line(result, detail), flush=True)
 
 
 def _free_port():
@@ -469,6 +477,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: package-default line, rooflines, live PMC traffic, "
+                         "other_configs, CPU baseline, at N > 1 the weak line and the JSON gather, bench_detail.json (the "
+                         "--no-* options drop single legs of it); without it the run times the headline and nothing else")
     ap.add_argument("--config", default="B", choices=["B", "E"],
                     help="B: 256-edge wireframes (BASELINE configs 2/3, the headline); E: ours-perspective.yml with "
                          "num_lines=1024, ragged 64..1024-edge wireframes (BASELINE config 5)")
@@ -483,8 +495,8 @@ def main():
     ap.add_argument("--gemm-tuning", default="", help="min_units,two_per_cu_units,fix_tenths[,small_max_rows] of ff_set_gemm_tuning")
     ap.add_argument("--x3-min-rows", type=int, default=0,
                     help="3 x bf16 projections (fp32-accurate, bf16 matrix cores) on launches with at least this many rows. "
-                         "The HEADLINE is measured with 0 (every product on the f32 matrix cores, dtype f32); the package "
-                         "default is measured as well and reported under 'package_default'")
+                         "The HEADLINE is measured with 0 (every product on the f32 matrix cores, dtype f32); with --full the "
+                         "package default is measured as well and reported under 'package_default'")
     ap.add_argument("--split-kind", default="", choices=["", "bf16x3", "fp16x2"],
                     help="how the split projections of the package-default line split an fp32 operand (default: the package's)")
     ap.add_argument("--no-fuse-ln", action="store_true", help="standalone LayerNorm launches (A/B of FF_FUSE_LAYERNORM)")
@@ -521,6 +533,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: set up, warm up, time the steps, dump, print the line -- no leg beyond the headline
+        args.no_cpu_baseline = args.no_roofline = args.no_x3_line = args.no_other_configs = args.no_json_gather = True
     t_start = time.perf_counter()
 
     # ---- launch contract: `--gpus N` is what runs, or nothing does ---------------------------------------------------
@@ -750,7 +764,7 @@ def main():
     falg = sum(alg_flops_per_wireframe(n, T) for n in n_local)
     result["path_roofline"] = path_roofline(falg, dt / args.steps)
 
-    if multi and sharded_c:
+    if multi and sharded_c and args.full:
         # the one-wireframe-per-GPU weak line (what N = 1 measures as its headline), plain model(batch) + all-gather
         one = to_dev(make_wireframes([args.edges], L_lines, T, "parallel", seeds=[rank]))
 
@@ -1146,7 +1160,7 @@ def main():
 
     if rank == 0:
         result["bench_seconds"] = time.perf_counter() - t_start
-        emit(result)
+        emit(result, args.full)
     if multi:
         dist.destroy_process_group()
 

@@ -1,8 +1,12 @@
-"""CPU: bench.py's launch contract -- `--gpus N` is what runs, or nothing does (missing #1)."""
+"""bench.py's launch contract -- `--gpus N` is what runs, or nothing does (missing #1) -- and what a plain run
+is.  Every test but the last runs on the CPU."""
 import json
 import os
 import subprocess
 import sys
+import time
+
+import pytest
 
 from conftest import ROOT
 
@@ -109,3 +113,32 @@ def test_dump_outputs_writes_exact_tokens_and_a_bounded_seeded_sample(tmp_path, 
     assert np.array_equal(rows, pred.reshape(-1, 37)[idx.astype(np.int64)])
     assert np.array_equal(np.load(b[0]), rows) and np.array_equal(np.load(b[1]), idx)
     assert rows.nbytes + idx.nbytes <= bench.DUMP_LIMIT_BYTES
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_and_nothing_else(tmp_path):
+    """`bench.py --gpus 1` without --full: one stdout line with the contract keys and the headline's figures, none of the legs
+    --full adds, no bench_detail.json, the tokens of its last timed step dumped, and at most 30 s of the whole process
+    spent outside its warm-up and timed steps."""
+    import numpy as np
+    detail = os.path.join(ROOT, "bench_detail.json")
+    before = os.stat(detail).st_mtime_ns if os.path.exists(detail) else None
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout[:500]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "path_roofline"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["config"]["decode_steps"] == 36 and d["value"] > 0
+    for k in ("package_default", "roofline", "kernel_time_ms_per_step", "other_configs", "cpu_baseline", "speedup_vs_cpu",
+              "detail"):
+        assert k not in d, k
+    assert (os.stat(detail).st_mtime_ns if os.path.exists(detail) else None) == before
+    assert np.load(str(tmp_path / "predict.npy")).shape == (1, 256, 37)
+    assert wall - 3 * d["ms_per_step"] / 1e3 < 30.0, (wall, d["ms_per_step"])

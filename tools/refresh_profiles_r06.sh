@@ -43,7 +43,7 @@ if [ "${1:-all}" = "seq" ] || [ "${1:-all}" = "all" ]; then
   timeout 600 python tools/time_seq2seq.py > $OUT/seq2seq.txt 2>&1
 fi
 if [ "${1:-all}" = "bench" ] || [ "${1:-all}" = "all" ]; then
-  T0=$(date +%s); timeout 1200 python bench.py > $OUT/bench_line_final.json 2> $OUT/bench_stderr_final.txt; echo "bench.py wall: $(( $(date +%s) - T0 )) s" > $OUT/bench_wall.txt
+  T0=$(date +%s); timeout 1200 python bench.py --full > $OUT/bench_line_final.json 2> $OUT/bench_stderr_final.txt; echo "bench.py wall: $(( $(date +%s) - T0 )) s" > $OUT/bench_wall.txt
   cp bench_detail.json $OUT/bench_detail_final.json 2>/dev/null
 fi
 ls -la $OUT

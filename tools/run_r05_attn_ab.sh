@@ -11,7 +11,7 @@ done
 for rep in 1 2 3; do
   for n in "" "$@"; do
     lib=""; [ -n "$n" ] && lib=$PWD/build_ub/lib_$n.so
-    r=$(FF_HIP_LIB=$lib timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --no-x3-line 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f %.3f' % (d['ms_per_step'], d['kernel_time_ms_per_step']['attention_kernels']))")
+    r=$(FF_HIP_LIB=$lib timeout 600 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --no-x3-line 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f %.3f' % (d['ms_per_step'], d['kernel_time_ms_per_step']['attention_kernels']))")
     echo "lib=${n:-in-tree} -> ms_per_step, attention ms: $r"
   done
 done | tee gpurun_out/r05/attn_${1}_ab.txt

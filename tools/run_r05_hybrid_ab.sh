@@ -15,7 +15,7 @@ done
 for fix in ${FF_AB_FIXES:-10}; do
 for rep in 1 2 3 4 5 6; do
   for h in 0 1; do
-    r=$(FF_SK_HYBRID=$h FF_SK_HYBRID_FIX=$fix timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --no-x3-line 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f %.3f' % (d['ms_per_step'], d['kernel_time_ms_per_step']['gemm_f32_kernels']))")
+    r=$(FF_SK_HYBRID=$h FF_SK_HYBRID_FIX=$fix timeout 600 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --no-x3-line 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f %.3f' % (d['ms_per_step'], d['kernel_time_ms_per_step']['gemm_f32_kernels']))")
     echo "FF_SK_HYBRID=$h fix=$fix -> ms_per_step, gemm ms: $r"
   done
 done

@@ -3,7 +3,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r06g; mkdir -p $O
-T0=$(date +%s); timeout 1200 python bench.py > $O/bench_line.json 2> $O/bench_stderr.txt; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); timeout 1200 python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.txt; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
 cut -c1-3000 $O/bench_line.json; cp bench_detail.json $O/
 python - <<'PY' 2>&1 | tail -5
 import sys, types, torch

@@ -11,8 +11,8 @@ PY
 }
 {
 for i in 1 2; do
-  echo "LayerNorm in the epilogue (MODE 3):"; FF_BENCH_LN_EPILOGUE=1 timeout 600 python bench.py --no-cpu-baseline --no-roofline --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_epi.json; show $O/b_epi.json
-  echo "LayerNorm first (MODE 1):"; FF_BENCH_LN_EPILOGUE=0 timeout 600 python bench.py --no-cpu-baseline --no-roofline --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_first.json; show $O/b_first.json
+  echo "LayerNorm in the epilogue (MODE 3):"; FF_BENCH_LN_EPILOGUE=1 timeout 600 python bench.py --full --no-cpu-baseline --no-roofline --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_epi.json; show $O/b_epi.json
+  echo "LayerNorm first (MODE 1):"; FF_BENCH_LN_EPILOGUE=0 timeout 600 python bench.py --full --no-cpu-baseline --no-roofline --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_first.json; show $O/b_first.json
 done
 } > $O/fp16x2_ln_form_ab.txt 2>&1
 cat $O/fp16x2_ln_form_ab.txt

@@ -9,7 +9,7 @@ FF_PARITY_MARGINS=$PWD/$O/parity_margins_split.txt timeout 1500 python -m pytest
 grep fp16x2 $O/parity_margins_split.txt | sort -k6 -n -r | head -8
 for kind in bf16x3 fp16x2 bf16x3 fp16x2; do
   echo "== $kind"
-  timeout 600 python bench.py --no-cpu-baseline --no-roofline --steps 6 --warmup 2 --split-kind $kind --other-list C128,E32 2>/dev/null > $O/bench_$kind.json
+  timeout 600 python bench.py --full --no-cpu-baseline --no-roofline --steps 6 --warmup 2 --split-kind $kind --other-list C128,E32 2>/dev/null > $O/bench_$kind.json
   python - $O/bench_$kind.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

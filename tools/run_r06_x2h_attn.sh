@@ -16,8 +16,8 @@ PY
 }
 {
 for i in 1 2; do
-  echo "f32 attention kernels (FF_X2H_ATTN=0):"; FF_X2H_ATTN=0 timeout 600 python bench.py --no-cpu-baseline --no-roofline --no-live-traffic --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_off.json; show $O/b_off.json
-  echo "2 x fp16 cross-attention (default):"; timeout 600 python bench.py --no-cpu-baseline --no-roofline --no-live-traffic --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_on.json; show $O/b_on.json
+  echo "f32 attention kernels (FF_X2H_ATTN=0):"; FF_X2H_ATTN=0 timeout 600 python bench.py --full --no-cpu-baseline --no-roofline --no-live-traffic --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_off.json; show $O/b_off.json
+  echo "2 x fp16 cross-attention (default):"; timeout 600 python bench.py --full --no-cpu-baseline --no-roofline --no-live-traffic --steps 6 --warmup 2 --other-list C128,E32 2>/dev/null > $O/b_on.json; show $O/b_on.json
 done
 } > $O/x2h_attention_ab.txt 2>&1
 cat $O/x2h_attention_ab.txt
