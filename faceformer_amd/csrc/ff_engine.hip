@@ -18,11 +18,9 @@
 // slot[i] (a chunk-local index of the plan above; tokens, traces, extra-mask rows and finish positions stay in that original
 // order) -- and every sync_every steps the host drops the finished sequences from it (compact_chunks below).  The slots of a
 // chunk keep the w = i / Fc structure with a smaller Fc, so attention, masks and kv_len are addressed as before.
-#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
-#include <string>
 #include <vector>
 
 #include "ff_common.h"
@@ -126,8 +124,6 @@ int check_model(const ff_model* m) {
   return FF_OK;
 }
 
-struct Linear { const float* w; const float* b; };
-
 int gemm(const float* A, int lda, const float* A2, int n_split, const float* W, int ldw,
          const float* bias, const float* res, int ldr, float* C, int ldc, int M, int N, int K, int act,
          hipStream_t st) {
@@ -145,16 +141,62 @@ inline bool x3_wins(const ff_decode_params* prm, int M, int N, int K, int lda) {
   return M >= need;
 }
 
-// The same product through the 3 x bf16 kernel when the weight's planes are bound and the launch is in the
-// range where it wins.
-int gemm_or_x3(const ff_model* m, const ff_decode_params* prm, const void* planes, const float* A, int lda, const float* A2, int n_split,
-               const float* W, int ldw, const float* bias, const float* res, int ldr, float* C, int ldc, int M,
-               int N, int K, int act, hipStream_t st) {
-  if (planes && x3_wins(prm, M, N, K, lda) && (!A2 || (n_split % 128) == 0))
-    return m->split_kind == 2 ? ff_gemm_h1(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st)
-           : m->split_kind == 1 ? ff_gemm_x2h(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st)
-                                : ff_gemm_x3(A, lda, A2, n_split, planes, bias, res, ldr, C, ldc, M, N, K, act, st);
-  return gemm(A, lda, A2, n_split, W, ldw, bias, res, ldr, C, ldc, M, N, K, act, st);
+// Are the split products of the decoder's projections bound and switched on at all?  (Layer 0 stands for all: a model binds them together.)
+inline bool split_bound(const ff_model* m, const ff_decode_params* prm) {
+  return prm->x3_min_rows > 0 && m->num_dec_layers > 0 && m->dec[0].in_proj_planes != nullptr;
+}
+
+// Does a decode step with R active rows take the split products?  Its widest product decides -- q|k|v, [R, E] x [E, 3E]: the
+// steps whose projections take the split kernel also read the fp16 planes of the cross-attention K | V.
+inline bool step_splits(const ff_model* m, const ff_decode_params* prm, long R) {
+  return split_bound(m, prm) && x3_wins(prm, (int)R, 3 * m->E, m->E, m->E);
+}
+
+// One projection of the decoder: C = act(LN?(A) W^T + bias [+ table]) [+ residual], optionally leaving the row statistics of C.
+struct Proj {
+  const float *A = nullptr, *A2 = nullptr;   // columns >= n_split of the product read A2 (q|k from LN(x) + qpos, v from LN(x))
+  const float *W = nullptr, *bias = nullptr, *res = nullptr;
+  const void* planes = nullptr;              // (optional) the split planes of the [plane_rows, K] weight whose rows [row0, row0 + N) are W
+  const float* colsum = nullptr;             // ... and its row sums (the epilogue form of the normalisation; used with st_in only)
+  float* C = nullptr;
+  const float *st_in = nullptr, *table = nullptr;   // segment statistics of A's rows (LN folded in); position table added per row
+  float* st_out = nullptr;                   // segment statistics of C's rows for the next LayerNorm
+  int lda = 0, n_split = 0, ldw = 0, plane_rows = 0, row0 = 0, ldr = 0, ldc = 0, M = 0, N = 0, K = 0, act = 0, ldt = 0, tcols = 0;
+  Proj& in(const float* a, int ld, const float* a2 = nullptr, int ns = 0) { A = a; lda = ld; A2 = a2; n_split = ns; return *this; }
+  Proj& weight(const float* w, int ld, const float* b) { W = w; ldw = ld; bias = b; return *this; }
+  Proj& split(const void* pl, int rows, int r0 = 0, const float* cs = nullptr) { planes = pl; plane_rows = rows; row0 = r0; colsum = cs; return *this; }
+  Proj& add(const float* r, int ld) { res = r; ldr = ld; return *this; }
+  Proj& out(float* c, int ld, int m_, int n_, int k_, int a = 0) { C = c; ldc = ld; M = m_; N = n_; K = k_; act = a; return *this; }
+  Proj& norm(const float* s) { st_in = s; return *this; }
+  Proj& pos(const float* t, int ld, int cols) { table = t; ldt = ld; tcols = cols; return *this; }
+  Proj& stats(float* s) { st_out = s; return *this; }
+};
+
+// The projection through the split kernel of the model's kind when the weight's planes are bound and the launch is in the range
+// where it wins, through the f32 family otherwise.  A projection that reads or leaves row statistics, or adds a position table,
+// takes the LayerNorm-folded forms (ff_gemm_*_ln; row_div: rows per position of that table); the others the plain forms.
+int project(const ff_model* m, const ff_decode_params* prm, int row_div, hipStream_t st, const Proj& d) {
+  struct Kernels { decltype(&ff_gemm_x3) plain; decltype(&ff_gemm_x3_ln) ln; };
+  static const Kernels by_kind[3] = {{ff_gemm_x3, ff_gemm_x3_ln}, {ff_gemm_x2h, ff_gemm_x2h_ln}, {ff_gemm_h1, ff_gemm_h1_ln}};
+  // (0 = bf16 x 3 planes, 1 = fp16 x 2 planes, 2 = one fp16 plane: check_model; any other value takes the bf16 kernels, as before)
+  const Kernels& sk = by_kind[m->split_kind == 1 || m->split_kind == 2 ? m->split_kind : 0];
+  // what the split kernels do not have: a column split inside a 128-wide tile, folded statistics at K != 512, a table whose
+  // width is not a multiple of 4 (each clause names operands of one form only: the other form leaves them null)
+  const bool split = d.planes && x3_wins(prm, d.M, d.N, d.K, d.lda) && (!d.A2 || (d.n_split % 128) == 0) &&
+                     (!d.st_in || d.K == 512) && (!d.table || (d.tcols & 3) == 0);
+  if (!d.st_in && !d.table && !d.st_out) {
+    if (split) return sk.plain(d.A, d.lda, d.A2, d.n_split, d.planes, d.bias, d.res, d.ldr, d.C, d.ldc, d.M, d.N, d.K, d.act, st);
+    return gemm(d.A, d.lda, d.A2, d.n_split, d.W, d.ldw, d.bias, d.res, d.ldr, d.C, d.ldc, d.M, d.N, d.K, d.act, st);
+  }
+  ff_gemm_ln_desc g;
+  memset(&g, 0, sizeof(g));
+  g.A = d.A; g.lda = d.lda; g.W = d.W; g.ldw = d.ldw; g.bias = d.bias; g.residual = d.res; g.ldr = d.ldr; g.C = d.C; g.ldc = d.ldc;
+  g.M = d.M; g.N = d.N; g.K = d.K; g.act = d.act; g.tile = 0;
+  g.ln_stats_in = d.st_in; g.ln_nseg = d.K / 32; g.ln_eps = m->ln_eps;
+  g.row_table = d.table; g.ld_row_table = d.ldt; g.row_div = row_div; g.row_cols = d.tcols;
+  g.ln_stats_out = d.st_out;
+  if (split) return sk.ln(&g, d.planes, d.plane_rows, d.row0, d.st_in ? d.colsum : nullptr, st);
+  return ff_gemm_f32_ln(&g, st);
 }
 
 // Scratch of one in-flight micro-batch (one set per stream): R = t*Bc active rows, position-major.
@@ -172,6 +214,7 @@ struct DecodeBuffers {
                                     // folded project weight [E, E]; per micro-batch G = memory_w W' [S, E] and c = memory_w b' [S4]
   int* tok_all;   // [T, Btot] global, position-major
   Scratch scr[FF_MAX_STREAMS];
+  int* zeroed; size_t zeroed_count;   // cnt_ge | cnt_eq | arrive | seen as ONE block of zeroed_count ints: one fill per decode
   int *cnt_ge, *cnt_eq;   // [T, nch] per (step, micro-batch)
   int *arrive;            // [T, nch] arrivals of the pointer launches (counter hand-over to the host)
   int *seen;              // [Btot] FF_STOP_EACH_EOS: the sequence has produced an EOS
@@ -232,13 +275,12 @@ void plan_chunks(const ff_decode_params* p, const int* num_input_host, int ns, s
     }
     const int fstep = split ? p->chunk_seqs : Fm;
     for (int f0 = 0; f0 < Fm; f0 += fstep) {
-      Chunk c;
+      Chunk c{};   // (views into the workspace: bound by the decode)
       c.w0 = w; c.nw = nw; c.f0 = f0;
       c.Fc = (Fm - f0) < fstep ? (Fm - f0) : fstep;
       c.b0 = b0; c.Bc = nw * c.Fc;
       c.sid = (int)(out ? out->size() % (size_t)ns : 0);
-      c.x0 = nullptr; c.qkv0 = nullptr; c.x0stat = nullptr; c.pg = nullptr; c.pc = nullptr;
-      c.Fl = c.Fc; c.Bl = c.Bc; c.slot = nullptr; c.perm = nullptr;
+      c.Fl = c.Fc; c.Bl = c.Bc;
       b0 += c.Bc;
       mx = c.Bc > mx ? c.Bc : mx;
       ++nc;
@@ -276,9 +318,19 @@ EngineKnobs engine_knobs(const ff_decode_params* p) {
   return k;
 }
 
-// Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
-bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm);
+// LayerNorm fusion is possible when the folded weights are bound and the shapes fit the fused GEMM forms.
+bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
+  if (!(prm->flags & FF_FUSE_LAYERNORM)) return false;
+  if (m->E % 64 != 0 || m->E < 128 || m->E > 512 || m->FF % 64 != 0 || m->FF < 128) return false;
+  if (!m->proj_fold_w || !m->proj_fold_b) return false;
+  for (int l = 0; l < m->num_dec_layers; ++l) {
+    const ff_layer_weights& w = m->dec[l];
+    if (!w.ln1_w || !w.ln1_b || !w.ln1_pos || !w.ln2_w || !w.ln2_b || !w.ln2_pos || !w.ln3_w || !w.ln3_b) return false;
+  }
+  return true;
+}
 
+// Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
                      Bump& bp, DecodeBuffers* out) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
@@ -317,10 +369,11 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     c.logits = bp.take<float>(Bch * (size_t)S);
     c.lnstat = bp.take<float>(Rmax * (size_t)(E / 32 + 1) * 2);
   }
-  b.cnt_ge = bp.take<int>((size_t)T * nch);   // (these four stay in this order, back to back: ff_decode zeroes them with one fill)
-  b.cnt_eq = bp.take<int>((size_t)T * nch);
-  b.arrive = bp.take<int>((size_t)T * nch);
-  b.seen = bp.take<int>(Btot);
+  // the four counter arrays every decode starts from zero: ONE block, one fill (the [T, nch] ones padded to 256-byte units)
+  const size_t ncnt = ff_align_up((size_t)T * nch * sizeof(int), 256) / sizeof(int);
+  b.zeroed_count = 3 * ncnt + Btot;
+  b.zeroed = bp.take<int>(b.zeroed_count);   // (size query: take() returns null)
+  if (b.zeroed) { b.cnt_ge = b.zeroed; b.cnt_eq = b.cnt_ge + ncnt; b.arrive = b.cnt_eq + ncnt; b.seen = b.arrive + ncnt; }
   b.cnt_tot = bp.take<int>(T);
   b.steps_dev = bp.take<int>(4);
   if (retiring(p)) {
@@ -332,22 +385,10 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
   return bp.off;
 }
 
-// LayerNorm fusion is possible when the folded weights are bound and the shapes fit the fused GEMM forms.
-bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
-  if (!(prm->flags & FF_FUSE_LAYERNORM)) return false;
-  if (m->E % 64 != 0 || m->E < 128 || m->E > 512 || m->FF % 64 != 0 || m->FF < 128) return false;
-  if (!m->proj_fold_w || !m->proj_fold_b) return false;
-  for (int l = 0; l < m->num_dec_layers; ++l) {
-    const ff_layer_weights& w = m->dec[l];
-    if (!w.ln1_w || !w.ln1_b || !w.ln1_pos || !w.ln2_w || !w.ln2_b || !w.ln2_pos || !w.ln3_w || !w.ln3_b) return false;
-  }
-  return true;
-}
-
 // Does a decode step with R active rows take the LayerNorm-folded projections?  (decoder_pass and the engine loop ask.)
 bool step_fuses(const ff_model* m, const ff_decode_params* prm, long R) {
-  const int nd = m->num_dec_layers, E = m->E;
-  const bool x3_bound = prm->x3_min_rows > 0 && nd > 0 && m->dec[0].in_proj_planes != nullptr;
+  const int E = m->E;
+  const bool x3_bound = split_bound(m, prm);
   const bool x3_folds = x3_bound && m->dec[0].ln1_planes != nullptr && m->dec[0].ln2_planes != nullptr &&
                         m->dec[0].ln3_planes != nullptr && E == 512;
   // f32 only: since round 4 the LDS-DMA kernel of the f32 family carries the folded forms at every size too (K = E = 512), so
@@ -358,7 +399,8 @@ bool step_fuses(const ff_model* m, const ff_decode_params* prm, long R) {
   return can_fuse_layernorm(m, prm) && R <= fuse_max;
 }
 
-// One decoder pass over the current prefix (t positions) of one micro-batch.
+// One decoder pass over the current prefix (t positions) of one micro-batch, Bc sequences wide with Fc of them per wireframe
+// (the chunk's own widths, or its live widths under FF_RETIRE_FINISHED).
 // full_rows: evaluate every layer for all rows and project all rows into proj_all (ld = E rows
 // position-major within the chunk); otherwise the result is p[Bc, E] for the newest position.
 //
@@ -367,10 +409,10 @@ bool step_fuses(const ff_model* m, const ff_decode_params* prm, long R) {
 // projection that consumes LN(x) (+ qpos) reads x and the statistics and applies gamma / beta / qpos W^T through
 // folded weights (ff_gemm_f32_ln).  19 -> 1 LayerNorm launches per decode step of a 6-layer decoder.
 int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKnobs& kn, const DecodeBuffers& bufs, const Scratch& buf,
-                 const Chunk& ck, const unsigned char* mask, const int* kv_len, int t, bool full_rows,
+                 const Chunk& ck, int Fc, int Bc, const unsigned char* mask, const int* kv_len, int t, bool full_rows,
                  float* proj_all, hipStream_t st, float* logits_out = nullptr) {
-  const int E = m->E, FFd = m->FF, H = m->H, S = prm->L + m->num_token, F = ck.Fc, T = prm->T;
-  const int Bc = ck.Bc, R = t * Bc, nd = m->num_dec_layers;
+  const int E = m->E, FFd = m->FF, H = m->H, S = prm->L + m->num_token, F = Fc, T = prm->T;
+  const int R = t * Bc, nd = m->num_dec_layers;
   const size_t newoff = (size_t)(t - 1) * Bc;
   const bool reuse0 = (prm->flags & FF_REUSE_LAYER0_QKV) != 0 && ck.qkv0 != nullptr;
   const bool prune_last = (prm->flags & FF_LAST_LAYER_LAST_ROW) != 0 && !full_rows;
@@ -387,46 +429,17 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
   const int nseg = E / 32;
   const float* qpos = m->qpos_table;
   const float* qpos_new = qpos + (size_t)(t - 1) * E;
-
-  // C = act(LN?(A) W^T + bias [+ table]) [+ residual], optionally leaving the row statistics of C
-  // `planes` (optional): the bf16 planes of the [plane_rows, K] weight whose rows [row0, row0 + N) are W
-  auto gemm_ln = [&](const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, int ldr,
-                     float* C, int ldc, int M, int N, int K, int act, const float* st_in, const float* table, int ldt,
-                     int tcols, float* st_out, const void* planes = nullptr, int plane_rows = 0, int row0 = 0,
-                     const float* colsum = nullptr) -> int {
-    ff_gemm_ln_desc d;
-    memset(&d, 0, sizeof(d));
-    d.A = A; d.lda = lda; d.W = W; d.ldw = ldw; d.bias = bias; d.residual = res; d.ldr = ldr; d.C = C; d.ldc = ldc;
-    d.M = M; d.N = N; d.K = K; d.act = act; d.tile = 0;
-    d.ln_stats_in = st_in; d.ln_nseg = K / 32; d.ln_eps = m->ln_eps;
-    d.row_table = table; d.ld_row_table = ldt; d.row_div = Bc; d.row_cols = tcols;
-    d.ln_stats_out = st_out;
-    if (planes && x3_wins(prm, M, N, K, lda) && (!st_in || K == 512) && (!table || (tcols & 3) == 0))
-      return m->split_kind == 2 ? ff_gemm_h1_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st)
-             : m->split_kind == 1 ? ff_gemm_x2h_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st)
-                                  : ff_gemm_x3_ln(&d, planes, plane_rows, row0, st_in ? colsum : nullptr, st);
-    return ff_gemm_f32_ln(&d, st);
-  };
-
-  // the LayerNorm-folded projection over all R rows that opens layer l2 > 0: q|k|v, or k|v alone when the layer is pruned to
-  // its newest position (its q then covers Bc rows only)
+  auto proj = [&](const Proj& d) -> int { return project(m, prm, Bc, st, d); };
   // The pruned last layer needs k | v of every row and q of the newest position only: two launches.  On launch-bound steps
   // (few rows) ONE q | k | v launch over all rows is cheaper than the second launch it saves (FF_LAST_QKV_ONE_LAUNCH_ROWS: up
   // to this many active rows; 0 = never); the q of the older rows is computed and not used.
   const bool last_qkv_one = R <= kn.one_launch_rows;
-  auto first_proj = [&](int l2) -> int {
-    const ff_layer_weights& w2 = m->dec[l2];
-    if (prune_last && l2 == nd - 1 && t > 1 && !last_qkv_one)
-      return gemm_ln(buf.x, E, w2.ln1_w + (size_t)E * E, E, w2.ln1_b + E, nullptr, 0, buf.qkv + E, 3 * E, R, 2 * E, E, 0,
-                     buf.lnstat, w2.ln1_pos + E, 2 * E, E, nullptr, w2.ln1_planes, 3 * E, E, w2.ln1_csum);
-    return gemm_ln(buf.x, E, w2.ln1_w, E, w2.ln1_b, nullptr, 0, buf.qkv, 3 * E, R, 3 * E, E, 0, buf.lnstat, w2.ln1_pos, 2 * E,
-                   2 * E, nullptr, w2.ln1_planes, 3 * E, 0, w2.ln1_csum);
-  };
   for (int l = 0; l < nd; ++l) {
     const ff_layer_weights& w = m->dec[l];
+    const ff_mha_weights& sa = w.self_attn;
     const bool last = prune_last && (l == nd - 1);
     const float* xin = (l == 0) ? ck.x0 : buf.x;
-    const float* QKV;
+    const float* QKV = buf.qkv;
     // ---- self attention: q = k = LN1(x) + qpos, v = LN1(x), no mask (transformer.py:242-246) ----
     if (l == 0 && reuse0) {
       if (full_rows) {
@@ -434,141 +447,120 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
       } else if (fuse && t > 1 && ck.x0stat) {
         // the newest rows were appended by the previous step's pointer launch together with their segment statistics: the
         // folded projection normalises them itself (no LayerNorm launch left in a decode step after the first)
-        FF_RETURN_IF(gemm_ln(xin + newoff * E, E, w.ln1_w, E, w.ln1_b, nullptr, 0, ck.qkv0 + newoff * 3 * E, 3 * E, Bc, 3 * E, E,
-                             0, ck.x0stat, w.ln1_pos + (size_t)(t - 1) * 2 * E, 2 * E, 2 * E, nullptr));
+        FF_RETURN_IF(proj(Proj().in(xin + newoff * E, E).weight(w.ln1_w, E, w.ln1_b).norm(ck.x0stat)
+                              .pos(w.ln1_pos + (size_t)(t - 1) * 2 * E, 2 * E, 2 * E).out(ck.qkv0 + newoff * 3 * E, 3 * E, Bc, 3 * E, E)));
       } else {
         FF_RETURN_IF(ff_layernorm(xin + newoff * E, E, w.norm1_w, w.norm1_b, m->ln_eps, buf.y, E, buf.yq, E,
                                   qpos_new, E, Bc, 1, Bc, E, st));
-        FF_RETURN_IF(gemm(buf.yq, E, buf.y, 2 * E, w.self_attn.in_proj_w, E, w.self_attn.in_proj_b, nullptr, 0,
-                          ck.qkv0 + newoff * 3 * E, 3 * E, Bc, 3 * E, E, 0, st));
+        FF_RETURN_IF(proj(Proj().in(buf.yq, E, buf.y, 2 * E).weight(sa.in_proj_w, E, sa.in_proj_b)
+                              .out(ck.qkv0 + newoff * 3 * E, 3 * E, Bc, 3 * E, E)));
       }
       QKV = ck.qkv0;
     } else if (fuse && l > 0) {
-      FF_RETURN_IF(first_proj(l));
-      if (last && t > 1 && !last_qkv_one) {
-        // the pruned last layer attends from its newest position only: k | v for every row (above), q for the last Bc rows
-        FF_RETURN_IF(gemm_ln(xin + newoff * E, E, w.ln1_w, E, w.ln1_b, nullptr, 0, buf.qkv + newoff * 3 * E, 3 * E, Bc, E, E,
-                             0, buf.lnstat + newoff * nseg * 2, w.ln1_pos + (size_t)(t - 1) * 2 * E, 2 * E, E, nullptr));
-      }
-      QKV = buf.qkv;
+      // the LayerNorm-folded projection over all R rows that opens layer l > 0: q|k|v, or k|v alone (weight rows and output
+      // columns from c0 = E on) when the layer is pruned to its newest position; its q then covers the last Bc rows only
+      const bool kv_only = last && t > 1 && !last_qkv_one;
+      const int c0 = kv_only ? E : 0;
+      FF_RETURN_IF(proj(Proj().in(buf.x, E).weight(w.ln1_w + (size_t)c0 * E, E, w.ln1_b + c0).split(w.ln1_planes, 3 * E, c0, w.ln1_csum)
+                            .norm(buf.lnstat).pos(w.ln1_pos + c0, 2 * E, 2 * E - c0).out(buf.qkv + c0, 3 * E, R, 3 * E - c0, E)));
+      if (kv_only)
+        FF_RETURN_IF(proj(Proj().in(xin + newoff * E, E).weight(w.ln1_w, E, w.ln1_b).norm(buf.lnstat + newoff * nseg * 2)
+                              .pos(w.ln1_pos + (size_t)(t - 1) * 2 * E, 2 * E, E).out(buf.qkv + newoff * 3 * E, 3 * E, Bc, E, E)));
     } else {
-      FF_RETURN_IF(ff_layernorm(xin, E, w.norm1_w, w.norm1_b, m->ln_eps, buf.y, E, buf.yq, E, qpos, E, Bc, T,
-                                R, E, st));
-      const long x3_need = (long)prm->x3_min_rows;   // (the bf16 planes cover the whole [3E, E] weight: no row ranges)
-      const bool x3_here = w.in_proj_planes && prm->x3_min_rows > 0 && R >= x3_need;
+      FF_RETURN_IF(ff_layernorm(xin, E, w.norm1_w, w.norm1_b, m->ln_eps, buf.y, E, buf.yq, E, qpos, E, Bc, T, R, E, st));
+      // Not step_splits(): this picks the launch FORM, not the kernel.  From x3_min_rows rows on (no per-width factor, no
+      // shape conditions) the pruned layer keeps ONE q|k|v launch, which project() then routes by its own rule; the planes
+      // cover the whole [3E, E] weight (no row ranges), so the two-launch form below never takes the split kernel.
+      const bool x3_here = w.in_proj_planes && prm->x3_min_rows > 0 && R >= (long)prm->x3_min_rows;
       if (last && t > 1 && !x3_here && (E % 64) == 0) {
         // pruned last layer: k (from LN(x)+qpos) | v (from LN(x)) for every row, q for the newest position only
-        FF_RETURN_IF(gemm(buf.yq, E, buf.y, E, w.self_attn.in_proj_w + (size_t)E * E, E, w.self_attn.in_proj_b + E, nullptr,
-                          0, buf.qkv + E, 3 * E, R, 2 * E, E, 0, st));
-        FF_RETURN_IF(gemm(buf.yq + newoff * E, E, nullptr, 0, w.self_attn.in_proj_w, E, w.self_attn.in_proj_b, nullptr, 0,
-                          buf.qkv + newoff * 3 * E, 3 * E, Bc, E, E, 0, st));
+        FF_RETURN_IF(proj(Proj().in(buf.yq, E, buf.y, E).weight(sa.in_proj_w + (size_t)E * E, E, sa.in_proj_b + E)
+                              .out(buf.qkv + E, 3 * E, R, 2 * E, E)));
+        FF_RETURN_IF(proj(Proj().in(buf.yq + newoff * E, E).weight(sa.in_proj_w, E, sa.in_proj_b)
+                              .out(buf.qkv + newoff * 3 * E, 3 * E, Bc, E, E)));
       } else {
-        FF_RETURN_IF(gemm_or_x3(m, prm, w.in_proj_planes, buf.yq, E, buf.y, 2 * E, w.self_attn.in_proj_w, E,
-                                w.self_attn.in_proj_b, nullptr, 0, buf.qkv, 3 * E, R, 3 * E, E, 0, st));
+        FF_RETURN_IF(proj(Proj().in(buf.yq, E, buf.y, 2 * E).weight(sa.in_proj_w, E, sa.in_proj_b).split(w.in_proj_planes, 3 * E)
+                              .out(buf.qkv, 3 * E, R, 3 * E, E)));
       }
-      QKV = buf.qkv;
     }
     // rows that continue through the rest of this layer
     const size_t roff = last ? newoff : 0;
     const int Rl = last ? Bc : R;
-    float* stat = buf.lnstat + roff * nseg * 2;
+    float* x = buf.x + roff * E;      // the layer's running rows, their attention output and FFN hidden rows
+    float* o = buf.o + roff * E;
+    float* h = buf.h + roff * FFd;
+    float* qc = buf.qkv + roff * E;   // cross-attention q: a [rows, E] view of the q|k|v scratch
+    // folded steps: every projection with a residual leaves the statistics of its rows, the next projection normalises with them
+    float* stat = fuse ? buf.lnstat + roff * nseg * 2 : nullptr;
     {
       ff_attn_desc d;
       memset(&d, 0, sizeof(d));
-      d.q = QKV + roff * 3 * E;  d.ldq = 3 * E;
-      d.k = QKV + E;             d.ldk = 3 * E;
-      d.v = QKV + 2 * E;         d.ldv = 3 * E;
-      d.o = buf.o + roff * E;    d.ldo = E;
-      d.num_groups = Bc; d.num_heads = H;
-      d.nq = last ? 1 : t;
-      d.q_group_stride = 1; d.q_inner = 1; d.q_outer_stride = Bc;
+      d.q = QKV + roff * 3 * E; d.k = QKV + E; d.v = QKV + 2 * E; d.o = o;
+      d.ldq = d.ldk = d.ldv = 3 * E; d.ldo = E;
+      d.num_groups = Bc; d.num_heads = H; d.scale = 0.125f;
+      d.nq = last ? 1 : t; d.q_group_stride = 1; d.q_inner = 1; d.q_outer_stride = Bc;
       d.nk = t; d.k_group_stride = 1; d.k_stride = Bc;
-      d.scale = 0.125f;
       FF_RETURN_IF(ff_attention(&d, st));
     }
-    float* qc = buf.qkv;  // [rows, E] view of the scratch
+    FF_RETURN_IF(proj(Proj().in(o, E).weight(sa.out_w, E, sa.out_b).split(w.self_out_planes, E).add(xin + roff * E, E)
+                          .out(x, E, Rl, E, E).stats(stat)));
+    // ---- cross attention: q = LN2(x) + qpos, k = memory + pos, v = memory (transformer.py:247-252);
+    //      K/V come from the per-batch cache ----
     if (fuse) {
-      FF_RETURN_IF(gemm_ln(buf.o + roff * E, E, w.self_attn.out_w, E, w.self_attn.out_b, xin + roff * E, E,
-                           buf.x + roff * E, E, Rl, E, E, 0, nullptr, nullptr, 0, 0, stat, w.self_out_planes, E, 0));
-      // ---- cross attention: q = LN2(x) + qpos (transformer.py:247-252) ----
-      FF_RETURN_IF(gemm_ln(buf.x + roff * E, E, w.ln2_w, E, w.ln2_b, nullptr, 0, qc + roff * E, E, Rl, E, E, 0, stat,
-                           w.ln2_pos + (last ? (size_t)(t - 1) * E : 0), E, E, nullptr, w.ln2_planes, E, 0, w.ln2_csum));
+      FF_RETURN_IF(proj(Proj().in(x, E).weight(w.ln2_w, E, w.ln2_b).split(w.ln2_planes, E, 0, w.ln2_csum).norm(stat)
+                            .pos(w.ln2_pos + (last ? (size_t)(t - 1) * E : 0), E, E).out(qc, E, Rl, E, E)));
     } else {
-      FF_RETURN_IF(gemm_or_x3(m, prm, w.self_out_planes, buf.o + roff * E, E, nullptr, 0, w.self_attn.out_w, E,
-                              w.self_attn.out_b, xin + roff * E, E, buf.x + roff * E, E, Rl, E, E, 0, st));
-      // ---- cross attention: q = LN2(x) + qpos, k = memory + pos, v = memory (transformer.py:247-252);
-      //      K/V come from the per-batch cache ----
       if (last)
-        FF_RETURN_IF(ff_layernorm(buf.x + roff * E, E, w.norm2_w, w.norm2_b, m->ln_eps, nullptr, 0, buf.yq + roff * E,
-                                  E, qpos_new, E, Bc, 1, Rl, E, st));
+        FF_RETURN_IF(ff_layernorm(x, E, w.norm2_w, w.norm2_b, m->ln_eps, nullptr, 0, buf.yq + roff * E, E, qpos_new, E, Bc, 1, Rl, E, st));
       else
-        FF_RETURN_IF(ff_layernorm(buf.x, E, w.norm2_w, w.norm2_b, m->ln_eps, nullptr, 0, buf.yq, E, qpos, E, Bc, T,
-                                  Rl, E, st));
-      FF_RETURN_IF(gemm_or_x3(m, prm, w.cross_q_planes, buf.yq + roff * E, E, nullptr, 0, w.cross_attn.in_proj_w, E,
-                              w.cross_attn.in_proj_b, nullptr, 0, qc + roff * E, E, Rl, E, E, 0, st));
+        FF_RETURN_IF(ff_layernorm(buf.x, E, w.norm2_w, w.norm2_b, m->ln_eps, nullptr, 0, buf.yq, E, qpos, E, Bc, T, Rl, E, st));
+      FF_RETURN_IF(proj(Proj().in(buf.yq + roff * E, E).weight(w.cross_attn.in_proj_w, E, w.cross_attn.in_proj_b)
+                            .split(w.cross_q_planes, E).out(qc, E, Rl, E, E)));
     }
     {
       ff_attn_desc d;
       memset(&d, 0, sizeof(d));
-      d.q = qc + roff * E;      d.ldq = E;
-      d.k = bufs.kvc[l] + (size_t)ck.w0 * S * 2 * E;     d.ldk = 2 * E;
-      d.v = d.k + E;            d.ldv = 2 * E;
-      d.o = buf.o + roff * E;   d.ldo = E;
-      d.num_groups = ck.nw; d.num_heads = H;
-      d.nq = last ? F : F * t;
-      d.q_group_stride = F; d.q_inner = F; d.q_outer_stride = Bc;
+      d.q = qc; d.k = bufs.kvc[l] + (size_t)ck.w0 * S * 2 * E; d.v = d.k + E; d.o = o;
+      d.ldq = d.ldo = E; d.ldk = d.ldv = 2 * E;
+      d.num_groups = ck.nw; d.num_heads = H; d.scale = 0.125f;
+      d.nq = last ? F : F * t; d.q_group_stride = F; d.q_inner = F; d.q_outer_stride = Bc;
       d.nk = S; d.k_group_stride = S; d.k_stride = 1;
-      d.kv_len = kv_len + ck.w0;
-      d.key_mask = mask + (size_t)ck.w0 * S; d.mask_stride = S;
-      d.scale = 0.125f;
-      if (bufs.kvp[l] && x3_wins(prm, R, 3 * E, E, E))   // (the steps whose projections take the split products)
+      d.kv_len = kv_len + ck.w0; d.key_mask = mask + (size_t)ck.w0 * S; d.mask_stride = S;
+      // (layout_decode makes kvp[l] only with the split products bound: step_splits() asks no more here than the row rule)
+      if (bufs.kvp[l] && step_splits(m, prm, R))
         d.kv_planes = bufs.kvp[l] + (size_t)ck.w0 * H * (ff_attention_planes_bytes(1, H) / H);
       d.kv_terms = m->split_kind == 2 ? 1 : 0;
       FF_RETURN_IF(ff_attention(&d, st));
     }
+    FF_RETURN_IF(proj(Proj().in(o, E).weight(w.cross_attn.out_w, E, w.cross_attn.out_b).split(w.cross_out_planes, E).add(x, E)
+                          .out(x, E, Rl, E, E).stats(stat)));
+    // ---- feed forward (transformer.py:253-255) ----
     if (fuse) {
-      FF_RETURN_IF(gemm_ln(buf.o + roff * E, E, w.cross_attn.out_w, E, w.cross_attn.out_b, buf.x + roff * E, E,
-                           buf.x + roff * E, E, Rl, E, E, 0, nullptr, nullptr, 0, 0, stat, w.cross_out_planes, E, 0));
-      // ---- feed forward (transformer.py:253-255) ----
-      FF_RETURN_IF(gemm_ln(buf.x + roff * E, E, w.ln3_w, E, w.ln3_b, nullptr, 0, buf.h + roff * FFd, FFd, Rl, FFd, E, 1,
-                           stat, nullptr, 0, 0, nullptr, w.ln3_planes, FFd, 0, w.ln3_csum));
-      FF_RETURN_IF(gemm_ln(buf.h + roff * FFd, FFd, w.lin2_w, FFd, w.lin2_b, buf.x + roff * E, E, buf.x + roff * E, E,
-                           Rl, E, FFd, 0, nullptr, nullptr, 0, 0, stat, w.lin2_planes, E, 0));
+      FF_RETURN_IF(proj(Proj().in(x, E).weight(w.ln3_w, E, w.ln3_b).split(w.ln3_planes, FFd, 0, w.ln3_csum).norm(stat)
+                            .out(h, FFd, Rl, FFd, E, 1)));
     } else {
-      FF_RETURN_IF(gemm_or_x3(m, prm, w.cross_out_planes, buf.o + roff * E, E, nullptr, 0, w.cross_attn.out_w, E,
-                              w.cross_attn.out_b, buf.x + roff * E, E, buf.x + roff * E, E, Rl, E, E, 0, st));
-      // ---- feed forward (transformer.py:253-255) ----
-      FF_RETURN_IF(ff_layernorm(buf.x + roff * E, E, w.norm3_w, w.norm3_b, m->ln_eps, buf.y + roff * E, E, nullptr, 0,
-                                nullptr, 0, 1, 1, Rl, E, st));
-      FF_RETURN_IF(gemm_or_x3(m, prm, w.lin1_planes, buf.y + roff * E, E, nullptr, 0, w.lin1_w, E, w.lin1_b, nullptr, 0,
-                              buf.h + roff * FFd, FFd, Rl, FFd, E, 1, st));
-      FF_RETURN_IF(gemm_or_x3(m, prm, w.lin2_planes, buf.h + roff * FFd, FFd, nullptr, 0, w.lin2_w, FFd, w.lin2_b,
-                              buf.x + roff * E, E, buf.x + roff * E, E, Rl, E, FFd, 0, st));
+      FF_RETURN_IF(ff_layernorm(x, E, w.norm3_w, w.norm3_b, m->ln_eps, buf.y + roff * E, E, nullptr, 0, nullptr, 0, 1, 1, Rl, E, st));
+      FF_RETURN_IF(proj(Proj().in(buf.y + roff * E, E).weight(w.lin1_w, E, w.lin1_b).split(w.lin1_planes, FFd)
+                            .out(h, FFd, Rl, FFd, E, 1)));
     }
+    FF_RETURN_IF(proj(Proj().in(h, FFd).weight(w.lin2_w, FFd, w.lin2_b).split(w.lin2_planes, E).add(x, E)
+                          .out(x, E, Rl, E, FFd).stats(stat)));
   }
-  // ---- decoder.norm + project (transformer.py:115-116, model_para.py:225) ----
-  if (fuse) {
-    if (full_rows)
-      FF_RETURN_IF(gemm_ln(buf.x, E, m->proj_fold_w, E, m->proj_fold_b, nullptr, 0, proj_all, E, R, E, E, 0, buf.lnstat,
-                           nullptr, 0, 0, nullptr));
-    else if (logits_out && ck.pg)
-      // pointer_fold: logits = <project(LN(x)), memory_s> = LN(x) (memory W')^T + memory b' -- ONE launch for decoder.norm,
-      // project and the pointer's dot products of a one-wireframe micro-batch (G and c are made once per call)
-      FF_RETURN_IF(gemm_ln(buf.x + newoff * E, E, ck.pg, E, ck.pc, nullptr, 0, logits_out, S, Bc, S, E, 0,
-                           buf.lnstat + newoff * nseg * 2, nullptr, 0, 0, nullptr));
-    else
-      FF_RETURN_IF(gemm_ln(buf.x + newoff * E, E, m->proj_fold_w, E, m->proj_fold_b, nullptr, 0, buf.p, E, Bc, E, E, 0,
-                           buf.lnstat + newoff * nseg * 2, nullptr, 0, 0, nullptr));
-  } else if (full_rows) {
-    FF_RETURN_IF(ff_layernorm(buf.x, E, m->dec_norm_w, m->dec_norm_b, m->ln_eps, buf.y, E, nullptr, 0, nullptr, 0,
-                              1, 1, R, E, st));
-    FF_RETURN_IF(gemm(buf.y, E, nullptr, 0, m->proj_w, E, m->proj_b, nullptr, 0, proj_all, E, R, E, E, 0, st));
-  } else {
-    FF_RETURN_IF(ff_layernorm(buf.x + newoff * E, E, m->dec_norm_w, m->dec_norm_b, m->ln_eps, buf.y, E, nullptr, 0,
-                              nullptr, 0, 1, 1, Bc, E, st));
-    FF_RETURN_IF(gemm(buf.y, E, nullptr, 0, m->proj_w, E, m->proj_b, nullptr, 0, buf.p, E, Bc, E, E, 0, st));
+  // ---- decoder.norm + project (transformer.py:115-116, model_para.py:225): every row, or the newest position's ----
+  const size_t hoff = full_rows ? 0 : newoff;
+  const int Rh = full_rows ? R : Bc;
+  float* dst = full_rows ? proj_all : buf.p;
+  if (!fuse) {
+    FF_RETURN_IF(ff_layernorm(buf.x + hoff * E, E, m->dec_norm_w, m->dec_norm_b, m->ln_eps, buf.y, E, nullptr, 0, nullptr, 0,
+                              1, 1, Rh, E, st));
+    return proj(Proj().in(buf.y, E).weight(m->proj_w, E, m->proj_b).out(dst, E, Rh, E, E));
   }
-  return FF_OK;
+  Proj d = Proj().in(buf.x + hoff * E, E).norm(buf.lnstat + hoff * nseg * 2);
+  if (!full_rows && logits_out && ck.pg)
+    // pointer_fold: logits = <project(LN(x)), memory_s> = LN(x) (memory W')^T + memory b' -- ONE launch for decoder.norm,
+    // project and the pointer's dot products of a one-wireframe micro-batch (G and c are made once per call)
+    return proj(d.weight(ck.pg, E, ck.pc).out(logits_out, S, Bc, S, E));
+  return proj(d.weight(m->proj_fold_w, E, m->proj_fold_b).out(dst, E, Rh, E, E));
 }
 
 // Internal side streams + fork/join events: one pool per device, created on first use.
@@ -626,6 +618,451 @@ std::mutex* pool_busy_mutex() {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FF_MAX_DEVICES) return nullptr;
   return &g_pool_busy[dev];
 }
+
+// What the caller hands to ff_decode besides the model, the parameters and the workspace.
+struct DecodeIO {
+  const float* memory; const unsigned char* mask; const int *kv_len, *num_input, *num_input_host; const unsigned char* extra_mask;
+  int64_t* predict; int *steps_done, *step_counts; float *pointer_out, *trace_logits, *trace_best, *trace_second; int* seq_of_row;
+  hipStream_t main_st;
+};
+
+// FF_RETIRE_FINISHED slot order of a chunk of nw wireframes with `width` entries each, entry i live or finished: per wireframe
+// the live entries in order, then finished ones of the same wireframe, up to the chunk's widest live count (returned: every
+// wireframe of a chunk keeps the same number of slots).  Appends the entries' indices to `out`, the live count to *nlive.
+int ordered_slots(const std::vector<char>& live, int nw, int width, std::vector<int>* out, long* nlive = nullptr) {
+  int fl = 0;
+  for (int wl = 0; wl < nw; ++wl) {
+    int n = 0;
+    for (int k = 0; k < width; ++k) n += live[(size_t)wl * width + k] ? 1 : 0;
+    fl = n > fl ? n : fl;
+    if (nlive) *nlive += n;
+  }
+  for (int wl = 0; wl < nw; ++wl) {
+    int taken = 0;
+    for (int want = 1; want >= 0; --want)
+      for (int k = 0; k < width && taken < fl; ++k)
+        if ((live[(size_t)wl * width + k] ? 1 : 0) == want) { out->push_back(wl * width + k); ++taken; }
+  }
+  return fl;
+}
+
+// One ff_decode call: the state its phases share, and the phases in the order ff_decode calls them.
+struct DecodeRun {
+  const ff_model* m = nullptr;
+  ff_decode_params prm;                       // the caller's parameters; `p` points here
+  const ff_decode_params* p = nullptr;
+  DecodeIO io;
+  EngineKnobs kn;
+  int E = 0, S = 0, T = 0, F = 0, N = 0, Btot = 0, nch = 0, ns = 1;
+  bool retire = false, dedup = false, forked = false, each_eos = false;
+  bool lagged = false;                        // the stop counters fit the host-mapped slots: checked without draining the queue
+  std::vector<Chunk> chunks;
+  DecodeBuffers buf;
+  hipStream_t sts[FF_MAX_STREAMS];
+  StreamPool* pool = nullptr;
+  int enq = 0, pending_enq = 0;               // steps enqueued so far; > 0: events covering steps [0, pending_enq) are in flight
+  bool stopped = false;
+  std::vector<int> slots_per_step, tot;
+  std::vector<int> hfin;                      // host copy of the finish positions (pageable; filled from fin_host at check points)
+  std::vector<std::vector<int>> hslot;        // per chunk: the chunk-local sequence of every slot
+  int* fin_host = nullptr;                    // host address of the finish positions when they are host-mapped, else null
+  int* fin_dev = nullptr;
+  int validate(const ff_model* m_, const ff_decode_params* p_, const DecodeIO& io_, const void* workspace) {
+    m = m_; io = io_;
+    FF_RETURN_IF(check_model(m));
+    FF_CHECK_ARG(p_ != nullptr, "ff_decode: null params");
+    FF_CHECK_ARG(p_->variant == FF_PARALLEL || p_->variant == FF_SEQ2SEQ, "ff_decode: bad variant");
+    FF_CHECK_ARG(p_->N > 0 && p_->L >= 0 && p_->F > 0 && p_->T >= 1, "ff_decode: bad sizes");
+    FF_CHECK_ARG(io.memory && io.mask && io.kv_len && io.predict && workspace, "ff_decode: null pointer");
+    FF_CHECK_ARG(p_->variant != FF_PARALLEL || io.num_input, "ff_decode: num_input required for the parallel variant");
+    FF_CHECK_ARG(p_->variant != FF_SEQ2SEQ || p_->F == 1, "ff_decode: seq2seq decodes one sequence per wireframe");
+    FF_CHECK_ARG(!p_->stop_fn || (p_->flags & FF_NO_STOP) || p_->sync_every > 0, "ff_decode: stop_fn needs sync_every > 0");
+    // The callback's cadence is a CONTRACT with callers that replay it elsewhere (an idle rank of a sharded decode joins the
+    // same host collectives: faceformer_amd/dist.py check_points): the counters of the first n = enq - sync_every steps when
+    // enq = 2 sync_every, 3 sync_every, ... steps are enqueued.  Both check paths of check_point() (host-mapped counters; drain +
+    // copy when there are more counters than slots) keep that cadence for a stop_fn (tests: FF_PINNED_COUNTERS=8 in a child process).
+    FF_CHECK_ARG(!(p_->flags & FF_STOP_EACH_EOS) || p_->variant == FF_SEQ2SEQ, "ff_decode: FF_STOP_EACH_EOS is a seq2seq rule");
+    E = m->E; S = p_->L + m->num_token; T = p_->T; F = p_->F; N = p_->N;
+    FF_CHECK_ARG(S <= m->pos_len, "ff_decode: S=%d exceeds the position table (%d rows)", S, m->pos_len);
+    FF_CHECK_ARG(T - 1 <= m->qpos_len, "ff_decode: T-1=%d exceeds the query position table (%d rows)", T - 1, m->qpos_len);
+    FF_CHECK_ARG(p_->variant != FF_PARALLEL || F <= S, "ff_decode: F=%d anchors exceed S=%d", F, S);
+    FF_CHECK_ARG(!(p_->flags & FF_RETURN_POINTER) || io.pointer_out, "ff_decode: pointer_out required");
+    if (p_->flags & FF_RETIRE_FINISHED) {
+      FF_CHECK_ARG(p_->variant == FF_PARALLEL, "ff_decode: FF_RETIRE_FINISHED is a parallel-variant option");
+      FF_CHECK_ARG(!(p_->flags & (FF_RETURN_POINTER | FF_NO_STOP)) && !p_->stop_fn,
+                   "ff_decode: FF_RETIRE_FINISHED excludes FF_RETURN_POINTER, FF_NO_STOP and a stop_fn");
+      FF_CHECK_ARG(io.num_input_host, "ff_decode: FF_RETIRE_FINISHED needs num_input_host");
+      FF_CHECK_ARG(p_->term_lo < p_->term_hi, "ff_decode: empty terminator range [%d, %d)", p_->term_lo, p_->term_hi);
+    }
+    // every padding-anchor sequence has its own row of an extra mask: no de-duplication then
+    prm = *p_;
+    if (io.extra_mask) prm.flags &= ~FF_DEDUP_PAD_ANCHORS;
+    p = &prm;
+    retire = retiring(p);
+    dedup = p->variant == FF_PARALLEL && (p->flags & FF_DEDUP_PAD_ANCHORS) && io.num_input_host;
+    each_eos = (p->flags & FF_STOP_EACH_EOS) != 0;
+    kn = engine_knobs(p);
+    return FF_OK;
+  }
+  // Micro-batch plan, workspace layout and every chunk's views into it.
+  int bind_chunks(void* workspace, size_t workspace_bytes) {
+    const int ns_req = plan_streams(p);
+    int max_bc = 0;
+    plan_chunks(p, io.num_input_host, ns_req, &chunks, &Btot, &max_bc);
+    nch = (int)chunks.size();
+    Bump bp(workspace, workspace_bytes);
+    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf);
+    if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
+    for (Chunk& c : chunks) {
+      c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
+      c.qkv0 = buf.qkv0_all ? buf.qkv0_all + (size_t)T * c.b0 * 3 * E : nullptr;
+      c.x0stat = buf.x0stat_all ? buf.x0stat_all + (size_t)c.b0 * (E / 32) * 2 : nullptr;
+      const size_t ci = (size_t)(&c - chunks.data());
+      const bool one = c.nw == 1 && buf.pg_all != nullptr;
+      c.pg = one ? buf.pg_all + ci * (size_t)S * E : nullptr;
+      c.pc = one ? buf.pc_all + ci * (size_t)((S + 3) & ~3) : nullptr;
+      if (retire) { c.slot = buf.slot_all + c.b0; c.perm = buf.perm_all + c.b0; }
+    }
+    ns = ns_req < nch ? ns_req : nch;
+    forked = ns > 1;
+    lagged = (size_t)T * (size_t)nch <= (size_t)kn.pinned;
+    fin_dev = buf.fin;
+    slots_per_step.reserve((size_t)T);   // (the loop below allocates nothing per step)
+    tot.reserve((size_t)T);
+    return FF_OK;
+  }
+  // With more than one stream ALL micro-batch work runs on the internal pool (the caller's stream is
+  // often the legacy default stream, whose implicit synchronisation would serialise the others).
+  int bind_streams() {
+    FF_RETURN_IF(pool_get(forked ? ns : 0, &pool));   // (also owns the pinned counter buffer / events of the stop check)
+    sts[0] = io.main_st;
+    if (forked)
+      for (int s = 0; s < ns; ++s) sts[s] = pool->side[s];
+    return FF_OK;
+  }
+  // ---- FF_RETIRE_FINISHED: the initial slot sets (host side) -------------------------------------------------------------------
+  // fin[seq] = 0 for the sequences whose start token already ends them (the padding anchors and anchors term_lo.. of the model:
+  // reference quirk C-3) and for the surplus padding copies of narrow wireframes; T (none yet) for the others.  Every chunk starts
+  // with its live sequences only: per wireframe the live ones in order, then finished ones of the same wireframe up to the
+  // chunk's widest live count.
+  int init_retirement() {
+    if (!retire) return FF_OK;
+    const size_t ncnt = (size_t)T * nch;
+    if (lagged && ncnt + (size_t)Btot <= (size_t)kn.pinned) {
+      fin_host = pool->hpin + ncnt;
+      fin_dev = pool->hpin_dev + ncnt;
+    }
+    if (pool->stage_cap < 2 * (size_t)Btot) {   // (no upload of an earlier decode is in flight: it synchronised before returning)
+      if (pool->stage) FF_CHECK_HIP(hipHostFree(pool->stage));
+      pool->stage = nullptr; pool->stage_cap = 0;
+      FF_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&pool->stage), sizeof(int) * 2 * (size_t)Btot, hipHostMallocDefault));
+      pool->stage_cap = 2 * (size_t)Btot;
+    }
+    hfin.assign((size_t)Btot, T);
+    hslot.resize(chunks.size());
+    for (Chunk& c : chunks) {
+      std::vector<char> live((size_t)c.Bc);
+      for (int wl = 0; wl < c.nw; ++wl) {
+        const int w = c.w0 + wl, n = io.num_input_host[w], cw = compact_width(p, io.num_input_host, w);
+        for (int f = 0; f < c.Fc; ++f) {
+          const int fc = c.f0 + f, k = wl * c.Fc + f;
+          const int start = fc < n ? fc : m->num_token - 1;
+          live[(size_t)k] = !(fc >= cw || (start >= p->term_lo && start < p->term_hi));
+          if (!live[(size_t)k]) hfin[(size_t)c.b0 + k] = 0;
+        }
+      }
+      c.Fl = ordered_slots(live, c.nw, c.Fc, &hslot[(size_t)(&c - chunks.data())]);
+      c.Bl = c.nw * c.Fl;
+    }
+    if (lagged) memset(pool->hpin, 0, sizeof(int) * ncnt);   // (counters of launches a finished chunk never makes)
+    if (fin_host) memcpy(fin_host, hfin.data(), sizeof(int) * (size_t)Btot);
+    return FF_OK;
+  }
+  int sync_all() { for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipStreamSynchronize(sts[s])); return FF_OK; }
+  // prologue(), greedy_loop() and epilogue() queue kernels that use the caller's workspace.  When one of them fails, ff_decode
+  // drains every stream before it returns the error: the caller frees the workspace next.
+  void drain() {
+    for (int s = 0; s < ns; ++s) (void)hipStreamSynchronize(sts[s]);
+    (void)hipStreamSynchronize(io.main_st);
+  }
+  // the side streams continue behind what the main stream holds now
+  int fork() {
+    if (!forked) return FF_OK;
+    FF_CHECK_HIP(hipEventRecord(pool->fork_ev, io.main_st));
+    for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipStreamWaitEvent(sts[s], pool->fork_ev, 0));
+    return FF_OK;
+  }
+  // n ints of device memory on the host, behind everything enqueued so far (drained: the streams are idle already)
+  int read_back(int* dst, const int* src, size_t n, bool drained = false) {
+    if (!drained) FF_RETURN_IF(sync_all());
+    FF_CHECK_HIP(hipMemcpyAsync(dst, src, sizeof(int) * n, hipMemcpyDeviceToHost, io.main_st));
+    FF_CHECK_HIP(hipStreamSynchronize(io.main_st));
+    return FF_OK;
+  }
+  // ---- per-batch invariants (main stream), then the first decoder input rows of every micro-batch ----
+  int prologue() {
+    const float* memory = io.memory;
+    const hipStream_t main_st = io.main_st;
+    const int RS = N * S;
+    // memory + pos, cross-attention K|V of every layer
+    FF_RETURN_IF(ff_add_pos(memory, E, m->pos_table, E, 1, S, buf.mem_pos, E, RS, E, main_st));
+    for (int l = 0; l < m->num_dec_layers; ++l) {
+      const ff_mha_weights& c = m->dec[l].cross_attn;
+      FF_RETURN_IF(gemm(buf.mem_pos, E, memory, E, c.in_proj_w + (size_t)E * E, E, c.in_proj_b + E, nullptr, 0,
+                        buf.kvc[l], 2 * E, RS, 2 * E, E, 0, main_st));
+      if (buf.kvp[l])
+        FF_RETURN_IF(ff_attention_split_kv(buf.kvc[l], buf.kvc[l] + E, 2 * E, 2 * E, N, m->H, S, S, 1, buf.kvp[l], main_st));
+    }
+    FF_CHECK_HIP(hipMemsetAsync(buf.zeroed, 0, sizeof(int) * buf.zeroed_count, main_st));
+    if (retire) {   // initial slot maps (and finish positions when they live in the workspace), from the pinned staging area
+      int *st_slot = pool->stage, *st_fin = pool->stage + Btot;
+      for (const Chunk& c : chunks) {
+        const std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
+        if (!hs.empty()) memcpy(st_slot + c.b0, hs.data(), sizeof(int) * hs.size());
+      }
+      FF_CHECK_HIP(hipMemcpyAsync(buf.slot_all, st_slot, sizeof(int) * (size_t)Btot, hipMemcpyHostToDevice, main_st));
+      if (!fin_host) {
+        memcpy(st_fin, hfin.data(), sizeof(int) * (size_t)Btot);
+        FF_CHECK_HIP(hipMemcpyAsync(buf.fin, st_fin, sizeof(int) * (size_t)Btot, hipMemcpyHostToDevice, main_st));
+      }
+    }
+    FF_RETURN_IF(fork());
+    // pointer_fold operands of the one-wireframe micro-batches: G = memory_w W' ([S, E]; W' = the folded project weight, used
+    // transposed), c = memory_w b'
+    bool any_pg = false;
+    for (const Chunk& c : chunks) any_pg = any_pg || c.pg != nullptr;
+    if (any_pg) {
+      FF_RETURN_IF(ff_transpose(m->proj_fold_w, E, E, E, buf.projT, E, main_st));
+      FF_RETURN_IF(fork());
+      for (const Chunk& c : chunks) {
+        if (!c.pg) continue;
+        const float* mem_w = memory + (size_t)c.w0 * S * E;
+        FF_RETURN_IF(gemm(mem_w, E, nullptr, 0, buf.projT, E, nullptr, nullptr, 0, c.pg, E, S, E, E, 0, sts[c.sid]));
+        FF_RETURN_IF(gemm(mem_w, E, nullptr, 0, m->proj_fold_b, E, nullptr, nullptr, 0, c.pc, 1, S, 1, E, 0, sts[c.sid]));
+      }
+    }
+    // start tokens (anchors / SOS) and first decoder input rows of every micro-batch
+    for (const Chunk& c : chunks) {
+      // (retirement: the start tokens of the slots go to the chunk's perm area, free until its first compaction)
+      hipLaunchKernelGGL(init_tokens_kernel, dim3(ff_cdiv(c.Bc, 256)), dim3(256), 0, sts[c.sid], buf.tok_all + c.b0,
+                         c.Bc, c.Fc, c.f0, io.num_input ? io.num_input + c.w0 : nullptr, p->variant, m->num_token - 1,
+                         p->tok_sos, c.slot, c.perm, c.slot ? c.Bl : 0);
+      FF_CHECK_LAUNCH();
+      if (c.Bl > 0)
+        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, c.slot ? c.perm : buf.tok_all + c.b0, c.Bl, c.Fl, c.x0, E,
+                                    sts[c.sid]));
+    }
+    return FF_OK;
+  }
+  // Decode step `step` (position t = step + 1) of every micro-batch that has slots left, on the chunk's stream: the slot set
+  // decoded now is Fl / Bl wide (the chunk's Fc / Bc without retirement).
+  int enqueue_step(int step) {
+    const int t = step + 1;
+    int nslots = 0;
+    for (const Chunk& c : chunks) {
+      if (c.Bl == 0) continue;   // (retirement: nothing of this micro-batch is left)
+      nslots += c.Bl;
+      hipStream_t st = sts[c.sid];
+      const Scratch& sc = buf.scr[c.sid];
+      const size_t trow = (size_t)step * ((size_t)N * F) + c.b0;  // traces: step stride N*F (caller sizes them so)
+      const size_t slot = (size_t)step * nch + (size_t)(&c - chunks.data());
+      const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bl);
+      // (retirement: the logits rows are in slot order; a traced step scatters them to the sequences' rows below)
+      float* logits_dst = (io.trace_logits && !retire) ? io.trace_logits + trow * S : sc.logits;
+      ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, lagged ? buf.arrive + slot : nullptr,
+                            lagged ? pool->hpin_dev + slot : nullptr, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
+                            folded_head ? 1 : 0, c.slot, retire ? fin_dev + c.b0 : nullptr, t, p->term_lo, p->term_hi};
+      FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fl, c.Bl, io.mask, io.kv_len, t, false, nullptr, st,
+                                folded_head ? logits_dst : nullptr));
+      FF_RETURN_IF(ff_pointer_argmax_sync(
+          folded_head ? nullptr : sc.p, E, io.memory + (size_t)c.w0 * S * E, S, E, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0,
+          io.extra_mask ? io.extra_mask + (size_t)c.b0 * S : nullptr, S, c.Bl, c.Fl,
+          buf.tok_all + (size_t)t * Btot + c.b0, io.trace_best ? io.trace_best + trow : nullptr,
+          io.trace_second ? io.trace_second + trow : nullptr, logits_dst, S,
+          c.x0 + (size_t)t * c.Bl * E, E, buf.cnt_ge + slot, m->num_token, buf.cnt_eq + slot, p->tok_eos,
+          (each_eos || lagged || c.x0stat || folded_head || retire) ? &psync : nullptr, st));
+      if (retire && io.trace_logits)
+        FF_RETURN_IF(ff_permute_rows(sc.logits, c.Bl, nullptr, io.trace_logits + trow * S, c.Bc, c.slot, 1, c.Bl, S, st));
+    }
+    slots_per_step.push_back(nslots);
+    return FF_OK;
+  }
+  // the stop rule over the first n steps' counters, per_chunk = [n][nch]
+  bool stop_rule(const int* per_chunk, int n) {
+    tot.assign((size_t)n, 0);
+    const volatile int* v = per_chunk;
+    for (int s = 0; s < n; ++s)
+      for (int c = 0; c < nch; ++c) tot[(size_t)s] += v[(size_t)s * nch + c];
+    const int* cnt = tot.data();
+    if (p->stop_fn) return p->stop_fn(p->stop_user, cnt, n) != 0;   // the caller's (batch-global) rule
+    if (p->variant == FF_PARALLEL) {
+      for (int s = 0; s < n; ++s) if (cnt[s] == 0) return true;
+    } else {
+      int cum = 0;
+      for (int s = 0; s < n; ++s) { cum += cnt[s]; if (cum == N) return true; }
+    }
+    return false;
+  }
+  // FF_RETIRE_FINISHED check point: sequences whose finish position is <= bound leave their micro-batch.  `bound` is a position
+  // whose step is already enqueued, and only finish positions <= bound are looked at (later ones may or may not be visible
+  // yet): the decision does not depend on timing.  A chunk is compacted when it loses at least retire_min_shrink of its slots.
+  // x0 (positions 0..enq), qkv0 (0..enq-1) and the appended rows' statistics are gathered into the stream's scratch in the new
+  // slot order and copied back; the maps come from the pinned staging area, whose previous uploads have completed (every check
+  // point first waits for events recorded behind them, or drains the streams).  Returns the number of live sequences left.
+  int compact_chunks(int bound, long* live_left) {
+    *live_left = 0;
+    size_t soff = 0;
+    for (Chunk& c : chunks) {
+      if (c.Bl == 0) continue;
+      std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
+      std::vector<char> live((size_t)c.Bl);
+      for (int i = 0; i < c.Bl; ++i) live[(size_t)i] = hfin[(size_t)c.b0 + hs[(size_t)i]] > bound;
+      std::vector<int> perm;
+      const int fl = ordered_slots(live, c.nw, c.Fl, &perm, live_left), nb = c.nw * fl;
+      const int shrink = c.Bl - nb;
+      if (shrink == 0 || (double)shrink < (double)p->retire_min_shrink * c.Bl) continue;
+      hipStream_t st = sts[c.sid];
+      std::vector<int> nhs((size_t)nb);
+      for (int i = 0; i < nb; ++i) nhs[(size_t)i] = hs[(size_t)perm[(size_t)i]];
+      if (nb > 0) {
+        int* sp = pool->stage + soff;
+        int* ss = sp + nb;
+        soff += 2 * (size_t)nb;
+        memcpy(sp, perm.data(), sizeof(int) * (size_t)nb);
+        memcpy(ss, nhs.data(), sizeof(int) * (size_t)nb);
+        FF_CHECK_HIP(hipMemcpyAsync(c.perm, sp, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, st));
+        const Scratch& sc = buf.scr[c.sid];
+        auto regather = [&](float* rows, float* scratch, int npos, int width) -> int {   // npos positions of `width` floats per slot
+          FF_RETURN_IF(ff_permute_rows(rows, c.Bl, c.perm, scratch, nb, nullptr, npos, nb, width, st));
+          FF_CHECK_HIP(hipMemcpyAsync(rows, scratch, sizeof(float) * (size_t)npos * nb * width, hipMemcpyDeviceToDevice, st));
+          return FF_OK;
+        };
+        FF_RETURN_IF(regather(c.x0, sc.x, enq + 1, E));
+        if (c.qkv0) FF_RETURN_IF(regather(c.qkv0, sc.qkv, enq, 3 * E));
+        if (c.x0stat) FF_RETURN_IF(regather(c.x0stat, sc.y, 1, E / 16));
+        // the new slot map: perm and slot are adjacent in the staging area, the device slot map is behind the gather above
+        FF_CHECK_HIP(hipMemcpyAsync(c.slot, ss, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, st));
+      }
+      hs.swap(nhs);
+      c.Fl = fl; c.Bl = nb;
+    }
+    return FF_OK;
+  }
+  // retirement at a check point: finish positions <= bound, read from host-mapped memory (behind the events just waited for)
+  // or -- when they live in the workspace -- after draining the streams (bound = enq - 1: step `bound` is enqueued either way)
+  int retire_at(int bound, bool drained) {
+    if (fin_host) {
+      const volatile int* v = fin_host;
+      for (int i = 0; i < Btot; ++i) hfin[(size_t)i] = v[i];
+    } else {
+      FF_RETURN_IF(read_back(hfin.data(), buf.fin, (size_t)Btot, drained));
+      bound = enq - 1;
+    }
+    long live = 0;
+    FF_RETURN_IF(compact_chunks(bound, &live));
+    if (live == 0) stopped = true;   // (the steps_kernel finds the step with no unfinished sequence among those enqueued)
+    return FF_OK;
+  }
+  int wait_marks() { for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipEventSynchronize(pool->chk_ev[s])); return FF_OK; }
+  // Stop rule on the host WITHOUT draining the queue and WITHOUT a copy launch: every pointer launch owns the counter of
+  // its (step, micro-batch) and its last block stores the total into host-mapped pinned memory (ff_pointer_count_block).
+  // Every sync_every steps an event is recorded behind the steps enqueued so far (on every stream); it is waited for
+  // when another sync_every steps have been enqueued -- by then the host is a whole period ahead of it, so the wait
+  // normally returns at once and the GPU always has a period of steps queued.  A stop is noticed at most
+  // 2 * sync_every - 1 steps late; those surplus steps are dropped by the finalize kernels (exact results).
+  int check_point() {
+    if (lagged) {
+      if (pending_enq > 0) {
+        FF_RETURN_IF(wait_marks());
+        stopped = stop_rule(pool->hpin, pending_enq);
+        if (!stopped && retire) FF_RETURN_IF(retire_at(pending_enq, false));
+        pending_enq = 0;
+      }
+      if (!stopped) {
+        for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipEventRecord(pool->chk_ev[s], sts[s]));
+        pending_enq = enq;
+      }
+      return FF_OK;
+    }
+    // more (step, micro-batch) counters than host slots: drain and copy
+    // A caller's stop_fn is asked at the SAME cadence as on the lagged path (the first enq - sync_every steps, from
+    // enq = 2 sync_every on): peers and idle ranks of a sharded decode replay exactly that sequence of host collectives
+    // (dist.check_points).  The local rule has no such contract and looks at everything that has run.
+    const int n_eval = p->stop_fn ? enq - p->sync_every : enq;
+    if (n_eval <= 0) return FF_OK;
+    std::vector<int> hcnt((size_t)n_eval * nch);
+    FF_RETURN_IF(read_back(hcnt.data(), p->variant == FF_PARALLEL ? buf.cnt_ge : buf.cnt_eq, hcnt.size()));
+    stopped = stop_rule(hcnt.data(), n_eval);
+    if (!stopped && retire) FF_RETURN_IF(retire_at(enq - 1, true));
+    return FF_OK;
+  }
+  // ---- greedy loop -----------------------------------------------------------------------------------
+  int greedy_loop() {
+    const int max_steps = T - 1;
+    const auto host_t0 = std::chrono::steady_clock::now();
+    while (enq < max_steps && !stopped) {
+      FF_RETURN_IF(enqueue_step(enq));
+      ++enq;
+      if (p->sync_every > 0 && !(p->flags & FF_NO_STOP) && (enq % p->sync_every) == 0 && enq < max_steps) FF_RETURN_IF(check_point());
+    }
+    if (pending_enq > 0) FF_RETURN_IF(wait_marks());   // the slots are reused by the next call
+    if (p->slots_per_step)
+      for (int s = 0; s < T - 1; ++s) p->slots_per_step[s] = s < (int)slots_per_step.size() ? slots_per_step[(size_t)s] : 0;
+    if (kn.dbg_timing) {
+      const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
+      FF_RETURN_IF(sync_all());
+      const double tot_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
+      fprintf(stderr, "[ff_decode] host enqueue of %d steps x %zu chunks (%d of %d sequences decoded): %.2f ms; until GPU idle: "
+                      "%.2f ms\n", enq, chunks.size(), Btot, N * F, host_ms, tot_ms);
+    }
+    return FF_OK;
+  }
+  // Join, then everything after the greedy loop on the main stream: stop step, packing, the optional return-pointer pass.
+  int epilogue() {
+    const hipStream_t main_st = io.main_st;
+    if (forked)
+      for (int s = 0; s < ns; ++s) {
+        FF_CHECK_HIP(hipEventRecord(pool->join_ev[s], sts[s]));
+        FF_CHECK_HIP(hipStreamWaitEvent(main_st, pool->join_ev[s], 0));
+      }
+    hipLaunchKernelGGL(steps_kernel, dim3(1), dim3(64), 0, main_st, buf.cnt_ge, buf.cnt_eq, nch, p->variant, N, enq,
+                       ((p->flags & FF_NO_STOP) || p->stop_fn) ? 1 : 0, buf.cnt_tot, buf.steps_dev);
+    FF_CHECK_LAUNCH();
+    for (const Chunk& c : chunks) {
+      const long total = (long)c.nw * F * T;
+      const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+      hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
+                         io.num_input, dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, io.predict, io.seq_of_row,
+                         retire ? fin_dev : nullptr);
+      FF_CHECK_LAUNCH();
+    }
+    int steps = 0;
+    FF_CHECK_HIP(hipMemcpyAsync(&steps, buf.steps_dev, sizeof(int), hipMemcpyDeviceToHost, main_st));
+    if (io.step_counts && enq > 0)
+      FF_CHECK_HIP(hipMemcpyAsync(io.step_counts, buf.cnt_tot, sizeof(int) * enq, hipMemcpyDeviceToHost, main_st));
+    FF_CHECK_HIP(hipStreamSynchronize(main_st));
+    if (io.steps_done) *io.steps_done = steps;
+
+    // ---- optional: project(decoder(...)) of every prefix row at the last executed step
+    //      (SurfaceFormer returns it as inputs['pointer'], reference model.py:217) --------------------
+    if ((p->flags & FF_RETURN_POINTER) && steps > 0) {
+      FF_CHECK_ARG(m->FF >= m->E, "ff_decode: FF_RETURN_POINTER needs FF >= E");
+      FF_CHECK_ARG(Btot == N * F, "ff_decode: FF_RETURN_POINTER is not available with de-duplicated sequences");
+      for (const Chunk& c : chunks) {
+        const Scratch& sc = buf.scr[0];
+        // one micro-batch: its [steps * Bc, E] rows ARE pointer_out [steps, Btot, E]; several: through the FF-wide scratch
+        // and one strided copy per micro-batch (was one copy launch per position: 258 of them for configs A / D)
+        float* proj_all = nch == 1 ? io.pointer_out : sc.h;
+        FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, steps, true, proj_all, main_st));
+        if (nch > 1)
+          FF_CHECK_HIP(hipMemcpy2DAsync(io.pointer_out + (size_t)c.b0 * E, sizeof(float) * (size_t)Btot * E, proj_all,
+                                        sizeof(float) * (size_t)c.Bc * E, sizeof(float) * (size_t)c.Bc * E, (size_t)steps,
+                                        hipMemcpyDeviceToDevice, main_st));
+      }
+    }
+    return FF_OK;
+  }
+};
 
 }  // namespace
 
@@ -708,443 +1145,19 @@ extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const flo
                          int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
                          float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
                          size_t workspace_bytes, ff_stream_t stream) {
-  FF_RETURN_IF(check_model(m));
-  FF_CHECK_ARG(p != nullptr, "ff_decode: null params");
-  FF_CHECK_ARG(p->variant == FF_PARALLEL || p->variant == FF_SEQ2SEQ, "ff_decode: bad variant");
-  FF_CHECK_ARG(p->N > 0 && p->L >= 0 && p->F > 0 && p->T >= 1, "ff_decode: bad sizes");
-  FF_CHECK_ARG(memory && mask && kv_len && predict && workspace, "ff_decode: null pointer");
-  FF_CHECK_ARG(p->variant != FF_PARALLEL || num_input, "ff_decode: num_input required for the parallel variant");
-  FF_CHECK_ARG(p->variant != FF_SEQ2SEQ || p->F == 1, "ff_decode: seq2seq decodes one sequence per wireframe");
-  FF_CHECK_ARG(!p->stop_fn || (p->flags & FF_NO_STOP) || p->sync_every > 0, "ff_decode: stop_fn needs sync_every > 0");
-  // The callback's cadence is a CONTRACT with callers that replay it elsewhere (an idle rank of a sharded decode joins the
-  // same host collectives: faceformer_amd/dist.py check_points): the counters of the first n = enq - sync_every steps when
-  // enq = 2 sync_every, 3 sync_every, ... steps are enqueued.  Both check paths below (host-mapped counters; drain + copy when
-  // there are more counters than slots) keep that cadence for a stop_fn (tests: FF_PINNED_COUNTERS=8 in a child process).
-  FF_CHECK_ARG(!(p->flags & FF_STOP_EACH_EOS) || p->variant == FF_SEQ2SEQ, "ff_decode: FF_STOP_EACH_EOS is a seq2seq rule");
-  const int E = m->E, S = p->L + m->num_token, T = p->T, F = p->F, N = p->N;
-  FF_CHECK_ARG(S <= m->pos_len, "ff_decode: S=%d exceeds the position table (%d rows)", S, m->pos_len);
-  FF_CHECK_ARG(T - 1 <= m->qpos_len, "ff_decode: T-1=%d exceeds the query position table (%d rows)", T - 1, m->qpos_len);
-  FF_CHECK_ARG(p->variant != FF_PARALLEL || F <= S, "ff_decode: F=%d anchors exceed S=%d", F, S);
-  FF_CHECK_ARG(!(p->flags & FF_RETURN_POINTER) || pointer_out, "ff_decode: pointer_out required");
-  const bool retire = retiring(p);
-  if (p->flags & FF_RETIRE_FINISHED) {
-    FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode: FF_RETIRE_FINISHED is a parallel-variant option");
-    FF_CHECK_ARG(!(p->flags & (FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn,
-                 "ff_decode: FF_RETIRE_FINISHED excludes FF_RETURN_POINTER, FF_NO_STOP and a stop_fn");
-    FF_CHECK_ARG(num_input_host, "ff_decode: FF_RETIRE_FINISHED needs num_input_host");
-    FF_CHECK_ARG(p->term_lo < p->term_hi, "ff_decode: empty terminator range [%d, %d)", p->term_lo, p->term_hi);
-  }
-  // every padding-anchor sequence has its own row of an extra mask: no de-duplication then
-  ff_decode_params prm_local = *p;
-  if (extra_mask) prm_local.flags &= ~FF_DEDUP_PAD_ANCHORS;
-  p = &prm_local;
-  const bool dedup = p->variant == FF_PARALLEL && (p->flags & FF_DEDUP_PAD_ANCHORS) && num_input_host;
-  hipStream_t main_st = (hipStream_t)stream;
-
-  const int ns_req = plan_streams(p);
-  std::vector<Chunk> chunks;
-  int Btot = 0, max_bc = 0;
-  plan_chunks(p, num_input_host, ns_req, &chunks, &Btot, &max_bc);
-  Bump bp(workspace, workspace_bytes);
-  DecodeBuffers buf;
-  const int nch = (int)chunks.size();
-  const EngineKnobs kn = engine_knobs(p);
-  layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf);
-  if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
-  for (Chunk& c : chunks) {
-    c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
-    c.qkv0 = buf.qkv0_all ? buf.qkv0_all + (size_t)T * c.b0 * 3 * E : nullptr;
-    c.x0stat = buf.x0stat_all ? buf.x0stat_all + (size_t)c.b0 * (E / 32) * 2 : nullptr;
-    const size_t ci = (size_t)(&c - chunks.data());
-    const bool one = c.nw == 1 && buf.pg_all != nullptr;
-    c.pg = one ? buf.pg_all + ci * (size_t)(p->L + m->num_token) * E : nullptr;
-    c.pc = one ? buf.pc_all + ci * (size_t)((p->L + m->num_token + 3) & ~3) : nullptr;
-    if (retire) { c.slot = buf.slot_all + c.b0; c.perm = buf.perm_all + c.b0; }
-  }
-  const int ns = ns_req < (int)chunks.size() ? ns_req : (int)chunks.size();
-  const bool forked = ns > 1;
-  // With more than one stream ALL micro-batch work runs on the internal pool (the caller's stream is
-  // often the legacy default stream, whose implicit synchronisation would serialise the others).
-  hipStream_t sts[FF_MAX_STREAMS];
-  sts[0] = main_st;
-  StreamPool* pool = nullptr;
-  FF_RETURN_IF(ff_gemm_prepare_stream(main_st));
+  DecodeRun r;
+  FF_RETURN_IF(r.validate(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, extra_mask, predict, steps_done, step_counts,
+                                         pointer_out, trace_logits, trace_best, trace_second, seq_of_row, (hipStream_t)stream}, workspace));
+  FF_RETURN_IF(r.bind_chunks(workspace, workspace_bytes));
+  FF_RETURN_IF(ff_gemm_prepare_stream(r.io.main_st));
   std::mutex* busy = pool_busy_mutex();
   FF_CHECK_ARG(busy, "ff_decode: no current device");
   std::lock_guard<std::mutex> one_decode_per_device(*busy);
-  FF_RETURN_IF(pool_get(forked ? ns : 0, &pool));   // (also owns the pinned counter buffer / events of the stop check)
-
-  // ---- FF_RETIRE_FINISHED: the initial slot sets (host side) -------------------------------------------------------------------
-  // fin[seq] = 0 for the sequences whose start token already ends them (the padding anchors and anchors term_lo.. of the model:
-  // reference quirk C-3) and for the surplus padding copies of narrow wireframes; T (none yet) for the others.  Every chunk starts
-  // with its live sequences only: per wireframe the live ones in order, then finished ones of the same wireframe up to the
-  // chunk's widest live count.
-  std::vector<int> hfin;                       // host copy of the finish positions (pageable; filled from fin_host at check points)
-  std::vector<std::vector<int>> hslot;         // per chunk: the chunk-local sequence of every slot
-  int* fin_host = nullptr;                     // host address of the finish positions when they are host-mapped, else null
-  int* fin_dev = buf.fin;
-  const bool lagged_ = (size_t)T * (size_t)nch <= (size_t)kn.pinned;
-  if (retire) {
-    if (lagged_ && (size_t)T * nch + (size_t)Btot <= (size_t)kn.pinned) {
-      fin_host = pool->hpin + (size_t)T * nch;
-      fin_dev = pool->hpin_dev + (size_t)T * nch;
-    }
-    if (pool->stage_cap < 2 * (size_t)Btot) {   // (no upload of an earlier decode is in flight: it synchronised before returning)
-      if (pool->stage) FF_CHECK_HIP(hipHostFree(pool->stage));
-      pool->stage = nullptr; pool->stage_cap = 0;
-      FF_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&pool->stage), sizeof(int) * 2 * (size_t)Btot, hipHostMallocDefault));
-      pool->stage_cap = 2 * (size_t)Btot;
-    }
-    hfin.assign((size_t)Btot, T);
-    hslot.resize(chunks.size());
-    for (Chunk& c : chunks) {
-      std::vector<std::vector<int>> live((size_t)c.nw), dead((size_t)c.nw);
-      int fl = 0;
-      for (int wl = 0; wl < c.nw; ++wl) {
-        const int w = c.w0 + wl, n = num_input_host[w], cw = compact_width(p, num_input_host, w);
-        for (int f = 0; f < c.Fc; ++f) {
-          const int fc = c.f0 + f, k = wl * c.Fc + f;
-          const int start = fc < n ? fc : m->num_token - 1;
-          const bool dead_now = fc >= cw || (start >= p->term_lo && start < p->term_hi);
-          if (dead_now) hfin[(size_t)c.b0 + k] = 0;
-          (dead_now ? dead : live)[(size_t)wl].push_back(k);
-        }
-        fl = (int)live[(size_t)wl].size() > fl ? (int)live[(size_t)wl].size() : fl;
-      }
-      std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
-      for (int wl = 0; wl < c.nw; ++wl) {
-        std::vector<int> order = live[(size_t)wl];
-        order.insert(order.end(), dead[(size_t)wl].begin(), dead[(size_t)wl].end());
-        hs.insert(hs.end(), order.begin(), order.begin() + fl);
-      }
-      c.Fl = fl; c.Bl = c.nw * fl;
-    }
-    if (lagged_) memset(pool->hpin, 0, sizeof(int) * (size_t)T * nch);   // (counters of launches a finished chunk never makes)
-    if (fin_host) memcpy(fin_host, hfin.data(), sizeof(int) * (size_t)Btot);
-  }
-  std::vector<int> slots_per_step;
-  if (forked)
-    for (int s = 0; s < ns; ++s) sts[s] = pool->side[s];
-  auto sync_all = [&]() -> int {
-    for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipStreamSynchronize(sts[s]));
-    return FF_OK;
-  };
-
-  int enq = 0;
-  const bool each_eos = (p->flags & FF_STOP_EACH_EOS) != 0;
-  // Everything that enqueues work on the side streams sits in this lambda: on ANY failure the streams are
-  // drained before the error is returned (the caller frees the workspace the queued kernels use).
-  auto run = [&]() -> int {
-    // ---- per-batch invariants (main stream): memory + pos, cross-attention K|V of every layer ----
-    const int RS = N * S;
-    FF_RETURN_IF(ff_add_pos(memory, E, m->pos_table, E, 1, S, buf.mem_pos, E, RS, E, main_st));
-    for (int l = 0; l < m->num_dec_layers; ++l) {
-      const ff_mha_weights& c = m->dec[l].cross_attn;
-      FF_RETURN_IF(gemm(buf.mem_pos, E, memory, E, c.in_proj_w + (size_t)E * E, E, c.in_proj_b + E, nullptr, 0,
-                        buf.kvc[l], 2 * E, RS, 2 * E, E, 0, main_st));
-      if (buf.kvp[l])
-        FF_RETURN_IF(ff_attention_split_kv(buf.kvc[l], buf.kvc[l] + E, 2 * E, 2 * E, N, m->H, S, S, 1, buf.kvp[l], main_st));
-    }
-    // cnt_ge | cnt_eq | arrive | seen are consecutive in the workspace (layout_decode): ONE fill
-    FF_CHECK_HIP(hipMemsetAsync(buf.cnt_ge, 0, (size_t)(reinterpret_cast<char*>(buf.seen + Btot) - reinterpret_cast<char*>(buf.cnt_ge)),
-                                main_st));
-    if (retire) {   // initial slot maps (and finish positions when they live in the workspace), from the pinned staging area
-      int* st_slot = pool->stage;
-      int* st_fin = pool->stage + Btot;
-      for (const Chunk& c : chunks) {
-        const std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
-        if (!hs.empty()) memcpy(st_slot + c.b0, hs.data(), sizeof(int) * hs.size());
-      }
-      FF_CHECK_HIP(hipMemcpyAsync(buf.slot_all, st_slot, sizeof(int) * (size_t)Btot, hipMemcpyHostToDevice, main_st));
-      if (!fin_host) {
-        memcpy(st_fin, hfin.data(), sizeof(int) * (size_t)Btot);
-        FF_CHECK_HIP(hipMemcpyAsync(buf.fin, st_fin, sizeof(int) * (size_t)Btot, hipMemcpyHostToDevice, main_st));
-      }
-    }
-    if (forked) {  // fork
-      FF_CHECK_HIP(hipEventRecord(pool->fork_ev, main_st));
-      for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipStreamWaitEvent(sts[s], pool->fork_ev, 0));
-    }
-    // pointer_fold operands of the one-wireframe micro-batches: G = memory_w W' ([S, E]; W' = the folded project weight, used
-    // transposed), c = memory_w b'
-    bool any_pg = false;
-    for (const Chunk& c : chunks) any_pg = any_pg || c.pg != nullptr;
-    if (any_pg) {
-      FF_RETURN_IF(ff_transpose(m->proj_fold_w, E, E, E, buf.projT, E, main_st));
-      if (forked) {
-        FF_CHECK_HIP(hipEventRecord(pool->fork_ev, main_st));
-        for (int s = 0; s < ns; ++s) FF_CHECK_HIP(hipStreamWaitEvent(sts[s], pool->fork_ev, 0));
-      }
-      for (const Chunk& c : chunks) {
-        if (!c.pg) continue;
-        const float* mem_w = memory + (size_t)c.w0 * S * E;
-        FF_RETURN_IF(gemm(mem_w, E, nullptr, 0, buf.projT, E, nullptr, nullptr, 0, c.pg, E, S, E, E, 0, sts[c.sid]));
-        FF_RETURN_IF(gemm(mem_w, E, nullptr, 0, m->proj_fold_b, E, nullptr, nullptr, 0, c.pc, 1, S, 1, E, 0, sts[c.sid]));
-      }
-    }
-    // start tokens (anchors / SOS) and first decoder input rows of every micro-batch
-    for (const Chunk& c : chunks) {
-      // (retirement: the start tokens of the slots go to the chunk's perm area, free until its first compaction)
-      hipLaunchKernelGGL(init_tokens_kernel, dim3(ff_cdiv(c.Bc, 256)), dim3(256), 0, sts[c.sid], buf.tok_all + c.b0,
-                         c.Bc, c.Fc, c.f0, num_input ? num_input + c.w0 : nullptr, p->variant, m->num_token - 1,
-                         p->tok_sos, c.slot, c.perm, c.slot ? c.Bl : 0);
-      FF_CHECK_LAUNCH();
-      if (c.Bl > 0)
-        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, c.slot ? c.perm : buf.tok_all + c.b0, c.Bl, c.Fl, c.x0, E,
-                                    sts[c.sid]));
-    }
-
-    // ---- greedy loop -----------------------------------------------------------------------------------
-    const int max_steps = T - 1;
-    const bool dbg_timing = kn.dbg_timing;
-    const auto host_t0 = std::chrono::steady_clock::now();
-    // Stop rule on the host WITHOUT draining the queue and WITHOUT a copy launch: every pointer launch owns the counter of
-    // its (step, micro-batch) and its last block stores the total into host-mapped pinned memory (ff_pointer_count_block).
-    // Every sync_every steps an event is recorded behind the steps enqueued so far (on every stream); it is waited for
-    // when another sync_every steps have been enqueued -- by then the host is a whole period ahead of it, so the wait
-    // normally returns at once and the GPU always has a period of steps queued.  A stop is noticed at most
-    // 2 * sync_every - 1 steps late; those surplus steps are dropped by the finalize kernels (exact results).
-    bool stopped = false;
-    int pending_enq = 0;   // > 0: events covering steps [0, pending_enq) are in flight
-    const bool lagged = lagged_;
-    std::vector<int> tot;
-    auto host_totals = [&](const int* per_chunk, int n) -> const int* {   // [n][nch] -> per-step totals
-      tot.assign((size_t)n, 0);
-      const volatile int* v = per_chunk;
-      for (int s_ = 0; s_ < n; ++s_)
-        for (int c = 0; c < nch; ++c) tot[(size_t)s_] += v[(size_t)s_ * nch + c];
-      return tot.data();
-    };
-    auto eval_counts = [&](const int* cnt, int n) {
-      if (p->stop_fn) return p->stop_fn(p->stop_user, cnt, n) != 0;   // the caller's (batch-global) rule
-      if (p->variant == FF_PARALLEL) {
-        for (int s = 0; s < n; ++s) if (cnt[s] == 0) return true;
-      } else {
-        int cum = 0;
-        for (int s = 0; s < n; ++s) { cum += cnt[s]; if (cum == N) return true; }
-      }
-      return false;
-    };
-    auto enqueue_step = [&](int step) -> int {
-      const int t = step + 1;
-      int nslots = 0;
-      for (const Chunk& c0 : chunks) {
-        if (c0.Bl == 0) continue;   // (retirement: nothing of this micro-batch is left)
-        nslots += c0.Bl;
-        Chunk c = c0;               // the slot set decoded now: Fc / Bc = the live widths (unchanged without retirement)
-        c.Fc = c0.Fl; c.Bc = c0.Bl;
-        hipStream_t st = sts[c.sid];
-        const Scratch& sc = buf.scr[c.sid];
-        const size_t trow = (size_t)step * ((size_t)N * F) + c.b0;  // traces: step stride N*F (caller sizes them so)
-        const size_t slot = (size_t)step * nch + (size_t)(&c0 - chunks.data());
-        const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bc);
-        // (retirement: the logits rows are in slot order; a traced step scatters them to the sequences' rows below)
-        float* logits_dst = (trace_logits && !retire) ? trace_logits + trow * S : sc.logits;
-        ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, lagged ? buf.arrive + slot : nullptr,
-                              lagged ? pool->hpin_dev + slot : nullptr, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
-                              folded_head ? 1 : 0, c.slot, retire ? fin_dev + c.b0 : nullptr, t, p->term_lo, p->term_hi};
-        auto pointer_head = [&]() -> int {
-          return ff_pointer_argmax_sync(
-              folded_head ? nullptr : sc.p, E, memory + (size_t)c.w0 * S * E, S, E, mask + (size_t)c.w0 * S, kv_len + c.w0,
-              extra_mask ? extra_mask + (size_t)c.b0 * S : nullptr, S, c.Bc, c.Fc,
-              buf.tok_all + (size_t)t * Btot + c.b0, trace_best ? trace_best + trow : nullptr,
-              trace_second ? trace_second + trow : nullptr, logits_dst, S,
-              c.x0 + (size_t)t * c.Bc * E, E, buf.cnt_ge + slot, m->num_token, buf.cnt_eq + slot, p->tok_eos,
-              (each_eos || lagged || c.x0stat || folded_head || retire) ? &psync : nullptr, st);
-        };
-        FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, mask, kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
-        FF_RETURN_IF(pointer_head());
-        if (retire && trace_logits)
-          FF_RETURN_IF(ff_permute_rows(sc.logits, c.Bc, nullptr, trace_logits + trow * S, c0.Bc, c.slot, 1, c.Bc, S, st));
-      }
-      slots_per_step.push_back(nslots);
-      return FF_OK;
-    };
-    // FF_RETIRE_FINISHED check point: sequences whose finish position is <= bound leave their micro-batch.  `bound` is a position
-    // whose step is already enqueued, and only finish positions <= bound are looked at (later ones may or may not be visible
-    // yet): the decision does not depend on timing.  A chunk is compacted when it loses at least retire_min_shrink of its slots.
-    // x0 (positions 0..enq), qkv0 (0..enq-1) and the appended rows' statistics are gathered into the stream's scratch in the new
-    // slot order and copied back; the maps come from the pinned staging area, whose previous uploads have completed (every check
-    // point first waits for events recorded behind them, or drains the streams).  Returns the number of live sequences left.
-    auto compact_chunks = [&](int bound, long* live_left) -> int {
-      *live_left = 0;
-      size_t soff = 0;
-      for (Chunk& c : chunks) {
-        if (c.Bl == 0) continue;
-        std::vector<int>& hs = hslot[(size_t)(&c - chunks.data())];
-        std::vector<int> perm;
-        int fl = 0;
-        std::vector<std::vector<int>> live((size_t)c.nw), done((size_t)c.nw);
-        for (int wl = 0; wl < c.nw; ++wl) {
-          for (int k = 0; k < c.Fl; ++k) {
-            const int i = wl * c.Fl + k, f = hfin[(size_t)c.b0 + hs[(size_t)i]];
-            (f > bound ? live : done)[(size_t)wl].push_back(i);
-          }
-          *live_left += (long)live[(size_t)wl].size();
-          fl = (int)live[(size_t)wl].size() > fl ? (int)live[(size_t)wl].size() : fl;
-        }
-        const int shrink = c.Bl - c.nw * fl;
-        if (shrink == 0 || (double)shrink < (double)p->retire_min_shrink * c.Bl) continue;
-        for (int wl = 0; wl < c.nw; ++wl) {
-          std::vector<int> order = live[(size_t)wl];
-          order.insert(order.end(), done[(size_t)wl].begin(), done[(size_t)wl].end());
-          perm.insert(perm.end(), order.begin(), order.begin() + fl);
-        }
-        const int nb = c.nw * fl;
-        hipStream_t st = sts[c.sid];
-        if (nb > 0) {
-          int* sp = pool->stage + soff;
-          int* ss = sp + nb;
-          soff += 2 * (size_t)nb;
-          for (int i = 0; i < nb; ++i) { sp[i] = perm[(size_t)i]; ss[i] = hs[(size_t)perm[(size_t)i]]; }
-          FF_CHECK_HIP(hipMemcpyAsync(c.perm, sp, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, st));
-          const Scratch& sc = buf.scr[c.sid];
-          FF_RETURN_IF(ff_permute_rows(c.x0, c.Bl, c.perm, sc.x, nb, nullptr, enq + 1, nb, E, st));
-          FF_CHECK_HIP(hipMemcpyAsync(c.x0, sc.x, sizeof(float) * (size_t)(enq + 1) * nb * E, hipMemcpyDeviceToDevice, st));
-          if (c.qkv0) {
-            FF_RETURN_IF(ff_permute_rows(c.qkv0, c.Bl, c.perm, sc.qkv, nb, nullptr, enq, nb, 3 * E, st));
-            FF_CHECK_HIP(hipMemcpyAsync(c.qkv0, sc.qkv, sizeof(float) * (size_t)enq * nb * 3 * E, hipMemcpyDeviceToDevice, st));
-          }
-          if (c.x0stat) {
-            FF_RETURN_IF(ff_permute_rows(c.x0stat, c.Bl, c.perm, sc.y, nb, nullptr, 1, nb, E / 16, st));
-            FF_CHECK_HIP(hipMemcpyAsync(c.x0stat, sc.y, sizeof(float) * (size_t)nb * (E / 16), hipMemcpyDeviceToDevice, st));
-          }
-          // the new slot map: perm and slot are adjacent in the staging area, the device slot map is behind the gather above
-          FF_CHECK_HIP(hipMemcpyAsync(c.slot, ss, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, st));
-        }
-        std::vector<int> nhs((size_t)nb);
-        for (int i = 0; i < nb; ++i) nhs[(size_t)i] = hs[(size_t)perm[(size_t)i]];
-        hs.swap(nhs);
-        c.Fl = fl; c.Bl = nb;
-      }
-      return FF_OK;
-    };
-    // retirement at a check point: finish positions <= bound, read from host-mapped memory (behind the events just waited for)
-    // or -- when they live in the workspace -- after draining the streams (bound = enq - 1: step `bound` is enqueued either way)
-    auto retire_at = [&](int bound, bool drained) -> int {
-      if (fin_host) {
-        const volatile int* v = fin_host;
-        for (int i = 0; i < Btot; ++i) hfin[(size_t)i] = v[i];
-      } else {
-        if (!drained) FF_RETURN_IF(sync_all());
-        FF_CHECK_HIP(hipMemcpyAsync(hfin.data(), buf.fin, sizeof(int) * (size_t)Btot, hipMemcpyDeviceToHost, main_st));
-        FF_CHECK_HIP(hipStreamSynchronize(main_st));
-        bound = enq - 1;
-      }
-      long live = 0;
-      FF_RETURN_IF(compact_chunks(bound, &live));
-      if (live == 0) stopped = true;   // (the steps_kernel finds the step with no unfinished sequence among those enqueued)
-      return FF_OK;
-    };
-    for (int step = 0; step < max_steps && !stopped;) {
-      FF_RETURN_IF(enqueue_step(step));
-      ++step;
-      enq = step;
-      if (p->sync_every > 0 && !(p->flags & FF_NO_STOP) && (enq % p->sync_every) == 0 && enq < max_steps) {
-        if (lagged) {
-          if (pending_enq > 0) {
-            for (int s_ = 0; s_ < ns; ++s_) FF_CHECK_HIP(hipEventSynchronize(pool->chk_ev[s_]));
-            stopped = eval_counts(host_totals(pool->hpin, pending_enq), pending_enq);
-            if (!stopped && retire) FF_RETURN_IF(retire_at(pending_enq, false));
-            pending_enq = 0;
-          }
-          if (!stopped) {
-            for (int s_ = 0; s_ < ns; ++s_) FF_CHECK_HIP(hipEventRecord(pool->chk_ev[s_], sts[s_]));
-            pending_enq = enq;
-          }
-        } else {   // more (step, micro-batch) counters than host slots: drain and copy
-          // A caller's stop_fn is asked at the SAME cadence as on the lagged path (the first enq - sync_every steps, from
-          // enq = 2 sync_every on): peers and idle ranks of a sharded decode replay exactly that sequence of host collectives
-          // (dist.check_points).  The local rule has no such contract and looks at everything that has run.
-          const int n_eval = p->stop_fn ? enq - p->sync_every : enq;
-          if (n_eval > 0) {
-            std::vector<int> hcnt((size_t)n_eval * nch);
-            FF_RETURN_IF(sync_all());
-            FF_CHECK_HIP(hipMemcpyAsync(hcnt.data(), (p->variant == FF_PARALLEL) ? buf.cnt_ge : buf.cnt_eq,
-                                        sizeof(int) * hcnt.size(), hipMemcpyDeviceToHost, main_st));
-            FF_CHECK_HIP(hipStreamSynchronize(main_st));
-            stopped = eval_counts(host_totals(hcnt.data(), n_eval), n_eval);
-            if (!stopped && retire) FF_RETURN_IF(retire_at(enq - 1, true));
-          }
-        }
-      }
-    }
-    if (pending_enq > 0)   // the slots are reused by the next call
-      for (int s_ = 0; s_ < ns; ++s_) FF_CHECK_HIP(hipEventSynchronize(pool->chk_ev[s_]));
-    if (p->slots_per_step) {
-      for (int s_ = 0; s_ < T - 1; ++s_) p->slots_per_step[s_] = s_ < (int)slots_per_step.size() ? slots_per_step[(size_t)s_] : 0;
-    }
-    if (dbg_timing) {
-      const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
-      FF_RETURN_IF(sync_all());
-      const double tot_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
-      fprintf(stderr, "[ff_decode] host enqueue of %d steps x %zu chunks (%d of %d sequences decoded): %.2f ms; until GPU idle: "
-                      "%.2f ms\n", enq, chunks.size(), Btot, N * F, host_ms, tot_ms);
-    }
-    if (forked) {  // join
-      for (int s = 0; s < ns; ++s) {
-        FF_CHECK_HIP(hipEventRecord(pool->join_ev[s], sts[s]));
-        FF_CHECK_HIP(hipStreamWaitEvent(main_st, pool->join_ev[s], 0));
-      }
-    }
-    return FF_OK;
-  };
-  {
-    const int rc = run();
-    if (rc != FF_OK) {
-      for (int s = 0; s < ns; ++s) (void)hipStreamSynchronize(sts[s]);
-      (void)hipStreamSynchronize(main_st);
-      return rc;
-    }
-  }
-
-  // Everything after the greedy loop (stop step, packing, the optional return-pointer pass) enqueues work that reads the
-  // caller's workspace as well: same rule as above -- on any failure the streams are drained before the error goes back.
-  auto finish = [&]() -> int {
-    hipLaunchKernelGGL(steps_kernel, dim3(1), dim3(64), 0, main_st, buf.cnt_ge, buf.cnt_eq, nch, p->variant, N, enq,
-                       ((p->flags & FF_NO_STOP) || p->stop_fn) ? 1 : 0, buf.cnt_tot, buf.steps_dev);
-    FF_CHECK_LAUNCH();
-    for (const Chunk& c : chunks) {
-      const long total = (long)c.nw * F * T;
-      const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-      hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
-                         num_input, dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, predict, seq_of_row,
-                         retire ? fin_dev : nullptr);
-      FF_CHECK_LAUNCH();
-    }
-    int steps = 0;
-    FF_CHECK_HIP(hipMemcpyAsync(&steps, buf.steps_dev, sizeof(int), hipMemcpyDeviceToHost, main_st));
-    if (step_counts && enq > 0)
-      FF_CHECK_HIP(hipMemcpyAsync(step_counts, buf.cnt_tot, sizeof(int) * enq, hipMemcpyDeviceToHost, main_st));
-    FF_CHECK_HIP(hipStreamSynchronize(main_st));
-    if (steps_done) *steps_done = steps;
-
-    // ---- optional: project(decoder(...)) of every prefix row at the last executed step
-    //      (SurfaceFormer returns it as inputs['pointer'], reference model.py:217) --------------------
-    if ((p->flags & FF_RETURN_POINTER) && steps > 0) {
-      FF_CHECK_ARG(m->FF >= m->E, "ff_decode: FF_RETURN_POINTER needs FF >= E");
-      FF_CHECK_ARG(Btot == N * F, "ff_decode: FF_RETURN_POINTER is not available with de-duplicated sequences");
-      for (const Chunk& c : chunks) {
-        const Scratch& sc = buf.scr[0];
-        // one micro-batch: its [steps * Bc, E] rows ARE pointer_out [steps, Btot, E]; several: through the FF-wide scratch
-        // and one strided copy per micro-batch (was one copy launch per position: 258 of them for configs A / D)
-        float* proj_all = nch == 1 ? pointer_out : sc.h;
-        FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, mask, kv_len, steps, true, proj_all, main_st));
-        if (nch > 1)
-          FF_CHECK_HIP(hipMemcpy2DAsync(pointer_out + (size_t)c.b0 * E, sizeof(float) * (size_t)Btot * E, proj_all,
-                                        sizeof(float) * (size_t)c.Bc * E, sizeof(float) * (size_t)c.Bc * E, (size_t)steps,
-                                        hipMemcpyDeviceToDevice, main_st));
-      }
-    }
-    return FF_OK;
-  };
-  {
-    const int rc = finish();
-    if (rc != FF_OK) {
-      for (int s = 0; s < ns; ++s) (void)hipStreamSynchronize(sts[s]);
-      (void)hipStreamSynchronize(main_st);
-      return rc;
-    }
-  }
-  return FF_OK;
+  FF_RETURN_IF(r.bind_streams());
+  FF_RETURN_IF(r.init_retirement());
+  int rc = r.prologue();
+  if (rc == FF_OK) rc = r.greedy_loop();
+  if (rc == FF_OK) rc = r.epilogue();
+  if (rc != FF_OK) r.drain();
+  return rc;
 }

@@ -1630,43 +1630,34 @@ int ff_gemm_dma_f32(const GemmArgs& a, hipStream_t st, int bn) {
   return x3_launch(g, a.ln_in ? 1 : (a.ln_out ? 2 : 0), st, true, bn == 64 ? 64 : X3_BN);
 }
 
-extern "C" size_t ff_split_weight_bytes(int N, int K) { return (size_t)3 * N * K * sizeof(unsigned short); }
-
-extern "C" int ff_split_weight_bf16x3(const float* W, int ldw, int N, int K, void* planes, ff_stream_t stream) {
-  FF_CHECK_ARG(W && planes && N > 0 && K > 0 && (K & 15) == 0 && ldw >= K, "ff_split_weight_bf16x3: bad arguments (K %% 16)");
-  FF_CHECK_ARG(ff_aligned16(planes), "ff_split_weight_bf16x3: planes must be 16-byte aligned");
+// The three split entry points differ in kernel and term count only: fp16_terms = 0 is the 3 x bf16 split, 2 / 1 the fp16 ones.
+static int split_weight_launch(const char* who, const char* what, int fp16_terms, const float* W, int ldw, int N, int K, void* planes, ff_stream_t stream) {
+  FF_CHECK_ARG(W && planes && N > 0 && K > 0 && (K & 15) == 0 && ldw >= K, "%s: bad arguments (K %% 16)", who);
+  FF_CHECK_ARG(ff_aligned16(planes), "%s: %s must be 16-byte aligned", who, what);
   const size_t n2 = (size_t)N * (K / 2);
   const int grid = (int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096);
-  hipLaunchKernelGGL(split_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K,
-                     static_cast<unsigned short*>(planes));
+  unsigned short* out = static_cast<unsigned short*>(planes);
+  if (fp16_terms == 0)
+    hipLaunchKernelGGL(split_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K, out);
+  else
+    hipLaunchKernelGGL(split_weight_fp16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K, out, fp16_terms);
   FF_CHECK_LAUNCH();
   return FF_OK;
+}
+
+extern "C" size_t ff_split_weight_bytes(int N, int K) { return (size_t)3 * N * K * sizeof(unsigned short); }
+extern "C" int ff_split_weight_bf16x3(const float* W, int ldw, int N, int K, void* planes, ff_stream_t stream) {
+  return split_weight_launch("ff_split_weight_bf16x3", "planes", 0, W, ldw, N, K, planes, stream);
 }
 
 extern "C" size_t ff_split_weight_fp16x2_bytes(int N, int K) { return (size_t)2 * N * K * sizeof(unsigned short); }
-
 extern "C" int ff_split_weight_fp16x2(const float* W, int ldw, int N, int K, void* planes, ff_stream_t stream) {
-  FF_CHECK_ARG(W && planes && N > 0 && K > 0 && (K & 15) == 0 && ldw >= K, "ff_split_weight_fp16x2: bad arguments (K %% 16)");
-  FF_CHECK_ARG(ff_aligned16(planes), "ff_split_weight_fp16x2: planes must be 16-byte aligned");
-  const size_t n2 = (size_t)N * (K / 2);
-  const int grid = (int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096);
-  hipLaunchKernelGGL(split_weight_fp16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K,
-                     static_cast<unsigned short*>(planes), 2);
-  FF_CHECK_LAUNCH();
-  return FF_OK;
+  return split_weight_launch("ff_split_weight_fp16x2", "planes", 2, W, ldw, N, K, planes, stream);
 }
 
 extern "C" size_t ff_split_weight_fp16_bytes(int N, int K) { return (size_t)N * K * sizeof(unsigned short); }
-
 extern "C" int ff_split_weight_fp16(const float* W, int ldw, int N, int K, void* plane, ff_stream_t stream) {
-  FF_CHECK_ARG(W && plane && N > 0 && K > 0 && (K & 15) == 0 && ldw >= K, "ff_split_weight_fp16: bad arguments (K %% 16)");
-  FF_CHECK_ARG(ff_aligned16(plane), "ff_split_weight_fp16: the plane must be 16-byte aligned");
-  const size_t n2 = (size_t)N * (K / 2);
-  const int grid = (int)((n2 + 255) / 256 < 4096 ? (n2 + 255) / 256 : 4096);
-  hipLaunchKernelGGL(split_weight_fp16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K,
-                     static_cast<unsigned short*>(plane), 1);
-  FF_CHECK_LAUNCH();
-  return FF_OK;
+  return split_weight_launch("ff_split_weight_fp16", "the plane", 1, W, ldw, N, K, plane, stream);
 }
 
 extern "C" int ff_x3_prepare_stream(hipStream_t st) {

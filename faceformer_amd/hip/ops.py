@@ -124,6 +124,29 @@ def linear(x, weight, bias=None, act=0, residual=None, x2=None, n_split=0, tile=
     return out
 
 
+def _ln_desc(x, lda, bias, act, residual, out, ldc, M, N, K, stats_in, eps, row_table, row_div, row_cols, want_stats):
+    """(d, stats, keep): the GemmLnDesc that linear_ln and linear_x3_ln share (everything but the weight), the statistics tensor it
+    fills (or None) and the tensors behind its raw pointers, which the caller keeps alive until the launch is enqueued."""
+    d = _L.GemmLnDesc()
+    d.A, d.lda, d.bias = _p(x), lda, _p(bias)
+    if residual is not None:
+        residual, ldr = _rows(residual, "residual")
+        d.residual, d.ldr = _p(residual), ldr
+    d.C, d.ldc, d.M, d.N, d.K, d.act = _p(out), ldc, M, N, K, act
+    if stats_in is not None:
+        _dev(stats_in, "stats_in")
+        stats_in = stats_in.contiguous()
+        d.ln_stats_in, d.ln_nseg, d.ln_eps = _p(stats_in), stats_in.size(1), eps
+    if row_table is not None:
+        row_table, ldt = _rows(row_table, "row_table")
+        d.row_table, d.ld_row_table, d.row_div, d.row_cols = _p(row_table), ldt, row_div, row_cols or row_table.size(1)
+    stats = None
+    if want_stats:
+        stats = torch.full((M, N // 32, 2), float("nan"), device=x.device, dtype=torch.float32)
+        d.ln_stats_out = _p(stats)
+    return d, stats, (residual, stats_in, row_table)   # (the contiguous copies made above: the caller holds them over the launch)
+
+
 @_on_tensor_device
 def linear_ln(x, weight, bias=None, act=0, residual=None, stats_in=None, eps=1e-5, row_table=None, row_div=1,
               row_cols=0, want_stats=False, tile=0, out=None):
@@ -137,24 +160,10 @@ def linear_ln(x, weight, bias=None, act=0, residual=None, stats_in=None, eps=1e-
     if out is None:
         out = torch.empty((M, N), device=x.device, dtype=torch.float32)
     out, ldc = _rows(out, "out")
-    d = _L.GemmLnDesc()
-    d.A, d.lda, d.W, d.ldw, d.bias = _p(x), lda, _p(weight), ldw, _p(bias)
-    if residual is not None:
-        residual, ldr = _rows(residual, "residual")
-        d.residual, d.ldr = _p(residual), ldr
-    d.C, d.ldc, d.M, d.N, d.K, d.act, d.tile = _p(out), ldc, M, N, K, act, tile
-    if stats_in is not None:
-        _dev(stats_in, "stats_in")
-        stats_in = stats_in.contiguous()
-        d.ln_stats_in, d.ln_nseg, d.ln_eps = _p(stats_in), stats_in.size(1), eps
-    if row_table is not None:
-        row_table, ldt = _rows(row_table, "row_table")
-        d.row_table, d.ld_row_table, d.row_div, d.row_cols = _p(row_table), ldt, row_div, row_cols or row_table.size(1)
-    stats = None
-    if want_stats:
-        stats = torch.full((M, N // 32, 2), float("nan"), device=x.device, dtype=torch.float32)
-        d.ln_stats_out = _p(stats)
+    d, stats, keep = _ln_desc(x, lda, bias, act, residual, out, ldc, M, N, K, stats_in, eps, row_table, row_div, row_cols, want_stats)
+    d.W, d.ldw, d.tile = _p(weight), ldw, tile
     _L.check(_L.load().ff_gemm_f32_ln(C.byref(d), _stream()), "ff_gemm_f32_ln")
+    del keep
     return (out, stats) if want_stats else out
 
 
@@ -175,28 +184,13 @@ def linear_x3_ln(x, planes, bias=None, act=0, residual=None, stats_in=None, eps=
     if out is None:
         out = torch.empty((M, N), device=x.device, dtype=torch.float32)
     out, ldc = _rows(out, "out")
-    d = _L.GemmLnDesc()
-    d.A, d.lda, d.bias = _p(x), lda, _p(bias)
-    if residual is not None:
-        residual, ldr = _rows(residual, "residual")
-        d.residual, d.ldr = _p(residual), ldr
-    d.C, d.ldc, d.M, d.N, d.K, d.act = _p(out), ldc, M, N, K, act
-    if stats_in is not None:
-        _dev(stats_in, "stats_in")
-        stats_in = stats_in.contiguous()
-        d.ln_stats_in, d.ln_nseg, d.ln_eps = _p(stats_in), stats_in.size(1), eps
-    if row_table is not None:
-        row_table, ldt = _rows(row_table, "row_table")
-        d.row_table, d.ld_row_table, d.row_div, d.row_cols = _p(row_table), ldt, row_div, row_cols or row_table.size(1)
-    stats = None
-    if want_stats:
-        stats = torch.full((M, N // 32, 2), float("nan"), device=x.device, dtype=torch.float32)
-        d.ln_stats_out = _p(stats)
+    d, stats, keep = _ln_desc(x, lda, bias, act, residual, out, ldc, M, N, K, stats_in, eps, row_table, row_div, row_cols, want_stats)
     if colsum is not None:
         _dev(colsum, "colsum")
     lib = _L.load()
     fn, who = _split_fn(planes, lib, "_ln")
     _L.check(fn(C.byref(d), planes.data_ptr(), plane_rows, row0, _p(colsum), _stream()), who)
+    del keep
     return (out, stats) if want_stats else out
 
 
@@ -410,6 +404,9 @@ def set_gemm_tuning(min_units=2, two_per_cu_units=2048, fix_tenths=25, small_max
 
 
 SPLIT_KINDS = {"bf16x3": 0, "fp16x2": 1, "fp16": 2}     # ff_model.split_kind ("fp16": one fp16 product, opt-in)
+_SPLIT_TABLE = {"bf16x3": (3, torch.bfloat16, "ff_split_weight_bf16x3"),     # kind: (terms, plane dtype, entry point)
+                "fp16x2": (2, torch.float16, "ff_split_weight_fp16x2"),
+                "fp16": (1, torch.float16, "ff_split_weight_fp16")}
 
 
 @_on_tensor_device
@@ -421,19 +418,11 @@ def split_weight(weight, kind="bf16x3"):
     N, K = weight.shape
     if K % 16:
         raise ValueError("split_weight: K must be a multiple of 16")
-    if kind == "fp16":
-        planes = torch.empty((1, K // 16, N, 16), device=weight.device, dtype=torch.float16)
-        _L.check(_L.load().ff_split_weight_fp16(_p(weight), ldw, N, K, planes.data_ptr(), _stream()), "ff_split_weight_fp16")
-        return planes
-    if kind == "fp16x2":
-        planes = torch.empty((2, K // 16, N, 16), device=weight.device, dtype=torch.float16)
-        _L.check(_L.load().ff_split_weight_fp16x2(_p(weight), ldw, N, K, planes.data_ptr(), _stream()), "ff_split_weight_fp16x2")
-        return planes
-    if kind != "bf16x3":
+    if kind not in _SPLIT_TABLE:
         raise ValueError("split_weight: kind must be one of %s" % sorted(SPLIT_KINDS))
-    planes = torch.empty((3, K // 16, N, 16), device=weight.device, dtype=torch.bfloat16)
-    _L.check(_L.load().ff_split_weight_bf16x3(_p(weight), ldw, N, K, planes.data_ptr(), _stream()),
-             "ff_split_weight_bf16x3")
+    terms, dtype, entry = _SPLIT_TABLE[kind]
+    planes = torch.empty((terms, K // 16, N, 16), device=weight.device, dtype=dtype)
+    _L.check(getattr(_L.load(), entry)(_p(weight), ldw, N, K, planes.data_ptr(), _stream()), entry)
     return planes
 
 
