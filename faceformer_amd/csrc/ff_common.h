@@ -116,9 +116,9 @@ struct ff_pointer_sync {
 };
 int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, int E, const unsigned char* mask,
                            const int* kv_len, const unsigned char* extra_mask, int ldextra, int B, int seqs_per_group,
-                           int* next_tok, float* best, float* second, float* logits, int ldlogits, float* next_rows,
-                           int ldnext, int* count_ge, int ge_bound, int* count_eq, int eq_value,
-                           const ff_pointer_sync* sync, ff_stream_t stream);
+                           int* next_tok, float* best, float* second, float* logprob, float* logits, int ldlogits,
+                           float* next_rows, int ldnext, int* count_ge, int ge_bound, int* count_eq, int eq_value,
+                           const ff_pointer_sync* sync, ff_stream_t stream);   // logprob: [B] or null (ff_pointer_argmax_lp)
 
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);

@@ -688,6 +688,9 @@ struct PointerArgs {
   // count_ge counts unfinished sequences only, and a token in [term_lo, term_hi) sets fin to fin_j (the position written).
   const int* slot;
   int* fin; int fin_j, term_lo, term_hi;
+  // Opt-in (null otherwise; last, so that every other member keeps its place): [B] log-probability of the selected key,
+  // log_softmax(masked logits)[next_tok], indexed like best / second.  A launch with it runs the LP = true kernels.
+  float* logprob;
 };
 __device__ __forceinline__ int ff_pointer_seq(const PointerArgs& a, int b) { return a.slot ? a.slot[b] : b; }
 
@@ -726,10 +729,27 @@ __device__ __forceinline__ void ff_pointer_count_block(const PointerArgs& a, int
   }
 }
 
+// (max, sum of exp(x - max)) of two disjoint key sets -> of their union; returns the sum, *mout the maximum
+__device__ __forceinline__ float ff_lse_merge(float m, float s, float om, float os, float* mout) {
+  const float d = om - m;                 // (both maxima are finite: -FLT_MAX at the least)
+  const float e = __expf(-fabsf(d));
+  *mout = d > 0.f ? om : m;
+  return d > 0.f ? s * e + os : s + os * e;
+}
+
 // `logits` holds the raw dot products of every (sequence, key); mask the row in place and reduce (value, index) pairs --
 // per lane over its strided keys, then across the 64 lanes with a butterfly that keeps torch's tie rule (lowest index)
 // and the runner-up value.
 // Returns the selected token (wave-uniform); the caller counts it (ff_pointer_count_block).
+//
+// LP (a.logprob != null; compiled out otherwise): the selection's log-probability, -log sum_s exp(l[s] - l[i*]).  The selected
+// logit is the row maximum, so every term is <= 1 and the largest is exactly 1: no cancellation, no overflow.  A lane keeps the
+// sum of its keys relative to its own running maximum b1 (one exp per key: the older sum is rescaled when the maximum moves),
+// the butterfly merges (maximum, sum) pairs in the rounds that merge (b1, b2, i1) -- a fixed tree, the same on every run.
+// Masked keys hold -FLT_MAX: exp(-FLT_MAX - max) = 0, and a row of masked keys only sums S ones (-log S, torch's value).
+// __expf (v_exp_f32 of x log2(e)): ~2 ulp on the terms near 1, which carry the sum; the argument's rounding grows with |x| as
+// the term vanishes.  One accurate logf per row.
+template <bool LP>
 __device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b, int lane) {
   const int w = b / a.spg;
   int kv = a.S;
@@ -741,19 +761,30 @@ __device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b
   const float FILL = -3.402823466e+38f;  // -FLT_MAX = torch.finfo(float32).min (reference utils.py:16-20)
   float b1 = -INFINITY, b2 = -INFINITY;
   int i1 = 0x7fffffff;
+  float lsum = 0.f;   // LP: sum of exp(v - b1) over the lane's keys so far
   for (int s = lane; s < a.S; s += 64) {
     bool ok = s < kv;
     if (ok && mrow) ok = ff_ldw(mrow + s) == 0;
     if (ok && erow) ok = ff_ldw(erow + s) == 0;
     const float v = ok ? ff_ld4(lrow + s) : FILL;
     ff_st4(lrow + s, v);
+    if (LP) {
+      const float d = v - b1;             // +inf at the lane's first key: e = 0, the sum starts at 1
+      const float e = __expf(-fabsf(d));
+      lsum = d > 0.f ? lsum * e + 1.f : lsum + e;
+    }
     if (v > b1) { b2 = b1; b1 = v; i1 = s; }
     else if (v > b2) b2 = v;
   }
+  float lmax = fmaxf(b1, FILL);   // LP: a lane without keys (S < 64) enters the merge as (-FLT_MAX, 0)
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float ob1 = __shfl_xor(b1, off, FF_WAVE), ob2 = __shfl_xor(b2, off, FF_WAVE);
     const int oi1 = __shfl_xor(i1, off, FF_WAVE);
+    if (LP) {
+      const float om = __shfl_xor(lmax, off, FF_WAVE), os = __shfl_xor(lsum, off, FF_WAVE);
+      lsum = ff_lse_merge(lmax, lsum, om, os, &lmax);
+    }
     const bool other = (ob1 > b1) || (ob1 == b1 && oi1 < i1);
     const float nb2 = other ? fmaxf(ob2, b1) : fmaxf(b2, ob1);
     if (other) { b1 = ob1; i1 = oi1; }
@@ -764,6 +795,7 @@ __device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b
     ff_st4i(a.next_tok + seq, i1);
     if (a.best) ff_st4(a.best + seq, b1);
     if (a.second) ff_st4(a.second + seq, b2);
+    if (LP) ff_st4(a.logprob + seq, -logf(lsum));
   }
   if (a.next_rows) {
     const float* src = a.memory + ((size_t)w * a.S + i1) * a.E;

@@ -90,10 +90,13 @@ __global__ void steps_kernel(const int* __restrict__ cnt_ge, const int* __restri
 // padding-anchor sequence stored at compact index num_input[w] (those rows are identical by construction:
 // same start token, same memory, same mask; reference model_para.py:204-205).  One launch per micro-batch:
 // it writes the rows whose compact sequence lives in [f0, f0 + Fc) of its wireframes.
+// logprob (optional, laid out like predict): lp_all[j - 1, seq], the log-probability of the token at position j >= 1, under the
+// same `last` rule; 0 in column 0 (the start token is not selected) and wherever predict is zero padded.
 __global__ void finalize_chunk_kernel(const int* __restrict__ tok_all, int Btot, int T, const int* __restrict__ steps_p,
                                       const int* __restrict__ num_input, int dedup, int F, int w0, int nw, int Fc,
                                       int f0, int b0, int64_t* __restrict__ predict, int* __restrict__ seq_of_row,
-                                      const int* __restrict__ fin) {
+                                      const int* __restrict__ fin, const float* __restrict__ lp_all = nullptr,
+                                      float* __restrict__ logprob = nullptr) {
   const int steps = *steps_p;
   const size_t total = (size_t)nw * F * T;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -106,6 +109,7 @@ __global__ void finalize_chunk_kernel(const int* __restrict__ tok_all, int Btot,
     const size_t row = (size_t)(w0 + wl) * F + fo;
     const int last = fin ? (fin[seq] < steps ? fin[seq] : steps) : steps;   // FF_RETIRE_FINISHED: up to the finish position
     predict[row * T + j] = (j <= last) ? (int64_t)tok_all[(size_t)j * Btot + seq] : (int64_t)0;
+    if (logprob) logprob[row * T + j] = (j >= 1 && j <= last) ? lp_all[(size_t)(j - 1) * Btot + seq] : 0.f;
     if (seq_of_row && j == 0) seq_of_row[row] = seq;
   }
 }
@@ -213,6 +217,7 @@ struct DecodeBuffers {
   float *projT, *pg_all, *pc_all;   // folded project + pointer GEMM of one-wireframe micro-batches (see pointer_fold): the transposed
                                     // folded project weight [E, E]; per micro-batch G = memory_w W' [S, E] and c = memory_w b' [S4]
   int* tok_all;   // [T, Btot] global, position-major
+  float* lp_all;  // [T-1, Btot] log-probability of the token every step selected (ff_decode_lp with a logprob output), or null
   Scratch scr[FF_MAX_STREAMS];
   int* zeroed; size_t zeroed_count;   // cnt_ge | cnt_eq | arrive | seen as ONE block of zeroed_count ints: one fill per decode
   int *cnt_ge, *cnt_eq;   // [T, nch] per (step, micro-batch)
@@ -331,8 +336,9 @@ bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
 }
 
 // Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
+// want_lp: also the log-probability rows (ff_decode_lp) -- taken LAST, so that everything else lies where it lies without them.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
-                     Bump& bp, DecodeBuffers* out) {
+                     Bump& bp, DecodeBuffers* out, bool want_lp = false) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
   const int ns = plan_streams(p);
   const size_t Rmax = (size_t)(T - 1 > 0 ? T - 1 : 1) * Bch;
@@ -381,6 +387,7 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     b.slot_all = bp.take<int>(Btot);
     b.perm_all = bp.take<int>(Btot);
   }
+  if (want_lp) b.lp_all = bp.take<float>((size_t)(T - 1 > 0 ? T - 1 : 1) * Btot);
   if (out) *out = b;
   return bp.off;
 }
@@ -624,6 +631,7 @@ struct DecodeIO {
   const float* memory; const unsigned char* mask; const int *kv_len, *num_input, *num_input_host; const unsigned char* extra_mask;
   int64_t* predict; int *steps_done, *step_counts; float *pointer_out, *trace_logits, *trace_best, *trace_second; int* seq_of_row;
   hipStream_t main_st;
+  float* logprob;   // [N*F, T] like predict, or null (ff_decode)
 };
 
 // FF_RETIRE_FINISHED slot order of a chunk of nw wireframes with `width` entries each, entry i live or finished: per wireframe
@@ -711,7 +719,7 @@ struct DecodeRun {
     plan_chunks(p, io.num_input_host, ns_req, &chunks, &Btot, &max_bc);
     nch = (int)chunks.size();
     Bump bp(workspace, workspace_bytes);
-    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf);
+    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr);
     if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
     for (Chunk& c : chunks) {
       c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
@@ -878,7 +886,9 @@ struct DecodeRun {
           folded_head ? nullptr : sc.p, E, io.memory + (size_t)c.w0 * S * E, S, E, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0,
           io.extra_mask ? io.extra_mask + (size_t)c.b0 * S : nullptr, S, c.Bl, c.Fl,
           buf.tok_all + (size_t)t * Btot + c.b0, io.trace_best ? io.trace_best + trow : nullptr,
-          io.trace_second ? io.trace_second + trow : nullptr, logits_dst, S,
+          io.trace_second ? io.trace_second + trow : nullptr,
+          buf.lp_all ? buf.lp_all + (size_t)step * Btot + c.b0 : nullptr,   // (indexed by sequence, as the tokens are)
+          logits_dst, S,
           c.x0 + (size_t)t * c.Bl * E, E, buf.cnt_ge + slot, m->num_token, buf.cnt_eq + slot, p->tok_eos,
           (each_eos || lagged || c.x0stat || folded_head || retire) ? &psync : nullptr, st));
       if (retire && io.trace_logits)
@@ -1033,7 +1043,7 @@ struct DecodeRun {
       const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
       hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
                          io.num_input, dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, io.predict, io.seq_of_row,
-                         retire ? fin_dev : nullptr);
+                         retire ? fin_dev : nullptr, buf.lp_all, io.logprob);
       FF_CHECK_LAUNCH();
     }
     int steps = 0;
@@ -1139,15 +1149,34 @@ extern "C" size_t ff_decode_workspace_bytes(const ff_model* m, const ff_decode_p
   return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr) + 256;
 }
 
+extern "C" size_t ff_decode_lp_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
+  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
+  int btot = 0, max_bc = 0, nch = 0;
+  plan_chunks(p, num_input_host, 1, nullptr, &btot, &max_bc, &nch);
+  Bump bp(nullptr, 0);
+  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, true) + 256;
+}
+
 extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const float* memory,
                          const unsigned char* mask, const int* kv_len, const int* num_input,
                          const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
                          int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
                          float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
                          size_t workspace_bytes, ff_stream_t stream) {
+  return ff_decode_lp(m, p, memory, mask, kv_len, num_input, num_input_host, extra_mask, predict, steps_done, step_counts,
+                      pointer_out, trace_logits, trace_best, trace_second, seq_of_row, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int ff_decode_lp(const ff_model* m, const ff_decode_params* p, const float* memory,
+                            const unsigned char* mask, const int* kv_len, const int* num_input,
+                            const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                            int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                            float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                            size_t workspace_bytes, float* logprob, ff_stream_t stream) {
   DecodeRun r;
   FF_RETURN_IF(r.validate(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, extra_mask, predict, steps_done, step_counts,
-                                         pointer_out, trace_logits, trace_best, trace_second, seq_of_row, (hipStream_t)stream}, workspace));
+                                         pointer_out, trace_logits, trace_best, trace_second, seq_of_row, (hipStream_t)stream, logprob},
+                          workspace));
   FF_RETURN_IF(r.bind_chunks(workspace, workspace_bytes));
   FF_RETURN_IF(ff_gemm_prepare_stream(r.io.main_st));
   std::mutex* busy = pool_busy_mutex();

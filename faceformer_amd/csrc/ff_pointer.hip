@@ -16,7 +16,9 @@ namespace {
 
 
 // one sequence by one wavefront; returns its token (wave-uniform)
-template <int NV>
+// LP (a.logprob != null; compiled out otherwise): -log sum_s exp(l[s] - max), as ff_pointer_reduce_row -- the logits are
+// wave-uniform here, so ONE running (best, sum) per wave, in key order.
+template <int NV, bool LP>
 __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane) {
   const int w = b / a.spg;
   const int nvec = a.E >> 2;
@@ -38,6 +40,7 @@ __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane
   float best = -INFINITY, second = -INFINITY;
   int best_idx = 0;
   float keep = FILL;  // logit owned by this lane in the current block of 64 keys (trace output)
+  float lsum = 0.f;   // LP: sum of exp(v - best) over the keys visited so far
 
   for (int s0 = 0; s0 < kv; s0 += 4) {
     float part[4];
@@ -73,6 +76,11 @@ __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane
       const int s = s0 + u;
       if (s >= kv) break;
       const float v = live[u] ? part[u] : FILL;
+      if (LP) {
+        const float d = v - best;           // +inf at the first key: e = 0, the sum starts at 1
+        const float e = __expf(-fabsf(d));
+        lsum = d > 0.f ? lsum * e + 1.f : lsum + e;
+      }
       if (v > best) { second = best; best = v; best_idx = s; }
       else if (v > second) { second = v; }
       if (a.logits) {
@@ -84,7 +92,9 @@ __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane
       }
     }
   }
-  // keys >= kv are masked: they matter only for the trace and for the runner-up value
+  // keys >= kv are masked: they matter only for the trace, for the runner-up value and -- when no key before them is live, so
+  // that the row maximum is the fill value itself -- as one term of 1 each in the log-probability's sum
+  if (LP && kv < a.S && !(best > FILL)) lsum += (float)(a.S - kv);
   if (kv < a.S) {
     if (FILL > best) { second = best; best = FILL; best_idx = kv; }
     else if (FILL > second) second = FILL;
@@ -103,6 +113,7 @@ __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane
     a.next_tok[seq] = best_idx;
     if (a.best) a.best[seq] = best;
     if (a.second) a.second[seq] = second;
+    if (LP) a.logprob[seq] = -logf(lsum);
   }
   if (a.next_rows) {
     const float* src = mem + (size_t)best_idx * a.E;
@@ -116,12 +127,12 @@ __device__ __forceinline__ int pointer_row(const PointerArgs& a, int b, int lane
   return best_idx;
 }
 
-template <int NV>
+template <int NV, bool LP>
 __global__ __launch_bounds__(256) void pointer_kernel(PointerArgs a) {
   __shared__ int s_tok[4];
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (b < a.B) s_tok[threadIdx.x >> 6] = pointer_row<NV>(a, b, lane);
+  if (b < a.B) s_tok[threadIdx.x >> 6] = pointer_row<NV, LP>(a, b, lane);
   __syncthreads();
   if (threadIdx.x == 0) {
     const int b0 = blockIdx.x * (blockDim.x >> 6);
@@ -130,11 +141,12 @@ __global__ __launch_bounds__(256) void pointer_kernel(PointerArgs a) {
 }
 
 // GEMM path, stage 2 (ff_pointer_reduce_row, ff_device.h): mask the raw logit row in place and reduce it.
+template <bool LP>
 __global__ __launch_bounds__(256) void pointer_reduce_kernel(PointerArgs a) {
   __shared__ int s_tok[4];
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (b < a.B) s_tok[threadIdx.x >> 6] = ff_pointer_reduce_row(a, b, lane);
+  if (b < a.B) s_tok[threadIdx.x >> 6] = ff_pointer_reduce_row<LP>(a, b, lane);
   __syncthreads();
   if (threadIdx.x == 0) {
     const int b0 = blockIdx.x * (blockDim.x >> 6);
@@ -152,15 +164,27 @@ extern "C" int ff_pointer_argmax(const float* p, int ldp, const float* memory, i
                                  int* count_ge, int ge_bound, int* count_eq, int eq_value,
                                  ff_stream_t stream) {
   return ff_pointer_argmax_sync(p, ldp, memory, S, E, mask, kv_len, extra_mask, ldextra, B, seqs_per_group, next_tok, best,
-                                second, logits, ldlogits, next_rows, ldnext, count_ge, ge_bound, count_eq, eq_value, nullptr,
-                                stream);
+                                second, nullptr, logits, ldlogits, next_rows, ldnext, count_ge, ge_bound, count_eq, eq_value,
+                                nullptr, stream);
+}
+
+extern "C" int ff_pointer_argmax_lp(const float* p, int ldp, const float* memory, int S, int E,
+                                    const unsigned char* mask, const int* kv_len,
+                                    const unsigned char* extra_mask, int ldextra, int B,
+                                    int seqs_per_group, int* next_tok, float* best, float* second,
+                                    float* logits, int ldlogits, float* next_rows, int ldnext,
+                                    int* count_ge, int ge_bound, int* count_eq, int eq_value,
+                                    float* logprob, ff_stream_t stream) {
+  return ff_pointer_argmax_sync(p, ldp, memory, S, E, mask, kv_len, extra_mask, ldextra, B, seqs_per_group, next_tok, best,
+                                second, logprob, logits, ldlogits, next_rows, ldnext, count_ge, ge_bound, count_eq, eq_value,
+                                nullptr, stream);
 }
 
 // The same operator with the decode engine's counter hand-over (ff_common.h: ff_pointer_sync); not part of the C ABI.
 int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, int E, const unsigned char* mask,
                            const int* kv_len, const unsigned char* extra_mask, int ldextra, int B, int seqs_per_group,
-                           int* next_tok, float* best, float* second, float* logits, int ldlogits, float* next_rows,
-                           int ldnext, int* count_ge, int ge_bound, int* count_eq, int eq_value,
+                           int* next_tok, float* best, float* second, float* logprob, float* logits, int ldlogits,
+                           float* next_rows, int ldnext, int* count_ge, int ge_bound, int* count_eq, int eq_value,
                            const ff_pointer_sync* sync, ff_stream_t stream) {
   if (B == 0) return FF_OK;
   FF_CHECK_ARG(B > 0 && S > 0 && E > 0 && (E & 3) == 0 && E <= 2048 && seqs_per_group > 0,
@@ -181,7 +205,7 @@ int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, 
                 sync ? sync->seen : nullptr, sync ? sync->arrive : nullptr, sync ? sync->host_slot : nullptr,
                 sync ? sync->host_which : 0, sync ? sync->next_stats : nullptr,
                 sync ? sync->slot : nullptr, sync ? sync->fin : nullptr, sync ? sync->fin_j : 0,
-                sync ? sync->term_lo : 0, sync ? sync->term_hi : 0};
+                sync ? sync->term_lo : 0, sync ? sync->term_hi : 0, logprob};
   FF_CHECK_ARG(!a.arrive || (a.host_slot && (a.host_which ? count_eq : count_ge)), "ff_pointer_argmax: counter hand-over without a counter");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ff_cdiv(B, 4)), block(256);
@@ -193,16 +217,23 @@ int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, 
                                        (long long)seqs_per_group * ldp, (long long)S * E,
                                        (long long)seqs_per_group * ldlogits, stream));
     FFProfScope prof(FF_CAT_POINTER, (double)B * S * 8.0, st);
-    hipLaunchKernelGGL(pointer_reduce_kernel, grid, block, 0, st, a);
+    // (the log-probability is a compile-time form of the kernels: a launch without it runs the code it ran before the option)
+    if (logprob) hipLaunchKernelGGL(pointer_reduce_kernel<true>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(pointer_reduce_kernel<false>, grid, block, 0, st, a);
     FF_CHECK_LAUNCH();
     return FF_OK;
   }
   FFProfScope prof(FF_CAT_POINTER, 2.0 * B * (double)S * E, st);
   const int nv = ff_cdiv(E / 4, 64);
-  if (nv <= 1) hipLaunchKernelGGL(pointer_kernel<1>, grid, block, 0, st, a);
-  else if (nv <= 2) hipLaunchKernelGGL(pointer_kernel<2>, grid, block, 0, st, a);
-  else if (nv <= 4) hipLaunchKernelGGL(pointer_kernel<4>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(pointer_kernel<8>, grid, block, 0, st, a);
+  if (logprob) {
+    if (nv <= 1) hipLaunchKernelGGL((pointer_kernel<1, true>), grid, block, 0, st, a);
+    else if (nv <= 2) hipLaunchKernelGGL((pointer_kernel<2, true>), grid, block, 0, st, a);
+    else if (nv <= 4) hipLaunchKernelGGL((pointer_kernel<4, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((pointer_kernel<8, true>), grid, block, 0, st, a);
+  } else if (nv <= 1) hipLaunchKernelGGL((pointer_kernel<1, false>), grid, block, 0, st, a);
+  else if (nv <= 2) hipLaunchKernelGGL((pointer_kernel<2, false>), grid, block, 0, st, a);
+  else if (nv <= 4) hipLaunchKernelGGL((pointer_kernel<4, false>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((pointer_kernel<8, false>), grid, block, 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }

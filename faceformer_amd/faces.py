@@ -22,7 +22,8 @@ import numpy as np
 
 __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_with_majority_type", "face_metrics",
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
-           "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record"]
+           "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
+           "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores"]
 
 
 def _tok(token, name, default):
@@ -172,6 +173,96 @@ def face_metrics(predict_faces, label_faces):
         prec, rec = face_tp / len(pred_set), face_tp / len(label_set)
         tacc = type_tp / face_tp if face_tp else 0
     return {"precision": prec, "recall": rec, "type_acc": tacc, "predictions": pred_set, "labels": label_set}
+
+
+# ---- scored faces: the decode's log-probabilities (models' return_logprob) summed per face -------------------------------------
+# New functions beside the unscored ones, which stay as they are: the same rows, filters, grouping and order, plus a score.
+# logprobs are laid out like the tokens: entry j is log_softmax(masked logits)[token j], 0 at the start token and in the padding.
+def parse_parallel_faces_scored(predicts, logprobs, num_edges, token):
+    """parse_parallel_faces' predicted faces with a score each: [(type, (edge, ...), score)], the rows and filters of
+    `_parallel_rows`.  score = sum of the row's log-probabilities over positions 1 .. fin, fin the position of the first
+    face-type token (the terminator included; the start token at position 0 is given, not selected)."""
+    off, ntok = _tok(token, "face_type_offset", 1), _tok(token, "len", 4)
+    faces = []
+    for row, lp in zip(np.asarray(predicts), np.asarray(logprobs, dtype=np.float64)):
+        row = np.asarray(row, dtype=np.int64)
+        seq = _prefix_through_first(row, (row >= off) & (row < ntok))
+        if seq.size == 0:
+            continue
+        idx = _edge_indices(seq, ntok, num_edges)
+        if idx:
+            faces.append((int(seq[-1]) - off, idx, float(lp[1: seq.size].sum())))
+    return faces
+
+
+def parse_faces_scored(predicts, logprobs, num_edges, token):
+    """parse_faces' predicted faces with a score each: [(0, (edge, ...), score)], the pieces and filters of `_seq_faces`.
+    score = sum of the log-probabilities over the face's piece, its SEP / EOS included (SOS, in the first piece, carries 0)."""
+    eos, sep, ntok = _tok(token, "EOS", 3), _tok(token, "SEP", 2), _tok(token, "len", 4)
+    seq = np.asarray(predicts, dtype=np.int64)
+    seq = _prefix_through_first(seq, seq == eos)
+    lp = np.asarray(logprobs, dtype=np.float64)[: seq.size]
+    cuts = np.flatnonzero(seq == sep) + 1
+    faces = []
+    for piece, plp in zip(np.split(seq, cuts), np.split(lp, cuts)):
+        if piece.size <= 1:
+            continue
+        idx = _edge_indices(piece[:-1], ntok, num_edges)
+        if idx:
+            faces.append((0, idx, float(plp.sum())))
+    return faces
+
+
+def unique_faces_with_scores(faces):
+    """unique_faces_with_majority_type over scored faces [(type, edges, score)]: the same grouping (by the SET of edge indices)
+    and first-seen order.  Returns [(majority type, sorted_unique_edges, best score, votes)]: the highest score and the number
+    of the faces that share the edge set."""
+    groups = {}
+    for ftype, idx, score in faces:
+        groups.setdefault(tuple(sorted(set(idx))), []).append((ftype, score))
+    return [(Counter(t for t, _ in g).most_common(1)[0][0], key, max(s for _, s in g), len(g)) for key, g in groups.items()]
+
+
+# Two private helpers of the scored paths (the CLI's --scores, the parallel model's return_logprob).  They restate the rules of
+# retired_view / apply_own_stop_rule for a second array, because those functions return tokens only and stay as they are here;
+# tests/test_logprob.py pins each pair against the other.  Follow-up: derive retired_view / apply_own_stop_rule from these.
+def _retired_keep(predict, token):
+    """Boolean array of predict's shape: True where retired_view keeps predict's entry, False where it writes its zero padding
+    (tokens cannot tell: 0 is a token too).  retired_view(p) == np.where(_retired_keep(p), p, 0)."""
+    p = np.asarray(predict, dtype=np.int64)
+    rows = p.reshape(-1, p.shape[-1])
+    T = rows.shape[1]
+    off, ntok = _tok(token, "face_type_offset", 1), _tok(token, "len", 4)
+    term = (rows >= off) & (rows < ntok)
+    fin = np.where(term.any(axis=1), term.argmax(axis=1), T)
+    steps = T - 1
+    for j in range(1, T):
+        if not ((rows[:, j] >= ntok) & (fin >= j)).any():
+            steps = j
+            break
+    return (np.arange(T)[None, :] <= np.minimum(fin, steps)[:, None]).reshape(p.shape)
+
+
+def _apply_own_stop_rule_scored(predict, logprob, token, parallel, eos=None):
+    """apply_own_stop_rule on the tokens, and the log-probabilities zeroed at the positions it cuts off.  Returns copies
+    (tokens, logprobs)."""
+    p = np.array(predict, dtype=np.int64, copy=True)
+    lp = np.array(logprob, dtype=np.float64, copy=True)
+    ntok = _tok(token, "len", 4)
+    if parallel:
+        rows, lrows = p.reshape(-1, p.shape[-1]), lp.reshape(-1, p.shape[-1])
+        for j in range(1, rows.shape[1]):
+            if (rows[:, j] < ntok).all():
+                rows[:, j + 1:] = 0
+                lrows[:, j + 1:] = 0
+                break
+        return rows.reshape(p.shape), lrows.reshape(p.shape)
+    e = _tok(token, "EOS", 3) if eos is None else eos
+    hit = np.nonzero(p[1:] == e)[0]
+    if hit.size:
+        p[hit[0] + 2:] = 0
+        lp[hit[0] + 2:] = 0
+    return p, lp
 
 
 # ---- geometric post-processing (co-edge configs) ---------------------------------------------------

@@ -338,9 +338,13 @@ class PathEngine:
                chunk_wireframes=0, chunk_seqs=0, num_streams=1, sync_every=4, flags=DEFAULT_FLAGS,
                tok_sos=1, tok_eos=3, x3_min_rows=0, chunk_max_seqs=0, ln_fuse_max_rows=0,
                trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
-               retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK):
+               retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
-        tensors indexed like predict's rows], slots_per_step, slot_rows).
+        tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).
+
+        logprob=True (ff_decode_lp): also `logprob` [N*F, T] fp32, laid out like predict -- column j >= 1 is
+        log_softmax(masked logits of step j-1)[predict[:, j]], 0 in column 0 and wherever predict is zero padded.  Tokens, steps
+        and traces are those of the call without it.
 
         retire=True (parallel variant, FF_RETIRE_FINISHED): a sequence is finished from the first position holding a token in
         term_range = (lo, hi); the stop rule looks at unfinished sequences only, `predict` is zero after min(finish position,
@@ -400,7 +404,9 @@ class PathEngine:
             tb = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
             ts = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
         rows = torch.empty(B, device=dev, dtype=torch.int32)
-        nbytes = self._lib.ff_decode_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host)
+        lp = torch.empty((B, T), device=dev, dtype=torch.float32) if logprob else None
+        ws_bytes = self._lib.ff_decode_lp_workspace_bytes if logprob else self._lib.ff_decode_workspace_bytes
+        nbytes = ws_bytes(C.byref(self.model), C.byref(prm), ni_host)
         ws = self._workspace(nbytes)
         cb_error, cb = [], None
         if stop_callback is not None and not no_stop:
@@ -418,11 +424,14 @@ class PathEngine:
         counts = (C.c_int * max(T - 1, 1))()
         slots = (C.c_int * max(T - 1, 1))()
         prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
-        with torch.cuda.device(dev):
-            _L.check(self._lib.ff_decode(
-                C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), _p(ni), ni_host,
+        args = (C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), _p(ni), ni_host,
                 _p(extra_mask), _p(predict), C.byref(steps), counts, _p(pointer), _p(tl), _p(tb), _p(ts),
-                _p(rows), _p(ws), ws.numel(), _stream()), "ff_decode")
+                _p(rows), _p(ws), ws.numel())
+        with torch.cuda.device(dev):
+            if logprob:
+                _L.check(self._lib.ff_decode_lp(*args, _p(lp), _stream()), "ff_decode_lp")
+            else:
+                _L.check(self._lib.ff_decode(*args, _stream()), "ff_decode")
         if cb_error:
             raise cb_error[0]
         sps = [int(v) for v in slots]
@@ -430,6 +439,8 @@ class PathEngine:
                "seq_of_row": rows, "slots_per_step": sps, "slot_rows": sum((s + 1) * v for s, v in enumerate(sps))}
         if return_pointer:
             out["pointer"] = pointer[: steps.value]
+        if logprob:
+            out["logprob"] = lp
         if trace:
             # the C side indexes its traces by DECODED sequence (padding-anchor rows share one); expand to
             # one entry per row of `predict`

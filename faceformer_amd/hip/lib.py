@@ -185,6 +185,9 @@ SIGNATURES = {
     "ff_pointer_argmax": (C.c_int, [fptr, C.c_int, fptr, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int,
                                     C.c_int, C.c_int, fptr, fptr, fptr, fptr, C.c_int, fptr, C.c_int,
                                     fptr, C.c_int, fptr, C.c_int, fptr]),
+    "ff_pointer_argmax_lp": (C.c_int, [fptr, C.c_int, fptr, C.c_int, C.c_int, fptr, fptr, fptr, C.c_int,
+                                       C.c_int, C.c_int, fptr, fptr, fptr, fptr, C.c_int, fptr, C.c_int,
+                                       fptr, C.c_int, fptr, C.c_int, fptr, fptr]),
     "ff_permute_rows": (C.c_int, [fptr, C.c_int, fptr, fptr, C.c_int, fptr, C.c_int, C.c_int, C.c_int, fptr]),
     "ff_gather_rows": (C.c_int, [fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, fptr, C.c_int, fptr]),
     "ff_assemble_embedding": (C.c_int, [fptr, C.c_int, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr,
@@ -198,6 +201,11 @@ SIGNATURES = {
                             C.POINTER(C.c_int), fptr,
                             fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                             C.c_size_t, fptr]),
+    "ff_decode_lp_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int)]),
+    "ff_decode_lp": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                               C.POINTER(C.c_int), fptr,
+                               fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                               C.c_size_t, fptr, fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 
@@ -229,7 +237,9 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            raise HipExtensionError("%s does not export %s (stale build?)" % (LIB_PATH, name))
+            # (entries are also added WITHIN an ABI version -- the *_lp ones of 105 -- so the version check below cannot stand in)
+            raise HipExtensionError("%s does not export %s (stale build): rebuild it "
+                                    "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res
         fn.argtypes = args
     if lib.ff_version() != FF_ABI_VERSION:   # a stale .so would read the ctypes structs above with another layout

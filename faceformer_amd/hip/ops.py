@@ -318,8 +318,9 @@ def attention_general(q, k, v, num_groups, num_heads, head_dim, nq, nk, q_group_
 
 @_on_tensor_device
 def pointer_argmax(p, memory, mask=None, kv_len=None, extra_mask=None, seqs_per_group=1,
-                   want_logits=False, want_rows=False, counters=None, ge_bound=0, eq_value=0):
-    """select_next: returns dict(next, best, second, [logits], [rows])."""
+                   want_logits=False, want_rows=False, counters=None, ge_bound=0, eq_value=0, want_logprob=False):
+    """select_next: returns dict(next, best, second, [logits], [rows], [logprob]).
+    want_logprob: also log_softmax(masked logits)[next] per sequence (ff_pointer_argmax_lp); the other outputs do not change."""
     p, ldp = _rows(p, "p")
     _dev(memory, "memory")
     if memory.dim() != 3 or not memory.is_contiguous():
@@ -344,11 +345,15 @@ def pointer_argmax(p, memory, mask=None, kv_len=None, extra_mask=None, seqs_per_
     if counters is not None:
         _dev(counters, "counters", torch.int32)
         cge, ceq = counters.data_ptr(), counters.data_ptr() + 4
-    _L.check(_L.load().ff_pointer_argmax(
-        _p(p), ldp, _p(memory), S, E, _p(mask), _p(kv_len), _p(extra_mask), ldextra, B,
-        seqs_per_group, _p(nxt), _p(best), _p(second), _p(logits), S, _p(rows), E,
-        cge, ge_bound, ceq, eq_value, _stream()), "ff_pointer_argmax")
+    args = (_p(p), ldp, _p(memory), S, E, _p(mask), _p(kv_len), _p(extra_mask), ldextra, B,
+            seqs_per_group, _p(nxt), _p(best), _p(second), _p(logits), S, _p(rows), E,
+            cge, ge_bound, ceq, eq_value)
     out = {"next": nxt, "best": best, "second": second}
+    if want_logprob:
+        out["logprob"] = torch.empty(B, device=dev, dtype=torch.float32)
+        _L.check(_L.load().ff_pointer_argmax_lp(*args, _p(out["logprob"]), _stream()), "ff_pointer_argmax_lp")
+    else:
+        _L.check(_L.load().ff_pointer_argmax(*args, _stream()), "ff_pointer_argmax")
     if want_logits:
         out["logits"] = logits
     if want_rows:

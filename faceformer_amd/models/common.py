@@ -62,6 +62,9 @@ class SurfaceFormerBase(nn.Module):
         self.retire_finished = False   # parallel model: a face loop stops being decoded once it has produced its face-type token;
                                        # `predict` is then faces.retired_view of the reference's (same faces: DESIGN.md 10).
                                        # Not with dist.decode_sharded or the single-sequence model (ValueError)
+        self.return_logprob = False    # forward_eval also returns inputs["predict_logprob"], shaped like inputs["predict"]: the
+                                       # log-probability log_softmax(masked logits)[token] of every greedy selection, 0 at the
+                                       # start token and wherever predict is zero padded.  Not with dist.decode_sharded
         # Decoder projections of launches with at least this many rows (q|k|v; linear1 from 7/4 x, the 512-column ones from
         # 11/4 x as many) run as 3 x bf16 split products on the bf16 matrix cores: fp32-accurate (error vs fp64 = an fp32 dot
         # product's, tests/test_hip_ops.py), LayerNorm folding included (ff_gemm_x3_ln), and 1.3-1.6x the f32-MFMA kernel
@@ -170,6 +173,8 @@ class SurfaceFormerBase(nn.Module):
         extra = self._extra_mask(inputs)
         eos_seen, pointer = 0, None
         trace = getattr(self, "_module_trace", None)        # tests: a list that receives the masked logits of every step
+        want_lp = bool(getattr(self, "return_logprob", False))
+        lps = [torch.zeros(tokens.size(1), device=inp.device)] if want_lp else []   # position 0: the start token is not selected
         if trace is not None:
             self._module_memory = mem_rows
         for step in range(T - 1):
@@ -177,8 +182,10 @@ class SurfaceFormerBase(nn.Module):
             pointer = self.project(self.decoder(tgt, mem_seq, memory_key_padding_mask=mask_seq, pos=pos,
                                                 query_pos=qpos[: step + 1]))
             res = ops.pointer_argmax(pointer[-1].contiguous(), mem_rows, mask=mask_u8, extra_mask=extra,
-                                     seqs_per_group=F, want_logits=trace is not None)
+                                     seqs_per_group=F, want_logits=trace is not None, want_logprob=want_lp)
             nxt = res["next"].to(torch.long).unsqueeze(0)
+            if want_lp:
+                lps.append(res["logprob"])
             if trace is not None:
                 trace.append(res["logits"])
             tokens = torch.cat((tokens, nxt), dim=0)
@@ -191,6 +198,9 @@ class SurfaceFormerBase(nn.Module):
                     break
         pad = torch.zeros((T - tokens.size(0), tokens.size(1)), dtype=torch.long, device=inp.device)
         predict = torch.cat((tokens, pad), dim=0).transpose(0, 1)
+        if want_lp:
+            lp = torch.cat((torch.stack(lps), pad.to(torch.float32)), dim=0).transpose(0, 1)
+            inputs["predict_logprob"] = lp.reshape(N, F, T) if parallel else lp.contiguous()
         if parallel:
             inputs["predict"] = predict.reshape(N, F, T)
         else:

@@ -48,20 +48,25 @@ class SurfaceFormer(SurfaceFormerBase):
             inputs["embedding"] = torch.zeros((0, S, self.num_model), device=dev)
             inputs["pointer"] = torch.zeros((0, 1, self.num_model), device=dev)
             inputs["predict"] = torch.zeros((0, T), dtype=torch.long, device=dev)
+            if getattr(self, "return_logprob", False):
+                inputs["predict_logprob"] = torch.zeros((0, T), device=dev)
             return inputs
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             return self._forward_eval_modules(inputs, parallel=False)
         if label.size(1) < T - 1:
             raise ValueError("label has %d positions but label_seq_length-1=%d query positions are "
                              "needed" % (label.size(1), T - 1))
+        want_lp = bool(getattr(self, "return_logprob", False))
         eng, memory, mask, kv_len = self._encode(inputs)
         out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1,
                          flags=self.decode_flags | (_L.FF_STOP_EACH_EOS if self.stop_each_eos else 0),
                          x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS, tok_eos=self.token.EOS,
-                         return_pointer=True, extra_mask=self._extra_mask(inputs))
+                         return_pointer=True, extra_mask=self._extra_mask(inputs), logprob=want_lp)
         inputs["embedding"] = memory
         inputs["pointer"] = out["pointer"].transpose(0, 1)
         inputs["predict"] = out["predict"]
+        if want_lp:
+            inputs["predict_logprob"] = out["logprob"]
         return inputs

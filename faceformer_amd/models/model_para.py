@@ -41,8 +41,11 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             inputs = self._forward_eval_modules(inputs, parallel=True)
             if self.retire_finished:         # (that loop decodes every sequence; the result is the same function of its tokens)
-                inputs["predict"] = torch.as_tensor(_faces.retired_view(inputs["predict"].cpu().numpy(), self.token),
-                                                    device=inputs["predict"].device)
+                full = inputs["predict"].cpu().numpy()
+                inputs["predict"] = torch.as_tensor(_faces.retired_view(full, self.token), device=inputs["predict"].device)
+                if "predict_logprob" in inputs:
+                    keep = torch.as_tensor(_faces._retired_keep(full, self.token), device=inputs["predict"].device)
+                    inputs["predict_logprob"] = inputs["predict_logprob"] * keep
             return inputs
         if label.size(2) < T - 1:
             raise ValueError("label has %d positions but max_face_length-1=%d query positions are "
@@ -55,6 +58,7 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         if N != inputs["input"].size(0):
             raise ValueError("num_input has %d entries for a batch of %d" % (N, inputs["input"].size(0)))
         extra = self._extra_mask(inputs)
+        want_lp = bool(getattr(self, "return_logprob", False))
         # Ragged batch: decode the wireframes sorted by edge count so that a micro-batch holds wireframes of
         # (nearly) the same width; wireframes are independent, the result rows are put back in batch order.
         order = None
@@ -76,13 +80,18 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
                          chunk_max_seqs=self.chunk_max_seqs,
                          num_streams=self.num_streams, sync_every=self.sync_every,
                          flags=self.decode_flags, x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, extra_mask=extra,
-                         retire=self.retire_finished, term_range=(int(self.token.face_type_offset), int(self.token.len)))
+                         retire=self.retire_finished, term_range=(int(self.token.face_type_offset), int(self.token.len)),
+                         logprob=want_lp)
         pred = out["predict"].view(N, F, T)
+        lp = out["logprob"].view(N, F, T) if want_lp else None
         if order is not None:
             inv = torch.empty(N, dtype=torch.long, device=pred.device)
             inv[torch.tensor(order, device=pred.device)] = torch.arange(N, device=pred.device)
             pred = pred.index_select(0, inv)
+            lp = lp.index_select(0, inv) if want_lp else None
         inputs["predict"] = pred
+        if want_lp:
+            inputs["predict_logprob"] = lp
         self.last_decode_stats = {"decoded_seqs": sum(min(F, n + 1) for n in num_input), "rows": N * F,
                                   "slot_rows": out["slot_rows"], "steps": out["steps"]}
         return inputs

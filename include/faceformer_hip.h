@@ -376,6 +376,23 @@ int ff_pointer_argmax(const float* p, int ldp, const float* memory, int S, int E
                       float* next_rows, int ldnext,
                       int* count_ge, int ge_bound, int* count_eq, int eq_value,
                       ff_stream_t stream);
+/* ff_pointer_argmax plus the log-probability of the selection (opt-in; entry added within ABI 105, nothing else changed):
+ *   logprob [B] (NULL: exactly ff_pointer_argmax, which forwards here with NULL)
+ *     = log_softmax(masked logits of b)[next_tok[b]] = -log sum_s exp(logit[b,s] - logit[b,next_tok[b]])
+ * i.e. torch.log_softmax over the row select_next takes its argmax of (reference model_para.py:173-179, model.py:161-167),
+ * masked entries at finfo.min as it leaves them: they contribute exp(finfo.min - max) = 0, and a row whose keys are ALL masked
+ * gives -log S (torch's value for an all-equal row).  Evaluated in the second form -- the selected logit is the row maximum, so
+ * the largest term is exactly 1: no cancellation, no overflow at any logit scale; always <= 0.  Both code paths; the sum is
+ * merged in a fixed order (the same value on every run).  next_tok, best, second and logits are bit-identical with and without
+ * it: the logits are read, never changed. */
+int ff_pointer_argmax_lp(const float* p, int ldp, const float* memory, int S, int E,
+                         const unsigned char* mask, const int* kv_len,
+                         const unsigned char* extra_mask, int ldextra,
+                         int B, int seqs_per_group,
+                         int* next_tok, float* best, float* second, float* logits, int ldlogits,
+                         float* next_rows, int ldnext,
+                         int* count_ge, int ge_bound, int* count_eq, int eq_value,
+                         float* logprob, ff_stream_t stream);
 
 /* out[b,:] = memory[(b / seqs_per_group), tok[b], :]   (first decoder input: anchors / SOS;
  * reference model_para.py:217-219 at step 0). */
@@ -577,6 +594,24 @@ int ff_decode(const ff_model* m, const ff_decode_params* p,
               int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
               float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
               void* workspace, size_t workspace_bytes, ff_stream_t stream);
+/* ff_decode plus the log-probabilities of the greedy selections (opt-in; entries added within ABI 105; ff_decode forwards here
+ * with NULL, and with NULL the workspace layout is ff_decode's byte for byte):
+ *   logprob [N*F, T] fp32, laid out like predict: column 0 is 0 (the start token is not selected); column j >= 1 is
+ *     log_softmax(masked logits of step j-1)[predict[:, j]] -- the value ff_pointer_argmax_lp defines, over the row select_next
+ *     takes its argmax of (reference model_para.py:173-179, model.py:161-167) -- and 0 wherever predict is zero padded: after
+ *     the stop step, and with FF_RETIRE_FINISHED after min(finish position, stop step).  With FF_NO_STOP / a stop_fn every
+ *     executed step is kept, as for predict.  Padding-anchor rows under FF_DEDUP_PAD_ANCHORS carry the shared sequence's values,
+ *     as they carry its tokens.  Every step's pointer launch writes its own row of a [T-1, sequences] workspace array: no extra
+ *     launch per step, no host traffic.
+ * ff_decode_lp_workspace_bytes: the workspace ff_decode_lp needs when logprob is given (ff_decode_workspace_bytes plus that
+ * array); same arguments and rules as ff_decode_workspace_bytes. */
+size_t ff_decode_lp_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host);
+int ff_decode_lp(const ff_model* m, const ff_decode_params* p,
+                 const float* memory, const unsigned char* mask, const int* kv_len,
+                 const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                 int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                 float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                 void* workspace, size_t workspace_bytes, float* logprob, ff_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -46,45 +46,76 @@ def decode_batch(model, batch):
         return model(batch)["predict"].cpu().numpy()
 
 
-def record_of(cfg, raw, item, pred, parallel):
-    """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300)."""
+def decode_batch_scored(model, batch):
+    """(`predict`, `predict_logprob`) of `model(batch)` as numpy arrays (--scores: the model's return_logprob is set)."""
+    with torch.no_grad():
+        out = model(batch)
+    return out["predict"].cpu().numpy(), out["predict_logprob"].cpu().numpy()
+
+
+def record_of(cfg, raw, item, pred, parallel, logprob=None):
+    """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
+    logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
+    de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored)."""
+    scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
         # the wireframe's OWN anchor sequences: in a batch `predict` is padded to F = max(num_input) rows per wireframe with
         # padding-anchor sequences (reference model_para.py:204-205), which the reference's one-sample test batches never contain
-        pred = pred[: int(item["num_input"])]
+        n = int(item["num_input"])
+        pred, logprob = pred[:n], (logprob[:n] if scored else None)
     # ... and their tokens up to the wireframe's OWN stop step (in a batch the loop runs on until every wireframe is done)
-    pred = FZ.apply_own_stop_rule(pred, cfg.model.token, parallel)
+    if scored:
+        pred, logprob = FZ._apply_own_stop_rule_scored(pred, logprob, cfg.model.token, parallel)
+    else:
+        pred = FZ.apply_own_stop_rule(pred, cfg.model.token, parallel)
     pf, lf = parse(pred, item["label"], len(raw["edges"]), cfg.model.token)
+    sf = None
+    if scored:      # the same faces in the same order, with a score each
+        sf = (FZ.parse_parallel_faces_scored if parallel else FZ.parse_faces_scored)(pred, logprob, len(raw["edges"]), cfg.model.token)
     if cfg.post_process.is_coedge:
         pairings = raw.get("pairings", {})
         tol = cfg.post_process.enclosedness_tol
         pf = FZ.postprocess_faces(pf, raw["edges"], pairings, tol)
         lf = FZ.postprocess_faces(lf, raw["edges"], pairings, tol)
+        if scored:  # the filters work face by face, so a face keeps its score or leaves with it (checked against pf below)
+            sf = [(t, idx, s) for ftype, face, s in sf
+                  for t, idx in FZ.postprocess_faces([(ftype, face)], raw["edges"], pairings, tol)]
+    if scored and [(t, idx) for t, idx, _ in sf] != pf:
+        raise RuntimeError("--scores: the scored faces are not the record's faces (a post-processing step is no longer face by face?)")
     m = FZ.face_metrics(pf, lf)
     rec = FZ.faces_record(raw["edges"], raw.get("dominant_directions", []), m["predictions"], m["labels"])
+    if scored:      # (unique_faces_with_scores groups like unique_faces_with_majority_type: parallel to m["predictions"])
+        rec["pred_face_scores"] = [s for _, _, s, _ in FZ.unique_faces_with_scores(sf)]
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
-def configure_model(model, retire_finished=False, fp16=False):
-    """The CLI's decode options on a built model: retirement of finished face loops, and the opt-in one-fp16-product
-    projections and cross-attention (split_kind "fp16").  Without them the model keeps its defaults."""
+def configure_model(model, retire_finished=False, fp16=False, scores=False):
+    """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
+    projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
+    (return_logprob).  Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
     if fp16:
         model.split_kind = "fp16"
+    if scores:
+        model.return_logprob = True
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
-             retire_finished=False, fp16=False):
+             retire_finished=False, fp16=False, scores=False):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
     retire_finished: the parallel model stops decoding a face loop once it has ended (models/common.py retire_finished).
-    fp16: the decoder's large projections and its cross-attention take one fp16 product each (split_kind "fp16")."""
+    fp16: the decoder's large projections and its cross-attention take one fp16 product each (split_kind "fp16").
+    scores: every record gains `pred_face_scores` (record_of); single-process runs only."""
     if retire_finished and cfg.model_class != "SurfaceFormer_Parallel":
         raise ValueError("--retire-finished applies to SurfaceFormer_Parallel only")
+    if scores and dist_mod is not None and dist_mod.get_world_size() > 1:
+        raise ValueError("--scores (return_logprob) is not implemented for multi-rank runs: the log-probabilities are not "
+                         "gathered across ranks")
     model_class = getattr(models, cfg.model_class)
     dataset_class = getattr(D, cfg.dataset_class)
     if model is None:
@@ -92,7 +123,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         sd, _ = load_lightning_checkpoint(ckpt_path)
         model.load_state_dict(sd)
         model = model.eval().to(device)
-    configure_model(model, retire_finished, fp16)
+    configure_model(model, retire_finished, fp16, scores)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -113,11 +144,11 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         if torch.cuda.is_available() and str(device).startswith("cuda"):
             torch.cuda.synchronize()
         t0 = time.time()
-        pred = decode_batch(model, batch)
+        pred, lps = decode_batch_scored(model, batch) if scores else (decode_batch(model, batch), None)
         total += time.time() - t0
         done += len(idx)
         for k, i in enumerate(idx):
-            text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel)
+            text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel, lps[k] if scores else None)
             stats.append(st)
             records.append((os.path.splitext(os.path.basename(items[k]["name"]))[0], text))
         print("Avg Time", total / done, "seconds.")
@@ -155,6 +186,9 @@ def build_parser():
                         help="decode the decoder's large projections and its cross-attention with ONE fp16 product each, fp32 "
                              "accumulation (split_kind 'fp16', DESIGN.md 11): the arithmetic of the reference's 16-bit GPU decode. "
                              "cfg.trainer.precision is NOT read for this -- honouring it by default would change today's records")
+    parser.add_argument("--scores", action="store_true",
+                        help="every JSON record gains pred_face_scores, parallel to pred_faces: the summed log-probability of the "
+                             "face's greedy selections (DESIGN.md 12); single-process runs only")
     return parser
 
 
@@ -173,7 +207,7 @@ def main(argv=None):
         device = "cuda:%d" % local_rank
         dist_mod.init_process_group("nccl", device_id=torch.device(device))
     run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
-             retire_finished=args.retire_finished, fp16=args.fp16)
+             retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
