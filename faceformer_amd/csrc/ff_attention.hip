@@ -16,10 +16,9 @@
 // a query; they exchange only the tile max (one __shfl_xor 32) and add their partial sums at the end.
 #include <math.h>
 
-#include <atomic>
-
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 // Timing experiment (tools/attn_phase_probe.py, -DFF_EXP_ATTN_STAMP): workgroup 0, wave 0 of the K/V-resident kernel stamps the
 // shader clock at entry, when K / V are in LDS, when its items are done, after the partial records are exchanged, at the end.
@@ -701,13 +700,12 @@ __global__ __launch_bounds__(64 * RK_NW, 2) void attention_resident_kernel(ff_at
   }
 }
 
-int g_attention_algo = 0;  // 0 = automatic, 1 = block-shared LDS staging, 2 = wave-independent
+FFSetting g_attention_algo{{0}};  // 0 = automatic, 1 = block-shared LDS staging, 2 = wave-independent
 
 }  // namespace
 
 extern "C" int ff_set_attention_algo(int algo) {
-  const int old = g_attention_algo;
-  g_attention_algo = algo;
+  const int old = g_attention_algo.set(algo);
   ff_tuning_changed();
   return old;
 }
@@ -726,6 +724,7 @@ extern "C" int ff_attention(const ff_attn_desc* desc, ff_stream_t stream) {
                "ff_attention: ld smaller than num_heads*64");
   FF_CHECK_ARG(d.q_inner > 0, "ff_attention: q_inner must be positive");
   hipStream_t st = (hipStream_t)stream;
+  const int algo = g_attention_algo.get();
   const long gh = (long)d.num_groups * d.num_heads;
   int nw = d.nq > 64 ? 4 : (d.nq > 32 ? 2 : 1);
   const int q_tiles = ff_cdiv(d.nq, 32 * nw);
@@ -746,18 +745,12 @@ extern "C" int ff_attention(const ff_attn_desc* desc, ff_stream_t stream) {
   // 2 x fp16 kernel (round 6): the caller split K | V into fp16 planes (ff_attention_split_kv) -- same launches as the K/V-resident
   // kernel, an item at 24 half-length MFMAs instead of 65
   if (d.kv_planes && ff_attention_x2h_ok(d) &&
-      (g_attention_algo == 4 || (g_attention_algo == 0 && ff_knob(FF_K_X2H_ATTN) && qt32 >= 4 && gh * qt32 >= 512)))
+      (algo == 4 || (algo == 0 && ff_knob(FF_K_X2H_ATTN) && qt32 >= 4 && gh * qt32 >= 512)))
     return ff_attention_x2h_launch(d, d.kv_planes, (long long)ff_attention_planes_stride(), st);
-  if (g_attention_algo == 3 ? resident_ok : (g_attention_algo == 0 && resident_ok && qt32 >= 4 && gh * qt32 >= 512)) {
-    static std::atomic<bool> attr_done[16] = {};   // idempotent per-device attribute; host threads may race here
-    int dev = 0;
-    FF_CHECK_HIP(hipGetDevice(&dev));
+  if (algo == 3 ? resident_ok : (algo == 0 && resident_ok && qt32 >= 4 && gh * qt32 >= 512)) {
+    static FFLdsLimit attr_set = {};
     constexpr int lds_bytes = RK_LDS_FLOATS * (int)sizeof(float);
-    if (dev < 0 || dev >= 16 || !attr_done[dev].load(std::memory_order_acquire)) {
-      FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_resident_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-      if (dev >= 0 && dev < 16) attr_done[dev].store(true, std::memory_order_release);
-    }
+    FF_RETURN_IF(ff_lds_limit_once(attention_resident_kernel, lds_bytes, &attr_set));
     const int P = (int)gh;
     const int cus = ff_num_cus();
     int c = P <= cus ? cus / P : 1;
@@ -780,8 +773,8 @@ extern "C" int ff_attention(const ff_attn_desc* desc, ff_stream_t stream) {
   //  units of 516 / 1028 keys 39 / 63 us (wave) vs 51 / 89 (block-shared), 600 units of 304 keys 39 vs 31, 1024 units of 1028
   //  keys 114 vs 94, 1200 units of 304 keys 70 vs 54)
   const long wave_units_max = d.nk > RK_KEYS ? 576 : 1536;
-  const bool use_wave = g_attention_algo == 2 ||
-                        (g_attention_algo == 0 && (gh * ff_cdiv(d.nq, 32) < wave_units_max || d.nq <= 64));
+  const bool use_wave = algo == 2 ||
+                        (algo == 0 && (gh * ff_cdiv(d.nq, 32) < wave_units_max || d.nq <= 64));
   if (use_wave) {
     // wave-independent kernel: units = (group, head, 32-query tile); the key tiles are dealt round-robin to ks waves
     // (ks = 1, 2, 4, 8: a power of two up to the tile count, idle waves allowed) while the launch would otherwise

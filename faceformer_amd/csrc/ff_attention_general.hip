@@ -13,9 +13,8 @@
 // yield 0 there; the case never occurs on the decode path).
 #include <math.h>
 
-#include <atomic>
-
 #include "ff_common.h"
+#include "ff_launch.h"
 
 namespace {
 
@@ -150,15 +149,9 @@ extern "C" int ff_attention_general(const ff_attn_general_desc* desc, ff_stream_
   FF_CHECK_ARG(lds_bytes <= 160 * 1024, "ff_attention_general: head_dim + nk = %d + %d exceeds the 160 KB of LDS of a CU (4 rows of %d floats)",
                d.head_dim, d.nk, p.row_floats);
   hipStream_t st = (hipStream_t)stream;
-  if (lds_bytes > 64 * 1024) {
-    static std::atomic<size_t> attr_bytes[16] = {};
-    int dev = 0;
-    FF_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16 || attr_bytes[dev].load(std::memory_order_acquire) < lds_bytes) {
-      FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_general_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      if (dev >= 0 && dev < 16) attr_bytes[dev].store(160 * 1024, std::memory_order_release);
-    }
+  if (lds_bytes > 64 * 1024) {   // (launches up to 64 KB need no attribute; above, the limit is raised to the whole CU's 160 KB, once)
+    static FFLdsLimit attr_set = {};
+    FF_RETURN_IF(ff_lds_limit_once(attention_general_kernel, 160 * 1024, &attr_set));
   }
   FFProfScope prof(FF_CAT_ATTN, 4.0 * d.head_dim * (double)p.units * d.nk, st);
   const long long want = (p.units + GA_WAVES - 1) / GA_WAVES;

@@ -25,10 +25,9 @@
 // One term (NT = 1, ff_attn_desc.kv_terms = 1, the split kind "fp16"): the same kernel on the FIRST planes only, fp16(k) and fp16(v) --
 // fp16(q scale) fp16(K)^T in one MFMA chain (times log2 e in fp32), fp32 online softmax, fp16(P) fp16(V): 8 MFMAs per 32 x 32 item instead of 24.  Only
 // K1 and V1t are copied (75 KB of LDS instead of 146 KB).
-#include <atomic>
-
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 namespace {
 
@@ -288,14 +287,8 @@ bool ff_attention_x2h_ok(const ff_attn_desc& d) { return d.nk > 0 && d.nk <= XK_
 namespace {
 template <int NT>
 int x2h_launch(const ff_attn_desc& d, const void* planes, long long plane_stride, hipStream_t st) {
-  static std::atomic<bool> attr_done[16] = {};
-  int dev = 0;
-  FF_CHECK_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16 || !attr_done[dev].load(std::memory_order_acquire)) {
-    FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x2h_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     xk_lds_bytes<NT>()));
-    if (dev >= 0 && dev < 16) attr_done[dev].store(true, std::memory_order_release);
-  }
+  static FFLdsLimit attr_set = {};
+  FF_RETURN_IF(ff_lds_limit_once(attention_x2h_kernel<NT>, xk_lds_bytes<NT>(), &attr_set));
   const long gh = (long)d.num_groups * d.num_heads;
   FF_CHECK_ARG(gh < 2147483647L, "ff_attention: too many (group, head) pairs");
   // block slots: xk_blocks_per_cu per CU (one for both kernels, see XK_H1_BLOCKS)

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ff_common.h"
+#include "ff_launch.h"
 
 namespace {
 
@@ -585,7 +586,6 @@ struct StreamPool {
   int created;
   bool events;
 };
-constexpr int FF_MAX_DEVICES = 16;
 StreamPool g_pools[FF_MAX_DEVICES];
 std::mutex g_pool_mu;
 // The pool's side streams, events and pinned counters belong to ONE decode at a time: host threads that

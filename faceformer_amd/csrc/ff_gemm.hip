@@ -25,14 +25,11 @@
 // CU; wave-private tiles (no barrier, 2x the L2 traffic) and in-block split-K lost; barriers and the
 // phase of co-resident blocks do not matter; unpadded XOR-swizzled LDS rows (48 KB per block) with THREE
 // blocks per CU instead of two: 116.6 vs 115.4 TF/s at 8192x1536x512 -- occupancy is not the limit.
-#include <atomic>
-#include <mutex>
-#include <vector>
-
 #include <stdlib.h>
 
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 // Timing experiment (tools/gemm_slice_probe.py, -DFF_EXP_STAMP): the four waves of workgroup 0 of the persistent kernel stamp
 // the shader clock in front of and behind the block barrier of their first 256 slices.
@@ -1082,27 +1079,11 @@ __global__ __launch_bounds__(256) void gemm_streamk_kernel(GemmArgs g, StreamK s
   FF_EXP_SKSTAMP(5);
 }
 
-// hipFuncSetAttribute is per device: one flag per (kernel, device)
-constexpr int FF_MAX_DEV = 16;
-struct AttrFlags { std::atomic<bool> done[FF_MAX_DEV]; };   // idempotent attribute: host threads may race here
-template <typename K>
-int set_lds_limit(K kernel, int bytes, AttrFlags* fl) {
-  int dev = 0;
-  FF_CHECK_HIP(hipGetDevice(&dev));
-  const bool track = dev >= 0 && dev < FF_MAX_DEV;
-  if (!track || !fl->done[dev].load(std::memory_order_acquire)) {
-    FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    if (track) fl->done[dev].store(true, std::memory_order_release);
-  }
-  return FF_OK;
-}
-
 template <int BM, int BN, int WM, int WN>
 int launch_generic(GemmArgs g, int batch, hipStream_t st) {
-  static AttrFlags attr_set = {};
+  static FFLdsLimit attr_set = {};
   constexpr int bytes = 2 * (BM + BN) * 36 * (int)sizeof(float);
-  FF_RETURN_IF(set_lds_limit(&gemm_generic_kernel<BM, BN, WM, WN>, bytes, &attr_set));
+  FF_RETURN_IF(ff_lds_limit_once(&gemm_generic_kernel<BM, BN, WM, WN>, bytes, &attr_set));
   g.tiles_m = ff_cdiv(g.M, BM);
   g.tiles_n = ff_cdiv(g.N, BN);
   hipLaunchKernelGGL((gemm_generic_kernel<BM, BN, WM, WN>), dim3(g.tiles_m * g.tiles_n, batch), dim3(256), bytes,
@@ -1114,9 +1095,9 @@ int launch_generic(GemmArgs g, int batch, hipStream_t st) {
 template <int BM, int BN, int WM, int WN, int BK = 32>
 int launch_pipe(GemmArgs g, int batch, hipStream_t st) {
   if (g.K % BK != 0) return launch_generic<BM, BN, WM, WN>(g, batch, st);
-  static AttrFlags attr_set = {};
+  static FFLdsLimit attr_set = {};
   constexpr int bytes = 3 * (BM + BN) * (BK + 4) * (int)sizeof(float);
-  FF_RETURN_IF(set_lds_limit(&gemm_pipe_kernel<BM, BN, WM, WN, BK>, bytes, &attr_set));
+  FF_RETURN_IF(ff_lds_limit_once(&gemm_pipe_kernel<BM, BN, WM, WN, BK>, bytes, &attr_set));
   g.tiles_m = ff_cdiv(g.M, BM);
   g.tiles_n = ff_cdiv(g.N, BN);
   hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, WM, WN, BK>), dim3(g.tiles_m * g.tiles_n, batch), dim3(256), bytes, st,
@@ -1130,9 +1111,9 @@ constexpr int LN_PATCH_BYTES = 4 * 32 * 33 * (int)sizeof(float);  // MODE 2: one
 
 template <int MODE>
 int launch_persist_mode(GemmArgs g, int batch, hipStream_t st) {
-  static AttrFlags attr_set = {};
+  static FFLdsLimit attr_set = {};
   constexpr int bytes = 3 * 128 * 36 * (int)sizeof(float) + (MODE == 2 ? LN_PATCH_BYTES : 0);
-  FF_RETURN_IF(set_lds_limit(&gemm_persist_kernel<MODE>, bytes, &attr_set));
+  FF_RETURN_IF(ff_lds_limit_once(&gemm_persist_kernel<MODE>, bytes, &attr_set));
   g.tiles_m = ff_cdiv(g.M, 64);
   g.tiles_n = ff_cdiv(g.N, 64);
   const long total = (long)g.tiles_m * g.tiles_n * batch;
@@ -1148,46 +1129,16 @@ int launch_persist(GemmArgs g, int batch, hipStream_t st) {
     FF_CHECK_ARG(mode == 0, "ff_gemm_f32: the LayerNorm-fused forms need K %% 64 == 0 and K >= 128 (K=%d)", g.K);
     return launch_pipe<64, 64, 32, 32>(g, batch, st);
   }
-  if (mode == 1) return launch_persist_mode<1>(g, batch, st);
-  if (mode == 2) return launch_persist_mode<2>(g, batch, st);
-  return launch_persist_mode<0>(g, batch, st);
+  return ff_dispatch<1, 2, 0>(mode, [&](auto m) { return launch_persist_mode<m>(g, batch, st); });
 }
 
-// Stream-K workspace: one per (device, stream) -- launches on one stream are ordered, launches on
-// different streams may overlap and must not share partial-tile slots.  Allocated on first use, kept
-// for the life of the process (512 slots x 16 KB + flags).
+// Stream-K workspace: one area per (device, stream), 512 slots x 16 KB + flags (FFStreamAreas).
 constexpr int SK_MAX_GRID = 512;
-struct SkWorkspace {
-  int device;
-  hipStream_t st;
-  float* ws;
-  unsigned int* flags;
-};
-std::mutex g_sk_mu;
-std::vector<SkWorkspace> g_sk;
-int g_sk_min_units = 2;      // smallest range handed to a block (units of 64 k)
-int g_sk_two_per_cu = 2048;  // from this many units on, 512 blocks (2 per CU); below, at most 256
-int g_small_max_rows = 1024;  // tile 7 hands launches with at most this many rows to gemm_small_kernel
-double g_sk_fix_units = 2.5;  // what cutting tiles costs a launch, in units of per-CU work (policy only)
-
-int sk_acquire(hipStream_t st, StreamK* out) {
-  int dev = 0;
-  FF_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(g_sk_mu);
-  for (SkWorkspace& w : g_sk)
-    if (w.device == dev && w.st == st) {
-      out->ws = w.ws; out->flags = w.flags;
-      return FF_OK;
-    }
-  SkWorkspace w{dev, st, nullptr, nullptr};
-  FF_CHECK_HIP(hipMalloc(&w.ws, (size_t)SK_MAX_GRID * 4096 * sizeof(float)));
-  FF_CHECK_HIP(hipMalloc(&w.flags, SK_MAX_GRID * sizeof(unsigned int)));
-  FF_CHECK_HIP(hipMemset(w.flags, 0, SK_MAX_GRID * sizeof(unsigned int)));
-  FF_CHECK_HIP(hipDeviceSynchronize());
-  g_sk.push_back(w);
-  out->ws = w.ws; out->flags = w.flags;
-  return FF_OK;
-}
+FFStreamAreas g_sk_areas{(size_t)SK_MAX_GRID * 4096 * sizeof(float), SK_MAX_GRID};
+FFSetting g_sk_min_units{{2}};      // smallest range handed to a block (units of 64 k)
+FFSetting g_sk_two_per_cu{{2048}};  // from this many units on, 512 blocks (2 per CU); below, at most 256
+FFSetting g_small_max_rows{{1024}};  // tile 7 hands launches with at most this many rows to gemm_small_kernel
+FFSetting g_sk_fix_tenths{{25}};    // what cutting tiles costs a launch, in tenths of a unit of per-CU work (policy only)
 
 // ---- small-M kernel: one 32x32 output tile per block, K split over the four waves ---------------------------
 // The first decode steps (and the whole seq2seq variant) launch products with a few hundred rows: every
@@ -1386,9 +1337,9 @@ __global__ __launch_bounds__(512) void gemm_panel_kernel(GemmArgs g) {
 
 template <int KC, int MODE>
 int launch_panel(const GemmArgs& g, dim3 grid, hipStream_t st) {
-  static AttrFlags attr_set = {};
+  static FFLdsLimit attr_set = {};
   constexpr int bytes = (64 * (KC + 4) + 64) * (int)sizeof(float);
-  FF_RETURN_IF(set_lds_limit(&gemm_panel_kernel<KC, MODE>, bytes, &attr_set));
+  FF_RETURN_IF(ff_lds_limit_once(&gemm_panel_kernel<KC, MODE>, bytes, &attr_set));
   hipLaunchKernelGGL((gemm_panel_kernel<KC, MODE>), grid, dim3(512), bytes, st, g);
   return FF_OK;
 }
@@ -1431,10 +1382,7 @@ int launch_small(GemmArgs g, int batch, hipStream_t st) {
   g.tiles_m = ff_cdiv(g.M, 32);
   g.tiles_n = ff_cdiv(g.N, 32);
   const dim3 grid(g.tiles_m * g.tiles_n, batch);
-  const int mode = gemm_mode(g);
-  if (mode == 1) return launch_small_mode<1>(g, grid, st);
-  if (mode == 2) return launch_small_mode<2>(g, grid, st);
-  return launch_small_mode<0>(g, grid, st);
+  return ff_dispatch<1, 2, 0>(gemm_mode(g), [&](auto m) { return launch_small_mode<m>(g, grid, st); });
 }
 bool small_ok(const GemmArgs& g) {
   return (g.K == 128 || g.K == 256 || g.K == 512 || g.K == 1024) && (!g.A2 || (g.n_split % 32) == 0);
@@ -1443,29 +1391,29 @@ bool small_ok(const GemmArgs& g) {
 // mode 0: whole tiles (persistent kernel) or equal unit ranges, whichever the cost model prefers; 2: unit ranges
 template <int MODE>
 int launch_streamk_mode(const GemmArgs& g, const StreamK& sk, int grid, hipStream_t st) {
-  static AttrFlags attr_set = {};
+  static FFLdsLimit attr_set = {};
   constexpr int bytes = 3 * 128 * 36 * (int)sizeof(float) + (MODE == 2 ? LN_PATCH_BYTES : 0);
-  FF_RETURN_IF(set_lds_limit(&gemm_streamk_kernel<MODE>, bytes, &attr_set));
+  FF_RETURN_IF(ff_lds_limit_once(&gemm_streamk_kernel<MODE>, bytes, &attr_set));
   hipLaunchKernelGGL(gemm_streamk_kernel<MODE>, dim3(grid), dim3(256), bytes, st, g, sk);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
 
-int launch_streamk(GemmArgs g, int batch, hipStream_t st, int mode) {
-  if (g.K % 64 != 0 || g.K < 128) return launch_persist(g, batch, st);   // (reports the LN-fused restriction)
-  g.tiles_m = ff_cdiv(g.M, 64);
-  g.tiles_n = ff_cdiv(g.N, 64);
-  StreamK sk;
-  sk.upt = g.K / 64;
-  const long tiles = (long)g.tiles_m * g.tiles_n * batch;
-  const long units = tiles * sk.upt;
-  FF_CHECK_ARG(units < (1L << 30), "ff_gemm_f32: problem too large for the stream-K launcher");
+// Launch plan of the stream-K family: which of its three forms runs, the grid and the kernel's StreamK fields (ws / flags are
+// filled at the launch).  Host arithmetic only: tiles and units per tile of the launch, the caller's mode (0: the cost model
+// decides, 2: unit ranges), the CUs of the device; the knobs and ff_set_gemm_tuning's settings are read here.
+enum SkForm { SK_WHOLE, SK_HYBRID, SK_RANGES };   // persistent whole tiles (gemm_persist_kernel) / hybrid / equal unit ranges
+struct SkPlan { SkForm form; int grid; StreamK sk; };
+SkPlan sk_plan(long tiles, int upt, int mode, int num_cus) {
+  SkPlan p{SK_RANGES, 0, {}};
+  StreamK& sk = p.sk;
+  sk.upt = upt;
+  const long units = tiles * upt;
   // Whole tiles (no exchange) when they spread evenly enough over the 256 CUs, otherwise equal unit
-  // ranges: per-CU cost in units, the cut costing about g_sk_fix_units on top of the even share.
+  // ranges: per-CU cost in units, the cut costing about g_sk_fix_tenths / 10 on top of the even share.
   const long cus = SK_MAX_GRID / 2;
   const double whole_cost = (double)((tiles + cus - 1) / cus) * sk.upt;
-  const double split_cost = (double)units / cus + g_sk_fix_units;
-  sk.nA = 0; sk.tH = 0; sk.tL = 0; sk.uA = 0; sk.gx = 0;
+  const double split_cost = (double)units / cus + 0.1 * g_sk_fix_tenths.get();
   // Hybrid (see StreamK): hw whole tiles per CU + the units of the remaining tiles dealt to a second block per CU.
   const int hyb_on = ff_knob(FF_K_SK_HYBRID);               // (A/B knob)
   const double hyb_fix = 0.1 * ff_knob(FF_K_SK_HYBRID_FIX);
@@ -1476,7 +1424,7 @@ int launch_streamk(GemmArgs g, int batch, hipStream_t st, int mode) {
   const int hyb_force = ff_knob(FF_K_SK_HYBRID_FORCE);   // (probe: whole rounds too)
   // (the hybrid plan -- 256 heavy + up to 256 light blocks, light blocks waiting for partials of lower-numbered ones -- is made for
   //  and measured on the 256 CUs of an MI355X in SPX mode; a partition with another CU count keeps the older launch shapes)
-  if (mode == 0 && hyb_on && ff_num_cus() == (int)cus && hw >= 1 && (left > 0 || hyb_force) && 8 * left <= hyb_max_left8 * cus) {
+  if (mode == 0 && hyb_on && num_cus == (int)cus && hw >= 1 && (left > 0 || hyb_force) && 8 * left <= hyb_max_left8 * cus) {
     const long left_units = left * sk.upt;
     const long hyb_min_units = ff_knob(FF_K_SK_HYBRID_MINU);   // (A/B knob)
     long gb = left_units / (hyb_min_units > 0 ? hyb_min_units : 1);
@@ -1488,47 +1436,56 @@ int launch_streamk(GemmArgs g, int batch, hipStream_t st, int mode) {
       sk.gx = (int)gb;
       sk.base = (int)(left_units / gb);
       sk.rem = (int)(left_units % gb);
-      FF_RETURN_IF(sk_acquire(st, &sk));
-      const int lmh = gemm_mode(g);
-      const int gridh = (int)(cus + (sk.tL > 0 ? cus : gb));   // light blocks: all 256 when they carry whole tiles
-      if (lmh == 1) return launch_streamk_mode<1>(g, sk, gridh, st);
-      if (lmh == 2) return launch_streamk_mode<2>(g, sk, gridh, st);
-      return launch_streamk_mode<0>(g, sk, gridh, st);
+      p.form = SK_HYBRID;
+      p.grid = (int)(cus + (sk.tL > 0 ? cus : gb));   // light blocks: all 256 when they carry whole tiles
+      return p;
     }
   }
-  if (mode == 0 && whole_cost <= split_cost) return launch_persist(g, batch, st);
+  if (mode == 0 && whole_cost <= split_cost) {
+    p.form = SK_WHOLE;
+    return p;
+  }
   long grid;
-  if (units >= g_sk_two_per_cu) grid = SK_MAX_GRID;
+  if (units >= g_sk_two_per_cu.get()) grid = SK_MAX_GRID;
   else {
-    grid = ff_cdiv((int)units, g_sk_min_units);
+    grid = ff_cdiv((int)units, g_sk_min_units.get());
     if (grid > cus) grid = cus;
   }
   if (grid > units) grid = units;
   sk.base = (int)(units / grid);
   sk.rem = (int)(units % grid);
-  FF_RETURN_IF(sk_acquire(st, &sk));
-  const int lm = gemm_mode(g);
-  if (lm == 1) return launch_streamk_mode<1>(g, sk, (int)grid, st);
-  if (lm == 2) return launch_streamk_mode<2>(g, sk, (int)grid, st);
-  return launch_streamk_mode<0>(g, sk, (int)grid, st);
+  p.grid = (int)grid;
+  return p;
+}
+
+int launch_streamk(GemmArgs g, int batch, hipStream_t st, int mode) {
+  if (g.K % 64 != 0 || g.K < 128) return launch_persist(g, batch, st);   // (reports the LN-fused restriction)
+  g.tiles_m = ff_cdiv(g.M, 64);
+  g.tiles_n = ff_cdiv(g.N, 64);
+  const long tiles = (long)g.tiles_m * g.tiles_n * batch;
+  FF_CHECK_ARG(tiles * (g.K / 64) < (1L << 30), "ff_gemm_f32: problem too large for the stream-K launcher");
+  SkPlan p = sk_plan(tiles, g.K / 64, mode, ff_num_cus());
+  if (p.form == SK_WHOLE) return launch_persist(g, batch, st);
+  FF_RETURN_IF(g_sk_areas.acquire(st, &p.sk.ws, &p.sk.flags));
+  return ff_dispatch<1, 2, 0>(gemm_mode(g), [&](auto m) { return launch_streamk_mode<m>(g, p.sk, p.grid, st); });
 }
 
 }  // namespace
 
 extern "C" int ff_gemm_prepare_stream(ff_stream_t stream) {
-  StreamK sk;
-  FF_RETURN_IF(sk_acquire((hipStream_t)stream, &sk));
+  float* ws = nullptr;
+  unsigned int* flags = nullptr;
+  FF_RETURN_IF(g_sk_areas.acquire((hipStream_t)stream, &ws, &flags));
   return ff_x3_prepare_stream((hipStream_t)stream);
 }
 
 extern "C" int ff_set_gemm_tuning(int min_units, int two_per_cu_units, int fix_tenths, int small_max_rows) {
   FF_CHECK_ARG(min_units >= 1 && two_per_cu_units >= 1 && fix_tenths >= 0 && small_max_rows >= 0,
                "ff_set_gemm_tuning: bad arguments");
-  std::lock_guard<std::mutex> lock(g_sk_mu);
-  g_sk_min_units = min_units;
-  g_sk_two_per_cu = two_per_cu_units;
-  g_sk_fix_units = 0.1 * fix_tenths;
-  g_small_max_rows = small_max_rows;
+  g_sk_min_units.set(min_units);
+  g_sk_two_per_cu.set(two_per_cu_units);
+  g_sk_fix_tenths.set(fix_tenths);   // (0.1 * tenths is formed where it is used: the same double as before)
+  g_small_max_rows.set(small_max_rows);
   ff_tuning_changed();
   return FF_OK;
 }
@@ -1576,7 +1533,7 @@ int gemm_dispatch(GemmArgs g, int batch, int tile, hipStream_t st) {
       // few rows, the path's K (512 / 1024): the unstaged split-K kernel (its unshared operand loads cost more
       // than the staging from ~1000 rows on; with K < 512 a wave's share of K is too short to be worth it)
       // (wide outputs leave it earlier: at 1024 rows the persistent kernel is 8 % / 22 % faster for N = 1536 / 1024)
-      if ((long)M * batch <= (N <= 512 ? g_small_max_rows : (g_small_max_rows * 3) / 4) && K >= 512 && small_ok(g))
+      if (const int smr = g_small_max_rows.get(); (long)M * batch <= (N <= 512 ? smr : (smr * 3) / 4) && K >= 512 && small_ok(g))
         return launch_small(g, batch, st);
       // Plain projections of the large steps: 128x64 block tiles with 64x32 wave tiles and 16-wide slices (two
       // accumulators share every W fragment: 6 instead of 8 fragment reads per 16 MFMAs, half the global -> LDS

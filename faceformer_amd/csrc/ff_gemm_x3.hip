@@ -36,13 +36,9 @@
 // Measured (profiles/r04): the loop runs into the chip's POWER limit, not its issue limit -- 245-272 TF/s fp32-equivalent
 // on zero-filled operands, 170-200 on random ones (same binary); pre-split activation planes are worth 0-8 % and were
 // dropped again.
-#include <mutex>
-#include <vector>
-
-#include <atomic>
-
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 // Timing experiment (tools/x3_phase_probe.py, -DX3_EXP_STAMP): wave 0 of workgroup 0 of gemm_x3_kernel sums, over its K-loop iterations,
 // the shader-clock time of (0) the MFMA block with everything placed in its gaps, (1) the wait for the DMA / fragment reads behind
@@ -1436,69 +1432,34 @@ __global__ __launch_bounds__(256, 3) void gemm_dma_f32_kernel(X3Args g) {
   }
 }
 
-// Partial-tile workspace: one per (device, stream), as in ff_gemm.hip.
+// Partial-tile workspace: one area per (device, stream), as in ff_gemm.hip (FFStreamAreas).
 constexpr int X3_MAX_GRID = 768;
 constexpr size_t X3_WS_BYTES = (size_t)X3_MAX_GRID * 64 * 128 * sizeof(float);   // one 32 KB partial tile per block
-struct X3Workspace {
-  int device;
-  hipStream_t st;
-  float* ws;
-  unsigned int* flags;
-};
-std::mutex g_x3_mu;
-std::vector<X3Workspace> g_x3;
-
-int x3_acquire(hipStream_t st, X3Args* out) {
-  int dev = 0;
-  FF_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(g_x3_mu);
-  for (X3Workspace& w : g_x3)
-    if (w.device == dev && w.st == st) {
-      out->ws = w.ws; out->flags = w.flags;
-      return FF_OK;
-    }
-  X3Workspace w{dev, st, nullptr, nullptr};
-  FF_CHECK_HIP(hipMalloc(&w.ws, X3_WS_BYTES));
-  FF_CHECK_HIP(hipMalloc(&w.flags, X3_MAX_GRID * sizeof(unsigned int)));
-  FF_CHECK_HIP(hipMemset(w.flags, 0, X3_MAX_GRID * sizeof(unsigned int)));
-  FF_CHECK_HIP(hipDeviceSynchronize());
-  g_x3.push_back(w);
-  out->ws = w.ws; out->flags = w.flags;
-  return FF_OK;
-}
+FFStreamAreas g_x3_areas{X3_WS_BYTES, X3_MAX_GRID};
 
 // tuning / tests: force the launch shape (0 auto, 1 whole tiles, 2 unit ranges)
-int g_x3_force_shape = 0;
+FFSetting g_x3_force_shape{{0}};
 
 template <int BM, int MODE, int NT = 3>
 int x3_launch_mode(const X3Args& g, int grid, hipStream_t st) {
-  static std::atomic<bool> attr_set[16] = {};   // hipFuncSetAttribute is per device; host threads may race here (idempotent)
+  static FFLdsLimit attr_set = {};
 #ifndef X3_EXP_LDS_PAD     // probe: extra dynamic LDS per block = fewer blocks per CU (occupancy experiments)
 #define X3_EXP_LDS_PAD 0
 #endif
   constexpr int bytes = x3_ring<MODE, NT>() * (BM * 64 + NT * X3_BN * 32) + (MODE == 1 ? X3_STAT_BYTES : 0) + X3_EXP_LDS_PAD;
-  int dev = 0;
-  FF_CHECK_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-    FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x3_kernel<BM, MODE, NT>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    if (dev >= 0 && dev < 16) attr_set[dev] = true;
-  }
+  FF_RETURN_IF(ff_lds_limit_once(&gemm_x3_kernel<BM, MODE, NT>, bytes, &attr_set));
   hipLaunchKernelGGL((gemm_x3_kernel<BM, MODE, NT>), dim3(grid), dim3(256), bytes, st, g);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
+// block slots per CU of gemm_dma_f32_kernel: the 64-column tile needs 109-111 registers without the LayerNorm consumer's
+// state, so four blocks fit a CU; every other form runs three
+constexpr int dma_f32_blocks_per_cu(int mode, int bn) { return (bn == 64 && mode != 1) ? 4 : 3; }
 template <int BM, int MODE, int BN = X3_BN>
 int dma_f32_launch_mode(const X3Args& g, int grid, hipStream_t st) {
-  static std::atomic<bool> attr_set[16] = {};
+  static FFLdsLimit attr_set = {};
   constexpr int bytes = X3_RING_F32 * (BM * 64 + BN * 64) + (MODE == 1 ? X3_STAT_BYTES : 0);
-  int dev = 0;
-  FF_CHECK_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-    FF_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dma_f32_kernel<BM, MODE, BN>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    if (dev >= 0 && dev < 16) attr_set[dev] = true;
-  }
+  FF_RETURN_IF(ff_lds_limit_once(&gemm_dma_f32_kernel<BM, MODE, BN>, bytes, &attr_set));
   hipLaunchKernelGGL((gemm_dma_f32_kernel<BM, MODE, BN>), dim3(grid), dim3(256), bytes, st, g);
   FF_CHECK_LAUNCH();
   return FF_OK;
@@ -1513,21 +1474,16 @@ int dma_f32_launch_mode(const X3Args& g, int grid, hipStream_t st) {
 // and the register allocator then spills INTO the K loop (a spill of a fragment register that an asynchronous ds_read has
 // not filled yet stores garbage, and every reload costs a full vmcnt drain); where it compiled cleanly it was within +-7 %
 // of the 64-row tile.
-int x3_launch(X3Args g, int mode, hipStream_t st, bool f32 = false, int bn = X3_BN) {
-  const int M = g.M, N = g.N, K = g.K;
-  constexpr int BM = 64;
-  const int cus = ff_num_cus();   // 256 on an MI355X in SPX mode; a partition (CPX / fewer CUs) gets its own launch shape
-  // block slots per CU: registers / the statistics patch of the LayerNorm consumers decide
-  // (the 64-column f32 tile needs 109-111 registers without the LayerNorm consumer's state: four blocks fit a CU)
-  const int spc = f32 ? ((bn == 64 && mode != 1) ? 4 : 3) : (mode == 3 ? 2 : (mode == 1 ? (g.nt == 2 ? X3_LN_H_BLOCKS : 2) : 3));
+constexpr int X3_BM = 64;
+// The plan, host arithmetic only: tiles and 32-wide K units per tile of the launch, the device's CUs (256 on an MI355X in
+// SPX mode; a partition (CPX / fewer CUs) gets its own launch shape), the kernel's block slots per CU (registers / the
+// statistics patch of the LayerNorm consumers decide), ff_set_x3_tuning's forced shape and the FF_X3_SMALL_SPLIT knob.
+struct X3Plan { int grid, hyb, hw, hs, ha, nA, gran, base, rem, bal; };
+X3Plan x3_plan(long tiles, int upt, int cus, int spc, int force_shape, int small_split) {
+  X3Plan p{};
   const int slots = cus * spc;
-  g.tiles_n = ff_cdiv(N, bn);
-  g.tiles_m = ff_cdiv(M, BM);
-  g.upt = K / 32;
-  const long tiles = (long)g.tiles_m * g.tiles_n;
-  const long units = tiles * g.upt;
-  FF_CHECK_ARG(units < (1L << 30), "ff_gemm_x3: problem too large");
-  int shape = g_x3_force_shape ? g_x3_force_shape : 1;
+  const long units = tiles * upt;
+  int shape = force_shape ? force_shape : 1;
   if (units < 2) shape = 1;
   long grid;
   // Hybrid (the default whenever it applies): hw = tiles / CUs whole tiles per CU and the r = tiles % CUs remaining tiles cut
@@ -1536,54 +1492,62 @@ int x3_launch(X3Args g, int mode, hipStream_t st, bool f32 = false, int bn = X3_
   const long hw = tiles / cus, hr = tiles % cus;
   int hs = 0;
   for (int c = 8; c >= 2; c >>= 1)
-    if (hr * c <= cus && g.upt % c == 0 && g.upt / c >= 2) { hs = c; break; }
-  const int small_split = ff_knob(FF_K_X3_SMALL_SPLIT);   // (probe: K-pieces for launches below one tile per CU)
-  if (!g_x3_force_shape && ((hw >= 1 && hr > 0) || (small_split && hw == 0 && hr * 2 <= cus)) && hs > 0) {
-    g.hyb = 1; g.hw = (int)hw; g.hs = hs; g.cus = cus;
-    g.ha = (spc == 2 || hw == 1) ? 1 : 2;   // (one slot stays for the K-piece blocks)
-    g.nA = hw == 0 ? 0 : cus * g.ha;
-    grid = g.nA + hr * hs;
+    if (hr * c <= cus && upt % c == 0 && upt / c >= 2) { hs = c; break; }
+  // (small_split: a probe -- K-pieces for launches below one tile per CU)
+  if (!force_shape && ((hw >= 1 && hr > 0) || (small_split && hw == 0 && hr * 2 <= cus)) && hs > 0) {
+    p.hyb = 1; p.hw = (int)hw; p.hs = hs;
+    p.ha = (spc == 2 || hw == 1) ? 1 : 2;   // (one slot stays for the K-piece blocks)
+    p.nA = hw == 0 ? 0 : cus * p.ha;
+    grid = p.nA + hr * hs;
   } else if (shape == 1) {        // whole tiles: contiguous runs of tiles per block
     grid = tiles < slots ? tiles : slots;
-    g.gran = g.upt;
-    g.base = (int)(tiles / grid);
-    g.rem = (int)(tiles % grid);
-    g.bal = 1;
+    p.gran = upt;
+    p.base = (int)(tiles / grid);
+    p.rem = (int)(tiles % grid);
+    p.bal = 1;
   } else {                 // equal unit ranges over every resident block slot
     grid = units < slots ? units : slots;
-    g.gran = 1;
-    g.base = (int)(units / grid);
-    g.rem = (int)(units % grid);
+    p.gran = 1;
+    p.base = (int)(units / grid);
+    p.rem = (int)(units % grid);
   }
-  FF_RETURN_IF(x3_acquire(st, &g));
-  if (f32 && bn == 64) {
-    if (mode == 1) return dma_f32_launch_mode<BM, 1, 64>(g, (int)grid, st);
-    if (mode == 2) return dma_f32_launch_mode<BM, 2, 64>(g, (int)grid, st);
-    return dma_f32_launch_mode<BM, 0, 64>(g, (int)grid, st);
+  p.grid = (int)grid;
+  return p;
+}
+
+// Tiles of the launch (bn tile columns), its plan for `spc` block slots per CU and the stream's workspace -> g; the grid -> *grid.
+int x3_shape(X3Args& g, int bn, int spc, hipStream_t st, int* grid) {
+  g.tiles_n = ff_cdiv(g.N, bn);
+  g.tiles_m = ff_cdiv(g.M, X3_BM);
+  g.upt = g.K / 32;
+  const long tiles = (long)g.tiles_m * g.tiles_n;
+  FF_CHECK_ARG(tiles * g.upt < (1L << 30), "ff_gemm_x3: problem too large");
+  const int cus = ff_num_cus();
+  const X3Plan p = x3_plan(tiles, g.upt, cus, spc, g_x3_force_shape.get(), ff_knob(FF_K_X3_SMALL_SPLIT));
+  g.hyb = p.hyb; g.hw = p.hw; g.hs = p.hs; g.ha = p.ha; g.nA = p.nA; g.cus = p.hyb ? cus : 0;
+  g.gran = p.gran; g.base = p.base; g.rem = p.rem; g.bal = p.bal;
+  *grid = p.grid;
+  return g_x3_areas.acquire(st, &g.ws, &g.flags);
+}
+
+// The part of X3Args every entry point fills the same way; the callers add the weight (W / ldw, or Wp / plane_stride / nt),
+// w_row0 and colsum.  ln: the LayerNorm fields of the fused forms, or null.
+struct X3Ln { const float* ln_in; float ln_eps; const float* rowtab; int ld_rowtab, rowtab_div, rowtab_cols; float* ln_out; };
+X3Args x3_args(const float* A, const float* A2, int lda, const float* bias, const float* res, int ldr, float* C, int ldc,
+               int M, int N, int K, int n_split, int act, const X3Ln* ln) {
+  X3Args g;
+  memset(&g, 0, sizeof(g));
+  g.A = A; g.A2 = A2; g.lda = lda;
+  g.bias = bias; g.res = res; g.ldr = ldr;
+  g.C = C; g.ldc = ldc;
+  g.M = M; g.N = N; g.K = K; g.n_split = A2 ? n_split : N; g.act = act;
+  g.w_rows = N;
+  if (ln) {
+    g.ln_in = ln->ln_in; g.ln_eps = ln->ln_eps;
+    g.rowtab = ln->rowtab; g.ld_rowtab = ln->ld_rowtab; g.rowtab_div = ln->rowtab_div > 0 ? ln->rowtab_div : 1; g.rowtab_cols = ln->rowtab_cols;
+    g.ln_out = ln->ln_out;
   }
-  if (f32) {   // (the caller opened the f32 family's profiling scope)
-    if (mode == 1) return dma_f32_launch_mode<BM, 1>(g, (int)grid, st);
-    if (mode == 2) return dma_f32_launch_mode<BM, 2>(g, (int)grid, st);
-    return dma_f32_launch_mode<BM, 0>(g, (int)grid, st);
-  }
-  FFProfScope prof(FF_CAT_GEMM_X3, 2.0 * M * N * K, st);
-  ff_prof_add_bytes(FF_CAT_GEMM_X3, 4.0 * (double)M * K + 2.0 * g.nt * (double)N * K + 4.0 * (double)M * N * (g.res ? 2 : 1));
-  if (g.nt == 1) {
-    if (mode == 1) return x3_launch_mode<BM, 1, 1>(g, (int)grid, st);
-    if (mode == 2) return x3_launch_mode<BM, 2, 1>(g, (int)grid, st);
-    if (mode == 3) return x3_launch_mode<BM, 3, 1>(g, (int)grid, st);
-    return x3_launch_mode<BM, 0, 1>(g, (int)grid, st);
-  }
-  if (g.nt == 2) {
-    if (mode == 1) return x3_launch_mode<BM, 1, 2>(g, (int)grid, st);
-    if (mode == 2) return x3_launch_mode<BM, 2, 2>(g, (int)grid, st);
-    if (mode == 3) return x3_launch_mode<BM, 3, 2>(g, (int)grid, st);
-    return x3_launch_mode<BM, 0, 2>(g, (int)grid, st);
-  }
-  if (mode == 1) return x3_launch_mode<BM, 1>(g, (int)grid, st);
-  if (mode == 2) return x3_launch_mode<BM, 2>(g, (int)grid, st);
-  if (mode == 3) return x3_launch_mode<BM, 3>(g, (int)grid, st);
-  return x3_launch_mode<BM, 0>(g, (int)grid, st);
+  return g;
 }
 
 int x3_check_common(const float* A, int lda, const void* w_planes, const float* bias, const float* residual, int ldr,
@@ -1617,17 +1581,18 @@ bool ff_gemm_dma_f32_ok(const GemmArgs& a, int batch) {
   return true;
 }
 int ff_gemm_dma_f32(const GemmArgs& a, hipStream_t st, int bn) {
-  X3Args g;
-  memset(&g, 0, sizeof(g));
-  g.A = a.A; g.A2 = a.A2; g.lda = a.lda;
-  g.W = a.W; g.ldw = a.ldw; g.bias = a.bias; g.res = a.res; g.ldr = a.ldr;
-  g.C = a.C; g.ldc = a.ldc;
-  g.M = a.M; g.N = a.N; g.K = a.K; g.n_split = a.A2 ? a.n_split : a.N; g.act = a.act;
-  g.w_rows = a.N; g.w_row0 = 0;
-  g.ln_in = a.ln_in; g.ln_eps = a.ln_eps;
-  g.rowtab = a.rowtab; g.ld_rowtab = a.ld_rowtab; g.rowtab_div = a.rowtab_div > 0 ? a.rowtab_div : 1; g.rowtab_cols = a.rowtab_cols;
-  g.ln_out = a.ln_out;
-  return x3_launch(g, a.ln_in ? 1 : (a.ln_out ? 2 : 0), st, true, bn == 64 ? 64 : X3_BN);
+  const X3Ln ln{a.ln_in, a.ln_eps, a.rowtab, a.ld_rowtab, a.rowtab_div, a.rowtab_cols, a.ln_out};
+  X3Args g = x3_args(a.A, a.A2, a.lda, a.bias, a.res, a.ldr, a.C, a.ldc, a.M, a.N, a.K, a.n_split, a.act, &ln);
+  g.W = a.W; g.ldw = a.ldw;
+  const int mode = a.ln_in ? 1 : (a.ln_out ? 2 : 0);
+  // (no profiling scope here: the dispatcher of ff_gemm.hip books the f32 family under its own category)
+  return ff_dispatch<64, X3_BN>(bn, [&](auto tile_n) {
+    return ff_dispatch<1, 2, 0>(mode, [&](auto m) {
+      int grid = 0;
+      FF_RETURN_IF(x3_shape(g, tile_n, dma_f32_blocks_per_cu(m, tile_n), st, &grid));
+      return dma_f32_launch_mode<X3_BM, m, tile_n>(g, grid, st);
+    });
+  });
 }
 
 // The three split entry points differ in kernel and term count only: fp16_terms = 0 is the 3 x bf16 split, 2 / 1 the fp16 ones.
@@ -1661,28 +1626,40 @@ extern "C" int ff_split_weight_fp16(const float* W, int ldw, int N, int K, void*
 }
 
 extern "C" int ff_x3_prepare_stream(hipStream_t st) {
-  X3Args g;
-  return x3_acquire(st, &g);
+  float* ws = nullptr;
+  unsigned int* flags = nullptr;
+  return g_x3_areas.acquire(st, &ws, &flags);
 }
 
 // The same per-(device, stream) area as scratch memory of other kernels on that stream (stream order keeps the users apart):
 // the K/V-resident attention kernel parks its first partial records there (ff_attention.hip).
 int ff_stream_scratch(hipStream_t st, size_t bytes, float** out) {
   FF_CHECK_ARG(bytes <= X3_WS_BYTES, "ff_stream_scratch: %zu bytes requested, the area has %zu", bytes, X3_WS_BYTES);
-  X3Args g;
-  FF_RETURN_IF(x3_acquire(st, &g));
-  *out = g.ws;
-  return FF_OK;
+  unsigned int* flags = nullptr;
+  return g_x3_areas.acquire(st, out, &flags);
 }
 
 extern "C" int ff_set_x3_tuning(int shape) {
   FF_CHECK_ARG(shape >= 0 && shape <= 2, "ff_set_x3_tuning: shape in {0, 1, 2}");
-  g_x3_force_shape = shape;
+  g_x3_force_shape.set(shape);
   ff_tuning_changed();
   return FF_OK;
 }
 
 namespace {
+// The split kernels: slots per CU are what __launch_bounds__ of the chosen (MODE, NT) form states.
+int x3_launch(X3Args g, int mode, hipStream_t st) {
+  return ff_dispatch<1, 2, 3>(g.nt, [&](auto nt) {
+    return ff_dispatch<1, 2, 3, 0>(mode, [&](auto m) {
+      int grid = 0;
+      FF_RETURN_IF(x3_shape(g, X3_BN, x3_blocks_per_cu<m, nt>(), st, &grid));
+      FFProfScope prof(FF_CAT_GEMM_X3, 2.0 * g.M * g.N * g.K, st);
+      ff_prof_add_bytes(FF_CAT_GEMM_X3, 4.0 * (double)g.M * g.K + 2.0 * g.nt * (double)g.N * g.K + 4.0 * (double)g.M * g.N * (g.res ? 2 : 1));
+      return x3_launch_mode<X3_BM, m, nt>(g, grid, st);
+    });
+  });
+}
+
 int gemm_split_plain(int nt, const char* who, const float* A, int lda, const float* A2, int n_split, const void* w_planes,
                      const float* bias, const float* residual, int ldr, float* C, int ldc, int M, int N,
                      int K, int act, ff_stream_t stream) {
@@ -1690,15 +1667,10 @@ int gemm_split_plain(int nt, const char* who, const float* A, int lda, const flo
   FF_RETURN_IF(x3_check_common(A, lda, w_planes, bias, residual, ldr, C, ldc, M, N, K, act, who));
   FF_CHECK_ARG(!A2 || ff_aligned16(A2), "%s: A2 must be 16-byte aligned", who);
   if (A2) FF_CHECK_ARG(n_split > 0 && n_split < N && (n_split % 128) == 0, "%s: n_split must be a multiple of 128 inside (0,N)", who);
-  X3Args g;
-  memset(&g, 0, sizeof(g));
+  X3Args g = x3_args(A, A2, lda, bias, residual, ldr, C, ldc, M, N, K, n_split, act, nullptr);
   g.nt = nt;
-  g.A = A; g.A2 = A2; g.lda = lda;
-  g.Wp = static_cast<const unsigned short*>(w_planes); g.bias = bias; g.res = residual; g.ldr = ldr;
-  g.C = C; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K; g.n_split = A2 ? n_split : N; g.act = act;
+  g.Wp = static_cast<const unsigned short*>(w_planes);
   g.plane_stride = (long long)N * K;
-  g.w_rows = N; g.w_row0 = 0;
   return x3_launch(g, 0, (hipStream_t)stream);
 }
 }  // namespace
@@ -1744,18 +1716,12 @@ int gemm_split_ln(int nt, const ff_gemm_ln_desc* d, const void* w_planes, int pl
                                  ff_aligned16(d->row_table)),
                "ff_gemm_x3_ln: row_table needs ln_stats_in, no residual, row_div > 0, 0 < row_cols <= N, row_cols / ld %% 4");
   FF_CHECK_ARG(!d->ln_stats_out || (N & 31) == 0, "ff_gemm_x3_ln: ln_stats_out needs N %% 32 == 0");
-  X3Args g;
-  memset(&g, 0, sizeof(g));
+  const X3Ln ln{d->ln_stats_in, d->ln_eps, d->row_table, d->ld_row_table, d->row_div, d->row_cols, d->ln_stats_out};
+  X3Args g = x3_args(d->A, nullptr, d->lda, d->bias, d->residual, d->ldr, d->C, d->ldc, M, N, K, N, d->act, &ln);
   g.nt = nt;
-  g.A = d->A; g.lda = d->lda;
-  g.Wp = static_cast<const unsigned short*>(w_planes); g.bias = d->bias; g.res = d->residual; g.ldr = d->ldr;
-  g.C = d->C; g.ldc = d->ldc;
-  g.M = M; g.N = N; g.K = K; g.n_split = N; g.act = d->act;
+  g.Wp = static_cast<const unsigned short*>(w_planes);
   g.plane_stride = (long long)plane_rows * K;
   g.w_rows = plane_rows; g.w_row0 = row0;
-  g.ln_in = d->ln_stats_in; g.ln_eps = d->ln_eps;
-  g.rowtab = d->row_table; g.ld_rowtab = d->ld_row_table; g.rowtab_div = d->row_div > 0 ? d->row_div : 1; g.rowtab_cols = d->row_cols;
-  g.ln_out = d->ln_stats_out;
   g.colsum = w_colsum;
   FF_CHECK_ARG(!w_colsum || (ff_aligned16(w_colsum) && (row0 & 3) == 0), "ff_gemm_x3_ln: w_colsum must be 16-byte aligned, row0 %% 4 == 0");
   return x3_launch(g, d->ln_stats_in ? (w_colsum ? 3 : 1) : (d->ln_stats_out ? 2 : 0), (hipStream_t)stream);

@@ -10,6 +10,7 @@
 
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 // ---- library-level helpers ---------------------------------------------------------------------
 static thread_local char g_ff_error[512] = "";
@@ -22,9 +23,9 @@ void ff_set_error(const char* fmt, ...) {
 }
 
 int ff_num_cus() {
-  static std::atomic<int> cached[16] = {};
+  static std::atomic<int> cached[FF_MAX_DEVICES] = {};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FF_MAX_DEVICES) return 256;
   int n = cached[dev].load(std::memory_order_relaxed);
   if (n == 0) {
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;

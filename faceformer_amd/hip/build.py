@@ -45,7 +45,8 @@ def build(force=False, verbose=False):
 
 def _build(BUILD_DIR, LIB_PATH, FLAGS, force, verbose):
     os.makedirs(BUILD_DIR, exist_ok=True)
-    headers = [os.path.join(INCLUDE, "faceformer_hip.h"), os.path.join(CSRC, "ff_common.h"), os.path.join(CSRC, "ff_device.h")]
+    headers = [os.path.join(INCLUDE, "faceformer_hip.h"), os.path.join(CSRC, "ff_common.h"), os.path.join(CSRC, "ff_device.h"),
+               os.path.join(CSRC, "ff_launch.h")]
     hipcc = _hipcc()
     objs = []
     relink = force or not os.path.exists(LIB_PATH)

@@ -493,6 +493,40 @@ def test_gemm_x3_every_tile_and_launch_shape(ops, split_kind, x3_tuning, M, N, K
     assert rel_err(wide[:, :N], a.double() @ w.double().t() + bias.double()) < 3e-6
 
 
+def test_two_streams_keep_their_partial_tile_areas_apart(ops):
+    """The partial-tile areas are per (device, stream): a side stream runs the stream-K unit ranges (tile 6; 128 x 128 x 256 is
+    four tiles cut into eight two-unit ranges, so partial tiles go through the workspace) while the default stream runs the
+    3 x bf16 kernel's unit ranges at the same shape (16 one-unit blocks over two tiles), alternately and without a synchronise
+    in between.  Both forms sum in an order fixed by the grid: every overlapped result equals, bit for bit, the same call run
+    alone on the default stream (so it was with one registry per file, before csrc/ff_launch.h: that fixes the assertion)."""
+    M, N, K = 128, 128, 256
+    a, w, bias = rnd(M, K, seed=21).cuda(), rnd(N, K, seed=22, scale=0.1).cuda(), rnd(N, seed=23).cuda()
+    ref = (a.double() @ w.double().t() + bias.double()).cpu()
+    planes = ops.split_weight(w)
+    side = torch.cuda.Stream()
+    sk, x3 = [], []
+    ops.set_x3_tuning(2)
+    try:
+        torch.cuda.synchronize()
+        for _ in range(4):
+            with torch.cuda.stream(side):
+                sk.append(ops.linear(a, w, bias, tile=6))
+            x3.append(ops.linear_x3(a, planes, bias))
+        torch.cuda.synchronize()
+        sk_alone = ops.linear(a, w, bias, tile=6)
+        torch.cuda.synchronize()
+        x3_alone = ops.linear_x3(a, planes, bias)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_x3_tuning(0)
+    assert rel_err(sk_alone, ref) < 3e-6 and rel_err(x3_alone, ref) < 3e-6
+    for i in range(4):
+        print("iteration %d: stream-K max |diff| %.3g, 3 x bf16 max |diff| %.3g"
+              % (i, float((sk[i] - sk_alone).abs().max()), float((x3[i] - x3_alone).abs().max())))
+    assert all(torch.equal(o, sk_alone) for o in sk)
+    assert all(torch.equal(o, x3_alone) for o in x3)
+
+
 @pytest.mark.parametrize("M,N,K", [(37, 512, 512), (300, 512, 1024), (1300, 512, 512), (5000, 512, 512), (640, 128, 256),
                                    (9216, 512, 1024), (6400, 512, 512), (6656, 512, 1024)])
 def test_gemm_x3_emits_layernorm_segment_statistics(hip_lib, ops, split_kind, x3_tuning, M, N, K):
