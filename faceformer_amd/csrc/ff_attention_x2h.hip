@@ -56,10 +56,7 @@ template <int NT> constexpr int xk_lds_bytes() { return xk_lds_planes<NT>() + XK
 template <int NT> constexpr int xk_v_lds() { return NT == 1 ? XK_K_BYTES : 2 * XK_K_BYTES; }
 // Blocks per CU of the one-term kernel.  Two fit its LDS image, but they measured no faster than one (config B 33.13 vs 33.25 ms,
 // C128 2597 vs 2601 ms, inside the run-to-run spread: profiles/fp16/variants_ab.txt): one block, as the two-term kernel.
-#ifndef XK_H1_BLOCKS
-#define XK_H1_BLOCKS 1
-#endif
-template <int NT> constexpr int xk_blocks_per_cu() { return NT == 1 ? XK_H1_BLOCKS : 1; }
+template <int NT> constexpr int xk_blocks_per_cu() { return 1; }
 
 // x (two floats) -> packed fp16 pairs of the two terms (second term at 2^11)
 __device__ __forceinline__ void split_h2(float x0, float x1, unsigned& p1, unsigned& p2) {
@@ -291,7 +288,7 @@ int x2h_launch(const ff_attn_desc& d, const void* planes, long long plane_stride
   FF_RETURN_IF(ff_lds_limit_once(attention_x2h_kernel<NT>, xk_lds_bytes<NT>(), &attr_set));
   const long gh = (long)d.num_groups * d.num_heads;
   FF_CHECK_ARG(gh < 2147483647L, "ff_attention: too many (group, head) pairs");
-  // block slots: xk_blocks_per_cu per CU (one for both kernels, see XK_H1_BLOCKS)
+  // block slots: xk_blocks_per_cu per CU (one for both kernels)
   const int P = (int)gh, slots = ff_num_cus() * xk_blocks_per_cu<NT>(), qt32 = ff_cdiv(d.nq, 32);
   int c = P <= slots ? slots / P : 1;
   const int cmax = ff_cdiv(qt32, XK_NW);   // blocks beyond one query tile per wave are idle

@@ -123,8 +123,9 @@ int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, 
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);
 
-// partial-tile workspace of the 3 x bf16 kernel for (current device, stream): allocate now (ff_gemm_x3.hip)
-extern "C" int ff_x3_prepare_stream(hipStream_t st);
+// partial-tile workspace of the 3 x bf16 kernel for (current device, stream): allocate now (ff_gemm_x3.hip).  Called across
+// translation units only, so hidden: the library exports exactly the ff_* symbols of include/faceformer_hip.h
+extern "C" __attribute__((visibility("hidden"))) int ff_x3_prepare_stream(hipStream_t st);
 // ... and the same area as scratch memory for another kernel of that stream (at most 24 MB)
 int ff_stream_scratch(hipStream_t st, size_t bytes, float** out);
 

@@ -96,12 +96,8 @@ __device__ __forceinline__ void ff_gemm_small_tile(const GemmArgs& g, int tile, 
   // before anything is waited for; the row statistics (MODE 1) are merged ONCE per block -- wave w takes 32 / NW rows,
   // eight lanes per row, one 16-byte load each -- and handed round through LDS (every wave loading every row's
   // segments itself was half of the kernel's load requests).
-#ifndef FF_SMALL_V
-#define FF_SMALL_V 2
-#endif
-  constexpr int V = FF_SMALL_V;            // 1: all operand loads before the first MFMA; 2: groups of 4 k-groups, pipelined
   constexpr int NG = KQ / 8;               // 8-wide k groups per wave
-  constexpr int GB = (V == 1) ? (NG < 16 ? NG : 16) : (NG < 4 ? NG : 4);   // groups per batch
+  constexpr int GB = NG < 4 ? NG : 4;      // groups per batch: batches of 4 k-groups, pipelined (not all operand loads before the first MFMA)
   f32x4 a[2][GB], b[2][GB];
 #pragma unroll
   for (int j = 0; j < GB; ++j) {

@@ -31,51 +31,6 @@
 #include "ff_device.h"
 #include "ff_launch.h"
 
-// Timing experiment (tools/gemm_slice_probe.py, -DFF_EXP_STAMP): the four waves of workgroup 0 of the persistent kernel stamp
-// the shader clock in front of and behind the block barrier of their first 256 slices.
-#ifdef FF_EXP_STAMP
-__device__ unsigned long long ff_exp_stamps[4][256][2];
-#define FF_EXP_STAMP_PRE()                                                                          \
-  unsigned long long _t0 = 0;                                                                       \
-  if (blockIdx.x == 0 && _slice < 256) _t0 = __builtin_readcyclecounter();
-#define FF_EXP_STAMP_POST()                                                                         \
-  if (blockIdx.x == 0 && _slice < 256) {                                                            \
-    const unsigned long long _t1 = __builtin_readcyclecounter();                                    \
-    if (lane == 0) { ff_exp_stamps[wave][_slice][0] = _t0; ff_exp_stamps[wave][_slice][1] = _t1; }  \
-  }                                                                                                 \
-  ++_slice;
-extern "C" int ff_exp_read_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(ff_exp_stamps), sizeof(ff_exp_stamps)) == hipSuccess ? 0 : -1;
-}
-#else
-#define FF_EXP_STAMP_PRE()
-#define FF_EXP_STAMP_POST()
-#endif
-
-// Timing experiment (tools/panel_phase_probe.py, -DFF_EXP_PANEL_STAMP): workgroup 0 of gemm_panel_kernel stamps the shader
-// clock at entry, when its panels are in LDS, when the MFMA chains are done and after the stores were issued.
-#ifdef FF_EXP_PANEL_STAMP
-__device__ unsigned long long ff_exp_panel_stamps[8];
-extern "C" int ff_exp_read_panel_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(ff_exp_panel_stamps), sizeof(ff_exp_panel_stamps)) == hipSuccess ? 0 : -1;
-}
-#define FF_EXP_PSTAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ff_exp_panel_stamps[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define FF_EXP_PSTAMP(i) do { } while (0)
-#endif
-
-// Timing experiment (tools/streamk_probe.py, -DFF_EXP_SK_STAMP): block lb == 100 of gemm_streamk_kernel stamps the shader clock at
-// entry, around its hand-over (contributed partial tile) and around its fix-up (owned tile) and at its end.
-#ifdef FF_EXP_SK_STAMP
-__device__ unsigned long long ff_exp_sk_stamps[8];
-extern "C" int ff_exp_read_sk_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(ff_exp_sk_stamps), sizeof(ff_exp_sk_stamps)) == hipSuccess ? 0 : -1;
-}
-#define FF_EXP_SKSTAMP(i) do { if (lb == 100 && threadIdx.x == 0) ff_exp_sk_stamps[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define FF_EXP_SKSTAMP(i) do { } while (0)
-#endif
-
 namespace {
 
 
@@ -707,7 +662,7 @@ __device__ __forceinline__ void gemm_persist_body(const GemmArgs& g, int total_t
     // All values FIRST, then the stores back to back.  (With the store inside the loop each of its 16 guarded blocks began
     // with `s_waitcnt vmcnt(0)` -- the compiler re-establishes "bias / residual have arrived" in every block, and on gfx9 that
     // counter also counts the store issued by the block before: sixteen serialised write round trips, ~600 cycles each,
-    // 9.8 k cycles per tile against 2.0 k per K-slice: tools/gemm_slice_probe.py.)
+    // 9.8 k cycles per tile against 2.0 k per K-slice: profiles/r03/gemm_slice_probe.txt.)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const bool tab = MODE == 1 && g.rowtab != nullptr;   // a position table belongs INSIDE the activation
@@ -735,9 +690,6 @@ __device__ __forceinline__ void gemm_persist_body(const GemmArgs& g, int total_t
   read_frags(fa[0], fb[0], 0);
 
   int b0 = 0, b1 = 1, b2 = 2;
-#ifdef FF_EXP_STAMP
-  int _slice = 0;
-#endif
   // Outer loop over this block's tiles, inner loop over the K-slices of one tile (two per trip: static register-set
   // indices).  The software pipeline (staging registers, LDS ring, load cursor) runs across the tile boundary; only
   // the epilogue sits between two inner loops, so the hot loop body is one straight basic block.
@@ -752,9 +704,7 @@ __device__ __forceinline__ void gemm_persist_body(const GemmArgs& g, int total_t
         mfma_frags(fa[u], fb[u]);
         ff_persist_hints<MODE>();
         advance(true);
-        FF_EXP_STAMP_PRE();
         __syncthreads();
-        FF_EXP_STAMP_POST();
         { const int tmp = b0; b0 = b1; b1 = b2; b2 = tmp; }
       }
     }
@@ -832,7 +782,6 @@ __global__ __launch_bounds__(256) void gemm_streamk_kernel(GemmArgs g, StreamK s
   }
   const bool has_x = u0 < u1;
   if (!has_x && nmain == 0) return;
-  FF_EXP_SKSTAMP(0);
   const int k0 = has_x ? u0 / upt : 0, k1 = has_x ? (u1 - 1) / upt : 0;
   const int ja = u0 - k0 * upt;  // first unit of tile k0 in the range
   const int jb = has_x ? u1 - k1 * upt : upt;  // one past the last unit of tile k1 in the range (1..upt)
@@ -980,7 +929,6 @@ __global__ __launch_bounds__(256) void gemm_streamk_kernel(GemmArgs g, StreamK s
   // (sc1 accesses that bypass the non-coherent cache levels), ordered by vmcnt(0) + the block barrier
   // on the writer and by the data dependence on the flag on the reader.
   auto end_segment = [&]() {
-    FF_EXP_SKSTAMP(cp_kind == 1 ? 1 : (cp_kind == 2 ? 3 : 6));
     if (cp_kind == 1) {  // hand over the raw accumulators: slot[lb][4 quads][256 threads] float4
       // 16-byte write-through (sc1) stores: four fabric writes per thread instead of sixteen 4-byte ones (MI355X: a scalar
       // sc1 store is one fabric write whatever its width; inline asm: the compiler has no vector form of an agent-scope access)
@@ -994,7 +942,6 @@ __global__ __launch_bounds__(256) void gemm_streamk_kernel(GemmArgs g, StreamK s
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (tid == 0) __hip_atomic_store(sk.flags + lb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      FF_EXP_SKSTAMP(2);
       return;
     }
     if (cp_kind == 2) {  // add the partials of the blocks that hold units [k0 * upt, u0) of this tile
@@ -1016,7 +963,6 @@ __global__ __launch_bounds__(256) void gemm_streamk_kernel(GemmArgs g, StreamK s
       }
       __syncthreads();  // every thread is past its flag polls
       if (tid < lb - c0) __hip_atomic_store(sk.flags + c0 + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      FF_EXP_SKSTAMP(4);
     }
     float* cp = g.C + e_coff;
     float fin[16];
@@ -1076,7 +1022,6 @@ __global__ __launch_bounds__(256) void gemm_streamk_kernel(GemmArgs g, StreamK s
     end_segment();
     if (cp_p + 1 < nseg) begin_segment(cp_p + 1);
   }
-  FF_EXP_SKSTAMP(5);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -1180,7 +1125,6 @@ __global__ __launch_bounds__(512) void gemm_panel_kernel(GemmArgs g) {
   float* const lnrow = lds + 64 * LD;     // MODE 1: [32][2] (mean, rstd)
   float* const red = lds;                 // after the MFMA chain: [8][16][64] partial tiles (+ MODE 2 patch [32][33])
   static_assert(64 * LD >= NW * 16 * 64 + 32 * 33, "the partial tiles reuse the panel area");
-  FF_EXP_PSTAMP(0);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
   const int m0 = (blockIdx.x / g.tiles_n) * 32, n0 = (blockIdx.x % g.tiles_n) * 32;
   const long long bz = blockIdx.y;
@@ -1272,7 +1216,6 @@ __global__ __launch_bounds__(512) void gemm_panel_kernel(GemmArgs g) {
       }
     }
     __syncthreads();
-    FF_EXP_PSTAMP(1);
     // ---- wave w: columns [w KQ, w KQ + KQ) of the chunk; lane half h takes k = 8j + 4h .. +3 of every 8-wide group ----
     const float* fa = As + l32 * LD + wave * KQ + half * 4;
     const float* fb = Ws + l32 * LD + wave * KQ + half * 4;
@@ -1287,7 +1230,6 @@ __global__ __launch_bounds__(512) void gemm_panel_kernel(GemmArgs g) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j][c], b[j][c], acc, 0, 0, 0);
     __syncthreads();   // the panels are overwritten by the next chunk / the partial tiles
-    FF_EXP_PSTAMP(2);
   }
   // partial tiles -> LDS [wave][reg][lane]; wave w then finishes registers RPW*w .. RPW*w + RPW-1
 #pragma unroll
@@ -1312,11 +1254,9 @@ __global__ __launch_bounds__(512) void gemm_panel_kernel(GemmArgs g) {
     if (!tab) o[q] += rv[q];
     if (MODE == 2) patch[prow[q] * 33 + l32] = o[q];
   }
-  FF_EXP_PSTAMP(3);
 #pragma unroll
   for (int q = 0; q < RPW; ++q)
     if (colok && orow[q] < g.M) Cout[(size_t)orow[q] * g.ldc + ocol] = o[q];
-  FF_EXP_PSTAMP(4);
   if (MODE == 2) {  // row statistics of the finished 32x32 tile: 64 threads, (row, column half) each
     __syncthreads();
     if (tid < 64) {
@@ -1344,10 +1284,7 @@ int launch_panel(const GemmArgs& g, dim3 grid, hipStream_t st) {
   return FF_OK;
 }
 
-#ifndef FF_SMALL_WIDE_BLOCKS
-#define FF_SMALL_WIDE_BLOCKS 256
-#endif
-int g_small_wide_blocks = FF_SMALL_WIDE_BLOCKS;  // launches with at most this many tiles split K over eight waves instead of four
+constexpr int g_small_wide_blocks = 256;  // launches with at most this many tiles split K over eight waves instead of four
 
 inline int small_panel() { return ff_knob(FF_K_NO_PANEL) ? 0 : 1; }   // 1: launches of at most one tile per CU take gemm_panel_kernel (0: the eight-wave gemm_small_kernel)
 
@@ -1562,10 +1499,8 @@ extern "C" int ff_gemm_f32_batched(const float* A, int lda, const float* A2, int
   if (M == 0 || N == 0 || batch == 0) return FF_OK;
   FF_CHECK_ARG(M > 0 && N > 0 && K > 0 && (K & 3) == 0, "ff_gemm_f32: bad M=%d N=%d K=%d (K %% 4)", M, N, K);
   FF_CHECK_ARG(A && W && C, "ff_gemm_f32: null operand");
-#ifndef FF_EXP_NO_LD_CHECK   // (tools/gemm_latency_probe.py aliases all rows onto one: timing experiments only)
   FF_CHECK_ARG((lda & 3) == 0 && (ldw & 3) == 0 && lda >= K && ldw >= K && ldc >= N,
                "ff_gemm_f32: bad leading dimensions lda=%d ldw=%d ldc=%d", lda, ldw, ldc);
-#endif
   FF_CHECK_ARG(ff_aligned16(A) && ff_aligned16(W) && (!A2 || ff_aligned16(A2)),
                "ff_gemm_f32: A/A2/W must be 16-byte aligned");
   FF_CHECK_ARG(!residual || ldr >= N, "ff_gemm_f32: bad ldr");

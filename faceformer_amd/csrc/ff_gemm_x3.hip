@@ -40,16 +40,6 @@
 #include "ff_device.h"
 #include "ff_launch.h"
 
-// Timing experiment (tools/x3_phase_probe.py, -DX3_EXP_STAMP): wave 0 of workgroup 0 of gemm_x3_kernel sums, over its K-loop iterations,
-// the shader-clock time of (0) the MFMA block with everything placed in its gaps, (1) the wait for the DMA / fragment reads behind
-// it, (2) the segment-end branch + block barrier, (3) the rest of the iteration; [4] = iterations, [5] = whole kernel.
-#ifdef X3_EXP_STAMP
-__device__ unsigned long long ff_exp_x3_stamps[8];
-extern "C" int ff_exp_read_x3_stamps(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(ff_exp_x3_stamps), sizeof(ff_exp_x3_stamps)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -188,31 +178,15 @@ constexpr int X3_BN = 128, X3_BK = 16;
 // (3 x 2 x 32 = 192 matrix-core cycles per slice and wave against 6 x 64 / 16 x 64 of the bf16 / f32 loops; MFMA-busy 0.18-0.28
 // whatever the size) waits for its DMA: rings of four (plain forms, three blocks per CU) / five / six slots (the two-block
 // LayerNorm consumers) measured the same as three within the run-to-run noise (profiles/r06/x2h_loop_probes.txt), and so did
-// a loop that never waits for vmcnt -- the DMA round trip is covered.  Three slots stay; the depth is a build-time constant
-// for probes (tools/build_variant.sh ... -DX3_RING_H=4).
-#ifndef X3_RING_H
-#define X3_RING_H 3
-#endif
-#ifndef X3_RING_H1
-#define X3_RING_H1 3
-#endif
-#ifndef X3_RING_H3
-#define X3_RING_H3 3
-#endif
-#ifndef X3_RING_F32
-#define X3_RING_F32 3
-#endif
+// a loop that never waits for vmcnt -- the DMA round trip is covered (docs/EXPERIMENTS.md, round 6).  Three slots stay, for
+// every MODE of the bf16 and fp16x2 loops and for gemm_dma_f32_kernel.
+constexpr int X3_RING_F32 = 3;
 // One fp16 term (NT = 1, the opt-in split kind "fp16"): a slice is one 8 KB slot (4 KB of rows + 4 KB of ONE weight plane) and
 // two MFMAs per wave -- a third of the fp16x2 loop's matrix-core time per slice, so more slices must be in flight to cover the
 // same DMA round trip.  Measured in the fp16 decode (profiles/fp16/variants_ab.txt): three slots are 3.4 % (config B) / 3.6 % (C128)
 // slower than four, six the same as four within the run-to-run spread (+0.8 % / -0.6 %): four slots, 32 KB per block.
-#ifndef X3_RING_1
-#define X3_RING_1 4
-#endif
-template <int MODE, int NT>
-constexpr int x3_ring() {
-  return NT == 3 ? 3 : (NT == 1 ? X3_RING_1 : (MODE == 1 ? X3_RING_H1 : (MODE == 3 ? X3_RING_H3 : X3_RING_H)));
-}
+template <int NT>
+constexpr int x3_ring() { return NT == 1 ? 4 : 3; }
 constexpr int X3_STAT_BYTES = 16384;   // MODE 1: one 4 KB patch per wave (32 rows x 16 segments x (mean, M2))
 
 // BM: 128 (4 x 1 waves) or 64 (2 x 2 waves).  MODE: 0 plain, 1 LayerNorm consumer (rows normalised before the split),
@@ -224,14 +198,13 @@ constexpr int X3_STAT_BYTES = 16384;   // MODE 1: one 4 KB patch per wave (32 ro
 // the fp32 class (profiles/r06/fp16_split_error_table.txt; tests/test_hip_ops.py::test_gemm_x2h_*).  fp16 has 5 exponent
 // bits: |x| must stay below 65504, which the callers guarantee (LayerNorm output is bounded by sqrt(K); the engine checks the
 // norm bounds of the other operands when it binds the planes: faceformer_amd/hip/engine.py).
-#ifndef X3_LN_H_BLOCKS      // blocks per CU of the LayerNorm-consuming fp16 form (MODE 1, NT 2).  Round 6 tried 3 (168 registers, spills on the
-#define X3_LN_H_BLOCKS 2    // tile-change paths only; 52 KB of LDS each): +5 % on the isolated launch, -1.5 % on config B / C128 end to end -- stays at 2 (199 registers)
-#endif
+// Blocks per CU.  The LayerNorm-consuming fp16 form (MODE 1, NT 2): round 6 tried 3 (168 registers, spills on the tile-change
+// paths only; 52 KB of LDS each): +5 % on the isolated launch, -1.5 % on config B / C128 end to end -- stays at 2 (199 registers).
 // NT = 1: no second accumulator set and a third of the fragment registers, but FOUR blocks per CU (128 registers) do not fit:
 // the compiler spills 156-533 registers per form (MODE 0 / 2 / 3), inside the K loop.  At the other kinds' 168 / 256 registers
 // (three blocks; two for the LayerNorm consumers) the forms spill 0-19 registers -- outside the MFMA runs (tools/check_x3_asm.py).
 template <int MODE, int NT>
-constexpr int x3_blocks_per_cu() { return MODE == 3 ? 2 : (MODE == 1 ? (NT == 2 ? X3_LN_H_BLOCKS : 2) : 3); }
+constexpr int x3_blocks_per_cu() { return (MODE == 3 || MODE == 1) ? 2 : 3; }
 template <int BM, int MODE, int NT>
 __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_kernel(X3Args g) {   // (MODE 3 with two terms at three blocks per CU: 368 B of scratch, 10 accesses inside the MFMA runs -- stays at two)
   constexpr int BN = X3_BN, BK = X3_BK;
@@ -240,7 +213,7 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
   constexpr int NPA = BM / 64;              // A pieces (16 rows x 64 B) per wave and slice
   constexpr int NP = NPA + NT;              // DMA pieces per wave and slice
   constexpr int A_REG = BM * 64, SLOT = A_REG + NT * BN * 32;
-  constexpr int RING = x3_ring<MODE, NT>();
+  constexpr int RING = x3_ring<NT>();
   constexpr int NPROD = NT == 3 ? 6 : (NT == 2 ? 3 : 1);    // partial products per fp32 product
   constexpr int NMF = NPROD * NI;           // MFMAs per wave and slice
   constexpr int NRD = 2 + NT * NI;          // fragment reads per wave and slice
@@ -289,9 +262,6 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
     u1 = u0 + (g.base + mine) * g.gran;
   }
   if (u0 >= u1) return;
-#if defined(X3_EXP_STAGGER)         // probe: blocks start in three phases, X3_EXP_STAGGER x 0.85 us apart (de-phases the tile ends -- and with
-  for (int q = 0; q < (int)(blockIdx.x % 3) * X3_EXP_STAGGER; ++q) __builtin_amdgcn_s_sleep(32);   // them the chip-wide bursts of result stores)
-#endif
   const int k0 = u0 / upt, k1 = (u1 - 1) / upt;
   const int ja = u0 - k0 * upt;
   const int jb = u1 - k1 * upt;
@@ -343,13 +313,6 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
   };
   auto issue_piece = [&](int k, int slot) {   // piece k of the slice the loader stands on -> ring slot `slot`
     unsigned char* base = lds + slot * SLOT;
-#if defined(X3_EXP_NODMA)          // probe: the loop without its operand traffic (computes on whatever the LDS holds)
-    if (g.M > 0) return;
-#elif defined(X3_EXP_NODMA_A)      // probe: ... without the activation pieces only
-    if (k < NPA) return;
-#elif defined(X3_EXP_NODMA_W)      // probe: ... without the weight pieces only
-    if (k >= NPA) return;
-#endif
     if (k < NPA) {
       __builtin_amdgcn_global_load_lds(a_base + a_off[k < NPA ? k : 0], X3_LDS_PTR(base + (wave * NPA + k) * 1024), 16, 0, 0);
     } else {
@@ -358,9 +321,6 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
     }
   };
   auto advance = [&]() {
-#if defined(X3_EXP_NOADVANCE)      // probe: the loader stays on its first slice (no pointer / segment bookkeeping per slice)
-    if (g.M > 0) return;
-#endif
     if (++ld_j == ld_end) {
       if (ld_p + 1 < nseg) {
         int tile, j0, n, kind;
@@ -469,34 +429,18 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
         asm volatile("" : "+v"(p1_[q]));
         return;
       }
-      if (NT == 2) {     // fp16 terms: x1 = fp16(x) (round to nearest), residual exact in fp32
+      if (NT == 2) {     // fp16 terms: x1 = fp16(x) (round to nearest), residual exact in fp32.  (A cheaper split with one
+                         // v_fma_mix{lo,hi}_f16 per second term gave the same bits and no speed-up: docs/EXPERIMENTS.md, round 6.)
         if (MODE == 3) {   // RAW (un-normalised) rows: 2^-6 keeps |x| up to 4.2e6 inside fp16's range (undone, exactly, per tile)
           x0 = x3_fmul(x0, 0.015625f);
           x1 = x3_fmul(x1, 0.015625f);
         }
-#if defined(X3_EXP_NOSPLIT)      // probe: no split arithmetic at all (wrong numbers; the upper bound of what cheaper splitting can buy)
-        p1_[q] = __builtin_bit_cast(unsigned, x0);
-        r_[q][0] = x1; r_[q][1] = x0;
-        asm volatile("" : "+v"(p1_[q]), "+v"(r_[q][0]), "+v"(r_[q][1]));
-        return;
-#elif defined(X3_MIXSPLIT)
-        // x1 = fp16(x) (one packed conversion); the scaled inputs t = x 2^11 (exact); the second terms then are ONE mixed-precision
-        // fma each, fp16(fma(x1, -2^11, t)) = fp16((x - x1) 2^11) -- fma's argument is exact in fp32, so the bits are those of the
-        // five-instruction form (convert back, subtract, scale, convert) at five VALU per pair instead of eight
-        const f16x2 h = __builtin_convertvector(f32x2{x0, x1}, f16x2);
-        p1_[q] = __builtin_bit_cast(unsigned, h);
-        r_[q][0] = x3_fmul(x0, 2048.0f);
-        r_[q][1] = x3_fmul(x1, 2048.0f);
-        asm volatile("" : "+v"(p1_[q]), "+v"(r_[q][0]), "+v"(r_[q][1]));
-        return;
-#else
         const f16x2 h = __builtin_convertvector(f32x2{x0, x1}, f16x2);
         p1_[q] = __builtin_bit_cast(unsigned, h);
         r_[q][0] = x3_fsub(x0, (float)h[0]);
         r_[q][1] = x3_fsub(x1, (float)h[1]);
         asm volatile("" : "+v"(p1_[q]), "+v"(r_[q][0]), "+v"(r_[q][1]));
         return;
-#endif
       }
       p1_[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
       r_[q][0] = x3_fsub(x0, __builtin_bit_cast(float, p1_[q] << 16));
@@ -504,21 +448,8 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
       asm volatile("" : "+v"(p1_[q]), "+v"(r_[q][0]), "+v"(r_[q][1]));
     } else if (NT == 1) {   // (nothing: one term)
     } else if (NT == 2) {   // second term, scaled by 2^11 (exact)
-#if defined(X3_EXP_NOSPLIT)
-      p2_[q] = __builtin_bit_cast(unsigned, r_[q][0]);
-      asm volatile("" : "+v"(p2_[q]));
-#elif defined(X3_MIXSPLIT)
-      unsigned d;
-      const float m2048 = -2048.0f;
-      asm volatile("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]\n\t"
-                   "v_fma_mixhi_f16 %0, %1, %2, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                   : "=&v"(d) : "v"(p1_[q]), "v"(m2048), "v"(r_[q][0]), "v"(r_[q][1]));
-      p2_[q] = d;
-      asm volatile("" : "+v"(p2_[q]));
-#else
       p2_[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x3_fmul(r_[q][0], 2048.0f), x3_fmul(r_[q][1], 2048.0f)}, f16x2));
       asm volatile("" : "+v"(p2_[q]));
-#endif
     } else {
       p2_[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r_[q][0], r_[q][1]}, bf16x2));
       const float s0 = x3_fsub(r_[q][0], __builtin_bit_cast(float, p2_[q] << 16));
@@ -647,10 +578,8 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
         xv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         bv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         cv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if !defined(X3_EXP_NOEPILOAD)      // probe: the epilogue without its bias / residual / table loads (wrong numbers)
         if (xrow && n + 3 < xlim) xv[j] = gload16(xrow + n);
         if (g.bias && n + 3 < g.N) bv[j] = gload16(g.bias + n);
-#endif
         if (MODE == 3 && n + 3 < g.N) cv[j] = gload16(g.colsum + g.w_row0 + n);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -715,14 +644,7 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
       for (int q = 0; q < NQ; ++q)
         if (nb0 + (q >> 2) * 32 + (q & 3) * 8 + 3 < g.N) {
           const f32x4 v = {acc[q >> 2][4 * (q & 3)], acc[q >> 2][4 * (q & 3) + 1], acc[q >> 2][4 * (q & 3) + 2], acc[q >> 2][4 * (q & 3) + 3]};
-#if defined(X3_EXP_NOSTORE)        // probe: results are not stored (one store per lane and tile keeps the accumulators alive)
-          if (q == 0)
-#endif
-#if defined(X3_EXP_NTSTORE)        // probe: non-temporal result stores
-          asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(cp + (q >> 2) * 32 + (q & 3) * 8), "v"(v) : "memory");
-#else
           asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(cp + (q >> 2) * 32 + (q & 3) * 8), "v"(v) : "memory");
-#endif
         }
     }
 #pragma unroll
@@ -775,18 +697,9 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
   constexpr int DM0 = NI == 4 ? NRD : NG - NP;    // first DMA piece
   int s0 = 0, s1 = 1;   // ring slots of slice s, s + 1  (slice s + RING goes to slot s0)
   const int total = 2 * (u1 - u0);
-#ifdef X3_EXP_STAMP
-  const bool stamping = blockIdx.x == 0 && wave == 0;
-  unsigned long long st_d[4] = {0, 0, 0, 0}, st_n = 0, st_t3 = 0;
-  const unsigned long long st_begin = __builtin_readcyclecounter();
-#endif
   for (int s = 0; s < total; s += 2) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-#ifdef X3_EXP_STAMP
-      unsigned long long st_t0 = 0, st_t1 = 0, st_t2 = 0;
-      if (stamping) { st_t0 = __builtin_readcyclecounter(); if (st_n) st_d[3] += st_t0 - st_t3; }
-#endif
       const unsigned nb = lds0 + s1 * SLOT;   // slot of slice s + 1
       if (MODE == 1) {   // the rows split in this iteration belong to the next segment's tile when this is the segment's last slice
         const bool nx = cp_cnt + 1 == cp_n;
@@ -795,11 +708,7 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
       // NMF MFMAs of slice s; in their gaps: the reads of slice s + 1 (one per gap), the split of its rows, the DMA of s + 3
 #pragma unroll
       for (int i = 0; i < NG; ++i) {
-#if defined(X3_EXP_MFMA_ORDER)     // probe: the x1 y1 products between the two small ones (same-accumulator MFMAs four apart, not two)
-        const int t = NT == 2 ? (i / NI == 1 ? 2 : (i / NI == 2 ? 1 : 0)) : i / NI, ni = i % NI;
-#else
         const int t = i / NI, ni = i % NI;
-#endif
         if (NT == 1) {     // one product per slice and column tile: a single accumulator chain
           if (i < NMF) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[u][0][ni]),
                                                                         __builtin_bit_cast(f16x8, af[u][0]), acc[ni], 0, 0, 0);
@@ -809,23 +718,14 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
           else acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[u][PB[t]][ni]),
                                                                  __builtin_bit_cast(bf16x8, af[u][PA[t]]), acc[ni], 0, 0, 0);
         } else {
-#if defined(X3_EXP_NOMFMA)         // probe: the loop without its matrix-core work
-          if (g.M < 0)
-#endif
           if (t < 2) accs[ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[u][PB[t]][ni]),
                                                                        __builtin_bit_cast(f16x8, af[u][PA[t]]), accs[ni], 0, 0, 0);
           else acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[u][PB[t]][ni]),
                                                                 __builtin_bit_cast(f16x8, af[u][PA[t]]), acc[ni], 0, 0, 0);
         }
-#if defined(X3_EXP_NOLDSREAD)       // probe: no fragment reads in the loop (both register sets keep the prologue's values)
-        if (g.M < 0) {
-#else
-        {
-#endif
         if (i == 0) ar[0] = x3_lds_read16(nb + fa_r0);
         else if (i == 1) ar[1] = x3_lds_read16(nb + fa_r1);
         else if (i < NRD) x3_read_w_i<NI>(wf[u ^ 1], nb + fw, i - 2);
-        }
         if (i == SP0) {
           if (SP0 == 5) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(ar[0]), "+v"(ar[1])::"memory");
           else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ar[0]), "+v"(ar[1])::"memory");
@@ -841,22 +741,12 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
         __builtin_amdgcn_sched_barrier(0);
       }
       if (SPC >= NG) split_collect(af[u ^ 1]);
-#ifdef X3_EXP_STAMP
-      if (stamping) st_t1 = __builtin_readcyclecounter();
-#endif
       // slice s + 2 has landed (own pieces), every fragment of slice s + 1 is in registers
-#if defined(X3_EXP_NOVMWAIT)      // probe: the loop never waits for its DMA (reads whatever the LDS holds)
-      __builtin_amdgcn_s_waitcnt(0x0F70 & ~0x0F00);   // lgkmcnt(0) only
-#else
       __builtin_amdgcn_s_waitcnt(0x0070 | ((RING - 2) * NP));   // vmcnt: everything but the youngest RING - 2 slices; lgkmcnt(0)
-#endif
 #pragma unroll
       for (int p = 0; p < NT; ++p)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) asm volatile("" : "+v"(wf[u ^ 1][p][ni]));
-#ifdef X3_EXP_STAMP
-      if (stamping) st_t2 = __builtin_readcyclecounter();
-#endif
       if (++cp_cnt == cp_n) {  // block-uniform: the last slice of the segment was just issued
         end_segment();
         if (++cp_p < nseg) begin_segment(cp_p);
@@ -886,26 +776,10 @@ __global__ __launch_bounds__(256, (x3_blocks_per_cu<MODE, NT>())) void gemm_x3_k
           stats_fetch(cp_p + 2);
         }
       }
-#if defined(X3_EXP_NOBARRIER)     // probe: no block barrier in the K loop (races: wrong numbers)
-#elif defined(X3_EXP_HALFBARRIER) // probe: a barrier every second slice only
-      if (u == 1) __builtin_amdgcn_s_barrier();
-#else
       __builtin_amdgcn_s_barrier();
-#endif
-#if !defined(X3_EXP_FIXEDSLOT)      // probe: without the ring rotation (slot offsets become loop constants)
       s0 = s1; s1 = s1 + 1 == RING ? 0 : s1 + 1;
-#endif
-#ifdef X3_EXP_STAMP
-      if (stamping) { st_t3 = __builtin_readcyclecounter(); st_d[0] += st_t1 - st_t0; st_d[1] += st_t2 - st_t1; st_d[2] += st_t3 - st_t2; ++st_n; }
-#endif
     }
   }
-#ifdef X3_EXP_STAMP
-  if (stamping && lane == 0) {
-    for (int q = 0; q < 4; ++q) ff_exp_x3_stamps[q] = st_d[q];
-    ff_exp_x3_stamps[4] = st_n; ff_exp_x3_stamps[5] = __builtin_readcyclecounter() - st_begin;
-  }
-#endif
 }
 
 // ---- the same launch structure on the f32 matrix cores ------------------------------------------------------------------------
@@ -973,9 +847,6 @@ __global__ __launch_bounds__(256, 3) void gemm_dma_f32_kernel(X3Args g) {
     u1 = u0 + (g.base + mine) * g.gran;
   }
   if (u0 >= u1) return;
-#if defined(X3_EXP_STAGGER)         // probe: blocks start in three phases, X3_EXP_STAGGER x 0.85 us apart (de-phases the tile ends -- and with
-  for (int q = 0; q < (int)(blockIdx.x % 3) * X3_EXP_STAGGER; ++q) __builtin_amdgcn_s_sleep(32);   // them the chip-wide bursts of result stores)
-#endif
   const int k0 = u0 / upt, k1 = (u1 - 1) / upt;
   const int ja = u0 - k0 * upt;
   const int jb = u1 - k1 * upt;
@@ -1027,9 +898,6 @@ __global__ __launch_bounds__(256, 3) void gemm_dma_f32_kernel(X3Args g) {
   };
   auto issue_piece = [&](int k, int slot) {   // piece k of the slice the loader stands on -> ring slot `slot`
     unsigned char* base = lds + slot * SLOT;
-#if defined(X3_EXP_NODMA)          // probe (see gemm_x3_kernel)
-    if (g.M > 0) return;
-#endif
     if (k < NPA) {
       __builtin_amdgcn_global_load_lds(a_base + a_off[k < NPA ? k : 0], X3_LDS_PTR(base + (wave * NPA + k) * 1024), 16, 0, 0);
     } else {
@@ -1247,10 +1115,8 @@ __global__ __launch_bounds__(256, 3) void gemm_dma_f32_kernel(X3Args g) {
         xv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         bv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         cv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if !defined(X3_EXP_NOEPILOAD)      // probe: the epilogue without its bias / residual / table loads (wrong numbers)
         if (xrow && n + 3 < xlim) xv[j] = gload16(xrow + n);
         if (g.bias && n + 3 < g.N) bv[j] = gload16(g.bias + n);
-#endif
         if (MODE == 3 && n + 3 < g.N) cv[j] = gload16(g.colsum + g.w_row0 + n);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1303,14 +1169,7 @@ __global__ __launch_bounds__(256, 3) void gemm_dma_f32_kernel(X3Args g) {
       for (int q = 0; q < NQ; ++q)
         if (nb0 + (q >> 2) * 32 + (q & 3) * 8 + 3 < g.N) {
           const f32x4 v = {acc[q >> 2][4 * (q & 3)], acc[q >> 2][4 * (q & 3) + 1], acc[q >> 2][4 * (q & 3) + 2], acc[q >> 2][4 * (q & 3) + 3]};
-#if defined(X3_EXP_NOSTORE)        // probe: results are not stored (one store per lane and tile keeps the accumulators alive)
-          if (q == 0)
-#endif
-#if defined(X3_EXP_NTSTORE)        // probe: non-temporal result stores
-          asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(cp + (q >> 2) * 32 + (q & 3) * 8), "v"(v) : "memory");
-#else
           asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(cp + (q >> 2) * 32 + (q & 3) * 8), "v"(v) : "memory");
-#endif
         }
     }
 #pragma unroll
@@ -1372,9 +1231,6 @@ __global__ __launch_bounds__(256, 3) void gemm_dma_f32_kernel(X3Args g) {
 #pragma unroll
       for (int i = 0; i < NMF; ++i) {
         const int e = i / NI, ni = i % NI;
-#if defined(X3_EXP_NOMFMA)
-        if (g.M < 0)
-#endif
         acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(__builtin_bit_cast(f32x4, wf[u][e >> 2][ni])[e & 3],
                                                        __builtin_bit_cast(f32x4, af[u][e >> 2])[e & 3], acc[ni], 0, 0, 0);
         if (i == 0) af[u ^ 1][0] = x3_lds_read16(nb + fa_r0);
@@ -1443,10 +1299,7 @@ FFSetting g_x3_force_shape{{0}};
 template <int BM, int MODE, int NT = 3>
 int x3_launch_mode(const X3Args& g, int grid, hipStream_t st) {
   static FFLdsLimit attr_set = {};
-#ifndef X3_EXP_LDS_PAD     // probe: extra dynamic LDS per block = fewer blocks per CU (occupancy experiments)
-#define X3_EXP_LDS_PAD 0
-#endif
-  constexpr int bytes = x3_ring<MODE, NT>() * (BM * 64 + NT * X3_BN * 32) + (MODE == 1 ? X3_STAT_BYTES : 0) + X3_EXP_LDS_PAD;
+  constexpr int bytes = x3_ring<NT>() * (BM * 64 + NT * X3_BN * 32) + (MODE == 1 ? X3_STAT_BYTES : 0);
   FF_RETURN_IF(ff_lds_limit_once(&gemm_x3_kernel<BM, MODE, NT>, bytes, &attr_set));
   hipLaunchKernelGGL((gemm_x3_kernel<BM, MODE, NT>), dim3(grid), dim3(256), bytes, st, g);
   FF_CHECK_LAUNCH();

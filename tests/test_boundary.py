@@ -198,6 +198,32 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert hip_lib.ff_device_count() >= 0
 
 
+def test_library_exports_only_the_declared_ff_symbols(hip_lib):
+    """The defined dynamic ff_* symbols of the built library are exactly lib.SIGNATURES (= the header's declarations, see above):
+    a helper shared between translation units has hidden visibility, and no probe reader is left in the product."""
+    import shutil
+    import subprocess
+    from faceformer_amd.hip import lib
+    nm = shutil.which("nm") or next((p for p in (shutil.which("llvm-nm"), "/opt/rocm/llvm/bin/llvm-nm", "/opt/rocm/lib/llvm/bin/llvm-nm")
+                                     if p and os.path.exists(p)), None)
+    assert nm, "neither nm nor ROCm's llvm-nm found: the library cannot have been built without ROCm"
+    out = subprocess.run([nm, "-D", "--defined-only", lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()}
+    exported = {s for s in exported if s.startswith("ff_")}
+    assert exported == set(lib.SIGNATURES), sorted(exported ^ set(lib.SIGNATURES))
+
+
+def test_kernel_sources_have_no_preprocessor_conditionals():
+    """No build-time switches in csrc/ (DESIGN.md section 9): the product is the only reading of a kernel; the headers use #pragma once."""
+    pat = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b")
+    hits = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "faceformer_amd", "csrc", "*"))):
+        for i, line in enumerate(open(path), 1):
+            if pat.match(line):
+                hits.append("%s:%d" % (os.path.relpath(path, ROOT), i))
+    assert not hits, "preprocessor conditionals in the kernel sources: " + ", ".join(hits)
+
+
 def test_struct_layouts_match_the_header(hip_lib):
     """ctypes mirrors vs. the compiler's layout, via a tiny C probe compiled with gcc."""
     import shutil
@@ -241,6 +267,9 @@ def test_entry_points_reject_bad_arguments_without_touching_the_device(hip_lib):
     assert b"K" in hip_lib.ff_last_error()
     assert hip_lib.ff_gemm_f32(None, 8, None, 0, p, 8, None, None, 0, p, 8, 2, 2, 8, 0, 0, None) == FF_ERR_ARG
     assert hip_lib.ff_gemm_f32(p, 8, None, 0, p, 8, None, None, 0, p, 8, 2, 2, 8, 0, 99, None) == FF_ERR_ARG
+    # a leading dimension below K
+    assert hip_lib.ff_gemm_f32(p, 4, None, 0, p, 8, None, None, 0, p, 8, 2, 2, 8, 0, 0, None) == FF_ERR_ARG
+    assert b"leading dimensions" in hip_lib.ff_last_error()
     # empty problems are a no-op, not an error
     assert hip_lib.ff_gemm_f32(p, 8, None, 0, p, 8, None, None, 0, p, 8, 0, 2, 8, 0, 0, None) == 0
     # LayerNorm width must be a multiple of 4; attention needs its tensors
