@@ -120,6 +120,19 @@ int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, 
                            float* next_rows, int ldnext, int* count_ge, int ge_bound, int* count_eq, int eq_value,
                            const ff_pointer_sync* sync, ff_stream_t stream);   // logprob: [B] or null (ff_pointer_argmax_lp)
 
+// ff_beam_select with the decode engine's hand-over (ff_beam.hip): next_stats as above; arrive counts the launch's GROUPS, the
+// last block stores count_ge to host_slot.  And the start state / output packing of a beam decode (kernels' comments).
+int ff_beam_select_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int groups, int width,
+                        int groups_per_wireframe, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
+                        int* hist, int ldhist, int t, int* parent, int* next_tok, int term_lo, int term_hi, const float* memory,
+                        int E, float* next_rows, int ldnext, int* count_ge, int ge_bound, float* next_stats, int* arrive,
+                        int* host_slot, ff_stream_t stream);
+int ff_beam_init(int* tok, float* score, int* fin, int* parent, int Bc, int Fc, int W, int f0, const int* num_input, int pad_tok,
+                 int term_lo, int term_hi, hipStream_t st);
+int ff_beam_finalize(const int* tok, const int* parent, const float* score, int Btot, int T, const int* steps_dev,
+                     const int* num_input, int dedup, int F, int W, int w0, int nw, int Fc, int f0, int b0, int64_t* beams,
+                     float* scores, int64_t* predict, int* seq_of_row, hipStream_t st);
+
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);
 

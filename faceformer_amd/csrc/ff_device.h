@@ -745,8 +745,11 @@ __device__ __forceinline__ float ff_lse_merge(float m, float s, float om, float 
 // Masked keys hold -FLT_MAX: exp(-FLT_MAX - max) = 0, and a row of masked keys only sums S ones (-log S, torch's value).
 // __expf (v_exp_f32 of x log2(e)): ~2 ulp on the terms near 1, which carry the sum; the argument's rounding grows with |x| as
 // the term vanishes.  One accurate logf per row.
+// The reduction proper is ff_pointer_mask_reduce (also the first half of a beam-search step, ff_beam.hip), the feedback gather
+// ff_pointer_append_row; ff_pointer_reduce_row is the two with the greedy decode's stores between them.
 template <bool LP>
-__device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b, int lane) {
+__device__ __forceinline__ void ff_pointer_mask_reduce(const PointerArgs& a, int b, int lane, float* b1_out, float* b2_out,
+                                                       int* i1_out, float* lsum_out) {
   const int w = b / a.spg;
   int kv = a.S;
   if (a.kv_len) { const int k = ff_ldw(a.kv_len + w); kv = k < kv ? k : kv; }
@@ -787,36 +790,48 @@ __device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b
     b2 = nb2;
   }
   if (i1 == 0x7fffffff) { i1 = 0; b1 = FILL; }
+  *b1_out = b1; *b2_out = b2; *i1_out = i1; *lsum_out = lsum;
+}
+
+// Row i1 of wireframe w's memory appended as launch row b of next_rows, with its LayerNorm segment statistics when asked for.
+__device__ __forceinline__ void ff_pointer_append_row(const PointerArgs& a, int w, int b, int i1, int lane) {
+  const float* src = a.memory + ((size_t)w * a.S + i1) * a.E;
+  float* dst = a.next_rows + (size_t)b * a.ldnext;
+  if (!a.next_stats) {
+    for (int vi = lane; vi < (a.E >> 2); vi += 64)
+      ff_st16(dst + vi * 4, ff_ldw16(src + vi * 4));
+  } else {
+    // the same copy, leaving (mean, M2) of every 32-column segment of the row (two passes like the LayerNorm kernel and the
+    // statistics-producing GEMM epilogue): a segment is the 8 float4 of 8 consecutive lanes
+    float* sdst = a.next_stats + (size_t)b * (a.E >> 5) * 2;
+    for (int v0 = 0; v0 < (a.E >> 2); v0 += 64) {      // (wave-uniform bound: the shuffles below need every lane)
+      const int vi = v0 + lane;
+      const bool in = vi < (a.E >> 2);
+      f32x4 x = {0.f, 0.f, 0.f, 0.f};
+      if (in) { x = ff_ldw16(src + vi * 4); ff_st16(dst + vi * 4, x); }
+      float sm = (x.x + x.y) + (x.z + x.w);
+      sm += __shfl_xor(sm, 1, FF_WAVE); sm += __shfl_xor(sm, 2, FF_WAVE); sm += __shfl_xor(sm, 4, FF_WAVE);
+      const float mean = sm * (1.0f / 32.0f);
+      const float d0 = x.x - mean, d1 = x.y - mean, d2 = x.z - mean, d3 = x.w - mean;
+      float m2 = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+      m2 += __shfl_xor(m2, 1, FF_WAVE); m2 += __shfl_xor(m2, 2, FF_WAVE); m2 += __shfl_xor(m2, 4, FF_WAVE);
+      if (in && (lane & 7) == 0) ff_st8(sdst + (vi >> 3) * 2, f32x2{mean, m2});
+    }
+  }
+}
+
+template <bool LP>
+__device__ __forceinline__ int ff_pointer_reduce_row(const PointerArgs& a, int b, int lane) {
+  float b1, b2, lsum;
+  int i1;
+  ff_pointer_mask_reduce<LP>(a, b, lane, &b1, &b2, &i1, &lsum);
+  const int seq = ff_pointer_seq(a, b);
   if (lane == 0) {
     ff_st4i(a.next_tok + seq, i1);
     if (a.best) ff_st4(a.best + seq, b1);
     if (a.second) ff_st4(a.second + seq, b2);
     if (LP) ff_st4(a.logprob + seq, -logf(lsum));
   }
-  if (a.next_rows) {
-    const float* src = a.memory + ((size_t)w * a.S + i1) * a.E;
-    float* dst = a.next_rows + (size_t)b * a.ldnext;
-    if (!a.next_stats) {
-      for (int vi = lane; vi < (a.E >> 2); vi += 64)
-        ff_st16(dst + vi * 4, ff_ldw16(src + vi * 4));
-    } else {
-      // the same copy, leaving (mean, M2) of every 32-column segment of the row (two passes like the LayerNorm kernel and the
-      // statistics-producing GEMM epilogue): a segment is the 8 float4 of 8 consecutive lanes
-      float* sdst = a.next_stats + (size_t)b * (a.E >> 5) * 2;
-      for (int v0 = 0; v0 < (a.E >> 2); v0 += 64) {      // (wave-uniform bound: the shuffles below need every lane)
-        const int vi = v0 + lane;
-        const bool in = vi < (a.E >> 2);
-        f32x4 x = {0.f, 0.f, 0.f, 0.f};
-        if (in) { x = ff_ldw16(src + vi * 4); ff_st16(dst + vi * 4, x); }
-        float sm = (x.x + x.y) + (x.z + x.w);
-        sm += __shfl_xor(sm, 1, FF_WAVE); sm += __shfl_xor(sm, 2, FF_WAVE); sm += __shfl_xor(sm, 4, FF_WAVE);
-        const float mean = sm * (1.0f / 32.0f);
-        const float d0 = x.x - mean, d1 = x.y - mean, d2 = x.z - mean, d3 = x.w - mean;
-        float m2 = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        m2 += __shfl_xor(m2, 1, FF_WAVE); m2 += __shfl_xor(m2, 2, FF_WAVE); m2 += __shfl_xor(m2, 4, FF_WAVE);
-        if (in && (lane & 7) == 0) ff_st8(sdst + (vi >> 3) * 2, f32x2{mean, m2});
-      }
-    }
-  }
+  if (a.next_rows) ff_pointer_append_row(a, b / a.spg, b, i1, lane);
   return i1;
 }

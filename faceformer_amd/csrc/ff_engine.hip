@@ -18,6 +18,11 @@
 // slot[i] (a chunk-local index of the plan above; tokens, traces, extra-mask rows and finish positions stay in that original
 // order) -- and every sync_every steps the host drops the finished sequences from it (compact_chunks below).  The slots of a
 // chunk keep the w = i / Fc structure with a smaller Fc, so attention, masks and kv_len are addressed as before.
+//
+// Beam decode (ff_decode_beam, opt-in, parallel variant): the same run with W sequences per anchor -- beam k of
+// compact anchor a is chunk-local sequence a * W + k, so a chunk's Fc / Bc are W times its anchor counts and w = i / Fc holds.
+// A step's pointer launch is replaced by ff_beam_select (+ ff_beam_reorder of the x0 / qkv0 prefixes); every step leaves its
+// (token, parent, score, finished) row in the workspace and the output is packed from those rows behind the stop step.
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
@@ -227,6 +232,9 @@ struct DecodeBuffers {
   int *cnt_tot;           // [T] per-step totals (steps_kernel)
   int *steps_dev;
   int *fin, *slot_all, *perm_all;   // FF_RETIRE_FINISHED: finish positions [Btot] (when not host-mapped), slot maps [Btot]
+  // beam decode: [T, Btot] each, row s = the beams' state after s steps (row 0: the start state); the tokens are tok_all's rows
+  float* bm_score;
+  int *bm_fin, *bm_parent;
 };
 
 // A micro-batch is a contiguous range [b0, b0 + Bc) of the COMPACT sequence index: nw >= 1 consecutive
@@ -234,6 +242,7 @@ struct DecodeBuffers {
 // padding-anchor de-duplication the compact width of every wireframe is F and b = w*F + f as in the reference.
 struct Chunk {
   int w0, nw, Fc, f0, b0, Bc, sid;
+  // (beam decode: Fc, b0, Bc, Fl, Bl count beams -- W per anchor; f0 stays the chunk's first compact ANCHOR)
   int Fl, Bl;    // FF_RETIRE_FINISHED: slots per wireframe / in all of the chunk now (Bl = nw * Fl <= Bc; 0: nothing left)
   int *slot, *perm;   // ... device [Bc]: chunk-local sequence of every slot; the compaction's gather indices
   float* x0;     // [T, Bc, E]
@@ -299,6 +308,19 @@ void plan_chunks(const ff_decode_params* p, const int* num_input_host, int ns, s
   if (nchunks) *nchunks = nc;
 }
 
+// The plan of a beam decode: plan_chunks over the anchors (its sequence limits divided by W), every chunk W times as wide.
+void plan_beam_chunks(const ff_decode_params* p, const int* num_input_host, int ns, int W, std::vector<Chunk>* out, int* btot,
+                      int* max_bc, int* nchunks = nullptr) {
+  ff_decode_params q = *p;
+  if (q.chunk_max_seqs > 0) q.chunk_max_seqs = q.chunk_max_seqs / W > 1 ? q.chunk_max_seqs / W : 1;
+  if (q.chunk_seqs > 0) q.chunk_seqs = q.chunk_seqs / W > 1 ? q.chunk_seqs / W : 1;
+  plan_chunks(&q, num_input_host, ns, out, btot, max_bc, nchunks);
+  if (out)
+    for (Chunk& c : *out) { c.Fc *= W; c.b0 *= W; c.Bc *= W; c.Fl *= W; c.Bl *= W; }
+  *btot *= W;
+  *max_bc *= W;
+}
+
 int plan_streams(const ff_decode_params* p) {
   return p->num_streams < 1 ? 1 : (p->num_streams > FF_MAX_STREAMS ? FF_MAX_STREAMS : p->num_streams);
 }
@@ -338,8 +360,9 @@ bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
 
 // Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
 // want_lp: also the log-probability rows (ff_decode_lp) -- taken LAST, so that everything else lies where it lies without them.
+// beam: also the per-step records of a beam decode (ff_decode_beam), last as well.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
-                     Bump& bp, DecodeBuffers* out, bool want_lp = false) {
+                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
   const int ns = plan_streams(p);
   const size_t Rmax = (size_t)(T - 1 > 0 ? T - 1 : 1) * Bch;
@@ -389,6 +412,11 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     b.perm_all = bp.take<int>(Btot);
   }
   if (want_lp) b.lp_all = bp.take<float>((size_t)(T - 1 > 0 ? T - 1 : 1) * Btot);
+  if (beam) {
+    b.bm_score = bp.take<float>((size_t)T * Btot);
+    b.bm_fin = bp.take<int>((size_t)T * Btot);
+    b.bm_parent = bp.take<int>((size_t)T * Btot);
+  }
   if (out) *out = b;
   return bp.off;
 }
@@ -675,6 +703,8 @@ struct DecodeRun {
   std::vector<std::vector<int>> hslot;        // per chunk: the chunk-local sequence of every slot
   int* fin_host = nullptr;                    // host address of the finish positions when they are host-mapped, else null
   int* fin_dev = nullptr;
+  const ff_beam_params* beam = nullptr;       // ff_decode_beam (null: the greedy decode)
+  int W = 0;                                  // ... its width; 0 without beams
   int validate(const ff_model* m_, const ff_decode_params* p_, const DecodeIO& io_, const void* workspace) {
     m = m_; io = io_;
     FF_RETURN_IF(check_model(m));
@@ -716,10 +746,11 @@ struct DecodeRun {
   int bind_chunks(void* workspace, size_t workspace_bytes) {
     const int ns_req = plan_streams(p);
     int max_bc = 0;
-    plan_chunks(p, io.num_input_host, ns_req, &chunks, &Btot, &max_bc);
+    if (W) plan_beam_chunks(p, io.num_input_host, ns_req, W, &chunks, &Btot, &max_bc);
+    else plan_chunks(p, io.num_input_host, ns_req, &chunks, &Btot, &max_bc);
     nch = (int)chunks.size();
     Bump bp(workspace, workspace_bytes);
-    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr);
+    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr, W > 0);
     if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
     for (Chunk& c : chunks) {
       c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
@@ -851,6 +882,12 @@ struct DecodeRun {
     }
     // start tokens (anchors / SOS) and first decoder input rows of every micro-batch
     for (const Chunk& c : chunks) {
+      if (W) {
+        FF_RETURN_IF(ff_beam_init(buf.tok_all + c.b0, buf.bm_score + c.b0, buf.bm_fin + c.b0, buf.bm_parent + c.b0, c.Bc, c.Fc / W, W,
+                                  c.f0, io.num_input + c.w0, m->num_token - 1, p->term_lo, p->term_hi, sts[c.sid]));
+        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
+        continue;
+      }
       // (retirement: the start tokens of the slots go to the chunk's perm area, free until its first compaction)
       hipLaunchKernelGGL(init_tokens_kernel, dim3(ff_cdiv(c.Bc, 256)), dim3(256), 0, sts[c.sid], buf.tok_all + c.b0,
                          c.Bc, c.Fc, c.f0, io.num_input ? io.num_input + c.w0 : nullptr, p->variant, m->num_token - 1,
@@ -872,11 +909,15 @@ struct DecodeRun {
       nslots += c.Bl;
       hipStream_t st = sts[c.sid];
       const Scratch& sc = buf.scr[c.sid];
-      const size_t trow = (size_t)step * ((size_t)N * F) + c.b0;  // traces: step stride N*F (caller sizes them so)
+      const size_t trow = (size_t)step * ((size_t)N * F * (W ? W : 1)) + c.b0;  // traces: step stride N*F (N*F*W with beams; caller sizes them so)
       const size_t slot = (size_t)step * nch + (size_t)(&c - chunks.data());
       const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bl);
       // (retirement: the logits rows are in slot order; a traced step scatters them to the sequences' rows below)
       float* logits_dst = (io.trace_logits && !retire) ? io.trace_logits + trow * S : sc.logits;
+      if (W) {
+        FF_RETURN_IF(beam_step(c, sc, step, slot, folded_head, logits_dst, trow, st));
+        continue;
+      }
       ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, lagged ? buf.arrive + slot : nullptr,
                             lagged ? pool->hpin_dev + slot : nullptr, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
                             folded_head ? 1 : 0, c.slot, retire ? fin_dev + c.b0 : nullptr, t, p->term_lo, p->term_hi};
@@ -895,6 +936,28 @@ struct DecodeRun {
         FF_RETURN_IF(ff_permute_rows(sc.logits, c.Bl, nullptr, io.trace_logits + trow * S, c.Bc, c.slot, 1, c.Bl, S, st));
     }
     slots_per_step.push_back(nslots);
+    return FF_OK;
+  }
+  // Beam decode, step `step` of one micro-batch: the decoder pass, then top-W selection and prefix reorder in place of the
+  // pointer launch.  The selection reads the state row `step` and writes row t = step + 1, the chunk's next x0 rows (with their
+  // statistics) and the stop counter; the reorder then moves positions < t of x0 and qkv0 behind it on the same stream, so the
+  // next decoder pass reads reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
+  int beam_step(const Chunk& c, const Scratch& sc, int step, size_t slot, bool folded_head, float* logits_dst, size_t trow, hipStream_t st) {
+    const int t = step + 1, G = c.Bc / W;
+    const float* mem_w = io.memory + (size_t)c.w0 * S * E;
+    FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
+    if (!folded_head)   // logits[w * Fc + i, s] = < p[w * Fc + i, :], memory[w, s, :] >: one GEMM problem per wireframe, as the pointer launch
+      FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
+                                       (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
+    const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
+    FF_RETURN_IF(ff_beam_select_sync(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, G, W, c.Fc / W, buf.bm_score + in,
+                                     buf.bm_score + out, buf.bm_fin + in, buf.bm_fin + out, nullptr, 0, t, buf.bm_parent + out,
+                                     buf.tok_all + out, p->term_lo, p->term_hi, mem_w, E, c.x0 + (size_t)t * c.Bc * E, E,
+                                     buf.cnt_ge + slot, m->num_token, c.x0stat, lagged ? buf.arrive + slot : nullptr,
+                                     lagged ? pool->hpin_dev + slot : nullptr, st));
+    if (beam->trace_parent)
+      FF_CHECK_HIP(hipMemcpyAsync(beam->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
+    if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
     return FF_OK;
   }
   // the stop rule over the first n steps' counters, per_chunk = [n][nch]
@@ -1039,6 +1102,11 @@ struct DecodeRun {
                        ((p->flags & FF_NO_STOP) || p->stop_fn) ? 1 : 0, buf.cnt_tot, buf.steps_dev);
     FF_CHECK_LAUNCH();
     for (const Chunk& c : chunks) {
+      if (W) {
+        FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.bm_parent, buf.bm_score, Btot, T, buf.steps_dev, io.num_input, dedup ? 1 : 0, F, W,
+                                      c.w0, c.nw, c.Fc / W, c.f0, c.b0, beam->beams, beam->scores, io.predict, io.seq_of_row, main_st));
+        continue;
+      }
       const long total = (long)c.nw * F * T;
       const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
       hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
@@ -1073,6 +1141,10 @@ struct DecodeRun {
     return FF_OK;
   }
 };
+
+// One decode call from validation to the packed outputs (ff_decode / ff_decode_lp: beam null; ff_decode_beam).
+int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
+               const ff_beam_params* beam);
 
 }  // namespace
 
@@ -1157,6 +1229,14 @@ extern "C" size_t ff_decode_lp_workspace_bytes(const ff_model* m, const ff_decod
   return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, true) + 256;
 }
 
+extern "C" size_t ff_decode_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host, int width) {
+  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0 || width < 1 || width > 8) return 0;
+  int btot = 0, max_bc = 0, nch = 0;
+  plan_beam_chunks(p, num_input_host, 1, width, nullptr, &btot, &max_bc, &nch);
+  Bump bp(nullptr, 0);
+  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, true) + 256;
+}
+
 extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const float* memory,
                          const unsigned char* mask, const int* kv_len, const int* num_input,
                          const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
@@ -1173,10 +1253,41 @@ extern "C" int ff_decode_lp(const ff_model* m, const ff_decode_params* p, const 
                             int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
                             float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
                             size_t workspace_bytes, float* logprob, ff_stream_t stream) {
+  return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, extra_mask, predict, steps_done, step_counts,
+                                   pointer_out, trace_logits, trace_best, trace_second, seq_of_row, (hipStream_t)stream, logprob},
+                    workspace, workspace_bytes, nullptr);
+}
+
+extern "C" int ff_decode_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
+                              const unsigned char* mask, const int* kv_len, const int* num_input,
+                              const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                              int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                              float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                              size_t workspace_bytes, const ff_beam_params* beam, ff_stream_t stream) {
+  FF_CHECK_ARG(m && p && beam, "ff_decode_beam: null model, params or beam params");
+  FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode_beam: beams are a parallel-variant option");
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
+               "ff_decode_beam: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask");
+  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token,
+               "ff_decode_beam: width=%d outside 1..8 or above S=%d", beam->width, p->L + m->num_token);
+  FF_CHECK_ARG(p->term_lo < p->term_hi, "ff_decode_beam: empty terminator range [%d, %d)", p->term_lo, p->term_hi);
+  FF_CHECK_ARG(beam->beams && beam->scores && !trace_best && !trace_second && !pointer_out,
+               "ff_decode_beam: beams and scores required; no best / second traces, no pointer_out");
+  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
+  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
+               "ff_decode_beam: width=%d at E=%d exceeds the reorder's staging area", beam->width, m->E);
+  return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
+                                   nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr},
+                    workspace, workspace_bytes, beam);
+}
+
+namespace {
+int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
+               const ff_beam_params* beam) {
   DecodeRun r;
-  FF_RETURN_IF(r.validate(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, extra_mask, predict, steps_done, step_counts,
-                                         pointer_out, trace_logits, trace_best, trace_second, seq_of_row, (hipStream_t)stream, logprob},
-                          workspace));
+  r.beam = beam;
+  r.W = beam ? beam->width : 0;
+  FF_RETURN_IF(r.validate(m, p, io, workspace));
   FF_RETURN_IF(r.bind_chunks(workspace, workspace_bytes));
   FF_RETURN_IF(ff_gemm_prepare_stream(r.io.main_st));
   std::mutex* busy = pool_busy_mutex();
@@ -1190,3 +1301,4 @@ extern "C" int ff_decode_lp(const ff_model* m, const ff_decode_params* p, const 
   if (rc != FF_OK) r.drain();
   return rc;
 }
+}  // namespace

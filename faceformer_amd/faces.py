@@ -23,7 +23,7 @@ import numpy as np
 __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_with_majority_type", "face_metrics",
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
-           "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores"]
+           "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored"]
 
 
 def _tok(token, name, default):
@@ -210,6 +210,27 @@ def parse_faces_scored(predicts, logprobs, num_edges, token):
         idx = _edge_indices(piece[:-1], ntok, num_edges)
         if idx:
             faces.append((0, idx, float(plp.sum())))
+    return faces
+
+
+def parse_parallel_beams_scored(beams, scores, num_edges, token):
+    """The faces of a beam decode (the parallel model's beam_width): beams [..., W, T] tokens, scores [..., W] the
+    beams' summed log-probabilities (-inf: an empty beam, skipped).  Every other beam is read as `_parallel_rows` reads a row --
+    tokens through the first face-type token, edge filters included -- and carries its beam score: [(type, (edge, ...), score)]
+    in row order, the form unique_faces_with_scores takes."""
+    off, ntok = _tok(token, "face_type_offset", 1), _tok(token, "len", 4)
+    rows = np.asarray(beams, dtype=np.int64)
+    rows = rows.reshape(-1, rows.shape[-1])
+    faces = []
+    for row, score in zip(rows, np.asarray(scores, dtype=np.float64).reshape(-1)):
+        if score == -np.inf:
+            continue
+        seq = _prefix_through_first(row, (row >= off) & (row < ntok))
+        if seq.size == 0:
+            continue
+        idx = _edge_indices(seq, ntok, num_edges)
+        if idx:
+            faces.append((int(seq[-1]) - off, idx, float(score)))
     return faces
 
 

@@ -84,6 +84,18 @@ def fp16_operand_bounds(tensors, n_dec, E, weights=0.0):
     return worst
 
 
+def check_beam_options(width, S, variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, term_range):
+    """The combinations a beam decode rejects (ff_decode_beam's FF_ERR_ARG list), as ValueError before anything is launched."""
+    if variant != _L.FF_PARALLEL:
+        raise ValueError("beam_width is a parallel-variant option")
+    if not 1 <= width <= 8 or width > S:
+        raise ValueError("beam_width=%d: must be in 1..8 and at most S = %d" % (width, S))
+    if retire or return_pointer or no_stop or stop_callback is not None or extra_mask is not None or logprob:
+        raise ValueError("beam_width excludes retire, return_pointer, no_stop, stop_callback, extra_mask and logprob")
+    if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
+        raise ValueError("beam_width needs term_range = (lo, hi) with lo < hi")
+
+
 class PathEngine:
     """Encoder + greedy pointer decode of one model instance on one ROCm device.
 
@@ -338,7 +350,7 @@ class PathEngine:
                chunk_wireframes=0, chunk_seqs=0, num_streams=1, sync_every=4, flags=DEFAULT_FLAGS,
                tok_sos=1, tok_eos=3, x3_min_rows=0, chunk_max_seqs=0, ln_fuse_max_rows=0,
                trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
-               retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False):
+               retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).
 
@@ -349,7 +361,17 @@ class PathEngine:
         retire=True (parallel variant, FF_RETIRE_FINISHED): a sequence is finished from the first position holding a token in
         term_range = (lo, hi); the stop rule looks at unfinished sequences only, `predict` is zero after min(finish position,
         stop step) -- faces.retired_view of the default decode -- and finished sequences leave their micro-batch at the check
-        points.  slot_rows = sum over executed steps of (step + 1) * slots: the decoder rows the call computed."""
+        points.  slot_rows = sum over executed steps of (step + 1) * slots: the decoder rows the call computed.
+
+        beam_width=W >= 1 (parallel variant, ff_decode_beam; None or 0: the greedy decode above): W beams per anchor.  Also
+        `beams` [N*F*W, T] int64 (row (w*F + f)*W + k is beam k of anchor f, best first, zero after the beam's finish position
+        and the stop step), `beam_scores` [N*F*W] fp32 (-inf: empty beam); `predict` is beam 0; with trace=True `logits` is
+        [T-1, N*F*W, S] and `beam_parent` [T-1, N*F*W] int32, both in output-row order.  Needs term_range; excludes retire,
+        return_pointer, no_stop, stop_callback, extra_mask and logprob (ValueError).  beam_width=1 equals the retire=True decode."""
+        W = int(beam_width or 0)
+        if W:
+            check_beam_options(W, memory.shape[1], variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob,
+                               term_range)
         _dev(memory, "memory")
         self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
         N, S, E = memory.shape
@@ -377,6 +399,8 @@ class PathEngine:
             prm.retire_min_shrink = float(retire_min_shrink)
         if return_pointer or extra_mask is not None:   # (every padding-anchor row has its own extra-mask row)
             prm.flags &= ~_L.FF_DEDUP_PAD_ANCHORS
+        if W:
+            prm.term_lo, prm.term_hi = int(term_range[0]), int(term_range[1])
         prm.tok_sos, prm.tok_eos = tok_sos, tok_eos
         prm.x3_min_rows = int(x3_min_rows) if self._planes else 0
         B = N * F
@@ -399,14 +423,23 @@ class PathEngine:
             extra_mask = extra_mask.contiguous()
         pointer = torch.zeros((max(T - 1, 1), B, E), device=dev, dtype=torch.float32) if return_pointer else None
         tl = tb = ts = rows = None
-        if trace:
+        if trace and W:
+            tl = torch.full((max(T - 1, 1), B * W, S), float("nan"), device=dev, dtype=torch.float32)
+        elif trace:
             tl = torch.full((max(T - 1, 1), B, S), float("nan"), device=dev, dtype=torch.float32)
             tb = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
             ts = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
-        rows = torch.empty(B, device=dev, dtype=torch.int32)
+        rows = torch.empty(B * max(W, 1), device=dev, dtype=torch.int32)
         lp = torch.empty((B, T), device=dev, dtype=torch.float32) if logprob else None
-        ws_bytes = self._lib.ff_decode_lp_workspace_bytes if logprob else self._lib.ff_decode_workspace_bytes
-        nbytes = ws_bytes(C.byref(self.model), C.byref(prm), ni_host)
+        if W:
+            beams = torch.empty((B * W, T), device=dev, dtype=torch.int64)
+            bscores = torch.empty(B * W, device=dev, dtype=torch.float32)
+            bparent = torch.full((max(T - 1, 1), B * W), -1, device=dev, dtype=torch.int32) if trace else None
+            bprm = _L.BeamParams(W, _p(beams), _p(bscores), _p(bparent))
+            nbytes = self._lib.ff_decode_beam_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host, W)
+        else:
+            ws_bytes = self._lib.ff_decode_lp_workspace_bytes if logprob else self._lib.ff_decode_workspace_bytes
+            nbytes = ws_bytes(C.byref(self.model), C.byref(prm), ni_host)
         ws = self._workspace(nbytes)
         cb_error, cb = [], None
         if stop_callback is not None and not no_stop:
@@ -428,7 +461,9 @@ class PathEngine:
                 _p(extra_mask), _p(predict), C.byref(steps), counts, _p(pointer), _p(tl), _p(tb), _p(ts),
                 _p(rows), _p(ws), ws.numel())
         with torch.cuda.device(dev):
-            if logprob:
+            if W:
+                _L.check(self._lib.ff_decode_beam(*args, C.byref(bprm), _stream()), "ff_decode_beam")
+            elif logprob:
                 _L.check(self._lib.ff_decode_lp(*args, _p(lp), _stream()), "ff_decode_lp")
             else:
                 _L.check(self._lib.ff_decode(*args, _stream()), "ff_decode")
@@ -441,7 +476,13 @@ class PathEngine:
             out["pointer"] = pointer[: steps.value]
         if logprob:
             out["logprob"] = lp
-        if trace:
+        if W:
+            out["beams"], out["beam_scores"] = beams, bscores
+            if trace:   # (the C side indexes its traces by decoded sequence, as below)
+                idx = rows.long()
+                out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
+                out["logits"], out["beam_parent"] = tl[:, idx], bparent[:, idx]
+        elif trace:
             # the C side indexes its traces by DECODED sequence (padding-anchor rows share one); expand to
             # one entry per row of `predict`
             idx = rows.long()

@@ -129,6 +129,10 @@ class DecodeParams(C.Structure):
     ]
 
 
+class BeamParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("beams", fptr), ("scores", fptr), ("trace_parent", fptr)]
+
+
 # ff_stop_fn: int (*)(void* user, const int* step_counts, int num_steps)
 STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int)
 
@@ -206,6 +210,15 @@ SIGNATURES = {
                                C.POINTER(C.c_int), fptr,
                                fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                C.c_size_t, fptr, fptr]),
+    "ff_beam_select": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
+                                 fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, fptr, C.c_int,
+                                 fptr, C.c_int, fptr]),
+    "ff_beam_reorder": (C.c_int, [fptr, C.c_int, fptr, C.c_int, C.c_int, C.c_int, fptr, C.c_int, C.c_int, fptr]),
+    "ff_decode_beam_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int), C.c_int]),
+    "ff_decode_beam": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                 C.POINTER(C.c_int), fptr,
+                                 fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                                 C.c_size_t, C.POINTER(BeamParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 
@@ -237,7 +250,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp and *_beam* ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

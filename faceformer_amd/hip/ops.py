@@ -361,6 +361,75 @@ def pointer_argmax(p, memory, mask=None, kv_len=None, extra_mask=None, seqs_per_
     return out
 
 
+BEAM_MAX_WIDTH = 8
+
+
+@_on_tensor_device
+def beam_select(logits, scores, fin, width, groups_per_wireframe=None, mask=None, kv_len=None, hist=None, t=0,
+                term_range=(1, 4), memory=None, want_rows=False, counter=None, ge_bound=0):
+    """One beam-search step of every group (ff_beam_select).  logits [G * width, S] fp32 raw dot products (masked IN PLACE),
+    scores [G * width] fp32 (-inf: empty beam) and fin [G * width] int32 (nonzero: finished) are the state before the step;
+    hist (optional) [t + 1, G * width] int32 token history, permuted in place, position t written.  Returns dict(parent, next,
+    scores, fin, [rows]): the new beams in rank order, best first."""
+    _dev(logits, "logits"), _dev(scores, "scores"), _dev(fin, "fin", torch.int32)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be a 2-D tensor with unit inner stride")
+    B, S = logits.shape
+    if not 1 <= width <= BEAM_MAX_WIDTH or width > S or B % width:
+        raise ValueError("beam width %d: must be in 1..%d, at most S = %d, and divide the %d rows" % (width, BEAM_MAX_WIDTH, S, B))
+    G = B // width
+    gpw = G if groups_per_wireframe is None else int(groups_per_wireframe)
+    dev = logits.device
+    if mask is not None:
+        _dev(mask, "mask", torch.uint8)
+    if kv_len is not None:
+        _dev(kv_len, "kv_len", torch.int32)
+    ldhist = 0
+    if hist is not None:
+        _dev(hist, "hist", torch.int32)
+        if hist.dim() != 2 or hist.size(0) < t + 1 or hist.size(1) < B or hist.stride(1) != 1:
+            raise ValueError("hist must be [>= t + 1, >= G * width] int32")
+        ldhist = hist.stride(0)
+    out = {"parent": torch.empty(B, device=dev, dtype=torch.int32), "next": torch.empty(B, device=dev, dtype=torch.int32),
+           "scores": torch.empty(B, device=dev, dtype=torch.float32), "fin": torch.empty(B, device=dev, dtype=torch.int32)}
+    rows, E = None, 0
+    if memory is not None:
+        _dev(memory, "memory")
+        if memory.dim() != 3 or not memory.is_contiguous() or memory.size(1) != S:
+            raise ValueError("memory must be a contiguous [N, S, E] tensor")
+        E = memory.size(2)
+        if want_rows:
+            rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
+    if counter is not None:
+        _dev(counter, "counter", torch.int32)
+    _L.check(_L.load().ff_beam_select(
+        _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), G, width, gpw, _p(scores.contiguous()), _p(out["scores"]),
+        _p(fin.contiguous()), _p(out["fin"]), _p(hist), ldhist, t, _p(out["parent"]), _p(out["next"]), int(term_range[0]),
+        int(term_range[1]), _p(memory), E, _p(rows), E, _p(counter), ge_bound, _stream()), "ff_beam_select")
+    return out
+
+
+@_on_tensor_device
+def beam_reorder(rows_a, parent, width, rows_b=None):
+    """rows_a [npos, R, wa] (and rows_b [npos, R, wb]) fp32, in place: row (j, g * width + k) <- row (j, g * width + parent[g *
+    width + k]) for every position j and group g < len(parent) / width (ff_beam_reorder)."""
+    _dev(rows_a, "rows_a"), _dev(parent, "parent", torch.int32)
+    if rows_a.dim() != 3 or not rows_a.is_contiguous():
+        raise ValueError("rows_a must be a contiguous [npos, rows, width] tensor")
+    npos, R, wa = rows_a.shape
+    wb = 0
+    if rows_b is not None:
+        _dev(rows_b, "rows_b")
+        if rows_b.dim() != 3 or not rows_b.is_contiguous() or rows_b.shape[:2] != rows_a.shape[:2]:
+            raise ValueError("rows_b must be a contiguous [npos, rows, width] tensor with rows_a's positions and rows")
+        wb = rows_b.size(2)
+    if not 1 <= width <= BEAM_MAX_WIDTH or parent.numel() % width:
+        raise ValueError("beam width %d: must be in 1..%d and divide the %d parents" % (width, BEAM_MAX_WIDTH, parent.numel()))
+    _L.check(_L.load().ff_beam_reorder(_p(rows_a), wa, _p(rows_b), wb, R, npos, _p(parent.contiguous()), parent.numel() // width,
+                                       width, _stream()), "ff_beam_reorder")
+    return rows_a
+
+
 @_on_tensor_device
 def gather_rows(memory, tok, seqs_per_group=1):
     _dev(memory, "memory"), _dev(tok, "tok", torch.int32)

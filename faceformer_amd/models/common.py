@@ -65,6 +65,10 @@ class SurfaceFormerBase(nn.Module):
         self.return_logprob = False    # forward_eval also returns inputs["predict_logprob"], shaped like inputs["predict"]: the
                                        # log-probability log_softmax(masked logits)[token] of every greedy selection, 0 at the
                                        # start token and wherever predict is zero padded.  Not with dist.decode_sharded
+        self.beam_width = 0            # parallel model: >= 1 decodes with this many beams per anchor (beam search):
+                                       # forward_eval adds predict_beams / predict_beam_scores, predict is beam 0.  0 = greedy.
+                                       # Not with retire_finished, return_logprob, an extra mask, dist.decode_sharded or the
+                                       # single-sequence model (ValueError)
         # Decoder projections of launches with at least this many rows (q|k|v; linear1 from 7/4 x, the 512-column ones from
         # 11/4 x as many) run as 3 x bf16 split products on the bf16 matrix cores: fp32-accurate (error vs fp64 = an fp32 dot
         # product's, tests/test_hip_ops.py), LayerNorm folding included (ff_gemm_x3_ln), and 1.3-1.6x the f32-MFMA kernel

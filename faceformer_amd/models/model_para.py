@@ -35,9 +35,15 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
 
     def forward_eval(self, inputs):
         """inputs: input N x L x P x D, input_mask N x L (True = padding), label N x F' x T (shape
-        only), num_input: N edge counts.  Adds predict N x F x T (int64), F = max(num_input)."""
+        only), num_input: N edge counts.  Adds predict N x F x T (int64), F = max(num_input).
+        beam_width = W >= 1 (default 0: the greedy decode): beam search with W beams per anchor -- also predict_beams
+        N x F x W x T (best first; zero after a beam's face-type token and after the stop step) and predict_beam_scores
+        N x F x W (summed log-probabilities, -inf for empty beams); predict is beam 0."""
         label = inputs["label"]
         T = self.max_face_length
+        W = int(getattr(self, "beam_width", 0) or 0)
+        if W and not self.engine_supported():
+            raise ValueError("beam_width needs the native engine: this model's constructor arguments take the sub-module loop")
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             inputs = self._forward_eval_modules(inputs, parallel=True)
             if self.retire_finished:         # (that loop decodes every sequence; the result is the same function of its tokens)
@@ -81,17 +87,26 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
                          num_streams=self.num_streams, sync_every=self.sync_every,
                          flags=self.decode_flags, x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, extra_mask=extra,
                          retire=self.retire_finished, term_range=(int(self.token.face_type_offset), int(self.token.len)),
-                         logprob=want_lp)
+                         logprob=want_lp, beam_width=W or None)
         pred = out["predict"].view(N, F, T)
         lp = out["logprob"].view(N, F, T) if want_lp else None
+        beams = out["beams"].view(N, F, W, T) if W else None
+        bscores = out["beam_scores"].view(N, F, W) if W else None
         if order is not None:
             inv = torch.empty(N, dtype=torch.long, device=pred.device)
             inv[torch.tensor(order, device=pred.device)] = torch.arange(N, device=pred.device)
             pred = pred.index_select(0, inv)
             lp = lp.index_select(0, inv) if want_lp else None
+            if W:
+                beams, bscores = beams.index_select(0, inv), bscores.index_select(0, inv)
         inputs["predict"] = pred
+        if W:   # (predict is beam 0 of every anchor)
+            inputs["predict_beams"], inputs["predict_beam_scores"] = beams, bscores
         if want_lp:
             inputs["predict_logprob"] = lp
         self.last_decode_stats = {"decoded_seqs": sum(min(F, n + 1) for n in num_input), "rows": N * F,
                                   "slot_rows": out["slot_rows"], "steps": out["steps"]}
+        if W:   # (W sequences per decoded anchor; `rows` stays the reference's N * F)
+            self.last_decode_stats["decoded_seqs"] *= W
+            self.last_decode_stats["beam_width"] = W
         return inputs

@@ -613,6 +613,64 @@ int ff_decode_lp(const ff_model* m, const ff_decode_params* p,
                  float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                  void* workspace, size_t workspace_bytes, float* logprob, ff_stream_t stream);
 
+/* ---- beam search over the pointer head (opt-in, parallel variant; entries added within ABI 105) ---------------
+ * The reference decodes greedily: select_next takes the argmax of the masked logit row (model_para.py:173-179) inside the loop
+ * of model_para.py:216-233.  These entries extend exactly those two call sites: the selection keeps the `width` best
+ * continuations of the `width` beams of every anchor (a GROUP) instead of one, the loop carries width sequences per anchor.
+ *
+ * ff_beam_select: one step of every group.  Launch row b = g * width + k is beam k of group g; wireframe of a row:
+ *   b / (groups_per_wireframe * width) (mask [wireframes, S], kv_len [wireframes], memory [wireframes, S, E]).
+ *   logits   [groups * width, ldlogits] raw dot products; masked IN PLACE as the pointer launch masks them (key padding mask,
+ *            kv_len: masked entries become -FLT_MAX and stay candidates at that value).  Rows of empty / finished beams are not read.
+ *   scores_in / fin_in   [groups * width]: a beam with score -inf is EMPTY (no candidates); fin != 0: finished -- it contributes
+ *            one candidate, itself: token 0, score unchanged.
+ *   Every other beam k contributes S candidates of score c_k + log_softmax(masked row)[s], fp32, saturated at -FLT_MAX.
+ *   The width best candidates of the group are kept in descending order; equal scores go to the lower flat index k * S + s
+ *   (s = 0 for a finished beam).  Rank r writes parent[b] (the k it extends; r itself when fewer than r + 1 candidates exist: the
+ *   beam stays empty, score -inf, token 0), next_tok[b], scores_out[b], fin_out[b] (parent finished, or token in
+ *   [term_lo, term_hi)).  scores_out / fin_out may be scores_in / fin_in.
+ *   hist     (optional) token history [t + 1, ldhist] ints, positions 0..t-1 filled: permuted in place by the parents, position
+ *            t receives next_tok.
+ *   next_rows (optional, with memory and E): row b receives memory[wireframe, next_tok[b], :], the next decoder input row.
+ *   count_ge (optional): += number of kept candidates of unfinished beams whose token is >= ge_bound (the stop rule's count).
+ * ff_beam_reorder: rows_a[(j * rows_per_pos + g * width + k) * width_a ..] <- the row of k' = parent[g * width + k], for every
+ *   position j < npos and group g < groups, in place; likewise rows_b (optional, width_b floats per row; NULL with width_b = 0).
+ *   Widths are multiples of 4, bases 16-byte aligned, width * (width_a + width_b) * 4 <= 65536 bytes.  parent[] holds
+ *   group-local beam indices 0..width-1 (what ff_beam_select writes); a value outside is clamped into that range.
+ * 1 <= width <= 8; ff_beam_select also needs width <= S. */
+int ff_beam_select(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int groups, int width,
+                   int groups_per_wireframe, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
+                   int* hist, int ldhist, int t, int* parent, int* next_tok, int term_lo, int term_hi, const float* memory, int E,
+                   float* next_rows, int ldnext, int* count_ge, int ge_bound, ff_stream_t stream);
+int ff_beam_reorder(float* rows_a, int width_a, float* rows_b, int width_b, int rows_per_pos, int npos, const int* parent,
+                    int groups, int width, ff_stream_t stream);
+/* ff_decode_beam: the parallel decode (model_para.py:216-233) with `width` beams per anchor; ff_decode's arguments, then:
+ *   beams  [N*F*width, T] int64: row (w*F + f) * width + k is beam k of anchor f, best first; zero after the beam's finish
+ *          position and after the stop step.  scores [N*F*width] fp32: the beams' summed log-probabilities (-inf: empty beam,
+ *          whose row is the start token followed by zeros).  predict [N*F, T] receives beam 0 of every anchor.
+ *   trace_parent (optional) [T-1, N*F*width] int32: the parent (0..width-1, within its group) of every beam at every executed
+ *          step, indexed like trace_logits -- by decoded sequence, seq_of_row [N*F*width] maps output rows to them; trace_logits
+ *          holds [T-1, N*F*width, S] entries; trace_best / trace_second must be NULL.
+ * A beam is finished from the first position (the start token included) holding a token in [term_lo, term_hi) of the
+ * parameters; the decode stops after the first step at which no unfinished beam selected a token >= num_token, else after T-1
+ * steps.  With width 1 the beams are FF_RETIRE_FINISHED's predict of the same batch.  FF_ERR_ARG for: FF_SEQ2SEQ,
+ * FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn, an extra_mask, width outside 1..8 or above S, term_lo >= term_hi.
+ * ff_decode_beam_workspace_bytes: the workspace it needs (ff_decode_workspace_bytes' rules, width sequences per anchor plus the
+ * per-step records).  ff_decode and ff_decode_lp launch and lay out what they did before these entries. */
+typedef struct ff_beam_params {
+  int width;
+  int64_t* beams;
+  float* scores;
+  int* trace_parent;
+} ff_beam_params;
+size_t ff_decode_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host, int width);
+int ff_decode_beam(const ff_model* m, const ff_decode_params* p,
+                   const float* memory, const unsigned char* mask, const int* kv_len,
+                   const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                   int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                   float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                   void* workspace, size_t workspace_bytes, const ff_beam_params* beam, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

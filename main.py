@@ -53,10 +53,20 @@ def decode_batch_scored(model, batch):
     return out["predict"].cpu().numpy(), out["predict_logprob"].cpu().numpy()
 
 
-def record_of(cfg, raw, item, pred, parallel, logprob=None):
+def decode_batch_beams(model, batch):
+    """(`predict`, `predict_beams`, `predict_beam_scores`) of `model(batch)` as numpy arrays (--beam: the model's beam_width is set)."""
+    with torch.no_grad():
+        out = model(batch)
+    return out["predict"].cpu().numpy(), out["predict_beams"].cpu().numpy(), out["predict_beam_scores"].cpu().numpy()
+
+
+def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
-    de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored)."""
+    de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
+    beams (--beam; (tokens [F, W, T], scores [F, W]) of this sample): the record also gets `pred_beam_faces` and
+    `pred_beam_face_scores`, the de-duplicated faces over ALL beams of the wireframe's own anchors ranked by their best beam
+    score; `pred_faces` stays what beam 0 (pred) gives."""
     scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
@@ -87,30 +97,45 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None):
     rec = FZ.faces_record(raw["edges"], raw.get("dominant_directions", []), m["predictions"], m["labels"])
     if scored:      # (unique_faces_with_scores groups like unique_faces_with_majority_type: parallel to m["predictions"])
         rec["pred_face_scores"] = [s for _, _, s, _ in FZ.unique_faces_with_scores(sf)]
+    if beams is not None:
+        n = int(item["num_input"])
+        bf = FZ.parse_parallel_beams_scored(beams[0][:n], beams[1][:n], len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_beam_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_beam_face_scores"] = [s for _, _, s, _ in ranked]
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
-def configure_model(model, retire_finished=False, fp16=False, scores=False):
+def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
-    (return_logprob).  Without them the model keeps its defaults."""
+    (return_logprob), beam search with `beam` beams per anchor (beam_width).  Without them the
+    model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
     if fp16:
         model.split_kind = "fp16"
     if scores:
         model.return_logprob = True
+    if beam:
+        model.beam_width = int(beam)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
-             retire_finished=False, fp16=False, scores=False):
+             retire_finished=False, fp16=False, scores=False, beam=0):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
     retire_finished: the parallel model stops decoding a face loop once it has ended (models/common.py retire_finished).
     fp16: the decoder's large projections and its cross-attention take one fp16 product each (split_kind "fp16").
-    scores: every record gains `pred_face_scores` (record_of); single-process runs only."""
+    scores: every record gains `pred_face_scores` (record_of); single-process runs only.
+    beam: beam search with this many beams per anchor (parallel model, single process, not with retire_finished / scores):
+    every record gains `pred_beam_faces` / `pred_beam_face_scores`."""
+    if beam and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores):
+        raise ValueError("--beam applies to SurfaceFormer_Parallel only, and not together with --retire-finished or --scores")
+    if beam and dist_mod is not None and dist_mod.get_world_size() > 1:
+        raise ValueError("--beam (beam_width) is not implemented for multi-rank runs")
     if retire_finished and cfg.model_class != "SurfaceFormer_Parallel":
         raise ValueError("--retire-finished applies to SurfaceFormer_Parallel only")
     if scores and dist_mod is not None and dist_mod.get_world_size() > 1:
@@ -123,7 +148,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         sd, _ = load_lightning_checkpoint(ckpt_path)
         model.load_state_dict(sd)
         model = model.eval().to(device)
-    configure_model(model, retire_finished, fp16, scores)
+    configure_model(model, retire_finished, fp16, scores, beam)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -144,11 +169,17 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         if torch.cuda.is_available() and str(device).startswith("cuda"):
             torch.cuda.synchronize()
         t0 = time.time()
-        pred, lps = decode_batch_scored(model, batch) if scores else (decode_batch(model, batch), None)
+        bms = None
+        if beam:
+            pred, bt, bs = decode_batch_beams(model, batch)
+            lps, bms = None, list(zip(bt, bs))
+        else:
+            pred, lps = decode_batch_scored(model, batch) if scores else (decode_batch(model, batch), None)
         total += time.time() - t0
         done += len(idx)
         for k, i in enumerate(idx):
-            text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel, lps[k] if scores else None)
+            text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel, lps[k] if scores else None,
+                                 bms[k] if beam else None)
             stats.append(st)
             records.append((os.path.splitext(os.path.basename(items[k]["name"]))[0], text))
         print("Avg Time", total / done, "seconds.")
@@ -189,6 +220,10 @@ def build_parser():
     parser.add_argument("--scores", action="store_true",
                         help="every JSON record gains pred_face_scores, parallel to pred_faces: the summed log-probability of the "
                              "face's greedy selections (DESIGN.md 12); single-process runs only")
+    parser.add_argument("--beam", type=int, default=0, metavar="W",
+                        help="parallel model: beam search with W (1..8) beams per anchor edge (DESIGN.md 13); pred_faces come from "
+                             "the best beam, and every JSON record gains pred_beam_faces / pred_beam_face_scores: the faces of all "
+                             "beams, de-duplicated and ranked by score; single-process runs only")
     return parser
 
 
@@ -207,7 +242,7 @@ def main(argv=None):
         device = "cuda:%d" % local_rank
         dist_mod.init_process_group("nccl", device_id=torch.device(device))
     run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
-             retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores)
+             retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
