@@ -133,6 +133,12 @@ int ff_beam_finalize(const int* tok, const int* parent, const float* score, int 
                      const int* num_input, int dedup, int F, int W, int w0, int nw, int Fc, int f0, int b0, int64_t* beams,
                      float* scores, int64_t* predict, int* seq_of_row, hipStream_t st);
 
+// Forced decode (ff_forced.hip): the [rows, T] int64 paths as the engine's position-major int32 tokens (clamped into [0, S)),
+// and the output packing (kernels' comments).
+int ff_forced_tokens(const int64_t* paths, int* tok, int rows, int T, int S, hipStream_t st);
+int ff_forced_finalize(const int* tok, const float* lp_all, const int* greedy_all, const int* rank_all, const int* lengths, int rows,
+                       int T, float* logprob, int64_t* greedy, int* rank, float* seq_logprob, hipStream_t st);
+
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);
 

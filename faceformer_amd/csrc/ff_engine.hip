@@ -23,6 +23,10 @@
 // compact anchor a is chunk-local sequence a * W + k, so a chunk's Fc / Bc are W times its anchor counts and w = i / Fc holds.
 // A step's pointer launch is replaced by ff_beam_select (+ ff_beam_reorder of the x0 / qkv0 prefixes); every step leaves its
 // (token, parent, score, finished) row in the workspace and the output is packed from those rows behind the stop step.
+//
+// Forced decode (ff_decode_forced, opt-in, both variants): the same run fed a given path -- the token array holds
+// the caller's paths from the start, a step's pointer launch is replaced by ff_pointer_forced (which appends the FORCED token's
+// row), every micro-batch runs max(lengths of its rows) steps, and there is no stop rule: no counters, no check points.
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
@@ -235,6 +239,9 @@ struct DecodeBuffers {
   // beam decode: [T, Btot] each, row s = the beams' state after s steps (row 0: the start state); the tokens are tok_all's rows
   float* bm_score;
   int *bm_fin, *bm_parent;
+  // forced decode: [T-1, Btot] each, row s = what step s scored (log-probability of the forced token, the argmax, the rank)
+  float* fc_lp;
+  int *fc_greedy, *fc_rank;
 };
 
 // A micro-batch is a contiguous range [b0, b0 + Bc) of the COMPACT sequence index: nw >= 1 consecutive
@@ -360,9 +367,9 @@ bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
 
 // Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
 // want_lp: also the log-probability rows (ff_decode_lp) -- taken LAST, so that everything else lies where it lies without them.
-// beam: also the per-step records of a beam decode (ff_decode_beam), last as well.
+// beam: also the per-step records of a beam decode (ff_decode_beam), last as well.  forced: those of a forced decode, likewise.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
-                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false) {
+                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false, bool forced = false) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
   const int ns = plan_streams(p);
   const size_t Rmax = (size_t)(T - 1 > 0 ? T - 1 : 1) * Bch;
@@ -416,6 +423,12 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     b.bm_score = bp.take<float>((size_t)T * Btot);
     b.bm_fin = bp.take<int>((size_t)T * Btot);
     b.bm_parent = bp.take<int>((size_t)T * Btot);
+  }
+  if (forced) {
+    const size_t n = (size_t)(T - 1 > 0 ? T - 1 : 1) * Btot;
+    b.fc_lp = bp.take<float>(n);
+    b.fc_greedy = bp.take<int>(n);
+    b.fc_rank = bp.take<int>(n);
   }
   if (out) *out = b;
   return bp.off;
@@ -705,14 +718,17 @@ struct DecodeRun {
   int* fin_dev = nullptr;
   const ff_beam_params* beam = nullptr;       // ff_decode_beam (null: the greedy decode)
   int W = 0;                                  // ... its width; 0 without beams
+  const ff_forced_params* forced = nullptr;   // ff_decode_forced (null otherwise)
+  std::vector<int> chunk_steps;               // ... steps every micro-batch runs: the largest length among its rows
+  int forced_steps = 0;                       // ... and the largest of those
   int validate(const ff_model* m_, const ff_decode_params* p_, const DecodeIO& io_, const void* workspace) {
     m = m_; io = io_;
     FF_RETURN_IF(check_model(m));
     FF_CHECK_ARG(p_ != nullptr, "ff_decode: null params");
     FF_CHECK_ARG(p_->variant == FF_PARALLEL || p_->variant == FF_SEQ2SEQ, "ff_decode: bad variant");
     FF_CHECK_ARG(p_->N > 0 && p_->L >= 0 && p_->F > 0 && p_->T >= 1, "ff_decode: bad sizes");
-    FF_CHECK_ARG(io.memory && io.mask && io.kv_len && io.predict && workspace, "ff_decode: null pointer");
-    FF_CHECK_ARG(p_->variant != FF_PARALLEL || io.num_input, "ff_decode: num_input required for the parallel variant");
+    FF_CHECK_ARG(io.memory && io.mask && io.kv_len && (io.predict || forced) && workspace, "ff_decode: null pointer");
+    FF_CHECK_ARG(p_->variant != FF_PARALLEL || io.num_input || forced, "ff_decode: num_input required for the parallel variant");
     FF_CHECK_ARG(p_->variant != FF_SEQ2SEQ || p_->F == 1, "ff_decode: seq2seq decodes one sequence per wireframe");
     FF_CHECK_ARG(!p_->stop_fn || (p_->flags & FF_NO_STOP) || p_->sync_every > 0, "ff_decode: stop_fn needs sync_every > 0");
     // The callback's cadence is a CONTRACT with callers that replay it elsewhere (an idle rank of a sharded decode joins the
@@ -723,7 +739,7 @@ struct DecodeRun {
     E = m->E; S = p_->L + m->num_token; T = p_->T; F = p_->F; N = p_->N;
     FF_CHECK_ARG(S <= m->pos_len, "ff_decode: S=%d exceeds the position table (%d rows)", S, m->pos_len);
     FF_CHECK_ARG(T - 1 <= m->qpos_len, "ff_decode: T-1=%d exceeds the query position table (%d rows)", T - 1, m->qpos_len);
-    FF_CHECK_ARG(p_->variant != FF_PARALLEL || F <= S, "ff_decode: F=%d anchors exceed S=%d", F, S);
+    FF_CHECK_ARG(p_->variant != FF_PARALLEL || F <= S || forced, "ff_decode: F=%d anchors exceed S=%d", F, S);   // (forced rows are no anchors)
     FF_CHECK_ARG(!(p_->flags & FF_RETURN_POINTER) || io.pointer_out, "ff_decode: pointer_out required");
     if (p_->flags & FF_RETIRE_FINISHED) {
       FF_CHECK_ARG(p_->variant == FF_PARALLEL, "ff_decode: FF_RETIRE_FINISHED is a parallel-variant option");
@@ -734,7 +750,7 @@ struct DecodeRun {
     }
     // every padding-anchor sequence has its own row of an extra mask: no de-duplication then
     prm = *p_;
-    if (io.extra_mask) prm.flags &= ~FF_DEDUP_PAD_ANCHORS;
+    if (io.extra_mask || forced) prm.flags &= ~FF_DEDUP_PAD_ANCHORS;   // (forced: the rows are arbitrary paths)
     p = &prm;
     retire = retiring(p);
     dedup = p->variant == FF_PARALLEL && (p->flags & FF_DEDUP_PAD_ANCHORS) && io.num_input_host;
@@ -750,7 +766,7 @@ struct DecodeRun {
     else plan_chunks(p, io.num_input_host, ns_req, &chunks, &Btot, &max_bc);
     nch = (int)chunks.size();
     Bump bp(workspace, workspace_bytes);
-    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr, W > 0);
+    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr, W > 0, forced != nullptr);
     if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
     for (Chunk& c : chunks) {
       c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
@@ -768,6 +784,14 @@ struct DecodeRun {
     fin_dev = buf.fin;
     slots_per_step.reserve((size_t)T);   // (the loop below allocates nothing per step)
     tot.reserve((size_t)T);
+    if (forced) {   // (the plan has no de-duplication: sequence b0 + i of a chunk is row b0 + i of the paths)
+      for (const Chunk& c : chunks) {
+        int mx = 0;
+        for (int i = 0; i < c.Bc; ++i) mx = forced->lengths_host[c.b0 + i] > mx ? forced->lengths_host[c.b0 + i] : mx;
+        chunk_steps.push_back(mx);
+        forced_steps = mx > forced_steps ? mx : forced_steps;
+      }
+    }
     return FF_OK;
   }
   // With more than one stream ALL micro-batch work runs on the internal pool (the caller's stream is
@@ -882,6 +906,10 @@ struct DecodeRun {
     }
     // start tokens (anchors / SOS) and first decoder input rows of every micro-batch
     for (const Chunk& c : chunks) {
+      if (forced) {   // (the start tokens are row 0 of the token array: forced_tokens() put the paths there)
+        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
+        continue;
+      }
       if (W) {
         FF_RETURN_IF(ff_beam_init(buf.tok_all + c.b0, buf.bm_score + c.b0, buf.bm_fin + c.b0, buf.bm_parent + c.b0, c.Bc, c.Fc / W, W,
                                   c.f0, io.num_input + c.w0, m->num_token - 1, p->term_lo, p->term_hi, sts[c.sid]));
@@ -958,6 +986,49 @@ struct DecodeRun {
     if (beam->trace_parent)
       FF_CHECK_HIP(hipMemcpyAsync(beam->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
     if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
+    return FF_OK;
+  }
+  // ---- forced decode ------------------------------------------------------------------------------------------------------------
+  // The caller's paths as the token array (main stream, in front of the prologue's fork: every stream sees them).
+  int forced_tokens() { return ff_forced_tokens(forced->paths, buf.tok_all, Btot, T, S, io.main_st); }
+  // Step `step` of every micro-batch that still has a row to score: the decoder pass over the forced prefix, the pointer GEMM
+  // (always the GEMM + reduce form, as a decode with log-probabilities), then ff_pointer_forced in place of the pointer launch:
+  // it scores position t = step + 1 of the paths and appends THAT token's row.  Nothing is read back, nothing is counted.
+  int forced_loop() {
+    for (int step = 0; step < forced_steps; ++step) {
+      const int t = step + 1;
+      for (const Chunk& c : chunks) {
+        if (step >= chunk_steps[(size_t)(&c - chunks.data())]) continue;
+        hipStream_t st = sts[c.sid];
+        const Scratch& sc = buf.scr[c.sid];
+        const float* mem_w = io.memory + (size_t)c.w0 * S * E;
+        const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bc);
+        float* logits_dst = io.trace_logits ? io.trace_logits + ((size_t)step * Btot + c.b0) * S : sc.logits;
+        FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
+        if (!folded_head)
+          FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
+                                           (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
+        const size_t rec = (size_t)step * Btot + c.b0;
+        FF_RETURN_IF(ff_pointer_forced(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, c.Bc, c.Fc,
+                                       buf.tok_all + (size_t)t * Btot + c.b0, buf.fc_lp + rec, buf.fc_greedy + rec, buf.fc_rank + rec,
+                                       mem_w, E, c.x0 + (size_t)t * c.Bc * E, E, c.x0stat, st));
+      }
+    }
+    enq = forced_steps;
+    return FF_OK;
+  }
+  // Join, then the packing of the per-step records on the main stream.
+  int forced_epilogue() {
+    const hipStream_t main_st = io.main_st;
+    if (forked && forced_steps > 0)
+      for (int s = 0; s < ns; ++s) {
+        FF_CHECK_HIP(hipEventRecord(pool->join_ev[s], sts[s]));
+        FF_CHECK_HIP(hipStreamWaitEvent(main_st, pool->join_ev[s], 0));
+      }
+    FF_RETURN_IF(ff_forced_finalize(buf.tok_all, buf.fc_lp, buf.fc_greedy, buf.fc_rank, forced->lengths, Btot, T, forced->logprob,
+                                    forced->greedy, forced->rank, forced->seq_logprob, main_st));
+    FF_CHECK_HIP(hipStreamSynchronize(main_st));   // (the caller may free or reuse the workspace next, as after ff_decode)
+    if (io.steps_done) *io.steps_done = forced_steps;
     return FF_OK;
   }
   // the stop rule over the first n steps' counters, per_chunk = [n][nch]
@@ -1144,7 +1215,7 @@ struct DecodeRun {
 
 // One decode call from validation to the packed outputs (ff_decode / ff_decode_lp: beam null; ff_decode_beam).
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam);
+               const ff_beam_params* beam, const ff_forced_params* forced = nullptr);
 
 }  // namespace
 
@@ -1281,10 +1352,39 @@ extern "C" int ff_decode_beam(const ff_model* m, const ff_decode_params* p, cons
                     workspace, workspace_bytes, beam);
 }
 
+extern "C" size_t ff_decode_forced_workspace_bytes(const ff_model* m, const ff_decode_params* p) {
+  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
+  ff_decode_params q = *p;
+  q.flags &= ~FF_DEDUP_PAD_ANCHORS;
+  int btot = 0, max_bc = 0, nch = 0;
+  plan_chunks(&q, nullptr, 1, nullptr, &btot, &max_bc, &nch);
+  Bump bp(nullptr, 0);
+  return layout_decode(m, &q, engine_knobs(&q), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, false, true) + 256;
+}
+
+extern "C" int ff_decode_forced(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
+                                const int* kv_len, const ff_forced_params* forced, int* steps_done, float* trace_logits,
+                                void* workspace, size_t workspace_bytes, ff_stream_t stream) {
+  FF_CHECK_ARG(m && p && forced, "ff_decode_forced: null model, params or forced params");
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_STOP_EACH_EOS)) && !p->stop_fn,
+               "ff_decode_forced: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_STOP_EACH_EOS and a stop_fn");
+  FF_CHECK_ARG(forced->paths && forced->lengths && forced->lengths_host && forced->logprob && forced->greedy && forced->rank &&
+                   forced->seq_logprob, "ff_decode_forced: paths, lengths (device and host) and the four outputs are required");
+  FF_CHECK_ARG(p->N > 0 && p->F > 0 && p->T >= 1 && (long long)p->N * p->F < (1LL << 31) && (p->variant != FF_SEQ2SEQ || p->F == 1),
+               "ff_decode_forced: bad sizes (seq2seq scores one row per wireframe)");
+  for (long long r = 0; r < (long long)p->N * p->F; ++r)
+    FF_CHECK_ARG(forced->lengths_host[r] >= 0 && forced->lengths_host[r] <= p->T - 1, "ff_decode_forced: lengths[%lld]=%d outside 0..%d",
+                 r, forced->lengths_host[r], p->T - 1);
+  return run_decode(m, p, DecodeIO{memory, mask, kv_len, nullptr, nullptr, nullptr, nullptr, steps_done, nullptr, nullptr, trace_logits,
+                                   nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr},
+                    workspace, workspace_bytes, nullptr, forced);
+}
+
 namespace {
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam) {
+               const ff_beam_params* beam, const ff_forced_params* forced) {
   DecodeRun r;
+  r.forced = forced;
   r.beam = beam;
   r.W = beam ? beam->width : 0;
   FF_RETURN_IF(r.validate(m, p, io, workspace));
@@ -1295,9 +1395,17 @@ int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io,
   std::lock_guard<std::mutex> one_decode_per_device(*busy);
   FF_RETURN_IF(r.bind_streams());
   FF_RETURN_IF(r.init_retirement());
-  int rc = r.prologue();
-  if (rc == FF_OK) rc = r.greedy_loop();
-  if (rc == FF_OK) rc = r.epilogue();
+  int rc = FF_OK;
+  if (forced) {   // (no row to score: the start tokens are packed, no decoder launch is made)
+    rc = r.forced_tokens();
+    if (rc == FF_OK && r.forced_steps > 0) rc = r.prologue();
+    if (rc == FF_OK) rc = r.forced_loop();
+    if (rc == FF_OK) rc = r.forced_epilogue();
+  } else {
+    rc = r.prologue();
+    if (rc == FF_OK) rc = r.greedy_loop();
+    if (rc == FF_OK) rc = r.epilogue();
+  }
   if (rc != FF_OK) r.drain();
   return rc;
 }

@@ -23,7 +23,7 @@ import numpy as np
 __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_with_majority_type", "face_metrics",
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
-           "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored"]
+           "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary"]
 
 
 def _tok(token, name, default):
@@ -232,6 +232,33 @@ def parse_parallel_beams_scored(beams, scores, num_edges, token):
         if idx:
             faces.append((int(seq[-1]) - off, idx, float(score)))
     return faces
+
+
+def score_summary(logprob, greedy, rank, paths, lengths):
+    """Likelihood metrics of teacher-forced scores (the models' score()), per wireframe.  logprob / greedy / rank /
+    paths [N, ..., T] as score() returns them (parallel: N x F x T, seq2seq: N x T), lengths [N, ...]: positions 1..lengths of a
+    row were scored.  Returns dict of length-N arrays: `tokens` (scored positions, int64), `nll` (- sum of their log-probabilities
+    / tokens), `tf_accuracy` (share with rank 0: the model's own argmax, given the true prefix, was the path's token) and
+    `mean_rank`; NaN where a wireframe has no scored position."""
+    lp = np.asarray(logprob, dtype=np.float64)
+    rk, gr, pa = np.asarray(rank, dtype=np.int64), np.asarray(greedy, dtype=np.int64), np.asarray(paths, dtype=np.int64)
+    ln = np.asarray(lengths, dtype=np.int64)
+    if not (lp.shape == rk.shape == gr.shape == pa.shape) or lp.ndim < 2 or ln.shape != lp.shape[:-1]:
+        raise ValueError("logprob, greedy, rank and paths must share one [N, ..., T] shape, lengths its leading dimensions")
+    N, T = lp.shape[0], lp.shape[-1]
+    j = np.arange(T)
+    scored = ((j >= 1) & (j <= ln[..., None])).reshape(N, -1)
+    lp, rk, hit = lp.reshape(N, -1), rk.reshape(N, -1), (gr == pa).reshape(N, -1)
+    if ((rk == 0) != hit)[scored].any():
+        raise ValueError("rank and greedy disagree: rank 0 means greedy == paths")
+    tokens = scored.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        den = np.where(tokens > 0, tokens, 1).astype(np.float64)
+        none = np.where(tokens > 0, 0.0, np.nan)
+        nll = -np.where(scored, lp, 0.0).sum(axis=1) / den + none
+        acc = (scored & (rk == 0)).sum(axis=1) / den + none
+        mean_rank = np.where(scored, rk, 0).sum(axis=1) / den + none
+    return {"tokens": tokens.astype(np.int64), "nll": nll, "tf_accuracy": acc, "mean_rank": mean_rank}
 
 
 def unique_faces_with_scores(faces):

@@ -96,6 +96,28 @@ def check_beam_options(width, S, variant, retire, return_pointer, no_stop, stop_
         raise ValueError("beam_width needs term_range = (lo, hi) with lo < hi")
 
 
+def check_forced_options(paths, lengths, rows, T, S, retire=False, beam_width=None, logprob=False, return_pointer=False,
+                         stop_callback=None, stop_each_eos=False, extra_mask=None):
+    """What a forced decode rejects (ff_decode_forced's FF_ERR_ARG list, and the options of decode() it has no argument for), as
+    ValueError before anything is launched.  Also the one pass over the paths: every token of positions 0..lengths[r] must lie
+    in [0, S) -- the C entry cannot see them and would clamp.  Returns (paths int64 [rows, T], lengths as a list)."""
+    if retire or beam_width or logprob or return_pointer or stop_callback is not None or stop_each_eos or extra_mask is not None:
+        raise ValueError("scoring given paths excludes retire, beam_width, logprob, return_pointer, stop_callback, "
+                         "stop_each_eos and extra_mask")
+    if not torch.is_tensor(paths) or paths.dtype != torch.int64 or paths.dim() != 2 or tuple(paths.shape) != (rows, T):
+        raise ValueError("paths must be an int64 tensor of shape [%d, %d]" % (rows, T))
+    lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lens) != rows or any(not 0 <= v <= T - 1 for v in lens):
+        raise ValueError("lengths must hold %d values in 0..%d" % (rows, T - 1))
+    if rows:
+        used = torch.arange(T, device=paths.device)[None, :] <= torch.tensor(lens, device=paths.device)[:, None]
+        bad = used & ((paths < 0) | (paths >= S))
+        if bool(bad.any()):
+            r, j = [int(v) for v in bad.nonzero()[0]]
+            raise ValueError("paths[%d, %d] = %d lies outside [0, %d)" % (r, j, int(paths[r, j]), S))
+    return paths, lens
+
+
 class PathEngine:
     """Encoder + greedy pointer decode of one model instance on one ROCm device.
 
@@ -488,4 +510,57 @@ class PathEngine:
             idx = rows.long()
             out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
             out["logits"], out["best"], out["second"] = tl[:, idx], tb[:, idx], ts[:, idx]
+        return out
+
+    def score(self, memory, mask_u8, kv_len, variant, T, paths, lengths, F=1, trace=False,
+              chunk_wireframes=0, chunk_seqs=0, num_streams=1, flags=DEFAULT_FLAGS, x3_min_rows=0, chunk_max_seqs=0,
+              ln_fuse_max_rows=0, retire=False, beam_width=None, logprob=False, return_pointer=False, stop_callback=None,
+              stop_each_eos=False, extra_mask=None):
+        """Teacher-forced scoring of given paths (ff_decode_forced): the decode loop of decode(), fed `paths` instead
+        of its argmax.  paths [N*F, T] int64 shaped like predict (column 0: the row's own start token), lengths [N*F] in 0..T-1:
+        positions 1..lengths[r] of row r are scored; row r belongs to wireframe r // F.  Returns dict(logprob [N*F, T] fp32,
+        greedy [N*F, T] int64, rank [N*F, T] int32 -- column j belongs to paths[:, j], zero past lengths[r] -- seq_logprob [N*F]
+        fp32, steps = max(lengths), [logits [T-1, N*F, S] with trace=True: the masked rows, NaN where a micro-batch did not run]).
+        The options of decode() that a forced decode excludes (retire, beam_width, logprob, return_pointer, stop_callback,
+        extra_mask, stop_each_eos) raise ValueError; tokens outside [0, S) too."""
+        _dev(memory, "memory")
+        self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
+        N, S, E = memory.shape
+        if variant == _L.FF_SEQ2SEQ and F != 1:
+            raise ValueError("the seq2seq variant scores one row per wireframe (F = 1)")
+        for bit, name in ((_L.FF_RETIRE_FINISHED, "FF_RETIRE_FINISHED"), (_L.FF_RETURN_POINTER, "FF_RETURN_POINTER"),
+                          (_L.FF_STOP_EACH_EOS, "FF_STOP_EACH_EOS")):
+            if flags & bit:
+                raise ValueError("scoring given paths excludes the flag %s" % name)
+        B = N * F
+        if torch.is_tensor(paths):
+            self._same_device(paths, "paths")
+        paths, lens = check_forced_options(paths, lengths, B, T, S, retire=retire, beam_width=beam_width, logprob=logprob,
+                                           return_pointer=return_pointer, stop_callback=stop_callback, stop_each_eos=stop_each_eos,
+                                           extra_mask=extra_mask)
+        paths = paths.contiguous()
+        prm = _L.DecodeParams()
+        prm.variant, prm.N, prm.L, prm.F, prm.T = variant, N, S - self.num_token, F, T
+        prm.chunk_wireframes, prm.chunk_seqs, prm.num_streams = chunk_wireframes, chunk_seqs, num_streams
+        prm.chunk_max_seqs, prm.ln_fuse_max_rows = int(chunk_max_seqs), int(ln_fuse_max_rows)
+        prm.flags = flags & ~_L.FF_DEDUP_PAD_ANCHORS
+        prm.x3_min_rows = int(x3_min_rows) if self._planes else 0
+        dev = self.device
+        lens_host = (C.c_int * max(B, 1))(*lens)
+        lens_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+        out = {"logprob": torch.empty((B, T), device=dev, dtype=torch.float32),
+               "greedy": torch.empty((B, T), device=dev, dtype=torch.int64),
+               "rank": torch.empty((B, T), device=dev, dtype=torch.int32),
+               "seq_logprob": torch.empty(B, device=dev, dtype=torch.float32)}
+        tl = torch.full((max(T - 1, 1), B, S), float("nan"), device=dev, dtype=torch.float32) if trace else None
+        fprm = _L.ForcedParams(_p(paths), _p(lens_dev), C.cast(lens_host, C.POINTER(C.c_int)), _p(out["logprob"]), _p(out["greedy"]),
+                               _p(out["rank"]), _p(out["seq_logprob"]))
+        ws = self._workspace(self._lib.ff_decode_forced_workspace_bytes(C.byref(self.model), C.byref(prm)))
+        steps = C.c_int(0)
+        with torch.cuda.device(dev):
+            _L.check(self._lib.ff_decode_forced(C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), C.byref(fprm),
+                                                C.byref(steps), _p(tl), _p(ws), ws.numel(), _stream()), "ff_decode_forced")
+        out["steps"] = steps.value
+        if trace:
+            out["logits"] = tl
         return out

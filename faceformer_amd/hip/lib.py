@@ -133,6 +133,11 @@ class BeamParams(C.Structure):
     _fields_ = [("width", C.c_int), ("beams", fptr), ("scores", fptr), ("trace_parent", fptr)]
 
 
+class ForcedParams(C.Structure):
+    _fields_ = [("paths", fptr), ("lengths", fptr), ("lengths_host", C.POINTER(C.c_int)), ("logprob", fptr), ("greedy", fptr),
+                ("rank", fptr), ("seq_logprob", fptr)]
+
+
 # ff_stop_fn: int (*)(void* user, const int* step_counts, int num_steps)
 STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int)
 
@@ -219,6 +224,11 @@ SIGNATURES = {
                                  C.POINTER(C.c_int), fptr,
                                  fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                  C.c_size_t, C.POINTER(BeamParams), fptr]),
+    "ff_pointer_forced": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, C.c_int,
+                                    fptr, C.c_int, fptr, fptr]),
+    "ff_decode_forced_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams)]),
+    "ff_decode_forced": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, C.POINTER(ForcedParams),
+                                   C.POINTER(C.c_int), fptr, fptr, C.c_size_t, fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 
@@ -250,7 +260,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp and *_beam* ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam* and *_forced* ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

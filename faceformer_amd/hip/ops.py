@@ -431,6 +431,54 @@ def beam_reorder(rows_a, parent, width, rows_b=None):
 
 
 @_on_tensor_device
+def pointer_forced(logits, forced, memory=None, mask=None, kv_len=None, seqs_per_group=1, want_rows=False, want_stats=False):
+    """One teacher-forced pointer step (ff_pointer_forced).  logits [B, S] fp32 raw dot products (masked IN PLACE as
+    the pointer launch masks them), forced [B] int32 tokens in [0, S) (ValueError otherwise; the C entry would clamp them).  Row
+    b belongs to wireframe b // seqs_per_group of mask [W, S] / kv_len [W] / memory [W, S, E].  Returns dict(logprob [B] fp32:
+    log_softmax(masked row)[forced], saturated at -FLT_MAX; greedy [B] int32: the row's argmax, lowest index on ties; rank [B]
+    int32: keys ranked before the forced one; [rows [B, E]: memory[w, forced]]; [stats [B, E/32, 2]: their LayerNorm segment
+    statistics])."""
+    _dev(logits, "logits"), _dev(forced, "forced", torch.int32)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be a 2-D tensor with unit inner stride")
+    B, S = logits.shape
+    if forced.dim() != 1 or forced.numel() != B:
+        raise ValueError("forced must hold one token per row of logits")
+    if B and (int(forced.min()) < 0 or int(forced.max()) >= S):
+        raise ValueError("forced tokens must lie in [0, %d)" % S)
+    spg = int(seqs_per_group)
+    if spg < 1:
+        raise ValueError("seqs_per_group must be positive")
+    nw = (B + spg - 1) // spg
+    dev = logits.device
+    for t, name, dt in ((mask, "mask", torch.uint8), (kv_len, "kv_len", torch.int32)):
+        if t is not None:
+            _dev(t, name, dt)
+            if not t.is_contiguous() or t.size(0) < nw or (name == "mask" and (t.dim() != 2 or t.size(1) != S)):
+                raise ValueError("%s must be contiguous and cover %d wireframes of %d keys" % (name, nw, S))
+    out = {"logprob": torch.empty(B, device=dev, dtype=torch.float32), "greedy": torch.empty(B, device=dev, dtype=torch.int32),
+           "rank": torch.empty(B, device=dev, dtype=torch.int32)}
+    rows, stats, E = None, None, 0
+    if memory is not None:
+        _dev(memory, "memory")
+        if memory.dim() != 3 or not memory.is_contiguous() or memory.size(1) != S or memory.size(0) < nw:
+            raise ValueError("memory must be a contiguous [>= %d, %d, E] tensor" % (nw, S))
+        E = memory.size(2)
+    if want_rows or want_stats:
+        if memory is None:
+            raise ValueError("rows / stats need memory")
+        rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
+        if want_stats:
+            if E % 32:
+                raise ValueError("stats need E % 32 == 0")
+            stats = out["stats"] = torch.empty((B, E // 32, 2), device=dev, dtype=torch.float32)
+    _L.check(_L.load().ff_pointer_forced(
+        _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(forced.contiguous()), _p(out["logprob"]),
+        _p(out["greedy"]), _p(out["rank"]), _p(memory), E, _p(rows), E, _p(stats), _stream()), "ff_pointer_forced")
+    return out
+
+
+@_on_tensor_device
 def gather_rows(memory, tok, seqs_per_group=1):
     _dev(memory, "memory"), _dev(tok, "tok", torch.int32)
     N, S, E = memory.shape

@@ -65,6 +65,7 @@ class SurfaceFormerBase(nn.Module):
         self.return_logprob = False    # forward_eval also returns inputs["predict_logprob"], shaped like inputs["predict"]: the
                                        # log-probability log_softmax(masked logits)[token] of every greedy selection, 0 at the
                                        # start token and wherever predict is zero padded.  Not with dist.decode_sharded
+        self.last_score_stats = None   # score(): {"rows", "steps"} of the last call
         self.beam_width = 0            # parallel model: >= 1 decodes with this many beams per anchor (beam search):
                                        # forward_eval adds predict_beams / predict_beam_scores, predict is beam 0.  0 = greedy.
                                        # Not with retire_finished, return_logprob, an extra mask, dist.decode_sharded or the
@@ -261,6 +262,30 @@ class SurfaceFormerBase(nn.Module):
             return None
         pad = torch.zeros((extra.size(0), self.num_token), dtype=torch.bool, device=extra.device)
         return torch.cat([pad, extra.to(torch.bool)], dim=1).to(torch.uint8).contiguous()
+
+    def _score(self, inputs, variant, T, F, paths, lengths):
+        """Teacher-forced scoring of `paths` (PathEngine.score) with this model's decode options; adds the score_*
+        keys to `inputs`.  The wireframes are scored in batch order: a forced decode has no padding-anchor de-duplication, so
+        every wireframe is F rows wide whatever its edge count -- the micro-batches forward_eval gets by sorting are the ones
+        this plan has already -- and there is no sort_by_edges permutation to undo.  stop_each_eos (seq2seq) is a rule of the
+        greedy decode and is not looked at: a forced decode has no stop rule."""
+        if not self.engine_supported():
+            raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
+        eng, memory, mask, kv_len = self._encode(inputs)
+        out = eng.score(memory, mask, kv_len, variant, T, paths.to(memory.device), lengths, F=F,
+                        chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs, chunk_max_seqs=self.chunk_max_seqs,
+                        num_streams=self.num_streams, flags=self.decode_flags, x3_min_rows=self.x3_min_rows,
+                        ln_fuse_max_rows=self.ln_fuse_max_rows,
+                        retire=bool(getattr(self, "retire_finished", False)), beam_width=int(getattr(self, "beam_width", 0) or 0),
+                        logprob=bool(getattr(self, "return_logprob", False)), extra_mask=inputs.get("extra_mask"))
+        N = memory.size(0)
+        shape = (N, F, T) if variant == _L.FF_PARALLEL else (N, T)
+        inputs["score_logprob"] = out["logprob"].view(shape)
+        inputs["score_greedy"] = out["greedy"].view(shape)
+        inputs["score_rank"] = out["rank"].view(shape)
+        inputs["score_seq_logprob"] = out["seq_logprob"].view(shape[:-1])
+        self.last_score_stats = {"rows": out["logprob"].size(0), "steps": out["steps"]}
+        return inputs
 
     def forward(self, inputs):
         if self.training:

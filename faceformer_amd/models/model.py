@@ -70,3 +70,25 @@ class SurfaceFormer(SurfaceFormerBase):
         if want_lp:
             inputs["predict_logprob"] = out["logprob"]
         return inputs
+
+    def label_paths(self, inputs):
+        """score()'s defaults, the data set's own labels: (paths N x T = label, lengths N = num_label - 1)."""
+        return inputs["label"][:, :self.num_labels], torch.as_tensor(inputs["num_label"]).reshape(-1) - 1
+
+    @torch.no_grad()
+    def score(self, inputs, paths=None, lengths=None):
+        """Teacher-forced scoring of token sequences.  paths N x T int64 shaped like predict (column 0: SOS),
+        lengths N in 0..T-1: positions 1..lengths are scored.  Defaults: the data set's own labels, paths = label and lengths =
+        num_label - 1.  Adds score_logprob / score_greedy / score_rank N x T and score_seq_logprob N; see
+        SurfaceFormer_Parallel.score.  Not with return_logprob, an extra mask or the sub-module loop; stop_each_eos, a rule of the
+        greedy decode, is not looked at."""
+        T = self.num_labels
+        if paths is None:
+            paths, default_lengths = self.label_paths(inputs)
+            lengths = default_lengths if lengths is None else lengths
+        elif lengths is None:
+            raise ValueError("score(): paths need lengths")
+        paths = torch.as_tensor(paths).to(torch.int64)
+        if paths.dim() != 2 or paths.size(0) != inputs["input"].size(0) or paths.size(1) != T:
+            raise ValueError("paths must be N x %d" % T)
+        return self._score(inputs, _L.FF_SEQ2SEQ, T, 1, paths, torch.as_tensor(lengths).reshape(-1))

@@ -110,3 +110,36 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
             self.last_decode_stats["decoded_seqs"] *= W
             self.last_decode_stats["beam_width"] = W
         return inputs
+
+    def label_paths(self, inputs):
+        """score()'s defaults, the data set's own labels: (paths N x F x T = label[:, :max(num_input)], lengths N x F = the
+        non-PAD tokens after column 0 by label_mask; unused rows, which hold one token, get 0)."""
+        T = self.max_face_length
+        ni_in = inputs["num_input"]
+        F = max(int(n) for n in (ni_in.tolist() if torch.is_tensor(ni_in) else ni_in))
+        label = inputs["label"]
+        lmask = inputs["label_mask"] if "label_mask" in inputs else label == self.token.PAD
+        return label[:, :F, :T], (~lmask[:, :F, 1:T].to(torch.bool)).sum(dim=-1)
+
+    @torch.no_grad()
+    def score(self, inputs, paths=None, lengths=None):
+        """Teacher-forced scoring of face loops: how probable is a GIVEN path under the model as it decodes?
+        paths N x F x T int64 shaped like predict -- column 0 is the row's own start token (an edge token, not the anchor
+        index), F is whatever the caller passes -- and lengths N x F in 0..T-1: positions 1..lengths of a row are scored.
+        Defaults: the data set's own labels, paths = label[:, :max(num_input)], lengths = the non-PAD tokens after column 0
+        (label_mask; unused rows get 0).  Adds score_logprob / score_greedy / score_rank N x F x T (column j belongs to
+        paths[..., j]; zero past the row's length; score_greedy's column 0 repeats the start token) and score_seq_logprob
+        N x F.  Not with retire_finished, beam_width, return_logprob, an extra mask or the sub-module loop (ValueError); tokens
+        outside [0, S) raise ValueError.  forward / forward_eval are untouched."""
+        T = self.max_face_length
+        if paths is None:
+            paths, default_lengths = self.label_paths(inputs)
+            lengths = default_lengths if lengths is None else lengths
+        elif lengths is None:
+            raise ValueError("score(): paths need lengths")
+        paths = torch.as_tensor(paths).to(torch.int64)
+        if paths.dim() != 3 or paths.size(0) != inputs["input"].size(0) or paths.size(2) != T:
+            raise ValueError("paths must be N x F x %d" % T)
+        F = paths.size(1)
+        lengths = torch.as_tensor(lengths).reshape(-1)
+        return self._score(inputs, _L.FF_PARALLEL, T, F, paths.reshape(-1, T), lengths)

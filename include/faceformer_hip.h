@@ -671,6 +671,61 @@ int ff_decode_beam(const ff_model* m, const ff_decode_params* p,
                    float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                    void* workspace, size_t workspace_bytes, const ff_beam_params* beam, ff_stream_t stream);
 
+/* ---- teacher-forced scoring of given token paths (opt-in; entries added within ABI 105) ------------------------
+ * The reference's eval loops (model_para.py:216-233; model.py:169-219) re-encode the prefix with the unmasked decoder at every
+ * step and append select_next's argmax (model_para.py:173-179, model.py:161-167).  These entries restate exactly those call
+ * sites with ONE change: the token appended for the next step comes from a given path, never from the argmax.  What is scored
+ * is the masked logit row l[0..S) select_next forms (masked keys at finfo.min = -FLT_MAX), g = the forced token, m = max l:
+ *   logprob = (l[g] - m) - log sum_s exp(l[s] - m), fp32, saturated at -FLT_MAX (a masked forced key scores -FLT_MAX; when
+ *             every key of the row is masked it scores -log S, ff_pointer_argmax_lp's value);
+ *   greedy  = argmax l, lowest index on ties (what select_next would have taken given the forced prefix);
+ *   rank    = #{s : l[s] > l[g], or l[s] == l[g] and s < g}; rank 0 <=> greedy == g.
+ *
+ * ff_pointer_forced: one step of B sequences.  Row b belongs to wireframe b / seqs_per_group (mask [wireframes, S], kv_len
+ *   [wireframes], memory [wireframes, S, E]; B need not be a multiple of seqs_per_group).
+ *   logits  [B, ldlogits] raw dot products; masked IN PLACE as the pointer launch masks them (key padding mask, kv_len).
+ *   forced  [B] int32 DEVICE tokens.  The entry cannot see device data: a token outside [0, S) is CLAMPED into that range, so
+ *           that no launch reads outside `memory` -- callers that want an error check their tokens first (the Python layers do).
+ *   logprob [B] fp32, greedy [B] int32, rank [B] int32: as defined above.
+ *   next_rows (optional, with memory and E; ldnext >= E): row b receives memory[wireframe, forced[b], :], the next decoder
+ *           input row.  next_stats (optional, with next_rows; E % 32 == 0) [B, E/32, 2]: (mean, M2) of every 32-column segment
+ *           of that row -- the LayerNorm segment statistics ff_gemm_f32_ln consumes (ln_stats_in).
+ * ff_decode_forced: the decode loop fed `paths`.  ff_decode's model / parameters / memory / mask / kv_len, then
+ *   paths [N*F, T] int64 DEVICE, shaped like predict: column 0 is the row's own start token (parallel: NOT derived from the
+ *           anchor index; seq2seq: SOS), column j >= 1 the token forced at position j; row r belongs to wireframe r / F (F is
+ *           whatever the caller passes; 1 for FF_SEQ2SEQ).  Tokens outside [0, S) are clamped, as above.
+ *   lengths [N*F] int32 DEVICE and lengths_host, the same values on the HOST, 0 <= len <= T-1 (else FF_ERR_ARG): positions
+ *           1..len of the row are scored.  A micro-batch runs max(lengths of its rows) steps, known before the first launch;
+ *           rows past their own length stay in it, are computed and ignored.  No stop rule, no host counters, no host
+ *           synchronisation inside the loop; with max(lengths) == 0 no decoder launch is made.
+ *   logprob [N*F, T] fp32, greedy [N*F, T] int64, rank [N*F, T] int32, laid out like predict: column j >= 1 belongs to
+ *           paths[:, j]; column 0 is 0 / the start token / 0; everything past lengths[r] is 0.
+ *   seq_logprob [N*F] fp32: the sum of the row's scored log-probabilities (ascending positions, saturated at -FLT_MAX).
+ *   steps_done (optional HOST int): max(lengths).  trace_logits (optional) [T-1, N*F, S]: the masked rows of every step a
+ *           row's micro-batch ran (tests).
+ * Micro-batches are planned as ff_decode plans them WITHOUT padding-anchor de-duplication (FF_DEDUP_PAD_ANCHORS is cleared: the
+ * rows are arbitrary); a step is the decoder pass, the pointer GEMM and ff_pointer_forced in place of the pointer launch.
+ * FF_ERR_ARG for FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_STOP_EACH_EOS and a stop_fn; FF_NO_STOP is ignored (there is no
+ * stop rule).  ff_decode_forced_workspace_bytes: ff_decode_workspace_bytes' rules (num_input_host NULL) plus the per-step
+ * records, taken last.  ff_decode, ff_decode_lp and ff_decode_beam launch and lay out what they did before these entries. */
+int ff_pointer_forced(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                      int seqs_per_group, const int* forced, float* logprob, int* greedy, int* rank,
+                      const float* memory, int E, float* next_rows, int ldnext, float* next_stats, ff_stream_t stream);
+typedef struct ff_forced_params {
+  const int64_t* paths;
+  const int* lengths;
+  const int* lengths_host;
+  float* logprob;
+  int64_t* greedy;
+  int* rank;
+  float* seq_logprob;
+} ff_forced_params;
+size_t ff_decode_forced_workspace_bytes(const ff_model* m, const ff_decode_params* p);
+int ff_decode_forced(const ff_model* m, const ff_decode_params* p,
+                     const float* memory, const unsigned char* mask, const int* kv_len,
+                     const ff_forced_params* forced, int* steps_done, float* trace_logits,
+                     void* workspace, size_t workspace_bytes, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

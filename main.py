@@ -27,6 +27,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -60,13 +61,26 @@ def decode_batch_beams(model, batch):
     return out["predict"].cpu().numpy(), out["predict_beams"].cpu().numpy(), out["predict_beam_scores"].cpu().numpy()
 
 
-def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None):
+def score_batch(model, batch):
+    """`model.score(batch)` on the data set's own label rows (--score-labels) as numpy arrays: dict(logprob, greedy, rank, paths
+    [N, ..., T], lengths, seq_logprob [N, ...])."""
+    out = model.score(dict(batch))
+    paths, lengths = model.label_paths(batch)
+    lp = out["score_logprob"]
+    return {"logprob": lp.cpu().numpy(), "greedy": out["score_greedy"].cpu().numpy(), "rank": out["score_rank"].cpu().numpy(),
+            "paths": paths.cpu().numpy(), "lengths": lengths.reshape(lp.shape[:-1]).cpu().numpy(), "seq_logprob": out["score_seq_logprob"].cpu().numpy()}
+
+
+def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
     beams (--beam; (tokens [F, W, T], scores [F, W]) of this sample): the record also gets `pred_beam_faces` and
     `pred_beam_face_scores`, the de-duplicated faces over ALL beams of the wireframe's own anchors ranked by their best beam
-    score; `pred_faces` stays what beam 0 (pred) gives."""
+    score; `pred_faces` stays what beam 0 (pred) gives.
+    label_scores (--score-labels; this sample's slice of score_batch): the record also gets `label_logprob` (the summed
+    log-probability of every scored label row, in row order), `label_nll` (per token) and `label_tf_accuracy`
+    (faces.score_summary; null when the sample has no scored label token)."""
     scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
@@ -103,6 +117,12 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None):
         ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
         rec["pred_beam_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
         rec["pred_beam_face_scores"] = [s for _, _, s, _ in ranked]
+    if label_scores is not None:
+        ls = {k: np.asarray(v)[None] for k, v in label_scores.items()}
+        sm = FZ.score_summary(ls["logprob"], ls["greedy"], ls["rank"], ls["paths"], ls["lengths"])
+        rec["label_logprob"] = [float(v) for v, n in zip(ls["seq_logprob"].reshape(-1), ls["lengths"].reshape(-1)) if n > 0]
+        rec["label_nll"] = float(sm["nll"][0]) if sm["tokens"][0] else None
+        rec["label_tf_accuracy"] = float(sm["tf_accuracy"][0]) if sm["tokens"][0] else None
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
@@ -123,7 +143,7 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
-             retire_finished=False, fp16=False, scores=False, beam=0):
+             retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -131,7 +151,13 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     fp16: the decoder's large projections and its cross-attention take one fp16 product each (split_kind "fp16").
     scores: every record gains `pred_face_scores` (record_of); single-process runs only.
     beam: beam search with this many beams per anchor (parallel model, single process, not with retire_finished / scores):
-    every record gains `pred_beam_faces` / `pred_beam_face_scores`."""
+    every record gains `pred_beam_faces` / `pred_beam_face_scores`.
+    score_labels: every record gains `label_logprob` / `label_nll` / `label_tf_accuracy`, the model's teacher-forced scores of
+    the sample's own label rows (models' score()); single process, not with retire_finished / scores / beam."""
+    if score_labels and (retire_finished or scores or beam):
+        raise ValueError("--score-labels does not combine with --retire-finished, --scores or --beam (a forced decode excludes them)")
+    if score_labels and dist_mod is not None and dist_mod.get_world_size() > 1:
+        raise ValueError("--score-labels (score) is not implemented for multi-rank runs: the scores are not gathered across ranks")
     if beam and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores):
         raise ValueError("--beam applies to SurfaceFormer_Parallel only, and not together with --retire-finished or --scores")
     if beam and dist_mod is not None and dist_mod.get_world_size() > 1:
@@ -175,11 +201,12 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
             lps, bms = None, list(zip(bt, bs))
         else:
             pred, lps = decode_batch_scored(model, batch) if scores else (decode_batch(model, batch), None)
+        lsc = score_batch(model, batch) if score_labels else None
         total += time.time() - t0
         done += len(idx)
         for k, i in enumerate(idx):
             text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel, lps[k] if scores else None,
-                                 bms[k] if beam else None)
+                                 bms[k] if beam else None, {n: v[k] for n, v in lsc.items()} if score_labels else None)
             stats.append(st)
             records.append((os.path.splitext(os.path.basename(items[k]["name"]))[0], text))
         print("Avg Time", total / done, "seconds.")
@@ -224,6 +251,10 @@ def build_parser():
                         help="parallel model: beam search with W (1..8) beams per anchor edge (DESIGN.md 13); pred_faces come from "
                              "the best beam, and every JSON record gains pred_beam_faces / pred_beam_face_scores: the faces of all "
                              "beams, de-duplicated and ranked by score; single-process runs only")
+    parser.add_argument("--score-labels", action="store_true",
+                        help="every JSON record gains label_logprob (per label row), label_nll (per token) and label_tf_accuracy: "
+                             "the model's teacher-forced scores of the sample's own label rows (DESIGN.md 14); single-process runs "
+                             "only, not with --retire-finished, --scores or --beam")
     return parser
 
 
@@ -242,7 +273,8 @@ def main(argv=None):
         device = "cuda:%d" % local_rank
         dist_mod.init_process_group("nccl", device_id=torch.device(device))
     run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
-             retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam)
+             retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam,
+             score_labels=args.score_labels)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
