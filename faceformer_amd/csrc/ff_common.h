@@ -139,6 +139,19 @@ int ff_forced_tokens(const int64_t* paths, int* tok, int rows, int T, int S, hip
 int ff_forced_finalize(const int* tok, const float* lp_all, const int* greedy_all, const int* rank_all, const int* lengths, int rows,
                        int T, float* logprob, int64_t* greedy, int* rank, float* seq_logprob, hipStream_t st);
 
+// ff_pointer_sample with the decode engine's hand-over (ff_sample.hip): arrive counts the launch's rows, the last block stores
+// count_ge to host_slot.  And the start state / output packing of a sampled decode (kernels' comments).
+int ff_pointer_sample_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                           int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
+                           float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok, float* logprob,
+                           int* fin_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                           int* count_ge, int ge_bound, int* arrive, int* host_slot, ff_stream_t stream);
+int ff_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F, const int* num_input,
+                   int pad_tok, int term_lo, int term_hi, hipStream_t st);
+int ff_sample_finalize(const int* tok, const float* lp, const int* fin, int Btot, int T, const int* steps_dev, const int* num_input,
+                       int dedup, int F, int R, int w0, int nw, int Fc, int f0, int b0, int64_t* samples, float* logprob,
+                       float* scores, int64_t* predict, int* seq_of_row, hipStream_t st);
+
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);
 

@@ -27,6 +27,11 @@
 // Forced decode (ff_decode_forced, opt-in, both variants): the same run fed a given path -- the token array holds
 // the caller's paths from the start, a step's pointer launch is replaced by ff_pointer_forced (which appends the FORCED token's
 // row), every micro-batch runs max(lengths of its rows) steps, and there is no stop rule: no counters, no check points.
+//
+// Sampled decode (ff_decode_sample, opt-in, parallel variant): R sequences per anchor in the beam decode's layout
+// (plan_beam_chunks), independent of each other -- no reorder.  A step's pointer launch is replaced by ff_pointer_sample, which
+// reads the caller's uniforms through a per-sequence row_id; every step leaves its (token, log-probability, finished) row in
+// the workspace and the output is packed from the rows up to the stop step.
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
@@ -242,6 +247,10 @@ struct DecodeBuffers {
   // forced decode: [T-1, Btot] each, row s = what step s scored (log-probability of the forced token, the argmax, the rank)
   float* fc_lp;
   int *fc_greedy, *fc_rank;
+  // sampled decode: [T, Btot] each, row s = the samples' state after s steps (row 0: the start state); and the draw every
+  // sequence reads, [Btot], written once per call
+  float* sm_lp;
+  int *sm_fin, *sm_row;
 };
 
 // A micro-batch is a contiguous range [b0, b0 + Bc) of the COMPACT sequence index: nw >= 1 consecutive
@@ -368,8 +377,9 @@ bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
 // Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
 // want_lp: also the log-probability rows (ff_decode_lp) -- taken LAST, so that everything else lies where it lies without them.
 // beam: also the per-step records of a beam decode (ff_decode_beam), last as well.  forced: those of a forced decode, likewise.
+// sample: those of a sampled decode and its row_id array, likewise.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
-                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false, bool forced = false) {
+                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false, bool forced = false, bool sample = false) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
   const int ns = plan_streams(p);
   const size_t Rmax = (size_t)(T - 1 > 0 ? T - 1 : 1) * Bch;
@@ -429,6 +439,11 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     b.fc_lp = bp.take<float>(n);
     b.fc_greedy = bp.take<int>(n);
     b.fc_rank = bp.take<int>(n);
+  }
+  if (sample) {
+    b.sm_lp = bp.take<float>((size_t)T * Btot);
+    b.sm_fin = bp.take<int>((size_t)T * Btot);
+    b.sm_row = bp.take<int>(Btot);
   }
   if (out) *out = b;
   return bp.off;
@@ -721,6 +736,8 @@ struct DecodeRun {
   const ff_forced_params* forced = nullptr;   // ff_decode_forced (null otherwise)
   std::vector<int> chunk_steps;               // ... steps every micro-batch runs: the largest length among its rows
   int forced_steps = 0;                       // ... and the largest of those
+  const ff_sample_params* sample = nullptr;   // ff_decode_sample (null otherwise)
+  int R = 0;                                  // ... its samples per anchor; 0 without sampling
   int validate(const ff_model* m_, const ff_decode_params* p_, const DecodeIO& io_, const void* workspace) {
     m = m_; io = io_;
     FF_RETURN_IF(check_model(m));
@@ -762,11 +779,12 @@ struct DecodeRun {
   int bind_chunks(void* workspace, size_t workspace_bytes) {
     const int ns_req = plan_streams(p);
     int max_bc = 0;
-    if (W) plan_beam_chunks(p, io.num_input_host, ns_req, W, &chunks, &Btot, &max_bc);
+    if (W || R) plan_beam_chunks(p, io.num_input_host, ns_req, W ? W : R, &chunks, &Btot, &max_bc);
     else plan_chunks(p, io.num_input_host, ns_req, &chunks, &Btot, &max_bc);
     nch = (int)chunks.size();
     Bump bp(workspace, workspace_bytes);
-    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr, W > 0, forced != nullptr);
+    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr, W > 0, forced != nullptr,
+                  R > 0);
     if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
     for (Chunk& c : chunks) {
       c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
@@ -916,6 +934,12 @@ struct DecodeRun {
         FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
         continue;
       }
+      if (R) {
+        FF_RETURN_IF(ff_sample_init(buf.tok_all + c.b0, buf.sm_lp + c.b0, buf.sm_fin + c.b0, buf.sm_row + c.b0, c.Bc, c.Fc / R, R, c.f0,
+                                    c.w0, F, io.num_input + c.w0, m->num_token - 1, p->term_lo, p->term_hi, sts[c.sid]));
+        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
+        continue;
+      }
       // (retirement: the start tokens of the slots go to the chunk's perm area, free until its first compaction)
       hipLaunchKernelGGL(init_tokens_kernel, dim3(ff_cdiv(c.Bc, 256)), dim3(256), 0, sts[c.sid], buf.tok_all + c.b0,
                          c.Bc, c.Fc, c.f0, io.num_input ? io.num_input + c.w0 : nullptr, p->variant, m->num_token - 1,
@@ -937,13 +961,17 @@ struct DecodeRun {
       nslots += c.Bl;
       hipStream_t st = sts[c.sid];
       const Scratch& sc = buf.scr[c.sid];
-      const size_t trow = (size_t)step * ((size_t)N * F * (W ? W : 1)) + c.b0;  // traces: step stride N*F (N*F*W with beams; caller sizes them so)
+      const size_t trow = (size_t)step * ((size_t)N * F * (W ? W : (R ? R : 1))) + c.b0;  // traces: step stride N*F (N*F*W with beams, N*F*R with samples; caller sizes them so)
       const size_t slot = (size_t)step * nch + (size_t)(&c - chunks.data());
       const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bl);
       // (retirement: the logits rows are in slot order; a traced step scatters them to the sequences' rows below)
       float* logits_dst = (io.trace_logits && !retire) ? io.trace_logits + trow * S : sc.logits;
       if (W) {
         FF_RETURN_IF(beam_step(c, sc, step, slot, folded_head, logits_dst, trow, st));
+        continue;
+      }
+      if (R) {
+        FF_RETURN_IF(sample_step(c, sc, step, slot, folded_head, logits_dst, st));
         continue;
       }
       ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, lagged ? buf.arrive + slot : nullptr,
@@ -987,6 +1015,25 @@ struct DecodeRun {
       FF_CHECK_HIP(hipMemcpyAsync(beam->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
     if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
     return FF_OK;
+  }
+  // Sampled decode, step `step` of one micro-batch: the decoder pass, the pointer GEMM (always the GEMM + reduce form, as a
+  // decode with log-probabilities), then ff_pointer_sample in place of the pointer launch.  It reads the state row `step` and
+  // this step's uniforms through the chunk's row_id, and writes row t = step + 1, the chunk's next x0 rows (with their
+  // statistics) and the stop counter.  Every step has rows of its own: one enqueued past the stop changes nothing that is read.
+  int sample_step(const Chunk& c, const Scratch& sc, int step, size_t slot, bool folded_head, float* logits_dst, hipStream_t st) {
+    const int t = step + 1;
+    const float* mem_w = io.memory + (size_t)c.w0 * S * E;
+    FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
+    if (!folded_head)
+      FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
+                                       (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
+    const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
+    const int rows = N * F * R;
+    return ff_pointer_sample_sync(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, c.Bc, c.Fc,
+                                  sample->uniforms + (size_t)step * rows, rows, buf.sm_row + c.b0, buf.sm_fin + in, sample->temperature,
+                                  sample->top_k, sample->top_p, p->term_lo, p->term_hi, buf.tok_all + out, buf.sm_lp + out,
+                                  buf.sm_fin + out, mem_w, E, c.x0 + (size_t)t * c.Bc * E, E, c.x0stat, buf.cnt_ge + slot,
+                                  m->num_token, lagged ? buf.arrive + slot : nullptr, lagged ? pool->hpin_dev + slot : nullptr, st);
   }
   // ---- forced decode ------------------------------------------------------------------------------------------------------------
   // The caller's paths as the token array (main stream, in front of the prologue's fork: every stream sees them).
@@ -1178,6 +1225,12 @@ struct DecodeRun {
                                       c.w0, c.nw, c.Fc / W, c.f0, c.b0, beam->beams, beam->scores, io.predict, io.seq_of_row, main_st));
         continue;
       }
+      if (R) {
+        FF_RETURN_IF(ff_sample_finalize(buf.tok_all, buf.sm_lp, buf.sm_fin, Btot, T, buf.steps_dev, io.num_input, dedup ? 1 : 0, F, R,
+                                        c.w0, c.nw, c.Fc / R, c.f0, c.b0, sample->samples, sample->logprob, sample->scores,
+                                        io.predict, io.seq_of_row, main_st));
+        continue;
+      }
       const long total = (long)c.nw * F * T;
       const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
       hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
@@ -1215,7 +1268,7 @@ struct DecodeRun {
 
 // One decode call from validation to the packed outputs (ff_decode / ff_decode_lp: beam null; ff_decode_beam).
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam, const ff_forced_params* forced = nullptr);
+               const ff_beam_params* beam, const ff_forced_params* forced = nullptr, const ff_sample_params* sample = nullptr);
 
 }  // namespace
 
@@ -1380,11 +1433,45 @@ extern "C" int ff_decode_forced(const ff_model* m, const ff_decode_params* p, co
                     workspace, workspace_bytes, nullptr, forced);
 }
 
+extern "C" size_t ff_decode_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
+                                                   int num_samples) {
+  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0 || num_samples < 1 || num_samples > 64) return 0;
+  int btot = 0, max_bc = 0, nch = 0;
+  plan_beam_chunks(p, num_input_host, 1, num_samples, nullptr, &btot, &max_bc, &nch);
+  Bump bp(nullptr, 0);
+  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, false, false, true) + 256;
+}
+
+extern "C" int ff_decode_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                const unsigned char* mask, const int* kv_len, const int* num_input,
+                                const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                                int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                                float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                                size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream) {
+  FF_CHECK_ARG(m && p && sample, "ff_decode_sample: null model, params or sample params");
+  FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode_sample: sampling is a parallel-variant option");
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
+               "ff_decode_sample: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask");
+  FF_CHECK_ARG(sample->num_samples >= 1 && sample->num_samples <= 64, "ff_decode_sample: num_samples=%d outside 1..64", sample->num_samples);
+  FF_CHECK_ARG(sample->temperature >= 0.f && sample->temperature <= 3.402823466e+38f && sample->top_k >= 0 && sample->top_p > 0.f &&
+                   sample->top_p <= 1.f, "ff_decode_sample: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]",
+               (double)sample->temperature, sample->top_k, (double)sample->top_p);
+  FF_CHECK_ARG(p->term_lo < p->term_hi, "ff_decode_sample: empty terminator range [%d, %d)", p->term_lo, p->term_hi);
+  FF_CHECK_ARG(sample->uniforms && sample->samples && sample->logprob && sample->scores && !trace_best && !trace_second && !pointer_out,
+               "ff_decode_sample: uniforms, samples, logprob and scores required; no best / second traces, no pointer_out");
+  FF_CHECK_ARG(p->N > 0 && p->F > 0 && (long long)p->N * p->F * sample->num_samples < (1LL << 31), "ff_decode_sample: bad sizes");
+  return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
+                                   nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr},
+                    workspace, workspace_bytes, nullptr, nullptr, sample);
+}
+
 namespace {
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam, const ff_forced_params* forced) {
+               const ff_beam_params* beam, const ff_forced_params* forced, const ff_sample_params* sample) {
   DecodeRun r;
   r.forced = forced;
+  r.sample = sample;
+  r.R = sample ? sample->num_samples : 0;
   r.beam = beam;
   r.W = beam ? beam->width : 0;
   FF_RETURN_IF(r.validate(m, p, io, workspace));

@@ -1,0 +1,300 @@
+// Temperature / top-k / top-p sampling over the pointer head (opt-in, parallel variant): one step's draw of every
+// sequence, and the start state / output packing of a sampled decode.
+//
+// pointer_sample_kernel: one wavefront per sequence, four per block, as pointer_reduce_kernel.  A finished sequence appends
+// token 0 and draws nothing.  Every other one masks and reduces its raw logit row exactly as the greedy launch does
+// (ff_pointer_mask_reduce<true>, ff_device.h: row maximum m, argmax with torch's tie rule, sum exp(l - m)); a row without a live
+// key takes token 0, temperature 0 takes the argmax.  Otherwise, with w[s] = exp((l[s] - m) / temperature) over the live keys:
+//   top-k   v_K, the K-th largest logit, by bisection on the order-preserving integer image of the fp32 value: 32 rounds, each
+//           a count of the keys at or above the candidate (one ballot per 64 keys).  Exact; ties at v_K are all kept.
+//   top-p   theta, the largest kept logit at which the mass of the keys >= theta reaches P * (mass of the kept keys), by the same
+//           bisection.  A mass is the lane's terms added in key order, then a butterfly: a fixed tree of fp32 additions of
+//           non-negative terms, hence monotone in the key set, so the bisection is well defined and the same on every run.
+//   draw    inclusive prefix sums c[s] of w over the kept keys in ascending key index: a wave scan per 64 consecutive keys plus
+//           the carried total of the chunks before (at most ceil(S / 64) + 6 dependent additions); Z is the last carry.  The
+//           scan runs twice -- once for Z, once more for the ballot on c[s] > u * Z -- with the same operations in the same
+//           order.  No key crosses: the last kept key.
+// The row is re-read from memory in every round (each lane reads the keys it masked itself): no LDS beyond the four counter
+// words, no scratch, whatever S and K are.  Lane 0 stores token, log-probability (under the MODEL, (l[tok] - m) - log sum,
+// saturated at -FLT_MAX) and the finished flag; the wave appends memory[w, token] through ff_pointer_append_row, so the row
+// carries its LayerNorm segment statistics and a sampled decode keeps FF_L0_FOLD.  Stop counter: beam_select_kernel's scheme.
+//
+// The uniform of a row is uniforms[row_id[b]], clamped into [0, 1 - 2^-24]: a draw is keyed by the OUTPUT row, never by the
+// sequence's place in a launch.  There is no random number generator in device code.
+#include <float.h>
+
+#include "ff_common.h"
+#include "ff_device.h"
+
+namespace {
+
+struct SampleArgs {
+  PointerArgs p;             // logits / masks / memory / next rows / counters of the B launch rows
+  const float* uniforms;     // [num_uniforms] this step's draws
+  const int* row_id;         // [B] the draw every launch row reads (null: b); clamped into [0, num_uniforms)
+  int num_uniforms;
+  const int* fin_in;         // [B] nonzero: finished before this step (null: none)
+  int* fin_out;              // [B] out
+  int* tok; float* logprob;  // [B] out
+  float temperature; int top_k; float top_p;
+};
+
+// fp32 -> unsigned, order preserving (-0 counts as +0); and back
+__device__ __forceinline__ unsigned sample_key(float v) {
+  const unsigned b = __float_as_uint(v + 0.f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float sample_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// inclusive scan of one value per lane, lanes in ascending order (Hillis-Steele: six rounds)
+__device__ __forceinline__ float sample_wave_scan(float c, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float o = __shfl_up(c, off, FF_WAVE);
+    if (lane >= off) c += o;
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(256) void pointer_sample_kernel(SampleArgs a) {
+  __shared__ int s_cnt[4];
+  const PointerArgs& pa = a.p;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.x * 4 + wv;
+  const float FILL = -FLT_MAX;
+  int nge = 0;
+  if (b < pa.B) {   // (wave-uniform)
+    const int S = pa.S;
+    const int was_fin = a.fin_in ? ff_ld4i(a.fin_in + b) : 0;
+    int tok = 0;
+    float lp = 0.f;
+    if (!was_fin) {
+      float m, b2, lsum;
+      int i1;
+      ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &i1, &lsum);
+      const float* lrow = pa.logits + (size_t)b * pa.ldlogits;
+      const int nchunk = (S + 63) >> 6;
+      const float tau = a.temperature;
+      if (m == FILL) tok = 0;            // no live key (masked keys hold -FLT_MAX)
+      else if (tau == 0.f) tok = i1;     // greedy's rule
+      else {
+        int nlive = 0;
+        for (int c = 0; c < nchunk && a.top_k > 0; ++c) {
+          const int s = c * 64 + lane;
+          nlive += __popcll(__ballot(s < S && ff_ld4(lrow + s) > FILL));
+        }
+        // top-k: the largest key image with at least K keys at or above it is the image of the K-th largest logit
+        float thr = FILL;
+        if (a.top_k > 0 && a.top_k < nlive) {
+          unsigned th = 0;
+          for (unsigned bit = 0x80000000u; bit; bit >>= 1) {
+            const unsigned cand = th | bit;
+            int cnt = 0;
+            for (int c = 0; c < nchunk; ++c) {
+              const int s = c * 64 + lane;
+              cnt += __popcll(__ballot(s < S && sample_key(ff_ld4(lrow + s)) >= cand));
+            }
+            if (cnt >= a.top_k) th = cand;
+          }
+          thr = sample_unkey(th);
+        }
+        // top-p over the keys top-k kept
+        if (a.top_p < 1.f) {
+          const float vk = thr;
+          float target = 0.f;
+          unsigned th = 0;
+          for (int round = -1; round < 32; ++round) {   // round -1: the mass of everything top-k kept
+            const unsigned cand = round < 0 ? 0u : (th | (0x80000000u >> round));
+            float mass = 0.f;
+            for (int s = lane; s < S; s += 64) {
+              const float v = ff_ld4(lrow + s);
+              const bool in = v > FILL && v >= vk && sample_key(v) >= cand;
+              mass += in ? __expf((v - m) / tau) : 0.f;
+            }
+            mass = ff_wave_sum(mass);
+            if (round < 0) target = a.top_p * mass;
+            else if (mass >= target) th = cand;
+          }
+          thr = sample_unkey(th);
+        }
+        // draw
+        int rid = a.row_id ? ff_ld4i(a.row_id + b) : b;
+        rid = min(max(rid, 0), a.num_uniforms - 1);
+        const float u = fminf(fmaxf(ff_ld4(a.uniforms + rid), 0.f), 0.99999994f);   // 1 - 2^-24
+        float Z = 0.f;
+        for (int c = 0; c < nchunk; ++c) {
+          const int s = c * 64 + lane;
+          const float v = s < S ? ff_ld4(lrow + s) : FILL;
+          const float w = (v > FILL && v >= thr) ? __expf((v - m) / tau) : 0.f;
+          Z = Z + __shfl(sample_wave_scan(w, lane), 63, FF_WAVE);
+        }
+        const float uz = u * Z;
+        float carry = 0.f;
+        int last = 0;
+        bool found = false;
+        for (int c = 0; c < nchunk && !found; ++c) {
+          const int s = c * 64 + lane;
+          const float v = s < S ? ff_ld4(lrow + s) : FILL;
+          const bool kept = v > FILL && v >= thr;
+          const float local = sample_wave_scan(kept ? __expf((v - m) / tau) : 0.f, lane);
+          const unsigned long long kb = __ballot(kept);
+          const unsigned long long hb = __ballot(kept && carry + local > uz);
+          if (kb) last = c * 64 + 63 - __clzll(kb);
+          if (hb) { tok = c * 64 + __ffsll((long long)hb) - 1; found = true; }
+          carry = carry + __shfl(local, 63, FF_WAVE);
+        }
+        if (!found) tok = last;
+      }
+      // the masked l[tok] was stored by lane tok % 64 a moment ago: that lane reads its own store back and broadcasts it
+      const int owner = tok & 63;
+      const float mine = lane == owner ? ff_ld4(lrow + tok) : 0.f;
+      const float lg = __shfl(mine, owner, FF_WAVE);
+      lp = fmaxf((lg - m) - logf(lsum), FILL);   // saturates: no -inf, no NaN (lsum >= 1, every term finite)
+      nge = tok >= pa.ge_bound ? 1 : 0;
+    }
+    if (lane == 0) {
+      ff_st4i(a.tok + b, tok);
+      ff_st4(a.logprob + b, lp);
+      ff_st4i(a.fin_out + b, (was_fin || (tok >= pa.term_lo && tok < pa.term_hi)) ? 1 : 0);
+    }
+    if (pa.next_rows) ff_pointer_append_row(pa, b / pa.spg, b, tok, lane);
+  }
+  if (!pa.count_ge) return;   // (launch-uniform)
+  if (lane == 0) s_cnt[wv] = nge;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // one atomic per block; the launch's last block publishes the total to the host-mapped twin (as ff_pointer_count_block)
+    const int nvalid = pa.B - blockIdx.x * 4 < 4 ? pa.B - blockIdx.x * 4 : 4;
+    int n = 0;
+    for (int i = 0; i < nvalid; ++i) n += s_cnt[i];
+    if (n) atomicAdd(pa.count_ge, n);
+    if (pa.arrive) {
+      const int prev = __hip_atomic_fetch_add(pa.arrive, nvalid, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      if (prev + nvalid == pa.B) {
+        const int v = __hip_atomic_load(pa.count_ge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(pa.host_slot, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+  }
+}
+
+// ---- engine side: start state and output packing of a sampled decode (ff_engine.hip) ---------------------------------------------
+// Start state of one micro-batch of Bc = nw * Fc * R sequences (Fc anchors per wireframe, compact anchors [f0, f0 + Fc)): every
+// sample of an anchor holds the anchor's start token (model_para.py:201-205), log-probability 0; a start token in the terminator
+// range finishes the sample at position 0 (the padding anchors).  row_id: the output row (w * F + f) * R + k whose draws the
+// sequence reads -- whatever micro-batch or compact place it decodes in.
+__global__ void sample_init_kernel(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F,
+                                   const int* num_input, int pad_tok, int term_lo, int term_hi) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bc) return;
+  const int k = i % R, a = i / R, wl = a / Fc, f = f0 + a % Fc;
+  const int t = f < num_input[wl] ? f : pad_tok;
+  tok[i] = t;
+  lp[i] = 0.f;
+  fin[i] = (t >= term_lo && t < term_hi) ? 1 : 0;
+  row_id[i] = ((w0 + wl) * F + (f < F ? f : F - 1)) * R + k;
+}
+
+// samples[(w, fo, k), :], logprob (same layout), scores and predict[(w, fo), :] = sample 0, from the per-step records (tok, lp,
+// fin: [T, Btot], row s = the state after s steps).  Position j is kept when j <= the stop step and the sample was not finished
+// before it: last = min(finish position, stop step); rows behind the stop step are never looked at, so the result does not
+// depend on when the host saw the stop.  scores: the kept log-probabilities added in ascending position (fp64 accumulator,
+// rounded once, saturated at -FLT_MAX).  Rows fo >= num_input[w] of a de-duplicated decode read the one padding-anchor group.
+__global__ void sample_finalize_kernel(const int* __restrict__ tok, const float* __restrict__ lp, const int* __restrict__ fin,
+                                       int Btot, int T, const int* __restrict__ steps_p, const int* __restrict__ num_input,
+                                       int dedup, int F, int R, int w0, int nw, int Fc, int f0, int b0,
+                                       int64_t* __restrict__ samples, float* __restrict__ logprob, float* __restrict__ scores,
+                                       int64_t* __restrict__ predict, int* __restrict__ seq_of_row) {
+  const int steps = *steps_p;
+  const int total = nw * F * R;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int k = i % R, fo = (i / R) % F, wl = i / (R * F);
+    int f = fo;
+    if (dedup) { const int n = num_input[w0 + wl]; f = fo < n ? fo : n; }
+    if (f < f0 || f >= f0 + Fc) continue;
+    const int seq = b0 + (wl * Fc + (f - f0)) * R + k;
+    const size_t row = ((size_t)(w0 + wl) * F + fo) * R + k;
+    int64_t* out = samples + row * T;
+    float* olp = logprob + row * T;
+    int64_t* pred = k == 0 ? predict + ((size_t)(w0 + wl) * F + fo) * T : nullptr;
+    double sum = 0.0;
+    bool done = false;   // finished before position j
+    for (int j = 0; j < T; ++j) {
+      const bool in = j <= steps && !done;
+      const int v = in ? tok[(size_t)j * Btot + seq] : 0;
+      const float l = (in && j >= 1) ? lp[(size_t)j * Btot + seq] : 0.f;
+      out[j] = v;
+      olp[j] = l;
+      if (pred) pred[j] = v;
+      sum += (double)l;
+      if (in) done = fin[(size_t)j * Btot + seq] != 0;
+    }
+    scores[row] = (float)fmax(sum, -(double)FLT_MAX);
+    if (seq_of_row) seq_of_row[row] = seq;
+  }
+}
+
+}  // namespace
+
+int ff_pointer_sample_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                           int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
+                           float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok, float* logprob,
+                           int* fin_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                           int* count_ge, int ge_bound, int* arrive, int* host_slot, ff_stream_t stream) {
+  if (B == 0) return FF_OK;
+  FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "ff_pointer_sample: bad sizes B=%d S=%d", B, S);
+  FF_CHECK_ARG(logits && ldlogits >= S, "ff_pointer_sample: logits missing or ldlogits < S");
+  FF_CHECK_ARG(uniforms && num_uniforms > 0 && next_tok && logprob && fin_out, "ff_pointer_sample: null pointer");
+  FF_CHECK_ARG(row_id || num_uniforms >= B, "ff_pointer_sample: %d uniforms for %d rows without a row_id", num_uniforms, B);
+  FF_CHECK_ARG(temperature >= 0.f && temperature <= FLT_MAX && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
+               "ff_pointer_sample: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]", (double)temperature,
+               top_k, (double)top_p);
+  FF_CHECK_ARG(!next_rows || (memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ldnext >= E && ff_aligned16(memory) && ff_aligned16(next_rows)),
+               "ff_pointer_sample: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment");
+  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "ff_pointer_sample: next_stats needs next_rows and E %% 32 == 0");
+  FF_CHECK_ARG(!arrive || (host_slot && count_ge), "ff_pointer_sample: counter hand-over without a counter");
+  SampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p.memory = memory; a.p.S = S; a.p.E = E; a.p.mask = mask; a.p.kv_len = kv_len;
+  a.p.B = B; a.p.spg = seqs_per_group;
+  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.next_rows = next_rows; a.p.ldnext = ldnext; a.p.next_stats = next_stats;
+  a.p.count_ge = count_ge; a.p.ge_bound = ge_bound; a.p.arrive = arrive; a.p.host_slot = host_slot;
+  a.p.term_lo = term_lo; a.p.term_hi = term_hi;
+  a.uniforms = uniforms; a.num_uniforms = num_uniforms; a.row_id = row_id; a.fin_in = fin_in; a.fin_out = fin_out;
+  a.tok = next_tok; a.logprob = logprob;
+  a.temperature = temperature; a.top_k = top_k; a.top_p = top_p;
+  hipStream_t st = (hipStream_t)stream;
+  FFProfScope prof(FF_CAT_POINTER, (double)B * S * 12.0, st);
+  hipLaunchKernelGGL(pointer_sample_kernel, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+extern "C" int ff_pointer_sample(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                 int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
+                                 float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok,
+                                 float* logprob, int* fin_out, const float* memory, int E, float* next_rows, int ldnext,
+                                 float* next_stats, int* count_ge, int ge_bound, ff_stream_t stream) {
+  return ff_pointer_sample_sync(logits, ldlogits, S, mask, kv_len, B, seqs_per_group, uniforms, num_uniforms, row_id, fin_in,
+                                temperature, top_k, top_p, term_lo, term_hi, next_tok, logprob, fin_out, memory, E, next_rows,
+                                ldnext, next_stats, count_ge, ge_bound, nullptr, nullptr, stream);
+}
+
+int ff_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F, const int* num_input,
+                   int pad_tok, int term_lo, int term_hi, hipStream_t st) {
+  hipLaunchKernelGGL(sample_init_kernel, dim3(ff_cdiv(Bc, 256)), dim3(256), 0, st, tok, lp, fin, row_id, Bc, Fc, R, f0, w0, F,
+                     num_input, pad_tok, term_lo, term_hi);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+int ff_sample_finalize(const int* tok, const float* lp, const int* fin, int Btot, int T, const int* steps_dev, const int* num_input,
+                       int dedup, int F, int R, int w0, int nw, int Fc, int f0, int b0, int64_t* samples, float* logprob,
+                       float* scores, int64_t* predict, int* seq_of_row, hipStream_t st) {
+  const int total = nw * F * R;
+  hipLaunchKernelGGL(sample_finalize_kernel, dim3(ff_cdiv(total, 256) < 1024 ? ff_cdiv(total, 256) : 1024), dim3(256), 0, st, tok,
+                     lp, fin, Btot, T, steps_dev, num_input, dedup, F, R, w0, nw, Fc, f0, b0, samples, logprob, scores, predict,
+                     seq_of_row);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}

@@ -23,7 +23,8 @@ import numpy as np
 __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_with_majority_type", "face_metrics",
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
-           "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary"]
+           "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
+           "parse_parallel_samples_scored"]
 
 
 def _tok(token, name, default):
@@ -232,6 +233,21 @@ def parse_parallel_beams_scored(beams, scores, num_edges, token):
         if idx:
             faces.append((int(seq[-1]) - off, idx, float(score)))
     return faces
+
+
+def parse_parallel_samples_scored(samples, scores, num_edges, token):
+    """The faces of a sampled decode (the parallel model's num_samples): samples [..., R, T] tokens; scores either
+    [..., R], the samples' summed log-probabilities (predict_sample_scores), or [..., R, T], their per-position
+    log-probabilities (predict_sample_logprob), which are summed here.  Every sample is read as parse_parallel_beams_scored
+    reads a beam and carries its score: [(type, (edge, ...), score)] in row order, the form unique_faces_with_scores takes --
+    whose vote count is then the number of SAMPLES that drew the face."""
+    rows = np.asarray(samples, dtype=np.int64)
+    sc = np.asarray(scores, dtype=np.float64)
+    if sc.shape == rows.shape:
+        sc = sc.sum(axis=-1)
+    if sc.shape != rows.shape[:-1]:
+        raise ValueError("scores must be shaped like samples, or like samples without the position axis")
+    return parse_parallel_beams_scored(rows, sc, num_edges, token)
 
 
 def score_summary(logprob, greedy, rank, paths, lengths):

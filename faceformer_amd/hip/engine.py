@@ -96,6 +96,27 @@ def check_beam_options(width, S, variant, retire, return_pointer, no_stop, stop_
         raise ValueError("beam_width needs term_range = (lo, hi) with lo < hi")
 
 
+SAMPLE_MAX = 64
+
+
+def check_sample_options(num_samples, temperature, top_k, top_p, variant, retire, return_pointer, no_stop, stop_callback, extra_mask,
+                         logprob, beam_width, term_range):
+    """The combinations a sampled decode rejects (ff_decode_sample's FF_ERR_ARG list, and the options of decode() it cannot be
+    combined with), as ValueError before anything is launched."""
+    if variant != _L.FF_PARALLEL:
+        raise ValueError("num_samples is a parallel-variant option")
+    if not 1 <= num_samples <= SAMPLE_MAX:
+        raise ValueError("num_samples=%d: must be in 1..%d" % (num_samples, SAMPLE_MAX))
+    t, k, pp = float(temperature), int(top_k), float(top_p)
+    if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
+        raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]: got %r, %r, %r"
+                         % (temperature, top_k, top_p))
+    if retire or return_pointer or no_stop or stop_callback is not None or extra_mask is not None or logprob or beam_width:
+        raise ValueError("num_samples excludes retire, return_pointer, no_stop, stop_callback, extra_mask, logprob and beam_width")
+    if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
+        raise ValueError("num_samples needs term_range = (lo, hi) with lo < hi")
+
+
 def check_forced_options(paths, lengths, rows, T, S, retire=False, beam_width=None, logprob=False, return_pointer=False,
                          stop_callback=None, stop_each_eos=False, extra_mask=None):
     """What a forced decode rejects (ff_decode_forced's FF_ERR_ARG list, and the options of decode() it has no argument for), as
@@ -372,7 +393,8 @@ class PathEngine:
                chunk_wireframes=0, chunk_seqs=0, num_streams=1, sync_every=4, flags=DEFAULT_FLAGS,
                tok_sos=1, tok_eos=3, x3_min_rows=0, chunk_max_seqs=0, ln_fuse_max_rows=0,
                trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
-               retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None):
+               retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
+               num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).
 
@@ -389,8 +411,23 @@ class PathEngine:
         `beams` [N*F*W, T] int64 (row (w*F + f)*W + k is beam k of anchor f, best first, zero after the beam's finish position
         and the stop step), `beam_scores` [N*F*W] fp32 (-inf: empty beam); `predict` is beam 0; with trace=True `logits` is
         [T-1, N*F*W, S] and `beam_parent` [T-1, N*F*W] int32, both in output-row order.  Needs term_range; excludes retire,
-        return_pointer, no_stop, stop_callback, extra_mask and logprob (ValueError).  beam_width=1 equals the retire=True decode."""
+        return_pointer, no_stop, stop_callback, extra_mask and logprob (ValueError).  beam_width=1 equals the retire=True decode.
+
+        num_samples=R >= 1 (parallel variant, ff_decode_sample; None or 0: the greedy decode above): R independent
+        draws per anchor under temperature / top_k / top_p, driven by `uniforms` [T-1, N*F*R] fp32 on the device (step t of
+        output row r reads uniforms[t, r]).  Also `samples` [N*F*R, T] int64 (row (w*F + f)*R + k is sample k of anchor f, zero
+        after the sample's finish position and the stop step), `sample_logprob` (same layout, fp32: the model's log-probability
+        of every drawn token) and `sample_scores` [N*F*R] (their sums); `predict` is sample 0; with trace=True `logits` is
+        [T-1, N*F*R, S] in output-row order.  Needs term_range; excludes retire, return_pointer, no_stop, stop_callback,
+        extra_mask, logprob and beam_width (ValueError).  temperature=0 equals the retire=True decode, R times."""
         W = int(beam_width or 0)
+        R = int(num_samples or 0)
+        if R:
+            check_sample_options(R, temperature, top_k, top_p, variant, retire, return_pointer, no_stop, stop_callback, extra_mask,
+                                 logprob, W, term_range)
+            rows_out = memory.shape[0] * F * R
+            if not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (max(T - 1, 1), rows_out):
+                raise ValueError("uniforms must be a float32 tensor of shape [%d, %d]" % (max(T - 1, 1), rows_out))
         if W:
             check_beam_options(W, memory.shape[1], variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob,
                                term_range)
@@ -421,7 +458,7 @@ class PathEngine:
             prm.retire_min_shrink = float(retire_min_shrink)
         if return_pointer or extra_mask is not None:   # (every padding-anchor row has its own extra-mask row)
             prm.flags &= ~_L.FF_DEDUP_PAD_ANCHORS
-        if W:
+        if W or R:
             prm.term_lo, prm.term_hi = int(term_range[0]), int(term_range[1])
         prm.tok_sos, prm.tok_eos = tok_sos, tok_eos
         prm.x3_min_rows = int(x3_min_rows) if self._planes else 0
@@ -445,13 +482,14 @@ class PathEngine:
             extra_mask = extra_mask.contiguous()
         pointer = torch.zeros((max(T - 1, 1), B, E), device=dev, dtype=torch.float32) if return_pointer else None
         tl = tb = ts = rows = None
-        if trace and W:
-            tl = torch.full((max(T - 1, 1), B * W, S), float("nan"), device=dev, dtype=torch.float32)
+        G = W or R    # sequences per anchor of a beam / sampled decode
+        if trace and G:
+            tl = torch.full((max(T - 1, 1), B * G, S), float("nan"), device=dev, dtype=torch.float32)
         elif trace:
             tl = torch.full((max(T - 1, 1), B, S), float("nan"), device=dev, dtype=torch.float32)
             tb = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
             ts = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
-        rows = torch.empty(B * max(W, 1), device=dev, dtype=torch.int32)
+        rows = torch.empty(B * max(G, 1), device=dev, dtype=torch.int32)
         lp = torch.empty((B, T), device=dev, dtype=torch.float32) if logprob else None
         if W:
             beams = torch.empty((B * W, T), device=dev, dtype=torch.int64)
@@ -459,6 +497,15 @@ class PathEngine:
             bparent = torch.full((max(T - 1, 1), B * W), -1, device=dev, dtype=torch.int32) if trace else None
             bprm = _L.BeamParams(W, _p(beams), _p(bscores), _p(bparent))
             nbytes = self._lib.ff_decode_beam_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host, W)
+        elif R:
+            _dev(uniforms, "uniforms")
+            self._same_device(uniforms, "uniforms")
+            uniforms = uniforms.contiguous()
+            samples = torch.empty((B * R, T), device=dev, dtype=torch.int64)
+            slp = torch.empty((B * R, T), device=dev, dtype=torch.float32)
+            sscores = torch.empty(B * R, device=dev, dtype=torch.float32)
+            sprm = _L.SampleParams(R, float(temperature), int(top_k), float(top_p), _p(uniforms), _p(samples), _p(slp), _p(sscores))
+            nbytes = self._lib.ff_decode_sample_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host, R)
         else:
             ws_bytes = self._lib.ff_decode_lp_workspace_bytes if logprob else self._lib.ff_decode_workspace_bytes
             nbytes = ws_bytes(C.byref(self.model), C.byref(prm), ni_host)
@@ -485,6 +532,8 @@ class PathEngine:
         with torch.cuda.device(dev):
             if W:
                 _L.check(self._lib.ff_decode_beam(*args, C.byref(bprm), _stream()), "ff_decode_beam")
+            elif R:
+                _L.check(self._lib.ff_decode_sample(*args, C.byref(sprm), _stream()), "ff_decode_sample")
             elif logprob:
                 _L.check(self._lib.ff_decode_lp(*args, _p(lp), _stream()), "ff_decode_lp")
             else:
@@ -504,6 +553,12 @@ class PathEngine:
                 idx = rows.long()
                 out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
                 out["logits"], out["beam_parent"] = tl[:, idx], bparent[:, idx]
+        elif R:
+            out["samples"], out["sample_logprob"], out["sample_scores"] = samples, slp, sscores
+            if trace:   # (likewise)
+                idx = rows.long()
+                out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
+                out["logits"] = tl[:, idx]
         elif trace:
             # the C side indexes its traces by DECODED sequence (padding-anchor rows share one); expand to
             # one entry per row of `predict`

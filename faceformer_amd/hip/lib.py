@@ -138,6 +138,11 @@ class ForcedParams(C.Structure):
                 ("rank", fptr), ("seq_logprob", fptr)]
 
 
+class SampleParams(C.Structure):
+    _fields_ = [("num_samples", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("uniforms", fptr),
+                ("samples", fptr), ("logprob", fptr), ("scores", fptr)]
+
+
 # ff_stop_fn: int (*)(void* user, const int* step_counts, int num_steps)
 STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int)
 
@@ -229,6 +234,14 @@ SIGNATURES = {
     "ff_decode_forced_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams)]),
     "ff_decode_forced": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, C.POINTER(ForcedParams),
                                    C.POINTER(C.c_int), fptr, fptr, C.c_size_t, fptr]),
+    "ff_pointer_sample": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, fptr, fptr,
+                                    C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, fptr, fptr, fptr, fptr, C.c_int, fptr, C.c_int,
+                                    fptr, fptr, C.c_int, fptr]),
+    "ff_decode_sample_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int), C.c_int]),
+    "ff_decode_sample": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                   C.POINTER(C.c_int), fptr,
+                                   fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                                   C.c_size_t, C.POINTER(SampleParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 
@@ -260,7 +273,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam* and *_forced* ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced* and *_sample* ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

@@ -479,6 +479,72 @@ def pointer_forced(logits, forced, memory=None, mask=None, kv_len=None, seqs_per
 
 
 @_on_tensor_device
+def pointer_sample(logits, uniforms, temperature=1.0, top_k=0, top_p=1.0, row_id=None, fin=None, memory=None, mask=None, kv_len=None,
+                   seqs_per_group=1, term_range=(1, 4), want_rows=False, want_stats=False, counter=None, ge_bound=0):
+    """One sampling step of the pointer head (ff_pointer_sample).  logits [B, S] fp32 raw dot products (masked IN
+    PLACE as the pointer launch masks them; rows of finished sequences are not touched), uniforms [U] fp32; row b reads
+    uniforms[row_id[b]] (row_id [B] int32 in [0, U), ValueError otherwise; None: b), fin (optional) [B] int32, nonzero =
+    finished: token 0, log-probability 0, no draw.  Row b belongs to wireframe b // seqs_per_group of mask [W, S] / kv_len [W] /
+    memory [W, S, E].  Returns dict(next [B] int32: the drawn tokens; logprob [B] fp32: log_softmax(masked row)[next] under the
+    model, saturated at -FLT_MAX; fin [B] int32; [rows [B, E]: memory[w, next]]; [stats [B, E/32, 2]])."""
+    _dev(logits, "logits"), _dev(uniforms, "uniforms")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be a 2-D tensor with unit inner stride")
+    B, S = logits.shape
+    if uniforms.dim() != 1 or not uniforms.is_contiguous() or uniforms.numel() < 1:
+        raise ValueError("uniforms must be a contiguous non-empty 1-D tensor")
+    U = uniforms.numel()
+    t, k, pp = float(temperature), int(top_k), float(top_p)
+    if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
+        raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]")
+    if row_id is not None:
+        _dev(row_id, "row_id", torch.int32)
+        if row_id.dim() != 1 or row_id.numel() != B or (B and (int(row_id.min()) < 0 or int(row_id.max()) >= U)):
+            raise ValueError("row_id must hold one index in [0, %d) per row of logits" % U)
+        row_id = row_id.contiguous()
+    elif U < B:
+        raise ValueError("%d uniforms for %d rows" % (U, B))
+    if fin is not None:
+        _dev(fin, "fin", torch.int32)
+        if fin.dim() != 1 or fin.numel() != B:
+            raise ValueError("fin must hold one flag per row of logits")
+        fin = fin.contiguous()
+    spg = int(seqs_per_group)
+    if spg < 1:
+        raise ValueError("seqs_per_group must be positive")
+    nw = (B + spg - 1) // spg
+    dev = logits.device
+    for x, name, dt in ((mask, "mask", torch.uint8), (kv_len, "kv_len", torch.int32)):
+        if x is not None:
+            _dev(x, name, dt)
+            if not x.is_contiguous() or x.size(0) < nw or (name == "mask" and (x.dim() != 2 or x.size(1) != S)):
+                raise ValueError("%s must be contiguous and cover %d wireframes of %d keys" % (name, nw, S))
+    out = {"next": torch.empty(B, device=dev, dtype=torch.int32), "logprob": torch.empty(B, device=dev, dtype=torch.float32),
+           "fin": torch.empty(B, device=dev, dtype=torch.int32)}
+    rows, stats, E = None, None, 0
+    if memory is not None:
+        _dev(memory, "memory")
+        if memory.dim() != 3 or not memory.is_contiguous() or memory.size(1) != S or memory.size(0) < nw:
+            raise ValueError("memory must be a contiguous [>= %d, %d, E] tensor" % (nw, S))
+        E = memory.size(2)
+    if want_rows or want_stats:
+        if memory is None:
+            raise ValueError("rows / stats need memory")
+        rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
+        if want_stats:
+            if E % 32:
+                raise ValueError("stats need E % 32 == 0")
+            stats = out["stats"] = torch.empty((B, E // 32, 2), device=dev, dtype=torch.float32)
+    if counter is not None:
+        _dev(counter, "counter", torch.int32)
+    _L.check(_L.load().ff_pointer_sample(
+        _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(uniforms), U, _p(row_id), _p(fin), t, k, pp,
+        int(term_range[0]), int(term_range[1]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(memory), E, _p(rows), E,
+        _p(stats), _p(counter), int(ge_bound), _stream()), "ff_pointer_sample")
+    return out
+
+
+@_on_tensor_device
 def gather_rows(memory, tok, seqs_per_group=1):
     _dev(memory, "memory"), _dev(tok, "tok", torch.int32)
     N, S, E = memory.shape

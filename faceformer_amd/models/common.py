@@ -70,6 +70,16 @@ class SurfaceFormerBase(nn.Module):
                                        # forward_eval adds predict_beams / predict_beam_scores, predict is beam 0.  0 = greedy.
                                        # Not with retire_finished, return_logprob, an extra mask, dist.decode_sharded or the
                                        # single-sequence model (ValueError)
+        self.num_samples = 0           # parallel model: R >= 1 (at most 64) decodes R independent DRAWS per anchor (temperature /
+                                       # top-k / top-p sampling): forward_eval adds predict_samples,
+                                       # predict_sample_logprob (N x F x R x T) and predict_sample_scores (N x F x R); predict is
+                                       # sample 0, a fair draw.  0 = greedy.  Not with retire_finished, beam_width, return_logprob,
+                                       # an extra mask, score(), dist.decode_sharded or the single-sequence model (ValueError)
+        self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
+        self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
+        self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
+        self.sample_seed = 0           # ... seed of the torch.Generator that makes the uniforms; inputs["sample_uniforms"]
+                                       # [T-1, N*F*R] fp32, column (w*F + f)*R + k in the batch's own order, overrides it
         # Decoder projections of launches with at least this many rows (q|k|v; linear1 from 7/4 x, the 512-column ones from
         # 11/4 x as many) run as 3 x bf16 split products on the bf16 matrix cores: fp32-accurate (error vs fp64 = an fp32 dot
         # product's, tests/test_hip_ops.py), LayerNorm folding included (ff_gemm_x3_ln), and 1.3-1.6x the f32-MFMA kernel
@@ -269,6 +279,8 @@ class SurfaceFormerBase(nn.Module):
         every wireframe is F rows wide whatever its edge count -- the micro-batches forward_eval gets by sorting are the ones
         this plan has already -- and there is no sort_by_edges permutation to undo.  stop_each_eos (seq2seq) is a rule of the
         greedy decode and is not looked at: a forced decode has no stop rule."""
+        if int(getattr(self, "num_samples", 0) or 0):
+            raise ValueError("score() excludes num_samples: set model.num_samples = 0 to score given paths")
         if not self.engine_supported():
             raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
         eng, memory, mask, kv_len = self._encode(inputs)

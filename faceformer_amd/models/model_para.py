@@ -13,6 +13,7 @@ last layer and the output projection are evaluated for the newest position only.
 import torch
 
 from .. import faces as _faces
+from ..hip import engine as _engine
 from ..hip import lib as _L
 from .common import SurfaceFormerBase
 
@@ -38,10 +39,23 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         only), num_input: N edge counts.  Adds predict N x F x T (int64), F = max(num_input).
         beam_width = W >= 1 (default 0: the greedy decode): beam search with W beams per anchor -- also predict_beams
         N x F x W x T (best first; zero after a beam's face-type token and after the stop step) and predict_beam_scores
-        N x F x W (summed log-probabilities, -inf for empty beams); predict is beam 0."""
+        N x F x W (summed log-probabilities, -inf for empty beams); predict is beam 0.
+        num_samples = R >= 1 (default 0): R independent draws per anchor under sample_temperature / sample_top_k / sample_top_p
+         -- also predict_samples and predict_sample_logprob N x F x R x T (zero after a sample's face-type token and
+        after the stop step) and predict_sample_scores N x F x R (summed log-probabilities under the model); predict is sample 0.
+        The uniforms come from torch.Generator(device).manual_seed(sample_seed), or from inputs["sample_uniforms"]
+        [T-1, N*F*R]; either way column (w*F + f)*R + k belongs to wireframe w of the batch AS GIVEN."""
         label = inputs["label"]
         T = self.max_face_length
         W = int(getattr(self, "beam_width", 0) or 0)
+        R = int(getattr(self, "num_samples", 0) or 0)
+        if R:
+            if not self.engine_supported():
+                raise ValueError("num_samples needs the native engine: this model's constructor arguments take the sub-module loop")
+            if W or self.retire_finished or getattr(self, "return_logprob", False) or inputs.get("extra_mask") is not None:
+                raise ValueError("num_samples excludes beam_width, retire_finished, return_logprob and an extra mask")
+            _engine.check_sample_options(R, self.sample_temperature, self.sample_top_k, self.sample_top_p, _L.FF_PARALLEL, False, False,
+                                         False, None, None, False, 0, (int(self.token.face_type_offset), int(self.token.len)))
         if W and not self.engine_supported():
             raise ValueError("beam_width needs the native engine: this model's constructor arguments take the sub-module loop")
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
@@ -81,14 +95,19 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
             eng = self.engine()
             staged = eng.stage_num_input(ni)
             eng, memory, mask, kv_len = self._encode(inputs, eng)
+        skw = {}
+        if R:
+            skw = dict(num_samples=R, temperature=float(self.sample_temperature), top_k=int(self.sample_top_k),
+                       top_p=float(self.sample_top_p), uniforms=self._sample_uniforms(inputs, memory.device, T, N, F, R, order))
         out = eng.decode(memory, mask, kv_len, _L.FF_PARALLEL, T=T, F=F, num_input=ni, staged_num_input=staged,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs,
                          num_streams=self.num_streams, sync_every=self.sync_every,
                          flags=self.decode_flags, x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, extra_mask=extra,
                          retire=self.retire_finished, term_range=(int(self.token.face_type_offset), int(self.token.len)),
-                         logprob=want_lp, beam_width=W or None)
+                         logprob=want_lp, beam_width=W or None, **skw)
         pred = out["predict"].view(N, F, T)
+        smp = (out["samples"].view(N, F, R, T), out["sample_logprob"].view(N, F, R, T), out["sample_scores"].view(N, F, R)) if R else None
         lp = out["logprob"].view(N, F, T) if want_lp else None
         beams = out["beams"].view(N, F, W, T) if W else None
         bscores = out["beam_scores"].view(N, F, W) if W else None
@@ -99,7 +118,11 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
             lp = lp.index_select(0, inv) if want_lp else None
             if W:
                 beams, bscores = beams.index_select(0, inv), bscores.index_select(0, inv)
+            if R:
+                smp = tuple(t.index_select(0, inv) for t in smp)
         inputs["predict"] = pred
+        if R:   # (predict is sample 0 of every anchor: a fair draw, not a selected one)
+            inputs["predict_samples"], inputs["predict_sample_logprob"], inputs["predict_sample_scores"] = smp
         if W:   # (predict is beam 0 of every anchor)
             inputs["predict_beams"], inputs["predict_beam_scores"] = beams, bscores
         if want_lp:
@@ -109,7 +132,28 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         if W:   # (W sequences per decoded anchor; `rows` stays the reference's N * F)
             self.last_decode_stats["decoded_seqs"] *= W
             self.last_decode_stats["beam_width"] = W
+        if R:
+            self.last_decode_stats["decoded_seqs"] *= R
+            self.last_decode_stats["num_samples"] = R
         return inputs
+
+    def _sample_uniforms(self, inputs, device, T, N, F, R, order):
+        """The uniforms [T-1, N*F*R] of a sampled decode in the DECODE's wireframe order: made (or given) for the batch as given,
+        column (w*F + f)*R + k, then permuted like the wireframes when they are decoded sorted by edge count -- a draw belongs
+        to the wireframe's place in the batch, not to its sorted place."""
+        shape = (max(T - 1, 1), N * F * R)
+        u = inputs.get("sample_uniforms")
+        if u is None:
+            gen = torch.Generator(device=device).manual_seed(int(self.sample_seed))
+            u = torch.rand(shape, generator=gen, device=device, dtype=torch.float32)
+        else:
+            u = torch.as_tensor(u)
+            if tuple(u.shape) != shape:
+                raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
+            u = u.to(device=device, dtype=torch.float32)
+        if order is not None:
+            u = u.view(shape[0], N, F * R).index_select(1, torch.tensor(order, device=device)).reshape(shape)
+        return u.contiguous()
 
     def label_paths(self, inputs):
         """score()'s defaults, the data set's own labels: (paths N x F x T = label[:, :max(num_input)], lengths N x F = the

@@ -726,6 +726,79 @@ int ff_decode_forced(const ff_model* m, const ff_decode_params* p,
                      const ff_forced_params* forced, int* steps_done, float* trace_logits,
                      void* workspace, size_t workspace_bytes, ff_stream_t stream);
 
+/* ---- temperature / top-k / top-p sampling over the pointer head (opt-in, parallel variant; entries added within ABI 105;
+ *      DESIGN.md 15) ------------------------------------------------------------------------------------------------------------
+ * The reference decodes greedily: select_next takes the argmax of the masked logit row (model_para.py:173-179) inside the loop
+ * of model_para.py:216-233.  These entries restate exactly those two call sites with ONE change: the token is DRAWN from the
+ * masked row, and the loop carries num_samples independent sequences per anchor.  Randomness is an input: the caller passes
+ * uniforms in [0, 1); there is no generator in device code.
+ *
+ * The rule for one unfinished row.  l[0..S) is the masked logit row select_next forms (masked keys at finfo.min = -FLT_MAX), A
+ * its live keys (l > -FLT_MAX), m = max l; temperature tau >= 0, top_k K >= 0, 0 < top_p P <= 1, u the row's uniform clamped
+ * into [0, 1 - 2^-24]:
+ *   1. A empty: token 0, log-probability -log S (ff_pointer_argmax_lp's value).  No draw is used.
+ *   2. tau == 0: token = argmax l, lowest index on ties.  No draw is used.
+ *   3. w[s] = exp((l[s] - m) / tau) for s in A (the largest weight is exactly 1).
+ *   4. top-k: if 0 < K < |A|, A_k = {s in A : l[s] >= v_K}, v_K the K-th largest live logit counted with multiplicity (ties at
+ *      the threshold are all kept); else A_k = A.
+ *   5. top-p: if P < 1, theta = the first of the distinct values of l over A_k, descending, at which
+ *      sum_{s in A_k, l[s] >= theta} w[s] >= P * sum_{A_k} w; A_p = {s in A_k : l[s] >= theta}; else A_p = A_k.
+ *   6. c[s] = inclusive prefix sum of w over A_p in ascending key index, Z its last value; token = the first s in A_p with
+ *      c[s] > u * Z, the last key of A_p when there is none.
+ *   7. log-probability = (l[token] - m) - log sum_s exp(l[s] - m) over all S keys: under the MODEL, not under the shaped
+ *      distribution; fp32, saturated at -FLT_MAX.
+ *
+ * ff_pointer_sample: one step of B sequences.  Row b belongs to wireframe b / seqs_per_group (mask [wireframes, S], kv_len
+ *   [wireframes], memory [wireframes, S, E]; B need not be a multiple of seqs_per_group).
+ *   logits   [B, ldlogits] raw dot products; masked IN PLACE as the pointer launch masks them (rows of finished sequences are
+ *            not touched).
+ *   uniforms [num_uniforms] fp32 DEVICE; row b reads uniforms[row_id[b]] (row_id [B] int32 DEVICE, or NULL: b, which needs
+ *            num_uniforms >= B).  The entry cannot see device data: an index outside [0, num_uniforms) is CLAMPED into it.
+ *   fin_in   (optional) [B] int32: nonzero = finished before this step -- token 0, log-probability 0, no draw.
+ *   next_tok [B] int32, logprob [B] fp32, fin_out [B] int32 (fin_in, or the token lies in [term_lo, term_hi)); fin_out may be fin_in.
+ *   next_rows / next_stats (optional): as ff_pointer_forced -- memory[wireframe, next_tok[b], :] and its LayerNorm segment
+ *            statistics.  count_ge (optional): += number of unfinished rows whose token is >= ge_bound (the stop rule's count).
+ * ff_decode_sample: the parallel decode (model_para.py:216-233) with num_samples draws per anchor; ff_decode's arguments, then
+ *   uniforms [T-1, N*F*num_samples] fp32 DEVICE: step t of output row r reads uniforms[t, r], whatever micro-batch or compact
+ *            place the sequence decodes in.
+ *   samples  [N*F*num_samples, T] int64: row (w*F + f) * num_samples + k is sample k of anchor f; logprob, same layout, fp32: the
+ *            log-probability of the token at every position (0 in column 0); both zero after the sample's finish position and
+ *            after the stop step.  scores [N*F*num_samples] fp32: the sum of a row's log-probabilities (ascending positions, fp64
+ *            accumulator, rounded once).  predict [N*F, T] receives sample 0 of every anchor.
+ *   trace_logits (optional) [T-1, N*F*num_samples, S], indexed by decoded sequence (seq_of_row [N*F*num_samples] maps output rows
+ *            to them): the MASKED row of every sequence still unfinished before the step; a sequence finished before the step
+ *            is not masked or read, its row holds the raw dot products.  trace_best / trace_second must be NULL.
+ * A sample is finished from the first position (the start token included) holding a token in [term_lo, term_hi) of the
+ * parameters; the decode stops after the first step at which no unfinished sample selected a token >= num_token, else after T-1
+ * steps.  With temperature 0 every sample is FF_RETIRE_FINISHED's predict of the same batch.  FF_ERR_ARG before any launch for:
+ * FF_SEQ2SEQ, FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn, an extra_mask, best / second traces, num_samples
+ * outside 1..64, temperature < 0 or not finite, top_k < 0, top_p outside (0, 1], a NULL uniforms / samples / logprob / scores,
+ * term_lo >= term_hi.  ff_decode_sample_workspace_bytes: the workspace it needs (ff_decode_workspace_bytes' rules, num_samples
+ * sequences per anchor, plus the per-step records and the row_id array, taken last).  ff_decode, ff_decode_lp, ff_decode_beam
+ * and ff_decode_forced launch and lay out what they did before these entries. */
+int ff_pointer_sample(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                      int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
+                      float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok, float* logprob,
+                      int* fin_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                      int* count_ge, int ge_bound, ff_stream_t stream);
+typedef struct ff_sample_params {
+  int num_samples;
+  float temperature;
+  int top_k;
+  float top_p;
+  const float* uniforms;
+  int64_t* samples;
+  float* logprob;
+  float* scores;
+} ff_sample_params;
+size_t ff_decode_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host, int num_samples);
+int ff_decode_sample(const ff_model* m, const ff_decode_params* p,
+                     const float* memory, const unsigned char* mask, const int* kv_len,
+                     const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                     int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                     float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                     void* workspace, size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,14 @@ def decode_batch_beams(model, batch):
     return out["predict"].cpu().numpy(), out["predict_beams"].cpu().numpy(), out["predict_beam_scores"].cpu().numpy()
 
 
+def decode_batch_samples(model, batch):
+    """(`predict`, `predict_samples`, `predict_sample_scores`) of `model(batch)` as numpy arrays (--sample: the model's
+    num_samples is set)."""
+    with torch.no_grad():
+        out = model(batch)
+    return out["predict"].cpu().numpy(), out["predict_samples"].cpu().numpy(), out["predict_sample_scores"].cpu().numpy()
+
+
 def score_batch(model, batch):
     """`model.score(batch)` on the data set's own label rows (--score-labels) as numpy arrays: dict(logprob, greedy, rank, paths
     [N, ..., T], lengths, seq_logprob [N, ...])."""
@@ -71,7 +79,7 @@ def score_batch(model, batch):
             "paths": paths.cpu().numpy(), "lengths": lengths.reshape(lp.shape[:-1]).cpu().numpy(), "seq_logprob": out["score_seq_logprob"].cpu().numpy()}
 
 
-def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None):
+def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -80,7 +88,10 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     score; `pred_faces` stays what beam 0 (pred) gives.
     label_scores (--score-labels; this sample's slice of score_batch): the record also gets `label_logprob` (the summed
     log-probability of every scored label row, in row order), `label_nll` (per token) and `label_tf_accuracy`
-    (faces.score_summary; null when the sample has no scored label token)."""
+    (faces.score_summary; null when the sample has no scored label token).
+    samples (--sample; (tokens [F, R, T], scores [F, R]) of this sample): the record also gets `pred_sample_faces`,
+    `pred_sample_face_scores` and `pred_sample_face_votes`, the de-duplicated faces over ALL draws of the wireframe's own anchors
+    ranked by their best score, with the number of draws that produced each; `pred_faces` stays what sample 0 (pred) gives."""
     scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
@@ -123,14 +134,23 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["label_logprob"] = [float(v) for v, n in zip(ls["seq_logprob"].reshape(-1), ls["lengths"].reshape(-1)) if n > 0]
         rec["label_nll"] = float(sm["nll"][0]) if sm["tokens"][0] else None
         rec["label_tf_accuracy"] = float(sm["tf_accuracy"][0]) if sm["tokens"][0] else None
+    if samples is not None:
+        n = int(item["num_input"])
+        sf = FZ.parse_parallel_samples_scored(samples[0][:n], samples[1][:n], len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(sf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_sample_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_sample_face_scores"] = [s for _, _, s, _ in ranked]
+        rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
-def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0):
+def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
+                    seed=0):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
-    (return_logprob), beam search with `beam` beams per anchor (beam_width).  Without them the
-    model keeps its defaults."""
+    (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
+    under temperature / top_k / top_p from the seeded generator (num_samples).  Without them the model keeps its
+    defaults."""
     if retire_finished:
         model.retire_finished = True
     if fp16:
@@ -139,11 +159,16 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.return_logprob = True
     if beam:
         model.beam_width = int(beam)
+    if sample:
+        model.num_samples = int(sample)
+        model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
+        model.sample_seed = int(seed)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
-             retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False):
+             retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
+             top_p=1.0, seed=0):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -153,7 +178,15 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     beam: beam search with this many beams per anchor (parallel model, single process, not with retire_finished / scores):
     every record gains `pred_beam_faces` / `pred_beam_face_scores`.
     score_labels: every record gains `label_logprob` / `label_nll` / `label_tf_accuracy`, the model's teacher-forced scores of
-    the sample's own label rows (models' score()); single process, not with retire_finished / scores / beam."""
+    the sample's own label rows (models' score()); single process, not with retire_finished / scores / beam.
+    sample: this many draws per anchor under temperature / top_k / top_p, uniforms from a generator seeded with `seed` (parallel
+    model, single process, not with retire_finished / scores / beam / score_labels): every record gains `pred_sample_faces` /
+    `pred_sample_face_scores` / `pred_sample_face_votes`."""
+    if sample and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores or beam or score_labels):
+        raise ValueError("--sample applies to SurfaceFormer_Parallel only, and not together with --retire-finished, --scores, "
+                         "--beam or --score-labels")
+    if sample and dist_mod is not None and dist_mod.get_world_size() > 1:
+        raise ValueError("--sample (num_samples) is not implemented for multi-rank runs")
     if score_labels and (retire_finished or scores or beam):
         raise ValueError("--score-labels does not combine with --retire-finished, --scores or --beam (a forced decode excludes them)")
     if score_labels and dist_mod is not None and dist_mod.get_world_size() > 1:
@@ -174,7 +207,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         sd, _ = load_lightning_checkpoint(ckpt_path)
         model.load_state_dict(sd)
         model = model.eval().to(device)
-    configure_model(model, retire_finished, fp16, scores, beam)
+    configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -195,8 +228,11 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         if torch.cuda.is_available() and str(device).startswith("cuda"):
             torch.cuda.synchronize()
         t0 = time.time()
-        bms = None
-        if beam:
+        bms = sms = None
+        if sample:
+            pred, stk, ssc = decode_batch_samples(model, batch)
+            lps, sms = None, list(zip(stk, ssc))
+        elif beam:
             pred, bt, bs = decode_batch_beams(model, batch)
             lps, bms = None, list(zip(bt, bs))
         else:
@@ -206,7 +242,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         done += len(idx)
         for k, i in enumerate(idx):
             text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel, lps[k] if scores else None,
-                                 bms[k] if beam else None, {n: v[k] for n, v in lsc.items()} if score_labels else None)
+                                 bms[k] if beam else None, {n: v[k] for n, v in lsc.items()} if score_labels else None,
+                                 sms[k] if sample else None)
             stats.append(st)
             records.append((os.path.splitext(os.path.basename(items[k]["name"]))[0], text))
         print("Avg Time", total / done, "seconds.")
@@ -255,6 +292,17 @@ def build_parser():
                         help="every JSON record gains label_logprob (per label row), label_nll (per token) and label_tf_accuracy: "
                              "the model's teacher-forced scores of the sample's own label rows (DESIGN.md 14); single-process runs "
                              "only, not with --retire-finished, --scores or --beam")
+    parser.add_argument("--sample", type=int, default=0, metavar="R",
+                        help="parallel model: R (1..64) independent draws per anchor edge instead of the argmax (DESIGN.md 15); "
+                             "pred_faces come from draw 0, and every JSON record gains pred_sample_faces / pred_sample_face_scores / "
+                             "pred_sample_face_votes: the faces of all draws, de-duplicated, ranked by score, with their vote counts; "
+                             "single-process runs only, not with --retire-finished, --scores, --beam or --score-labels")
+    parser.add_argument("--temperature", type=float, default=1.0, help="--sample: the logits are divided by it (0: the argmax)")
+    parser.add_argument("--top-k", type=int, default=0, help="--sample: draw among the K most probable keys (0: all)")
+    parser.add_argument("--top-p", type=float, default=1.0, help="--sample: draw among the most probable keys up to this share of the mass")
+    parser.add_argument("--seed", type=int, default=0, help="--sample: seed of the generator that makes the uniforms.  The generator is seeded anew for every "
+                                                                 "model(batch) call and a draw belongs to the wireframe's place in its batch, so wireframes at the "
+                                                                 "same place of different batches (with --batch-size 1: all of them) read the same uniform stream")
     return parser
 
 
@@ -274,7 +322,8 @@ def main(argv=None):
         dist_mod.init_process_group("nccl", device_id=torch.device(device))
     run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
              retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam,
-             score_labels=args.score_labels)
+             score_labels=args.score_labels, sample=args.sample, temperature=args.temperature, top_k=args.top_k,
+             top_p=args.top_p, seed=args.seed)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
