@@ -152,6 +152,21 @@ int ff_sample_finalize(const int* tok, const float* lp, const int* fin, int Btot
                        int dedup, int F, int R, int w0, int nw, int Fc, int f0, int b0, int64_t* samples, float* logprob,
                        float* scores, int64_t* predict, int* seq_of_row, hipStream_t st);
 
+// ff_pointer_constrained with the decode engine's hand-over (ff_constrain.hip): arrive counts the launch's rows, the last block
+// stores count_ge to host_slot.  And the start state / output packing of a constrained decode (kernels' comments).
+int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi,
+                                const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
+                                unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
+                                int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                                int* count_ge, int* arrive, int* host_slot, ff_stream_t stream);
+int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int Fc, int f0,
+                      const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok, const unsigned* follows, int L,
+                      hipStream_t st);
+int ff_constrain_finalize(const int* tok, const float* lp, const int* fin, const int* dead, int Btot, int T, const int* steps_dev,
+                          const int* num_input, int dedup, int F, int w0, int nw, int Fc, int f0, int b0, int64_t* predict,
+                          float* logprob, int* dead_end, int* seq_of_row, hipStream_t st);
+
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);
 

@@ -1,0 +1,298 @@
+// Loop-constrained greedy selection over the pointer head (opt-in, parallel variant): the co-edge follow table,
+// one step's constrained selection of every sequence, and the start state / output packing of a constrained decode.
+//
+// The rule (include/faceformer_hip.h states it on tokens): a face is one or more closed chains of co-edges, so a sequence with
+// an OPEN loop (first != none) may only continue with an edge that starts where its last edge ends (CONNECT), never with an
+// edge it holds already (NO_REPEAT) and never with a special token; when no such edge is left the terminators are opened
+// instead and the sequence ends there, flagged as a dead end.  With the loop CLOSED the terminators and every unvisited edge
+// are open.
+//
+// follow_table_kernel: one wavefront per (wireframe, edge a) row, 64 candidate edges b per round; the ballot of
+// |end(a) - start(b)| < tol in x and in y (fp32 subtraction, fp32 compare) is the two 32-bit words of the round.
+//
+// pointer_constrained_kernel: one wavefront per sequence, four per block, as pointer_reduce_kernel.  A finished sequence appends
+// token 0 and keeps its state.  Every other one writes the byte row of ITS constraint mask (lane = key mod 64), votes once on
+// "any live edge" (the vote sees padding, kv_len and visited), re-opens the terminators on a dead end (same lane = key mod 64
+// mapping), and then masks and reduces its logit row exactly as the greedy launch does with an extra mask
+// (ff_pointer_mask_reduce<true>, ff_device.h): every lane reads back the bytes it wrote itself.  Lane 0 stores token,
+// log-probability (-log sum exp(l - l[token]) over the constrained row), the flags and the next (first, prev), and sets the
+// token's bit in the sequence's visited words; the wave appends memory[w, token] through ff_pointer_append_row, so a
+// constrained decode keeps FF_L0_FOLD.  No LDS beyond the four counter words.  Stop counter: pointer_sample_kernel's scheme.
+#include <float.h>
+
+#include "ff_common.h"
+#include "ff_device.h"
+
+namespace {
+
+struct ConstrainArgs {
+  PointerArgs p;                 // logits / masks / memory / next rows / counters of the B launch rows; p.extra = rows
+  unsigned char* rows;           // [B, S] out: the constraint byte row of every unfinished sequence (1 = masked)
+  const unsigned* follows;       // [wireframes, L, fw] bits or null: bit b of row a = edge b starts where edge a ends
+  int L, fw;                     // edges per wireframe (S - ntok), words per row ceil(L / 32)
+  int flags, ntok;
+  const int* fin_in;             // [B] nonzero: finished before this step
+  const int* first_in;           // [B] first edge of the open loop, -1: none (closed)
+  const int* prev_in;            // [B] last edge, -1: none
+  unsigned* visited;             // [B, fw] in / out: the edges of the prefix
+  int *fin_out, *first_out, *prev_out, *dead_out;   // [B] out
+  int* tok; float* logprob;      // [B] out
+};
+
+__global__ __launch_bounds__(256) void follow_table_kernel(const float* __restrict__ starts, const float* __restrict__ ends, int N,
+                                                           int L, const int* __restrict__ num_input, float tol,
+                                                           unsigned* __restrict__ bits) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long row = (long long)blockIdx.x * 4 + wv;
+  if (row >= (long long)N * L) return;   // (wave-uniform)
+  const int w = (int)(row / L), a = (int)(row % L), fw = (L + 31) >> 5;
+  int n = num_input[w];
+  n = n < 0 ? 0 : (n > L ? L : n);
+  const float ex = ends[row * 2], ey = ends[row * 2 + 1];
+  const float* sp = starts + (size_t)w * L * 2;
+  unsigned* out = bits + row * fw;
+  for (int c0 = 0; c0 < L; c0 += 64) {
+    const int b = c0 + lane;
+    bool ok = a < n && b < n;
+    if (ok) ok = fabsf(ex - sp[b * 2]) < tol && fabsf(ey - sp[b * 2 + 1]) < tol;
+    const unsigned long long bal = __ballot(ok);
+    if (lane == 0) {
+      out[c0 >> 5] = (unsigned)bal;
+      if ((c0 >> 5) + 1 < fw) out[(c0 >> 5) + 1] = (unsigned)(bal >> 32);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs a) {
+  __shared__ int s_cnt[4];
+  const PointerArgs& pa = a.p;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.x * 4 + wv;
+  int nge = 0;
+  if (b < pa.B) {   // (wave-uniform)
+    const int S = pa.S, ntok = a.ntok;
+    const int was_fin = ff_ld4i(a.fin_in + b);
+    int first = ff_ld4i(a.first_in + b), prev = ff_ld4i(a.prev_in + b);
+    first = (first < 0 || first >= a.L) ? -1 : first;   // (the entry cannot see device data: anything else is "none")
+    prev = (prev < 0 || prev >= a.L) ? -1 : prev;
+    int tok = 0, dead = 0;
+    float lp = 0.f;
+    if (!was_fin) {
+      const int w = b / pa.spg;
+      const bool connect = (a.flags & FF_CONSTRAIN_CONNECT) != 0, norep = (a.flags & FF_CONSTRAIN_NO_REPEAT) != 0;
+      const bool open = connect && first >= 0 && prev >= 0;
+      int kv = S;
+      if (pa.kv_len) { const int k = ff_ldw(pa.kv_len + w); kv = k < kv ? k : kv; }
+      const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * S : nullptr;
+      const unsigned* frow = open ? a.follows + ((size_t)w * a.L + prev) * a.fw : nullptr;
+      const unsigned* vrow = a.visited + (size_t)b * a.fw;
+      unsigned char* xrow = a.rows + (size_t)b * S;
+      bool live_edge = false;
+      for (int s = lane; s < S; s += 64) {
+        bool masked;
+        if (s < ntok) {
+          masked = connect && (open || s < pa.term_lo || s >= pa.term_hi);
+        } else {
+          const int e = s - ntok;
+          const unsigned bit = 1u << (e & 31);
+          masked = (norep && (vrow[e >> 5] & bit) != 0) || (open && (frow[e >> 5] & bit) == 0);
+          bool pad = s >= kv;
+          if (!pad && mrow) pad = ff_ldw(mrow + s) != 0;
+          live_edge = live_edge || (!masked && !pad);
+        }
+        xrow[s] = masked ? 1 : 0;
+      }
+      if (open && __ballot(live_edge) == 0ull) {   // dead end: the terminators instead (every lane rewrites its own keys)
+        dead = 1;
+        for (int s = lane; s < pa.term_hi; s += 64)
+          if (s >= pa.term_lo) xrow[s] = 0;
+      }
+      float m, b2, lsum;
+      ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &tok, &lsum);
+      lp = -logf(lsum);
+      if (tok >= ntok) {
+        const int e = tok - ntok;
+        nge = 1;
+        if (first < 0) first = e;
+        prev = e;
+        if (a.follows) {
+          const unsigned word = a.follows[((size_t)w * a.L + e) * a.fw + (first >> 5)];
+          if ((word >> (first & 31)) & 1u) first = -1;   // (a one-edge loop closes on itself)
+        }
+        if (lane == 0) a.visited[(size_t)b * a.fw + (e >> 5)] |= 1u << (e & 31);
+      }
+    }
+    if (lane == 0) {
+      ff_st4i(a.tok + b, tok);
+      ff_st4(a.logprob + b, lp);
+      ff_st4i(a.fin_out + b, (was_fin || dead || (tok >= pa.term_lo && tok < pa.term_hi)) ? 1 : 0);
+      ff_st4i(a.dead_out + b, dead);
+      ff_st4i(a.first_out + b, first);
+      ff_st4i(a.prev_out + b, prev);
+    }
+    if (pa.next_rows) ff_pointer_append_row(pa, b / pa.spg, b, tok, lane);
+  }
+  if (!pa.count_ge) return;   // (launch-uniform)
+  if (lane == 0) s_cnt[wv] = nge;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // one atomic per block; the launch's last block publishes the total to the host-mapped twin (as ff_pointer_count_block)
+    const int nvalid = pa.B - blockIdx.x * 4 < 4 ? pa.B - blockIdx.x * 4 : 4;
+    int n = 0;
+    for (int i = 0; i < nvalid; ++i) n += s_cnt[i];
+    if (n) atomicAdd(pa.count_ge, n);
+    if (pa.arrive) {
+      const int prev = __hip_atomic_fetch_add(pa.arrive, nvalid, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      if (prev + nvalid == pa.B) {
+        const int v = __hip_atomic_load(pa.count_ge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(pa.host_slot, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+  }
+}
+
+// ---- engine side: start state and output packing of a constrained decode (ff_engine.hip) -----------------------------------------
+// Start state of one micro-batch of Bc = nw * Fc sequences (compact anchors [f0, f0 + Fc) of every wireframe): the anchor's
+// start token (model_para.py:201-205), log-probability 0, and the rule's state after column 0 -- a start token below ntok
+// leaves it empty; an edge is visited, is prev and opens a loop unless it closes on itself.  A start token in the terminator
+// range finishes the sequence at position 0 (the padding anchors).
+__global__ void constrain_init_kernel(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc,
+                                      int Fc, int f0, const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok,
+                                      const unsigned* follows, int L, int fw) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bc) return;
+  const int wl = i / Fc, f = f0 + i % Fc;
+  const int t = f < num_input[wl] ? f : pad_tok;
+  tok[i] = t;
+  lp[i] = 0.f;
+  fin[i] = (t >= term_lo && t < term_hi) ? 1 : 0;
+  dead[i] = 0;
+  unsigned* v = visited + (size_t)i * fw;
+  for (int k = 0; k < fw; ++k) v[k] = 0u;
+  int fi = -1, pv = -1;
+  const int e = t - ntok;
+  if (e >= 0 && e < L) {
+    v[e >> 5] = 1u << (e & 31);
+    fi = pv = e;
+    if (follows && ((follows[((size_t)wl * L + e) * fw + (e >> 5)] >> (e & 31)) & 1u)) fi = -1;
+  }
+  first[i] = fi;
+  prev[i] = pv;
+}
+
+// predict[(w, fo), :], logprob (same layout) and dead_end[(w, fo)] from the per-step records (tok, lp, fin, dead: [T, Btot],
+// row s = the state after s steps).  Position j is kept when j <= the stop step and the sequence was not finished before it:
+// last = min(finish position, stop step); rows behind the stop step are never looked at, so the result does not depend on
+// when the host saw the stop.  Rows fo >= num_input[w] of a de-duplicated decode read the one padding-anchor sequence.
+__global__ void constrain_finalize_kernel(const int* __restrict__ tok, const float* __restrict__ lp, const int* __restrict__ fin,
+                                          const int* __restrict__ dead, int Btot, int T, const int* __restrict__ steps_p,
+                                          const int* __restrict__ num_input, int dedup, int F, int w0, int nw, int Fc, int f0, int b0,
+                                          int64_t* __restrict__ predict, float* __restrict__ logprob, int* __restrict__ dead_end,
+                                          int* __restrict__ seq_of_row) {
+  const int steps = *steps_p;
+  const int total = nw * F;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int fo = i % F, wl = i / F;
+    int f = fo;
+    if (dedup) { const int n = num_input[w0 + wl]; f = fo < n ? fo : n; }
+    if (f < f0 || f >= f0 + Fc) continue;
+    const int seq = b0 + wl * Fc + (f - f0);
+    const size_t row = (size_t)(w0 + wl) * F + fo;
+    int64_t* out = predict + row * T;
+    float* olp = logprob + row * T;
+    int de = 0;
+    bool done = false;   // finished before position j
+    for (int j = 0; j < T; ++j) {
+      const bool in = j <= steps && !done;
+      out[j] = in ? tok[(size_t)j * Btot + seq] : 0;
+      olp[j] = (in && j >= 1) ? lp[(size_t)j * Btot + seq] : 0.f;
+      if (in) { de |= dead[(size_t)j * Btot + seq]; done = fin[(size_t)j * Btot + seq] != 0; }
+    }
+    dead_end[row] = de;
+    if (seq_of_row) seq_of_row[row] = seq;
+  }
+}
+
+}  // namespace
+
+extern "C" int ff_follow_table(const float* starts, const float* ends, int N, int L, const int* num_input, float tol,
+                               unsigned* bits, ff_stream_t stream) {
+  if (N == 0 || L == 0) return FF_OK;
+  FF_CHECK_ARG(N > 0 && L > 0 && starts && ends && num_input && bits, "ff_follow_table: bad sizes N=%d L=%d or a null pointer", N, L);
+  FF_CHECK_ARG(tol >= 0.f && ((long long)N * L + 3) / 4 < (1LL << 31), "ff_follow_table: tol=%g must be >= 0, N*L below 2^33", (double)tol);
+  hipStream_t st = (hipStream_t)stream;
+  FFProfScope prof(FF_CAT_ROWOP, (double)N * L * L, st);
+  hipLaunchKernelGGL(follow_table_kernel, dim3((unsigned)(((long long)N * L + 3) / 4)), dim3(256), 0, st, starts, ends, N, L,
+                     num_input, tol, bits);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi,
+                                const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
+                                unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
+                                int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                                int* count_ge, int* arrive, int* host_slot, ff_stream_t stream) {
+  if (B == 0) return FF_OK;
+  FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "ff_pointer_constrained: bad sizes B=%d S=%d", B, S);
+  FF_CHECK_ARG(logits && ldlogits >= S, "ff_pointer_constrained: logits missing or ldlogits < S");
+  FF_CHECK_ARG(!(flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "ff_pointer_constrained: unknown flag bits %d", flags);
+  FF_CHECK_ARG(ntok >= 0 && L >= 0 && L == S - ntok, "ff_pointer_constrained: L=%d must be S - ntok = %d - %d", L, S, ntok);
+  FF_CHECK_ARG(term_lo >= 0 && term_lo < term_hi && term_hi <= ntok, "ff_pointer_constrained: terminator range [%d, %d) empty or outside the %d special tokens",
+               term_lo, term_hi, ntok);
+  FF_CHECK_ARG(follows || !(flags & FF_CONSTRAIN_CONNECT), "ff_pointer_constrained: FF_CONSTRAIN_CONNECT needs the follow table");
+  FF_CHECK_ARG(fin_in && first_in && prev_in && visited && mask_rows && next_tok && logprob && fin_out && dead_end && first_out && prev_out,
+               "ff_pointer_constrained: null pointer");
+  FF_CHECK_ARG(!next_rows || (memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ldnext >= E && ff_aligned16(memory) && ff_aligned16(next_rows)),
+               "ff_pointer_constrained: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment");
+  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "ff_pointer_constrained: next_stats needs next_rows and E %% 32 == 0");
+  FF_CHECK_ARG(!arrive || (host_slot && count_ge), "ff_pointer_constrained: counter hand-over without a counter");
+  ConstrainArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p.memory = memory; a.p.S = S; a.p.E = E; a.p.mask = mask; a.p.kv_len = kv_len;
+  a.p.extra = mask_rows; a.p.ldextra = S;
+  a.p.B = B; a.p.spg = seqs_per_group;
+  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.next_rows = next_rows; a.p.ldnext = ldnext; a.p.next_stats = next_stats;
+  a.p.count_ge = count_ge; a.p.ge_bound = ntok; a.p.arrive = arrive; a.p.host_slot = host_slot;
+  a.p.term_lo = term_lo; a.p.term_hi = term_hi;
+  a.rows = mask_rows; a.follows = follows; a.L = L; a.fw = (L + 31) >> 5; a.flags = flags; a.ntok = ntok;
+  a.fin_in = fin_in; a.first_in = first_in; a.prev_in = prev_in; a.visited = visited;
+  a.fin_out = fin_out; a.first_out = first_out; a.prev_out = prev_out; a.dead_out = dead_end;
+  a.tok = next_tok; a.logprob = logprob;
+  hipStream_t st = (hipStream_t)stream;
+  FFProfScope prof(FF_CAT_POINTER, (double)B * S * 4.0, st);
+  hipLaunchKernelGGL(pointer_constrained_kernel, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+extern "C" int ff_pointer_constrained(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                      int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo,
+                                      int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
+                                      unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
+                                      int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
+                                      float* next_stats, int* count_ge, ff_stream_t stream) {
+  return ff_pointer_constrained_sync(logits, ldlogits, S, mask, kv_len, B, seqs_per_group, follows, L, flags, ntok, term_lo, term_hi,
+                                     fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out,
+                                     prev_out, memory, E, next_rows, ldnext, next_stats, count_ge, nullptr, nullptr, stream);
+}
+
+int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int Fc, int f0,
+                      const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok, const unsigned* follows, int L,
+                      hipStream_t st) {
+  hipLaunchKernelGGL(constrain_init_kernel, dim3(ff_cdiv(Bc, 256)), dim3(256), 0, st, tok, lp, fin, dead, first, prev, visited, Bc, Fc,
+                     f0, num_input, pad_tok, term_lo, term_hi, ntok, follows, L, (L + 31) >> 5);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+int ff_constrain_finalize(const int* tok, const float* lp, const int* fin, const int* dead, int Btot, int T, const int* steps_dev,
+                          const int* num_input, int dedup, int F, int w0, int nw, int Fc, int f0, int b0, int64_t* predict,
+                          float* logprob, int* dead_end, int* seq_of_row, hipStream_t st) {
+  const int total = nw * F;
+  hipLaunchKernelGGL(constrain_finalize_kernel, dim3(ff_cdiv(total, 256) < 1024 ? ff_cdiv(total, 256) : 1024), dim3(256), 0, st, tok,
+                     lp, fin, dead, Btot, T, steps_dev, num_input, dedup, F, w0, nw, Fc, f0, b0, predict, logprob, dead_end, seq_of_row);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}

@@ -32,6 +32,11 @@
 // (plan_beam_chunks), independent of each other -- no reorder.  A step's pointer launch is replaced by ff_pointer_sample, which
 // reads the caller's uniforms through a per-sequence row_id; every step leaves its (token, log-probability, finished) row in
 // the workspace and the output is packed from the rows up to the stop step.
+//
+// Constrained decode (ff_decode_constrained, opt-in, parallel variant): the default decode's plan (plan_chunks), one
+// sequence per anchor.  A step's pointer launch is replaced by ff_pointer_constrained, which masks the keys the enclosure walk
+// could not accept; per-step records and the rule's state (first, prev per step; visited words and the byte mask per sequence)
+// live last in the workspace, and the output is packed as the sampled decode's.
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
@@ -251,6 +256,12 @@ struct DecodeBuffers {
   // sequence reads, [Btot], written once per call
   float* sm_lp;
   int *sm_fin, *sm_row;
+  // constrained decode: [T, Btot] each, row s = the sequences' state after s steps (log-probability, finished, dead end, first,
+  // prev); the visited words [Btot, ceil(L/32)] and the constraint byte rows [Btot, S], both rewritten by every step
+  float* cn_lp;
+  int *cn_fin, *cn_dead, *cn_first, *cn_prev;
+  unsigned* cn_visited;
+  unsigned char* cn_rows;
 };
 
 // A micro-batch is a contiguous range [b0, b0 + Bc) of the COMPACT sequence index: nw >= 1 consecutive
@@ -377,9 +388,10 @@ bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
 // Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
 // want_lp: also the log-probability rows (ff_decode_lp) -- taken LAST, so that everything else lies where it lies without them.
 // beam: also the per-step records of a beam decode (ff_decode_beam), last as well.  forced: those of a forced decode, likewise.
-// sample: those of a sampled decode and its row_id array, likewise.
+// sample: those of a sampled decode and its row_id array, likewise.  constrain: those of a constrained decode and its state, likewise.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
-                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false, bool forced = false, bool sample = false) {
+                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false, bool forced = false, bool sample = false,
+                     bool constrain = false) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
   const int ns = plan_streams(p);
   const size_t Rmax = (size_t)(T - 1 > 0 ? T - 1 : 1) * Bch;
@@ -444,6 +456,16 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     b.sm_lp = bp.take<float>((size_t)T * Btot);
     b.sm_fin = bp.take<int>((size_t)T * Btot);
     b.sm_row = bp.take<int>(Btot);
+  }
+  if (constrain) {
+    b.cn_lp = bp.take<float>((size_t)T * Btot);
+    b.cn_fin = bp.take<int>((size_t)T * Btot);
+    b.cn_dead = bp.take<int>((size_t)T * Btot);
+    b.cn_first = bp.take<int>((size_t)T * Btot);
+    b.cn_prev = bp.take<int>((size_t)T * Btot);
+    const size_t fw = (size_t)(p->L + 31) / 32;   // visited words per sequence; one word at L = 0, so that the array is never empty
+    b.cn_visited = bp.take<unsigned>(Btot * (fw > 0 ? fw : 1));
+    b.cn_rows = bp.take<unsigned char>(Btot * (size_t)S);
   }
   if (out) *out = b;
   return bp.off;
@@ -738,6 +760,7 @@ struct DecodeRun {
   int forced_steps = 0;                       // ... and the largest of those
   const ff_sample_params* sample = nullptr;   // ff_decode_sample (null otherwise)
   int R = 0;                                  // ... its samples per anchor; 0 without sampling
+  const ff_constrain_params* con = nullptr;   // ff_decode_constrained (null otherwise)
   int validate(const ff_model* m_, const ff_decode_params* p_, const DecodeIO& io_, const void* workspace) {
     m = m_; io = io_;
     FF_RETURN_IF(check_model(m));
@@ -784,7 +807,7 @@ struct DecodeRun {
     nch = (int)chunks.size();
     Bump bp(workspace, workspace_bytes);
     layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr, W > 0, forced != nullptr,
-                  R > 0);
+                  R > 0, con != nullptr);
     if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
     for (Chunk& c : chunks) {
       c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
@@ -940,6 +963,15 @@ struct DecodeRun {
         FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
         continue;
       }
+      if (con) {
+        const int fw = (p->L + 31) / 32;
+        FF_RETURN_IF(ff_constrain_init(buf.tok_all + c.b0, buf.cn_lp + c.b0, buf.cn_fin + c.b0, buf.cn_dead + c.b0, buf.cn_first + c.b0,
+                                       buf.cn_prev + c.b0, buf.cn_visited + (size_t)c.b0 * fw, c.Bc, c.Fc, c.f0, io.num_input + c.w0,
+                                       m->num_token - 1, p->term_lo, p->term_hi, m->num_token,
+                                       con->follows ? con->follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, sts[c.sid]));
+        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
+        continue;
+      }
       // (retirement: the start tokens of the slots go to the chunk's perm area, free until its first compaction)
       hipLaunchKernelGGL(init_tokens_kernel, dim3(ff_cdiv(c.Bc, 256)), dim3(256), 0, sts[c.sid], buf.tok_all + c.b0,
                          c.Bc, c.Fc, c.f0, io.num_input ? io.num_input + c.w0 : nullptr, p->variant, m->num_token - 1,
@@ -972,6 +1004,10 @@ struct DecodeRun {
       }
       if (R) {
         FF_RETURN_IF(sample_step(c, sc, step, slot, folded_head, logits_dst, st));
+        continue;
+      }
+      if (con) {
+        FF_RETURN_IF(constrained_step(c, sc, step, slot, folded_head, logits_dst, st));
         continue;
       }
       ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, lagged ? buf.arrive + slot : nullptr,
@@ -1034,6 +1070,27 @@ struct DecodeRun {
                                   sample->top_k, sample->top_p, p->term_lo, p->term_hi, buf.tok_all + out, buf.sm_lp + out,
                                   buf.sm_fin + out, mem_w, E, c.x0 + (size_t)t * c.Bc * E, E, c.x0stat, buf.cnt_ge + slot,
                                   m->num_token, lagged ? buf.arrive + slot : nullptr, lagged ? pool->hpin_dev + slot : nullptr, st);
+  }
+  // Constrained decode, step `step` of one micro-batch: the decoder pass, the pointer GEMM (always the GEMM + reduce form, as a
+  // decode with log-probabilities), then ff_pointer_constrained in place of the pointer launch.  It reads the state row `step`
+  // and writes row t = step + 1, the chunk's next x0 rows (with their statistics) and the stop counter; the visited words and
+  // the byte rows belong to the sequence and are rewritten in stream order.  A step enqueued past the stop writes records and
+  // state that nothing reads.
+  int constrained_step(const Chunk& c, const Scratch& sc, int step, size_t slot, bool folded_head, float* logits_dst, hipStream_t st) {
+    const int t = step + 1, L = p->L, fw = (L + 31) / 32;
+    const float* mem_w = io.memory + (size_t)c.w0 * S * E;
+    FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
+    if (!folded_head)
+      FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
+                                       (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
+    const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
+    return ff_pointer_constrained_sync(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, c.Bc, c.Fc,
+                                       con->follows ? con->follows + (size_t)c.w0 * L * fw : nullptr, L, con->flags, m->num_token,
+                                       p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in,
+                                       buf.cn_visited + (size_t)c.b0 * fw, buf.cn_rows + (size_t)c.b0 * S, buf.tok_all + out,
+                                       buf.cn_lp + out, buf.cn_fin + out, buf.cn_dead + out, buf.cn_first + out, buf.cn_prev + out,
+                                       mem_w, E, c.x0 + (size_t)t * c.Bc * E, E, c.x0stat, buf.cnt_ge + slot,
+                                       lagged ? buf.arrive + slot : nullptr, lagged ? pool->hpin_dev + slot : nullptr, st);
   }
   // ---- forced decode ------------------------------------------------------------------------------------------------------------
   // The caller's paths as the token array (main stream, in front of the prologue's fork: every stream sees them).
@@ -1231,6 +1288,12 @@ struct DecodeRun {
                                         io.predict, io.seq_of_row, main_st));
         continue;
       }
+      if (con) {
+        FF_RETURN_IF(ff_constrain_finalize(buf.tok_all, buf.cn_lp, buf.cn_fin, buf.cn_dead, Btot, T, buf.steps_dev, io.num_input,
+                                           dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, io.predict, con->logprob, con->dead_end,
+                                           io.seq_of_row, main_st));
+        continue;
+      }
       const long total = (long)c.nw * F * T;
       const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
       hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
@@ -1268,7 +1331,8 @@ struct DecodeRun {
 
 // One decode call from validation to the packed outputs (ff_decode / ff_decode_lp: beam null; ff_decode_beam).
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam, const ff_forced_params* forced = nullptr, const ff_sample_params* sample = nullptr);
+               const ff_beam_params* beam, const ff_forced_params* forced = nullptr, const ff_sample_params* sample = nullptr,
+               const ff_constrain_params* constrain = nullptr);
 
 }  // namespace
 
@@ -1465,10 +1529,41 @@ extern "C" int ff_decode_sample(const ff_model* m, const ff_decode_params* p, co
                     workspace, workspace_bytes, nullptr, nullptr, sample);
 }
 
+extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
+  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
+  int btot = 0, max_bc = 0, nch = 0;
+  plan_chunks(p, num_input_host, 1, nullptr, &btot, &max_bc, &nch);
+  Bump bp(nullptr, 0);
+  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, false, false, false, true) + 256;
+}
+
+extern "C" int ff_decode_constrained(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                     const unsigned char* mask, const int* kv_len, const int* num_input,
+                                     const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                                     int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                                     float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                                     size_t workspace_bytes, const ff_constrain_params* constrain, ff_stream_t stream) {
+  FF_CHECK_ARG(m && p && constrain, "ff_decode_constrained: null model, params or constrain params");
+  FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode_constrained: the constrained decode is a parallel-variant option");
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
+               "ff_decode_constrained: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask");
+  FF_CHECK_ARG(!(constrain->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "ff_decode_constrained: unknown flag bits %d", constrain->flags);
+  FF_CHECK_ARG(constrain->follows || !(constrain->flags & FF_CONSTRAIN_CONNECT), "ff_decode_constrained: FF_CONSTRAIN_CONNECT needs the follow table");
+  FF_CHECK_ARG(p->term_lo >= 0 && p->term_lo < p->term_hi && p->term_hi <= m->num_token,
+               "ff_decode_constrained: terminator range [%d, %d) empty or outside the %d special tokens", p->term_lo, p->term_hi, m->num_token);
+  FF_CHECK_ARG(constrain->logprob && constrain->dead_end && !trace_best && !trace_second && !pointer_out,
+               "ff_decode_constrained: logprob and dead_end required; no best / second traces, no pointer_out");
+  return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
+                                   nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr},
+                    workspace, workspace_bytes, nullptr, nullptr, nullptr, constrain);
+}
+
 namespace {
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam, const ff_forced_params* forced, const ff_sample_params* sample) {
+               const ff_beam_params* beam, const ff_forced_params* forced, const ff_sample_params* sample,
+               const ff_constrain_params* constrain) {
   DecodeRun r;
+  r.con = constrain;
   r.forced = forced;
   r.sample = sample;
   r.R = sample ? sample->num_samples : 0;

@@ -216,6 +216,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
         raise ValueError("decode_sharded does not implement beam_width (a beam decode takes no external stop rule)")
     if getattr(model, "num_samples", 0):
         raise ValueError("decode_sharded does not implement num_samples (a sampled decode takes no external stop rule)")
+    if getattr(model, "constrain", None) is not None:
+        raise ValueError("decode_sharded does not implement constrain (a constrained decode takes no external stop rule)")
     rank, world = dist_mod.get_rank(group), dist_mod.get_world_size(group)
     parallel = isinstance(model, SurfaceFormer_Parallel)
     variant = _L.FF_PARALLEL if parallel else _L.FF_SEQ2SEQ

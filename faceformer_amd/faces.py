@@ -24,7 +24,7 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
-           "parse_parallel_samples_scored"]
+           "parse_parallel_samples_scored", "follow_table", "pack_follow_bits"]
 
 
 def _tok(token, name, default):
@@ -332,6 +332,43 @@ def _apply_own_stop_rule_scored(predict, logprob, token, parallel, eos=None):
 # ---- geometric post-processing (co-edge configs) ---------------------------------------------------
 def _connects(e1, e2, tol):
     return abs(e1[-1][0] - e2[0][0]) < tol and abs(e1[-1][1] - e2[0][1]) < tol
+
+
+def follow_table(edges, tol, num_input=None):
+    """The co-edge follow table the constrained decode walks, in numpy: table[a, b] is True iff edge b starts
+    where edge a ends -- _connects(edges[a], edges[b], tol), evaluated in float32 (one float32 subtraction and one float32
+    compare per coordinate, as ff_follow_table does, so the two agree bit for bit).  edges: a list of point lists (a record's
+    "edges"), or an array [L, P, D], or the pair (starts, ends) of float32 end points [..., L, 2]; leading batch axes are kept.
+    num_input (optional, one count per leading index): rows and columns at and beyond it are False."""
+    if isinstance(edges, tuple) and len(edges) == 2:
+        starts, ends = (np.asarray(x, dtype=np.float32) for x in edges)
+    else:
+        pts = [np.asarray(e, dtype=np.float32) for e in edges] if isinstance(edges, list) else np.asarray(edges, dtype=np.float32)
+        if isinstance(pts, list):
+            starts = np.stack([e[0][:2] for e in pts]) if pts else np.zeros((0, 2), np.float32)
+            ends = np.stack([e[-1][:2] for e in pts]) if pts else np.zeros((0, 2), np.float32)
+        else:
+            starts, ends = pts[..., 0, :2], pts[..., -1, :2]
+    t = np.float32(tol)
+    d = np.abs(ends[..., :, None, :] - starts[..., None, :, :])          # float32 throughout
+    table = (d[..., 0] < t) & (d[..., 1] < t)
+    if num_input is not None:
+        n = np.asarray(num_input).reshape(table.shape[:-2] + (1,))
+        ok = np.arange(table.shape[-1]) < n
+        table = table & ok[..., :, None] & ok[..., None, :]
+    return table
+
+
+def pack_follow_bits(table):
+    """A boolean follow table [..., L, L] as the words ff_follow_table writes: int32 [..., L, ceil(L/32)], bit b % 32 of word
+    b // 32 of row a = table[a, b] (the uint32 words, viewed as int32 for torch)."""
+    table = np.asarray(table, dtype=bool)
+    L = table.shape[-1]
+    fw = (L + 31) // 32
+    padded = np.zeros(table.shape[:-1] + (fw * 32,), dtype=np.uint64)
+    padded[..., :L] = table
+    words = (padded.reshape(table.shape[:-1] + (fw, 32)) << np.arange(32, dtype=np.uint64)).sum(axis=-1)
+    return words.astype(np.uint32).view(np.int32)
 
 
 def is_face_enclosed(edges, face_indices, tol):

@@ -117,6 +117,38 @@ def check_sample_options(num_samples, temperature, top_k, top_p, variant, retire
         raise ValueError("num_samples needs term_range = (lo, hi) with lo < hi")
 
 
+CONSTRAIN_MODES = {"no_repeat": _L.FF_CONSTRAIN_NO_REPEAT, "loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT}
+
+
+def constrain_flags(constrain):
+    """The flag bits of a `constrain` value: None -> None (the option is off), "no_repeat" / "loops", or the bits themselves
+    (0..3: the C entries also take CONNECT alone, and 0, which is the plumbing's identity with the retired greedy decode)."""
+    if constrain is None:
+        return None
+    if isinstance(constrain, str):
+        if constrain not in CONSTRAIN_MODES:
+            raise ValueError("constrain=%r: must be None, 'no_repeat' or 'loops'" % (constrain,))
+        return CONSTRAIN_MODES[constrain]
+    if isinstance(constrain, bool) or not isinstance(constrain, int) or not 0 <= constrain <= 3:
+        raise ValueError("constrain=%r: must be None, 'no_repeat', 'loops' or flag bits 0..3" % (constrain,))
+    return int(constrain)
+
+
+def check_constrain_options(flags, variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, beam_width,
+                            num_samples, term_range, follow_table):
+    """The combinations a constrained decode rejects (ff_decode_constrained's FF_ERR_ARG list, and the options of decode() it
+    cannot be combined with), as ValueError before anything is launched."""
+    if variant != _L.FF_PARALLEL:
+        raise ValueError("constrain is a parallel-variant option")
+    if retire or return_pointer or no_stop or stop_callback is not None or extra_mask is not None or logprob or beam_width or num_samples:
+        raise ValueError("constrain excludes retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, beam_width and "
+                         "num_samples")
+    if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
+        raise ValueError("constrain needs term_range = (lo, hi) with lo < hi")
+    if flags & _L.FF_CONSTRAIN_CONNECT and follow_table is None:
+        raise ValueError("constrain='loops' needs follow_table (ops.follow_table)")
+
+
 def check_forced_options(paths, lengths, rows, T, S, retire=False, beam_width=None, logprob=False, return_pointer=False,
                          stop_callback=None, stop_each_eos=False, extra_mask=None):
     """What a forced decode rejects (ff_decode_forced's FF_ERR_ARG list, and the options of decode() it has no argument for), as
@@ -394,7 +426,7 @@ class PathEngine:
                tok_sos=1, tok_eos=3, x3_min_rows=0, chunk_max_seqs=0, ln_fuse_max_rows=0,
                trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
-               num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None):
+               num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).
 
@@ -419,9 +451,26 @@ class PathEngine:
         after the sample's finish position and the stop step), `sample_logprob` (same layout, fp32: the model's log-probability
         of every drawn token) and `sample_scores` [N*F*R] (their sums); `predict` is sample 0; with trace=True `logits` is
         [T-1, N*F*R, S] in output-row order.  Needs term_range; excludes retire, return_pointer, no_stop, stop_callback,
-        extra_mask, logprob and beam_width (ValueError).  temperature=0 equals the retire=True decode, R times."""
+        extra_mask, logprob and beam_width (ValueError).  temperature=0 equals the retire=True decode, R times.
+
+        constrain="no_repeat" / "loops" (parallel variant, ff_decode_constrained; None: the greedy decode above; the
+        flag bits 0..3 are taken too): the greedy decode over keys the enclosure filter can accept.  follow_table [N, L,
+        ceil(L/32)] int32 on the device (ops.follow_table), required by "loops".  `predict` is the constrained decode (zero after
+        the row's finish position and the stop step); also `logprob` [N*F, T] fp32 (under the renormalised distribution) and
+        `dead_end` [N*F] int32; with trace=True `logits` [T-1, N*F, S] holds the constrained masked rows.  Needs term_range;
+        excludes retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, beam_width and num_samples (ValueError).
+        Bits 0 equal the retire=True decode."""
         W = int(beam_width or 0)
         R = int(num_samples or 0)
+        CF = constrain_flags(constrain)
+        if CF is not None:
+            check_constrain_options(CF, variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, W, R, term_range,
+                                    follow_table)
+            if follow_table is not None:
+                Lt = memory.shape[1] - self.num_token
+                if (not torch.is_tensor(follow_table) or follow_table.dtype != torch.int32
+                        or tuple(follow_table.shape) != (memory.shape[0], Lt, (Lt + 31) // 32)):
+                    raise ValueError("follow_table must be an int32 tensor of shape [%d, %d, %d]" % (memory.shape[0], Lt, (Lt + 31) // 32))
         if R:
             check_sample_options(R, temperature, top_k, top_p, variant, retire, return_pointer, no_stop, stop_callback, extra_mask,
                                  logprob, W, term_range)
@@ -458,7 +507,7 @@ class PathEngine:
             prm.retire_min_shrink = float(retire_min_shrink)
         if return_pointer or extra_mask is not None:   # (every padding-anchor row has its own extra-mask row)
             prm.flags &= ~_L.FF_DEDUP_PAD_ANCHORS
-        if W or R:
+        if W or R or CF is not None:
             prm.term_lo, prm.term_hi = int(term_range[0]), int(term_range[1])
         prm.tok_sos, prm.tok_eos = tok_sos, tok_eos
         prm.x3_min_rows = int(x3_min_rows) if self._planes else 0
@@ -483,8 +532,8 @@ class PathEngine:
         pointer = torch.zeros((max(T - 1, 1), B, E), device=dev, dtype=torch.float32) if return_pointer else None
         tl = tb = ts = rows = None
         G = W or R    # sequences per anchor of a beam / sampled decode
-        if trace and G:
-            tl = torch.full((max(T - 1, 1), B * G, S), float("nan"), device=dev, dtype=torch.float32)
+        if trace and (G or CF is not None):
+            tl = torch.full((max(T - 1, 1), B * max(G, 1), S), float("nan"), device=dev, dtype=torch.float32)
         elif trace:
             tl = torch.full((max(T - 1, 1), B, S), float("nan"), device=dev, dtype=torch.float32)
             tb = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
@@ -506,6 +555,15 @@ class PathEngine:
             sscores = torch.empty(B * R, device=dev, dtype=torch.float32)
             sprm = _L.SampleParams(R, float(temperature), int(top_k), float(top_p), _p(uniforms), _p(samples), _p(slp), _p(sscores))
             nbytes = self._lib.ff_decode_sample_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host, R)
+        elif CF is not None:
+            if follow_table is not None:
+                _dev(follow_table, "follow_table", torch.int32)
+                self._same_device(follow_table, "follow_table")
+                follow_table = follow_table.contiguous()
+            clp = torch.empty((B, T), device=dev, dtype=torch.float32)
+            cdead = torch.empty(B, device=dev, dtype=torch.int32)
+            cprm = _L.ConstrainParams(CF, _p(follow_table), _p(clp), _p(cdead))
+            nbytes = self._lib.ff_decode_constrained_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host)
         else:
             ws_bytes = self._lib.ff_decode_lp_workspace_bytes if logprob else self._lib.ff_decode_workspace_bytes
             nbytes = ws_bytes(C.byref(self.model), C.byref(prm), ni_host)
@@ -534,6 +592,8 @@ class PathEngine:
                 _L.check(self._lib.ff_decode_beam(*args, C.byref(bprm), _stream()), "ff_decode_beam")
             elif R:
                 _L.check(self._lib.ff_decode_sample(*args, C.byref(sprm), _stream()), "ff_decode_sample")
+            elif CF is not None:
+                _L.check(self._lib.ff_decode_constrained(*args, C.byref(cprm), _stream()), "ff_decode_constrained")
             elif logprob:
                 _L.check(self._lib.ff_decode_lp(*args, _p(lp), _stream()), "ff_decode_lp")
             else:
@@ -555,6 +615,12 @@ class PathEngine:
                 out["logits"], out["beam_parent"] = tl[:, idx], bparent[:, idx]
         elif R:
             out["samples"], out["sample_logprob"], out["sample_scores"] = samples, slp, sscores
+            if trace:   # (likewise)
+                idx = rows.long()
+                out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
+                out["logits"] = tl[:, idx]
+        elif CF is not None:
+            out["logprob"], out["dead_end"] = clp, cdead
             if trace:   # (likewise)
                 idx = rows.long()
                 out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0

@@ -143,6 +143,13 @@ class SampleParams(C.Structure):
                 ("samples", fptr), ("logprob", fptr), ("scores", fptr)]
 
 
+class ConstrainParams(C.Structure):
+    _fields_ = [("flags", C.c_int), ("follows", fptr), ("logprob", fptr), ("dead_end", fptr)]
+
+
+FF_CONSTRAIN_NO_REPEAT = 1
+FF_CONSTRAIN_CONNECT = 2
+
 # ff_stop_fn: int (*)(void* user, const int* step_counts, int num_steps)
 STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int)
 
@@ -242,6 +249,15 @@ SIGNATURES = {
                                    C.POINTER(C.c_int), fptr,
                                    fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                    C.c_size_t, C.POINTER(SampleParams), fptr]),
+    "ff_follow_table": (C.c_int, [fptr, fptr, C.c_int, C.c_int, fptr, C.c_float, fptr, fptr]),
+    "ff_pointer_constrained": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                         C.c_int, fptr, C.c_int, fptr, fptr, fptr]),
+    "ff_decode_constrained_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int)]),
+    "ff_decode_constrained": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                        C.POINTER(C.c_int), fptr,
+                                        fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                                        C.c_size_t, C.POINTER(ConstrainParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 
@@ -273,7 +289,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced* and *_sample* ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample* and *_constrain* ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

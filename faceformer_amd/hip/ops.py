@@ -545,6 +545,102 @@ def pointer_sample(logits, uniforms, temperature=1.0, top_k=0, top_p=1.0, row_id
 
 
 @_on_tensor_device
+def follow_table(starts, ends, num_input, tol):
+    """The co-edge follow table of N wireframes (ff_follow_table).  starts / ends [N, L, 2] fp32: (x, y) of every
+    co-edge's first and last point; num_input [N] int32.  Returns bits [N, L, ceil(L/32)] int32 (the uint32 words): bit b of row
+    a is set iff a, b < num_input[w] and |ends[a] - starts[b]| < tol in x and in y (fp32 subtraction, fp32 compare)."""
+    _dev(starts, "starts"), _dev(ends, "ends"), _dev(num_input, "num_input", torch.int32)
+    if starts.dim() != 3 or starts.size(2) != 2 or starts.shape != ends.shape:
+        raise ValueError("starts and ends must both be [N, L, 2]")
+    N, L = starts.size(0), starts.size(1)
+    if num_input.dim() != 1 or num_input.numel() != N:
+        raise ValueError("num_input must hold one count per wireframe")
+    if not float(tol) >= 0.0:
+        raise ValueError("tol must be >= 0")
+    starts, ends, num_input = starts.contiguous(), ends.contiguous(), num_input.contiguous()
+    bits = torch.zeros((N, L, (L + 31) // 32), device=starts.device, dtype=torch.int32)
+    _L.check(_L.load().ff_follow_table(_p(starts), _p(ends), N, L, _p(num_input), float(tol), _p(bits), _stream()), "ff_follow_table")
+    return bits
+
+
+@_on_tensor_device
+def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=None, memory=None, mask=None, kv_len=None,
+                        seqs_per_group=1, term_range=(1, 4), want_rows=False, want_stats=False, counter=None):
+    """One constrained selection step of the pointer head (ff_pointer_constrained).  logits [B, S] fp32 raw dot
+    products (masked IN PLACE with the constrained mask; rows of finished sequences are not touched); fin / first / prev [B]
+    int32: the state before the step (first / prev: edge index, -1 = none; the loop is open only when both are edges); visited [B, ceil(L/32)] int32 words, L = S - ntok
+    (not modified: the updated copy is returned); follows [W, L, ceil(L/32)] int32 words (ops.follow_table) or None when CONNECT
+    is clear.  Row b belongs to wireframe b // seqs_per_group of mask / kv_len / memory / follows.  Returns dict(next, fin,
+    dead_end, first, prev [B] int32; logprob [B] fp32; visited; mask_rows [B, S] uint8: the rule's own mask of every unfinished
+    row; [rows [B, E]]; [stats [B, E/32, 2]])."""
+    _dev(logits, "logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be a 2-D tensor with unit inner stride")
+    B, S = logits.shape
+    flags, ntok = int(flags), int(ntok)
+    L = S - ntok
+    fw = (L + 31) // 32
+    lo, hi = int(term_range[0]), int(term_range[1])
+    if flags & ~(_L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT):
+        raise ValueError("unknown constraint flag bits %d" % flags)
+    if L < 0 or not 0 <= lo < hi <= ntok:
+        raise ValueError("need 0 <= term_lo < term_hi <= ntok <= S")
+    if follows is None and flags & _L.FF_CONSTRAIN_CONNECT:
+        raise ValueError("FF_CONSTRAIN_CONNECT needs the follow table")
+    spg = int(seqs_per_group)
+    if spg < 1:
+        raise ValueError("seqs_per_group must be positive")
+    nw = (B + spg - 1) // spg
+    for x, name in ((fin, "fin"), (first, "first"), (prev, "prev")):
+        _dev(x, name, torch.int32)
+        if x.dim() != 1 or x.numel() != B:
+            raise ValueError("%s must hold one int32 per row of logits" % name)
+    fin, first, prev = fin.contiguous(), first.contiguous(), prev.contiguous()
+    _dev(visited, "visited", torch.int32)
+    if tuple(visited.shape) != (B, fw):
+        raise ValueError("visited must be [%d, %d]" % (B, fw))
+    visited = visited.clone().contiguous()
+    if follows is not None:
+        _dev(follows, "follows", torch.int32)
+        if follows.dim() != 3 or not follows.is_contiguous() or follows.size(0) < nw or tuple(follows.shape[1:]) != (L, fw):
+            raise ValueError("follows must be a contiguous [>= %d, %d, %d] tensor" % (nw, L, fw))
+    dev = logits.device
+    for x, name, dt in ((mask, "mask", torch.uint8), (kv_len, "kv_len", torch.int32)):
+        if x is not None:
+            _dev(x, name, dt)
+            if not x.is_contiguous() or x.size(0) < nw or (name == "mask" and (x.dim() != 2 or x.size(1) != S)):
+                raise ValueError("%s must be contiguous and cover %d wireframes of %d keys" % (name, nw, S))
+    i32 = lambda: torch.empty(B, device=dev, dtype=torch.int32)
+    out = {"next": i32(), "logprob": torch.empty(B, device=dev, dtype=torch.float32), "fin": i32(), "dead_end": i32(),
+           "first": i32(), "prev": i32(), "visited": visited, "mask_rows": torch.zeros((B, S), device=dev, dtype=torch.uint8)}
+    rows, stats, E = None, None, 0
+    if memory is not None:
+        _dev(memory, "memory")
+        if memory.dim() != 3 or not memory.is_contiguous() or memory.size(1) != S or memory.size(0) < nw:
+            raise ValueError("memory must be a contiguous [>= %d, %d, E] tensor" % (nw, S))
+        E = memory.size(2)
+    if want_rows or want_stats:
+        if memory is None:
+            raise ValueError("rows / stats need memory")
+        rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
+        if want_stats:
+            if E % 32:
+                raise ValueError("stats need E % 32 == 0")
+            stats = out["stats"] = torch.empty((B, E // 32, 2), device=dev, dtype=torch.float32)
+    if counter is not None:
+        _dev(counter, "counter", torch.int32)
+    # (L = 0: no edge key, nothing of the table or the visited words is read -- one word each so that the pointers are not null)
+    one = torch.zeros(1, device=dev, dtype=torch.int32)
+    vis = visited if fw else one
+    fol = one if (follows is not None and not (L and fw)) else follows
+    _L.check(_L.load().ff_pointer_constrained(
+        _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(fol), L, flags, ntok, lo, hi, _p(fin), _p(first),
+        _p(prev), _p(vis), _p(out["mask_rows"]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(out["dead_end"]),
+        _p(out["first"]), _p(out["prev"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter), _stream()), "ff_pointer_constrained")
+    return out
+
+
+@_on_tensor_device
 def gather_rows(memory, tok, seqs_per_group=1):
     _dev(memory, "memory"), _dev(tok, "tok", torch.int32)
     N, S, E = memory.shape

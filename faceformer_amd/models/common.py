@@ -75,6 +75,14 @@ class SurfaceFormerBase(nn.Module):
                                        # predict_sample_logprob (N x F x R x T) and predict_sample_scores (N x F x R); predict is
                                        # sample 0, a fair draw.  0 = greedy.  Not with retire_finished, beam_width, return_logprob,
                                        # an extra mask, score(), dist.decode_sharded or the single-sequence model (ValueError)
+        self.constrain = None          # parallel model: "no_repeat" or "loops" decodes greedily over the keys the harness's
+                                       # enclosure filter can accept: no edge twice / only an edge that starts
+                                       # where the last one ended while a loop is open; forward_eval adds predict_logprob
+                                       # (N x F x T, under the renormalised distribution) and predict_dead_end (N x F).  None =
+                                       # greedy.  Not with retire_finished, beam_width, num_samples, return_logprob, an extra
+                                       # mask, score(), dist.decode_sharded or the single-sequence model (ValueError)
+        self.constrain_tol = 2e-4      # ... two end points coincide below this distance in x and in y (the harness's
+                                       # post_process.enclosedness_tol); inputs["follow_table"] overrides the built table
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
         self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
         self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
@@ -281,6 +289,8 @@ class SurfaceFormerBase(nn.Module):
         greedy decode and is not looked at: a forced decode has no stop rule."""
         if int(getattr(self, "num_samples", 0) or 0):
             raise ValueError("score() excludes num_samples: set model.num_samples = 0 to score given paths")
+        if getattr(self, "constrain", None) is not None:
+            raise ValueError("score() excludes constrain: set model.constrain = None to score given paths")
         if not self.engine_supported():
             raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
         eng, memory, mask, kv_len = self._encode(inputs)

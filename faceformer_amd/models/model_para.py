@@ -10,6 +10,7 @@ lowest index (173-179); the loop stops after the first step whose tokens are all
 and masks are never replicated per sequence (212-214), cross-attention K/V are projected once, the
 last layer and the output projection are evaluated for the newest position only.
 """
+import numpy as _np
 import torch
 
 from .. import faces as _faces
@@ -44,11 +45,22 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
          -- also predict_samples and predict_sample_logprob N x F x R x T (zero after a sample's face-type token and
         after the stop step) and predict_sample_scores N x F x R (summed log-probabilities under the model); predict is sample 0.
         The uniforms come from torch.Generator(device).manual_seed(sample_seed), or from inputs["sample_uniforms"]
-        [T-1, N*F*R]; either way column (w*F + f)*R + k belongs to wireframe w of the batch AS GIVEN."""
+        [T-1, N*F*R]; either way column (w*F + f)*R + k belongs to wireframe w of the batch AS GIVEN.
+        constrain = "no_repeat" / "loops" (default None): the greedy decode over the keys the enclosure filter can accept
+         -- predict is the constrained decode (zero after a row's face-type token and after the stop step), also
+        predict_logprob N x F x T (under the renormalised distribution) and predict_dead_end N x F.  The follow table is built
+        from the end points input[:, :, 0, :2] / input[:, :, -1, :2] with constrain_tol, or taken from inputs["follow_table"]
+        (bool N x L x L, or the packed int32 words N x L x ceil(L/32)), for the batch AS GIVEN."""
         label = inputs["label"]
         T = self.max_face_length
         W = int(getattr(self, "beam_width", 0) or 0)
         R = int(getattr(self, "num_samples", 0) or 0)
+        CF = _engine.constrain_flags(getattr(self, "constrain", None))
+        if CF is not None:
+            if not self.engine_supported():
+                raise ValueError("constrain needs the native engine: this model's constructor arguments take the sub-module loop")
+            if W or R or self.retire_finished or getattr(self, "return_logprob", False) or inputs.get("extra_mask") is not None:
+                raise ValueError("constrain excludes beam_width, num_samples, retire_finished, return_logprob and an extra mask")
         if R:
             if not self.engine_supported():
                 raise ValueError("num_samples needs the native engine: this model's constructor arguments take the sub-module loop")
@@ -99,6 +111,10 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         if R:
             skw = dict(num_samples=R, temperature=float(self.sample_temperature), top_k=int(self.sample_top_k),
                        top_p=float(self.sample_top_p), uniforms=self._sample_uniforms(inputs, memory.device, T, N, F, R, order))
+        if CF is not None:
+            # (without CONNECT nothing reads the table: neither the mask nor, first being unused, the closure test)
+            table = self._follow_table(inputs, memory.device, num_input, order) if CF & _L.FF_CONSTRAIN_CONNECT else None
+            skw = dict(constrain=CF, follow_table=table)
         out = eng.decode(memory, mask, kv_len, _L.FF_PARALLEL, T=T, F=F, num_input=ni, staged_num_input=staged,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs,
@@ -108,14 +124,16 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
                          logprob=want_lp, beam_width=W or None, **skw)
         pred = out["predict"].view(N, F, T)
         smp = (out["samples"].view(N, F, R, T), out["sample_logprob"].view(N, F, R, T), out["sample_scores"].view(N, F, R)) if R else None
-        lp = out["logprob"].view(N, F, T) if want_lp else None
+        lp = out["logprob"].view(N, F, T) if (want_lp or CF is not None) else None
+        dead = out["dead_end"].view(N, F) if CF is not None else None
         beams = out["beams"].view(N, F, W, T) if W else None
         bscores = out["beam_scores"].view(N, F, W) if W else None
         if order is not None:
             inv = torch.empty(N, dtype=torch.long, device=pred.device)
             inv[torch.tensor(order, device=pred.device)] = torch.arange(N, device=pred.device)
             pred = pred.index_select(0, inv)
-            lp = lp.index_select(0, inv) if want_lp else None
+            lp = lp.index_select(0, inv) if lp is not None else None
+            dead = dead.index_select(0, inv) if dead is not None else None
             if W:
                 beams, bscores = beams.index_select(0, inv), bscores.index_select(0, inv)
             if R:
@@ -127,6 +145,8 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
             inputs["predict_beams"], inputs["predict_beam_scores"] = beams, bscores
         if want_lp:
             inputs["predict_logprob"] = lp
+        if CF is not None:
+            inputs["predict_logprob"], inputs["predict_dead_end"] = lp, dead
         self.last_decode_stats = {"decoded_seqs": sum(min(F, n + 1) for n in num_input), "rows": N * F,
                                   "slot_rows": out["slot_rows"], "steps": out["steps"]}
         if W:   # (W sequences per decoded anchor; `rows` stays the reference's N * F)
@@ -136,6 +156,33 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
             self.last_decode_stats["decoded_seqs"] *= R
             self.last_decode_stats["num_samples"] = R
         return inputs
+
+    def _follow_table(self, inputs, device, num_input, order):
+        """The follow table [N, L, ceil(L/32)] int32 of a constrained decode in the DECODE's wireframe order: built on the device
+        from the edges' end points (ops.follow_table with constrain_tol), or inputs["follow_table"] -- bool [N, L, L] or the
+        packed words -- for the batch as given; then permuted like the wireframes when they are decoded sorted by edge count."""
+        from ..hip import ops as _ops
+        x = inputs["input"]
+        N, L = x.size(0), x.size(1)
+        fw = (L + 31) // 32
+        given = inputs.get("follow_table")
+        if given is None:
+            ni = torch.tensor(num_input, dtype=torch.int32).to(device)
+            bits = _ops.follow_table(x[:, :, 0, :2].to(device=device, dtype=torch.float32).contiguous(),
+                                     x[:, :, -1, :2].to(device=device, dtype=torch.float32).contiguous(), ni, float(self.constrain_tol))
+        else:
+            if torch.is_tensor(given) and given.dtype == torch.int32 and tuple(given.shape) == (N, L, fw):
+                bits = given.to(device)                          # packed words: taken as they are (no copy when on the device)
+            else:
+                g = _np.asarray(given.cpu().numpy() if torch.is_tensor(given) else given)
+                if g.dtype == _np.bool_ and g.shape == (N, L, L):
+                    g = _faces.pack_follow_bits(g)
+                if g.dtype != _np.int32 or g.shape != (N, L, fw):
+                    raise ValueError("follow_table must be bool [%d, %d, %d] or packed int32 [%d, %d, %d]" % (N, L, L, N, L, fw))
+                bits = torch.as_tensor(g).to(device)
+        if order is not None:
+            bits = bits.index_select(0, torch.tensor(order, device=device))
+        return bits.contiguous()
 
     def _sample_uniforms(self, inputs, device, T, N, F, R, order):
         """The uniforms [T-1, N*F*R] of a sampled decode in the DECODE's wireframe order: made (or given) for the batch as given,

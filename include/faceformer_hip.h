@@ -799,6 +799,82 @@ int ff_decode_sample(const ff_model* m, const ff_decode_params* p,
                      float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                      void* workspace, size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream);
 
+/* ---- loop-constrained greedy decode of the pointer head (opt-in, parallel variant; entries added within ABI 105) --
+ * The reference decodes greedily: select_next takes the argmax of the masked logit row (model_para.py:173-179) inside the loop
+ * of model_para.py:216-233, and its harness then drops every predicted face that is not one or more closed chains of co-edges
+ * (post_processing.py's enclosure walk, is_face_enclosed / filter_faces_by_encloseness).  These entries restate those two call
+ * sites with ONE change: keys the enclosure walk could not accept are masked before the argmax.
+ *
+ * The rule, on tokens.  ntok = token.len; [term_lo, term_hi) = [face_type_offset, len); edge e is token ntok + e;
+ * follows[w][a][b] is a bit: edge b of wireframe w starts where edge a ends.
+ * Per-sequence state, a function of the row's prefix (column 0, the start token, included):
+ *   visited  the edge tokens in the prefix;  prev  the last edge token;  first  the first edge of the currently open loop, or none.
+ * State update when an edge e is appended:
+ *   1. if first is none, set first = e;   2. set prev = e;   3. if follows[prev][first], the loop is closed and first becomes none.
+ * A one-edge loop closes on itself.  This is exactly is_face_enclosed's walk.  A start token below ntok leaves the state empty
+ * (closed, nothing visited).  (Without a follow table -- allowed when CONNECT is clear -- step 3 never fires.)
+ * A sequence is finished from the first position holding a terminator, the start token included (the rule of
+ * FF_RETIRE_FINISHED's predict and of the sample mode); a dead end (below) finishes it as well.
+ * Keys additionally masked for one unfinished row, on top of padding and kv_len (masked keys are set to finfo.min = -FLT_MAX,
+ * as select_next leaves them):
+ *   FF_CONSTRAIN_NO_REPEAT   every edge token in visited is masked.
+ *   FF_CONSTRAIN_CONNECT, loop open (first != none):  every special token is masked; every edge b without follows[prev][b] is
+ *       masked.  Dead end: no edge key is left live after all masks -- the terminators [term_lo, term_hi) are then un-masked
+ *       instead, the sequence ends there, and dead_end[row] = 1.
+ *   FF_CONSTRAIN_CONNECT, loop closed:  every special token outside [term_lo, term_hi) is masked; edges are limited only by
+ *       NO_REPEAT.
+ * Selection: the token is the argmax of the constrained row, lowest index on ties; logprob = -log sum_s exp(l[s] - l[i*]) over
+ * the constrained row (DESIGN.md 12's evaluation on that row: the log-probability under the RENORMALISED distribution).  A row
+ * with no live key gives token 0 and -log S.
+ * Stop and padding follow the sample mode: the decode stops after the first step at which no unfinished sequence selected a
+ * token >= ntok, else after T-1 steps; tokens and log-probabilities are 0 after min(finish position, stop step); column 0 of
+ * logprob is 0; padding-anchor rows are finished at 0.  With both bits clear the result is FF_RETIRE_FINISHED's predict of the
+ * greedy decode, token for token, with the same steps.
+ *
+ * ff_follow_table: bits [N, L, ceil(L/32)] uint32 from starts / ends [N, L, 2] fp32 (x, y of every co-edge's first and last
+ *   point): bit b of row a is set iff a, b < num_input[w] (clamped into [0, L]) and fabsf(ends[a].x - starts[b].x) < tol and the
+ *   same in y -- one fp32 subtraction and one fp32 compare each.  Bits at and beyond L in the last word are 0.
+ * ff_pointer_constrained: one step of B sequences.  Row b belongs to wireframe b / seqs_per_group (mask [wireframes, S], kv_len
+ *   [wireframes], memory [wireframes, S, E], follows [wireframes, L, ceil(L/32)]); L must equal S - ntok.
+ *   logits    [B, ldlogits] raw dot products; masked IN PLACE with the constrained mask (rows of finished sequences are not touched).
+ *   fin_in / first_in / prev_in  [B] int32 state before the step (first / prev: edge index, -1 = none; values outside [0, L) read
+ *             as none; a row whose first OR prev is none is CLOSED -- the open-loop rules need both); visited [B, ceil(L/32)] uint32, updated IN PLACE with the selected edge.
+ *   mask_rows [B, S] bytes, out: the constraint row of every unfinished sequence (1 = masked by the rule).
+ *   next_tok, logprob, fin_out, dead_end (this step's), first_out, prev_out [B]: outputs; the *_out may be the *_in.
+ *   A finished row: token 0, log-probability 0, state carried over.
+ *   next_rows / next_stats (optional): as ff_pointer_forced.  count_ge (optional): += number of unfinished rows whose token is >= ntok.
+ * ff_decode_constrained: the parallel decode under the rule; ff_decode's arguments, then ff_constrain_params:
+ *   follows   [N, L, ceil(L/32)] DEVICE (may be NULL when CONNECT is clear);  logprob [N*F, T] fp32;  dead_end [N*F] int32.
+ *   trace_logits (optional) [T-1, N*F, S], indexed by decoded sequence (seq_of_row): the CONSTRAINED masked row of every sequence
+ *   still unfinished before the step; a finished sequence's row holds the raw dot products.
+ * FF_ERR_ARG before any launch for: FF_SEQ2SEQ, FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn, an extra_mask,
+ * best / second traces, a NULL table when CONNECT is set, a NULL logprob / dead_end, unknown flag bits, term_lo >= term_hi or
+ * term_hi > num_token.  ff_decode_constrained_workspace_bytes: the workspace it needs (ff_decode_workspace_bytes' rules, plus the
+ * per-step records and the state, taken last).  The other decode entries launch and lay out what they did before these. */
+#define FF_CONSTRAIN_NO_REPEAT 1
+#define FF_CONSTRAIN_CONNECT 2
+int ff_follow_table(const float* starts, const float* ends, int N, int L, const int* num_input, float tol, unsigned int* bits,
+                    ff_stream_t stream);
+int ff_pointer_constrained(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                           int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok, int term_lo, int term_hi,
+                           const int* fin_in, const int* first_in, const int* prev_in, unsigned int* visited,
+                           unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
+                           int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                           int* count_ge, ff_stream_t stream);
+typedef struct ff_constrain_params {
+  int flags;
+  const unsigned int* follows;
+  float* logprob;
+  int* dead_end;
+} ff_constrain_params;
+size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host);
+int ff_decode_constrained(const ff_model* m, const ff_decode_params* p,
+                          const float* memory, const unsigned char* mask, const int* kv_len,
+                          const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                          int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                          float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                          void* workspace, size_t workspace_bytes, const ff_constrain_params* constrain, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

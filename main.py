@@ -69,6 +69,13 @@ def decode_batch_samples(model, batch):
     return out["predict"].cpu().numpy(), out["predict_samples"].cpu().numpy(), out["predict_sample_scores"].cpu().numpy()
 
 
+def decode_batch_constrained(model, batch):
+    """(`predict`, `predict_dead_end`) of `model(batch)` as numpy arrays (--constrain: the model's constrain is set)."""
+    with torch.no_grad():
+        out = model(batch)
+    return out["predict"].cpu().numpy(), out["predict_dead_end"].cpu().numpy()
+
+
 def score_batch(model, batch):
     """`model.score(batch)` on the data set's own label rows (--score-labels) as numpy arrays: dict(logprob, greedy, rank, paths
     [N, ..., T], lengths, seq_logprob [N, ...])."""
@@ -79,7 +86,7 @@ def score_batch(model, batch):
             "paths": paths.cpu().numpy(), "lengths": lengths.reshape(lp.shape[:-1]).cpu().numpy(), "seq_logprob": out["score_seq_logprob"].cpu().numpy()}
 
 
-def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None):
+def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -91,7 +98,10 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     (faces.score_summary; null when the sample has no scored label token).
     samples (--sample; (tokens [F, R, T], scores [F, R]) of this sample): the record also gets `pred_sample_faces`,
     `pred_sample_face_scores` and `pred_sample_face_votes`, the de-duplicated faces over ALL draws of the wireframe's own anchors
-    ranked by their best score, with the number of draws that produced each; `pred_faces` stays what sample 0 (pred) gives."""
+    ranked by their best score, with the number of draws that produced each; `pred_faces` stays what sample 0 (pred) gives.
+    dead_end (--constrain; the dead-end flags [F] of this sample): the record also gets `pred_dead_ends`, the number of the
+    wireframe's own anchor rows the constrained decode ended at a dead end, and `pred_unclosed`, the number of own anchor rows
+    whose face does not pass the enclosure walk (dead ends, and loops still open at the last position)."""
     scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
@@ -134,6 +144,12 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["label_logprob"] = [float(v) for v, n in zip(ls["seq_logprob"].reshape(-1), ls["lengths"].reshape(-1)) if n > 0]
         rec["label_nll"] = float(sm["nll"][0]) if sm["tokens"][0] else None
         rec["label_tf_accuracy"] = float(sm["tf_accuracy"][0]) if sm["tokens"][0] else None
+    if dead_end is not None:
+        n = int(item["num_input"])
+        own = [f for i in range(len(pred)) for f in FZ._parallel_rows(pred[i:i + 1], cfg.model.token, len(raw["edges"]))]
+        rec["pred_dead_ends"] = int(np.asarray(dead_end[:n]).astype(bool).sum())
+        rec["pred_unclosed"] = sum(1 for _, idx in own
+                                   if not FZ.is_face_enclosed(raw["edges"], idx, cfg.post_process.enclosedness_tol))
     if samples is not None:
         n = int(item["num_input"])
         sf = FZ.parse_parallel_samples_scored(samples[0][:n], samples[1][:n], len(raw["edges"]), cfg.model.token)
@@ -145,11 +161,12 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
 
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
-                    seed=0):
+                    seed=0, constrain=None, constrain_tol=None):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
-    under temperature / top_k / top_p from the seeded generator (num_samples).  Without them the model keeps its
+    under temperature / top_k / top_p from the seeded generator (num_samples), the loop-constrained greedy decode
+    (constrain "no_repeat" / "loops" with the end-point tolerance constrain_tol).  Without them the model keeps its
     defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -163,12 +180,16 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.num_samples = int(sample)
         model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
         model.sample_seed = int(seed)
+    if constrain:
+        model.constrain = str(constrain)
+        if constrain_tol is not None:
+            model.constrain_tol = float(constrain_tol)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
-             top_p=1.0, seed=0):
+             top_p=1.0, seed=0, constrain=None):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -181,7 +202,17 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     the sample's own label rows (models' score()); single process, not with retire_finished / scores / beam.
     sample: this many draws per anchor under temperature / top_k / top_p, uniforms from a generator seeded with `seed` (parallel
     model, single process, not with retire_finished / scores / beam / score_labels): every record gains `pred_sample_faces` /
-    `pred_sample_face_scores` / `pred_sample_face_votes`."""
+    `pred_sample_face_scores` / `pred_sample_face_votes`.
+    constrain: "no_repeat" or "loops", the loop-constrained greedy decode with cfg.post_process.enclosedness_tol as the end-point
+    tolerance (parallel model, single process, not with retire_finished / scores / beam / sample / score_labels): every record
+    gains `pred_dead_ends` / `pred_unclosed`."""
+    if constrain and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores or beam or sample or score_labels):
+        raise ValueError("--constrain applies to SurfaceFormer_Parallel only, and not together with --retire-finished, --scores, "
+                         "--beam, --sample or --score-labels")
+    if constrain and constrain not in ("no_repeat", "loops"):
+        raise ValueError("--constrain must be 'no_repeat' or 'loops'")
+    if constrain and dist_mod is not None and dist_mod.get_world_size() > 1:
+        raise ValueError("--constrain is not implemented for multi-rank runs")
     if sample and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores or beam or score_labels):
         raise ValueError("--sample applies to SurfaceFormer_Parallel only, and not together with --retire-finished, --scores, "
                          "--beam or --score-labels")
@@ -207,7 +238,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         sd, _ = load_lightning_checkpoint(ckpt_path)
         model.load_state_dict(sd)
         model = model.eval().to(device)
-    configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed)
+    configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
+                    cfg.post_process.enclosedness_tol if constrain else None)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -228,8 +260,11 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         if torch.cuda.is_available() and str(device).startswith("cuda"):
             torch.cuda.synchronize()
         t0 = time.time()
-        bms = sms = None
-        if sample:
+        bms = sms = dds = None
+        if constrain:
+            pred, dds = decode_batch_constrained(model, batch)
+            lps = None
+        elif sample:
             pred, stk, ssc = decode_batch_samples(model, batch)
             lps, sms = None, list(zip(stk, ssc))
         elif beam:
@@ -243,7 +278,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         for k, i in enumerate(idx):
             text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel, lps[k] if scores else None,
                                  bms[k] if beam else None, {n: v[k] for n, v in lsc.items()} if score_labels else None,
-                                 sms[k] if sample else None)
+                                 sms[k] if sample else None, dds[k] if constrain else None)
             stats.append(st)
             records.append((os.path.splitext(os.path.basename(items[k]["name"]))[0], text))
         print("Avg Time", total / done, "seconds.")
@@ -303,6 +338,12 @@ def build_parser():
     parser.add_argument("--seed", type=int, default=0, help="--sample: seed of the generator that makes the uniforms.  The generator is seeded anew for every "
                                                                  "model(batch) call and a draw belongs to the wireframe's place in its batch, so wireframes at the "
                                                                  "same place of different batches (with --batch-size 1: all of them) read the same uniform stream")
+    parser.add_argument("--constrain", choices=("no_repeat", "loops"), default=None,
+                        help="parallel model: the greedy decode over the keys the enclosure filter can accept (DESIGN.md 16) -- "
+                             "no_repeat: never an edge the row holds already; loops: also only an edge that starts where the last "
+                             "one ended while a loop is open, and no face-type token before the loop is closed; every JSON record "
+                             "gains pred_dead_ends / pred_unclosed; single-process runs only, not with --retire-finished, --scores, "
+                             "--beam, --sample or --score-labels")
     return parser
 
 
@@ -323,7 +364,7 @@ def main(argv=None):
     run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
              retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam,
              score_labels=args.score_labels, sample=args.sample, temperature=args.temperature, top_k=args.top_k,
-             top_p=args.top_p, seed=args.seed)
+             top_p=args.top_p, seed=args.seed, constrain=args.constrain)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
