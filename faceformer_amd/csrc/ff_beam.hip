@@ -49,10 +49,9 @@ __device__ __forceinline__ void beam_insert(float (&lsc)[W], int (&lix)[W], floa
 
 template <int W>
 __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
-  __shared__ int s_cnt[4];
   const PointerArgs& pa = a.p;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int g = blockIdx.x * 4 + wv;
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
   const float FILL = -FLT_MAX;
   int nge = 0;
   if (g < a.groups) {
@@ -129,23 +128,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
       for (int k = 0; k < W; ++k) ff_pointer_append_row(pa, (b0 + k) / pa.spg, b0 + k, __shfl(tk, k, FF_WAVE), lane);
     }
   }
-  if (!pa.count_ge) return;   // (launch-uniform)
-  if (lane == 0) s_cnt[wv] = nge;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    // one atomic per block; the launch's last block publishes the total to the host-mapped twin (as ff_pointer_count_block)
-    const int nvalid = a.groups - blockIdx.x * 4 < 4 ? a.groups - blockIdx.x * 4 : 4;
-    int n = 0;
-    for (int i = 0; i < nvalid; ++i) n += s_cnt[i];
-    if (n) atomicAdd(pa.count_ge, n);
-    if (pa.arrive) {
-      const int prev = __hip_atomic_fetch_add(pa.arrive, nvalid, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev + nvalid == a.groups) {
-        const int v = __hip_atomic_load(pa.count_ge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pa.host_slot, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
+  ff_pointer_count_waves(pa, a.groups, nge);
 }
 
 // rows_a [npos, rows_per_pos, wa] and (optional) rows_b [npos, rows_per_pos, wb]; row (j, g * W + k) <- row (j, g * W + parent[k]).
@@ -189,11 +172,11 @@ __global__ void beam_init_kernel(int* tok, float* score, int* fin, int* parent, 
                                  const int* num_input, int pad_tok, int term_lo, int term_hi) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= Bc) return;
-  const int k = i % W, a = i / W, f = f0 + a % Fc;
-  const int t = f < num_input[a / Fc] ? f : pad_tok;
-  tok[i] = t;
+  const int k = i % W, a = i / W;
+  int done;
+  tok[i] = ff_start_token(f0 + a % Fc, num_input[a / Fc], pad_tok, term_lo, term_hi, &done);
   score[i] = k == 0 ? 0.f : -INFINITY;
-  fin[i] = (t >= term_lo && t < term_hi) ? 1 : 0;
+  fin[i] = done;
   parent[i] = k;
 }
 
@@ -209,10 +192,9 @@ __global__ void beam_finalize_kernel(const int* __restrict__ tok, const int* __r
   const int total = nw * F * W;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int k = i % W, fo = (i / W) % F, wl = i / (W * F);
-    int f = fo;
-    if (dedup) { const int n = num_input[w0 + wl]; f = fo < n ? fo : n; }
-    if (f < f0 || f >= f0 + Fc) continue;
-    const int grp = b0 + (wl * Fc + (f - f0)) * W;
+    int a;
+    if (!ff_compact_seq(num_input, dedup, w0, wl, fo, Fc, f0, &a)) continue;
+    const int grp = b0 + a * W;
     const size_t row = ((size_t)(w0 + wl) * F + fo) * W + k;
     int64_t* out = beams + row * T;
     int64_t* pred = k == 0 ? predict + ((size_t)(w0 + wl) * F + fo) * T : nullptr;
@@ -246,16 +228,12 @@ int ff_beam_select_sync(float* logits, int ldlogits, int S, const unsigned char*
   FF_RETURN_IF(check_select(groups, width, S, groups_per_wireframe, logits, ldlogits));
   FF_CHECK_ARG(scores_in && scores_out && fin_in && fin_out && parent && next_tok, "ff_beam_select: null pointer");
   FF_CHECK_ARG(!hist || (t >= 1 && ldhist >= groups * width), "ff_beam_select: history needs t >= 1 and ldhist >= groups * width");
-  FF_CHECK_ARG(!next_rows || (memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ff_aligned16(memory) && ff_aligned16(next_rows)),
-               "ff_beam_select: next_rows needs memory, E %% 4 == 0 and 16-byte alignment");
-  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "ff_beam_select: next_stats needs next_rows and E %% 32 == 0");
-  FF_CHECK_ARG(!arrive || (host_slot && count_ge), "ff_beam_select: counter hand-over without a counter");
   BeamArgs a;
   memset(&a, 0, sizeof(a));
-  a.p.memory = memory; a.p.S = S; a.p.E = E; a.p.mask = mask; a.p.kv_len = kv_len;
+  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_beam_select", false, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
+  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
   a.p.B = groups * width; a.p.spg = groups_per_wireframe * width;
-  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.next_rows = next_rows; a.p.ldnext = ldnext;
-  a.p.count_ge = count_ge; a.p.ge_bound = ge_bound; a.p.arrive = arrive; a.p.host_slot = host_slot; a.p.next_stats = next_stats;
+  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.ge_bound = ge_bound;
   a.p.term_lo = term_lo; a.p.term_hi = term_hi;
   a.groups = groups; a.score_in = scores_in; a.score_out = scores_out; a.fin_in = fin_in; a.fin_out = fin_out;
   a.hist = hist; a.ldhist = ldhist; a.t = t; a.parent = parent; a.tok = next_tok;

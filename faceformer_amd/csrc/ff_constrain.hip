@@ -22,6 +22,7 @@
 
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 namespace {
 
@@ -64,10 +65,9 @@ __global__ __launch_bounds__(256) void follow_table_kernel(const float* __restri
 }
 
 __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs a) {
-  __shared__ int s_cnt[4];
   const PointerArgs& pa = a.p;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.x * 4 + wv;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   int nge = 0;
   if (b < pa.B) {   // (wave-uniform)
     const int S = pa.S, ntok = a.ntok;
@@ -132,23 +132,7 @@ __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs 
     }
     if (pa.next_rows) ff_pointer_append_row(pa, b / pa.spg, b, tok, lane);
   }
-  if (!pa.count_ge) return;   // (launch-uniform)
-  if (lane == 0) s_cnt[wv] = nge;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    // one atomic per block; the launch's last block publishes the total to the host-mapped twin (as ff_pointer_count_block)
-    const int nvalid = pa.B - blockIdx.x * 4 < 4 ? pa.B - blockIdx.x * 4 : 4;
-    int n = 0;
-    for (int i = 0; i < nvalid; ++i) n += s_cnt[i];
-    if (n) atomicAdd(pa.count_ge, n);
-    if (pa.arrive) {
-      const int prev = __hip_atomic_fetch_add(pa.arrive, nvalid, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev + nvalid == pa.B) {
-        const int v = __hip_atomic_load(pa.count_ge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pa.host_slot, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
+  ff_pointer_count_waves(pa, pa.B, nge);
 }
 
 // ---- engine side: start state and output packing of a constrained decode (ff_engine.hip) -----------------------------------------
@@ -162,10 +146,11 @@ __global__ void constrain_init_kernel(int* tok, float* lp, int* fin, int* dead, 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= Bc) return;
   const int wl = i / Fc, f = f0 + i % Fc;
-  const int t = f < num_input[wl] ? f : pad_tok;
+  int done;
+  const int t = ff_start_token(f, num_input[wl], pad_tok, term_lo, term_hi, &done);
   tok[i] = t;
   lp[i] = 0.f;
-  fin[i] = (t >= term_lo && t < term_hi) ? 1 : 0;
+  fin[i] = done;
   dead[i] = 0;
   unsigned* v = visited + (size_t)i * fw;
   for (int k = 0; k < fw; ++k) v[k] = 0u;
@@ -193,10 +178,9 @@ __global__ void constrain_finalize_kernel(const int* __restrict__ tok, const flo
   const int total = nw * F;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int fo = i % F, wl = i / F;
-    int f = fo;
-    if (dedup) { const int n = num_input[w0 + wl]; f = fo < n ? fo : n; }
-    if (f < f0 || f >= f0 + Fc) continue;
-    const int seq = b0 + wl * Fc + (f - f0);
+    int a;
+    if (!ff_compact_seq(num_input, dedup, w0, wl, fo, Fc, f0, &a)) continue;
+    const int seq = b0 + a;
     const size_t row = (size_t)(w0 + wl) * F + fo;
     int64_t* out = predict + row * T;
     float* olp = logprob + row * T;
@@ -244,17 +228,13 @@ int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsign
   FF_CHECK_ARG(follows || !(flags & FF_CONSTRAIN_CONNECT), "ff_pointer_constrained: FF_CONSTRAIN_CONNECT needs the follow table");
   FF_CHECK_ARG(fin_in && first_in && prev_in && visited && mask_rows && next_tok && logprob && fin_out && dead_end && first_out && prev_out,
                "ff_pointer_constrained: null pointer");
-  FF_CHECK_ARG(!next_rows || (memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ldnext >= E && ff_aligned16(memory) && ff_aligned16(next_rows)),
-               "ff_pointer_constrained: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment");
-  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "ff_pointer_constrained: next_stats needs next_rows and E %% 32 == 0");
-  FF_CHECK_ARG(!arrive || (host_slot && count_ge), "ff_pointer_constrained: counter hand-over without a counter");
   ConstrainArgs a;
   memset(&a, 0, sizeof(a));
-  a.p.memory = memory; a.p.S = S; a.p.E = E; a.p.mask = mask; a.p.kv_len = kv_len;
+  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_pointer_constrained", true, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
+  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
   a.p.extra = mask_rows; a.p.ldextra = S;
   a.p.B = B; a.p.spg = seqs_per_group;
-  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.next_rows = next_rows; a.p.ldnext = ldnext; a.p.next_stats = next_stats;
-  a.p.count_ge = count_ge; a.p.ge_bound = ntok; a.p.arrive = arrive; a.p.host_slot = host_slot;
+  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.ge_bound = ntok;
   a.p.term_lo = term_lo; a.p.term_hi = term_hi;
   a.rows = mask_rows; a.follows = follows; a.L = L; a.fw = (L + 31) >> 5; a.flags = flags; a.ntok = ntok;
   a.fin_in = fin_in; a.first_in = first_in; a.prev_in = prev_in; a.visited = visited;

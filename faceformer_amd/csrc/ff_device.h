@@ -725,6 +725,50 @@ __device__ __forceinline__ void ff_pointer_count_block(const PointerArgs& a, int
   }
 }
 
+// The same hand-over for the launches whose waves count for themselves (beam, sampled and constrained selection): every thread
+// of a 256-thread block calls it, wave i with the count `nge` of unit blockIdx.x * 4 + i (a sequence, or the beams of a group);
+// `units` of them exist in the launch, and the arrivals count units.
+__device__ __forceinline__ void ff_pointer_count_waves(const PointerArgs& a, int units, int nge) {
+  __shared__ int s_cnt[4];
+  if (!a.count_ge) return;   // (launch-uniform)
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = nge;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int nvalid = units - blockIdx.x * 4 < 4 ? units - blockIdx.x * 4 : 4;
+    int n = 0;
+    for (int i = 0; i < nvalid; ++i) n += s_cnt[i];
+    if (n) atomicAdd(a.count_ge, n);
+    if (a.arrive) {
+      const int prev = __hip_atomic_fetch_add(a.arrive, nvalid, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      if (prev + nvalid == units) {
+        const int v = __hip_atomic_load(a.count_ge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.host_slot, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+  }
+}
+
+// ---- decode engine: the two index rules every mode's start-state and packing kernels share --------------------------------------
+// Start token of compact anchor f of a wireframe with n edges: anchors = arange(F) per wireframe, WITHOUT the +num_token offset
+// (reference quirk C-3, model_para.py:201); anchors >= n start from pad_tok = num_token - 1 (model_para.py:204-205).
+// *fin (optional): the token lies in the terminator range, so the sequence is finished at position 0.
+__device__ __forceinline__ int ff_start_token(int f, int n, int pad_tok, int term_lo = 0, int term_hi = 0, int* fin = nullptr) {
+  const int t = f < n ? f : pad_tok;
+  if (fin) *fin = (t >= term_lo && t < term_hi) ? 1 : 0;
+  return t;
+}
+// Output row fo of the wl-th wireframe (w0 + wl of the batch) of a micro-batch that holds the compact sequences [f0, f0 + Fc) of
+// its wireframes: *k = the chunk-local index wl * Fc + (f - f0) of the compact sequence that stands for the row; false when that
+// sequence lives in another micro-batch.  With padding-anchor de-duplication every row fo >= num_input[w] is the ONE
+// padding-anchor sequence stored at compact index num_input[w].
+__device__ __forceinline__ bool ff_compact_seq(const int* __restrict__ num_input, int dedup, int w0, int wl, int fo, int Fc, int f0,
+                                               int* k) {
+  int f = fo;
+  if (dedup) { const int n = num_input[w0 + wl]; f = fo < n ? fo : n; }
+  *k = wl * Fc + (f - f0);
+  return f >= f0 && f < f0 + Fc;
+}
+
 // (max, sum of exp(x - max)) of two disjoint key sets -> of their union; returns the sum, *mout the maximum
 __device__ __forceinline__ float ff_lse_merge(float m, float s, float om, float os, float* mout) {
   const float d = om - m;                 // (both maxima are finite: -FLT_MAX at the least)

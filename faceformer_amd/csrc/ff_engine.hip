@@ -19,30 +19,29 @@
 // order) -- and every sync_every steps the host drops the finished sequences from it (compact_chunks below).  The slots of a
 // chunk keep the w = i / Fc structure with a smaller Fc, so attention, masks and kv_len are addressed as before.
 //
-// Beam decode (ff_decode_beam, opt-in, parallel variant): the same run with W sequences per anchor -- beam k of
-// compact anchor a is chunk-local sequence a * W + k, so a chunk's Fc / Bc are W times its anchor counts and w = i / Fc holds.
-// A step's pointer launch is replaced by ff_beam_select (+ ff_beam_reorder of the x0 / qkv0 prefixes); every step leaves its
-// (token, parent, score, finished) row in the workspace and the output is packed from those rows behind the stop step.
-//
-// Forced decode (ff_decode_forced, opt-in, both variants): the same run fed a given path -- the token array holds
-// the caller's paths from the start, a step's pointer launch is replaced by ff_pointer_forced (which appends the FORCED token's
-// row), every micro-batch runs max(lengths of its rows) steps, and there is no stop rule: no counters, no check points.
-//
-// Sampled decode (ff_decode_sample, opt-in, parallel variant): R sequences per anchor in the beam decode's layout
-// (plan_beam_chunks), independent of each other -- no reorder.  A step's pointer launch is replaced by ff_pointer_sample, which
-// reads the caller's uniforms through a per-sequence row_id; every step leaves its (token, log-probability, finished) row in
-// the workspace and the output is packed from the rows up to the stop step.
-//
-// Constrained decode (ff_decode_constrained, opt-in, parallel variant): the default decode's plan (plan_chunks), one
-// sequence per anchor.  A step's pointer launch is replaced by ff_pointer_constrained, which masks the keys the enclosure walk
-// could not accept; per-step records and the rule's state (first, prev per step; visited words and the byte mask per sequence)
-// live last in the workspace, and the output is packed as the sampled decode's.
+// The opt-in decodes are the same run with another selection in place of the greedy pointer launch: a Mode (below) names the
+// kind, its sequences per anchor and its parameters; every kind is one case of the switches in layout_decode, init_state, select_step
+// and pack, behind one plan (plan_mode), one size query (decode_workspace_bytes) and one step head (step_head).  Their per-step
+// records lie last in the workspace, and the output is packed from the records up to the stop step.
+//   beam (ff_decode_beam): W sequences per anchor -- beam k of compact anchor a is chunk-local sequence a * W + k,
+//     so a chunk's Fc / Bc are W times its anchor counts and w = i / Fc holds.  ff_beam_select (+ ff_beam_reorder of the x0 /
+//     qkv0 prefixes); records (token, parent, score, finished).
+//   forced (ff_decode_forced, both variants): the token array holds the caller's paths from the start,
+//     ff_pointer_forced appends the FORCED token's row, every micro-batch runs max(lengths of its rows) steps, and there is no
+//     stop rule: no counters, no check points, a loop and an epilogue of its own.
+//   sample (ff_decode_sample): R sequences per anchor in the beam decode's layout, independent of each other -- no
+//     reorder.  ff_pointer_sample reads the caller's uniforms through a per-sequence row_id; records (token, log-probability,
+//     finished).
+//   constrain (ff_decode_constrained): the default plan, one sequence per anchor.  ff_pointer_constrained masks
+//     the keys the enclosure walk could not accept; records and the rule's state (first, prev per step; visited words and the
+//     byte mask per sequence).
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
 #include <vector>
 
 #include "ff_common.h"
+#include "ff_device.h"
 #include "ff_launch.h"
 
 namespace {
@@ -72,18 +71,11 @@ __global__ void init_tokens_kernel(int* tok, int Bc, int Fc, int f0, const int* 
                                    int pad_tok, int sos, const int* slot = nullptr, int* tok_slot = nullptr, int nslots = 0) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot && i < nslots) {
-    const int k = slot[i], f = f0 + k % Fc;
-    tok_slot[i] = f < num_input[k / Fc] ? f : pad_tok;
+    const int k = slot[i];
+    tok_slot[i] = ff_start_token(f0 + k % Fc, num_input[k / Fc], pad_tok);
   }
   if (i >= Bc) return;
-  if (variant == FF_PARALLEL) {
-    // anchors = arange(F) per wireframe, WITHOUT the +num_token offset (reference quirk C-3,
-    // model_para.py:201); rows >= num_input[w] start from token num_token-1 (model_para.py:204-205)
-    const int f = f0 + i % Fc;
-    tok[i] = f < num_input[i / Fc] ? f : pad_tok;
-  } else {
-    tok[i] = sos;
-  }
+  tok[i] = variant == FF_PARALLEL ? ff_start_token(f0 + i % Fc, num_input[i / Fc], pad_tok) : sos;
 }
 
 // steps_done from the per-step counters (the reference's stop rules, model_para.py:232 / model.py:207-210)
@@ -122,10 +114,9 @@ __global__ void finalize_chunk_kernel(const int* __restrict__ tok_all, int Btot,
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int j = (int)(i % T);
     const int fo = (int)((i / T) % F), wl = (int)(i / ((size_t)T * F));
-    int f = fo;
-    if (dedup) { const int n = num_input[w0 + wl]; f = fo < n ? fo : n; }
-    if (f < f0 || f >= f0 + Fc) continue;
-    const int seq = b0 + wl * Fc + (f - f0);
+    int k;
+    if (!ff_compact_seq(num_input, dedup, w0, wl, fo, Fc, f0, &k)) continue;
+    const int seq = b0 + k;
     const size_t row = (size_t)(w0 + wl) * F + fo;
     const int last = fin ? (fin[seq] < steps ? fin[seq] : steps) : steps;   // FF_RETIRE_FINISHED: up to the finish position
     predict[row * T + j] = (j <= last) ? (int64_t)tok_all[(size_t)j * Btot + seq] : (int64_t)0;
@@ -352,6 +343,35 @@ int plan_streams(const ff_decode_params* p) {
   return p->num_streams < 1 ? 1 : (p->num_streams > FF_MAX_STREAMS ? FF_MAX_STREAMS : p->num_streams);
 }
 
+// What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
+// 1) and that kind's parameters (null in a size query, which needs the kind and G only).
+struct Mode {
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN } kind;
+  int G;
+  const void* prm;
+  Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
+  const ff_beam_params* beam() const { return static_cast<const ff_beam_params*>(prm); }          // (each for its own kind only)
+  const ff_forced_params* forced() const { return static_cast<const ff_forced_params*>(prm); }
+  const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }
+  const ff_constrain_params* con() const { return static_cast<const ff_constrain_params*>(prm); }
+};
+
+// The micro-batch plan of a mode: the default plan for greedy and constrain; without de-duplication for forced (the rows are
+// arbitrary paths: sequence b of the plan is row b); over the anchors, G times as wide, for beam and sample.
+void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, const Mode& mode, std::vector<Chunk>* out, int* btot,
+               int* max_bc, int* nchunks = nullptr) {
+  switch (mode.kind) {
+    case Mode::BEAM:
+    case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
+    case Mode::FORCED: {
+      ff_decode_params q = *p;
+      q.flags &= ~FF_DEDUP_PAD_ANCHORS;
+      return plan_chunks(&q, nullptr, ns, out, btot, max_bc, nchunks);
+    }
+    default: return plan_chunks(p, num_input_host, ns, out, btot, max_bc, nchunks);
+  }
+}
+
 // The tuning knobs that shape a decode, read ONCE per ff_decode / ff_decode_workspace_bytes call: the workspace
 // layout and every step of that call see the same values whatever ff_set_tuning() does meanwhile.  The two that change the
 // LAYOUT can also be switched off per call through ff_decode_params.flags (FF_NO_L0_FOLD, FF_NO_POINTER_FOLD).
@@ -387,11 +407,10 @@ bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
 
 // Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
 // want_lp: also the log-probability rows (ff_decode_lp) -- taken LAST, so that everything else lies where it lies without them.
-// beam: also the per-step records of a beam decode (ff_decode_beam), last as well.  forced: those of a forced decode, likewise.
-// sample: those of a sampled decode and its row_id array, likewise.  constrain: those of a constrained decode and its state, likewise.
+// mode: also the per-step records of a beam, forced, sampled (with its row_id array) or constrained (with its state) decode,
+// last as well.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
-                     Bump& bp, DecodeBuffers* out, bool want_lp = false, bool beam = false, bool forced = false, bool sample = false,
-                     bool constrain = false) {
+                     Bump& bp, DecodeBuffers* out, const Mode& mode, bool want_lp = false) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
   const int ns = plan_streams(p);
   const size_t Rmax = (size_t)(T - 1 > 0 ? T - 1 : 1) * Bch;
@@ -441,34 +460,49 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     b.perm_all = bp.take<int>(Btot);
   }
   if (want_lp) b.lp_all = bp.take<float>((size_t)(T - 1 > 0 ? T - 1 : 1) * Btot);
-  if (beam) {
-    b.bm_score = bp.take<float>((size_t)T * Btot);
-    b.bm_fin = bp.take<int>((size_t)T * Btot);
-    b.bm_parent = bp.take<int>((size_t)T * Btot);
-  }
-  if (forced) {
-    const size_t n = (size_t)(T - 1 > 0 ? T - 1 : 1) * Btot;
-    b.fc_lp = bp.take<float>(n);
-    b.fc_greedy = bp.take<int>(n);
-    b.fc_rank = bp.take<int>(n);
-  }
-  if (sample) {
-    b.sm_lp = bp.take<float>((size_t)T * Btot);
-    b.sm_fin = bp.take<int>((size_t)T * Btot);
-    b.sm_row = bp.take<int>(Btot);
-  }
-  if (constrain) {
-    b.cn_lp = bp.take<float>((size_t)T * Btot);
-    b.cn_fin = bp.take<int>((size_t)T * Btot);
-    b.cn_dead = bp.take<int>((size_t)T * Btot);
-    b.cn_first = bp.take<int>((size_t)T * Btot);
-    b.cn_prev = bp.take<int>((size_t)T * Btot);
-    const size_t fw = (size_t)(p->L + 31) / 32;   // visited words per sequence; one word at L = 0, so that the array is never empty
-    b.cn_visited = bp.take<unsigned>(Btot * (fw > 0 ? fw : 1));
-    b.cn_rows = bp.take<unsigned char>(Btot * (size_t)S);
+  switch (mode.kind) {
+    case Mode::BEAM:
+      b.bm_score = bp.take<float>((size_t)T * Btot);
+      b.bm_fin = bp.take<int>((size_t)T * Btot);
+      b.bm_parent = bp.take<int>((size_t)T * Btot);
+      break;
+    case Mode::FORCED: {
+      const size_t n = (size_t)(T - 1 > 0 ? T - 1 : 1) * Btot;
+      b.fc_lp = bp.take<float>(n);
+      b.fc_greedy = bp.take<int>(n);
+      b.fc_rank = bp.take<int>(n);
+      break;
+    }
+    case Mode::SAMPLE:
+      b.sm_lp = bp.take<float>((size_t)T * Btot);
+      b.sm_fin = bp.take<int>((size_t)T * Btot);
+      b.sm_row = bp.take<int>(Btot);
+      break;
+    case Mode::CONSTRAIN: {
+      b.cn_lp = bp.take<float>((size_t)T * Btot);
+      b.cn_fin = bp.take<int>((size_t)T * Btot);
+      b.cn_dead = bp.take<int>((size_t)T * Btot);
+      b.cn_first = bp.take<int>((size_t)T * Btot);
+      b.cn_prev = bp.take<int>((size_t)T * Btot);
+      const size_t fw = (size_t)(p->L + 31) / 32;   // visited words per sequence; one word at L = 0, so that the array is never empty
+      b.cn_visited = bp.take<unsigned>(Btot * (fw > 0 ? fw : 1));
+      b.cn_rows = bp.take<unsigned char>(Btot * (size_t)S);
+      break;
+    }
+    default: break;
   }
   if (out) *out = b;
   return bp.off;
+}
+
+// Workspace bytes of a decode in `mode` (every ff_decode*_workspace_bytes entry, behind its own argument check).
+size_t decode_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host, const Mode& mode,
+                              bool want_lp = false) {
+  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
+  int btot = 0, max_bc = 0, nch = 0;
+  plan_mode(p, num_input_host, 1, mode, nullptr, &btot, &max_bc, &nch);
+  Bump bp(nullptr, 0);
+  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, mode, want_lp) + 256;
 }
 
 // Does a decode step with R active rows take the LayerNorm-folded projections?  (decoder_pass and the engine loop ask.)
@@ -753,16 +787,12 @@ struct DecodeRun {
   std::vector<std::vector<int>> hslot;        // per chunk: the chunk-local sequence of every slot
   int* fin_host = nullptr;                    // host address of the finish positions when they are host-mapped, else null
   int* fin_dev = nullptr;
-  const ff_beam_params* beam = nullptr;       // ff_decode_beam (null: the greedy decode)
-  int W = 0;                                  // ... its width; 0 without beams
-  const ff_forced_params* forced = nullptr;   // ff_decode_forced (null otherwise)
-  std::vector<int> chunk_steps;               // ... steps every micro-batch runs: the largest length among its rows
+  Mode mode;                                  // greedy (ff_decode / ff_decode_lp) or the opt-in decode of the entry
+  std::vector<int> chunk_steps;               // forced: steps every micro-batch runs: the largest length among its rows
   int forced_steps = 0;                       // ... and the largest of those
-  const ff_sample_params* sample = nullptr;   // ff_decode_sample (null otherwise)
-  int R = 0;                                  // ... its samples per anchor; 0 without sampling
-  const ff_constrain_params* con = nullptr;   // ff_decode_constrained (null otherwise)
   int validate(const ff_model* m_, const ff_decode_params* p_, const DecodeIO& io_, const void* workspace) {
     m = m_; io = io_;
+    const bool forced = mode.kind == Mode::FORCED;
     FF_RETURN_IF(check_model(m));
     FF_CHECK_ARG(p_ != nullptr, "ff_decode: null params");
     FF_CHECK_ARG(p_->variant == FF_PARALLEL || p_->variant == FF_SEQ2SEQ, "ff_decode: bad variant");
@@ -802,12 +832,10 @@ struct DecodeRun {
   int bind_chunks(void* workspace, size_t workspace_bytes) {
     const int ns_req = plan_streams(p);
     int max_bc = 0;
-    if (W || R) plan_beam_chunks(p, io.num_input_host, ns_req, W ? W : R, &chunks, &Btot, &max_bc);
-    else plan_chunks(p, io.num_input_host, ns_req, &chunks, &Btot, &max_bc);
+    plan_mode(p, io.num_input_host, ns_req, mode, &chunks, &Btot, &max_bc);
     nch = (int)chunks.size();
     Bump bp(workspace, workspace_bytes);
-    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, io.logprob != nullptr, W > 0, forced != nullptr,
-                  R > 0, con != nullptr);
+    layout_decode(m, p, kn, (size_t)Btot, (size_t)max_bc, (size_t)nch, bp, &buf, mode, io.logprob != nullptr);
     if (!bp.ok) { ff_set_error("ff_decode: workspace too small (%zu needed, %zu given)", bp.off, workspace_bytes); return FF_ERR_WORKSPACE; }
     for (Chunk& c : chunks) {
       c.x0 = buf.x0_all + (size_t)T * c.b0 * E;
@@ -825,10 +853,10 @@ struct DecodeRun {
     fin_dev = buf.fin;
     slots_per_step.reserve((size_t)T);   // (the loop below allocates nothing per step)
     tot.reserve((size_t)T);
-    if (forced) {   // (the plan has no de-duplication: sequence b0 + i of a chunk is row b0 + i of the paths)
+    if (mode.kind == Mode::FORCED) {   // (the plan has no de-duplication: sequence b0 + i of a chunk is row b0 + i of the paths)
       for (const Chunk& c : chunks) {
         int mx = 0;
-        for (int i = 0; i < c.Bc; ++i) mx = forced->lengths_host[c.b0 + i] > mx ? forced->lengths_host[c.b0 + i] : mx;
+        for (int i = 0; i < c.Bc; ++i) mx = mode.forced()->lengths_host[c.b0 + i] > mx ? mode.forced()->lengths_host[c.b0 + i] : mx;
         chunk_steps.push_back(mx);
         forced_steps = mx > forced_steps ? mx : forced_steps;
       }
@@ -947,28 +975,8 @@ struct DecodeRun {
     }
     // start tokens (anchors / SOS) and first decoder input rows of every micro-batch
     for (const Chunk& c : chunks) {
-      if (forced) {   // (the start tokens are row 0 of the token array: forced_tokens() put the paths there)
-        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
-        continue;
-      }
-      if (W) {
-        FF_RETURN_IF(ff_beam_init(buf.tok_all + c.b0, buf.bm_score + c.b0, buf.bm_fin + c.b0, buf.bm_parent + c.b0, c.Bc, c.Fc / W, W,
-                                  c.f0, io.num_input + c.w0, m->num_token - 1, p->term_lo, p->term_hi, sts[c.sid]));
-        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
-        continue;
-      }
-      if (R) {
-        FF_RETURN_IF(ff_sample_init(buf.tok_all + c.b0, buf.sm_lp + c.b0, buf.sm_fin + c.b0, buf.sm_row + c.b0, c.Bc, c.Fc / R, R, c.f0,
-                                    c.w0, F, io.num_input + c.w0, m->num_token - 1, p->term_lo, p->term_hi, sts[c.sid]));
-        FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
-        continue;
-      }
-      if (con) {
-        const int fw = (p->L + 31) / 32;
-        FF_RETURN_IF(ff_constrain_init(buf.tok_all + c.b0, buf.cn_lp + c.b0, buf.cn_fin + c.b0, buf.cn_dead + c.b0, buf.cn_first + c.b0,
-                                       buf.cn_prev + c.b0, buf.cn_visited + (size_t)c.b0 * fw, c.Bc, c.Fc, c.f0, io.num_input + c.w0,
-                                       m->num_token - 1, p->term_lo, p->term_hi, m->num_token,
-                                       con->follows ? con->follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, sts[c.sid]));
+      if (mode.kind != Mode::GREEDY) {
+        FF_RETURN_IF(init_state(c));
         FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
         continue;
       }
@@ -983,6 +991,28 @@ struct DecodeRun {
     }
     return FF_OK;
   }
+  // Row 0 of the mode's per-step records and of the token array for one micro-batch: the start state of its sequences.
+  int init_state(const Chunk& c) {
+    const int G = mode.G, pad_tok = m->num_token - 1;
+    const int* ni = io.num_input ? io.num_input + c.w0 : nullptr;
+    hipStream_t st = sts[c.sid];
+    switch (mode.kind) {
+      case Mode::BEAM:
+        return ff_beam_init(buf.tok_all + c.b0, buf.bm_score + c.b0, buf.bm_fin + c.b0, buf.bm_parent + c.b0, c.Bc, c.Fc / G, G, c.f0, ni,
+                            pad_tok, p->term_lo, p->term_hi, st);
+      case Mode::SAMPLE:
+        return ff_sample_init(buf.tok_all + c.b0, buf.sm_lp + c.b0, buf.sm_fin + c.b0, buf.sm_row + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F,
+                              ni, pad_tok, p->term_lo, p->term_hi, st);
+      case Mode::CONSTRAIN: {
+        const int fw = (p->L + 31) / 32;
+        const unsigned* follows = mode.con()->follows;
+        return ff_constrain_init(buf.tok_all + c.b0, buf.cn_lp + c.b0, buf.cn_fin + c.b0, buf.cn_dead + c.b0, buf.cn_first + c.b0,
+                                 buf.cn_prev + c.b0, buf.cn_visited + (size_t)c.b0 * fw, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo,
+                                 p->term_hi, m->num_token, follows ? follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, st);
+      }
+      default: return FF_OK;   // (forced: the start tokens are row 0 of the token array, forced_tokens() put the paths there)
+    }
+  }
   // Decode step `step` (position t = step + 1) of every micro-batch that has slots left, on the chunk's stream: the slot set
   // decoded now is Fl / Bl wide (the chunk's Fc / Bc without retirement).
   int enqueue_step(int step) {
@@ -993,111 +1023,97 @@ struct DecodeRun {
       nslots += c.Bl;
       hipStream_t st = sts[c.sid];
       const Scratch& sc = buf.scr[c.sid];
-      const size_t trow = (size_t)step * ((size_t)N * F * (W ? W : (R ? R : 1))) + c.b0;  // traces: step stride N*F (N*F*W with beams, N*F*R with samples; caller sizes them so)
+      const size_t trow = (size_t)step * ((size_t)N * F * mode.G) + c.b0;  // traces: step stride N*F (N*F*W with beams, N*F*R with samples; caller sizes them so)
       const size_t slot = (size_t)step * nch + (size_t)(&c - chunks.data());
       const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bl);
       // (retirement: the logits rows are in slot order; a traced step scatters them to the sequences' rows below)
       float* logits_dst = (io.trace_logits && !retire) ? io.trace_logits + trow * S : sc.logits;
-      if (W) {
-        FF_RETURN_IF(beam_step(c, sc, step, slot, folded_head, logits_dst, trow, st));
-        continue;
-      }
-      if (R) {
-        FF_RETURN_IF(sample_step(c, sc, step, slot, folded_head, logits_dst, st));
-        continue;
-      }
-      if (con) {
-        FF_RETURN_IF(constrained_step(c, sc, step, slot, folded_head, logits_dst, st));
-        continue;
-      }
-      ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, lagged ? buf.arrive + slot : nullptr,
-                            lagged ? pool->hpin_dev + slot : nullptr, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
-                            folded_head ? 1 : 0, c.slot, retire ? fin_dev + c.b0 : nullptr, t, p->term_lo, p->term_hi};
-      FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fl, c.Bl, io.mask, io.kv_len, t, false, nullptr, st,
-                                folded_head ? logits_dst : nullptr));
-      FF_RETURN_IF(ff_pointer_argmax_sync(
-          folded_head ? nullptr : sc.p, E, io.memory + (size_t)c.w0 * S * E, S, E, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0,
-          io.extra_mask ? io.extra_mask + (size_t)c.b0 * S : nullptr, S, c.Bl, c.Fl,
-          buf.tok_all + (size_t)t * Btot + c.b0, io.trace_best ? io.trace_best + trow : nullptr,
-          io.trace_second ? io.trace_second + trow : nullptr,
-          buf.lp_all ? buf.lp_all + (size_t)step * Btot + c.b0 : nullptr,   // (indexed by sequence, as the tokens are)
-          logits_dst, S,
-          c.x0 + (size_t)t * c.Bl * E, E, buf.cnt_ge + slot, m->num_token, buf.cnt_eq + slot, p->tok_eos,
-          (each_eos || lagged || c.x0stat || folded_head || retire) ? &psync : nullptr, st));
-      if (retire && io.trace_logits)
-        FF_RETURN_IF(ff_permute_rows(sc.logits, c.Bl, nullptr, io.trace_logits + trow * S, c.Bc, c.slot, 1, c.Bl, S, st));
+      // (the greedy pointer launch makes its own dot products when the head is not folded)
+      if (mode.kind == Mode::GREEDY)
+        FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fl, c.Bl, io.mask, io.kv_len, t, false, nullptr, st,
+                                  folded_head ? logits_dst : nullptr));
+      else
+        FF_RETURN_IF(step_head(c, sc, t, c.Fc, c.Bc, folded_head, logits_dst, st));
+      FF_RETURN_IF(select_step(c, sc, step, slot, folded_head, logits_dst, trow, st));
     }
     slots_per_step.push_back(nslots);
     return FF_OK;
   }
-  // Beam decode, step `step` of one micro-batch: the decoder pass, then top-W selection and prefix reorder in place of the
-  // pointer launch.  The selection reads the state row `step` and writes row t = step + 1, the chunk's next x0 rows (with their
-  // statistics) and the stop counter; the reorder then moves positions < t of x0 and qkv0 behind it on the same stream, so the
-  // next decoder pass reads reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
-  int beam_step(const Chunk& c, const Scratch& sc, int step, size_t slot, bool folded_head, float* logits_dst, size_t trow, hipStream_t st) {
-    const int t = step + 1, G = c.Bc / W;
-    const float* mem_w = io.memory + (size_t)c.w0 * S * E;
-    FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
-    if (!folded_head)   // logits[w * Fc + i, s] = < p[w * Fc + i, :], memory[w, s, :] >: one GEMM problem per wireframe, as the pointer launch
-      FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
-                                       (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
-    const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
-    FF_RETURN_IF(ff_beam_select_sync(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, G, W, c.Fc / W, buf.bm_score + in,
-                                     buf.bm_score + out, buf.bm_fin + in, buf.bm_fin + out, nullptr, 0, t, buf.bm_parent + out,
-                                     buf.tok_all + out, p->term_lo, p->term_hi, mem_w, E, c.x0 + (size_t)t * c.Bc * E, E,
-                                     buf.cnt_ge + slot, m->num_token, c.x0stat, lagged ? buf.arrive + slot : nullptr,
-                                     lagged ? pool->hpin_dev + slot : nullptr, st));
-    if (beam->trace_parent)
-      FF_CHECK_HIP(hipMemcpyAsync(beam->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
-    if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
-    return FF_OK;
+  // What every opt-in step opens with: the decoder pass over the prefix, then -- unless the folded head has left them already --
+  // the logits by the pointer GEMM (always the GEMM + reduce form, as a decode with log-probabilities):
+  // logits[w * Fc + i, s] = < p[w * Fc + i, :], memory[w, s, :] >, one GEMM problem per wireframe, as the pointer launch.
+  int step_head(const Chunk& c, const Scratch& sc, int t, int Fc, int Bc, bool folded_head, float* logits_dst, hipStream_t st) {
+    FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, Fc, Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
+    if (folded_head) return FF_OK;
+    return ff_gemm_f32_batched(sc.p, E, nullptr, 0, io.memory + (size_t)c.w0 * S * E, E, nullptr, nullptr, 0, logits_dst, S, Fc, S, E, 0,
+                               0, c.nw, (long long)Fc * E, (long long)S * E, (long long)Fc * S, st);
   }
-  // Sampled decode, step `step` of one micro-batch: the decoder pass, the pointer GEMM (always the GEMM + reduce form, as a
-  // decode with log-probabilities), then ff_pointer_sample in place of the pointer launch.  It reads the state row `step` and
-  // this step's uniforms through the chunk's row_id, and writes row t = step + 1, the chunk's next x0 rows (with their
-  // statistics) and the stop counter.  Every step has rows of its own: one enqueued past the stop changes nothing that is read.
-  int sample_step(const Chunk& c, const Scratch& sc, int step, size_t slot, bool folded_head, float* logits_dst, hipStream_t st) {
+  // The selection of step `step` (position t = step + 1) of one micro-batch from its logits.  Every opt-in launch reads the
+  // mode's state row `step` and writes row t, the chunk's next x0 rows (with their statistics) and -- but for the forced one,
+  // which counts nothing -- the stop counter; a step enqueued past the stop writes rows that nothing reads.
+  int select_step(const Chunk& c, const Scratch& sc, int step, size_t slot, bool folded_head, float* logits_dst, size_t trow, hipStream_t st) {
     const int t = step + 1;
     const float* mem_w = io.memory + (size_t)c.w0 * S * E;
-    FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
-    if (!folded_head)
-      FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
-                                       (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
+    const unsigned char* mask_w = io.mask + (size_t)c.w0 * S;
+    const int* kv_w = io.kv_len + c.w0;
     const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
-    const int rows = N * F * R;
-    return ff_pointer_sample_sync(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, c.Bc, c.Fc,
-                                  sample->uniforms + (size_t)step * rows, rows, buf.sm_row + c.b0, buf.sm_fin + in, sample->temperature,
-                                  sample->top_k, sample->top_p, p->term_lo, p->term_hi, buf.tok_all + out, buf.sm_lp + out,
-                                  buf.sm_fin + out, mem_w, E, c.x0 + (size_t)t * c.Bc * E, E, c.x0stat, buf.cnt_ge + slot,
-                                  m->num_token, lagged ? buf.arrive + slot : nullptr, lagged ? pool->hpin_dev + slot : nullptr, st);
-  }
-  // Constrained decode, step `step` of one micro-batch: the decoder pass, the pointer GEMM (always the GEMM + reduce form, as a
-  // decode with log-probabilities), then ff_pointer_constrained in place of the pointer launch.  It reads the state row `step`
-  // and writes row t = step + 1, the chunk's next x0 rows (with their statistics) and the stop counter; the visited words and
-  // the byte rows belong to the sequence and are rewritten in stream order.  A step enqueued past the stop writes records and
-  // state that nothing reads.
-  int constrained_step(const Chunk& c, const Scratch& sc, int step, size_t slot, bool folded_head, float* logits_dst, hipStream_t st) {
-    const int t = step + 1, L = p->L, fw = (L + 31) / 32;
-    const float* mem_w = io.memory + (size_t)c.w0 * S * E;
-    FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
-    if (!folded_head)
-      FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
-                                       (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
-    const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
-    return ff_pointer_constrained_sync(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, c.Bc, c.Fc,
-                                       con->follows ? con->follows + (size_t)c.w0 * L * fw : nullptr, L, con->flags, m->num_token,
-                                       p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in,
-                                       buf.cn_visited + (size_t)c.b0 * fw, buf.cn_rows + (size_t)c.b0 * S, buf.tok_all + out,
-                                       buf.cn_lp + out, buf.cn_fin + out, buf.cn_dead + out, buf.cn_first + out, buf.cn_prev + out,
-                                       mem_w, E, c.x0 + (size_t)t * c.Bc * E, E, c.x0stat, buf.cnt_ge + slot,
-                                       lagged ? buf.arrive + slot : nullptr, lagged ? pool->hpin_dev + slot : nullptr, st);
+    float* next_rows = c.x0 + (size_t)t * c.Bl * E;   // (Bl = Bc but under retirement, which every opt-in mode excludes)
+    const bool hand_over = lagged && mode.kind != Mode::FORCED;   // (a forced step counts nothing: its slot and trow are not used)
+    int* arrive = hand_over ? buf.arrive + slot : nullptr;
+    int* host_slot = hand_over ? pool->hpin_dev + slot : nullptr;
+    switch (mode.kind) {
+      case Mode::BEAM: {
+        // top-W selection, then the reorder of positions < t of x0 and qkv0 behind it on the same stream: the next decoder pass
+        // reads reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
+        const int W = mode.G, G = c.Bc / W;
+        FF_RETURN_IF(ff_beam_select_sync(logits_dst, S, S, mask_w, kv_w, G, W, c.Fc / W, buf.bm_score + in, buf.bm_score + out,
+                                         buf.bm_fin + in, buf.bm_fin + out, nullptr, 0, t, buf.bm_parent + out, buf.tok_all + out,
+                                         p->term_lo, p->term_hi, mem_w, E, next_rows, E, buf.cnt_ge + slot, m->num_token, c.x0stat,
+                                         arrive, host_slot, st));
+        if (mode.beam()->trace_parent)
+          FF_CHECK_HIP(hipMemcpyAsync(mode.beam()->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
+        if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
+        return FF_OK;
+      }
+      case Mode::SAMPLE: {   // (this step's uniforms are read through the chunk's row_id)
+        const ff_sample_params* sp = mode.sample();
+        const int rows = N * F * mode.G;
+        return ff_pointer_sample_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, sp->uniforms + (size_t)step * rows, rows,
+                                      buf.sm_row + c.b0, buf.sm_fin + in, sp->temperature, sp->top_k, sp->top_p, p->term_lo, p->term_hi,
+                                      buf.tok_all + out, buf.sm_lp + out, buf.sm_fin + out, mem_w, E, next_rows, E, c.x0stat,
+                                      buf.cnt_ge + slot, m->num_token, arrive, host_slot, st);
+      }
+      case Mode::CONSTRAIN: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
+        const int L = p->L, fw = (L + 31) / 32;
+        const unsigned* follows = mode.con()->follows;
+        return ff_pointer_constrained_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, follows ? follows + (size_t)c.w0 * L * fw : nullptr,
+                                           L, mode.con()->flags, m->num_token,
+                                           p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in,
+                                           buf.cn_visited + (size_t)c.b0 * fw, buf.cn_rows + (size_t)c.b0 * S, buf.tok_all + out,
+                                           buf.cn_lp + out, buf.cn_fin + out, buf.cn_dead + out, buf.cn_first + out, buf.cn_prev + out,
+                                           mem_w, E, next_rows, E, c.x0stat, buf.cnt_ge + slot, arrive, host_slot, st);
+      }
+      case Mode::FORCED:   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
+        return ff_pointer_forced(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, buf.tok_all + out, buf.fc_lp + in, buf.fc_greedy + in,
+                                 buf.fc_rank + in, mem_w, E, next_rows, E, c.x0stat, st);
+      default: break;
+    }
+    ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, arrive, host_slot, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
+                          folded_head ? 1 : 0, c.slot, retire ? fin_dev + c.b0 : nullptr, t, p->term_lo, p->term_hi};
+    FF_RETURN_IF(ff_pointer_argmax_sync(
+        folded_head ? nullptr : sc.p, E, mem_w, S, E, mask_w, kv_w, io.extra_mask ? io.extra_mask + (size_t)c.b0 * S : nullptr, S, c.Bl,
+        c.Fl, buf.tok_all + out, io.trace_best ? io.trace_best + trow : nullptr, io.trace_second ? io.trace_second + trow : nullptr,
+        buf.lp_all ? buf.lp_all + in : nullptr,   // (indexed by sequence, as the tokens are)
+        logits_dst, S, next_rows, E, buf.cnt_ge + slot, m->num_token, buf.cnt_eq + slot, p->tok_eos,
+        (each_eos || lagged || c.x0stat || folded_head || retire) ? &psync : nullptr, st));
+    if (retire && io.trace_logits)
+      FF_RETURN_IF(ff_permute_rows(sc.logits, c.Bl, nullptr, io.trace_logits + trow * S, c.Bc, c.slot, 1, c.Bl, S, st));
+    return FF_OK;
   }
   // ---- forced decode ------------------------------------------------------------------------------------------------------------
   // The caller's paths as the token array (main stream, in front of the prologue's fork: every stream sees them).
-  int forced_tokens() { return ff_forced_tokens(forced->paths, buf.tok_all, Btot, T, S, io.main_st); }
-  // Step `step` of every micro-batch that still has a row to score: the decoder pass over the forced prefix, the pointer GEMM
-  // (always the GEMM + reduce form, as a decode with log-probabilities), then ff_pointer_forced in place of the pointer launch:
-  // it scores position t = step + 1 of the paths and appends THAT token's row.  Nothing is read back, nothing is counted.
+  int forced_tokens() { return ff_forced_tokens(mode.forced()->paths, buf.tok_all, Btot, T, S, io.main_st); }
+  // Step `step` of every micro-batch that still has a row to score.  Nothing is read back, nothing is counted.
   int forced_loop() {
     for (int step = 0; step < forced_steps; ++step) {
       const int t = step + 1;
@@ -1105,17 +1121,10 @@ struct DecodeRun {
         if (step >= chunk_steps[(size_t)(&c - chunks.data())]) continue;
         hipStream_t st = sts[c.sid];
         const Scratch& sc = buf.scr[c.sid];
-        const float* mem_w = io.memory + (size_t)c.w0 * S * E;
         const bool folded_head = c.pg != nullptr && step_fuses(m, p, (long)t * c.Bc);
         float* logits_dst = io.trace_logits ? io.trace_logits + ((size_t)step * Btot + c.b0) * S : sc.logits;
-        FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fc, c.Bc, io.mask, io.kv_len, t, false, nullptr, st, folded_head ? logits_dst : nullptr));
-        if (!folded_head)
-          FF_RETURN_IF(ff_gemm_f32_batched(sc.p, E, nullptr, 0, mem_w, E, nullptr, nullptr, 0, logits_dst, S, c.Fc, S, E, 0, 0, c.nw,
-                                           (long long)c.Fc * E, (long long)S * E, (long long)c.Fc * S, st));
-        const size_t rec = (size_t)step * Btot + c.b0;
-        FF_RETURN_IF(ff_pointer_forced(logits_dst, S, S, io.mask + (size_t)c.w0 * S, io.kv_len + c.w0, c.Bc, c.Fc,
-                                       buf.tok_all + (size_t)t * Btot + c.b0, buf.fc_lp + rec, buf.fc_greedy + rec, buf.fc_rank + rec,
-                                       mem_w, E, c.x0 + (size_t)t * c.Bc * E, E, c.x0stat, st));
+        FF_RETURN_IF(step_head(c, sc, t, c.Fc, c.Bc, folded_head, logits_dst, st));
+        FF_RETURN_IF(select_step(c, sc, step, 0, folded_head, logits_dst, 0, st));   // (no counter slot, no trace row offset)
       }
     }
     enq = forced_steps;
@@ -1129,8 +1138,9 @@ struct DecodeRun {
         FF_CHECK_HIP(hipEventRecord(pool->join_ev[s], sts[s]));
         FF_CHECK_HIP(hipStreamWaitEvent(main_st, pool->join_ev[s], 0));
       }
-    FF_RETURN_IF(ff_forced_finalize(buf.tok_all, buf.fc_lp, buf.fc_greedy, buf.fc_rank, forced->lengths, Btot, T, forced->logprob,
-                                    forced->greedy, forced->rank, forced->seq_logprob, main_st));
+    const ff_forced_params* fp = mode.forced();
+    FF_RETURN_IF(ff_forced_finalize(buf.tok_all, buf.fc_lp, buf.fc_greedy, buf.fc_rank, fp->lengths, Btot, T, fp->logprob, fp->greedy,
+                                    fp->rank, fp->seq_logprob, main_st));
     FF_CHECK_HIP(hipStreamSynchronize(main_st));   // (the caller may free or reuse the workspace next, as after ff_decode)
     if (io.steps_done) *io.steps_done = forced_steps;
     return FF_OK;
@@ -1265,6 +1275,30 @@ struct DecodeRun {
     }
     return FF_OK;
   }
+  // The outputs of one micro-batch's rows from the per-step records up to the stop step (main stream).
+  int pack(const Chunk& c) {
+    const hipStream_t main_st = io.main_st;
+    const int G = mode.G, dd = dedup ? 1 : 0;
+    switch (mode.kind) {
+      case Mode::BEAM:
+        return ff_beam_finalize(buf.tok_all, buf.bm_parent, buf.bm_score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
+                                c.Fc / G, c.f0, c.b0, mode.beam()->beams, mode.beam()->scores, io.predict, io.seq_of_row, main_st);
+      case Mode::SAMPLE:
+        return ff_sample_finalize(buf.tok_all, buf.sm_lp, buf.sm_fin, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
+                                  c.Fc / G, c.f0, c.b0, mode.sample()->samples, mode.sample()->logprob, mode.sample()->scores, io.predict,
+                                  io.seq_of_row, main_st);
+      case Mode::CONSTRAIN:
+        return ff_constrain_finalize(buf.tok_all, buf.cn_lp, buf.cn_fin, buf.cn_dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
+                                     c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con()->logprob, mode.con()->dead_end, io.seq_of_row, main_st);
+      default: break;   // (forced: forced_epilogue packs all rows at once)
+    }
+    const long total = (long)c.nw * F * T;
+    const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+    hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev, io.num_input, dd,
+                       F, c.w0, c.nw, c.Fc, c.f0, c.b0, io.predict, io.seq_of_row, retire ? fin_dev : nullptr, buf.lp_all, io.logprob);
+    FF_CHECK_LAUNCH();
+    return FF_OK;
+  }
   // Join, then everything after the greedy loop on the main stream: stop step, packing, the optional return-pointer pass.
   int epilogue() {
     const hipStream_t main_st = io.main_st;
@@ -1276,31 +1310,7 @@ struct DecodeRun {
     hipLaunchKernelGGL(steps_kernel, dim3(1), dim3(64), 0, main_st, buf.cnt_ge, buf.cnt_eq, nch, p->variant, N, enq,
                        ((p->flags & FF_NO_STOP) || p->stop_fn) ? 1 : 0, buf.cnt_tot, buf.steps_dev);
     FF_CHECK_LAUNCH();
-    for (const Chunk& c : chunks) {
-      if (W) {
-        FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.bm_parent, buf.bm_score, Btot, T, buf.steps_dev, io.num_input, dedup ? 1 : 0, F, W,
-                                      c.w0, c.nw, c.Fc / W, c.f0, c.b0, beam->beams, beam->scores, io.predict, io.seq_of_row, main_st));
-        continue;
-      }
-      if (R) {
-        FF_RETURN_IF(ff_sample_finalize(buf.tok_all, buf.sm_lp, buf.sm_fin, Btot, T, buf.steps_dev, io.num_input, dedup ? 1 : 0, F, R,
-                                        c.w0, c.nw, c.Fc / R, c.f0, c.b0, sample->samples, sample->logprob, sample->scores,
-                                        io.predict, io.seq_of_row, main_st));
-        continue;
-      }
-      if (con) {
-        FF_RETURN_IF(ff_constrain_finalize(buf.tok_all, buf.cn_lp, buf.cn_fin, buf.cn_dead, Btot, T, buf.steps_dev, io.num_input,
-                                           dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, io.predict, con->logprob, con->dead_end,
-                                           io.seq_of_row, main_st));
-        continue;
-      }
-      const long total = (long)c.nw * F * T;
-      const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-      hipLaunchKernelGGL(finalize_chunk_kernel, dim3(grid), dim3(256), 0, main_st, buf.tok_all, Btot, T, buf.steps_dev,
-                         io.num_input, dedup ? 1 : 0, F, c.w0, c.nw, c.Fc, c.f0, c.b0, io.predict, io.seq_of_row,
-                         retire ? fin_dev : nullptr, buf.lp_all, io.logprob);
-      FF_CHECK_LAUNCH();
-    }
+    for (const Chunk& c : chunks) FF_RETURN_IF(pack(c));
     int steps = 0;
     FF_CHECK_HIP(hipMemcpyAsync(&steps, buf.steps_dev, sizeof(int), hipMemcpyDeviceToHost, main_st));
     if (io.step_counts && enq > 0)
@@ -1329,10 +1339,32 @@ struct DecodeRun {
   }
 };
 
-// One decode call from validation to the packed outputs (ff_decode / ff_decode_lp: beam null; ff_decode_beam).
+// One decode call from validation to the packed outputs.
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam, const ff_forced_params* forced = nullptr, const ff_sample_params* sample = nullptr,
-               const ff_constrain_params* constrain = nullptr);
+               const Mode& mode);
+
+// What ff_decode_beam, ff_decode_sample and ff_decode_constrained (`name`; `subject`: the option as its message words it) have
+// in common: the combinations they exclude ...
+int check_opt_in(const char* name, const char* subject, const ff_decode_params* p, const unsigned char* extra_mask) {
+  FF_CHECK_ARG(p->variant == FF_PARALLEL, "%s: %s a parallel-variant option", name, subject);
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
+               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask", name);
+  return FF_OK;
+}
+// ... a terminator range, their own outputs (`required`: their names; have: all given) and none of the greedy call's traces ...
+int check_opt_in_outputs(const char* name, const ff_decode_params* p, const char* required, bool have, const float* trace_best,
+                         const float* trace_second, const float* pointer_out) {
+  FF_CHECK_ARG(p->term_lo < p->term_hi, "%s: empty terminator range [%d, %d)", name, p->term_lo, p->term_hi);
+  FF_CHECK_ARG(have && !trace_best && !trace_second && !pointer_out, "%s: %s required; no best / second traces, no pointer_out", name,
+               required);
+  return FF_OK;
+}
+// ... and what they hand to the decode: no extra mask, no pointer_out, no best / second traces, no log-probabilities.
+DecodeIO opt_in_io(const float* memory, const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host,
+                   int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row, ff_stream_t stream) {
+  return DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
+                  nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr};
+}
 
 }  // namespace
 
@@ -1402,27 +1434,16 @@ extern "C" int ff_encode(const ff_model* m, const float* input, const unsigned c
 }
 
 extern "C" size_t ff_decode_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
-  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
-  int btot = 0, max_bc = 0, nch = 0;
-  plan_chunks(p, num_input_host, 1, nullptr, &btot, &max_bc, &nch);
-  Bump bp(nullptr, 0);
-  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr) + 256;
+  return decode_workspace_bytes(m, p, num_input_host, Mode());
 }
 
 extern "C" size_t ff_decode_lp_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
-  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
-  int btot = 0, max_bc = 0, nch = 0;
-  plan_chunks(p, num_input_host, 1, nullptr, &btot, &max_bc, &nch);
-  Bump bp(nullptr, 0);
-  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, true) + 256;
+  return decode_workspace_bytes(m, p, num_input_host, Mode(), true);
 }
 
 extern "C" size_t ff_decode_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host, int width) {
-  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0 || width < 1 || width > 8) return 0;
-  int btot = 0, max_bc = 0, nch = 0;
-  plan_beam_chunks(p, num_input_host, 1, width, nullptr, &btot, &max_bc, &nch);
-  Bump bp(nullptr, 0);
-  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, true) + 256;
+  if (width < 1 || width > 8) return 0;
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::BEAM, width));
 }
 
 extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const float* memory,
@@ -1443,7 +1464,7 @@ extern "C" int ff_decode_lp(const ff_model* m, const ff_decode_params* p, const 
                             size_t workspace_bytes, float* logprob, ff_stream_t stream) {
   return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, extra_mask, predict, steps_done, step_counts,
                                    pointer_out, trace_logits, trace_best, trace_second, seq_of_row, (hipStream_t)stream, logprob},
-                    workspace, workspace_bytes, nullptr);
+                    workspace, workspace_bytes, Mode());
 }
 
 extern "C" int ff_decode_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
@@ -1453,30 +1474,21 @@ extern "C" int ff_decode_beam(const ff_model* m, const ff_decode_params* p, cons
                               float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
                               size_t workspace_bytes, const ff_beam_params* beam, ff_stream_t stream) {
   FF_CHECK_ARG(m && p && beam, "ff_decode_beam: null model, params or beam params");
-  FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode_beam: beams are a parallel-variant option");
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
-               "ff_decode_beam: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask");
+  FF_RETURN_IF(check_opt_in("ff_decode_beam", "beams are", p, extra_mask));
   FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token,
                "ff_decode_beam: width=%d outside 1..8 or above S=%d", beam->width, p->L + m->num_token);
-  FF_CHECK_ARG(p->term_lo < p->term_hi, "ff_decode_beam: empty terminator range [%d, %d)", p->term_lo, p->term_hi);
-  FF_CHECK_ARG(beam->beams && beam->scores && !trace_best && !trace_second && !pointer_out,
-               "ff_decode_beam: beams and scores required; no best / second traces, no pointer_out");
+  FF_RETURN_IF(check_opt_in_outputs("ff_decode_beam", p, "beams and scores", beam->beams && beam->scores, trace_best, trace_second,
+                                    pointer_out));
   // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
   FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
                "ff_decode_beam: width=%d at E=%d exceeds the reorder's staging area", beam->width, m->E);
-  return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
-                                   nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr},
-                    workspace, workspace_bytes, beam);
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::BEAM, beam->width, beam));
 }
 
 extern "C" size_t ff_decode_forced_workspace_bytes(const ff_model* m, const ff_decode_params* p) {
-  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
-  ff_decode_params q = *p;
-  q.flags &= ~FF_DEDUP_PAD_ANCHORS;
-  int btot = 0, max_bc = 0, nch = 0;
-  plan_chunks(&q, nullptr, 1, nullptr, &btot, &max_bc, &nch);
-  Bump bp(nullptr, 0);
-  return layout_decode(m, &q, engine_knobs(&q), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, false, true) + 256;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::FORCED, 1));
 }
 
 extern "C" int ff_decode_forced(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
@@ -1494,16 +1506,13 @@ extern "C" int ff_decode_forced(const ff_model* m, const ff_decode_params* p, co
                  r, forced->lengths_host[r], p->T - 1);
   return run_decode(m, p, DecodeIO{memory, mask, kv_len, nullptr, nullptr, nullptr, nullptr, steps_done, nullptr, nullptr, trace_logits,
                                    nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr},
-                    workspace, workspace_bytes, nullptr, forced);
+                    workspace, workspace_bytes, Mode(Mode::FORCED, 1, forced));
 }
 
 extern "C" size_t ff_decode_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
                                                    int num_samples) {
-  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0 || num_samples < 1 || num_samples > 64) return 0;
-  int btot = 0, max_bc = 0, nch = 0;
-  plan_beam_chunks(p, num_input_host, 1, num_samples, nullptr, &btot, &max_bc, &nch);
-  Bump bp(nullptr, 0);
-  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, false, false, true) + 256;
+  if (num_samples < 1 || num_samples > 64) return 0;
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::SAMPLE, num_samples));
 }
 
 extern "C" int ff_decode_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
@@ -1513,28 +1522,22 @@ extern "C" int ff_decode_sample(const ff_model* m, const ff_decode_params* p, co
                                 float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
                                 size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream) {
   FF_CHECK_ARG(m && p && sample, "ff_decode_sample: null model, params or sample params");
-  FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode_sample: sampling is a parallel-variant option");
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
-               "ff_decode_sample: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask");
+  FF_RETURN_IF(check_opt_in("ff_decode_sample", "sampling is", p, extra_mask));
   FF_CHECK_ARG(sample->num_samples >= 1 && sample->num_samples <= 64, "ff_decode_sample: num_samples=%d outside 1..64", sample->num_samples);
   FF_CHECK_ARG(sample->temperature >= 0.f && sample->temperature <= 3.402823466e+38f && sample->top_k >= 0 && sample->top_p > 0.f &&
                    sample->top_p <= 1.f, "ff_decode_sample: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]",
                (double)sample->temperature, sample->top_k, (double)sample->top_p);
-  FF_CHECK_ARG(p->term_lo < p->term_hi, "ff_decode_sample: empty terminator range [%d, %d)", p->term_lo, p->term_hi);
-  FF_CHECK_ARG(sample->uniforms && sample->samples && sample->logprob && sample->scores && !trace_best && !trace_second && !pointer_out,
-               "ff_decode_sample: uniforms, samples, logprob and scores required; no best / second traces, no pointer_out");
+  FF_RETURN_IF(check_opt_in_outputs("ff_decode_sample", p, "uniforms, samples, logprob and scores",
+                                    sample->uniforms && sample->samples && sample->logprob && sample->scores, trace_best, trace_second,
+                                    pointer_out));
   FF_CHECK_ARG(p->N > 0 && p->F > 0 && (long long)p->N * p->F * sample->num_samples < (1LL << 31), "ff_decode_sample: bad sizes");
-  return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
-                                   nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr},
-                    workspace, workspace_bytes, nullptr, nullptr, sample);
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::SAMPLE, sample->num_samples, sample));
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
-  if (!m || !p || p->N <= 0 || p->F <= 0 || p->T <= 0) return 0;
-  int btot = 0, max_bc = 0, nch = 0;
-  plan_chunks(p, num_input_host, 1, nullptr, &btot, &max_bc, &nch);
-  Bump bp(nullptr, 0);
-  return layout_decode(m, p, engine_knobs(p), (size_t)btot, (size_t)max_bc, (size_t)nch, bp, nullptr, false, false, false, false, true) + 256;
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN, 1));
 }
 
 extern "C" int ff_decode_constrained(const ff_model* m, const ff_decode_params* p, const float* memory,
@@ -1544,31 +1547,24 @@ extern "C" int ff_decode_constrained(const ff_model* m, const ff_decode_params* 
                                      float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
                                      size_t workspace_bytes, const ff_constrain_params* constrain, ff_stream_t stream) {
   FF_CHECK_ARG(m && p && constrain, "ff_decode_constrained: null model, params or constrain params");
-  FF_CHECK_ARG(p->variant == FF_PARALLEL, "ff_decode_constrained: the constrained decode is a parallel-variant option");
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
-               "ff_decode_constrained: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask");
+  FF_RETURN_IF(check_opt_in("ff_decode_constrained", "the constrained decode is", p, extra_mask));
   FF_CHECK_ARG(!(constrain->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "ff_decode_constrained: unknown flag bits %d", constrain->flags);
   FF_CHECK_ARG(constrain->follows || !(constrain->flags & FF_CONSTRAIN_CONNECT), "ff_decode_constrained: FF_CONSTRAIN_CONNECT needs the follow table");
+  // (its own wording of the terminator rule, stricter than the shared one behind it)
   FF_CHECK_ARG(p->term_lo >= 0 && p->term_lo < p->term_hi && p->term_hi <= m->num_token,
                "ff_decode_constrained: terminator range [%d, %d) empty or outside the %d special tokens", p->term_lo, p->term_hi, m->num_token);
-  FF_CHECK_ARG(constrain->logprob && constrain->dead_end && !trace_best && !trace_second && !pointer_out,
-               "ff_decode_constrained: logprob and dead_end required; no best / second traces, no pointer_out");
-  return run_decode(m, p, DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
-                                   nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr},
-                    workspace, workspace_bytes, nullptr, nullptr, nullptr, constrain);
+  FF_RETURN_IF(check_opt_in_outputs("ff_decode_constrained", p, "logprob and dead_end", constrain->logprob && constrain->dead_end,
+                                    trace_best, trace_second, pointer_out));
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN, 1, constrain));
 }
 
 namespace {
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
-               const ff_beam_params* beam, const ff_forced_params* forced, const ff_sample_params* sample,
-               const ff_constrain_params* constrain) {
+               const Mode& mode) {
   DecodeRun r;
-  r.con = constrain;
-  r.forced = forced;
-  r.sample = sample;
-  r.R = sample ? sample->num_samples : 0;
-  r.beam = beam;
-  r.W = beam ? beam->width : 0;
+  r.mode = mode;
   FF_RETURN_IF(r.validate(m, p, io, workspace));
   FF_RETURN_IF(r.bind_chunks(workspace, workspace_bytes));
   FF_RETURN_IF(ff_gemm_prepare_stream(r.io.main_st));
@@ -1578,7 +1574,7 @@ int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io,
   FF_RETURN_IF(r.bind_streams());
   FF_RETURN_IF(r.init_retirement());
   int rc = FF_OK;
-  if (forced) {   // (no row to score: the start tokens are packed, no decoder launch is made)
+  if (mode.kind == Mode::FORCED) {   // (no row to score: the start tokens are packed, no decoder launch is made)
     rc = r.forced_tokens();
     if (rc == FF_OK && r.forced_steps > 0) rc = r.prologue();
     if (rc == FF_OK) rc = r.forced_loop();

@@ -18,6 +18,7 @@
 
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 namespace {
 
@@ -104,14 +105,12 @@ extern "C" int ff_pointer_forced(float* logits, int ldlogits, int S, const unsig
   FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "ff_pointer_forced: bad sizes B=%d S=%d", B, S);
   FF_CHECK_ARG(logits && ldlogits >= S, "ff_pointer_forced: logits missing or ldlogits < S");
   FF_CHECK_ARG(forced && logprob && greedy && rank, "ff_pointer_forced: null pointer");
-  FF_CHECK_ARG(!next_rows || (memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ldnext >= E && ff_aligned16(memory) && ff_aligned16(next_rows)),
-               "ff_pointer_forced: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment");
-  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "ff_pointer_forced: next_stats needs next_rows and E %% 32 == 0");
   ForcedArgs a;
   memset(&a, 0, sizeof(a));
-  a.p.memory = memory; a.p.S = S; a.p.E = E; a.p.mask = mask; a.p.kv_len = kv_len;
+  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_pointer_forced", true, memory, E, next_rows, ldnext, next_stats, nullptr, nullptr, nullptr));
+  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
   a.p.B = B; a.p.spg = seqs_per_group;
-  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.next_rows = next_rows; a.p.ldnext = ldnext; a.p.next_stats = next_stats;
+  a.p.logits = logits; a.p.ldlogits = ldlogits;
   a.forced = forced; a.logprob = logprob; a.greedy = greedy; a.rank = rank;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 12.0, st);

@@ -11,6 +11,7 @@
 
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 namespace {
 
@@ -178,6 +179,21 @@ extern "C" int ff_pointer_argmax_lp(const float* p, int ldp, const float* memory
   return ff_pointer_argmax_sync(p, ldp, memory, S, E, mask, kv_len, extra_mask, ldextra, B, seqs_per_group, next_tok, best,
                                 second, logprob, logits, ldlogits, next_rows, ldnext, count_ge, ge_bound, count_eq, eq_value,
                                 nullptr, stream);
+}
+
+// The feedback members of the mode launches' PointerArgs (ff_launch.h)
+int ff_pointer_feedback(PointerArgs* a, const char* op, bool ld_rule, const float* memory, int E, float* next_rows, int ldnext,
+                        float* next_stats, int* count_ge, int* arrive, int* host_slot) {
+  const bool rows_ok = memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ff_aligned16(memory) && ff_aligned16(next_rows);
+  if (ld_rule)
+    FF_CHECK_ARG(!next_rows || (rows_ok && ldnext >= E), "%s: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment", op);
+  else
+    FF_CHECK_ARG(!next_rows || rows_ok, "%s: next_rows needs memory, E %% 4 == 0 and 16-byte alignment", op);
+  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "%s: next_stats needs next_rows and E %% 32 == 0", op);
+  FF_CHECK_ARG(!arrive || (host_slot && count_ge), "%s: counter hand-over without a counter", op);
+  a->memory = memory; a->E = E; a->next_rows = next_rows; a->ldnext = ldnext; a->next_stats = next_stats;
+  a->count_ge = count_ge; a->arrive = arrive; a->host_slot = host_slot;
+  return FF_OK;
 }
 
 // The same operator with the decode engine's counter hand-over (ff_common.h: ff_pointer_sync); not part of the C ABI.

@@ -25,6 +25,7 @@
 
 #include "ff_common.h"
 #include "ff_device.h"
+#include "ff_launch.h"
 
 namespace {
 
@@ -57,10 +58,9 @@ __device__ __forceinline__ float sample_wave_scan(float c, int lane) {
 }
 
 __global__ __launch_bounds__(256) void pointer_sample_kernel(SampleArgs a) {
-  __shared__ int s_cnt[4];
   const PointerArgs& pa = a.p;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.x * 4 + wv;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   const float FILL = -FLT_MAX;
   int nge = 0;
   if (b < pa.B) {   // (wave-uniform)
@@ -159,23 +159,7 @@ __global__ __launch_bounds__(256) void pointer_sample_kernel(SampleArgs a) {
     }
     if (pa.next_rows) ff_pointer_append_row(pa, b / pa.spg, b, tok, lane);
   }
-  if (!pa.count_ge) return;   // (launch-uniform)
-  if (lane == 0) s_cnt[wv] = nge;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    // one atomic per block; the launch's last block publishes the total to the host-mapped twin (as ff_pointer_count_block)
-    const int nvalid = pa.B - blockIdx.x * 4 < 4 ? pa.B - blockIdx.x * 4 : 4;
-    int n = 0;
-    for (int i = 0; i < nvalid; ++i) n += s_cnt[i];
-    if (n) atomicAdd(pa.count_ge, n);
-    if (pa.arrive) {
-      const int prev = __hip_atomic_fetch_add(pa.arrive, nvalid, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev + nvalid == pa.B) {
-        const int v = __hip_atomic_load(pa.count_ge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pa.host_slot, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
+  ff_pointer_count_waves(pa, pa.B, nge);
 }
 
 // ---- engine side: start state and output packing of a sampled decode (ff_engine.hip) ---------------------------------------------
@@ -188,10 +172,10 @@ __global__ void sample_init_kernel(int* tok, float* lp, int* fin, int* row_id, i
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= Bc) return;
   const int k = i % R, a = i / R, wl = a / Fc, f = f0 + a % Fc;
-  const int t = f < num_input[wl] ? f : pad_tok;
-  tok[i] = t;
+  int done;
+  tok[i] = ff_start_token(f, num_input[wl], pad_tok, term_lo, term_hi, &done);
   lp[i] = 0.f;
-  fin[i] = (t >= term_lo && t < term_hi) ? 1 : 0;
+  fin[i] = done;
   row_id[i] = ((w0 + wl) * F + (f < F ? f : F - 1)) * R + k;
 }
 
@@ -209,10 +193,9 @@ __global__ void sample_finalize_kernel(const int* __restrict__ tok, const float*
   const int total = nw * F * R;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int k = i % R, fo = (i / R) % F, wl = i / (R * F);
-    int f = fo;
-    if (dedup) { const int n = num_input[w0 + wl]; f = fo < n ? fo : n; }
-    if (f < f0 || f >= f0 + Fc) continue;
-    const int seq = b0 + (wl * Fc + (f - f0)) * R + k;
+    int a;
+    if (!ff_compact_seq(num_input, dedup, w0, wl, fo, Fc, f0, &a)) continue;
+    const int seq = b0 + a * R + k;
     const size_t row = ((size_t)(w0 + wl) * F + fo) * R + k;
     int64_t* out = samples + row * T;
     float* olp = logprob + row * T;
@@ -249,16 +232,12 @@ int ff_pointer_sample_sync(float* logits, int ldlogits, int S, const unsigned ch
   FF_CHECK_ARG(temperature >= 0.f && temperature <= FLT_MAX && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
                "ff_pointer_sample: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]", (double)temperature,
                top_k, (double)top_p);
-  FF_CHECK_ARG(!next_rows || (memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ldnext >= E && ff_aligned16(memory) && ff_aligned16(next_rows)),
-               "ff_pointer_sample: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment");
-  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "ff_pointer_sample: next_stats needs next_rows and E %% 32 == 0");
-  FF_CHECK_ARG(!arrive || (host_slot && count_ge), "ff_pointer_sample: counter hand-over without a counter");
   SampleArgs a;
   memset(&a, 0, sizeof(a));
-  a.p.memory = memory; a.p.S = S; a.p.E = E; a.p.mask = mask; a.p.kv_len = kv_len;
+  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_pointer_sample", true, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
+  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
   a.p.B = B; a.p.spg = seqs_per_group;
-  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.next_rows = next_rows; a.p.ldnext = ldnext; a.p.next_stats = next_stats;
-  a.p.count_ge = count_ge; a.p.ge_bound = ge_bound; a.p.arrive = arrive; a.p.host_slot = host_slot;
+  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.ge_bound = ge_bound;
   a.p.term_lo = term_lo; a.p.term_hi = term_hi;
   a.uniforms = uniforms; a.num_uniforms = num_uniforms; a.row_id = row_id; a.fin_in = fin_in; a.fin_out = fin_out;
   a.tok = next_tok; a.logprob = logprob;

@@ -530,43 +530,48 @@ class PathEngine:
             self._same_device(extra_mask, "extra_mask")
             extra_mask = extra_mask.contiguous()
         pointer = torch.zeros((max(T - 1, 1), B, E), device=dev, dtype=torch.float32) if return_pointer else None
-        tl = tb = ts = rows = None
         G = W or R    # sequences per anchor of a beam / sampled decode
-        if trace and (G or CF is not None):
-            tl = torch.full((max(T - 1, 1), B * max(G, 1), S), float("nan"), device=dev, dtype=torch.float32)
-        elif trace:
-            tl = torch.full((max(T - 1, 1), B, S), float("nan"), device=dev, dtype=torch.float32)
-            tb = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
-            ts = torch.full((max(T - 1, 1), B), float("nan"), device=dev, dtype=torch.float32)
+        steps_max = max(T - 1, 1)
+        traced = {}   # the traces, which the C side indexes by decoded sequence
+        if trace:
+            traced["logits"] = torch.full((steps_max, B * max(G, 1), S), float("nan"), device=dev, dtype=torch.float32)
+            if not (G or CF is not None):
+                traced["best"] = torch.full((steps_max, B), float("nan"), device=dev, dtype=torch.float32)
+                traced["second"] = torch.full((steps_max, B), float("nan"), device=dev, dtype=torch.float32)
         rows = torch.empty(B * max(G, 1), device=dev, dtype=torch.int32)
         lp = torch.empty((B, T), device=dev, dtype=torch.float32) if logprob else None
+        # per mode, once: the entry's name (its size query is <name>_workspace_bytes) with the arguments only that query and only
+        # that entry take (its parameter struct, or the log-probability output), and the mode's outputs
+        name, size_args, tail, extra = "ff_decode", (), (), {}
         if W:
-            beams = torch.empty((B * W, T), device=dev, dtype=torch.int64)
-            bscores = torch.empty(B * W, device=dev, dtype=torch.float32)
-            bparent = torch.full((max(T - 1, 1), B * W), -1, device=dev, dtype=torch.int32) if trace else None
-            bprm = _L.BeamParams(W, _p(beams), _p(bscores), _p(bparent))
-            nbytes = self._lib.ff_decode_beam_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host, W)
+            extra = {"beams": torch.empty((B * W, T), device=dev, dtype=torch.int64),
+                     "beam_scores": torch.empty(B * W, device=dev, dtype=torch.float32)}
+            if trace:
+                traced["beam_parent"] = torch.full((steps_max, B * W), -1, device=dev, dtype=torch.int32)
+            mprm = _L.BeamParams(W, _p(extra["beams"]), _p(extra["beam_scores"]), _p(traced.get("beam_parent")))
+            name, size_args, tail = "ff_decode_beam", (W,), (C.byref(mprm),)
         elif R:
             _dev(uniforms, "uniforms")
             self._same_device(uniforms, "uniforms")
             uniforms = uniforms.contiguous()
-            samples = torch.empty((B * R, T), device=dev, dtype=torch.int64)
-            slp = torch.empty((B * R, T), device=dev, dtype=torch.float32)
-            sscores = torch.empty(B * R, device=dev, dtype=torch.float32)
-            sprm = _L.SampleParams(R, float(temperature), int(top_k), float(top_p), _p(uniforms), _p(samples), _p(slp), _p(sscores))
-            nbytes = self._lib.ff_decode_sample_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host, R)
+            extra = {"samples": torch.empty((B * R, T), device=dev, dtype=torch.int64),
+                     "sample_logprob": torch.empty((B * R, T), device=dev, dtype=torch.float32),
+                     "sample_scores": torch.empty(B * R, device=dev, dtype=torch.float32)}
+            mprm = _L.SampleParams(R, float(temperature), int(top_k), float(top_p), _p(uniforms), _p(extra["samples"]),
+                                   _p(extra["sample_logprob"]), _p(extra["sample_scores"]))
+            name, size_args, tail = "ff_decode_sample", (R,), (C.byref(mprm),)
         elif CF is not None:
             if follow_table is not None:
                 _dev(follow_table, "follow_table", torch.int32)
                 self._same_device(follow_table, "follow_table")
                 follow_table = follow_table.contiguous()
-            clp = torch.empty((B, T), device=dev, dtype=torch.float32)
-            cdead = torch.empty(B, device=dev, dtype=torch.int32)
-            cprm = _L.ConstrainParams(CF, _p(follow_table), _p(clp), _p(cdead))
-            nbytes = self._lib.ff_decode_constrained_workspace_bytes(C.byref(self.model), C.byref(prm), ni_host)
-        else:
-            ws_bytes = self._lib.ff_decode_lp_workspace_bytes if logprob else self._lib.ff_decode_workspace_bytes
-            nbytes = ws_bytes(C.byref(self.model), C.byref(prm), ni_host)
+            extra = {"logprob": torch.empty((B, T), device=dev, dtype=torch.float32),
+                     "dead_end": torch.empty(B, device=dev, dtype=torch.int32)}
+            mprm = _L.ConstrainParams(CF, _p(follow_table), _p(extra["logprob"]), _p(extra["dead_end"]))
+            name, tail = "ff_decode_constrained", (C.byref(mprm),)
+        elif logprob:
+            name, tail, extra = "ff_decode_lp", (_p(lp),), {"logprob": lp}
+        nbytes = getattr(self._lib, name + "_workspace_bytes")(C.byref(self.model), C.byref(prm), ni_host, *size_args)
         ws = self._workspace(nbytes)
         cb_error, cb = [], None
         if stop_callback is not None and not no_stop:
@@ -585,19 +590,10 @@ class PathEngine:
         slots = (C.c_int * max(T - 1, 1))()
         prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
         args = (C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), _p(ni), ni_host,
-                _p(extra_mask), _p(predict), C.byref(steps), counts, _p(pointer), _p(tl), _p(tb), _p(ts),
-                _p(rows), _p(ws), ws.numel())
+                _p(extra_mask), _p(predict), C.byref(steps), counts, _p(pointer), _p(traced.get("logits")),
+                _p(traced.get("best")), _p(traced.get("second")), _p(rows), _p(ws), ws.numel())
         with torch.cuda.device(dev):
-            if W:
-                _L.check(self._lib.ff_decode_beam(*args, C.byref(bprm), _stream()), "ff_decode_beam")
-            elif R:
-                _L.check(self._lib.ff_decode_sample(*args, C.byref(sprm), _stream()), "ff_decode_sample")
-            elif CF is not None:
-                _L.check(self._lib.ff_decode_constrained(*args, C.byref(cprm), _stream()), "ff_decode_constrained")
-            elif logprob:
-                _L.check(self._lib.ff_decode_lp(*args, _p(lp), _stream()), "ff_decode_lp")
-            else:
-                _L.check(self._lib.ff_decode(*args, _stream()), "ff_decode")
+            _L.check(getattr(self._lib, name)(*args, *tail, _stream()), name)
         if cb_error:
             raise cb_error[0]
         sps = [int(v) for v in slots]
@@ -605,32 +601,13 @@ class PathEngine:
                "seq_of_row": rows, "slots_per_step": sps, "slot_rows": sum((s + 1) * v for s, v in enumerate(sps))}
         if return_pointer:
             out["pointer"] = pointer[: steps.value]
-        if logprob:
-            out["logprob"] = lp
-        if W:
-            out["beams"], out["beam_scores"] = beams, bscores
-            if trace:   # (the C side indexes its traces by decoded sequence, as below)
-                idx = rows.long()
-                out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
-                out["logits"], out["beam_parent"] = tl[:, idx], bparent[:, idx]
-        elif R:
-            out["samples"], out["sample_logprob"], out["sample_scores"] = samples, slp, sscores
-            if trace:   # (likewise)
-                idx = rows.long()
-                out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
-                out["logits"] = tl[:, idx]
-        elif CF is not None:
-            out["logprob"], out["dead_end"] = clp, cdead
-            if trace:   # (likewise)
-                idx = rows.long()
-                out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
-                out["logits"] = tl[:, idx]
-        elif trace:
+        out.update(extra)
+        if trace:
             # the C side indexes its traces by DECODED sequence (padding-anchor rows share one); expand to
-            # one entry per row of `predict`
+            # one entry per row of `predict` (per output row of a beam / sampled decode)
             idx = rows.long()
             out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
-            out["logits"], out["best"], out["second"] = tl[:, idx], tb[:, idx], ts[:, idx]
+            out.update((key, t[:, idx]) for key, t in traced.items())
         return out
 
     def score(self, memory, mask_u8, kv_len, variant, T, paths, lengths, F=1, trace=False,
