@@ -573,12 +573,20 @@ def test_engine_beam_scores_against_the_teacher_forced_oracle(hip_lib, name):
     log_softmax at the beam's tokens, over the steps up to the beam's terminator (or the stop step).  Bound per beam: the sum over
     those steps of 2 tol(step) + 2^-16 (tol of test_parity_golden on the oracle's logits of the step; the derivation of
     test_engine_logprob_against_the_reference_logits)."""
-    from test_parity_golden import _tol, _truth_along
     W = 4
     case, model, b = _model(name, "default")
     sd, batch = case_weights_and_batch(case)
-    T = case["model"]["seq_len"]
     out = _decode(model, case, b, beam_width=W, term_range=TERM)
+    _check_scores_against_oracle(name, case, sd, batch, out, W)
+
+
+def _check_scores_against_oracle(name, case, sd, batch, out, W, step_tol=None, what=None):
+    """The body of test_engine_beam_scores_against_the_teacher_forced_oracle for a beam decode `out`.  step_tol(pred, steps,
+    truth) -> fn(step, oracle logits of the step): the tolerance of a step along the tokens `pred` (default:
+    test_parity_golden._tol_along).  Returns the worst error / bound."""
+    from test_parity_golden import _tol_along, _truth_along
+    what = what or name
+    T = case["model"]["seq_len"]
     steps = out["steps"]
     beams = out["beams"].cpu().numpy().reshape(-1, W, T)
     got = out["beam_scores"].cpu().numpy().astype(np.float64).reshape(-1, W)
@@ -586,8 +594,10 @@ def test_engine_beam_scores_against_the_teacher_forced_oracle(hip_lib, name):
     term = (beams >= TERM[0]) & (beams < TERM[1])
     worst, checked = 0.0, 0
     for k in range(W):
-        truth, _, _ = _truth_along(name, case, sd, batch, dict(predict=np.ascontiguousarray(beams[:, k]), steps=steps))   # [steps, B, S]
-        tol = np.array([_tol(truth[s]) for s in range(steps)])
+        pred = np.ascontiguousarray(beams[:, k])
+        truth, _, _ = _truth_along(name, case, sd, batch, dict(predict=pred, steps=steps))   # [steps, B, S]
+        tol_of = (step_tol or _tol_along)(pred, steps, truth)
+        tol = np.array([tol_of(s, truth[s]) for s in range(steps)])
         for r in np.where(np.isfinite(got[:, k]))[0]:
             want, bound = 0.0, 0.0
             for j in range(1, steps + 1):
@@ -600,9 +610,10 @@ def test_engine_beam_scores_against_the_teacher_forced_oracle(hip_lib, name):
             err = abs(got[r, k] - want)
             worst = max(worst, err / bound) if bound else worst
             checked += 1
-            assert err <= bound, (name, k, int(r), got[r, k], want, bound)
-    print(name, "W=%d: %d beams, worst |score - oracle| / bound = %.3f" % (W, checked, worst))
+            assert err <= bound, (what, k, int(r), got[r, k], want, bound)
+    print(what, "W=%d: %d beams, worst |score - oracle| / bound = %.3f" % (W, checked, worst))
     assert checked > beams.shape[0]                                  # more than the best beams were compared
+    return worst
 
 
 # ---- GPU: the option off ----------------------------------------------------------------------------------------------------------

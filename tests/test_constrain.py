@@ -673,12 +673,23 @@ def test_loops_guarantee_every_ended_row_is_enclosed(hip_lib, name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ENGINE_GOLDENS)
 def test_engine_against_the_teacher_forced_oracle(hip_lib, name):
-    from test_parity_golden import _tol, _truth_along
     case, z, model, gb, sd, lat, b, edges, table = _model(name)
-    T, F = case["model"]["seq_len"], max(lat["num_input"])
     out = _with_pad(_constrained(model, case, b, LOOPS, table, trace=True), b)
+    left, pairs, _ = _check_against_oracle(name, case, sd, lat, out)
+    assert left <= CR.CAP * pairs, (name, left, pairs)
+
+
+def _check_against_oracle(name, case, sd, lat, out, step_tol=None, what=None):
+    """The body of test_engine_against_the_teacher_forced_oracle for a traced constrained decode `out` of the lattice batch
+    `lat`.  step_tol(pred, steps, truth) -> fn(step, oracle logits of the step's unfinished rows with the keys the decode masked
+    at finfo.min): the tolerance of a step along the tokens `pred` (default: test_parity_golden._tol_along).  Returns (pairs left
+    out, pairs, worst error / tolerance); the caller holds the left-out pairs against its cap."""
+    from test_parity_golden import _tol_along, _truth_along
+    what = what or name
+    T = case["model"]["seq_len"]
     pred, lp, fin, steps = _check_layout(out, T)
     truth, _, _ = _truth_along("constrain:" + name, case, sd, lat, dict(predict=pred, steps=steps))
+    tol_of = (step_tol or _tol_along)(pred, steps, truth)
     logits = out["logits"].cpu().numpy()
     pairs = left = 0
     worst = 0.0
@@ -686,22 +697,22 @@ def test_engine_against_the_teacher_forced_oracle(hip_lib, name):
         rows = np.flatnonzero(fin > j)
         if not rows.size:
             continue
-        tol = _tol(np.where(logits[j][rows] > np.float32(FILL), truth[j][rows], np.finfo(np.float32).min).astype(np.float32))
+        tol = tol_of(j, np.where(logits[j][rows] > np.float32(FILL), truth[j][rows], np.finfo(np.float32).min).astype(np.float32))
         for r in rows:
             live = logits[j, r] > np.float32(FILL)
             err = np.abs(logits[j, r][live].astype(np.float64) - truth[j, r][live])
             worst = max(worst, float(err.max()) / tol if err.size else 0.0)
-            assert (err <= tol).all(), (name, j, int(r), float(err.max()), tol)
+            assert (err <= tol).all(), (what, j, int(r), float(err.max()), tol)
             t64 = np.where(live, truth[j, r], -np.inf)
             order = np.sort(t64[live])
             margin = order[-1] - order[-2] if order.size > 1 else np.inf
             pairs += 1
             if margin > 2 * tol:
-                assert pred[r, j + 1] == int(np.argmax(t64)), (name, j, int(r))
+                assert pred[r, j + 1] == int(np.argmax(t64)), (what, j, int(r))
             else:
                 left += 1
-    print(name, "steps=%d pairs=%d left out %.2f %%; worst |logit - oracle| / tol = %.3f" % (steps, pairs, 100.0 * left / max(1, pairs), worst))
-    assert left <= CR.CAP * pairs, (name, left, pairs)
+    print(what, "steps=%d pairs=%d left out %.2f %%; worst |logit - oracle| / tol = %.3f" % (steps, pairs, 100.0 * left / max(1, pairs), worst))
+    return left, pairs, worst
 
 
 def _same_on_decisive_pairs(a, ma, c, mc, tol_of, T, what):

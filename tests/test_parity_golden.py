@@ -31,6 +31,13 @@ def _tol(ref_logits_step):
     return LOGIT_TOL * max(1.0, scale / LOGIT_SCALE)
 
 
+def _tol_along(pred, steps, truth):
+    """The step tolerances of the fp32-class engine forms along the tokens `pred`, as the mode tests' oracle checks take them:
+    fn(step, reference logits of the step) = _tol of those logits.  (tests/test_mode_forms.py hands the same checks the derived
+    tolerance of the one-fp16-product kind, which needs the tokens and the oracle's logits `truth` [steps, B, S].)"""
+    return lambda step, ref_logits_step: _tol(ref_logits_step)
+
+
 def run_traced(model, case, batch):
     """Run encode+decode through the engine with tracing; returns dict of numpy arrays."""
     from faceformer_amd.hip import lib as L

@@ -544,18 +544,29 @@ def test_engine_samples_replay_under_the_numpy_rule(hip_lib, name, params):
 def test_engine_sample_scores_against_the_teacher_forced_oracle(hip_lib, name):
     """Every sample's score against the fp64 oracle teacher-forced along that sample: bound = the sum over the sample's steps
     of 2 tol(step) + 2^-16 (DESIGN.md 13's derivation)."""
-    from test_parity_golden import _tol, _truth_along
     case, z, model, b, sd, batch = _model(name)
-    T, R = case["model"]["seq_len"], 2
+    R = 2
     out = _sampled(model, case, b, R, 1.0, 0, 1.0, _uniforms(case, b, R, 5))
+    _check_scores_against_oracle(name, case, sd, batch, out, R)
+
+
+def _check_scores_against_oracle(name, case, sd, batch, out, R, step_tol=None, what=None):
+    """The body of test_engine_sample_scores_against_the_teacher_forced_oracle for a sampled decode `out`.  step_tol(pred, steps,
+    truth) -> fn(step, oracle logits of the step): the tolerance of a step along the tokens `pred` (default:
+    test_parity_golden._tol_along).  Returns the worst error / bound."""
+    from test_parity_golden import _tol_along, _truth_along
+    what = what or name
+    T = case["model"]["seq_len"]
     smp, lp, fin, steps = _check_layout(out, T)
     smp = smp.reshape(-1, R, T)
     got = out["sample_scores"].cpu().numpy().astype(np.float64).reshape(-1, R)
     fin = fin.reshape(-1, R)
     worst = 0.0
     for k in range(R):
-        truth, _, _ = _truth_along(name, case, sd, batch, dict(predict=np.ascontiguousarray(smp[:, k]), steps=steps))
-        tol = np.array([_tol(truth[s]) for s in range(steps)])
+        pred = np.ascontiguousarray(smp[:, k])
+        truth, _, _ = _truth_along(name, case, sd, batch, dict(predict=pred, steps=steps))
+        tol_of = (step_tol or _tol_along)(pred, steps, truth)
+        tol = np.array([tol_of(s, truth[s]) for s in range(steps)])
         for r in range(smp.shape[0]):
             want, bound = 0.0, 0.0
             for j in range(1, min(int(fin[r, k]), steps) + 1):
@@ -565,8 +576,9 @@ def test_engine_sample_scores_against_the_teacher_forced_oracle(hip_lib, name):
                 bound += 2 * tol[j - 1] + SR.LP_BAR
             err = abs(got[r, k] - want)
             worst = max(worst, err / bound) if bound else worst
-            assert err <= bound, (name, k, r, got[r, k], want, bound)
-    print(name, "R=%d: worst |score - oracle| / bound = %.3f" % (R, worst))
+            assert err <= bound, (what, k, r, got[r, k], want, bound)
+    print(what, "R=%d: worst |score - oracle| / bound = %.3f" % (R, worst))
+    return worst
 
 
 def _same_on_decisive_pairs(A, dA, fin_a, c, clp, csc, c_steps, dB, T, what):
