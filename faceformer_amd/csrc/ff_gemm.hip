@@ -1444,6 +1444,7 @@ int gemm_dispatch(GemmArgs g, int batch, int tile, hipStream_t st) {
   const bool split128 = !g.A2 || (g.n_split % 128) == 0;
   if (tile == 0) tile = 7;  // stream-K kernel, launch shape by cost model (falls back by itself for K tails)
   if (tile == 5 && !split128) tile = 4;
+  if (tile == 10 && !split128) tile = 9;   // (128-column tiles straddle an n_split that is only a multiple of 64: the 128 x 64 form of the same kernel)
   const int M = g.M, N = g.N, K = g.K;
   FFProfScope prof(FF_CAT_GEMM, 2.0 * M * N * K * batch, st);
   ff_prof_add_bytes(FF_CAT_GEMM, 4.0 * batch * ((double)M * K + (double)N * K + (double)M * N * (g.res ? 2 : 1)));

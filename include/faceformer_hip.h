@@ -106,7 +106,8 @@ int ff_gelu(float* x, int ldx, int rows, int E, ff_stream_t stream);
  * K in {128, 256, 512, 1024} split over four or eight waves; 7 hands it every launch of at most 1024 rows);
  * 9 = pipelined 128x64 with 16-wide K slices (two blocks per CU; 7 hands it the plain projections of at
  * least 4096 rows whose tile count fills the resident block slots evenly), 10 = pipelined 128x128 with
- * 16-wide slices (measurement only), 11 = the LDS-DMA kernel (both operands by global_load_lds, transposed accumulators,
+ * 16-wide slices (measurement only; like 5 it needs n_split % 128 == 0 and takes its 128x64 form, 9 / 4, otherwise),
+ * 11 = the LDS-DMA kernel (both operands by global_load_lds, transposed accumulators,
  * 64 x 128 tiles at three blocks per CU, whole tiles + remaining tiles cut into K pieces; K % 32 == 0, K >= 64, N % 4 == 0,
  * leading dimensions % 4, 16-byte aligned operands; 7 hands it the launches of at least FF_DMA_MIN_ROWS rows), 12 = the same
  * kernel with 64 x 64 tiles (round 6; up to four blocks per CU).
