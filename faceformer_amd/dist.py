@@ -24,6 +24,7 @@ import os
 import torch
 
 from .hip import lib as _L
+from .hip import modes as _modes
 
 
 def shard_range(n_items, rank, world):
@@ -208,16 +209,10 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
     stop_each_eos: single-sequence model only -- None = the module's own `stop_each_eos`; True / False = this call's rule,
         passed down as an argument (the module attribute is NOT touched: other host threads may be decoding with the model)."""
     from .models import SurfaceFormer_Parallel
-    if getattr(model, "retire_finished", False):
-        raise ValueError("decode_sharded does not implement retire_finished (the batch-global stop rule counts every sequence)")
-    if getattr(model, "return_logprob", False):
-        raise ValueError("decode_sharded does not implement return_logprob (the log-probabilities are not gathered across ranks)")
-    if getattr(model, "beam_width", 0):
-        raise ValueError("decode_sharded does not implement beam_width (a beam decode takes no external stop rule)")
-    if getattr(model, "num_samples", 0):
-        raise ValueError("decode_sharded does not implement num_samples (a sampled decode takes no external stop rule)")
-    if getattr(model, "constrain", None) is not None:
-        raise ValueError("decode_sharded does not implement constrain (a constrained decode takes no external stop rule)")
+    for mode in reversed(_modes.MODES):
+        for sw in mode.switches:
+            if sw.sharded and sw.on(model):
+                raise ValueError("decode_sharded does not implement %s (%s)" % (sw.attr, sw.sharded))
     rank, world = dist_mod.get_rank(group), dist_mod.get_world_size(group)
     parallel = isinstance(model, SurfaceFormer_Parallel)
     variant = _L.FF_PARALLEL if parallel else _L.FF_SEQ2SEQ

@@ -5,6 +5,8 @@ import ctypes as C
 import torch
 
 from . import lib as _L
+from . import modes as _modes
+from .modes import CONSTRAIN_MODES, SAMPLE_MAX, constrain_flags  # noqa: F401  (importers find them here)
 from .ops import SPLIT_KINDS, _dev, _p, _stream, split_weight
 
 import operator
@@ -84,91 +86,31 @@ def fp16_operand_bounds(tensors, n_dec, E, weights=0.0):
     return worst
 
 
+# The per-mode checks as functions: calls into the table, which reads the options by decode()'s names -- these parameters' names.
 def check_beam_options(width, S, variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, term_range):
     """The combinations a beam decode rejects (ff_decode_beam's FF_ERR_ARG list), as ValueError before anything is launched."""
-    if variant != _L.FF_PARALLEL:
-        raise ValueError("beam_width is a parallel-variant option")
-    if not 1 <= width <= 8 or width > S:
-        raise ValueError("beam_width=%d: must be in 1..8 and at most S = %d" % (width, S))
-    if retire or return_pointer or no_stop or stop_callback is not None or extra_mask is not None or logprob:
-        raise ValueError("beam_width excludes retire, return_pointer, no_stop, stop_callback, extra_mask and logprob")
-    if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
-        raise ValueError("beam_width needs term_range = (lo, hi) with lo < hi")
-
-
-SAMPLE_MAX = 64
+    _modes.check_options(_modes.BEAM, variant, dict(locals(), beam_width=width), term_range)
 
 
 def check_sample_options(num_samples, temperature, top_k, top_p, variant, retire, return_pointer, no_stop, stop_callback, extra_mask,
                          logprob, beam_width, term_range):
     """The combinations a sampled decode rejects (ff_decode_sample's FF_ERR_ARG list, and the options of decode() it cannot be
     combined with), as ValueError before anything is launched."""
-    if variant != _L.FF_PARALLEL:
-        raise ValueError("num_samples is a parallel-variant option")
-    if not 1 <= num_samples <= SAMPLE_MAX:
-        raise ValueError("num_samples=%d: must be in 1..%d" % (num_samples, SAMPLE_MAX))
-    t, k, pp = float(temperature), int(top_k), float(top_p)
-    if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
-        raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]: got %r, %r, %r"
-                         % (temperature, top_k, top_p))
-    if retire or return_pointer or no_stop or stop_callback is not None or extra_mask is not None or logprob or beam_width:
-        raise ValueError("num_samples excludes retire, return_pointer, no_stop, stop_callback, extra_mask, logprob and beam_width")
-    if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
-        raise ValueError("num_samples needs term_range = (lo, hi) with lo < hi")
-
-
-CONSTRAIN_MODES = {"no_repeat": _L.FF_CONSTRAIN_NO_REPEAT, "loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT}
-
-
-def constrain_flags(constrain):
-    """The flag bits of a `constrain` value: None -> None (the option is off), "no_repeat" / "loops", or the bits themselves
-    (0..3: the C entries also take CONNECT alone, and 0, which is the plumbing's identity with the retired greedy decode)."""
-    if constrain is None:
-        return None
-    if isinstance(constrain, str):
-        if constrain not in CONSTRAIN_MODES:
-            raise ValueError("constrain=%r: must be None, 'no_repeat' or 'loops'" % (constrain,))
-        return CONSTRAIN_MODES[constrain]
-    if isinstance(constrain, bool) or not isinstance(constrain, int) or not 0 <= constrain <= 3:
-        raise ValueError("constrain=%r: must be None, 'no_repeat', 'loops' or flag bits 0..3" % (constrain,))
-    return int(constrain)
+    _modes.check_options(_modes.SAMPLE, variant, locals(), term_range)
 
 
 def check_constrain_options(flags, variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, beam_width,
                             num_samples, term_range, follow_table):
     """The combinations a constrained decode rejects (ff_decode_constrained's FF_ERR_ARG list, and the options of decode() it
     cannot be combined with), as ValueError before anything is launched."""
-    if variant != _L.FF_PARALLEL:
-        raise ValueError("constrain is a parallel-variant option")
-    if retire or return_pointer or no_stop or stop_callback is not None or extra_mask is not None or logprob or beam_width or num_samples:
-        raise ValueError("constrain excludes retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, beam_width and "
-                         "num_samples")
-    if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
-        raise ValueError("constrain needs term_range = (lo, hi) with lo < hi")
-    if flags & _L.FF_CONSTRAIN_CONNECT and follow_table is None:
-        raise ValueError("constrain='loops' needs follow_table (ops.follow_table)")
+    _modes.check_options(_modes.CONSTRAIN, variant, dict(locals(), constrain=flags), term_range)
 
 
 def check_forced_options(paths, lengths, rows, T, S, retire=False, beam_width=None, logprob=False, return_pointer=False,
                          stop_callback=None, stop_each_eos=False, extra_mask=None):
     """What a forced decode rejects (ff_decode_forced's FF_ERR_ARG list, and the options of decode() it has no argument for), as
-    ValueError before anything is launched.  Also the one pass over the paths: every token of positions 0..lengths[r] must lie
-    in [0, S) -- the C entry cannot see them and would clamp.  Returns (paths int64 [rows, T], lengths as a list)."""
-    if retire or beam_width or logprob or return_pointer or stop_callback is not None or stop_each_eos or extra_mask is not None:
-        raise ValueError("scoring given paths excludes retire, beam_width, logprob, return_pointer, stop_callback, "
-                         "stop_each_eos and extra_mask")
-    if not torch.is_tensor(paths) or paths.dtype != torch.int64 or paths.dim() != 2 or tuple(paths.shape) != (rows, T):
-        raise ValueError("paths must be an int64 tensor of shape [%d, %d]" % (rows, T))
-    lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-    if len(lens) != rows or any(not 0 <= v <= T - 1 for v in lens):
-        raise ValueError("lengths must hold %d values in 0..%d" % (rows, T - 1))
-    if rows:
-        used = torch.arange(T, device=paths.device)[None, :] <= torch.tensor(lens, device=paths.device)[:, None]
-        bad = used & ((paths < 0) | (paths >= S))
-        if bool(bad.any()):
-            r, j = [int(v) for v in bad.nonzero()[0]]
-            raise ValueError("paths[%d, %d] = %d lies outside [0, %d)" % (r, j, int(paths[r, j]), S))
-    return paths, lens
+    ValueError before anything is launched; and the one pass over the paths.  Returns (paths int64 [rows, T], lengths as a list)."""
+    return _modes.check_options(_modes.FORCED, None, locals(), None)
 
 
 class PathEngine:
@@ -428,7 +370,8 @@ class PathEngine:
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
-        tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).
+        tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
+        options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
 
         logprob=True (ff_decode_lp): also `logprob` [N*F, T] fp32, laid out like predict -- column j >= 1 is
         log_softmax(masked logits of step j-1)[predict[:, j]], 0 in column 0 and wherever predict is zero padded.  Tokens, steps
@@ -442,75 +385,50 @@ class PathEngine:
         beam_width=W >= 1 (parallel variant, ff_decode_beam; None or 0: the greedy decode above): W beams per anchor.  Also
         `beams` [N*F*W, T] int64 (row (w*F + f)*W + k is beam k of anchor f, best first, zero after the beam's finish position
         and the stop step), `beam_scores` [N*F*W] fp32 (-inf: empty beam); `predict` is beam 0; with trace=True `logits` is
-        [T-1, N*F*W, S] and `beam_parent` [T-1, N*F*W] int32, both in output-row order.  Needs term_range; excludes retire,
-        return_pointer, no_stop, stop_callback, extra_mask and logprob (ValueError).  beam_width=1 equals the retire=True decode.
+        [T-1, N*F*W, S] and `beam_parent` [T-1, N*F*W] int32, both in output-row order.  Excludes retire, return_pointer, no_stop,
+        stop_callback, extra_mask and logprob.  beam_width=1 equals the retire=True decode.
 
         num_samples=R >= 1 (parallel variant, ff_decode_sample; None or 0: the greedy decode above): R independent
         draws per anchor under temperature / top_k / top_p, driven by `uniforms` [T-1, N*F*R] fp32 on the device (step t of
         output row r reads uniforms[t, r]).  Also `samples` [N*F*R, T] int64 (row (w*F + f)*R + k is sample k of anchor f, zero
         after the sample's finish position and the stop step), `sample_logprob` (same layout, fp32: the model's log-probability
         of every drawn token) and `sample_scores` [N*F*R] (their sums); `predict` is sample 0; with trace=True `logits` is
-        [T-1, N*F*R, S] in output-row order.  Needs term_range; excludes retire, return_pointer, no_stop, stop_callback,
-        extra_mask, logprob and beam_width (ValueError).  temperature=0 equals the retire=True decode, R times.
+        [T-1, N*F*R, S] in output-row order.  Excludes those and beam_width.  temperature=0 equals the retire=True decode, R times.
 
         constrain="no_repeat" / "loops" (parallel variant, ff_decode_constrained; None: the greedy decode above; the
         flag bits 0..3 are taken too): the greedy decode over keys the enclosure filter can accept.  follow_table [N, L,
         ceil(L/32)] int32 on the device (ops.follow_table), required by "loops".  `predict` is the constrained decode (zero after
         the row's finish position and the stop step); also `logprob` [N*F, T] fp32 (under the renormalised distribution) and
-        `dead_end` [N*F] int32; with trace=True `logits` [T-1, N*F, S] holds the constrained masked rows.  Needs term_range;
-        excludes retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, beam_width and num_samples (ValueError).
-        Bits 0 equal the retire=True decode."""
-        W = int(beam_width or 0)
-        R = int(num_samples or 0)
-        CF = constrain_flags(constrain)
-        if CF is not None:
-            check_constrain_options(CF, variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, W, R, term_range,
-                                    follow_table)
-            if follow_table is not None:
-                Lt = memory.shape[1] - self.num_token
-                if (not torch.is_tensor(follow_table) or follow_table.dtype != torch.int32
-                        or tuple(follow_table.shape) != (memory.shape[0], Lt, (Lt + 31) // 32)):
-                    raise ValueError("follow_table must be an int32 tensor of shape [%d, %d, %d]" % (memory.shape[0], Lt, (Lt + 31) // 32))
-        if R:
-            check_sample_options(R, temperature, top_k, top_p, variant, retire, return_pointer, no_stop, stop_callback, extra_mask,
-                                 logprob, W, term_range)
-            rows_out = memory.shape[0] * F * R
-            if not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (max(T - 1, 1), rows_out):
-                raise ValueError("uniforms must be a float32 tensor of shape [%d, %d]" % (max(T - 1, 1), rows_out))
-        if W:
-            check_beam_options(W, memory.shape[1], variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob,
-                               term_range)
+        `dead_end` [N*F] int32; with trace=True `logits` [T-1, N*F, S] holds the constrained masked rows.  Excludes those, beam_width
+        and num_samples.  Bits 0 equal the retire=True decode."""
+        W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
+        mode, value = _modes.of_options(logprob, constrain=CF, num_samples=R, beam_width=W)      # (value None: the greedy record)
+        G = value if mode.per_anchor else 1       # sequences per anchor
+        o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
+                 logprob=logprob, beam_width=W, num_samples=R, constrain=CF, temperature=temperature, top_k=top_k, top_p=top_p,
+                 uniforms=uniforms, follow_table=follow_table, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
+                 N=memory.shape[0], S=memory.shape[1], F=F, T=T)
+        if value is not None:    # (retire, an option of the greedy record, is checked behind the operands)
+            _modes.check_options(mode, variant, o, term_range)
+            mode.operand(self, o)
         _dev(memory, "memory")
         self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
         N, S, E = memory.shape
-        L = S - self.num_token
-        prm = _L.DecodeParams()
-        prm.variant, prm.N, prm.L, prm.F, prm.T = variant, N, L, F, T
-        prm.chunk_wireframes, prm.sync_every = chunk_wireframes, sync_every
-        prm.chunk_seqs, prm.num_streams = chunk_seqs, num_streams
-        prm.chunk_max_seqs = int(chunk_max_seqs)
-        prm.ln_fuse_max_rows = int(ln_fuse_max_rows)
-        prm.flags = flags | (_L.FF_RETURN_POINTER if return_pointer else 0) | (_L.FF_NO_STOP if no_stop else 0)
+        flags |= (_L.FF_RETURN_POINTER if return_pointer else 0) | (_L.FF_NO_STOP if no_stop else 0)
         if retire:
-            if variant != _L.FF_PARALLEL:
-                raise ValueError("retire=True is a parallel-variant option")
-            if return_pointer or no_stop or stop_callback is not None:
-                raise ValueError("retire=True excludes return_pointer, no_stop and stop_callback")
-            if term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1]):
-                raise ValueError("retire=True needs term_range = (lo, hi) with lo < hi")
-            if num_input is None and staged_num_input is None:
-                raise ValueError("retire=True needs num_input")
-            prm.flags |= _L.FF_RETIRE_FINISHED
+            _modes.check_options(_modes.GREEDY, variant, o, term_range)
+            flags |= _L.FF_RETIRE_FINISHED
             if extra_mask is None:     # (retirement supersedes the padding-anchor de-duplication: both on)
-                prm.flags |= _L.FF_DEDUP_PAD_ANCHORS
-            prm.term_lo, prm.term_hi = int(term_range[0]), int(term_range[1])
-            prm.retire_min_shrink = float(retire_min_shrink)
+                flags |= _L.FF_DEDUP_PAD_ANCHORS
         if return_pointer or extra_mask is not None:   # (every padding-anchor row has its own extra-mask row)
-            prm.flags &= ~_L.FF_DEDUP_PAD_ANCHORS
-        if W or R or CF is not None:
+            flags &= ~_L.FF_DEDUP_PAD_ANCHORS
+        prm = self._params(variant, N, S, F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows, flags,
+                           x3_min_rows)
+        prm.sync_every, prm.tok_sos, prm.tok_eos = sync_every, tok_sos, tok_eos
+        if retire or value is not None:
             prm.term_lo, prm.term_hi = int(term_range[0]), int(term_range[1])
-        prm.tok_sos, prm.tok_eos = tok_sos, tok_eos
-        prm.x3_min_rows = int(x3_min_rows) if self._planes else 0
+        if retire:
+            prm.retire_min_shrink = float(retire_min_shrink)
         B = N * F
         dev = self.device
         predict = torch.empty((B, T), device=dev, dtype=torch.int64)
@@ -529,49 +447,18 @@ class PathEngine:
             _dev(extra_mask, "extra_mask", torch.uint8)
             self._same_device(extra_mask, "extra_mask")
             extra_mask = extra_mask.contiguous()
-        pointer = torch.zeros((max(T - 1, 1), B, E), device=dev, dtype=torch.float32) if return_pointer else None
-        G = W or R    # sequences per anchor of a beam / sampled decode
         steps_max = max(T - 1, 1)
+        pointer = torch.zeros((steps_max, B, E), device=dev, dtype=torch.float32) if return_pointer else None
         traced = {}   # the traces, which the C side indexes by decoded sequence
         if trace:
-            traced["logits"] = torch.full((steps_max, B * max(G, 1), S), float("nan"), device=dev, dtype=torch.float32)
-            if not (G or CF is not None):
-                traced["best"] = torch.full((steps_max, B), float("nan"), device=dev, dtype=torch.float32)
-                traced["second"] = torch.full((steps_max, B), float("nan"), device=dev, dtype=torch.float32)
-        rows = torch.empty(B * max(G, 1), device=dev, dtype=torch.int32)
-        lp = torch.empty((B, T), device=dev, dtype=torch.float32) if logprob else None
-        # per mode, once: the entry's name (its size query is <name>_workspace_bytes) with the arguments only that query and only
-        # that entry take (its parameter struct, or the log-probability output), and the mode's outputs
-        name, size_args, tail, extra = "ff_decode", (), (), {}
-        if W:
-            extra = {"beams": torch.empty((B * W, T), device=dev, dtype=torch.int64),
-                     "beam_scores": torch.empty(B * W, device=dev, dtype=torch.float32)}
-            if trace:
-                traced["beam_parent"] = torch.full((steps_max, B * W), -1, device=dev, dtype=torch.int32)
-            mprm = _L.BeamParams(W, _p(extra["beams"]), _p(extra["beam_scores"]), _p(traced.get("beam_parent")))
-            name, size_args, tail = "ff_decode_beam", (W,), (C.byref(mprm),)
-        elif R:
-            _dev(uniforms, "uniforms")
-            self._same_device(uniforms, "uniforms")
-            uniforms = uniforms.contiguous()
-            extra = {"samples": torch.empty((B * R, T), device=dev, dtype=torch.int64),
-                     "sample_logprob": torch.empty((B * R, T), device=dev, dtype=torch.float32),
-                     "sample_scores": torch.empty(B * R, device=dev, dtype=torch.float32)}
-            mprm = _L.SampleParams(R, float(temperature), int(top_k), float(top_p), _p(uniforms), _p(extra["samples"]),
-                                   _p(extra["sample_logprob"]), _p(extra["sample_scores"]))
-            name, size_args, tail = "ff_decode_sample", (R,), (C.byref(mprm),)
-        elif CF is not None:
-            if follow_table is not None:
-                _dev(follow_table, "follow_table", torch.int32)
-                self._same_device(follow_table, "follow_table")
-                follow_table = follow_table.contiguous()
-            extra = {"logprob": torch.empty((B, T), device=dev, dtype=torch.float32),
-                     "dead_end": torch.empty(B, device=dev, dtype=torch.int32)}
-            mprm = _L.ConstrainParams(CF, _p(follow_table), _p(extra["logprob"]), _p(extra["dead_end"]))
-            name, tail = "ff_decode_constrained", (C.byref(mprm),)
-        elif logprob:
-            name, tail, extra = "ff_decode_lp", (_p(lp),), {"logprob": lp}
-        nbytes = getattr(self._lib, name + "_workspace_bytes")(C.byref(self.model), C.byref(prm), ni_host, *size_args)
+            traced["logits"] = torch.full((steps_max, B * G, S), float("nan"), device=dev, dtype=torch.float32)
+            for key in mode.row_traces:
+                traced[key] = torch.full((steps_max, B), float("nan"), device=dev, dtype=torch.float32)
+        rows = torch.empty(B * G, device=dev, dtype=torch.int32)
+        # the mode's outputs, and the arguments only its entry takes (its parameter struct, or the log-probability output)
+        extra, tail = _modes.outputs(mode, self, o, B, traced)
+        nbytes = getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm), ni_host,
+                                                                      *((G,) if mode.per_anchor else ()))
         ws = self._workspace(nbytes)
         cb_error, cb = [], None
         if stop_callback is not None and not no_stop:
@@ -586,14 +473,14 @@ class PathEngine:
             cb = _L.STOP_FN(_stop)
             prm.stop_fn = C.cast(cb, C.c_void_p)
         steps = C.c_int(0)
-        counts = (C.c_int * max(T - 1, 1))()
-        slots = (C.c_int * max(T - 1, 1))()
+        counts = (C.c_int * steps_max)()
+        slots = (C.c_int * steps_max)()
         prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
         args = (C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), _p(ni), ni_host,
                 _p(extra_mask), _p(predict), C.byref(steps), counts, _p(pointer), _p(traced.get("logits")),
                 _p(traced.get("best")), _p(traced.get("second")), _p(rows), _p(ws), ws.numel())
         with torch.cuda.device(dev):
-            _L.check(getattr(self._lib, name)(*args, *tail, _stream()), name)
+            _L.check(getattr(self._lib, mode.entry)(*args, *tail, _stream()), mode.entry)
         if cb_error:
             raise cb_error[0]
         sps = [int(v) for v in slots]
@@ -609,6 +496,17 @@ class PathEngine:
             out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
             out.update((key, t[:, idx]) for key, t in traced.items())
         return out
+
+    def _params(self, variant, N, S, F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows, flags,
+                x3_min_rows):
+        """The DecodeParams every entry takes (decode() adds its stop rule's, score() has none)."""
+        prm = _L.DecodeParams()
+        prm.variant, prm.N, prm.L, prm.F, prm.T = variant, N, S - self.num_token, F, T
+        prm.chunk_wireframes, prm.chunk_seqs, prm.num_streams = chunk_wireframes, chunk_seqs, num_streams
+        prm.chunk_max_seqs, prm.ln_fuse_max_rows = int(chunk_max_seqs), int(ln_fuse_max_rows)
+        prm.flags = flags
+        prm.x3_min_rows = int(x3_min_rows) if self._planes else 0
+        return prm
 
     def score(self, memory, mask_u8, kv_len, variant, T, paths, lengths, F=1, trace=False,
               chunk_wireframes=0, chunk_seqs=0, num_streams=1, flags=DEFAULT_FLAGS, x3_min_rows=0, chunk_max_seqs=0,
@@ -636,28 +534,19 @@ class PathEngine:
         paths, lens = check_forced_options(paths, lengths, B, T, S, retire=retire, beam_width=beam_width, logprob=logprob,
                                            return_pointer=return_pointer, stop_callback=stop_callback, stop_each_eos=stop_each_eos,
                                            extra_mask=extra_mask)
-        paths = paths.contiguous()
-        prm = _L.DecodeParams()
-        prm.variant, prm.N, prm.L, prm.F, prm.T = variant, N, S - self.num_token, F, T
-        prm.chunk_wireframes, prm.chunk_seqs, prm.num_streams = chunk_wireframes, chunk_seqs, num_streams
-        prm.chunk_max_seqs, prm.ln_fuse_max_rows = int(chunk_max_seqs), int(ln_fuse_max_rows)
-        prm.flags = flags & ~_L.FF_DEDUP_PAD_ANCHORS
-        prm.x3_min_rows = int(x3_min_rows) if self._planes else 0
+        mode = _modes.FORCED
+        o = dict(paths=paths.contiguous(), T=T, lengths_host=(C.c_int * max(B, 1))(*lens))
+        prm = self._params(variant, N, S, F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows,
+                           flags & ~_L.FF_DEDUP_PAD_ANCHORS, x3_min_rows)
         dev = self.device
-        lens_host = (C.c_int * max(B, 1))(*lens)
-        lens_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
-        out = {"logprob": torch.empty((B, T), device=dev, dtype=torch.float32),
-               "greedy": torch.empty((B, T), device=dev, dtype=torch.int64),
-               "rank": torch.empty((B, T), device=dev, dtype=torch.int32),
-               "seq_logprob": torch.empty(B, device=dev, dtype=torch.float32)}
+        o["lengths_dev"] = torch.tensor(lens, dtype=torch.int32).to(dev)
+        out, tail = _modes.outputs(mode, self, o, B, None)
         tl = torch.full((max(T - 1, 1), B, S), float("nan"), device=dev, dtype=torch.float32) if trace else None
-        fprm = _L.ForcedParams(_p(paths), _p(lens_dev), C.cast(lens_host, C.POINTER(C.c_int)), _p(out["logprob"]), _p(out["greedy"]),
-                               _p(out["rank"]), _p(out["seq_logprob"]))
-        ws = self._workspace(self._lib.ff_decode_forced_workspace_bytes(C.byref(self.model), C.byref(prm)))
+        ws = self._workspace(getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm)))
         steps = C.c_int(0)
         with torch.cuda.device(dev):
-            _L.check(self._lib.ff_decode_forced(C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), C.byref(fprm),
-                                                C.byref(steps), _p(tl), _p(ws), ws.numel(), _stream()), "ff_decode_forced")
+            _L.check(getattr(self._lib, mode.entry)(C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), *tail,
+                                                    C.byref(steps), _p(tl), _p(ws), ws.numel(), _stream()), mode.entry)
         out["steps"] = steps.value
         if trace:
             out["logits"] = tl

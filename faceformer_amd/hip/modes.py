@@ -1,0 +1,216 @@
+"""The one place the Python side describes a decode mode: greedy (with its options retire and logprob), beam,
+sample, constrained, and forced (score()).  A `Mode` record holds what PathEngine.decode / score, the models, dist.decode_sharded
+and main.py need to know about a mode; `check_options` words every combination error from it.  The C side's counterpart is the
+`Mode` descriptor of ff_decode (csrc/ff_engine.hip); the per-mode entries and their parameter structs are lib.py's."""
+import collections
+import ctypes as C
+
+import torch
+
+from . import lib as _L
+from .ops import _dev, _p
+
+SAMPLE_MAX = 64
+CONSTRAIN_MODES = {"no_repeat": _L.FF_CONSTRAIN_NO_REPEAT, "loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT}
+
+
+class Switch(collections.namedtuple("Switch", "attr off sharded seq2seq scored")):
+    """A model attribute that switches a mode (or an option of the greedy mode) on: its name and `off` value, why decode_sharded /
+    the single-sequence model do not take it (None: they do), whether score() hands it to the engine (False: rejects it itself)."""
+
+    def on(self, model):
+        v = getattr(model, self.attr, self.off)
+        return v is not None if self.off is None else bool(v)      # (constrain = 0, the flag bits of no rule, is on)
+
+
+# subject        the mode as the error texts name it (beam, sample, constrain: the option of decode() that switches it on)
+# excludes       the options of decode() / score() it cannot be combined with, in the order the text lists them
+# term_range     needs term_range = (lo, hi);  parallel_only: a parallel-variant option
+# entry          the C entry (its size query is <entry>_workspace_bytes)
+# per_anchor     the option's value is G, the sequences per anchor: the size query's extra argument, the factor of the trace rows
+# row_traces     the per-row fp32 traces beside `logits` (beam's beam_parent, an int32 one, is made by its `tail`)
+# values / values_first   the mode's value check over the options `o`, and whether it runs before the exclusions or after them
+# operand        (engine, o): decode()'s shape check of the operand only this mode reads
+# own, outs, tail   see outputs(): (name, dtype) of the operand only this mode reads; the outputs as (key, dimensions, dtype) --
+#                a model publishes them as inputs["predict_" + key], viewed N x F x the dimensions; (o, the outputs' addresses,
+#                traced) -> the arguments only this entry takes
+# switches       the model attributes: [0] switches the mode on (greedy: its two options)
+# model_excludes the model-level exclusions in the words of that text;  model_checked: forward_eval runs check_options itself
+# prepare        (model, value, inputs, device, T, N, F, num_input, order) -> the keyword arguments of decode()
+Mode = collections.namedtuple(
+    "Mode", "subject excludes entry term_range parallel_only per_anchor row_traces values values_first operand own outs tail "
+            "switches model_excludes model_checked prepare",
+    defaults=(True, True, False, (), lambda *a: None, False, lambda *a: None, (), (), lambda *a: (), (), (), False, lambda *a: {}))
+
+
+def check_options(mode, variant, o, term_range):
+    """Every variant, exclusion and term_range error of a mode, with the mode's value check (`o`: the options by decode()'s
+    names), as ValueError before anything is launched.  Returns what the value check returns."""
+    if mode.parallel_only and variant != _L.FF_PARALLEL:
+        raise ValueError("%s is a parallel-variant option" % mode.subject)
+    if mode.values_first:
+        mode.values(o)
+    if any(o.get(k) is not None if k in ("stop_callback", "extra_mask") else o.get(k) for k in mode.excludes):
+        raise ValueError("%s excludes %s and %s" % (mode.subject, ", ".join(mode.excludes[:-1]), mode.excludes[-1]))
+    if mode.term_range and (term_range is None or len(term_range) != 2 or not int(term_range[0]) < int(term_range[1])):
+        raise ValueError("%s needs term_range = (lo, hi) with lo < hi" % mode.subject)
+    if not mode.values_first:
+        return mode.values(o)
+
+
+def constrain_flags(constrain):
+    """The flag bits of a `constrain` value: None -> None (the option is off), "no_repeat" / "loops", or the bits themselves
+    (0..3: the C entries also take CONNECT alone, and 0, which is the plumbing's identity with the retired greedy decode)."""
+    if constrain is None:
+        return None
+    if isinstance(constrain, str):
+        if constrain not in CONSTRAIN_MODES:
+            raise ValueError("constrain=%r: must be None, 'no_repeat' or 'loops'" % (constrain,))
+        return CONSTRAIN_MODES[constrain]
+    if isinstance(constrain, bool) or not isinstance(constrain, int) or not 0 <= constrain <= 3:
+        raise ValueError("constrain=%r: must be None, 'no_repeat', 'loops' or flag bits 0..3" % (constrain,))
+    return int(constrain)
+
+
+# ---- the value checks ------------------------------------------------------------------------------------------------------------
+def _beam_values(o):
+    if not 1 <= o["beam_width"] <= 8 or o["beam_width"] > o["S"]:
+        raise ValueError("beam_width=%d: must be in 1..8 and at most S = %d" % (o["beam_width"], o["S"]))
+
+
+def _sample_values(o):
+    if not 1 <= o["num_samples"] <= SAMPLE_MAX:
+        raise ValueError("num_samples=%d: must be in 1..%d" % (o["num_samples"], SAMPLE_MAX))
+    t, k, pp = float(o["temperature"]), int(o["top_k"]), float(o["top_p"])
+    if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
+        raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]: got %r, %r, %r"
+                         % (o["temperature"], o["top_k"], o["top_p"]))
+
+
+def _sample_operand(eng, o):
+    shape = (max(o["T"] - 1, 1), o["N"] * o["F"] * o["num_samples"])
+    u = o["uniforms"]
+    if not torch.is_tensor(u) or u.dtype != torch.float32 or tuple(u.shape) != shape:
+        raise ValueError("uniforms must be a float32 tensor of shape [%d, %d]" % shape)
+
+
+def _constrain_values(o):
+    if o["constrain"] & _L.FF_CONSTRAIN_CONNECT and o["follow_table"] is None:
+        raise ValueError("constrain='loops' needs follow_table (ops.follow_table)")
+
+
+def _constrain_operand(eng, o):
+    L = o["S"] - eng.num_token
+    shape = (o["N"], L, (L + 31) // 32)
+    ft = o["follow_table"]
+    if ft is not None and (not torch.is_tensor(ft) or ft.dtype != torch.int32 or tuple(ft.shape) != shape):
+        raise ValueError("follow_table must be an int32 tensor of shape [%d, %d, %d]" % shape)
+
+
+def _retire_values(o):
+    if o["num_input"] is None and o["staged_num_input"] is None:
+        raise ValueError("retire=True needs num_input")
+
+
+def _forced_values(o):
+    """The one pass over the paths: every token of positions 0..lengths[r] must lie in [0, S) -- the C entry cannot see them and
+    would clamp.  Returns (paths int64 [rows, T], lengths as a list)."""
+    paths, lengths, rows, T, S = o["paths"], o["lengths"], o["rows"], o["T"], o["S"]
+    if not torch.is_tensor(paths) or paths.dtype != torch.int64 or paths.dim() != 2 or tuple(paths.shape) != (rows, T):
+        raise ValueError("paths must be an int64 tensor of shape [%d, %d]" % (rows, T))
+    lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lens) != rows or any(not 0 <= v <= T - 1 for v in lens):
+        raise ValueError("lengths must hold %d values in 0..%d" % (rows, T - 1))
+    if rows:
+        used = torch.arange(T, device=paths.device)[None, :] <= torch.tensor(lens, device=paths.device)[:, None]
+        bad = used & ((paths < 0) | (paths >= S))
+        if bool(bad.any()):
+            r, j = [int(v) for v in bad.nonzero()[0]]
+            raise ValueError("paths[%d, %d] = %d lies outside [0, %d)" % (r, j, int(paths[r, j]), S))
+    return paths, lens
+
+
+# ---- the outputs -----------------------------------------------------------------------------------------------------------------
+def _beam_tail(o, ptrs, traced):
+    if o["trace"]:
+        logits = traced["logits"]
+        traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
+    return (C.byref(_L.BeamParams(o["beam_width"], *ptrs, _p(traced.get("beam_parent")))),)
+
+
+def outputs(mode, eng, o, B, traced):
+    """(the mode's outputs by key: [B * G if "G" is among the dimensions else B, T if "T" is], the arguments only its entry takes:
+    its parameter struct, or the log-probability output).  The mode's own operand is checked and made contiguous first."""
+    for name, dtype in mode.own:
+        if o[name] is not None:
+            _dev(o[name], name, dtype)
+            eng._same_device(o[name], name)
+            o[name] = o[name].contiguous()      # (`o`, which lives as long as the call, keeps a copy alive)
+    G = o[mode.subject] if mode.per_anchor else 1
+    out = {key: torch.empty((B * G if "G" in dims else B,) + ((o["T"],) if "T" in dims else ()), device=eng.device, dtype=dtype)
+           for key, dims, dtype in mode.outs}
+    return out, mode.tail(o, [t.data_ptr() for t in out.values()], traced)
+
+
+# ---- the records -----------------------------------------------------------------------------------------------------------------
+_COMMON = ("retire", "return_pointer", "no_stop", "stop_callback", "extra_mask", "logprob")
+_NO_STOP_RULE = "a %s decode takes no external stop rule"
+_F32, _I32, _I64 = torch.float32, torch.int32, torch.int64
+
+CONSTRAIN = Mode(
+    subject="constrain", excludes=_COMMON + ("beam_width", "num_samples"), entry="ff_decode_constrained", values=_constrain_values,
+    operand=_constrain_operand, own=(("follow_table", _I32),),
+    outs=(("logprob", "T", _F32), ("dead_end", "", _I32)),
+    tail=lambda o, ptrs, traced: (C.byref(_L.ConstrainParams(o["constrain"], _p(o["follow_table"]), *ptrs)),),
+    switches=(Switch("constrain", None, _NO_STOP_RULE % "constrained", "the single-sequence model emits loops of plain edges", False),),
+    model_excludes=("beam_width", "num_samples", "retire_finished", "return_logprob", "an extra mask"),
+    # (without CONNECT nothing reads the table: neither the mask nor, first being unused, the closure test)
+    prepare=lambda m, CF, inputs, dev, T, N, F, ni, order: dict(
+        constrain=CF, follow_table=m._follow_table(inputs, dev, ni, order) if CF & _L.FF_CONSTRAIN_CONNECT else None))
+
+SAMPLE = Mode(
+    subject="num_samples", excludes=_COMMON + ("beam_width",), entry="ff_decode_sample", per_anchor=True, values=_sample_values,
+    values_first=True, operand=_sample_operand, own=(("uniforms", _F32),),
+    outs=(("samples", "GT", _I64), ("sample_logprob", "GT", _F32), ("sample_scores", "G", _F32)),
+    tail=lambda o, ptrs, traced: (C.byref(_L.SampleParams(o["num_samples"], float(o["temperature"]), int(o["top_k"]),
+                                                          float(o["top_p"]), _p(o["uniforms"]), *ptrs)),),
+    switches=(Switch("num_samples", 0, _NO_STOP_RULE % "sampled", "sampling for the single-sequence model is not implemented", False),),
+    model_excludes=("beam_width", "retire_finished", "return_logprob", "an extra mask"), model_checked=True,
+    prepare=lambda m, R, inputs, dev, T, N, F, ni, order: dict(
+        num_samples=R, temperature=float(m.sample_temperature), top_k=int(m.sample_top_k), top_p=float(m.sample_top_p),
+        uniforms=m._sample_uniforms(inputs, dev, T, N, F, R, order)))
+
+BEAM = Mode(
+    subject="beam_width", excludes=_COMMON, entry="ff_decode_beam", per_anchor=True, values=_beam_values, values_first=True,
+    outs=(("beams", "GT", _I64), ("beam_scores", "G", _F32)), tail=_beam_tail,
+    switches=(Switch("beam_width", 0, _NO_STOP_RULE % "beam", None, True),),
+    prepare=lambda m, W, inputs, dev, T, N, F, ni, order: dict(beam_width=W))
+
+# greedy: the exclusions, the variant and the term_range are those of its option retire=True and are checked only with it
+GREEDY = Mode(
+    subject="retire=True", excludes=("return_pointer", "no_stop", "stop_callback"), entry="ff_decode", row_traces=("best", "second"),
+    values=_retire_values,
+    switches=(Switch("retire_finished", False, "the batch-global stop rule counts every sequence",
+                     "the single-sequence model has one sequence per wireframe", True),
+              Switch("return_logprob", False, "the log-probabilities are not gathered across ranks", None, True)))
+GREEDY_LOGPROB = GREEDY._replace(entry="ff_decode_lp", outs=(("logprob", "T", _F32),), tail=lambda o, ptrs, traced: tuple(ptrs))
+
+FORCED = Mode(
+    subject="scoring given paths", excludes=("retire", "beam_width", "logprob", "return_pointer", "stop_callback", "stop_each_eos", "extra_mask"),
+    term_range=False, parallel_only=False, entry="ff_decode_forced", values=_forced_values,
+    outs=(("logprob", "T", _F32), ("greedy", "T", _I64), ("rank", "T", _I32), ("seq_logprob", "", _F32)),
+    tail=lambda o, ptrs, traced: (C.byref(_L.ForcedParams(_p(o["paths"]), _p(o["lengths_dev"]),
+                                                          C.cast(o["lengths_host"], C.POINTER(C.c_int)), *ptrs)),))
+
+MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several mode options, the first one's record reports
+SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
+
+
+def of_options(logprob=False, **values):
+    """(record, value) of the first of MODES whose option is set in `values` (constrain: the flag bits or None; num_samples;
+    beam_width); else the greedy record (its logprob form with `logprob`) and None."""
+    for mode in MODES[:-1]:
+        v = values[mode.subject]
+        if v is not None and (v or mode is CONSTRAIN):
+            return mode, v
+    return (GREEDY_LOGPROB if logprob else GREEDY), None

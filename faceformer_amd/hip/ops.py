@@ -430,34 +430,23 @@ def beam_reorder(rows_a, parent, width, rows_b=None):
     return rows_a
 
 
-@_on_tensor_device
-def pointer_forced(logits, forced, memory=None, mask=None, kv_len=None, seqs_per_group=1, want_rows=False, want_stats=False):
-    """One teacher-forced pointer step (ff_pointer_forced, DESIGN.md 14).  logits [B, S] fp32 raw dot products (masked IN PLACE as
-    the pointer launch masks them), forced [B] int32 tokens in [0, S) (ValueError otherwise; the C entry would clamp them).  Row
-    b belongs to wireframe b // seqs_per_group of mask [W, S] / kv_len [W] / memory [W, S, E].  Returns dict(logprob [B] fp32:
-    log_softmax(masked row)[forced], saturated at -FLT_MAX; greedy [B] int32: the row's argmax, lowest index on ties; rank [B]
-    int32: keys ranked before the forced one; [rows [B, E]: memory[w, forced]]; [stats [B, E/32, 2]: their LayerNorm segment
-    statistics])."""
-    _dev(logits, "logits"), _dev(forced, "forced", torch.int32)
+def _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out):
+    """The operands the pointer-step ops share (pointer_forced / pointer_sample / pointer_constrained): logits [B, S] with unit
+    inner stride; row b belongs to wireframe b // seqs_per_group of mask [W, S] / kv_len [W] / memory [W, S, E]; `rows` [B, E]
+    and `stats` [B, E/32, 2] are made on request and put into `out`, which the caller appends to its own outputs.  Returns (B, S, spg, nw, E, rows, stats)."""
+    _dev(logits, "logits")
     if logits.dim() != 2 or logits.stride(1) != 1:
         raise ValueError("logits must be a 2-D tensor with unit inner stride")
     B, S = logits.shape
-    if forced.dim() != 1 or forced.numel() != B:
-        raise ValueError("forced must hold one token per row of logits")
-    if B and (int(forced.min()) < 0 or int(forced.max()) >= S):
-        raise ValueError("forced tokens must lie in [0, %d)" % S)
     spg = int(seqs_per_group)
     if spg < 1:
         raise ValueError("seqs_per_group must be positive")
     nw = (B + spg - 1) // spg
-    dev = logits.device
     for t, name, dt in ((mask, "mask", torch.uint8), (kv_len, "kv_len", torch.int32)):
         if t is not None:
             _dev(t, name, dt)
             if not t.is_contiguous() or t.size(0) < nw or (name == "mask" and (t.dim() != 2 or t.size(1) != S)):
                 raise ValueError("%s must be contiguous and cover %d wireframes of %d keys" % (name, nw, S))
-    out = {"logprob": torch.empty(B, device=dev, dtype=torch.float32), "greedy": torch.empty(B, device=dev, dtype=torch.int32),
-           "rank": torch.empty(B, device=dev, dtype=torch.int32)}
     rows, stats, E = None, None, 0
     if memory is not None:
         _dev(memory, "memory")
@@ -467,11 +456,32 @@ def pointer_forced(logits, forced, memory=None, mask=None, kv_len=None, seqs_per
     if want_rows or want_stats:
         if memory is None:
             raise ValueError("rows / stats need memory")
-        rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
+        rows = out["rows"] = torch.empty((B, E), device=logits.device, dtype=torch.float32)
         if want_stats:
             if E % 32:
                 raise ValueError("stats need E % 32 == 0")
-            stats = out["stats"] = torch.empty((B, E // 32, 2), device=dev, dtype=torch.float32)
+            stats = out["stats"] = torch.empty((B, E // 32, 2), device=logits.device, dtype=torch.float32)
+    return B, S, spg, nw, E, rows, stats
+
+
+@_on_tensor_device
+def pointer_forced(logits, forced, memory=None, mask=None, kv_len=None, seqs_per_group=1, want_rows=False, want_stats=False):
+    """One teacher-forced pointer step (ff_pointer_forced, DESIGN.md 14).  logits [B, S] fp32 raw dot products (masked IN PLACE as
+    the pointer launch masks them), forced [B] int32 tokens in [0, S) (ValueError otherwise; the C entry would clamp them).  Row
+    b belongs to wireframe b // seqs_per_group of mask [W, S] / kv_len [W] / memory [W, S, E].  Returns dict(logprob [B] fp32:
+    log_softmax(masked row)[forced], saturated at -FLT_MAX; greedy [B] int32: the row's argmax, lowest index on ties; rank [B]
+    int32: keys ranked before the forced one; [rows [B, E]: memory[w, forced]]; [stats [B, E/32, 2]: their LayerNorm segment
+    statistics])."""
+    _dev(logits, "logits"), _dev(forced, "forced", torch.int32)
+    out = {}
+    B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
+    if forced.dim() != 1 or forced.numel() != B:
+        raise ValueError("forced must hold one token per row of logits")
+    if B and (int(forced.min()) < 0 or int(forced.max()) >= S):
+        raise ValueError("forced tokens must lie in [0, %d)" % S)
+    dev = logits.device
+    out = dict({"logprob": torch.empty(B, device=dev, dtype=torch.float32), "greedy": torch.empty(B, device=dev, dtype=torch.int32),
+                "rank": torch.empty(B, device=dev, dtype=torch.int32)}, **out)
     _L.check(_L.load().ff_pointer_forced(
         _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(forced.contiguous()), _p(out["logprob"]),
         _p(out["greedy"]), _p(out["rank"]), _p(memory), E, _p(rows), E, _p(stats), _stream()), "ff_pointer_forced")
@@ -488,9 +498,8 @@ def pointer_sample(logits, uniforms, temperature=1.0, top_k=0, top_p=1.0, row_id
     memory [W, S, E].  Returns dict(next [B] int32: the drawn tokens; logprob [B] fp32: log_softmax(masked row)[next] under the
     model, saturated at -FLT_MAX; fin [B] int32; [rows [B, E]: memory[w, next]]; [stats [B, E/32, 2]])."""
     _dev(logits, "logits"), _dev(uniforms, "uniforms")
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise ValueError("logits must be a 2-D tensor with unit inner stride")
-    B, S = logits.shape
+    out = {}
+    B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
     if uniforms.dim() != 1 or not uniforms.is_contiguous() or uniforms.numel() < 1:
         raise ValueError("uniforms must be a contiguous non-empty 1-D tensor")
     U = uniforms.numel()
@@ -509,32 +518,9 @@ def pointer_sample(logits, uniforms, temperature=1.0, top_k=0, top_p=1.0, row_id
         if fin.dim() != 1 or fin.numel() != B:
             raise ValueError("fin must hold one flag per row of logits")
         fin = fin.contiguous()
-    spg = int(seqs_per_group)
-    if spg < 1:
-        raise ValueError("seqs_per_group must be positive")
-    nw = (B + spg - 1) // spg
     dev = logits.device
-    for x, name, dt in ((mask, "mask", torch.uint8), (kv_len, "kv_len", torch.int32)):
-        if x is not None:
-            _dev(x, name, dt)
-            if not x.is_contiguous() or x.size(0) < nw or (name == "mask" and (x.dim() != 2 or x.size(1) != S)):
-                raise ValueError("%s must be contiguous and cover %d wireframes of %d keys" % (name, nw, S))
-    out = {"next": torch.empty(B, device=dev, dtype=torch.int32), "logprob": torch.empty(B, device=dev, dtype=torch.float32),
-           "fin": torch.empty(B, device=dev, dtype=torch.int32)}
-    rows, stats, E = None, None, 0
-    if memory is not None:
-        _dev(memory, "memory")
-        if memory.dim() != 3 or not memory.is_contiguous() or memory.size(1) != S or memory.size(0) < nw:
-            raise ValueError("memory must be a contiguous [>= %d, %d, E] tensor" % (nw, S))
-        E = memory.size(2)
-    if want_rows or want_stats:
-        if memory is None:
-            raise ValueError("rows / stats need memory")
-        rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
-        if want_stats:
-            if E % 32:
-                raise ValueError("stats need E % 32 == 0")
-            stats = out["stats"] = torch.empty((B, E // 32, 2), device=dev, dtype=torch.float32)
+    out = dict({"next": torch.empty(B, device=dev, dtype=torch.int32), "logprob": torch.empty(B, device=dev, dtype=torch.float32),
+                "fin": torch.empty(B, device=dev, dtype=torch.int32)}, **out)
     if counter is not None:
         _dev(counter, "counter", torch.int32)
     _L.check(_L.load().ff_pointer_sample(
@@ -574,9 +560,8 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
     dead_end, first, prev [B] int32; logprob [B] fp32; visited; mask_rows [B, S] uint8: the rule's own mask of every unfinished
     row; [rows [B, E]]; [stats [B, E/32, 2]])."""
     _dev(logits, "logits")
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise ValueError("logits must be a 2-D tensor with unit inner stride")
-    B, S = logits.shape
+    out = {}
+    B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
     flags, ntok = int(flags), int(ntok)
     L = S - ntok
     fw = (L + 31) // 32
@@ -587,10 +572,6 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
         raise ValueError("need 0 <= term_lo < term_hi <= ntok <= S")
     if follows is None and flags & _L.FF_CONSTRAIN_CONNECT:
         raise ValueError("FF_CONSTRAIN_CONNECT needs the follow table")
-    spg = int(seqs_per_group)
-    if spg < 1:
-        raise ValueError("seqs_per_group must be positive")
-    nw = (B + spg - 1) // spg
     for x, name in ((fin, "fin"), (first, "first"), (prev, "prev")):
         _dev(x, name, torch.int32)
         if x.dim() != 1 or x.numel() != B:
@@ -605,28 +586,9 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
         if follows.dim() != 3 or not follows.is_contiguous() or follows.size(0) < nw or tuple(follows.shape[1:]) != (L, fw):
             raise ValueError("follows must be a contiguous [>= %d, %d, %d] tensor" % (nw, L, fw))
     dev = logits.device
-    for x, name, dt in ((mask, "mask", torch.uint8), (kv_len, "kv_len", torch.int32)):
-        if x is not None:
-            _dev(x, name, dt)
-            if not x.is_contiguous() or x.size(0) < nw or (name == "mask" and (x.dim() != 2 or x.size(1) != S)):
-                raise ValueError("%s must be contiguous and cover %d wireframes of %d keys" % (name, nw, S))
     i32 = lambda: torch.empty(B, device=dev, dtype=torch.int32)
-    out = {"next": i32(), "logprob": torch.empty(B, device=dev, dtype=torch.float32), "fin": i32(), "dead_end": i32(),
-           "first": i32(), "prev": i32(), "visited": visited, "mask_rows": torch.zeros((B, S), device=dev, dtype=torch.uint8)}
-    rows, stats, E = None, None, 0
-    if memory is not None:
-        _dev(memory, "memory")
-        if memory.dim() != 3 or not memory.is_contiguous() or memory.size(1) != S or memory.size(0) < nw:
-            raise ValueError("memory must be a contiguous [>= %d, %d, E] tensor" % (nw, S))
-        E = memory.size(2)
-    if want_rows or want_stats:
-        if memory is None:
-            raise ValueError("rows / stats need memory")
-        rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
-        if want_stats:
-            if E % 32:
-                raise ValueError("stats need E % 32 == 0")
-            stats = out["stats"] = torch.empty((B, E // 32, 2), device=dev, dtype=torch.float32)
+    out = dict({"next": i32(), "logprob": torch.empty(B, device=dev, dtype=torch.float32), "fin": i32(), "dead_end": i32(),
+                "first": i32(), "prev": i32(), "visited": visited, "mask_rows": torch.zeros((B, S), device=dev, dtype=torch.uint8)}, **out)
     if counter is not None:
         _dev(counter, "counter", torch.int32)
     # (L = 0: no edge key, nothing of the table or the visited words is read -- one word each so that the pointers are not null)

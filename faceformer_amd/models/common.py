@@ -5,6 +5,7 @@ import torch.nn as nn
 
 from ..embedding import PositionEmbeddingLearned, VanillaEmedding
 from ..hip import lib as _L
+from ..hip import modes as _modes
 from ..hip import ops
 from ..hip.engine import DEFAULT_FLAGS, PathEngine
 from ..transformer import (HipLinear, TransformerDecoder, TransformerDecoderLayer, TransformerEncoder,
@@ -59,28 +60,18 @@ class SurfaceFormerBase(nn.Module):
                                        # (the queue never drains: free at every step, tools/run_sync_probe.sh); a decode
                                        # that stops at step s executes s + k ... s + 2k - 1 steps
         self.sharded_sync_every = 2    # ... period of the batch-global rule in dist.decode_sharded (a host all-reduce per check)
+        # The opt-in decode modes and options (SurfaceFormer_Parallel.forward_eval's docstring says what each adds; hip/modes.py
+        # holds what each excludes and where it is not taken: dist.decode_sharded, the single-sequence model, score() -- ValueError)
         self.retire_finished = False   # parallel model: a face loop stops being decoded once it has produced its face-type token;
-                                       # `predict` is then faces.retired_view of the reference's (same faces: DESIGN.md 10).
-                                       # Not with dist.decode_sharded or the single-sequence model (ValueError)
+                                       # `predict` is then faces.retired_view of the reference's (same faces: DESIGN.md 10)
         self.return_logprob = False    # forward_eval also returns inputs["predict_logprob"], shaped like inputs["predict"]: the
                                        # log-probability log_softmax(masked logits)[token] of every greedy selection, 0 at the
-                                       # start token and wherever predict is zero padded.  Not with dist.decode_sharded
+                                       # start token and wherever predict is zero padded
         self.last_score_stats = None   # score(): {"rows", "steps"} of the last call
-        self.beam_width = 0            # parallel model: >= 1 decodes with this many beams per anchor (beam search):
-                                       # forward_eval adds predict_beams / predict_beam_scores, predict is beam 0.  0 = greedy.
-                                       # Not with retire_finished, return_logprob, an extra mask, dist.decode_sharded or the
-                                       # single-sequence model (ValueError)
-        self.num_samples = 0           # parallel model: R >= 1 (at most 64) decodes R independent DRAWS per anchor (temperature /
-                                       # top-k / top-p sampling): forward_eval adds predict_samples,
-                                       # predict_sample_logprob (N x F x R x T) and predict_sample_scores (N x F x R); predict is
-                                       # sample 0, a fair draw.  0 = greedy.  Not with retire_finished, beam_width, return_logprob,
-                                       # an extra mask, score(), dist.decode_sharded or the single-sequence model (ValueError)
-        self.constrain = None          # parallel model: "no_repeat" or "loops" decodes greedily over the keys the harness's
-                                       # enclosure filter can accept: no edge twice / only an edge that starts
-                                       # where the last one ended while a loop is open; forward_eval adds predict_logprob
-                                       # (N x F x T, under the renormalised distribution) and predict_dead_end (N x F).  None =
-                                       # greedy.  Not with retire_finished, beam_width, num_samples, return_logprob, an extra
-                                       # mask, score(), dist.decode_sharded or the single-sequence model (ValueError)
+        self.beam_width = 0            # parallel model: >= 1 = beam search with this many beams per anchor; 0 = greedy
+        self.num_samples = 0           # parallel model: R >= 1 (at most 64) independent DRAWS per anchor; 0 = greedy
+        self.constrain = None          # parallel model: "no_repeat" / "loops", the greedy decode over the keys the harness's
+                                       # enclosure filter can accept; None = greedy
         self.constrain_tol = 2e-4      # ... two end points coincide below this distance in x and in y (the harness's
                                        # post_process.enclosedness_tol); inputs["follow_table"] overrides the built table
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
@@ -281,16 +272,42 @@ class SurfaceFormerBase(nn.Module):
         pad = torch.zeros((extra.size(0), self.num_token), dtype=torch.bool, device=extra.device)
         return torch.cat([pad, extra.to(torch.bool)], dim=1).to(torch.uint8).contiguous()
 
+    def _decode_mode(self, inputs, parallel):
+        """(record, value) of the mode this model's attributes select (hip/modes.py: the first of MODES switched on; value: beam
+        width / number of samples / constraint flag bits, None for greedy), after the rules only the model can check: what the
+        single-sequence model does not take; an opt-in mode needs the native engine and excludes what its record lists."""
+        if not parallel:
+            for mode in reversed(_modes.MODES):
+                for sw in mode.switches:
+                    if sw.seq2seq and sw.on(self):
+                        raise ValueError("%s is a SurfaceFormer_Parallel option (%s)" % (sw.attr, sw.seq2seq))
+            return (_modes.GREEDY_LOGPROB if getattr(self, "return_logprob", False) else _modes.GREEDY), None
+        mode, value = _modes.of_options(getattr(self, "return_logprob", False),
+                                        constrain=_modes.constrain_flags(getattr(self, "constrain", None)),
+                                        num_samples=int(getattr(self, "num_samples", 0) or 0), beam_width=int(getattr(self, "beam_width", 0) or 0))
+        if value is not None:
+            attr = mode.switches[0].attr
+            if not self.engine_supported():
+                raise ValueError("%s needs the native engine: this model's constructor arguments take the sub-module loop" % attr)
+            if any(inputs.get("extra_mask") is not None if word == "an extra mask" else _modes.SWITCH[word].on(self)
+                   for word in mode.model_excludes):
+                raise ValueError("%s excludes %s and %s" % (attr, ", ".join(mode.model_excludes[:-1]), mode.model_excludes[-1]))
+            if mode.model_checked:
+                _modes.check_options(mode, _L.FF_PARALLEL, dict(num_samples=value, temperature=self.sample_temperature,
+                                                               top_k=self.sample_top_k, top_p=self.sample_top_p),
+                                     (int(self.token.face_type_offset), int(self.token.len)))
+        return mode, value
+
     def _score(self, inputs, variant, T, F, paths, lengths):
         """Teacher-forced scoring of `paths` (PathEngine.score) with this model's decode options; adds the score_*
         keys to `inputs`.  The wireframes are scored in batch order: a forced decode has no padding-anchor de-duplication, so
         every wireframe is F rows wide whatever its edge count -- the micro-batches forward_eval gets by sorting are the ones
         this plan has already -- and there is no sort_by_edges permutation to undo.  stop_each_eos (seq2seq) is a rule of the
         greedy decode and is not looked at: a forced decode has no stop rule."""
-        if int(getattr(self, "num_samples", 0) or 0):
-            raise ValueError("score() excludes num_samples: set model.num_samples = 0 to score given paths")
-        if getattr(self, "constrain", None) is not None:
-            raise ValueError("score() excludes constrain: set model.constrain = None to score given paths")
+        for mode in reversed(_modes.MODES):
+            for sw in mode.switches:
+                if not sw.scored and sw.on(self):
+                    raise ValueError("score() excludes %s: set model.%s = %r to score given paths" % (sw.attr, sw.attr, sw.off))
         if not self.engine_supported():
             raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
         eng, memory, mask, kv_len = self._encode(inputs)
@@ -302,10 +319,8 @@ class SurfaceFormerBase(nn.Module):
                         logprob=bool(getattr(self, "return_logprob", False)), extra_mask=inputs.get("extra_mask"))
         N = memory.size(0)
         shape = (N, F, T) if variant == _L.FF_PARALLEL else (N, T)
-        inputs["score_logprob"] = out["logprob"].view(shape)
-        inputs["score_greedy"] = out["greedy"].view(shape)
-        inputs["score_rank"] = out["rank"].view(shape)
-        inputs["score_seq_logprob"] = out["seq_logprob"].view(shape[:-1])
+        for key, dims, _ in _modes.FORCED.outs:
+            inputs["score_" + key] = out[key].view(shape if dims else shape[:-1])
         self.last_score_stats = {"rows": out["logprob"].size(0), "steps": out["steps"]}
         return inputs
 

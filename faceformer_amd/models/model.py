@@ -41,12 +41,7 @@ class SurfaceFormer(SurfaceFormerBase):
         Adds predict N x T (int64), embedding N x S x E, pointer N x t_last x E."""
         label = inputs["label"]
         T = self.num_labels
-        if getattr(self, "retire_finished", False):
-            raise ValueError("retire_finished is a SurfaceFormer_Parallel option (the single-sequence model has one sequence per wireframe)")
-        if int(getattr(self, "num_samples", 0) or 0):
-            raise ValueError("num_samples is a SurfaceFormer_Parallel option (sampling for the single-sequence model is not implemented)")
-        if getattr(self, "constrain", None) is not None:
-            raise ValueError("constrain is a SurfaceFormer_Parallel option (the single-sequence model emits loops of plain edges)")
+        self._decode_mode(inputs, parallel=False)       # (the records' reasons: hip/modes.py)
         if inputs["input"].size(0) == 0:     # an empty batch: the reference's loop stops after its first step (0 EOS == batch size 0, model.py:207)
             dev, S = inputs["input"].device, inputs["input"].size(1) + self.num_token
             inputs["embedding"] = torch.zeros((0, S, self.num_model), device=dev)

@@ -14,7 +14,6 @@ import numpy as _np
 import torch
 
 from .. import faces as _faces
-from ..hip import engine as _engine
 from ..hip import lib as _L
 from .common import SurfaceFormerBase
 
@@ -53,23 +52,7 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         (bool N x L x L, or the packed int32 words N x L x ceil(L/32)), for the batch AS GIVEN."""
         label = inputs["label"]
         T = self.max_face_length
-        W = int(getattr(self, "beam_width", 0) or 0)
-        R = int(getattr(self, "num_samples", 0) or 0)
-        CF = _engine.constrain_flags(getattr(self, "constrain", None))
-        if CF is not None:
-            if not self.engine_supported():
-                raise ValueError("constrain needs the native engine: this model's constructor arguments take the sub-module loop")
-            if W or R or self.retire_finished or getattr(self, "return_logprob", False) or inputs.get("extra_mask") is not None:
-                raise ValueError("constrain excludes beam_width, num_samples, retire_finished, return_logprob and an extra mask")
-        if R:
-            if not self.engine_supported():
-                raise ValueError("num_samples needs the native engine: this model's constructor arguments take the sub-module loop")
-            if W or self.retire_finished or getattr(self, "return_logprob", False) or inputs.get("extra_mask") is not None:
-                raise ValueError("num_samples excludes beam_width, retire_finished, return_logprob and an extra mask")
-            _engine.check_sample_options(R, self.sample_temperature, self.sample_top_k, self.sample_top_p, _L.FF_PARALLEL, False, False,
-                                         False, None, None, False, 0, (int(self.token.face_type_offset), int(self.token.len)))
-        if W and not self.engine_supported():
-            raise ValueError("beam_width needs the native engine: this model's constructor arguments take the sub-module loop")
+        mode, value = self._decode_mode(inputs, parallel=True)
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             inputs = self._forward_eval_modules(inputs, parallel=True)
             if self.retire_finished:         # (that loop decodes every sequence; the result is the same function of its tokens)
@@ -93,68 +76,35 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         want_lp = bool(getattr(self, "return_logprob", False))
         # Ragged batch: decode the wireframes sorted by edge count so that a micro-batch holds wireframes of
         # (nearly) the same width; wireframes are independent, the result rows are put back in batch order.
-        order = None
+        order, sub, ni = None, inputs, num_input
         if self.sort_by_edges and extra is None and len(set(num_input)) > 1:
             order = sorted(range(N), key=lambda i: -num_input[i])
             idx = torch.tensor(order, device=inputs["input"].device)
             sub = {"input": inputs["input"].index_select(0, idx), "input_mask": inputs["input_mask"].index_select(0, idx)}
             ni = [num_input[i] for i in order]
-            eng = self.engine()
-            staged = eng.stage_num_input(ni)       # (before the encoder is enqueued: see stage_num_input)
-            eng, memory, mask, kv_len = self._encode(sub, eng)
-        else:
-            ni = num_input
-            eng = self.engine()
-            staged = eng.stage_num_input(ni)
-            eng, memory, mask, kv_len = self._encode(inputs, eng)
-        skw = {}
-        if R:
-            skw = dict(num_samples=R, temperature=float(self.sample_temperature), top_k=int(self.sample_top_k),
-                       top_p=float(self.sample_top_p), uniforms=self._sample_uniforms(inputs, memory.device, T, N, F, R, order))
-        if CF is not None:
-            # (without CONNECT nothing reads the table: neither the mask nor, first being unused, the closure test)
-            table = self._follow_table(inputs, memory.device, num_input, order) if CF & _L.FF_CONSTRAIN_CONNECT else None
-            skw = dict(constrain=CF, follow_table=table)
+        eng = self.engine()
+        staged = eng.stage_num_input(ni)       # (before the encoder is enqueued: see stage_num_input)
+        eng, memory, mask, kv_len = self._encode(sub, eng)
         out = eng.decode(memory, mask, kv_len, _L.FF_PARALLEL, T=T, F=F, num_input=ni, staged_num_input=staged,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs,
                          num_streams=self.num_streams, sync_every=self.sync_every,
                          flags=self.decode_flags, x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, extra_mask=extra,
                          retire=self.retire_finished, term_range=(int(self.token.face_type_offset), int(self.token.len)),
-                         logprob=want_lp, beam_width=W or None, **skw)
-        pred = out["predict"].view(N, F, T)
-        smp = (out["samples"].view(N, F, R, T), out["sample_logprob"].view(N, F, R, T), out["sample_scores"].view(N, F, R)) if R else None
-        lp = out["logprob"].view(N, F, T) if (want_lp or CF is not None) else None
-        dead = out["dead_end"].view(N, F) if CF is not None else None
-        beams = out["beams"].view(N, F, W, T) if W else None
-        bscores = out["beam_scores"].view(N, F, W) if W else None
+                         logprob=want_lp, **mode.prepare(self, value, inputs, memory.device, T, N, F, num_input, order))
+        # predict and the mode's outputs (predict is beam 0 / sample 0 of every anchor: a fair draw, not a selected one), N x F x ...
+        G = value if mode.per_anchor else 1
+        views = [("predict", out["predict"].view(N, F, T))]
+        views += [("predict_" + key, out[key].view((N, F) + tuple({"G": G, "T": T}[d] for d in dims))) for key, dims, _ in mode.outs]
         if order is not None:
-            inv = torch.empty(N, dtype=torch.long, device=pred.device)
-            inv[torch.tensor(order, device=pred.device)] = torch.arange(N, device=pred.device)
-            pred = pred.index_select(0, inv)
-            lp = lp.index_select(0, inv) if lp is not None else None
-            dead = dead.index_select(0, inv) if dead is not None else None
-            if W:
-                beams, bscores = beams.index_select(0, inv), bscores.index_select(0, inv)
-            if R:
-                smp = tuple(t.index_select(0, inv) for t in smp)
-        inputs["predict"] = pred
-        if R:   # (predict is sample 0 of every anchor: a fair draw, not a selected one)
-            inputs["predict_samples"], inputs["predict_sample_logprob"], inputs["predict_sample_scores"] = smp
-        if W:   # (predict is beam 0 of every anchor)
-            inputs["predict_beams"], inputs["predict_beam_scores"] = beams, bscores
-        if want_lp:
-            inputs["predict_logprob"] = lp
-        if CF is not None:
-            inputs["predict_logprob"], inputs["predict_dead_end"] = lp, dead
-        self.last_decode_stats = {"decoded_seqs": sum(min(F, n + 1) for n in num_input), "rows": N * F,
+            inv = torch.empty(N, dtype=torch.long, device=memory.device)
+            inv[torch.tensor(order, device=memory.device)] = torch.arange(N, device=memory.device)
+            views = [(key, t.index_select(0, inv)) for key, t in views]
+        inputs.update(views)
+        self.last_decode_stats = {"decoded_seqs": G * sum(min(F, n + 1) for n in num_input), "rows": N * F,
                                   "slot_rows": out["slot_rows"], "steps": out["steps"]}
-        if W:   # (W sequences per decoded anchor; `rows` stays the reference's N * F)
-            self.last_decode_stats["decoded_seqs"] *= W
-            self.last_decode_stats["beam_width"] = W
-        if R:
-            self.last_decode_stats["decoded_seqs"] *= R
-            self.last_decode_stats["num_samples"] = R
+        if mode.per_anchor:   # (G sequences per decoded anchor; `rows` stays the reference's N * F)
+            self.last_decode_stats[mode.switches[0].attr] = G
         return inputs
 
     def _follow_table(self, inputs, device, num_input, order):

@@ -47,33 +47,52 @@ def decode_batch(model, batch):
         return model(batch)["predict"].cpu().numpy()
 
 
-def decode_batch_scored(model, batch):
-    """(`predict`, `predict_logprob`) of `model(batch)` as numpy arrays (--scores: the model's return_logprob is set)."""
+# The decode flags of run_test, in the order their rejections report: (run_test parameter, CLI name, SurfaceFormer_Parallel only,
+# the parameters it does not combine with in the order the message lists them, the values it takes (None: any), the text behind
+# the name when multi-rank runs do not take it (else None), what a record gains: (record_of parameter, the model's output keys))
+CLI_FLAGS = (
+    ("constrain", "--constrain", True, ("retire_finished", "scores", "beam", "sample", "score_labels"), ("no_repeat", "loops"), "",
+     ("dead_end", ("predict_dead_end",))),
+    ("sample", "--sample", True, ("retire_finished", "scores", "beam", "score_labels"), None, " (num_samples)",
+     ("samples", ("predict_samples", "predict_sample_scores"))),
+    ("score_labels", "--score-labels", False, ("retire_finished", "scores", "beam"), None, " (score)", None),
+    ("beam", "--beam", True, ("retire_finished", "scores"), None, " (beam_width)", ("beams", ("predict_beams", "predict_beam_scores"))),
+    ("retire_finished", "--retire-finished", True, (), None, None, None),
+    ("scores", "--scores", False, (), None, " (return_logprob)", ("logprob", ("predict_logprob",))),
+)
+NOT_GATHERED = {"score_labels": ": the scores are not gathered across ranks", "scores": ": the log-probabilities are not gathered across ranks"}
+
+
+def check_cli_flags(given, model_class, world):
+    """run_test's rejections, one pass over CLI_FLAGS (`given`: the flags by run_test's parameter names)."""
+    cli = {flag: name for flag, name, *_ in CLI_FLAGS}
+    for flag, name, parallel_only, excludes, choices, multi, _ in CLI_FLAGS:
+        if not given[flag]:
+            continue
+        others = [cli[f] for f in excludes]
+        together = ", ".join(others[:-1]) + " or " + others[-1] if others else ""
+        if parallel_only and (model_class != "SurfaceFormer_Parallel" or any(given[f] for f in excludes)):
+            raise ValueError("%s applies to SurfaceFormer_Parallel only%s" % (name, ", and not together with " + together if others else ""))
+        if any(given[f] for f in excludes):      # (--score-labels, the one flag of both models that excludes others)
+            raise ValueError("%s does not combine with %s (a forced decode excludes them)" % (name, together))
+        if choices and given[flag] not in choices:
+            raise ValueError("%s must be %s" % (name, " or ".join(repr(c) for c in choices)))
+        if multi is not None and world > 1:
+            raise ValueError("%s%s is not implemented for multi-rank runs%s" % (name, multi, NOT_GATHERED.get(flag, "")))
+
+
+def decode_batch_with(model, batch, wanted):
+    """(`predict`, {record_of parameter: one entry per sample}) of `model(batch)` as numpy arrays; `wanted`: the
+    (record_of parameter, output keys) of CLI_FLAGS whose flag is set -- several keys come as one tuple per sample."""
+    if not wanted:
+        return decode_batch(model, batch), {}
     with torch.no_grad():
         out = model(batch)
-    return out["predict"].cpu().numpy(), out["predict_logprob"].cpu().numpy()
-
-
-def decode_batch_beams(model, batch):
-    """(`predict`, `predict_beams`, `predict_beam_scores`) of `model(batch)` as numpy arrays (--beam: the model's beam_width is set)."""
-    with torch.no_grad():
-        out = model(batch)
-    return out["predict"].cpu().numpy(), out["predict_beams"].cpu().numpy(), out["predict_beam_scores"].cpu().numpy()
-
-
-def decode_batch_samples(model, batch):
-    """(`predict`, `predict_samples`, `predict_sample_scores`) of `model(batch)` as numpy arrays (--sample: the model's
-    num_samples is set)."""
-    with torch.no_grad():
-        out = model(batch)
-    return out["predict"].cpu().numpy(), out["predict_samples"].cpu().numpy(), out["predict_sample_scores"].cpu().numpy()
-
-
-def decode_batch_constrained(model, batch):
-    """(`predict`, `predict_dead_end`) of `model(batch)` as numpy arrays (--constrain: the model's constrain is set)."""
-    with torch.no_grad():
-        out = model(batch)
-    return out["predict"].cpu().numpy(), out["predict_dead_end"].cpu().numpy()
+    extras = {}
+    for param, keys in wanted:
+        arrays = [out[k].cpu().numpy() for k in keys]
+        extras[param] = arrays[0] if len(arrays) == 1 else list(zip(*arrays))
+    return out["predict"].cpu().numpy(), extras
 
 
 def score_batch(model, batch):
@@ -193,44 +212,12 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
-    retire_finished: the parallel model stops decoding a face loop once it has ended (models/common.py retire_finished).
-    fp16: the decoder's large projections and its cross-attention take one fp16 product each (split_kind "fp16").
-    scores: every record gains `pred_face_scores` (record_of); single-process runs only.
-    beam: beam search with this many beams per anchor (parallel model, single process, not with retire_finished / scores):
-    every record gains `pred_beam_faces` / `pred_beam_face_scores`.
-    score_labels: every record gains `label_logprob` / `label_nll` / `label_tf_accuracy`, the model's teacher-forced scores of
-    the sample's own label rows (models' score()); single process, not with retire_finished / scores / beam.
-    sample: this many draws per anchor under temperature / top_k / top_p, uniforms from a generator seeded with `seed` (parallel
-    model, single process, not with retire_finished / scores / beam / score_labels): every record gains `pred_sample_faces` /
-    `pred_sample_face_scores` / `pred_sample_face_votes`.
-    constrain: "no_repeat" or "loops", the loop-constrained greedy decode with cfg.post_process.enclosedness_tol as the end-point
-    tolerance (parallel model, single process, not with retire_finished / scores / beam / sample / score_labels): every record
-    gains `pred_dead_ends` / `pred_unclosed`."""
-    if constrain and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores or beam or sample or score_labels):
-        raise ValueError("--constrain applies to SurfaceFormer_Parallel only, and not together with --retire-finished, --scores, "
-                         "--beam, --sample or --score-labels")
-    if constrain and constrain not in ("no_repeat", "loops"):
-        raise ValueError("--constrain must be 'no_repeat' or 'loops'")
-    if constrain and dist_mod is not None and dist_mod.get_world_size() > 1:
-        raise ValueError("--constrain is not implemented for multi-rank runs")
-    if sample and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores or beam or score_labels):
-        raise ValueError("--sample applies to SurfaceFormer_Parallel only, and not together with --retire-finished, --scores, "
-                         "--beam or --score-labels")
-    if sample and dist_mod is not None and dist_mod.get_world_size() > 1:
-        raise ValueError("--sample (num_samples) is not implemented for multi-rank runs")
-    if score_labels and (retire_finished or scores or beam):
-        raise ValueError("--score-labels does not combine with --retire-finished, --scores or --beam (a forced decode excludes them)")
-    if score_labels and dist_mod is not None and dist_mod.get_world_size() > 1:
-        raise ValueError("--score-labels (score) is not implemented for multi-rank runs: the scores are not gathered across ranks")
-    if beam and (cfg.model_class != "SurfaceFormer_Parallel" or retire_finished or scores):
-        raise ValueError("--beam applies to SurfaceFormer_Parallel only, and not together with --retire-finished or --scores")
-    if beam and dist_mod is not None and dist_mod.get_world_size() > 1:
-        raise ValueError("--beam (beam_width) is not implemented for multi-rank runs")
-    if retire_finished and cfg.model_class != "SurfaceFormer_Parallel":
-        raise ValueError("--retire-finished applies to SurfaceFormer_Parallel only")
-    if scores and dist_mod is not None and dist_mod.get_world_size() > 1:
-        raise ValueError("--scores (return_logprob) is not implemented for multi-rank runs: the log-probabilities are not "
-                         "gathered across ranks")
+    The decode flags (CLI_FLAGS holds which model, which other flags and whether multi-rank runs take each; build_parser's help
+    and configure_model say what each does) -- scores / beam / score_labels / sample / constrain add keys to every record: see
+    record_of; sample draws under temperature / top_k / top_p with uniforms from a generator seeded with `seed`; constrain uses
+    cfg.post_process.enclosedness_tol as the end-point tolerance."""
+    given = dict(constrain=constrain, sample=sample, score_labels=score_labels, beam=beam, retire_finished=retire_finished, scores=scores)
+    check_cli_flags(given, cfg.model_class, dist_mod.get_world_size() if dist_mod is not None else 1)
     model_class = getattr(models, cfg.model_class)
     dataset_class = getattr(D, cfg.dataset_class)
     if model is None:
@@ -252,6 +239,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     lo, hi, _ = shard_range(n_all, rank, world)
     batch_size = max(1, int(batch_size))
     total, done, stats, records = 0.0, 0, [], []
+    wanted = [gain for flag, *_, gain in CLI_FLAGS if given[flag] and gain]
     for b0 in range(lo, hi, batch_size):
         idx = list(range(b0, min(hi, b0 + batch_size)))
         items = [ds[i] for i in idx]
@@ -260,25 +248,14 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         if torch.cuda.is_available() and str(device).startswith("cuda"):
             torch.cuda.synchronize()
         t0 = time.time()
-        bms = sms = dds = None
-        if constrain:
-            pred, dds = decode_batch_constrained(model, batch)
-            lps = None
-        elif sample:
-            pred, stk, ssc = decode_batch_samples(model, batch)
-            lps, sms = None, list(zip(stk, ssc))
-        elif beam:
-            pred, bt, bs = decode_batch_beams(model, batch)
-            lps, bms = None, list(zip(bt, bs))
-        else:
-            pred, lps = decode_batch_scored(model, batch) if scores else (decode_batch(model, batch), None)
+        pred, extras = decode_batch_with(model, batch, wanted)
         lsc = score_batch(model, batch) if score_labels else None
         total += time.time() - t0
         done += len(idx)
         for k, i in enumerate(idx):
-            text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel, lps[k] if scores else None,
-                                 bms[k] if beam else None, {n: v[k] for n, v in lsc.items()} if score_labels else None,
-                                 sms[k] if sample else None, dds[k] if constrain else None)
+            text, st = record_of(cfg, ds.raw_datas[i], items[k], pred[k], parallel,
+                                 label_scores={n: v[k] for n, v in lsc.items()} if score_labels else None,
+                                 **{param: v[k] for param, v in extras.items()})
             stats.append(st)
             records.append((os.path.splitext(os.path.basename(items[k]["name"]))[0], text))
         print("Avg Time", total / done, "seconds.")
