@@ -167,6 +167,16 @@ int ff_constrain_finalize(const int* tok, const float* lp, const int* fin, const
                           const int* num_input, int dedup, int F, int w0, int nw, int Fc, int f0, int b0, int64_t* predict,
                           float* logprob, int* dead_end, int* seq_of_row, hipStream_t st);
 
+// ff_beam_constrained_select with the decode engine's hand-over (ff_constrain_beam.hip): arrive counts the
+// launch's GROUPS, the last block stores count_ge to host_slot.  And the start state / dead-end output of a constrained beam
+// decode (kernels' comments); its beams, scores and predict are packed by ff_beam_finalize.
+int ff_beam_constrained_select_sync(const ff_beam_constrained_step* step, int* arrive, int* host_slot, ff_stream_t stream);
+int ff_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* parent, int* first, int* prev, unsigned* visited, int Bc,
+                           int Fc, int W, int f0, const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok,
+                           const unsigned* follows, int L, hipStream_t st);
+int ff_constrain_beam_dead(const int* dead, int Btot, const int* steps_dev, const int* num_input, int dedup, int F, int W, int w0,
+                           int nw, int Fc, int f0, int b0, int* dead_end, hipStream_t st);
+
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);
 

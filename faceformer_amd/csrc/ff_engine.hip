@@ -35,6 +35,9 @@
 //   constrain (ff_decode_constrained): the default plan, one sequence per anchor.  ff_pointer_constrained masks
 //     the keys the enclosure walk could not accept; records and the rule's state (first, prev per step; visited words and the
 //     byte mask per sequence).
+//   constrained beam (ff_decode_constrained_beam): the beam decode's plan, records and reorder with
+//     ff_beam_constrained_select as the selection; also the cumulative dead flag per step, the rule's state in two halves that
+//     the steps read and write alternately, and the byte mask per sequence.
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
@@ -253,6 +256,12 @@ struct DecodeBuffers {
   int *cn_fin, *cn_dead, *cn_first, *cn_prev;
   unsigned* cn_visited;
   unsigned char* cn_rows;
+  // constrained beam decode: the beam decode's records (bm_*) plus the cumulative dead flag [T, Btot]; the rule's state as two
+  // halves that the steps read and write alternately (first, prev: [2, Btot]; visited: [2, Btot, ceil(L/32)]: step s reads
+  // half s & 1); the constraint byte rows [Btot, S]
+  int *cb_dead, *cb_first, *cb_prev;
+  unsigned* cb_visited;
+  unsigned char* cb_rows;
 };
 
 // A micro-batch is a contiguous range [b0, b0 + Bc) of the COMPACT sequence index: nw >= 1 consecutive
@@ -346,7 +355,7 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
@@ -354,6 +363,7 @@ struct Mode {
   const ff_forced_params* forced() const { return static_cast<const ff_forced_params*>(prm); }
   const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }
   const ff_constrain_params* con() const { return static_cast<const ff_constrain_params*>(prm); }
+  const ff_constrain_beam_params* cbeam() const { return static_cast<const ff_constrain_beam_params*>(prm); }
 };
 
 // The micro-batch plan of a mode: the default plan for greedy and constrain; without de-duplication for forced (the rows are
@@ -362,6 +372,7 @@ void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, con
                int* max_bc, int* nchunks = nullptr) {
   switch (mode.kind) {
     case Mode::BEAM:
+    case Mode::CONSTRAIN_BEAM:
     case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
     case Mode::FORCED: {
       ff_decode_params q = *p;
@@ -487,6 +498,18 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
       const size_t fw = (size_t)(p->L + 31) / 32;   // visited words per sequence; one word at L = 0, so that the array is never empty
       b.cn_visited = bp.take<unsigned>(Btot * (fw > 0 ? fw : 1));
       b.cn_rows = bp.take<unsigned char>(Btot * (size_t)S);
+      break;
+    }
+    case Mode::CONSTRAIN_BEAM: {
+      b.bm_score = bp.take<float>((size_t)T * Btot);
+      b.bm_fin = bp.take<int>((size_t)T * Btot);
+      b.bm_parent = bp.take<int>((size_t)T * Btot);
+      b.cb_dead = bp.take<int>((size_t)T * Btot);
+      b.cb_first = bp.take<int>(2 * Btot);
+      b.cb_prev = bp.take<int>(2 * Btot);
+      const size_t fw = (size_t)(p->L + 31) / 32;   // (one word at L = 0, so that the array is never empty)
+      b.cb_visited = bp.take<unsigned>(2 * Btot * (fw > 0 ? fw : 1));
+      b.cb_rows = bp.take<unsigned char>(Btot * (size_t)S);
       break;
     }
     default: break;
@@ -1010,6 +1033,14 @@ struct DecodeRun {
                                  buf.cn_prev + c.b0, buf.cn_visited + (size_t)c.b0 * fw, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo,
                                  p->term_hi, m->num_token, follows ? follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, st);
       }
+      case Mode::CONSTRAIN_BEAM: {   // (half 0 of the ping-pong state: step 0 reads it)
+        const int fw = (p->L + 31) / 32;
+        const unsigned* follows = mode.cbeam()->follows;
+        return ff_constrain_beam_init(buf.tok_all + c.b0, buf.bm_score + c.b0, buf.bm_fin + c.b0, buf.cb_dead + c.b0, buf.bm_parent + c.b0,
+                                      buf.cb_first + c.b0, buf.cb_prev + c.b0, buf.cb_visited + (size_t)c.b0 * fw, c.Bc, c.Fc / G, G, c.f0,
+                                      ni, pad_tok, p->term_lo, p->term_hi, m->num_token,
+                                      follows ? follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, st);
+      }
       default: return FF_OK;   // (forced: the start tokens are row 0 of the token array, forced_tokens() put the paths there)
     }
   }
@@ -1092,6 +1123,30 @@ struct DecodeRun {
                                            buf.cn_visited + (size_t)c.b0 * fw, buf.cn_rows + (size_t)c.b0 * S, buf.tok_all + out,
                                            buf.cn_lp + out, buf.cn_fin + out, buf.cn_dead + out, buf.cn_first + out, buf.cn_prev + out,
                                            mem_w, E, next_rows, E, c.x0stat, buf.cnt_ge + slot, arrive, host_slot, st);
+      }
+      case Mode::CONSTRAIN_BEAM: {
+        // the constrained top-W selection (state half step & 1 -> half t & 1), then the beam decode's reorder of the prefixes
+        const ff_constrain_beam_params* cb = mode.cbeam();
+        const int W = mode.G, G = c.Bc / W, L = p->L, fw = (L + 31) / 32;
+        const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
+        ff_beam_constrained_step d;
+        memset(&d, 0, sizeof(d));
+        d.logits = logits_dst; d.ldlogits = S; d.S = S; d.mask = mask_w; d.kv_len = kv_w;
+        d.groups = G; d.width = W; d.groups_per_wireframe = c.Fc / W;
+        d.follows = cb->follows ? cb->follows + (size_t)c.w0 * L * fw : nullptr;
+        d.L = L; d.flags = cb->flags; d.ntok = m->num_token; d.term_lo = p->term_lo; d.term_hi = p->term_hi;
+        d.scores_in = buf.bm_score + in; d.fin_in = buf.bm_fin + in; d.dead_in = buf.cb_dead + in;
+        d.first_in = buf.cb_first + hin; d.prev_in = buf.cb_prev + hin; d.visited_in = buf.cb_visited + hin * fw;
+        d.scores_out = buf.bm_score + out; d.fin_out = buf.bm_fin + out; d.dead_out = buf.cb_dead + out;
+        d.first_out = buf.cb_first + hout; d.prev_out = buf.cb_prev + hout; d.visited_out = buf.cb_visited + hout * fw;
+        d.mask_rows = buf.cb_rows + (size_t)c.b0 * S;
+        d.parent = buf.bm_parent + out; d.next_tok = buf.tok_all + out;
+        d.memory = mem_w; d.E = E; d.next_rows = next_rows; d.ldnext = E; d.next_stats = c.x0stat; d.count_ge = buf.cnt_ge + slot;
+        FF_RETURN_IF(ff_beam_constrained_select_sync(&d, arrive, host_slot, st));
+        if (cb->trace_parent)
+          FF_CHECK_HIP(hipMemcpyAsync(cb->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
+        if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
+        return FF_OK;
       }
       case Mode::FORCED:   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
         return ff_pointer_forced(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, buf.tok_all + out, buf.fc_lp + in, buf.fc_greedy + in,
@@ -1290,6 +1345,12 @@ struct DecodeRun {
       case Mode::CONSTRAIN:
         return ff_constrain_finalize(buf.tok_all, buf.cn_lp, buf.cn_fin, buf.cn_dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
                                      c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con()->logprob, mode.con()->dead_end, io.seq_of_row, main_st);
+      case Mode::CONSTRAIN_BEAM:
+        FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.bm_parent, buf.bm_score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0,
+                                      c.nw, c.Fc / G, c.f0, c.b0, mode.cbeam()->beams, mode.cbeam()->scores, io.predict, io.seq_of_row,
+                                      main_st));
+        return ff_constrain_beam_dead(buf.cb_dead, Btot, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G, c.f0, c.b0,
+                                      mode.cbeam()->dead_end, main_st);
       default: break;   // (forced: forced_epilogue packs all rows at once)
     }
     const long total = (long)c.nw * F * T;
@@ -1558,6 +1619,37 @@ extern "C" int ff_decode_constrained(const ff_model* m, const ff_decode_params* 
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::CONSTRAIN, 1, constrain));
+}
+
+extern "C" size_t ff_decode_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
+                                                             int width) {
+  if (width < 1 || width > 8) return 0;
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_BEAM, width));
+}
+
+extern "C" int ff_decode_constrained_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                          const unsigned char* mask, const int* kv_len, const int* num_input,
+                                          const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                                          int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                                          float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                                          size_t workspace_bytes, const ff_constrain_beam_params* beam, ff_stream_t stream) {
+  const char* name = "ff_decode_constrained_beam";
+  FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
+  FF_RETURN_IF(check_opt_in(name, "the constrained beam decode is", p, extra_mask));
+  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d",
+               name, beam->width, p->L + m->num_token);
+  FF_CHECK_ARG(!(beam->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", name, beam->flags);
+  FF_CHECK_ARG(beam->follows || !(beam->flags & FF_CONSTRAIN_CONNECT), "%s: FF_CONSTRAIN_CONNECT needs the follow table", name);
+  FF_CHECK_ARG(p->term_lo >= 0 && p->term_lo < p->term_hi && p->term_hi <= m->num_token,
+               "%s: terminator range [%d, %d) empty or outside the %d special tokens", name, p->term_lo, p->term_hi, m->num_token);
+  FF_RETURN_IF(check_opt_in_outputs(name, p, "beams, scores and dead_end", beam->beams && beam->scores && beam->dead_end, trace_best,
+                                    trace_second, pointer_out));
+  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
+  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
+               "%s: width=%d at E=%d exceeds the reorder's staging area", name, beam->width, m->E);
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM, beam->width, beam));
 }
 
 namespace {

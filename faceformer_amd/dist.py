@@ -213,6 +213,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
         for sw in mode.switches:
             if sw.sharded and sw.on(model):
                 raise ValueError("decode_sharded does not implement %s (%s)" % (sw.attr, sw.sharded))
+    if getattr(model, "constrain_beams", 0):     # (with constrain the lines above have raised; without it the option is an error anywhere)
+        raise ValueError("decode_sharded does not implement constrain_beams (%s)" % _modes.SWITCH["constrain"].sharded)
     rank, world = dist_mod.get_rank(group), dist_mod.get_world_size(group)
     parallel = isinstance(model, SurfaceFormer_Parallel)
     variant = _L.FF_PARALLEL if parallel else _L.FF_SEQ2SEQ

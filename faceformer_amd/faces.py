@@ -235,6 +235,15 @@ def parse_parallel_beams_scored(beams, scores, num_edges, token):
     return faces
 
 
+def parse_parallel_constrained_beams_scored(beams, scores, dead_end, num_edges, token):
+    """The faces of a constrained beam decode (the parallel model's constrain_beams): parse_parallel_beams_scored
+    over the beams that did not run into a dead end -- dead_end [..., W] nonzero: the beam is left out, as an empty one is (a
+    dead-ended beam ends in a terminator the rule opened for want of an edge: its loop is open)."""
+    sc = np.array(scores, dtype=np.float64, copy=True)
+    sc[np.asarray(dead_end).reshape(sc.shape) != 0] = -np.inf
+    return parse_parallel_beams_scored(beams, sc, num_edges, token)
+
+
 def parse_parallel_samples_scored(samples, scores, num_edges, token):
     """The faces of a sampled decode (the parallel model's num_samples): samples [..., R, T] tokens; scores either
     [..., R], the samples' summed log-probabilities (predict_sample_scores), or [..., R, T], their per-position

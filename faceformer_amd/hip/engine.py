@@ -100,9 +100,14 @@ def check_sample_options(num_samples, temperature, top_k, top_p, variant, retire
 
 
 def check_constrain_options(flags, variant, retire, return_pointer, no_stop, stop_callback, extra_mask, logprob, beam_width,
-                            num_samples, term_range, follow_table):
+                            num_samples, term_range, follow_table, constrain_beams=0, S=None):
     """The combinations a constrained decode rejects (ff_decode_constrained's FF_ERR_ARG list, and the options of decode() it
-    cannot be combined with), as ValueError before anything is launched."""
+    cannot be combined with), as ValueError before anything is launched.  constrain_beams = W > 0 (with S, the keys per row):
+    those of the beam search over the constrained keys (ff_decode_constrained_beam)."""
+    W = _modes.constrain_beams_value(constrain_beams, flags)
+    if W:      # (S not given: the width is held to 1..8 alone)
+        return _modes.check_options(_modes.CONSTRAIN_BEAM, variant, dict(locals(), constrain=flags, constrain_beams=W,
+                                                                         S=8 if S is None else S), term_range)
     _modes.check_options(_modes.CONSTRAIN, variant, dict(locals(), constrain=flags), term_range)
 
 
@@ -368,7 +373,8 @@ class PathEngine:
                tok_sos=1, tok_eos=3, x3_min_rows=0, chunk_max_seqs=0, ln_fuse_max_rows=0,
                trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
-               num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None):
+               num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
+               constrain_beams=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -400,12 +406,19 @@ class PathEngine:
         ceil(L/32)] int32 on the device (ops.follow_table), required by "loops".  `predict` is the constrained decode (zero after
         the row's finish position and the stop step); also `logprob` [N*F, T] fp32 (under the renormalised distribution) and
         `dead_end` [N*F] int32; with trace=True `logits` [T-1, N*F, S] holds the constrained masked rows.  Excludes those, beam_width
-        and num_samples.  Bits 0 equal the retire=True decode."""
+        and num_samples.  Bits 0 equal the retire=True decode.
+
+        constrain_beams=W in 1..8, W <= S (only with constrain; ff_decode_constrained_beam; None or 0: the
+        constrained greedy decode above): the beam search over the constrained keys, W beams per anchor.  Also `beams`
+        [N*F*W, T] int64 and `beam_scores` [N*F*W] fp32 as beam_width's, `beam_dead_end` [N*F*W] int32 (the beam ran into a dead
+        end); `predict` is beam 0; with trace=True `logits` [T-1, N*F*W, S] (the constrained masked rows) and `beam_parent`.
+        No `logprob` / `dead_end`.  W = 1 equals the constrained greedy decode."""
         W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
-        mode, value = _modes.of_options(logprob, constrain=CF, num_samples=R, beam_width=W)      # (value None: the greedy record)
+        CB = _modes.constrain_beams_value(constrain_beams, CF)
+        mode, value = _modes.of_options(logprob, CB, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
         G = value if mode.per_anchor else 1       # sequences per anchor
         o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
-                 logprob=logprob, beam_width=W, num_samples=R, constrain=CF, temperature=temperature, top_k=top_k, top_p=top_p,
+                 logprob=logprob, beam_width=W, num_samples=R, constrain=CF, constrain_beams=CB, temperature=temperature, top_k=top_k, top_p=top_p,
                  uniforms=uniforms, follow_table=follow_table, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
                  N=memory.shape[0], S=memory.shape[1], F=F, T=T)
         if value is not None:    # (retire, an option of the greedy record, is checked behind the operands)

@@ -147,6 +147,22 @@ class ConstrainParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("follows", fptr), ("logprob", fptr), ("dead_end", fptr)]
 
 
+class BeamConstrainedStep(C.Structure):
+    _fields_ = [("logits", fptr), ("ldlogits", C.c_int), ("S", C.c_int), ("mask", fptr), ("kv_len", fptr),
+                ("groups", C.c_int), ("width", C.c_int), ("groups_per_wireframe", C.c_int),
+                ("follows", fptr), ("L", C.c_int), ("flags", C.c_int), ("ntok", C.c_int), ("term_lo", C.c_int), ("term_hi", C.c_int),
+                ("scores_in", fptr), ("fin_in", fptr), ("dead_in", fptr), ("first_in", fptr), ("prev_in", fptr), ("visited_in", fptr),
+                ("scores_out", fptr), ("fin_out", fptr), ("dead_out", fptr), ("first_out", fptr), ("prev_out", fptr),
+                ("visited_out", fptr), ("mask_rows", fptr), ("parent", fptr), ("next_tok", fptr),
+                ("memory", fptr), ("E", C.c_int), ("next_rows", fptr), ("ldnext", C.c_int), ("next_stats", fptr),
+                ("count_ge", fptr)]
+
+
+class ConstrainBeamParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("flags", C.c_int), ("follows", fptr), ("beams", fptr), ("scores", fptr), ("dead_end", fptr),
+                ("trace_parent", fptr)]
+
+
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
 
@@ -258,6 +274,12 @@ SIGNATURES = {
                                         C.POINTER(C.c_int), fptr,
                                         fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                         C.c_size_t, C.POINTER(ConstrainParams), fptr]),
+    "ff_beam_constrained_select": (C.c_int, [C.POINTER(BeamConstrainedStep), fptr]),
+    "ff_decode_constrained_beam_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int), C.c_int]),
+    "ff_decode_constrained_beam": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                             C.POINTER(C.c_int), fptr,
+                                             fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                                             C.c_size_t, C.POINTER(ConstrainBeamParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 

@@ -99,6 +99,25 @@ def _constrain_values(o):
         raise ValueError("constrain='loops' needs follow_table (ops.follow_table)")
 
 
+def constrain_beams_value(constrain_beams, flags):
+    """The width of a `constrain_beams` value: None / 0 -> 0 (the option is off); else 1..8, and only with `constrain` set
+    (`flags`: constrain_flags of it)."""
+    if constrain_beams is None or (not isinstance(constrain_beams, bool) and constrain_beams == 0):
+        return 0
+    if isinstance(constrain_beams, bool) or not isinstance(constrain_beams, int) or not 1 <= constrain_beams <= 8:
+        raise ValueError("constrain_beams=%r: must be None, 0 or a width in 1..8" % (constrain_beams,))
+    if flags is None:
+        raise ValueError("constrain_beams=%d needs constrain ('no_repeat' or 'loops'): it is the beam search over the constrained keys"
+                         % constrain_beams)
+    return int(constrain_beams)
+
+
+def _constrain_beam_values(o):
+    if not 1 <= o["constrain_beams"] <= 8 or o["constrain_beams"] > o["S"]:
+        raise ValueError("constrain_beams=%d: must be in 1..8 and at most S = %d" % (o["constrain_beams"], o["S"]))
+    _constrain_values(o)
+
+
 def _constrain_operand(eng, o):
     L = o["S"] - eng.num_token
     shape = (o["N"], L, (L + 31) // 32)
@@ -138,6 +157,14 @@ def _beam_tail(o, ptrs, traced):
     return (C.byref(_L.BeamParams(o["beam_width"], *ptrs, _p(traced.get("beam_parent")))),)
 
 
+def _constrain_beam_tail(o, ptrs, traced):
+    if o["trace"]:
+        logits = traced["logits"]
+        traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
+    return (C.byref(_L.ConstrainBeamParams(o["constrain_beams"], o["constrain"], _p(o["follow_table"]), *ptrs,
+                                           _p(traced.get("beam_parent")))),)
+
+
 def outputs(mode, eng, o, B, traced):
     """(the mode's outputs by key: [B * G if "G" is among the dimensions else B, T if "T" is], the arguments only its entry takes:
     its parameter struct, or the log-probability output).  The mode's own operand is checked and made contiguous first."""
@@ -167,6 +194,14 @@ CONSTRAIN = Mode(
     # (without CONNECT nothing reads the table: neither the mask nor, first being unused, the closure test)
     prepare=lambda m, CF, inputs, dev, T, N, F, ni, order: dict(
         constrain=CF, follow_table=m._follow_table(inputs, dev, ni, order) if CF & _L.FF_CONSTRAIN_CONNECT else None))
+
+# constrain with its option constrain_beams = W: the beam search over the constrained keys.  Outside MODES, as
+# GREEDY_LOGPROB is: the option that switches the mode on stays `constrain`, whose record reports every error without the option.
+CONSTRAIN_BEAM = CONSTRAIN._replace(
+    subject="constrain_beams", entry="ff_decode_constrained_beam", per_anchor=True, values=_constrain_beam_values,
+    outs=(("beams", "GT", _I64), ("beam_scores", "G", _F32), ("beam_dead_end", "G", _I32)), tail=_constrain_beam_tail,
+    prepare=lambda m, W, inputs, dev, T, N, F, ni, order: dict(
+        CONSTRAIN.prepare(m, constrain_flags(m.constrain), inputs, dev, T, N, F, ni, order), constrain_beams=W))
 
 SAMPLE = Mode(
     subject="num_samples", excludes=_COMMON + ("beam_width",), entry="ff_decode_sample", per_anchor=True, values=_sample_values,
@@ -206,11 +241,14 @@ MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 
 
-def of_options(logprob=False, **values):
+def of_options(logprob=False, constrain_beams=0, **values):
     """(record, value) of the first of MODES whose option is set in `values` (constrain: the flag bits or None; num_samples;
-    beam_width); else the greedy record (its logprob form with `logprob`) and None."""
+    beam_width); else the greedy record (its logprob form with `logprob`) and None.  constrain with constrain_beams = W > 0:
+    the CONSTRAIN_BEAM record and W."""
     for mode in MODES[:-1]:
         v = values[mode.subject]
         if v is not None and (v or mode is CONSTRAIN):
+            if mode is CONSTRAIN and constrain_beams:
+                return CONSTRAIN_BEAM, constrain_beams
             return mode, v
     return (GREEDY_LOGPROB if logprob else GREEDY), None

@@ -49,7 +49,10 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
          -- predict is the constrained decode (zero after a row's face-type token and after the stop step), also
         predict_logprob N x F x T (under the renormalised distribution) and predict_dead_end N x F.  The follow table is built
         from the end points input[:, :, 0, :2] / input[:, :, -1, :2] with constrain_tol, or taken from inputs["follow_table"]
-        (bool N x L x L, or the packed int32 words N x L x ceil(L/32)), for the batch AS GIVEN."""
+        (bool N x L x L, or the packed int32 words N x L x ceil(L/32)), for the batch AS GIVEN.
+        constrain_beams = W in 1..8 (default 0; only with constrain): the beam search over the constrained keys --
+        predict_beams N x F x W x T, predict_beam_scores and predict_beam_dead_end N x F x W in place of predict_logprob; predict
+        and predict_dead_end are beam 0's."""
         label = inputs["label"]
         T = self.max_face_length
         mode, value = self._decode_mode(inputs, parallel=True)
@@ -101,10 +104,12 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
             inv[torch.tensor(order, device=memory.device)] = torch.arange(N, device=memory.device)
             views = [(key, t.index_select(0, inv)) for key, t in views]
         inputs.update(views)
+        if "predict_beam_dead_end" in inputs:     # (constrain_beams: the constrained decode's key, for beam 0)
+            inputs["predict_dead_end"] = inputs["predict_beam_dead_end"][:, :, 0]
         self.last_decode_stats = {"decoded_seqs": G * sum(min(F, n + 1) for n in num_input), "rows": N * F,
                                   "slot_rows": out["slot_rows"], "steps": out["steps"]}
         if mode.per_anchor:   # (G sequences per decoded anchor; `rows` stays the reference's N * F)
-            self.last_decode_stats[mode.switches[0].attr] = G
+            self.last_decode_stats[mode.subject if mode.subject == "constrain_beams" else mode.switches[0].attr] = G
         return inputs
 
     def _follow_table(self, inputs, device, num_input, order):

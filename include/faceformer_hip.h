@@ -876,6 +876,80 @@ int ff_decode_constrained(const ff_model* m, const ff_decode_params* p,
                           float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                           void* workspace, size_t workspace_bytes, const ff_constrain_params* constrain, ff_stream_t stream);
 
+/* ---- beam search over the loop-constrained pointer decode (opt-in, parallel variant; entries added within ABI 105)
+ * The beam search above keeps the `width` best continuations per anchor, each of which the harness's enclosure filter may still
+ * drop; the constrained decode above only selects keys that filter can accept, but greedily.  These entries are the two
+ * together: a beam search whose candidates are the LIVE keys of the constrained rows.
+ *
+ * Layout and start state.  The decode runs N*F*width sequences in the beam layout: sequence (w*F + f)*width + k.  Per group
+ * (the width beams of one anchor) beam 0 starts with score 0, the others are empty (score -inf).  Every beam carries the
+ * constrained decode's state (visited, first, prev), initialised from column 0 as there, and a cumulative `dead` flag.
+ * Candidates of one step and group:
+ *   an empty beam      none.
+ *   a finished beam    itself: token 0, score unchanged.
+ *   an unfinished beam k   its constraint row is formed exactly as ff_pointer_constrained forms it (NO_REPEAT, CONNECT, the
+ *       dead-end vote over padding, kv_len and visited, the terminators re-opened on a dead end); the row is masked and reduced
+ *       as there.  Its candidates are the live keys only, l[s] > -FLT_MAX, each at c_k + (l[s] - m) - log sum exp(l - m) over
+ *       the constrained row: the renormalised distribution, fp32, saturated at -FLT_MAX.  A masked key is never a candidate
+ *       (ff_beam_select keeps them at -FLT_MAX).  A row with no live key at all contributes one candidate: token 0 with score
+ *       c_k - log S -- what the constrained greedy launch selects there.
+ * Selection: higher score first, then the lower flat index k * S + s.  A group with fewer than width candidates leaves its last
+ * beams empty: parent = own index, token 0, score -inf, flags clear, state that of the own index.
+ * Update for new beam i with parent p and token tk: (first, prev) = the rule's three-step update applied to p's (first, prev),
+ * with the closure test against follows, when tk is an edge of an unfinished p, else p's;  visited_out[i] = visited_in[p] |
+ * bit(tk);  dead_out[i] = dead_in[p] | (p dead-ended at this step);  fin_out[i] = fin_in[p] | (p dead-ended at this step) |
+ * tk in [term_lo, term_hi).  All state is read from the *_in arrays and written to the *_out arrays, so that no beam reads a
+ * sibling's overwritten state: visited_out must not be visited_in; the other *_out may be their *_in.
+ * Stop rule, padding after the stop step, parent back-tracking, padding anchors and FF_DEDUP_PAD_ANCHORS are ff_decode_beam's.
+ * Identities: width 1 is ff_decode_constrained (tokens, steps and dead_end exact; the score is the sum of its logprob); with
+ * both flag bits clear the result is ff_decode_beam's at the same width wherever that kept no masked candidate.
+ *
+ * ff_beam_constrained_select: one step of every group, described by ff_beam_constrained_step.  Launch row b = g * width + k;
+ *   wireframe of a row: b / (groups_per_wireframe * width).  logits [groups * width, ldlogits] are masked IN PLACE with the
+ *   constrained masks (rows of empty / finished beams are not touched); mask_rows [groups * width, S] bytes receive the rule's
+ *   own mask of every non-empty unfinished beam.  first / prev: edge index, -1 = none (values outside [0, L) read as none).
+ *   parent, next_tok, scores_out, fin_out, dead_out, first_out, prev_out [groups * width], visited_out [groups * width,
+ *   ceil(L/32)]: the new beams in rank order.  next_rows (optional, with memory, E, ldnext >= E): row b receives
+ *   memory[wireframe, next_tok[b], :]; next_stats (optional) as ff_pointer_forced's.  count_ge (optional): += number of kept candidates of unfinished beams whose token is
+ *   >= ntok.  1 <= width <= 8, width <= S, L = S - ntok, 0 <= term_lo < term_hi <= ntok.
+ * ff_decode_constrained_beam: the parallel decode under the rule with `width` beams per anchor; ff_decode's arguments, then
+ *   ff_constrain_beam_params: follows [N, L, ceil(L/32)] DEVICE (may be NULL when CONNECT is clear); beams [N*F*width, T] int64,
+ *   scores [N*F*width] fp32 and predict = beam 0 as ff_decode_beam's; dead_end [N*F*width] int32: the beam's cumulative dead
+ *   flag at the stop step; trace_parent (optional) and trace_logits as ff_decode_beam's (the constrained masked rows).
+ * FF_ERR_ARG before any launch for everything ff_decode_beam and ff_decode_constrained reject, a NULL table when CONNECT is set
+ * and term_hi > num_token.  ff_decode_constrained_beam_workspace_bytes: the workspace it needs (ff_decode_beam_workspace_bytes'
+ * rules, plus the per-step dead record, the ping-pong state and the byte rows, taken last).  The other decode entries launch and
+ * lay out what they did before these. */
+typedef struct ff_beam_constrained_step {
+  float* logits; int ldlogits; int S;
+  const unsigned char* mask; const int* kv_len;
+  int groups, width, groups_per_wireframe;
+  const unsigned int* follows; int L, flags, ntok, term_lo, term_hi;
+  const float* scores_in; const int *fin_in, *dead_in, *first_in, *prev_in; const unsigned int* visited_in;
+  float* scores_out; int *fin_out, *dead_out, *first_out, *prev_out; unsigned int* visited_out;
+  unsigned char* mask_rows;
+  int *parent, *next_tok;
+  const float* memory; int E; float* next_rows; int ldnext; float* next_stats;
+  int* count_ge;
+} ff_beam_constrained_step;
+int ff_beam_constrained_select(const ff_beam_constrained_step* step, ff_stream_t stream);
+typedef struct ff_constrain_beam_params {
+  int width;
+  int flags;
+  const unsigned int* follows;
+  int64_t* beams;
+  float* scores;
+  int* dead_end;
+  int* trace_parent;
+} ff_constrain_beam_params;
+size_t ff_decode_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host, int width);
+int ff_decode_constrained_beam(const ff_model* m, const ff_decode_params* p,
+                               const float* memory, const unsigned char* mask, const int* kv_len,
+                               const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                               int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                               float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                               void* workspace, size_t workspace_bytes, const ff_constrain_beam_params* beam, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,7 +105,8 @@ def score_batch(model, batch):
             "paths": paths.cpu().numpy(), "lengths": lengths.reshape(lp.shape[:-1]).cpu().numpy(), "seq_logprob": out["score_seq_logprob"].cpu().numpy()}
 
 
-def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None):
+def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
+              constrained_beams=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -120,7 +121,10 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     ranked by their best score, with the number of draws that produced each; `pred_faces` stays what sample 0 (pred) gives.
     dead_end (--constrain; the dead-end flags [F] of this sample): the record also gets `pred_dead_ends`, the number of the
     wireframe's own anchor rows the constrained decode ended at a dead end, and `pred_unclosed`, the number of own anchor rows
-    whose face does not pass the enclosure walk (dead ends, and loops still open at the last position)."""
+    whose face does not pass the enclosure walk (dead ends, and loops still open at the last position).
+    constrained_beams (--constrain-beams; (tokens [F, W, T], scores [F, W], dead-end flags [F, W]) of this sample): the record
+    also gets `pred_beam_faces` and `pred_beam_face_scores` as under --beam, over the beams that did not run into a dead end;
+    `pred_faces`, `pred_dead_ends` and `pred_unclosed` stay what beam 0 (pred, dead_end) gives."""
     scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
@@ -169,6 +173,13 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["pred_dead_ends"] = int(np.asarray(dead_end[:n]).astype(bool).sum())
         rec["pred_unclosed"] = sum(1 for _, idx in own
                                    if not FZ.is_face_enclosed(raw["edges"], idx, cfg.post_process.enclosedness_tol))
+    if constrained_beams is not None:
+        n = int(item["num_input"])
+        bf = FZ.parse_parallel_constrained_beams_scored(constrained_beams[0][:n], constrained_beams[1][:n], constrained_beams[2][:n],
+                                                        len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_beam_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_beam_face_scores"] = [s for _, _, s, _ in ranked]
     if samples is not None:
         n = int(item["num_input"])
         sf = FZ.parse_parallel_samples_scored(samples[0][:n], samples[1][:n], len(raw["edges"]), cfg.model.token)
@@ -180,13 +191,13 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
 
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
-                    seed=0, constrain=None, constrain_tol=None):
+                    seed=0, constrain=None, constrain_tol=None, constrain_beams=0):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
     under temperature / top_k / top_p from the seeded generator (num_samples), the loop-constrained greedy decode
-    (constrain "no_repeat" / "loops" with the end-point tolerance constrain_tol).  Without them the model keeps its
-    defaults."""
+    (constrain "no_repeat" / "loops" with the end-point tolerance constrain_tol), the beam search over its keys
+    with `constrain_beams` beams per anchor.  Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
     if fp16:
@@ -203,19 +214,29 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.constrain = str(constrain)
         if constrain_tol is not None:
             model.constrain_tol = float(constrain_tol)
+    if constrain_beams:
+        model.constrain_beams = int(constrain_beams)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
-             top_p=1.0, seed=0, constrain=None):
+             top_p=1.0, seed=0, constrain=None, constrain_beams=0):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
     The decode flags (CLI_FLAGS holds which model, which other flags and whether multi-rank runs take each; build_parser's help
     and configure_model say what each does) -- scores / beam / score_labels / sample / constrain add keys to every record: see
     record_of; sample draws under temperature / top_k / top_p with uniforms from a generator seeded with `seed`; constrain uses
-    cfg.post_process.enclosedness_tol as the end-point tolerance."""
+    cfg.post_process.enclosedness_tol as the end-point tolerance; constrain_beams = W (1..8, only with constrain, single-rank
+    runs only) decodes W constrained beams per anchor and adds pred_beam_faces / pred_beam_face_scores."""
+    if constrain_beams:
+        if not constrain:
+            raise ValueError("--constrain-beams requires --constrain")
+        if isinstance(constrain_beams, bool) or not isinstance(constrain_beams, int) or not 1 <= constrain_beams <= 8:
+            raise ValueError("--constrain-beams must be a width in 1..8")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--constrain-beams is not implemented for multi-rank runs")
     given = dict(constrain=constrain, sample=sample, score_labels=score_labels, beam=beam, retire_finished=retire_finished, scores=scores)
     check_cli_flags(given, cfg.model_class, dist_mod.get_world_size() if dist_mod is not None else 1)
     model_class = getattr(models, cfg.model_class)
@@ -226,7 +247,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         model.load_state_dict(sd)
         model = model.eval().to(device)
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
-                    cfg.post_process.enclosedness_tol if constrain else None)
+                    cfg.post_process.enclosedness_tol if constrain else None, constrain_beams)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -240,6 +261,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     batch_size = max(1, int(batch_size))
     total, done, stats, records = 0.0, 0, [], []
     wanted = [gain for flag, *_, gain in CLI_FLAGS if given[flag] and gain]
+    if constrain_beams:
+        wanted.append(("constrained_beams", ("predict_beams", "predict_beam_scores", "predict_beam_dead_end")))
     for b0 in range(lo, hi, batch_size):
         idx = list(range(b0, min(hi, b0 + batch_size)))
         items = [ds[i] for i in idx]
@@ -321,6 +344,11 @@ def build_parser():
                              "one ended while a loop is open, and no face-type token before the loop is closed; every JSON record "
                              "gains pred_dead_ends / pred_unclosed; single-process runs only, not with --retire-finished, --scores, "
                              "--beam, --sample or --score-labels")
+    parser.add_argument("--constrain-beams", type=int, default=0, metavar="W",
+                        help="with --constrain: beam search with W (1..8) beams per anchor edge over the constrained keys "
+                             "(DESIGN.md 21); pred_faces, pred_dead_ends and pred_unclosed come from the best beam, and every JSON "
+                             "record gains pred_beam_faces / pred_beam_face_scores: the faces of all beams that did not run into a "
+                             "dead end, de-duplicated and ranked by score; single-process runs only")
     return parser
 
 
@@ -341,7 +369,7 @@ def main(argv=None):
     run_test(cfg, args.test_ckpt, device=device, batch_size=args.batch_size, dist_mod=dist_mod,
              retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam,
              score_labels=args.score_labels, sample=args.sample, temperature=args.temperature, top_k=args.top_k,
-             top_p=args.top_p, seed=args.seed, constrain=args.constrain)
+             top_p=args.top_p, seed=args.seed, constrain=args.constrain, constrain_beams=args.constrain_beams)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 

@@ -6,7 +6,8 @@ Every file of build.SOURCES is compiled with build.FLAGS + --cuda-device-only -S
 .amdhsa_kernel symbol: the function's text from its label to its .size line, plus its .amdhsa_* block (registers, scratch, LDS).
 Printed per file: the kernel count and the sha256 of the per-kernel texts sorted by symbol.  With --against, the same for the
 other checkout's sources (compiled with THIS checkout's flags), and whether the symbol sets, every kernel's text and the order
-of the kernels are equal; the kernels that differ are named and the exit status is 1."""
+of the kernels are equal; the kernels that differ are named and the exit status is 1.  A file of build.SOURCES that the other
+checkout does not have is listed with its own count and digest and compared with nothing."""
 import argparse
 import hashlib
 import os
@@ -48,7 +49,8 @@ def main():
     args = ap.parse_args()
     roots = [ROOT] + ([os.path.abspath(args.against)] if args.against else [])
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
-        jobs = {(r, src): pool.submit(kernels, r, src, tmp) for r in roots for src in build.SOURCES}
+        jobs = {(r, src): pool.submit(kernels, r, src, tmp) for r in roots for src in build.SOURCES
+                if os.path.exists(os.path.join(r, "faceformer_amd", "csrc", src))}      # (a file only this checkout has: see below)
         got = {k: f.result() for k, f in jobs.items()}
     print("flags: " + " ".join(build.FLAGS).replace(ROOT + os.sep, "") + " --cuda-device-only -S")
     bad = 0
@@ -56,6 +58,9 @@ def main():
         new = got[(ROOT, src)]
         if not args.against:
             print("%s: %d kernels  sha256 %s" % (src, len(new), digest(new)))
+            continue
+        if (roots[1], src) not in got:
+            print("%s: not in the other checkout, %d kernels here  sha256 %s" % (src, len(new), digest(new)))
             continue
         old = got[(roots[1], src)]
         dn, do = dict(new), dict(old)
