@@ -160,6 +160,14 @@ int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsign
                                 unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
                                 int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
                                 int* count_ge, int* arrive, int* host_slot, ff_stream_t stream);
+// ff_pointer_constrained_ahead with the same hand-over (the closure look-ahead)
+int ff_pointer_constrained_ahead_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                      int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo,
+                                      int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
+                                      unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
+                                      int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
+                                      float* next_stats, int* count_ge, const unsigned char* close_dist,
+                                      const unsigned char* cycle_len, int budget, int* arrive, int* host_slot, ff_stream_t stream);
 int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int Fc, int f0,
                       const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok, const unsigned* follows, int L,
                       hipStream_t st);

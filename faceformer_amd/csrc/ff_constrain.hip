@@ -18,6 +18,16 @@
 // log-probability (-log sum exp(l - l[token]) over the constrained row), the flags and the next (first, prev), and sets the
 // token's bit in the sequence's visited words; the wave appends memory[w, token] through ff_pointer_append_row, so a
 // constrained decode keeps FF_L0_FOLD.  No LDS beyond the four counter words.  Stop counter: pointer_sample_kernel's scheme.
+// pointer_constrained_kernel<true> is the same launch with the closure look-ahead: one byte row per sequence
+// (close_dist[w][first] with the loop open, cycle_len[w] with it closed), one byte load and one compare per edge key in the loop
+// that writes the byte row, in front of the vote.  <false> is what ff_pointer_constrained and ff_decode_constrained launch.
+//
+// follow_distance_kernel: one wavefront per (wireframe, source edge b), four per block: a breadth-first search FORWARD from b
+// over the bit rows, which needs no transposed table.  Lane k holds words k, k + 64, ... of the reached, frontier and next sets
+// (FD_CHUNKS of them: L <= 2048 * FD_CHUNKS); a level walks the frontier's set bits wave-uniformly and ORs the successors' rows
+// into `next`, every word load coalesced and served from L2 (at most L rows of fw words per wave).  Each level stores the byte
+// of the newly reached edges x to close_dist[w][x][b] -- plain byte stores with stride L, one per element of the table -- and
+// b reached again is cycle_len[w][b].  What no level reached is stored as 255 at the end.
 #include <float.h>
 
 #include "ff_common.h"
@@ -38,6 +48,9 @@ struct ConstrainArgs {
   unsigned* visited;             // [B, fw] in / out: the edges of the prefix
   int *fin_out, *first_out, *prev_out, *dead_out;   // [B] out
   int* tok; float* logprob;      // [B] out
+  const unsigned char* close_dist;   // <true> only: [wireframes, L, L] bytes, close_dist[w][f][b] = D(b -> f)
+  const unsigned char* cycle_len;    // <true> only: [wireframes, L] bytes, D(b -> b)
+  int budget;                        // <true> only: T - 1 - the position this step selects
 };
 
 __global__ __launch_bounds__(256) void follow_table_kernel(const float* __restrict__ starts, const float* __restrict__ ends, int N,
@@ -64,6 +77,78 @@ __global__ __launch_bounds__(256) void follow_table_kernel(const float* __restri
   }
 }
 
+constexpr int FD_CHUNKS = 4;   // 64-word chunks of a bit row a lane holds: L <= 64 * 32 * FD_CHUNKS = 8192
+
+__global__ __launch_bounds__(256) void follow_distance_kernel(const unsigned* __restrict__ follows, int N, int L,
+                                                              const int* __restrict__ num_input, int hmax,
+                                                              unsigned char* __restrict__ close_dist,
+                                                              unsigned char* __restrict__ cycle_len) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long src = (long long)blockIdx.x * 4 + wv;
+  if (src >= (long long)N * L) return;   // (wave-uniform)
+  const int w = (int)(src / L), b = (int)(src % L), fw = (L + 31) >> 5;
+  int n = num_input[w];
+  n = n < 0 ? 0 : (n > L ? L : n);
+  const unsigned* rows = follows + (size_t)w * L * fw;
+  unsigned char* out = close_dist + (size_t)w * L * L + b;   // element x of this wave's column: out[x * L]
+  unsigned valid[FD_CHUNKS], reached[FD_CHUNKS], frontier[FD_CHUNKS];   // (valid: the edges below num_input of this lane's words)
+#pragma unroll
+  for (int c = 0; c < FD_CHUNKS; ++c) {
+    const int x0 = (c * 64 + lane) * 32;
+    valid[c] = x0 >= n ? 0u : (n - x0 >= 32 ? 0xffffffffu : (1u << (n - x0)) - 1u);
+    reached[c] = 0u;
+    frontier[c] = (b < n && (b >> 5) == c * 64 + lane) ? 1u << (b & 31) : 0u;
+  }
+  int cyc = 255;
+  for (int h = 1; h <= hmax; ++h) {
+    unsigned next[FD_CHUNKS];
+#pragma unroll
+    for (int c = 0; c < FD_CHUNKS; ++c) next[c] = 0u;
+#pragma unroll
+    for (int c = 0; c < FD_CHUNKS; ++c) {
+      unsigned long long lanes = __ballot(frontier[c] != 0u);
+      while (lanes) {   // (wave-uniform walk: every frontier word, then every set bit of it)
+        const int k = __builtin_ctzll(lanes);
+        lanes &= lanes - 1;
+        unsigned word = (unsigned)__builtin_amdgcn_readlane((int)frontier[c], k);
+        while (word) {
+          const int x = (c * 64 + k) * 32 + __builtin_ctz(word);   // (< n <= L: valid[] cleared everything else)
+          word &= word - 1;
+          const unsigned* xr = rows + (size_t)x * fw;
+#pragma unroll
+          for (int c2 = 0; c2 < FD_CHUNKS; ++c2)
+            if (c2 * 64 + lane < fw) next[c2] |= xr[c2 * 64 + lane];
+        }
+      }
+    }
+    bool any = false, self = false;   // self: the search came back to b, in the one lane that holds b's word
+#pragma unroll
+    for (int c = 0; c < FD_CHUNKS; ++c) {
+      next[c] &= valid[c] & ~reached[c];
+      reached[c] |= next[c];
+      frontier[c] = next[c];
+      any = any || next[c] != 0u;
+      self = self || ((b >> 5) == c * 64 + lane && ((next[c] >> (b & 31)) & 1u) != 0u);
+      unsigned word = next[c];
+      while (word) {   // the bytes of the newly reached edges
+        const int x = (c * 64 + lane) * 32 + __builtin_ctz(word);
+        word &= word - 1;
+        out[(size_t)x * L] = (unsigned char)h;
+      }
+    }
+    if (__ballot(self) != 0ull) cyc = h;
+    if (__ballot(any) == 0ull) break;
+  }
+#pragma unroll
+  for (int c = 0; c < FD_CHUNKS; ++c) {   // what no level reached, the rows at and beyond num_input included
+    const int x0 = (c * 64 + lane) * 32;
+    for (int j = 0; j < 32 && x0 + j < L; ++j)
+      if (!((reached[c] >> j) & 1u)) out[(size_t)(x0 + j) * L] = 255;
+  }
+  if (lane == 0) cycle_len[(size_t)w * L + b] = (unsigned char)cyc;
+}
+
+template <bool AHEAD>
 __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
@@ -87,6 +172,9 @@ __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs 
       const unsigned* frow = open ? a.follows + ((size_t)w * a.L + prev) * a.fw : nullptr;
       const unsigned* vrow = a.visited + (size_t)b * a.fw;
       unsigned char* xrow = a.rows + (size_t)b * S;
+      // (look-ahead: the distance of every edge to the loop's first edge while it is open, else the edge's own shortest cycle)
+      const unsigned char* drow = nullptr;
+      if (AHEAD && connect) drow = open ? a.close_dist + ((size_t)w * a.L + first) * a.L : a.cycle_len + (size_t)w * a.L;
       bool live_edge = false;
       for (int s = lane; s < S; s += 64) {
         bool masked;
@@ -96,6 +184,7 @@ __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs 
           const int e = s - ntok;
           const unsigned bit = 1u << (e & 31);
           masked = (norep && (vrow[e >> 5] & bit) != 0) || (open && (frow[e >> 5] & bit) == 0);
+          if (AHEAD && drow) masked = masked || (int)drow[e] > a.budget;
           bool pad = s >= kv;
           if (!pad && mrow) pad = ff_ldw(mrow + s) != 0;
           live_edge = live_edge || (!masked && !pad);
@@ -212,25 +301,34 @@ extern "C" int ff_follow_table(const float* starts, const float* ends, int N, in
   return FF_OK;
 }
 
-int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                                int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi,
-                                const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
-                                unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
-                                int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
-                                int* count_ge, int* arrive, int* host_slot, ff_stream_t stream) {
+namespace {
+// The one launch behind ff_pointer_constrained (ahead = false: the tables and the budget are not looked at) and
+// ff_pointer_constrained_ahead; `name` words the errors.
+int constrained_launch(const char* name, bool ahead, const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                       float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B, int seqs_per_group,
+                       const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi, const int* fin_in,
+                       const int* first_in, const int* prev_in, unsigned* visited, unsigned char* mask_rows, int* next_tok,
+                       float* logprob, int* fin_out, int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
+                       float* next_rows, int ldnext, float* next_stats, int* count_ge, int* arrive, int* host_slot,
+                       ff_stream_t stream) {
   if (B == 0) return FF_OK;
-  FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "ff_pointer_constrained: bad sizes B=%d S=%d", B, S);
-  FF_CHECK_ARG(logits && ldlogits >= S, "ff_pointer_constrained: logits missing or ldlogits < S");
-  FF_CHECK_ARG(!(flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "ff_pointer_constrained: unknown flag bits %d", flags);
-  FF_CHECK_ARG(ntok >= 0 && L >= 0 && L == S - ntok, "ff_pointer_constrained: L=%d must be S - ntok = %d - %d", L, S, ntok);
-  FF_CHECK_ARG(term_lo >= 0 && term_lo < term_hi && term_hi <= ntok, "ff_pointer_constrained: terminator range [%d, %d) empty or outside the %d special tokens",
-               term_lo, term_hi, ntok);
-  FF_CHECK_ARG(follows || !(flags & FF_CONSTRAIN_CONNECT), "ff_pointer_constrained: FF_CONSTRAIN_CONNECT needs the follow table");
+  FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "%s: bad sizes B=%d S=%d", name, B, S);
+  FF_CHECK_ARG(logits && ldlogits >= S, "%s: logits missing or ldlogits < S", name);
+  FF_CHECK_ARG(!(flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", name, flags);
+  FF_CHECK_ARG(ntok >= 0 && L >= 0 && L == S - ntok, "%s: L=%d must be S - ntok = %d - %d", name, L, S, ntok);
+  FF_CHECK_ARG(term_lo >= 0 && term_lo < term_hi && term_hi <= ntok, "%s: terminator range [%d, %d) empty or outside the %d special tokens",
+               name, term_lo, term_hi, ntok);
+  FF_CHECK_ARG(follows || !(flags & FF_CONSTRAIN_CONNECT), "%s: FF_CONSTRAIN_CONNECT needs the follow table", name);
   FF_CHECK_ARG(fin_in && first_in && prev_in && visited && mask_rows && next_tok && logprob && fin_out && dead_end && first_out && prev_out,
-               "ff_pointer_constrained: null pointer");
+               "%s: null pointer", name);
+  if (ahead) {
+    FF_CHECK_ARG(flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", name);
+    FF_CHECK_ARG(close_dist && cycle_len, "%s: close_dist and cycle_len are required", name);
+    FF_CHECK_ARG(budget >= 0 && budget <= 254, "%s: budget=%d outside 0..254", name, budget);
+  }
   ConstrainArgs a;
   memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_pointer_constrained", true, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
+  FF_RETURN_IF(ff_pointer_feedback(&a.p, name, true, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
   a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
   a.p.extra = mask_rows; a.p.ldextra = S;
   a.p.B = B; a.p.spg = seqs_per_group;
@@ -240,9 +338,67 @@ int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsign
   a.fin_in = fin_in; a.first_in = first_in; a.prev_in = prev_in; a.visited = visited;
   a.fin_out = fin_out; a.first_out = first_out; a.prev_out = prev_out; a.dead_out = dead_end;
   a.tok = next_tok; a.logprob = logprob;
+  a.close_dist = close_dist; a.cycle_len = cycle_len; a.budget = budget;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 4.0, st);
-  hipLaunchKernelGGL(pointer_constrained_kernel, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  if (ahead)
+    hipLaunchKernelGGL(pointer_constrained_kernel<true>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(pointer_constrained_kernel<false>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+}  // namespace
+
+// (the arguments the three entries below hand through unchanged)
+#define FF_CONSTRAINED_STEP_ARGS                                                                                                   \
+  logits, ldlogits, S, mask, kv_len, B, seqs_per_group, follows, L, flags, ntok, term_lo, term_hi, fin_in, first_in, prev_in,      \
+      visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out, memory, E, next_rows, ldnext, next_stats,     \
+      count_ge
+
+int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi,
+                                const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
+                                unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
+                                int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                                int* count_ge, int* arrive, int* host_slot, ff_stream_t stream) {
+  return constrained_launch("ff_pointer_constrained", false, nullptr, nullptr, 0, FF_CONSTRAINED_STEP_ARGS, arrive, host_slot, stream);
+}
+
+int ff_pointer_constrained_ahead_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                      int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo,
+                                      int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
+                                      unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
+                                      int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
+                                      float* next_stats, int* count_ge, const unsigned char* close_dist,
+                                      const unsigned char* cycle_len, int budget, int* arrive, int* host_slot, ff_stream_t stream) {
+  return constrained_launch("ff_pointer_constrained_ahead", true, close_dist, cycle_len, budget, FF_CONSTRAINED_STEP_ARGS, arrive,
+                            host_slot, stream);
+}
+
+extern "C" int ff_pointer_constrained_ahead(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                            int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo,
+                                            int term_hi, const int* fin_in, const int* first_in, const int* prev_in,
+                                            unsigned* visited, unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out,
+                                            int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
+                                            float* next_rows, int ldnext, float* next_stats, int* count_ge,
+                                            const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                                            ff_stream_t stream) {
+  return constrained_launch("ff_pointer_constrained_ahead", true, close_dist, cycle_len, budget, FF_CONSTRAINED_STEP_ARGS, nullptr,
+                            nullptr, stream);
+}
+
+extern "C" int ff_follow_distance(const unsigned* follows, int N, int L, const int* num_input, int hmax, unsigned char* close_dist,
+                                  unsigned char* cycle_len, ff_stream_t stream) {
+  FF_CHECK_ARG(hmax >= 1 && hmax <= 254, "ff_follow_distance: hmax=%d outside 1..254", hmax);
+  if (N == 0 || L == 0) return FF_OK;
+  FF_CHECK_ARG(N > 0 && L > 0 && follows && num_input && close_dist && cycle_len, "ff_follow_distance: bad sizes N=%d L=%d or a null pointer", N, L);
+  FF_CHECK_ARG(L <= 2048 * FD_CHUNKS && ((long long)N * L + 3) / 4 < (1LL << 31), "ff_follow_distance: L=%d above %d, or N*L not below 2^33", L,
+               2048 * FD_CHUNKS);
+  hipStream_t st = (hipStream_t)stream;
+  FFProfScope prof(FF_CAT_ROWOP, (double)N * L * L, st);
+  hipLaunchKernelGGL(follow_distance_kernel, dim3((unsigned)(((long long)N * L + 3) / 4)), dim3(256), 0, st, follows, N, L, num_input,
+                     hmax, close_dist, cycle_len);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }

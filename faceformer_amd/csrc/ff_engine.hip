@@ -35,6 +35,9 @@
 //   constrain (ff_decode_constrained): the default plan, one sequence per anchor.  ff_pointer_constrained masks
 //     the keys the enclosure walk could not accept; records and the rule's state (first, prev per step; visited words and the
 //     byte mask per sequence).
+//   constrain with look-ahead (ff_decode_constrained_ahead): constrain's plan, workspace, start state and packing;
+//     only the selection launch differs -- ff_pointer_constrained_ahead with budget = T - 1 - position and the two distance
+//     tables, operands offset per chunk as `follows` is.
 //   constrained beam (ff_decode_constrained_beam): the beam decode's plan, records and reorder with
 //     ff_beam_constrained_select as the selection; also the cumulative dead flag per step, the rule's state in two halves that
 //     the steps read and write alternately, and the byte mask per sequence.
@@ -355,14 +358,19 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
   const ff_beam_params* beam() const { return static_cast<const ff_beam_params*>(prm); }          // (each for its own kind only)
   const ff_forced_params* forced() const { return static_cast<const ff_forced_params*>(prm); }
   const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }
-  const ff_constrain_params* con() const { return static_cast<const ff_constrain_params*>(prm); }
+  const ff_constrain_ahead_params* ahead() const { return static_cast<const ff_constrain_ahead_params*>(prm); }
+  // (CONSTRAIN and CONSTRAIN_AHEAD: the four parameters the two share)
+  ff_constrain_params con() const {
+    if (kind != CONSTRAIN_AHEAD) return *static_cast<const ff_constrain_params*>(prm);
+    return ff_constrain_params{ahead()->flags, ahead()->follows, ahead()->logprob, ahead()->dead_end};
+  }
   const ff_constrain_beam_params* cbeam() const { return static_cast<const ff_constrain_beam_params*>(prm); }
 };
 
@@ -489,7 +497,8 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
       b.sm_fin = bp.take<int>((size_t)T * Btot);
       b.sm_row = bp.take<int>(Btot);
       break;
-    case Mode::CONSTRAIN: {
+    case Mode::CONSTRAIN:
+    case Mode::CONSTRAIN_AHEAD: {   // (the tables of the look-ahead are operands: nothing of it lies here)
       b.cn_lp = bp.take<float>((size_t)T * Btot);
       b.cn_fin = bp.take<int>((size_t)T * Btot);
       b.cn_dead = bp.take<int>((size_t)T * Btot);
@@ -1026,9 +1035,10 @@ struct DecodeRun {
       case Mode::SAMPLE:
         return ff_sample_init(buf.tok_all + c.b0, buf.sm_lp + c.b0, buf.sm_fin + c.b0, buf.sm_row + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F,
                               ni, pad_tok, p->term_lo, p->term_hi, st);
-      case Mode::CONSTRAIN: {
+      case Mode::CONSTRAIN:
+      case Mode::CONSTRAIN_AHEAD: {
         const int fw = (p->L + 31) / 32;
-        const unsigned* follows = mode.con()->follows;
+        const unsigned* follows = mode.con().follows;
         return ff_constrain_init(buf.tok_all + c.b0, buf.cn_lp + c.b0, buf.cn_fin + c.b0, buf.cn_dead + c.b0, buf.cn_first + c.b0,
                                  buf.cn_prev + c.b0, buf.cn_visited + (size_t)c.b0 * fw, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo,
                                  p->term_hi, m->num_token, follows ? follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, st);
@@ -1114,15 +1124,26 @@ struct DecodeRun {
                                       buf.tok_all + out, buf.sm_lp + out, buf.sm_fin + out, mem_w, E, next_rows, E, c.x0stat,
                                       buf.cnt_ge + slot, m->num_token, arrive, host_slot, st);
       }
-      case Mode::CONSTRAIN: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
+      case Mode::CONSTRAIN:
+      case Mode::CONSTRAIN_AHEAD: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
         const int L = p->L, fw = (L + 31) / 32;
-        const unsigned* follows = mode.con()->follows;
-        return ff_pointer_constrained_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, follows ? follows + (size_t)c.w0 * L * fw : nullptr,
-                                           L, mode.con()->flags, m->num_token,
-                                           p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in,
-                                           buf.cn_visited + (size_t)c.b0 * fw, buf.cn_rows + (size_t)c.b0 * S, buf.tok_all + out,
-                                           buf.cn_lp + out, buf.cn_fin + out, buf.cn_dead + out, buf.cn_first + out, buf.cn_prev + out,
-                                           mem_w, E, next_rows, E, c.x0stat, buf.cnt_ge + slot, arrive, host_slot, st);
+        const ff_constrain_params cp = mode.con();
+        const unsigned* follows = cp.follows ? cp.follows + (size_t)c.w0 * L * fw : nullptr;
+        unsigned* visited = buf.cn_visited + (size_t)c.b0 * fw;
+        unsigned char* byte_rows = buf.cn_rows + (size_t)c.b0 * S;
+        if (mode.kind == Mode::CONSTRAIN)
+          return ff_pointer_constrained_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, follows, L, cp.flags, m->num_token,
+                                             p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in, visited,
+                                             byte_rows, buf.tok_all + out, buf.cn_lp + out, buf.cn_fin + out, buf.cn_dead + out,
+                                             buf.cn_first + out, buf.cn_prev + out, mem_w, E, next_rows, E, c.x0stat,
+                                             buf.cnt_ge + slot, arrive, host_slot, st);
+        // the look-ahead: this step selects position t, so a loop has T - 1 - t further positions to close in
+        return ff_pointer_constrained_ahead_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, follows, L, cp.flags, m->num_token,
+                                                 p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in,
+                                                 visited, byte_rows, buf.tok_all + out, buf.cn_lp + out, buf.cn_fin + out,
+                                                 buf.cn_dead + out, buf.cn_first + out, buf.cn_prev + out, mem_w, E, next_rows, E,
+                                                 c.x0stat, buf.cnt_ge + slot, mode.ahead()->close_dist + (size_t)c.w0 * L * L,
+                                                 mode.ahead()->cycle_len + (size_t)c.w0 * L, T - 1 - t, arrive, host_slot, st);
       }
       case Mode::CONSTRAIN_BEAM: {
         // the constrained top-W selection (state half step & 1 -> half t & 1), then the beam decode's reorder of the prefixes
@@ -1343,8 +1364,9 @@ struct DecodeRun {
                                   c.Fc / G, c.f0, c.b0, mode.sample()->samples, mode.sample()->logprob, mode.sample()->scores, io.predict,
                                   io.seq_of_row, main_st);
       case Mode::CONSTRAIN:
+      case Mode::CONSTRAIN_AHEAD:
         return ff_constrain_finalize(buf.tok_all, buf.cn_lp, buf.cn_fin, buf.cn_dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
-                                     c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con()->logprob, mode.con()->dead_end, io.seq_of_row, main_st);
+                                     c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con().logprob, mode.con().dead_end, io.seq_of_row, main_st);
       case Mode::CONSTRAIN_BEAM:
         FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.bm_parent, buf.bm_score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0,
                                       c.nw, c.Fc / G, c.f0, c.b0, mode.cbeam()->beams, mode.cbeam()->scores, io.predict, io.seq_of_row,
@@ -1619,6 +1641,33 @@ extern "C" int ff_decode_constrained(const ff_model* m, const ff_decode_params* 
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::CONSTRAIN, 1, constrain));
+}
+
+extern "C" size_t ff_decode_constrained_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_AHEAD, 1));
+}
+
+extern "C" int ff_decode_constrained_ahead(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                           const unsigned char* mask, const int* kv_len, const int* num_input,
+                                           const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                                           int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                                           float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                                           size_t workspace_bytes, const ff_constrain_ahead_params* ahead, ff_stream_t stream) {
+  const char* name = "ff_decode_constrained_ahead";
+  FF_CHECK_ARG(m && p && ahead, "%s: null model, params or look-ahead params", name);
+  FF_RETURN_IF(check_opt_in(name, "the constrained decode with look-ahead is", p, extra_mask));
+  FF_CHECK_ARG(!(ahead->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", name, ahead->flags);
+  FF_CHECK_ARG(ahead->flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", name);
+  FF_CHECK_ARG(ahead->follows, "%s: FF_CONSTRAIN_CONNECT needs the follow table", name);
+  FF_CHECK_ARG(ahead->close_dist && ahead->cycle_len, "%s: close_dist and cycle_len are required", name);
+  FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the tables' byte)", name, p->T);
+  FF_CHECK_ARG(p->term_lo >= 0 && p->term_lo < p->term_hi && p->term_hi <= m->num_token,
+               "%s: terminator range [%d, %d) empty or outside the %d special tokens", name, p->term_lo, p->term_hi, m->num_token);
+  FF_RETURN_IF(check_opt_in_outputs(name, p, "logprob and dead_end", ahead->logprob && ahead->dead_end, trace_best, trace_second,
+                                    pointer_out));
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_AHEAD, 1, ahead));
 }
 
 extern "C" size_t ff_decode_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,

@@ -24,7 +24,7 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
-           "parse_parallel_samples_scored", "follow_table", "pack_follow_bits"]
+           "parse_parallel_samples_scored", "follow_table", "pack_follow_bits", "follow_distance"]
 
 
 def _tok(token, name, default):
@@ -378,6 +378,46 @@ def pack_follow_bits(table):
     padded[..., :L] = table
     words = (padded.reshape(table.shape[:-1] + (fw, 32)) << np.arange(32, dtype=np.uint64)).sum(axis=-1)
     return words.astype(np.uint32).view(np.int32)
+
+
+def follow_distance(table, hmax=254, num_input=None):
+    """The closing distances of a follow table, the numpy restatement of ff_follow_distance: the integers are the
+    kernel's.  table: bool [..., L, L], table[a, b] = edge b starts where edge a ends.  D(a -> b) is the least h >= 1 for which
+    there are a = x_0, ..., x_h = b with table[x_i, x_i+1] for every i; 255 = unreachable or more than hmax hops (1 <= hmax <=
+    254).  num_input (optional, one count per leading index): only edges below it take part; rows and columns at or beyond it are
+    255.  Returns (close_dist uint8 [..., L, L] with close_dist[f, b] = D(b -> f), cycle_len uint8 [..., L] = D(b -> b))."""
+    if isinstance(hmax, bool) or not isinstance(hmax, (int, np.integer)) or not 1 <= hmax <= 254:
+        raise ValueError("hmax=%r: must be in 1..254" % (hmax,))
+    t = np.asarray(table, dtype=bool)
+    L = t.shape[-1]
+    if t.ndim < 2 or t.shape[-2] != L:
+        raise ValueError("table must be [..., L, L]")
+    if num_input is not None:
+        ok = np.arange(L) < np.clip(np.asarray(num_input), 0, L).reshape(t.shape[:-2] + (1,))
+        t = t & ok[..., :, None] & ok[..., None, :]
+    if L == 0:
+        return np.zeros(t.shape, dtype=np.uint8), np.zeros(t.shape[:-1], dtype=np.uint8)
+    flat = t.reshape((-1, L, L))
+    dist = np.full(flat.shape, 255, dtype=np.uint8)       # dist[w, b, x] = D(b -> x): a breadth-first search from every b at once
+    nbytes = (L + 7) // 8
+    for w in range(flat.shape[0]):
+        packed = np.packbits(flat[w], axis=-1, bitorder="little")          # row x: the successors of x, eight to the byte
+        reach = np.zeros((L, L), dtype=bool)
+        new = flat[w].copy()                                                # level 1: the successors of every source
+        for h in range(1, int(hmax) + 1):
+            new &= ~reach
+            if not new.any():
+                break
+            dist[w][new] = h
+            reach |= new
+            rows, cols = np.nonzero(new)                                    # (sorted by source): OR the rows of the new edges
+            first = np.flatnonzero(np.r_[True, rows[1:] != rows[:-1]])
+            front = np.zeros((L, nbytes), dtype=np.uint8)
+            front[rows[first]] = np.bitwise_or.reduceat(packed[cols], first, axis=0)
+            new = np.unpackbits(front, axis=-1, count=L, bitorder="little").astype(bool)
+    dist = dist.reshape(t.shape)
+    close = np.ascontiguousarray(np.swapaxes(dist, -1, -2))
+    return close, np.ascontiguousarray(np.diagonal(dist, axis1=-2, axis2=-1))
 
 
 def is_face_enclosed(edges, face_indices, tol):

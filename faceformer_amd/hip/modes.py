@@ -118,6 +118,38 @@ def _constrain_beam_values(o):
     _constrain_values(o)
 
 
+def constrain_lookahead_value(lookahead, flags, constrain_beams=0):
+    """Whether the closure look-ahead is on (`constrain_lookahead`): only with constrain='loops' (`flags`:
+    constrain_flags of it -- the look-ahead masks under CONNECT) and not with constrain_beams."""
+    if not lookahead:
+        return False
+    if flags is None:
+        raise ValueError("constrain_lookahead needs constrain='loops': it is the closure look-ahead of the loop-constrained decode")
+    if not flags & _L.FF_CONSTRAIN_CONNECT:
+        raise ValueError("constrain_lookahead needs constrain='loops' (FF_CONSTRAIN_CONNECT): without it no loop is tracked")
+    if constrain_beams:
+        raise ValueError("constrain_lookahead excludes constrain_beams: the beam search over the constrained keys has no look-ahead")
+    return True
+
+
+def _constrain_ahead_values(o):
+    _constrain_values(o)
+    if o["T"] > 256:
+        raise ValueError("constrain_lookahead takes T <= 256 (got %d): the budget T - 2 must fit the tables' byte" % o["T"])
+    for name in ("close_dist", "cycle_len"):
+        if o[name] is None:
+            raise ValueError("constrain_lookahead needs close_dist and cycle_len (ops.follow_distance)")
+
+
+def _constrain_ahead_operand(eng, o):
+    _constrain_operand(eng, o)
+    L = o["S"] - eng.num_token
+    for name, shape in (("close_dist", (o["N"], L, L)), ("cycle_len", (o["N"], L))):
+        t = o[name]
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != shape:
+            raise ValueError("%s must be a uint8 tensor of shape [%s]" % (name, ", ".join(str(v) for v in shape)))
+
+
 def _constrain_operand(eng, o):
     L = o["S"] - eng.num_token
     shape = (o["N"], L, (L + 31) // 32)
@@ -203,6 +235,20 @@ CONSTRAIN_BEAM = CONSTRAIN._replace(
     prepare=lambda m, W, inputs, dev, T, N, F, ni, order: dict(
         CONSTRAIN.prepare(m, constrain_flags(m.constrain), inputs, dev, T, N, F, ni, order), constrain_beams=W))
 
+def _constrain_ahead_prepare(m, CF, inputs, dev, T, N, F, ni, order):
+    kw = CONSTRAIN.prepare(m, CF, inputs, dev, T, N, F, ni, order)
+    return dict(kw, constrain_lookahead=True, **m._follow_distance(inputs, dev, T, ni, order, kw["follow_table"]))
+
+
+# constrain='loops' with its option constrain_lookahead: the same decode with the closure look-ahead in the
+# selection launch.  Outside MODES, as CONSTRAIN_BEAM is; the two tables are operands beside follow_table.
+CONSTRAIN_AHEAD = CONSTRAIN._replace(
+    subject="constrain_lookahead", entry="ff_decode_constrained_ahead", values=_constrain_ahead_values, operand=_constrain_ahead_operand,
+    own=(("follow_table", _I32), ("close_dist", torch.uint8), ("cycle_len", torch.uint8)),
+    tail=lambda o, ptrs, traced: (C.byref(_L.ConstrainAheadParams(o["constrain"], _p(o["follow_table"]), _p(o["close_dist"]),
+                                                                  _p(o["cycle_len"]), *ptrs)),),
+    prepare=lambda *a: _constrain_ahead_prepare(*a))
+
 SAMPLE = Mode(
     subject="num_samples", excludes=_COMMON + ("beam_width",), entry="ff_decode_sample", per_anchor=True, values=_sample_values,
     values_first=True, operand=_sample_operand, own=(("uniforms", _F32),),
@@ -241,14 +287,16 @@ MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 
 
-def of_options(logprob=False, constrain_beams=0, **values):
+def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, **values):
     """(record, value) of the first of MODES whose option is set in `values` (constrain: the flag bits or None; num_samples;
     beam_width); else the greedy record (its logprob form with `logprob`) and None.  constrain with constrain_beams = W > 0:
-    the CONSTRAIN_BEAM record and W."""
+    the CONSTRAIN_BEAM record and W; with constrain_lookahead: the CONSTRAIN_AHEAD record and the flag bits."""
     for mode in MODES[:-1]:
         v = values[mode.subject]
         if v is not None and (v or mode is CONSTRAIN):
             if mode is CONSTRAIN and constrain_beams:
                 return CONSTRAIN_BEAM, constrain_beams
+            if mode is CONSTRAIN and constrain_lookahead:
+                return CONSTRAIN_AHEAD, v
             return mode, v
     return (GREEDY_LOGPROB if logprob else GREEDY), None

@@ -559,6 +559,14 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
     is clear.  Row b belongs to wireframe b // seqs_per_group of mask / kv_len / memory / follows.  Returns dict(next, fin,
     dead_end, first, prev [B] int32; logprob [B] fp32; visited; mask_rows [B, S] uint8: the rule's own mask of every unfinished
     row; [rows [B, E]]; [stats [B, E/32, 2]])."""
+    return _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
+                             want_rows, want_stats, counter, None)
+
+
+def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
+                      want_rows, want_stats, counter, ahead):
+    """pointer_constrained (ahead None) and pointer_constrained_ahead (ahead = (close_dist, cycle_len, budget)): the checks, the
+    outputs and the launch the two share."""
     _dev(logits, "logits")
     out = {}
     B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
@@ -595,11 +603,63 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
     one = torch.zeros(1, device=dev, dtype=torch.int32)
     vis = visited if fw else one
     fol = one if (follows is not None and not (L and fw)) else follows
-    _L.check(_L.load().ff_pointer_constrained(
+    entry, tail = "ff_pointer_constrained", ()
+    if ahead is not None:
+        close_dist, cycle_len, budget = ahead
+        if not flags & _L.FF_CONSTRAIN_CONNECT:
+            raise ValueError("the look-ahead needs FF_CONSTRAIN_CONNECT")
+        for x, name, shape in ((close_dist, "close_dist", (L, L)), (cycle_len, "cycle_len", (L,))):
+            _dev(x, name, torch.uint8)
+            if x.dim() != 1 + len(shape) or not x.is_contiguous() or x.size(0) < nw or tuple(x.shape[1:]) != shape:
+                raise ValueError("%s must be a contiguous uint8 [>= %d, %s] tensor" % (name, nw, ", ".join(str(v) for v in shape)))
+        if not 0 <= int(budget) <= 254:
+            raise ValueError("budget=%r: must be in 0..254" % (budget,))
+        byte = torch.zeros(1, device=dev, dtype=torch.uint8)      # (L = 0: nothing of the tables is read)
+        entry, tail = "ff_pointer_constrained_ahead", (_p(close_dist if L else byte), _p(cycle_len if L else byte), int(budget))
+    _L.check(getattr(_L.load(), entry)(
         _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(fol), L, flags, ntok, lo, hi, _p(fin), _p(first),
         _p(prev), _p(vis), _p(out["mask_rows"]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(out["dead_end"]),
-        _p(out["first"]), _p(out["prev"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter), _stream()), "ff_pointer_constrained")
+        _p(out["first"]), _p(out["prev"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter), *tail, _stream()), entry)
     return out
+
+
+@_on_tensor_device
+def pointer_constrained_ahead(logits, fin, first, prev, visited, flags, ntok, follows, close_dist, cycle_len, budget, memory=None,
+                              mask=None, kv_len=None, seqs_per_group=1, term_range=(1, 4), want_rows=False, want_stats=False,
+                              counter=None):
+    """pointer_constrained with the closure look-ahead (ff_pointer_constrained_ahead): under CONNECT an edge b is
+    also masked when close_dist[w][first][b] > budget (loop open) or cycle_len[w][b] > budget (loop closed).  close_dist
+    [W, L, L] / cycle_len [W, L] uint8 (ops.follow_distance), budget in 0..254: the positions left behind the one this step
+    selects.  Operands and results are pointer_constrained's; with both tables zero the results are too."""
+    return _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
+                             want_rows, want_stats, counter, (close_dist, cycle_len, budget))
+
+
+FOLLOW_DISTANCE_MAX_L = 8192
+
+
+@_on_tensor_device
+def follow_distance(follows, num_input, hmax):
+    """The closing distances of N wireframes' follow tables (ff_follow_distance).  follows [N, L, ceil(L/32)] int32
+    words (ops.follow_table), num_input [N] int32, hmax in 1..254.  Returns (close_dist [N, L, L] uint8: close_dist[w][f][b] =
+    D(b -> f), the least number of "follows" hops from edge b to edge f; cycle_len [N, L] uint8: D(b -> b)); 255: unreachable, more
+    than hmax hops, or an edge at or beyond num_input[w].  faces.follow_distance is the numpy restatement."""
+    if isinstance(hmax, bool) or not isinstance(hmax, int) or not 1 <= hmax <= 254:
+        raise ValueError("hmax=%r: must be in 1..254" % (hmax,))
+    _dev(follows, "follows", torch.int32), _dev(num_input, "num_input", torch.int32)
+    if follows.dim() != 3 or follows.size(2) != (follows.size(1) + 31) // 32:
+        raise ValueError("follows must be [N, L, ceil(L/32)]")
+    N, L = follows.size(0), follows.size(1)
+    if num_input.dim() != 1 or num_input.numel() != N:
+        raise ValueError("num_input must hold one count per wireframe")
+    if L > FOLLOW_DISTANCE_MAX_L:
+        raise ValueError("follow_distance takes at most %d edges per wireframe (got %d)" % (FOLLOW_DISTANCE_MAX_L, L))
+    follows, num_input = follows.contiguous(), num_input.contiguous()
+    close_dist = torch.empty((N, L, L), device=follows.device, dtype=torch.uint8)
+    cycle_len = torch.empty((N, L), device=follows.device, dtype=torch.uint8)
+    _L.check(_L.load().ff_follow_distance(_p(follows), N, L, _p(num_input), hmax, _p(close_dist), _p(cycle_len), _stream()),
+             "ff_follow_distance")
+    return close_dist, cycle_len
 
 
 @_on_tensor_device

@@ -76,6 +76,8 @@ class SurfaceFormerBase(nn.Module):
                                        # post_process.enclosedness_tol); inputs["follow_table"] overrides the built table
         self.constrain_beams = 0       # ... W in 1..8 = the beam search over the constrained keys, W beams per anchor;
                                        # 0 = the constrained greedy decode; only with constrain
+        self.constrain_lookahead = False   # ... with "loops": also mask every edge from which the loop cannot close within
+                                       # max_face_length; inputs["close_dist"] / ["cycle_len"] override the built tables
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
         self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
         self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
@@ -280,15 +282,19 @@ class SurfaceFormerBase(nn.Module):
         single-sequence model does not take; an opt-in mode needs the native engine and excludes what its record lists."""
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
+        look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
         if not parallel:
             if CB:
                 raise ValueError("constrain_beams is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
+            if look:
+                raise ValueError("constrain_lookahead is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
             for mode in reversed(_modes.MODES):
                 for sw in mode.switches:
                     if sw.seq2seq and sw.on(self):
                         raise ValueError("%s is a SurfaceFormer_Parallel option (%s)" % (sw.attr, sw.seq2seq))
             return (_modes.GREEDY_LOGPROB if getattr(self, "return_logprob", False) else _modes.GREEDY), None
-        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, constrain=CF,
+        LA = _modes.constrain_lookahead_value(look, CF, CB)
+        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, LA, constrain=CF,
                                         num_samples=int(getattr(self, "num_samples", 0) or 0), beam_width=int(getattr(self, "beam_width", 0) or 0))
         if value is not None:
             attr = mode.switches[0].attr
@@ -304,6 +310,10 @@ class SurfaceFormerBase(nn.Module):
             if mode is _modes.CONSTRAIN_BEAM:
                 _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, constrain_beams=value, follow_table=True,
                                                                S=inputs["input"].size(1) + self.num_token),
+                                     (int(self.token.face_type_offset), int(self.token.len)))
+            if mode is _modes.CONSTRAIN_AHEAD:      # (the tables are made behind the encoder: only T is checked here)
+                _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, follow_table=True, close_dist=True, cycle_len=True,
+                                                               T=self.max_face_length),
                                      (int(self.token.face_type_offset), int(self.token.len)))
         return mode, value
 

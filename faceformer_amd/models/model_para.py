@@ -52,7 +52,12 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         (bool N x L x L, or the packed int32 words N x L x ceil(L/32)), for the batch AS GIVEN.
         constrain_beams = W in 1..8 (default 0; only with constrain): the beam search over the constrained keys --
         predict_beams N x F x W x T, predict_beam_scores and predict_beam_dead_end N x F x W in place of predict_logprob; predict
-        and predict_dead_end are beam 0's."""
+        and predict_dead_end are beam 0's.
+        constrain_lookahead = True (default False; only with constrain = "loops", not with constrain_beams): the
+        constrained decode also masks every edge from which the loop cannot close within max_face_length; predict_dead_end then
+        also means "cannot close in time".  The two distance tables are built on the device from the follow table
+        (ops.follow_distance, hmax = max(T - 2, 1)), or taken from inputs["close_dist"] (uint8 N x L x L) and inputs["cycle_len"]
+        (uint8 N x L), for the batch AS GIVEN.  The published keys are constrain's."""
         label = inputs["label"]
         T = self.max_face_length
         mode, value = self._decode_mode(inputs, parallel=True)
@@ -138,6 +143,31 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         if order is not None:
             bits = bits.index_select(0, torch.tensor(order, device=device))
         return bits.contiguous()
+
+    def _follow_distance(self, inputs, device, T, num_input, order, bits):
+        """dict(close_dist [N, L, L], cycle_len [N, L]) uint8 of a decode with look-ahead in the DECODE's wireframe order: built on
+        the device from `bits` (the follow table, in that order already) with hmax = max(T - 2, 1), the largest budget a step
+        compares against; or inputs["close_dist"] / inputs["cycle_len"] for the batch as given, permuted like the wireframes
+        when they are decoded sorted by edge count (the edges of a wireframe keep their order: only the leading axis moves)."""
+        from ..hip import ops as _ops
+        N, L = inputs["input"].size(0), inputs["input"].size(1)
+        given = [inputs.get("close_dist"), inputs.get("cycle_len")]
+        if given[0] is None and given[1] is None:
+            ni = torch.tensor(num_input if order is None else [num_input[i] for i in order], dtype=torch.int32).to(device)
+            cd, cl = _ops.follow_distance(bits, ni, min(max(T - 2, 1), 254))
+            return {"close_dist": cd, "cycle_len": cl}
+        out = {}
+        for name, t, shape in (("close_dist", given[0], (N, L, L)), ("cycle_len", given[1], (N, L))):
+            if t is None:
+                raise ValueError("inputs['close_dist'] and inputs['cycle_len'] are given together")
+            t = torch.as_tensor(t)
+            if t.dtype != torch.uint8 or tuple(t.shape) != shape:
+                raise ValueError("%s must be uint8 [%s]" % (name, ", ".join(str(v) for v in shape)))
+            t = t.to(device)
+            if order is not None:
+                t = t.index_select(0, torch.tensor(order, device=device))
+            out[name] = t.contiguous()
+        return out
 
     def _sample_uniforms(self, inputs, device, T, N, F, R, order):
         """The uniforms [T-1, N*F*R] of a sampled decode in the DECODE's wireframe order: made (or given) for the batch as given,

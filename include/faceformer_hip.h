@@ -950,6 +950,74 @@ int ff_decode_constrained_beam(const ff_model* m, const ff_decode_params* p,
                                float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                                void* workspace, size_t workspace_bytes, const ff_constrain_beam_params* beam, ff_stream_t stream);
 
+/* ---- closure look-ahead for the loop-constrained pointer decode (opt-in, parallel variant; entries added within ABI 105;
+ * DESIGN.md 22).  The constrained decode above looks one edge ahead: it can select a connected edge from which the loop cannot
+ * close before the row runs out of positions.  Whether a loop can still close is a function of the follow table alone.
+ *
+ * Distances.  Take edges a, b < num_input[w].  D(a->b) is the least h >= 1 for which there are a = x_0, ..., x_h = b with
+ * follows[x_i][x_i+1] for every i.
+ *   - D(a->a) is the length of the shortest cycle through a.  It is 1 when the edge closes on itself.
+ *   - Stored as uint8.
+ *   - The value 255 means "unreachable, or more than hmax hops".  The search stops after hmax levels, 1 <= hmax <= 254.
+ *   - Rows and columns at or beyond num_input[w] are 255.
+ * Two tables come out of this:
+ *   - close_dist[w][f][b] = D(b->f).  Shape [N, L, L], contiguous in b, so the decode reads one row per sequence.
+ *   - cycle_len[w][b] = D(b->b).  Shape [N, L].
+ *
+ * Mask.  The step that selects position p (1 <= p <= T - 1) has budget = T - 1 - p.  For an unfinished row under CONNECT, on
+ * top of the masks of the constrained decode above:
+ *   - Loop open: edge b is also masked when close_dist[w][first][b] > budget.
+ *   - Loop closed: edge b is also masked when cycle_len[w][b] > budget.  A new loop that cannot close in time is not started.
+ *   - Everything else is the constrained decode's, unchanged.
+ *     - The dead-end vote runs after these masks.  It sees padding, kv_len, visited and the look-ahead.
+ *     - On a dead end the terminators are re-opened and dead_end = 1.
+ *     - Argmax takes the lowest index on ties.  logprob is under the renormalised row.
+ *     - State update, stop rule and padding anchors are as today.
+ *     - FF_DEDUP_PAD_ANCHORS keeps working.
+ * dead_end therefore now also means "cannot close within T".
+ *
+ * Limits of the guarantee.  The test is necessary, not sufficient.  It ignores visited, so a later dead end is still possible.
+ * What is guaranteed, and tested: at min(finish position, stop step) every sequence has either dead_end set or a closed state
+ * (first = none).
+ *
+ * Identity.  With both tables all zero, the result is the constrained decode's under FF_CONSTRAIN_NO_REPEAT |
+ * FF_CONSTRAIN_CONNECT ("loops"), bit for bit.
+ *
+ * ff_follow_distance: close_dist [N, L, L] and cycle_len [N, L] bytes from follows [N, L, ceil(L/32)] (ff_follow_table's words)
+ *   and num_input [N] (clamped into [0, L]; bits of edges at or beyond it are ignored).  L <= 8192.
+ * ff_pointer_constrained_ahead: ff_pointer_constrained's arguments, then close_dist [wireframes, L, L], cycle_len
+ *   [wireframes, L] and budget in 0..254; flags must hold FF_CONSTRAIN_CONNECT.
+ * ff_decode_constrained_ahead: ff_decode_constrained with ff_constrain_ahead_params; the step that selects position p runs
+ *   ff_pointer_constrained_ahead with budget = T - 1 - p.  Plan, workspace layout, start state and packing are
+ *   ff_decode_constrained's; the tables are operands, not workspace.
+ * FF_ERR_ARG before any launch for everything ff_decode_constrained rejects, CONNECT clear, a NULL table and T > 256 (the
+ * budget, at most 254, must fit the byte); ff_follow_distance: hmax outside 1..254.
+ * ff_decode_constrained_ahead_workspace_bytes equals ff_decode_constrained_workspace_bytes. */
+int ff_follow_distance(const unsigned int* follows, int N, int L, const int* num_input, int hmax, unsigned char* close_dist,
+                       unsigned char* cycle_len, ff_stream_t stream);
+int ff_pointer_constrained_ahead(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                 int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok, int term_lo,
+                                 int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned int* visited,
+                                 unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
+                                 int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
+                                 float* next_stats, int* count_ge, const unsigned char* close_dist, const unsigned char* cycle_len,
+                                 int budget, ff_stream_t stream);
+typedef struct ff_constrain_ahead_params {
+  int flags;
+  const unsigned int* follows;
+  const unsigned char* close_dist;
+  const unsigned char* cycle_len;
+  float* logprob;
+  int* dead_end;
+} ff_constrain_ahead_params;
+size_t ff_decode_constrained_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host);
+int ff_decode_constrained_ahead(const ff_model* m, const ff_decode_params* p,
+                                const float* memory, const unsigned char* mask, const int* kv_len,
+                                const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                                int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                                float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                                void* workspace, size_t workspace_bytes, const ff_constrain_ahead_params* ahead, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
