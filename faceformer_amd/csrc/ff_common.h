@@ -89,6 +89,7 @@ enum FFKnob {
   FF_K_RK_SPLIT_OLD, FF_K_RK_SPLIT_YOUNG, FF_K_RK_PHASE, FF_K_RK_ROTATE,   // K/V-resident attention probes
   FF_K_X3_NEED_N1024, FF_K_X3_NEED_N512,   // split products: rows needed by the 1024- / 512-column projections, in quarters of x3_min_rows
   FF_K_X2H_ATTN,                  // 1: cross-attention launches whose descriptor carries fp16 planes take the 2 x fp16 kernel
+  FF_K_LAST_FOLD_MIN_ROWS,        // pruned last layer: k | v folded into the query from this many active rows on (0: never)
   FF_K_COUNT
 };
 int ff_knob(int id);
@@ -187,6 +188,13 @@ int ff_constrain_beam_dead(const int* dead, int Btot, const int* steps_dev, cons
 
 // out[c, r] = in[r, c] for an [rows, cols] fp32 matrix (ff_rowops.hip; the engine's per-call transposes)
 int ff_transpose(const float* in, int ld_in, int rows, int cols, float* out, int ld_out, hipStream_t st);
+
+// The per-call tables of the folded last-layer self-attention (ff_attention_fold.hip), ONE block of
+// ff_attention_fold_table_floats(E, H, T) floats: kt [H, E + T, 64], the W operand of the head-batched qt | c product, then
+// ob [E], the self-attention out-projection's bias with the folded v bias carried through.  Weights only: one launch per call.
+size_t ff_attention_fold_table_floats(int E, int H, int T);
+int ff_attention_fold_tables(const float* ln1_w, const float* ln1_b, const float* ln1_pos, int pos_rows, const float* out_w,
+                             const float* out_b, int E, int H, int T, float* kt, float* ob, hipStream_t st);
 
 // partial-tile workspace of the 3 x bf16 kernel for (current device, stream): allocate now (ff_gemm_x3.hip).  Called across
 // translation units only, so hidden: the library exports exactly the ff_* symbols of include/faceformer_hip.h

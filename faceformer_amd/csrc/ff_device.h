@@ -74,6 +74,23 @@ __device__ __forceinline__ float ff_sum8(float v) {  // sum over the aligned gro
   return v;
 }
 
+// (mean, rstd) of a LayerNorm input row from the (mean, M2) statistics of its 32-column segments: Chan's update for equal parts
+// (no E[x^2] - mean^2 cancellation), two segments per lane, the eight lanes of an aligned group per row (nseg even, <= 16).
+// sv = the pairs of segments 2 * spart and 2 * spart + 1 (spart = lane & 7; zero where they do not exist).  -> (mean, biased
+// variance) on all eight lanes; rstd = 1.0f / sqrtf(var + eps) is left to the lanes that need it.  The arithmetic, statement for
+// statement, of the small-M projection tile below (ff_gemm_small_tile, MODE 1), which keeps its own text -- see there; used by
+// ff_attention_prefix_fold, whose x^ then has the bits that consumer forms.
+__device__ __forceinline__ f32x2 ff_ln_merge8(const f32x4& sv, int spart, int nseg) {
+  const bool sok = 2 * spart < nseg;
+  const float fn = (float)nseg;
+  const float mean = ff_sum8(sok ? sv.x + sv.z : 0.f) / fn;
+  const float m2 = ff_sum8(sok ? sv.y + sv.w : 0.f);
+  const float d0 = sv.x - mean, d1 = sv.z - mean;
+  const float dev = ff_sum8(sok ? d0 * d0 + d1 * d1 : 0.f);
+  const float var = (m2 + 32.f * dev) / (32.f * fn);
+  return f32x2{mean, var};
+}
+
 // LDS floats of one ff_gemm_small_tile instance
 __host__ __device__ constexpr int ff_gemm_small_lds_floats(int mode, int nw) {
   return nw * 16 * 64 + (mode == 2 ? 32 * 33 : 0) + (mode == 1 ? 64 : 0);
@@ -133,6 +150,8 @@ __device__ __forceinline__ void ff_gemm_small_tile(const GemmArgs& g, int tile, 
   float mu = 0.f, rs = 1.f;
   if (MODE == 1) {
     // Chan's update over the row's 32-column segments, two per lane, eight lanes per row (ln_nseg even, <= 16)
+    // (the text of ff_ln_merge8 above, kept in place: routed through the helper, the four-wave forms of this register-tuned
+    //  kernel come out with other device code than before, the eight-wave forms with the same)
     const bool sok = 2 * spart < g.ln_nseg;
     const float fn = (float)g.ln_nseg;
     const float mean = ff_sum8(sok ? sv.x + sv.z : 0.f) / fn;

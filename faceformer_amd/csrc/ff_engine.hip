@@ -231,6 +231,8 @@ struct DecodeBuffers {
   unsigned char* kvp[FF_MAX_LAYERS];   // fp16 planes of the cross-attention K | V (2 x fp16 attention kernel) or null
   float *x0_all, *qkv0_all;
   float* x0stat_all;   // [Btot, E/32, 2] LayerNorm segment statistics of the NEWEST x0 rows (written by the pointer launches)
+  float *fold_kt, *fold_ob;         // folded last-layer self-attention (FF_LAST_FOLD_MIN_ROWS): the per-call tables
+                                    // kt [H, E + T, 64] and ob [E] (ff_attention_fold_tables), one block; or null
   float *projT, *pg_all, *pc_all;   // folded project + pointer GEMM of one-wireframe micro-batches (see pointer_fold): the transposed
                                     // folded project weight [E, E]; per micro-batch G = memory_w W' [S, E] and c = memory_w b' [S4]
   int* tok_all;   // [T, Btot] global, position-major
@@ -399,6 +401,7 @@ struct EngineKnobs {
   bool l0_fold, pointer_fold, dbg_timing;
   bool x2h_attn;             // cross-attention K | V also as fp16 planes (FF_X2H_ATTN, with the fp16 split products in use)
   int one_launch_rows, pinned;
+  int last_fold_rows;        // pruned last layer: k | v folded into the query from this many active rows on (0: never)
 };
 EngineKnobs engine_knobs(const ff_decode_params* p) {
   EngineKnobs k;
@@ -407,6 +410,7 @@ EngineKnobs engine_knobs(const ff_decode_params* p) {
   k.dbg_timing = ff_knob(FF_K_DEBUG_TIMING) != 0;
   k.x2h_attn = ff_knob(FF_K_X2H_ATTN) != 0;
   k.one_launch_rows = ff_knob(FF_K_LAST_QKV_ONE_LAUNCH_ROWS);
+  k.last_fold_rows = ff_knob(FF_K_LAST_FOLD_MIN_ROWS);
   const int pc = ff_knob(FF_K_PINNED_COUNTERS);
   k.pinned = pc > 0 && pc < FF_PINNED_SLOTS ? pc : FF_PINNED_SLOTS;
   return k;
@@ -452,6 +456,10 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
   // (FF_POINTER_FOLD=0 / FF_NO_POINTER_FOLD: project and the pointer GEMM as two launches, as before round 5)
   const bool pf = kn.pointer_fold && can_fuse_layernorm(m, p);
   b.projT = pf ? bp.take<float>((size_t)E * E) : nullptr;
+  // (FF_LAST_FOLD_MIN_ROWS = 0, or more rows than a step of this call can have: no folded last layer, no tables)
+  const bool lf = kn.last_fold_rows > 0 && Rmax >= (size_t)kn.last_fold_rows && (p->flags & FF_LAST_LAYER_LAST_ROW) && m->num_dec_layers > 1 && can_fuse_layernorm(m, p);
+  b.fold_kt = lf ? bp.take<float>(ff_attention_fold_table_floats(E, m->H, T)) : nullptr;
+  b.fold_ob = b.fold_kt ? b.fold_kt + (size_t)m->H * (E + T) * 64 : nullptr;
   b.pg_all = pf ? bp.take<float>(nch * (size_t)S * E) : nullptr;
   b.pc_all = pf ? bp.take<float>(nch * (size_t)((S + 3) & ~3)) : nullptr;
   for (int s = 0; s < ns; ++s) {
@@ -592,6 +600,7 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
     const bool last = prune_last && (l == nd - 1);
     const float* xin = (l == 0) ? ck.x0 : buf.x;
     const float* QKV = buf.qkv;
+    bool fold_last = false;   // the pruned layer with k | v folded into the query: o is written by its own launches below
     // ---- self attention: q = k = LN1(x) + qpos, v = LN1(x), no mask (transformer.py:242-246) ----
     if (l == 0 && reuse0) {
       if (full_rows) {
@@ -609,15 +618,35 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
       }
       QKV = ck.qkv0;
     } else if (fuse && l > 0) {
+      // Third form of the pruned layer, from FF_LAST_FOLD_MIN_ROWS active rows on: k | v of the prefix rows are
+      // not projected at all.  q of the newest rows as in the two-launch form (the same launch: q keeps its bits); qt | c =
+      // q_h [W'k_h | kb_h] (head-batched, K = 64); ONE pass over the prefix rows and their statistics leaves u_h = sum_j p_j x^_j;
+      // o_h = u_h W'v_h^T (head-batched) into the o rows the out-projection reads -- its bias is then the table's ob, which
+      // carries b'v.  qt | c and u lie in the feed-forward scratch h, dead until this layer's linear1.
+      const size_t qt_floats = ff_align_up((size_t)Bc * H * (E + t), 4);
+      fold_last = last && t > 1 && bufs.fold_kt && R >= kn.last_fold_rows && !step_splits(m, prm, R) &&
+                  qt_floats + (size_t)Bc * H * E <= (size_t)(T - 1 > 0 ? T - 1 : 1) * Bc * FFd;
       // the LayerNorm-folded projection over all R rows that opens layer l > 0: q|k|v, or k|v alone (weight rows and output
       // columns from c0 = E on) when the layer is pruned to its newest position; its q then covers the last Bc rows only
       const bool kv_only = last && t > 1 && !last_qkv_one;
       const int c0 = kv_only ? E : 0;
-      FF_RETURN_IF(proj(Proj().in(buf.x, E).weight(w.ln1_w + (size_t)c0 * E, E, w.ln1_b + c0).split(w.ln1_planes, 3 * E, c0, w.ln1_csum)
-                            .norm(buf.lnstat).pos(w.ln1_pos + c0, 2 * E, 2 * E - c0).out(buf.qkv + c0, 3 * E, R, 3 * E - c0, E)));
-      if (kv_only)
+      if (!fold_last)
+        FF_RETURN_IF(proj(Proj().in(buf.x, E).weight(w.ln1_w + (size_t)c0 * E, E, w.ln1_b + c0).split(w.ln1_planes, 3 * E, c0, w.ln1_csum)
+                              .norm(buf.lnstat).pos(w.ln1_pos + c0, 2 * E, 2 * E - c0).out(buf.qkv + c0, 3 * E, R, 3 * E - c0, E)));
+      if (kv_only || fold_last)
         FF_RETURN_IF(proj(Proj().in(xin + newoff * E, E).weight(w.ln1_w, E, w.ln1_b).norm(buf.lnstat + newoff * nseg * 2)
                               .pos(w.ln1_pos + (size_t)(t - 1) * 2 * E, 2 * E, E).out(buf.qkv + newoff * 3 * E, 3 * E, Bc, E, E)));
+      if (fold_last) {
+        float* qt = buf.h;
+        float* u = buf.h + qt_floats;
+        FF_RETURN_IF(ff_gemm_f32_batched(buf.qkv + newoff * 3 * E, 3 * E, nullptr, 0, bufs.fold_kt, FF_HEAD_DIM, nullptr, nullptr, 0,
+                                         qt, H * (E + t), Bc, E + t, FF_HEAD_DIM, 0, 0, H, FF_HEAD_DIM,
+                                         (long long)(E + T) * FF_HEAD_DIM, E + t, st));
+        FF_RETURN_IF(ff_attention_prefix_fold(buf.x, buf.lnstat, m->ln_eps, qt, 0.125f, Bc, t, E, H, u, st));
+        FF_RETURN_IF(ff_gemm_f32_batched(u, H * E, nullptr, 0, w.ln1_w + (size_t)2 * E * E, E, nullptr, nullptr, 0,
+                                         buf.o + newoff * E, E, Bc, FF_HEAD_DIM, E, 0, 0, H, E, (long long)FF_HEAD_DIM * E,
+                                         FF_HEAD_DIM, st));
+      }
     } else {
       FF_RETURN_IF(ff_layernorm(xin, E, w.norm1_w, w.norm1_b, m->ln_eps, buf.y, E, buf.yq, E, qpos, E, Bc, T, R, E, st));
       // Not step_splits(): this picks the launch FORM, not the kernel.  From x3_min_rows rows on (no per-width factor, no
@@ -644,7 +673,7 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
     float* qc = buf.qkv + roff * E;   // cross-attention q: a [rows, E] view of the q|k|v scratch
     // folded steps: every projection with a residual leaves the statistics of its rows, the next projection normalises with them
     float* stat = fuse ? buf.lnstat + roff * nseg * 2 : nullptr;
-    {
+    if (!fold_last) {
       ff_attn_desc d;
       memset(&d, 0, sizeof(d));
       d.q = QKV + roff * 3 * E; d.k = QKV + E; d.v = QKV + 2 * E; d.o = o;
@@ -654,7 +683,7 @@ int decoder_pass(const ff_model* m, const ff_decode_params* prm, const EngineKno
       d.nk = t; d.k_group_stride = 1; d.k_stride = Bc;
       FF_RETURN_IF(ff_attention(&d, st));
     }
-    FF_RETURN_IF(proj(Proj().in(o, E).weight(sa.out_w, E, sa.out_b).split(w.self_out_planes, E).add(xin + roff * E, E)
+    FF_RETURN_IF(proj(Proj().in(o, E).weight(sa.out_w, E, fold_last ? bufs.fold_ob : sa.out_b).split(w.self_out_planes, E).add(xin + roff * E, E)
                           .out(x, E, Rl, E, E).stats(stat)));
     // ---- cross attention: q = LN2(x) + qpos, k = memory + pos, v = memory (transformer.py:247-252);
     //      K/V come from the per-batch cache ----
@@ -989,6 +1018,11 @@ struct DecodeRun {
         memcpy(st_fin, hfin.data(), sizeof(int) * (size_t)Btot);
         FF_CHECK_HIP(hipMemcpyAsync(buf.fin, st_fin, sizeof(int) * (size_t)Btot, hipMemcpyHostToDevice, main_st));
       }
+    }
+    if (buf.fold_kt) {   // the folded last layer's tables (weights only)
+      const ff_layer_weights& w = m->dec[m->num_dec_layers - 1];
+      FF_RETURN_IF(ff_attention_fold_tables(w.ln1_w, w.ln1_b, w.ln1_pos, m->qpos_len, w.self_attn.out_w, w.self_attn.out_b, E, m->H, T,
+                                            buf.fold_kt, buf.fold_ob, main_st));
     }
     FF_RETURN_IF(fork());
     // pointer_fold operands of the one-wireframe micro-batches: G = memory_w W' ([S, E]; W' = the folded project weight, used

@@ -217,6 +217,7 @@ SIGNATURES = {
     "ff_set_x3_tuning": (C.c_int, [C.c_int]),
     "ff_attention": (C.c_int, [C.POINTER(AttnDesc), fptr]),
     "ff_attention_general": (C.c_int, [C.POINTER(AttnGeneralDesc), fptr]),
+    "ff_attention_prefix_fold": (C.c_int, [fptr, fptr, C.c_float, fptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr]),
     "ff_set_attention_algo": (C.c_int, [C.c_int]),
     "ff_attention_planes_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ff_attention_split_kv": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr]),

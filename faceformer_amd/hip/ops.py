@@ -317,6 +317,23 @@ def attention_general(q, k, v, num_groups, num_heads, head_dim, nq, nk, q_group_
 
 
 @_on_tensor_device
+def attention_prefix_fold(x, stats, qt, Bc, t, E, H, eps=1e-5, scale=0.125, out=None):
+    """ff_attention_prefix_fold: u [Bc, H*E] = sum_j softmax_j(scale (qt . x^_j + c_j)) x^_j over the first t positions of the
+    position-major rows x ([>= t*Bc, E], row j*Bc + b) with segment statistics stats ([>= t*Bc, E/32, 2]); qt [Bc, H, E + t] holds
+    qt | c.  The tensors are handed over as they are (contiguous; views into larger buffers are fine)."""
+    _dev(x, "x"), _dev(stats, "stats"), _dev(qt, "qt")
+    for name, a in (("x", x), ("stats", stats), ("qt", qt)):
+        if not a.is_contiguous():
+            raise ValueError("attention_prefix_fold: %s must be contiguous" % name)
+    if out is None:
+        out = torch.empty((Bc, H * E), device=x.device, dtype=torch.float32)
+    _dev(out, "out")
+    _L.check(_L.load().ff_attention_prefix_fold(_p(x), _p(stats), eps, _p(qt), scale, Bc, t, E, H, _p(out), _stream()),
+             "ff_attention_prefix_fold")
+    return out
+
+
+@_on_tensor_device
 def pointer_argmax(p, memory, mask=None, kv_len=None, extra_mask=None, seqs_per_group=1,
                    want_logits=False, want_rows=False, counters=None, ge_bound=0, eq_value=0, want_logprob=False):
     """select_next: returns dict(next, best, second, [logits], [rows], [logprob]).

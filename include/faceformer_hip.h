@@ -337,8 +337,30 @@ typedef struct ff_attn_general_desc {
 } ff_attn_general_desc;
 int ff_attention_general(const ff_attn_general_desc* desc, ff_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Self-attention of the pruned last decoder layer with k | v folded into the query (entry added within ABI 105; DESIGN.md 23;
+ * reference transformer.py:242-246 for the newest position only).  With x^_j = (x_j - mean_j) rstd_j the LayerNorm-normalised
+ * prefix rows and W', b', P the folded in-projection (ff_fold_layernorm_linear),
+ *   q_h . k_{j,h} = (q_h W'k_h) . x^_j + q_h . (b'k_h + P[j, k columns of head h])  =  qt_h . x^_j + c_{h,j}
+ *   o_h = sum_j p_j v_{j,h} = (sum_j p_j x^_j) W'v_h^T + b'v_h                      =  u_h W'v_h^T + b'v_h
+ * and this entry is the pass in the middle: per sequence b and head h
+ *   s_j = scale (qt[b,h,0:E] . x^_j + qt[b,h,E + j]),   p = softmax_j(s) over j < t,   u[b, h E : (h+1) E] = sum_j p_j x^_j.
+ *   x     [t * Bc, E]          the running rows, row j * Bc + b (position-major, contiguous)
+ *   stats [t * Bc, E / 32, 2]  their (mean, M2) per 32-column segment, as ln_stats_out of ff_gemm_f32_ln leaves them; merged to
+ *                              (mean, rstd) by Chan's update, x^ = (x - mean) * rstd as the LayerNorm-folded consumers form it
+ *   qt    [Bc, H, E + t]       qt | c (contiguous; any 4-byte alignment),   u [Bc, H * E]
+ * E % 64 == 0, 128 <= E <= 512, H = E / 64 (the range of the LayerNorm-folded decode); (2 + H) t + H + 3 <= 12000 (the scores
+ * a block keeps: t <= 1199 at E = 512); x / stats / u 16-byte aligned; anything else returns FF_ERR_ARG.  Rows >= t * Bc of x and
+ * stats are not read.  Plain fp32 on the vector units, one block per sequence, fixed summation order (the result depends on the
+ * operands alone); the normalised rows stay in LDS between the score and the u pass while t * E floats fit beside the scores in
+ * 150 KB, and are re-formed from x otherwise (same values, same order).  Counted under the attention category of the
+ * measurement hooks. */
+int ff_attention_prefix_fold(const float* x, const float* stats, float ln_eps, const float* qt, float scale,
+                             int Bc, int t, int E, int H, float* u, ff_stream_t stream);
+
 /* Tuning knobs (round 6): every A/B switch of the library is one int in one table.  `name` is the environment
  * variable that initialises the knob when the library is first used (FF_L0_FOLD, FF_POINTER_FOLD, FF_LAST_QKV_ONE_LAUNCH_ROWS,
+ * FF_LAST_FOLD_MIN_ROWS,
  * FF_PINNED_COUNTERS, FF_DEBUG_TIMING, FF_DMA_MIN_ROWS, FF_DMA_MIN_ROWS_N512, FF_DMA_MIN_ROWS_WIDE, FF_SK_HYBRID, FF_SK_HYBRID_FIX,
  * FF_SK_HYBRID_MAXLEFT8, FF_SK_HYBRID_MINU, FF_SK_HYBRID_FORCE, FF_NO_PANEL, FF_X3_SMALL_SPLIT, FF_RK_SPLIT_OLD, FF_RK_SPLIT_YOUNG,
  * FF_RK_PHASE, FF_RK_ROTATE).  ff_set_tuning changes it for the process (tests and tools flip knobs without child processes);
