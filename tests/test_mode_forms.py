@@ -5,8 +5,14 @@ oracle comparisons are the mode tests' own helpers.
 
 Forms (FORMS): model attributes, per-call decode options (all read from the model by the mode tests' _decode / _score) and
 tuning knobs (set in-process with ops.set_tuning, back with ops.reset_tuning in a `finally`).
-  arithmetic forms   f32, fp16x2, fp16x2_f32attn, bf16x3, fp16, no_l0_fold, unfused_ln: checks 1, 2, 3
+  arithmetic forms   f32, last_fold, fp16x2, fp16x2_f32attn, bf16x3, fp16, no_l0_fold, unfused_ln: checks 1, 2, 3
   scheduling forms   no_pointer_fold, last_qkv_apart, drained, two_streams: checks 1, 2 (drained, two_streams also 4)
+f32 and last_fold are the two sides of the pruned last layer's third form on the f32 matrix cores: f32 sets
+FF_LAST_FOLD_MIN_ROWS = 0, so that no step of any mode folds k | v into the query however many rows beams and samples make of a
+step (left at the package's 2048 rows, some steps of the beam and sampling calls folded and the others did not); last_fold sets it
+to 1 with FF_LAST_QKV_ONE_LAUNCH_ROWS = 0, so that every step after the first folds, and is compared with f32_unfolded: f32 with
+the same FF_LAST_QKV_ONE_LAUNCH_ROWS, i.e. the two-launch form the fold replaces, at every step.  Under last_fold every mode also
+profiles its own traced call against that base (_check_fold_ran): the modes multiply rows and reorder sequences between steps.
 The last six run on the package kind with x3_min_rows = 1, with one exception: with the split planes bound from row 1 the
 engine folds no LayerNorm at E != 512 (ff_engine.hip, step_fuses: the split kernels fold at K = 512 only), and the fold is
 what no_l0_fold, no_pointer_fold, unfused_ln and last_qkv_apart switch.  On par_small_ragged (E = 128) these four keep the
@@ -67,7 +73,8 @@ SEQ_GOLDEN = "seq_full_A4_gain4"          # forced and greedy-logprob only
 # from 512 query tiles on, which no golden of this module reaches), as test_fp16_decode_against_fp64_truth does
 X2H = dict(attention_algo=4)
 FORMS = {
-    "f32": dict(attrs=dict(x3_min_rows=0)),
+    "f32": dict(attrs=dict(x3_min_rows=0), knobs=dict(FF_LAST_FOLD_MIN_ROWS=0)),
+    "last_fold": dict(attrs=dict(x3_min_rows=0), knobs=dict(FF_LAST_FOLD_MIN_ROWS=1, FF_LAST_QKV_ONE_LAUNCH_ROWS=0), base="f32_unfolded"),
     "fp16x2": dict(attrs=dict(x3_min_rows=1), **X2H),
     "fp16x2_f32attn": dict(attrs=dict(x3_min_rows=1), knobs=dict(FF_X2H_ATTN=0), base="fp16x2", **X2H),
     "bf16x3": dict(attrs=dict(x3_min_rows=1, split_kind="bf16x3")),
@@ -80,9 +87,10 @@ FORMS = {
     "drained": dict(attrs=dict(x3_min_rows=1), one_wireframe=True, knobs=dict(FF_PINNED_COUNTERS=8), base="one_wireframe", **X2H),
     "two_streams": dict(attrs=dict(x3_min_rows=1, num_streams=2), one_wireframe=True, base="one_wireframe", **X2H),
     "one_wireframe": dict(attrs=dict(x3_min_rows=1), one_wireframe=True, **X2H),   # (no form of the matrix: the base of three)
+    "f32_unfolded": dict(attrs=dict(x3_min_rows=0), knobs=dict(FF_LAST_FOLD_MIN_ROWS=0, FF_LAST_QKV_ONE_LAUNCH_ROWS=0)),   # (the base of last_fold)
 }
-MATRIX_FORMS = [f for f in FORMS if f != "one_wireframe"]
-ARITHMETIC = ("f32", "fp16x2", "fp16x2_f32attn", "bf16x3", "fp16", "no_l0_fold", "unfused_ln")
+MATRIX_FORMS = [f for f in FORMS if f not in ("one_wireframe", "f32_unfolded")]
+ARITHMETIC = ("f32", "last_fold", "fp16x2", "fp16x2_f32attn", "bf16x3", "fp16", "no_l0_fold", "unfused_ln")
 BIT_EQUAL = ("drained", "two_streams")
 SPLIT_KIND = {"bf16x3": "bf16x3", "fp16": "fp16"}                                # (every other form: the package kind)
 
@@ -166,6 +174,22 @@ def _tuned(form):
     finally:
         ops.reset_tuning()
         ops.set_attention_algo(old)
+
+
+@contextlib.contextmanager
+def _base_knobs(form):
+    """Inside _tuned(form): the tuning table of the form's base, and the form's own back afterwards."""
+    from faceformer_amd.hip import ops
+    saved = {k: ops.get_tuning(k) for k in FORMS[form].get("knobs", {})}
+    ops.reset_tuning()
+    try:
+        for k, v in FORMS[FORMS[form]["base"]].get("knobs", {}).items():
+            ops.set_tuning(k, v)
+        yield
+    finally:
+        ops.reset_tuning()
+        for k, v in saved.items():
+            ops.set_tuning(k, v)
 
 
 def _record(line):
@@ -364,16 +388,21 @@ def _took_effect(m, out, cnt):
     base = FORMS[m.form].get("base")
     if base is None:
         return
-    saved = {k: ops.get_tuning(k) for k in FORMS[m.form].get("knobs", {})}
-    ops.reset_tuning()
-    try:
+    with _base_knobs(m.form):
         ref, base_cnt = _launches(lambda: _greedy(_base(m)))
         base_ws = _workspace_bytes(_base(m))
-    finally:
-        for k, v in saved.items():
-            ops.set_tuning(k, v)
     if m.form in ("unfused_ln", "no_l0_fold"):
         assert cnt[2] > base_cnt[2], (m.what, cnt, base_cnt)
+    if m.form == "last_fold":
+        # every step after the first, every micro-batch: the q, qt | c and o products in place of the k | v and q launches; the
+        # per-call tables are one row-op launch and exactly one 256-byte aligned block kt [H, E + T, 64] | ob [E] of the workspace
+        ran = _steps_run(out)
+        assert ran == _steps_run(ref) >= 3, (m.what, ran)
+        more = cnt[0] - base_cnt[0]
+        assert more > 0 and more % (ran - 1) == 0, (m.what, cnt, base_cnt, ran)
+        assert cnt[4] == base_cnt[4] + 1 and cnt[2] == base_cnt[2], (m.what, cnt, base_cnt)
+        E = m.case["model"]["E"]
+        assert _workspace_bytes(m) - base_ws == -(-4 * ((E // 64) * (E + m.T) * 64 + E) // 256) * 256, m.what
     if m.form == "last_qkv_apart":                             # k|v and q of the pruned last layer: one more GEMM per step
         assert cnt[0] + cnt[6] > base_cnt[0] + base_cnt[6] and cnt[2] == base_cnt[2], (m.what, cnt, base_cnt)
     if m.form == "fp16x2_f32attn":                             # no fp16 planes of the cross-attention K | V in the workspace,
@@ -388,6 +417,25 @@ def _took_effect(m, out, cnt):
         assert m.model.chunk_wireframes == 1 and m.T * m.N > ops.get_tuning("FF_PINNED_COUNTERS") == 8, m.what
     if m.form == "two_streams":                                # at least two micro-batches: the decode forks
         assert m.model.num_streams == 2 and m.model.chunk_wireframes == 1 and m.N >= 2, m.what
+
+
+def _steps_run(out):
+    """The steps a call enqueued, from its own report (the executed steps and those the stop rule noticed late)."""
+    return sum(1 for v in out["slots_per_step"] if v > 0)
+
+
+def _check_fold_ran(m, call, what):
+    """last_fold: `call` (a mode's traced call) profiled under the form and under its base's knobs -- more f32 GEMM launches, the
+    tables' row-op launch, as many LayerNorm launches: the fold ran in this mode, not only in the greedy decode."""
+    if m.form != "last_fold":
+        return
+    out, cnt = _launches(lambda: call(m))
+    with _base_knobs(m.form):
+        ref, base_cnt = _launches(lambda: call(_base(m)))
+    # (the same steps in both: the launch counts differ by the form alone; a scoring call reports its steps only)
+    assert out["steps"] == ref["steps"] and out.get("slots_per_step") == ref.get("slots_per_step"), (m.what, what)
+    _record("launch %-17s %-15s %s: by category without / with the fold %s %s" % (m.name, m.form, what, base_cnt[:7], cnt[:7]))
+    assert cnt[0] > base_cnt[0] and cnt[4] == base_cnt[4] + 1 and cnt[2] == base_cnt[2], (m.what, what, cnt, base_cnt)
 
 
 # ---- greedy with log-probabilities --------------------------------------------------------------------------------------------------
@@ -430,6 +478,7 @@ def test_beam(hip_lib, name, form, monkeypatch):
         one = _beam(m, 1)
         greedy = _greedy(m)
         _check_bit_equal(m, lambda b: _beam(b, W, trace=True), m.what)                            # check 4
+        _check_fold_ran(m, lambda b: _beam(b, W, trace=True), "beam")
     # check 1: test_engine_beams_replay_under_the_numpy_rule
     beams = out["beams"].cpu().numpy()
     got_scores = out["beam_scores"].cpu().numpy().astype(np.float64)
@@ -471,6 +520,7 @@ def test_sample(hip_lib, name, form, monkeypatch):
         scored = _sample(m, 2, (1.0, 0, 1.0), 5)[0]
         greedy = _greedy(m)
         _check_bit_equal(m, lambda b: _sample(b, R, SR.REPLAY_PARAMS[1], SR.REPLAY_SEEDS[name], trace=True)[0], m.what)  # check 4
+        _check_fold_ran(m, lambda b: _sample(b, R, SR.REPLAY_PARAMS[1], SR.REPLAY_SEEDS[name], trace=True)[0], "sample")
     shares = []
     for params, out, u in replays:                                                                # check 1
         dec, left = _replay(out, u, *params, m.T, (m.what, params))
@@ -510,6 +560,7 @@ def test_constrain(hip_lib, name, form, monkeypatch):
         clear = _constrain(m, 0, lattice=False)
         greedy = _greedy(m)
         _check_bit_equal(m, lambda b: _constrain(b, LOOPS, trace=True), m.what)                   # check 4
+        _check_fold_ran(m, lambda b: _constrain(b, LOOPS, trace=True), "constrain")
     pairs, _ = _replay(out, LOOPS, table, max(lat["num_input"]), m.T, m.what)                     # check 1: nothing left out
     assert pairs > 0
     pred, want, steps, glp, kept = _retired_greedy(m, greedy)                                           # check 2
@@ -544,6 +595,7 @@ def test_forced(hip_lib, name, form, monkeypatch):
         own_len = _own_paths(m, pred, faces.retired_view(pred, TOK, return_steps=True)[1] if m.parallel else gsteps)
         own = _forced(m, pred, own_len)                                                           # along the form's own greedy decode
         _check_bit_equal(m, lambda b: _forced(b, gold, lengths, trace=True), m.what)              # check 4
+        _check_fold_ran(m, lambda b: _forced(b, gold, lengths, trace=True), "forced")
     lp, gr, rk = _check_layout(out, gold, lengths)                                                # check 1 (layout; scores below)
     # check 2: forcing the greedy decode of the same form along its own tokens
     olp, ogr, ork = _check_layout(own, pred, own_len)
