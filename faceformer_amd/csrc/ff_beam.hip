@@ -3,9 +3,8 @@
 //
 // beam_select_kernel<W>: one wavefront per group.  For each non-empty unfinished beam it masks and reduces the raw logit row
 // exactly as pointer_reduce_kernel does (ff_pointer_mask_reduce<true>, ff_device.h: the row maximum m and sum exp(l - m)), every
-// lane then walks its strided keys once more and keeps the W best candidates c_k + (l[s] - m) - log(sum) in a sorted register
-// list; six butterfly rounds merge the lanes' lists in a fixed tree.  Order: higher score first, equal scores by the lower
-// flat index k * S + s -- a total order, so both lanes of a pair compute the same list and the result is the same on every run.
+// lane then walks its strided keys once more and keeps the W best candidates c_k + (l[s] - m) - log(sum) in the sorted register
+// list of ff_select.h (insert, walk, butterfly merge, "lane k takes rank k": shared with the constrained beam kernel).
 // Lanes 0..W-1 then own one new beam each (parent, token, score, finished flag), the wave permutes the group's token history
 // in place, appends the next decoder input rows memory[w, token] and adds to the launch's stop counter.
 //
@@ -19,11 +18,9 @@
 #include "ff_common.h"
 #include "ff_device.h"
 #include "ff_launch.h"
+#include "ff_select.h"
 
 namespace {
-
-constexpr int BEAM_MAX_W = 8;
-constexpr int BEAM_NONE = 0x7fffffff;   // flat index of a list entry that holds no candidate (score -inf)
 
 struct BeamArgs {
   PointerArgs p;            // logits / masks / memory / next rows of the B = groups * W launch rows, spg = beams per wireframe
@@ -34,25 +31,11 @@ struct BeamArgs {
   int* parent; int* tok;     // [B] out
 };
 
-// candidate (sc, ix) into the sorted list when it ranks before an entry: higher score, or the same score and a lower index
-template <int W>
-__device__ __forceinline__ void beam_insert(float (&lsc)[W], int (&lix)[W], float sc, int ix) {
-#pragma unroll
-  for (int i = W - 1; i >= 0; --i) {
-    const bool before = sc > lsc[i] || (sc == lsc[i] && ix < lix[i]);
-    if (before) {
-      if (i < W - 1) { lsc[i + 1] = lsc[i]; lix[i + 1] = lix[i]; }
-      lsc[i] = sc; lix[i] = ix;
-    }
-  }
-}
-
 template <int W>
 __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const float FILL = -FLT_MAX;
   int nge = 0;
   if (g < a.groups) {
     const int S = pa.S, b0 = g * W;
@@ -61,43 +44,27 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     const int my_f = lane < W ? a.fin_in[b0 + lane] : 0;
     float lsc[W];
     int lix[W];
-#pragma unroll
-    for (int i = 0; i < W; ++i) { lsc[i] = -INFINITY; lix[i] = BEAM_NONE; }
+    ff_beam_list_init<W>(lsc, lix);
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       const float c = __shfl(my_c, k, FF_WAVE);
       const int f = __shfl(my_f, k, FF_WAVE);
       if (c == -INFINITY) continue;                      // empty beam: no candidates (wave-uniform)
       if (f) {                                           // finished: itself, token 0, score unchanged
-        if (lane == 0) beam_insert<W>(lsc, lix, c, k * S);
+        if (lane == 0) ff_beam_insert<W>(lsc, lix, c, k * S);
         continue;
       }
       float m, b2, lsum;
       int i1;
       ff_pointer_mask_reduce<true>(pa, b0 + k, lane, &m, &b2, &i1, &lsum);
       const float logz = logf(lsum);
-      const float* lrow = pa.logits + (size_t)(b0 + k) * pa.ldlogits;
-      for (int s = lane; s < S; s += 64) {
-        const float sc = fmaxf(c + ((ff_ld4(lrow + s) - m) - logz), FILL);   // saturates: no -inf, no NaN (all terms finite)
-        beam_insert<W>(lsc, lix, sc, k * S + s);
-      }
+      ff_beam_walk<W, false>(lsc, lix, pa.logits + (size_t)(b0 + k) * pa.ldlogits, S, lane, k, c, m, logz);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      float osc[W];
-      int oix[W];
-#pragma unroll
-      for (int i = 0; i < W; ++i) { osc[i] = __shfl_xor(lsc[i], off, FF_WAVE); oix[i] = __shfl_xor(lix[i], off, FF_WAVE); }
-#pragma unroll
-      for (int i = 0; i < W; ++i) beam_insert<W>(lsc, lix, osc[i], oix[i]);
-    }
-    // lane k takes rank k
-    float sc = -INFINITY;
-    int ix = BEAM_NONE;
-#pragma unroll
-    for (int i = 0; i < W; ++i)
-      if (lane == i) { sc = lsc[i]; ix = lix[i]; }
-    const bool some = lane < W && ix != BEAM_NONE;
+    ff_beam_merge<W>(lsc, lix);
+    float sc;
+    int ix;
+    ff_beam_rank<W>(lsc, lix, lane, &sc, &ix);
+    const bool some = lane < W && ix != FF_BEAM_NONE;
     const int par = some ? ix / S : (lane < W ? lane : 0);
     const int pfin = __shfl(my_f, par, FF_WAVE);
     const int tk = (some && !pfin) ? ix - par * S : 0;
@@ -137,10 +104,10 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(float* __restrict__ r
                                                            int rows_per_pos, const int* __restrict__ parent, int W) {
   extern __shared__ f32x4 lds[];
   const int g = blockIdx.x, j = blockIdx.y;
-  int par[BEAM_MAX_W];
+  int par[FF_BEAM_MAX_W];
   bool ident = true;
 #pragma unroll
-  for (int k = 0; k < BEAM_MAX_W; ++k) {
+  for (int k = 0; k < FF_BEAM_MAX_W; ++k) {
     par[k] = k < W ? min(max(parent[g * W + k], 0), W - 1) : k;   // (a caller's parent outside 0..W-1 stays inside the staged rows)
     ident = ident && par[k] == k;
   }
@@ -154,7 +121,7 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(float* __restrict__ r
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < BEAM_MAX_W; ++k) {
+  for (int k = 0; k < FF_BEAM_MAX_W; ++k) {
     if (k >= W || par[k] == k) continue;
     const f32x4* src = lds + par[k] * vw;
     for (int c = threadIdx.x; c < vw; c += blockDim.x) {
@@ -211,34 +178,27 @@ __global__ void beam_finalize_kernel(const int* __restrict__ tok, const int* __r
   }
 }
 
-int check_select(int groups, int width, int S, int gpw, const float* logits, int ldlogits) {
-  FF_CHECK_ARG(width >= 1 && width <= BEAM_MAX_W && width <= S, "ff_beam_select: width=%d outside 1..%d or above S=%d", width, BEAM_MAX_W, S);
-  FF_CHECK_ARG(groups > 0 && S > 0 && gpw > 0 && (long long)groups * width < (1LL << 31), "ff_beam_select: bad sizes groups=%d S=%d", groups, S);
-  FF_CHECK_ARG(logits && ldlogits >= S, "ff_beam_select: logits missing or ldlogits < S");
+}  // namespace
+
+int ff_beam_check_sizes(const char* op, int groups, int width, int groups_per_wireframe, int S) {
+  FF_CHECK_ARG(width >= 1 && width <= FF_BEAM_MAX_W && width <= S, "%s: width=%d outside 1..%d or above S=%d", op, width, FF_BEAM_MAX_W, S);
+  FF_CHECK_ARG(groups > 0 && S > 0 && groups_per_wireframe > 0 && (long long)groups * width < (1LL << 31), "%s: bad sizes groups=%d S=%d", op,
+               groups, S);
   return FF_OK;
 }
 
-}  // namespace
-
-int ff_beam_select_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int groups, int width,
-                        int groups_per_wireframe, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
-                        int* hist, int ldhist, int t, int* parent, int* next_tok, int term_lo, int term_hi, const float* memory,
-                        int E, float* next_rows, int ldnext, int* count_ge, int ge_bound, float* next_stats, int* arrive,
-                        int* host_slot, ff_stream_t stream) {
-  FF_RETURN_IF(check_select(groups, width, S, groups_per_wireframe, logits, ldlogits));
-  FF_CHECK_ARG(scores_in && scores_out && fin_in && fin_out && parent && next_tok, "ff_beam_select: null pointer");
-  FF_CHECK_ARG(!hist || (t >= 1 && ldhist >= groups * width), "ff_beam_select: history needs t >= 1 and ldhist >= groups * width");
+int ff_beam_select_sync(const ff_step_io& io, int width, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
+                        int* hist, int ldhist, int t, int* parent, int* next_tok, ff_stream_t stream) {
+  const int S = io.S, groups = io.rows / width;
   BeamArgs a;
   memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_beam_select", false, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
-  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
-  a.p.B = groups * width; a.p.spg = groups_per_wireframe * width;
-  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.ge_bound = ge_bound;
-  a.p.term_lo = term_lo; a.p.term_hi = term_hi;
+  FF_RETURN_IF(ff_step_args(&a.p, "ff_beam_select", false, io));
+  FF_CHECK_ARG(scores_in && scores_out && fin_in && fin_out && parent && next_tok, "ff_beam_select: null pointer");
+  FF_CHECK_ARG(!hist || (t >= 1 && ldhist >= io.rows), "ff_beam_select: history needs t >= 1 and ldhist >= groups * width");
   a.groups = groups; a.score_in = scores_in; a.score_out = scores_out; a.fin_in = fin_in; a.fin_out = fin_out;
   a.hist = hist; a.ldhist = ldhist; a.t = t; a.parent = parent; a.tok = next_tok;
   hipStream_t st = (hipStream_t)stream;
-  FFProfScope prof(FF_CAT_POINTER, (double)groups * width * S * 12.0, st);
+  FFProfScope prof(FF_CAT_POINTER, (double)io.rows * S * 12.0, st);
   const dim3 grid(ff_cdiv(groups, 4)), block(256);
   const int rc = ff_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(width, [&](auto w) {
     hipLaunchKernelGGL(beam_select_kernel<decltype(w)::value>, grid, block, 0, st, a);
@@ -254,15 +214,16 @@ extern "C" int ff_beam_select(float* logits, int ldlogits, int S, const unsigned
                               int* fin_out, int* hist, int ldhist, int t, int* parent, int* next_tok, int term_lo, int term_hi,
                               const float* memory, int E, float* next_rows, int ldnext, int* count_ge, int ge_bound,
                               ff_stream_t stream) {
-  return ff_beam_select_sync(logits, ldlogits, S, mask, kv_len, groups, width, groups_per_wireframe, scores_in, scores_out, fin_in,
-                             fin_out, hist, ldhist, t, parent, next_tok, term_lo, term_hi, memory, E, next_rows, ldnext, count_ge,
-                             ge_bound, nullptr, nullptr, nullptr, stream);
+  FF_RETURN_IF(ff_beam_check_sizes("ff_beam_select", groups, width, groups_per_wireframe, S));
+  return ff_beam_select_sync(ff_step_io{logits, ldlogits, S, mask, kv_len, groups * width, groups_per_wireframe * width, term_lo,
+                                        term_hi, ge_bound, memory, E, next_rows, ldnext, nullptr, count_ge, nullptr, nullptr},
+                             width, scores_in, scores_out, fin_in, fin_out, hist, ldhist, t, parent, next_tok, stream);
 }
 
 extern "C" int ff_beam_reorder(float* rows_a, int width_a, float* rows_b, int width_b, int rows_per_pos, int npos,
                                const int* parent, int groups, int width, ff_stream_t stream) {
   if (npos == 0 || groups == 0) return FF_OK;
-  FF_CHECK_ARG(width >= 1 && width <= BEAM_MAX_W, "ff_beam_reorder: width=%d outside 1..%d", width, BEAM_MAX_W);
+  FF_CHECK_ARG(width >= 1 && width <= FF_BEAM_MAX_W, "ff_beam_reorder: width=%d outside 1..%d", width, FF_BEAM_MAX_W);
   FF_CHECK_ARG(npos > 0 && npos <= 65535 && groups > 0 && (long long)groups * width <= rows_per_pos, "ff_beam_reorder: bad sizes npos=%d groups=%d", npos, groups);
   FF_CHECK_ARG(rows_a && parent && width_a > 0 && (width_a & 3) == 0 && ff_aligned16(rows_a), "ff_beam_reorder: rows_a must be 16-byte rows");
   FF_CHECK_ARG(rows_b ? (width_b > 0 && (width_b & 3) == 0 && ff_aligned16(rows_b)) : width_b == 0, "ff_beam_reorder: rows_b must be 16-byte rows (or null with width 0)");

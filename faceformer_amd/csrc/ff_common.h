@@ -121,13 +121,27 @@ int ff_pointer_argmax_sync(const float* p, int ldp, const float* memory, int S, 
                            float* next_rows, int ldnext, int* count_ge, int ge_bound, int* count_eq, int eq_value,
                            const ff_pointer_sync* sync, ff_stream_t stream);   // logprob: [B] or null (ff_pointer_argmax_lp)
 
-// ff_beam_select with the decode engine's hand-over (ff_beam.hip): next_stats as above; arrive counts the launch's GROUPS, the
-// last block stores count_ge to host_slot.  And the start state / output packing of a beam decode (kernels' comments).
-int ff_beam_select_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int groups, int width,
-                        int groups_per_wireframe, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
-                        int* hist, int ldhist, int t, int* parent, int* next_tok, int term_lo, int term_hi, const float* memory,
-                        int E, float* next_rows, int ldnext, int* count_ge, int ge_bound, float* next_stats, int* arrive,
-                        int* host_slot, ff_stream_t stream);
+// What every selection launch of a decode step takes (internal: the extern "C" operators build it from their parameter lists,
+// the engine fills it once per step).  ff_step_args (ff_launch.h) checks it and fills the launch's PointerArgs from it.
+struct ff_step_io {
+  float* logits; int ldlogits;             // [rows, ldlogits] raw logits in, masked logits out
+  int S; const unsigned char* mask; const int* kv_len;
+  int rows, rows_per_wireframe;            // launch rows (sequences, beams or samples) and how many of them share a wireframe
+  int term_lo, term_hi, ge_bound;          // terminator range; count_ge counts the selected tokens >= ge_bound
+  const float* memory; int E;
+  float* next_rows; int ldnext;            // or null: the next decoder input rows memory[w, token]
+  float* next_stats;                       // [rows, E/32, 2] or null: their LayerNorm segment statistics
+  int* count_ge;                           // or null: the launch's stop counter
+  int *arrive, *host_slot;                 // decode engine only: arrivals of the launch's waves (zero before it), and the host-mapped
+                                           // pinned int that receives count_ge from the last one
+};
+
+// The selection operators on a descriptor (ff_beam.hip, ff_sample.hip, ff_constrain.hip, ff_constrain_beam.hip, ff_forced.hip), and
+// the start state / output packing of each decode mode (kernels' comments).  Beam forms: io.rows = groups * width, and the
+// width and sizes are checked by ff_beam_check_sizes before that product is formed (the extern "C" entries; the engine's own checks).
+int ff_beam_check_sizes(const char* op, int groups, int width, int groups_per_wireframe, int S);
+int ff_beam_select_sync(const ff_step_io& io, int width, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
+                        int* hist, int ldhist, int t, int* parent, int* next_tok, ff_stream_t stream);
 int ff_beam_init(int* tok, float* score, int* fin, int* parent, int Bc, int Fc, int W, int f0, const int* num_input, int pad_tok,
                  int term_lo, int term_hi, hipStream_t st);
 int ff_beam_finalize(const int* tok, const int* parent, const float* score, int Btot, int T, const int* steps_dev,
@@ -136,39 +150,34 @@ int ff_beam_finalize(const int* tok, const int* parent, const float* score, int 
 
 // Forced decode (ff_forced.hip): the [rows, T] int64 paths as the engine's position-major int32 tokens (clamped into [0, S)),
 // and the output packing (kernels' comments).
+int ff_pointer_forced_sync(const ff_step_io& io, const int* forced, float* logprob, int* greedy, int* rank, ff_stream_t stream);
 int ff_forced_tokens(const int64_t* paths, int* tok, int rows, int T, int S, hipStream_t st);
 int ff_forced_finalize(const int* tok, const float* lp_all, const int* greedy_all, const int* rank_all, const int* lengths, int rows,
                        int T, float* logprob, int64_t* greedy, int* rank, float* seq_logprob, hipStream_t st);
 
-// ff_pointer_sample with the decode engine's hand-over (ff_sample.hip): arrive counts the launch's rows, the last block stores
-// count_ge to host_slot.  And the start state / output packing of a sampled decode (kernels' comments).
-int ff_pointer_sample_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                           int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
-                           float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok, float* logprob,
-                           int* fin_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
-                           int* count_ge, int ge_bound, int* arrive, int* host_slot, ff_stream_t stream);
+// (sampled decode)
+int ff_pointer_sample_sync(const ff_step_io& io, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
+                           float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream);
 int ff_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F, const int* num_input,
                    int pad_tok, int term_lo, int term_hi, hipStream_t st);
 int ff_sample_finalize(const int* tok, const float* lp, const int* fin, int Btot, int T, const int* steps_dev, const int* num_input,
                        int dedup, int F, int R, int w0, int nw, int Fc, int f0, int b0, int64_t* samples, float* logprob,
                        float* scores, int64_t* predict, int* seq_of_row, hipStream_t st);
 
-// ff_pointer_constrained with the decode engine's hand-over (ff_constrain.hip): arrive counts the launch's rows, the last block
-// stores count_ge to host_slot.  And the start state / output packing of a constrained decode (kernels' comments).
-int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                                int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi,
-                                const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
-                                unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
-                                int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
-                                int* count_ge, int* arrive, int* host_slot, ff_stream_t stream);
-// ff_pointer_constrained_ahead with the same hand-over (the closure look-ahead)
-int ff_pointer_constrained_ahead_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                                      int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo,
-                                      int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
-                                      unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
-                                      int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
-                                      float* next_stats, int* count_ge, const unsigned char* close_dist,
-                                      const unsigned char* cycle_len, int budget, int* arrive, int* host_slot, ff_stream_t stream);
+// The loop rule's operands of a constrained step, and their check for operator `op` (ff_constrain.hip): the flag bits,
+// L = S - ntok, the terminator range inside the special tokens, FF_CONSTRAIN_CONNECT with its follow table.
+struct ff_loop_rule_io { const unsigned* follows; int L, flags, ntok; };
+int ff_loop_rule_check(const char* op, const ff_loop_rule_io& r, int S, int term_lo, int term_hi);
+// Constrained decode.  state: what a step reads and writes per row; ahead (or null): the closure look-ahead.
+struct ff_constrained_state {
+  const int *fin_in, *first_in, *prev_in;
+  unsigned* visited; unsigned char* mask_rows;
+  int* next_tok; float* logprob;
+  int *fin_out, *dead_end, *first_out, *prev_out;
+};
+struct ff_lookahead_io { const unsigned char *close_dist, *cycle_len; int budget; };
+int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,
+                                const ff_lookahead_io* ahead, ff_stream_t stream);
 int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int Fc, int f0,
                       const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok, const unsigned* follows, int L,
                       hipStream_t st);
@@ -176,10 +185,9 @@ int ff_constrain_finalize(const int* tok, const float* lp, const int* fin, const
                           const int* num_input, int dedup, int F, int w0, int nw, int Fc, int f0, int b0, int64_t* predict,
                           float* logprob, int* dead_end, int* seq_of_row, hipStream_t st);
 
-// ff_beam_constrained_select with the decode engine's hand-over (ff_constrain_beam.hip): arrive counts the
-// launch's GROUPS, the last block stores count_ge to host_slot.  And the start state / dead-end output of a constrained beam
-// decode (kernels' comments); its beams, scores and predict are packed by ff_beam_finalize.
-int ff_beam_constrained_select_sync(const ff_beam_constrained_step* step, int* arrive, int* host_slot, ff_stream_t stream);
+// Constrained beam decode: `step` supplies the rule's and the beams' operands, io the common ones (io.rows = groups * width);
+// its beams, scores and predict are packed by ff_beam_finalize.
+int ff_beam_constrained_select_sync(const ff_step_io& io, const ff_beam_constrained_step* step, ff_stream_t stream);
 int ff_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* parent, int* first, int* prev, unsigned* visited, int Bc,
                            int Fc, int W, int f0, const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok,
                            const unsigned* follows, int L, hipStream_t st);

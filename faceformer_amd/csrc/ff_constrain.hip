@@ -10,14 +10,17 @@
 // follow_table_kernel: one wavefront per (wireframe, edge a) row, 64 candidate edges b per round; the ballot of
 // |end(a) - start(b)| < tol in x and in y (fp32 subtraction, fp32 compare) is the two 32-bit words of the round.
 //
+// The rule's device code is ff_select.h's, shared with the constrained beam kernel (ff_constrain_beam.hip): the byte row of a
+// sequence's constraint mask with the "any live edge" vote and the terminators re-opened on a dead end (ff_loop_write_row), the
+// three-step update of (first, prev) (ff_loop_advance) and the state after column 0 (ff_loop_start).
+//
 // pointer_constrained_kernel: one wavefront per sequence, four per block, as pointer_reduce_kernel.  A finished sequence appends
-// token 0 and keeps its state.  Every other one writes the byte row of ITS constraint mask (lane = key mod 64), votes once on
-// "any live edge" (the vote sees padding, kv_len and visited), re-opens the terminators on a dead end (same lane = key mod 64
-// mapping), and then masks and reduces its logit row exactly as the greedy launch does with an extra mask
-// (ff_pointer_mask_reduce<true>, ff_device.h): every lane reads back the bytes it wrote itself.  Lane 0 stores token,
-// log-probability (-log sum exp(l - l[token]) over the constrained row), the flags and the next (first, prev), and sets the
-// token's bit in the sequence's visited words; the wave appends memory[w, token] through ff_pointer_append_row, so a
-// constrained decode keeps FF_L0_FOLD.  No LDS beyond the four counter words.  Stop counter: pointer_sample_kernel's scheme.
+// token 0 and keeps its state.  Every other one writes the byte row of ITS constraint mask and then masks and reduces its logit
+// row exactly as the greedy launch does with an extra mask (ff_pointer_mask_reduce<true>, ff_device.h): every lane reads back
+// the bytes it wrote itself.  Lane 0 stores token, log-probability (-log sum exp(l - l[token]) over the constrained row), the
+// flags and the next (first, prev), and sets the token's bit in the sequence's visited words; the wave appends memory[w, token]
+// through ff_pointer_append_row, so a constrained decode keeps FF_L0_FOLD.  No LDS beyond the four counter words.  Stop counter:
+// pointer_sample_kernel's scheme.
 // pointer_constrained_kernel<true> is the same launch with the closure look-ahead: one byte row per sequence
 // (close_dist[w][first] with the loop open, cycle_len[w] with it closed), one byte load and one compare per edge key in the loop
 // that writes the byte row, in front of the vote.  <false> is what ff_pointer_constrained and ff_decode_constrained launch.
@@ -33,6 +36,7 @@
 #include "ff_common.h"
 #include "ff_device.h"
 #include "ff_launch.h"
+#include "ff_select.h"
 
 namespace {
 
@@ -155,59 +159,25 @@ __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs 
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   int nge = 0;
   if (b < pa.B) {   // (wave-uniform)
-    const int S = pa.S, ntok = a.ntok;
+    const int ntok = a.ntok;
     const int was_fin = ff_ld4i(a.fin_in + b);
-    int first = ff_ld4i(a.first_in + b), prev = ff_ld4i(a.prev_in + b);
-    first = (first < 0 || first >= a.L) ? -1 : first;   // (the entry cannot see device data: anything else is "none")
-    prev = (prev < 0 || prev >= a.L) ? -1 : prev;
+    int first = ff_loop_edge(ff_ld4i(a.first_in + b), a.L), prev = ff_loop_edge(ff_ld4i(a.prev_in + b), a.L);
     int tok = 0, dead = 0;
     float lp = 0.f;
     if (!was_fin) {
       const int w = b / pa.spg;
-      const bool connect = (a.flags & FF_CONSTRAIN_CONNECT) != 0, norep = (a.flags & FF_CONSTRAIN_NO_REPEAT) != 0;
-      const bool open = connect && first >= 0 && prev >= 0;
-      int kv = S;
+      int kv = pa.S;
       if (pa.kv_len) { const int k = ff_ldw(pa.kv_len + w); kv = k < kv ? k : kv; }
-      const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * S : nullptr;
-      const unsigned* frow = open ? a.follows + ((size_t)w * a.L + prev) * a.fw : nullptr;
-      const unsigned* vrow = a.visited + (size_t)b * a.fw;
-      unsigned char* xrow = a.rows + (size_t)b * S;
-      // (look-ahead: the distance of every edge to the loop's first edge while it is open, else the edge's own shortest cycle)
-      const unsigned char* drow = nullptr;
-      if (AHEAD && connect) drow = open ? a.close_dist + ((size_t)w * a.L + first) * a.L : a.cycle_len + (size_t)w * a.L;
-      bool live_edge = false;
-      for (int s = lane; s < S; s += 64) {
-        bool masked;
-        if (s < ntok) {
-          masked = connect && (open || s < pa.term_lo || s >= pa.term_hi);
-        } else {
-          const int e = s - ntok;
-          const unsigned bit = 1u << (e & 31);
-          masked = (norep && (vrow[e >> 5] & bit) != 0) || (open && (frow[e >> 5] & bit) == 0);
-          if (AHEAD && drow) masked = masked || (int)drow[e] > a.budget;
-          bool pad = s >= kv;
-          if (!pad && mrow) pad = ff_ldw(mrow + s) != 0;
-          live_edge = live_edge || (!masked && !pad);
-        }
-        xrow[s] = masked ? 1 : 0;
-      }
-      if (open && __ballot(live_edge) == 0ull) {   // dead end: the terminators instead (every lane rewrites its own keys)
-        dead = 1;
-        for (int s = lane; s < pa.term_hi; s += 64)
-          if (s >= pa.term_lo) xrow[s] = 0;
-      }
+      const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * pa.S : nullptr;
+      const FFLoopRule rule{a.follows, a.L, a.fw, a.flags, ntok, a.close_dist, a.cycle_len, a.budget};
+      dead = ff_loop_write_row<AHEAD>(pa, rule, lane, w, kv, mrow, first, prev, a.visited + (size_t)b * a.fw, a.rows + (size_t)b * pa.S) ? 1 : 0;
       float m, b2, lsum;
       ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &tok, &lsum);
       lp = -logf(lsum);
       if (tok >= ntok) {
         const int e = tok - ntok;
         nge = 1;
-        if (first < 0) first = e;
-        prev = e;
-        if (a.follows) {
-          const unsigned word = a.follows[((size_t)w * a.L + e) * a.fw + (first >> 5)];
-          if ((word >> (first & 31)) & 1u) first = -1;   // (a one-edge loop closes on itself)
-        }
+        ff_loop_advance(a.follows, w, a.L, a.fw, e, &first, &prev);
         if (lane == 0) a.visited[(size_t)b * a.fw + (e >> 5)] |= 1u << (e & 31);
       }
     }
@@ -241,15 +211,8 @@ __global__ void constrain_init_kernel(int* tok, float* lp, int* fin, int* dead, 
   lp[i] = 0.f;
   fin[i] = done;
   dead[i] = 0;
-  unsigned* v = visited + (size_t)i * fw;
-  for (int k = 0; k < fw; ++k) v[k] = 0u;
-  int fi = -1, pv = -1;
-  const int e = t - ntok;
-  if (e >= 0 && e < L) {
-    v[e >> 5] = 1u << (e & 31);
-    fi = pv = e;
-    if (follows && ((follows[((size_t)wl * L + e) * fw + (e >> 5)] >> (e & 31)) & 1u)) fi = -1;
-  }
+  int fi, pv;
+  ff_loop_start(t, ntok, follows, wl, L, fw, visited + (size_t)i * fw, &fi, &pv);
   first[i] = fi;
   prev[i] = pv;
 }
@@ -301,44 +264,38 @@ extern "C" int ff_follow_table(const float* starts, const float* ends, int N, in
   return FF_OK;
 }
 
-namespace {
-// The one launch behind ff_pointer_constrained (ahead = false: the tables and the budget are not looked at) and
-// ff_pointer_constrained_ahead; `name` words the errors.
-int constrained_launch(const char* name, bool ahead, const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
-                       float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B, int seqs_per_group,
-                       const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi, const int* fin_in,
-                       const int* first_in, const int* prev_in, unsigned* visited, unsigned char* mask_rows, int* next_tok,
-                       float* logprob, int* fin_out, int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
-                       float* next_rows, int ldnext, float* next_stats, int* count_ge, int* arrive, int* host_slot,
-                       ff_stream_t stream) {
+int ff_loop_rule_check(const char* op, const ff_loop_rule_io& r, int S, int term_lo, int term_hi) {
+  FF_CHECK_ARG(!(r.flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", op, r.flags);
+  FF_CHECK_ARG(r.ntok >= 0 && r.L >= 0 && r.L == S - r.ntok, "%s: L=%d must be S - ntok = %d - %d", op, r.L, S, r.ntok);
+  FF_CHECK_ARG(term_lo >= 0 && term_lo < term_hi && term_hi <= r.ntok, "%s: terminator range [%d, %d) empty or outside the %d special tokens",
+               op, term_lo, term_hi, r.ntok);
+  FF_CHECK_ARG(r.follows || !(r.flags & FF_CONSTRAIN_CONNECT), "%s: FF_CONSTRAIN_CONNECT needs the follow table", op);
+  return FF_OK;
+}
+
+// The one launch behind ff_pointer_constrained (ahead = null) and ff_pointer_constrained_ahead; `op` words the errors.
+int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& s,
+                                const ff_lookahead_io* ahead, ff_stream_t stream) {
+  const int B = io.rows, S = io.S;
   if (B == 0) return FF_OK;
-  FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "%s: bad sizes B=%d S=%d", name, B, S);
-  FF_CHECK_ARG(logits && ldlogits >= S, "%s: logits missing or ldlogits < S", name);
-  FF_CHECK_ARG(!(flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", name, flags);
-  FF_CHECK_ARG(ntok >= 0 && L >= 0 && L == S - ntok, "%s: L=%d must be S - ntok = %d - %d", name, L, S, ntok);
-  FF_CHECK_ARG(term_lo >= 0 && term_lo < term_hi && term_hi <= ntok, "%s: terminator range [%d, %d) empty or outside the %d special tokens",
-               name, term_lo, term_hi, ntok);
-  FF_CHECK_ARG(follows || !(flags & FF_CONSTRAIN_CONNECT), "%s: FF_CONSTRAIN_CONNECT needs the follow table", name);
-  FF_CHECK_ARG(fin_in && first_in && prev_in && visited && mask_rows && next_tok && logprob && fin_out && dead_end && first_out && prev_out,
-               "%s: null pointer", name);
-  if (ahead) {
-    FF_CHECK_ARG(flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", name);
-    FF_CHECK_ARG(close_dist && cycle_len, "%s: close_dist and cycle_len are required", name);
-    FF_CHECK_ARG(budget >= 0 && budget <= 254, "%s: budget=%d outside 0..254", name, budget);
-  }
+  FF_CHECK_ARG(B > 0 && S > 0 && io.rows_per_wireframe > 0, "%s: bad sizes B=%d S=%d", op, B, S);
   ConstrainArgs a;
   memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_pointer_feedback(&a.p, name, true, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
-  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
-  a.p.extra = mask_rows; a.p.ldextra = S;
-  a.p.B = B; a.p.spg = seqs_per_group;
-  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.ge_bound = ntok;
-  a.p.term_lo = term_lo; a.p.term_hi = term_hi;
-  a.rows = mask_rows; a.follows = follows; a.L = L; a.fw = (L + 31) >> 5; a.flags = flags; a.ntok = ntok;
-  a.fin_in = fin_in; a.first_in = first_in; a.prev_in = prev_in; a.visited = visited;
-  a.fin_out = fin_out; a.first_out = first_out; a.prev_out = prev_out; a.dead_out = dead_end;
-  a.tok = next_tok; a.logprob = logprob;
-  a.close_dist = close_dist; a.cycle_len = cycle_len; a.budget = budget;
+  FF_RETURN_IF(ff_step_args(&a.p, op, true, io));
+  FF_RETURN_IF(ff_loop_rule_check(op, rule, S, io.term_lo, io.term_hi));
+  FF_CHECK_ARG(s.fin_in && s.first_in && s.prev_in && s.visited && s.mask_rows && s.next_tok && s.logprob && s.fin_out && s.dead_end &&
+                   s.first_out && s.prev_out, "%s: null pointer", op);
+  if (ahead) {
+    FF_CHECK_ARG(rule.flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", op);
+    FF_CHECK_ARG(ahead->close_dist && ahead->cycle_len, "%s: close_dist and cycle_len are required", op);
+    FF_CHECK_ARG(ahead->budget >= 0 && ahead->budget <= 254, "%s: budget=%d outside 0..254", op, ahead->budget);
+    a.close_dist = ahead->close_dist; a.cycle_len = ahead->cycle_len; a.budget = ahead->budget;
+  }
+  a.p.extra = s.mask_rows; a.p.ldextra = S;
+  a.rows = s.mask_rows; a.follows = rule.follows; a.L = rule.L; a.fw = (rule.L + 31) >> 5; a.flags = rule.flags; a.ntok = rule.ntok;
+  a.fin_in = s.fin_in; a.first_in = s.first_in; a.prev_in = s.prev_in; a.visited = s.visited;
+  a.fin_out = s.fin_out; a.first_out = s.first_out; a.prev_out = s.prev_out; a.dead_out = s.dead_end;
+  a.tok = s.next_tok; a.logprob = s.logprob;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 4.0, st);
   if (ahead)
@@ -347,33 +304,6 @@ int constrained_launch(const char* name, bool ahead, const unsigned char* close_
     hipLaunchKernelGGL(pointer_constrained_kernel<false>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
-}
-}  // namespace
-
-// (the arguments the three entries below hand through unchanged)
-#define FF_CONSTRAINED_STEP_ARGS                                                                                                   \
-  logits, ldlogits, S, mask, kv_len, B, seqs_per_group, follows, L, flags, ntok, term_lo, term_hi, fin_in, first_in, prev_in,      \
-      visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out, memory, E, next_rows, ldnext, next_stats,     \
-      count_ge
-
-int ff_pointer_constrained_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                                int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo, int term_hi,
-                                const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
-                                unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end, int* first_out,
-                                int* prev_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
-                                int* count_ge, int* arrive, int* host_slot, ff_stream_t stream) {
-  return constrained_launch("ff_pointer_constrained", false, nullptr, nullptr, 0, FF_CONSTRAINED_STEP_ARGS, arrive, host_slot, stream);
-}
-
-int ff_pointer_constrained_ahead_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                                      int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo,
-                                      int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned* visited,
-                                      unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
-                                      int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
-                                      float* next_stats, int* count_ge, const unsigned char* close_dist,
-                                      const unsigned char* cycle_len, int budget, int* arrive, int* host_slot, ff_stream_t stream) {
-  return constrained_launch("ff_pointer_constrained_ahead", true, close_dist, cycle_len, budget, FF_CONSTRAINED_STEP_ARGS, arrive,
-                            host_slot, stream);
 }
 
 extern "C" int ff_pointer_constrained_ahead(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
@@ -384,8 +314,14 @@ extern "C" int ff_pointer_constrained_ahead(float* logits, int ldlogits, int S, 
                                             float* next_rows, int ldnext, float* next_stats, int* count_ge,
                                             const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
                                             ff_stream_t stream) {
-  return constrained_launch("ff_pointer_constrained_ahead", true, close_dist, cycle_len, budget, FF_CONSTRAINED_STEP_ARGS, nullptr,
-                            nullptr, stream);
+  const ff_lookahead_io ahead{close_dist, cycle_len, budget};
+  return ff_pointer_constrained_sync(
+      "ff_pointer_constrained_ahead",
+      ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, term_lo, term_hi, ntok, memory, E, next_rows, ldnext, next_stats,
+                 count_ge, nullptr, nullptr},
+      ff_loop_rule_io{follows, L, flags, ntok},
+      ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
+      &ahead, stream);
 }
 
 extern "C" int ff_follow_distance(const unsigned* follows, int N, int L, const int* num_input, int hmax, unsigned char* close_dist,
@@ -409,9 +345,13 @@ extern "C" int ff_pointer_constrained(float* logits, int ldlogits, int S, const 
                                       unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
                                       int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
                                       float* next_stats, int* count_ge, ff_stream_t stream) {
-  return ff_pointer_constrained_sync(logits, ldlogits, S, mask, kv_len, B, seqs_per_group, follows, L, flags, ntok, term_lo, term_hi,
-                                     fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out,
-                                     prev_out, memory, E, next_rows, ldnext, next_stats, count_ge, nullptr, nullptr, stream);
+  return ff_pointer_constrained_sync(
+      "ff_pointer_constrained",
+      ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, term_lo, term_hi, ntok, memory, E, next_rows, ldnext, next_stats,
+                 count_ge, nullptr, nullptr},
+      ff_loop_rule_io{follows, L, flags, ntok},
+      ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
+      nullptr, stream);
 }
 
 int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int Fc, int f0,

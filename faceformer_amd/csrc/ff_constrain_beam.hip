@@ -2,28 +2,26 @@
 // the LIVE keys of the W constrained rows of every group, with the rule's per-beam state following the parent permutation.
 //
 // beam_constrained_select_kernel<W>: one wavefront per group, four per block, as beam_select_kernel.  For each non-empty
-// unfinished beam the wave writes the byte row of the beam's constraint mask exactly as pointer_constrained_kernel does (lane =
-// key mod 64), votes once on "any live edge", re-opens the terminators on a dead end, masks and reduces the logit row with that
-// row as the extra mask (ff_pointer_mask_reduce<true>, ff_device.h: every lane reads back only bytes and logits it wrote
-// itself), walks its strided keys once more and keeps the W best LIVE candidates c_k + (l[s] - m) - log(sum) in the sorted
-// register list of ff_beam.hip -- a masked key (l[s] = -FLT_MAX) is never a candidate; a row without a live key contributes
-// token 0 at c_k - log S, what the constrained greedy launch selects there.  The beam's dead-end bit goes into a wave-uniform
-// mask.  Six butterfly rounds merge the lanes' lists (order: higher score, then the lower flat index k * S + s).  Lanes 0..W-1
-// then own one new beam each: parent, token, score, the finished and the cumulative dead flag, and the rule's three-step update
-// of the PARENT's (first, prev) -- one word of the follow table for the closure test; the wave writes the W * fw words of
-// visited_out = visited_in[parent] | bit(token) together.  All state is read from the *_in arrays and written to the *_out
-// arrays: no beam reads what a sibling wrote.  Rows are appended by ff_pointer_append_row (FF_L0_FOLD is kept), the stop
-// counter is ff_pointer_count_waves'.  No LDS beyond the four counter words.
+// unfinished beam the wave writes the byte row of the beam's constraint mask with the function pointer_constrained_kernel calls
+// (ff_loop_write_row<false>, ff_select.h: the vote on "any live edge", the terminators re-opened on a dead end), masks and
+// reduces the logit row with that row as the extra mask (ff_pointer_mask_reduce<true>, ff_device.h: every lane reads back only
+// bytes and logits it wrote itself), walks its strided keys once more and keeps the W best LIVE candidates
+// c_k + (l[s] - m) - log(sum) in the sorted register list of ff_select.h, beam_select_kernel's -- a masked key
+// (l[s] = -FLT_MAX) is never a candidate; a row without a live key contributes token 0 at c_k - log S, what the constrained
+// greedy launch selects there.  The beam's dead-end bit goes into a wave-uniform mask.  The list's butterfly merge; lanes
+// 0..W-1 then own one new beam each: parent, token, score, the finished and the cumulative dead flag, and the rule's update of
+// the PARENT's (first, prev) (ff_loop_advance); the wave writes the W * fw words of visited_out = visited_in[parent] |
+// bit(token) together.  All state is read from the *_in arrays and written to the *_out arrays: no beam reads what a sibling
+// wrote.  Rows are appended by ff_pointer_append_row (FF_L0_FOLD is kept), the stop counter is ff_pointer_count_waves'.  No LDS
+// beyond the four counter words.
 #include <float.h>
 
 #include "ff_common.h"
 #include "ff_device.h"
 #include "ff_launch.h"
+#include "ff_select.h"
 
 namespace {
-
-constexpr int CBEAM_MAX_W = 8;
-constexpr int CBEAM_NONE = 0x7fffffff;   // flat index of a list entry that holds no candidate (score -inf)
 
 struct ConBeamArgs {
   PointerArgs p;                 // logits / masks / memory / next rows / counters of the B = groups * W launch rows; p.extra = rows
@@ -39,19 +37,6 @@ struct ConBeamArgs {
   int* parent; int* tok;         // [B] out
 };
 
-// candidate (sc, ix) into the sorted list when it ranks before an entry: higher score, or the same score and a lower index
-template <int W>
-__device__ __forceinline__ void cbeam_insert(float (&lsc)[W], int (&lix)[W], float sc, int ix) {
-#pragma unroll
-  for (int i = W - 1; i >= 0; --i) {
-    const bool before = sc > lsc[i] || (sc == lsc[i] && ix < lix[i]);
-    if (before) {
-      if (i < W - 1) { lsc[i + 1] = lsc[i]; lix[i + 1] = lix[i]; }
-      lsc[i] = sc; lix[i] = ix;
-    }
-  }
-}
-
 template <int W>
 __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArgs a) {
   const PointerArgs& pa = a.p;
@@ -62,7 +47,6 @@ __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArg
   if (g < a.groups) {   // (wave-uniform)
     const int S = pa.S, ntok = a.ntok, b0 = g * W, fw = a.fw;
     const int w = b0 / pa.spg;   // (the beams of a group share the wireframe)
-    const bool connect = (a.flags & FF_CONSTRAIN_CONNECT) != 0, norep = (a.flags & FF_CONSTRAIN_NO_REPEAT) != 0;
     int kv = S;
     if (pa.kv_len) { const int k = ff_ldw(pa.kv_len + w); kv = k < kv ? k : kv; }
     const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * S : nullptr;
@@ -70,14 +54,13 @@ __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArg
     const float my_c = lane < W ? a.score_in[b0 + lane] : -INFINITY;
     const int my_f = lane < W ? a.fin_in[b0 + lane] : 0;
     const int my_d = lane < W ? a.dead_in[b0 + lane] : 0;
-    int my_first = lane < W ? a.first_in[b0 + lane] : -1, my_prev = lane < W ? a.prev_in[b0 + lane] : -1;
-    my_first = (my_first < 0 || my_first >= a.L) ? -1 : my_first;   // (the entry cannot see device data: anything else is "none")
-    my_prev = (my_prev < 0 || my_prev >= a.L) ? -1 : my_prev;
+    const int my_first = ff_loop_edge(lane < W ? a.first_in[b0 + lane] : -1, a.L);
+    const int my_prev = ff_loop_edge(lane < W ? a.prev_in[b0 + lane] : -1, a.L);
+    const FFLoopRule rule{a.follows, a.L, fw, a.flags, ntok, nullptr, nullptr, 0};
     unsigned deadmask = 0u;   // bit k: beam k dead-ended at this step (wave-uniform)
     float lsc[W];
     int lix[W];
-#pragma unroll
-    for (int i = 0; i < W; ++i) { lsc[i] = -INFINITY; lix[i] = CBEAM_NONE; }
+    ff_beam_list_init<W>(lsc, lix);
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       const float c = __shfl(my_c, k, FF_WAVE);
@@ -85,64 +68,27 @@ __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArg
       const int first = __shfl(my_first, k, FF_WAVE), prev = __shfl(my_prev, k, FF_WAVE);
       if (c == -INFINITY) continue;                      // empty beam: no candidates (wave-uniform)
       if (f) {                                           // finished: itself, token 0, score unchanged
-        if (lane == 0) cbeam_insert<W>(lsc, lix, c, k * S);
+        if (lane == 0) ff_beam_insert<W>(lsc, lix, c, k * S);
         continue;
       }
       const int b = b0 + k;
-      const bool open = connect && first >= 0 && prev >= 0;
-      const unsigned* frow = open ? a.follows + ((size_t)w * a.L + prev) * fw : nullptr;
-      const unsigned* vrow = a.visited_in + (size_t)b * fw;
-      unsigned char* xrow = a.rows + (size_t)b * S;
-      bool live_edge = false;
-      for (int s = lane; s < S; s += 64) {
-        bool masked;
-        if (s < ntok) {
-          masked = connect && (open || s < pa.term_lo || s >= pa.term_hi);
-        } else {
-          const int e = s - ntok;
-          const unsigned bit = 1u << (e & 31);
-          masked = (norep && (vrow[e >> 5] & bit) != 0) || (open && (frow[e >> 5] & bit) == 0);
-          bool pad = s >= kv;
-          if (!pad && mrow) pad = ff_ldw(mrow + s) != 0;
-          live_edge = live_edge || (!masked && !pad);
-        }
-        xrow[s] = masked ? 1 : 0;
-      }
-      if (open && __ballot(live_edge) == 0ull) {   // dead end: the terminators instead (every lane rewrites its own keys)
+      if (ff_loop_write_row<false>(pa, rule, lane, w, kv, mrow, first, prev, a.visited_in + (size_t)b * fw, a.rows + (size_t)b * S))
         deadmask |= 1u << k;
-        for (int s = lane; s < pa.term_hi; s += 64)
-          if (s >= pa.term_lo) xrow[s] = 0;
-      }
       float m, b2, lsum;
       int i1;
       ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &i1, &lsum);
       const float logz = logf(lsum);
       if (!(m > FILL)) {                                 // no live key: token 0 at c - log S (wave-uniform)
-        if (lane == 0) cbeam_insert<W>(lsc, lix, fmaxf(c - logz, FILL), k * S);
+        if (lane == 0) ff_beam_insert<W>(lsc, lix, fmaxf(c - logz, FILL), k * S);
         continue;
       }
-      const float* lrow = pa.logits + (size_t)b * pa.ldlogits;
-      for (int s = lane; s < S; s += 64) {
-        const float v = ff_ld4(lrow + s);
-        if (v > FILL) cbeam_insert<W>(lsc, lix, fmaxf(c + ((v - m) - logz), FILL), k * S + s);   // (live keys only)
-      }
+      ff_beam_walk<W, true>(lsc, lix, pa.logits + (size_t)b * pa.ldlogits, S, lane, k, c, m, logz);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      float osc[W];
-      int oix[W];
-#pragma unroll
-      for (int i = 0; i < W; ++i) { osc[i] = __shfl_xor(lsc[i], off, FF_WAVE); oix[i] = __shfl_xor(lix[i], off, FF_WAVE); }
-#pragma unroll
-      for (int i = 0; i < W; ++i) cbeam_insert<W>(lsc, lix, osc[i], oix[i]);
-    }
-    // lane k takes rank k
-    float sc = -INFINITY;
-    int ix = CBEAM_NONE;
-#pragma unroll
-    for (int i = 0; i < W; ++i)
-      if (lane == i) { sc = lsc[i]; ix = lix[i]; }
-    const bool some = lane < W && ix != CBEAM_NONE;
+    ff_beam_merge<W>(lsc, lix);
+    float sc;
+    int ix;
+    ff_beam_rank<W>(lsc, lix, lane, &sc, &ix);
+    const bool some = lane < W && ix != FF_BEAM_NONE;
     const int par = some ? ix / S : (lane < W ? lane : 0);
     const int pfin = __shfl(my_f, par, FF_WAVE), pdead = __shfl(my_d, par, FF_WAVE);
     int first = __shfl(my_first, par, FF_WAVE), prev = __shfl(my_prev, par, FF_WAVE);
@@ -152,14 +98,7 @@ __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArg
     const int ndead = some ? ((pdead || dead_now) ? 1 : 0) : 0;
     const int e_new = (some && !pfin && tk >= ntok) ? tk - ntok : -1;
     nge = __popcll(__ballot(e_new >= 0));
-    if (e_new >= 0) {   // the rule's three-step update of the parent's (first, prev)
-      if (first < 0) first = e_new;
-      prev = e_new;
-      if (a.follows) {
-        const unsigned word = a.follows[((size_t)w * a.L + e_new) * fw + (first >> 5)];
-        if ((word >> (first & 31)) & 1u) first = -1;   // (a one-edge loop closes on itself)
-      }
-    }
+    if (e_new >= 0) ff_loop_advance(a.follows, w, a.L, fw, e_new, &first, &prev);   // (of the parent's first, prev)
     if (lane < W) {
       a.parent[b0 + lane] = par;
       a.tok[b0 + lane] = tk;
@@ -206,15 +145,8 @@ __global__ void cbeam_init_kernel(int* tok, float* score, int* fin, int* dead, i
   fin[i] = done;
   dead[i] = 0;
   parent[i] = k;
-  unsigned* v = visited + (size_t)i * fw;
-  for (int j = 0; j < fw; ++j) v[j] = 0u;
-  int fi = -1, pv = -1;
-  const int e = t - ntok;
-  if (e >= 0 && e < L) {
-    v[e >> 5] = 1u << (e & 31);
-    fi = pv = e;
-    if (follows && ((follows[((size_t)wl * L + e) * fw + (e >> 5)] >> (e & 31)) & 1u)) fi = -1;
-  }
+  int fi, pv;
+  ff_loop_start(t, ntok, follows, wl, L, fw, visited + (size_t)i * fw, &fi, &pv);
   first[i] = fi;
   prev[i] = pv;
 }
@@ -236,39 +168,26 @@ __global__ void cbeam_dead_kernel(const int* __restrict__ dead, int Btot, const 
 
 }  // namespace
 
-int ff_beam_constrained_select_sync(const ff_beam_constrained_step* d, int* arrive, int* host_slot, ff_stream_t stream) {
+int ff_beam_constrained_select_sync(const ff_step_io& io, const ff_beam_constrained_step* d, ff_stream_t stream) {
   const char* op = "ff_beam_constrained_select";
-  FF_CHECK_ARG(d != nullptr, "%s: null descriptor", op);
-  const int S = d->S, W = d->width, L = d->L;
-  FF_CHECK_ARG(W >= 1 && W <= CBEAM_MAX_W && W <= S, "%s: width=%d outside 1..%d or above S=%d", op, W, CBEAM_MAX_W, S);
-  FF_CHECK_ARG(d->groups > 0 && S > 0 && d->groups_per_wireframe > 0 && (long long)d->groups * W < (1LL << 31),
-               "%s: bad sizes groups=%d S=%d", op, d->groups, S);
-  FF_CHECK_ARG(d->logits && d->ldlogits >= S, "%s: logits missing or ldlogits < S", op);
-  FF_CHECK_ARG(!(d->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", op, d->flags);
-  FF_CHECK_ARG(d->ntok >= 0 && L >= 0 && L == S - d->ntok, "%s: L=%d must be S - ntok = %d - %d", op, L, S, d->ntok);
-  FF_CHECK_ARG(d->term_lo >= 0 && d->term_lo < d->term_hi && d->term_hi <= d->ntok,
-               "%s: terminator range [%d, %d) empty or outside the %d special tokens", op, d->term_lo, d->term_hi, d->ntok);
-  FF_CHECK_ARG(d->follows || !(d->flags & FF_CONSTRAIN_CONNECT), "%s: FF_CONSTRAIN_CONNECT needs the follow table", op);
+  const int S = io.S, W = d->width, groups = io.rows / W;
+  ConBeamArgs a;
+  memset(&a, 0, sizeof(a));
+  FF_RETURN_IF(ff_step_args(&a.p, op, true, io));
+  FF_RETURN_IF(ff_loop_rule_check(op, ff_loop_rule_io{d->follows, d->L, d->flags, d->ntok}, S, io.term_lo, io.term_hi));
   FF_CHECK_ARG(d->scores_in && d->scores_out && d->fin_in && d->fin_out && d->dead_in && d->dead_out && d->first_in && d->first_out &&
                    d->prev_in && d->prev_out && d->visited_in && d->visited_out && d->mask_rows && d->parent && d->next_tok,
                "%s: null pointer", op);
   FF_CHECK_ARG(d->visited_in != d->visited_out, "%s: visited_out must not be visited_in", op);
-  ConBeamArgs a;
-  memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_pointer_feedback(&a.p, op, true, d->memory, d->E, d->next_rows, d->ldnext, d->next_stats, d->count_ge, arrive, host_slot));
-  a.p.S = S; a.p.mask = d->mask; a.p.kv_len = d->kv_len;
   a.p.extra = d->mask_rows; a.p.ldextra = S;
-  a.p.B = d->groups * W; a.p.spg = d->groups_per_wireframe * W;
-  a.p.logits = d->logits; a.p.ldlogits = d->ldlogits; a.p.ge_bound = d->ntok;
-  a.p.term_lo = d->term_lo; a.p.term_hi = d->term_hi;
-  a.groups = d->groups; a.rows = d->mask_rows; a.follows = d->follows; a.L = L; a.fw = (L + 31) >> 5; a.flags = d->flags; a.ntok = d->ntok;
+  a.groups = groups; a.rows = d->mask_rows; a.follows = d->follows; a.L = d->L; a.fw = (d->L + 31) >> 5; a.flags = d->flags; a.ntok = d->ntok;
   a.score_in = d->scores_in; a.score_out = d->scores_out;
   a.fin_in = d->fin_in; a.dead_in = d->dead_in; a.first_in = d->first_in; a.prev_in = d->prev_in; a.visited_in = d->visited_in;
   a.fin_out = d->fin_out; a.dead_out = d->dead_out; a.first_out = d->first_out; a.prev_out = d->prev_out; a.visited_out = d->visited_out;
   a.parent = d->parent; a.tok = d->next_tok;
   hipStream_t st = (hipStream_t)stream;
-  FFProfScope prof(FF_CAT_POINTER, (double)d->groups * W * S * 14.0, st);
-  const dim3 grid(ff_cdiv(d->groups, 4)), block(256);
+  FFProfScope prof(FF_CAT_POINTER, (double)io.rows * S * 14.0, st);
+  const dim3 grid(ff_cdiv(groups, 4)), block(256);
   const int rc = ff_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(W, [&](auto w) {
     hipLaunchKernelGGL(beam_constrained_select_kernel<decltype(w)::value>, grid, block, 0, st, a);
     return FF_OK;
@@ -278,8 +197,13 @@ int ff_beam_constrained_select_sync(const ff_beam_constrained_step* d, int* arri
   return FF_OK;
 }
 
-extern "C" int ff_beam_constrained_select(const ff_beam_constrained_step* step, ff_stream_t stream) {
-  return ff_beam_constrained_select_sync(step, nullptr, nullptr, stream);
+extern "C" int ff_beam_constrained_select(const ff_beam_constrained_step* d, ff_stream_t stream) {
+  FF_CHECK_ARG(d != nullptr, "ff_beam_constrained_select: null descriptor");
+  FF_RETURN_IF(ff_beam_check_sizes("ff_beam_constrained_select", d->groups, d->width, d->groups_per_wireframe, d->S));
+  return ff_beam_constrained_select_sync(
+      ff_step_io{d->logits, d->ldlogits, d->S, d->mask, d->kv_len, d->groups * d->width, d->groups_per_wireframe * d->width, d->term_lo,
+                 d->term_hi, d->ntok, d->memory, d->E, d->next_rows, d->ldnext, d->next_stats, d->count_ge, nullptr, nullptr},
+      d, stream);
 }
 
 int ff_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* parent, int* first, int* prev, unsigned* visited, int Bc,

@@ -22,7 +22,10 @@
 // The opt-in decodes are the same run with another selection in place of the greedy pointer launch: a Mode (below) names the
 // kind, its sequences per anchor and its parameters; every kind is one case of the switches in layout_decode, init_state, select_step
 // and pack, behind one plan (plan_mode), one size query (decode_workspace_bytes) and one step head (step_head).  Their per-step
-// records lie last in the workspace, and the output is packed from the records up to the stop step.
+// records lie last in the workspace, named by role in DecodeBuffers (score, finished, parent, dead, first, prev, visited,
+// byte_rows, ...), and the output is packed from the records up to the stop step.  select_step fills ONE ff_step_io (ff_common.h:
+// what every selection launch takes) per step; a case adds its mode's records and parameters.  The cases of constrain and
+// constrained beam share the rule's operands (rule_of), those of beam and constrained beam the parent trace and the reorder.
 //   beam (ff_decode_beam): W sequences per anchor -- beam k of compact anchor a is chunk-local sequence a * W + k,
 //     so a chunk's Fc / Bc are W times its anchor counts and w = i / Fc holds.  ff_beam_select (+ ff_beam_reorder of the x0 /
 //     qkv0 prefixes); records (token, parent, score, finished).
@@ -245,28 +248,19 @@ struct DecodeBuffers {
   int *cnt_tot;           // [T] per-step totals (steps_kernel)
   int *steps_dev;
   int *fin, *slot_all, *perm_all;   // FF_RETIRE_FINISHED: finish positions [Btot] (when not host-mapped), slot maps [Btot]
-  // beam decode: [T, Btot] each, row s = the beams' state after s steps (row 0: the start state); the tokens are tok_all's rows
-  float* bm_score;
-  int *bm_fin, *bm_parent;
-  // forced decode: [T-1, Btot] each, row s = what step s scored (log-probability of the forced token, the argmax, the rank)
-  float* fc_lp;
-  int *fc_greedy, *fc_rank;
-  // sampled decode: [T, Btot] each, row s = the samples' state after s steps (row 0: the start state); and the draw every
-  // sequence reads, [Btot], written once per call
-  float* sm_lp;
-  int *sm_fin, *sm_row;
-  // constrained decode: [T, Btot] each, row s = the sequences' state after s steps (log-probability, finished, dead end, first,
-  // prev); the visited words [Btot, ceil(L/32)] and the constraint byte rows [Btot, S], both rewritten by every step
-  float* cn_lp;
-  int *cn_fin, *cn_dead, *cn_first, *cn_prev;
-  unsigned* cn_visited;
-  unsigned char* cn_rows;
-  // constrained beam decode: the beam decode's records (bm_*) plus the cumulative dead flag [T, Btot]; the rule's state as two
-  // halves that the steps read and write alternately (first, prev: [2, Btot]; visited: [2, Btot, ceil(L/32)]: step s reads
-  // half s & 1); the constraint byte rows [Btot, S]
-  int *cb_dead, *cb_first, *cb_prev;
-  unsigned* cb_visited;
-  unsigned char* cb_rows;
+  // The opt-in modes' records, one pointer per role (layout_decode: which of them a mode has, and their sizes).  Per step, [T, Btot],
+  // row s = the state after s steps (row 0: the start state); the tokens are tok_all's rows:
+  float* score;             // beam, constrained beam: the beams' scores; sample, constrain: the log-probability of the step's token
+  int *finished, *parent, *dead; // finished (all four); parent beam (the beam modes); dead end (constrain), cumulative (constrained beam)
+  // The loop rule's state.  constrain: first, prev [T, Btot] per step; visited [Btot, ceil(L/32)] rewritten by every step.
+  // constrained beam: two halves that the steps read and write alternately (first, prev: [2, Btot]; visited: [2, Btot, ceil(L/32)]:
+  // step s reads half s & 1).  byte_rows [Btot, S]: the constraint byte rows, rewritten by every step.
+  int *first, *prev;
+  unsigned* visited;
+  unsigned char* byte_rows;
+  int* row_id;              // sample: [Btot] the draw every sequence reads, written once per call
+  // forced: [T-1, Btot] each, row s = what step s scored (the forced token's log-probability is `score`; the argmax, the rank)
+  int *greedy, *rank;
 };
 
 // A micro-batch is a contiguous range [b0, b0 + Bc) of the COMPACT sequence index: nw >= 1 consecutive
@@ -487,48 +481,44 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     b.perm_all = bp.take<int>(Btot);
   }
   if (want_lp) b.lp_all = bp.take<float>((size_t)(T - 1 > 0 ? T - 1 : 1) * Btot);
+  // (every mode's arrays in the order and sizes they always had: tests/test_workspace_layout.py holds the table)
+  const size_t TB = (size_t)T * Btot;
+  const size_t fw = (size_t)(p->L + 31) / 32, vw = Btot * (fw > 0 ? fw : 1);   // visited words; one word per sequence at L = 0, so that the array is never empty
   switch (mode.kind) {
     case Mode::BEAM:
-      b.bm_score = bp.take<float>((size_t)T * Btot);
-      b.bm_fin = bp.take<int>((size_t)T * Btot);
-      b.bm_parent = bp.take<int>((size_t)T * Btot);
+    case Mode::CONSTRAIN_BEAM:
+      b.score = bp.take<float>(TB);
+      b.finished = bp.take<int>(TB);
+      b.parent = bp.take<int>(TB);
+      if (mode.kind == Mode::BEAM) break;
+      b.dead = bp.take<int>(TB);
+      b.first = bp.take<int>(2 * Btot);     // (the two halves)
+      b.prev = bp.take<int>(2 * Btot);
+      b.visited = bp.take<unsigned>(2 * vw);
+      b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
       break;
     case Mode::FORCED: {
       const size_t n = (size_t)(T - 1 > 0 ? T - 1 : 1) * Btot;
-      b.fc_lp = bp.take<float>(n);
-      b.fc_greedy = bp.take<int>(n);
-      b.fc_rank = bp.take<int>(n);
+      b.score = bp.take<float>(n);
+      b.greedy = bp.take<int>(n);
+      b.rank = bp.take<int>(n);
       break;
     }
     case Mode::SAMPLE:
-      b.sm_lp = bp.take<float>((size_t)T * Btot);
-      b.sm_fin = bp.take<int>((size_t)T * Btot);
-      b.sm_row = bp.take<int>(Btot);
+      b.score = bp.take<float>(TB);
+      b.finished = bp.take<int>(TB);
+      b.row_id = bp.take<int>(Btot);
       break;
     case Mode::CONSTRAIN:
-    case Mode::CONSTRAIN_AHEAD: {   // (the tables of the look-ahead are operands: nothing of it lies here)
-      b.cn_lp = bp.take<float>((size_t)T * Btot);
-      b.cn_fin = bp.take<int>((size_t)T * Btot);
-      b.cn_dead = bp.take<int>((size_t)T * Btot);
-      b.cn_first = bp.take<int>((size_t)T * Btot);
-      b.cn_prev = bp.take<int>((size_t)T * Btot);
-      const size_t fw = (size_t)(p->L + 31) / 32;   // visited words per sequence; one word at L = 0, so that the array is never empty
-      b.cn_visited = bp.take<unsigned>(Btot * (fw > 0 ? fw : 1));
-      b.cn_rows = bp.take<unsigned char>(Btot * (size_t)S);
+    case Mode::CONSTRAIN_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
+      b.score = bp.take<float>(TB);
+      b.finished = bp.take<int>(TB);
+      b.dead = bp.take<int>(TB);
+      b.first = bp.take<int>(TB);
+      b.prev = bp.take<int>(TB);
+      b.visited = bp.take<unsigned>(vw);
+      b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
       break;
-    }
-    case Mode::CONSTRAIN_BEAM: {
-      b.bm_score = bp.take<float>((size_t)T * Btot);
-      b.bm_fin = bp.take<int>((size_t)T * Btot);
-      b.bm_parent = bp.take<int>((size_t)T * Btot);
-      b.cb_dead = bp.take<int>((size_t)T * Btot);
-      b.cb_first = bp.take<int>(2 * Btot);
-      b.cb_prev = bp.take<int>(2 * Btot);
-      const size_t fw = (size_t)(p->L + 31) / 32;   // (one word at L = 0, so that the array is never empty)
-      b.cb_visited = bp.take<unsigned>(2 * Btot * (fw > 0 ? fw : 1));
-      b.cb_rows = bp.take<unsigned char>(Btot * (size_t)S);
-      break;
-    }
     default: break;
   }
   if (out) *out = b;
@@ -1057,35 +1047,41 @@ struct DecodeRun {
     }
     return FF_OK;
   }
+  // The loop rule's operands of one micro-batch in the three constrained modes: the flags, the chunk's part of the follow table
+  // and the words per row of it (= per sequence of `visited`).
+  struct Rule { const unsigned* follows; int L, fw, flags; };
+  Rule rule_of(const Chunk& c) const {
+    const int L = p->L, fw = (L + 31) / 32;
+    const unsigned* follows = mode.kind == Mode::CONSTRAIN_BEAM ? mode.cbeam()->follows : mode.con().follows;
+    return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, mode.kind == Mode::CONSTRAIN_BEAM ? mode.cbeam()->flags : mode.con().flags};
+  }
   // Row 0 of the mode's per-step records and of the token array for one micro-batch: the start state of its sequences.
   int init_state(const Chunk& c) {
     const int G = mode.G, pad_tok = m->num_token - 1;
     const int* ni = io.num_input ? io.num_input + c.w0 : nullptr;
     hipStream_t st = sts[c.sid];
+    if (mode.kind == Mode::FORCED) return FF_OK;   // (the start tokens are row 0 of the token array, forced_tokens() put the paths there)
+    int* tok = buf.tok_all + c.b0;
+    float* score = buf.score + c.b0;
+    int* fin = buf.finished + c.b0;
     switch (mode.kind) {
       case Mode::BEAM:
-        return ff_beam_init(buf.tok_all + c.b0, buf.bm_score + c.b0, buf.bm_fin + c.b0, buf.bm_parent + c.b0, c.Bc, c.Fc / G, G, c.f0, ni,
-                            pad_tok, p->term_lo, p->term_hi, st);
+        return ff_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok, p->term_lo, p->term_hi, st);
       case Mode::SAMPLE:
-        return ff_sample_init(buf.tok_all + c.b0, buf.sm_lp + c.b0, buf.sm_fin + c.b0, buf.sm_row + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F,
-                              ni, pad_tok, p->term_lo, p->term_hi, st);
+        return ff_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F, ni, pad_tok, p->term_lo, p->term_hi, st);
       case Mode::CONSTRAIN:
-      case Mode::CONSTRAIN_AHEAD: {
-        const int fw = (p->L + 31) / 32;
-        const unsigned* follows = mode.con().follows;
-        return ff_constrain_init(buf.tok_all + c.b0, buf.cn_lp + c.b0, buf.cn_fin + c.b0, buf.cn_dead + c.b0, buf.cn_first + c.b0,
-                                 buf.cn_prev + c.b0, buf.cn_visited + (size_t)c.b0 * fw, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo,
-                                 p->term_hi, m->num_token, follows ? follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, st);
+      case Mode::CONSTRAIN_AHEAD:
+      case Mode::CONSTRAIN_BEAM: {   // (constrained beam: half 0 of the ping-pong state, step 0 reads it)
+        const Rule r = rule_of(c);
+        int *dead = buf.dead + c.b0, *first = buf.first + c.b0, *prev = buf.prev + c.b0;
+        unsigned* visited = buf.visited + (size_t)c.b0 * r.fw;
+        if (mode.kind == Mode::CONSTRAIN_BEAM)
+          return ff_constrain_beam_init(tok, score, fin, dead, buf.parent + c.b0, first, prev, visited, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok,
+                                        p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
+        return ff_constrain_init(tok, score, fin, dead, first, prev, visited, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo, p->term_hi,
+                                 m->num_token, r.follows, r.L, st);
       }
-      case Mode::CONSTRAIN_BEAM: {   // (half 0 of the ping-pong state: step 0 reads it)
-        const int fw = (p->L + 31) / 32;
-        const unsigned* follows = mode.cbeam()->follows;
-        return ff_constrain_beam_init(buf.tok_all + c.b0, buf.bm_score + c.b0, buf.bm_fin + c.b0, buf.cb_dead + c.b0, buf.bm_parent + c.b0,
-                                      buf.cb_first + c.b0, buf.cb_prev + c.b0, buf.cb_visited + (size_t)c.b0 * fw, c.Bc, c.Fc / G, G, c.f0,
-                                      ni, pad_tok, p->term_lo, p->term_hi, m->num_token,
-                                      follows ? follows + (size_t)c.w0 * p->L * fw : nullptr, p->L, st);
-      }
-      default: return FF_OK;   // (forced: the start tokens are row 0 of the token array, forced_tokens() put the paths there)
+      default: return FF_OK;
     }
   }
   // Decode step `step` (position t = step + 1) of every micro-batch that has slots left, on the chunk's stream: the slot set
@@ -1136,76 +1132,61 @@ struct DecodeRun {
     const bool hand_over = lagged && mode.kind != Mode::FORCED;   // (a forced step counts nothing: its slot and trow are not used)
     int* arrive = hand_over ? buf.arrive + slot : nullptr;
     int* host_slot = hand_over ? pool->hpin_dev + slot : nullptr;
+    // what every opt-in launch takes: the chunk's logits, masks and memory, its Bc rows, the next x0 rows and the stop counter
+    const ff_step_io sio{logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, p->term_lo, p->term_hi, m->num_token, mem_w, E, next_rows, E, c.x0stat,
+                         mode.kind != Mode::FORCED ? buf.cnt_ge + slot : nullptr, arrive, host_slot};
+    int* tok_out = buf.tok_all + out;
     switch (mode.kind) {
-      case Mode::BEAM: {
+      case Mode::BEAM:
+      case Mode::CONSTRAIN_BEAM: {
         // top-W selection, then the reorder of positions < t of x0 and qkv0 behind it on the same stream: the next decoder pass
         // reads reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
-        const int W = mode.G, G = c.Bc / W;
-        FF_RETURN_IF(ff_beam_select_sync(logits_dst, S, S, mask_w, kv_w, G, W, c.Fc / W, buf.bm_score + in, buf.bm_score + out,
-                                         buf.bm_fin + in, buf.bm_fin + out, nullptr, 0, t, buf.bm_parent + out, buf.tok_all + out,
-                                         p->term_lo, p->term_hi, mem_w, E, next_rows, E, buf.cnt_ge + slot, m->num_token, c.x0stat,
-                                         arrive, host_slot, st));
-        if (mode.beam()->trace_parent)
-          FF_CHECK_HIP(hipMemcpyAsync(mode.beam()->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
-        if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
+        const int W = mode.G;
+        int* trace_parent;
+        if (mode.kind == Mode::BEAM) {
+          trace_parent = mode.beam()->trace_parent;
+          FF_RETURN_IF(ff_beam_select_sync(sio, W, buf.score + in, buf.score + out, buf.finished + in, buf.finished + out, nullptr, 0, t,
+                                           buf.parent + out, tok_out, st));
+        } else {   // the constrained selection: state half step & 1 -> half t & 1 (the common operands come from sio)
+          trace_parent = mode.cbeam()->trace_parent;
+          const Rule r = rule_of(c);
+          const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
+          ff_beam_constrained_step d;
+          memset(&d, 0, sizeof(d));
+          d.width = W; d.follows = r.follows; d.L = r.L; d.flags = r.flags; d.ntok = m->num_token;
+          d.scores_in = buf.score + in; d.fin_in = buf.finished + in; d.dead_in = buf.dead + in;
+          d.first_in = buf.first + hin; d.prev_in = buf.prev + hin; d.visited_in = buf.visited + hin * r.fw;
+          d.scores_out = buf.score + out; d.fin_out = buf.finished + out; d.dead_out = buf.dead + out;
+          d.first_out = buf.first + hout; d.prev_out = buf.prev + hout; d.visited_out = buf.visited + hout * r.fw;
+          d.mask_rows = buf.byte_rows + (size_t)c.b0 * S;
+          d.parent = buf.parent + out; d.next_tok = tok_out;
+          FF_RETURN_IF(ff_beam_constrained_select_sync(sio, &d, st));
+        }
+        if (trace_parent)
+          FF_CHECK_HIP(hipMemcpyAsync(trace_parent + trow, buf.parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
+        if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.parent + out, c.Bc / W, W, st));
         return FF_OK;
       }
       case Mode::SAMPLE: {   // (this step's uniforms are read through the chunk's row_id)
         const ff_sample_params* sp = mode.sample();
         const int rows = N * F * mode.G;
-        return ff_pointer_sample_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, sp->uniforms + (size_t)step * rows, rows,
-                                      buf.sm_row + c.b0, buf.sm_fin + in, sp->temperature, sp->top_k, sp->top_p, p->term_lo, p->term_hi,
-                                      buf.tok_all + out, buf.sm_lp + out, buf.sm_fin + out, mem_w, E, next_rows, E, c.x0stat,
-                                      buf.cnt_ge + slot, m->num_token, arrive, host_slot, st);
+        return ff_pointer_sample_sync(sio, sp->uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, buf.finished + in, sp->temperature,
+                                      sp->top_k, sp->top_p, tok_out, buf.score + out, buf.finished + out, st);
       }
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
-        const int L = p->L, fw = (L + 31) / 32;
-        const ff_constrain_params cp = mode.con();
-        const unsigned* follows = cp.follows ? cp.follows + (size_t)c.w0 * L * fw : nullptr;
-        unsigned* visited = buf.cn_visited + (size_t)c.b0 * fw;
-        unsigned char* byte_rows = buf.cn_rows + (size_t)c.b0 * S;
-        if (mode.kind == Mode::CONSTRAIN)
-          return ff_pointer_constrained_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, follows, L, cp.flags, m->num_token,
-                                             p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in, visited,
-                                             byte_rows, buf.tok_all + out, buf.cn_lp + out, buf.cn_fin + out, buf.cn_dead + out,
-                                             buf.cn_first + out, buf.cn_prev + out, mem_w, E, next_rows, E, c.x0stat,
-                                             buf.cnt_ge + slot, arrive, host_slot, st);
+        const Rule r = rule_of(c);
+        const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
+                                      buf.byte_rows + (size_t)c.b0 * S, tok_out, buf.score + out, buf.finished + out, buf.dead + out,
+                                      buf.first + out, buf.prev + out};
+        const ff_loop_rule_io rio{r.follows, r.L, r.flags, m->num_token};
+        if (mode.kind == Mode::CONSTRAIN) return ff_pointer_constrained_sync("ff_pointer_constrained", sio, rio, cs, nullptr, st);
         // the look-ahead: this step selects position t, so a loop has T - 1 - t further positions to close in
-        return ff_pointer_constrained_ahead_sync(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, follows, L, cp.flags, m->num_token,
-                                                 p->term_lo, p->term_hi, buf.cn_fin + in, buf.cn_first + in, buf.cn_prev + in,
-                                                 visited, byte_rows, buf.tok_all + out, buf.cn_lp + out, buf.cn_fin + out,
-                                                 buf.cn_dead + out, buf.cn_first + out, buf.cn_prev + out, mem_w, E, next_rows, E,
-                                                 c.x0stat, buf.cnt_ge + slot, mode.ahead()->close_dist + (size_t)c.w0 * L * L,
-                                                 mode.ahead()->cycle_len + (size_t)c.w0 * L, T - 1 - t, arrive, host_slot, st);
-      }
-      case Mode::CONSTRAIN_BEAM: {
-        // the constrained top-W selection (state half step & 1 -> half t & 1), then the beam decode's reorder of the prefixes
-        const ff_constrain_beam_params* cb = mode.cbeam();
-        const int W = mode.G, G = c.Bc / W, L = p->L, fw = (L + 31) / 32;
-        const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
-        ff_beam_constrained_step d;
-        memset(&d, 0, sizeof(d));
-        d.logits = logits_dst; d.ldlogits = S; d.S = S; d.mask = mask_w; d.kv_len = kv_w;
-        d.groups = G; d.width = W; d.groups_per_wireframe = c.Fc / W;
-        d.follows = cb->follows ? cb->follows + (size_t)c.w0 * L * fw : nullptr;
-        d.L = L; d.flags = cb->flags; d.ntok = m->num_token; d.term_lo = p->term_lo; d.term_hi = p->term_hi;
-        d.scores_in = buf.bm_score + in; d.fin_in = buf.bm_fin + in; d.dead_in = buf.cb_dead + in;
-        d.first_in = buf.cb_first + hin; d.prev_in = buf.cb_prev + hin; d.visited_in = buf.cb_visited + hin * fw;
-        d.scores_out = buf.bm_score + out; d.fin_out = buf.bm_fin + out; d.dead_out = buf.cb_dead + out;
-        d.first_out = buf.cb_first + hout; d.prev_out = buf.cb_prev + hout; d.visited_out = buf.cb_visited + hout * fw;
-        d.mask_rows = buf.cb_rows + (size_t)c.b0 * S;
-        d.parent = buf.bm_parent + out; d.next_tok = buf.tok_all + out;
-        d.memory = mem_w; d.E = E; d.next_rows = next_rows; d.ldnext = E; d.next_stats = c.x0stat; d.count_ge = buf.cnt_ge + slot;
-        FF_RETURN_IF(ff_beam_constrained_select_sync(&d, arrive, host_slot, st));
-        if (cb->trace_parent)
-          FF_CHECK_HIP(hipMemcpyAsync(cb->trace_parent + trow, buf.bm_parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
-        if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.bm_parent + out, G, W, st));
-        return FF_OK;
+        const ff_lookahead_io ahead{mode.ahead()->close_dist + (size_t)c.w0 * r.L * r.L, mode.ahead()->cycle_len + (size_t)c.w0 * r.L, T - 1 - t};
+        return ff_pointer_constrained_sync("ff_pointer_constrained_ahead", sio, rio, cs, &ahead, st);
       }
       case Mode::FORCED:   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
-        return ff_pointer_forced(logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, buf.tok_all + out, buf.fc_lp + in, buf.fc_greedy + in,
-                                 buf.fc_rank + in, mem_w, E, next_rows, E, c.x0stat, st);
+        return ff_pointer_forced_sync(sio, tok_out, buf.score + in, buf.greedy + in, buf.rank + in, st);
       default: break;
     }
     ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, arrive, host_slot, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
@@ -1249,7 +1230,7 @@ struct DecodeRun {
         FF_CHECK_HIP(hipStreamWaitEvent(main_st, pool->join_ev[s], 0));
       }
     const ff_forced_params* fp = mode.forced();
-    FF_RETURN_IF(ff_forced_finalize(buf.tok_all, buf.fc_lp, buf.fc_greedy, buf.fc_rank, fp->lengths, Btot, T, fp->logprob, fp->greedy,
+    FF_RETURN_IF(ff_forced_finalize(buf.tok_all, buf.score, buf.greedy, buf.rank, fp->lengths, Btot, T, fp->logprob, fp->greedy,
                                     fp->rank, fp->seq_logprob, main_st));
     FF_CHECK_HIP(hipStreamSynchronize(main_st));   // (the caller may free or reuse the workspace next, as after ff_decode)
     if (io.steps_done) *io.steps_done = forced_steps;
@@ -1391,22 +1372,23 @@ struct DecodeRun {
     const int G = mode.G, dd = dedup ? 1 : 0;
     switch (mode.kind) {
       case Mode::BEAM:
-        return ff_beam_finalize(buf.tok_all, buf.bm_parent, buf.bm_score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
-                                c.Fc / G, c.f0, c.b0, mode.beam()->beams, mode.beam()->scores, io.predict, io.seq_of_row, main_st);
+      case Mode::CONSTRAIN_BEAM: {
+        const bool con = mode.kind == Mode::CONSTRAIN_BEAM;
+        FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.parent, buf.score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
+                                      c.Fc / G, c.f0, c.b0, con ? mode.cbeam()->beams : mode.beam()->beams,
+                                      con ? mode.cbeam()->scores : mode.beam()->scores, io.predict, io.seq_of_row, main_st));
+        if (!con) return FF_OK;
+        return ff_constrain_beam_dead(buf.dead, Btot, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G, c.f0, c.b0,
+                                      mode.cbeam()->dead_end, main_st);
+      }
       case Mode::SAMPLE:
-        return ff_sample_finalize(buf.tok_all, buf.sm_lp, buf.sm_fin, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
+        return ff_sample_finalize(buf.tok_all, buf.score, buf.finished, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
                                   c.Fc / G, c.f0, c.b0, mode.sample()->samples, mode.sample()->logprob, mode.sample()->scores, io.predict,
                                   io.seq_of_row, main_st);
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
-        return ff_constrain_finalize(buf.tok_all, buf.cn_lp, buf.cn_fin, buf.cn_dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
+        return ff_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
                                      c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con().logprob, mode.con().dead_end, io.seq_of_row, main_st);
-      case Mode::CONSTRAIN_BEAM:
-        FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.bm_parent, buf.bm_score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0,
-                                      c.nw, c.Fc / G, c.f0, c.b0, mode.cbeam()->beams, mode.cbeam()->scores, io.predict, io.seq_of_row,
-                                      main_st));
-        return ff_constrain_beam_dead(buf.cb_dead, Btot, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G, c.f0, c.b0,
-                                      mode.cbeam()->dead_end, main_st);
       default: break;   // (forced: forced_epilogue packs all rows at once)
     }
     const long total = (long)c.nw * F * T;
@@ -1475,6 +1457,10 @@ int check_opt_in_outputs(const char* name, const ff_decode_params* p, const char
   FF_CHECK_ARG(have && !trace_best && !trace_second && !pointer_out, "%s: %s required; no best / second traces, no pointer_out", name,
                required);
   return FF_OK;
+}
+// ... the loop rule's operands in the three constrained decodes (the operators' own check: flags, follow table, terminator range) ...
+int check_loop_rule(const char* name, int flags, const unsigned* follows, const ff_model* m, const ff_decode_params* p) {
+  return ff_loop_rule_check(name, ff_loop_rule_io{follows, p->L, flags, m->num_token}, p->L + m->num_token, p->term_lo, p->term_hi);
 }
 // ... and what they hand to the decode: no extra mask, no pointer_out, no best / second traces, no log-probabilities.
 DecodeIO opt_in_io(const float* memory, const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host,
@@ -1665,11 +1651,7 @@ extern "C" int ff_decode_constrained(const ff_model* m, const ff_decode_params* 
                                      size_t workspace_bytes, const ff_constrain_params* constrain, ff_stream_t stream) {
   FF_CHECK_ARG(m && p && constrain, "ff_decode_constrained: null model, params or constrain params");
   FF_RETURN_IF(check_opt_in("ff_decode_constrained", "the constrained decode is", p, extra_mask));
-  FF_CHECK_ARG(!(constrain->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "ff_decode_constrained: unknown flag bits %d", constrain->flags);
-  FF_CHECK_ARG(constrain->follows || !(constrain->flags & FF_CONSTRAIN_CONNECT), "ff_decode_constrained: FF_CONSTRAIN_CONNECT needs the follow table");
-  // (its own wording of the terminator rule, stricter than the shared one behind it)
-  FF_CHECK_ARG(p->term_lo >= 0 && p->term_lo < p->term_hi && p->term_hi <= m->num_token,
-               "ff_decode_constrained: terminator range [%d, %d) empty or outside the %d special tokens", p->term_lo, p->term_hi, m->num_token);
+  FF_RETURN_IF(check_loop_rule("ff_decode_constrained", constrain->flags, constrain->follows, m, p));
   FF_RETURN_IF(check_opt_in_outputs("ff_decode_constrained", p, "logprob and dead_end", constrain->logprob && constrain->dead_end,
                                     trace_best, trace_second, pointer_out));
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
@@ -1690,13 +1672,10 @@ extern "C" int ff_decode_constrained_ahead(const ff_model* m, const ff_decode_pa
   const char* name = "ff_decode_constrained_ahead";
   FF_CHECK_ARG(m && p && ahead, "%s: null model, params or look-ahead params", name);
   FF_RETURN_IF(check_opt_in(name, "the constrained decode with look-ahead is", p, extra_mask));
-  FF_CHECK_ARG(!(ahead->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", name, ahead->flags);
+  FF_RETURN_IF(check_loop_rule(name, ahead->flags, ahead->follows, m, p));
   FF_CHECK_ARG(ahead->flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", name);
-  FF_CHECK_ARG(ahead->follows, "%s: FF_CONSTRAIN_CONNECT needs the follow table", name);
   FF_CHECK_ARG(ahead->close_dist && ahead->cycle_len, "%s: close_dist and cycle_len are required", name);
   FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the tables' byte)", name, p->T);
-  FF_CHECK_ARG(p->term_lo >= 0 && p->term_lo < p->term_hi && p->term_hi <= m->num_token,
-               "%s: terminator range [%d, %d) empty or outside the %d special tokens", name, p->term_lo, p->term_hi, m->num_token);
   FF_RETURN_IF(check_opt_in_outputs(name, p, "logprob and dead_end", ahead->logprob && ahead->dead_end, trace_best, trace_second,
                                     pointer_out));
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
@@ -1721,10 +1700,7 @@ extern "C" int ff_decode_constrained_beam(const ff_model* m, const ff_decode_par
   FF_RETURN_IF(check_opt_in(name, "the constrained beam decode is", p, extra_mask));
   FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d",
                name, beam->width, p->L + m->num_token);
-  FF_CHECK_ARG(!(beam->flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT)), "%s: unknown flag bits %d", name, beam->flags);
-  FF_CHECK_ARG(beam->follows || !(beam->flags & FF_CONSTRAIN_CONNECT), "%s: FF_CONSTRAIN_CONNECT needs the follow table", name);
-  FF_CHECK_ARG(p->term_lo >= 0 && p->term_lo < p->term_hi && p->term_hi <= m->num_token,
-               "%s: terminator range [%d, %d) empty or outside the %d special tokens", name, p->term_lo, p->term_hi, m->num_token);
+  FF_RETURN_IF(check_loop_rule(name, beam->flags, beam->follows, m, p));
   FF_RETURN_IF(check_opt_in_outputs(name, p, "beams, scores and dead_end", beam->beams && beam->scores && beam->dead_end, trace_best,
                                     trace_second, pointer_out));
   // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS

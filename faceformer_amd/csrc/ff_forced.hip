@@ -98,25 +98,29 @@ __global__ void forced_finalize_kernel(const int* __restrict__ tok, const float*
 
 }  // namespace
 
-extern "C" int ff_pointer_forced(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                                 int seqs_per_group, const int* forced, float* logprob, int* greedy, int* rank,
-                                 const float* memory, int E, float* next_rows, int ldnext, float* next_stats, ff_stream_t stream) {
+int ff_pointer_forced_sync(const ff_step_io& io, const int* forced, float* logprob, int* greedy, int* rank, ff_stream_t stream) {
+  const int B = io.rows, S = io.S;
   if (B == 0) return FF_OK;
-  FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "ff_pointer_forced: bad sizes B=%d S=%d", B, S);
-  FF_CHECK_ARG(logits && ldlogits >= S, "ff_pointer_forced: logits missing or ldlogits < S");
-  FF_CHECK_ARG(forced && logprob && greedy && rank, "ff_pointer_forced: null pointer");
+  FF_CHECK_ARG(B > 0 && S > 0 && io.rows_per_wireframe > 0, "ff_pointer_forced: bad sizes B=%d S=%d", B, S);
   ForcedArgs a;
   memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_pointer_forced", true, memory, E, next_rows, ldnext, next_stats, nullptr, nullptr, nullptr));
-  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
-  a.p.B = B; a.p.spg = seqs_per_group;
-  a.p.logits = logits; a.p.ldlogits = ldlogits;
+  FF_RETURN_IF(ff_step_args(&a.p, "ff_pointer_forced", true, io));
+  FF_CHECK_ARG(forced && logprob && greedy && rank, "ff_pointer_forced: null pointer");
   a.forced = forced; a.logprob = logprob; a.greedy = greedy; a.rank = rank;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 12.0, st);
   hipLaunchKernelGGL(pointer_forced_kernel, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
+}
+
+// (no terminator range, no counter: a forced step finishes nothing and counts nothing)
+extern "C" int ff_pointer_forced(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                 int seqs_per_group, const int* forced, float* logprob, int* greedy, int* rank,
+                                 const float* memory, int E, float* next_rows, int ldnext, float* next_stats, ff_stream_t stream) {
+  return ff_pointer_forced_sync(ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, 0, 0, 0, memory, E, next_rows, ldnext,
+                                           next_stats, nullptr, nullptr, nullptr},
+                                forced, logprob, greedy, rank, stream);
 }
 
 int ff_forced_tokens(const int64_t* paths, int* tok, int rows, int T, int S, hipStream_t st) {

@@ -37,12 +37,13 @@ int ff_dispatch(int v, F&& f) {
   else return v == V ? f(std::integral_constant<int, V>{}) : ff_dispatch<Rest...>(v, f);
 }
 
-// The feedback members of a pointer-head launch's arguments (PointerArgs, ff_device.h), checked and filled for operator `op`:
-// the next decoder input rows gathered from `memory` with their LayerNorm statistics, and the stop counter with its hand-over
-// to the host.  ld_rule: also ldnext >= E (ff_beam_select never had that rule: both wordings are kept).  (ff_pointer.hip)
+// A selection launch's arguments (PointerArgs, ff_device.h) from its step descriptor (ff_step_io, ff_common.h), checked and filled
+// for operator `op`: the logits, the common members (S, mask, kv_len, B, spg, ge_bound, the terminator range) and the feedback
+// members -- the next decoder input rows gathered from `memory` with their LayerNorm statistics, and the stop counter with its
+// hand-over to the host.  ld_rule: also ldnext >= E (ff_beam_select never had that rule: both wordings are kept).  The caller
+// adds `extra` where it has one.  (ff_pointer.hip)
 struct PointerArgs;
-int ff_pointer_feedback(PointerArgs* a, const char* op, bool ld_rule, const float* memory, int E, float* next_rows, int ldnext,
-                        float* next_stats, int* count_ge, int* arrive, int* host_slot);
+int ff_step_args(PointerArgs* a, const char* op, bool ld_rule, const ff_step_io& io);
 
 // A launch setting written by a setter (ff_set_gemm_tuning, ...) while other host threads launch: relaxed, like the knob table.
 struct FFSetting {

@@ -181,18 +181,22 @@ extern "C" int ff_pointer_argmax_lp(const float* p, int ldp, const float* memory
                                 nullptr, stream);
 }
 
-// The feedback members of the mode launches' PointerArgs (ff_launch.h)
-int ff_pointer_feedback(PointerArgs* a, const char* op, bool ld_rule, const float* memory, int E, float* next_rows, int ldnext,
-                        float* next_stats, int* count_ge, int* arrive, int* host_slot) {
-  const bool rows_ok = memory && E > 0 && (E & 3) == 0 && (ldnext & 3) == 0 && ff_aligned16(memory) && ff_aligned16(next_rows);
+// The mode launches' PointerArgs from their step descriptor (ff_launch.h)
+int ff_step_args(PointerArgs* a, const char* op, bool ld_rule, const ff_step_io& io) {
+  FF_CHECK_ARG(io.logits && io.ldlogits >= io.S, "%s: logits missing or ldlogits < S", op);
+  const bool rows_ok = io.memory && io.E > 0 && (io.E & 3) == 0 && (io.ldnext & 3) == 0 && ff_aligned16(io.memory) && ff_aligned16(io.next_rows);
   if (ld_rule)
-    FF_CHECK_ARG(!next_rows || (rows_ok && ldnext >= E), "%s: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment", op);
+    FF_CHECK_ARG(!io.next_rows || (rows_ok && io.ldnext >= io.E), "%s: next_rows needs memory, E %% 4 == 0, ldnext >= E and 16-byte alignment", op);
   else
-    FF_CHECK_ARG(!next_rows || rows_ok, "%s: next_rows needs memory, E %% 4 == 0 and 16-byte alignment", op);
-  FF_CHECK_ARG(!next_stats || (next_rows && (E & 31) == 0), "%s: next_stats needs next_rows and E %% 32 == 0", op);
-  FF_CHECK_ARG(!arrive || (host_slot && count_ge), "%s: counter hand-over without a counter", op);
-  a->memory = memory; a->E = E; a->next_rows = next_rows; a->ldnext = ldnext; a->next_stats = next_stats;
-  a->count_ge = count_ge; a->arrive = arrive; a->host_slot = host_slot;
+    FF_CHECK_ARG(!io.next_rows || rows_ok, "%s: next_rows needs memory, E %% 4 == 0 and 16-byte alignment", op);
+  FF_CHECK_ARG(!io.next_stats || (io.next_rows && (io.E & 31) == 0), "%s: next_stats needs next_rows and E %% 32 == 0", op);
+  FF_CHECK_ARG(!io.arrive || (io.host_slot && io.count_ge), "%s: counter hand-over without a counter", op);
+  a->S = io.S; a->mask = io.mask; a->kv_len = io.kv_len;
+  a->B = io.rows; a->spg = io.rows_per_wireframe;
+  a->logits = io.logits; a->ldlogits = io.ldlogits; a->ge_bound = io.ge_bound;
+  a->term_lo = io.term_lo; a->term_hi = io.term_hi;
+  a->memory = io.memory; a->E = io.E; a->next_rows = io.next_rows; a->ldnext = io.ldnext; a->next_stats = io.next_stats;
+  a->count_ge = io.count_ge; a->arrive = io.arrive; a->host_slot = io.host_slot;
   return FF_OK;
 }
 

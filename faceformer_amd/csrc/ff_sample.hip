@@ -219,26 +219,19 @@ __global__ void sample_finalize_kernel(const int* __restrict__ tok, const float*
 
 }  // namespace
 
-int ff_pointer_sample_sync(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
-                           int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
-                           float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok, float* logprob,
-                           int* fin_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
-                           int* count_ge, int ge_bound, int* arrive, int* host_slot, ff_stream_t stream) {
+int ff_pointer_sample_sync(const ff_step_io& io, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
+                           float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream) {
+  const int B = io.rows, S = io.S;
   if (B == 0) return FF_OK;
-  FF_CHECK_ARG(B > 0 && S > 0 && seqs_per_group > 0, "ff_pointer_sample: bad sizes B=%d S=%d", B, S);
-  FF_CHECK_ARG(logits && ldlogits >= S, "ff_pointer_sample: logits missing or ldlogits < S");
+  FF_CHECK_ARG(B > 0 && S > 0 && io.rows_per_wireframe > 0, "ff_pointer_sample: bad sizes B=%d S=%d", B, S);
+  SampleArgs a;
+  memset(&a, 0, sizeof(a));
+  FF_RETURN_IF(ff_step_args(&a.p, "ff_pointer_sample", true, io));
   FF_CHECK_ARG(uniforms && num_uniforms > 0 && next_tok && logprob && fin_out, "ff_pointer_sample: null pointer");
   FF_CHECK_ARG(row_id || num_uniforms >= B, "ff_pointer_sample: %d uniforms for %d rows without a row_id", num_uniforms, B);
   FF_CHECK_ARG(temperature >= 0.f && temperature <= FLT_MAX && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
                "ff_pointer_sample: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]", (double)temperature,
                top_k, (double)top_p);
-  SampleArgs a;
-  memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_pointer_feedback(&a.p, "ff_pointer_sample", true, memory, E, next_rows, ldnext, next_stats, count_ge, arrive, host_slot));
-  a.p.S = S; a.p.mask = mask; a.p.kv_len = kv_len;
-  a.p.B = B; a.p.spg = seqs_per_group;
-  a.p.logits = logits; a.p.ldlogits = ldlogits; a.p.ge_bound = ge_bound;
-  a.p.term_lo = term_lo; a.p.term_hi = term_hi;
   a.uniforms = uniforms; a.num_uniforms = num_uniforms; a.row_id = row_id; a.fin_in = fin_in; a.fin_out = fin_out;
   a.tok = next_tok; a.logprob = logprob;
   a.temperature = temperature; a.top_k = top_k; a.top_p = top_p;
@@ -254,9 +247,9 @@ extern "C" int ff_pointer_sample(float* logits, int ldlogits, int S, const unsig
                                  float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok,
                                  float* logprob, int* fin_out, const float* memory, int E, float* next_rows, int ldnext,
                                  float* next_stats, int* count_ge, int ge_bound, ff_stream_t stream) {
-  return ff_pointer_sample_sync(logits, ldlogits, S, mask, kv_len, B, seqs_per_group, uniforms, num_uniforms, row_id, fin_in,
-                                temperature, top_k, top_p, term_lo, term_hi, next_tok, logprob, fin_out, memory, E, next_rows,
-                                ldnext, next_stats, count_ge, ge_bound, nullptr, nullptr, stream);
+  return ff_pointer_sample_sync(ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, term_lo, term_hi, ge_bound, memory, E,
+                                           next_rows, ldnext, next_stats, count_ge, nullptr, nullptr},
+                                uniforms, num_uniforms, row_id, fin_in, temperature, top_k, top_p, next_tok, logprob, fin_out, stream);
 }
 
 int ff_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F, const int* num_input,

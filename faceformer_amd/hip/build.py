@@ -46,7 +46,7 @@ def build(force=False, verbose=False):
 def _build(BUILD_DIR, LIB_PATH, FLAGS, force, verbose):
     os.makedirs(BUILD_DIR, exist_ok=True)
     headers = [os.path.join(INCLUDE, "faceformer_hip.h"), os.path.join(CSRC, "ff_common.h"), os.path.join(CSRC, "ff_device.h"),
-               os.path.join(CSRC, "ff_launch.h")]
+               os.path.join(CSRC, "ff_launch.h"), os.path.join(CSRC, "ff_select.h")]
     hipcc = _hipcc()
     objs = []
     relink = force or not os.path.exists(LIB_PATH)
