@@ -168,14 +168,16 @@ int ff_sample_finalize(const int* tok, const float* lp, const int* fin, int Btot
 // L = S - ntok, the terminator range inside the special tokens, FF_CONSTRAIN_CONNECT with its follow table.
 struct ff_loop_rule_io { const unsigned* follows; int L, flags, ntok; };
 int ff_loop_rule_check(const char* op, const ff_loop_rule_io& r, int S, int term_lo, int term_hi);
-// Constrained decode.  state: what a step reads and writes per row; ahead (or null): the closure look-ahead.
+// Constrained decode.  state: what a step reads and writes per row; ahead (or null): the closure look-ahead, or
+// with `exact` the exact one (close_dist unused, null).
 struct ff_constrained_state {
   const int *fin_in, *first_in, *prev_in;
   unsigned* visited; unsigned char* mask_rows;
   int* next_tok; float* logprob;
   int *fin_out, *dead_end, *first_out, *prev_out;
 };
-struct ff_lookahead_io { const unsigned char *close_dist, *cycle_len; int budget; };
+constexpr int FF_EXACT_MAX_S = 2048;   // keys (L + ntok) of a row the exact look-ahead's search takes
+struct ff_lookahead_io { const unsigned char *close_dist, *cycle_len; int budget; int exact; };
 int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,
                                 const ff_lookahead_io* ahead, ff_stream_t stream);
 int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int Fc, int f0,

@@ -14,7 +14,8 @@
 // sequence's constraint mask with the "any live edge" vote and the terminators re-opened on a dead end (ff_loop_write_row), the
 // three-step update of (first, prev) (ff_loop_advance) and the state after column 0 (ff_loop_start).
 //
-// pointer_constrained_kernel: one wavefront per sequence, four per block, as pointer_reduce_kernel.  A finished sequence appends
+// pointer_constrained_form_kernel<FORM> (pointer_constrained_kernel<false> / <true> name its first two forms): one wavefront per
+// sequence, four per block, as pointer_reduce_kernel.  A finished sequence appends
 // token 0 and keeps its state.  Every other one writes the byte row of ITS constraint mask and then masks and reduces its logit
 // row exactly as the greedy launch does with an extra mask (ff_pointer_mask_reduce<true>, ff_device.h): every lane reads back
 // the bytes it wrote itself.  Lane 0 stores token, log-probability (-log sum exp(l - l[token]) over the constrained row), the
@@ -24,6 +25,10 @@
 // pointer_constrained_kernel<true> is the same launch with the closure look-ahead: one byte row per sequence
 // (close_dist[w][first] with the loop open, cycle_len[w] with it closed), one byte load and one compare per edge key in the loop
 // that writes the byte row, in front of the vote.  <false> is what ff_pointer_constrained and ff_decode_constrained launch.
+// pointer_constrained_form_kernel<FF_LOOP_EXACT> is the third form: an unfinished sequence with the loop open first
+// runs one backward breadth-first search from its first edge over the edges it has not used (ff_loop_closure_reach, ff_select.h:
+// a few words per lane, ballots and readlane, no LDS) and masks what cannot reach it within the budget; with the loop closed it
+// is <true>'s cycle_len compare.  Layout and tail are the other forms'.
 //
 // follow_distance_kernel: one wavefront per (wireframe, source edge b), four per block: a breadth-first search FORWARD from b
 // over the bit rows, which needs no transposed table.  Lane k holds words k, k + 64, ... of the reached, frontier and next sets
@@ -53,8 +58,8 @@ struct ConstrainArgs {
   int *fin_out, *first_out, *prev_out, *dead_out;   // [B] out
   int* tok; float* logprob;      // [B] out
   const unsigned char* close_dist;   // <true> only: [wireframes, L, L] bytes, close_dist[w][f][b] = D(b -> f)
-  const unsigned char* cycle_len;    // <true> only: [wireframes, L] bytes, D(b -> b)
-  int budget;                        // <true> only: T - 1 - the position this step selects
+  const unsigned char* cycle_len;    // <true>, exact: [wireframes, L] bytes, D(b -> b)
+  int budget;                        // <true>, exact: T - 1 - the position this step selects
 };
 
 __global__ __launch_bounds__(256) void follow_table_kernel(const float* __restrict__ starts, const float* __restrict__ ends, int N,
@@ -152,8 +157,9 @@ __global__ __launch_bounds__(256) void follow_distance_kernel(const unsigned* __
   if (lane == 0) cycle_len[(size_t)w * L + b] = (unsigned char)cyc;
 }
 
-template <bool AHEAD>
-__global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs a) {
+// One kernel per compile-time form of the rule (FF_LOOP_PLAIN / FF_LOOP_AHEAD / FF_LOOP_EXACT, ff_select.h).
+template <int FORM>
+__global__ __launch_bounds__(256) void pointer_constrained_form_kernel(ConstrainArgs a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -170,7 +176,7 @@ __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs 
       if (pa.kv_len) { const int k = ff_ldw(pa.kv_len + w); kv = k < kv ? k : kv; }
       const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * pa.S : nullptr;
       const FFLoopRule rule{a.follows, a.L, a.fw, a.flags, ntok, a.close_dist, a.cycle_len, a.budget};
-      dead = ff_loop_write_row<AHEAD>(pa, rule, lane, w, kv, mrow, first, prev, a.visited + (size_t)b * a.fw, a.rows + (size_t)b * pa.S) ? 1 : 0;
+      dead = ff_loop_write_row<FORM>(pa, rule, lane, w, kv, mrow, first, prev, a.visited + (size_t)b * a.fw, a.rows + (size_t)b * pa.S) ? 1 : 0;
       float m, b2, lsum;
       ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &tok, &lsum);
       lp = -logf(lsum);
@@ -193,6 +199,10 @@ __global__ __launch_bounds__(256) void pointer_constrained_kernel(ConstrainArgs 
   }
   ff_pointer_count_waves(pa, pa.B, nge);
 }
+
+// The two forms without a search under the names they are launched by: <false> is FF_LOOP_PLAIN, <true> FF_LOOP_AHEAD.
+template <bool AHEAD>
+constexpr auto pointer_constrained_kernel = pointer_constrained_form_kernel<AHEAD ? FF_LOOP_AHEAD : FF_LOOP_PLAIN>;
 
 // ---- engine side: start state and output packing of a constrained decode (ff_engine.hip) -----------------------------------------
 // Start state of one micro-batch of Bc = nw * Fc sequences (compact anchors [f0, f0 + Fc) of every wireframe): the anchor's
@@ -273,7 +283,8 @@ int ff_loop_rule_check(const char* op, const ff_loop_rule_io& r, int S, int term
   return FF_OK;
 }
 
-// The one launch behind ff_pointer_constrained (ahead = null) and ff_pointer_constrained_ahead; `op` words the errors.
+// The one launch behind ff_pointer_constrained (ahead = null), ff_pointer_constrained_ahead and ff_pointer_constrained_exact
+// (ahead->exact); `op` words the errors.
 int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& s,
                                 const ff_lookahead_io* ahead, ff_stream_t stream) {
   const int B = io.rows, S = io.S;
@@ -285,7 +296,14 @@ int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_l
   FF_RETURN_IF(ff_loop_rule_check(op, rule, S, io.term_lo, io.term_hi));
   FF_CHECK_ARG(s.fin_in && s.first_in && s.prev_in && s.visited && s.mask_rows && s.next_tok && s.logprob && s.fin_out && s.dead_end &&
                    s.first_out && s.prev_out, "%s: null pointer", op);
-  if (ahead) {
+  if (ahead && ahead->exact) {
+    FF_CHECK_ARG((rule.flags & FF_CONSTRAIN_CONNECT) && (rule.flags & FF_CONSTRAIN_NO_REPEAT),
+                 "%s: the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT", op);
+    FF_CHECK_ARG(ahead->cycle_len, "%s: cycle_len is required", op);
+    FF_CHECK_ARG(S <= FF_EXACT_MAX_S, "%s: S=%d above %d keys (L + ntok)", op, S, FF_EXACT_MAX_S);
+    FF_CHECK_ARG(ahead->budget >= 0 && ahead->budget <= 254, "%s: budget=%d outside 0..254", op, ahead->budget);
+    a.cycle_len = ahead->cycle_len; a.budget = ahead->budget;
+  } else if (ahead) {
     FF_CHECK_ARG(rule.flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", op);
     FF_CHECK_ARG(ahead->close_dist && ahead->cycle_len, "%s: close_dist and cycle_len are required", op);
     FF_CHECK_ARG(ahead->budget >= 0 && ahead->budget <= 254, "%s: budget=%d outside 0..254", op, ahead->budget);
@@ -298,10 +316,12 @@ int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_l
   a.tok = s.next_tok; a.logprob = s.logprob;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 4.0, st);
-  if (ahead)
+  if (ahead && !ahead->exact)
     hipLaunchKernelGGL(pointer_constrained_kernel<true>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
-  else
+  else if (!ahead)
     hipLaunchKernelGGL(pointer_constrained_kernel<false>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(pointer_constrained_form_kernel<FF_LOOP_EXACT>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
@@ -314,7 +334,7 @@ extern "C" int ff_pointer_constrained_ahead(float* logits, int ldlogits, int S, 
                                             float* next_rows, int ldnext, float* next_stats, int* count_ge,
                                             const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
                                             ff_stream_t stream) {
-  const ff_lookahead_io ahead{close_dist, cycle_len, budget};
+  const ff_lookahead_io ahead{close_dist, cycle_len, budget, 0};
   return ff_pointer_constrained_sync(
       "ff_pointer_constrained_ahead",
       ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, term_lo, term_hi, ntok, memory, E, next_rows, ldnext, next_stats,
@@ -322,6 +342,23 @@ extern "C" int ff_pointer_constrained_ahead(float* logits, int ldlogits, int S, 
       ff_loop_rule_io{follows, L, flags, ntok},
       ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
       &ahead, stream);
+}
+
+extern "C" int ff_pointer_constrained_exact(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                            int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int term_lo,
+                                            int term_hi, const int* fin_in, const int* first_in, const int* prev_in,
+                                            unsigned* visited, unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out,
+                                            int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
+                                            float* next_rows, int ldnext, float* next_stats, int* count_ge,
+                                            const unsigned char* cycle_len, int budget, ff_stream_t stream) {
+  const ff_lookahead_io exact{nullptr, cycle_len, budget, 1};
+  return ff_pointer_constrained_sync(
+      "ff_pointer_constrained_exact",
+      ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, term_lo, term_hi, ntok, memory, E, next_rows, ldnext, next_stats,
+                 count_ge, nullptr, nullptr},
+      ff_loop_rule_io{follows, L, flags, ntok},
+      ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
+      &exact, stream);
 }
 
 extern "C" int ff_follow_distance(const unsigned* follows, int N, int L, const int* num_input, int hmax, unsigned char* close_dist,

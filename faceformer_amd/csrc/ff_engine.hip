@@ -41,6 +41,8 @@
 //   constrain with look-ahead (ff_decode_constrained_ahead): constrain's plan, workspace, start state and packing;
 //     only the selection launch differs -- ff_pointer_constrained_ahead with budget = T - 1 - position and the two distance
 //     tables, operands offset per chunk as `follows` is.
+//   constrain with exact look-ahead (ff_decode_constrained_exact): the same again with
+//     ff_pointer_constrained_exact as the selection launch: budget = T - 1 - position and cycle_len as the one operand table.
 //   constrained beam (ff_decode_constrained_beam): the beam decode's plan, records and reorder with
 //     ff_beam_constrained_select as the selection; also the cumulative dead flag per step, the rule's state in two halves that
 //     the steps read and write alternately, and the byte mask per sequence.
@@ -354,7 +356,7 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
@@ -362,8 +364,10 @@ struct Mode {
   const ff_forced_params* forced() const { return static_cast<const ff_forced_params*>(prm); }
   const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }
   const ff_constrain_ahead_params* ahead() const { return static_cast<const ff_constrain_ahead_params*>(prm); }
-  // (CONSTRAIN and CONSTRAIN_AHEAD: the four parameters the two share)
+  const ff_constrain_exact_params* exact() const { return static_cast<const ff_constrain_exact_params*>(prm); }
+  // (CONSTRAIN, CONSTRAIN_AHEAD and CONSTRAIN_EXACT: the four parameters the three share)
   ff_constrain_params con() const {
+    if (kind == CONSTRAIN_EXACT) return ff_constrain_params{exact()->flags, exact()->follows, exact()->logprob, exact()->dead_end};
     if (kind != CONSTRAIN_AHEAD) return *static_cast<const ff_constrain_params*>(prm);
     return ff_constrain_params{ahead()->flags, ahead()->follows, ahead()->logprob, ahead()->dead_end};
   }
@@ -510,6 +514,7 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
       b.row_id = bp.take<int>(Btot);
       break;
     case Mode::CONSTRAIN:
+    case Mode::CONSTRAIN_EXACT:
     case Mode::CONSTRAIN_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
       b.score = bp.take<float>(TB);
       b.finished = bp.take<int>(TB);
@@ -1071,6 +1076,7 @@ struct DecodeRun {
         return ff_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F, ni, pad_tok, p->term_lo, p->term_hi, st);
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
+      case Mode::CONSTRAIN_EXACT:
       case Mode::CONSTRAIN_BEAM: {   // (constrained beam: half 0 of the ping-pong state, step 0 reads it)
         const Rule r = rule_of(c);
         int *dead = buf.dead + c.b0, *first = buf.first + c.b0, *prev = buf.prev + c.b0;
@@ -1174,6 +1180,7 @@ struct DecodeRun {
                                       sp->top_k, sp->top_p, tok_out, buf.score + out, buf.finished + out, st);
       }
       case Mode::CONSTRAIN:
+      case Mode::CONSTRAIN_EXACT:
       case Mode::CONSTRAIN_AHEAD: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
         const Rule r = rule_of(c);
         const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
@@ -1181,8 +1188,12 @@ struct DecodeRun {
                                       buf.first + out, buf.prev + out};
         const ff_loop_rule_io rio{r.follows, r.L, r.flags, m->num_token};
         if (mode.kind == Mode::CONSTRAIN) return ff_pointer_constrained_sync("ff_pointer_constrained", sio, rio, cs, nullptr, st);
-        // the look-ahead: this step selects position t, so a loop has T - 1 - t further positions to close in
-        const ff_lookahead_io ahead{mode.ahead()->close_dist + (size_t)c.w0 * r.L * r.L, mode.ahead()->cycle_len + (size_t)c.w0 * r.L, T - 1 - t};
+        // the look-aheads: this step selects position t, so a loop has T - 1 - t further positions to close in
+        if (mode.kind == Mode::CONSTRAIN_EXACT) {
+          const ff_lookahead_io exact{nullptr, mode.exact()->cycle_len + (size_t)c.w0 * r.L, T - 1 - t, 1};
+          return ff_pointer_constrained_sync("ff_pointer_constrained_exact", sio, rio, cs, &exact, st);
+        }
+        const ff_lookahead_io ahead{mode.ahead()->close_dist + (size_t)c.w0 * r.L * r.L, mode.ahead()->cycle_len + (size_t)c.w0 * r.L, T - 1 - t, 0};
         return ff_pointer_constrained_sync("ff_pointer_constrained_ahead", sio, rio, cs, &ahead, st);
       }
       case Mode::FORCED:   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
@@ -1387,6 +1398,7 @@ struct DecodeRun {
                                   io.seq_of_row, main_st);
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
+      case Mode::CONSTRAIN_EXACT:
         return ff_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
                                      c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con().logprob, mode.con().dead_end, io.seq_of_row, main_st);
       default: break;   // (forced: forced_epilogue packs all rows at once)
@@ -1681,6 +1693,33 @@ extern "C" int ff_decode_constrained_ahead(const ff_model* m, const ff_decode_pa
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::CONSTRAIN_AHEAD, 1, ahead));
+}
+
+extern "C" size_t ff_decode_constrained_exact_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_EXACT, 1));
+}
+
+extern "C" int ff_decode_constrained_exact(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                           const unsigned char* mask, const int* kv_len, const int* num_input,
+                                           const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                                           int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                                           float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                                           size_t workspace_bytes, const ff_constrain_exact_params* exact, ff_stream_t stream) {
+  const char* name = "ff_decode_constrained_exact";
+  FF_CHECK_ARG(m && p && exact, "%s: null model, params or exact look-ahead params", name);
+  FF_RETURN_IF(check_opt_in(name, "the constrained decode with exact look-ahead is", p, extra_mask));
+  FF_RETURN_IF(check_loop_rule(name, exact->flags, exact->follows, m, p));
+  FF_CHECK_ARG((exact->flags & FF_CONSTRAIN_CONNECT) && (exact->flags & FF_CONSTRAIN_NO_REPEAT),
+               "%s: the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT", name);
+  FF_CHECK_ARG(exact->cycle_len, "%s: cycle_len is required", name);
+  FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the table's byte)", name, p->T);
+  FF_CHECK_ARG(p->L + m->num_token <= FF_EXACT_MAX_S, "%s: L=%d above %d (L + num_token keys at most %d)", name, p->L,
+               FF_EXACT_MAX_S - m->num_token, FF_EXACT_MAX_S);
+  FF_RETURN_IF(check_opt_in_outputs(name, p, "logprob and dead_end", exact->logprob && exact->dead_end, trace_best, trace_second,
+                                    pointer_out));
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_EXACT, 1, exact));
 }
 
 extern "C" size_t ff_decode_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,

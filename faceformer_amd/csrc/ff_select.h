@@ -92,20 +92,86 @@ struct FFLoopRule {
   const unsigned* follows;           // [wireframes, L, fw] bits or null: bit b of row a = edge b starts where edge a ends
   int L, fw, flags, ntok;
   const unsigned char* close_dist;   // look-ahead only: [wireframes, L, L] bytes, close_dist[w][f][b] = D(b -> f)
-  const unsigned char* cycle_len;    // look-ahead only: [wireframes, L] bytes, D(b -> b)
-  int budget;                        // look-ahead only
+  const unsigned char* cycle_len;    // look-ahead, exact: [wireframes, L] bytes, D(b -> b)
+  int budget;                        // look-ahead, exact
 };
 
 // first / prev as stored -> an edge of the wireframe or "none" (the entries cannot see device data: anything else is "none")
 __device__ __forceinline__ int ff_loop_edge(int e, int L) { return (e < 0 || e >= L) ? -1 : e; }
 
+// ---- exact closure look-ahead (include/faceformer_hip.h states the rule) ----------------------------------------------
+enum { FF_LOOP_PLAIN = 0, FF_LOOP_AHEAD = 1, FF_LOOP_EXACT = 2 };   // the compile-time forms of ff_loop_write_row
+
+// Which edges b reach the open loop's first edge within r.budget hops through unused edges: D_V(b -> first) <= budget, where a
+// path's inner nodes are `avail` (an edge key that is not padded and not visited) and b itself is any edge.  One backward
+// breadth-first search from `first` per sequence, pull-style over the FORWARD table: level 1 = {x: follows[x][first]}, level
+// h + 1 = {x not reached: follows[x] meets the avail nodes of level h}.  Lane (ntok + x) mod 64 owns node x, as in the byte-row
+// loop, so the bit this returns (bit c: key c * 64 + lane reached) is in the lane that writes the byte.  A level's frontier is
+// the ballots of its new avail nodes, re-cut into the table's words: lane j keeps word j (edges 32j .. 32j + 31) and every
+// lane reads it with a wave-uniform readlane; words of an empty frontier part are skipped.  No LDS, no barrier.
+// Ends at the first of: an empty frontier, `budget` levels, every unvisited candidate of follows[prev] reached -- the padded
+// candidates included: their byte is the rule's as well (D_V is defined for any b), so one that cannot be reached keeps the
+// search going to the budget or to an empty frontier; that costs time only.
+// Needs S <= FF_EXACT_MAX_S (ff_common.h: bit c of a lane's words is its key c * 64 + lane, c < 32; so fw <= 64), first and prev edges of the wireframe, CONNECT and NO_REPEAT (the entries check).
+__device__ __forceinline__ unsigned ff_loop_closure_reach(const PointerArgs& pa, const FFLoopRule& r, int lane, int w, int kv,
+                                                          const unsigned char* mrow, int first, int prev, const unsigned* vrow) {
+  const int S = pa.S, ntok = r.ntok, fw = r.fw;
+  if (r.budget < 1) return 0u;
+  const unsigned* rows = r.follows + (size_t)w * r.L * fw;
+  const unsigned* prow = rows + (size_t)prev * fw;
+  unsigned avail = 0u, want = 0u, reach = 0u;
+  for (int s = lane; s < S; s += 64) {   // level 1, and what the levels need of every key
+    if (s < ntok) continue;
+    const int e = s - ntok;
+    const unsigned bit = 1u << (e & 31), cbit = 1u << (s >> 6);
+    const bool vis = (vrow[e >> 5] & bit) != 0u;
+    bool pad = s >= kv;
+    if (!pad && mrow) pad = ff_ldw(mrow + s) != 0;
+    if (!vis && !pad) avail |= cbit;
+    if (!vis && (prow[e >> 5] & bit) != 0u) want |= cbit;
+    if ((rows[(size_t)e * fw + (first >> 5)] >> (first & 31)) & 1u) reach |= cbit;
+  }
+  unsigned fresh = reach & avail;   // the nodes of the last level that a path may pass through
+  const int nch = (S + 63) >> 6, a0 = lane * 32 + ntok;   // a0: the key of bit 0 of this lane's frontier word
+  for (int h = 1; h < r.budget && __ballot((want & ~reach) != 0u) != 0ull; ++h) {
+    unsigned front = 0u;
+    bool any = false;
+    for (int c = 0; c < nch; ++c) {
+      const unsigned long long bal = __ballot(((fresh >> c) & 1u) != 0u);
+      if (bal == 0ull) continue;   // (wave-uniform)
+      any = true;
+      const int d = a0 - c * 64;   // bit i of the word is bit d + i of this chunk's ballot
+      if (d >= 0 && d < 64) front |= (unsigned)(bal >> d);
+      if (d < 0 && d > -32) front |= (unsigned)bal << -d;
+    }
+    if (!any) break;
+    fresh = 0u;
+    for (int c = 0; c < nch; ++c) {
+      const int s = c * 64 + lane;
+      const bool todo = s >= ntok && s < S && ((reach >> c) & 1u) == 0u;
+      if (__ballot(todo) == 0ull) continue;   // (wave-uniform)
+      const unsigned* xr = rows + (size_t)(todo ? s - ntok : 0) * fw;
+      unsigned hit = 0u;
+      for (int j = 0; j < fw; ++j) {
+        const unsigned fj = (unsigned)__builtin_amdgcn_readlane((int)front, j);
+        if (fj == 0u) continue;   // (wave-uniform)
+        if (todo) hit |= xr[j] & fj;
+      }
+      if (hit != 0u) { reach |= 1u << c; fresh |= avail & (1u << c); }
+    }
+  }
+  return reach;
+}
+
 // The byte row xrow[0..S) of one sequence's constraint mask (1 = masked) from its (first, prev) and visited words vrow, for
 // wireframe w with kv keys and padding-mask row mrow: one vote on "any live edge" (it sees padding, kv and visited), and on a
 // dead end of an open loop the terminators re-opened; returns the dead-end bit (wave-uniform).  Every loop keeps lane = key
 // mod 64: ff_pointer_mask_reduce reads back only bytes its own lane wrote, so there is no barrier.
-// AHEAD: the closure look-ahead -- the distance of every edge to the loop's first edge while it is open, else
-// the edge's own shortest cycle, against the budget; compiled out for <false>.
-template <bool AHEAD>
+// FORM (a compile-time form of the one rule): FF_LOOP_PLAIN; FF_LOOP_AHEAD, the closure look-ahead -- the
+// distance of every edge to the loop's first edge while it is open, else the edge's own shortest cycle, against the budget;
+// FF_LOOP_EXACT, the exact closure look-ahead -- with the loop open the search above in place of the distance
+// row, with it closed the look-ahead's cycle_len.  What a form does not use is compiled out: <false> and <true> are PLAIN and AHEAD.
+template <int FORM>
 __device__ __forceinline__ bool ff_loop_write_row(const PointerArgs& pa, const FFLoopRule& r, int lane, int w, int kv,
                                                   const unsigned char* mrow, int first, int prev, const unsigned* vrow,
                                                   unsigned char* xrow) {
@@ -114,7 +180,10 @@ __device__ __forceinline__ bool ff_loop_write_row(const PointerArgs& pa, const F
   const bool open = connect && first >= 0 && prev >= 0;
   const unsigned* frow = open ? r.follows + ((size_t)w * r.L + prev) * r.fw : nullptr;
   const unsigned char* drow = nullptr;
-  if (AHEAD && connect) drow = open ? r.close_dist + ((size_t)w * r.L + first) * r.L : r.cycle_len + (size_t)w * r.L;
+  if (FORM == FF_LOOP_AHEAD && connect) drow = open ? r.close_dist + ((size_t)w * r.L + first) * r.L : r.cycle_len + (size_t)w * r.L;
+  if (FORM == FF_LOOP_EXACT && connect && !open) drow = r.cycle_len + (size_t)w * r.L;
+  unsigned reach = 0u;
+  if (FORM == FF_LOOP_EXACT && open) reach = ff_loop_closure_reach(pa, r, lane, w, kv, mrow, first, prev, vrow);
   bool live_edge = false;
   for (int s = lane; s < S; s += 64) {
     bool masked;
@@ -124,7 +193,8 @@ __device__ __forceinline__ bool ff_loop_write_row(const PointerArgs& pa, const F
       const int e = s - ntok;
       const unsigned bit = 1u << (e & 31);
       masked = (norep && (vrow[e >> 5] & bit) != 0) || (open && (frow[e >> 5] & bit) == 0);
-      if (AHEAD && drow) masked = masked || (int)drow[e] > r.budget;
+      if (FORM != FF_LOOP_PLAIN && drow) masked = masked || (int)drow[e] > r.budget;
+      if (FORM == FF_LOOP_EXACT && open) masked = masked || ((reach >> (s >> 6)) & 1u) == 0u;
       bool pad = s >= kv;
       if (!pad && mrow) pad = ff_ldw(mrow + s) != 0;
       live_edge = live_edge || (!masked && !pad);

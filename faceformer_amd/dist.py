@@ -211,6 +211,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
     from .models import SurfaceFormer_Parallel
     if getattr(model, "constrain_lookahead", False):     # (an option of constrain, which is not taken here either)
         raise ValueError("decode_sharded does not implement constrain_lookahead (%s)" % _modes.SWITCH["constrain"].sharded)
+    if getattr(model, "constrain_exact", False):
+        raise ValueError("decode_sharded does not implement constrain_exact (%s)" % _modes.SWITCH["constrain"].sharded)
     for mode in reversed(_modes.MODES):
         for sw in mode.switches:
             if sw.sharded and sw.on(model):

@@ -24,7 +24,7 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
-           "parse_parallel_samples_scored", "follow_table", "pack_follow_bits", "follow_distance"]
+           "parse_parallel_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance"]
 
 
 def _tok(token, name, default):
@@ -418,6 +418,45 @@ def follow_distance(table, hmax=254, num_input=None):
     dist = dist.reshape(t.shape)
     close = np.ascontiguousarray(np.swapaxes(dist, -1, -2))
     return close, np.ascontiguousarray(np.diagonal(dist, axis1=-2, axis2=-1))
+
+
+def closure_distance(table, visited, first, hmax=254, num_input=None, pad=None):
+    """The closing distances of one sequence with an open loop, the numpy restatement of the search in
+    ff_pointer_constrained_exact.  table: bool [L, L], table[a, b] = edge b starts where edge a ends; visited: bool [L] or the
+    indices of the edges the row holds; first: the loop's first edge; num_input: only edges below it are available; pad: bool [L],
+    edges whose key is padded.  avail(x) = x < num_input, not padded, not visited.  D_V(b -> first) is the least h >= 1 with
+    b = x_0, ..., x_h = first, table[x_i, x_i+1] for every i and avail(x_i) for 1 <= i < h (b itself may be any edge; first is the
+    target only).  Returns uint8 [L]: D_V(b -> first), 255 for unreachable or more than hmax hops (1 <= hmax <= 254)."""
+    if isinstance(hmax, bool) or not isinstance(hmax, (int, np.integer)) or not 1 <= hmax <= 254:
+        raise ValueError("hmax=%r: must be in 1..254" % (hmax,))
+    t = np.asarray(table, dtype=bool)
+    if t.ndim != 2 or t.shape[0] != t.shape[1]:
+        raise ValueError("table must be [L, L]")
+    L = t.shape[0]
+    v = np.asarray(visited)
+    if v.dtype != np.bool_:
+        idx, v = v.astype(np.int64).reshape(-1), np.zeros(L, dtype=bool)
+        v[idx] = True
+    if v.shape != (L,):
+        raise ValueError("visited must be bool [L] or a list of edges")
+    if not 0 <= int(first) < L:
+        raise ValueError("first=%r: must be an edge of the table" % (first,))
+    avail = ~v
+    if num_input is not None:
+        avail &= np.arange(L) < int(num_input)
+    if pad is not None:
+        avail &= ~np.asarray(pad, dtype=bool).reshape(L)
+    dist = np.full(L, 255, dtype=np.uint8)
+    new = t[:, int(first)].copy()                   # level 1: every edge the first edge follows
+    reached = np.zeros(L, dtype=bool)
+    for h in range(1, int(hmax) + 1):
+        new &= ~reached
+        if not new.any():
+            break
+        dist[new] = h
+        reached |= new
+        new = t[:, new & avail].any(axis=1)         # the edges with a successor among the available ones of this level
+    return dist
 
 
 def is_face_enclosed(edges, face_indices, tol):

@@ -374,7 +374,7 @@ class PathEngine:
                trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
-               constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None):
+               constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -417,15 +417,23 @@ class PathEngine:
         constrain_lookahead=True (only with constrain="loops", not with constrain_beams, T <= 256; ff_decode_constrained_ahead,
         DESIGN.md 22): the constrained decode also masks every edge from which the loop cannot close within T -- close_dist
         [N, L, L] / cycle_len [N, L] uint8 on the device (ops.follow_distance of follow_table), both required.  Outputs are
-        constrain's; `dead_end` then also means "cannot close within T".  With both tables zero it equals the "loops" decode."""
+        constrain's; `dead_end` then also means "cannot close within T".  With both tables zero it equals the "loops" decode.
+
+        constrain_exact=True (only with constrain="loops", not with constrain_lookahead -- it contains it -- nor constrain_beams,
+        T <= 256, at most 2048 keys; ff_decode_constrained_exact): while a loop is open the constrained decode also
+        masks every edge from which it cannot close within T through edges the row has not used (one search per open row and
+        step); with it closed, every edge with cycle_len > the positions left.  cycle_len [N, L] uint8 on the device
+        (ops.follow_distance) is required, close_dist is not read.  Outputs are constrain's; a dead end is then only possible
+        right after the position that opened the loop."""
         W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
         CB = _modes.constrain_beams_value(constrain_beams, CF)
         LA = _modes.constrain_lookahead_value(constrain_lookahead, CF, CB)
-        mode, value = _modes.of_options(logprob, CB, LA, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
+        EX = _modes.constrain_exact_value(constrain_exact, CF, CB, LA)
+        mode, value = _modes.of_options(logprob, CB, LA, EX, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
         G = value if mode.per_anchor else 1       # sequences per anchor
         o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
                  logprob=logprob, beam_width=W, num_samples=R, constrain=CF, constrain_beams=CB, temperature=temperature, top_k=top_k, top_p=top_p,
-                 uniforms=uniforms, follow_table=follow_table, constrain_lookahead=LA, close_dist=close_dist, cycle_len=cycle_len, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
+                 uniforms=uniforms, follow_table=follow_table, constrain_lookahead=LA, constrain_exact=EX, close_dist=close_dist, cycle_len=cycle_len, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
                  N=memory.shape[0], S=memory.shape[1], F=F, T=T)
         if value is not None:    # (retire, an option of the greedy record, is checked behind the operands)
             _modes.check_options(mode, variant, o, term_range)

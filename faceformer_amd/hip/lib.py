@@ -168,6 +168,10 @@ class ConstrainAheadParams(C.Structure):
                 ("dead_end", fptr)]
 
 
+class ConstrainExactParams(C.Structure):
+    _fields_ = [("flags", C.c_int), ("follows", fptr), ("cycle_len", fptr), ("logprob", fptr), ("dead_end", fptr)]
+
+
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
 
@@ -295,6 +299,14 @@ SIGNATURES = {
                                               C.POINTER(C.c_int), fptr,
                                               fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                               C.c_size_t, C.POINTER(ConstrainAheadParams), fptr]),
+    "ff_pointer_constrained_exact": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                               fptr, C.c_int, fptr, C.c_int, fptr, fptr, fptr, C.c_int, fptr]),
+    "ff_decode_constrained_exact_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int)]),
+    "ff_decode_constrained_exact": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                              C.POINTER(C.c_int), fptr,
+                                              fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                                              C.c_size_t, C.POINTER(ConstrainExactParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 
@@ -326,7 +338,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain* and *_ahead / ff_follow_distance ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance and *_exact ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

@@ -8,7 +8,7 @@ import ctypes as C
 import torch
 
 from . import lib as _L
-from .ops import _dev, _p
+from .ops import EXACT_MAX_KEYS, _dev, _p      # (EXACT_MAX_KEYS: L + num_token the exact look-ahead's search takes)
 
 SAMPLE_MAX = 64
 CONSTRAIN_MODES = {"no_repeat": _L.FF_CONSTRAIN_NO_REPEAT, "loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT}
@@ -150,6 +150,43 @@ def _constrain_ahead_operand(eng, o):
             raise ValueError("%s must be a uint8 tensor of shape [%s]" % (name, ", ".join(str(v) for v in shape)))
 
 
+def constrain_exact_value(exact, flags, constrain_beams=0, constrain_lookahead=False):
+    """Whether the exact closure look-ahead is on (`constrain_exact`): only with constrain='loops' (`flags`:
+    constrain_flags of it -- it needs CONNECT for the loop and NO_REPEAT for `visited`), not with constrain_lookahead, which it
+    contains, and not with constrain_beams."""
+    if not exact:
+        return False
+    if flags is None:
+        raise ValueError("constrain_exact needs constrain='loops': it is the exact closure look-ahead of the loop-constrained decode")
+    if flags != CONSTRAIN_MODES["loops"]:
+        raise ValueError("constrain_exact needs constrain='loops' (FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT): without CONNECT "
+                         "no loop is tracked, without NO_REPEAT there is no visited set to be exact about")
+    if constrain_lookahead:
+        raise ValueError("constrain_exact excludes constrain_lookahead: it contains it (every edge the look-ahead masks is masked)")
+    if constrain_beams:
+        raise ValueError("constrain_exact excludes constrain_beams: the beam search over the constrained keys has no look-ahead")
+    return True
+
+
+def _constrain_exact_values(o):
+    _constrain_values(o)
+    if o["T"] > 256:
+        raise ValueError("constrain_exact takes T <= 256 (got %d): the budget T - 2 must fit the table's byte" % o["T"])
+    if o["cycle_len"] is None:
+        raise ValueError("constrain_exact needs cycle_len (ops.follow_distance)")
+
+
+def _constrain_exact_operand(eng, o):
+    _constrain_operand(eng, o)
+    L = o["S"] - eng.num_token
+    if o["S"] > EXACT_MAX_KEYS:
+        raise ValueError("constrain_exact takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
+                         % (EXACT_MAX_KEYS - eng.num_token, L, EXACT_MAX_KEYS))
+    t = o["cycle_len"]
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != (o["N"], L):
+        raise ValueError("cycle_len must be a uint8 tensor of shape [%d, %d]" % (o["N"], L))
+
+
 def _constrain_operand(eng, o):
     L = o["S"] - eng.num_token
     shape = (o["N"], L, (L + 31) // 32)
@@ -249,6 +286,19 @@ CONSTRAIN_AHEAD = CONSTRAIN._replace(
                                                                   _p(o["cycle_len"]), *ptrs)),),
     prepare=lambda *a: _constrain_ahead_prepare(*a))
 
+def _constrain_exact_prepare(m, CF, inputs, dev, T, N, F, ni, order):
+    kw = CONSTRAIN.prepare(m, CF, inputs, dev, T, N, F, ni, order)
+    return dict(kw, constrain_exact=True, cycle_len=m._cycle_len(inputs, dev, T, ni, order, kw["follow_table"]))
+
+
+# constrain='loops' with its option constrain_exact: the same decode with the exact closure look-ahead -- a search
+# over the unused edges per open row -- in the selection launch.  Outside MODES, as CONSTRAIN_AHEAD is; cycle_len is an operand.
+CONSTRAIN_EXACT = CONSTRAIN._replace(
+    subject="constrain_exact", entry="ff_decode_constrained_exact", values=_constrain_exact_values, operand=_constrain_exact_operand,
+    own=(("follow_table", _I32), ("cycle_len", torch.uint8)),
+    tail=lambda o, ptrs, traced: (C.byref(_L.ConstrainExactParams(o["constrain"], _p(o["follow_table"]), _p(o["cycle_len"]), *ptrs)),),
+    prepare=lambda *a: _constrain_exact_prepare(*a))
+
 SAMPLE = Mode(
     subject="num_samples", excludes=_COMMON + ("beam_width",), entry="ff_decode_sample", per_anchor=True, values=_sample_values,
     values_first=True, operand=_sample_operand, own=(("uniforms", _F32),),
@@ -287,10 +337,11 @@ MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 
 
-def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, **values):
+def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, constrain_exact=False, **values):
     """(record, value) of the first of MODES whose option is set in `values` (constrain: the flag bits or None; num_samples;
     beam_width); else the greedy record (its logprob form with `logprob`) and None.  constrain with constrain_beams = W > 0:
-    the CONSTRAIN_BEAM record and W; with constrain_lookahead: the CONSTRAIN_AHEAD record and the flag bits."""
+    the CONSTRAIN_BEAM record and W; with constrain_lookahead: the CONSTRAIN_AHEAD record and the flag bits; with constrain_exact:
+    the CONSTRAIN_EXACT record and the flag bits."""
     for mode in MODES[:-1]:
         v = values[mode.subject]
         if v is not None and (v or mode is CONSTRAIN):
@@ -298,5 +349,7 @@ def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, **va
                 return CONSTRAIN_BEAM, constrain_beams
             if mode is CONSTRAIN and constrain_lookahead:
                 return CONSTRAIN_AHEAD, v
+            if mode is CONSTRAIN and constrain_exact:
+                return CONSTRAIN_EXACT, v
             return mode, v
     return (GREEDY_LOGPROB if logprob else GREEDY), None

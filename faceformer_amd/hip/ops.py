@@ -582,8 +582,8 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
 
 def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
                       want_rows, want_stats, counter, ahead):
-    """pointer_constrained (ahead None) and pointer_constrained_ahead (ahead = (close_dist, cycle_len, budget)): the checks, the
-    outputs and the launch the two share."""
+    """pointer_constrained (ahead None), pointer_constrained_ahead (ahead = ("ahead", close_dist, cycle_len, budget)) and
+    pointer_constrained_exact (ahead = ("exact", cycle_len, budget)): the checks, the outputs and the launch the three share."""
     _dev(logits, "logits")
     out = {}
     B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
@@ -621,8 +621,21 @@ def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, m
     vis = visited if fw else one
     fol = one if (follows is not None and not (L and fw)) else follows
     entry, tail = "ff_pointer_constrained", ()
-    if ahead is not None:
-        close_dist, cycle_len, budget = ahead
+    if ahead is not None and ahead[0] == "exact":
+        _, cycle_len, budget = ahead
+        if flags != _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT:
+            raise ValueError("the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT")
+        if S > EXACT_MAX_KEYS:
+            raise ValueError("pointer_constrained_exact takes at most %d keys (L + ntok; got %d)" % (EXACT_MAX_KEYS, S))
+        _dev(cycle_len, "cycle_len", torch.uint8)
+        if cycle_len.dim() != 2 or not cycle_len.is_contiguous() or cycle_len.size(0) < nw or cycle_len.size(1) != L:
+            raise ValueError("cycle_len must be a contiguous uint8 [>= %d, %d] tensor" % (nw, L))
+        if not 0 <= int(budget) <= 254:
+            raise ValueError("budget=%r: must be in 0..254" % (budget,))
+        byte = torch.zeros(1, device=dev, dtype=torch.uint8)      # (L = 0: nothing of the table is read)
+        entry, tail = "ff_pointer_constrained_exact", (_p(cycle_len if L else byte), int(budget))
+    elif ahead is not None:
+        _, close_dist, cycle_len, budget = ahead
         if not flags & _L.FF_CONSTRAIN_CONNECT:
             raise ValueError("the look-ahead needs FF_CONSTRAIN_CONNECT")
         for x, name, shape in ((close_dist, "close_dist", (L, L)), (cycle_len, "cycle_len", (L,))):
@@ -649,7 +662,22 @@ def pointer_constrained_ahead(logits, fin, first, prev, visited, flags, ntok, fo
     [W, L, L] / cycle_len [W, L] uint8 (ops.follow_distance), budget in 0..254: the positions left behind the one this step
     selects.  Operands and results are pointer_constrained's; with both tables zero the results are too."""
     return _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
-                             want_rows, want_stats, counter, (close_dist, cycle_len, budget))
+                             want_rows, want_stats, counter, ("ahead", close_dist, cycle_len, budget))
+
+
+EXACT_MAX_KEYS = 2048      # (ff_pointer_constrained_exact: L + ntok)
+
+
+@_on_tensor_device
+def pointer_constrained_exact(logits, fin, first, prev, visited, flags, ntok, follows, cycle_len, budget, memory=None, mask=None,
+                              kv_len=None, seqs_per_group=1, term_range=(1, 4), want_rows=False, want_stats=False, counter=None):
+    """pointer_constrained with the exact closure look-ahead (ff_pointer_constrained_exact): with the loop open an
+    edge b is also masked when no path of at most `budget` hops leads from b to the loop's first edge through edges that are
+    neither visited nor padded (faces.closure_distance is the numpy restatement); with it closed when cycle_len[w][b] > budget.
+    flags must be NO_REPEAT | CONNECT; cycle_len [W, L] uint8 (ops.follow_distance), budget in 0..254; at most 2048 keys.
+    Operands and results are pointer_constrained's."""
+    return _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
+                             want_rows, want_stats, counter, ("exact", cycle_len, budget))
 
 
 FOLLOW_DISTANCE_MAX_L = 8192

@@ -78,6 +78,9 @@ class SurfaceFormerBase(nn.Module):
                                        # 0 = the constrained greedy decode; only with constrain
         self.constrain_lookahead = False   # ... with "loops": also mask every edge from which the loop cannot close within
                                        # max_face_length; inputs["close_dist"] / ["cycle_len"] override the built tables
+        self.constrain_exact = False   # ... with "loops": the exact closure look-ahead -- while a loop is open, also mask
+                                       # every edge from which it cannot close within max_face_length through edges the row has
+                                       # not used; contains constrain_lookahead; inputs["cycle_len"] overrides the built table
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
         self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
         self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
@@ -283,18 +286,24 @@ class SurfaceFormerBase(nn.Module):
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
+        exact = getattr(self, "constrain_exact", False)         # (and this)
         if not parallel:
             if CB:
                 raise ValueError("constrain_beams is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
             if look:
                 raise ValueError("constrain_lookahead is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
+            if exact:
+                raise ValueError("constrain_exact is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
             for mode in reversed(_modes.MODES):
                 for sw in mode.switches:
                     if sw.seq2seq and sw.on(self):
                         raise ValueError("%s is a SurfaceFormer_Parallel option (%s)" % (sw.attr, sw.seq2seq))
             return (_modes.GREEDY_LOGPROB if getattr(self, "return_logprob", False) else _modes.GREEDY), None
         LA = _modes.constrain_lookahead_value(look, CF, CB)
-        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, LA, constrain=CF,
+        EX = _modes.constrain_exact_value(exact, CF, CB, LA)
+        if EX and not self.engine_supported():
+            raise ValueError("constrain_exact needs the native engine: this model's constructor arguments take the sub-module loop")
+        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, LA, EX, constrain=CF,
                                         num_samples=int(getattr(self, "num_samples", 0) or 0), beam_width=int(getattr(self, "beam_width", 0) or 0))
         if value is not None:
             attr = mode.switches[0].attr
@@ -315,6 +324,17 @@ class SurfaceFormerBase(nn.Module):
                 _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, follow_table=True, close_dist=True, cycle_len=True,
                                                                T=self.max_face_length),
                                      (int(self.token.face_type_offset), int(self.token.len)))
+            if mode is _modes.CONSTRAIN_EXACT:      # (the table is made behind the encoder: only T is checked here)
+                _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, follow_table=True, cycle_len=True, T=self.max_face_length),
+                                     (int(self.token.face_type_offset), int(self.token.len)))
+                L = inputs["input"].size(1)
+                if L + self.num_token > _modes.EXACT_MAX_KEYS:
+                    raise ValueError("constrain_exact takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
+                                     % (_modes.EXACT_MAX_KEYS - self.num_token, L, _modes.EXACT_MAX_KEYS))
+                given = inputs.get("cycle_len")
+                shape = tuple(inputs["input"].shape[:2])
+                if given is not None and (torch.as_tensor(given).dtype != torch.uint8 or tuple(torch.as_tensor(given).shape) != shape):
+                    raise ValueError("cycle_len must be uint8 [%d, %d]" % shape)
         return mode, value
 
     def _score(self, inputs, variant, T, F, paths, lengths):

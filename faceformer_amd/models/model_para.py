@@ -57,7 +57,12 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         constrained decode also masks every edge from which the loop cannot close within max_face_length; predict_dead_end then
         also means "cannot close in time".  The two distance tables are built on the device from the follow table
         (ops.follow_distance, hmax = max(T - 2, 1)), or taken from inputs["close_dist"] (uint8 N x L x L) and inputs["cycle_len"]
-        (uint8 N x L), for the batch AS GIVEN.  The published keys are constrain's."""
+        (uint8 N x L), for the batch AS GIVEN.  The published keys are constrain's.
+        constrain_exact = True (default False; only with constrain = "loops", not with constrain_lookahead, which it contains, nor
+        with constrain_beams): while a loop is open the constrained decode also masks every edge from which it
+        cannot close within max_face_length through edges the row has not used, so a row can only dead-end right after the
+        position that opened a loop.  cycle_len is built on the device (ops.follow_distance, hmax = max(T - 2, 1)) or taken from
+        inputs["cycle_len"] (uint8 N x L) for the batch AS GIVEN.  The published keys are constrain's."""
         label = inputs["label"]
         T = self.max_face_length
         mode, value = self._decode_mode(inputs, parallel=True)
@@ -168,6 +173,20 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
                 t = t.index_select(0, torch.tensor(order, device=device))
             out[name] = t.contiguous()
         return out
+
+    def _cycle_len(self, inputs, device, T, num_input, order, bits):
+        """cycle_len [N, L] uint8 of a decode with the exact look-ahead in the DECODE's wireframe order: built on the device from
+        `bits` (the follow table, in that order already) with hmax = max(T - 2, 1), or inputs["cycle_len"] for the batch as
+        given (_decode_mode has checked its shape), permuted like the wireframes when they are decoded sorted by edge count."""
+        from ..hip import ops as _ops
+        given = inputs.get("cycle_len")
+        if given is None:
+            ni = torch.tensor(num_input if order is None else [num_input[i] for i in order], dtype=torch.int32).to(device)
+            return _ops.follow_distance(bits, ni, min(max(T - 2, 1), 254))[1]
+        t = torch.as_tensor(given).to(device)
+        if order is not None:
+            t = t.index_select(0, torch.tensor(order, device=device))
+        return t.contiguous()
 
     def _sample_uniforms(self, inputs, device, T, N, F, R, order):
         """The uniforms [T-1, N*F*R] of a sampled decode in the DECODE's wireframe order: made (or given) for the batch as given,

@@ -1040,6 +1040,66 @@ int ff_decode_constrained_ahead(const ff_model* m, const ff_decode_params* p,
                                 float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                                 void* workspace, size_t workspace_bytes, const ff_constrain_ahead_params* ahead, ff_stream_t stream);
 
+/* ---- exact closure look-ahead for the loop-constrained pointer decode (opt-in, parallel variant; entries added within ABI 105;
+ * DESIGN.md 25).  The look-ahead above ignores visited, so a row can still run into a dead end later.  This form accounts for
+ * visited while a loop is open: one breadth-first search per sequence and step, backward from the loop's first edge over the
+ * edges the row has not used.
+ *
+ * Everything is ff_decode_constrained's under FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT, plus one more mask in front of the
+ * dead-end vote.  The step that selects position p has budget = T - 1 - p, so T <= 256.
+ *   - Loop open (first, prev set).
+ *     - Let avail(x) hold when all three are true: x < L; key ntok + x is not padded (padding-mask byte clear and
+ *       ntok + x < kv_len[w]); x is not in visited.
+ *     - D_V(b->first) is the least h >= 1 with b = x_0, ..., x_h = first, follows[x_i][x_i+1] for every i, and avail(x_i) for
+ *       1 <= i < h.
+ *     - first itself is visited; it is the target only.
+ *     - Edge b is additionally masked when D_V(b->first) > budget.  Unreachable counts as > budget.
+ *   - Loop closed.
+ *     - Edge b is additionally masked when cycle_len[w][b] > budget.  This is the look-ahead's static rule, unchanged.
+ *     - A cycle through b that avoids visited would need one search per candidate.  That is explicitly out of scope.
+ *   - The dead-end vote sees padding, kv_len, visited and this mask.
+ *     - Terminators are re-opened on a dead end.
+ *     - dead_end, argmax with lowest-index ties, logprob under the renormalised row, state update, stop rule, padding anchors
+ *       and FF_DEDUP_PAD_ANCHORS are all the constrained decode's.
+ *   - Guaranteed, and tested.
+ *     - A row's dead_end can only be raised at a position whose previous position opened the current loop.  Position 1 after
+ *       an anchor edge is such a position.
+ *     - Every row without dead_end that reaches a terminator has a closed state.
+ *     - For every row and step, the masked set contains what the look-ahead above would mask, using the same cycle_len and its
+ *       close_dist.  This holds because D_V >= D.
+ *
+ * Limit.  The search keeps one bit per 64-key chunk in a 32-bit word per lane: L + ntok <= 2048 keys (L = 1024 of config E
+ * fits).  Above it the entries return FF_ERR_ARG before any launch.
+ *
+ * ff_pointer_constrained_exact: ff_pointer_constrained's arguments, then cycle_len [wireframes, L] (ff_follow_distance's) and
+ *   budget in 0..254; flags must hold both FF_CONSTRAIN_NO_REPEAT and FF_CONSTRAIN_CONNECT.
+ * ff_decode_constrained_exact: ff_decode_constrained with ff_constrain_exact_params; the step that selects position p runs
+ *   ff_pointer_constrained_exact with budget = T - 1 - p.  Plan, workspace layout, start state and packing are
+ *   ff_decode_constrained's; cycle_len is an operand, not workspace.
+ * FF_ERR_ARG before any launch for everything ff_decode_constrained rejects, CONNECT or NO_REPEAT clear (without NO_REPEAT
+ * there is no visited to be exact about), a NULL table, T > 256 and L + ntok > 2048.
+ * ff_decode_constrained_exact_workspace_bytes equals ff_decode_constrained_workspace_bytes. */
+int ff_pointer_constrained_exact(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                 int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok, int term_lo,
+                                 int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned int* visited,
+                                 unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
+                                 int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
+                                 float* next_stats, int* count_ge, const unsigned char* cycle_len, int budget, ff_stream_t stream);
+typedef struct ff_constrain_exact_params {
+  int flags;
+  const unsigned int* follows;
+  const unsigned char* cycle_len;
+  float* logprob;
+  int* dead_end;
+} ff_constrain_exact_params;
+size_t ff_decode_constrained_exact_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host);
+int ff_decode_constrained_exact(const ff_model* m, const ff_decode_params* p,
+                                const float* memory, const unsigned char* mask, const int* kv_len,
+                                const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                                int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                                float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                                void* workspace, size_t workspace_bytes, const ff_constrain_exact_params* exact, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

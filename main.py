@@ -191,13 +191,14 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
 
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
-                    seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False):
+                    seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
     under temperature / top_k / top_p from the seeded generator (num_samples), the loop-constrained greedy decode
     (constrain "no_repeat" / "loops" with the end-point tolerance constrain_tol), the beam search over its keys
-    with `constrain_beams` beams per anchor, the closure look-ahead of "loops" (constrain_lookahead).
+    with `constrain_beams` beams per anchor, the closure look-ahead of "loops" (constrain_lookahead), its exact form
+    (constrain_exact).
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -219,12 +220,14 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.constrain_beams = int(constrain_beams)
     if constrain_lookahead:
         model.constrain_lookahead = True
+    if constrain_exact:
+        model.constrain_exact = True
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
-             top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False):
+             top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -234,7 +237,17 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     cfg.post_process.enclosedness_tol as the end-point tolerance; constrain_beams = W (1..8, only with constrain, single-rank
     runs only) decodes W constrained beams per anchor and adds pred_beam_faces / pred_beam_face_scores; constrain_lookahead (only
     with constrain "loops", not with constrain_beams, single-rank runs only) also masks the edges from which a loop cannot close
-    in time -- the record keys stay constrain's."""
+    in time -- the record keys stay constrain's; constrain_exact (only with constrain "loops", not with constrain_lookahead or
+    constrain_beams, single-rank runs only) is the exact form of that look-ahead, with the same record keys."""
+    if constrain_exact:
+        if constrain != "loops":
+            raise ValueError("--constrain-exact requires --constrain loops")
+        if constrain_lookahead:
+            raise ValueError("--constrain-exact is not combined with --constrain-lookahead: it contains it")
+        if constrain_beams:
+            raise ValueError("--constrain-exact is not implemented with --constrain-beams")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--constrain-exact is not implemented for multi-rank runs")
     if constrain_lookahead:
         if constrain != "loops":
             raise ValueError("--constrain-lookahead requires --constrain loops")
@@ -259,7 +272,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         model.load_state_dict(sd)
         model = model.eval().to(device)
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
-                    cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead)
+                    cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -365,6 +378,11 @@ def build_parser():
                         help="with --constrain loops: also never an edge from which the loop cannot close before the row runs out "
                              "of positions (DESIGN.md 22); pred_dead_ends then also counts rows that could not close in time; "
                              "single-process runs only, not with --constrain-beams")
+    parser.add_argument("--constrain-exact", action="store_true",
+                        help="with --constrain loops: the exact form of --constrain-lookahead (DESIGN.md 25) -- while a loop is open, "
+                             "never an edge from which it cannot close in time through edges the row has not used, so a row can "
+                             "only dead-end right after the edge that opened a loop; same record keys; single-process runs only, "
+                             "not with --constrain-lookahead or --constrain-beams")
     return parser
 
 
@@ -386,7 +404,7 @@ def main(argv=None):
              retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam,
              score_labels=args.score_labels, sample=args.sample, temperature=args.temperature, top_k=args.top_k,
              top_p=args.top_p, seed=args.seed, constrain=args.constrain, constrain_beams=args.constrain_beams,
-             constrain_lookahead=args.constrain_lookahead)
+             constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
