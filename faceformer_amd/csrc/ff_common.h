@@ -155,7 +155,9 @@ int ff_forced_tokens(const int64_t* paths, int* tok, int rows, int T, int S, hip
 int ff_forced_finalize(const int* tok, const float* lp_all, const int* greedy_all, const int* rank_all, const int* lengths, int rows,
                        int T, float* logprob, int64_t* greedy, int* rank, float* seq_logprob, hipStream_t st);
 
-// (sampled decode)
+// (sampled decode)  What a draw reads besides the step descriptor, and its check for operator `op` (ff_sample.hip).
+struct ff_sample_draw_io { const float* uniforms; int num_uniforms; const int* row_id; float temperature; int top_k; float top_p; };
+int ff_sample_draw_check(const char* op, const ff_sample_draw_io& d, int rows);
 int ff_pointer_sample_sync(const ff_step_io& io, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
                            float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream);
 int ff_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F, const int* num_input,
@@ -178,6 +180,7 @@ struct ff_constrained_state {
 };
 constexpr int FF_EXACT_MAX_S = 2048;   // keys (L + ntok) of a row the exact look-ahead's search takes
 struct ff_lookahead_io { const unsigned char *close_dist, *cycle_len; int budget; int exact; };
+int ff_lookahead_check(const char* op, const ff_loop_rule_io& rule, int S, const ff_lookahead_io& ahead);
 int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,
                                 const ff_lookahead_io* ahead, ff_stream_t stream);
 int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int Fc, int f0,
@@ -186,6 +189,18 @@ int ff_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int*
 int ff_constrain_finalize(const int* tok, const float* lp, const int* fin, const int* dead, int Btot, int T, const int* steps_dev,
                           const int* num_input, int dedup, int F, int w0, int nw, int Fc, int f0, int b0, int64_t* predict,
                           float* logprob, int* dead_end, int* seq_of_row, hipStream_t st);
+
+// Constrained sampled decode (ff_constrain_sample.hip): the constrained step's operands and the draw's; R draws per
+// anchor in the sampled decode's layout, each with the constrained decode's state.
+int ff_pointer_constrained_sample_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,
+                                       const ff_lookahead_io* ahead, const ff_sample_draw_io& draw, ff_stream_t stream);
+int ff_constrain_sample_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int* row_id, int Bc,
+                             int Fc, int R, int f0, int w0, int F, const int* num_input, int pad_tok, int term_lo, int term_hi,
+                             int ntok, const unsigned* follows, int L, hipStream_t st);
+int ff_constrain_sample_finalize(const int* tok, const float* lp, const int* fin, const int* dead, int Btot, int T,
+                                 const int* steps_dev, const int* num_input, int dedup, int F, int R, int w0, int nw, int Fc, int f0,
+                                 int b0, int64_t* samples, float* logprob, float* scores, int* dead_end, int64_t* predict,
+                                 float* predict_logprob, int* predict_dead_end, int* seq_of_row, hipStream_t st);
 
 // Constrained beam decode: `step` supplies the rule's and the beams' operands, io the common ones (io.rows = groups * width);
 // its beams, scores and predict are packed by ff_beam_finalize.

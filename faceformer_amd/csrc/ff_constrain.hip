@@ -283,6 +283,22 @@ int ff_loop_rule_check(const char* op, const ff_loop_rule_io& r, int S, int term
   return FF_OK;
 }
 
+// What a look-ahead adds to a constrained step's checks, for operator `op`: the flag bits its form needs, its tables, the budget's
+// range and, for the exact form, the key limit of its search.
+int ff_lookahead_check(const char* op, const ff_loop_rule_io& rule, int S, const ff_lookahead_io& ahead) {
+  if (ahead.exact) {
+    FF_CHECK_ARG((rule.flags & FF_CONSTRAIN_CONNECT) && (rule.flags & FF_CONSTRAIN_NO_REPEAT),
+                 "%s: the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT", op);
+    FF_CHECK_ARG(ahead.cycle_len, "%s: cycle_len is required", op);
+    FF_CHECK_ARG(S <= FF_EXACT_MAX_S, "%s: S=%d above %d keys (L + ntok)", op, S, FF_EXACT_MAX_S);
+  } else {
+    FF_CHECK_ARG(rule.flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", op);
+    FF_CHECK_ARG(ahead.close_dist && ahead.cycle_len, "%s: close_dist and cycle_len are required", op);
+  }
+  FF_CHECK_ARG(ahead.budget >= 0 && ahead.budget <= 254, "%s: budget=%d outside 0..254", op, ahead.budget);
+  return FF_OK;
+}
+
 // The one launch behind ff_pointer_constrained (ahead = null), ff_pointer_constrained_ahead and ff_pointer_constrained_exact
 // (ahead->exact); `op` words the errors.
 int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& s,
@@ -296,18 +312,9 @@ int ff_pointer_constrained_sync(const char* op, const ff_step_io& io, const ff_l
   FF_RETURN_IF(ff_loop_rule_check(op, rule, S, io.term_lo, io.term_hi));
   FF_CHECK_ARG(s.fin_in && s.first_in && s.prev_in && s.visited && s.mask_rows && s.next_tok && s.logprob && s.fin_out && s.dead_end &&
                    s.first_out && s.prev_out, "%s: null pointer", op);
-  if (ahead && ahead->exact) {
-    FF_CHECK_ARG((rule.flags & FF_CONSTRAIN_CONNECT) && (rule.flags & FF_CONSTRAIN_NO_REPEAT),
-                 "%s: the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT", op);
-    FF_CHECK_ARG(ahead->cycle_len, "%s: cycle_len is required", op);
-    FF_CHECK_ARG(S <= FF_EXACT_MAX_S, "%s: S=%d above %d keys (L + ntok)", op, S, FF_EXACT_MAX_S);
-    FF_CHECK_ARG(ahead->budget >= 0 && ahead->budget <= 254, "%s: budget=%d outside 0..254", op, ahead->budget);
-    a.cycle_len = ahead->cycle_len; a.budget = ahead->budget;
-  } else if (ahead) {
-    FF_CHECK_ARG(rule.flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", op);
-    FF_CHECK_ARG(ahead->close_dist && ahead->cycle_len, "%s: close_dist and cycle_len are required", op);
-    FF_CHECK_ARG(ahead->budget >= 0 && ahead->budget <= 254, "%s: budget=%d outside 0..254", op, ahead->budget);
-    a.close_dist = ahead->close_dist; a.cycle_len = ahead->cycle_len; a.budget = ahead->budget;
+  if (ahead) {
+    FF_RETURN_IF(ff_lookahead_check(op, rule, S, *ahead));
+    a.close_dist = ahead->exact ? nullptr : ahead->close_dist; a.cycle_len = ahead->cycle_len; a.budget = ahead->budget;
   }
   a.p.extra = s.mask_rows; a.p.ldextra = S;
   a.rows = s.mask_rows; a.follows = rule.follows; a.L = rule.L; a.fw = (rule.L + 31) >> 5; a.flags = rule.flags; a.ntok = rule.ntok;

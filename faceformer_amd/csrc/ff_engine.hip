@@ -43,6 +43,10 @@
 //     tables, operands offset per chunk as `follows` is.
 //   constrain with exact look-ahead (ff_decode_constrained_exact): the same again with
 //     ff_pointer_constrained_exact as the selection launch: budget = T - 1 - position and cycle_len as the one operand table.
+//   constrained sample (ff_decode_constrained_sample): the sampled decode's plan -- R independent sequences per
+//     anchor, no reorder -- with constrain's records and state per sequence (first, prev per step; visited words and the byte
+//     mask per sequence) and the sampled decode's row_id.  ff_pointer_constrained_sample in one of its three forms, the
+//     look-aheads with budget = T - 1 - position as above.
 //   constrained beam (ff_decode_constrained_beam): the beam decode's plan, records and reorder with
 //     ff_beam_constrained_select as the selection; also the cumulative dead flag per step, the rule's state in two halves that
 //     the steps read and write alternately, and the byte mask per sequence.
@@ -260,7 +264,7 @@ struct DecodeBuffers {
   int *first, *prev;
   unsigned* visited;
   unsigned char* byte_rows;
-  int* row_id;              // sample: [Btot] the draw every sequence reads, written once per call
+  int* row_id;              // sample, constrained sample: [Btot] the draw every sequence reads, written once per call
   // forced: [T-1, Btot] each, row s = what step s scored (the forced token's log-probability is `score`; the argmax, the rank)
   int *greedy, *rank;
 };
@@ -356,7 +360,7 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
@@ -372,6 +376,7 @@ struct Mode {
     return ff_constrain_params{ahead()->flags, ahead()->follows, ahead()->logprob, ahead()->dead_end};
   }
   const ff_constrain_beam_params* cbeam() const { return static_cast<const ff_constrain_beam_params*>(prm); }
+  const ff_constrain_sample_params* csample() const { return static_cast<const ff_constrain_sample_params*>(prm); }
 };
 
 // The micro-batch plan of a mode: the default plan for greedy and constrain; without de-duplication for forced (the rows are
@@ -381,6 +386,7 @@ void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, con
   switch (mode.kind) {
     case Mode::BEAM:
     case Mode::CONSTRAIN_BEAM:
+    case Mode::CONSTRAIN_SAMPLE:
     case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
     case Mode::FORCED: {
       ff_decode_params q = *p;
@@ -521,6 +527,16 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
       b.dead = bp.take<int>(TB);
       b.first = bp.take<int>(TB);
       b.prev = bp.take<int>(TB);
+      b.visited = bp.take<unsigned>(vw);
+      b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
+      break;
+    case Mode::CONSTRAIN_SAMPLE:   // (constrain's records per sequence of the sampled plan; row_id, visited and the byte rows last)
+      b.score = bp.take<float>(TB);
+      b.finished = bp.take<int>(TB);
+      b.dead = bp.take<int>(TB);
+      b.first = bp.take<int>(TB);
+      b.prev = bp.take<int>(TB);
+      b.row_id = bp.take<int>(Btot);
       b.visited = bp.take<unsigned>(vw);
       b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
       break;
@@ -1052,13 +1068,30 @@ struct DecodeRun {
     }
     return FF_OK;
   }
-  // The loop rule's operands of one micro-batch in the three constrained modes: the flags, the chunk's part of the follow table
+  // The loop rule's operands of one micro-batch in the constrained modes: the flags, the chunk's part of the follow table
   // and the words per row of it (= per sequence of `visited`).
   struct Rule { const unsigned* follows; int L, fw, flags; };
   Rule rule_of(const Chunk& c) const {
     const int L = p->L, fw = (L + 31) / 32;
-    const unsigned* follows = mode.kind == Mode::CONSTRAIN_BEAM ? mode.cbeam()->follows : mode.con().follows;
-    return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, mode.kind == Mode::CONSTRAIN_BEAM ? mode.cbeam()->flags : mode.con().flags};
+    const unsigned* follows;
+    int flags;
+    switch (mode.kind) {
+      case Mode::CONSTRAIN_BEAM: follows = mode.cbeam()->follows; flags = mode.cbeam()->flags; break;
+      case Mode::CONSTRAIN_SAMPLE: follows = mode.csample()->follows; flags = mode.csample()->flags; break;
+      default: follows = mode.con().follows; flags = mode.con().flags; break;
+    }
+    return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, flags};
+  }
+  // The look-ahead of the constrained greedy and constrained sampled modes: the form (0 none, 1 the closure look-ahead, 2 the
+  // exact one) and the whole batch's tables as the caller gave them.
+  struct Ahead { int form; const unsigned char *close_dist, *cycle_len; };
+  Ahead ahead_of() const {
+    switch (mode.kind) {
+      case Mode::CONSTRAIN_AHEAD: return Ahead{1, mode.ahead()->close_dist, mode.ahead()->cycle_len};
+      case Mode::CONSTRAIN_EXACT: return Ahead{2, nullptr, mode.exact()->cycle_len};
+      case Mode::CONSTRAIN_SAMPLE: return Ahead{mode.csample()->lookahead, mode.csample()->close_dist, mode.csample()->cycle_len};
+      default: return Ahead{0, nullptr, nullptr};
+    }
   }
   // Row 0 of the mode's per-step records and of the token array for one micro-batch: the start state of its sequences.
   int init_state(const Chunk& c) {
@@ -1077,6 +1110,7 @@ struct DecodeRun {
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
       case Mode::CONSTRAIN_EXACT:
+      case Mode::CONSTRAIN_SAMPLE:
       case Mode::CONSTRAIN_BEAM: {   // (constrained beam: half 0 of the ping-pong state, step 0 reads it)
         const Rule r = rule_of(c);
         int *dead = buf.dead + c.b0, *first = buf.first + c.b0, *prev = buf.prev + c.b0;
@@ -1084,6 +1118,9 @@ struct DecodeRun {
         if (mode.kind == Mode::CONSTRAIN_BEAM)
           return ff_constrain_beam_init(tok, score, fin, dead, buf.parent + c.b0, first, prev, visited, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok,
                                         p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
+        if (mode.kind == Mode::CONSTRAIN_SAMPLE)
+          return ff_constrain_sample_init(tok, score, fin, dead, first, prev, visited, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F,
+                                          ni, pad_tok, p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
         return ff_constrain_init(tok, score, fin, dead, first, prev, visited, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo, p->term_hi,
                                  m->num_token, r.follows, r.L, st);
       }
@@ -1181,20 +1218,25 @@ struct DecodeRun {
       }
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_EXACT:
-      case Mode::CONSTRAIN_AHEAD: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
+      case Mode::CONSTRAIN_AHEAD:
+      case Mode::CONSTRAIN_SAMPLE: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
         const Rule r = rule_of(c);
         const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
                                       buf.byte_rows + (size_t)c.b0 * S, tok_out, buf.score + out, buf.finished + out, buf.dead + out,
                                       buf.first + out, buf.prev + out};
         const ff_loop_rule_io rio{r.follows, r.L, r.flags, m->num_token};
-        if (mode.kind == Mode::CONSTRAIN) return ff_pointer_constrained_sync("ff_pointer_constrained", sio, rio, cs, nullptr, st);
         // the look-aheads: this step selects position t, so a loop has T - 1 - t further positions to close in
-        if (mode.kind == Mode::CONSTRAIN_EXACT) {
-          const ff_lookahead_io exact{nullptr, mode.exact()->cycle_len + (size_t)c.w0 * r.L, T - 1 - t, 1};
-          return ff_pointer_constrained_sync("ff_pointer_constrained_exact", sio, rio, cs, &exact, st);
+        const Ahead la = ahead_of();
+        const ff_lookahead_io ahead{la.form == 1 ? la.close_dist + (size_t)c.w0 * r.L * r.L : nullptr,
+                                    la.form ? la.cycle_len + (size_t)c.w0 * r.L : nullptr, T - 1 - t, la.form == 2 ? 1 : 0};
+        if (mode.kind == Mode::CONSTRAIN_SAMPLE) {   // (this step's uniforms are read through the chunk's row_id)
+          const ff_constrain_sample_params* q = mode.csample();
+          const int rows = N * F * mode.G;
+          const ff_sample_draw_io draw{q->uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, q->temperature, q->top_k, q->top_p};
+          return ff_pointer_constrained_sample_sync("ff_pointer_constrained_sample", sio, rio, cs, la.form ? &ahead : nullptr, draw, st);
         }
-        const ff_lookahead_io ahead{mode.ahead()->close_dist + (size_t)c.w0 * r.L * r.L, mode.ahead()->cycle_len + (size_t)c.w0 * r.L, T - 1 - t, 0};
-        return ff_pointer_constrained_sync("ff_pointer_constrained_ahead", sio, rio, cs, &ahead, st);
+        static const char* const op[3] = {"ff_pointer_constrained", "ff_pointer_constrained_ahead", "ff_pointer_constrained_exact"};
+        return ff_pointer_constrained_sync(op[la.form], sio, rio, cs, la.form ? &ahead : nullptr, st);
       }
       case Mode::FORCED:   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
         return ff_pointer_forced_sync(sio, tok_out, buf.score + in, buf.greedy + in, buf.rank + in, st);
@@ -1401,6 +1443,12 @@ struct DecodeRun {
       case Mode::CONSTRAIN_EXACT:
         return ff_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
                                      c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con().logprob, mode.con().dead_end, io.seq_of_row, main_st);
+      case Mode::CONSTRAIN_SAMPLE: {
+        const ff_constrain_sample_params* q = mode.csample();
+        return ff_constrain_sample_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, G,
+                                            c.w0, c.nw, c.Fc / G, c.f0, c.b0, q->samples, q->logprob, q->scores, q->dead_end, io.predict,
+                                            q->predict_logprob, q->predict_dead_end, io.seq_of_row, main_st);
+      }
       default: break;   // (forced: forced_epilogue packs all rows at once)
     }
     const long total = (long)c.nw * F * T;
@@ -1473,6 +1521,24 @@ int check_opt_in_outputs(const char* name, const ff_decode_params* p, const char
 // ... the loop rule's operands in the three constrained decodes (the operators' own check: flags, follow table, terminator range) ...
 int check_loop_rule(const char* name, int flags, const unsigned* follows, const ff_model* m, const ff_decode_params* p) {
   return ff_loop_rule_check(name, ff_loop_rule_io{follows, p->L, flags, m->num_token}, p->L + m->num_token, p->term_lo, p->term_hi);
+}
+// ... the look-ahead of a constrained decode (form 1: the closure look-ahead, 2: the exact one), beyond what the step checks:
+// the flag bits and tables of the form, and the limits of the budget's byte and of the exact search ...
+int check_lookahead(const char* name, int form, int flags, const unsigned char* close_dist, const unsigned char* cycle_len,
+                    const ff_model* m, const ff_decode_params* p) {
+  if (form == 1) {
+    FF_CHECK_ARG(flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", name);
+    FF_CHECK_ARG(close_dist && cycle_len, "%s: close_dist and cycle_len are required", name);
+    FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the tables' byte)", name, p->T);
+  } else if (form == 2) {
+    FF_CHECK_ARG((flags & FF_CONSTRAIN_CONNECT) && (flags & FF_CONSTRAIN_NO_REPEAT),
+                 "%s: the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT", name);
+    FF_CHECK_ARG(cycle_len, "%s: cycle_len is required", name);
+    FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the table's byte)", name, p->T);
+    FF_CHECK_ARG(p->L + m->num_token <= FF_EXACT_MAX_S, "%s: L=%d above %d (L + num_token keys at most %d)", name, p->L,
+                 FF_EXACT_MAX_S - m->num_token, FF_EXACT_MAX_S);
+  }
+  return FF_OK;
 }
 // ... and what they hand to the decode: no extra mask, no pointer_out, no best / second traces, no log-probabilities.
 DecodeIO opt_in_io(const float* memory, const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host,
@@ -1685,9 +1751,7 @@ extern "C" int ff_decode_constrained_ahead(const ff_model* m, const ff_decode_pa
   FF_CHECK_ARG(m && p && ahead, "%s: null model, params or look-ahead params", name);
   FF_RETURN_IF(check_opt_in(name, "the constrained decode with look-ahead is", p, extra_mask));
   FF_RETURN_IF(check_loop_rule(name, ahead->flags, ahead->follows, m, p));
-  FF_CHECK_ARG(ahead->flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", name);
-  FF_CHECK_ARG(ahead->close_dist && ahead->cycle_len, "%s: close_dist and cycle_len are required", name);
-  FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the tables' byte)", name, p->T);
+  FF_RETURN_IF(check_lookahead(name, 1, ahead->flags, ahead->close_dist, ahead->cycle_len, m, p));
   FF_RETURN_IF(check_opt_in_outputs(name, p, "logprob and dead_end", ahead->logprob && ahead->dead_end, trace_best, trace_second,
                                     pointer_out));
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
@@ -1709,12 +1773,7 @@ extern "C" int ff_decode_constrained_exact(const ff_model* m, const ff_decode_pa
   FF_CHECK_ARG(m && p && exact, "%s: null model, params or exact look-ahead params", name);
   FF_RETURN_IF(check_opt_in(name, "the constrained decode with exact look-ahead is", p, extra_mask));
   FF_RETURN_IF(check_loop_rule(name, exact->flags, exact->follows, m, p));
-  FF_CHECK_ARG((exact->flags & FF_CONSTRAIN_CONNECT) && (exact->flags & FF_CONSTRAIN_NO_REPEAT),
-               "%s: the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT", name);
-  FF_CHECK_ARG(exact->cycle_len, "%s: cycle_len is required", name);
-  FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the table's byte)", name, p->T);
-  FF_CHECK_ARG(p->L + m->num_token <= FF_EXACT_MAX_S, "%s: L=%d above %d (L + num_token keys at most %d)", name, p->L,
-               FF_EXACT_MAX_S - m->num_token, FF_EXACT_MAX_S);
+  FF_RETURN_IF(check_lookahead(name, 2, exact->flags, nullptr, exact->cycle_len, m, p));
   FF_RETURN_IF(check_opt_in_outputs(name, p, "logprob and dead_end", exact->logprob && exact->dead_end, trace_best, trace_second,
                                     pointer_out));
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
@@ -1748,6 +1807,36 @@ extern "C" int ff_decode_constrained_beam(const ff_model* m, const ff_decode_par
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM, beam->width, beam));
+}
+
+extern "C" size_t ff_decode_constrained_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
+                                                               int num_samples) {
+  if (num_samples < 1 || num_samples > 64) return 0;
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_SAMPLE, num_samples));
+}
+
+extern "C" int ff_decode_constrained_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                            const unsigned char* mask, const int* kv_len, const int* num_input,
+                                            const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                                            int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                                            float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                                            size_t workspace_bytes, const ff_constrain_sample_params* cs, ff_stream_t stream) {
+  const char* name = "ff_decode_constrained_sample";
+  FF_CHECK_ARG(m && p && cs, "%s: null model, params or constrained sample params", name);
+  FF_RETURN_IF(check_opt_in(name, "the constrained sampled decode is", p, extra_mask));
+  FF_CHECK_ARG(cs->num_samples >= 1 && cs->num_samples <= 64, "%s: num_samples=%d outside 1..64", name, cs->num_samples);
+  FF_RETURN_IF(check_loop_rule(name, cs->flags, cs->follows, m, p));
+  FF_CHECK_ARG(cs->lookahead >= 0 && cs->lookahead <= 2, "%s: lookahead=%d must be 0 (none), 1 (look-ahead) or 2 (exact)", name, cs->lookahead);
+  FF_RETURN_IF(check_lookahead(name, cs->lookahead, cs->flags, cs->close_dist, cs->cycle_len, m, p));
+  FF_RETURN_IF(check_opt_in_outputs(name, p, "uniforms, samples, logprob, scores and dead_end",
+                                    cs->uniforms && cs->samples && cs->logprob && cs->scores && cs->dead_end, trace_best, trace_second,
+                                    pointer_out));
+  FF_CHECK_ARG(p->N > 0 && p->F > 0 && (long long)p->N * p->F * cs->num_samples < (1LL << 31), "%s: bad sizes", name);
+  const int rows = p->N * p->F * cs->num_samples;   // (the draw's own check, with the step's text: the uniforms of one step)
+  FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{cs->uniforms, rows, nullptr, cs->temperature, cs->top_k, cs->top_p}, rows));
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_SAMPLE, cs->num_samples, cs));
 }
 
 namespace {

@@ -4,7 +4,8 @@
 // pointer_sample_kernel: one wavefront per sequence, four per block, as pointer_reduce_kernel.  A finished sequence appends
 // token 0 and draws nothing.  Every other one masks and reduces its raw logit row exactly as the greedy launch does
 // (ff_pointer_mask_reduce<true>, ff_device.h: row maximum m, argmax with torch's tie rule, sum exp(l - m)); a row without a live
-// key takes token 0, temperature 0 takes the argmax.  Otherwise, with w[s] = exp((l[s] - m) / temperature) over the live keys:
+// key takes token 0, temperature 0 takes the argmax.  Otherwise (ff_sample_draw, ff_select.h: one copy, shared with the
+// constrained sampling launch of ff_constrain_sample.hip), with w[s] = exp((l[s] - m) / temperature) over the live keys:
 //   top-k   v_K, the K-th largest logit, by bisection on the order-preserving integer image of the fp32 value: 32 rounds, each
 //           a count of the keys at or above the candidate (one ballot per 64 keys).  Exact; ties at v_K are all kept.
 //   top-p   theta, the largest kept logit at which the mass of the keys >= theta reaches P * (mass of the kept keys), by the same
@@ -26,6 +27,7 @@
 #include "ff_common.h"
 #include "ff_device.h"
 #include "ff_launch.h"
+#include "ff_select.h"
 
 namespace {
 
@@ -39,23 +41,6 @@ struct SampleArgs {
   int* tok; float* logprob;  // [B] out
   float temperature; int top_k; float top_p;
 };
-
-// fp32 -> unsigned, order preserving (-0 counts as +0); and back
-__device__ __forceinline__ unsigned sample_key(float v) {
-  const unsigned b = __float_as_uint(v + 0.f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float sample_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// inclusive scan of one value per lane, lanes in ascending order (Hillis-Steele: six rounds)
-__device__ __forceinline__ float sample_wave_scan(float c, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const float o = __shfl_up(c, off, FF_WAVE);
-    if (lane >= off) c += o;
-  }
-  return c;
-}
 
 __global__ __launch_bounds__(256) void pointer_sample_kernel(SampleArgs a) {
   const PointerArgs& pa = a.p;
@@ -73,78 +58,7 @@ __global__ __launch_bounds__(256) void pointer_sample_kernel(SampleArgs a) {
       int i1;
       ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &i1, &lsum);
       const float* lrow = pa.logits + (size_t)b * pa.ldlogits;
-      const int nchunk = (S + 63) >> 6;
-      const float tau = a.temperature;
-      if (m == FILL) tok = 0;            // no live key (masked keys hold -FLT_MAX)
-      else if (tau == 0.f) tok = i1;     // greedy's rule
-      else {
-        int nlive = 0;
-        for (int c = 0; c < nchunk && a.top_k > 0; ++c) {
-          const int s = c * 64 + lane;
-          nlive += __popcll(__ballot(s < S && ff_ld4(lrow + s) > FILL));
-        }
-        // top-k: the largest key image with at least K keys at or above it is the image of the K-th largest logit
-        float thr = FILL;
-        if (a.top_k > 0 && a.top_k < nlive) {
-          unsigned th = 0;
-          for (unsigned bit = 0x80000000u; bit; bit >>= 1) {
-            const unsigned cand = th | bit;
-            int cnt = 0;
-            for (int c = 0; c < nchunk; ++c) {
-              const int s = c * 64 + lane;
-              cnt += __popcll(__ballot(s < S && sample_key(ff_ld4(lrow + s)) >= cand));
-            }
-            if (cnt >= a.top_k) th = cand;
-          }
-          thr = sample_unkey(th);
-        }
-        // top-p over the keys top-k kept
-        if (a.top_p < 1.f) {
-          const float vk = thr;
-          float target = 0.f;
-          unsigned th = 0;
-          for (int round = -1; round < 32; ++round) {   // round -1: the mass of everything top-k kept
-            const unsigned cand = round < 0 ? 0u : (th | (0x80000000u >> round));
-            float mass = 0.f;
-            for (int s = lane; s < S; s += 64) {
-              const float v = ff_ld4(lrow + s);
-              const bool in = v > FILL && v >= vk && sample_key(v) >= cand;
-              mass += in ? __expf((v - m) / tau) : 0.f;
-            }
-            mass = ff_wave_sum(mass);
-            if (round < 0) target = a.top_p * mass;
-            else if (mass >= target) th = cand;
-          }
-          thr = sample_unkey(th);
-        }
-        // draw
-        int rid = a.row_id ? ff_ld4i(a.row_id + b) : b;
-        rid = min(max(rid, 0), a.num_uniforms - 1);
-        const float u = fminf(fmaxf(ff_ld4(a.uniforms + rid), 0.f), 0.99999994f);   // 1 - 2^-24
-        float Z = 0.f;
-        for (int c = 0; c < nchunk; ++c) {
-          const int s = c * 64 + lane;
-          const float v = s < S ? ff_ld4(lrow + s) : FILL;
-          const float w = (v > FILL && v >= thr) ? __expf((v - m) / tau) : 0.f;
-          Z = Z + __shfl(sample_wave_scan(w, lane), 63, FF_WAVE);
-        }
-        const float uz = u * Z;
-        float carry = 0.f;
-        int last = 0;
-        bool found = false;
-        for (int c = 0; c < nchunk && !found; ++c) {
-          const int s = c * 64 + lane;
-          const float v = s < S ? ff_ld4(lrow + s) : FILL;
-          const bool kept = v > FILL && v >= thr;
-          const float local = sample_wave_scan(kept ? __expf((v - m) / tau) : 0.f, lane);
-          const unsigned long long kb = __ballot(kept);
-          const unsigned long long hb = __ballot(kept && carry + local > uz);
-          if (kb) last = c * 64 + 63 - __clzll(kb);
-          if (hb) { tok = c * 64 + __ffsll((long long)hb) - 1; found = true; }
-          carry = carry + __shfl(local, 63, FF_WAVE);
-        }
-        if (!found) tok = last;
-      }
+      tok = ff_sample_draw(lrow, S, lane, m, i1, a.temperature, a.top_k, a.top_p, a.uniforms, a.row_id, a.num_uniforms, b);
       // the masked l[tok] was stored by lane tok % 64 a moment ago: that lane reads its own store back and broadcasts it
       const int owner = tok & 63;
       const float mine = lane == owner ? ff_ld4(lrow + tok) : 0.f;
@@ -219,6 +133,16 @@ __global__ void sample_finalize_kernel(const int* __restrict__ tok, const float*
 
 }  // namespace
 
+// What a draw adds to a step's checks, for operator `op`: the uniforms and how the B launch rows index them, the parameters' ranges.
+int ff_sample_draw_check(const char* op, const ff_sample_draw_io& d, int B) {
+  FF_CHECK_ARG(d.uniforms && d.num_uniforms > 0, "%s: null pointer", op);
+  FF_CHECK_ARG(d.row_id || d.num_uniforms >= B, "%s: %d uniforms for %d rows without a row_id", op, d.num_uniforms, B);
+  FF_CHECK_ARG(d.temperature >= 0.f && d.temperature <= FLT_MAX && d.top_k >= 0 && d.top_p > 0.f && d.top_p <= 1.f,
+               "%s: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]", op, (double)d.temperature, d.top_k,
+               (double)d.top_p);
+  return FF_OK;
+}
+
 int ff_pointer_sample_sync(const ff_step_io& io, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
                            float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream) {
   const int B = io.rows, S = io.S;
@@ -227,11 +151,8 @@ int ff_pointer_sample_sync(const ff_step_io& io, const float* uniforms, int num_
   SampleArgs a;
   memset(&a, 0, sizeof(a));
   FF_RETURN_IF(ff_step_args(&a.p, "ff_pointer_sample", true, io));
-  FF_CHECK_ARG(uniforms && num_uniforms > 0 && next_tok && logprob && fin_out, "ff_pointer_sample: null pointer");
-  FF_CHECK_ARG(row_id || num_uniforms >= B, "ff_pointer_sample: %d uniforms for %d rows without a row_id", num_uniforms, B);
-  FF_CHECK_ARG(temperature >= 0.f && temperature <= FLT_MAX && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
-               "ff_pointer_sample: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]", (double)temperature,
-               top_k, (double)top_p);
+  FF_CHECK_ARG(next_tok && logprob && fin_out, "ff_pointer_sample: null pointer");
+  FF_RETURN_IF(ff_sample_draw_check("ff_pointer_sample", ff_sample_draw_io{uniforms, num_uniforms, row_id, temperature, top_k, top_p}, B));
   a.uniforms = uniforms; a.num_uniforms = num_uniforms; a.row_id = row_id; a.fin_in = fin_in; a.fin_out = fin_out;
   a.tok = next_tok; a.logprob = logprob;
   a.temperature = temperature; a.top_k = top_k; a.top_p = top_p;

@@ -86,6 +86,109 @@ __device__ __forceinline__ void ff_beam_rank(const float (&lsc)[W], const int (&
   *ix = x;
 }
 
+// ---- the draw of a sampled step (include/faceformer_hip.h states the rule) --------------------------------------------
+// One copy for pointer_sample_kernel (ff_sample.hip) and pointer_constrained_sample_kernel (ff_constrain_sample.hip): what lies
+// between the masked reduction of a row and the store of its log-probability.
+// fp32 -> unsigned, order preserving (-0 counts as +0); and back
+__device__ __forceinline__ unsigned sample_key(float v) {
+  const unsigned b = __float_as_uint(v + 0.f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float sample_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// inclusive scan of one value per lane, lanes in ascending order (Hillis-Steele: six rounds)
+__device__ __forceinline__ float sample_wave_scan(float c, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float o = __shfl_up(c, off, FF_WAVE);
+    if (lane >= off) c += o;
+  }
+  return c;
+}
+
+// The token of launch row b from its masked and reduced logit row lrow[0..S) (maximum m, argmax i1; masked keys hold -FLT_MAX):
+// no live key -> 0, temperature 0 -> i1, else the top-k bisection, the top-p bisection and the two scans of the header's rule,
+// with the row's uniform uniforms[row_id[b]] (row_id null: b) clamped into [0, 1 - 2^-24].  Wave-uniform.  The row is re-read
+// from memory in every round with lane = key mod 64: a lane reads only the keys it masked itself.  Selects into a local and
+// returns it (the note above ff_beam_walk: no conditional stores through references).
+__device__ __forceinline__ int ff_sample_draw(const float* lrow, int S, int lane, float m, int i1, float tau, int top_k, float top_p,
+                                              const float* uniforms, const int* row_id, int num_uniforms, int b) {
+  const float FILL = -FLT_MAX;
+  const int nchunk = (S + 63) >> 6;
+  int tok = 0;
+  if (m == FILL) tok = 0;            // no live key (masked keys hold -FLT_MAX)
+  else if (tau == 0.f) tok = i1;     // greedy's rule
+  else {
+    int nlive = 0;
+    for (int c = 0; c < nchunk && top_k > 0; ++c) {
+      const int s = c * 64 + lane;
+      nlive += __popcll(__ballot(s < S && ff_ld4(lrow + s) > FILL));
+    }
+    // top-k: the largest key image with at least K keys at or above it is the image of the K-th largest logit
+    float thr = FILL;
+    if (top_k > 0 && top_k < nlive) {
+      unsigned th = 0;
+      for (unsigned bit = 0x80000000u; bit; bit >>= 1) {
+        const unsigned cand = th | bit;
+        int cnt = 0;
+        for (int c = 0; c < nchunk; ++c) {
+          const int s = c * 64 + lane;
+          cnt += __popcll(__ballot(s < S && sample_key(ff_ld4(lrow + s)) >= cand));
+        }
+        if (cnt >= top_k) th = cand;
+      }
+      thr = sample_unkey(th);
+    }
+    // top-p over the keys top-k kept
+    if (top_p < 1.f) {
+      const float vk = thr;
+      float target = 0.f;
+      unsigned th = 0;
+      for (int round = -1; round < 32; ++round) {   // round -1: the mass of everything top-k kept
+        const unsigned cand = round < 0 ? 0u : (th | (0x80000000u >> round));
+        float mass = 0.f;
+        for (int s = lane; s < S; s += 64) {
+          const float v = ff_ld4(lrow + s);
+          const bool in = v > FILL && v >= vk && sample_key(v) >= cand;
+          mass += in ? __expf((v - m) / tau) : 0.f;
+        }
+        mass = ff_wave_sum(mass);
+        if (round < 0) target = top_p * mass;
+        else if (mass >= target) th = cand;
+      }
+      thr = sample_unkey(th);
+    }
+    // draw
+    int rid = row_id ? ff_ld4i(row_id + b) : b;
+    rid = min(max(rid, 0), num_uniforms - 1);
+    const float u = fminf(fmaxf(ff_ld4(uniforms + rid), 0.f), 0.99999994f);   // 1 - 2^-24
+    float Z = 0.f;
+    for (int c = 0; c < nchunk; ++c) {
+      const int s = c * 64 + lane;
+      const float v = s < S ? ff_ld4(lrow + s) : FILL;
+      const float w = (v > FILL && v >= thr) ? __expf((v - m) / tau) : 0.f;
+      Z = Z + __shfl(sample_wave_scan(w, lane), 63, FF_WAVE);
+    }
+    const float uz = u * Z;
+    float carry = 0.f;
+    int last = 0;
+    bool found = false;
+    for (int c = 0; c < nchunk && !found; ++c) {
+      const int s = c * 64 + lane;
+      const float v = s < S ? ff_ld4(lrow + s) : FILL;
+      const bool kept = v > FILL && v >= thr;
+      const float local = sample_wave_scan(kept ? __expf((v - m) / tau) : 0.f, lane);
+      const unsigned long long kb = __ballot(kept);
+      const unsigned long long hb = __ballot(kept && carry + local > uz);
+      if (kb) last = c * 64 + 63 - __clzll(kb);
+      if (hb) { tok = c * 64 + __ffsll((long long)hb) - 1; found = true; }
+      carry = carry + __shfl(local, 63, FF_WAVE);
+    }
+    if (!found) tok = last;
+  }
+  return tok;
+}
+
 // ---- face-loop rule (include/faceformer_hip.h states it on tokens) ---------------------------------------------------
 // What the rule reads of one launch besides PointerArgs; the kernels fill it from their own arguments.
 struct FFLoopRule {

@@ -24,7 +24,7 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
-           "parse_parallel_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance"]
+           "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance"]
 
 
 def _tok(token, name, default):
@@ -256,6 +256,21 @@ def parse_parallel_samples_scored(samples, scores, num_edges, token):
         sc = sc.sum(axis=-1)
     if sc.shape != rows.shape[:-1]:
         raise ValueError("scores must be shaped like samples, or like samples without the position axis")
+    return parse_parallel_beams_scored(rows, sc, num_edges, token)
+
+
+def parse_parallel_constrained_samples_scored(samples, scores, dead_end, num_edges, token):
+    """The faces of a constrained sampled decode (the parallel model's constrain_samples): parse_parallel_samples_scored
+    over the draws that did not run into a dead end -- dead_end [..., R] nonzero: the draw is left out (it ends in a terminator
+    the rule opened for want of an edge: its loop is open).  scores [..., R] or [..., R, T] as there.  unique_faces_with_scores
+    then gives every face's best score and the number of DRAWS that produced it."""
+    rows = np.asarray(samples, dtype=np.int64)
+    sc = np.array(scores, dtype=np.float64, copy=True)
+    if sc.shape == rows.shape:
+        sc = sc.sum(axis=-1)
+    if sc.shape != rows.shape[:-1]:
+        raise ValueError("scores must be shaped like samples, or like samples without the position axis")
+    sc[np.asarray(dead_end).reshape(sc.shape) != 0] = -np.inf
     return parse_parallel_beams_scored(rows, sc, num_edges, token)
 
 

@@ -374,7 +374,8 @@ class PathEngine:
                trace=False, return_pointer=False, no_stop=False, stop_callback=None, staged_num_input=None,
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
-               constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False):
+               constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
+               constrain_samples=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -424,15 +425,25 @@ class PathEngine:
         masks every edge from which it cannot close within T through edges the row has not used (one search per open row and
         step); with it closed, every edge with cycle_len > the positions left.  cycle_len [N, L] uint8 on the device
         (ops.follow_distance) is required, close_dist is not read.  Outputs are constrain's; a dead end is then only possible
-        right after the position that opened the loop."""
+        right after the position that opened the loop.
+
+        constrain_samples=R in 1..64 (only with constrain, not with constrain_beams; ff_decode_constrained_sample, DESIGN.md 26;
+        None or 0: the constrained greedy decode above): R independent draws per anchor from the CONSTRAINED row under
+        temperature / top_k / top_p, driven by `uniforms` [T-1, N*F*R] as num_samples' are; with constrain_lookahead or
+        constrain_exact (and their tables) the row is that form's.  Also `samples` [N*F*R, T] int64, `sample_logprob` (same
+        layout: the log-probability under the model renormalised over the keys the rule allows), `sample_scores` [N*F*R] and
+        `sample_dead_end` [N*F*R] int32; `predict`, `logprob` and `dead_end` are draw 0; with trace=True `logits`
+        [T-1, N*F*R, S] holds the constrained masked rows.  temperature=0 equals the constrained greedy decode of the same form,
+        R times; flag bits 0 equal the num_samples decode."""
         W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
         CB = _modes.constrain_beams_value(constrain_beams, CF)
         LA = _modes.constrain_lookahead_value(constrain_lookahead, CF, CB)
         EX = _modes.constrain_exact_value(constrain_exact, CF, CB, LA)
-        mode, value = _modes.of_options(logprob, CB, LA, EX, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
+        CS = _modes.constrain_samples_value(constrain_samples, CF, CB)
+        mode, value = _modes.of_options(logprob, CB, LA, EX, CS, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
         G = value if mode.per_anchor else 1       # sequences per anchor
         o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
-                 logprob=logprob, beam_width=W, num_samples=R, constrain=CF, constrain_beams=CB, temperature=temperature, top_k=top_k, top_p=top_p,
+                 logprob=logprob, beam_width=W, num_samples=R, constrain=CF, constrain_beams=CB, constrain_samples=CS, temperature=temperature, top_k=top_k, top_p=top_p,
                  uniforms=uniforms, follow_table=follow_table, constrain_lookahead=LA, constrain_exact=EX, close_dist=close_dist, cycle_len=cycle_len, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
                  N=memory.shape[0], S=memory.shape[1], F=F, T=T)
         if value is not None:    # (retire, an option of the greedy record, is checked behind the operands)

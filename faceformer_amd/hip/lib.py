@@ -172,6 +172,13 @@ class ConstrainExactParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("follows", fptr), ("cycle_len", fptr), ("logprob", fptr), ("dead_end", fptr)]
 
 
+class ConstrainSampleParams(C.Structure):
+    _fields_ = [("num_samples", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("uniforms", fptr),
+                ("flags", C.c_int), ("follows", fptr), ("lookahead", C.c_int), ("close_dist", fptr), ("cycle_len", fptr),
+                ("samples", fptr), ("logprob", fptr), ("scores", fptr), ("dead_end", fptr), ("predict_logprob", fptr),
+                ("predict_dead_end", fptr)]
+
+
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
 
@@ -307,6 +314,16 @@ SIGNATURES = {
                                               C.POINTER(C.c_int), fptr,
                                               fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                               C.c_size_t, C.POINTER(ConstrainExactParams), fptr]),
+    "ff_pointer_constrained_sample": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                                fptr, C.c_int, fptr, C.c_int, fptr, fptr, fptr, C.c_int, fptr, C.c_float, C.c_int,
+                                                C.c_float, C.c_int, fptr, fptr, C.c_int, fptr]),
+    "ff_decode_constrained_sample_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int),
+                                                                  C.c_int]),
+    "ff_decode_constrained_sample": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                               C.POINTER(C.c_int), fptr,
+                                               fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                                               C.c_size_t, C.POINTER(ConstrainSampleParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
 }
 

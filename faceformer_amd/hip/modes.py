@@ -187,6 +187,42 @@ def _constrain_exact_operand(eng, o):
         raise ValueError("cycle_len must be a uint8 tensor of shape [%d, %d]" % (o["N"], L))
 
 
+def constrain_samples_value(constrain_samples, flags, constrain_beams=0):
+    """The count of a `constrain_samples` value: None / 0 -> 0 (the option is off); else 1..SAMPLE_MAX, only with
+    `constrain` set (`flags`: constrain_flags of it) and not with constrain_beams."""
+    if constrain_samples is None or (not isinstance(constrain_samples, bool) and constrain_samples == 0):
+        return 0
+    if isinstance(constrain_samples, bool) or not isinstance(constrain_samples, int) or not 1 <= constrain_samples <= SAMPLE_MAX:
+        raise ValueError("constrain_samples=%r: must be None, 0 or a count in 1..%d" % (constrain_samples, SAMPLE_MAX))
+    if flags is None:
+        raise ValueError("constrain_samples=%d needs constrain ('no_repeat' or 'loops'): it is the sampling over the constrained keys"
+                         % constrain_samples)
+    if constrain_beams:
+        raise ValueError("constrain_samples excludes constrain_beams: a decode draws from the constrained keys or searches them")
+    return int(constrain_samples)
+
+
+def _constrain_sample_values(o):
+    """constrain's value check, the sampled decode's on constrain_samples and the parameters, and the selected look-ahead's."""
+    _sample_values(dict(o, num_samples=o["constrain_samples"]))
+    if o["constrain_exact"]:
+        _constrain_exact_values(o)
+    elif o["constrain_lookahead"]:
+        _constrain_ahead_values(o)
+    else:
+        _constrain_values(o)
+
+
+def _constrain_sample_operand(eng, o):
+    if o["constrain_exact"]:
+        _constrain_exact_operand(eng, o)
+    elif o["constrain_lookahead"]:
+        _constrain_ahead_operand(eng, o)
+    else:
+        _constrain_operand(eng, o)
+    _sample_operand(eng, dict(o, num_samples=o["constrain_samples"]))
+
+
 def _constrain_operand(eng, o):
     L = o["S"] - eng.num_token
     shape = (o["N"], L, (L + 31) // 32)
@@ -299,6 +335,36 @@ CONSTRAIN_EXACT = CONSTRAIN._replace(
     tail=lambda o, ptrs, traced: (C.byref(_L.ConstrainExactParams(o["constrain"], _p(o["follow_table"]), _p(o["cycle_len"]), *ptrs)),),
     prepare=lambda *a: _constrain_exact_prepare(*a))
 
+def _constrain_sample_tail(o, ptrs, traced):
+    form = 2 if o["constrain_exact"] else (1 if o["constrain_lookahead"] else 0)
+    return (C.byref(_L.ConstrainSampleParams(
+        o["constrain_samples"], float(o["temperature"]), int(o["top_k"]), float(o["top_p"]), _p(o["uniforms"]), o["constrain"],
+        _p(o["follow_table"]), form, _p(o["close_dist"]) if form == 1 else None, _p(o["cycle_len"]) if form else None, *ptrs)),)
+
+
+def _constrain_sample_prepare(m, R, inputs, dev, T, N, F, ni, order):
+    CF = constrain_flags(m.constrain)
+    if getattr(m, "constrain_exact", False):
+        kw = _constrain_exact_prepare(m, CF, inputs, dev, T, N, F, ni, order)
+    elif getattr(m, "constrain_lookahead", False):
+        kw = _constrain_ahead_prepare(m, CF, inputs, dev, T, N, F, ni, order)
+    else:
+        kw = CONSTRAIN.prepare(m, CF, inputs, dev, T, N, F, ni, order)
+    return dict(kw, constrain_samples=R, temperature=float(m.sample_temperature), top_k=int(m.sample_top_k),
+                top_p=float(m.sample_top_p), uniforms=m._sample_uniforms(inputs, dev, T, N, F, R, order))
+
+
+# constrain with its option constrain_samples = R: R draws per anchor from the constrained row, in the plain form
+# or with constrain_lookahead / constrain_exact.  Outside MODES, as CONSTRAIN_BEAM is.  The outputs: the draws, and draw 0 under
+# constrain's own keys (logprob, dead_end).
+CONSTRAIN_SAMPLE = CONSTRAIN._replace(
+    subject="constrain_samples", entry="ff_decode_constrained_sample", per_anchor=True, values=_constrain_sample_values,
+    operand=_constrain_sample_operand,
+    own=(("follow_table", _I32), ("uniforms", _F32), ("close_dist", torch.uint8), ("cycle_len", torch.uint8)),
+    outs=(("samples", "GT", _I64), ("sample_logprob", "GT", _F32), ("sample_scores", "G", _F32), ("sample_dead_end", "G", _I32),
+          ("logprob", "T", _F32), ("dead_end", "", _I32)),
+    tail=_constrain_sample_tail, prepare=lambda *a: _constrain_sample_prepare(*a))
+
 SAMPLE = Mode(
     subject="num_samples", excludes=_COMMON + ("beam_width",), entry="ff_decode_sample", per_anchor=True, values=_sample_values,
     values_first=True, operand=_sample_operand, own=(("uniforms", _F32),),
@@ -337,16 +403,19 @@ MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 
 
-def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, constrain_exact=False, **values):
+def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, constrain_exact=False, constrain_samples=0, **values):
     """(record, value) of the first of MODES whose option is set in `values` (constrain: the flag bits or None; num_samples;
     beam_width); else the greedy record (its logprob form with `logprob`) and None.  constrain with constrain_beams = W > 0:
-    the CONSTRAIN_BEAM record and W; with constrain_lookahead: the CONSTRAIN_AHEAD record and the flag bits; with constrain_exact:
-    the CONSTRAIN_EXACT record and the flag bits."""
+    the CONSTRAIN_BEAM record and W; with constrain_samples = R > 0: the CONSTRAIN_SAMPLE record and R (whatever look-ahead is
+    set: the record reads it); with constrain_lookahead: the CONSTRAIN_AHEAD record and the flag bits; with constrain_exact: the
+    CONSTRAIN_EXACT record and the flag bits."""
     for mode in MODES[:-1]:
         v = values[mode.subject]
         if v is not None and (v or mode is CONSTRAIN):
             if mode is CONSTRAIN and constrain_beams:
                 return CONSTRAIN_BEAM, constrain_beams
+            if mode is CONSTRAIN and constrain_samples:
+                return CONSTRAIN_SAMPLE, constrain_samples
             if mode is CONSTRAIN and constrain_lookahead:
                 return CONSTRAIN_AHEAD, v
             if mode is CONSTRAIN and constrain_exact:

@@ -581,9 +581,11 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
 
 
 def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
-                      want_rows, want_stats, counter, ahead):
+                      want_rows, want_stats, counter, ahead, draw=None):
     """pointer_constrained (ahead None), pointer_constrained_ahead (ahead = ("ahead", close_dist, cycle_len, budget)) and
-    pointer_constrained_exact (ahead = ("exact", cycle_len, budget)): the checks, the outputs and the launch the three share."""
+    pointer_constrained_exact (ahead = ("exact", cycle_len, budget)): the checks, the outputs and the launch the three share.
+    draw = (uniforms, row_id, temperature, top_k, top_p): pointer_constrained_sample, the same step with the draw in place of the
+    argmax, in the form `ahead` names."""
     _dev(logits, "logits")
     out = {}
     B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
@@ -646,6 +648,25 @@ def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, m
             raise ValueError("budget=%r: must be in 0..254" % (budget,))
         byte = torch.zeros(1, device=dev, dtype=torch.uint8)      # (L = 0: nothing of the tables is read)
         entry, tail = "ff_pointer_constrained_ahead", (_p(close_dist if L else byte), _p(cycle_len if L else byte), int(budget))
+    if draw is not None:
+        uniforms, row_id, temperature, top_k, top_p = draw
+        _dev(uniforms, "uniforms")
+        if uniforms.dim() != 1 or not uniforms.is_contiguous() or uniforms.numel() < 1:
+            raise ValueError("uniforms must be a contiguous non-empty 1-D tensor")
+        U = uniforms.numel()
+        t, k, pp = float(temperature), int(top_k), float(top_p)
+        if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
+            raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]")
+        if row_id is not None:
+            _dev(row_id, "row_id", torch.int32)
+            if row_id.dim() != 1 or row_id.numel() != B or (B and (int(row_id.min()) < 0 or int(row_id.max()) >= U)):
+                raise ValueError("row_id must hold one index in [0, %d) per row of logits" % U)
+            row_id = row_id.contiguous()
+        elif U < B:
+            raise ValueError("%d uniforms for %d rows" % (U, B))
+        form = {"ff_pointer_constrained": 0, "ff_pointer_constrained_ahead": 1, "ff_pointer_constrained_exact": 2}[entry]
+        tables = {0: (None, None, 0), 1: tail, 2: (None,) + tail}[form]      # (close_dist, cycle_len, budget)
+        entry, tail = "ff_pointer_constrained_sample", (_p(uniforms), U, _p(row_id), t, k, pp, form) + tuple(tables)
     _L.check(getattr(_L.load(), entry)(
         _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(fol), L, flags, ntok, lo, hi, _p(fin), _p(first),
         _p(prev), _p(vis), _p(out["mask_rows"]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(out["dead_end"]),
@@ -666,6 +687,24 @@ def pointer_constrained_ahead(logits, fin, first, prev, visited, flags, ntok, fo
 
 
 EXACT_MAX_KEYS = 2048      # (ff_pointer_constrained_exact: L + ntok)
+
+
+@_on_tensor_device
+def pointer_constrained_sample(logits, uniforms, fin, first, prev, visited, flags, ntok, follows=None, temperature=1.0, top_k=0,
+                               top_p=1.0, row_id=None, lookahead=None, close_dist=None, cycle_len=None, budget=0, memory=None,
+                               mask=None, kv_len=None, seqs_per_group=1, term_range=(1, 4), want_rows=False, want_stats=False,
+                               counter=None):
+    """One constrained sampling step of the pointer head (ff_pointer_constrained_sample): pointer_constrained's
+    byte row and state update -- lookahead None, "ahead" (pointer_constrained_ahead's, with close_dist / cycle_len / budget) or
+    "exact" (pointer_constrained_exact's, with cycle_len / budget) -- with pointer_sample's draw from the constrained masked row
+    in place of the argmax: uniforms [U] fp32, row b reads uniforms[row_id[b]] (None: b).  Returns pointer_constrained's dict;
+    logprob is (l[next] - max) - log sum exp(l - max) over the constrained row.  temperature=0 is pointer_constrained's step, bit
+    for bit; flags=0 is pointer_sample's."""
+    if lookahead not in (None, "ahead", "exact"):
+        raise ValueError("lookahead=%r: must be None, 'ahead' or 'exact'" % (lookahead,))
+    ahead = None if lookahead is None else (("ahead", close_dist, cycle_len, budget) if lookahead == "ahead" else ("exact", cycle_len, budget))
+    return _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
+                             want_rows, want_stats, counter, ahead, (uniforms, row_id, temperature, top_k, top_p))
 
 
 @_on_tensor_device

@@ -76,6 +76,8 @@ class SurfaceFormerBase(nn.Module):
                                        # post_process.enclosedness_tol); inputs["follow_table"] overrides the built table
         self.constrain_beams = 0       # ... W in 1..8 = the beam search over the constrained keys, W beams per anchor;
                                        # 0 = the constrained greedy decode; only with constrain
+        self.constrain_samples = 0     # ... R in 1..64 = R draws per anchor from the constrained keys under sample_temperature / sample_top_k /
+                                       # sample_top_p; 0 = the constrained greedy decode; only with constrain, not with constrain_beams
         self.constrain_lookahead = False   # ... with "loops": also mask every edge from which the loop cannot close within
                                        # max_face_length; inputs["close_dist"] / ["cycle_len"] override the built tables
         self.constrain_exact = False   # ... with "loops": the exact closure look-ahead -- while a loop is open, also mask
@@ -287,7 +289,10 @@ class SurfaceFormerBase(nn.Module):
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
         exact = getattr(self, "constrain_exact", False)         # (and this)
+        CS = _modes.constrain_samples_value(getattr(self, "constrain_samples", 0), CF if parallel else 0, CB)     # (and this)
         if not parallel:
+            if CS:
+                raise ValueError("constrain_samples is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
             if CB:
                 raise ValueError("constrain_beams is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
             if look:
@@ -303,7 +308,7 @@ class SurfaceFormerBase(nn.Module):
         EX = _modes.constrain_exact_value(exact, CF, CB, LA)
         if EX and not self.engine_supported():
             raise ValueError("constrain_exact needs the native engine: this model's constructor arguments take the sub-module loop")
-        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, LA, EX, constrain=CF,
+        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, LA, EX, CS, constrain=CF,
                                         num_samples=int(getattr(self, "num_samples", 0) or 0), beam_width=int(getattr(self, "beam_width", 0) or 0))
         if value is not None:
             attr = mode.switches[0].attr
@@ -320,6 +325,12 @@ class SurfaceFormerBase(nn.Module):
                 _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, constrain_beams=value, follow_table=True,
                                                                S=inputs["input"].size(1) + self.num_token),
                                      (int(self.token.face_type_offset), int(self.token.len)))
+            if mode is _modes.CONSTRAIN_SAMPLE:     # (the operands are made behind the encoder: the values and T are checked here)
+                _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, constrain_samples=value, follow_table=True, close_dist=True,
+                                                               cycle_len=True, constrain_lookahead=LA, constrain_exact=EX,
+                                                               temperature=self.sample_temperature, top_k=self.sample_top_k,
+                                                               top_p=self.sample_top_p, T=self.max_face_length),
+                                     (int(self.token.face_type_offset), int(self.token.len)))
             if mode is _modes.CONSTRAIN_AHEAD:      # (the tables are made behind the encoder: only T is checked here)
                 _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, follow_table=True, close_dist=True, cycle_len=True,
                                                                T=self.max_face_length),
@@ -327,6 +338,13 @@ class SurfaceFormerBase(nn.Module):
             if mode is _modes.CONSTRAIN_EXACT:      # (the table is made behind the encoder: only T is checked here)
                 _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, follow_table=True, cycle_len=True, T=self.max_face_length),
                                      (int(self.token.face_type_offset), int(self.token.len)))
+            if mode is _modes.CONSTRAIN_SAMPLE and inputs.get("sample_uniforms") is not None:      # (made behind the encoder otherwise)
+                ni = inputs["num_input"]
+                ni = [int(n) for n in (ni.tolist() if torch.is_tensor(ni) else ni)]
+                shape = (max(self.max_face_length - 1, 1), len(ni) * max(ni) * value)
+                if tuple(torch.as_tensor(inputs["sample_uniforms"]).shape) != shape:
+                    raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
+            if mode is _modes.CONSTRAIN_EXACT or (mode is _modes.CONSTRAIN_SAMPLE and EX):
                 L = inputs["input"].size(1)
                 if L + self.num_token > _modes.EXACT_MAX_KEYS:
                     raise ValueError("constrain_exact takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
@@ -347,6 +365,8 @@ class SurfaceFormerBase(nn.Module):
             for sw in mode.switches:
                 if not sw.scored and sw.on(self):
                     raise ValueError("score() excludes %s: set model.%s = %r to score given paths" % (sw.attr, sw.attr, sw.off))
+        if getattr(self, "constrain_samples", 0):     # (an option of constrain: without constrain the lines above have not raised)
+            raise ValueError("score() excludes constrain_samples: set model.constrain_samples = 0 to score given paths")
         if not self.engine_supported():
             raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
         eng, memory, mask, kv_len = self._encode(inputs)

@@ -62,7 +62,12 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         with constrain_beams): while a loop is open the constrained decode also masks every edge from which it
         cannot close within max_face_length through edges the row has not used, so a row can only dead-end right after the
         position that opened a loop.  cycle_len is built on the device (ops.follow_distance, hmax = max(T - 2, 1)) or taken from
-        inputs["cycle_len"] (uint8 N x L) for the batch AS GIVEN.  The published keys are constrain's."""
+        inputs["cycle_len"] (uint8 N x L) for the batch AS GIVEN.  The published keys are constrain's.
+        constrain_samples = R in 1..64 (default 0; only with constrain, not with constrain_beams): R independent draws
+        per anchor from the constrained row -- in the plain form, or with constrain_lookahead / constrain_exact in that form's
+        -- under sample_temperature / sample_top_k / sample_top_p, with the uniforms of num_samples (sample_seed, or
+        inputs["sample_uniforms"] [T-1, N*F*R]).  Also predict_samples and predict_sample_logprob N x F x R x T,
+        predict_sample_scores and predict_sample_dead_end N x F x R; predict, predict_logprob and predict_dead_end are draw 0."""
         label = inputs["label"]
         T = self.max_face_length
         mode, value = self._decode_mode(inputs, parallel=True)
@@ -119,7 +124,7 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         self.last_decode_stats = {"decoded_seqs": G * sum(min(F, n + 1) for n in num_input), "rows": N * F,
                                   "slot_rows": out["slot_rows"], "steps": out["steps"]}
         if mode.per_anchor:   # (G sequences per decoded anchor; `rows` stays the reference's N * F)
-            self.last_decode_stats[mode.subject if mode.subject == "constrain_beams" else mode.switches[0].attr] = G
+            self.last_decode_stats[mode.subject if mode.subject in ("constrain_beams", "constrain_samples") else mode.switches[0].attr] = G
         return inputs
 
     def _follow_table(self, inputs, device, num_input, order):

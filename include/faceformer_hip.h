@@ -1100,6 +1100,102 @@ int ff_decode_constrained_exact(const ff_model* m, const ff_decode_params* p,
                                 float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                                 void* workspace, size_t workspace_bytes, const ff_constrain_exact_params* exact, ff_stream_t stream);
 
+/* ---- sampling over the loop-constrained pointer decode (opt-in, parallel variant; entries added within ABI 105) ---
+ * ff_decode_sample draws R sequences per anchor from the padded row; ff_decode_constrained takes the argmax of the row the loop
+ * rule leaves.  These entries draw from THAT row: R diverse draws per anchor, each a closed chain of co-edges unless it is
+ * flagged, scored under the distribution it was drawn from.  Nothing of either rule changes.
+ *
+ * Layout.  The decode runs N*F*R sequences in the beam layout (the sampled decode's plan with R).  Draw k of anchor f of
+ * wireframe w is sequence (w*F + f)*R + k.  Every sequence carries its own rule state (visited, first, prev), its finished flag
+ * and its dead-end flag.  They start as the constrained decode starts them from the anchor's start token.  The R siblings are
+ * independent: nothing is reordered and no state is shared.
+ *
+ * One step, for one unfinished sequence.
+ *   1. The constraint byte row is ff_decode_constrained's, or ff_decode_constrained_ahead's / ff_decode_constrained_exact's with
+ *      the look-ahead forms.  It is a function of that sequence's own prefix.  On a dead end the terminators are re-opened and
+ *      dead_end is set.
+ *   2. l is the logit row masked by padding, kv_len and that byte row.
+ *   3. ff_decode_sample's selection rule is applied to l, unchanged: the live set A, tau, top-k, top-p, prefix sums in ascending
+ *      key order, c[s] > u*Z, and the last kept key when none crosses.
+ * Top-k and top-p therefore act on the constrained row.  On a dead end the draw is among the re-opened terminators, and the
+ * sequence ends there.
+ * A row with no live key gives token 0 and -log S, with no draw.  tau = 0 gives the argmax with the lowest index on ties.
+ * Uniforms are [T-1, N*F*R] fp32, keyed by the output row through row_id and clamped into [0, 1 - 2^-24].  There is no generator
+ * in device code.
+ *
+ * Log-probability.  (l[tok] - m) - log sum_s exp(l[s] - m) over the constrained row, saturated at -FLT_MAX.  This is the model's
+ * distribution renormalised over the keys the rule allows.  It is at tau = 1 and without top-k / top-p: ff_decode_constrained's
+ * evaluation at the drawn token, and ff_decode_sample's formula on the constrained row.  scores is its sum over the draw's own
+ * positions (fp64 accumulator, rounded once).
+ *
+ * Stop, finish, padding.  As in ff_decode_sample / ff_decode_constrained:
+ *   - A sequence is finished from the first terminator (column 0 included) or from a dead end.
+ *   - The decode stops after the first step at which no unfinished sequence selected a token >= ntok, else after T-1 steps.
+ *   - Outputs are zero after min(finish position, stop step).
+ *   - Padding-anchor groups are finished at 0, so FF_DEDUP_PAD_ANCHORS keeps working.
+ *
+ * Identities (all three are tests).
+ *   (a) tau = 0: every one of the R draws equals the constrained greedy decode of the same form.  Tokens and dead_end are equal,
+ *       steps is the same, and the log-probability is bit-equal at the operator.  Both launches compute -logf(lsum) from the same
+ *       reduction.
+ *   (b) Both flag bits clear (the C entries take 0, as ff_decode_constrained does): equals ff_decode_sample with the same
+ *       uniforms, token for token.  Log-probabilities are bit-equal on the same micro-batch plan.
+ *   (c) Draw k of an R-wide decode equals the R = 1 decode fed column k of the uniforms, on every pair decisive in both.
+ *
+ * ff_pointer_constrained_sample: one step of B sequences: ff_pointer_constrained's arguments, then ff_pointer_sample's
+ *   (uniforms [num_uniforms], row_id [B] or NULL, temperature, top_k, top_p), then the form: lookahead 0 (none), 1 (the closure
+ *   look-ahead: close_dist [wireframes, L, L], cycle_len [wireframes, L], budget in 0..254) or 2 (the exact one: cycle_len and
+ *   budget; flags must hold both bits, S <= 2048; close_dist is not read).  A finished row: token 0, log-probability 0, state
+ *   carried over, no draw.
+ * ff_decode_constrained_sample: the parallel decode; ff_decode's arguments, then ff_constrain_sample_params:
+ *   uniforms [T-1, N*F*num_samples] fp32 DEVICE; follows [N, L, ceil(L/32)] DEVICE (may be NULL when CONNECT is clear);
+ *   lookahead 0 / 1 / 2 with close_dist [N, L, L] / cycle_len [N, L] DEVICE as the form needs; the step that selects position p
+ *   runs with budget = T - 1 - p.
+ *   samples [N*F*num_samples, T] int64, logprob (same layout) fp32, scores [N*F*num_samples] fp32, dead_end [N*F*num_samples]
+ *   int32 (the draw ran into a dead end at a kept position).  predict [N*F, T], predict_logprob [N*F, T] (optional) and
+ *   predict_dead_end [N*F] (optional) receive draw 0 of every anchor.
+ *   trace_logits (optional) [T-1, N*F*num_samples, S], indexed by decoded sequence (seq_of_row): the CONSTRAINED masked row of
+ *   every sequence still unfinished before the step; a finished sequence's row holds the raw dot products.
+ * FF_ERR_ARG before any launch for everything ff_decode_constrained and ff_decode_sample reject, lookahead outside 0..2, and
+ * with a look-ahead what ff_decode_constrained_ahead / ff_decode_constrained_exact reject (T > 256; exact: a flag bit clear,
+ * L + ntok > 2048).  ff_decode_constrained_sample_workspace_bytes: ff_decode_sample_workspace_bytes' rules, with the constrained
+ * decode's records per sequence; row_id, the visited words and the byte rows are taken last.  The other decode entries launch and
+ * lay out what they did before these. */
+int ff_pointer_constrained_sample(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                  int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok, int term_lo,
+                                  int term_hi, const int* fin_in, const int* first_in, const int* prev_in, unsigned int* visited,
+                                  unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
+                                  int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
+                                  float* next_stats, int* count_ge, const float* uniforms, int num_uniforms, const int* row_id,
+                                  float temperature, int top_k, float top_p, int lookahead, const unsigned char* close_dist,
+                                  const unsigned char* cycle_len, int budget, ff_stream_t stream);
+typedef struct ff_constrain_sample_params {
+  int num_samples;
+  float temperature;
+  int top_k;
+  float top_p;
+  const float* uniforms;
+  int flags;
+  const unsigned int* follows;
+  int lookahead;
+  const unsigned char* close_dist;
+  const unsigned char* cycle_len;
+  int64_t* samples;
+  float* logprob;
+  float* scores;
+  int* dead_end;
+  float* predict_logprob;
+  int* predict_dead_end;
+} ff_constrain_sample_params;
+size_t ff_decode_constrained_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
+                                                    int num_samples);
+int ff_decode_constrained_sample(const ff_model* m, const ff_decode_params* p,
+                                 const float* memory, const unsigned char* mask, const int* kv_len,
+                                 const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                                 int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                                 float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                                 void* workspace, size_t workspace_bytes, const ff_constrain_sample_params* sample, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,7 +106,7 @@ def score_batch(model, batch):
 
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
-              constrained_beams=None):
+              constrained_beams=None, constrained_samples=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -124,7 +124,11 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     whose face does not pass the enclosure walk (dead ends, and loops still open at the last position).
     constrained_beams (--constrain-beams; (tokens [F, W, T], scores [F, W], dead-end flags [F, W]) of this sample): the record
     also gets `pred_beam_faces` and `pred_beam_face_scores` as under --beam, over the beams that did not run into a dead end;
-    `pred_faces`, `pred_dead_ends` and `pred_unclosed` stay what beam 0 (pred, dead_end) gives."""
+    `pred_faces`, `pred_dead_ends` and `pred_unclosed` stay what beam 0 (pred, dead_end) gives.
+    constrained_samples (--constrain-samples; (tokens [F, R, T], scores [F, R], dead-end flags [F, R]) of this sample): the record
+    also gets `pred_sample_faces`, `pred_sample_face_scores` and `pred_sample_face_votes` as under --sample, over the draws that
+    did not run into a dead end; `pred_faces` stays what draw 0 (pred) gives, and `pred_dead_ends` / `pred_unclosed` are counted
+    over ALL draws of the wireframe's own anchors."""
     scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
@@ -180,6 +184,19 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
         rec["pred_beam_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
         rec["pred_beam_face_scores"] = [s for _, _, s, _ in ranked]
+    if constrained_samples is not None:
+        n = int(item["num_input"])
+        toks, scs, dead = (np.asarray(v[:n]) for v in constrained_samples)
+        sf = FZ.parse_parallel_constrained_samples_scored(toks, scs, dead, len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(sf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_sample_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_sample_face_scores"] = [s for _, _, s, _ in ranked]
+        rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
+        draws = FZ.apply_own_stop_rule(toks.reshape(-1, toks.shape[-1]), cfg.model.token, parallel)
+        own = [f for i in range(len(draws)) for f in FZ._parallel_rows(draws[i:i + 1], cfg.model.token, len(raw["edges"]))]
+        rec["pred_dead_ends"] = int(dead.astype(bool).sum())
+        rec["pred_unclosed"] = sum(1 for _, idx in own
+                                   if not FZ.is_face_enclosed(raw["edges"], idx, cfg.post_process.enclosedness_tol))
     if samples is not None:
         n = int(item["num_input"])
         sf = FZ.parse_parallel_samples_scored(samples[0][:n], samples[1][:n], len(raw["edges"]), cfg.model.token)
@@ -191,14 +208,16 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
 
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
-                    seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False):
+                    seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
+                    constrain_samples=0):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
     under temperature / top_k / top_p from the seeded generator (num_samples), the loop-constrained greedy decode
     (constrain "no_repeat" / "loops" with the end-point tolerance constrain_tol), the beam search over its keys
     with `constrain_beams` beams per anchor, the closure look-ahead of "loops" (constrain_lookahead), its exact form
-    (constrain_exact).
+    (constrain_exact), `constrain_samples` draws per anchor from the constrained keys under temperature / top_k /
+    top_p / seed.
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -222,12 +241,17 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.constrain_lookahead = True
     if constrain_exact:
         model.constrain_exact = True
+    if constrain_samples:
+        model.constrain_samples = int(constrain_samples)
+        model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
+        model.sample_seed = int(seed)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
-             top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False):
+             top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
+             constrain_samples=0):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -238,7 +262,19 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     runs only) decodes W constrained beams per anchor and adds pred_beam_faces / pred_beam_face_scores; constrain_lookahead (only
     with constrain "loops", not with constrain_beams, single-rank runs only) also masks the edges from which a loop cannot close
     in time -- the record keys stay constrain's; constrain_exact (only with constrain "loops", not with constrain_lookahead or
-    constrain_beams, single-rank runs only) is the exact form of that look-ahead, with the same record keys."""
+    constrain_beams, single-rank runs only) is the exact form of that look-ahead, with the same record keys; constrain_samples = R
+    (1..64, only with constrain, not with constrain_beams, single-rank runs only; with constrain_lookahead or constrain_exact in
+    that form) draws R loops per anchor from the constrained keys under temperature / top_k / top_p / seed and adds
+    pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes, with pred_dead_ends / pred_unclosed over all draws."""
+    if constrain_samples:
+        if not constrain:
+            raise ValueError("--constrain-samples requires --constrain")
+        if isinstance(constrain_samples, bool) or not isinstance(constrain_samples, int) or not 1 <= constrain_samples <= 64:
+            raise ValueError("--constrain-samples must be a count in 1..64")
+        if constrain_beams:
+            raise ValueError("--constrain-samples is not implemented with --constrain-beams")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--constrain-samples is not implemented for multi-rank runs")
     if constrain_exact:
         if constrain != "loops":
             raise ValueError("--constrain-exact requires --constrain loops")
@@ -272,7 +308,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         model.load_state_dict(sd)
         model = model.eval().to(device)
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
-                    cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact)
+                    cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact,
+                    constrain_samples)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -288,6 +325,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     wanted = [gain for flag, *_, gain in CLI_FLAGS if given[flag] and gain]
     if constrain_beams:
         wanted.append(("constrained_beams", ("predict_beams", "predict_beam_scores", "predict_beam_dead_end")))
+    if constrain_samples:
+        wanted.append(("constrained_samples", ("predict_samples", "predict_sample_scores", "predict_sample_dead_end")))
     for b0 in range(lo, hi, batch_size):
         idx = list(range(b0, min(hi, b0 + batch_size)))
         items = [ds[i] for i in idx]
@@ -383,6 +422,13 @@ def build_parser():
                              "never an edge from which it cannot close in time through edges the row has not used, so a row can "
                              "only dead-end right after the edge that opened a loop; same record keys; single-process runs only, "
                              "not with --constrain-lookahead or --constrain-beams")
+    parser.add_argument("--constrain-samples", type=int, default=0, metavar="R",
+                        help="with --constrain: R (1..64) independent draws per anchor edge from the constrained keys under "
+                             "--temperature / --top-k / --top-p / --seed (DESIGN.md 26), in the plain form or with "
+                             "--constrain-lookahead / --constrain-exact in that form; pred_faces come from draw 0, every JSON record "
+                             "gains pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes over the draws that did not "
+                             "run into a dead end, and pred_dead_ends / pred_unclosed count all draws; single-process runs only, not "
+                             "with --constrain-beams")
     return parser
 
 
@@ -404,7 +450,8 @@ def main(argv=None):
              retire_finished=args.retire_finished, fp16=args.fp16, scores=args.scores, beam=args.beam,
              score_labels=args.score_labels, sample=args.sample, temperature=args.temperature, top_k=args.top_k,
              top_p=args.top_p, seed=args.seed, constrain=args.constrain, constrain_beams=args.constrain_beams,
-             constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact)
+             constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact,
+             constrain_samples=args.constrain_samples)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
