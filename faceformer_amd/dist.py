@@ -209,6 +209,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
     stop_each_eos: single-sequence model only -- None = the module's own `stop_each_eos`; True / False = this call's rule,
         passed down as an argument (the module attribute is NOT touched: other host threads may be decoding with the model)."""
     from .models import SurfaceFormer_Parallel
+    if getattr(model, "extract_faces", False):
+        raise ValueError("decode_sharded does not implement extract_faces (the faces of a wireframe are made on the rank that decoded it)")
     if getattr(model, "constrain_lookahead", False):     # (an option of constrain, which is not taken here either)
         raise ValueError("decode_sharded does not implement constrain_lookahead (%s)" % _modes.SWITCH["constrain"].sharded)
     if getattr(model, "constrain_exact", False):

@@ -24,7 +24,8 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "is_face_enclosed", "filter_faces_by_encloseness", "map_coedge_into_edges",
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
-           "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance"]
+           "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance",
+           "face_rows", "face_votes", "faces_of_rows"]
 
 
 def _tok(token, name, default):
@@ -545,6 +546,206 @@ def postprocess_faces(faces, edges, pairings, tol):
     closed = filter_faces_by_encloseness(edges, faces, tol)
     return [(ftype, map_coedge_into_edges(pairings, [i for loop in loops for i in loop]))
             for ftype, loops in closed]
+
+
+# ---- face extraction as arrays: the numpy restatements of ff_face_rows / ff_face_votes ----------------------------
+# The same arguments, keys, dtypes and bits as ops.face_rows / ops.face_votes; faces_of_rows turns the arrays of one wireframe
+# back into the list forms above, which makes the whole contract testable on the CPU.
+FACE_MAX_T = 256
+FACE_MAX_ROWS = 65536
+
+
+def _face_tokens4(tokens):
+    t = np.asarray(tokens, dtype=np.int64)
+    if t.ndim == 3:
+        t = t[:, :, None, :]
+    if t.ndim != 4:
+        raise ValueError("tokens must be [N, F, T] or [N, F, G, T]")
+    if not 1 <= t.shape[3] <= FACE_MAX_T:
+        raise ValueError("tokens hold T=%d positions: 1..%d are taken" % (t.shape[3], FACE_MAX_T))
+    return t
+
+
+def face_rows(tokens, num_input, token, num_edges=None, scores=None, logprob=None, dead_end=None, own_stop=False, follows=None,
+              edge_map=None, num_lines=None):
+    """ff_face_rows in numpy (include/faceformer_hip.h states the rule): every row of tokens [N, F, G, T] (or [N, F, T]: G = 1)
+    parsed as `_parallel_rows` parses it, walked as is_face_enclosed walks it on the packed follow table `follows`
+    [N, L, ceil(L/32)] int32, ordered as filter_faces_by_encloseness orders it, and keyed by the bitmap of its (mapped) edge set.
+    num_input [N]; num_edges [N] or None (= num_input), clamped into [0, L]; scores [N, F, G] or logprob [N, F, G, T] (not both);
+    dead_end [N, F, G]; own_stop: apply_own_stop_rule over every wireframe's own rows; edge_map [N, L] int32 or None.
+    L = the table's / the map's, else num_lines, else F.  Returns dict of arrays: len, type, closed, loops [N, F, G] int32; edges,
+    loop_of [N, F, G, T] int32 (-1 behind len); set_bits [N, F, G, ceil(L/32)] int32 (the uint32 words); score [N, F, G] float64."""
+    t = _face_tokens4(tokens)
+    N, F, G, T = t.shape
+    off, ntok = _tok(token, "face_type_offset", 1), _tok(token, "len", 4)
+    if not 0 <= off < ntok:
+        raise ValueError("face_type_offset=%d must be in [0, len=%d)" % (off, ntok))
+    if scores is not None and logprob is not None:
+        raise ValueError("scores and logprob may not both be given")
+    ni = np.asarray(num_input, dtype=np.int64).reshape(N)
+    fol = None if follows is None else np.asarray(follows).view(np.uint32) if np.asarray(follows).dtype == np.int32 else np.asarray(follows, dtype=np.uint32)
+    emap = None if edge_map is None else np.asarray(edge_map, dtype=np.int64)
+    L = fol.shape[1] if fol is not None else emap.shape[1] if emap is not None else F if num_lines is None else int(num_lines)
+    fw = (L + 31) // 32
+    if fol is not None and fol.shape != (N, L, fw):
+        raise ValueError("follows must be [N, L, ceil(L/32)]")
+    if emap is not None and emap.shape != (N, L):
+        raise ValueError("edge_map must be [N, L]")
+    ne = np.clip(ni if num_edges is None else np.asarray(num_edges, dtype=np.int64).reshape(N), 0, L)
+    sc = None if scores is None else np.asarray(scores, dtype=np.float32).reshape(N, F, G)
+    lp = None if logprob is None else np.asarray(logprob, dtype=np.float32).reshape(N, F, G, T)
+    de = None if dead_end is None else np.asarray(dead_end).reshape(N, F, G)
+    out = {"len": np.zeros((N, F, G), np.int32), "type": np.zeros((N, F, G), np.int32),
+           "closed": np.full((N, F, G), 0 if fol is not None else -1, np.int32), "loops": np.zeros((N, F, G), np.int32),
+           "edges": np.full((N, F, G, T), -1, np.int32), "loop_of": np.full((N, F, G, T), -1, np.int32),
+           "set_bits": np.zeros((N, F, G, fw), np.uint32), "score": np.zeros((N, F, G), np.float64)}
+
+    def bit(w, a, b):
+        return bool((int(fol[w, a, b >> 5]) >> (b & 31)) & 1)
+
+    for w in range(N):
+        stop = T - 1
+        if own_stop:
+            own = t[w, :max(0, min(int(ni[w]), F))].reshape(-1, T)
+            for j in range(1, T):
+                if (own[:, j] < ntok).all():
+                    stop = j
+                    break
+        for f in range(min(F, max(int(ni[w]), 0))):
+            for g in range(G):
+                if sc is not None and sc[w, f, g] == -np.inf:
+                    continue
+                if de is not None and de[w, f, g] != 0:
+                    continue
+                row = t[w, f, g].copy()
+                row[stop + 1:] = 0
+                hit = np.flatnonzero((row >= off) & (row < ntok))
+                fin = int(hit[0]) if hit.size else T - 1
+                v = row[: fin + 1] - ntok
+                e = [int(x) for x in v[(v >= 0) & (v < ne[w])]]
+                if not e:
+                    continue
+                n = len(e)
+                out["len"][w, f, g] = n
+                out["type"][w, f, g] = np.int64(row[fin] - off).astype(np.int32)
+                if sc is not None:
+                    out["score"][w, f, g] = np.float64(sc[w, f, g])
+                elif lp is not None:
+                    terms = lp[w, f, g].astype(np.float64)
+                    terms[stop + 1:] = 0.0
+                    out["score"][w, f, g] = np.cumsum(np.concatenate(([0.0], terms[1: fin + 1])))[-1]     # (0 + x1 + x2 + ..., one by one)
+                order, loop_of = e, [-1] * n
+                if fol is not None:
+                    loops, start, ok = [], None, True
+                    for i, x in enumerate(e):
+                        if start is None:
+                            start = i
+                        elif not bit(w, e[i - 1], x):
+                            ok = False
+                            break
+                        if bit(w, x, e[start]):
+                            loops.append(e[start: i + 1])
+                            start = None
+                    ok = ok and start is None
+                    out["closed"][w, f, g] = int(ok)
+                    if ok:
+                        out["loops"][w, f, g] = len(loops)
+                        rolled = []
+                        for lo in loops:
+                            m = lo.index(min(lo))
+                            rolled.append(lo[m:] + lo[:m])
+                        rolled.sort(key=lambda lo: lo[0])                     # (stable)
+                        order = [x for lo in rolled for x in lo]
+                        loop_of = [k for k, lo in enumerate(rolled) for _ in lo]
+                out["edges"][w, f, g, :n] = order
+                out["loop_of"][w, f, g, :n] = loop_of
+                for x in e:
+                    m = int(emap[w, x]) if emap is not None else x
+                    if not 0 <= m < L:
+                        m = x
+                    out["set_bits"][w, f, g, m >> 5] |= np.uint32(1 << (m & 31))
+    out["set_bits"] = out["set_bits"].view(np.int32)
+    return out
+
+
+def _score_order(v):
+    """float64 -> uint64 keys of ff_face_votes' total order (-0 below +0)."""
+    b = np.asarray(v, dtype=np.float64).view(np.uint64)
+    return np.where(b >> np.uint64(63), ~b, b | np.uint64(1 << 63))
+
+
+def face_votes(rows, require_closed=False):
+    """ff_face_votes in numpy: the rows of every wireframe grouped by their set_bits row.  rows: face_rows' dict.  A row takes part
+    iff len > 0 and, with require_closed, closed == 1.  Returns dict: rep [N, F, G] int32 (the least row f*G + g of the wireframe
+    with the same bitmap; -1: takes no part); for rep == own row: votes (group size), best (float64 highest score), major (most
+    frequent type, on a tie the one whose first row is the lowest: Counter.most_common), 0 elsewhere; num_faces [N] int32."""
+    ln = np.asarray(rows["len"])
+    N, F, G = ln.shape
+    R = F * G
+    if R > FACE_MAX_ROWS:
+        raise ValueError("face_votes takes at most %d rows per wireframe (got %d)" % (FACE_MAX_ROWS, R))
+    bits = np.asarray(rows["set_bits"]).reshape(N, R, -1)
+    ty, cl = np.asarray(rows["type"]).reshape(N, R), np.asarray(rows["closed"]).reshape(N, R)
+    sc = np.asarray(rows["score"], dtype=np.float64).reshape(N, R)
+    ln = ln.reshape(N, R)
+    rep = np.full((N, R), -1, np.int32)
+    votes, major = np.zeros((N, R), np.int32), np.zeros((N, R), np.int32)
+    best = np.zeros((N, R), np.float64)
+    num = np.zeros(N, np.int32)
+    for w in range(N):
+        groups = {}
+        for r in range(R):
+            if ln[w, r] > 0 and (not require_closed or cl[w, r] == 1):
+                groups.setdefault(bits[w, r].tobytes(), []).append(r)
+        num[w] = len(groups)
+        for members in groups.values():
+            p = members[0]
+            rep[w, members] = p
+            votes[w, p] = len(members)
+            s = sc[w, members]
+            best[w, p] = s[int(np.argmax(_score_order(s)))]
+            major[w, p] = Counter(int(ty[w, r]) for r in members).most_common(1)[0][0]
+    shape = (N, F, G)
+    return {"rep": rep.reshape(shape), "votes": votes.reshape(shape), "best": best.reshape(shape), "major": major.reshape(shape),
+            "num_faces": num}
+
+
+def faces_of_rows(rows, votes, w):
+    """The arrays of wireframe w (face_rows' and face_votes' dicts, numpy or anything np.asarray takes) as the list forms:
+    `parsed` [(type, (edge, ...))] in row order, the edges in decode order for an open or unwalked face and in canonical order
+    for a closed one; `scored` [(type, edges, score)] beside it; `enclosed` [(type, ((edge, ...), ...))], the closed faces as
+    filter_faces_by_encloseness returns them; `unique` [(major, sorted edge set, best, votes)] in first-seen order -- the edge
+    set is read back from the bitmap, so with an edge_map it holds the mapped edges.  votes may be None (no `unique`)."""
+    ln = np.asarray(rows["len"])[w].reshape(-1)
+    R = ln.size
+    ty = np.asarray(rows["type"])[w].reshape(-1)
+    cl = np.asarray(rows["closed"])[w].reshape(-1)
+    sc = np.asarray(rows["score"])[w].reshape(-1)
+    ed = np.asarray(rows["edges"])[w].reshape(R, -1)
+    lo = np.asarray(rows["loop_of"])[w].reshape(R, -1)
+    parsed, scored, enclosed = [], [], []
+    for r in range(R):
+        n = int(ln[r])
+        if n == 0:
+            continue
+        e = tuple(int(x) for x in ed[r, :n])
+        parsed.append((int(ty[r]), e))
+        scored.append((int(ty[r]), e, float(sc[r])))
+        if cl[r] == 1:
+            k = lo[r, :n]
+            enclosed.append((int(ty[r]), tuple(tuple(int(x) for x in ed[r, :n][k == i]) for i in range(int(k.max()) + 1))))
+    out = {"parsed": parsed, "scored": scored, "enclosed": enclosed}
+    if votes is not None:
+        bits = np.asarray(rows["set_bits"])[w].reshape(R, -1).view(np.uint32)
+        rep = np.asarray(votes["rep"])[w].reshape(-1)
+        vt, bs, mj = (np.asarray(votes[k])[w].reshape(-1) for k in ("votes", "best", "major"))
+        unique = []
+        for r in np.flatnonzero(rep == np.arange(R)):
+            word = bits[r]
+            key = tuple(int(32 * x + b) for x in range(word.size) for b in range(32) if (int(word[x]) >> b) & 1)
+            unique.append((int(mj[r]), key, float(bs[r]), int(vt[r])))
+        out["unique"] = unique
+    return out
 
 
 # ---- JSON record -------------------------------------------------------------------------------------

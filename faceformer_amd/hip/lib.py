@@ -181,6 +181,10 @@ class ConstrainSampleParams(C.Structure):
 
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
+FF_FACE_OWN_STOP = 1          # ff_face_rows
+FF_FACE_REQUIRE_CLOSED = 1    # ff_face_votes
+FF_FACE_MAX_T = 256
+FF_FACE_MAX_ROWS = 65536
 
 # ff_stop_fn: int (*)(void* user, const int* step_counts, int num_steps)
 STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int)
@@ -325,6 +329,11 @@ SIGNATURES = {
                                                fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                                C.c_size_t, C.POINTER(ConstrainSampleParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
+    "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
+                               fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
+    "ff_face_votes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ff_face_votes": (C.c_int, [fptr, fptr, fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr,
+                                C.c_size_t, fptr]),
 }
 
 _lib = None
@@ -355,7 +364,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance and *_exact ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact and ff_face_* ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

@@ -746,6 +746,121 @@ def follow_distance(follows, num_input, hmax):
     return close_dist, cycle_len
 
 
+FACE_ROW_KEYS = ("len", "type", "closed", "loops", "edges", "loop_of", "set_bits", "score")
+FACE_VOTE_KEYS = ("rep", "votes", "best", "major", "num_faces")
+
+
+def _tok_field(token, name):
+    try:
+        return int(getattr(token, name))
+    except AttributeError:
+        return int(token[name])
+
+
+@_on_tensor_device
+def face_rows(tokens, num_input, token, num_edges=None, scores=None, logprob=None, dead_end=None, own_stop=False, follows=None,
+              edge_map=None, num_lines=None):
+    """The faces of decoded rows, on the device (ff_face_rows; include/faceformer_hip.h states the rule).  tokens
+    [N, F, G, T] int64 (or [N, F, T]: G = 1), T <= 256; num_input [N] int32; token: the config's (face_type_offset, len);
+    num_edges [N] int32 or None (= num_input); scores [N, F, G] fp32 or logprob [N, F, G, T] fp32 (not both); dead_end [N, F, G]
+    int32; own_stop: every wireframe's own stop rule first; follows [N, L, ceil(L/32)] int32 (ops.follow_table) or None: no walk;
+    edge_map [N, L] int32 or None.  L = the table's / the map's, else num_lines, else F.  Returns a dict of device tensors: len,
+    type, closed, loops [N, F, G] int32; edges, loop_of [N, F, G, T] int32; set_bits [N, F, G, ceil(L/32)] int32; score [N, F, G]
+    fp64.  faces.face_rows is the numpy restatement, bit for bit."""
+    if not torch.is_tensor(tokens) or tokens.dim() not in (3, 4):
+        raise ValueError("tokens must be a tensor [N, F, T] or [N, F, G, T]")
+    if tokens.dim() == 3:
+        tokens = tokens.unsqueeze(2)
+    N, F, G, T = tokens.shape
+    if not 1 <= T <= _L.FF_FACE_MAX_T:
+        raise ValueError("face_rows takes 1..%d positions per row (got T=%d)" % (_L.FF_FACE_MAX_T, T))
+    off, ntok = _tok_field(token, "face_type_offset"), _tok_field(token, "len")
+    if not 0 <= off < ntok:
+        raise ValueError("face_type_offset=%d must be in [0, len=%d)" % (off, ntok))
+    if scores is not None and logprob is not None:
+        raise ValueError("scores and logprob may not both be given")
+    _dev(tokens, "tokens", torch.int64), _dev(num_input, "num_input", torch.int32)
+    if num_input.dim() != 1 or num_input.numel() != N:
+        raise ValueError("num_input must hold one count per wireframe")
+    if num_edges is not None:
+        _dev(num_edges, "num_edges", torch.int32)
+        if num_edges.dim() != 1 or num_edges.numel() != N:
+            raise ValueError("num_edges must hold one count per wireframe")
+    for t, name, dtype, shape in ((scores, "scores", torch.float32, (N, F, G)), (logprob, "logprob", torch.float32, (N, F, G, T)),
+                                  (dead_end, "dead_end", torch.int32, (N, F, G))):
+        if t is not None:
+            _dev(t, name, dtype)
+            if t.numel() != N * F * G * (T if len(shape) == 4 else 1) or (t.dim() == len(shape) and tuple(t.shape) != shape):
+                raise ValueError("%s must be [%s]" % (name, ", ".join(str(v) for v in shape)))
+    if follows is not None:
+        _dev(follows, "follows", torch.int32)
+        if follows.dim() != 3 or follows.size(0) != N or follows.size(2) != (follows.size(1) + 31) // 32:
+            raise ValueError("follows must be [N, L, ceil(L/32)]")
+    L = follows.size(1) if follows is not None else edge_map.size(1) if torch.is_tensor(edge_map) and edge_map.dim() == 2 else \
+        F if num_lines is None else int(num_lines)
+    if edge_map is not None:
+        _dev(edge_map, "edge_map", torch.int32)
+        if tuple(edge_map.shape) != (N, L):
+            raise ValueError("edge_map must be [N, L] = [%d, %d]" % (N, L))
+    if L < 0:
+        raise ValueError("num_lines must be >= 0")
+    fw = (L + 31) // 32
+    c = lambda t: None if t is None else t.contiguous()
+    tokens, num_input, num_edges, scores, logprob, dead_end, follows, edge_map = (
+        c(t) for t in (tokens, num_input, num_edges, scores, logprob, dead_end, follows, edge_map))
+    dev = tokens.device
+    out = {k: torch.empty((N, F, G), device=dev, dtype=torch.int32) for k in ("len", "type", "closed", "loops")}
+    out["edges"] = torch.empty((N, F, G, T), device=dev, dtype=torch.int32)
+    out["loop_of"] = torch.empty((N, F, G, T), device=dev, dtype=torch.int32)
+    out["set_bits"] = torch.empty((N, F, G, fw), device=dev, dtype=torch.int32)
+    out["score"] = torch.empty((N, F, G), device=dev, dtype=torch.float64)
+    _L.check(_L.load().ff_face_rows(_p(tokens), N, F, G, T, _p(num_input), _p(num_edges), L, off, ntok, _p(scores), _p(logprob),
+                                    _p(dead_end), _p(follows), _p(edge_map), _L.FF_FACE_OWN_STOP if own_stop else 0,
+                                    *[_p(out[k]) for k in FACE_ROW_KEYS], _stream()), "ff_face_rows")
+    return out
+
+
+@_on_tensor_device
+def _face_votes(set_bits, ln, ty, closed, score, require_closed):
+    N, F, G = ln.shape
+    R = F * G
+    dev = ln.device
+    out = {k: torch.empty((N, F, G), device=dev, dtype=torch.int32) for k in ("rep", "votes", "major")}
+    out["best"] = torch.empty((N, F, G), device=dev, dtype=torch.float64)
+    out["num_faces"] = torch.empty((N,), device=dev, dtype=torch.int32)
+    lib = _L.load()
+    nbytes = lib.ff_face_votes_workspace_bytes(N, R)
+    ws = torch.empty(((nbytes + 7) // 8,), device=dev, dtype=torch.int64)
+    _L.check(lib.ff_face_votes(_p(set_bits), _p(ln), _p(ty), _p(closed), _p(score), N, R, set_bits.size(-1),
+                               _L.FF_FACE_REQUIRE_CLOSED if require_closed else 0, *[_p(out[k]) for k in FACE_VOTE_KEYS],
+                               _p(ws), ws.numel() * 8, _stream()), "ff_face_votes")
+    return out
+
+
+def face_votes(rows, require_closed=False):
+    """The de-duplicated faces of every wireframe, on the device (ff_face_votes).  rows: face_rows' dict (set_bits,
+    len, type, closed, score are read).  A row takes part iff len > 0 and, with require_closed, closed == 1.  Returns a dict of
+    device tensors: rep [N, F, G] int32 (the least row f*G + g of the wireframe with the same bitmap, -1: takes no part); votes,
+    best (fp64), major at the rows with rep == own index, 0 elsewhere; num_faces [N] int32.  At most 65536 rows per wireframe.
+    faces.face_votes is the numpy restatement, bit for bit."""
+    try:
+        set_bits, ln, ty, closed, score = (rows[k] for k in ("set_bits", "len", "type", "closed", "score"))
+    except (KeyError, TypeError):
+        raise ValueError("face_votes takes the dict face_rows returns")
+    if not torch.is_tensor(ln) or ln.dim() != 3:
+        raise ValueError("rows['len'] must be a tensor [N, F, G]")
+    N, F, G = ln.shape
+    if F * G > _L.FF_FACE_MAX_ROWS:
+        raise ValueError("face_votes takes at most %d rows per wireframe (got %d)" % (_L.FF_FACE_MAX_ROWS, F * G))
+    for t, name, dtype in ((set_bits, "set_bits", torch.int32), (ln, "len", torch.int32), (ty, "type", torch.int32),
+                           (closed, "closed", torch.int32), (score, "score", torch.float64)):
+        _dev(t, "rows['%s']" % name, dtype)
+        if tuple(t.shape[:3]) != (N, F, G) or t.dim() != (4 if name == "set_bits" else 3):
+            raise ValueError("rows['%s'] must be [N, F, G%s]" % (name, ", words" if name == "set_bits" else ""))
+    return _face_votes(set_bits.contiguous(), ln.contiguous(), ty.contiguous(), closed.contiguous(), score.contiguous(),
+                       bool(require_closed))
+
+
 @_on_tensor_device
 def beam_constrained_select(logits, scores, fin, dead, first, prev, visited, width, flags, ntok, follows=None, memory=None,
                             mask=None, kv_len=None, groups_per_wireframe=None, term_range=(1, 4), want_rows=False, want_stats=False,

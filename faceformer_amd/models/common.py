@@ -83,6 +83,10 @@ class SurfaceFormerBase(nn.Module):
         self.constrain_exact = False   # ... with "loops": the exact closure look-ahead -- while a loop is open, also mask
                                        # every edge from which it cannot close within max_face_length through edges the row has
                                        # not used; contains constrain_lookahead; inputs["cycle_len"] overrides the built table
+        self.extract_faces = False     # parallel model: "parse" / "enclosed" = the decoded rows also leave as faces, on the device
+                                       # (inputs["faces"]: ops.face_rows + ops.face_votes behind the decode);
+                                       # "enclosed" walks the enclosure rule on the follow table (constrain_tol) and counts
+                                       # closed faces only; inputs["edge_map"] (int32 N x L) maps edges before the grouping
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
         self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
         self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
@@ -281,10 +285,30 @@ class SurfaceFormerBase(nn.Module):
         pad = torch.zeros((extra.size(0), self.num_token), dtype=torch.bool, device=extra.device)
         return torch.cat([pad, extra.to(torch.bool)], dim=1).to(torch.uint8).contiguous()
 
+    def _extract_faces_value(self, inputs, parallel):
+        """extract_faces as None / "parse" / "enclosed", after its rules (ValueError, before anything is launched): a
+        SurfaceFormer_Parallel option of the native engine; inputs["edge_map"], when given, is int32 N x L."""
+        ef = getattr(self, "extract_faces", False)
+        if ef is False or ef is None:
+            return None
+        if ef not in ("parse", "enclosed") or not isinstance(ef, str):
+            raise ValueError("extract_faces=%r: must be False, 'parse' or 'enclosed'" % (ef,))
+        if not parallel:
+            raise ValueError("extract_faces is a SurfaceFormer_Parallel option (the single-sequence model's faces are split at SEP)")
+        if not self.engine_supported():
+            raise ValueError("extract_faces needs the native engine: this model's constructor arguments take the sub-module loop")
+        em = inputs.get("edge_map")
+        if em is not None:
+            x = inputs["input"]
+            if not torch.is_tensor(em) or em.dtype != torch.int32 or tuple(em.shape) != (x.size(0), x.size(1)):
+                raise ValueError("edge_map must be an int32 tensor of shape [%d, %d]" % (x.size(0), x.size(1)))
+        return ef
+
     def _decode_mode(self, inputs, parallel):
         """(record, value) of the mode this model's attributes select (hip/modes.py: the first of MODES switched on; value: beam
         width / number of samples / constraint flag bits, None for greedy), after the rules only the model can check: what the
         single-sequence model does not take; an opt-in mode needs the native engine and excludes what its record lists."""
+        self._extract_faces_value(inputs, parallel)
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)

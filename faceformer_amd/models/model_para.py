@@ -67,10 +67,15 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         per anchor from the constrained row -- in the plain form, or with constrain_lookahead / constrain_exact in that form's
         -- under sample_temperature / sample_top_k / sample_top_p, with the uniforms of num_samples (sample_seed, or
         inputs["sample_uniforms"] [T-1, N*F*R]).  Also predict_samples and predict_sample_logprob N x F x R x T,
-        predict_sample_scores and predict_sample_dead_end N x F x R; predict, predict_logprob and predict_dead_end are draw 0."""
+        predict_sample_scores and predict_sample_dead_end N x F x R; predict, predict_logprob and predict_dead_end are draw 0.
+        extract_faces = "parse" / "enclosed" (default False): also inputs["faces"], a dict of device tensors -- len,
+        type, closed, loops, score, rep, votes, best, major N x F x G, edges, loop_of N x F x G x T, set_bits N x F x G x
+        ceil(L/32), num_faces N -- made by two launches behind the decode from the rows it published (G = the beam width, the
+        number of draws, or 1); faces.faces_of_rows turns one wireframe's arrays into the list forms."""
         label = inputs["label"]
         T = self.max_face_length
         mode, value = self._decode_mode(inputs, parallel=True)
+        extract = self._extract_faces_value(inputs, parallel=True)
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             inputs = self._forward_eval_modules(inputs, parallel=True)
             if self.retire_finished:         # (that loop decodes every sequence; the result is the same function of its tokens)
@@ -103,13 +108,14 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         eng = self.engine()
         staged = eng.stage_num_input(ni)       # (before the encoder is enqueued: see stage_num_input)
         eng, memory, mask, kv_len = self._encode(sub, eng)
+        prepared = mode.prepare(self, value, inputs, memory.device, T, N, F, num_input, order)
         out = eng.decode(memory, mask, kv_len, _L.FF_PARALLEL, T=T, F=F, num_input=ni, staged_num_input=staged,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs,
                          num_streams=self.num_streams, sync_every=self.sync_every,
                          flags=self.decode_flags, x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, extra_mask=extra,
                          retire=self.retire_finished, term_range=(int(self.token.face_type_offset), int(self.token.len)),
-                         logprob=want_lp, **mode.prepare(self, value, inputs, memory.device, T, N, F, num_input, order))
+                         logprob=want_lp, **prepared)
         # predict and the mode's outputs (predict is beam 0 / sample 0 of every anchor: a fair draw, not a selected one), N x F x ...
         G = value if mode.per_anchor else 1
         views = [("predict", out["predict"].view(N, F, T))]
@@ -121,11 +127,40 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         inputs.update(views)
         if "predict_beam_dead_end" in inputs:     # (constrain_beams: the constrained decode's key, for beam 0)
             inputs["predict_dead_end"] = inputs["predict_beam_dead_end"][:, :, 0]
+        if extract:
+            table = prepared.get("follow_table") if extract == "enclosed" else None
+            if table is not None and order is not None:      # (made in the decode's wireframe order: back into the batch's)
+                table = table.index_select(0, inv)
+            inputs["faces"] = self._faces_of_decode(inputs, extract, num_input, memory.device, table)
         self.last_decode_stats = {"decoded_seqs": G * sum(min(F, n + 1) for n in num_input), "rows": N * F,
                                   "slot_rows": out["slot_rows"], "steps": out["steps"]}
         if mode.per_anchor:   # (G sequences per decoded anchor; `rows` stays the reference's N * F)
             self.last_decode_stats[mode.subject if mode.subject in ("constrain_beams", "constrain_samples") else mode.switches[0].attr] = G
         return inputs
+
+    def _faces_of_decode(self, inputs, extract, num_input, device, table):
+        """inputs["faces"]: ops.face_rows + ops.face_votes on the rows the decode published, in batch order --
+        predict_beams / predict_samples with their scores and dead-end flags when the mode has them, else predict under every
+        wireframe's own stop rule (with predict_logprob when there is one).  "enclosed": the enclosure walk on `table` (the
+        constrained decode's follow table in batch order) or on the table built from the end points with constrain_tol, and
+        only closed faces are counted.  Returns a dict of device tensors N x F x G ..., num_faces N."""
+        from ..hip import ops as _ops
+        for rows in ("beam", "sample"):
+            if "predict_%ss" % rows in inputs:
+                tokens = inputs["predict_%ss" % rows]
+                kw = dict(scores=inputs["predict_%s_scores" % rows], dead_end=inputs.get("predict_%s_dead_end" % rows))
+                break
+        else:
+            tokens = inputs["predict"]
+            kw = dict(logprob=inputs.get("predict_logprob"), own_stop=True)
+        if extract == "enclosed" and table is None:
+            table = self._follow_table(inputs, device, num_input, None)
+        edge_map = inputs.get("edge_map")
+        ni = torch.tensor(num_input, dtype=torch.int32).to(device)
+        found = _ops.face_rows(tokens, ni, self.token, follows=table, edge_map=None if edge_map is None else edge_map.to(device),
+                               num_lines=inputs["input"].size(1), **kw)
+        found.update(_ops.face_votes(found, require_closed=extract == "enclosed"))
+        return found
 
     def _follow_table(self, inputs, device, num_input, order):
         """The follow table [N, L, ceil(L/32)] int32 of a constrained decode in the DECODE's wireframe order: built on the device

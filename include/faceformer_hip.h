@@ -1196,6 +1196,67 @@ int ff_decode_constrained_sample(const ff_model* m, const ff_decode_params* p,
                                  float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                                  void* workspace, size_t workspace_bytes, const ff_constrain_sample_params* sample, ff_stream_t stream);
 
+/* ---- device-side face extraction behind the parallel decode (opt-in; entries added within ABI 105) ----------------
+ * The decode ends as token rows; the harness wants faces.  These entries restate, on device tensors, what faceformer_amd/faces.py
+ * does with lists after the rows were copied to the host: the parse of a row (trainer.py:181-208), the enclosure walk and the
+ * canonical order (post_processing.py:8-22 on check_faces_enclosed.py:11-46, read on the follow table), and the de-duplication
+ * with type votes (trainer.py:257-293).  Everything is integer-exact; faces.face_rows / faces.face_votes are the numpy
+ * restatements with the same bits.  Nothing of the decode changes.
+ *
+ * ff_face_rows: one wavefront per row.  Rows are r = (w*F + f)*G + g; R = F*G rows per wireframe.
+ *   tokens [N, F, G, T] int64 (G = 1, the beam width or the number of draws), 1 <= T <= FF_FACE_MAX_T; num_input [N] int32;
+ *   num_edges [N] int32 or NULL (= num_input), clamped into [0, L]; off / ntok: the config's face_type_offset and len,
+ *   0 <= off < ntok; scores [N, F, G] fp32 or NULL; logprob [N, F, G, T] fp32 or NULL (not both); dead_end [N, F, G] int32 or
+ *   NULL; follows [N, L, ceil(L/32)] (ff_follow_table's words) or NULL; edge_map [N, L] int32 or NULL.
+ *   Own stop (FF_FACE_OWN_STOP): s_w is the least j >= 1 at which every row with f < num_input[w], for all g, holds a token
+ *     < ntok, T-1 if there is none; tokens (and log-probabilities) at positions > s_w read as 0.  A pre-pass launch.
+ *   Parse: a row yields no face if f >= num_input[w], its score is -inf, or its dead_end is nonzero.  Otherwise fin is the least
+ *     j >= 0 with off <= tok[j] < ntok, T-1 if there is none; type = (int)(tok[fin] - off), whatever tok[fin] is; the edges are
+ *     tok[j] - ntok for j <= fin with 0 <= tok[j] - ntok < num_edges[w], in order; len is their count, and len = 0 is the only
+ *     "no face" marker.  A no-face row: type 0, closed 0 (-1 without follows), loops 0, edges and loop_of all -1, key all zero,
+ *     score 0.
+ *   Score (fp64): the row's scores value; or the sum of logprob over positions 1..fin, added one by one in ascending order in
+ *     fp64; or 0.
+ *   Enclosure walk (follows given): the first edge of a loop is `first`; edge i inside a loop needs follows[e_(i-1)][e_i] (the
+ *     first edge of a loop is not checked against the last edge of the loop before); after every edge the loop closes iff
+ *     follows[e_i][first] (a one-edge loop may close on itself); a failed connect before or at the next closure: not enclosed;
+ *     enclosed iff the last edge closes a loop.  closed in {0, 1}, loops = number of loops (0 when not closed).  Without
+ *     follows: closed = -1, loops = 0.
+ *   Canonical order: a closed face's loops are each rotated so that the smallest index comes first (the first occurrence on
+ *     ties) and stably sorted by that index; edges[r, :len] is the flattening and loop_of[r, :len] the loop number.  Not closed:
+ *     decode order, loop_of = -1.  Behind len both hold -1.
+ *   Key: set_bits[r, ceil(L/32)] is the bitmap of { edge_map[w][e] } over the face's edges; a map value outside [0, L) counts
+ *     as e itself; NULL is the identity.
+ *   Outputs: len, type, closed, loops [N*R] int32; edges, loop_of [N*R, T] int32; set_bits [N*R, ceil(L/32)] uint32; score
+ *     [N*R] fp64.
+ *   FF_ERR_ARG before any launch for T outside 1..FF_FACE_MAX_T, off outside [0, ntok), scores together with logprob, unknown
+ *   flag bits, a negative size, NULL tokens / num_input / outputs.
+ *
+ * ff_face_votes: de-duplication per wireframe, one workgroup per wireframe.
+ *   set_bits [N, R, words] uint32, len / type / closed [N, R] int32, score [N, R] fp64 as ff_face_rows leaves them.
+ *   A row participates iff len > 0 and, with FF_FACE_REQUIRE_CLOSED, closed == 1.  rep[r] (index inside the wireframe) is the
+ *   least participating row of the wireframe whose set_bits row is bit-identical, -1 for a row that does not participate.  For
+ *   rep[r] == r: votes = the group's size, best = its highest score (fp64; -0 orders below +0), major = its most frequent type,
+ *   a tie going to the type whose first member has the lowest row; every other row gets 0.  num_faces [N] = representatives.
+ *   Method: an open-addressing table of row indices per wireframe in the workspace; the hash only routes, a slot is claimed by
+ *   compare-and-swap, membership is decided by comparing the row's bitmap with the claimant's word for word, rep is an
+ *   atomicMin; the type counts repeat this on (rep, type).  Every result is a minimum, a maximum or an integer sum: it does not
+ *   depend on scheduling.
+ *   R <= FF_FACE_MAX_ROWS (FF_ERR_ARG above, before any launch); words is free.  workspace: ff_face_votes_workspace_bytes(N, R)
+ *   bytes, 8-byte aligned, contents arbitrary (FF_ERR_WORKSPACE when smaller); the query returns 0 for sizes the entry refuses. */
+#define FF_FACE_OWN_STOP 1
+#define FF_FACE_REQUIRE_CLOSED 1
+#define FF_FACE_MAX_T 256
+#define FF_FACE_MAX_ROWS 65536
+int ff_face_rows(const int64_t* tokens, int N, int F, int G, int T, const int* num_input, const int* num_edges, int L, int off,
+                 int ntok, const float* scores, const float* logprob, const int* dead_end, const unsigned int* follows,
+                 const int* edge_map, int flags, int* len, int* type, int* closed, int* loops, int* edges, int* loop_of,
+                 unsigned int* set_bits, double* score, ff_stream_t stream);
+size_t ff_face_votes_workspace_bytes(int N, int R);
+int ff_face_votes(const unsigned int* set_bits, const int* len, const int* type, const int* closed, const double* score, int N, int R,
+                  int words, int flags, int* rep, int* votes, double* best, int* major, int* num_faces, void* workspace,
+                  size_t workspace_bytes, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

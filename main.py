@@ -84,15 +84,56 @@ def check_cli_flags(given, model_class, world):
 def decode_batch_with(model, batch, wanted):
     """(`predict`, {record_of parameter: one entry per sample}) of `model(batch)` as numpy arrays; `wanted`: the
     (record_of parameter, output keys) of CLI_FLAGS whose flag is set -- several keys come as one tuple per sample."""
-    if not wanted:
+    faces = ("device_faces", ("faces",)) in wanted
+    wanted = [w for w in wanted if w[0] != "device_faces"]
+    if not wanted and not faces:
         return decode_batch(model, batch), {}
     with torch.no_grad():
         out = model(batch)
     extras = {}
     for param, keys in wanted:
-        arrays = [out[k].cpu().numpy() for k in keys]
+        # (--device-faces: token rows and log-probabilities stay on the device -- record_of only asks whether they exist)
+        arrays = [[True] * out[k].size(0) if faces and (k == "predict_logprob" or (i == 0 and len(keys) > 1)) else out[k].cpu().numpy()
+                  for i, k in enumerate(keys)]
         extras[param] = arrays[0] if len(arrays) == 1 else list(zip(*arrays))
+    if faces:       # (--device-faces: the face arrays come over, not the token rows; one wireframe's slice per sample)
+        arrays = {k: v.cpu().numpy() for k, v in out["faces"].items()}
+        n = arrays["num_faces"].shape[0]
+        extras["device_faces"] = [{k: v[i:i + 1] for k, v in arrays.items()} for i in range(n)]
+        if arrays["len"].shape[2] > 1 or "predict_beams" in out:
+            # beams / draws: `pred_faces` comes from `predict` under the wireframe's OWN stop rule, as record_of reads it on the
+            # host -- a second, small extraction over the N x F rows of predict (the beams and draws are published as decoded)
+            sub = {k: out[k] for k in ("predict", "input", "edge_map") if out.get(k) is not None}
+            ni = [int(v) for v in (out["num_input"].tolist() if torch.is_tensor(out["num_input"]) else out["num_input"])]
+            with torch.no_grad():
+                first = {k: v.cpu().numpy() for k, v in model._faces_of_decode(sub, model.extract_faces, ni, out["predict"].device, None).items()}
+            for i in range(n):
+                extras["device_faces"][i]["first"] = {k: v[i:i + 1] for k, v in first.items()}
+        return [None] * n, extras
     return out["predict"].cpu().numpy(), extras
+
+
+def _edge_bitmap(edges, words):
+    """set_bits of the UNMAPPED edge sets of face arrays: edges [..., T] int32 (-1 behind a face) -> [..., words] int32."""
+    e = np.asarray(edges)
+    bits = np.zeros(e.shape[:-1] + (words,), dtype=np.uint32)
+    at = np.nonzero(e >= 0)
+    v = e[at]
+    np.bitwise_or.at(bits, at[:-1] + (v >> 5,), (np.uint32(1) << (v & 31).astype(np.uint32)))
+    return bits.view(np.int32)
+
+
+def _device_unique(rows, require_closed, unmapped, device_votes):
+    """[(majority type, sorted edge set, best score, votes)] in first-seen order of ONE wireframe's face arrays (`rows`: the
+    model's inputs["faces"] cut to the sample, 1 x F x G ...).  unmapped: keyed by the edges themselves although the arrays
+    were keyed through an edge map.  device_votes: the grouping the device made is the one asked for; otherwise
+    faces.face_votes groups the same arrays here."""
+    if device_votes:
+        return FZ.faces_of_rows(rows, rows, 0)["unique"]
+    sub = dict(rows)
+    if unmapped:
+        sub["set_bits"] = _edge_bitmap(sub["edges"], sub["set_bits"].shape[-1])
+    return FZ.faces_of_rows(sub, FZ.face_votes(sub, require_closed=require_closed), 0)["unique"]
 
 
 def score_batch(model, batch):
@@ -106,7 +147,7 @@ def score_batch(model, batch):
 
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
-              constrained_beams=None, constrained_samples=None):
+              constrained_beams=None, constrained_samples=None, device_faces=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -128,7 +169,14 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     constrained_samples (--constrain-samples; (tokens [F, R, T], scores [F, R], dead-end flags [F, R]) of this sample): the record
     also gets `pred_sample_faces`, `pred_sample_face_scores` and `pred_sample_face_votes` as under --sample, over the draws that
     did not run into a dead end; `pred_faces` stays what draw 0 (pred) gives, and `pred_dead_ends` / `pred_unclosed` are counted
-    over ALL draws of the wireframe's own anchors."""
+    over ALL draws of the wireframe's own anchors.
+    device_faces (--device-faces; this sample's slice of the model's inputs["faces"]): the predicted faces of
+    every key above come from these arrays (faces.faces_of_rows) instead of from pred, beams and samples, which are then not
+    read; label faces, the metrics and the JSON text are made here as before."""
+    if device_faces is not None:
+        return _record_of_device(cfg, raw, item, device_faces, logprob is not None, beams is not None or constrained_beams is not None,
+                                 samples is not None or constrained_samples is not None, dead_end,
+                                 constrained_samples[2] if constrained_samples is not None else None, label_scores)
     scored = logprob is not None
     parse = FZ.parse_parallel_faces if parallel else FZ.parse_faces
     if parallel:
@@ -207,6 +255,54 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
+def _record_of_device(cfg, raw, item, rows, scored, beams, samples, dead_end, sample_dead_end, label_scores):
+    """record_of for --device-faces: the same record, key for key, from the face arrays `rows` (1 x F x G ...) of this sample.
+    beams / samples: the decode published beams / draws; dead_end: --constrain's flags of `predict` (else None);
+    sample_dead_end: --constrain-samples' flags of every draw."""
+    coedge = bool(cfg.post_process.is_coedge)
+    walked = bool((rows["closed"] >= 0).all())           # extract_faces "enclosed": the device counted closed faces only
+    n = int(item["num_input"])
+    lf = FZ._parallel_rows(item["label"], cfg.model.token, None)
+    if coedge:
+        lf = FZ.postprocess_faces(lf, raw["edges"], raw.get("pairings", {}), cfg.post_process.enclosedness_tol)
+    own = rows.get("first", rows)                        # (beams / draws: the extraction over `predict` alone)
+    first = _device_unique(own, coedge, False, walked == coedge)
+    m = FZ.face_metrics([(t, key) for t, key, _, _ in first], lf)
+    rec = FZ.faces_record(raw["edges"], raw.get("dominant_directions", []), m["predictions"], m["labels"])
+
+    def every_row(kind, votes):      # every beam / draw of the own anchors, unfiltered and keyed by the edges themselves
+        ranked = sorted(_device_unique(rows, False, coedge, not walked), key=lambda f: -f[2])
+        rec["pred_%s_faces" % kind] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_%s_face_scores" % kind] = [s for _, _, s, _ in ranked]
+        if votes:
+            rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
+    if scored:
+        rec["pred_face_scores"] = [s for _, _, s, _ in first]
+    if beams and dead_end is None:
+        every_row("beam", False)
+    if label_scores is not None:
+        ls = {k: np.asarray(v)[None] for k, v in label_scores.items()}
+        sm = FZ.score_summary(ls["logprob"], ls["greedy"], ls["rank"], ls["paths"], ls["lengths"])
+        rec["label_logprob"] = [float(v) for v, k in zip(ls["seq_logprob"].reshape(-1), ls["lengths"].reshape(-1)) if k > 0]
+        rec["label_nll"] = float(sm["nll"][0]) if sm["tokens"][0] else None
+        rec["label_tf_accuracy"] = float(sm["tf_accuracy"][0]) if sm["tokens"][0] else None
+    if dead_end is not None:
+        # own rows whose face does not pass the walk: `predict`'s, or under --constrain-samples those of every draw -- where a
+        # dead-ended draw was left out of the arrays, and its loop is open
+        every = sample_dead_end is not None
+        dead = np.asarray(sample_dead_end[:n] if every else dead_end[:n]).astype(bool)
+        ln, cl = ((rows if every else own)[k][0, :n] for k in ("len", "closed"))
+        rec["pred_dead_ends"] = int(dead.sum())
+        rec["pred_unclosed"] = int(((ln > 0) & (cl != 1)).sum()) + (int(dead.sum()) if every else 0)
+        if beams:
+            every_row("beam", False)
+        if samples:
+            every_row("sample", True)
+    elif samples:
+        every_row("sample", True)
+    return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
+
+
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
                     constrain_samples=0):
@@ -251,7 +347,7 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-             constrain_samples=0):
+             constrain_samples=0, device_faces=False):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -265,7 +361,15 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     constrain_beams, single-rank runs only) is the exact form of that look-ahead, with the same record keys; constrain_samples = R
     (1..64, only with constrain, not with constrain_beams, single-rank runs only; with constrain_lookahead or constrain_exact in
     that form) draws R loops per anchor from the constrained keys under temperature / top_k / top_p / seed and adds
-    pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes, with pred_dead_ends / pred_unclosed over all draws."""
+    pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes, with pred_dead_ends / pred_unclosed over all draws;
+    device_faces (parallel model, single-rank runs only): the predicted faces of every record are extracted on the
+    device (model.extract_faces: "enclosed" with the pairings as edge map for co-edge configs and under constrain, "parse"
+    otherwise) and the records are made from those arrays -- the same records."""
+    if device_faces:
+        if cfg.model_class != "SurfaceFormer_Parallel":
+            raise ValueError("--device-faces applies to SurfaceFormer_Parallel only")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--device-faces is not implemented for multi-rank runs")
     if constrain_samples:
         if not constrain:
             raise ValueError("--constrain-samples requires --constrain")
@@ -310,6 +414,9 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
                     cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact,
                     constrain_samples)
+    if device_faces:
+        model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
+        model.constrain_tol = float(cfg.post_process.enclosedness_tol)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -327,10 +434,19 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         wanted.append(("constrained_beams", ("predict_beams", "predict_beam_scores", "predict_beam_dead_end")))
     if constrain_samples:
         wanted.append(("constrained_samples", ("predict_samples", "predict_sample_scores", "predict_sample_dead_end")))
+    if device_faces:
+        wanted.append(("device_faces", ("faces",)))
     for b0 in range(lo, hi, batch_size):
         idx = list(range(b0, min(hi, b0 + batch_size)))
         items = [ds[i] for i in idx]
         batch = D.collate(items)
+        if device_faces and cfg.post_process.is_coedge:      # map_coedge_into_edges as a table: a co-edge counts as its partner
+            emap = torch.arange(batch["input"].size(1), dtype=torch.int32).repeat(len(idx), 1)
+            for k, i in enumerate(idx):
+                for a, b in ds.raw_datas[i].get("pairings", {}).items():
+                    if 0 <= int(a) < emap.size(1):
+                        emap[k, int(a)] = int(b)
+            batch["edge_map"] = emap
         batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
         if torch.cuda.is_available() and str(device).startswith("cuda"):
             torch.cuda.synchronize()
@@ -422,6 +538,10 @@ def build_parser():
                              "never an edge from which it cannot close in time through edges the row has not used, so a row can "
                              "only dead-end right after the edge that opened a loop; same record keys; single-process runs only, "
                              "not with --constrain-lookahead or --constrain-beams")
+    parser.add_argument("--device-faces", action="store_true",
+                        help="parallel model: the predicted faces of every record -- parse, enclosure filter, co-edge mapping, "
+                             "de-duplication with type votes, best score and vote count -- are extracted on the device behind the "
+                             "decode (DESIGN.md 27) instead of row by row on the host; the records are the same; single-process runs only")
     parser.add_argument("--constrain-samples", type=int, default=0, metavar="R",
                         help="with --constrain: R (1..64) independent draws per anchor edge from the constrained keys under "
                              "--temperature / --top-k / --top-p / --seed (DESIGN.md 26), in the plain form or with "
@@ -451,7 +571,7 @@ def main(argv=None):
              score_labels=args.score_labels, sample=args.sample, temperature=args.temperature, top_k=args.top_k,
              top_p=args.top_p, seed=args.seed, constrain=args.constrain, constrain_beams=args.constrain_beams,
              constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact,
-             constrain_samples=args.constrain_samples)
+             constrain_samples=args.constrain_samples, device_faces=args.device_faces)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
