@@ -203,8 +203,10 @@ int ff_constrain_sample_finalize(const int* tok, const float* lp, const int* fin
                                  float* predict_logprob, int* predict_dead_end, int* seq_of_row, hipStream_t st);
 
 // Constrained beam decode: `step` supplies the rule's and the beams' operands, io the common ones (io.rows = groups * width);
-// its beams, scores and predict are packed by ff_beam_finalize.
-int ff_beam_constrained_select_sync(const ff_step_io& io, const ff_beam_constrained_step* step, ff_stream_t stream);
+// its beams, scores and predict are packed by ff_beam_finalize.  ahead (or null): the closure look-ahead of every beam's row, or
+// with `exact` the exact one; `op` words the errors.
+int ff_beam_constrained_select_sync(const char* op, const ff_step_io& io, const ff_beam_constrained_step* step,
+                                    const ff_lookahead_io* ahead, ff_stream_t stream);
 int ff_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* parent, int* first, int* prev, unsigned* visited, int Bc,
                            int Fc, int W, int f0, const int* num_input, int pad_tok, int term_lo, int term_hi, int ntok,
                            const unsigned* follows, int L, hipStream_t st);

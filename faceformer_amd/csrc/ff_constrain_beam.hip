@@ -1,9 +1,11 @@
 // Beam search over the loop-constrained pointer head (opt-in, parallel variant): one step's top-W selection over
 // the LIVE keys of the W constrained rows of every group, with the rule's per-beam state following the parent permutation.
 //
-// beam_constrained_select_kernel<W>: one wavefront per group, four per block, as beam_select_kernel.  For each non-empty
+// beam_constrained_select_kernel<W, FORM>: one wavefront per group, four per block, as beam_select_kernel.  For each non-empty
 // unfinished beam the wave writes the byte row of the beam's constraint mask with the function pointer_constrained_kernel calls
-// (ff_loop_write_row<false>, ff_select.h: the vote on "any live edge", the terminators re-opened on a dead end), masks and
+// (ff_loop_write_row<FORM>, ff_select.h: the vote on "any live edge", the terminators re-opened on a dead end; FORM is the plain
+// rule, the closure look-ahead or the exact one -- DESIGN.md 28: the beam's own first / prev pick the table row, the exact form
+// runs one search per open beam over that beam's visited words, and all beams share the step's budget), masks and
 // reduces the logit row with that row as the extra mask (ff_pointer_mask_reduce<true>, ff_device.h: every lane reads back only
 // bytes and logits it wrote itself), walks its strided keys once more and keeps the W best LIVE candidates
 // c_k + (l[s] - m) - log(sum) in the sorted register list of ff_select.h, beam_select_kernel's -- a masked key
@@ -35,9 +37,12 @@ struct ConBeamArgs {
   int *fin_out, *dead_out, *first_out, *prev_out;
   unsigned* visited_out;         // [B, fw], not visited_in
   int* parent; int* tok;         // [B] out
+  const unsigned char* close_dist;   // FF_LOOP_AHEAD only: [wireframes, L, L] bytes
+  const unsigned char* cycle_len;    // FF_LOOP_AHEAD, FF_LOOP_EXACT: [wireframes, L] bytes
+  int budget;                        // FF_LOOP_AHEAD, FF_LOOP_EXACT: the step's, shared by every beam of the launch
 };
 
-template <int W>
+template <int W, int FORM>
 __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArgs a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
@@ -56,7 +61,7 @@ __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArg
     const int my_d = lane < W ? a.dead_in[b0 + lane] : 0;
     const int my_first = ff_loop_edge(lane < W ? a.first_in[b0 + lane] : -1, a.L);
     const int my_prev = ff_loop_edge(lane < W ? a.prev_in[b0 + lane] : -1, a.L);
-    const FFLoopRule rule{a.follows, a.L, fw, a.flags, ntok, nullptr, nullptr, 0};
+    const FFLoopRule rule{a.follows, a.L, fw, a.flags, ntok, a.close_dist, a.cycle_len, a.budget};
     unsigned deadmask = 0u;   // bit k: beam k dead-ended at this step (wave-uniform)
     float lsc[W];
     int lix[W];
@@ -72,7 +77,7 @@ __global__ __launch_bounds__(256) void beam_constrained_select_kernel(ConBeamArg
         continue;
       }
       const int b = b0 + k;
-      if (ff_loop_write_row<false>(pa, rule, lane, w, kv, mrow, first, prev, a.visited_in + (size_t)b * fw, a.rows + (size_t)b * S))
+      if (ff_loop_write_row<FORM>(pa, rule, lane, w, kv, mrow, first, prev, a.visited_in + (size_t)b * fw, a.rows + (size_t)b * S))
         deadmask |= 1u << k;
       float m, b2, lsum;
       int i1;
@@ -168,8 +173,10 @@ __global__ void cbeam_dead_kernel(const int* __restrict__ dead, int Btot, const 
 
 }  // namespace
 
-int ff_beam_constrained_select_sync(const ff_step_io& io, const ff_beam_constrained_step* d, ff_stream_t stream) {
-  const char* op = "ff_beam_constrained_select";
+// The one launch behind ff_beam_constrained_select (ahead = null: the plain rule) and ff_beam_constrained_select_ahead (the
+// closure look-ahead, or with ahead->exact the exact one); `op` words the errors.
+int ff_beam_constrained_select_sync(const char* op, const ff_step_io& io, const ff_beam_constrained_step* d, const ff_lookahead_io* ahead,
+                                    ff_stream_t stream) {
   const int S = io.S, W = d->width, groups = io.rows / W;
   ConBeamArgs a;
   memset(&a, 0, sizeof(a));
@@ -179,6 +186,10 @@ int ff_beam_constrained_select_sync(const ff_step_io& io, const ff_beam_constrai
                    d->prev_in && d->prev_out && d->visited_in && d->visited_out && d->mask_rows && d->parent && d->next_tok,
                "%s: null pointer", op);
   FF_CHECK_ARG(d->visited_in != d->visited_out, "%s: visited_out must not be visited_in", op);
+  if (ahead) {
+    FF_RETURN_IF(ff_lookahead_check(op, ff_loop_rule_io{d->follows, d->L, d->flags, d->ntok}, S, *ahead));
+    a.close_dist = ahead->exact ? nullptr : ahead->close_dist; a.cycle_len = ahead->cycle_len; a.budget = ahead->budget;
+  }
   a.p.extra = d->mask_rows; a.p.ldextra = S;
   a.groups = groups; a.rows = d->mask_rows; a.follows = d->follows; a.L = d->L; a.fw = (d->L + 31) >> 5; a.flags = d->flags; a.ntok = d->ntok;
   a.score_in = d->scores_in; a.score_out = d->scores_out;
@@ -188,22 +199,41 @@ int ff_beam_constrained_select_sync(const ff_step_io& io, const ff_beam_constrai
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)io.rows * S * 14.0, st);
   const dim3 grid(ff_cdiv(groups, 4)), block(256);
+  const int form = !ahead ? FF_LOOP_PLAIN : (ahead->exact ? FF_LOOP_EXACT : FF_LOOP_AHEAD);
   const int rc = ff_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(W, [&](auto w) {
-    hipLaunchKernelGGL(beam_constrained_select_kernel<decltype(w)::value>, grid, block, 0, st, a);
-    return FF_OK;
+    return ff_dispatch<FF_LOOP_PLAIN, FF_LOOP_AHEAD, FF_LOOP_EXACT>(form, [&](auto f) {
+      hipLaunchKernelGGL((beam_constrained_select_kernel<decltype(w)::value, decltype(f)::value>), grid, block, 0, st, a);
+      return FF_OK;
+    });
   });
   FF_RETURN_IF(rc);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
 
+namespace {
+// the common operands of a one-step descriptor as the launch's step io
+ff_step_io cbeam_step_io(const ff_beam_constrained_step* d) {
+  return ff_step_io{d->logits, d->ldlogits, d->S, d->mask, d->kv_len, d->groups * d->width, d->groups_per_wireframe * d->width, d->term_lo,
+                    d->term_hi, d->ntok, d->memory, d->E, d->next_rows, d->ldnext, d->next_stats, d->count_ge, nullptr, nullptr};
+}
+}  // namespace
+
 extern "C" int ff_beam_constrained_select(const ff_beam_constrained_step* d, ff_stream_t stream) {
-  FF_CHECK_ARG(d != nullptr, "ff_beam_constrained_select: null descriptor");
-  FF_RETURN_IF(ff_beam_check_sizes("ff_beam_constrained_select", d->groups, d->width, d->groups_per_wireframe, d->S));
-  return ff_beam_constrained_select_sync(
-      ff_step_io{d->logits, d->ldlogits, d->S, d->mask, d->kv_len, d->groups * d->width, d->groups_per_wireframe * d->width, d->term_lo,
-                 d->term_hi, d->ntok, d->memory, d->E, d->next_rows, d->ldnext, d->next_stats, d->count_ge, nullptr, nullptr},
-      d, stream);
+  const char* op = "ff_beam_constrained_select";
+  FF_CHECK_ARG(d != nullptr, "%s: null descriptor", op);
+  FF_RETURN_IF(ff_beam_check_sizes(op, d->groups, d->width, d->groups_per_wireframe, d->S));
+  return ff_beam_constrained_select_sync(op, cbeam_step_io(d), d, nullptr, stream);
+}
+
+extern "C" int ff_beam_constrained_select_ahead(const ff_beam_constrained_ahead_step* da, ff_stream_t stream) {
+  const char* op = "ff_beam_constrained_select_ahead";
+  FF_CHECK_ARG(da != nullptr, "%s: null descriptor", op);
+  const ff_beam_constrained_step* d = &da->step;
+  FF_RETURN_IF(ff_beam_check_sizes(op, d->groups, d->width, d->groups_per_wireframe, d->S));
+  FF_CHECK_ARG(da->lookahead == 1 || da->lookahead == 2, "%s: lookahead=%d must be 1 (look-ahead) or 2 (exact)", op, da->lookahead);
+  const ff_lookahead_io ahead{da->lookahead == 1 ? da->close_dist : nullptr, da->cycle_len, da->budget, da->lookahead == 2 ? 1 : 0};
+  return ff_beam_constrained_select_sync(op, cbeam_step_io(d), d, &ahead, stream);
 }
 
 int ff_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* parent, int* first, int* prev, unsigned* visited, int Bc,

@@ -360,7 +360,7 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
@@ -375,7 +375,14 @@ struct Mode {
     if (kind != CONSTRAIN_AHEAD) return *static_cast<const ff_constrain_params*>(prm);
     return ff_constrain_params{ahead()->flags, ahead()->follows, ahead()->logprob, ahead()->dead_end};
   }
-  const ff_constrain_beam_params* cbeam() const { return static_cast<const ff_constrain_beam_params*>(prm); }
+  const ff_constrain_beam_ahead_params* cbeam_ahead() const { return static_cast<const ff_constrain_beam_ahead_params*>(prm); }
+  // (CONSTRAIN_BEAM and CONSTRAIN_BEAM_AHEAD: the parameters the two share)
+  bool is_cbeam() const { return kind == CONSTRAIN_BEAM || kind == CONSTRAIN_BEAM_AHEAD; }
+  ff_constrain_beam_params cbeam() const {
+    if (kind != CONSTRAIN_BEAM_AHEAD) return *static_cast<const ff_constrain_beam_params*>(prm);
+    const ff_constrain_beam_ahead_params* q = cbeam_ahead();
+    return ff_constrain_beam_params{q->width, q->flags, q->follows, q->beams, q->scores, q->dead_end, q->trace_parent};
+  }
   const ff_constrain_sample_params* csample() const { return static_cast<const ff_constrain_sample_params*>(prm); }
 };
 
@@ -386,6 +393,7 @@ void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, con
   switch (mode.kind) {
     case Mode::BEAM:
     case Mode::CONSTRAIN_BEAM:
+    case Mode::CONSTRAIN_BEAM_AHEAD:
     case Mode::CONSTRAIN_SAMPLE:
     case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
     case Mode::FORCED: {
@@ -497,6 +505,7 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
   switch (mode.kind) {
     case Mode::BEAM:
     case Mode::CONSTRAIN_BEAM:
+    case Mode::CONSTRAIN_BEAM_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
       b.score = bp.take<float>(TB);
       b.finished = bp.take<int>(TB);
       b.parent = bp.take<int>(TB);
@@ -1076,13 +1085,14 @@ struct DecodeRun {
     const unsigned* follows;
     int flags;
     switch (mode.kind) {
-      case Mode::CONSTRAIN_BEAM: follows = mode.cbeam()->follows; flags = mode.cbeam()->flags; break;
+      case Mode::CONSTRAIN_BEAM:
+      case Mode::CONSTRAIN_BEAM_AHEAD: follows = mode.cbeam().follows; flags = mode.cbeam().flags; break;
       case Mode::CONSTRAIN_SAMPLE: follows = mode.csample()->follows; flags = mode.csample()->flags; break;
       default: follows = mode.con().follows; flags = mode.con().flags; break;
     }
     return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, flags};
   }
-  // The look-ahead of the constrained greedy and constrained sampled modes: the form (0 none, 1 the closure look-ahead, 2 the
+  // The look-ahead of the constrained greedy, sampled and beam modes: the form (0 none, 1 the closure look-ahead, 2 the
   // exact one) and the whole batch's tables as the caller gave them.
   struct Ahead { int form; const unsigned char *close_dist, *cycle_len; };
   Ahead ahead_of() const {
@@ -1090,6 +1100,8 @@ struct DecodeRun {
       case Mode::CONSTRAIN_AHEAD: return Ahead{1, mode.ahead()->close_dist, mode.ahead()->cycle_len};
       case Mode::CONSTRAIN_EXACT: return Ahead{2, nullptr, mode.exact()->cycle_len};
       case Mode::CONSTRAIN_SAMPLE: return Ahead{mode.csample()->lookahead, mode.csample()->close_dist, mode.csample()->cycle_len};
+      case Mode::CONSTRAIN_BEAM_AHEAD:
+        return Ahead{mode.cbeam_ahead()->lookahead, mode.cbeam_ahead()->close_dist, mode.cbeam_ahead()->cycle_len};
       default: return Ahead{0, nullptr, nullptr};
     }
   }
@@ -1111,11 +1123,12 @@ struct DecodeRun {
       case Mode::CONSTRAIN_AHEAD:
       case Mode::CONSTRAIN_EXACT:
       case Mode::CONSTRAIN_SAMPLE:
+      case Mode::CONSTRAIN_BEAM_AHEAD:
       case Mode::CONSTRAIN_BEAM: {   // (constrained beam: half 0 of the ping-pong state, step 0 reads it)
         const Rule r = rule_of(c);
         int *dead = buf.dead + c.b0, *first = buf.first + c.b0, *prev = buf.prev + c.b0;
         unsigned* visited = buf.visited + (size_t)c.b0 * r.fw;
-        if (mode.kind == Mode::CONSTRAIN_BEAM)
+        if (mode.is_cbeam())
           return ff_constrain_beam_init(tok, score, fin, dead, buf.parent + c.b0, first, prev, visited, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok,
                                         p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
         if (mode.kind == Mode::CONSTRAIN_SAMPLE)
@@ -1181,7 +1194,8 @@ struct DecodeRun {
     int* tok_out = buf.tok_all + out;
     switch (mode.kind) {
       case Mode::BEAM:
-      case Mode::CONSTRAIN_BEAM: {
+      case Mode::CONSTRAIN_BEAM:
+      case Mode::CONSTRAIN_BEAM_AHEAD: {
         // top-W selection, then the reorder of positions < t of x0 and qkv0 behind it on the same stream: the next decoder pass
         // reads reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
         const int W = mode.G;
@@ -1191,7 +1205,7 @@ struct DecodeRun {
           FF_RETURN_IF(ff_beam_select_sync(sio, W, buf.score + in, buf.score + out, buf.finished + in, buf.finished + out, nullptr, 0, t,
                                            buf.parent + out, tok_out, st));
         } else {   // the constrained selection: state half step & 1 -> half t & 1 (the common operands come from sio)
-          trace_parent = mode.cbeam()->trace_parent;
+          trace_parent = mode.cbeam().trace_parent;
           const Rule r = rule_of(c);
           const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
           ff_beam_constrained_step d;
@@ -1203,7 +1217,12 @@ struct DecodeRun {
           d.first_out = buf.first + hout; d.prev_out = buf.prev + hout; d.visited_out = buf.visited + hout * r.fw;
           d.mask_rows = buf.byte_rows + (size_t)c.b0 * S;
           d.parent = buf.parent + out; d.next_tok = tok_out;
-          FF_RETURN_IF(ff_beam_constrained_select_sync(sio, &d, st));
+          // the look-aheads: this step selects position t, so a loop has T - 1 - t further positions to close in
+          const Ahead la = ahead_of();
+          const ff_lookahead_io ahead{la.form == 1 ? la.close_dist + (size_t)c.w0 * r.L * r.L : nullptr,
+                                      la.form ? la.cycle_len + (size_t)c.w0 * r.L : nullptr, T - 1 - t, la.form == 2 ? 1 : 0};
+          FF_RETURN_IF(ff_beam_constrained_select_sync(la.form ? "ff_beam_constrained_select_ahead" : "ff_beam_constrained_select", sio,
+                                                       &d, la.form ? &ahead : nullptr, st));
         }
         if (trace_parent)
           FF_CHECK_HIP(hipMemcpyAsync(trace_parent + trow, buf.parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
@@ -1425,14 +1444,15 @@ struct DecodeRun {
     const int G = mode.G, dd = dedup ? 1 : 0;
     switch (mode.kind) {
       case Mode::BEAM:
-      case Mode::CONSTRAIN_BEAM: {
-        const bool con = mode.kind == Mode::CONSTRAIN_BEAM;
+      case Mode::CONSTRAIN_BEAM:
+      case Mode::CONSTRAIN_BEAM_AHEAD: {
+        const bool con = mode.is_cbeam();
         FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.parent, buf.score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
-                                      c.Fc / G, c.f0, c.b0, con ? mode.cbeam()->beams : mode.beam()->beams,
-                                      con ? mode.cbeam()->scores : mode.beam()->scores, io.predict, io.seq_of_row, main_st));
+                                      c.Fc / G, c.f0, c.b0, con ? mode.cbeam().beams : mode.beam()->beams,
+                                      con ? mode.cbeam().scores : mode.beam()->scores, io.predict, io.seq_of_row, main_st));
         if (!con) return FF_OK;
         return ff_constrain_beam_dead(buf.dead, Btot, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G, c.f0, c.b0,
-                                      mode.cbeam()->dead_end, main_st);
+                                      mode.cbeam().dead_end, main_st);
       }
       case Mode::SAMPLE:
         return ff_sample_finalize(buf.tok_all, buf.score, buf.finished, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
@@ -1807,6 +1827,37 @@ extern "C" int ff_decode_constrained_beam(const ff_model* m, const ff_decode_par
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM, beam->width, beam));
+}
+
+extern "C" size_t ff_decode_constrained_beam_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p,
+                                                                   const int* num_input_host, int width) {
+  if (width < 1 || width > 8) return 0;
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_BEAM_AHEAD, width));
+}
+
+extern "C" int ff_decode_constrained_beam_ahead(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                                const unsigned char* mask, const int* kv_len, const int* num_input,
+                                                const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
+                                                int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
+                                                float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
+                                                size_t workspace_bytes, const ff_constrain_beam_ahead_params* beam,
+                                                ff_stream_t stream) {
+  const char* name = "ff_decode_constrained_beam_ahead";
+  FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
+  FF_RETURN_IF(check_opt_in(name, "the constrained beam decode with look-ahead is", p, extra_mask));
+  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d",
+               name, beam->width, p->L + m->num_token);
+  FF_RETURN_IF(check_loop_rule(name, beam->flags, beam->follows, m, p));
+  FF_CHECK_ARG(beam->lookahead == 1 || beam->lookahead == 2, "%s: lookahead=%d must be 1 (look-ahead) or 2 (exact)", name, beam->lookahead);
+  FF_RETURN_IF(check_lookahead(name, beam->lookahead, beam->flags, beam->close_dist, beam->cycle_len, m, p));
+  FF_RETURN_IF(check_opt_in_outputs(name, p, "beams, scores and dead_end", beam->beams && beam->scores && beam->dead_end, trace_best,
+                                    trace_second, pointer_out));
+  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
+  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
+               "%s: width=%d at E=%d exceeds the reorder's staging area", name, beam->width, m->E);
+  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
+                                    seq_of_row, stream),
+                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM_AHEAD, beam->width, beam));
 }
 
 extern "C" size_t ff_decode_constrained_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,

@@ -215,6 +215,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
         raise ValueError("decode_sharded does not implement constrain_lookahead (%s)" % _modes.SWITCH["constrain"].sharded)
     if getattr(model, "constrain_exact", False):
         raise ValueError("decode_sharded does not implement constrain_exact (%s)" % _modes.SWITCH["constrain"].sharded)
+    if getattr(model, "constrain_beam_closure", None) is not None:
+        raise ValueError("decode_sharded does not implement constrain_beam_closure (%s)" % _modes.SWITCH["constrain"].sharded)
     if getattr(model, "constrain_samples", 0):
         raise ValueError("decode_sharded does not implement constrain_samples (%s)" % _modes.SWITCH["constrain"].sharded)
     for mode in reversed(_modes.MODES):

@@ -375,7 +375,7 @@ class PathEngine:
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
-               constrain_samples=None):
+               constrain_samples=None, constrain_beam_closure=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -434,17 +434,25 @@ class PathEngine:
         layout: the log-probability under the model renormalised over the keys the rule allows), `sample_scores` [N*F*R] and
         `sample_dead_end` [N*F*R] int32; `predict`, `logprob` and `dead_end` are draw 0; with trace=True `logits`
         [T-1, N*F*R, S] holds the constrained masked rows.  temperature=0 equals the constrained greedy decode of the same form,
-        R times; flag bits 0 equal the num_samples decode."""
+        R times; flag bits 0 equal the num_samples decode.
+
+        constrain_beam_closure="lookahead" / "exact" (only with constrain="loops" and constrain_beams=W, T <= 256;
+        ff_decode_constrained_beam_ahead; None: the constrain_beams decode above): every beam's row is formed with
+        the closure look-ahead (close_dist and cycle_len required) or the exact one (cycle_len required, at most 2048 keys, one
+        search per open beam and step).  Outputs are constrain_beams'; `beam_dead_end` then also means "cannot close within T".
+        W = 1 equals the constrain_lookahead / constrain_exact decode; "lookahead" with both tables zero equals the
+        constrain_beams decode."""
         W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
         CB = _modes.constrain_beams_value(constrain_beams, CF)
         LA = _modes.constrain_lookahead_value(constrain_lookahead, CF, CB)
         EX = _modes.constrain_exact_value(constrain_exact, CF, CB, LA)
         CS = _modes.constrain_samples_value(constrain_samples, CF, CB)
-        mode, value = _modes.of_options(logprob, CB, LA, EX, CS, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
+        CL = _modes.constrain_beam_closure_value(constrain_beam_closure, CF, CB, LA, EX, CS)
+        mode, value = _modes.of_options(logprob, CB, LA, EX, CS, CL, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
         G = value if mode.per_anchor else 1       # sequences per anchor
         o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
                  logprob=logprob, beam_width=W, num_samples=R, constrain=CF, constrain_beams=CB, constrain_samples=CS, temperature=temperature, top_k=top_k, top_p=top_p,
-                 uniforms=uniforms, follow_table=follow_table, constrain_lookahead=LA, constrain_exact=EX, close_dist=close_dist, cycle_len=cycle_len, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
+                 uniforms=uniforms, follow_table=follow_table, constrain_lookahead=LA, constrain_exact=EX, constrain_beam_closure=CL, close_dist=close_dist, cycle_len=cycle_len, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
                  N=memory.shape[0], S=memory.shape[1], F=F, T=T)
         if value is not None:    # (retire, an option of the greedy record, is checked behind the operands)
             _modes.check_options(mode, variant, o, term_range)

@@ -163,6 +163,15 @@ class ConstrainBeamParams(C.Structure):
                 ("trace_parent", fptr)]
 
 
+class BeamConstrainedAheadStep(C.Structure):
+    _fields_ = [("step", BeamConstrainedStep), ("lookahead", C.c_int), ("close_dist", fptr), ("cycle_len", fptr), ("budget", C.c_int)]
+
+
+class ConstrainBeamAheadParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("flags", C.c_int), ("follows", fptr), ("lookahead", C.c_int), ("close_dist", fptr),
+                ("cycle_len", fptr), ("beams", fptr), ("scores", fptr), ("dead_end", fptr), ("trace_parent", fptr)]
+
+
 class ConstrainAheadParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("follows", fptr), ("close_dist", fptr), ("cycle_len", fptr), ("logprob", fptr),
                 ("dead_end", fptr)]
@@ -328,6 +337,13 @@ SIGNATURES = {
                                                C.POINTER(C.c_int), fptr,
                                                fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                                C.c_size_t, C.POINTER(ConstrainSampleParams), fptr]),
+    "ff_beam_constrained_select_ahead": (C.c_int, [C.POINTER(BeamConstrainedAheadStep), fptr]),
+    "ff_decode_constrained_beam_ahead_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.POINTER(C.c_int),
+                                                                      C.c_int]),
+    "ff_decode_constrained_beam_ahead": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                                   C.POINTER(C.c_int), fptr,
+                                                   fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
+                                                   C.c_size_t, C.POINTER(ConstrainBeamAheadParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
     "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
                                fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
@@ -364,7 +380,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact and ff_face_* ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_* and *_beam*_ahead ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

@@ -118,6 +118,54 @@ def _constrain_beam_values(o):
     _constrain_values(o)
 
 
+BEAM_CLOSURES = {"lookahead": 1, "exact": 2}      # constrain_beam_closure -> the `lookahead` form of the C entries
+
+
+def constrain_beam_closure_value(closure, flags, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
+                                 constrain_samples=0):
+    """The form of a `constrain_beam_closure` value: None -> None (the option is off); else "lookahead" or "exact",
+    only with constrain='loops' (`flags`: constrain_flags of it) and constrain_beams >= 1, and not with the greedy / sampled
+    decode's own look-ahead options (which exclude constrain_beams with their own texts before this is asked)."""
+    if closure is None:
+        return None
+    if not isinstance(closure, str) or closure not in BEAM_CLOSURES:
+        raise ValueError("constrain_beam_closure=%r: must be None, 'lookahead' or 'exact'" % (closure,))
+    if not constrain_beams:
+        raise ValueError("constrain_beam_closure=%r needs constrain_beams: it is the closure look-ahead of the beam search over the "
+                         "constrained keys" % closure)
+    if flags != CONSTRAIN_MODES["loops"]:
+        raise ValueError("constrain_beam_closure=%r needs constrain='loops' (FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT): without "
+                         "CONNECT no loop is tracked" % closure)
+    if constrain_lookahead or constrain_exact or constrain_samples:
+        raise ValueError("constrain_beam_closure excludes constrain_lookahead, constrain_exact and constrain_samples: they are the "
+                         "look-aheads of the greedy and the sampled decode")
+    return closure
+
+
+def _constrain_beam_ahead_values(o):
+    _constrain_beam_values(o)
+    exact = o["constrain_beam_closure"] == "exact"
+    if o["T"] > 256:
+        raise ValueError("constrain_beam_closure takes T <= 256 (got %d): the budget T - 2 must fit the tables' byte" % o["T"])
+    for name in ("cycle_len",) if exact else ("close_dist", "cycle_len"):
+        if o[name] is None:
+            raise ValueError("constrain_beam_closure=%r needs %s (ops.follow_distance)"
+                             % (o["constrain_beam_closure"], "cycle_len" if exact else "close_dist and cycle_len"))
+
+
+def _constrain_beam_ahead_operand(eng, o):
+    _constrain_operand(eng, o)
+    L = o["S"] - eng.num_token
+    exact = o["constrain_beam_closure"] == "exact"
+    if exact and o["S"] > EXACT_MAX_KEYS:
+        raise ValueError("constrain_beam_closure='exact' takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
+                         % (EXACT_MAX_KEYS - eng.num_token, L, EXACT_MAX_KEYS))
+    for name, shape in (("cycle_len", (o["N"], L)),) if exact else (("close_dist", (o["N"], L, L)), ("cycle_len", (o["N"], L))):
+        t = o[name]
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != shape:
+            raise ValueError("%s must be a uint8 tensor of shape [%s]" % (name, ", ".join(str(v) for v in shape)))
+
+
 def constrain_lookahead_value(lookahead, flags, constrain_beams=0):
     """Whether the closure look-ahead is on (`constrain_lookahead`): only with constrain='loops' (`flags`:
     constrain_flags of it -- the look-ahead masks under CONNECT) and not with constrain_beams."""
@@ -270,6 +318,16 @@ def _constrain_beam_tail(o, ptrs, traced):
                                            _p(traced.get("beam_parent")))),)
 
 
+def _constrain_beam_ahead_tail(o, ptrs, traced):
+    if o["trace"]:
+        logits = traced["logits"]
+        traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
+    form = BEAM_CLOSURES[o["constrain_beam_closure"]]
+    return (C.byref(_L.ConstrainBeamAheadParams(o["constrain_beams"], o["constrain"], _p(o["follow_table"]), form,
+                                                _p(o["close_dist"]) if form == 1 else None, _p(o["cycle_len"]), *ptrs,
+                                                _p(traced.get("beam_parent")))),)
+
+
 def outputs(mode, eng, o, B, traced):
     """(the mode's outputs by key: [B * G if "G" is among the dimensions else B, T if "T" is], the arguments only its entry takes:
     its parameter struct, or the log-probability output).  The mode's own operand is checked and made contiguous first."""
@@ -307,6 +365,23 @@ CONSTRAIN_BEAM = CONSTRAIN._replace(
     outs=(("beams", "GT", _I64), ("beam_scores", "G", _F32), ("beam_dead_end", "G", _I32)), tail=_constrain_beam_tail,
     prepare=lambda m, W, inputs, dev, T, N, F, ni, order: dict(
         CONSTRAIN.prepare(m, constrain_flags(m.constrain), inputs, dev, T, N, F, ni, order), constrain_beams=W))
+
+def _constrain_beam_ahead_prepare(m, W, inputs, dev, T, N, F, ni, order):
+    kw = CONSTRAIN_BEAM.prepare(m, W, inputs, dev, T, N, F, ni, order)
+    closure = m.constrain_beam_closure
+    if closure == "exact":      # (only cycle_len is needed)
+        return dict(kw, constrain_beam_closure=closure, cycle_len=m._cycle_len(inputs, dev, T, ni, order, kw["follow_table"]))
+    return dict(kw, constrain_beam_closure=closure, **m._follow_distance(inputs, dev, T, ni, order, kw["follow_table"]))
+
+
+# constrain='loops' with constrain_beams = W and its option constrain_beam_closure: the same beam search with the
+# closure look-ahead, or the exact one, in every beam's row of the selection launch.  Outside MODES, as CONSTRAIN_BEAM is; the
+# tables are operands beside follow_table.
+CONSTRAIN_BEAM_AHEAD = CONSTRAIN_BEAM._replace(
+    entry="ff_decode_constrained_beam_ahead", values=_constrain_beam_ahead_values, operand=_constrain_beam_ahead_operand,
+    own=(("follow_table", _I32), ("close_dist", torch.uint8), ("cycle_len", torch.uint8)), tail=_constrain_beam_ahead_tail,
+    prepare=lambda *a: _constrain_beam_ahead_prepare(*a))
+
 
 def _constrain_ahead_prepare(m, CF, inputs, dev, T, N, F, ni, order):
     kw = CONSTRAIN.prepare(m, CF, inputs, dev, T, N, F, ni, order)
@@ -403,17 +478,19 @@ MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 
 
-def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, constrain_exact=False, constrain_samples=0, **values):
+def of_options(logprob=False, constrain_beams=0, constrain_lookahead=False, constrain_exact=False, constrain_samples=0,
+               constrain_beam_closure=None, **values):
     """(record, value) of the first of MODES whose option is set in `values` (constrain: the flag bits or None; num_samples;
     beam_width); else the greedy record (its logprob form with `logprob`) and None.  constrain with constrain_beams = W > 0:
     the CONSTRAIN_BEAM record and W; with constrain_samples = R > 0: the CONSTRAIN_SAMPLE record and R (whatever look-ahead is
     set: the record reads it); with constrain_lookahead: the CONSTRAIN_AHEAD record and the flag bits; with constrain_exact: the
-    CONSTRAIN_EXACT record and the flag bits."""
+    CONSTRAIN_EXACT record and the flag bits; with constrain_beams = W > 0 and constrain_beam_closure: the CONSTRAIN_BEAM_AHEAD
+    record and W."""
     for mode in MODES[:-1]:
         v = values[mode.subject]
         if v is not None and (v or mode is CONSTRAIN):
             if mode is CONSTRAIN and constrain_beams:
-                return CONSTRAIN_BEAM, constrain_beams
+                return (CONSTRAIN_BEAM_AHEAD if constrain_beam_closure else CONSTRAIN_BEAM), constrain_beams
             if mode is CONSTRAIN and constrain_samples:
                 return CONSTRAIN_SAMPLE, constrain_samples
             if mode is CONSTRAIN and constrain_lookahead:

@@ -623,31 +623,10 @@ def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, m
     vis = visited if fw else one
     fol = one if (follows is not None and not (L and fw)) else follows
     entry, tail = "ff_pointer_constrained", ()
-    if ahead is not None and ahead[0] == "exact":
-        _, cycle_len, budget = ahead
-        if flags != _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT:
-            raise ValueError("the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT")
-        if S > EXACT_MAX_KEYS:
-            raise ValueError("pointer_constrained_exact takes at most %d keys (L + ntok; got %d)" % (EXACT_MAX_KEYS, S))
-        _dev(cycle_len, "cycle_len", torch.uint8)
-        if cycle_len.dim() != 2 or not cycle_len.is_contiguous() or cycle_len.size(0) < nw or cycle_len.size(1) != L:
-            raise ValueError("cycle_len must be a contiguous uint8 [>= %d, %d] tensor" % (nw, L))
-        if not 0 <= int(budget) <= 254:
-            raise ValueError("budget=%r: must be in 0..254" % (budget,))
-        byte = torch.zeros(1, device=dev, dtype=torch.uint8)      # (L = 0: nothing of the table is read)
-        entry, tail = "ff_pointer_constrained_exact", (_p(cycle_len if L else byte), int(budget))
-    elif ahead is not None:
-        _, close_dist, cycle_len, budget = ahead
-        if not flags & _L.FF_CONSTRAIN_CONNECT:
-            raise ValueError("the look-ahead needs FF_CONSTRAIN_CONNECT")
-        for x, name, shape in ((close_dist, "close_dist", (L, L)), (cycle_len, "cycle_len", (L,))):
-            _dev(x, name, torch.uint8)
-            if x.dim() != 1 + len(shape) or not x.is_contiguous() or x.size(0) < nw or tuple(x.shape[1:]) != shape:
-                raise ValueError("%s must be a contiguous uint8 [>= %d, %s] tensor" % (name, nw, ", ".join(str(v) for v in shape)))
-        if not 0 <= int(budget) <= 254:
-            raise ValueError("budget=%r: must be in 0..254" % (budget,))
-        byte = torch.zeros(1, device=dev, dtype=torch.uint8)      # (L = 0: nothing of the tables is read)
-        entry, tail = "ff_pointer_constrained_ahead", (_p(close_dist if L else byte), _p(cycle_len if L else byte), int(budget))
+    if ahead is not None:
+        what = "pointer_constrained_exact" if ahead[0] == "exact" else "pointer_constrained_ahead"
+        form, close_dist, cycle_len, budget = _lookahead_operands(ahead, flags, S, L, nw, dev, what)
+        entry, tail = "ff_" + what, ((_p(close_dist),) if form == 1 else ()) + (_p(cycle_len), budget)
     if draw is not None:
         uniforms, row_id, temperature, top_k, top_p = draw
         _dev(uniforms, "uniforms")
@@ -872,6 +851,59 @@ def beam_constrained_select(logits, scores, fin, dead, first, prev, visited, wid
     int32 words (ops.follow_table) or None when CONNECT is clear.  Row b belongs to wireframe b // (groups_per_wireframe * width).
     Returns dict(parent, next, fin, dead, first, prev [G * width] int32; scores fp32; visited; mask_rows [G * width, S] uint8:
     the rule's own mask of every non-empty unfinished beam; [rows]; [stats]): the new beams in rank order, best first."""
+    return _beam_constrained_step(logits, scores, fin, dead, first, prev, visited, width, flags, ntok, follows, memory, mask, kv_len,
+                                  groups_per_wireframe, term_range, want_rows, want_stats, counter, None)
+
+
+@_on_tensor_device
+def beam_constrained_select_ahead(logits, scores, fin, dead, first, prev, visited, width, flags, ntok, follows, lookahead, cycle_len,
+                                  budget, close_dist=None, memory=None, mask=None, kv_len=None, groups_per_wireframe=None,
+                                  term_range=(1, 4), want_rows=False, want_stats=False, counter=None):
+    """beam_constrained_select with a closure look-ahead in every beam's byte row (ff_beam_constrained_select_ahead, DESIGN.md
+    28).  lookahead "lookahead": pointer_constrained_ahead's row per beam (close_dist [W, L, L] and cycle_len [W, L] uint8,
+    ops.follow_distance); "exact": pointer_constrained_exact's (cycle_len only; flags must be NO_REPEAT | CONNECT, at most 2048
+    keys; one search per open beam over its own visited words).  budget in 0..254, shared by every beam of the launch.  Operands
+    and results are beam_constrained_select's; `dead` then also means "cannot close within the budget".  "lookahead" with both
+    tables zero is beam_constrained_select, bit for bit; width 1 is the constrained greedy step of the same form."""
+    if lookahead not in ("lookahead", "exact"):
+        raise ValueError("lookahead=%r: must be 'lookahead' or 'exact'" % (lookahead,))
+    ahead = ("ahead", close_dist, cycle_len, budget) if lookahead == "lookahead" else ("exact", cycle_len, budget)
+    return _beam_constrained_step(logits, scores, fin, dead, first, prev, visited, width, flags, ntok, follows, memory, mask, kv_len,
+                                  groups_per_wireframe, term_range, want_rows, want_stats, counter, ahead)
+
+
+def _lookahead_operands(ahead, flags, S, L, nw, dev, what):
+    """The checks of a look-ahead's operands that the constrained greedy and beam steps share: ahead = ("ahead", close_dist,
+    cycle_len, budget) or ("exact", cycle_len, budget) -> (form, close_dist or None, cycle_len, budget), one byte in place of the
+    tables at L = 0, where nothing of them is read."""
+    byte = torch.zeros(1, device=dev, dtype=torch.uint8)
+    if ahead[0] == "exact":
+        _, cycle_len, budget = ahead
+        if flags != _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT:
+            raise ValueError("the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT")
+        if S > EXACT_MAX_KEYS:
+            raise ValueError("%s takes at most %d keys (L + ntok; got %d)" % (what, EXACT_MAX_KEYS, S))
+        tables = ((cycle_len, "cycle_len", (L,)),)
+    else:
+        _, close_dist, cycle_len, budget = ahead
+        if not flags & _L.FF_CONSTRAIN_CONNECT:
+            raise ValueError("the look-ahead needs FF_CONSTRAIN_CONNECT")
+        tables = ((close_dist, "close_dist", (L, L)), (cycle_len, "cycle_len", (L,)))
+    for x, name, shape in tables:
+        _dev(x, name, torch.uint8)
+        if x.dim() != 1 + len(shape) or not x.is_contiguous() or x.size(0) < nw or tuple(x.shape[1:]) != shape:
+            raise ValueError("%s must be a contiguous uint8 [>= %d, %s] tensor" % (name, nw, ", ".join(str(v) for v in shape)))
+    if not 0 <= int(budget) <= 254:
+        raise ValueError("budget=%r: must be in 0..254" % (budget,))
+    if ahead[0] == "exact":
+        return 2, None, (cycle_len if L else byte), int(budget)
+    return 1, (close_dist if L else byte), (cycle_len if L else byte), int(budget)
+
+
+def _beam_constrained_step(logits, scores, fin, dead, first, prev, visited, width, flags, ntok, follows, memory, mask, kv_len,
+                           groups_per_wireframe, term_range, want_rows, want_stats, counter, ahead):
+    """beam_constrained_select (ahead None) and beam_constrained_select_ahead (ahead as _lookahead_operands takes it): the checks,
+    the outputs and the launch the two share."""
     _dev(logits, "logits"), _dev(scores, "scores")
     out = {}
     if logits.dim() != 2:
@@ -924,7 +956,12 @@ def beam_constrained_select(logits, scores, fin, dead, first, prev, visited, wid
         _p(scores), _p(fin), _p(dead), _p(first), _p(prev), _p(visited if fw else one),
         _p(out["scores"]), _p(out["fin"]), _p(out["dead"]), _p(out["first"]), _p(out["prev"]), _p(out["visited"] if fw else two),
         _p(out["mask_rows"]), _p(out["parent"]), _p(out["next"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter))
-    _L.check(_L.load().ff_beam_constrained_select(C.byref(d), _stream()), "ff_beam_constrained_select")
+    if ahead is None:
+        _L.check(_L.load().ff_beam_constrained_select(C.byref(d), _stream()), "ff_beam_constrained_select")
+        return out
+    form, close_dist, cycle_len, budget = _lookahead_operands(ahead, flags, S, L, nw, dev, "beam_constrained_select_ahead")
+    da = _L.BeamConstrainedAheadStep(d, form, _p(close_dist), _p(cycle_len), budget)
+    _L.check(_L.load().ff_beam_constrained_select_ahead(C.byref(da), _stream()), "ff_beam_constrained_select_ahead")
     return out
 
 

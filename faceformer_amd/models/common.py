@@ -76,6 +76,9 @@ class SurfaceFormerBase(nn.Module):
                                        # post_process.enclosedness_tol); inputs["follow_table"] overrides the built table
         self.constrain_beams = 0       # ... W in 1..8 = the beam search over the constrained keys, W beams per anchor;
                                        # 0 = the constrained greedy decode; only with constrain
+        self.constrain_beam_closure = None   # ... with "loops" and constrain_beams: "lookahead" / "exact" = the beam search under the
+                                       # closure look-ahead or the exact one; None = under the plain rule;
+                                       # inputs["close_dist"] / ["cycle_len"] override the built tables
         self.constrain_samples = 0     # ... R in 1..64 = R draws per anchor from the constrained keys under sample_temperature / sample_top_k /
                                        # sample_top_p; 0 = the constrained greedy decode; only with constrain, not with constrain_beams
         self.constrain_lookahead = False   # ... with "loops": also mask every edge from which the loop cannot close within
@@ -314,7 +317,11 @@ class SurfaceFormerBase(nn.Module):
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
         exact = getattr(self, "constrain_exact", False)         # (and this)
         CS = _modes.constrain_samples_value(getattr(self, "constrain_samples", 0), CF if parallel else 0, CB)     # (and this)
+        closure = getattr(self, "constrain_beam_closure", None)      # (and this)
         if not parallel:
+            if closure is not None:
+                _modes.constrain_beam_closure_value(closure, _modes.CONSTRAIN_MODES["loops"], 1)      # (the value alone)
+                raise ValueError("constrain_beam_closure is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
             if CS:
                 raise ValueError("constrain_samples is a SurfaceFormer_Parallel option (%s)" % _modes.SWITCH["constrain"].seq2seq)
             if CB:
@@ -332,7 +339,10 @@ class SurfaceFormerBase(nn.Module):
         EX = _modes.constrain_exact_value(exact, CF, CB, LA)
         if EX and not self.engine_supported():
             raise ValueError("constrain_exact needs the native engine: this model's constructor arguments take the sub-module loop")
-        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, LA, EX, CS, constrain=CF,
+        CL = _modes.constrain_beam_closure_value(closure, CF, CB, LA, EX, CS)
+        if CL and not self.engine_supported():
+            raise ValueError("constrain_beam_closure needs the native engine: this model's constructor arguments take the sub-module loop")
+        mode, value = _modes.of_options(getattr(self, "return_logprob", False), CB, LA, EX, CS, CL, constrain=CF,
                                         num_samples=int(getattr(self, "num_samples", 0) or 0), beam_width=int(getattr(self, "beam_width", 0) or 0))
         if value is not None:
             attr = mode.switches[0].attr
@@ -348,6 +358,11 @@ class SurfaceFormerBase(nn.Module):
             if mode is _modes.CONSTRAIN_BEAM:
                 _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, constrain_beams=value, follow_table=True,
                                                                S=inputs["input"].size(1) + self.num_token),
+                                     (int(self.token.face_type_offset), int(self.token.len)))
+            if mode is _modes.CONSTRAIN_BEAM_AHEAD:      # (the tables are made behind the encoder: the width and T are checked here)
+                _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, constrain_beams=value, constrain_beam_closure=CL,
+                                                               follow_table=True, close_dist=True, cycle_len=True,
+                                                               S=inputs["input"].size(1) + self.num_token, T=self.max_face_length),
                                      (int(self.token.face_type_offset), int(self.token.len)))
             if mode is _modes.CONSTRAIN_SAMPLE:     # (the operands are made behind the encoder: the values and T are checked here)
                 _modes.check_options(mode, _L.FF_PARALLEL, dict(constrain=CF, constrain_samples=value, follow_table=True, close_dist=True,
@@ -368,6 +383,15 @@ class SurfaceFormerBase(nn.Module):
                 shape = (max(self.max_face_length - 1, 1), len(ni) * max(ni) * value)
                 if tuple(torch.as_tensor(inputs["sample_uniforms"]).shape) != shape:
                     raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
+            if mode is _modes.CONSTRAIN_BEAM_AHEAD and CL == "exact":
+                L = inputs["input"].size(1)
+                if L + self.num_token > _modes.EXACT_MAX_KEYS:
+                    raise ValueError("constrain_beam_closure='exact' takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
+                                     % (_modes.EXACT_MAX_KEYS - self.num_token, L, _modes.EXACT_MAX_KEYS))
+                given = inputs.get("cycle_len")
+                shape = tuple(inputs["input"].shape[:2])
+                if given is not None and (torch.as_tensor(given).dtype != torch.uint8 or tuple(torch.as_tensor(given).shape) != shape):
+                    raise ValueError("cycle_len must be uint8 [%d, %d]" % shape)
             if mode is _modes.CONSTRAIN_EXACT or (mode is _modes.CONSTRAIN_SAMPLE and EX):
                 L = inputs["input"].size(1)
                 if L + self.num_token > _modes.EXACT_MAX_KEYS:

@@ -63,6 +63,11 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         cannot close within max_face_length through edges the row has not used, so a row can only dead-end right after the
         position that opened a loop.  cycle_len is built on the device (ops.follow_distance, hmax = max(T - 2, 1)) or taken from
         inputs["cycle_len"] (uint8 N x L) for the batch AS GIVEN.  The published keys are constrain's.
+        constrain_beam_closure = "lookahead" / "exact" (default None; only with constrain = "loops" and constrain_beams = W;
+        DESIGN.md 28): the beam search forms every beam's row with the closure look-ahead or the exact one, so that the W beams
+        are searched among continuations that can still close within max_face_length.  The tables are built on the device or
+        taken from inputs["close_dist"] / inputs["cycle_len"] as for constrain_lookahead / constrain_exact ("exact" needs
+        cycle_len only).  The published keys are constrain_beams'.
         constrain_samples = R in 1..64 (default 0; only with constrain, not with constrain_beams): R independent draws
         per anchor from the constrained row -- in the plain form, or with constrain_lookahead / constrain_exact in that form's
         -- under sample_temperature / sample_top_k / sample_top_p, with the uniforms of num_samples (sample_seed, or

@@ -1196,6 +1196,69 @@ int ff_decode_constrained_sample(const ff_model* m, const ff_decode_params* p,
                                  float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
                                  void* workspace, size_t workspace_bytes, const ff_constrain_sample_params* sample, ff_stream_t stream);
 
+/* ---- closure look-ahead (both forms) in the beam search over the loop-constrained decode (opt-in, parallel variant; entries added
+ * within ABI 105).  ff_decode_constrained_beam searches under the plain rule; the greedy and the sampled constrained
+ * decodes also run under the closure look-ahead and the exact one.  These entries are the beam search under those two forms.
+ *
+ * Selection.  ff_decode_constrained_beam's contract holds with one change: an unfinished, non-empty beam forms its byte row as
+ * ff_pointer_constrained_ahead (lookahead = 1) or ff_pointer_constrained_exact (lookahead = 2) forms it, not as
+ * ff_pointer_constrained does.
+ *   - All beams of a launch share the step's budget = T - 1 - position.
+ *   - lookahead = 1: the beam's own first / prev pick close_dist[w][first] while its loop is open and cycle_len[w] while it is
+ *     closed; an edge whose byte exceeds the budget is masked.
+ *   - lookahead = 2: one backward search per open beam, over that beam's own visited words (D_V of the exact look-ahead above);
+ *     cycle_len[w] while the loop is closed.
+ *   - The dead-end vote runs after these masks.  dead / dead_end therefore also mean "cannot close within T".
+ * Unchanged: the candidates are the live keys only; a row without a live key contributes token 0 at c_k - log S; order, ties,
+ * empty and finished beams; the state through the parent permutation, *_in -> *_out; reorder, stop rule, padding anchors,
+ * FF_DEDUP_PAD_ANCHORS and the packing.
+ *
+ * Identities (each is a test).
+ *   (a) width 1 equals the constrained greedy decode of the same form: tokens, steps and dead_end exact, the score the sum of
+ *       its logprob.
+ *   (b) lookahead = 1 with both tables all zero equals ff_decode_constrained_beam, bit for bit.
+ *   (c) For equal inputs every edge key that lookahead = 1 masks is masked by lookahead = 2.
+ *   (d) Under lookahead = 2 a beam can dead-end only right after the edge that opened a loop; every final beam that is non-empty,
+ *       not dead and ends in a terminator is an enclosed face.
+ *
+ * ff_beam_constrained_select_ahead: one step; ff_beam_constrained_step, then lookahead (1 or 2), close_dist [wireframes, L, L]
+ *   (lookahead = 1 only; not read otherwise), cycle_len [wireframes, L] and budget in 0..254.
+ * ff_decode_constrained_beam_ahead: ff_decode_constrained_beam with ff_constrain_beam_ahead_params; the step that selects position
+ *   p runs ff_beam_constrained_select_ahead with budget = T - 1 - p.  Plan, workspace layout, start state and packing are
+ *   ff_decode_constrained_beam's; the tables are operands, not workspace.
+ * FF_ERR_ARG before any launch for everything ff_decode_constrained_beam rejects, lookahead outside 1..2, and what
+ * ff_decode_constrained_ahead / ff_decode_constrained_exact reject (CONNECT clear, a NULL table, T > 256; exact: a flag bit clear,
+ * L + ntok > 2048).  ff_decode_constrained_beam_ahead_workspace_bytes equals ff_decode_constrained_beam_workspace_bytes. */
+typedef struct ff_beam_constrained_ahead_step {
+  ff_beam_constrained_step step;
+  int lookahead;
+  const unsigned char* close_dist;
+  const unsigned char* cycle_len;
+  int budget;
+} ff_beam_constrained_ahead_step;
+int ff_beam_constrained_select_ahead(const ff_beam_constrained_ahead_step* step, ff_stream_t stream);
+typedef struct ff_constrain_beam_ahead_params {
+  int width;
+  int flags;
+  const unsigned int* follows;
+  int lookahead;
+  const unsigned char* close_dist;
+  const unsigned char* cycle_len;
+  int64_t* beams;
+  float* scores;
+  int* dead_end;
+  int* trace_parent;
+} ff_constrain_beam_ahead_params;
+size_t ff_decode_constrained_beam_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
+                                                        int width);
+int ff_decode_constrained_beam_ahead(const ff_model* m, const ff_decode_params* p,
+                                     const float* memory, const unsigned char* mask, const int* kv_len,
+                                     const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+                                     int64_t* predict, int* steps_done, int* step_counts, float* pointer_out,
+                                     float* trace_logits, float* trace_best, float* trace_second, int* seq_of_row,
+                                     void* workspace, size_t workspace_bytes, const ff_constrain_beam_ahead_params* beam,
+                                     ff_stream_t stream);
+
 /* ---- device-side face extraction behind the parallel decode (opt-in; entries added within ABI 105) ----------------
  * The decode ends as token rows; the harness wants faces.  These entries restate, on device tensors, what faceformer_amd/faces.py
  * does with lists after the rows were copied to the host: the parse of a row (trainer.py:181-208), the enclosure walk and the

@@ -305,7 +305,7 @@ def _record_of_device(cfg, raw, item, rows, scored, beams, samples, dead_end, sa
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-                    constrain_samples=0):
+                    constrain_samples=0, constrain_beam_closure=None):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
@@ -313,7 +313,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     (constrain "no_repeat" / "loops" with the end-point tolerance constrain_tol), the beam search over its keys
     with `constrain_beams` beams per anchor, the closure look-ahead of "loops" (constrain_lookahead), its exact form
     (constrain_exact), `constrain_samples` draws per anchor from the constrained keys under temperature / top_k /
-    top_p / seed.
+    top_p / seed, the closure look-ahead of the constrained beam search (constrain_beam_closure "lookahead" /
+    "exact").
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -341,13 +342,15 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.constrain_samples = int(constrain_samples)
         model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
         model.sample_seed = int(seed)
+    if constrain_beam_closure:
+        model.constrain_beam_closure = str(constrain_beam_closure)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-             constrain_samples=0, device_faces=False):
+             constrain_samples=0, device_faces=False, constrain_beam_closure=None):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -364,7 +367,16 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes, with pred_dead_ends / pred_unclosed over all draws;
     device_faces (parallel model, single-rank runs only): the predicted faces of every record are extracted on the
     device (model.extract_faces: "enclosed" with the pairings as edge map for co-edge configs and under constrain, "parse"
-    otherwise) and the records are made from those arrays -- the same records."""
+    otherwise) and the records are made from those arrays -- the same records; constrain_beam_closure ("lookahead" / "exact",
+    only with constrain "loops" and constrain_beams, single-rank runs only) runs the constrained beam search
+    under the closure look-ahead or its exact form -- the record keys stay constrain_beams'."""
+    if constrain_beam_closure is not None:
+        if constrain_beam_closure not in ("lookahead", "exact"):
+            raise ValueError("--constrain-beam-closure must be lookahead or exact")
+        if constrain != "loops" or not constrain_beams:
+            raise ValueError("--constrain-beam-closure requires --constrain loops --constrain-beams W")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--constrain-beam-closure is not implemented for multi-rank runs")
     if device_faces:
         if cfg.model_class != "SurfaceFormer_Parallel":
             raise ValueError("--device-faces applies to SurfaceFormer_Parallel only")
@@ -413,7 +425,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         model = model.eval().to(device)
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
                     cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact,
-                    constrain_samples)
+                    constrain_samples, constrain_beam_closure)
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
@@ -549,6 +561,10 @@ def build_parser():
                              "gains pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes over the draws that did not "
                              "run into a dead end, and pred_dead_ends / pred_unclosed count all draws; single-process runs only, not "
                              "with --constrain-beams")
+    parser.add_argument("--constrain-beam-closure", choices=("lookahead", "exact"), default=None,
+                        help="with --constrain loops --constrain-beams W: the beam search forms every beam's row under the closure "
+                             "look-ahead (lookahead) or its exact form (exact), so that the W beams are searched among loops that "
+                             "can still close in time (DESIGN.md 28); same record keys as --constrain-beams; single-process runs only")
     return parser
 
 
@@ -571,7 +587,8 @@ def main(argv=None):
              score_labels=args.score_labels, sample=args.sample, temperature=args.temperature, top_k=args.top_k,
              top_p=args.top_p, seed=args.seed, constrain=args.constrain, constrain_beams=args.constrain_beams,
              constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact,
-             constrain_samples=args.constrain_samples, device_faces=args.device_faces)
+             constrain_samples=args.constrain_samples, device_faces=args.device_faces,
+             constrain_beam_closure=args.constrain_beam_closure)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
