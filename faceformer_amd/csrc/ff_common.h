@@ -159,7 +159,9 @@ int ff_forced_finalize(const int* tok, const float* lp_all, const int* greedy_al
 struct ff_sample_draw_io { const float* uniforms; int num_uniforms; const int* row_id; float temperature; int top_k; float top_p; };
 int ff_sample_draw_check(const char* op, const ff_sample_draw_io& d, int rows);
 int ff_pointer_sample_sync(const ff_step_io& io, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
-                           float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream);
+                           float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream,
+                           bool sequence_form = false);   // (the single-sequence decode's form: count_ge counts the rows unfinished after the step)
+int ff_sequence_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int R, int w0, int sos, hipStream_t st);
 int ff_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F, const int* num_input,
                    int pad_tok, int term_lo, int term_hi, hipStream_t st);
 int ff_sample_finalize(const int* tok, const float* lp, const int* fin, int Btot, int T, const int* steps_dev, const int* num_input,

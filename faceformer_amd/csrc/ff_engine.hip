@@ -35,6 +35,10 @@
 //   sample (ff_decode_sample): R sequences per anchor in the beam decode's layout, independent of each other -- no
 //     reorder.  ff_pointer_sample reads the caller's uniforms through a per-sequence row_id; records (token, log-probability,
 //     finished).
+//   sequence sample (ff_decode_sequence_sample, single-sequence variant): the sampled decode's plan, records and
+//     packing with F = 1 -- R draws per WIREFRAME, every one from SOS -- and the sequence form of ff_pointer_sample, whose counter
+//     is "rows unfinished after the step": the decode stops at the first step that leaves 0 (the parallel rule's test on another
+//     count; the cumulative EOS rule is not used).
 //   constrain (ff_decode_constrained): the default plan, one sequence per anchor.  ff_pointer_constrained masks
 //     the keys the enclosure walk could not accept; records and the rule's state (first, prev per step; visited words and the
 //     byte mask per sequence).
@@ -360,13 +364,13 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
   const ff_beam_params* beam() const { return static_cast<const ff_beam_params*>(prm); }          // (each for its own kind only)
   const ff_forced_params* forced() const { return static_cast<const ff_forced_params*>(prm); }
-  const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }
+  const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }   // (SAMPLE and SEQ_SAMPLE)
   const ff_constrain_ahead_params* ahead() const { return static_cast<const ff_constrain_ahead_params*>(prm); }
   const ff_constrain_exact_params* exact() const { return static_cast<const ff_constrain_exact_params*>(prm); }
   // (CONSTRAIN, CONSTRAIN_AHEAD and CONSTRAIN_EXACT: the four parameters the three share)
@@ -395,6 +399,7 @@ void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, con
     case Mode::CONSTRAIN_BEAM:
     case Mode::CONSTRAIN_BEAM_AHEAD:
     case Mode::CONSTRAIN_SAMPLE:
+    case Mode::SEQ_SAMPLE:   // (FF_SEQ2SEQ: a micro-batch is cut by sequences, chunk_max_seqs / R wireframes, at least one)
     case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
     case Mode::FORCED: {
       ff_decode_params q = *p;
@@ -524,6 +529,7 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
       break;
     }
     case Mode::SAMPLE:
+    case Mode::SEQ_SAMPLE:
       b.score = bp.take<float>(TB);
       b.finished = bp.take<int>(TB);
       b.row_id = bp.take<int>(Btot);
@@ -1119,6 +1125,8 @@ struct DecodeRun {
         return ff_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok, p->term_lo, p->term_hi, st);
       case Mode::SAMPLE:
         return ff_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F, ni, pad_tok, p->term_lo, p->term_hi, st);
+      case Mode::SEQ_SAMPLE:   // (Fc = R draws per wireframe)
+        return ff_sequence_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, G, c.w0, p->tok_sos, st);
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
       case Mode::CONSTRAIN_EXACT:
@@ -1229,11 +1237,12 @@ struct DecodeRun {
         if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.parent + out, c.Bc / W, W, st));
         return FF_OK;
       }
+      case Mode::SEQ_SAMPLE:   // (the same launch in its sequence form: the counter is "rows unfinished after the step")
       case Mode::SAMPLE: {   // (this step's uniforms are read through the chunk's row_id)
         const ff_sample_params* sp = mode.sample();
         const int rows = N * F * mode.G;
         return ff_pointer_sample_sync(sio, sp->uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, buf.finished + in, sp->temperature,
-                                      sp->top_k, sp->top_p, tok_out, buf.score + out, buf.finished + out, st);
+                                      sp->top_k, sp->top_p, tok_out, buf.score + out, buf.finished + out, st, mode.kind == Mode::SEQ_SAMPLE);
       }
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_EXACT:
@@ -1308,6 +1317,10 @@ struct DecodeRun {
     if (io.steps_done) *io.steps_done = forced_steps;
     return FF_OK;
   }
+  // Which counter the stop rule reads and how: cnt_ge and "the first step that leaves 0" for the parallel variant (tokens >=
+  // num_token of unfinished rows) and for the sequence sample mode (rows unfinished after the step); cnt_eq and the cumulative EOS
+  // count otherwise.
+  bool zero_rule() const { return p->variant == FF_PARALLEL || mode.kind == Mode::SEQ_SAMPLE; }
   // the stop rule over the first n steps' counters, per_chunk = [n][nch]
   bool stop_rule(const int* per_chunk, int n) {
     tot.assign((size_t)n, 0);
@@ -1316,7 +1329,7 @@ struct DecodeRun {
       for (int c = 0; c < nch; ++c) tot[(size_t)s] += v[(size_t)s * nch + c];
     const int* cnt = tot.data();
     if (p->stop_fn) return p->stop_fn(p->stop_user, cnt, n) != 0;   // the caller's (batch-global) rule
-    if (p->variant == FF_PARALLEL) {
+    if (zero_rule()) {
       for (int s = 0; s < n; ++s) if (cnt[s] == 0) return true;
     } else {
       int cum = 0;
@@ -1412,7 +1425,7 @@ struct DecodeRun {
     const int n_eval = p->stop_fn ? enq - p->sync_every : enq;
     if (n_eval <= 0) return FF_OK;
     std::vector<int> hcnt((size_t)n_eval * nch);
-    FF_RETURN_IF(read_back(hcnt.data(), p->variant == FF_PARALLEL ? buf.cnt_ge : buf.cnt_eq, hcnt.size()));
+    FF_RETURN_IF(read_back(hcnt.data(), zero_rule() ? buf.cnt_ge : buf.cnt_eq, hcnt.size()));
     stopped = stop_rule(hcnt.data(), n_eval);
     if (!stopped && retire) FF_RETURN_IF(retire_at(enq - 1, true));
     return FF_OK;
@@ -1454,6 +1467,7 @@ struct DecodeRun {
         return ff_constrain_beam_dead(buf.dead, Btot, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G, c.f0, c.b0,
                                       mode.cbeam().dead_end, main_st);
       }
+      case Mode::SEQ_SAMPLE:   // (F = 1, no de-duplication: num_input is not read)
       case Mode::SAMPLE:
         return ff_sample_finalize(buf.tok_all, buf.score, buf.finished, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
                                   c.Fc / G, c.f0, c.b0, mode.sample()->samples, mode.sample()->logprob, mode.sample()->scores, io.predict,
@@ -1486,7 +1500,7 @@ struct DecodeRun {
         FF_CHECK_HIP(hipEventRecord(pool->join_ev[s], sts[s]));
         FF_CHECK_HIP(hipStreamWaitEvent(main_st, pool->join_ev[s], 0));
       }
-    hipLaunchKernelGGL(steps_kernel, dim3(1), dim3(64), 0, main_st, buf.cnt_ge, buf.cnt_eq, nch, p->variant, N, enq,
+    hipLaunchKernelGGL(steps_kernel, dim3(1), dim3(64), 0, main_st, buf.cnt_ge, buf.cnt_eq, nch, zero_rule() ? FF_PARALLEL : p->variant, N, enq,
                        ((p->flags & FF_NO_STOP) || p->stop_fn) ? 1 : 0, buf.cnt_tot, buf.steps_dev);
     FF_CHECK_LAUNCH();
     for (const Chunk& c : chunks) FF_RETURN_IF(pack(c));
@@ -1735,6 +1749,37 @@ extern "C" int ff_decode_sample(const ff_model* m, const ff_decode_params* p, co
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::SAMPLE, sample->num_samples, sample));
+}
+
+extern "C" size_t ff_decode_sequence_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples) {
+  if (num_samples < 1 || num_samples > 64 || !p || p->variant != FF_SEQ2SEQ || p->F != 1) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_SAMPLE, num_samples));
+}
+
+extern "C" int ff_decode_sequence_sample(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
+                                         const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+                                         int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sample_params* sample,
+                                         ff_stream_t stream) {
+  const char* name = "ff_decode_sequence_sample";
+  FF_CHECK_ARG(m && p && sample, "%s: null model, params or sample params", name);
+  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1, "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has ff_decode_sample",
+               name);
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
+               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
+  FF_CHECK_ARG(sample->num_samples >= 1 && sample->num_samples <= 64, "%s: num_samples=%d outside 1..64", name, sample->num_samples);
+  FF_CHECK_ARG(sample->uniforms && sample->samples && sample->logprob && sample->scores && predict,
+               "%s: uniforms, samples, logprob, scores and predict are required", name);
+  FF_CHECK_ARG(p->N > 0 && (long long)p->N * sample->num_samples < (1LL << 31), "%s: bad sizes", name);
+  const int rows = p->N * sample->num_samples;   // (the draw's own check, with the step's text: the uniforms of one step)
+  FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{sample->uniforms, rows, nullptr, sample->temperature, sample->top_k,
+                                                            sample->top_p}, rows));
+  // the terminator range is the EOS token alone: SEP and the other special tokens do not finish a draw
+  ff_decode_params q = *p;
+  q.term_lo = p->tok_eos;
+  q.term_hi = p->tok_eos + 1;
+  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
+                                     stream),
+                    workspace, workspace_bytes, Mode(Mode::SEQ_SAMPLE, sample->num_samples, sample));
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {

@@ -22,6 +22,13 @@
 //
 // The uniform of a row is uniforms[row_id[b]], clamped into [0, 1 - 2^-24]: a draw is keyed by the OUTPUT row, never by the
 // sequence's place in a launch.  There is no random number generator in device code.
+//
+// Sequence form (opt-in, single-sequence variant): pointer_sample_kernel<true>, the same launch but for what a wave
+// adds to the stop counter -- 1 when its row is UNFINISHED AFTER this step (not finished before it, token outside the terminator
+// range), not "selected a token >= ge_bound": all draws of a single-sequence decode can select SEP in one step, so the parallel
+// rule would stop them.  A compile-time form: pointer_sample_kernel<false> is the launch the parallel decode always made.
+// sequence_sample_init_kernel is its start state (every draw at SOS, unfinished, row_id = w * R + k: no anchors, no padding
+// groups); the packing is sample_finalize_kernel with F = 1.
 #include <float.h>
 
 #include "ff_common.h"
@@ -42,6 +49,7 @@ struct SampleArgs {
   float temperature; int top_k; float top_p;
 };
 
+template <bool SEQ>
 __global__ __launch_bounds__(256) void pointer_sample_kernel(SampleArgs a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
@@ -64,7 +72,8 @@ __global__ __launch_bounds__(256) void pointer_sample_kernel(SampleArgs a) {
       const float mine = lane == owner ? ff_ld4(lrow + tok) : 0.f;
       const float lg = __shfl(mine, owner, FF_WAVE);
       lp = fmaxf((lg - m) - logf(lsum), FILL);   // saturates: no -inf, no NaN (lsum >= 1, every term finite)
-      nge = tok >= pa.ge_bound ? 1 : 0;
+      if (SEQ) nge = (tok >= pa.term_lo && tok < pa.term_hi) ? 0 : 1;   // unfinished after this step
+      else nge = tok >= pa.ge_bound ? 1 : 0;
     }
     if (lane == 0) {
       ff_st4i(a.tok + b, tok);
@@ -91,6 +100,17 @@ __global__ void sample_init_kernel(int* tok, float* lp, int* fin, int* row_id, i
   lp[i] = 0.f;
   fin[i] = done;
   row_id[i] = ((w0 + wl) * F + (f < F ? f : F - 1)) * R + k;
+}
+
+// Start state of one micro-batch of the sequence form: Bc = nw * R draws, draw k of the chunk's wl-th wireframe at i = wl * R + k.
+// Every draw starts from SOS (model.py:191) with log-probability 0, unfinished; row_id: its output row (w0 + wl) * R + k.
+__global__ void sequence_sample_init_kernel(int* tok, float* lp, int* fin, int* row_id, int Bc, int R, int w0, int sos) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bc) return;
+  tok[i] = sos;
+  lp[i] = 0.f;
+  fin[i] = 0;
+  row_id[i] = w0 * R + i;
 }
 
 // samples[(w, fo, k), :], logprob (same layout), scores and predict[(w, fo), :] = sample 0, from the per-step records (tok, lp,
@@ -144,21 +164,24 @@ int ff_sample_draw_check(const char* op, const ff_sample_draw_io& d, int B) {
 }
 
 int ff_pointer_sample_sync(const ff_step_io& io, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
-                           float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream) {
+                           float temperature, int top_k, float top_p, int* next_tok, float* logprob, int* fin_out, ff_stream_t stream,
+                           bool sequence_form) {
+  const char* op = sequence_form ? "ff_pointer_sequence_sample" : "ff_pointer_sample";
   const int B = io.rows, S = io.S;
   if (B == 0) return FF_OK;
-  FF_CHECK_ARG(B > 0 && S > 0 && io.rows_per_wireframe > 0, "ff_pointer_sample: bad sizes B=%d S=%d", B, S);
+  FF_CHECK_ARG(B > 0 && S > 0 && io.rows_per_wireframe > 0, "%s: bad sizes B=%d S=%d", op, B, S);
   SampleArgs a;
   memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_step_args(&a.p, "ff_pointer_sample", true, io));
-  FF_CHECK_ARG(next_tok && logprob && fin_out, "ff_pointer_sample: null pointer");
-  FF_RETURN_IF(ff_sample_draw_check("ff_pointer_sample", ff_sample_draw_io{uniforms, num_uniforms, row_id, temperature, top_k, top_p}, B));
+  FF_RETURN_IF(ff_step_args(&a.p, op, true, io));
+  FF_CHECK_ARG(next_tok && logprob && fin_out, "%s: null pointer", op);
+  FF_RETURN_IF(ff_sample_draw_check(op, ff_sample_draw_io{uniforms, num_uniforms, row_id, temperature, top_k, top_p}, B));
   a.uniforms = uniforms; a.num_uniforms = num_uniforms; a.row_id = row_id; a.fin_in = fin_in; a.fin_out = fin_out;
   a.tok = next_tok; a.logprob = logprob;
   a.temperature = temperature; a.top_k = top_k; a.top_p = top_p;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 12.0, st);
-  hipLaunchKernelGGL(pointer_sample_kernel, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  if (sequence_form) hipLaunchKernelGGL(pointer_sample_kernel<true>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(pointer_sample_kernel<false>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
@@ -171,6 +194,26 @@ extern "C" int ff_pointer_sample(float* logits, int ldlogits, int S, const unsig
   return ff_pointer_sample_sync(ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, term_lo, term_hi, ge_bound, memory, E,
                                            next_rows, ldnext, next_stats, count_ge, nullptr, nullptr},
                                 uniforms, num_uniforms, row_id, fin_in, temperature, top_k, top_p, next_tok, logprob, fin_out, stream);
+}
+
+// The sequence form of the step (single-sequence variant): ff_pointer_sample's arguments without ge_bound; count_unfinished +=
+// the number of rows unfinished after the step.
+extern "C" int ff_pointer_sequence_sample(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                          int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id,
+                                          const int* fin_in, float temperature, int top_k, float top_p, int term_lo, int term_hi,
+                                          int* next_tok, float* logprob, int* fin_out, const float* memory, int E, float* next_rows,
+                                          int ldnext, float* next_stats, int* count_unfinished, ff_stream_t stream) {
+  FF_CHECK_ARG(term_lo < term_hi, "ff_pointer_sequence_sample: empty terminator range [%d, %d)", term_lo, term_hi);
+  return ff_pointer_sample_sync(ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, term_lo, term_hi, 0, memory, E,
+                                           next_rows, ldnext, next_stats, count_unfinished, nullptr, nullptr},
+                                uniforms, num_uniforms, row_id, fin_in, temperature, top_k, top_p, next_tok, logprob, fin_out, stream,
+                                true);
+}
+
+int ff_sequence_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int R, int w0, int sos, hipStream_t st) {
+  hipLaunchKernelGGL(sequence_sample_init_kernel, dim3(ff_cdiv(Bc, 256)), dim3(256), 0, st, tok, lp, fin, row_id, Bc, R, w0, sos);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
 }
 
 int ff_sample_init(int* tok, float* lp, int* fin, int* row_id, int Bc, int Fc, int R, int f0, int w0, int F, const int* num_input,

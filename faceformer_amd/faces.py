@@ -25,7 +25,7 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
            "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance",
-           "face_rows", "face_votes", "faces_of_rows"]
+           "face_rows", "face_votes", "faces_of_rows", "parse_faces_samples_scored"]
 
 
 def _tok(token, name, default):
@@ -212,6 +212,27 @@ def parse_faces_scored(predicts, logprobs, num_edges, token):
         idx = _edge_indices(piece[:-1], ntok, num_edges)
         if idx:
             faces.append((0, idx, float(plp.sum())))
+    return faces
+
+
+def parse_faces_samples_scored(samples, logprobs, num_edges, token):
+    """The faces of a sampled single-sequence decode (SurfaceFormer.sequence_samples): samples [R, T] tokens and
+    logprobs [R, T] (predict_samples[w] / predict_sample_logprob[w]).  parse_faces_scored per draw; a face (as a SET of edge
+    indices) that occurs more than once in ONE draw is kept once, at its first place in the draw, with the best of its scores.
+    Returns [(0, (edge, ...), score)] in draw order, the form unique_faces_with_scores takes -- whose vote count is then the
+    number of DRAWS that produced the face."""
+    rows = np.asarray(samples, dtype=np.int64)
+    lps = np.asarray(logprobs, dtype=np.float64)
+    if rows.ndim != 2 or lps.shape != rows.shape:
+        raise ValueError("samples and logprobs must both be [R, T]")
+    faces = []
+    for row, lp in zip(rows, lps):
+        best = {}      # (insertion-ordered: the first place of every edge set in this draw)
+        for ftype, idx, score in parse_faces_scored(row, lp, num_edges, token):
+            key = tuple(sorted(set(idx)))
+            if key not in best or score > best[key][2]:
+                best[key] = (ftype, best[key][1] if key in best else idx, score)
+        faces.extend(best.values())
     return faces
 
 

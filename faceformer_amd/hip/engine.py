@@ -375,7 +375,7 @@ class PathEngine:
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
-               constrain_samples=None, constrain_beam_closure=None):
+               constrain_samples=None, constrain_beam_closure=None, sequence_samples=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -441,7 +441,26 @@ class PathEngine:
         the closure look-ahead (close_dist and cycle_len required) or the exact one (cycle_len required, at most 2048 keys, one
         search per open beam and step).  Outputs are constrain_beams'; `beam_dead_end` then also means "cannot close within T".
         W = 1 equals the constrain_lookahead / constrain_exact decode; "lookahead" with both tables zero equals the
-        constrain_beams decode."""
+        constrain_beams decode.
+
+        sequence_samples=R in 1..64 (single-sequence variant only, ff_decode_sequence_sample; None or 0: the greedy
+        decode above): R independent draws per WIREFRAME under temperature / top_k / top_p, all from tok_sos, off one encoding
+        and one set of cross-attention K | V; `uniforms` [T-1, N*R] fp32 on the device (step t of output row r reads
+        uniforms[t, r]).  A draw is finished by tok_eos alone; the decode stops after the first step that leaves no draw
+        unfinished (`steps`; `step_counts`: the draws unfinished after every step).  Also `samples` [N*R, T] int64 (row w*R + k is
+        draw k of wireframe w, zero behind its EOS and the stop step), `sample_logprob` (same layout) and `sample_scores` [N*R];
+        `predict` [N, T] is draw 0; with trace=True `logits` is [T-1, N*R, S] in output-row order.  No term_range.  Excludes every
+        other mode and option above, and stop_each_eos (the flag FF_STOP_EACH_EOS): the rule is per draw already.  temperature=0
+        equals, R times, the greedy FF_STOP_EACH_EOS decode cut behind every row's first EOS."""
+        SR = _modes.sequence_samples_value(sequence_samples)
+        if SR:
+            o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
+                     logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
+                     constrain=constrain is not None, sequence_samples=SR, temperature=temperature, top_k=top_k, top_p=top_p,
+                     uniforms=uniforms, trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
+            return self._decode_sequence_sample(memory, mask_u8, kv_len, variant, o, (
+                variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs,
+                ln_fuse_max_rows, flags, x3_min_rows), sync_every, tok_sos, tok_eos)
         W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
         CB = _modes.constrain_beams_value(constrain_beams, CF)
         LA = _modes.constrain_lookahead_value(constrain_lookahead, CF, CB)
@@ -541,6 +560,47 @@ class PathEngine:
             idx = rows.long()
             out["decoded_seqs"] = int(idx.max().item()) + 1 if B else 0
             out.update((key, t[:, idx]) for key, t in traced.items())
+        return out
+
+    def _decode_sequence_sample(self, memory, mask_u8, kv_len, variant, o, params, sync_every, tok_sos, tok_eos):
+        """decode(sequence_samples=R): the checks (ValueError before anything is launched), the outputs and the one call of
+        ff_decode_sequence_sample, whose argument list has no num_input, extra mask, pointer or best / second traces.
+        params: _params' arguments."""
+        mode = _modes.SEQUENCE_SAMPLE
+        if variant != _L.FF_SEQ2SEQ or o["F"] != 1:
+            raise ValueError("sequence_samples is a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant draws with num_samples")
+        _modes.check_options(mode, variant, o, None)
+        if params[-2] & _L.FF_STOP_EACH_EOS:
+            raise ValueError("sequence_samples excludes stop_each_eos (FF_STOP_EACH_EOS): every draw is finished by its own EOS already")
+        mode.operand(self, o)
+        prm = self._params(*params)
+        _dev(memory, "memory")
+        self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
+        N, S, E = memory.shape
+        T, R, dev = o["T"], o["sequence_samples"], self.device
+        prm.sync_every, prm.tok_sos, prm.tok_eos = sync_every, tok_sos, tok_eos
+        predict = torch.empty((N, T), device=dev, dtype=torch.int64)
+        steps_max = max(T - 1, 1)
+        traced = {"logits": torch.full((steps_max, N * R, S), float("nan"), device=dev, dtype=torch.float32)} if o["trace"] else {}
+        rows = torch.empty(N * R, device=dev, dtype=torch.int32)
+        extra, tail = _modes.outputs(mode, self, o, N, traced)
+        ws = self._workspace(self._lib.ff_decode_sequence_sample_workspace_bytes(C.byref(self.model), C.byref(prm), R))
+        steps = C.c_int(0)
+        counts = (C.c_int * steps_max)()
+        slots = (C.c_int * steps_max)()
+        prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
+        with torch.cuda.device(dev):
+            _L.check(self._lib.ff_decode_sequence_sample(C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len),
+                                                         _p(predict), C.byref(steps), counts, _p(traced.get("logits")), _p(rows),
+                                                         _p(ws), ws.numel(), *tail, _stream()), mode.entry)
+        sps = [int(v) for v in slots]
+        out = {"predict": predict, "steps": steps.value, "step_counts": list(counts)[: steps.value], "seq_of_row": rows,
+               "slots_per_step": sps, "slot_rows": sum((s + 1) * v for s, v in enumerate(sps))}
+        out.update(extra)
+        if o["trace"]:
+            idx = rows.long()
+            out["decoded_seqs"] = int(idx.max().item()) + 1
+            out["logits"] = traced["logits"][:, idx]
         return out
 
     def _params(self, variant, N, S, F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows, flags,

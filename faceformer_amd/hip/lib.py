@@ -344,6 +344,12 @@ SIGNATURES = {
                                                    C.POINTER(C.c_int), fptr,
                                                    fptr, C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, fptr, fptr, fptr,
                                                    C.c_size_t, C.POINTER(ConstrainBeamAheadParams), fptr]),
+    "ff_pointer_sequence_sample": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, fptr, fptr,
+                                             C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, fptr, fptr, fptr, fptr, C.c_int, fptr,
+                                             C.c_int, fptr, fptr, fptr]),
+    "ff_decode_sequence_sample_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
+    "ff_decode_sequence_sample": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t, C.POINTER(SampleParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
     "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
                                fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

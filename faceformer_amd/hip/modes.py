@@ -474,6 +474,38 @@ FORCED = Mode(
     tail=lambda o, ptrs, traced: (C.byref(_L.ForcedParams(_p(o["paths"]), _p(o["lengths_dev"]),
                                                           C.cast(o["lengths_host"], C.POINTER(C.c_int)), *ptrs)),))
 
+def _sequence_sample_values(o):
+    R = o["sequence_samples"]
+    if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= SAMPLE_MAX:
+        raise ValueError("sequence_samples=%r: must be in 1..%d" % (R, SAMPLE_MAX))
+    _sample_values(dict(o, num_samples=R))      # (temperature, top_k, top_p: the sampled decode's text)
+
+
+def _sequence_sample_operand(eng, o):
+    _sample_operand(eng, dict(o, F=1, num_samples=o["sequence_samples"]))
+
+
+def sequence_samples_value(sequence_samples):
+    """The count of a `sequence_samples` value: None / 0 -> 0 (the option is off); else 1..SAMPLE_MAX."""
+    if sequence_samples is None or (not isinstance(sequence_samples, bool) and sequence_samples == 0):
+        return 0
+    _sequence_sample_values(dict(sequence_samples=sequence_samples, temperature=1.0, top_k=0, top_p=1.0))
+    return int(sequence_samples)
+
+
+# The single-sequence model's sampling (DESIGN.md 29): R draws per WIREFRAME, every one from SOS, finished by EOS alone.  Outside
+# MODES: num_samples on that model stays the recorded rejection it is (SWITCH and every recorded text stay), and the option is
+# read where the single-sequence model decodes (SurfaceFormer.forward_eval) and refused everywhere else.  The terminator range is
+# the entry's own ([tok_eos, tok_eos + 1)): no term_range.  The entry has its own, shorter argument list (PathEngine.decode).
+SEQUENCE_SAMPLE = Mode(
+    subject="sequence_samples", excludes=_COMMON + ("beam_width", "num_samples", "constrain"), entry="ff_decode_sequence_sample",
+    term_range=False, parallel_only=False, per_anchor=True, values=_sequence_sample_values, values_first=True,
+    operand=_sequence_sample_operand, own=(("uniforms", _F32),), outs=SAMPLE.outs,
+    tail=lambda o, ptrs, traced: (C.byref(_L.SampleParams(o["sequence_samples"], float(o["temperature"]), int(o["top_k"]),
+                                                          float(o["top_p"]), _p(o["uniforms"]), *ptrs)),),
+    switches=(Switch("sequence_samples", 0, _NO_STOP_RULE % "sequence-sampled", None, False),),
+    model_excludes=("return_logprob", "an extra mask"))
+
 MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several mode options, the first one's record reports
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 

@@ -548,6 +548,47 @@ def pointer_sample(logits, uniforms, temperature=1.0, top_k=0, top_p=1.0, row_id
 
 
 @_on_tensor_device
+def pointer_sequence_sample(logits, uniforms, temperature=1.0, top_k=0, top_p=1.0, row_id=None, fin=None, memory=None, mask=None,
+                            kv_len=None, seqs_per_group=1, term_range=(3, 4), want_rows=False, want_stats=False, counter=None):
+    """One sampling step of the single-sequence decode (ff_pointer_sequence_sample): pointer_sample's operands,
+    selection and outputs; `counter` (int32, one element) += the number of rows UNFINISHED AFTER the step -- not finished before it
+    and with a token outside term_range = [EOS, EOS + 1) -- instead of the rows that selected a token >= ge_bound."""
+    _dev(logits, "logits"), _dev(uniforms, "uniforms")
+    out = {}
+    B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
+    if uniforms.dim() != 1 or not uniforms.is_contiguous() or uniforms.numel() < 1:
+        raise ValueError("uniforms must be a contiguous non-empty 1-D tensor")
+    U = uniforms.numel()
+    t, k, pp = float(temperature), int(top_k), float(top_p)
+    if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
+        raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]")
+    if not int(term_range[0]) < int(term_range[1]):
+        raise ValueError("term_range must be (lo, hi) with lo < hi")
+    if row_id is not None:
+        _dev(row_id, "row_id", torch.int32)
+        if row_id.dim() != 1 or row_id.numel() != B or (B and (int(row_id.min()) < 0 or int(row_id.max()) >= U)):
+            raise ValueError("row_id must hold one index in [0, %d) per row of logits" % U)
+        row_id = row_id.contiguous()
+    elif U < B:
+        raise ValueError("%d uniforms for %d rows" % (U, B))
+    if fin is not None:
+        _dev(fin, "fin", torch.int32)
+        if fin.dim() != 1 or fin.numel() != B:
+            raise ValueError("fin must hold one flag per row of logits")
+        fin = fin.contiguous()
+    dev = logits.device
+    out = dict({"next": torch.empty(B, device=dev, dtype=torch.int32), "logprob": torch.empty(B, device=dev, dtype=torch.float32),
+                "fin": torch.empty(B, device=dev, dtype=torch.int32)}, **out)
+    if counter is not None:
+        _dev(counter, "counter", torch.int32)
+    _L.check(_L.load().ff_pointer_sequence_sample(
+        _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(uniforms), U, _p(row_id), _p(fin), t, k, pp,
+        int(term_range[0]), int(term_range[1]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(memory), E, _p(rows), E,
+        _p(stats), _p(counter), _stream()), "ff_pointer_sequence_sample")
+    return out
+
+
+@_on_tensor_device
 def follow_table(starts, ends, num_input, tol):
     """The co-edge follow table of N wireframes (ff_follow_table).  starts / ends [N, L, 2] fp32: (x, y) of every
     co-edge's first and last point; num_input [N] int32.  Returns bits [N, L, ceil(L/32)] int32 (the uint32 words): bit b of row

@@ -90,6 +90,8 @@ class SurfaceFormerBase(nn.Module):
                                        # (inputs["faces"]: ops.face_rows + ops.face_votes behind the decode);
                                        # "enclosed" walks the enclosure rule on the follow table (constrain_tol) and counts
                                        # closed faces only; inputs["edge_map"] (int32 N x L) maps edges before the grouping
+        self.sequence_samples = 0      # single-sequence model: R in 1..64 = R independent draws per WIREFRAME under sample_temperature /
+                                       # sample_top_k / sample_top_p, decoded together off one encoding; 0 = greedy
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
         self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
         self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
@@ -312,6 +314,9 @@ class SurfaceFormerBase(nn.Module):
         width / number of samples / constraint flag bits, None for greedy), after the rules only the model can check: what the
         single-sequence model does not take; an opt-in mode needs the native engine and excludes what its record lists."""
         self._extract_faces_value(inputs, parallel)
+        if parallel and getattr(self, "sequence_samples", 0):
+            raise ValueError("sequence_samples is a SurfaceFormer option (draws per wireframe of the single-sequence model); "
+                             "SurfaceFormer_Parallel draws per anchor with num_samples")
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
@@ -413,6 +418,8 @@ class SurfaceFormerBase(nn.Module):
             for sw in mode.switches:
                 if not sw.scored and sw.on(self):
                     raise ValueError("score() excludes %s: set model.%s = %r to score given paths" % (sw.attr, sw.attr, sw.off))
+        if getattr(self, "sequence_samples", 0):
+            raise ValueError("score() excludes sequence_samples: set model.sequence_samples = 0 to score given paths")
         if getattr(self, "constrain_samples", 0):     # (an option of constrain: without constrain the lines above have not raised)
             raise ValueError("score() excludes constrain_samples: set model.constrain_samples = 0 to score given paths")
         if not self.engine_supported():

@@ -9,6 +9,7 @@ batch size (reference model.py:191,207-210), zero padding afterwards.
 import torch
 
 from ..hip import lib as _L
+from ..hip import modes as _modes
 from .common import SurfaceFormerBase
 
 
@@ -38,10 +39,19 @@ class SurfaceFormer(SurfaceFormerBase):
 
     def forward_eval(self, inputs):
         """inputs: input N x L x P x D, input_mask N x L (True = padding), label N x T (shape only).
-        Adds predict N x T (int64), embedding N x S x E, pointer N x t_last x E."""
+        Adds predict N x T (int64), embedding N x S x E, pointer N x t_last x E.
+
+        sequence_samples = R in 1..64 (0: the greedy decode above): R independent draws per wireframe under
+        sample_temperature / sample_top_k / sample_top_p, decoded together off one encoding.  The uniforms come from
+        torch.Generator(device).manual_seed(sample_seed), or from inputs["sample_uniforms"] [T-1, N*R] fp32 (column w*R + k).
+        Every draw starts from SOS and is finished by its own EOS; the decode stops once every draw is.  Adds predict_samples
+        N x R x T (zero behind a draw's EOS and the stop step), predict_sample_logprob N x R x T (the model's log-probability of
+        every drawn token) and predict_sample_scores N x R (their sums); predict is draw 0; embedding as above; no pointer.
+        stop_each_eos is not looked at.  Not with return_logprob, an extra mask or the sub-module loop (ValueError)."""
         label = inputs["label"]
         T = self.num_labels
         self._decode_mode(inputs, parallel=False)       # (the records' reasons: hip/modes.py)
+        R = self._sequence_samples_value(inputs)
         if inputs["input"].size(0) == 0:     # an empty batch: the reference's loop stops after its first step (0 EOS == batch size 0, model.py:207)
             dev, S = inputs["input"].device, inputs["input"].size(1) + self.num_token
             inputs["embedding"] = torch.zeros((0, S, self.num_model), device=dev)
@@ -49,6 +59,11 @@ class SurfaceFormer(SurfaceFormerBase):
             inputs["predict"] = torch.zeros((0, T), dtype=torch.long, device=dev)
             if getattr(self, "return_logprob", False):
                 inputs["predict_logprob"] = torch.zeros((0, T), device=dev)
+            if R:
+                del inputs["pointer"]
+                inputs["predict_samples"] = torch.zeros((0, R, T), dtype=torch.long, device=dev)
+                inputs["predict_sample_logprob"] = torch.zeros((0, R, T), device=dev)
+                inputs["predict_sample_scores"] = torch.zeros((0, R), device=dev)
             return inputs
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             return self._forward_eval_modules(inputs, parallel=False)
@@ -57,6 +72,8 @@ class SurfaceFormer(SurfaceFormerBase):
                              "needed" % (label.size(1), T - 1))
         want_lp = bool(getattr(self, "return_logprob", False))
         eng, memory, mask, kv_len = self._encode(inputs)
+        if R:
+            return self._forward_eval_samples(inputs, eng, memory, mask, kv_len, T, R)
         out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1,
@@ -68,6 +85,49 @@ class SurfaceFormer(SurfaceFormerBase):
         inputs["predict"] = out["predict"]
         if want_lp:
             inputs["predict_logprob"] = out["logprob"]
+        return inputs
+
+    def _sequence_samples_value(self, inputs):
+        """sequence_samples as 0 or R in 1..64, after the rules only the model can check (ValueError, before anything is
+        launched): the native engine, what the record excludes, the parameters' ranges, the shape of inputs["sample_uniforms"]."""
+        R = _modes.sequence_samples_value(getattr(self, "sequence_samples", 0))
+        if not R:
+            return 0
+        mode = _modes.SEQUENCE_SAMPLE
+        if not self.engine_supported():
+            raise ValueError("sequence_samples needs the native engine: this model's constructor arguments take the sub-module loop")
+        if getattr(self, "return_logprob", False) or inputs.get("extra_mask") is not None:
+            raise ValueError("sequence_samples excludes %s and %s" % mode.model_excludes)
+        _modes.check_options(mode, _L.FF_SEQ2SEQ, dict(sequence_samples=R, temperature=self.sample_temperature,
+                                                      top_k=self.sample_top_k, top_p=self.sample_top_p), None)
+        u = inputs.get("sample_uniforms")
+        shape = (max(self.num_labels - 1, 1), inputs["input"].size(0) * R)
+        if u is not None and tuple(torch.as_tensor(u).shape) != shape:
+            raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
+        return R
+
+    def _forward_eval_samples(self, inputs, eng, memory, mask, kv_len, T, R):
+        """forward_eval with sequence_samples = R behind the encoder.  The wireframes are decoded in batch order (this model
+        applies no permutation), so column w*R + k of the uniforms is draw k of wireframe w as given."""
+        N, dev = memory.size(0), memory.device
+        u = inputs.get("sample_uniforms")
+        if u is None:
+            gen = torch.Generator(device=dev).manual_seed(int(self.sample_seed))
+            u = torch.rand((max(T - 1, 1), N * R), generator=gen, device=dev, dtype=torch.float32)
+        else:
+            u = torch.as_tensor(u).to(device=dev, dtype=torch.float32).contiguous()
+        out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
+                         chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
+                         chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1, flags=self.decode_flags,
+                         x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS,
+                         tok_eos=self.token.EOS, sequence_samples=R, temperature=float(self.sample_temperature),
+                         top_k=int(self.sample_top_k), top_p=float(self.sample_top_p), uniforms=u)
+        inputs["embedding"] = memory
+        inputs["predict"] = out["predict"]
+        inputs["predict_samples"] = out["samples"].view(N, R, T)
+        inputs["predict_sample_logprob"] = out["sample_logprob"].view(N, R, T)
+        inputs["predict_sample_scores"] = out["sample_scores"].view(N, R)
+        self.last_sample_stats = {"steps": out["steps"], "slot_rows": out["slot_rows"]}
         return inputs
 
     def label_paths(self, inputs):

@@ -1320,6 +1320,52 @@ int ff_face_votes(const unsigned int* set_bits, const int* len, const int* type,
                   int words, int flags, int* rep, int* votes, double* best, int* major, int* num_faces, void* workspace,
                   size_t workspace_bytes, ff_stream_t stream);
 
+/* ---- sampling over the single-sequence decode (opt-in, FF_SEQ2SEQ; entries added within ABI 105) ------------------
+ * The single-sequence reference decodes ONE greedy sequence per wireframe: select_next takes the argmax of the masked logit row
+ * (model.py:161-167) inside the loop of model.py:193-210, which starts every sequence from SOS (model.py:191).  These entries
+ * restate those call sites with ONE change: the token is DRAWN from the masked row by ff_decode_sample's rule (steps 1-7 above,
+ * unchanged, bit for bit: one copy in device code), and the loop carries num_samples = R independent draws per wireframe off one
+ * encoding and one set of cross-attention K | V.
+ *
+ * Layout.  The decode runs N*R sequences; draw k of wireframe w is output row w*R + k, and sequence i of the engine belongs to
+ *   wireframe i / R (cross-attention, masks, kv_len, the pointer GEMM and the row gather).
+ * Start.  Every draw starts from tok_sos; log-probability 0 in column 0.
+ * Finish.  A draw is finished from the first position >= 1 holding tok_eos: the terminator range is [tok_eos, tok_eos + 1),
+ *   whatever term_lo / term_hi of the parameters hold.  SEP and the other special tokens do not finish a draw.  A finished draw
+ *   appends token 0, draws nothing, has log-probability 0 from then on; its output is zero after its EOS.
+ * Stop.  After the first step after which every draw of the call is finished, else after T-1 steps; *steps_done reports that step,
+ *   output past it is zero, and steps enqueued past it change nothing that is read.  step_counts[s] = the draws unfinished after
+ *   step s.  (ff_decode_sample's rule -- no unfinished row selected an edge token -- would be wrong here: all draws can select
+ *   SEP in one step.  ff_decode's cumulative EOS count cannot go wrong here either, a finished draw emits 0 and never a second
+ *   EOS, but is not used.)  FF_STOP_EACH_EOS is refused: the rule above is already per draw.
+ *
+ * ff_pointer_sequence_sample: one step; ff_pointer_sample's arguments without ge_bound, and count_unfinished (optional) += the
+ *   number of rows unfinished after the step (not finished before it, token outside [term_lo, term_hi)); term_lo < term_hi.
+ * ff_decode_sequence_sample: memory / mask / kv_len as ff_decode; then
+ *   predict  [N, T] int64: draw 0 of every wireframe.
+ *   sample:  ff_sample_params -- uniforms [max(T-1, 1), N*R] fp32 DEVICE (step t of output row r reads uniforms[t, r], whatever
+ *            micro-batch the sequence decodes in); samples [N*R, T] int64, logprob (same layout) fp32, scores [N*R] fp32 (the kept
+ *            log-probabilities added in ascending position, fp64 accumulator, rounded once).
+ *   trace_logits (optional) [T-1, N*R, S] indexed by decoded sequence (seq_of_row [N*R] maps output rows to them): the MASKED row of
+ *            every sequence unfinished before the step.
+ *   A micro-batch holds chunk_max_seqs / R wireframes (at least one).  With temperature 0 every draw of wireframe w is the greedy
+ *   FF_STOP_EACH_EOS decode's row w cut behind its first EOS, with the same steps.
+ * FF_ERR_ARG before any launch for: FF_PARALLEL or F != 1, FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS, a
+ * stop_fn, num_samples outside 1..64, temperature < 0 or not finite, top_k < 0, top_p outside (0, 1], a NULL uniforms / samples /
+ * logprob / scores / predict.  There is no extra mask, pointer_out or best / second trace argument.
+ * ff_decode_sequence_sample_workspace_bytes: ff_decode_sample_workspace_bytes' rules with R sequences per wireframe (0 for what
+ * the entry refuses).  Every other entry launches and lays out what it did before these. */
+int ff_pointer_sequence_sample(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                               int seqs_per_group, const float* uniforms, int num_uniforms, const int* row_id, const int* fin_in,
+                               float temperature, int top_k, float top_p, int term_lo, int term_hi, int* next_tok, float* logprob,
+                               int* fin_out, const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                               int* count_unfinished, ff_stream_t stream);
+size_t ff_decode_sequence_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples);
+int ff_decode_sequence_sample(const ff_model* m, const ff_decode_params* p,
+                              const float* memory, const unsigned char* mask, const int* kv_len,
+                              int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
+                              void* workspace, size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,7 +147,7 @@ def score_batch(model, batch):
 
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
-              constrained_beams=None, constrained_samples=None, device_faces=None):
+              constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -170,6 +170,10 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     also gets `pred_sample_faces`, `pred_sample_face_scores` and `pred_sample_face_votes` as under --sample, over the draws that
     did not run into a dead end; `pred_faces` stays what draw 0 (pred) gives, and `pred_dead_ends` / `pred_unclosed` are counted
     over ALL draws of the wireframe's own anchors.
+    sequence_samples (--sequence-samples, single-sequence model; (tokens [R, T], log-probabilities [R, T]) of this sample): the
+    record also gets `pred_sample_faces`, `pred_sample_face_scores` and `pred_sample_face_votes`, the de-duplicated faces over ALL
+    draws ranked by their best score, with the number of DRAWS that produced each (a face twice in one draw counts once);
+    `pred_faces` stays what draw 0 (pred) gives.
     device_faces (--device-faces; this sample's slice of the model's inputs["faces"]): the predicted faces of
     every key above come from these arrays (faces.faces_of_rows) instead of from pred, beams and samples, which are then not
     read; label faces, the metrics and the JSON text are made here as before."""
@@ -252,6 +256,12 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["pred_sample_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
         rec["pred_sample_face_scores"] = [s for _, _, s, _ in ranked]
         rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
+    if sequence_samples is not None:
+        sf = FZ.parse_faces_samples_scored(sequence_samples[0], sequence_samples[1], len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(sf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_sample_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_sample_face_scores"] = [s for _, _, s, _ in ranked]
+        rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
@@ -305,7 +315,7 @@ def _record_of_device(cfg, raw, item, rows, scored, beams, samples, dead_end, sa
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-                    constrain_samples=0, constrain_beam_closure=None):
+                    constrain_samples=0, constrain_beam_closure=None, sequence_samples=0):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
@@ -314,7 +324,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     with `constrain_beams` beams per anchor, the closure look-ahead of "loops" (constrain_lookahead), its exact form
     (constrain_exact), `constrain_samples` draws per anchor from the constrained keys under temperature / top_k /
     top_p / seed, the closure look-ahead of the constrained beam search (constrain_beam_closure "lookahead" /
-    "exact").
+    "exact"), `sequence_samples` draws per wireframe of the single-sequence model under temperature / top_k / top_p /
+    seed.
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -344,13 +355,17 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.sample_seed = int(seed)
     if constrain_beam_closure:
         model.constrain_beam_closure = str(constrain_beam_closure)
+    if sequence_samples:
+        model.sequence_samples = int(sequence_samples)
+        model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
+        model.sample_seed = int(seed)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-             constrain_samples=0, device_faces=False, constrain_beam_closure=None):
+             constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -369,7 +384,19 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     device (model.extract_faces: "enclosed" with the pairings as edge map for co-edge configs and under constrain, "parse"
     otherwise) and the records are made from those arrays -- the same records; constrain_beam_closure ("lookahead" / "exact",
     only with constrain "loops" and constrain_beams, single-rank runs only) runs the constrained beam search
-    under the closure look-ahead or its exact form -- the record keys stay constrain_beams'."""
+    under the closure look-ahead or its exact form -- the record keys stay constrain_beams'; sequence_samples = R (1..64,
+    single-sequence model, single-rank runs only, not with scores, score_labels, sample or device_faces) draws R
+    sequences per wireframe under temperature / top_k / top_p / seed and adds pred_sample_faces / pred_sample_face_scores /
+    pred_sample_face_votes; pred_faces stays draw 0's."""
+    if sequence_samples:
+        if isinstance(sequence_samples, bool) or not isinstance(sequence_samples, int) or not 1 <= sequence_samples <= 64:
+            raise ValueError("--sequence-samples must be a count in 1..64")
+        if cfg.model_class != "SurfaceFormer":
+            raise ValueError("--sequence-samples applies to SurfaceFormer only (SurfaceFormer_Parallel draws per anchor with --sample)")
+        if scores or score_labels or sample or device_faces:
+            raise ValueError("--sequence-samples does not combine with --scores, --score-labels, --sample or --device-faces")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--sequence-samples is not implemented for multi-rank runs")
     if constrain_beam_closure is not None:
         if constrain_beam_closure not in ("lookahead", "exact"):
             raise ValueError("--constrain-beam-closure must be lookahead or exact")
@@ -425,7 +452,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         model = model.eval().to(device)
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
                     cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact,
-                    constrain_samples, constrain_beam_closure)
+                    constrain_samples, constrain_beam_closure, sequence_samples)
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
@@ -446,6 +473,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         wanted.append(("constrained_beams", ("predict_beams", "predict_beam_scores", "predict_beam_dead_end")))
     if constrain_samples:
         wanted.append(("constrained_samples", ("predict_samples", "predict_sample_scores", "predict_sample_dead_end")))
+    if sequence_samples:
+        wanted.append(("sequence_samples", ("predict_samples", "predict_sample_logprob")))
     if device_faces:
         wanted.append(("device_faces", ("faces",)))
     for b0 in range(lo, hi, batch_size):
@@ -561,6 +590,13 @@ def build_parser():
                              "gains pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes over the draws that did not "
                              "run into a dead end, and pred_dead_ends / pred_unclosed count all draws; single-process runs only, not "
                              "with --constrain-beams")
+    parser.add_argument("--sequence-samples", type=int, default=0, metavar="R",
+                        help="single-sequence model: R (1..64) independent draws per wireframe instead of the argmax, decoded "
+                             "together off one encoding under --temperature / --top-k / --top-p / --seed (DESIGN.md 29); pred_faces "
+                             "come from draw 0, and every JSON record gains pred_sample_faces / pred_sample_face_scores / "
+                             "pred_sample_face_votes: the faces of all draws, de-duplicated, ranked by score, with the number of "
+                             "draws that produced each; single-process runs only, not with --scores, --score-labels, --sample or "
+                             "--device-faces")
     parser.add_argument("--constrain-beam-closure", choices=("lookahead", "exact"), default=None,
                         help="with --constrain loops --constrain-beams W: the beam search forms every beam's row under the closure "
                              "look-ahead (lookahead) or its exact form (exact), so that the W beams are searched among loops that "
@@ -588,7 +624,7 @@ def main(argv=None):
              top_p=args.top_p, seed=args.seed, constrain=args.constrain, constrain_beams=args.constrain_beams,
              constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact,
              constrain_samples=args.constrain_samples, device_faces=args.device_faces,
-             constrain_beam_closure=args.constrain_beam_closure)
+             constrain_beam_closure=args.constrain_beam_closure, sequence_samples=args.sequence_samples)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
