@@ -1,7 +1,7 @@
 // Beam search over the pointer head (opt-in, parallel variant): one step's top-W selection over the W x S
 // candidates of every group (the W beams of one anchor), and the prefix reorder that follows it.
 //
-// beam_select_kernel<W>: one wavefront per group.  For each non-empty unfinished beam it masks and reduces the raw logit row
+// beam_select_kernel<W, FORM>: one wavefront per group.  For each non-empty unfinished beam it masks and reduces the raw logit row
 // exactly as pointer_reduce_kernel does (ff_pointer_mask_reduce<true>, ff_device.h: the row maximum m and sum exp(l - m)), every
 // lane then walks its strided keys once more and keeps the W best candidates c_k + (l[s] - m) - log(sum) in the sorted register
 // list of ff_select.h (insert, walk, butterfly merge, "lane k takes rank k": shared with the constrained beam kernel).
@@ -10,6 +10,14 @@
 //
 // L0 fold: the appended rows are written by ff_pointer_append_row, the greedy pointer launch's own gather, so they carry their
 // LayerNorm segment statistics when the engine asks for them (FF_L0_FOLD): a beam decode folds layer 0 as a greedy one does.
+//
+// Sequence forms (opt-in, single-sequence variant): beam_select_kernel<W, FORM> is one launch in three compile-time
+// forms that differ ONLY in what a wave adds to the stop counter.  FORM 0 is the parallel decode's launch as it always was (kept
+// candidates of unfinished beams with a token >= ge_bound).  FORM 1 ("all") adds the group's non-empty beams that are UNFINISHED
+// AFTER this step; FORM 2 ("best") adds 1 when the group's rank 0 is unfinished after it.  All W beams of a single-sequence decode
+// can select SEP in one step, so the parallel count would stop them.  sequence_beam_init_kernel is the start state (every beam at
+// SOS, beam 0 with score 0: no anchors, no padding groups); the packing is beam_finalize_kernel with F = 1, which then also
+// writes the finished flags of the stop step's row.
 //
 // beam_reorder_kernel: one block per (position, group) moves rows[j][g][k] <- rows[j][g][parent[k]] of up to two row arrays
 // (the engine's x0 and layer-0 q|k|v) in place through LDS; a group whose parent map is the identity returns at once.
@@ -31,7 +39,7 @@ struct BeamArgs {
   int* parent; int* tok;     // [B] out
 };
 
-template <int W>
+template <int W, int FORM>
 __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
@@ -69,7 +77,9 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamArgs a) {
     const int pfin = __shfl(my_f, par, FF_WAVE);
     const int tk = (some && !pfin) ? ix - par * S : 0;
     const int nfin = some ? (pfin || (tk >= pa.term_lo && tk < pa.term_hi) ? 1 : 0) : 0;
-    nge = __popcll(__ballot(some && !pfin && tk >= pa.ge_bound));
+    if (FORM == 0) nge = __popcll(__ballot(some && !pfin && tk >= pa.ge_bound));
+    else if (FORM == 1) nge = __popcll(__ballot(some && !nfin));   // non-empty beams unfinished after this step
+    else nge = (int)(__ballot(some && !nfin) & 1ull);              // the group's rank 0 unfinished after this step
     if (a.hist) {
       // positions are independent of each other: 64 / W of them per pass, every lane loads its entry before any lane stores
       const int ppp = 64 / W, k = lane % W, jl = lane / W;
@@ -147,14 +157,28 @@ __global__ void beam_init_kernel(int* tok, float* score, int* fin, int* parent, 
   parent[i] = k;
 }
 
+// Start state of one micro-batch of the sequence forms: Bc = nw * W beams, beam k of the chunk's wl-th wireframe at i = wl * W + k.
+// Every beam holds SOS (model.py:191), unfinished; beam 0 has score 0, the others are empty (-inf).
+__global__ void sequence_beam_init_kernel(int* tok, float* score, int* fin, int* parent, int Bc, int W, int sos) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bc) return;
+  const int k = i % W;
+  tok[i] = sos;
+  score[i] = k == 0 ? 0.f : -INFINITY;
+  fin[i] = 0;
+  parent[i] = k;
+}
+
 // beams[(w, fo, k), :], scores and predict[(w, fo), :] = beam 0, from the per-step records (tok, parent: [T, Btot]; score:
 // [T, Btot], row s = the state after s steps).  The arrangement is the one after `steps` steps, the tokens come from walking
 // the parents back -- steps the host had enqueued past the stop step are never looked at, so the result does not depend on
 // when the host saw the stop.  Rows fo >= num_input[w] of a de-duplicated decode read the one padding-anchor group.
+// finished (optional, with fin [T, Btot]): the beams' finished flags of the stop step's row, in the beams' order.
 __global__ void beam_finalize_kernel(const int* __restrict__ tok, const int* __restrict__ parent, const float* __restrict__ score,
                                      int Btot, int T, const int* __restrict__ steps_p, const int* __restrict__ num_input, int dedup,
                                      int F, int W, int w0, int nw, int Fc, int f0, int b0, int64_t* __restrict__ beams,
-                                     float* __restrict__ scores, int64_t* __restrict__ predict, int* __restrict__ seq_of_row) {
+                                     float* __restrict__ scores, int64_t* __restrict__ predict, int* __restrict__ seq_of_row,
+                                     const int* __restrict__ fin, int* __restrict__ finished) {
   const int steps = *steps_p;
   const int total = nw * F * W;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -174,6 +198,7 @@ __global__ void beam_finalize_kernel(const int* __restrict__ tok, const int* __r
       cur = s > 0 ? parent[(size_t)s * Btot + grp + cur] : cur;
     }
     scores[row] = score[(size_t)steps * Btot + grp + k];
+    if (finished) finished[row] = fin[(size_t)steps * Btot + grp + k];
     if (seq_of_row) seq_of_row[row] = grp + k;
   }
 }
@@ -188,21 +213,24 @@ int ff_beam_check_sizes(const char* op, int groups, int width, int groups_per_wi
 }
 
 int ff_beam_select_sync(const ff_step_io& io, int width, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
-                        int* hist, int ldhist, int t, int* parent, int* next_tok, ff_stream_t stream) {
+                        int* hist, int ldhist, int t, int* parent, int* next_tok, ff_stream_t stream, int form) {
+  const char* op = form ? "ff_beam_sequence_select" : "ff_beam_select";
   const int S = io.S, groups = io.rows / width;
   BeamArgs a;
   memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(ff_step_args(&a.p, "ff_beam_select", false, io));
-  FF_CHECK_ARG(scores_in && scores_out && fin_in && fin_out && parent && next_tok, "ff_beam_select: null pointer");
-  FF_CHECK_ARG(!hist || (t >= 1 && ldhist >= io.rows), "ff_beam_select: history needs t >= 1 and ldhist >= groups * width");
+  FF_RETURN_IF(ff_step_args(&a.p, op, false, io));
+  FF_CHECK_ARG(scores_in && scores_out && fin_in && fin_out && parent && next_tok, "%s: null pointer", op);
+  FF_CHECK_ARG(!hist || (t >= 1 && ldhist >= io.rows), "%s: history needs t >= 1 and ldhist >= groups * width", op);
   a.groups = groups; a.score_in = scores_in; a.score_out = scores_out; a.fin_in = fin_in; a.fin_out = fin_out;
   a.hist = hist; a.ldhist = ldhist; a.t = t; a.parent = parent; a.tok = next_tok;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)io.rows * S * 12.0, st);
   const dim3 grid(ff_cdiv(groups, 4)), block(256);
   const int rc = ff_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(width, [&](auto w) {
-    hipLaunchKernelGGL(beam_select_kernel<decltype(w)::value>, grid, block, 0, st, a);
-    return FF_OK;
+    return ff_dispatch<0, 1, 2>(form, [&](auto f) {
+      hipLaunchKernelGGL((beam_select_kernel<decltype(w)::value, decltype(f)::value>), grid, block, 0, st, a);
+      return FF_OK;
+    });
   });
   FF_RETURN_IF(rc);
   FF_CHECK_LAUNCH();
@@ -218,6 +246,22 @@ extern "C" int ff_beam_select(float* logits, int ldlogits, int S, const unsigned
   return ff_beam_select_sync(ff_step_io{logits, ldlogits, S, mask, kv_len, groups * width, groups_per_wireframe * width, term_lo,
                                         term_hi, ge_bound, memory, E, next_rows, ldnext, nullptr, count_ge, nullptr, nullptr},
                              width, scores_in, scores_out, fin_in, fin_out, hist, ldhist, t, parent, next_tok, stream);
+}
+
+// The sequence forms of the step (single-sequence variant): ff_beam_select's arguments without ge_bound; count_unfinished += the
+// non-empty beams unfinished after the step, or with stop_best the groups whose rank 0 is unfinished after it.
+extern "C" int ff_beam_sequence_select(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int groups,
+                                       int width, int groups_per_wireframe, const float* scores_in, float* scores_out,
+                                       const int* fin_in, int* fin_out, int* hist, int ldhist, int t, int* parent, int* next_tok,
+                                       int term_lo, int term_hi, const float* memory, int E, float* next_rows, int ldnext,
+                                       int* count_unfinished, int stop_best, ff_stream_t stream) {
+  FF_RETURN_IF(ff_beam_check_sizes("ff_beam_sequence_select", groups, width, groups_per_wireframe, S));
+  FF_CHECK_ARG(term_lo < term_hi, "ff_beam_sequence_select: empty terminator range [%d, %d)", term_lo, term_hi);
+  FF_CHECK_ARG(stop_best == 0 || stop_best == 1, "ff_beam_sequence_select: stop_best=%d must be 0 or 1", stop_best);
+  return ff_beam_select_sync(ff_step_io{logits, ldlogits, S, mask, kv_len, groups * width, groups_per_wireframe * width, term_lo,
+                                        term_hi, 0, memory, E, next_rows, ldnext, nullptr, count_unfinished, nullptr, nullptr},
+                             width, scores_in, scores_out, fin_in, fin_out, hist, ldhist, t, parent, next_tok, stream,
+                             stop_best ? 2 : 1);
 }
 
 extern "C" int ff_beam_reorder(float* rows_a, int width_a, float* rows_b, int width_b, int rows_per_pos, int npos,
@@ -245,12 +289,19 @@ int ff_beam_init(int* tok, float* score, int* fin, int* parent, int Bc, int Fc, 
   return FF_OK;
 }
 
+int ff_sequence_beam_init(int* tok, float* score, int* fin, int* parent, int Bc, int W, int sos, hipStream_t st) {
+  hipLaunchKernelGGL(sequence_beam_init_kernel, dim3(ff_cdiv(Bc, 256)), dim3(256), 0, st, tok, score, fin, parent, Bc, W, sos);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
 int ff_beam_finalize(const int* tok, const int* parent, const float* score, int Btot, int T, const int* steps_dev,
                      const int* num_input, int dedup, int F, int W, int w0, int nw, int Fc, int f0, int b0, int64_t* beams,
-                     float* scores, int64_t* predict, int* seq_of_row, hipStream_t st) {
+                     float* scores, int64_t* predict, int* seq_of_row, hipStream_t st, const int* fin, int* finished) {
   const int total = nw * F * W;
   hipLaunchKernelGGL(beam_finalize_kernel, dim3(ff_cdiv(total, 256) < 1024 ? ff_cdiv(total, 256) : 1024), dim3(256), 0, st, tok,
-                     parent, score, Btot, T, steps_dev, num_input, dedup, F, W, w0, nw, Fc, f0, b0, beams, scores, predict, seq_of_row);
+                     parent, score, Btot, T, steps_dev, num_input, dedup, F, W, w0, nw, Fc, f0, b0, beams, scores, predict, seq_of_row,
+                     fin, finished);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }

@@ -141,12 +141,15 @@ struct ff_step_io {
 // width and sizes are checked by ff_beam_check_sizes before that product is formed (the extern "C" entries; the engine's own checks).
 int ff_beam_check_sizes(const char* op, int groups, int width, int groups_per_wireframe, int S);
 int ff_beam_select_sync(const ff_step_io& io, int width, const float* scores_in, float* scores_out, const int* fin_in, int* fin_out,
-                        int* hist, int ldhist, int t, int* parent, int* next_tok, ff_stream_t stream);
+                        int* hist, int ldhist, int t, int* parent, int* next_tok, ff_stream_t stream,
+                        int form = 0);   // (1 / 2: the single-sequence decode's forms, count_ge counts "all" / "best")
+int ff_sequence_beam_init(int* tok, float* score, int* fin, int* parent, int Bc, int W, int sos, hipStream_t st);
 int ff_beam_init(int* tok, float* score, int* fin, int* parent, int Bc, int Fc, int W, int f0, const int* num_input, int pad_tok,
                  int term_lo, int term_hi, hipStream_t st);
 int ff_beam_finalize(const int* tok, const int* parent, const float* score, int Btot, int T, const int* steps_dev,
                      const int* num_input, int dedup, int F, int W, int w0, int nw, int Fc, int f0, int b0, int64_t* beams,
-                     float* scores, int64_t* predict, int* seq_of_row, hipStream_t st);
+                     float* scores, int64_t* predict, int* seq_of_row, hipStream_t st, const int* fin = nullptr,
+                     int* finished = nullptr);   // (the finished flags of the stop step's row: the sequence beam decode's output)
 
 // Forced decode (ff_forced.hip): the [rows, T] int64 paths as the engine's position-major int32 tokens (clamped into [0, S)),
 // and the output packing (kernels' comments).

@@ -39,6 +39,10 @@
 //     packing with F = 1 -- R draws per WIREFRAME, every one from SOS -- and the sequence form of ff_pointer_sample, whose counter
 //     is "rows unfinished after the step": the decode stops at the first step that leaves 0 (the parallel rule's test on another
 //     count; the cumulative EOS rule is not used).
+//   sequence beam (ff_decode_sequence_beam, single-sequence variant): the beam decode's plan, records, reorder and
+//     packing with F = 1 -- W beams per WIREFRAME, every one from SOS, beam 0 alone non-empty -- and a sequence form of
+//     ff_beam_select, whose counter is "non-empty beams unfinished after the step" ("all") or "groups whose rank 0 is unfinished
+//     after the step" ("best"): the decode stops at the first step that leaves 0.
 //   constrain (ff_decode_constrained): the default plan, one sequence per anchor.  ff_pointer_constrained masks
 //     the keys the enclosure walk could not accept; records and the rule's state (first, prev per step; visited words and the
 //     byte mask per sequence).
@@ -364,11 +368,12 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
   const ff_beam_params* beam() const { return static_cast<const ff_beam_params*>(prm); }          // (each for its own kind only)
+  const ff_sequence_beam_params* seqbeam() const { return static_cast<const ff_sequence_beam_params*>(prm); }
   const ff_forced_params* forced() const { return static_cast<const ff_forced_params*>(prm); }
   const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }   // (SAMPLE and SEQ_SAMPLE)
   const ff_constrain_ahead_params* ahead() const { return static_cast<const ff_constrain_ahead_params*>(prm); }
@@ -400,6 +405,7 @@ void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, con
     case Mode::CONSTRAIN_BEAM_AHEAD:
     case Mode::CONSTRAIN_SAMPLE:
     case Mode::SEQ_SAMPLE:   // (FF_SEQ2SEQ: a micro-batch is cut by sequences, chunk_max_seqs / R wireframes, at least one)
+    case Mode::SEQ_BEAM:     // (likewise: chunk_max_seqs / W wireframes, at least one)
     case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
     case Mode::FORCED: {
       ff_decode_params q = *p;
@@ -509,12 +515,13 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
   const size_t fw = (size_t)(p->L + 31) / 32, vw = Btot * (fw > 0 ? fw : 1);   // visited words; one word per sequence at L = 0, so that the array is never empty
   switch (mode.kind) {
     case Mode::BEAM:
+    case Mode::SEQ_BEAM:
     case Mode::CONSTRAIN_BEAM:
     case Mode::CONSTRAIN_BEAM_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
       b.score = bp.take<float>(TB);
       b.finished = bp.take<int>(TB);
       b.parent = bp.take<int>(TB);
-      if (mode.kind == Mode::BEAM) break;
+      if (mode.kind == Mode::BEAM || mode.kind == Mode::SEQ_BEAM) break;
       b.dead = bp.take<int>(TB);
       b.first = bp.take<int>(2 * Btot);     // (the two halves)
       b.prev = bp.take<int>(2 * Btot);
@@ -1125,6 +1132,8 @@ struct DecodeRun {
         return ff_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok, p->term_lo, p->term_hi, st);
       case Mode::SAMPLE:
         return ff_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F, ni, pad_tok, p->term_lo, p->term_hi, st);
+      case Mode::SEQ_BEAM:   // (Fc = W beams per wireframe)
+        return ff_sequence_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, G, p->tok_sos, st);
       case Mode::SEQ_SAMPLE:   // (Fc = R draws per wireframe)
         return ff_sequence_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, G, c.w0, p->tok_sos, st);
       case Mode::CONSTRAIN:
@@ -1202,16 +1211,18 @@ struct DecodeRun {
     int* tok_out = buf.tok_all + out;
     switch (mode.kind) {
       case Mode::BEAM:
+      case Mode::SEQ_BEAM:
       case Mode::CONSTRAIN_BEAM:
       case Mode::CONSTRAIN_BEAM_AHEAD: {
         // top-W selection, then the reorder of positions < t of x0 and qkv0 behind it on the same stream: the next decoder pass
         // reads reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
         const int W = mode.G;
         int* trace_parent;
-        if (mode.kind == Mode::BEAM) {
-          trace_parent = mode.beam()->trace_parent;
+        if (mode.kind == Mode::BEAM || mode.kind == Mode::SEQ_BEAM) {   // (SEQ_BEAM: the same launch in a sequence form, its counter "all" or "best")
+          const bool sq = mode.kind == Mode::SEQ_BEAM;
+          trace_parent = sq ? mode.seqbeam()->trace_parent : mode.beam()->trace_parent;
           FF_RETURN_IF(ff_beam_select_sync(sio, W, buf.score + in, buf.score + out, buf.finished + in, buf.finished + out, nullptr, 0, t,
-                                           buf.parent + out, tok_out, st));
+                                           buf.parent + out, tok_out, st, sq ? (mode.seqbeam()->stop_best ? 2 : 1) : 0));
         } else {   // the constrained selection: state half step & 1 -> half t & 1 (the common operands come from sio)
           trace_parent = mode.cbeam().trace_parent;
           const Rule r = rule_of(c);
@@ -1318,9 +1329,9 @@ struct DecodeRun {
     return FF_OK;
   }
   // Which counter the stop rule reads and how: cnt_ge and "the first step that leaves 0" for the parallel variant (tokens >=
-  // num_token of unfinished rows) and for the sequence sample mode (rows unfinished after the step); cnt_eq and the cumulative EOS
-  // count otherwise.
-  bool zero_rule() const { return p->variant == FF_PARALLEL || mode.kind == Mode::SEQ_SAMPLE; }
+  // num_token of unfinished rows), for the sequence sample mode (rows unfinished after the step) and for the sequence beam mode
+  // (non-empty beams, or rank-0 beams, unfinished after the step); cnt_eq and the cumulative EOS count otherwise.
+  bool zero_rule() const { return p->variant == FF_PARALLEL || mode.kind == Mode::SEQ_SAMPLE || mode.kind == Mode::SEQ_BEAM; }
   // the stop rule over the first n steps' counters, per_chunk = [n][nch]
   bool stop_rule(const int* per_chunk, int n) {
     tot.assign((size_t)n, 0);
@@ -1456,6 +1467,11 @@ struct DecodeRun {
     const hipStream_t main_st = io.main_st;
     const int G = mode.G, dd = dedup ? 1 : 0;
     switch (mode.kind) {
+      case Mode::SEQ_BEAM: {   // (F = 1, no de-duplication: num_input is not read; also the finished flags of the stop step's row)
+        const ff_sequence_beam_params* q = mode.seqbeam();
+        return ff_beam_finalize(buf.tok_all, buf.parent, buf.score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G,
+                                c.f0, c.b0, q->beams, q->scores, io.predict, io.seq_of_row, main_st, buf.finished, q->finished);
+      }
       case Mode::BEAM:
       case Mode::CONSTRAIN_BEAM:
       case Mode::CONSTRAIN_BEAM_AHEAD: {
@@ -1780,6 +1796,38 @@ extern "C" int ff_decode_sequence_sample(const ff_model* m, const ff_decode_para
   return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
                                      stream),
                     workspace, workspace_bytes, Mode(Mode::SEQ_SAMPLE, sample->num_samples, sample));
+}
+
+extern "C" size_t ff_decode_sequence_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width) {
+  if (width < 1 || width > 8 || !p || p->variant != FF_SEQ2SEQ || p->F != 1) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_BEAM, width));
+}
+
+extern "C" int ff_decode_sequence_beam(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
+                                       const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+                                       int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_beam_params* beam,
+                                       ff_stream_t stream) {
+  const char* name = "ff_decode_sequence_beam";
+  FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
+  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1, "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has ff_decode_beam",
+               name);
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
+               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
+  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d", name,
+               beam->width, p->L + m->num_token);
+  FF_CHECK_ARG(beam->stop_best == 0 || beam->stop_best == 1, "%s: stop_best=%d must be 0 or 1", name, beam->stop_best);
+  FF_CHECK_ARG(beam->beams && beam->scores && beam->finished && predict, "%s: beams, scores, finished and predict are required", name);
+  FF_CHECK_ARG(p->N > 0 && (long long)p->N * beam->width < (1LL << 31), "%s: bad sizes", name);
+  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
+  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
+               "%s: width=%d at E=%d exceeds the reorder's staging area", name, beam->width, m->E);
+  // the terminator range is the EOS token alone: SEP and the other special tokens do not finish a beam
+  ff_decode_params q = *p;
+  q.term_lo = p->tok_eos;
+  q.term_hi = p->tok_eos + 1;
+  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
+                                     stream),
+                    workspace, workspace_bytes, Mode(Mode::SEQ_BEAM, beam->width, beam));
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {

@@ -25,7 +25,7 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
            "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance",
-           "face_rows", "face_votes", "faces_of_rows", "parse_faces_samples_scored"]
+           "face_rows", "face_votes", "faces_of_rows", "parse_faces_samples_scored", "parse_faces_beams_scored"]
 
 
 def _tok(token, name, default):
@@ -234,6 +234,34 @@ def parse_faces_samples_scored(samples, logprobs, num_edges, token):
                 best[key] = (ftype, best[key][1] if key in best else idx, score)
         faces.extend(best.values())
     return faces
+
+
+def parse_faces_beams_scored(beams, scores, finished, num_edges, token):
+    """The faces of a beam decode of the single-sequence model (SurfaceFormer.sequence_beams): beams [W, T] tokens,
+    scores [W] the beams' summed log-probabilities (-inf: an empty rank, skipped), finished [W] (predict_beams[w] /
+    predict_beam_scores[w] / predict_beam_finished[w]).  Every non-empty beam is read by this model's own parse (`_seq_faces`):
+    cut after the first EOS, split after every SEP, the last token of every piece dropped, edge filters applied, a piece of one
+    token skipped.  An UNFINISHED beam has no EOS; its zeros behind the stop step are padding, not tokens, and are cut off first,
+    so its last, unterminated piece loses its last edge as it does in parse_faces.  Every face carries its BEAM's score; a face
+    (as a SET of edge indices) that occurs in several beams, or twice in one, is kept once, at its first place, with the best of
+    its scores.  Returns [(0, (edge, ...), score)] in beam order, the form unique_faces_with_scores takes."""
+    rows = np.asarray(beams, dtype=np.int64)
+    sc = np.asarray(scores, dtype=np.float64).reshape(-1)
+    fin = np.asarray(finished).reshape(-1)
+    if rows.ndim != 2 or sc.shape != rows.shape[:1] or fin.shape != sc.shape:
+        raise ValueError("beams must be [W, T], scores and finished [W]")
+    best = {}      # (insertion-ordered: the first place of every edge set)
+    for row, score, done in zip(rows, sc, fin):
+        if score == -np.inf:
+            continue
+        if not done:
+            used = np.flatnonzero(row)
+            row = row[: used[-1] + 1] if used.size else row[:0]
+        for ftype, idx in _seq_faces(row, token, num_edges, True):
+            key = tuple(sorted(set(idx)))
+            if key not in best or score > best[key][2]:
+                best[key] = (ftype, best[key][1] if key in best else idx, float(score))
+    return list(best.values())
 
 
 def parse_parallel_beams_scored(beams, scores, num_edges, token):

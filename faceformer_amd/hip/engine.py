@@ -375,7 +375,8 @@ class PathEngine:
                retire=False, term_range=None, retire_min_shrink=RETIRE_MIN_SHRINK, logprob=False, beam_width=None,
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
-               constrain_samples=None, constrain_beam_closure=None, sequence_samples=None):
+               constrain_samples=None, constrain_beam_closure=None, sequence_samples=None, sequence_beams=None,
+               sequence_beam_stop="all"):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -451,16 +452,38 @@ class PathEngine:
         draw k of wireframe w, zero behind its EOS and the stop step), `sample_logprob` (same layout) and `sample_scores` [N*R];
         `predict` [N, T] is draw 0; with trace=True `logits` is [T-1, N*R, S] in output-row order.  No term_range.  Excludes every
         other mode and option above, and stop_each_eos (the flag FF_STOP_EACH_EOS): the rule is per draw already.  temperature=0
-        equals, R times, the greedy FF_STOP_EACH_EOS decode cut behind every row's first EOS."""
+        equals, R times, the greedy FF_STOP_EACH_EOS decode cut behind every row's first EOS.
+
+        sequence_beams=W in 1..8, at most S (single-sequence variant only, ff_decode_sequence_beam; None or 0: the
+        greedy decode above): beam search with W beams per WIREFRAME, all from tok_sos (beam 0 alone non-empty), off one encoding
+        and one set of cross-attention K | V.  A beam is finished by tok_eos alone.  sequence_beam_stop="all": the decode stops
+        after the first step that leaves no non-empty beam unfinished (`step_counts`: those beams after every step); "best": after
+        the first step that leaves rank 0 of every wireframe finished (`step_counts`: the wireframes whose rank 0 is not) -- exact
+        for beam 0, the other beams are returned as they stand.  Also `beams` [N*W, T] int64 (row w*W + k is beam k of wireframe
+        w, best first, zero behind its EOS and the stop step), `beam_scores` [N*W] (-inf: an empty rank) and `beam_finished`
+        [N*W] int32; `predict` [N, T] is beam 0; with trace=True `logits` [T-1, N*W, S] and `beam_parent` [T-1, N*W] in
+        output-row order.  No term_range.  Excludes every other mode and option above, and stop_each_eos.  W=1 equals the greedy
+        FF_STOP_EACH_EOS decode cut behind every row's first EOS."""
+        SB = _modes.sequence_beams_value(sequence_beams)
+        if SB:
+            o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
+                     logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
+                     constrain=constrain is not None, sequence_samples=sequence_samples, sequence_beams=SB,
+                     sequence_beam_stop=sequence_beam_stop, trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
+            return self._decode_sequence(_modes.SEQUENCE_BEAM, "the parallel variant searches with beam_width", memory, mask_u8, kv_len,
+                                         variant, o, (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs,
+                                                      num_streams, chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows),
+                                         sync_every, tok_sos, tok_eos)
         SR = _modes.sequence_samples_value(sequence_samples)
         if SR:
             o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
                      logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
                      constrain=constrain is not None, sequence_samples=SR, temperature=temperature, top_k=top_k, top_p=top_p,
                      uniforms=uniforms, trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
-            return self._decode_sequence_sample(memory, mask_u8, kv_len, variant, o, (
-                variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs,
-                ln_fuse_max_rows, flags, x3_min_rows), sync_every, tok_sos, tok_eos)
+            return self._decode_sequence(_modes.SEQUENCE_SAMPLE, "the parallel variant draws with num_samples", memory, mask_u8, kv_len,
+                                         variant, o, (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs,
+                                                      num_streams, chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows),
+                                         sync_every, tok_sos, tok_eos)
         W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
         CB = _modes.constrain_beams_value(constrain_beams, CF)
         LA = _modes.constrain_lookahead_value(constrain_lookahead, CF, CB)
@@ -562,37 +585,37 @@ class PathEngine:
             out.update((key, t[:, idx]) for key, t in traced.items())
         return out
 
-    def _decode_sequence_sample(self, memory, mask_u8, kv_len, variant, o, params, sync_every, tok_sos, tok_eos):
-        """decode(sequence_samples=R): the checks (ValueError before anything is launched), the outputs and the one call of
-        ff_decode_sequence_sample, whose argument list has no num_input, extra mask, pointer or best / second traces.
-        params: _params' arguments."""
-        mode = _modes.SEQUENCE_SAMPLE
+    def _decode_sequence(self, mode, parallel_has, memory, mask_u8, kv_len, variant, o, params, sync_every, tok_sos, tok_eos):
+        """decode(sequence_samples=R) and decode(sequence_beams=W), `mode` their record: the checks (ValueError before anything is
+        launched), the outputs and the one call of ff_decode_sequence_sample / ff_decode_sequence_beam, whose argument list has no
+        num_input, extra mask, pointer or best / second traces.  params: _params' arguments."""
         if variant != _L.FF_SEQ2SEQ or o["F"] != 1:
-            raise ValueError("sequence_samples is a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant draws with num_samples")
+            raise ValueError("%s is a single-sequence option (FF_SEQ2SEQ, F = 1); %s" % (mode.subject, parallel_has))
         _modes.check_options(mode, variant, o, None)
         if params[-2] & _L.FF_STOP_EACH_EOS:
-            raise ValueError("sequence_samples excludes stop_each_eos (FF_STOP_EACH_EOS): every draw is finished by its own EOS already")
+            raise ValueError("%s excludes stop_each_eos (FF_STOP_EACH_EOS): every %s is finished by its own EOS already"
+                             % (mode.subject, "draw" if mode is _modes.SEQUENCE_SAMPLE else "beam"))
         mode.operand(self, o)
         prm = self._params(*params)
         _dev(memory, "memory")
         self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
         N, S, E = memory.shape
-        T, R, dev = o["T"], o["sequence_samples"], self.device
+        T, R, dev = o["T"], o[mode.subject], self.device
         prm.sync_every, prm.tok_sos, prm.tok_eos = sync_every, tok_sos, tok_eos
         predict = torch.empty((N, T), device=dev, dtype=torch.int64)
         steps_max = max(T - 1, 1)
         traced = {"logits": torch.full((steps_max, N * R, S), float("nan"), device=dev, dtype=torch.float32)} if o["trace"] else {}
         rows = torch.empty(N * R, device=dev, dtype=torch.int32)
         extra, tail = _modes.outputs(mode, self, o, N, traced)
-        ws = self._workspace(self._lib.ff_decode_sequence_sample_workspace_bytes(C.byref(self.model), C.byref(prm), R))
+        ws = self._workspace(getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm), R))
         steps = C.c_int(0)
         counts = (C.c_int * steps_max)()
         slots = (C.c_int * steps_max)()
         prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
         with torch.cuda.device(dev):
-            _L.check(self._lib.ff_decode_sequence_sample(C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len),
-                                                         _p(predict), C.byref(steps), counts, _p(traced.get("logits")), _p(rows),
-                                                         _p(ws), ws.numel(), *tail, _stream()), mode.entry)
+            _L.check(getattr(self._lib, mode.entry)(C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len),
+                                                    _p(predict), C.byref(steps), counts, _p(traced.get("logits")), _p(rows),
+                                                    _p(ws), ws.numel(), *tail, _stream()), mode.entry)
         sps = [int(v) for v in slots]
         out = {"predict": predict, "steps": steps.value, "step_counts": list(counts)[: steps.value], "seq_of_row": rows,
                "slots_per_step": sps, "slot_rows": sum((s + 1) * v for s, v in enumerate(sps))}
@@ -600,7 +623,7 @@ class PathEngine:
         if o["trace"]:
             idx = rows.long()
             out["decoded_seqs"] = int(idx.max().item()) + 1
-            out["logits"] = traced["logits"][:, idx]
+            out.update((key, t[:, idx]) for key, t in traced.items())
         return out
 
     def _params(self, variant, N, S, F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows, flags,

@@ -133,6 +133,11 @@ class BeamParams(C.Structure):
     _fields_ = [("width", C.c_int), ("beams", fptr), ("scores", fptr), ("trace_parent", fptr)]
 
 
+class SequenceBeamParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("stop_best", C.c_int), ("beams", fptr), ("scores", fptr), ("finished", fptr),
+                ("trace_parent", fptr)]
+
+
 class ForcedParams(C.Structure):
     _fields_ = [("paths", fptr), ("lengths", fptr), ("lengths_host", C.POINTER(C.c_int)), ("logprob", fptr), ("greedy", fptr),
                 ("rank", fptr), ("seq_logprob", fptr)]
@@ -350,6 +355,12 @@ SIGNATURES = {
     "ff_decode_sequence_sample_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
     "ff_decode_sequence_sample": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t, C.POINTER(SampleParams), fptr]),
+    "ff_beam_sequence_select": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
+                                          fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, fptr, C.c_int,
+                                          fptr, C.c_int, fptr]),
+    "ff_decode_sequence_beam_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
+    "ff_decode_sequence_beam": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t, C.POINTER(SequenceBeamParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
     "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
                                fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

@@ -506,6 +506,51 @@ SEQUENCE_SAMPLE = Mode(
     switches=(Switch("sequence_samples", 0, _NO_STOP_RULE % "sequence-sampled", None, False),),
     model_excludes=("return_logprob", "an extra mask"))
 
+SEQUENCE_BEAM_STOPS = {"all": 0, "best": 1}      # sequence_beam_stop -> stop_best of the C entries
+
+
+def _sequence_beam_values(o):
+    W = o["sequence_beams"]
+    if isinstance(W, bool) or not isinstance(W, int) or not 1 <= W <= 8 or ("S" in o and W > o["S"]):
+        raise ValueError("sequence_beams=%r: must be in 1..8 and at most S%s" % (W, " = %d" % o["S"] if "S" in o else ""))
+    sequence_beam_stop_value(o.get("sequence_beam_stop", "all"))
+
+
+def sequence_beams_value(sequence_beams):
+    """The width of a `sequence_beams` value: None / 0 -> 0 (the option is off); else 1..8."""
+    if sequence_beams is None or (not isinstance(sequence_beams, bool) and sequence_beams == 0):
+        return 0
+    _sequence_beam_values(dict(sequence_beams=sequence_beams))
+    return int(sequence_beams)
+
+
+def sequence_beam_stop_value(stop):
+    """stop_best of a `sequence_beam_stop` value: "all" -> 0 (stop once no non-empty beam is unfinished), "best" ->
+    1 (stop once rank 0 of every wireframe is finished: exact for beam 0, the others are returned as they stand)."""
+    if not isinstance(stop, str) or stop not in SEQUENCE_BEAM_STOPS:
+        raise ValueError("sequence_beam_stop=%r: must be 'all' or 'best'" % (stop,))
+    return SEQUENCE_BEAM_STOPS[stop]
+
+
+def _sequence_beam_tail(o, ptrs, traced):
+    if o["trace"]:
+        logits = traced["logits"]
+        traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
+    return (C.byref(_L.SequenceBeamParams(o["sequence_beams"], sequence_beam_stop_value(o["sequence_beam_stop"]), *ptrs,
+                                          _p(traced.get("beam_parent")))),)
+
+
+# The single-sequence model's beam search (DESIGN.md 30): W beams per WIREFRAME, every one from SOS, finished by EOS alone.  Outside
+# MODES, as SEQUENCE_SAMPLE is: beam_width on that model stays the recorded rejection it is (SWITCH and every recorded text stay),
+# and the option is read where the single-sequence model decodes (SurfaceFormer.forward_eval) and refused everywhere else.  The
+# terminator range is the entry's own ([tok_eos, tok_eos + 1)): no term_range.  The entry has SEQUENCE_SAMPLE's argument list.
+SEQUENCE_BEAM = Mode(
+    subject="sequence_beams", excludes=_COMMON + ("beam_width", "num_samples", "constrain", "sequence_samples"),
+    entry="ff_decode_sequence_beam", term_range=False, parallel_only=False, per_anchor=True, values=_sequence_beam_values,
+    values_first=True, outs=(("beams", "GT", _I64), ("beam_scores", "G", _F32), ("beam_finished", "G", _I32)),
+    tail=_sequence_beam_tail, switches=(Switch("sequence_beams", 0, _NO_STOP_RULE % "sequence-beam", None, False),),
+    model_excludes=("sequence_samples", "beam_width", "return_logprob", "an extra mask"))
+
 MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several mode options, the first one's record reports
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 

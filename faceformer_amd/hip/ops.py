@@ -388,6 +388,26 @@ def beam_select(logits, scores, fin, width, groups_per_wireframe=None, mask=None
     scores [G * width] fp32 (-inf: empty beam) and fin [G * width] int32 (nonzero: finished) are the state before the step;
     hist (optional) [t + 1, G * width] int32 token history, permuted in place, position t written.  Returns dict(parent, next,
     scores, fin, [rows]): the new beams in rank order, best first."""
+    return _beam_select("ff_beam_select", ge_bound, logits, scores, fin, width, groups_per_wireframe, mask, kv_len, hist, t, term_range,
+                        memory, want_rows, counter)
+
+
+@_on_tensor_device
+def beam_sequence_select(logits, scores, fin, width, groups_per_wireframe=None, mask=None, kv_len=None, hist=None, t=0,
+                         term_range=(3, 4), memory=None, want_rows=False, counter=None, stop_best=False):
+    """One beam-search step of the single-sequence decode (ff_beam_sequence_select): beam_select's operands,
+    selection and outputs; `counter` (int32, one element) += the non-empty beams UNFINISHED AFTER the step -- or, with stop_best,
+    the groups whose rank 0 is unfinished after it -- instead of the kept candidates with a token >= ge_bound.  term_range =
+    [EOS, EOS + 1)."""
+    if not int(term_range[0]) < int(term_range[1]):
+        raise ValueError("term_range must be (lo, hi) with lo < hi")
+    return _beam_select("ff_beam_sequence_select", int(bool(stop_best)), logits, scores, fin, width, groups_per_wireframe, mask, kv_len,
+                        hist, t, term_range, memory, want_rows, counter)
+
+
+def _beam_select(entry, last, logits, scores, fin, width, groups_per_wireframe, mask, kv_len, hist, t, term_range, memory, want_rows,
+                 counter):
+    """The two selection entries' common call; `last`: the integer before the stream, ge_bound or stop_best."""
     _dev(logits, "logits"), _dev(scores, "scores"), _dev(fin, "fin", torch.int32)
     if logits.dim() != 2 or logits.stride(1) != 1:
         raise ValueError("logits must be a 2-D tensor with unit inner stride")
@@ -419,10 +439,10 @@ def beam_select(logits, scores, fin, width, groups_per_wireframe=None, mask=None
             rows = out["rows"] = torch.empty((B, E), device=dev, dtype=torch.float32)
     if counter is not None:
         _dev(counter, "counter", torch.int32)
-    _L.check(_L.load().ff_beam_select(
+    _L.check(getattr(_L.load(), entry)(
         _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), G, width, gpw, _p(scores.contiguous()), _p(out["scores"]),
         _p(fin.contiguous()), _p(out["fin"]), _p(hist), ldhist, t, _p(out["parent"]), _p(out["next"]), int(term_range[0]),
-        int(term_range[1]), _p(memory), E, _p(rows), E, _p(counter), ge_bound, _stream()), "ff_beam_select")
+        int(term_range[1]), _p(memory), E, _p(rows), E, _p(counter), last, _stream()), entry)
     return out
 
 

@@ -92,6 +92,9 @@ class SurfaceFormerBase(nn.Module):
                                        # closed faces only; inputs["edge_map"] (int32 N x L) maps edges before the grouping
         self.sequence_samples = 0      # single-sequence model: R in 1..64 = R independent draws per WIREFRAME under sample_temperature /
                                        # sample_top_k / sample_top_p, decoded together off one encoding; 0 = greedy
+        self.sequence_beams = 0        # single-sequence model: W in 1..8 = beam search with W beams per WIREFRAME, decoded together off one
+                                       # encoding; 0 = greedy
+        self.sequence_beam_stop = "all"  # ... "all": stop once every non-empty beam is finished; "best": once every wireframe's best is
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
         self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
         self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
@@ -317,6 +320,9 @@ class SurfaceFormerBase(nn.Module):
         if parallel and getattr(self, "sequence_samples", 0):
             raise ValueError("sequence_samples is a SurfaceFormer option (draws per wireframe of the single-sequence model); "
                              "SurfaceFormer_Parallel draws per anchor with num_samples")
+        if parallel and getattr(self, "sequence_beams", 0):
+            raise ValueError("sequence_beams is a SurfaceFormer option (beams per wireframe of the single-sequence model); "
+                             "SurfaceFormer_Parallel searches per anchor with beam_width")
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
@@ -420,6 +426,8 @@ class SurfaceFormerBase(nn.Module):
                     raise ValueError("score() excludes %s: set model.%s = %r to score given paths" % (sw.attr, sw.attr, sw.off))
         if getattr(self, "sequence_samples", 0):
             raise ValueError("score() excludes sequence_samples: set model.sequence_samples = 0 to score given paths")
+        if getattr(self, "sequence_beams", 0):
+            raise ValueError("score() excludes sequence_beams: set model.sequence_beams = 0 to score given paths")
         if getattr(self, "constrain_samples", 0):     # (an option of constrain: without constrain the lines above have not raised)
             raise ValueError("score() excludes constrain_samples: set model.constrain_samples = 0 to score given paths")
         if not self.engine_supported():

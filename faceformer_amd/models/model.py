@@ -47,10 +47,19 @@ class SurfaceFormer(SurfaceFormerBase):
         Every draw starts from SOS and is finished by its own EOS; the decode stops once every draw is.  Adds predict_samples
         N x R x T (zero behind a draw's EOS and the stop step), predict_sample_logprob N x R x T (the model's log-probability of
         every drawn token) and predict_sample_scores N x R (their sums); predict is draw 0; embedding as above; no pointer.
-        stop_each_eos is not looked at.  Not with return_logprob, an extra mask or the sub-module loop (ValueError)."""
+        stop_each_eos is not looked at.  Not with return_logprob, an extra mask or the sub-module loop (ValueError).
+
+        sequence_beams = W in 1..8, at most S (0: the greedy decode above): beam search with W beams per wireframe,
+        decoded together off one encoding.  Every beam starts from SOS (beam 0 alone non-empty) and is finished by its own EOS;
+        sequence_beam_stop "all" stops once no non-empty beam is unfinished, "best" once every wireframe's best beam is finished
+        (exact for that beam; the others are returned as they stand).  Adds predict_beams N x W x T (best first, zero behind a
+        beam's EOS and the stop step), predict_beam_scores N x W (summed log-probabilities; -inf: an empty rank) and
+        predict_beam_finished N x W (int32); predict is beam 0; embedding as above; no pointer.  stop_each_eos is not looked at.
+        Not with sequence_samples, beam_width, return_logprob, an extra mask or the sub-module loop (ValueError)."""
         label = inputs["label"]
         T = self.num_labels
         self._decode_mode(inputs, parallel=False)       # (the records' reasons: hip/modes.py)
+        W = self._sequence_beams_value(inputs)
         R = self._sequence_samples_value(inputs)
         if inputs["input"].size(0) == 0:     # an empty batch: the reference's loop stops after its first step (0 EOS == batch size 0, model.py:207)
             dev, S = inputs["input"].device, inputs["input"].size(1) + self.num_token
@@ -64,6 +73,11 @@ class SurfaceFormer(SurfaceFormerBase):
                 inputs["predict_samples"] = torch.zeros((0, R, T), dtype=torch.long, device=dev)
                 inputs["predict_sample_logprob"] = torch.zeros((0, R, T), device=dev)
                 inputs["predict_sample_scores"] = torch.zeros((0, R), device=dev)
+            if W:
+                del inputs["pointer"]
+                inputs["predict_beams"] = torch.zeros((0, W, T), dtype=torch.long, device=dev)
+                inputs["predict_beam_scores"] = torch.zeros((0, W), device=dev)
+                inputs["predict_beam_finished"] = torch.zeros((0, W), dtype=torch.int32, device=dev)
             return inputs
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             return self._forward_eval_modules(inputs, parallel=False)
@@ -72,6 +86,8 @@ class SurfaceFormer(SurfaceFormerBase):
                              "needed" % (label.size(1), T - 1))
         want_lp = bool(getattr(self, "return_logprob", False))
         eng, memory, mask, kv_len = self._encode(inputs)
+        if W:
+            return self._forward_eval_beams(inputs, eng, memory, mask, kv_len, T, W)
         if R:
             return self._forward_eval_samples(inputs, eng, memory, mask, kv_len, T, R)
         out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
@@ -85,6 +101,39 @@ class SurfaceFormer(SurfaceFormerBase):
         inputs["predict"] = out["predict"]
         if want_lp:
             inputs["predict_logprob"] = out["logprob"]
+        return inputs
+
+    def _sequence_beams_value(self, inputs):
+        """sequence_beams as 0 or W in 1..8, after the rules only the model can check (ValueError, before anything is launched):
+        the native engine, what the record excludes, the width against S, the stop value."""
+        W = _modes.sequence_beams_value(getattr(self, "sequence_beams", 0))
+        if not W:
+            return 0
+        mode = _modes.SEQUENCE_BEAM
+        if not self.engine_supported():
+            raise ValueError("sequence_beams needs the native engine: this model's constructor arguments take the sub-module loop")
+        if getattr(self, "sequence_samples", 0) or getattr(self, "beam_width", 0) or getattr(self, "return_logprob", False) or \
+                inputs.get("extra_mask") is not None:
+            raise ValueError("sequence_beams excludes %s, %s, %s and %s" % mode.model_excludes)
+        _modes.check_options(mode, _L.FF_SEQ2SEQ, dict(sequence_beams=W, sequence_beam_stop=getattr(self, "sequence_beam_stop", "all"),
+                                                      S=inputs["input"].size(1) + self.num_token), None)
+        return W
+
+    def _forward_eval_beams(self, inputs, eng, memory, mask, kv_len, T, W):
+        """forward_eval with sequence_beams = W behind the encoder.  The wireframes are decoded in batch order (this model applies
+        no permutation): row w*W + k of the engine's outputs is beam k of wireframe w as given."""
+        N = memory.size(0)
+        out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
+                         chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
+                         chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1, flags=self.decode_flags,
+                         x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS,
+                         tok_eos=self.token.EOS, sequence_beams=W, sequence_beam_stop=self.sequence_beam_stop)
+        inputs["embedding"] = memory
+        inputs["predict"] = out["predict"]
+        inputs["predict_beams"] = out["beams"].view(N, W, T)
+        inputs["predict_beam_scores"] = out["beam_scores"].view(N, W)
+        inputs["predict_beam_finished"] = out["beam_finished"].view(N, W)
+        self.last_beam_stats = {"steps": out["steps"], "slot_rows": out["slot_rows"]}
         return inputs
 
     def _sequence_samples_value(self, inputs):

@@ -1366,6 +1366,65 @@ int ff_decode_sequence_sample(const ff_model* m, const ff_decode_params* p,
                               int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
                               void* workspace, size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream);
 
+/* ---- beam search over the single-sequence decode (opt-in, FF_SEQ2SEQ; entries added within ABI 105) ----------------
+ * The single-sequence reference decodes ONE greedy sequence per wireframe: select_next takes the argmax of the masked logit row
+ * (model.py:161-167) inside the loop of model.py:193-210, which starts every sequence from SOS (model.py:191).  These entries
+ * restate those call sites with ONE change: the selection keeps the `width` best continuations of the `width` beams of every
+ * WIREFRAME by ff_beam_select's rule (candidates, order and tie rule unchanged, bit for bit: one copy in device code), and the loop
+ * carries width sequences per wireframe off one encoding and one set of cross-attention K | V.
+ *
+ * Layout.  The decode runs N*W sequences; beam k of wireframe w is row w*W + k, and sequence i of the engine belongs to wireframe
+ *   i / W (cross-attention, masks, kv_len, the pointer GEMM and the row gather).  One group is one wireframe.
+ * Start.  Every beam holds tok_sos at position 0; beam 0 has score 0, the others are empty (-inf, no candidates).
+ * Finish.  A beam is finished from the first position >= 1 holding tok_eos: the terminator range is [tok_eos, tok_eos + 1),
+ *   whatever term_lo / term_hi of the parameters hold.  SEP and the other special tokens do not finish a beam.  A finished beam
+ *   contributes one candidate: itself, token 0, score unchanged.
+ * Candidates.  An unfinished beam contributes its S masked logits (padding keys at -FLT_MAX, every token row selectable), each as
+ *   c_k + (l[s] - m) - log sum exp(l - m) in fp32, saturated at -FLT_MAX; descending, ties to the lower flat index k*S + s.
+ * Stop, stop_best = 0 ("all").  After the first step after which no beam of the call is both non-empty and unfinished, else after
+ *   T-1 steps; step_counts[s] = the non-empty beams unfinished after step s.  (ff_decode_beam's rule -- no unfinished beam selected
+ *   an edge token -- would be wrong here: every beam can select SEP in one step.)
+ * Stop, stop_best = 1 ("best").  After the first step after which rank 0 of every group is finished; step_counts[s] = the groups
+ *   whose rank 0 is unfinished after step s.  Exact for beam 0: log-probabilities are <= 0 and the list is sorted, so a finished
+ *   rank 0 re-enters as flat index 0 with its score unchanged, and no candidate can pass it or win a tie against it.  The other
+ *   beams are returned as they stand, possibly unfinished.
+ * *steps_done reports the stop step, output past it is zero, and steps enqueued past it change nothing that is read.
+ * FF_STOP_EACH_EOS is refused: the rules above are per beam already.
+ *
+ * ff_beam_sequence_select: one step; ff_beam_select's arguments without ge_bound, and count_unfinished (optional) += the
+ *   counter of the chosen rule (stop_best 0 or 1); term_lo < term_hi.
+ * ff_decode_sequence_beam: memory / mask / kv_len as ff_decode; then
+ *   predict  [N, T] int64: beam 0 of every wireframe.
+ *   beam:    ff_sequence_beam_params -- width W, stop_best; beams [N*W, T] int64, best first, from walking the parents back from the
+ *            stop step, zero past each beam's EOS and past the stop step; scores [N*W] fp32 (-inf: an empty rank); finished [N*W]
+ *            int32: the flags after the stop step; trace_parent (optional) [T-1, N*W] int32, indexed like trace_logits.
+ *   trace_logits (optional) [T-1, N*W, S] indexed by decoded sequence (seq_of_row [N*W] maps output rows to them).
+ *   A micro-batch holds chunk_max_seqs / W wireframes (at least one).  With W = 1 and either rule the beam is the greedy
+ *   FF_STOP_EACH_EOS decode's row cut behind its first EOS, with the same steps.
+ * FF_ERR_ARG before any launch for: FF_PARALLEL or F != 1, FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS, a
+ * stop_fn, width outside 1..8 or above S, stop_best outside 0..1, a NULL beams / scores / finished / predict.  There is no extra
+ * mask, pointer_out or best / second trace argument.  ff_decode_beam keeps refusing FF_SEQ2SEQ.
+ * ff_decode_sequence_beam_workspace_bytes: ff_decode_beam_workspace_bytes' rules with W sequences per wireframe (0 for what the
+ * entry refuses).  Every other entry launches and lays out what it did before these. */
+typedef struct ff_sequence_beam_params {
+  int width;
+  int stop_best;
+  int64_t* beams;
+  float* scores;
+  int* finished;
+  int* trace_parent;
+} ff_sequence_beam_params;
+int ff_beam_sequence_select(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int groups,
+                            int width, int groups_per_wireframe, const float* scores_in, float* scores_out, const int* fin_in,
+                            int* fin_out, int* hist, int ldhist, int t, int* parent, int* next_tok, int term_lo, int term_hi,
+                            const float* memory, int E, float* next_rows, int ldnext, int* count_unfinished, int stop_best,
+                            ff_stream_t stream);
+size_t ff_decode_sequence_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width);
+int ff_decode_sequence_beam(const ff_model* m, const ff_decode_params* p,
+                            const float* memory, const unsigned char* mask, const int* kv_len,
+                            int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
+                            void* workspace, size_t workspace_bytes, const ff_sequence_beam_params* beam, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

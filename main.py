@@ -147,7 +147,7 @@ def score_batch(model, batch):
 
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
-              constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None):
+              constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None, sequence_beams=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -174,6 +174,9 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     record also gets `pred_sample_faces`, `pred_sample_face_scores` and `pred_sample_face_votes`, the de-duplicated faces over ALL
     draws ranked by their best score, with the number of DRAWS that produced each (a face twice in one draw counts once);
     `pred_faces` stays what draw 0 (pred) gives.
+    sequence_beams (--sequence-beams, single-sequence model; (tokens [W, T], scores [W], finished [W]) of this sample): the record
+    also gets `pred_beam_faces` and `pred_beam_face_scores`, the de-duplicated faces over ALL non-empty beams ranked by their best
+    beam score (faces.parse_faces_beams_scored); `pred_faces` stays what beam 0 (pred) gives.
     device_faces (--device-faces; this sample's slice of the model's inputs["faces"]): the predicted faces of
     every key above come from these arrays (faces.faces_of_rows) instead of from pred, beams and samples, which are then not
     read; label faces, the metrics and the JSON text are made here as before."""
@@ -262,6 +265,11 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["pred_sample_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
         rec["pred_sample_face_scores"] = [s for _, _, s, _ in ranked]
         rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
+    if sequence_beams is not None:
+        bf = FZ.parse_faces_beams_scored(sequence_beams[0], sequence_beams[1], sequence_beams[2], len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_beam_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_beam_face_scores"] = [s for _, _, s, _ in ranked]
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
@@ -315,7 +323,7 @@ def _record_of_device(cfg, raw, item, rows, scored, beams, samples, dead_end, sa
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-                    constrain_samples=0, constrain_beam_closure=None, sequence_samples=0):
+                    constrain_samples=0, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0, sequence_beam_stop="all"):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
@@ -325,7 +333,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     (constrain_exact), `constrain_samples` draws per anchor from the constrained keys under temperature / top_k /
     top_p / seed, the closure look-ahead of the constrained beam search (constrain_beam_closure "lookahead" /
     "exact"), `sequence_samples` draws per wireframe of the single-sequence model under temperature / top_k / top_p /
-    seed.
+    seed, beam search with `sequence_beams` beams per wireframe of the single-sequence model under the stop rule
+    `sequence_beam_stop`.
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -359,13 +368,17 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.sequence_samples = int(sequence_samples)
         model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
         model.sample_seed = int(seed)
+    if sequence_beams:
+        model.sequence_beams = int(sequence_beams)
+        model.sequence_beam_stop = str(sequence_beam_stop)
     return model
 
 
 def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size=1, dist_mod=None, model=None,
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-             constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0):
+             constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0,
+             sequence_beam_stop="all"):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -387,7 +400,21 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     under the closure look-ahead or its exact form -- the record keys stay constrain_beams'; sequence_samples = R (1..64,
     single-sequence model, single-rank runs only, not with scores, score_labels, sample or device_faces) draws R
     sequences per wireframe under temperature / top_k / top_p / seed and adds pred_sample_faces / pred_sample_face_scores /
-    pred_sample_face_votes; pred_faces stays draw 0's."""
+    pred_sample_face_votes; pred_faces stays draw 0's; sequence_beams = W (1..8, single-sequence model, single-rank runs only, not
+    with scores, score_labels, sample, sequence_samples, beam or device_faces) searches W beams per wireframe under
+    sequence_beam_stop ("all" / "best") and adds pred_beam_faces / pred_beam_face_scores; pred_faces stays beam 0's."""
+    if sequence_beams:
+        if isinstance(sequence_beams, bool) or not isinstance(sequence_beams, int) or not 1 <= sequence_beams <= 8:
+            raise ValueError("--sequence-beams must be a width in 1..8")
+        if sequence_beam_stop not in ("all", "best"):
+            raise ValueError("--sequence-beam-stop must be all or best")
+        if cfg.model_class != "SurfaceFormer":
+            raise ValueError("--sequence-beams applies to SurfaceFormer only (SurfaceFormer_Parallel searches per anchor with --beam)")
+        if scores or score_labels or sample or sequence_samples or beam or device_faces:
+            raise ValueError("--sequence-beams does not combine with --scores, --score-labels, --sample, --sequence-samples, --beam or "
+                             "--device-faces")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--sequence-beams is not implemented for multi-rank runs")
     if sequence_samples:
         if isinstance(sequence_samples, bool) or not isinstance(sequence_samples, int) or not 1 <= sequence_samples <= 64:
             raise ValueError("--sequence-samples must be a count in 1..64")
@@ -452,7 +479,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         model = model.eval().to(device)
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
                     cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact,
-                    constrain_samples, constrain_beam_closure, sequence_samples)
+                    constrain_samples, constrain_beam_closure, sequence_samples, sequence_beams, sequence_beam_stop)
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
@@ -475,6 +502,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         wanted.append(("constrained_samples", ("predict_samples", "predict_sample_scores", "predict_sample_dead_end")))
     if sequence_samples:
         wanted.append(("sequence_samples", ("predict_samples", "predict_sample_logprob")))
+    if sequence_beams:
+        wanted.append(("sequence_beams", ("predict_beams", "predict_beam_scores", "predict_beam_finished")))
     if device_faces:
         wanted.append(("device_faces", ("faces",)))
     for b0 in range(lo, hi, batch_size):
@@ -597,6 +626,15 @@ def build_parser():
                              "pred_sample_face_votes: the faces of all draws, de-duplicated, ranked by score, with the number of "
                              "draws that produced each; single-process runs only, not with --scores, --score-labels, --sample or "
                              "--device-faces")
+    parser.add_argument("--sequence-beams", type=int, default=0, metavar="W",
+                        help="single-sequence model: beam search with W (1..8) beams per wireframe instead of the argmax, decoded "
+                             "together off one encoding (DESIGN.md 30); pred_faces come from beam 0, and every JSON record gains "
+                             "pred_beam_faces / pred_beam_face_scores: the faces of all beams, de-duplicated, ranked by their best "
+                             "beam score; single-process runs only, not with --scores, --score-labels, --sample, "
+                             "--sequence-samples, --beam or --device-faces")
+    parser.add_argument("--sequence-beam-stop", choices=("all", "best"), default="all",
+                        help="with --sequence-beams: stop once every non-empty beam is finished (all), or once the best beam of "
+                             "every wireframe is finished (best: exact for that beam, the others are written as they stand)")
     parser.add_argument("--constrain-beam-closure", choices=("lookahead", "exact"), default=None,
                         help="with --constrain loops --constrain-beams W: the beam search forms every beam's row under the closure "
                              "look-ahead (lookahead) or its exact form (exact), so that the W beams are searched among loops that "
@@ -624,7 +662,8 @@ def main(argv=None):
              top_p=args.top_p, seed=args.seed, constrain=args.constrain, constrain_beams=args.constrain_beams,
              constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact,
              constrain_samples=args.constrain_samples, device_faces=args.device_faces,
-             constrain_beam_closure=args.constrain_beam_closure, sequence_samples=args.sequence_samples)
+             constrain_beam_closure=args.constrain_beam_closure, sequence_samples=args.sequence_samples,
+             sequence_beams=args.sequence_beams, sequence_beam_stop=args.sequence_beam_stop)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
