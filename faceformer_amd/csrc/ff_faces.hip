@@ -366,6 +366,262 @@ __global__ __launch_bounds__(VOTE_THREADS) void face_votes_kernel(FaceVotesArgs 
   if (tid == 0) a.num_faces[w] = s_faces;
 }
 
+// ---- the single-sequence model's rows --------------------------------------------------------------------------
+constexpr int SEQ_T = FF_FACE_SEQ_MAX_T;   // positions of a row
+constexpr int SEQ_P = SEQ_T / 2;           // face slots of a row: a face takes an edge and a boundary
+constexpr int SEQ_THREADS = 256;
+
+struct FaceSeqArgs {
+  const int64_t* tokens; const int* num_edges; const float* scores; const float* logprob; const int* finished;
+  const unsigned* follows; const int* edge_map;
+  int G, T, L, fw, ntok, sep, eos, P, closed_only;
+  int *count, *len, *start, *type, *closed, *loops, *edges, *loop_of; unsigned* set_bits; double* score;
+  int *dup_of, *take; double* row_best;
+};
+
+// 57 KB: every index below is under 2048 and held in 16 bits.  The per-loop records of a slot (llen .. lnum, lminv) live at
+// [start, start + loops) of the slot's own edge range: a face has at most as many loops as edges.
+struct FaceSeqLds {
+  int e[SEQ_T];                    // the row's edges in decode order, all slots behind one another
+  int aux[SEQ_T];                  // per loop: its smallest edge; later per edge: the mapped edge of the key
+  unsigned short lid[SEQ_T];       // per edge: loop number inside its slot
+  unsigned short slot_of[SEQ_T];   // per edge: its slot
+  unsigned short llen[SEQ_T];      // per loop: length, position of its smallest edge (first occurrence), and in canonical order
+  unsigned short lrot[SEQ_T];      //   its offset inside the slot and its number
+  unsigned short loff[SEQ_T];
+  unsigned short lnum[SEQ_T];
+  unsigned short start[SEQ_P];     // per slot: first edge, edges, first and last position of the piece
+  unsigned short len[SEQ_P];
+  unsigned short pbeg[SEQ_P];
+  unsigned short pend[SEQ_P];
+  unsigned short loops[SEQ_P];
+  short dup[SEQ_P];
+  unsigned hash[SEQ_P];
+  signed char closed[SEQ_P];
+  int count, edges_total;
+};
+
+__device__ __forceinline__ unsigned long long seq_below(int lane) { return (1ull << lane) - 1ull; }
+
+// One block per row.  Wave 0 parses (two passes over chunks of 64 positions, every decision a ballot and a prefix count); the slots,
+// the edges, the words of the keys and the fold are then spread over the block, one thread per slot wherever a step is sequential.
+__global__ __launch_bounds__(SEQ_THREADS) void face_seq_rows_kernel(FaceSeqArgs a) {
+  __shared__ FaceSeqLds s;
+  const int tid = threadIdx.x, lane = face_lane();
+  const size_t row = blockIdx.x;
+  const int w = (int)(row / (size_t)a.G);
+  const int T = a.T, P = a.P, fw = a.fw, ntok = a.ntok;
+  int ne = a.num_edges[w];
+  ne = ne < 0 ? 0 : (ne > a.L ? a.L : ne);
+  const int64_t* trow = a.tokens + row * (size_t)T;
+
+  if (tid < FF_WAVE) {
+    bool face = !(a.scores && a.scores[row] == -INFINITY);
+    const bool cut_zeros = a.finished && a.finished[row] == 0;
+    // end: T - 1, or the last nonzero position of an unfinished row; then the first EOS at or before it
+    int last_nz = -1, first_eos = -1;
+    if (face)
+      for (int base = 0; base < T; base += FF_WAVE) {
+        const int p = base + lane;
+        const int64_t v = p < T ? trow[p] : 0;
+        const unsigned long long nz = __ballot(p < T && v != 0), eo = __ballot(p < T && v == (int64_t)a.eos);
+        if (nz) last_nz = base + 63 - __clzll((long long)nz);
+        if (first_eos < 0 && eo) first_eos = base + face_first(eo);
+      }
+    int end = cut_zeros ? last_nz : T - 1;
+    if (end < 0) face = false;
+    if (first_eos >= 0 && first_eos <= end) end = first_eos;
+    // pieces, faces and edges: running counts over the chunks
+    int edges_run = 0, faces_run = 0, last_eb = 0, last_bpos = -1;
+    if (face)
+      for (int base = 0; base <= end; base += FF_WAVE) {
+        const int p = base + lane;
+        const int64_t v = p <= end ? trow[p] : 0;
+        const bool bound = p <= end && (v == (int64_t)a.sep || p == end);
+        const bool is_edge = p <= end && !bound && v >= (int64_t)ntok && v - (int64_t)ntok < (int64_t)ne;
+        const unsigned long long bb = __ballot(bound), eb = __ballot(is_edge);
+        const int before = edges_run + face_prefix(eb);          // edges in front of this position
+        if (is_edge) s.e[before] = (int)(v - ntok);
+        // a boundary closes the piece behind the boundary before it
+        int prev_eb = last_eb, prev_bpos = last_bpos;
+        const unsigned long long lower = bb & seq_below(lane);
+        if (lower) {
+          const int pl = 63 - __clzll((long long)lower);
+          prev_eb = edges_run + __popcll(eb & seq_below(pl));
+          prev_bpos = base + pl;
+        }
+        const bool is_face = bound && before > prev_eb;
+        const unsigned long long fb = __ballot(is_face);
+        const int slot = faces_run + face_prefix(fb);
+        if (is_face && slot < P) {
+          s.start[slot] = (unsigned short)prev_eb; s.len[slot] = (unsigned short)(before - prev_eb);
+          s.pbeg[slot] = (unsigned short)(prev_bpos + 1); s.pend[slot] = (unsigned short)p;
+        }
+        if (bb) {
+          const int hl = 63 - __clzll((long long)bb);
+          last_eb = edges_run + __popcll(eb & seq_below(hl));
+          last_bpos = base + hl;
+        }
+        edges_run += __popcll(eb);
+        faces_run += __popcll(fb);
+      }
+    if (lane == 0) s.count = faces_run;
+  }
+  __syncthreads();
+  const int count = s.count;
+  const int filled = count < P ? count : P;
+  if (tid == 0) {
+    s.edges_total = filled ? (int)s.start[filled - 1] + (int)s.len[filled - 1] : 0;
+    a.count[row] = count;
+  }
+  __syncthreads();
+  const int E = s.edges_total;
+  const size_t slot0 = row * (size_t)P;
+  const unsigned* ftab = a.follows ? a.follows + (size_t)w * a.L * fw : nullptr;
+
+  // per slot, one thread: the score and the enclosure walk with the per-loop minima
+  for (int sl = tid; sl < P; sl += SEQ_THREADS) {
+    const size_t o = slot0 + sl;
+    if (sl >= filled) {
+      a.len[o] = 0; a.start[o] = 0; a.type[o] = 0; a.closed[o] = ftab ? 0 : -1; a.loops[o] = 0; a.score[o] = 0.0;
+      a.dup_of[o] = -1; a.take[o] = 0; a.row_best[o] = 0.0;
+      continue;
+    }
+    const int st = s.start[sl], n = s.len[sl];
+    double score = 0.0;
+    if (a.scores) score = (double)a.scores[row];
+    if (a.logprob) {
+      const float* lrow = a.logprob + row * (size_t)T;
+      const int pe = s.pend[sl];
+      for (int p = s.pbeg[sl]; p <= pe; ++p) score += (double)lrow[p];
+    }
+    int closed = -1, loops = 0;
+    if (ftab) {
+      closed = 1;
+      int cur = st, first = 0, prev = 0, mv = 0, mp = 0;
+      for (int i = st; i < st + n; ++i) {
+        const int ce = s.e[i];
+        if (i == cur) { first = ce; mv = ce; mp = i; }
+        else {
+          if (!((ftab[(size_t)prev * fw + (ce >> 5)] >> (ce & 31)) & 1u)) { closed = 0; break; }
+          if (ce < mv) { mv = ce; mp = i; }
+        }
+        s.lid[i] = (unsigned short)loops;
+        s.slot_of[i] = (unsigned short)sl;
+        prev = ce;
+        if ((ftab[(size_t)ce * fw + (first >> 5)] >> (first & 31)) & 1u) {
+          s.llen[st + loops] = (unsigned short)(i - cur + 1); s.lrot[st + loops] = (unsigned short)mp; s.aux[st + loops] = mv;
+          ++loops;
+          cur = i + 1;
+        }
+      }
+      if (closed == 1 && cur != st + n) closed = 0;      // the last edge does not close its loop
+      if (closed == 0) {
+        loops = 0;
+        for (int i = st; i < st + n; ++i) s.slot_of[i] = (unsigned short)sl;
+      }
+    }
+    s.closed[sl] = (signed char)closed; s.loops[sl] = (unsigned short)loops;
+    a.len[o] = n; a.start[o] = st; a.type[o] = 0; a.closed[o] = closed; a.loops[o] = loops; a.score[o] = score;
+  }
+  __syncthreads();
+
+  // canonical order of the closed faces: every loop rotated to its smallest edge, the loops of a face stably sorted by it
+  if (ftab) {
+    for (int i = tid; i < E; i += SEQ_THREADS) {
+      const int sl = s.slot_of[i], st = s.start[sl], l = i - st, nl = s.closed[sl] == 1 ? (int)s.loops[sl] : 0;
+      if (l >= nl) continue;
+      const int mv = s.aux[i];
+      int o = 0, num = 0;
+      for (int m = 0; m < nl; ++m) {
+        const int v = s.aux[st + m];
+        if (v < mv || (v == mv && m < l)) { o += s.llen[st + m]; ++num; }
+      }
+      s.loff[i] = (unsigned short)o; s.lnum[i] = (unsigned short)num;
+    }
+    __syncthreads();
+  }
+  int* out_edges = a.edges + row * (size_t)T;
+  int* out_loop = a.loop_of + row * (size_t)T;
+  for (int i = tid; i < T; i += SEQ_THREADS) {
+    if (i >= E) { out_edges[i] = -1; out_loop[i] = -1; continue; }
+    int at = i, num = -1;
+    if (ftab) {
+      const int sl = s.slot_of[i];
+      if (s.closed[sl] == 1) {
+        const int rec = s.start[sl] + s.lid[i], n = s.llen[rec];
+        int q = i - (int)s.lrot[rec];
+        if (q < 0) q += n;
+        at = s.start[sl] + s.loff[rec] + q;
+        num = s.lnum[rec];
+      }
+    }
+    out_edges[at] = s.e[i];
+    out_loop[at] = num;
+  }
+  __syncthreads();
+
+  // keys: the mapped edges, then one thread per word
+  const int* emap = a.edge_map ? a.edge_map + (size_t)w * a.L : nullptr;
+  for (int i = tid; i < E; i += SEQ_THREADS) {
+    const int e = s.e[i];
+    int m = emap ? emap[e] : e;
+    if (m < 0 || m >= a.L) m = e;
+    s.aux[i] = m;
+  }
+  __syncthreads();
+  unsigned* out_bits = a.set_bits + slot0 * (size_t)fw;
+  for (size_t x = tid; x < (size_t)P * fw; x += SEQ_THREADS) {
+    const int sl = (int)(x / fw), wd = (int)(x % fw);
+    unsigned word = 0u;
+    if (sl < filled) {
+      const int st = s.start[sl], n = s.len[sl];
+      for (int i = st; i < st + n; ++i) { const int m = s.aux[i]; if ((m >> 5) == wd) word |= 1u << (m & 31); }
+    }
+    out_bits[x] = word;
+  }
+  __syncthreads();      // (the words are read back below by other threads of the block)
+
+  // fold the duplicates of the row: the hash only filters, the words decide
+  for (int sl = tid; sl < filled; sl += SEQ_THREADS) {
+    unsigned h = 0u;
+    const unsigned* mine = out_bits + (size_t)sl * fw;
+    for (int x = 0; x < fw; ++x) h += vote_mix(mine[x] ^ ((unsigned)x * 0x9e3779b9u));
+    s.hash[sl] = h;
+  }
+  __syncthreads();
+  for (int sl = tid; sl < filled; sl += SEQ_THREADS) {
+    const bool part = !a.closed_only || s.closed[sl] == 1;
+    int dup = -1;
+    if (part) {
+      const unsigned h = s.hash[sl];
+      const unsigned* mine = out_bits + (size_t)sl * fw;
+      for (int o = 0; o < sl && dup < 0; ++o) {
+        if (s.hash[o] != h || (a.closed_only && s.closed[o] != 1)) continue;
+        const unsigned* theirs = out_bits + (size_t)o * fw;
+        bool same = true;
+        for (int x = 0; x < fw && same; ++x) same = mine[x] == theirs[x];
+        if (same) dup = o;
+      }
+    }
+    s.dup[sl] = (short)(part ? dup : -2);      // (-2: takes no part)
+  }
+  __syncthreads();
+  for (int sl = tid; sl < filled; sl += SEQ_THREADS) {
+    const size_t o = slot0 + sl;
+    const int dup = s.dup[sl];
+    const double own = a.score[o];
+    double best = own;
+    if (dup == -1) {
+      unsigned long long k = vote_key(own);
+      for (int m = sl + 1; m < filled; ++m)
+        if (s.dup[m] == sl) { const unsigned long long km = vote_key(a.score[slot0 + m]); k = km > k ? km : k; }
+      best = vote_unkey(k);
+    }
+    a.dup_of[o] = dup < 0 ? -1 : dup; a.take[o] = dup == -1 ? 1 : 0; a.row_best[o] = best;
+  }
+}
+
 int votes_cap(int R) {
   int cap = 64;
   while (cap < 2 * R) cap *= 2;
@@ -450,6 +706,39 @@ extern "C" int ff_face_votes(const unsigned* set_bits, const int* len, const int
   a.table_stride = votes_table_stride(R);
   FFProfScope prof(FF_CAT_ROWOP, (double)N * R * (fw + 1), st);
   hipLaunchKernelGGL(face_votes_kernel, dim3((unsigned)N), dim3(VOTE_THREADS), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+extern "C" int ff_face_seq_rows(const int64_t* tokens, int N, int G, int T, const int* num_edges, int L, int ntok, int sep, int eos,
+                                int P, const float* scores, const float* logprob, const int* finished, const unsigned* follows,
+                                const int* edge_map, int flags, int* count, int* len, int* start, int* type, int* closed, int* loops,
+                                int* edges, int* loop_of, unsigned* set_bits, double* score, int* dup_of, int* take,
+                                double* row_best, ff_stream_t stream) {
+  FF_CHECK_ARG(T >= 1 && T <= FF_FACE_SEQ_MAX_T, "ff_face_seq_rows: T=%d outside 1..%d", T, FF_FACE_SEQ_MAX_T);
+  FF_CHECK_ARG(P >= 1 && P <= (T / 2 > 1 ? T / 2 : 1), "ff_face_seq_rows: P=%d slots outside 1..max(T/2, 1) at T=%d", P, T);
+  FF_CHECK_ARG(N >= 0 && G >= 0 && L >= 0, "ff_face_seq_rows: negative size N=%d G=%d L=%d", N, G, L);
+  FF_CHECK_ARG(sep >= 0 && sep < ntok && eos >= 0 && eos < ntok && sep != eos,
+               "ff_face_seq_rows: SEP=%d and EOS=%d must be two tokens of [0, len=%d)", sep, eos, ntok);
+  FF_CHECK_ARG(!(flags & ~FF_FACE_SEQ_CLOSED_ONLY), "ff_face_seq_rows: unknown flag bits %d", flags);
+  FF_CHECK_ARG(!(scores && logprob), "ff_face_seq_rows: scores and logprob may not both be given");
+  FF_CHECK_ARG(tokens, "ff_face_seq_rows: tokens is null");
+  const long long rows = (long long)N * G;
+  if (rows == 0) return FF_OK;
+  FF_CHECK_ARG(num_edges, "ff_face_seq_rows: num_edges is null");
+  FF_CHECK_ARG(count && len && start && type && closed && loops && edges && loop_of && score && dup_of && take && row_best &&
+               (set_bits || L == 0), "ff_face_seq_rows: an output pointer is null");
+  FF_CHECK_ARG(rows < (1LL << 31), "ff_face_seq_rows: %lld rows are too many", rows);
+  hipStream_t st = (hipStream_t)stream;
+  FaceSeqArgs a;
+  a.tokens = tokens; a.num_edges = num_edges; a.scores = scores; a.logprob = logprob; a.finished = finished; a.follows = follows;
+  a.edge_map = edge_map;
+  a.G = G; a.T = T; a.L = L; a.fw = (L + 31) / 32; a.ntok = ntok; a.sep = sep; a.eos = eos; a.P = P;
+  a.closed_only = (flags & FF_FACE_SEQ_CLOSED_ONLY) ? 1 : 0;
+  a.count = count; a.len = len; a.start = start; a.type = type; a.closed = closed; a.loops = loops; a.edges = edges;
+  a.loop_of = loop_of; a.set_bits = set_bits; a.score = score; a.dup_of = dup_of; a.take = take; a.row_best = row_best;
+  FFProfScope prof(FF_CAT_ROWOP, (double)rows * T, st);
+  hipLaunchKernelGGL(face_seq_rows_kernel, dim3((unsigned)rows), dim3(SEQ_THREADS), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }

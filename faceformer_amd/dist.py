@@ -211,6 +211,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
     from .models import SurfaceFormer_Parallel
     if getattr(model, "extract_faces", False):
         raise ValueError("decode_sharded does not implement extract_faces (the faces of a wireframe are made on the rank that decoded it)")
+    if getattr(model, "sequence_faces", False):
+        raise ValueError("decode_sharded does not implement sequence_faces (the faces of a wireframe are made on the rank that decoded it)")
     if getattr(model, "constrain_lookahead", False):     # (an option of constrain, which is not taken here either)
         raise ValueError("decode_sharded does not implement constrain_lookahead (%s)" % _modes.SWITCH["constrain"].sharded)
     if getattr(model, "constrain_exact", False):

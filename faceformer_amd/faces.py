@@ -25,7 +25,8 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "filter_faces_by_coedge", "postprocess_faces", "faces_record", "dumps_record",
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
            "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance",
-           "face_rows", "face_votes", "faces_of_rows", "parse_faces_samples_scored", "parse_faces_beams_scored"]
+           "face_rows", "face_votes", "faces_of_rows", "parse_faces_samples_scored", "parse_faces_beams_scored",
+           "face_seq_rows", "face_seq_votes", "faces_of_seq_rows"]
 
 
 def _tok(token, name, default):
@@ -793,6 +794,197 @@ def faces_of_rows(rows, votes, w):
             word = bits[r]
             key = tuple(int(32 * x + b) for x in range(word.size) for b in range(32) if (int(word[x]) >> b) & 1)
             unique.append((int(mj[r]), key, float(bs[r]), int(vt[r])))
+        out["unique"] = unique
+    return out
+
+
+# ---- the single-sequence model's rows as arrays: the numpy restatements of ff_face_seq_rows and its grouping ------
+# A row holds ALL faces of a wireframe (or of one draw / beam of it), split at SEP: every row gets P face slots.
+FACE_SEQ_MAX_T = 2048
+FACE_SEQ_ROW_KEYS = ("count", "len", "start", "type", "closed", "loops", "edges", "loop_of", "set_bits", "score", "dup_of", "take",
+                     "row_best")
+
+
+def face_seq_rows(tokens, num_edges, token, slots=None, scores=None, logprob=None, finished=None, follows=None, edge_map=None,
+                  closed_only=False, num_lines=None):
+    """ff_face_seq_rows in numpy (include/faceformer_hip.h states the rule): every row of tokens [N, G, T] (or [N, T]: G = 1) split
+    into faces as `_seq_faces` splits it (cut after the first EOS, split after every SEP, the last token of a piece dropped; an
+    unfinished row -- finished [N, G] zero -- cut behind its last nonzero token first, as parse_faces_beams_scored does), every
+    face walked, ordered and keyed as face_rows does a row, duplicates inside a row folded.  num_edges [N], clamped into [0, L];
+    token: the config's (len, SEP, EOS); slots = P face slots per row (None: max(T // 2, 1)); scores [N, G] or logprob [N, G, T]
+    (not both); follows [N, L, ceil(L/32)] int32 or None; edge_map [N, L] int32 or None; closed_only: only closed faces take
+    part in the fold.  L = the table's / the map's, else num_lines.  Returns dict of arrays: count [N, G] int32; len, start, type,
+    closed, loops, dup_of, take [N, G, P] int32; edges, loop_of [N, G, T] int32; set_bits [N, G, P, ceil(L/32)] int32 (the uint32
+    words); score, row_best [N, G, P] float64."""
+    t = np.asarray(tokens, dtype=np.int64)
+    if t.ndim == 2:
+        t = t[:, None, :]
+    if t.ndim != 3:
+        raise ValueError("tokens must be [N, T] or [N, G, T]")
+    N, G, T = t.shape
+    if not 1 <= T <= FACE_SEQ_MAX_T:
+        raise ValueError("tokens hold T=%d positions: 1..%d are taken" % (T, FACE_SEQ_MAX_T))
+    P = max(T // 2, 1) if slots is None else int(slots)
+    if not 1 <= P <= max(T // 2, 1):
+        raise ValueError("slots=%d: must be in 1..max(T // 2, 1) = %d" % (P, max(T // 2, 1)))
+    ntok, sep, eos = _tok(token, "len", 4), _tok(token, "SEP", 2), _tok(token, "EOS", 3)
+    if not (0 <= sep < ntok and 0 <= eos < ntok and sep != eos):
+        raise ValueError("SEP=%d and EOS=%d must be two tokens of [0, len=%d)" % (sep, eos, ntok))
+    if scores is not None and logprob is not None:
+        raise ValueError("scores and logprob may not both be given")
+    fol = None if follows is None else np.asarray(follows).view(np.uint32) if np.asarray(follows).dtype == np.int32 else np.asarray(follows, dtype=np.uint32)
+    emap = None if edge_map is None else np.asarray(edge_map, dtype=np.int64)
+    if fol is None and emap is None and num_lines is None:
+        raise ValueError("num_lines is needed without a follow table and an edge map")
+    L = fol.shape[1] if fol is not None else emap.shape[1] if emap is not None else int(num_lines)
+    fw = (L + 31) // 32
+    if fol is not None and fol.shape != (N, L, fw):
+        raise ValueError("follows must be [N, L, ceil(L/32)]")
+    if emap is not None and emap.shape != (N, L):
+        raise ValueError("edge_map must be [N, L]")
+    ne = np.clip(np.asarray(num_edges, dtype=np.int64).reshape(N), 0, L)
+    sc = None if scores is None else np.asarray(scores, dtype=np.float32).reshape(N, G)
+    lp = None if logprob is None else np.asarray(logprob, dtype=np.float32).reshape(N, G, T)
+    fin = None if finished is None else np.asarray(finished).reshape(N, G)
+    i32 = lambda fill: np.full((N, G, P), fill, np.int32)
+    out = {"count": np.zeros((N, G), np.int32), "len": i32(0), "start": i32(0), "type": i32(0),
+           "closed": i32(0 if fol is not None else -1), "loops": i32(0), "edges": np.full((N, G, T), -1, np.int32),
+           "loop_of": np.full((N, G, T), -1, np.int32), "set_bits": np.zeros((N, G, P, fw), np.uint32),
+           "score": np.zeros((N, G, P), np.float64), "dup_of": i32(-1), "take": i32(0), "row_best": np.zeros((N, G, P), np.float64)}
+
+    def bit(w, a, b):
+        return bool((int(fol[w, a, b >> 5]) >> (b & 31)) & 1)
+
+    for w in range(N):
+        for g in range(G):
+            if sc is not None and sc[w, g] == -np.inf:
+                continue
+            row = t[w, g]
+            end = T - 1
+            if fin is not None and fin[w, g] == 0:
+                used = np.flatnonzero(row)
+                if used.size == 0:
+                    continue
+                end = int(used[-1])
+            hit = np.flatnonzero(row[: end + 1] == eos)
+            if hit.size:
+                end = int(hit[0])
+            s, at, first = 0, 0, 0                     # the next slot, its start, the first position of the running piece
+            for p in range(end + 1):
+                if row[p] != sep and p != end:
+                    continue
+                v = row[first: p] - ntok                # (the boundary token is dropped)
+                e = [int(x) for x in v[(v >= 0) & (v < ne[w])]]
+                a, first = first, p + 1
+                if not e:
+                    continue
+                if s >= P:
+                    s += 1
+                    continue
+                n = len(e)
+                out["len"][w, g, s], out["start"][w, g, s] = n, at
+                if sc is not None:
+                    out["score"][w, g, s] = np.float64(sc[w, g])
+                elif lp is not None:
+                    out["score"][w, g, s] = np.cumsum(np.concatenate(([0.0], lp[w, g, a: p + 1].astype(np.float64))))[-1]
+                order, loop_of = e, [-1] * n
+                if fol is not None:
+                    loops, start, ok = [], None, True
+                    for i, x in enumerate(e):
+                        if start is None:
+                            start = i
+                        elif not bit(w, e[i - 1], x):
+                            ok = False
+                            break
+                        if bit(w, x, e[start]):
+                            loops.append(e[start: i + 1])
+                            start = None
+                    ok = ok and start is None
+                    out["closed"][w, g, s] = int(ok)
+                    if ok:
+                        out["loops"][w, g, s] = len(loops)
+                        rolled = []
+                        for lo in loops:
+                            m = lo.index(min(lo))
+                            rolled.append(lo[m:] + lo[:m])
+                        rolled.sort(key=lambda lo: lo[0])                     # (stable)
+                        order = [x for lo in rolled for x in lo]
+                        loop_of = [k for k, lo in enumerate(rolled) for _ in lo]
+                out["edges"][w, g, at: at + n] = order
+                out["loop_of"][w, g, at: at + n] = loop_of
+                for x in e:
+                    m = int(emap[w, x]) if emap is not None else x
+                    if not 0 <= m < L:
+                        m = x
+                    out["set_bits"][w, g, s, m >> 5] |= np.uint32(1 << (m & 31))
+                s, at = s + 1, at + n
+            out["count"][w, g] = s
+            # the fold: a draw counts once for a face
+            seen = {}
+            for k in range(min(s, P)):
+                out["row_best"][w, g, k] = out["score"][w, g, k]
+                if closed_only and out["closed"][w, g, k] != 1:
+                    continue
+                key = out["set_bits"][w, g, k].tobytes()
+                if key in seen:
+                    out["dup_of"][w, g, k] = seen[key][0]
+                    seen[key].append(k)
+                else:
+                    seen[key] = [k]
+                    out["take"][w, g, k] = 1
+            for members in seen.values():
+                v = out["score"][w, g, members]
+                out["row_best"][w, g, members[0]] = v[int(np.argmax(_score_order(v)))]
+    out["set_bits"] = out["set_bits"].view(np.int32)
+    return out
+
+
+def face_seq_votes(rows, require_closed=False):
+    """The grouping behind face_seq_rows: face_votes, unchanged, over the G * P slots of every wireframe with len := take and
+    score := row_best -- `votes` is then the number of draws (beams) that hold the face, `rep` the first draw's first slot that
+    holds it (slot index g * P + s), `best` the best score.  Returns face_votes' dict shaped [N, G, P] (num_faces [N])."""
+    take = np.asarray(rows["take"])
+    N, G, P = take.shape
+    flat = lambda k: np.asarray(rows[k]).reshape(N, G * P, 1)
+    votes = face_votes({"len": flat("take"), "type": flat("type"), "closed": flat("closed"), "score": flat("row_best"),
+                        "set_bits": np.asarray(rows["set_bits"]).reshape(N, G * P, 1, -1)}, require_closed=require_closed)
+    return {k: (v if k == "num_faces" else v.reshape(N, G, P)) for k, v in votes.items()}
+
+
+def faces_of_seq_rows(rows, votes, w):
+    """The arrays of wireframe w (face_seq_rows' and face_seq_votes' dicts) as the list forms: `parsed` and `scored`, one list per
+    row g of [(0, (edge, ...))] / [(0, edges, score)] in slot order (decode order for an open or unwalked face, canonical order
+    for a closed one); `enclosed`, one list per row of the closed faces [(0, ((edge, ...), ...))] as filter_faces_by_encloseness
+    returns them; `unique` [(0, sorted edge set, best, votes)] over all rows in first-seen order -- the edge set is read back from
+    the bitmap, so with an edge_map it holds the mapped edges.  votes may be None (no `unique`)."""
+    ln, st, cl = (np.asarray(rows[k])[w] for k in ("len", "start", "closed"))
+    sc, ed, lo = (np.asarray(rows[k])[w] for k in ("score", "edges", "loop_of"))
+    G, P = ln.shape
+    parsed, scored, enclosed = [], [], []
+    for g in range(G):
+        parsed.append([])
+        scored.append([])
+        enclosed.append([])
+        for s in range(P):
+            n, a = int(ln[g, s]), int(st[g, s])
+            if n == 0:
+                continue
+            e = tuple(int(x) for x in ed[g, a: a + n])
+            parsed[g].append((0, e))
+            scored[g].append((0, e, float(sc[g, s])))
+            if cl[g, s] == 1:
+                k = lo[g, a: a + n]
+                enclosed[g].append((0, tuple(tuple(int(x) for x in ed[g, a: a + n][k == i]) for i in range(int(k.max()) + 1))))
+    out = {"parsed": parsed, "scored": scored, "enclosed": enclosed}
+    if votes is not None:
+        bits = np.asarray(rows["set_bits"])[w].reshape(G * P, -1).view(np.uint32)
+        rep = np.asarray(votes["rep"])[w].reshape(-1)
+        vt, bs = (np.asarray(votes[k])[w].reshape(-1) for k in ("votes", "best"))
+        unique = []
+        for r in np.flatnonzero(rep == np.arange(G * P)):
+            word = bits[r]
+            key = tuple(int(32 * x + b) for x in range(word.size) for b in range(32) if (int(word[x]) >> b) & 1)
+            unique.append((0, key, float(bs[r]), int(vt[r])))
         out["unique"] = unique
     return out
 

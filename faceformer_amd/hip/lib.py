@@ -199,6 +199,8 @@ FF_FACE_OWN_STOP = 1          # ff_face_rows
 FF_FACE_REQUIRE_CLOSED = 1    # ff_face_votes
 FF_FACE_MAX_T = 256
 FF_FACE_MAX_ROWS = 65536
+FF_FACE_SEQ_CLOSED_ONLY = 1   # ff_face_seq_rows
+FF_FACE_SEQ_MAX_T = 2048
 
 # ff_stop_fn: int (*)(void* user, const int* step_counts, int num_steps)
 STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int)
@@ -367,6 +369,8 @@ SIGNATURES = {
     "ff_face_votes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ff_face_votes": (C.c_int, [fptr, fptr, fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr,
                                 C.c_size_t, fptr]),
+    "ff_face_seq_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr,
+                                   fptr, fptr, C.c_int] + [fptr] * 13 + [fptr]),
 }
 
 _lib = None
@@ -397,7 +401,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_* and *_beam*_ahead ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead and ff_face_seq_rows ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

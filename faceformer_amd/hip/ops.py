@@ -901,6 +901,119 @@ def face_votes(rows, require_closed=False):
                        bool(require_closed))
 
 
+FACE_SEQ_ROW_KEYS = ("count", "len", "start", "type", "closed", "loops", "edges", "loop_of", "set_bits", "score", "dup_of", "take",
+                     "row_best")
+
+
+def _seq_operand(t, name, dtype, shape):
+    """An operand of face_seq_rows / face_seq_votes: ValueError for what is not a tensor of this dtype and shape (None in the
+    shape: any size)."""
+    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != len(shape) or \
+            any(s is not None and s != n for s, n in zip(shape, t.shape)):
+        raise ValueError("%s must be a %s tensor [%s]" % (name, str(dtype).replace("torch.", ""),
+                                                         ", ".join("*" if s is None else str(s) for s in shape)))
+
+
+@_on_tensor_device
+def face_seq_rows(tokens, num_edges, token, slots=None, scores=None, logprob=None, finished=None, follows=None, edge_map=None,
+                  closed_only=False, num_lines=None):
+    """The faces of the single-sequence model's decoded rows, on the device (ff_face_seq_rows; include/faceformer_hip.h
+    states the rule).  tokens [N, G, T] int64 (or [N, T]: G = 1, and the row operands may then leave that axis out too), T <= 2048; num_edges [N] int32; token: the config's (len, SEP,
+    EOS); slots = P face slots per row (None: max(T // 2, 1), which never truncates); scores [N, G] fp32 or logprob [N, G, T] fp32
+    (not both); finished [N, G] int32; follows [N, L, ceil(L/32)] int32 (ops.follow_table) or None: no walk; edge_map [N, L] int32
+    or None; closed_only: only closed faces take part in the fold.  L = the table's / the map's, else num_lines.  Returns a dict
+    of device tensors: count [N, G] int32; len, start, type, closed, loops, dup_of, take [N, G, P] int32; edges, loop_of [N, G, T]
+    int32; set_bits [N, G, P, ceil(L/32)] int32; score, row_best [N, G, P] fp64.  faces.face_seq_rows is the numpy restatement,
+    bit for bit.  Every refusal below is a ValueError raised before the library is touched."""
+    if not torch.is_tensor(tokens) or tokens.dim() not in (2, 3) or tokens.dtype != torch.int64:
+        raise ValueError("tokens must be an int64 tensor [N, T] or [N, G, T]")
+    if tokens.dim() == 2:        # (G = 1: the row operands may leave the axis out as well)
+        tokens = tokens.unsqueeze(1)
+        scores, finished = (t.unsqueeze(1) if torch.is_tensor(t) and t.dim() == 1 else t for t in (scores, finished))
+        logprob = logprob.unsqueeze(1) if torch.is_tensor(logprob) and logprob.dim() == 2 else logprob
+    N, G, T = tokens.shape
+    if not 1 <= T <= _L.FF_FACE_SEQ_MAX_T:
+        raise ValueError("face_seq_rows takes 1..%d positions per row (got T=%d)" % (_L.FF_FACE_SEQ_MAX_T, T))
+    pmax = max(T // 2, 1)
+    if slots is not None and (isinstance(slots, bool) or not isinstance(slots, int)):
+        raise ValueError("slots=%r: must be None or an integer" % (slots,))
+    P = pmax if slots is None else slots
+    if not 1 <= P <= pmax:
+        raise ValueError("slots=%d: must be in 1..max(T // 2, 1) = %d" % (P, pmax))
+    if G * P > _L.FF_FACE_MAX_ROWS:
+        raise ValueError("face_seq_rows takes at most %d slots per wireframe (got G * P = %d)" % (_L.FF_FACE_MAX_ROWS, G * P))
+    ntok, sep, eos = _tok_field(token, "len"), _tok_field(token, "SEP"), _tok_field(token, "EOS")
+    if not (0 <= sep < ntok and 0 <= eos < ntok and sep != eos):
+        raise ValueError("SEP=%d and EOS=%d must be two tokens of [0, len=%d)" % (sep, eos, ntok))
+    if scores is not None and logprob is not None:
+        raise ValueError("scores and logprob may not both be given")
+    _seq_operand(num_edges, "num_edges", torch.int32, (N,))
+    for t, name, dtype, shape in ((scores, "scores", torch.float32, (N, G)), (logprob, "logprob", torch.float32, (N, G, T)),
+                                  (finished, "finished", torch.int32, (N, G))):
+        if t is not None:
+            _seq_operand(t, name, dtype, shape)
+    if follows is not None:
+        _seq_operand(follows, "follows", torch.int32, (N, None, None))
+        if follows.size(2) != (follows.size(1) + 31) // 32:
+            raise ValueError("follows must be [N, L, ceil(L/32)]")
+    if follows is None and edge_map is None and num_lines is None:
+        raise ValueError("num_lines is needed without a follow table and an edge map")
+    if edge_map is not None:
+        _seq_operand(edge_map, "edge_map", torch.int32, (N, follows.size(1) if follows is not None else None))
+    L = follows.size(1) if follows is not None else edge_map.size(1) if edge_map is not None else int(num_lines)      # (the restatement's order)
+    if L < 0:
+        raise ValueError("num_lines must be >= 0")
+    for t, name, dtype in ((tokens, "tokens", torch.int64), (num_edges, "num_edges", torch.int32), (scores, "scores", torch.float32),
+                           (logprob, "logprob", torch.float32), (finished, "finished", torch.int32), (follows, "follows", torch.int32),
+                           (edge_map, "edge_map", torch.int32)):
+        if t is not None:
+            _dev(t, name, dtype)
+    fw = (L + 31) // 32
+    c = lambda t: None if t is None else t.contiguous()
+    tokens, num_edges, scores, logprob, finished, follows, edge_map = (
+        c(t) for t in (tokens, num_edges, scores, logprob, finished, follows, edge_map))
+    dev = tokens.device
+    out = {k: torch.empty((N, G, P), device=dev, dtype=torch.int32) for k in ("len", "start", "type", "closed", "loops", "dup_of", "take")}
+    out["count"] = torch.empty((N, G), device=dev, dtype=torch.int32)
+    out["edges"] = torch.empty((N, G, T), device=dev, dtype=torch.int32)
+    out["loop_of"] = torch.empty((N, G, T), device=dev, dtype=torch.int32)
+    out["set_bits"] = torch.empty((N, G, P, fw), device=dev, dtype=torch.int32)
+    out["score"] = torch.empty((N, G, P), device=dev, dtype=torch.float64)
+    out["row_best"] = torch.empty((N, G, P), device=dev, dtype=torch.float64)
+    _L.check(_L.load().ff_face_seq_rows(_p(tokens), N, G, T, _p(num_edges), L, ntok, sep, eos, P, _p(scores), _p(logprob), _p(finished),
+                                        _p(follows), _p(edge_map), _L.FF_FACE_SEQ_CLOSED_ONLY if closed_only else 0,
+                                        *[_p(out[k]) for k in FACE_SEQ_ROW_KEYS], _stream()), "ff_face_seq_rows")
+    return {k: out[k] for k in FACE_SEQ_ROW_KEYS}
+
+
+def face_seq_votes(rows, require_closed=False):
+    """The de-duplicated faces of every wireframe behind face_seq_rows, on the device: ff_face_votes, unchanged, over
+    the G * P slots of a wireframe with len := take and score := row_best.  rows: face_seq_rows' dict (set_bits, take, type,
+    closed, row_best are read).  Returns a dict of device tensors: rep [N, G, P] int32 (the least slot g * P + s of the wireframe
+    with the same bitmap, -1: takes no part); votes (the draws or beams that hold the face), best (fp64), major at the slots with
+    rep == own index, 0 elsewhere; num_faces [N] int32.  faces.face_seq_votes is the numpy restatement, bit for bit."""
+    try:
+        set_bits, take, ty, closed, best = (rows[k] for k in ("set_bits", "take", "type", "closed", "row_best"))
+    except (KeyError, TypeError):
+        raise ValueError("face_seq_votes takes the dict face_seq_rows returns")
+    if not torch.is_tensor(take) or take.dim() != 3:
+        raise ValueError("rows['take'] must be a tensor [N, G, P]")
+    N, G, P = take.shape
+    if G * P > _L.FF_FACE_MAX_ROWS:
+        raise ValueError("face_seq_votes takes at most %d slots per wireframe (got G * P = %d)" % (_L.FF_FACE_MAX_ROWS, G * P))
+    for t, name, dtype in ((take, "take", torch.int32), (ty, "type", torch.int32), (closed, "closed", torch.int32),
+                           (best, "row_best", torch.float64)):
+        _seq_operand(t, "rows['%s']" % name, dtype, (N, G, P))
+    _seq_operand(set_bits, "rows['set_bits']", torch.int32, (N, G, P, None))
+    for t, name, dtype in ((set_bits, "set_bits", torch.int32), (take, "take", torch.int32), (ty, "type", torch.int32),
+                           (closed, "closed", torch.int32), (best, "row_best", torch.float64)):
+        _dev(t, "rows['%s']" % name, dtype)
+    flat = lambda t: t.contiguous().view(N, G * P, 1)
+    out = _face_votes(set_bits.contiguous().view(N, G * P, 1, set_bits.size(-1)), flat(take), flat(ty), flat(closed), flat(best),
+                      bool(require_closed))
+    return {k: (v if k == "num_faces" else v.view(N, G, P)) for k, v in out.items()}
+
+
 @_on_tensor_device
 def beam_constrained_select(logits, scores, fin, dead, first, prev, visited, width, flags, ntok, follows=None, memory=None,
                             mask=None, kv_len=None, groups_per_wireframe=None, term_range=(1, 4), want_rows=False, want_stats=False,

@@ -1,8 +1,10 @@
 """Shared plumbing of the two model classes: parameter containers with the reference's names, lazy
 binding of those parameters into the native engine, mask/embedding helpers."""
+import numpy as _np
 import torch
 import torch.nn as nn
 
+from .. import faces as _faces
 from ..embedding import PositionEmbeddingLearned, VanillaEmedding
 from ..hip import lib as _L
 from ..hip import modes as _modes
@@ -95,6 +97,11 @@ class SurfaceFormerBase(nn.Module):
         self.sequence_beams = 0        # single-sequence model: W in 1..8 = beam search with W beams per WIREFRAME, decoded together off one
                                        # encoding; 0 = greedy
         self.sequence_beam_stop = "all"  # ... "all": stop once every non-empty beam is finished; "best": once every wireframe's best is
+        self.sequence_faces = False    # single-sequence model: "parse" / "enclosed" = the decoded rows also leave as faces, on the device
+                                       # (inputs["sequence_faces"]: ops.face_seq_rows + ops.face_seq_votes behind the decode,
+                                       # DESIGN.md 31); "enclosed" walks the enclosure rule on the follow table (constrain_tol) and
+                                       # counts closed faces only; inputs["edge_map"] (int32 N x L) maps edges before the grouping
+        self.sequence_faces_slots = None   # ... P face slots per row; None = label_seq_length // 2, which never truncates
         self.sample_temperature = 1.0  # ... logits are divided by it; 0 = the argmax
         self.sample_top_k = 0          # ... keep the K most probable keys (ties at the threshold included); 0 = all
         self.sample_top_p = 1.0        # ... keep the most probable keys up to this share of the mass; 1 = all
@@ -312,11 +319,70 @@ class SurfaceFormerBase(nn.Module):
                 raise ValueError("edge_map must be an int32 tensor of shape [%d, %d]" % (x.size(0), x.size(1)))
         return ef
 
+    def _sequence_faces_value(self, inputs, parallel):
+        """sequence_faces as None / "parse" / "enclosed", after its rules (ValueError, before anything is launched): a SurfaceFormer
+        option of the native engine; sequence_faces_slots = P in 1..max(T // 2, 1) with G * P slots per wireframe inside
+        ff_face_votes' limit (G: the draws or beams of the call); inputs["edge_map"], when given, is int32 N x L."""
+        sf = getattr(self, "sequence_faces", False)
+        if sf is False or sf is None:
+            return None
+        if sf not in ("parse", "enclosed") or not isinstance(sf, str):
+            raise ValueError("sequence_faces=%r: must be False, 'parse' or 'enclosed'" % (sf,))
+        if parallel:
+            raise ValueError("sequence_faces is a SurfaceFormer option (faces split at SEP); SurfaceFormer_Parallel extracts with extract_faces")
+        if not self.engine_supported():
+            raise ValueError("sequence_faces needs the native engine: this model's constructor arguments take the sub-module loop")
+        T = self.num_labels
+        if not 1 <= T <= _faces.FACE_SEQ_MAX_T:
+            raise ValueError("sequence_faces takes label_seq_length in 1..%d (got %d)" % (_faces.FACE_SEQ_MAX_T, T))
+        P = getattr(self, "sequence_faces_slots", None)
+        if P is not None and (isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= max(T // 2, 1)):
+            raise ValueError("sequence_faces_slots=%r: must be None or in 1..max(label_seq_length // 2, 1) = %d" % (P, max(T // 2, 1)))
+        G = max(int(getattr(self, "sequence_samples", 0) or 0), int(getattr(self, "sequence_beams", 0) or 0), 1)
+        if G * (max(T // 2, 1) if P is None else P) > _faces.FACE_MAX_ROWS:
+            raise ValueError("sequence_faces: %d rows x %d slots per wireframe are above %d; lower sequence_faces_slots" % (
+                G, max(T // 2, 1) if P is None else P, _faces.FACE_MAX_ROWS))
+        em = inputs.get("edge_map")
+        if em is not None:
+            x = inputs["input"]
+            if not torch.is_tensor(em) or em.dtype != torch.int32 or tuple(em.shape) != (x.size(0), x.size(1)):
+                raise ValueError("edge_map must be an int32 tensor of shape [%d, %d]" % (x.size(0), x.size(1)))
+        return sf
+
+    def _follow_table(self, inputs, device, num_input, order):
+        """The follow table [N, L, ceil(L/32)] int32 of a constrained decode in the DECODE's wireframe order: built on the device
+        from the edges' end points (ops.follow_table with constrain_tol), or inputs["follow_table"] -- bool [N, L, L] or the
+        packed words -- for the batch as given; then permuted like the wireframes when they are decoded sorted by edge count.
+        num_input: a list of counts or an int32 tensor [N]."""
+        x = inputs["input"]
+        N, L = x.size(0), x.size(1)
+        fw = (L + 31) // 32
+        given = inputs.get("follow_table")
+        if given is None:
+            ni = num_input.to(device=device, dtype=torch.int32) if torch.is_tensor(num_input) else \
+                torch.tensor(num_input, dtype=torch.int32).to(device)
+            bits = ops.follow_table(x[:, :, 0, :2].to(device=device, dtype=torch.float32).contiguous(),
+                                    x[:, :, -1, :2].to(device=device, dtype=torch.float32).contiguous(), ni, float(self.constrain_tol))
+        else:
+            if torch.is_tensor(given) and given.dtype == torch.int32 and tuple(given.shape) == (N, L, fw):
+                bits = given.to(device)                          # packed words: taken as they are (no copy when on the device)
+            else:
+                g = _np.asarray(given.cpu().numpy() if torch.is_tensor(given) else given)
+                if g.dtype == _np.bool_ and g.shape == (N, L, L):
+                    g = _faces.pack_follow_bits(g)
+                if g.dtype != _np.int32 or g.shape != (N, L, fw):
+                    raise ValueError("follow_table must be bool [%d, %d, %d] or packed int32 [%d, %d, %d]" % (N, L, L, N, L, fw))
+                bits = torch.as_tensor(g).to(device)
+        if order is not None:
+            bits = bits.index_select(0, torch.tensor(order, device=device))
+        return bits.contiguous()
+
     def _decode_mode(self, inputs, parallel):
         """(record, value) of the mode this model's attributes select (hip/modes.py: the first of MODES switched on; value: beam
         width / number of samples / constraint flag bits, None for greedy), after the rules only the model can check: what the
         single-sequence model does not take; an opt-in mode needs the native engine and excludes what its record lists."""
         self._extract_faces_value(inputs, parallel)
+        self._sequence_faces_value(inputs, parallel)
         if parallel and getattr(self, "sequence_samples", 0):
             raise ValueError("sequence_samples is a SurfaceFormer option (draws per wireframe of the single-sequence model); "
                              "SurfaceFormer_Parallel draws per anchor with num_samples")

@@ -55,10 +55,18 @@ class SurfaceFormer(SurfaceFormerBase):
         (exact for that beam; the others are returned as they stand).  Adds predict_beams N x W x T (best first, zero behind a
         beam's EOS and the stop step), predict_beam_scores N x W (summed log-probabilities; -inf: an empty rank) and
         predict_beam_finished N x W (int32); predict is beam 0; embedding as above; no pointer.  stop_each_eos is not looked at.
-        Not with sequence_samples, beam_width, return_logprob, an extra mask or the sub-module loop (ValueError)."""
+        Not with sequence_samples, beam_width, return_logprob, an extra mask or the sub-module loop (ValueError).
+
+        sequence_faces = "parse" / "enclosed" (default False): also inputs["sequence_faces"], a dict of device
+        tensors -- len, start, type, closed, loops, score, dup_of, take, row_best, rep, votes, best, major N x G x P, edges, loop_of
+        N x G x T, set_bits N x G x P x ceil(L/32), count N x G, num_faces N -- made by two launches behind the decode from the rows
+        it published (G = the number of draws, the beam width, or 1; P = sequence_faces_slots, None: T // 2);
+        faces.faces_of_seq_rows turns one wireframe's arrays into the list forms.  Nothing of the decode changes; an empty batch
+        publishes the same keys as empty tensors.  Not with the sub-module loop (ValueError)."""
         label = inputs["label"]
         T = self.num_labels
         self._decode_mode(inputs, parallel=False)       # (the records' reasons: hip/modes.py)
+        extract = self._sequence_faces_value(inputs, parallel=False)
         W = self._sequence_beams_value(inputs)
         R = self._sequence_samples_value(inputs)
         if inputs["input"].size(0) == 0:     # an empty batch: the reference's loop stops after its first step (0 EOS == batch size 0, model.py:207)
@@ -78,6 +86,14 @@ class SurfaceFormer(SurfaceFormerBase):
                 inputs["predict_beams"] = torch.zeros((0, W, T), dtype=torch.long, device=dev)
                 inputs["predict_beam_scores"] = torch.zeros((0, W), device=dev)
                 inputs["predict_beam_finished"] = torch.zeros((0, W), dtype=torch.int32, device=dev)
+            if extract:                      # (the keys, dtypes and trailing shapes of a non-empty batch; nothing is launched)
+                G, P = max(R, W, 1), getattr(self, "sequence_faces_slots", None) or max(T // 2, 1)
+                z = lambda dtype, *shape: torch.zeros((0,) + shape, dtype=dtype, device=dev)
+                found = {k: z(torch.int32, G, P) for k in ("len", "start", "type", "closed", "loops", "dup_of", "take", "rep", "votes", "major")}
+                found.update({k: z(torch.float64, G, P) for k in ("score", "row_best", "best")})
+                found.update(count=z(torch.int32, G), edges=z(torch.int32, G, T), loop_of=z(torch.int32, G, T), num_faces=z(torch.int32),
+                             set_bits=z(torch.int32, G, P, (inputs["input"].size(1) + 31) // 32))
+                inputs["sequence_faces"] = found
             return inputs
         if not self.engine_supported():      # post-norm / gelu constructor arguments: the sub-module loop (models/common.py)
             return self._forward_eval_modules(inputs, parallel=False)
@@ -86,10 +102,12 @@ class SurfaceFormer(SurfaceFormerBase):
                              "needed" % (label.size(1), T - 1))
         want_lp = bool(getattr(self, "return_logprob", False))
         eng, memory, mask, kv_len = self._encode(inputs)
-        if W:
-            return self._forward_eval_beams(inputs, eng, memory, mask, kv_len, T, W)
-        if R:
-            return self._forward_eval_samples(inputs, eng, memory, mask, kv_len, T, R)
+        if W or R:
+            inputs = self._forward_eval_beams(inputs, eng, memory, mask, kv_len, T, W) if W else \
+                self._forward_eval_samples(inputs, eng, memory, mask, kv_len, T, R)
+            if extract:
+                inputs["sequence_faces"] = self._sequence_faces_of_decode(inputs, extract, memory.device)
+            return inputs
         out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1,
@@ -101,7 +119,37 @@ class SurfaceFormer(SurfaceFormerBase):
         inputs["predict"] = out["predict"]
         if want_lp:
             inputs["predict_logprob"] = out["logprob"]
+        if extract:
+            inputs["sequence_faces"] = self._sequence_faces_of_decode(inputs, extract, memory.device)
         return inputs
+
+    def _sequence_faces_of_decode(self, inputs, extract, device, greedy_only=False):
+        """inputs["sequence_faces"]: ops.face_seq_rows + ops.face_seq_votes on the rows the decode published --
+        predict_samples with predict_sample_logprob, or predict_beams with predict_beam_scores and predict_beam_finished, else
+        predict (with predict_logprob when there is one; greedy_only: predict alone, whatever else was published).  "enclosed":
+        the enclosure walk on inputs["follow_table"] or on the table built from the end points with constrain_tol, only closed
+        faces are counted, and inputs["edge_map"] maps the edges of the key.  The edge count of a wireframe is inputs["num_input"]
+        when given, else its unmasked edges.  Returns a dict of device tensors N x G x P ..., count N x G, num_faces N."""
+        from ..hip import ops as _ops
+        if "predict_samples" in inputs and not greedy_only:
+            tokens, kw = inputs["predict_samples"], dict(logprob=inputs["predict_sample_logprob"])
+        elif "predict_beams" in inputs and not greedy_only:
+            tokens = inputs["predict_beams"]
+            kw = dict(scores=inputs["predict_beam_scores"], finished=inputs["predict_beam_finished"])
+        else:
+            tokens, kw = inputs["predict"], dict(logprob=inputs.get("predict_logprob"))
+        ni = inputs.get("num_input")
+        if ni is None:
+            ni = (~inputs["input_mask"].to(device=device, dtype=torch.bool)).sum(dim=1)
+        ni = torch.as_tensor(ni).to(device=device, dtype=torch.int32).reshape(-1)
+        enclosed = extract == "enclosed"
+        edge_map = inputs.get("edge_map")
+        found = _ops.face_seq_rows(tokens, ni, self.token, slots=getattr(self, "sequence_faces_slots", None),
+                                   follows=self._follow_table(inputs, device, ni, None) if enclosed else None,
+                                   edge_map=None if edge_map is None else edge_map.to(device), closed_only=enclosed,
+                                   num_lines=inputs["input"].size(1), **kw)
+        found.update(_ops.face_seq_votes(found, require_closed=enclosed))
+        return found
 
     def _sequence_beams_value(self, inputs):
         """sequence_beams as 0 or W in 1..8, after the rules only the model can check (ValueError, before anything is launched):

@@ -167,33 +167,6 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
         found.update(_ops.face_votes(found, require_closed=extract == "enclosed"))
         return found
 
-    def _follow_table(self, inputs, device, num_input, order):
-        """The follow table [N, L, ceil(L/32)] int32 of a constrained decode in the DECODE's wireframe order: built on the device
-        from the edges' end points (ops.follow_table with constrain_tol), or inputs["follow_table"] -- bool [N, L, L] or the
-        packed words -- for the batch as given; then permuted like the wireframes when they are decoded sorted by edge count."""
-        from ..hip import ops as _ops
-        x = inputs["input"]
-        N, L = x.size(0), x.size(1)
-        fw = (L + 31) // 32
-        given = inputs.get("follow_table")
-        if given is None:
-            ni = torch.tensor(num_input, dtype=torch.int32).to(device)
-            bits = _ops.follow_table(x[:, :, 0, :2].to(device=device, dtype=torch.float32).contiguous(),
-                                     x[:, :, -1, :2].to(device=device, dtype=torch.float32).contiguous(), ni, float(self.constrain_tol))
-        else:
-            if torch.is_tensor(given) and given.dtype == torch.int32 and tuple(given.shape) == (N, L, fw):
-                bits = given.to(device)                          # packed words: taken as they are (no copy when on the device)
-            else:
-                g = _np.asarray(given.cpu().numpy() if torch.is_tensor(given) else given)
-                if g.dtype == _np.bool_ and g.shape == (N, L, L):
-                    g = _faces.pack_follow_bits(g)
-                if g.dtype != _np.int32 or g.shape != (N, L, fw):
-                    raise ValueError("follow_table must be bool [%d, %d, %d] or packed int32 [%d, %d, %d]" % (N, L, L, N, L, fw))
-                bits = torch.as_tensor(g).to(device)
-        if order is not None:
-            bits = bits.index_select(0, torch.tensor(order, device=device))
-        return bits.contiguous()
-
     def _follow_distance(self, inputs, device, T, num_input, order, bits):
         """dict(close_dist [N, L, L], cycle_len [N, L]) uint8 of a decode with look-ahead in the DECODE's wireframe order: built on
         the device from `bits` (the follow table, in that order already) with hmax = max(T - 2, 1), the largest budget a step

@@ -1425,6 +1425,54 @@ int ff_decode_sequence_beam(const ff_model* m, const ff_decode_params* p,
                             int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
                             void* workspace, size_t workspace_bytes, const ff_sequence_beam_params* beam, ff_stream_t stream);
 
+/* ---- device-side face extraction behind the single-sequence decode (opt-in; entries added within ABI 105) ----------
+ * The single-sequence model writes all faces of a wireframe into ONE row, split at SEP and ended by EOS (trainer.py:153-177).
+ * ff_face_seq_rows restates faces.parse_faces / parse_faces_scored / parse_faces_samples_scored / parse_faces_beams_scored on
+ * device tensors: it splits every row into face SLOTS, walks, orders and keys every slot as ff_face_rows does a row, and folds
+ * the duplicates inside a row so that a draw (or beam) counts as one vote.  The grouping is ff_face_votes, unchanged.  Everything
+ * is integer-exact apart from one fp64 sum with a fixed order; faces.face_seq_rows is the numpy restatement with the same bits.
+ *
+ * ff_face_seq_rows: one workgroup per row.  Rows are r = w*G + g (G = 1, the number of draws or the beam width).
+ *   tokens [N, G, T] int64, 1 <= T <= FF_FACE_SEQ_MAX_T; num_edges [N] int32, clamped into [0, L]; ntok / sep / eos: the config's
+ *   len, SEP and EOS, 0 <= sep, eos < ntok and sep != eos; P: face slots per row, 1 <= P <= max(T / 2, 1); scores [N, G] fp32 or
+ *   NULL; logprob [N, G, T] fp32 or NULL (not both); finished [N, G] int32 or NULL; follows [N, L, ceil(L/32)] (ff_follow_table's
+ *   words) or NULL; edge_map [N, L] int32 or NULL; flags: FF_FACE_SEQ_CLOSED_ONLY.
+ *   Parse of row r:
+ *     The row yields no face when scores is given and scores[r] == -inf.
+ *     end = T - 1.  With finished given and finished[r] == 0, end is the last position holding a nonzero token; a row with no
+ *       nonzero token yields no face.  If a position p <= end holds eos, end becomes the first such position.
+ *     Position p <= end is a boundary when tok[p] == sep or p == end.  A piece is a maximal run of positions ending in a
+ *       boundary; the boundary token is dropped whatever it is, an edge at an unterminated end included.
+ *     The edges of a piece are its non-boundary tokens with tok - ntok inside [0, num_edges[w]), in order; the test is made on
+ *       the int64 value.
+ *     The faces are the pieces with at least one edge, numbered s = 0, 1, ... in order.  count[r] is their true number (it may
+ *       exceed P; no row has more than T / 2); slots s < min(count, P) are filled.
+ *   Per filled slot: len; start = the sum of the earlier slots' len (the slot's edges lie at edges[r, start .. start + len));
+ *     type = 0; closed and loops by ff_face_rows' enclosure walk on follows (closed = -1, loops = 0 without a table); a closed
+ *     face is written in ff_face_rows' canonical order with loop_of, an open one in decode order with loop_of = -1;
+ *     set_bits[r, s, ceil(L/32)] = the bitmap of the mapped edges by ff_face_rows' rule for edge_map; score (fp64) = scores[r], or
+ *     0 + lp[a] + ... + lp[b] added one by one in fp64 over ALL positions a..b of the piece, its boundary included, or 0.
+ *   Fold: a slot participates when it is filled and, under FF_FACE_SEQ_CLOSED_ONLY, closed == 1.  dup_of[s] = the least
+ *     participating slot s' < s of the row with a bit-identical key, -1 when there is none or s does not participate;
+ *     take[s] = 1 iff s participates and dup_of[s] == -1; row_best[s] (fp64) = at a take slot the greatest score among the slot
+ *     and its duplicates in ff_face_votes' total order (-0 below +0), elsewhere the slot's own score.
+ *   Unfilled slots: len 0, start 0, type 0, closed 0 (-1 without follows), loops 0, dup_of -1, take 0, score and row_best 0, key
+ *     all zero.  edges and loop_of hold -1 behind the last edge written.
+ *   Outputs: count [N*G] int32; len, start, type, closed, loops, dup_of, take [N*G*P] int32; edges, loop_of [N*G, T] int32;
+ *     set_bits [N*G*P, ceil(L/32)] uint32; score, row_best [N*G*P] fp64.  All offsets are size_t.
+ *   Grouping: ff_face_votes with R = G*P, len := take, score := row_best, and FF_FACE_REQUIRE_CLOSED whenever
+ *     FF_FACE_SEQ_CLOSED_ONLY was set: votes = the draws (beams) that hold the face, rep in first-draw, first-place order.
+ *   FF_ERR_ARG before any launch, the outputs untouched, for T outside 1..FF_FACE_SEQ_MAX_T, P outside 1..max(T / 2, 1), sep or
+ *   eos outside [0, ntok) or equal, scores together with logprob, NULL tokens, unknown flag bits, a negative size, a NULL
+ *   num_edges / output. */
+#define FF_FACE_SEQ_CLOSED_ONLY 1
+#define FF_FACE_SEQ_MAX_T 2048
+int ff_face_seq_rows(const int64_t* tokens, int N, int G, int T, const int* num_edges, int L, int ntok, int sep, int eos, int P,
+                     const float* scores, const float* logprob, const int* finished, const unsigned int* follows,
+                     const int* edge_map, int flags, int* count, int* len, int* start, int* type, int* closed, int* loops,
+                     int* edges, int* loop_of, unsigned int* set_bits, double* score, int* dup_of, int* take, double* row_best,
+                     ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,12 +85,35 @@ def decode_batch_with(model, batch, wanted):
     """(`predict`, {record_of parameter: one entry per sample}) of `model(batch)` as numpy arrays; `wanted`: the
     (record_of parameter, output keys) of CLI_FLAGS whose flag is set -- several keys come as one tuple per sample."""
     faces = ("device_faces", ("faces",)) in wanted
-    wanted = [w for w in wanted if w[0] != "device_faces"]
-    if not wanted and not faces:
+    seq_faces = ("sequence_device_faces", ("sequence_faces",)) in wanted
+    wanted = [w for w in wanted if w[0] not in ("device_faces", "sequence_device_faces")]
+    if not wanted and not faces and not seq_faces:
         return decode_batch(model, batch), {}
     with torch.no_grad():
         out = model(batch)
     extras = {}
+    if seq_faces:   # (--sequence-device-faces: the face arrays come over, not the token rows; one wireframe's slice per sample)
+        n = out["predict"].size(0)
+        for param, _ in wanted:          # (record_of only asks whether they exist)
+            extras[param] = [True] * n
+        cut = lambda d: [{k: v[i:i + 1] for k, v in d.items()} for i in range(n)]
+        to_host = lambda d: {k: v.cpu().numpy() for k, v in d.items()}
+        extras["sequence_device_faces"] = cut(to_host(out["sequence_faces"]))
+        if "predict_samples" in out or "predict_beams" in out:
+            # draws / beams: `pred_faces` comes from `predict` alone in the model's form (filtered and mapped for a co-edge
+            # config) -- a second, N-row extraction -- and the faces of all draws are the record's unfiltered, unmapped ones:
+            # for a co-edge config a third extraction in the "parse" form without the edge map
+            with torch.no_grad():
+                first = cut(to_host(model._sequence_faces_of_decode(out, model.sequence_faces, out["predict"].device, greedy_only=True)))
+                every = None
+                if model.sequence_faces == "enclosed":
+                    plain = {k: v for k, v in out.items() if k != "edge_map"}
+                    every = cut(to_host(model._sequence_faces_of_decode(plain, "parse", out["predict"].device)))
+            for i in range(n):
+                extras["sequence_device_faces"][i]["first"] = first[i]
+                if every is not None:
+                    extras["sequence_device_faces"][i]["every"] = every[i]
+        return [None] * n, extras
     for param, keys in wanted:
         # (--device-faces: token rows and log-probabilities stay on the device -- record_of only asks whether they exist)
         arrays = [[True] * out[k].size(0) if faces and (k == "predict_logprob" or (i == 0 and len(keys) > 1)) else out[k].cpu().numpy()
@@ -147,7 +170,8 @@ def score_batch(model, batch):
 
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
-              constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None, sequence_beams=None):
+              constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None, sequence_beams=None,
+              sequence_device_faces=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -179,7 +203,13 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     beam score (faces.parse_faces_beams_scored); `pred_faces` stays what beam 0 (pred) gives.
     device_faces (--device-faces; this sample's slice of the model's inputs["faces"]): the predicted faces of
     every key above come from these arrays (faces.faces_of_rows) instead of from pred, beams and samples, which are then not
-    read; label faces, the metrics and the JSON text are made here as before."""
+    read; label faces, the metrics and the JSON text are made here as before.
+    sequence_device_faces (--sequence-device-faces, single-sequence model; this sample's slice of the model's
+    inputs["sequence_faces"]): the same for that model -- the predicted faces come from these arrays
+    (faces.faces_of_seq_rows) instead of from pred, the draws and the beams, which are then not read."""
+    if sequence_device_faces is not None:
+        return _record_of_sequence_device(cfg, raw, item, sequence_device_faces, logprob is not None, sequence_beams is not None,
+                                          sequence_samples is not None)
     if device_faces is not None:
         return _record_of_device(cfg, raw, item, device_faces, logprob is not None, beams is not None or constrained_beams is not None,
                                  samples is not None or constrained_samples is not None, dead_end,
@@ -321,6 +351,30 @@ def _record_of_device(cfg, raw, item, rows, scored, beams, samples, dead_end, sa
     return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
 
 
+def _record_of_sequence_device(cfg, raw, item, rows, scored, beams, samples):
+    """record_of for --sequence-device-faces: the same record, key for key, from the face arrays `rows` (1 x G x P ...) of this
+    sample.  Under draws / beams, rows["first"] is the extraction over `predict` alone (pred_faces: filtered and mapped for a
+    co-edge config) and rows["every"], for a co-edge config, the one over all draws / beams unfiltered and unmapped."""
+    lf = FZ._seq_faces(item["label"], cfg.model.token, len(raw["edges"]), False)
+    if cfg.post_process.is_coedge:
+        lf = FZ.postprocess_faces(lf, raw["edges"], raw.get("pairings", {}), cfg.post_process.enclosedness_tol)
+    own = rows.get("first", rows)
+    first = FZ.faces_of_seq_rows(own, own, 0)["unique"]
+    m = FZ.face_metrics([(t, key) for t, key, _, _ in first], lf)
+    rec = FZ.faces_record(raw["edges"], raw.get("dominant_directions", []), m["predictions"], m["labels"])
+    if scored:
+        rec["pred_face_scores"] = [s for _, _, s, _ in first]
+    if samples or beams:
+        every = rows.get("every", rows)
+        ranked = sorted(FZ.faces_of_seq_rows(every, every, 0)["unique"], key=lambda f: -f[2])     # (stable: first seen wins among equal scores)
+        kind = "sample" if samples else "beam"
+        rec["pred_%s_faces" % kind] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_%s_face_scores" % kind] = [s for _, _, s, _ in ranked]
+        if samples:
+            rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
+    return FZ.dumps_record(rec), (m["precision"], m["recall"], m["type_acc"])
+
+
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
                     constrain_samples=0, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0, sequence_beam_stop="all"):
@@ -378,7 +432,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
              constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0,
-             sequence_beam_stop="all"):
+             sequence_beam_stop="all", sequence_device_faces=False):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -402,7 +456,11 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     sequences per wireframe under temperature / top_k / top_p / seed and adds pred_sample_faces / pred_sample_face_scores /
     pred_sample_face_votes; pred_faces stays draw 0's; sequence_beams = W (1..8, single-sequence model, single-rank runs only, not
     with scores, score_labels, sample, sequence_samples, beam or device_faces) searches W beams per wireframe under
-    sequence_beam_stop ("all" / "best") and adds pred_beam_faces / pred_beam_face_scores; pred_faces stays beam 0's."""
+    sequence_beam_stop ("all" / "best") and adds pred_beam_faces / pred_beam_face_scores; pred_faces stays beam 0's;
+    sequence_device_faces (single-sequence model, single-rank runs only, not with device_faces or score_labels; alone or with
+    scores, sequence_samples or sequence_beams): the predicted faces of every record are extracted on the device
+    (model.sequence_faces: "enclosed" with the pairings as edge map for co-edge configs, "parse" otherwise) and the records are
+    made from those arrays -- the same records."""
     if sequence_beams:
         if isinstance(sequence_beams, bool) or not isinstance(sequence_beams, int) or not 1 <= sequence_beams <= 8:
             raise ValueError("--sequence-beams must be a width in 1..8")
@@ -436,6 +494,13 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
             raise ValueError("--device-faces applies to SurfaceFormer_Parallel only")
         if dist_mod is not None and dist_mod.get_world_size() > 1:
             raise ValueError("--device-faces is not implemented for multi-rank runs")
+    if sequence_device_faces:
+        if cfg.model_class != "SurfaceFormer":
+            raise ValueError("--sequence-device-faces applies to SurfaceFormer only (SurfaceFormer_Parallel extracts with --device-faces)")
+        if device_faces or score_labels:
+            raise ValueError("--sequence-device-faces does not combine with --device-faces or --score-labels")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--sequence-device-faces is not implemented for multi-rank runs")
     if constrain_samples:
         if not constrain:
             raise ValueError("--constrain-samples requires --constrain")
@@ -483,6 +548,9 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
+    if sequence_device_faces:
+        model.sequence_faces = "enclosed" if cfg.post_process.is_coedge else "parse"
+        model.constrain_tol = float(cfg.post_process.enclosedness_tol)
     ds = dataset_class(cfg.root_dir, cfg.datasets_test, cfg.model)
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
@@ -506,11 +574,13 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         wanted.append(("sequence_beams", ("predict_beams", "predict_beam_scores", "predict_beam_finished")))
     if device_faces:
         wanted.append(("device_faces", ("faces",)))
+    if sequence_device_faces:
+        wanted.append(("sequence_device_faces", ("sequence_faces",)))
     for b0 in range(lo, hi, batch_size):
         idx = list(range(b0, min(hi, b0 + batch_size)))
         items = [ds[i] for i in idx]
         batch = D.collate(items)
-        if device_faces and cfg.post_process.is_coedge:      # map_coedge_into_edges as a table: a co-edge counts as its partner
+        if (device_faces or sequence_device_faces) and cfg.post_process.is_coedge:      # map_coedge_into_edges as a table: a co-edge counts as its partner
             emap = torch.arange(batch["input"].size(1), dtype=torch.int32).repeat(len(idx), 1)
             for k, i in enumerate(idx):
                 for a, b in ds.raw_datas[i].get("pairings", {}).items():
@@ -635,6 +705,12 @@ def build_parser():
     parser.add_argument("--sequence-beam-stop", choices=("all", "best"), default="all",
                         help="with --sequence-beams: stop once every non-empty beam is finished (all), or once the best beam of "
                              "every wireframe is finished (best: exact for that beam, the others are written as they stand)")
+    parser.add_argument("--sequence-device-faces", action="store_true",
+                        help="single-sequence model: the predicted faces of every record -- the split at SEP / EOS, enclosure filter, "
+                             "co-edge mapping, de-duplication with best score and vote count -- are extracted on the device behind "
+                             "the decode (DESIGN.md 31) instead of row by row on the host; alone or with --scores, "
+                             "--sequence-samples or --sequence-beams; the records are the same; single-process runs only, not with "
+                             "--device-faces or --score-labels")
     parser.add_argument("--constrain-beam-closure", choices=("lookahead", "exact"), default=None,
                         help="with --constrain loops --constrain-beams W: the beam search forms every beam's row under the closure "
                              "look-ahead (lookahead) or its exact form (exact), so that the W beams are searched among loops that "
@@ -663,7 +739,8 @@ def main(argv=None):
              constrain_lookahead=args.constrain_lookahead, constrain_exact=args.constrain_exact,
              constrain_samples=args.constrain_samples, device_faces=args.device_faces,
              constrain_beam_closure=args.constrain_beam_closure, sequence_samples=args.sequence_samples,
-             sequence_beams=args.sequence_beams, sequence_beam_stop=args.sequence_beam_stop)
+             sequence_beams=args.sequence_beams, sequence_beam_stop=args.sequence_beam_stop,
+             sequence_device_faces=args.sequence_device_faces)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
