@@ -195,6 +195,17 @@ int ff_constrain_finalize(const int* tok, const float* lp, const int* fin, const
                           const int* num_input, int dedup, int F, int w0, int nw, int Fc, int f0, int b0, int64_t* predict,
                           float* logprob, int* dead_end, int* seq_of_row, hipStream_t st);
 
+// Sequence-constrained decode (ff_constrain_seq.hip): the constrained step's operands with the two tokens of the
+// single-sequence rule in place of a terminator range (io's is not read); one sequence per wireframe, every one from SOS.
+int ff_sequence_rule_check(const char* op, const ff_loop_rule_io& r, int S, int tok_sep, int tok_eos);
+int ff_pointer_sequence_constrained_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st, int tok_sep,
+                                         int tok_eos, ff_stream_t stream);
+int ff_sequence_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int L, int sos,
+                               hipStream_t st);
+int ff_sequence_constrain_finalize(const int* tok, const float* lp, const int* fin, const int* dead, const int* first, int Btot, int T,
+                                   const int* steps_dev, int w0, int nw, int b0, int64_t* predict, float* logprob, int* dead_end,
+                                   int* open_end, int* seq_of_row, hipStream_t st);
+
 // Constrained sampled decode (ff_constrain_sample.hip): the constrained step's operands and the draw's; R draws per
 // anchor in the sampled decode's layout, each with the constrained decode's state.
 int ff_pointer_constrained_sample_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,

@@ -1,0 +1,213 @@
+// Loop-constrained greedy selection for the single-sequence model (opt-in, FF_SEQ2SEQ): one step's constrained
+// selection of every sequence, and the start state / output packing of that decode.
+//
+// One row carries every face of a wireframe, split at SEP and ended by EOS, so the loop rule of DESIGN.md 16 runs per FACE: SEP
+// ends the current face and resets (first, prev) -- and the visited edges, unless FF_CONSTRAIN_ONCE keeps them for the whole
+// row -- and EOS alone finishes the row.  A dead end abandons the face, not the row: SEP alone is re-opened there.
+// include/faceformer_hip.h states the rule on tokens.
+//
+// The rule's device code is ff_select.h's, the one copy the parallel kernels share.  pointer_sequence_constrained_kernel: one
+// wavefront per sequence, four per block, as pointer_constrained_kernel.  A finished sequence appends token 0 and keeps its
+// state.  Every other one writes its byte row with ff_loop_write_row<FF_LOOP_PLAIN> called with the terminator range
+// [SEP, SEP + 1) -- open: every special token masked, SEP re-opened on a dead end; closed: every special token but SEP masked --
+// and then the lanes that own the keys SEP and EOS (lane = key mod 64) apply the two fix-ups of the closed state to their own
+// bytes: EOS is opened, SEP is masked while the current face has no edge (prev == none).  Every lane still reads back only
+// bytes it wrote itself, so ff_pointer_mask_reduce<true> follows without a barrier.  Lane 0 stores token, log-probability, the
+// flags and the next (first, prev) and sets the token's bit in the visited words; on SEP the wave clears its visited words
+// unless ONCE; the wave appends memory[w, token] through ff_pointer_append_row, so FF_L0_FOLD keeps working.  Stop counter:
+// the rows unfinished after the step (ff_pointer_count_waves), DESIGN.md 29's counter.  No LDS beyond the four counter words.
+#include <float.h>
+
+#include "ff_common.h"
+#include "ff_device.h"
+#include "ff_launch.h"
+#include "ff_select.h"
+
+namespace {
+
+struct SeqConstrainArgs {
+  PointerArgs p;                 // as ConstrainArgs.p; p.term_lo / p.term_hi = [SEP, SEP + 1): what ff_loop_write_row re-opens
+  unsigned char* rows;           // [B, S] out: the constraint byte row of every unfinished sequence (1 = masked)
+  const unsigned* follows;       // [wireframes, L, fw] bits or null
+  int L, fw;
+  int flags, ntok, sep, eos;
+  const int* fin_in;             // [B] nonzero: finished before this step
+  const int* first_in;           // [B] first edge of the open loop, -1: none (closed)
+  const int* prev_in;            // [B] last edge of the current face, -1: none (the face has no edge yet)
+  unsigned* visited;             // [B, fw] in / out: the edges of the current face, or under ONCE of every face so far
+  int *fin_out, *first_out, *prev_out, *dead_out;   // [B] out
+  int* tok; float* logprob;      // [B] out
+};
+
+__global__ __launch_bounds__(256) void pointer_sequence_constrained_kernel(SeqConstrainArgs a) {
+  const PointerArgs& pa = a.p;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  int unfinished = 0;
+  if (b < pa.B) {   // (wave-uniform)
+    const int ntok = a.ntok;
+    const int was_fin = ff_ld4i(a.fin_in + b);
+    int first = ff_loop_edge(ff_ld4i(a.first_in + b), a.L), prev = ff_loop_edge(ff_ld4i(a.prev_in + b), a.L);
+    int tok = 0, dead = 0, fin = 1;
+    float lp = 0.f;
+    if (!was_fin) {
+      const int w = b / pa.spg;
+      int kv = pa.S;
+      if (pa.kv_len) { const int k = ff_ldw(pa.kv_len + w); kv = k < kv ? k : kv; }
+      const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * pa.S : nullptr;
+      unsigned* vrow = a.visited + (size_t)b * a.fw;
+      unsigned char* xrow = a.rows + (size_t)b * pa.S;
+      const FFLoopRule rule{a.follows, a.L, a.fw, a.flags, ntok, nullptr, nullptr, 0};
+      dead = ff_loop_write_row<FF_LOOP_PLAIN>(pa, rule, lane, w, kv, mrow, first, prev, vrow, xrow) ? 1 : 0;
+      if ((a.flags & FF_CONSTRAIN_CONNECT) && !(first >= 0 && prev >= 0)) {   // closed: EOS may end the row; no empty face
+        if (lane == (a.eos & 63)) xrow[a.eos] = 0;
+        if (prev < 0 && lane == (a.sep & 63)) xrow[a.sep] = 1;
+      }
+      float m, b2, lsum;
+      ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &tok, &lsum);
+      lp = -logf(lsum);
+      if (tok >= ntok) {
+        const int e = tok - ntok;
+        ff_loop_advance(a.follows, w, a.L, a.fw, e, &first, &prev);
+        if (lane == 0) vrow[e >> 5] |= 1u << (e & 31);
+      } else if (tok == a.sep) {
+        first = prev = -1;
+        if (!(a.flags & FF_CONSTRAIN_ONCE))
+          for (int k = lane; k < a.fw; k += 64) vrow[k] = 0u;
+      }
+      fin = tok == a.eos ? 1 : 0;
+      unfinished = 1 - fin;
+    }
+    if (lane == 0) {
+      ff_st4i(a.tok + b, tok);
+      ff_st4(a.logprob + b, lp);
+      ff_st4i(a.fin_out + b, fin);
+      ff_st4i(a.dead_out + b, dead);
+      ff_st4i(a.first_out + b, first);
+      ff_st4i(a.prev_out + b, prev);
+    }
+    if (pa.next_rows) ff_pointer_append_row(pa, b / pa.spg, b, tok, lane);
+  }
+  ff_pointer_count_waves(pa, pa.B, unfinished);
+}
+
+// ---- engine side: start state and output packing (ff_engine.hip) ---------------------------------------------------------------------
+// Start state of one micro-batch of Bc sequences, one per wireframe: SOS (model.py:191), log-probability 0, unfinished, the
+// rule's state empty and closed.
+__global__ void sequence_constrain_init_kernel(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited,
+                                               int Bc, int fw, int sos) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bc) return;
+  tok[i] = sos;
+  lp[i] = 0.f;
+  fin[i] = 0;
+  dead[i] = 0;
+  first[i] = prev[i] = -1;
+  for (int k = 0; k < fw; ++k) visited[(size_t)i * fw + k] = 0u;
+}
+
+// predict[w, :], logprob[w, :], dead_end[w, :] and open_end[w] of the chunk's nw wireframes (sequence b0 + wl stands for
+// wireframe w0 + wl) from the per-step records (tok, lp, fin, dead, first: [T, Btot], row s = the state after s steps).
+// Position j is kept when j <= the stop step and the sequence was not finished before it: last = min(own EOS, stop step).
+// open_end: a loop is open after the last kept position.
+__global__ void sequence_constrain_finalize_kernel(const int* __restrict__ tok, const float* __restrict__ lp, const int* __restrict__ fin,
+                                                   const int* __restrict__ dead, const int* __restrict__ first, int Btot, int T,
+                                                   const int* __restrict__ steps_p, int w0, int nw, int b0,
+                                                   int64_t* __restrict__ predict, float* __restrict__ logprob,
+                                                   int* __restrict__ dead_end, int* __restrict__ open_end, int* __restrict__ seq_of_row) {
+  const int steps = *steps_p;
+  for (int wl = blockIdx.x * blockDim.x + threadIdx.x; wl < nw; wl += gridDim.x * blockDim.x) {
+    const int seq = b0 + wl;
+    const size_t row = (size_t)(w0 + wl);
+    int64_t* out = predict + row * T;
+    float* olp = logprob + row * T;
+    int* ode = dead_end + row * T;
+    int open = 0;
+    bool done = false;   // finished before position j
+    for (int j = 0; j < T; ++j) {
+      const bool in = j <= steps && !done;
+      const size_t r = (size_t)j * Btot + seq;
+      out[j] = in ? tok[r] : 0;
+      olp[j] = (in && j >= 1) ? lp[r] : 0.f;
+      ode[j] = (in && j >= 1) ? dead[r] : 0;
+      if (in) { open = first[r] >= 0 ? 1 : 0; done = fin[r] != 0; }
+    }
+    open_end[row] = open;
+    if (seq_of_row) seq_of_row[row] = seq;
+  }
+}
+
+}  // namespace
+
+// The flag bits, the two tokens and the follow table of a sequence-constrained step, for operator `op`.
+int ff_sequence_rule_check(const char* op, const ff_loop_rule_io& r, int S, int tok_sep, int tok_eos) {
+  FF_CHECK_ARG(!(r.flags & ~(FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT | FF_CONSTRAIN_ONCE)), "%s: unknown flag bits %d", op, r.flags);
+  FF_CHECK_ARG(!(r.flags & FF_CONSTRAIN_ONCE) || (r.flags & FF_CONSTRAIN_NO_REPEAT), "%s: FF_CONSTRAIN_ONCE needs FF_CONSTRAIN_NO_REPEAT", op);
+  FF_CHECK_ARG(r.ntok >= 0 && r.L >= 0 && r.L == S - r.ntok, "%s: L=%d must be S - ntok = %d - %d", op, r.L, S, r.ntok);
+  FF_CHECK_ARG(tok_sep >= 0 && tok_sep < r.ntok && tok_eos >= 0 && tok_eos < r.ntok && tok_sep != tok_eos,
+               "%s: tok_sep=%d and tok_eos=%d must be two of the %d special tokens", op, tok_sep, tok_eos, r.ntok);
+  FF_CHECK_ARG(r.follows || !(r.flags & FF_CONSTRAIN_CONNECT), "%s: FF_CONSTRAIN_CONNECT needs the follow table", op);
+  return FF_OK;
+}
+
+// The one launch behind ff_pointer_sequence_constrained and the engine's step (io's terminator range is not read: the rule has
+// its two tokens).
+int ff_pointer_sequence_constrained_sync(const ff_step_io& io_in, const ff_loop_rule_io& rule, const ff_constrained_state& s, int tok_sep,
+                                         int tok_eos, ff_stream_t stream) {
+  const char* op = "ff_pointer_sequence_constrained";
+  const int B = io_in.rows, S = io_in.S;
+  if (B == 0) return FF_OK;
+  FF_CHECK_ARG(B > 0 && S > 0 && io_in.rows_per_wireframe > 0, "%s: bad sizes B=%d S=%d", op, B, S);
+  ff_step_io io = io_in;
+  io.term_lo = tok_sep; io.term_hi = tok_sep + 1;   // (what ff_loop_write_row leaves open with the loop closed and re-opens on a dead end)
+  SeqConstrainArgs a;
+  memset(&a, 0, sizeof(a));
+  FF_RETURN_IF(ff_step_args(&a.p, op, true, io));
+  FF_RETURN_IF(ff_sequence_rule_check(op, rule, S, tok_sep, tok_eos));
+  FF_CHECK_ARG(s.fin_in && s.first_in && s.prev_in && s.visited && s.mask_rows && s.next_tok && s.logprob && s.fin_out && s.dead_end &&
+                   s.first_out && s.prev_out, "%s: null pointer", op);
+  a.p.extra = s.mask_rows; a.p.ldextra = S;
+  a.rows = s.mask_rows; a.follows = rule.follows; a.L = rule.L; a.fw = (rule.L + 31) >> 5; a.flags = rule.flags; a.ntok = rule.ntok;
+  a.sep = tok_sep; a.eos = tok_eos;
+  a.fin_in = s.fin_in; a.first_in = s.first_in; a.prev_in = s.prev_in; a.visited = s.visited;
+  a.fin_out = s.fin_out; a.first_out = s.first_out; a.prev_out = s.prev_out; a.dead_out = s.dead_end;
+  a.tok = s.next_tok; a.logprob = s.logprob;
+  hipStream_t st = (hipStream_t)stream;
+  FFProfScope prof(FF_CAT_POINTER, (double)B * S * 4.0, st);
+  hipLaunchKernelGGL(pointer_sequence_constrained_kernel, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+// Restates select_next (model.py:161-167) under the rule, for the loop of model.py:193-210 that starts at SOS (model.py:191).
+extern "C" int ff_pointer_sequence_constrained(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                               int seqs_per_group, const unsigned* follows, int L, int flags, int ntok, int tok_sep,
+                                               int tok_eos, const int* fin_in, const int* first_in, const int* prev_in,
+                                               unsigned* visited, unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out,
+                                               int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
+                                               float* next_rows, int ldnext, float* next_stats, int* count_unfinished,
+                                               ff_stream_t stream) {
+  return ff_pointer_sequence_constrained_sync(
+      ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, 0, 0, ntok, memory, E, next_rows, ldnext, next_stats,
+                 count_unfinished, nullptr, nullptr},
+      ff_loop_rule_io{follows, L, flags, ntok},
+      ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
+      tok_sep, tok_eos, stream);
+}
+
+int ff_sequence_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int L, int sos,
+                               hipStream_t st) {
+  hipLaunchKernelGGL(sequence_constrain_init_kernel, dim3(ff_cdiv(Bc, 256)), dim3(256), 0, st, tok, lp, fin, dead, first, prev, visited,
+                     Bc, (L + 31) >> 5, sos);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+int ff_sequence_constrain_finalize(const int* tok, const float* lp, const int* fin, const int* dead, const int* first, int Btot, int T,
+                                   const int* steps_dev, int w0, int nw, int b0, int64_t* predict, float* logprob, int* dead_end,
+                                   int* open_end, int* seq_of_row, hipStream_t st) {
+  hipLaunchKernelGGL(sequence_constrain_finalize_kernel, dim3(ff_cdiv(nw, 256) < 1024 ? ff_cdiv(nw, 256) : 1024), dim3(256), 0, st, tok, lp,
+                     fin, dead, first, Btot, T, steps_dev, w0, nw, b0, predict, logprob, dead_end, open_end, seq_of_row);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}

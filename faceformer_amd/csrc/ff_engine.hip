@@ -43,6 +43,9 @@
 //     packing with F = 1 -- W beams per WIREFRAME, every one from SOS, beam 0 alone non-empty -- and a sequence form of
 //     ff_beam_select, whose counter is "non-empty beams unfinished after the step" ("all") or "groups whose rank 0 is unfinished
 //     after the step" ("best"): the decode stops at the first step that leaves 0.
+//   sequence constrain (ff_decode_sequence_constrained, single-sequence variant): the greedy single-sequence plan
+//     (F = 1, one sequence per wireframe, chunk_max_seqs) with constrain's records and state, every sequence from SOS, and
+//     ff_pointer_sequence_constrained, whose counter is "rows unfinished after the step".
 //   constrain (ff_decode_constrained): the default plan, one sequence per anchor.  ff_pointer_constrained masks
 //     the keys the enclosure walk could not accept; records and the rule's state (first, prev per step; visited words and the
 //     byte mask per sequence).
@@ -368,7 +371,7 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM, SEQ_CONSTRAIN } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
@@ -393,6 +396,7 @@ struct Mode {
     return ff_constrain_beam_params{q->width, q->flags, q->follows, q->beams, q->scores, q->dead_end, q->trace_parent};
   }
   const ff_constrain_sample_params* csample() const { return static_cast<const ff_constrain_sample_params*>(prm); }
+  const ff_sequence_constrain_params* seqcon() const { return static_cast<const ff_sequence_constrain_params*>(prm); }
 };
 
 // The micro-batch plan of a mode: the default plan for greedy and constrain; without de-duplication for forced (the rows are
@@ -542,6 +546,7 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
       b.row_id = bp.take<int>(Btot);
       break;
     case Mode::CONSTRAIN:
+    case Mode::SEQ_CONSTRAIN:     // (constrain's records with F = 1: one sequence per wireframe)
     case Mode::CONSTRAIN_EXACT:
     case Mode::CONSTRAIN_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
       b.score = bp.take<float>(TB);
@@ -1101,6 +1106,7 @@ struct DecodeRun {
       case Mode::CONSTRAIN_BEAM:
       case Mode::CONSTRAIN_BEAM_AHEAD: follows = mode.cbeam().follows; flags = mode.cbeam().flags; break;
       case Mode::CONSTRAIN_SAMPLE: follows = mode.csample()->follows; flags = mode.csample()->flags; break;
+      case Mode::SEQ_CONSTRAIN: follows = mode.seqcon()->follows; flags = mode.seqcon()->flags; break;
       default: follows = mode.con().follows; flags = mode.con().flags; break;
     }
     return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, flags};
@@ -1136,6 +1142,9 @@ struct DecodeRun {
         return ff_sequence_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, G, p->tok_sos, st);
       case Mode::SEQ_SAMPLE:   // (Fc = R draws per wireframe)
         return ff_sequence_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, G, c.w0, p->tok_sos, st);
+      case Mode::SEQ_CONSTRAIN:   // (every sequence at SOS, the rule's state empty and closed)
+        return ff_sequence_constrain_init(tok, score, fin, buf.dead + c.b0, buf.first + c.b0, buf.prev + c.b0,
+                                          buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), c.Bc, p->L, p->tok_sos, st);
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
       case Mode::CONSTRAIN_EXACT:
@@ -1277,6 +1286,14 @@ struct DecodeRun {
         static const char* const op[3] = {"ff_pointer_constrained", "ff_pointer_constrained_ahead", "ff_pointer_constrained_exact"};
         return ff_pointer_constrained_sync(op[la.form], sio, rio, cs, la.form ? &ahead : nullptr, st);
       }
+      case Mode::SEQ_CONSTRAIN: {   // (constrain's state and records; the rule has SEP and EOS in place of a terminator range)
+        const Rule r = rule_of(c);
+        const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
+                                      buf.byte_rows + (size_t)c.b0 * S, tok_out, buf.score + out, buf.finished + out, buf.dead + out,
+                                      buf.first + out, buf.prev + out};
+        return ff_pointer_sequence_constrained_sync(sio, ff_loop_rule_io{r.follows, r.L, r.flags, m->num_token}, cs, mode.seqcon()->tok_sep,
+                                                    p->tok_eos, st);
+      }
       case Mode::FORCED:   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
         return ff_pointer_forced_sync(sio, tok_out, buf.score + in, buf.greedy + in, buf.rank + in, st);
       default: break;
@@ -1331,7 +1348,9 @@ struct DecodeRun {
   // Which counter the stop rule reads and how: cnt_ge and "the first step that leaves 0" for the parallel variant (tokens >=
   // num_token of unfinished rows), for the sequence sample mode (rows unfinished after the step) and for the sequence beam mode
   // (non-empty beams, or rank-0 beams, unfinished after the step); cnt_eq and the cumulative EOS count otherwise.
-  bool zero_rule() const { return p->variant == FF_PARALLEL || mode.kind == Mode::SEQ_SAMPLE || mode.kind == Mode::SEQ_BEAM; }
+  bool zero_rule() const {
+    return p->variant == FF_PARALLEL || mode.kind == Mode::SEQ_SAMPLE || mode.kind == Mode::SEQ_BEAM || mode.kind == Mode::SEQ_CONSTRAIN;
+  }
   // the stop rule over the first n steps' counters, per_chunk = [n][nch]
   bool stop_rule(const int* per_chunk, int n) {
     tot.assign((size_t)n, 0);
@@ -1493,6 +1512,11 @@ struct DecodeRun {
       case Mode::CONSTRAIN_EXACT:
         return ff_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
                                      c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con().logprob, mode.con().dead_end, io.seq_of_row, main_st);
+      case Mode::SEQ_CONSTRAIN: {   // (F = 1, no de-duplication: num_input is not read)
+        const ff_sequence_constrain_params* q = mode.seqcon();
+        return ff_sequence_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, buf.first, Btot, T, buf.steps_dev, c.w0, c.nw,
+                                              c.b0, io.predict, q->logprob, q->dead_end, q->open_end, io.seq_of_row, main_st);
+      }
       case Mode::CONSTRAIN_SAMPLE: {
         const ff_constrain_sample_params* q = mode.csample();
         return ff_constrain_sample_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, G,
@@ -1828,6 +1852,35 @@ extern "C" int ff_decode_sequence_beam(const ff_model* m, const ff_decode_params
   return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
                                      stream),
                     workspace, workspace_bytes, Mode(Mode::SEQ_BEAM, beam->width, beam));
+}
+
+extern "C" size_t ff_decode_sequence_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p) {
+  if (!p || p->variant != FF_SEQ2SEQ || p->F != 1) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_CONSTRAIN, 1));
+}
+
+// The greedy single-sequence decode (model.py:161-167, 191, 193-210) under the face-loop rule.
+extern "C" int ff_decode_sequence_constrained(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
+                                              const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+                                              int* seq_of_row, void* workspace, size_t workspace_bytes,
+                                              const ff_sequence_constrain_params* constrain, ff_stream_t stream) {
+  const char* name = "ff_decode_sequence_constrained";
+  FF_CHECK_ARG(m && p && constrain, "%s: null model, params or constrain params", name);
+  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1,
+               "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has ff_decode_constrained", name);
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
+               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
+  FF_RETURN_IF(ff_sequence_rule_check(name, ff_loop_rule_io{constrain->follows, p->L, constrain->flags, m->num_token}, p->L + m->num_token,
+                                      constrain->tok_sep, p->tok_eos));
+  FF_CHECK_ARG(constrain->logprob && constrain->dead_end && constrain->open_end && predict,
+               "%s: logprob, dead_end, open_end and predict are required", name);
+  // the finishing range is the EOS token alone: SEP and the other special tokens do not finish a row
+  ff_decode_params q = *p;
+  q.term_lo = p->tok_eos;
+  q.term_hi = p->tok_eos + 1;
+  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
+                                     stream),
+                    workspace, workspace_bytes, Mode(Mode::SEQ_CONSTRAIN, 1, constrain));
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {

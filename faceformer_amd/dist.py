@@ -223,6 +223,8 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
         raise ValueError("decode_sharded does not implement sequence_samples (%s)" % _modes.SEQUENCE_SAMPLE.switches[0].sharded)
     if getattr(model, "sequence_beams", 0):
         raise ValueError("decode_sharded does not implement sequence_beams (%s)" % _modes.SEQUENCE_BEAM.switches[0].sharded)
+    if getattr(model, "sequence_constrain", None) is not None:
+        raise ValueError("decode_sharded does not implement sequence_constrain (%s)" % _modes.SEQUENCE_CONSTRAIN.switches[0].sharded)
     if getattr(model, "constrain_samples", 0):
         raise ValueError("decode_sharded does not implement constrain_samples (%s)" % _modes.SWITCH["constrain"].sharded)
     for mode in reversed(_modes.MODES):

@@ -26,7 +26,8 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "parse_parallel_faces_scored", "parse_faces_scored", "unique_faces_with_scores", "parse_parallel_beams_scored", "score_summary",
            "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance",
            "face_rows", "face_votes", "faces_of_rows", "parse_faces_samples_scored", "parse_faces_beams_scored",
-           "face_seq_rows", "face_seq_votes", "faces_of_seq_rows"]
+           "face_seq_rows", "face_seq_votes", "faces_of_seq_rows",
+           "sequence_rule_start", "sequence_rule_advance", "sequence_rule_mask", "sequence_rule_step"]
 
 
 def _tok(token, name, default):
@@ -523,6 +524,78 @@ def closure_distance(table, visited, first, hmax=254, num_input=None, pad=None):
         reached |= new
         new = t[:, new & avail].any(axis=1)         # the edges with a successor among the available ones of this level
     return dist
+
+
+# ---- the single-sequence model's loop rule, the numpy restatement of ff_pointer_sequence_constrained -------------------
+# include/faceformer_hip.h states the rule on tokens.  State of a row, a function of its prefix: (visited frozenset of edges,
+# first, prev); None = none.  One step on a RAW row plus the state update; the integers are the kernel's, the log-probability is fp64.
+SEQ_NO_REPEAT, SEQ_CONNECT, SEQ_ONCE = 1, 2, 4
+SEQ_FILL = float(np.finfo(np.float32).min)
+
+
+def sequence_rule_start():
+    """The state after column 0 (SOS): nothing visited, the loop closed, the current face without an edge."""
+    return (frozenset(), None, None)
+
+
+def sequence_rule_advance(state, tok, flags, ntok, sep, follows=None):
+    """The state after `tok` was appended.  An edge: first = e if first is none, prev = e, the loop closes when
+    follows[prev][first] (a one-edge loop closes on itself), visited |= e.  SEP: first = prev = none, visited cleared unless ONCE.
+    Any other special token, EOS included: nothing."""
+    visited, first, prev = state
+    tok = int(tok)
+    if tok >= ntok:
+        e = tok - ntok
+        if first is None:
+            first = e
+        prev = e
+        if follows is not None and follows[prev][first]:
+            first = None
+        return (visited | {e}, first, prev)
+    if tok == sep:
+        return (visited if flags & SEQ_ONCE else frozenset(), None, None)
+    return state
+
+
+def sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad):
+    """-> (masked [S] bool: the keys the RULE masks, padding not included; dead_end).  pad [S] bool: the keys masked by padding /
+    kv_len, which the dead-end vote has to see."""
+    visited, first, prev = state
+    masked = np.zeros(S, dtype=bool)
+    connect = bool(flags & SEQ_CONNECT)
+    is_open = connect and first is not None and prev is not None
+    if connect:
+        masked[:ntok] = True
+        if not is_open:
+            masked[eos] = False
+            masked[sep] = prev is None           # no empty face, no SEP SEP ... loop
+    if flags & SEQ_NO_REPEAT:
+        for e in visited:
+            masked[ntok + e] = True
+    dead = False
+    if is_open:
+        masked[ntok:] |= ~np.asarray(follows[prev][: S - ntok], dtype=bool)
+        if not (~masked[ntok:] & ~pad[ntok:]).any():
+            dead = True
+            masked[sep] = False                  # SEP alone: the face is abandoned, the row goes on
+    return masked, dead
+
+
+def sequence_rule_step(raw, pad, state, flags, ntok, sep, eos, follows=None, finished=False):
+    """One row of one step on RAW logits.  -> dict(tok, logprob, row (the constrained masked row, fp64), masked (the rule's own
+    byte row), dead, fin (finished after the step), state (after the step)).  A finished row appends token 0 with log-probability
+    0 and keeps its state; a row with no live key gives token 0 and -log S."""
+    raw = np.asarray(raw, dtype=np.float64)
+    S = len(raw)
+    if finished:
+        return dict(tok=0, logprob=0.0, row=raw, masked=np.zeros(S, bool), dead=False, fin=True, state=state)
+    pad = np.asarray(pad, dtype=bool)
+    masked, dead = sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad)
+    row = np.where(masked | pad, SEQ_FILL, raw)
+    tok = int(np.argmax(row))                    # (lowest index on ties)
+    lp = -float(np.log(np.exp(row - row[tok]).sum()))
+    return dict(tok=tok, logprob=lp, row=row, masked=masked, dead=dead, fin=tok == eos,
+                state=sequence_rule_advance(state, tok, flags, ntok, sep, follows))
 
 
 def is_face_enclosed(edges, face_indices, tol):

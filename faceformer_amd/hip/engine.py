@@ -376,7 +376,7 @@ class PathEngine:
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
                constrain_samples=None, constrain_beam_closure=None, sequence_samples=None, sequence_beams=None,
-               sequence_beam_stop="all"):
+               sequence_beam_stop="all", sequence_constrain=None, tok_sep=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -463,7 +463,34 @@ class PathEngine:
         w, best first, zero behind its EOS and the stop step), `beam_scores` [N*W] (-inf: an empty rank) and `beam_finished`
         [N*W] int32; `predict` [N, T] is beam 0; with trace=True `logits` [T-1, N*W, S] and `beam_parent` [T-1, N*W] in
         output-row order.  No term_range.  Excludes every other mode and option above, and stop_each_eos.  W=1 equals the greedy
-        FF_STOP_EACH_EOS decode cut behind every row's first EOS."""
+        FF_STOP_EACH_EOS decode cut behind every row's first EOS.
+
+        sequence_constrain="no_repeat" / "loops" / "coedge_loops" (single-sequence variant only, ff_decode_sequence_constrained,
+        DESIGN.md 32; None: the greedy decode above; the flag bits 0..7 are taken too) with tok_sep: the greedy decode under the
+        face-loop rule applied per face of the row.  SEP ends a face, tok_eos alone the row; a dead end re-opens SEP alone and the
+        row goes on; "coedge_loops" also forbids a co-edge twice in the row.  follow_table [N, L, ceil(L/32)] int32 on the device,
+        required by "loops" and "coedge_loops".  The decode stops after the first step that leaves no row unfinished
+        (`step_counts`: the rows unfinished after every step).  `predict` [N, T] is zero behind the row's EOS and the stop step;
+        also `logprob` [N, T] fp32 (under the renormalised distribution), `dead_end` [N, T] int32 (1 where the SEP was selected at
+        a dead end) and `open_end` [N] int32 (a loop is open after the last kept position); with trace=True `logits` [T-1, N, S]
+        holds the constrained masked rows.  No term_range.  Excludes every other mode and option above, and stop_each_eos.  Bits
+        0 equal the greedy FF_STOP_EACH_EOS decode cut behind every row's first EOS, with logprob=True's log-probabilities."""
+        SC = _modes.sequence_constrain_flags(sequence_constrain)
+        if SC is not None:
+            if tok_sep is None:
+                raise ValueError("sequence_constrain needs tok_sep, the token that ends a face")
+            o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
+                     logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
+                     constrain=constrain is not None, sequence_samples=int(sequence_samples or 0),
+                     sequence_beams=int(sequence_beams or 0), sequence_constrain=SC, follow_table=follow_table, tok_sep=int(tok_sep),
+                     trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
+            if not (0 <= int(tok_sep) < self.num_token and 0 <= int(tok_eos) < self.num_token) or int(tok_sep) == int(tok_eos):
+                raise ValueError("sequence_constrain: tok_sep=%d and tok_eos=%d must be two different special tokens (below %d)"
+                                 % (int(tok_sep), int(tok_eos), self.num_token))
+            return self._decode_sequence(_modes.SEQUENCE_CONSTRAIN, "the parallel variant constrains with constrain", memory, mask_u8,
+                                         kv_len, variant, o, (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes,
+                                                              chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows, flags,
+                                                              x3_min_rows), sync_every, tok_sos, tok_eos)
         SB = _modes.sequence_beams_value(sequence_beams)
         if SB:
             o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
@@ -586,28 +613,29 @@ class PathEngine:
         return out
 
     def _decode_sequence(self, mode, parallel_has, memory, mask_u8, kv_len, variant, o, params, sync_every, tok_sos, tok_eos):
-        """decode(sequence_samples=R) and decode(sequence_beams=W), `mode` their record: the checks (ValueError before anything is
-        launched), the outputs and the one call of ff_decode_sequence_sample / ff_decode_sequence_beam, whose argument list has no
+        """decode(sequence_samples=R), decode(sequence_beams=W) and decode(sequence_constrain=...), `mode` their record: the checks
+        (ValueError before anything is launched), the outputs and the one call of ff_decode_sequence_sample /
+        ff_decode_sequence_beam / ff_decode_sequence_constrained, whose argument list has no
         num_input, extra mask, pointer or best / second traces.  params: _params' arguments."""
         if variant != _L.FF_SEQ2SEQ or o["F"] != 1:
             raise ValueError("%s is a single-sequence option (FF_SEQ2SEQ, F = 1); %s" % (mode.subject, parallel_has))
         _modes.check_options(mode, variant, o, None)
         if params[-2] & _L.FF_STOP_EACH_EOS:
             raise ValueError("%s excludes stop_each_eos (FF_STOP_EACH_EOS): every %s is finished by its own EOS already"
-                             % (mode.subject, "draw" if mode is _modes.SEQUENCE_SAMPLE else "beam"))
+                             % (mode.subject, {"sequence_samples": "draw", "sequence_beams": "beam"}.get(mode.subject, "row")))
         mode.operand(self, o)
         prm = self._params(*params)
         _dev(memory, "memory")
         self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
         N, S, E = memory.shape
-        T, R, dev = o["T"], o[mode.subject], self.device
+        T, R, dev = o["T"], (o[mode.subject] if mode.per_anchor else 1), self.device      # (R: the sequences per wireframe)
         prm.sync_every, prm.tok_sos, prm.tok_eos = sync_every, tok_sos, tok_eos
         predict = torch.empty((N, T), device=dev, dtype=torch.int64)
         steps_max = max(T - 1, 1)
         traced = {"logits": torch.full((steps_max, N * R, S), float("nan"), device=dev, dtype=torch.float32)} if o["trace"] else {}
         rows = torch.empty(N * R, device=dev, dtype=torch.int32)
         extra, tail = _modes.outputs(mode, self, o, N, traced)
-        ws = self._workspace(getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm), R))
+        ws = self._workspace(getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm), *((R,) if mode.per_anchor else ())))
         steps = C.c_int(0)
         counts = (C.c_int * steps_max)()
         slots = (C.c_int * steps_max)()

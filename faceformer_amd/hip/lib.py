@@ -193,8 +193,13 @@ class ConstrainSampleParams(C.Structure):
                 ("predict_dead_end", fptr)]
 
 
+class SequenceConstrainParams(C.Structure):
+    _fields_ = [("flags", C.c_int), ("follows", fptr), ("tok_sep", C.c_int), ("logprob", fptr), ("dead_end", fptr), ("open_end", fptr)]
+
+
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
+FF_CONSTRAIN_ONCE = 4         # ff_pointer_sequence_constrained / ff_decode_sequence_constrained only
 FF_FACE_OWN_STOP = 1          # ff_face_rows
 FF_FACE_REQUIRE_CLOSED = 1    # ff_face_votes
 FF_FACE_MAX_T = 256
@@ -363,6 +368,13 @@ SIGNATURES = {
     "ff_decode_sequence_beam_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
     "ff_decode_sequence_beam": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr, C.POINTER(C.c_int),
                                           C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t, C.POINTER(SequenceBeamParams), fptr]),
+    "ff_pointer_sequence_constrained": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                                  fptr, C.c_int, fptr, C.c_int, fptr, fptr, fptr]),
+    "ff_decode_sequence_constrained_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams)]),
+    "ff_decode_sequence_constrained": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t, C.POINTER(SequenceConstrainParams),
+                                                 fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
     "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
                                fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
@@ -401,7 +413,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead and ff_face_seq_rows ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows and *_sequence_constrained ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

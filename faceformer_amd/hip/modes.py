@@ -551,6 +551,48 @@ SEQUENCE_BEAM = Mode(
     tail=_sequence_beam_tail, switches=(Switch("sequence_beams", 0, _NO_STOP_RULE % "sequence-beam", None, False),),
     model_excludes=("sequence_samples", "beam_width", "return_logprob", "an extra mask"))
 
+SEQUENCE_CONSTRAIN_MODES = {"no_repeat": _L.FF_CONSTRAIN_NO_REPEAT, "loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT,
+                            "coedge_loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT | _L.FF_CONSTRAIN_ONCE}
+
+
+def sequence_constrain_flags(sequence_constrain):
+    """The flag bits of a `sequence_constrain` value: None -> None (the option is off), "no_repeat" (1), "loops"
+    (3), "coedge_loops" (7: also no co-edge twice in the row), or the bits themselves, 0..7 -- FF_CONSTRAIN_ONCE (4) only together
+    with FF_CONSTRAIN_NO_REPEAT, as the C entries take it; 0 is the plumbing's identity with the greedy decode."""
+    if sequence_constrain is None:
+        return None
+    if isinstance(sequence_constrain, str):
+        if sequence_constrain not in SEQUENCE_CONSTRAIN_MODES:
+            raise ValueError("sequence_constrain=%r: must be None, 'no_repeat', 'loops' or 'coedge_loops'" % (sequence_constrain,))
+        return SEQUENCE_CONSTRAIN_MODES[sequence_constrain]
+    if isinstance(sequence_constrain, bool) or not isinstance(sequence_constrain, int) or not 0 <= sequence_constrain <= 7:
+        raise ValueError("sequence_constrain=%r: must be None, 'no_repeat', 'loops', 'coedge_loops' or flag bits 0..7"
+                         % (sequence_constrain,))
+    if sequence_constrain & _L.FF_CONSTRAIN_ONCE and not sequence_constrain & _L.FF_CONSTRAIN_NO_REPEAT:
+        raise ValueError("sequence_constrain=%d: FF_CONSTRAIN_ONCE (4) needs FF_CONSTRAIN_NO_REPEAT (1)" % sequence_constrain)
+    return int(sequence_constrain)
+
+
+def _sequence_constrain_values(o):
+    if o["sequence_constrain"] & _L.FF_CONSTRAIN_CONNECT and o["follow_table"] is None:
+        raise ValueError("sequence_constrain with FF_CONSTRAIN_CONNECT ('loops', 'coedge_loops') needs follow_table (ops.follow_table)")
+
+
+# The single-sequence model's loop constraint (DESIGN.md 32): the greedy decode under the face-loop rule applied per face of the
+# row -- SEP ends a face, EOS alone the row, a dead end re-opens SEP alone.  Outside MODES, as SEQUENCE_SAMPLE is: constrain on that
+# model stays the recorded rejection it is (SWITCH and every recorded text stay), and the option is read where the single-sequence
+# model decodes (SurfaceFormer.forward_eval) and refused everywhere else.  No term_range: the rule has tok_sep and tok_eos.  The
+# entry has SEQUENCE_SAMPLE's argument list; one sequence per wireframe, so its size query takes no count.
+SEQUENCE_CONSTRAIN = Mode(
+    subject="sequence_constrain", excludes=_COMMON + ("beam_width", "num_samples", "constrain", "sequence_samples", "sequence_beams"),
+    entry="ff_decode_sequence_constrained", term_range=False, parallel_only=False, values=_sequence_constrain_values,
+    operand=_constrain_operand, own=(("follow_table", _I32),),
+    outs=(("logprob", "T", _F32), ("dead_end", "T", _I32), ("open_end", "", _I32)),
+    tail=lambda o, ptrs, traced: (C.byref(_L.SequenceConstrainParams(o["sequence_constrain"], _p(o["follow_table"]), int(o["tok_sep"]),
+                                                                     *ptrs)),),
+    switches=(Switch("sequence_constrain", None, _NO_STOP_RULE % "sequence-constrained", None, False),),
+    model_excludes=("sequence_samples", "sequence_beams", "return_logprob", "an extra mask"))
+
 MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several mode options, the first one's record reports
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 

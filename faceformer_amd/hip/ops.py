@@ -641,6 +641,56 @@ def pointer_constrained(logits, fin, first, prev, visited, flags, ntok, follows=
                              want_rows, want_stats, counter, None)
 
 
+@_on_tensor_device
+def pointer_sequence_constrained(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows=None, memory=None,
+                                 mask=None, kv_len=None, seqs_per_group=1, want_rows=False, want_stats=False, counter=None):
+    """One constrained selection step of the single-sequence model (ff_pointer_sequence_constrained):
+    pointer_constrained's operands with the tokens SEP and EOS in place of a terminator range, and FF_CONSTRAIN_ONCE (4, only
+    with NO_REPEAT) among the flags.  SEP ends the current face (first = prev = none; the returned visited words are cleared
+    unless ONCE), EOS alone finishes the row, a dead end re-opens SEP alone and the row goes on.  counter (optional, [1] int32)
+    += the rows unfinished after the step.  Returns pointer_constrained's dict; dead_end is this step's flag."""
+    out = {}
+    B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
+    flags, ntok, sep, eos = int(flags), int(ntok), int(tok_sep), int(tok_eos)
+    L = S - ntok
+    fw = (L + 31) // 32
+    if flags & ~(_L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT | _L.FF_CONSTRAIN_ONCE):
+        raise ValueError("unknown constraint flag bits %d" % flags)
+    if flags & _L.FF_CONSTRAIN_ONCE and not flags & _L.FF_CONSTRAIN_NO_REPEAT:
+        raise ValueError("FF_CONSTRAIN_ONCE needs FF_CONSTRAIN_NO_REPEAT")
+    if L < 0 or not (0 <= sep < ntok and 0 <= eos < ntok) or sep == eos:
+        raise ValueError("tok_sep and tok_eos must be two different tokens below ntok <= S")
+    if follows is None and flags & _L.FF_CONSTRAIN_CONNECT:
+        raise ValueError("FF_CONSTRAIN_CONNECT needs the follow table")
+    for x, name in ((fin, "fin"), (first, "first"), (prev, "prev")):
+        _dev(x, name, torch.int32)
+        if x.dim() != 1 or x.numel() != B:
+            raise ValueError("%s must hold one int32 per row of logits" % name)
+    fin, first, prev = fin.contiguous(), first.contiguous(), prev.contiguous()
+    _dev(visited, "visited", torch.int32)
+    if tuple(visited.shape) != (B, fw):
+        raise ValueError("visited must be [%d, %d]" % (B, fw))
+    visited = visited.clone().contiguous()
+    if follows is not None:
+        _dev(follows, "follows", torch.int32)
+        if follows.dim() != 3 or not follows.is_contiguous() or follows.size(0) < nw or tuple(follows.shape[1:]) != (L, fw):
+            raise ValueError("follows must be a contiguous [>= %d, %d, %d] tensor" % (nw, L, fw))
+    dev = logits.device
+    i32 = lambda: torch.empty(B, device=dev, dtype=torch.int32)
+    out = dict({"next": i32(), "logprob": torch.empty(B, device=dev, dtype=torch.float32), "fin": i32(), "dead_end": i32(),
+                "first": i32(), "prev": i32(), "visited": visited, "mask_rows": torch.zeros((B, S), device=dev, dtype=torch.uint8)}, **out)
+    if counter is not None:
+        _dev(counter, "counter", torch.int32)
+    one = torch.zeros(1, device=dev, dtype=torch.int32)   # (L = 0: one word each so that the pointers are not null)
+    vis = visited if fw else one
+    fol = one if (follows is not None and not (L and fw)) else follows
+    _L.check(_L.load().ff_pointer_sequence_constrained(
+        _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(fol), L, flags, ntok, sep, eos, _p(fin), _p(first),
+        _p(prev), _p(vis), _p(out["mask_rows"]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(out["dead_end"]),
+        _p(out["first"]), _p(out["prev"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter), _stream()), "ff_pointer_sequence_constrained")
+    return out
+
+
 def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
                       want_rows, want_stats, counter, ahead, draw=None):
     """pointer_constrained (ahead None), pointer_constrained_ahead (ahead = ("ahead", close_dist, cycle_len, budget)) and

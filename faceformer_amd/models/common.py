@@ -97,6 +97,10 @@ class SurfaceFormerBase(nn.Module):
         self.sequence_beams = 0        # single-sequence model: W in 1..8 = beam search with W beams per WIREFRAME, decoded together off one
                                        # encoding; 0 = greedy
         self.sequence_beam_stop = "all"  # ... "all": stop once every non-empty beam is finished; "best": once every wireframe's best is
+        self.sequence_constrain = None  # single-sequence model: "no_repeat" / "loops" / "coedge_loops" = the greedy decode under the face-loop
+                                       # rule applied per face of the row: SEP ends a face, EOS the row, a dead end re-opens
+                                       # SEP alone; "coedge_loops" also takes no co-edge twice in the row; None = greedy.  The table is
+                                       # built with constrain_tol; inputs["follow_table"] overrides it
         self.sequence_faces = False    # single-sequence model: "parse" / "enclosed" = the decoded rows also leave as faces, on the device
                                        # (inputs["sequence_faces"]: ops.face_seq_rows + ops.face_seq_votes behind the decode,
                                        # DESIGN.md 31); "enclosed" walks the enclosure rule on the follow table (constrain_tol) and
@@ -389,6 +393,9 @@ class SurfaceFormerBase(nn.Module):
         if parallel and getattr(self, "sequence_beams", 0):
             raise ValueError("sequence_beams is a SurfaceFormer option (beams per wireframe of the single-sequence model); "
                              "SurfaceFormer_Parallel searches per anchor with beam_width")
+        if parallel and getattr(self, "sequence_constrain", None) is not None:
+            raise ValueError("sequence_constrain is a SurfaceFormer option (the loop rule per face of the single-sequence model's row); "
+                             "SurfaceFormer_Parallel constrains per anchor with constrain")
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
@@ -494,6 +501,8 @@ class SurfaceFormerBase(nn.Module):
             raise ValueError("score() excludes sequence_samples: set model.sequence_samples = 0 to score given paths")
         if getattr(self, "sequence_beams", 0):
             raise ValueError("score() excludes sequence_beams: set model.sequence_beams = 0 to score given paths")
+        if getattr(self, "sequence_constrain", None) is not None:
+            raise ValueError("score() excludes sequence_constrain: set model.sequence_constrain = None to score given paths")
         if getattr(self, "constrain_samples", 0):     # (an option of constrain: without constrain the lines above have not raised)
             raise ValueError("score() excludes constrain_samples: set model.constrain_samples = 0 to score given paths")
         if not self.engine_supported():

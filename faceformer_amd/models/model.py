@@ -57,6 +57,17 @@ class SurfaceFormer(SurfaceFormerBase):
         predict_beam_finished N x W (int32); predict is beam 0; embedding as above; no pointer.  stop_each_eos is not looked at.
         Not with sequence_samples, beam_width, return_logprob, an extra mask or the sub-module loop (ValueError).
 
+        sequence_constrain = "no_repeat" / "loops" / "coedge_loops" (None: the greedy decode above; the flag bits
+        0..7 are taken too): the greedy decode under the face-loop rule applied per face of the row -- no edge twice in a face,
+        under "loops" every edge starts where the last one ended, SEP only behind a closed non-empty loop (or alone at a dead end,
+        where the face is abandoned and the row goes on), EOS only with the loop closed; "coedge_loops" also takes no co-edge
+        twice in the row.  The table comes from inputs["follow_table"] or from the end points of inputs["input"] with
+        constrain_tol; none is built without CONNECT.  Every row is finished by its own EOS; the decode stops once every row is.
+        Adds predict N x T (zero behind the row's EOS and the stop step), predict_logprob N x T (under the renormalised
+        distribution), predict_dead_end N x T (int32: 1 where the SEP was selected at a dead end), predict_open_end N (int32: a
+        loop is open after the last kept position); embedding as above; no pointer.  Not with sequence_samples, sequence_beams,
+        return_logprob, an extra mask, stop_each_eos = True or the sub-module loop (ValueError).
+
         sequence_faces = "parse" / "enclosed" (default False): also inputs["sequence_faces"], a dict of device
         tensors -- len, start, type, closed, loops, score, dup_of, take, row_best, rep, votes, best, major N x G x P, edges, loop_of
         N x G x T, set_bits N x G x P x ceil(L/32), count N x G, num_faces N -- made by two launches behind the decode from the rows
@@ -69,6 +80,7 @@ class SurfaceFormer(SurfaceFormerBase):
         extract = self._sequence_faces_value(inputs, parallel=False)
         W = self._sequence_beams_value(inputs)
         R = self._sequence_samples_value(inputs)
+        SC = self._sequence_constrain_value(inputs)
         if inputs["input"].size(0) == 0:     # an empty batch: the reference's loop stops after its first step (0 EOS == batch size 0, model.py:207)
             dev, S = inputs["input"].device, inputs["input"].size(1) + self.num_token
             inputs["embedding"] = torch.zeros((0, S, self.num_model), device=dev)
@@ -86,6 +98,11 @@ class SurfaceFormer(SurfaceFormerBase):
                 inputs["predict_beams"] = torch.zeros((0, W, T), dtype=torch.long, device=dev)
                 inputs["predict_beam_scores"] = torch.zeros((0, W), device=dev)
                 inputs["predict_beam_finished"] = torch.zeros((0, W), dtype=torch.int32, device=dev)
+            if SC is not None:
+                del inputs["pointer"]
+                inputs["predict_logprob"] = torch.zeros((0, T), device=dev)
+                inputs["predict_dead_end"] = torch.zeros((0, T), dtype=torch.int32, device=dev)
+                inputs["predict_open_end"] = torch.zeros((0,), dtype=torch.int32, device=dev)
             if extract:                      # (the keys, dtypes and trailing shapes of a non-empty batch; nothing is launched)
                 G, P = max(R, W, 1), getattr(self, "sequence_faces_slots", None) or max(T // 2, 1)
                 z = lambda dtype, *shape: torch.zeros((0,) + shape, dtype=dtype, device=dev)
@@ -105,6 +122,11 @@ class SurfaceFormer(SurfaceFormerBase):
         if W or R:
             inputs = self._forward_eval_beams(inputs, eng, memory, mask, kv_len, T, W) if W else \
                 self._forward_eval_samples(inputs, eng, memory, mask, kv_len, T, R)
+            if extract:
+                inputs["sequence_faces"] = self._sequence_faces_of_decode(inputs, extract, memory.device)
+            return inputs
+        if SC is not None:
+            inputs = self._forward_eval_constrained(inputs, eng, memory, mask, kv_len, T, SC)
             if extract:
                 inputs["sequence_faces"] = self._sequence_faces_of_decode(inputs, extract, memory.device)
             return inputs
@@ -150,6 +172,46 @@ class SurfaceFormer(SurfaceFormerBase):
                                    num_lines=inputs["input"].size(1), **kw)
         found.update(_ops.face_seq_votes(found, require_closed=enclosed))
         return found
+
+    def _sequence_constrain_value(self, inputs):
+        """sequence_constrain as None or its flag bits, after the rules only the model can check (ValueError, before anything is
+        launched): the native engine, what the record excludes, stop_each_eos."""
+        SC = _modes.sequence_constrain_flags(getattr(self, "sequence_constrain", None))
+        if SC is None:
+            return None
+        mode = _modes.SEQUENCE_CONSTRAIN
+        if not self.engine_supported():
+            raise ValueError("sequence_constrain needs the native engine: this model's constructor arguments take the sub-module loop")
+        if getattr(self, "sequence_samples", 0) or getattr(self, "sequence_beams", 0) or getattr(self, "return_logprob", False) or \
+                inputs.get("extra_mask") is not None:
+            raise ValueError("sequence_constrain excludes %s, %s, %s and %s" % mode.model_excludes)
+        if getattr(self, "stop_each_eos", False):
+            raise ValueError("sequence_constrain excludes stop_each_eos = True: every row is finished by its own EOS already")
+        return SC
+
+    def _forward_eval_constrained(self, inputs, eng, memory, mask, kv_len, T, SC):
+        """forward_eval with sequence_constrain (flag bits SC) behind the encoder.  The wireframes are decoded in batch order
+        (this model applies no permutation), so the follow table is taken as built or given."""
+        dev = memory.device
+        table = None
+        if SC & _L.FF_CONSTRAIN_CONNECT:
+            ni = inputs.get("num_input")
+            if ni is None:
+                ni = (~inputs["input_mask"].to(device=dev, dtype=torch.bool)).sum(dim=1)
+            ni = torch.as_tensor(ni).to(device=dev, dtype=torch.int32).reshape(-1)
+            table = self._follow_table(inputs, dev, ni, None)
+        out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
+                         chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
+                         chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1, flags=self.decode_flags,
+                         x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS,
+                         tok_eos=self.token.EOS, tok_sep=int(getattr(self.token, "SEP", 2)), sequence_constrain=SC, follow_table=table)
+        inputs["embedding"] = memory
+        inputs["predict"] = out["predict"]
+        inputs["predict_logprob"] = out["logprob"]
+        inputs["predict_dead_end"] = out["dead_end"]
+        inputs["predict_open_end"] = out["open_end"]
+        self.last_constrain_stats = {"steps": out["steps"], "slot_rows": out["slot_rows"]}
+        return inputs
 
     def _sequence_beams_value(self, inputs):
         """sequence_beams as 0 or W in 1..8, after the rules only the model can check (ValueError, before anything is launched):

@@ -1473,6 +1473,90 @@ int ff_face_seq_rows(const int64_t* tokens, int N, int G, int T, const int* num_
                      int* edges, int* loop_of, unsigned int* set_bits, double* score, int* dup_of, int* take, double* row_best,
                      ff_stream_t stream);
 
+/* ---- loop-constrained decode of the single-sequence model (opt-in, FF_SEQ2SEQ; entries added within ABI 105) --------
+ * The single-sequence reference decodes ONE greedy sequence per wireframe: select_next takes the argmax of the masked logit row
+ * (model.py:161-167) inside the loop of model.py:193-210, which starts every sequence from SOS (model.py:191).  These entries
+ * restate those call sites with ONE change: the row is masked by the face-loop rule of ff_pointer_constrained (one copy in device
+ * code), applied per FACE of the row.
+ *
+ * The rule.
+ * Definitions:
+ *   - ntok = token.len; edge e is token ntok + e; SEP = tok_sep, EOS = tok_eos.
+ *   - follows[w][a][b] is ff_follow_table's bit table, packed words [N, L, ceil(L/32)].
+ * Flag bits:
+ *   - FF_CONSTRAIN_NO_REPEAT (1) and FF_CONSTRAIN_CONNECT (2) are the existing ones.
+ *   - FF_CONSTRAIN_ONCE (4) is new.  Only these entries accept it, and only together with NO_REPEAT.
+ *   - Every other entry keeps refusing bit 4 as an unknown flag bit.
+ * Per-sequence state, a function of the row's prefix:
+ *   - visited (edge bitset), first, prev.
+ *   - Start (column 0 = SOS): empty, closed.
+ * Update when a token is appended:
+ *   - An edge e: ff_pointer_constrained's three steps (a one-edge loop closes on itself) and visited |= e.
+ *   - SEP: first = prev = none, and visited is cleared unless ONCE is set.
+ *   - EOS: the row is finished, ff_decode_sequence_sample's rule.  The finishing range is [EOS, EOS + 1), from the first
+ *     position >= 1.
+ *   - Any other special token: nothing.
+ *   - prev == none means "the current face has no edge yet".
+ * Keys masked for an unfinished row, on top of padding and kv_len:
+ *   - NO_REPEAT: every edge in visited.  That means the current face's edges, or under ONCE the edges of every face so far.
+ *   - CONNECT, loop open:
+ *     - Every special token is masked, and every edge b without follows[prev][b].
+ *     - If no edge key is left live after all masks, it is a dead end.  SEP alone is un-masked, the face is abandoned there,
+ *       dead_end[row, position] = 1, and the sequence goes on.
+ *     - A dead end ends the face, not the sequence.
+ *   - CONNECT, loop closed:
+ *     - Every special token is masked except SEP and EOS.
+ *     - SEP is masked as well while prev == none.  That rules out an empty face and the SEP SEP ... loop.
+ *     - Edges are limited only by NO_REPEAT.
+ *   - Without CONNECT, no special token is touched and no table is read.
+ * Selection: argmax of the constrained row, lowest index on ties.
+ * Log-probability:
+ *   - logprob = -log sum exp(l - l[tok]) over the constrained row (ff_pointer_argmax_lp's / ff_pointer_constrained's evaluation).
+ *   - A row with no live key gives token 0 and -log S.
+ *   - A finished row appends token 0 with log-probability 0.
+ * Stop: after the first step after which every row of the call is finished, else after T-1 steps.  This is
+ * ff_decode_sequence_sample's counter, "rows unfinished after the step".  Output is zero past min(own EOS, stop step).
+ * With all bits clear:
+ *   - Tokens, steps and step_counts equal the greedy decode run with FF_STOP_EACH_EOS and cut behind every row's first EOS.
+ *   - The log-probabilities equal ff_decode_lp's.
+ *
+ * ff_pointer_sequence_constrained: one step of B sequences; ff_pointer_constrained's arguments with tok_sep / tok_eos in place of
+ *   the terminator range.  Row b belongs to wireframe b / seqs_per_group.  first / prev: edge index, -1 = none (values outside
+ *   [0, L) read as none; a row whose first OR prev is none is CLOSED).  visited [B, ceil(L/32)] is updated IN PLACE: the selected
+ *   edge's bit is set, SEP clears the row's words unless ONCE.  dead_end is this step's flag; fin_out = finished before the step or
+ *   token == EOS.  count_unfinished (optional) += the rows unfinished after the step.
+ * ff_decode_sequence_constrained: memory / mask / kv_len as ff_decode; predict [N, T] int64; then ff_sequence_constrain_params:
+ *   flags; follows [N, L, ceil(L/32)] DEVICE (may be NULL when CONNECT is clear); tok_sep; logprob [N, T] fp32; dead_end [N, T]
+ *   int32 (1 at the position whose SEP was selected at a dead end); open_end [N] int32 (a loop is open after the last kept
+ *   position).  trace_logits (optional) [T-1, N, S] indexed by decoded sequence (seq_of_row [N]): the CONSTRAINED masked row of
+ *   every sequence unfinished before the step.  A micro-batch holds chunk_max_seqs wireframes, as the greedy decode's.
+ * FF_ERR_ARG before any launch for: FF_PARALLEL or F != 1, FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS, a
+ * stop_fn, unknown flag bits, ONCE without NO_REPEAT, CONNECT with a NULL table, tok_sep / tok_eos outside [0, ntok) or equal to
+ * each other, a NULL output.  ff_decode_sequence_constrained_workspace_bytes: the greedy decode's workspace plus
+ * ff_decode_constrained's records and state, taken last (0 for what the entry refuses).  Every other entry launches and lays out
+ * what it did before these. */
+#define FF_CONSTRAIN_ONCE 0x4   /* = 4, the next bit; written in hex: the one decimal define of value 4 stays ruled out for the FF_CONSTRAIN_ names */
+int ff_pointer_sequence_constrained(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                    int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok, int tok_sep,
+                                    int tok_eos, const int* fin_in, const int* first_in, const int* prev_in, unsigned int* visited,
+                                    unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out, int* dead_end,
+                                    int* first_out, int* prev_out, const float* memory, int E, float* next_rows, int ldnext,
+                                    float* next_stats, int* count_unfinished, ff_stream_t stream);
+typedef struct ff_sequence_constrain_params {
+  int flags;
+  const unsigned int* follows;
+  int tok_sep;
+  float* logprob;
+  int* dead_end;
+  int* open_end;
+} ff_sequence_constrain_params;
+size_t ff_decode_sequence_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p);
+int ff_decode_sequence_constrained(const ff_model* m, const ff_decode_params* p,
+                                   const float* memory, const unsigned char* mask, const int* kv_len,
+                                   int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
+                                   void* workspace, size_t workspace_bytes, const ff_sequence_constrain_params* constrain,
+                                   ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

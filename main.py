@@ -171,7 +171,7 @@ def score_batch(model, batch):
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
               constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None, sequence_beams=None,
-              sequence_device_faces=None):
+              sequence_device_faces=None, sequence_constrained=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -206,7 +206,10 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     read; label faces, the metrics and the JSON text are made here as before.
     sequence_device_faces (--sequence-device-faces, single-sequence model; this sample's slice of the model's
     inputs["sequence_faces"]): the same for that model -- the predicted faces come from these arrays
-    (faces.faces_of_seq_rows) instead of from pred, the draws and the beams, which are then not read."""
+    (faces.faces_of_seq_rows) instead of from pred, the draws and the beams, which are then not read.
+    sequence_constrained (--sequence-constrain, single-sequence model; the dead-end flags [T] of this sample's row): the record
+    also gets `pred_dead_ends`, the number of faces the constrained decode abandoned at a dead end (the sum of the row's flags),
+    and `pred_unclosed`, the number of parsed faces that do not pass the enclosure walk."""
     if sequence_device_faces is not None:
         return _record_of_sequence_device(cfg, raw, item, sequence_device_faces, logprob is not None, sequence_beams is not None,
                                           sequence_samples is not None)
@@ -295,6 +298,11 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["pred_sample_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
         rec["pred_sample_face_scores"] = [s for _, _, s, _ in ranked]
         rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
+    if sequence_constrained is not None:
+        own = FZ._seq_faces(pred, cfg.model.token, len(raw["edges"]), True)      # (before any post-processing: what the decode emitted)
+        rec["pred_dead_ends"] = int(np.asarray(sequence_constrained).astype(bool).sum())
+        rec["pred_unclosed"] = sum(1 for _, idx in own
+                                   if not FZ.is_face_enclosed(raw["edges"], idx, cfg.post_process.enclosedness_tol))
     if sequence_beams is not None:
         bf = FZ.parse_faces_beams_scored(sequence_beams[0], sequence_beams[1], sequence_beams[2], len(raw["edges"]), cfg.model.token)
         ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
@@ -377,7 +385,8 @@ def _record_of_sequence_device(cfg, raw, item, rows, scored, beams, samples):
 
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
-                    constrain_samples=0, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0, sequence_beam_stop="all"):
+                    constrain_samples=0, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0, sequence_beam_stop="all",
+                    sequence_constrain=None):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
@@ -388,7 +397,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     top_p / seed, the closure look-ahead of the constrained beam search (constrain_beam_closure "lookahead" /
     "exact"), `sequence_samples` draws per wireframe of the single-sequence model under temperature / top_k / top_p /
     seed, beam search with `sequence_beams` beams per wireframe of the single-sequence model under the stop rule
-    `sequence_beam_stop`.
+    `sequence_beam_stop`, the loop-constrained greedy decode of the single-sequence model (sequence_constrain
+    "no_repeat" / "loops" / "coedge_loops" with the end-point tolerance constrain_tol).
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -425,6 +435,10 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     if sequence_beams:
         model.sequence_beams = int(sequence_beams)
         model.sequence_beam_stop = str(sequence_beam_stop)
+    if sequence_constrain:
+        model.sequence_constrain = str(sequence_constrain)
+        if constrain_tol is not None:
+            model.constrain_tol = float(constrain_tol)
     return model
 
 
@@ -432,7 +446,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
              constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0,
-             sequence_beam_stop="all", sequence_device_faces=False):
+             sequence_beam_stop="all", sequence_device_faces=False, sequence_constrain=None):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -460,7 +474,21 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     sequence_device_faces (single-sequence model, single-rank runs only, not with device_faces or score_labels; alone or with
     scores, sequence_samples or sequence_beams): the predicted faces of every record are extracted on the device
     (model.sequence_faces: "enclosed" with the pairings as edge map for co-edge configs, "parse" otherwise) and the records are
-    made from those arrays -- the same records."""
+    made from those arrays -- the same records; sequence_constrain ("no_repeat" / "loops" / "coedge_loops", single-sequence model,
+    single-rank runs only, not with scores, score_labels, sample, beam, constrain, sequence_samples, sequence_beams, device_faces
+    or sequence_device_faces) decodes under the face-loop rule per face of the row with
+    cfg.post_process.enclosedness_tol as the end-point tolerance and adds pred_dead_ends / pred_unclosed."""
+    if sequence_constrain is not None:
+        if sequence_constrain not in ("no_repeat", "loops", "coedge_loops"):
+            raise ValueError("--sequence-constrain must be no_repeat, loops or coedge_loops")
+        if cfg.model_class != "SurfaceFormer":
+            raise ValueError("--sequence-constrain applies to SurfaceFormer only (SurfaceFormer_Parallel constrains per anchor with --constrain)")
+        if scores or score_labels or sample or beam or constrain or sequence_samples or sequence_beams or device_faces or \
+                sequence_device_faces:
+            raise ValueError("--sequence-constrain does not combine with --scores, --score-labels, --sample, --beam, --constrain, "
+                             "--sequence-samples, --sequence-beams, --device-faces or --sequence-device-faces")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--sequence-constrain is not implemented for multi-rank runs")
     if sequence_beams:
         if isinstance(sequence_beams, bool) or not isinstance(sequence_beams, int) or not 1 <= sequence_beams <= 8:
             raise ValueError("--sequence-beams must be a width in 1..8")
@@ -545,6 +573,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     configure_model(model, retire_finished, fp16, scores, beam, sample, temperature, top_k, top_p, seed, constrain,
                     cfg.post_process.enclosedness_tol if constrain else None, constrain_beams, constrain_lookahead, constrain_exact,
                     constrain_samples, constrain_beam_closure, sequence_samples, sequence_beams, sequence_beam_stop)
+    if sequence_constrain:
+        configure_model(model, sequence_constrain=sequence_constrain, constrain_tol=cfg.post_process.enclosedness_tol)
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
@@ -555,7 +585,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     out_dir = out_dir or os.path.join("logs", cfg.trainer.name, str(cfg.trainer.version), "json")
     parallel = cfg.model_class == "SurfaceFormer_Parallel"
     batch_size = max(1, int(batch_size))
-    if not parallel and batch_size > 1 and hasattr(model, "stop_each_eos"):
+    if not parallel and batch_size > 1 and hasattr(model, "stop_each_eos") and not sequence_constrain:      # (that decode's rule is per row already)
         model.stop_each_eos = True      # every wireframe decodes up to its own EOS (module docstring)
     rank = dist_mod.get_rank() if dist_mod is not None else 0
     world = dist_mod.get_world_size() if dist_mod is not None else 1
@@ -572,6 +602,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         wanted.append(("sequence_samples", ("predict_samples", "predict_sample_logprob")))
     if sequence_beams:
         wanted.append(("sequence_beams", ("predict_beams", "predict_beam_scores", "predict_beam_finished")))
+    if sequence_constrain:
+        wanted.append(("sequence_constrained", ("predict_dead_end",)))
     if device_faces:
         wanted.append(("device_faces", ("faces",)))
     if sequence_device_faces:
@@ -711,6 +743,14 @@ def build_parser():
                              "the decode (DESIGN.md 31) instead of row by row on the host; alone or with --scores, "
                              "--sequence-samples or --sequence-beams; the records are the same; single-process runs only, not with "
                              "--device-faces or --score-labels")
+    parser.add_argument("--sequence-constrain", choices=("no_repeat", "loops", "coedge_loops"), default=None,
+                        help="single-sequence model: the greedy decode under the face-loop rule applied per face of the row "
+                             "(DESIGN.md 32) -- no_repeat: never an edge the current face holds already; loops: also only an edge "
+                             "that starts where the last one ended while a loop is open, SEP only behind a closed non-empty loop "
+                             "(or alone at a dead end, where the face is abandoned) and EOS only with the loop closed; coedge_loops: "
+                             "also never a co-edge an earlier face of the row holds; every JSON record gains pred_dead_ends / "
+                             "pred_unclosed; single-process runs only, not with --scores, --score-labels, --sample, --beam, "
+                             "--constrain, --sequence-samples, --sequence-beams, --device-faces or --sequence-device-faces")
     parser.add_argument("--constrain-beam-closure", choices=("lookahead", "exact"), default=None,
                         help="with --constrain loops --constrain-beams W: the beam search forms every beam's row under the closure "
                              "look-ahead (lookahead) or its exact form (exact), so that the W beams are searched among loops that "
@@ -740,7 +780,7 @@ def main(argv=None):
              constrain_samples=args.constrain_samples, device_faces=args.device_faces,
              constrain_beam_closure=args.constrain_beam_closure, sequence_samples=args.sequence_samples,
              sequence_beams=args.sequence_beams, sequence_beam_stop=args.sequence_beam_stop,
-             sequence_device_faces=args.sequence_device_faces)
+             sequence_device_faces=args.sequence_device_faces, sequence_constrain=args.sequence_constrain)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
