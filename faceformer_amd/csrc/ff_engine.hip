@@ -390,6 +390,7 @@ struct Mode {
   const ff_constrain_beam_ahead_params* cbeam_ahead() const { return static_cast<const ff_constrain_beam_ahead_params*>(prm); }
   // (CONSTRAIN_BEAM and CONSTRAIN_BEAM_AHEAD: the parameters the two share)
   bool is_cbeam() const { return kind == CONSTRAIN_BEAM || kind == CONSTRAIN_BEAM_AHEAD; }
+  bool is_sequence() const { return kind == SEQ_SAMPLE || kind == SEQ_BEAM || kind == SEQ_CONSTRAIN; }   // (the ff_decode_sequence_* entries)
   ff_constrain_beam_params cbeam() const {
     if (kind != CONSTRAIN_BEAM_AHEAD) return *static_cast<const ff_constrain_beam_params*>(prm);
     const ff_constrain_beam_ahead_params* q = cbeam_ahead();
@@ -1349,7 +1350,7 @@ struct DecodeRun {
   // num_token of unfinished rows), for the sequence sample mode (rows unfinished after the step) and for the sequence beam mode
   // (non-empty beams, or rank-0 beams, unfinished after the step); cnt_eq and the cumulative EOS count otherwise.
   bool zero_rule() const {
-    return p->variant == FF_PARALLEL || mode.kind == Mode::SEQ_SAMPLE || mode.kind == Mode::SEQ_BEAM || mode.kind == Mode::SEQ_CONSTRAIN;
+    return p->variant == FF_PARALLEL || mode.is_sequence();
   }
   // the stop rule over the first n steps' counters, per_chunk = [n][nch]
   bool stop_rule(const int* per_chunk, int n) {
@@ -1614,11 +1615,49 @@ int check_lookahead(const char* name, int form, int flags, const unsigned char* 
   }
   return FF_OK;
 }
+// ... the width of a beam decode, and the staging area of its reorder: ff_beam_reorder stages a group's x0 (+ q|k|v) rows in
+// 64 KB of LDS ...
+int check_beam_width(const char* name, int width, const ff_model* m, const ff_decode_params* p) {
+  FF_CHECK_ARG(width >= 1 && width <= 8 && width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d", name, width,
+               p->L + m->num_token);
+  return FF_OK;
+}
+int check_beam_staging(const char* name, int width, const ff_model* m, const ff_decode_params* p) {
+  FF_CHECK_ARG((size_t)width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
+               "%s: width=%d at E=%d exceeds the reorder's staging area", name, width, m->E);
+  return FF_OK;
+}
 // ... and what they hand to the decode: no extra mask, no pointer_out, no best / second traces, no log-probabilities.
 DecodeIO opt_in_io(const float* memory, const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host,
                    int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row, ff_stream_t stream) {
   return DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
                   nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr};
+}
+
+
+// The three single-sequence entries (ff_decode_sequence_*; `params`: the parameter struct as the message words it, `sibling`:
+// the parallel variant's entry): what their size queries refuse, the checks in front of their own ...
+bool sequence_query_ok(const ff_decode_params* p) { return p && p->variant == FF_SEQ2SEQ && p->F == 1; }
+int check_sequence(const char* name, const char* params, const char* sibling, const ff_model* m, const ff_decode_params* p,
+                   const void* prm) {
+  FF_CHECK_ARG(m && p && prm, "%s: null model, params or %s params", name, params);
+  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1, "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has %s",
+               name, sibling);
+  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
+               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
+  return FF_OK;
+}
+// ... and the decode behind them: the terminator range is the EOS token alone (SEP and the other special tokens do not finish a
+// draw, a beam or a row), and no num_input is read.
+int run_sequence(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask, const int* kv_len,
+                 int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row, void* workspace,
+                 size_t workspace_bytes, ff_stream_t stream, const Mode& mode) {
+  ff_decode_params q = *p;
+  q.term_lo = p->tok_eos;
+  q.term_hi = p->tok_eos + 1;
+  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
+                                     stream),
+                    workspace, workspace_bytes, mode);
 }
 
 }  // namespace
@@ -1730,13 +1769,10 @@ extern "C" int ff_decode_beam(const ff_model* m, const ff_decode_params* p, cons
                               size_t workspace_bytes, const ff_beam_params* beam, ff_stream_t stream) {
   FF_CHECK_ARG(m && p && beam, "ff_decode_beam: null model, params or beam params");
   FF_RETURN_IF(check_opt_in("ff_decode_beam", "beams are", p, extra_mask));
-  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token,
-               "ff_decode_beam: width=%d outside 1..8 or above S=%d", beam->width, p->L + m->num_token);
+  FF_RETURN_IF(check_beam_width("ff_decode_beam", beam->width, m, p));
   FF_RETURN_IF(check_opt_in_outputs("ff_decode_beam", p, "beams and scores", beam->beams && beam->scores, trace_best, trace_second,
                                     pointer_out));
-  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
-  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
-               "ff_decode_beam: width=%d at E=%d exceeds the reorder's staging area", beam->width, m->E);
+  FF_RETURN_IF(check_beam_staging("ff_decode_beam", beam->width, m, p));
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::BEAM, beam->width, beam));
@@ -1792,7 +1828,7 @@ extern "C" int ff_decode_sample(const ff_model* m, const ff_decode_params* p, co
 }
 
 extern "C" size_t ff_decode_sequence_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples) {
-  if (num_samples < 1 || num_samples > 64 || !p || p->variant != FF_SEQ2SEQ || p->F != 1) return 0;
+  if (num_samples < 1 || num_samples > 64 || !sequence_query_ok(p)) return 0;
   return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_SAMPLE, num_samples));
 }
 
@@ -1801,11 +1837,7 @@ extern "C" int ff_decode_sequence_sample(const ff_model* m, const ff_decode_para
                                          int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sample_params* sample,
                                          ff_stream_t stream) {
   const char* name = "ff_decode_sequence_sample";
-  FF_CHECK_ARG(m && p && sample, "%s: null model, params or sample params", name);
-  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1, "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has ff_decode_sample",
-               name);
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
-               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
+  FF_RETURN_IF(check_sequence(name, "sample", "ff_decode_sample", m, p, sample));
   FF_CHECK_ARG(sample->num_samples >= 1 && sample->num_samples <= 64, "%s: num_samples=%d outside 1..64", name, sample->num_samples);
   FF_CHECK_ARG(sample->uniforms && sample->samples && sample->logprob && sample->scores && predict,
                "%s: uniforms, samples, logprob, scores and predict are required", name);
@@ -1813,17 +1845,12 @@ extern "C" int ff_decode_sequence_sample(const ff_model* m, const ff_decode_para
   const int rows = p->N * sample->num_samples;   // (the draw's own check, with the step's text: the uniforms of one step)
   FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{sample->uniforms, rows, nullptr, sample->temperature, sample->top_k,
                                                             sample->top_p}, rows));
-  // the terminator range is the EOS token alone: SEP and the other special tokens do not finish a draw
-  ff_decode_params q = *p;
-  q.term_lo = p->tok_eos;
-  q.term_hi = p->tok_eos + 1;
-  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
-                                     stream),
-                    workspace, workspace_bytes, Mode(Mode::SEQ_SAMPLE, sample->num_samples, sample));
+  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
+                      stream, Mode(Mode::SEQ_SAMPLE, sample->num_samples, sample));
 }
 
 extern "C" size_t ff_decode_sequence_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width) {
-  if (width < 1 || width > 8 || !p || p->variant != FF_SEQ2SEQ || p->F != 1) return 0;
+  if (width < 1 || width > 8 || !sequence_query_ok(p)) return 0;
   return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_BEAM, width));
 }
 
@@ -1832,30 +1859,18 @@ extern "C" int ff_decode_sequence_beam(const ff_model* m, const ff_decode_params
                                        int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_beam_params* beam,
                                        ff_stream_t stream) {
   const char* name = "ff_decode_sequence_beam";
-  FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
-  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1, "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has ff_decode_beam",
-               name);
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
-               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
-  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d", name,
-               beam->width, p->L + m->num_token);
+  FF_RETURN_IF(check_sequence(name, "beam", "ff_decode_beam", m, p, beam));
+  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
   FF_CHECK_ARG(beam->stop_best == 0 || beam->stop_best == 1, "%s: stop_best=%d must be 0 or 1", name, beam->stop_best);
   FF_CHECK_ARG(beam->beams && beam->scores && beam->finished && predict, "%s: beams, scores, finished and predict are required", name);
   FF_CHECK_ARG(p->N > 0 && (long long)p->N * beam->width < (1LL << 31), "%s: bad sizes", name);
-  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
-  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
-               "%s: width=%d at E=%d exceeds the reorder's staging area", name, beam->width, m->E);
-  // the terminator range is the EOS token alone: SEP and the other special tokens do not finish a beam
-  ff_decode_params q = *p;
-  q.term_lo = p->tok_eos;
-  q.term_hi = p->tok_eos + 1;
-  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
-                                     stream),
-                    workspace, workspace_bytes, Mode(Mode::SEQ_BEAM, beam->width, beam));
+  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
+  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
+                      stream, Mode(Mode::SEQ_BEAM, beam->width, beam));
 }
 
 extern "C" size_t ff_decode_sequence_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p) {
-  if (!p || p->variant != FF_SEQ2SEQ || p->F != 1) return 0;
+  if (!sequence_query_ok(p)) return 0;
   return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_CONSTRAIN, 1));
 }
 
@@ -1865,22 +1880,13 @@ extern "C" int ff_decode_sequence_constrained(const ff_model* m, const ff_decode
                                               int* seq_of_row, void* workspace, size_t workspace_bytes,
                                               const ff_sequence_constrain_params* constrain, ff_stream_t stream) {
   const char* name = "ff_decode_sequence_constrained";
-  FF_CHECK_ARG(m && p && constrain, "%s: null model, params or constrain params", name);
-  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1,
-               "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has ff_decode_constrained", name);
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
-               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
+  FF_RETURN_IF(check_sequence(name, "constrain", "ff_decode_constrained", m, p, constrain));
   FF_RETURN_IF(ff_sequence_rule_check(name, ff_loop_rule_io{constrain->follows, p->L, constrain->flags, m->num_token}, p->L + m->num_token,
                                       constrain->tok_sep, p->tok_eos));
   FF_CHECK_ARG(constrain->logprob && constrain->dead_end && constrain->open_end && predict,
                "%s: logprob, dead_end, open_end and predict are required", name);
-  // the finishing range is the EOS token alone: SEP and the other special tokens do not finish a row
-  ff_decode_params q = *p;
-  q.term_lo = p->tok_eos;
-  q.term_hi = p->tok_eos + 1;
-  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
-                                     stream),
-                    workspace, workspace_bytes, Mode(Mode::SEQ_CONSTRAIN, 1, constrain));
+  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
+                      stream, Mode(Mode::SEQ_CONSTRAIN, 1, constrain));
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
@@ -1962,14 +1968,11 @@ extern "C" int ff_decode_constrained_beam(const ff_model* m, const ff_decode_par
   const char* name = "ff_decode_constrained_beam";
   FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
   FF_RETURN_IF(check_opt_in(name, "the constrained beam decode is", p, extra_mask));
-  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d",
-               name, beam->width, p->L + m->num_token);
+  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
   FF_RETURN_IF(check_loop_rule(name, beam->flags, beam->follows, m, p));
   FF_RETURN_IF(check_opt_in_outputs(name, p, "beams, scores and dead_end", beam->beams && beam->scores && beam->dead_end, trace_best,
                                     trace_second, pointer_out));
-  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
-  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
-               "%s: width=%d at E=%d exceeds the reorder's staging area", name, beam->width, m->E);
+  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM, beam->width, beam));
@@ -1991,16 +1994,13 @@ extern "C" int ff_decode_constrained_beam_ahead(const ff_model* m, const ff_deco
   const char* name = "ff_decode_constrained_beam_ahead";
   FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
   FF_RETURN_IF(check_opt_in(name, "the constrained beam decode with look-ahead is", p, extra_mask));
-  FF_CHECK_ARG(beam->width >= 1 && beam->width <= 8 && beam->width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d",
-               name, beam->width, p->L + m->num_token);
+  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
   FF_RETURN_IF(check_loop_rule(name, beam->flags, beam->follows, m, p));
   FF_CHECK_ARG(beam->lookahead == 1 || beam->lookahead == 2, "%s: lookahead=%d must be 1 (look-ahead) or 2 (exact)", name, beam->lookahead);
   FF_RETURN_IF(check_lookahead(name, beam->lookahead, beam->flags, beam->close_dist, beam->cycle_len, m, p));
   FF_RETURN_IF(check_opt_in_outputs(name, p, "beams, scores and dead_end", beam->beams && beam->scores && beam->dead_end, trace_best,
                                     trace_second, pointer_out));
-  // ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
-  FF_CHECK_ARG((size_t)beam->width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
-               "%s: width=%d at E=%d exceeds the reorder's staging area", name, beam->width, m->E);
+  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
   return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
                                     seq_of_row, stream),
                     workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM_AHEAD, beam->width, beam));

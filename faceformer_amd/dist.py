@@ -219,12 +219,9 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
         raise ValueError("decode_sharded does not implement constrain_exact (%s)" % _modes.SWITCH["constrain"].sharded)
     if getattr(model, "constrain_beam_closure", None) is not None:
         raise ValueError("decode_sharded does not implement constrain_beam_closure (%s)" % _modes.SWITCH["constrain"].sharded)
-    if getattr(model, "sequence_samples", 0):
-        raise ValueError("decode_sharded does not implement sequence_samples (%s)" % _modes.SEQUENCE_SAMPLE.switches[0].sharded)
-    if getattr(model, "sequence_beams", 0):
-        raise ValueError("decode_sharded does not implement sequence_beams (%s)" % _modes.SEQUENCE_BEAM.switches[0].sharded)
-    if getattr(model, "sequence_constrain", None) is not None:
-        raise ValueError("decode_sharded does not implement sequence_constrain (%s)" % _modes.SEQUENCE_CONSTRAIN.switches[0].sharded)
+    for mode in _modes.SEQUENCE_MODES:
+        if mode.switches[0].on(model):
+            raise ValueError("decode_sharded does not implement %s (%s)" % (mode.subject, mode.switches[0].sharded))
     if getattr(model, "constrain_samples", 0):
         raise ValueError("decode_sharded does not implement constrain_samples (%s)" % _modes.SWITCH["constrain"].sharded)
     for mode in reversed(_modes.MODES):

@@ -475,42 +475,19 @@ class PathEngine:
         a dead end) and `open_end` [N] int32 (a loop is open after the last kept position); with trace=True `logits` [T-1, N, S]
         holds the constrained masked rows.  No term_range.  Excludes every other mode and option above, and stop_each_eos.  Bits
         0 equal the greedy FF_STOP_EACH_EOS decode cut behind every row's first EOS, with logprob=True's log-probabilities."""
-        SC = _modes.sequence_constrain_flags(sequence_constrain)
-        if SC is not None:
-            if tok_sep is None:
-                raise ValueError("sequence_constrain needs tok_sep, the token that ends a face")
-            o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
-                     logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
-                     constrain=constrain is not None, sequence_samples=int(sequence_samples or 0),
-                     sequence_beams=int(sequence_beams or 0), sequence_constrain=SC, follow_table=follow_table, tok_sep=int(tok_sep),
-                     trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
-            if not (0 <= int(tok_sep) < self.num_token and 0 <= int(tok_eos) < self.num_token) or int(tok_sep) == int(tok_eos):
-                raise ValueError("sequence_constrain: tok_sep=%d and tok_eos=%d must be two different special tokens (below %d)"
-                                 % (int(tok_sep), int(tok_eos), self.num_token))
-            return self._decode_sequence(_modes.SEQUENCE_CONSTRAIN, "the parallel variant constrains with constrain", memory, mask_u8,
-                                         kv_len, variant, o, (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes,
-                                                              chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows, flags,
-                                                              x3_min_rows), sync_every, tok_sos, tok_eos)
-        SB = _modes.sequence_beams_value(sequence_beams)
-        if SB:
-            o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
-                     logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
-                     constrain=constrain is not None, sequence_samples=sequence_samples, sequence_beams=SB,
-                     sequence_beam_stop=sequence_beam_stop, trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
-            return self._decode_sequence(_modes.SEQUENCE_BEAM, "the parallel variant searches with beam_width", memory, mask_u8, kv_len,
-                                         variant, o, (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs,
-                                                      num_streams, chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows),
-                                         sync_every, tok_sos, tok_eos)
-        SR = _modes.sequence_samples_value(sequence_samples)
-        if SR:
-            o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
-                     logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
-                     constrain=constrain is not None, sequence_samples=SR, temperature=temperature, top_k=top_k, top_p=top_p,
-                     uniforms=uniforms, trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
-            return self._decode_sequence(_modes.SEQUENCE_SAMPLE, "the parallel variant draws with num_samples", memory, mask_u8, kv_len,
-                                         variant, o, (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs,
-                                                      num_streams, chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows),
-                                         sync_every, tok_sos, tok_eos)
+        seq = dict(sequence_samples=sequence_samples, sequence_beams=sequence_beams, sequence_constrain=sequence_constrain)
+        for mode in reversed(_modes.SEQUENCE_MODES):      # (of several set together, the last one's record reports)
+            value = mode.sequence.value(seq[mode.subject])
+            if value != mode.switches[0].off:
+                o = dict(seq, retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback,
+                         extra_mask=extra_mask, logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
+                         constrain=constrain is not None, temperature=temperature, top_k=top_k, top_p=top_p, uniforms=uniforms,
+                         sequence_beam_stop=sequence_beam_stop, follow_table=follow_table, tok_sep=tok_sep, tok_eos=tok_eos,
+                         trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
+                o[mode.subject] = value
+                return self._decode_sequence(mode, memory, mask_u8, kv_len, variant, o,
+                                             (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs, num_streams,
+                                              chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows), sync_every, tok_sos)
         W, R, CF = int(beam_width or 0), int(num_samples or 0), constrain_flags(constrain)
         CB = _modes.constrain_beams_value(constrain_beams, CF)
         LA = _modes.constrain_lookahead_value(constrain_lookahead, CF, CB)
@@ -518,7 +495,6 @@ class PathEngine:
         CS = _modes.constrain_samples_value(constrain_samples, CF, CB)
         CL = _modes.constrain_beam_closure_value(constrain_beam_closure, CF, CB, LA, EX, CS)
         mode, value = _modes.of_options(logprob, CB, LA, EX, CS, CL, constrain=CF, num_samples=R, beam_width=W)   # (value None: the greedy record)
-        G = value if mode.per_anchor else 1       # sequences per anchor
         o = dict(retire=retire, return_pointer=return_pointer, no_stop=no_stop, stop_callback=stop_callback, extra_mask=extra_mask,
                  logprob=logprob, beam_width=W, num_samples=R, constrain=CF, constrain_beams=CB, constrain_samples=CS, temperature=temperature, top_k=top_k, top_p=top_p,
                  uniforms=uniforms, follow_table=follow_table, constrain_lookahead=LA, constrain_exact=EX, constrain_beam_closure=CL, close_dist=close_dist, cycle_len=cycle_len, num_input=num_input, staged_num_input=staged_num_input, trace=trace,
@@ -544,9 +520,7 @@ class PathEngine:
             prm.term_lo, prm.term_hi = int(term_range[0]), int(term_range[1])
         if retire:
             prm.retire_min_shrink = float(retire_min_shrink)
-        B = N * F
         dev = self.device
-        predict = torch.empty((B, T), device=dev, dtype=torch.int64)
         ni = ni_host = None
         if staged_num_input is not None:
             ni_host, ni, vals = staged_num_input
@@ -562,19 +536,7 @@ class PathEngine:
             _dev(extra_mask, "extra_mask", torch.uint8)
             self._same_device(extra_mask, "extra_mask")
             extra_mask = extra_mask.contiguous()
-        steps_max = max(T - 1, 1)
-        pointer = torch.zeros((steps_max, B, E), device=dev, dtype=torch.float32) if return_pointer else None
-        traced = {}   # the traces, which the C side indexes by decoded sequence
-        if trace:
-            traced["logits"] = torch.full((steps_max, B * G, S), float("nan"), device=dev, dtype=torch.float32)
-            for key in mode.row_traces:
-                traced[key] = torch.full((steps_max, B), float("nan"), device=dev, dtype=torch.float32)
-        rows = torch.empty(B * G, device=dev, dtype=torch.int32)
-        # the mode's outputs, and the arguments only its entry takes (its parameter struct, or the log-probability output)
-        extra, tail = _modes.outputs(mode, self, o, B, traced)
-        nbytes = getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm), ni_host,
-                                                                      *((G,) if mode.per_anchor else ()))
-        ws = self._workspace(nbytes)
+        pointer = torch.zeros((max(T - 1, 1), N * F, E), device=dev, dtype=torch.float32) if return_pointer else None
         cb_error, cb = [], None
         if stop_callback is not None and not no_stop:
             # external stop rule (sharded decodes): `stop_callback(counts)` gets this call's per-step counters of the steps a
@@ -587,24 +549,46 @@ class PathEngine:
                     return 1
             cb = _L.STOP_FN(_stop)
             prm.stop_fn = C.cast(cb, C.c_void_p)
+        out = self._launch(mode, o, prm, N * F, S, (ni_host,), pointer, lambda predict, steps, counts, traced, rows: (
+            _p(memory), _p(mask_u8), _p(kv_len), _p(ni), ni_host, _p(extra_mask), _p(predict), C.byref(steps), counts, _p(pointer),
+            _p(traced.get("logits")), _p(traced.get("best")), _p(traced.get("second")), _p(rows)))
+        if cb_error:
+            raise cb_error[0]
+        return out
+
+    def _launch(self, mode, o, prm, B, S, size_args, pointer, args):
+        """The one call of `mode`'s entry for B rows of `predict` and what surrounds it, for decode() and _decode_sequence: the
+        traces, the mode's outputs, the workspace (size_args: what the size query takes behind the parameters), the host counters;
+        args(predict, steps, counts, traced, rows) -> the entry's arguments between the parameters and the workspace.  Returns
+        decode()'s dict."""
+        T, dev = o["T"], self.device
+        G = o[mode.subject] if mode.per_anchor else 1       # sequences per anchor (per wireframe of a single-sequence mode)
+        steps_max = max(T - 1, 1)
+        predict = torch.empty((B, T), device=dev, dtype=torch.int64)
+        traced = {}   # the traces, which the C side indexes by decoded sequence
+        if o["trace"]:
+            traced["logits"] = torch.full((steps_max, B * G, S), float("nan"), device=dev, dtype=torch.float32)
+            for key in mode.row_traces:
+                traced[key] = torch.full((steps_max, B), float("nan"), device=dev, dtype=torch.float32)
+        rows = torch.empty(B * G, device=dev, dtype=torch.int32)
+        # the mode's outputs, and the arguments only its entry takes (its parameter struct, or the log-probability output)
+        extra, tail = _modes.outputs(mode, self, o, B, traced)
+        ws = self._workspace(getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm), *size_args,
+                                                                                 *((G,) if mode.per_anchor else ())))
         steps = C.c_int(0)
         counts = (C.c_int * steps_max)()
         slots = (C.c_int * steps_max)()
         prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
-        args = (C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len), _p(ni), ni_host,
-                _p(extra_mask), _p(predict), C.byref(steps), counts, _p(pointer), _p(traced.get("logits")),
-                _p(traced.get("best")), _p(traced.get("second")), _p(rows), _p(ws), ws.numel())
         with torch.cuda.device(dev):
-            _L.check(getattr(self._lib, mode.entry)(*args, *tail, _stream()), mode.entry)
-        if cb_error:
-            raise cb_error[0]
+            _L.check(getattr(self._lib, mode.entry)(C.byref(self.model), C.byref(prm), *args(predict, steps, counts, traced, rows),
+                                                    _p(ws), ws.numel(), *tail, _stream()), mode.entry)
         sps = [int(v) for v in slots]
         out = {"predict": predict, "steps": steps.value, "step_counts": list(counts)[: steps.value],
                "seq_of_row": rows, "slots_per_step": sps, "slot_rows": sum((s + 1) * v for s, v in enumerate(sps))}
-        if return_pointer:
+        if pointer is not None:
             out["pointer"] = pointer[: steps.value]
         out.update(extra)
-        if trace:
+        if o["trace"]:
             # the C side indexes its traces by DECODED sequence (padding-anchor rows share one); expand to
             # one entry per row of `predict` (per output row of a beam / sampled decode)
             idx = rows.long()
@@ -612,47 +596,26 @@ class PathEngine:
             out.update((key, t[:, idx]) for key, t in traced.items())
         return out
 
-    def _decode_sequence(self, mode, parallel_has, memory, mask_u8, kv_len, variant, o, params, sync_every, tok_sos, tok_eos):
-        """decode(sequence_samples=R), decode(sequence_beams=W) and decode(sequence_constrain=...), `mode` their record: the checks
-        (ValueError before anything is launched), the outputs and the one call of ff_decode_sequence_sample /
-        ff_decode_sequence_beam / ff_decode_sequence_constrained, whose argument list has no
-        num_input, extra mask, pointer or best / second traces.  params: _params' arguments."""
+    def _decode_sequence(self, mode, memory, mask_u8, kv_len, variant, o, params, sync_every, tok_sos):
+        """decode() with one of SEQUENCE_MODES on, `mode` its record: the checks (ValueError before anything is launched) and
+        the call of its entry, whose argument list has no num_input, extra mask, pointer or best / second traces.  params:
+        _params' arguments."""
+        if mode.sequence.early:
+            mode.sequence.early(self, o)
         if variant != _L.FF_SEQ2SEQ or o["F"] != 1:
-            raise ValueError("%s is a single-sequence option (FF_SEQ2SEQ, F = 1); %s" % (mode.subject, parallel_has))
+            raise ValueError("%s is a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant %s with %s"
+                             % ((mode.subject,) + mode.sequence.parallel_has))
         _modes.check_options(mode, variant, o, None)
         if params[-2] & _L.FF_STOP_EACH_EOS:
             raise ValueError("%s excludes stop_each_eos (FF_STOP_EACH_EOS): every %s is finished by its own EOS already"
-                             % (mode.subject, {"sequence_samples": "draw", "sequence_beams": "beam"}.get(mode.subject, "row")))
+                             % (mode.subject, mode.sequence.each))
         mode.operand(self, o)
         prm = self._params(*params)
         _dev(memory, "memory")
         self._same_device(memory, "memory"), self._same_device(mask_u8, "mask"), self._same_device(kv_len, "kv_len")
-        N, S, E = memory.shape
-        T, R, dev = o["T"], (o[mode.subject] if mode.per_anchor else 1), self.device      # (R: the sequences per wireframe)
-        prm.sync_every, prm.tok_sos, prm.tok_eos = sync_every, tok_sos, tok_eos
-        predict = torch.empty((N, T), device=dev, dtype=torch.int64)
-        steps_max = max(T - 1, 1)
-        traced = {"logits": torch.full((steps_max, N * R, S), float("nan"), device=dev, dtype=torch.float32)} if o["trace"] else {}
-        rows = torch.empty(N * R, device=dev, dtype=torch.int32)
-        extra, tail = _modes.outputs(mode, self, o, N, traced)
-        ws = self._workspace(getattr(self._lib, mode.entry + "_workspace_bytes")(C.byref(self.model), C.byref(prm), *((R,) if mode.per_anchor else ())))
-        steps = C.c_int(0)
-        counts = (C.c_int * steps_max)()
-        slots = (C.c_int * steps_max)()
-        prm.slots_per_step = C.cast(slots, C.POINTER(C.c_int))
-        with torch.cuda.device(dev):
-            _L.check(getattr(self._lib, mode.entry)(C.byref(self.model), C.byref(prm), _p(memory), _p(mask_u8), _p(kv_len),
-                                                    _p(predict), C.byref(steps), counts, _p(traced.get("logits")), _p(rows),
-                                                    _p(ws), ws.numel(), *tail, _stream()), mode.entry)
-        sps = [int(v) for v in slots]
-        out = {"predict": predict, "steps": steps.value, "step_counts": list(counts)[: steps.value], "seq_of_row": rows,
-               "slots_per_step": sps, "slot_rows": sum((s + 1) * v for s, v in enumerate(sps))}
-        out.update(extra)
-        if o["trace"]:
-            idx = rows.long()
-            out["decoded_seqs"] = int(idx.max().item()) + 1
-            out.update((key, t[:, idx]) for key, t in traced.items())
-        return out
+        prm.sync_every, prm.tok_sos, prm.tok_eos = sync_every, tok_sos, o["tok_eos"]
+        return self._launch(mode, o, prm, o["N"], o["S"], (), None, lambda predict, steps, counts, traced, rows: (
+            _p(memory), _p(mask_u8), _p(kv_len), _p(predict), C.byref(steps), counts, _p(traced.get("logits")), _p(rows)))
 
     def _params(self, variant, N, S, F, T, chunk_wireframes, chunk_seqs, num_streams, chunk_max_seqs, ln_fuse_max_rows, flags,
                 x3_min_rows):

@@ -37,10 +37,20 @@ class Switch(collections.namedtuple("Switch", "attr off sharded seq2seq scored")
 # switches       the model attributes: [0] switches the mode on (greedy: its two options)
 # model_excludes the model-level exclusions in the words of that text;  model_checked: forward_eval runs check_options itself
 # prepare        (model, value, inputs, device, T, N, F, num_input, order) -> the keyword arguments of decode()
+# sequence       a single-sequence mode's companion record (SEQUENCE_MODES below); None for every other mode
 Mode = collections.namedtuple(
     "Mode", "subject excludes entry term_range parallel_only per_anchor row_traces values values_first operand own outs tail "
-            "switches model_excludes model_checked prepare",
-    defaults=(True, True, False, (), lambda *a: None, False, lambda *a: None, (), (), lambda *a: (), (), (), False, lambda *a: {}))
+            "switches model_excludes model_checked prepare sequence",
+    defaults=(True, True, False, (), lambda *a: None, False, lambda *a: None, (), (), lambda *a: (), (), (), False, lambda *a: {}, None))
+
+# What only a single-sequence mode has:
+# value          the option's value check: the decode() argument / model attribute -> the value, or the switch's `off` value
+# parallel_has   (verb, option): "the parallel variant <verb> with <option>", "SurfaceFormer_Parallel <verb> per anchor with <option>"
+# model_has      the words of "is a SurfaceFormer option (...)";  each: what its own EOS finishes (the noun of the stop_each_eos text)
+# early          (engine, o): decode()'s check in front of the variant check (None: none)
+# model_values   (model, value, inputs): the value checks only the model can make, behind the native-engine check and the exclusions
+# stats          the model attribute that receives steps and slot_rows
+Sequence = collections.namedtuple("Sequence", "value parallel_has model_has each model_values stats early", defaults=(None,))
 
 
 def check_options(mode, variant, o, term_range):
@@ -303,29 +313,28 @@ def _forced_values(o):
 
 
 # ---- the outputs -----------------------------------------------------------------------------------------------------------------
-def _beam_tail(o, ptrs, traced):
+def _beam_parent(o, traced):
+    """The address of a beam decode's int32 trace `beam_parent` [T-1, rows], made beside `logits` with trace=True (else None)."""
     if o["trace"]:
         logits = traced["logits"]
         traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
-    return (C.byref(_L.BeamParams(o["beam_width"], *ptrs, _p(traced.get("beam_parent")))),)
+    return _p(traced.get("beam_parent"))
+
+
+def _beam_tail(o, ptrs, traced):
+    return (C.byref(_L.BeamParams(o["beam_width"], *ptrs, _beam_parent(o, traced))),)
 
 
 def _constrain_beam_tail(o, ptrs, traced):
-    if o["trace"]:
-        logits = traced["logits"]
-        traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
     return (C.byref(_L.ConstrainBeamParams(o["constrain_beams"], o["constrain"], _p(o["follow_table"]), *ptrs,
-                                           _p(traced.get("beam_parent")))),)
+                                           _beam_parent(o, traced))),)
 
 
 def _constrain_beam_ahead_tail(o, ptrs, traced):
-    if o["trace"]:
-        logits = traced["logits"]
-        traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
     form = BEAM_CLOSURES[o["constrain_beam_closure"]]
     return (C.byref(_L.ConstrainBeamAheadParams(o["constrain_beams"], o["constrain"], _p(o["follow_table"]), form,
                                                 _p(o["close_dist"]) if form == 1 else None, _p(o["cycle_len"]), *ptrs,
-                                                _p(traced.get("beam_parent")))),)
+                                                _beam_parent(o, traced))),)
 
 
 def outputs(mode, eng, o, B, traced):
@@ -474,6 +483,15 @@ FORCED = Mode(
     tail=lambda o, ptrs, traced: (C.byref(_L.ForcedParams(_p(o["paths"]), _p(o["lengths_dev"]),
                                                           C.cast(o["lengths_host"], C.POINTER(C.c_int)), *ptrs)),))
 
+# ---- the single-sequence modes (SEQUENCE_MODES) -------------------------------------------------------------------------------------
+# The single-sequence model's sampling (R draws per WIREFRAME), beam search (30: W beams per WIREFRAME) and loop
+# constraint (32: the face-loop rule per face of the row -- SEP ends a face, a dead end re-opens SEP alone), every sequence from
+# SOS and finished by EOS alone.  The three records lie outside MODES, in a table of their own: num_samples, beam_width and
+# constrain on that model stay the recorded rejections they are (SWITCH and every recorded text stay), and the options are read
+# where the single-sequence model decodes (SurfaceFormer.forward_eval) and refused everywhere else, by loops over SEQUENCE_MODES.
+# The terminator range is the entries' own ([tok_eos, tok_eos + 1)): no term_range.  The entries share an argument list of their
+# own, shorter than ff_decode's (PathEngine._decode_sequence); one sequence per wireframe under the constraint, so that size
+# query takes no count.
 def _sequence_sample_values(o):
     R = o["sequence_samples"]
     if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= SAMPLE_MAX:
@@ -493,10 +511,15 @@ def sequence_samples_value(sequence_samples):
     return int(sequence_samples)
 
 
-# The single-sequence model's sampling: R draws per WIREFRAME, every one from SOS, finished by EOS alone.  Outside
-# MODES: num_samples on that model stays the recorded rejection it is (SWITCH and every recorded text stay), and the option is
-# read where the single-sequence model decodes (SurfaceFormer.forward_eval) and refused everywhere else.  The terminator range is
-# the entry's own ([tok_eos, tok_eos + 1)): no term_range.  The entry has its own, shorter argument list (PathEngine.decode).
+def _sequence_sample_model_values(m, R, inputs):
+    check_options(SEQUENCE_SAMPLE, _L.FF_SEQ2SEQ, dict(sequence_samples=R, temperature=m.sample_temperature, top_k=m.sample_top_k,
+                                                      top_p=m.sample_top_p), None)
+    u = inputs.get("sample_uniforms")
+    shape = (max(m.num_labels - 1, 1), inputs["input"].size(0) * R)
+    if u is not None and tuple(torch.as_tensor(u).shape) != shape:
+        raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
+
+
 SEQUENCE_SAMPLE = Mode(
     subject="sequence_samples", excludes=_COMMON + ("beam_width", "num_samples", "constrain"), entry="ff_decode_sequence_sample",
     term_range=False, parallel_only=False, per_anchor=True, values=_sequence_sample_values, values_first=True,
@@ -504,7 +527,13 @@ SEQUENCE_SAMPLE = Mode(
     tail=lambda o, ptrs, traced: (C.byref(_L.SampleParams(o["sequence_samples"], float(o["temperature"]), int(o["top_k"]),
                                                           float(o["top_p"]), _p(o["uniforms"]), *ptrs)),),
     switches=(Switch("sequence_samples", 0, _NO_STOP_RULE % "sequence-sampled", None, False),),
-    model_excludes=("return_logprob", "an extra mask"))
+    model_excludes=("return_logprob", "an extra mask"),
+    # (the wireframes are decoded in batch order: column w*R + k of the uniforms is draw k of wireframe w as given)
+    prepare=lambda m, R, inputs, dev, T, N, F, ni, order: dict(
+        sequence_samples=R, temperature=float(m.sample_temperature), top_k=int(m.sample_top_k), top_p=float(m.sample_top_p),
+        uniforms=m._sample_uniforms(inputs, dev, T, N, F, R, order)),
+    sequence=Sequence(sequence_samples_value, ("draws", "num_samples"), "draws per wireframe of the single-sequence model", "draw",
+                      _sequence_sample_model_values, "last_sample_stats"))
 
 SEQUENCE_BEAM_STOPS = {"all": 0, "best": 1}      # sequence_beam_stop -> stop_best of the C entries
 
@@ -533,23 +562,21 @@ def sequence_beam_stop_value(stop):
 
 
 def _sequence_beam_tail(o, ptrs, traced):
-    if o["trace"]:
-        logits = traced["logits"]
-        traced["beam_parent"] = torch.full(logits.shape[:2], -1, device=logits.device, dtype=torch.int32)
     return (C.byref(_L.SequenceBeamParams(o["sequence_beams"], sequence_beam_stop_value(o["sequence_beam_stop"]), *ptrs,
-                                          _p(traced.get("beam_parent")))),)
+                                          _beam_parent(o, traced))),)
 
 
-# The single-sequence model's beam search: W beams per WIREFRAME, every one from SOS, finished by EOS alone.  Outside
-# MODES, as SEQUENCE_SAMPLE is: beam_width on that model stays the recorded rejection it is (SWITCH and every recorded text stay),
-# and the option is read where the single-sequence model decodes (SurfaceFormer.forward_eval) and refused everywhere else.  The
-# terminator range is the entry's own ([tok_eos, tok_eos + 1)): no term_range.  The entry has SEQUENCE_SAMPLE's argument list.
 SEQUENCE_BEAM = Mode(
     subject="sequence_beams", excludes=_COMMON + ("beam_width", "num_samples", "constrain", "sequence_samples"),
     entry="ff_decode_sequence_beam", term_range=False, parallel_only=False, per_anchor=True, values=_sequence_beam_values,
     values_first=True, outs=(("beams", "GT", _I64), ("beam_scores", "G", _F32), ("beam_finished", "G", _I32)),
     tail=_sequence_beam_tail, switches=(Switch("sequence_beams", 0, _NO_STOP_RULE % "sequence-beam", None, False),),
-    model_excludes=("sequence_samples", "beam_width", "return_logprob", "an extra mask"))
+    model_excludes=("sequence_samples", "beam_width", "return_logprob", "an extra mask"),
+    prepare=lambda m, W, inputs, dev, T, N, F, ni, order: dict(sequence_beams=W, sequence_beam_stop=m.sequence_beam_stop),
+    sequence=Sequence(sequence_beams_value, ("searches", "beam_width"), "beams per wireframe of the single-sequence model", "beam",
+                      lambda m, W, inputs: check_options(
+                          SEQUENCE_BEAM, _L.FF_SEQ2SEQ, dict(sequence_beams=W, sequence_beam_stop=getattr(m, "sequence_beam_stop", "all"),
+                                                             S=inputs["input"].size(1) + m.num_token), None), "last_beam_stats"))
 
 SEQUENCE_CONSTRAIN_MODES = {"no_repeat": _L.FF_CONSTRAIN_NO_REPEAT, "loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT,
                             "coedge_loops": _L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT | _L.FF_CONSTRAIN_ONCE}
@@ -578,11 +605,20 @@ def _sequence_constrain_values(o):
         raise ValueError("sequence_constrain with FF_CONSTRAIN_CONNECT ('loops', 'coedge_loops') needs follow_table (ops.follow_table)")
 
 
-# The single-sequence model's loop constraint: the greedy decode under the face-loop rule applied per face of the
-# row -- SEP ends a face, EOS alone the row, a dead end re-opens SEP alone.  Outside MODES, as SEQUENCE_SAMPLE is: constrain on that
-# model stays the recorded rejection it is (SWITCH and every recorded text stay), and the option is read where the single-sequence
-# model decodes (SurfaceFormer.forward_eval) and refused everywhere else.  No term_range: the rule has tok_sep and tok_eos.  The
-# entry has SEQUENCE_SAMPLE's argument list; one sequence per wireframe, so its size query takes no count.
+def _sequence_constrain_early(eng, o):
+    sep, eos = o["tok_sep"], int(o["tok_eos"])
+    if sep is None:
+        raise ValueError("sequence_constrain needs tok_sep, the token that ends a face")
+    if not (0 <= int(sep) < eng.num_token and 0 <= eos < eng.num_token) or int(sep) == eos:
+        raise ValueError("sequence_constrain: tok_sep=%d and tok_eos=%d must be two different special tokens (below %d)"
+                         % (int(sep), eos, eng.num_token))
+
+
+def _sequence_constrain_model_values(m, SC, inputs):
+    if getattr(m, "stop_each_eos", False):
+        raise ValueError("sequence_constrain excludes stop_each_eos = True: every row is finished by its own EOS already")
+
+
 SEQUENCE_CONSTRAIN = Mode(
     subject="sequence_constrain", excludes=_COMMON + ("beam_width", "num_samples", "constrain", "sequence_samples", "sequence_beams"),
     entry="ff_decode_sequence_constrained", term_range=False, parallel_only=False, values=_sequence_constrain_values,
@@ -591,9 +627,20 @@ SEQUENCE_CONSTRAIN = Mode(
     tail=lambda o, ptrs, traced: (C.byref(_L.SequenceConstrainParams(o["sequence_constrain"], _p(o["follow_table"]), int(o["tok_sep"]),
                                                                      *ptrs)),),
     switches=(Switch("sequence_constrain", None, _NO_STOP_RULE % "sequence-constrained", None, False),),
-    model_excludes=("sequence_samples", "sequence_beams", "return_logprob", "an extra mask"))
+    model_excludes=("sequence_samples", "sequence_beams", "return_logprob", "an extra mask"),
+    # (batch order again: the follow table is taken as built or given; without CONNECT nothing reads one)
+    prepare=lambda m, SC, inputs, dev, T, N, F, ni, order: dict(
+        sequence_constrain=SC, tok_sep=int(getattr(m.token, "SEP", 2)),
+        follow_table=m._follow_table(inputs, dev, m._edge_counts(inputs, dev), None) if SC & _L.FF_CONSTRAIN_CONNECT else None),
+    sequence=Sequence(sequence_constrain_flags, ("constrains", "constrain"), "the loop rule per face of the single-sequence model's row",
+                      "row", _sequence_constrain_model_values, "last_constrain_stats", _sequence_constrain_early))
 
-MODES = (CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several mode options, the first one's record reports
+# in the order the refusals name them; of several set together, decode() lets the last one's record report, SurfaceFormer the
+# first of SEQUENCE_MODEL_ORDER that is on (a record excludes every record before it in SEQUENCE_MODES, by its option's name)
+SEQUENCE_MODES = (SEQUENCE_SAMPLE, SEQUENCE_BEAM, SEQUENCE_CONSTRAIN)
+SEQUENCE_MODEL_ORDER = (SEQUENCE_BEAM, SEQUENCE_SAMPLE, SEQUENCE_CONSTRAIN)
+
+MODES =(CONSTRAIN, SAMPLE, BEAM, GREEDY)      # in precedence order: of several mode options, the first one's record reports
 SWITCH = {sw.attr: sw for mode in MODES for sw in mode.switches}
 
 

@@ -381,21 +381,34 @@ class SurfaceFormerBase(nn.Module):
             bits = bits.index_select(0, torch.tensor(order, device=device))
         return bits.contiguous()
 
+    def _sample_uniforms(self, inputs, device, T, N, F, R, order):
+        """The uniforms [T-1, N*F*R] of a sampled decode in the DECODE's wireframe order: made (or given) for the batch as given,
+        column (w*F + f)*R + k, then permuted like the wireframes when they are decoded sorted by edge count -- a draw belongs
+        to the wireframe's place in the batch, not to its sorted place."""
+        shape = (max(T - 1, 1), N * F * R)
+        u = inputs.get("sample_uniforms")
+        if u is None:
+            gen = torch.Generator(device=device).manual_seed(int(self.sample_seed))
+            u = torch.rand(shape, generator=gen, device=device, dtype=torch.float32)
+        else:
+            u = torch.as_tensor(u)
+            if tuple(u.shape) != shape:
+                raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
+            u = u.to(device=device, dtype=torch.float32)
+        if order is not None:
+            u = u.view(shape[0], N, F * R).index_select(1, torch.tensor(order, device=device)).reshape(shape)
+        return u.contiguous()
+
     def _decode_mode(self, inputs, parallel):
         """(record, value) of the mode this model's attributes select (hip/modes.py: the first of MODES switched on; value: beam
         width / number of samples / constraint flag bits, None for greedy), after the rules only the model can check: what the
         single-sequence model does not take; an opt-in mode needs the native engine and excludes what its record lists."""
         self._extract_faces_value(inputs, parallel)
         self._sequence_faces_value(inputs, parallel)
-        if parallel and getattr(self, "sequence_samples", 0):
-            raise ValueError("sequence_samples is a SurfaceFormer option (draws per wireframe of the single-sequence model); "
-                             "SurfaceFormer_Parallel draws per anchor with num_samples")
-        if parallel and getattr(self, "sequence_beams", 0):
-            raise ValueError("sequence_beams is a SurfaceFormer option (beams per wireframe of the single-sequence model); "
-                             "SurfaceFormer_Parallel searches per anchor with beam_width")
-        if parallel and getattr(self, "sequence_constrain", None) is not None:
-            raise ValueError("sequence_constrain is a SurfaceFormer option (the loop rule per face of the single-sequence model's row); "
-                             "SurfaceFormer_Parallel constrains per anchor with constrain")
+        for mode in _modes.SEQUENCE_MODES if parallel else ():
+            if mode.switches[0].on(self):
+                raise ValueError("%s is a SurfaceFormer option (%s); SurfaceFormer_Parallel %s per anchor with %s"
+                                 % ((mode.subject, mode.sequence.model_has) + mode.sequence.parallel_has))
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
@@ -493,16 +506,10 @@ class SurfaceFormerBase(nn.Module):
         every wireframe is F rows wide whatever its edge count -- the micro-batches forward_eval gets by sorting are the ones
         this plan has already -- and there is no sort_by_edges permutation to undo.  stop_each_eos (seq2seq) is a rule of the
         greedy decode and is not looked at: a forced decode has no stop rule."""
-        for mode in reversed(_modes.MODES):
+        for mode in tuple(reversed(_modes.MODES)) + _modes.SEQUENCE_MODES:
             for sw in mode.switches:
                 if not sw.scored and sw.on(self):
                     raise ValueError("score() excludes %s: set model.%s = %r to score given paths" % (sw.attr, sw.attr, sw.off))
-        if getattr(self, "sequence_samples", 0):
-            raise ValueError("score() excludes sequence_samples: set model.sequence_samples = 0 to score given paths")
-        if getattr(self, "sequence_beams", 0):
-            raise ValueError("score() excludes sequence_beams: set model.sequence_beams = 0 to score given paths")
-        if getattr(self, "sequence_constrain", None) is not None:
-            raise ValueError("score() excludes sequence_constrain: set model.sequence_constrain = None to score given paths")
         if getattr(self, "constrain_samples", 0):     # (an option of constrain: without constrain the lines above have not raised)
             raise ValueError("score() excludes constrain_samples: set model.constrain_samples = 0 to score given paths")
         if not self.engine_supported():

@@ -78,9 +78,8 @@ class SurfaceFormer(SurfaceFormerBase):
         T = self.num_labels
         self._decode_mode(inputs, parallel=False)       # (the records' reasons: hip/modes.py)
         extract = self._sequence_faces_value(inputs, parallel=False)
-        W = self._sequence_beams_value(inputs)
-        R = self._sequence_samples_value(inputs)
-        SC = self._sequence_constrain_value(inputs)
+        mode, value = self._sequence_mode(inputs)
+        G = value if mode is not None and mode.per_anchor else 1       # draws or beams per wireframe
         if inputs["input"].size(0) == 0:     # an empty batch: the reference's loop stops after its first step (0 EOS == batch size 0, model.py:207)
             dev, S = inputs["input"].device, inputs["input"].size(1) + self.num_token
             inputs["embedding"] = torch.zeros((0, S, self.num_model), device=dev)
@@ -88,23 +87,12 @@ class SurfaceFormer(SurfaceFormerBase):
             inputs["predict"] = torch.zeros((0, T), dtype=torch.long, device=dev)
             if getattr(self, "return_logprob", False):
                 inputs["predict_logprob"] = torch.zeros((0, T), device=dev)
-            if R:
+            if mode is not None:             # (the keys, dtypes and trailing shapes of a non-empty batch)
                 del inputs["pointer"]
-                inputs["predict_samples"] = torch.zeros((0, R, T), dtype=torch.long, device=dev)
-                inputs["predict_sample_logprob"] = torch.zeros((0, R, T), device=dev)
-                inputs["predict_sample_scores"] = torch.zeros((0, R), device=dev)
-            if W:
-                del inputs["pointer"]
-                inputs["predict_beams"] = torch.zeros((0, W, T), dtype=torch.long, device=dev)
-                inputs["predict_beam_scores"] = torch.zeros((0, W), device=dev)
-                inputs["predict_beam_finished"] = torch.zeros((0, W), dtype=torch.int32, device=dev)
-            if SC is not None:
-                del inputs["pointer"]
-                inputs["predict_logprob"] = torch.zeros((0, T), device=dev)
-                inputs["predict_dead_end"] = torch.zeros((0, T), dtype=torch.int32, device=dev)
-                inputs["predict_open_end"] = torch.zeros((0,), dtype=torch.int32, device=dev)
+                for key, dims, dtype in mode.outs:
+                    inputs["predict_" + key] = torch.zeros((0,) + tuple({"G": G, "T": T}[d] for d in dims), dtype=dtype, device=dev)
             if extract:                      # (the keys, dtypes and trailing shapes of a non-empty batch; nothing is launched)
-                G, P = max(R, W, 1), getattr(self, "sequence_faces_slots", None) or max(T // 2, 1)
+                P = getattr(self, "sequence_faces_slots", None) or max(T // 2, 1)
                 z = lambda dtype, *shape: torch.zeros((0,) + shape, dtype=dtype, device=dev)
                 found = {k: z(torch.int32, G, P) for k in ("len", "start", "type", "closed", "loops", "dup_of", "take", "rep", "votes", "major")}
                 found.update({k: z(torch.float64, G, P) for k in ("score", "row_best", "best")})
@@ -119,28 +107,20 @@ class SurfaceFormer(SurfaceFormerBase):
                              "needed" % (label.size(1), T - 1))
         want_lp = bool(getattr(self, "return_logprob", False))
         eng, memory, mask, kv_len = self._encode(inputs)
-        if W or R:
-            inputs = self._forward_eval_beams(inputs, eng, memory, mask, kv_len, T, W) if W else \
-                self._forward_eval_samples(inputs, eng, memory, mask, kv_len, T, R)
-            if extract:
-                inputs["sequence_faces"] = self._sequence_faces_of_decode(inputs, extract, memory.device)
-            return inputs
-        if SC is not None:
-            inputs = self._forward_eval_constrained(inputs, eng, memory, mask, kv_len, T, SC)
-            if extract:
-                inputs["sequence_faces"] = self._sequence_faces_of_decode(inputs, extract, memory.device)
-            return inputs
-        out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
-                         chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
-                         chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1,
-                         flags=self.decode_flags | (_L.FF_STOP_EACH_EOS if self.stop_each_eos else 0),
-                         x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS, tok_eos=self.token.EOS,
-                         return_pointer=True, extra_mask=self._extra_mask(inputs), logprob=want_lp)
-        inputs["embedding"] = memory
-        inputs["pointer"] = out["pointer"].transpose(0, 1)
-        inputs["predict"] = out["predict"]
-        if want_lp:
-            inputs["predict_logprob"] = out["logprob"]
+        if mode is not None:
+            inputs = self._forward_eval_sequence(inputs, eng, memory, mask, kv_len, T, mode, value, G)
+        else:
+            out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
+                             chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
+                             chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1,
+                             flags=self.decode_flags | (_L.FF_STOP_EACH_EOS if self.stop_each_eos else 0),
+                             x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS, tok_eos=self.token.EOS,
+                             return_pointer=True, extra_mask=self._extra_mask(inputs), logprob=want_lp)
+            inputs["embedding"] = memory
+            inputs["pointer"] = out["pointer"].transpose(0, 1)
+            inputs["predict"] = out["predict"]
+            if want_lp:
+                inputs["predict_logprob"] = out["logprob"]
         if extract:
             inputs["sequence_faces"] = self._sequence_faces_of_decode(inputs, extract, memory.device)
         return inputs
@@ -160,10 +140,7 @@ class SurfaceFormer(SurfaceFormerBase):
             kw = dict(scores=inputs["predict_beam_scores"], finished=inputs["predict_beam_finished"])
         else:
             tokens, kw = inputs["predict"], dict(logprob=inputs.get("predict_logprob"))
-        ni = inputs.get("num_input")
-        if ni is None:
-            ni = (~inputs["input_mask"].to(device=device, dtype=torch.bool)).sum(dim=1)
-        ni = torch.as_tensor(ni).to(device=device, dtype=torch.int32).reshape(-1)
+        ni = self._edge_counts(inputs, device)
         enclosed = extract == "enclosed"
         edge_map = inputs.get("edge_map")
         found = _ops.face_seq_rows(tokens, ni, self.token, slots=getattr(self, "sequence_faces_slots", None),
@@ -173,120 +150,46 @@ class SurfaceFormer(SurfaceFormerBase):
         found.update(_ops.face_seq_votes(found, require_closed=enclosed))
         return found
 
-    def _sequence_constrain_value(self, inputs):
-        """sequence_constrain as None or its flag bits, after the rules only the model can check (ValueError, before anything is
-        launched): the native engine, what the record excludes, stop_each_eos."""
-        SC = _modes.sequence_constrain_flags(getattr(self, "sequence_constrain", None))
-        if SC is None:
-            return None
-        mode = _modes.SEQUENCE_CONSTRAIN
-        if not self.engine_supported():
-            raise ValueError("sequence_constrain needs the native engine: this model's constructor arguments take the sub-module loop")
-        if getattr(self, "sequence_samples", 0) or getattr(self, "sequence_beams", 0) or getattr(self, "return_logprob", False) or \
-                inputs.get("extra_mask") is not None:
-            raise ValueError("sequence_constrain excludes %s, %s, %s and %s" % mode.model_excludes)
-        if getattr(self, "stop_each_eos", False):
-            raise ValueError("sequence_constrain excludes stop_each_eos = True: every row is finished by its own EOS already")
-        return SC
+    def _edge_counts(self, inputs, device):
+        """The edge count of every wireframe, int32 [N] on `device`: inputs["num_input"] when given, else its unmasked edges."""
+        ni = inputs.get("num_input")
+        if ni is None:
+            ni = (~inputs["input_mask"].to(device=device, dtype=torch.bool)).sum(dim=1)
+        return torch.as_tensor(ni).to(device=device, dtype=torch.int32).reshape(-1)
 
-    def _forward_eval_constrained(self, inputs, eng, memory, mask, kv_len, T, SC):
-        """forward_eval with sequence_constrain (flag bits SC) behind the encoder.  The wireframes are decoded in batch order
-        (this model applies no permutation), so the follow table is taken as built or given."""
-        dev = memory.device
-        table = None
-        if SC & _L.FF_CONSTRAIN_CONNECT:
-            ni = inputs.get("num_input")
-            if ni is None:
-                ni = (~inputs["input_mask"].to(device=dev, dtype=torch.bool)).sum(dim=1)
-            ni = torch.as_tensor(ni).to(device=dev, dtype=torch.int32).reshape(-1)
-            table = self._follow_table(inputs, dev, ni, None)
-        out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
-                         chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
-                         chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1, flags=self.decode_flags,
-                         x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS,
-                         tok_eos=self.token.EOS, tok_sep=int(getattr(self.token, "SEP", 2)), sequence_constrain=SC, follow_table=table)
-        inputs["embedding"] = memory
-        inputs["predict"] = out["predict"]
-        inputs["predict_logprob"] = out["logprob"]
-        inputs["predict_dead_end"] = out["dead_end"]
-        inputs["predict_open_end"] = out["open_end"]
-        self.last_constrain_stats = {"steps": out["steps"], "slot_rows": out["slot_rows"]}
-        return inputs
+    def _sequence_mode(self, inputs):
+        """(record, value) of the one of SEQUENCE_MODES this model's attributes switch on (hip/modes.py; value: the draws, the
+        width or the flag bits), else (None, None), after the rules only the model can check (ValueError, before anything is
+        launched): the native engine, what the record excludes, its own value checks."""
+        found = (None, None)
+        for mode in _modes.SEQUENCE_MODEL_ORDER:
+            sw = mode.switches[0]
+            value = mode.sequence.value(getattr(self, sw.attr, sw.off))
+            if value == sw.off:
+                continue
+            if not self.engine_supported():
+                raise ValueError("%s needs the native engine: this model's constructor arguments take the sub-module loop" % sw.attr)
+            if any(inputs.get("extra_mask") is not None if word == "an extra mask" else getattr(self, word, False)
+                   for word in mode.model_excludes):
+                raise ValueError("%s excludes %s and %s" % (sw.attr, ", ".join(mode.model_excludes[:-1]), mode.model_excludes[-1]))
+            mode.sequence.model_values(self, value, inputs)
+            found = (mode, value)
+        return found
 
-    def _sequence_beams_value(self, inputs):
-        """sequence_beams as 0 or W in 1..8, after the rules only the model can check (ValueError, before anything is launched):
-        the native engine, what the record excludes, the width against S, the stop value."""
-        W = _modes.sequence_beams_value(getattr(self, "sequence_beams", 0))
-        if not W:
-            return 0
-        mode = _modes.SEQUENCE_BEAM
-        if not self.engine_supported():
-            raise ValueError("sequence_beams needs the native engine: this model's constructor arguments take the sub-module loop")
-        if getattr(self, "sequence_samples", 0) or getattr(self, "beam_width", 0) or getattr(self, "return_logprob", False) or \
-                inputs.get("extra_mask") is not None:
-            raise ValueError("sequence_beams excludes %s, %s, %s and %s" % mode.model_excludes)
-        _modes.check_options(mode, _L.FF_SEQ2SEQ, dict(sequence_beams=W, sequence_beam_stop=getattr(self, "sequence_beam_stop", "all"),
-                                                      S=inputs["input"].size(1) + self.num_token), None)
-        return W
-
-    def _forward_eval_beams(self, inputs, eng, memory, mask, kv_len, T, W):
-        """forward_eval with sequence_beams = W behind the encoder.  The wireframes are decoded in batch order (this model applies
-        no permutation): row w*W + k of the engine's outputs is beam k of wireframe w as given."""
+    def _forward_eval_sequence(self, inputs, eng, memory, mask, kv_len, T, mode, value, G):
+        """forward_eval with one of SEQUENCE_MODES on behind the encoder.  The wireframes are decoded in batch order (this model
+        applies no permutation): row w*G + k of the engine's outputs is draw / beam k of wireframe w as given."""
         N = memory.size(0)
         out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
                          chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
                          chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1, flags=self.decode_flags,
                          x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS,
-                         tok_eos=self.token.EOS, sequence_beams=W, sequence_beam_stop=self.sequence_beam_stop)
+                         tok_eos=self.token.EOS, **mode.prepare(self, value, inputs, memory.device, T, N, 1, None, None))
         inputs["embedding"] = memory
         inputs["predict"] = out["predict"]
-        inputs["predict_beams"] = out["beams"].view(N, W, T)
-        inputs["predict_beam_scores"] = out["beam_scores"].view(N, W)
-        inputs["predict_beam_finished"] = out["beam_finished"].view(N, W)
-        self.last_beam_stats = {"steps": out["steps"], "slot_rows": out["slot_rows"]}
-        return inputs
-
-    def _sequence_samples_value(self, inputs):
-        """sequence_samples as 0 or R in 1..64, after the rules only the model can check (ValueError, before anything is
-        launched): the native engine, what the record excludes, the parameters' ranges, the shape of inputs["sample_uniforms"]."""
-        R = _modes.sequence_samples_value(getattr(self, "sequence_samples", 0))
-        if not R:
-            return 0
-        mode = _modes.SEQUENCE_SAMPLE
-        if not self.engine_supported():
-            raise ValueError("sequence_samples needs the native engine: this model's constructor arguments take the sub-module loop")
-        if getattr(self, "return_logprob", False) or inputs.get("extra_mask") is not None:
-            raise ValueError("sequence_samples excludes %s and %s" % mode.model_excludes)
-        _modes.check_options(mode, _L.FF_SEQ2SEQ, dict(sequence_samples=R, temperature=self.sample_temperature,
-                                                      top_k=self.sample_top_k, top_p=self.sample_top_p), None)
-        u = inputs.get("sample_uniforms")
-        shape = (max(self.num_labels - 1, 1), inputs["input"].size(0) * R)
-        if u is not None and tuple(torch.as_tensor(u).shape) != shape:
-            raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
-        return R
-
-    def _forward_eval_samples(self, inputs, eng, memory, mask, kv_len, T, R):
-        """forward_eval with sequence_samples = R behind the encoder.  The wireframes are decoded in batch order (this model
-        applies no permutation), so column w*R + k of the uniforms is draw k of wireframe w as given."""
-        N, dev = memory.size(0), memory.device
-        u = inputs.get("sample_uniforms")
-        if u is None:
-            gen = torch.Generator(device=dev).manual_seed(int(self.sample_seed))
-            u = torch.rand((max(T - 1, 1), N * R), generator=gen, device=dev, dtype=torch.float32)
-        else:
-            u = torch.as_tensor(u).to(device=dev, dtype=torch.float32).contiguous()
-        out = eng.decode(memory, mask, kv_len, _L.FF_SEQ2SEQ, T=T, F=1,
-                         chunk_wireframes=self.chunk_wireframes, chunk_seqs=self.chunk_seqs,
-                         chunk_max_seqs=self.chunk_max_seqs, num_streams=self.num_streams, sync_every=1, flags=self.decode_flags,
-                         x3_min_rows=self.x3_min_rows, ln_fuse_max_rows=self.ln_fuse_max_rows, tok_sos=self.token.SOS,
-                         tok_eos=self.token.EOS, sequence_samples=R, temperature=float(self.sample_temperature),
-                         top_k=int(self.sample_top_k), top_p=float(self.sample_top_p), uniforms=u)
-        inputs["embedding"] = memory
-        inputs["predict"] = out["predict"]
-        inputs["predict_samples"] = out["samples"].view(N, R, T)
-        inputs["predict_sample_logprob"] = out["sample_logprob"].view(N, R, T)
-        inputs["predict_sample_scores"] = out["sample_scores"].view(N, R)
-        self.last_sample_stats = {"steps": out["steps"], "slot_rows": out["slot_rows"]}
+        for key, dims, _ in mode.outs:
+            inputs["predict_" + key] = out[key].view((N,) + tuple({"G": G, "T": T}[d] for d in dims))
+        setattr(self, mode.sequence.stats, {"steps": out["steps"], "slot_rows": out["slot_rows"]})
         return inputs
 
     def label_paths(self, inputs):

@@ -206,24 +206,6 @@ class SurfaceFormer_Parallel(SurfaceFormerBase):
             t = t.index_select(0, torch.tensor(order, device=device))
         return t.contiguous()
 
-    def _sample_uniforms(self, inputs, device, T, N, F, R, order):
-        """The uniforms [T-1, N*F*R] of a sampled decode in the DECODE's wireframe order: made (or given) for the batch as given,
-        column (w*F + f)*R + k, then permuted like the wireframes when they are decoded sorted by edge count -- a draw belongs
-        to the wireframe's place in the batch, not to its sorted place."""
-        shape = (max(T - 1, 1), N * F * R)
-        u = inputs.get("sample_uniforms")
-        if u is None:
-            gen = torch.Generator(device=device).manual_seed(int(self.sample_seed))
-            u = torch.rand(shape, generator=gen, device=device, dtype=torch.float32)
-        else:
-            u = torch.as_tensor(u)
-            if tuple(u.shape) != shape:
-                raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
-            u = u.to(device=device, dtype=torch.float32)
-        if order is not None:
-            u = u.view(shape[0], N, F * R).index_select(1, torch.tensor(order, device=device)).reshape(shape)
-        return u.contiguous()
-
     def label_paths(self, inputs):
         """score()'s defaults, the data set's own labels: (paths N x F x T = label[:, :max(num_input)], lengths N x F = the
         non-PAD tokens after column 0 by label_mask; unused rows, which hold one token, get 0)."""
