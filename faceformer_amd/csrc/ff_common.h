@@ -206,6 +206,17 @@ int ff_sequence_constrain_finalize(const int* tok, const float* lp, const int* f
                                    const int* steps_dev, int w0, int nw, int b0, int64_t* predict, float* logprob, int* dead_end,
                                    int* open_end, int* seq_of_row, hipStream_t st);
 
+// Sequence-constrained sampled decode (ff_constrain_seq.hip): the sequence-constrained step's operands and
+// the draw's; R draws per wireframe in the sequence-sampled decode's layout, each with the sequence-constrained decode's state.
+int ff_pointer_sequence_constrained_sample_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,
+                                                int tok_sep, int tok_eos, const ff_sample_draw_io& draw, ff_stream_t stream);
+int ff_sequence_constrain_sample_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int* row_id,
+                                      int Bc, int R, int w0, int L, int sos, hipStream_t st);
+int ff_sequence_constrain_sample_finalize(const int* tok, const float* lp, const int* fin, const int* dead, const int* first, int Btot,
+                                          int T, const int* steps_dev, int R, int w0, int nw, int b0, int64_t* samples, float* logprob,
+                                          float* scores, int* dead_end, int* open_end, int64_t* predict, float* predict_logprob,
+                                          int* predict_dead_end, int* predict_open_end, int* seq_of_row, hipStream_t st);
+
 // Constrained sampled decode (ff_constrain_sample.hip): the constrained step's operands and the draw's; R draws per
 // anchor in the sampled decode's layout, each with the constrained decode's state.
 int ff_pointer_constrained_sample_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,

@@ -16,6 +16,14 @@
 // flags and the next (first, prev) and sets the token's bit in the visited words; on SEP the wave clears its visited words
 // unless ONCE; the wave appends memory[w, token] through ff_pointer_append_row, so FF_L0_FOLD keeps working.  Stop counter:
 // the rows unfinished after the step (ff_pointer_count_waves), DESIGN.md 29's counter.  No LDS beyond the four counter words.
+//
+// The sampled form is a compile-time form of the same kernel, selected by the argument struct: behind the masked
+// reduction the wave draws from the constrained row with ff_sample_draw -- top-k and top-p therefore act on the constrained row,
+// and on a dead end the draw is SEP, the only live key -- and the lane that owns the token (lane = key mod 64) reads its own
+// masked logit back and broadcasts it for the log-probability (l[tok] - m) - log sum, saturated at -FLT_MAX: the model's
+// distribution renormalised over the keys the rule allows.  With temperature 0 the greedy expression -logf(lsum) stays, so
+// that the two forms agree bit for bit; with all flag bits clear the byte row is zero and the launch is
+// pointer_sample_kernel<true>'s.  Nothing of the rule or of the draw is restated; still no barrier and no further LDS.
 #include <float.h>
 
 #include "ff_common.h"
@@ -37,9 +45,20 @@ struct SeqConstrainArgs {
   unsigned* visited;             // [B, fw] in / out: the edges of the current face, or under ONCE of every face so far
   int *fin_out, *first_out, *prev_out, *dead_out;   // [B] out
   int* tok; float* logprob;      // [B] out
+  static constexpr bool DRAW = false;
 };
 
-__global__ __launch_bounds__(256) void pointer_sequence_constrained_kernel(SeqConstrainArgs a) {
+// The sampled form's operands: the above, and the draw's.
+struct SeqConstrainSampleArgs : SeqConstrainArgs {
+  const float* uniforms;         // [num_uniforms] this step's draws
+  const int* row_id;             // [B] the draw every launch row reads (null: b); clamped into [0, num_uniforms)
+  int num_uniforms;
+  float temperature; int top_k; float top_p;
+  static constexpr bool DRAW = true;
+};
+
+template <class Args>
+__global__ __launch_bounds__(256) void pointer_sequence_constrained_kernel(Args a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -66,6 +85,16 @@ __global__ __launch_bounds__(256) void pointer_sequence_constrained_kernel(SeqCo
       float m, b2, lsum;
       ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &tok, &lsum);
       lp = -logf(lsum);
+      if constexpr (Args::DRAW) {   // the draw in place of the argmax (ff_select.h's one copy), from the row masked just now
+        const float* lrow = pa.logits + (size_t)b * pa.ldlogits;
+        tok = ff_sample_draw(lrow, pa.S, lane, m, tok, a.temperature, a.top_k, a.top_p, a.uniforms, a.row_id, a.num_uniforms, b);
+        // the masked l[tok] was stored by lane tok % 64 a moment ago: that lane reads its own store back and broadcasts it
+        const int owner = tok & 63;
+        const float mine = lane == owner ? ff_ld4(lrow + tok) : 0.f;
+        const float lg = __shfl(mine, owner, FF_WAVE);
+        // saturates: no -inf, no NaN.  Temperature 0 selects the maximum, l[tok] = m: the greedy form's own expression stays
+        if (a.temperature != 0.f) lp = fmaxf((lg - m) - logf(lsum), -FLT_MAX);
+      }
       if (tok >= ntok) {
         const int e = tok - ntok;
         ff_loop_advance(a.follows, w, a.L, a.fw, e, &first, &prev);
@@ -90,6 +119,8 @@ __global__ __launch_bounds__(256) void pointer_sequence_constrained_kernel(SeqCo
   }
   ff_pointer_count_waves(pa, pa.B, unfinished);
 }
+// (the greedy form is instantiated here, in the place its code has always had in this file's device code)
+template __global__ void pointer_sequence_constrained_kernel<SeqConstrainArgs>(SeqConstrainArgs);
 
 // ---- engine side: start state and output packing (ff_engine.hip) ---------------------------------------------------------------------
 // Start state of one micro-batch of Bc sequences, one per wireframe: SOS (model.py:191), log-probability 0, unfinished, the
@@ -137,6 +168,71 @@ __global__ void sequence_constrain_finalize_kernel(const int* __restrict__ tok, 
   }
 }
 
+// ---- engine side of the sampled form: start state and output packing --------------------------------------------------
+// Start state of one micro-batch of Bc = nw * R draws, draw k of the chunk's wl-th wireframe at i = wl * R + k: SOS
+// (model.py:191), log-probability 0, unfinished, the rule's state empty and closed; row_id: its output row (w0 + wl) * R + k.
+__global__ void sequence_constrain_sample_init_kernel(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited,
+                                                      int* row_id, int Bc, int R, int w0, int fw, int sos) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bc) return;
+  tok[i] = sos;
+  lp[i] = 0.f;
+  fin[i] = 0;
+  dead[i] = 0;
+  first[i] = prev[i] = -1;
+  row_id[i] = w0 * R + i;
+  for (int k = 0; k < fw; ++k) visited[(size_t)i * fw + k] = 0u;
+}
+
+// samples[(w, k), :], logprob and dead_end (same layout), scores[(w, k)] and open_end[(w, k)] of the chunk's nw wireframes from
+// the per-step records (tok, lp, fin, dead, first: [T, Btot], row s = the state after s steps; sequence b0 + wl * R + k stands
+// for draw k of wireframe w0 + wl), and draw 0 under the greedy constrained decode's keys: predict[w, :], predict_logprob[w, :],
+// predict_dead_end[w, :], predict_open_end[w].  Position j is kept when j <= the stop step and the draw was not finished before
+// it: last = min(own EOS, stop step); rows behind the stop step are never looked at, so the result does not depend on when the
+// host saw the stop.  scores: the kept log-probabilities added in ascending position (fp64 accumulator, rounded once, saturated
+// at -FLT_MAX).  open_end: a loop is open after the last kept position.
+__global__ void sequence_constrain_sample_finalize_kernel(const int* __restrict__ tok, const float* __restrict__ lp,
+                                                          const int* __restrict__ fin, const int* __restrict__ dead,
+                                                          const int* __restrict__ first, int Btot, int T, const int* __restrict__ steps_p,
+                                                          int R, int w0, int nw, int b0, int64_t* __restrict__ samples,
+                                                          float* __restrict__ logprob, float* __restrict__ scores,
+                                                          int* __restrict__ dead_end, int* __restrict__ open_end,
+                                                          int64_t* __restrict__ predict, float* __restrict__ predict_logprob,
+                                                          int* __restrict__ predict_dead_end, int* __restrict__ predict_open_end,
+                                                          int* __restrict__ seq_of_row) {
+  const int steps = *steps_p;
+  const int total = nw * R;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int k = i % R, wl = i / R;
+    const int seq = b0 + i;
+    const size_t wf = (size_t)(w0 + wl), row = wf * R + k;
+    int64_t* out = samples + row * T;
+    float* olp = logprob + row * T;
+    int* ode = dead_end + row * T;
+    const bool p0 = k == 0;
+    double sum = 0.0;
+    int open = 0;
+    bool done = false;   // finished before position j
+    for (int j = 0; j < T; ++j) {
+      const bool in = j <= steps && !done;
+      const size_t r = (size_t)j * Btot + seq;
+      const int v = in ? tok[r] : 0;
+      const float l = (in && j >= 1) ? lp[r] : 0.f;
+      const int de = (in && j >= 1) ? dead[r] : 0;
+      out[j] = v;
+      olp[j] = l;
+      ode[j] = de;
+      if (p0) { predict[wf * T + j] = v; predict_logprob[wf * T + j] = l; predict_dead_end[wf * T + j] = de; }
+      sum += (double)l;
+      if (in) { open = first[r] >= 0 ? 1 : 0; done = fin[r] != 0; }
+    }
+    scores[row] = (float)fmax(sum, -(double)FLT_MAX);
+    open_end[row] = open;
+    if (p0) predict_open_end[wf] = open;
+    if (seq_of_row) seq_of_row[row] = seq;
+  }
+}
+
 }  // namespace
 
 // The flag bits, the two tokens and the follow table of a sequence-constrained step, for operator `op`.
@@ -150,18 +246,14 @@ int ff_sequence_rule_check(const char* op, const ff_loop_rule_io& r, int S, int 
   return FF_OK;
 }
 
-// The one launch behind ff_pointer_sequence_constrained and the engine's step (io's terminator range is not read: the rule has
-// its two tokens).
-int ff_pointer_sequence_constrained_sync(const ff_step_io& io_in, const ff_loop_rule_io& rule, const ff_constrained_state& s, int tok_sep,
-                                         int tok_eos, ff_stream_t stream) {
-  const char* op = "ff_pointer_sequence_constrained";
+// The checks and operands the greedy and the sampled launch share (io's terminator range is not read: the rule has its two
+// tokens); `a` zeroed by the caller.
+static int seq_constrain_args(SeqConstrainArgs& a, const char* op, const ff_step_io& io_in, const ff_loop_rule_io& rule,
+                              const ff_constrained_state& s, int tok_sep, int tok_eos) {
   const int B = io_in.rows, S = io_in.S;
-  if (B == 0) return FF_OK;
   FF_CHECK_ARG(B > 0 && S > 0 && io_in.rows_per_wireframe > 0, "%s: bad sizes B=%d S=%d", op, B, S);
   ff_step_io io = io_in;
   io.term_lo = tok_sep; io.term_hi = tok_sep + 1;   // (what ff_loop_write_row leaves open with the loop closed and re-opens on a dead end)
-  SeqConstrainArgs a;
-  memset(&a, 0, sizeof(a));
   FF_RETURN_IF(ff_step_args(&a.p, op, true, io));
   FF_RETURN_IF(ff_sequence_rule_check(op, rule, S, tok_sep, tok_eos));
   FF_CHECK_ARG(s.fin_in && s.first_in && s.prev_in && s.visited && s.mask_rows && s.next_tok && s.logprob && s.fin_out && s.dead_end &&
@@ -172,9 +264,40 @@ int ff_pointer_sequence_constrained_sync(const ff_step_io& io_in, const ff_loop_
   a.fin_in = s.fin_in; a.first_in = s.first_in; a.prev_in = s.prev_in; a.visited = s.visited;
   a.fin_out = s.fin_out; a.first_out = s.first_out; a.prev_out = s.prev_out; a.dead_out = s.dead_end;
   a.tok = s.next_tok; a.logprob = s.logprob;
+  return FF_OK;
+}
+
+// The one launch behind ff_pointer_sequence_constrained and the engine's step.
+int ff_pointer_sequence_constrained_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& s, int tok_sep,
+                                         int tok_eos, ff_stream_t stream) {
+  const int B = io.rows, S = io.S;
+  if (B == 0) return FF_OK;
+  SeqConstrainArgs a;
+  memset(&a, 0, sizeof(a));
+  FF_RETURN_IF(seq_constrain_args(a, "ff_pointer_sequence_constrained", io, rule, s, tok_sep, tok_eos));
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 4.0, st);
-  hipLaunchKernelGGL(pointer_sequence_constrained_kernel, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(pointer_sequence_constrained_kernel<SeqConstrainArgs>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+// The one launch behind ff_pointer_sequence_constrained_sample and the engine's sampled step: the checks above and
+// ff_pointer_sample_sync's (ff_sample_draw_check).
+int ff_pointer_sequence_constrained_sample_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& s,
+                                                int tok_sep, int tok_eos, const ff_sample_draw_io& d, ff_stream_t stream) {
+  const char* op = "ff_pointer_sequence_constrained_sample";
+  const int B = io.rows, S = io.S;
+  if (B == 0) return FF_OK;
+  SeqConstrainSampleArgs a;
+  memset(&a, 0, sizeof(a));
+  FF_RETURN_IF(seq_constrain_args(a, op, io, rule, s, tok_sep, tok_eos));
+  FF_RETURN_IF(ff_sample_draw_check(op, d, B));
+  a.uniforms = d.uniforms; a.num_uniforms = d.num_uniforms; a.row_id = d.row_id;
+  a.temperature = d.temperature; a.top_k = d.top_k; a.top_p = d.top_p;
+  hipStream_t st = (hipStream_t)stream;
+  FFProfScope prof(FF_CAT_POINTER, (double)B * S * 16.0, st);
+  hipLaunchKernelGGL(pointer_sequence_constrained_kernel<SeqConstrainSampleArgs>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
@@ -208,6 +331,44 @@ int ff_sequence_constrain_finalize(const int* tok, const float* lp, const int* f
                                    int* open_end, int* seq_of_row, hipStream_t st) {
   hipLaunchKernelGGL(sequence_constrain_finalize_kernel, dim3(ff_cdiv(nw, 256) < 1024 ? ff_cdiv(nw, 256) : 1024), dim3(256), 0, st, tok, lp,
                      fin, dead, first, Btot, T, steps_dev, w0, nw, b0, predict, logprob, dead_end, open_end, seq_of_row);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+// Restates select_next (model.py:161-167) under the rule and with the draw, for the loop of model.py:193-210 that starts at SOS
+// (model.py:191).
+extern "C" int ff_pointer_sequence_constrained_sample(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len,
+                                                      int B, int seqs_per_group, const unsigned* follows, int L, int flags, int ntok,
+                                                      int tok_sep, int tok_eos, const int* fin_in, const int* first_in,
+                                                      const int* prev_in, unsigned* visited, unsigned char* mask_rows, int* next_tok,
+                                                      float* logprob, int* fin_out, int* dead_end, int* first_out, int* prev_out,
+                                                      const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                                                      int* count_unfinished, const float* uniforms, int num_uniforms, const int* row_id,
+                                                      float temperature, int top_k, float top_p, ff_stream_t stream) {
+  return ff_pointer_sequence_constrained_sample_sync(
+      ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, 0, 0, ntok, memory, E, next_rows, ldnext, next_stats,
+                 count_unfinished, nullptr, nullptr},
+      ff_loop_rule_io{follows, L, flags, ntok},
+      ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
+      tok_sep, tok_eos, ff_sample_draw_io{uniforms, num_uniforms, row_id, temperature, top_k, top_p}, stream);
+}
+
+int ff_sequence_constrain_sample_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int* row_id,
+                                      int Bc, int R, int w0, int L, int sos, hipStream_t st) {
+  hipLaunchKernelGGL(sequence_constrain_sample_init_kernel, dim3(ff_cdiv(Bc, 256)), dim3(256), 0, st, tok, lp, fin, dead, first, prev,
+                     visited, row_id, Bc, R, w0, (L + 31) >> 5, sos);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+int ff_sequence_constrain_sample_finalize(const int* tok, const float* lp, const int* fin, const int* dead, const int* first, int Btot,
+                                          int T, const int* steps_dev, int R, int w0, int nw, int b0, int64_t* samples, float* logprob,
+                                          float* scores, int* dead_end, int* open_end, int64_t* predict, float* predict_logprob,
+                                          int* predict_dead_end, int* predict_open_end, int* seq_of_row, hipStream_t st) {
+  const int total = nw * R;
+  hipLaunchKernelGGL(sequence_constrain_sample_finalize_kernel, dim3(ff_cdiv(total, 256) < 1024 ? ff_cdiv(total, 256) : 1024), dim3(256), 0,
+                     st, tok, lp, fin, dead, first, Btot, T, steps_dev, R, w0, nw, b0, samples, logprob, scores, dead_end, open_end,
+                     predict, predict_logprob, predict_dead_end, predict_open_end, seq_of_row);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }

@@ -46,6 +46,8 @@
 //   sequence constrain (ff_decode_sequence_constrained, single-sequence variant): the greedy single-sequence plan
 //     (F = 1, one sequence per wireframe, chunk_max_seqs) with constrain's records and state, every sequence from SOS, and
 //     ff_pointer_sequence_constrained, whose counter is "rows unfinished after the step".
+//   sequence constrain sample (ff_decode_sequence_constrained_sample): sequence sample's plan (R draws per wireframe)
+//     with sequence constrain's records and state per draw plus row_id, and ff_pointer_sequence_constrained_sample.
 //   constrain (ff_decode_constrained): the default plan, one sequence per anchor.  ff_pointer_constrained masks
 //     the keys the enclosure walk could not accept; records and the rule's state (first, prev per step; visited words and the
 //     byte mask per sequence).
@@ -371,7 +373,7 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM, SEQ_CONSTRAIN } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM, SEQ_CONSTRAIN, SEQ_CONSTRAIN_SAMPLE } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
@@ -390,7 +392,7 @@ struct Mode {
   const ff_constrain_beam_ahead_params* cbeam_ahead() const { return static_cast<const ff_constrain_beam_ahead_params*>(prm); }
   // (CONSTRAIN_BEAM and CONSTRAIN_BEAM_AHEAD: the parameters the two share)
   bool is_cbeam() const { return kind == CONSTRAIN_BEAM || kind == CONSTRAIN_BEAM_AHEAD; }
-  bool is_sequence() const { return kind == SEQ_SAMPLE || kind == SEQ_BEAM || kind == SEQ_CONSTRAIN; }   // (the ff_decode_sequence_* entries)
+  bool is_sequence() const { return kind == SEQ_SAMPLE || kind == SEQ_BEAM || kind == SEQ_CONSTRAIN || kind == SEQ_CONSTRAIN_SAMPLE; }   // (the ff_decode_sequence_* entries)
   ff_constrain_beam_params cbeam() const {
     if (kind != CONSTRAIN_BEAM_AHEAD) return *static_cast<const ff_constrain_beam_params*>(prm);
     const ff_constrain_beam_ahead_params* q = cbeam_ahead();
@@ -398,6 +400,7 @@ struct Mode {
   }
   const ff_constrain_sample_params* csample() const { return static_cast<const ff_constrain_sample_params*>(prm); }
   const ff_sequence_constrain_params* seqcon() const { return static_cast<const ff_sequence_constrain_params*>(prm); }
+  const ff_sequence_constrain_sample_params* seqcs() const { return static_cast<const ff_sequence_constrain_sample_params*>(prm); }
 };
 
 // The micro-batch plan of a mode: the default plan for greedy and constrain; without de-duplication for forced (the rows are
@@ -411,6 +414,7 @@ void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, con
     case Mode::CONSTRAIN_SAMPLE:
     case Mode::SEQ_SAMPLE:   // (FF_SEQ2SEQ: a micro-batch is cut by sequences, chunk_max_seqs / R wireframes, at least one)
     case Mode::SEQ_BEAM:     // (likewise: chunk_max_seqs / W wireframes, at least one)
+    case Mode::SEQ_CONSTRAIN_SAMPLE:   // (SEQ_SAMPLE's plan)
     case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
     case Mode::FORCED: {
       ff_decode_params q = *p;
@@ -558,6 +562,7 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
       b.visited = bp.take<unsigned>(vw);
       b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
       break;
+    case Mode::SEQ_CONSTRAIN_SAMPLE:   // (likewise: SEQ_CONSTRAIN's records per sequence of SEQ_SAMPLE's plan)
     case Mode::CONSTRAIN_SAMPLE:   // (constrain's records per sequence of the sampled plan; row_id, visited and the byte rows last)
       b.score = bp.take<float>(TB);
       b.finished = bp.take<int>(TB);
@@ -1108,6 +1113,7 @@ struct DecodeRun {
       case Mode::CONSTRAIN_BEAM_AHEAD: follows = mode.cbeam().follows; flags = mode.cbeam().flags; break;
       case Mode::CONSTRAIN_SAMPLE: follows = mode.csample()->follows; flags = mode.csample()->flags; break;
       case Mode::SEQ_CONSTRAIN: follows = mode.seqcon()->follows; flags = mode.seqcon()->flags; break;
+      case Mode::SEQ_CONSTRAIN_SAMPLE: follows = mode.seqcs()->follows; flags = mode.seqcs()->flags; break;
       default: follows = mode.con().follows; flags = mode.con().flags; break;
     }
     return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, flags};
@@ -1146,6 +1152,10 @@ struct DecodeRun {
       case Mode::SEQ_CONSTRAIN:   // (every sequence at SOS, the rule's state empty and closed)
         return ff_sequence_constrain_init(tok, score, fin, buf.dead + c.b0, buf.first + c.b0, buf.prev + c.b0,
                                           buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), c.Bc, p->L, p->tok_sos, st);
+      case Mode::SEQ_CONSTRAIN_SAMPLE:   // (Fc = R draws per wireframe, every one at SOS with the rule's state empty and closed)
+        return ff_sequence_constrain_sample_init(tok, score, fin, buf.dead + c.b0, buf.first + c.b0, buf.prev + c.b0,
+                                                 buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), buf.row_id + c.b0, c.Bc, G, c.w0, p->L,
+                                                 p->tok_sos, st);
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
       case Mode::CONSTRAIN_EXACT:
@@ -1287,11 +1297,19 @@ struct DecodeRun {
         static const char* const op[3] = {"ff_pointer_constrained", "ff_pointer_constrained_ahead", "ff_pointer_constrained_exact"};
         return ff_pointer_constrained_sync(op[la.form], sio, rio, cs, la.form ? &ahead : nullptr, st);
       }
+      case Mode::SEQ_CONSTRAIN_SAMPLE:
       case Mode::SEQ_CONSTRAIN: {   // (constrain's state and records; the rule has SEP and EOS in place of a terminator range)
         const Rule r = rule_of(c);
         const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
                                       buf.byte_rows + (size_t)c.b0 * S, tok_out, buf.score + out, buf.finished + out, buf.dead + out,
                                       buf.first + out, buf.prev + out};
+        if (mode.kind == Mode::SEQ_CONSTRAIN_SAMPLE) {   // (this step's uniforms are read through the chunk's row_id)
+          const ff_sequence_constrain_sample_params* q = mode.seqcs();
+          const int rows = N * mode.G;
+          const ff_sample_draw_io draw{q->uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, q->temperature, q->top_k, q->top_p};
+          return ff_pointer_sequence_constrained_sample_sync(sio, ff_loop_rule_io{r.follows, r.L, r.flags, m->num_token}, cs, q->tok_sep,
+                                                             p->tok_eos, draw, st);
+        }
         return ff_pointer_sequence_constrained_sync(sio, ff_loop_rule_io{r.follows, r.L, r.flags, m->num_token}, cs, mode.seqcon()->tok_sep,
                                                     p->tok_eos, st);
       }
@@ -1517,6 +1535,13 @@ struct DecodeRun {
         const ff_sequence_constrain_params* q = mode.seqcon();
         return ff_sequence_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, buf.first, Btot, T, buf.steps_dev, c.w0, c.nw,
                                               c.b0, io.predict, q->logprob, q->dead_end, q->open_end, io.seq_of_row, main_st);
+      }
+      case Mode::SEQ_CONSTRAIN_SAMPLE: {   // (F = 1, no de-duplication: num_input is not read)
+        const ff_sequence_constrain_sample_params* q = mode.seqcs();
+        return ff_sequence_constrain_sample_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, buf.first, Btot, T, buf.steps_dev, G,
+                                                     c.w0, c.nw, c.b0, q->samples, q->logprob, q->scores, q->dead_end, q->open_end,
+                                                     io.predict, q->predict_logprob, q->predict_dead_end, q->predict_open_end,
+                                                     io.seq_of_row, main_st);
       }
       case Mode::CONSTRAIN_SAMPLE: {
         const ff_constrain_sample_params* q = mode.csample();
@@ -1887,6 +1912,32 @@ extern "C" int ff_decode_sequence_constrained(const ff_model* m, const ff_decode
                "%s: logprob, dead_end, open_end and predict are required", name);
   return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
                       stream, Mode(Mode::SEQ_CONSTRAIN, 1, constrain));
+}
+
+extern "C" size_t ff_decode_sequence_constrained_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples) {
+  if (num_samples < 1 || num_samples > 64 || !sequence_query_ok(p)) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_CONSTRAIN_SAMPLE, num_samples));
+}
+
+// R draws per wireframe of the single-sequence decode (model.py:161-167, 191, 193-210) from the row the face-loop rule leaves.
+extern "C" int ff_decode_sequence_constrained_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                                     const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done,
+                                                     int* step_counts, float* trace_logits, int* seq_of_row, void* workspace,
+                                                     size_t workspace_bytes, const ff_sequence_constrain_sample_params* cs,
+                                                     ff_stream_t stream) {
+  const char* name = "ff_decode_sequence_constrained_sample";
+  FF_RETURN_IF(check_sequence(name, "constrain sample", "ff_decode_constrained_sample", m, p, cs));
+  FF_CHECK_ARG(cs->num_samples >= 1 && cs->num_samples <= 64, "%s: num_samples=%d outside 1..64", name, cs->num_samples);
+  FF_RETURN_IF(ff_sequence_rule_check(name, ff_loop_rule_io{cs->follows, p->L, cs->flags, m->num_token}, p->L + m->num_token, cs->tok_sep,
+                                      p->tok_eos));
+  FF_CHECK_ARG(cs->uniforms && cs->samples && cs->logprob && cs->scores && cs->dead_end && cs->open_end && cs->predict_logprob &&
+                   cs->predict_dead_end && cs->predict_open_end && predict,
+               "%s: uniforms, samples, logprob, scores, dead_end, open_end, the three predict_ outputs and predict are required", name);
+  FF_CHECK_ARG(p->N > 0 && (long long)p->N * cs->num_samples < (1LL << 31), "%s: bad sizes", name);
+  const int rows = p->N * cs->num_samples;   // (the draw's own check, with the step's text: the uniforms of one step)
+  FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{cs->uniforms, rows, nullptr, cs->temperature, cs->top_k, cs->top_p}, rows));
+  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
+                      stream, Mode(Mode::SEQ_CONSTRAIN_SAMPLE, cs->num_samples, cs));
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {

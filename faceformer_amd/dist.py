@@ -222,6 +222,9 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
     for mode in _modes.SEQUENCE_MODES:
         if mode.switches[0].on(model):
             raise ValueError("decode_sharded does not implement %s (%s)" % (mode.subject, mode.switches[0].sharded))
+    if getattr(model, "sequence_constrain_samples", 0):     # (an option of sequence_constrain, which is not taken here either)
+        raise ValueError("decode_sharded does not implement sequence_constrain_samples (%s)"
+                         % _modes.SEQUENCE_CONSTRAIN_SAMPLE.switches[0].sharded)
     if getattr(model, "constrain_samples", 0):
         raise ValueError("decode_sharded does not implement constrain_samples (%s)" % _modes.SWITCH["constrain"].sharded)
     for mode in reversed(_modes.MODES):

@@ -27,7 +27,8 @@ __all__ = ["parse_parallel_faces", "retired_view", "parse_faces", "unique_faces_
            "parse_parallel_samples_scored", "parse_parallel_constrained_samples_scored", "follow_table", "pack_follow_bits", "follow_distance", "closure_distance",
            "face_rows", "face_votes", "faces_of_rows", "parse_faces_samples_scored", "parse_faces_beams_scored",
            "face_seq_rows", "face_seq_votes", "faces_of_seq_rows",
-           "sequence_rule_start", "sequence_rule_advance", "sequence_rule_mask", "sequence_rule_step"]
+           "sequence_rule_start", "sequence_rule_advance", "sequence_rule_mask", "sequence_rule_step",
+           "sequence_rule_sample_step", "parse_faces_constrained_samples_scored"]
 
 
 def _tok(token, name, default):
@@ -234,6 +235,36 @@ def parse_faces_samples_scored(samples, logprobs, num_edges, token):
             key = tuple(sorted(set(idx)))
             if key not in best or score > best[key][2]:
                 best[key] = (ftype, best[key][1] if key in best else idx, score)
+        faces.extend(best.values())
+    return faces
+
+
+def parse_faces_constrained_samples_scored(samples, logprobs, dead_end, num_edges, token):
+    """The faces of a constrained sampled single-sequence decode (SurfaceFormer.sequence_constrain_samples): samples,
+    logprobs and dead_end [R, T] (predict_samples[w] / predict_sample_logprob[w] / predict_sample_dead_end[w]).
+    parse_faces_samples_scored with the faces abandoned at a dead end left out -- a piece whose SEP carries the dead-end flag
+    ends in a separator the rule opened for want of an edge: its loop is open.  Returns [(0, (edge, ...), score)] in draw order;
+    unique_faces_with_scores then gives every face's best score and the number of DRAWS that produced it."""
+    rows = np.asarray(samples, dtype=np.int64)
+    lps = np.asarray(logprobs, dtype=np.float64)
+    dead = np.asarray(dead_end) != 0
+    if rows.ndim != 2 or lps.shape != rows.shape or dead.shape != rows.shape:
+        raise ValueError("samples, logprobs and dead_end must all be [R, T]")
+    eos, sep, ntok = _tok(token, "EOS", 3), _tok(token, "SEP", 2), _tok(token, "len", 4)
+    faces = []
+    for row, lp, de in zip(rows, lps, dead):
+        seq = _prefix_through_first(row, row == eos)
+        cuts = np.flatnonzero(seq == sep) + 1
+        best = {}      # (insertion-ordered: the first place of every edge set in this draw)
+        for piece, plp, pde in zip(np.split(seq, cuts), np.split(lp[: seq.size], cuts), np.split(de[: seq.size], cuts)):
+            if piece.size <= 1 or pde[-1]:
+                continue
+            idx = _edge_indices(piece[:-1], ntok, num_edges)
+            if not idx:
+                continue
+            key, score = tuple(sorted(set(idx))), float(plp.sum())
+            if key not in best or score > best[key][2]:
+                best[key] = (0, best[key][1] if key in best else idx, score)
         faces.extend(best.values())
     return faces
 
@@ -594,6 +625,46 @@ def sequence_rule_step(raw, pad, state, flags, ntok, sep, eos, follows=None, fin
     row = np.where(masked | pad, SEQ_FILL, raw)
     tok = int(np.argmax(row))                    # (lowest index on ties)
     lp = -float(np.log(np.exp(row - row[tok]).sum()))
+    return dict(tok=tok, logprob=lp, row=row, masked=masked, dead=dead, fin=tok == eos,
+                state=sequence_rule_advance(state, tok, flags, ntok, sep, follows))
+
+
+def sequence_rule_sample_step(raw, pad, state, flags, ntok, sep, eos, u, temperature=1.0, top_k=0, top_p=1.0, follows=None,
+                              finished=False):
+    """One row of one step of the sampled form (ff_pointer_sequence_constrained_sample) on RAW logits:
+    sequence_rule_mask's row, then the sampling rule of DESIGN.md 15 on it with the uniform u -- top-k and top-p act on the
+    constrained row, and at a dead end SEP, the only live key, is drawn whatever u is.  -> sequence_rule_step's dict.  logprob:
+    (l[tok] - max) - log sum exp(l - max) over the constrained row, fp64."""
+    raw = np.asarray(raw, dtype=np.float64)
+    S = len(raw)
+    if finished:
+        return dict(tok=0, logprob=0.0, row=raw, masked=np.zeros(S, bool), dead=False, fin=True, state=state)
+    pad = np.asarray(pad, dtype=bool)
+    masked, dead = sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad)
+    row = np.where(masked | pad, SEQ_FILL, raw)
+    live = row > SEQ_FILL
+    m = row.max()
+    if not live.any():
+        tok, lp = 0, -float(np.log(S))
+    else:
+        if temperature == 0:
+            tok = int(np.argmax(row))                # (lowest index on ties)
+        else:
+            w = np.where(live, np.exp(np.where(live, (row - m) / temperature, 0.0)), 0.0)
+            kept = live.copy()
+            if 0 < top_k < int(live.sum()):
+                kept &= row >= np.sort(row[live])[::-1][top_k - 1]
+            if top_p < 1:
+                vals = np.unique(row[kept])[::-1]
+                cum = np.array([w[kept & (row >= v)].sum() for v in vals])
+                hit = cum >= top_p * w[kept].sum()
+                kept &= row >= vals[int(np.argmax(hit)) if hit.any() else len(vals) - 1]
+            idx = np.flatnonzero(kept)
+            c = np.cumsum(w[idx])
+            uu = min(max(float(u) if u == u else 0.0, 0.0), 1.0 - 2.0 ** -24)
+            over = np.flatnonzero(c > uu * c[-1])
+            tok = int(idx[over[0]]) if over.size else int(idx[-1])
+        lp = max(float((row[tok] - m) - np.log(np.exp(row - m).sum())), SEQ_FILL)
     return dict(tok=tok, logprob=lp, row=row, masked=masked, dead=dead, fin=tok == eos,
                 state=sequence_rule_advance(state, tok, flags, ntok, sep, follows))
 

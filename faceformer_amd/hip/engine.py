@@ -376,7 +376,7 @@ class PathEngine:
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
                constrain_samples=None, constrain_beam_closure=None, sequence_samples=None, sequence_beams=None,
-               sequence_beam_stop="all", sequence_constrain=None, tok_sep=None):
+               sequence_beam_stop="all", sequence_constrain=None, tok_sep=None, sequence_constrain_samples=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -474,7 +474,19 @@ class PathEngine:
         also `logprob` [N, T] fp32 (under the renormalised distribution), `dead_end` [N, T] int32 (1 where the SEP was selected at
         a dead end) and `open_end` [N] int32 (a loop is open after the last kept position); with trace=True `logits` [T-1, N, S]
         holds the constrained masked rows.  No term_range.  Excludes every other mode and option above, and stop_each_eos.  Bits
-        0 equal the greedy FF_STOP_EACH_EOS decode cut behind every row's first EOS, with logprob=True's log-probabilities."""
+        0 equal the greedy FF_STOP_EACH_EOS decode cut behind every row's first EOS, with logprob=True's log-probabilities.
+
+        sequence_constrain_samples=R in 1..64 (only with sequence_constrain, not with sequence_samples or sequence_beams;
+        ff_decode_sequence_constrained_sample; None or 0: the sequence_constrain decode above): R independent draws
+        per WIREFRAME from the CONSTRAINED row under temperature / top_k / top_p, driven by `uniforms` [T-1, N*R] as
+        sequence_samples' are; every draw carries its own state of the rule and is finished by its own EOS.  Also `samples`
+        [N*R, T] int64 (row w*R + k is draw k of wireframe w), `sample_logprob` (same layout: the log-probability under the model
+        renormalised over the keys the rule allows), `sample_scores` [N*R], `sample_dead_end` [N*R, T] int32 and `sample_open_end`
+        [N*R] int32; `predict`, `logprob`, `dead_end` and `open_end` are draw 0; with trace=True `logits` [T-1, N*R, S] holds the
+        constrained masked rows.  temperature=0 equals the sequence_constrain decode, R times; flag bits 0 equal the
+        sequence_samples decode."""
+        SCS = _modes.sequence_constrain_samples_value(sequence_constrain_samples, _modes.sequence_constrain_flags(sequence_constrain),
+                                                      sequence_samples, sequence_beams) if sequence_constrain_samples else 0
         seq = dict(sequence_samples=sequence_samples, sequence_beams=sequence_beams, sequence_constrain=sequence_constrain)
         for mode in reversed(_modes.SEQUENCE_MODES):      # (of several set together, the last one's record reports)
             value = mode.sequence.value(seq[mode.subject])
@@ -485,6 +497,8 @@ class PathEngine:
                          sequence_beam_stop=sequence_beam_stop, follow_table=follow_table, tok_sep=tok_sep, tok_eos=tok_eos,
                          trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
                 o[mode.subject] = value
+                if SCS:      # (an option of sequence_constrain, the first record this loop looks at)
+                    mode, o["sequence_constrain_samples"] = _modes.SEQUENCE_CONSTRAIN_SAMPLE, SCS
                 return self._decode_sequence(mode, memory, mask_u8, kv_len, variant, o,
                                              (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs, num_streams,
                                               chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows), sync_every, tok_sos)

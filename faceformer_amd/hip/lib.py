@@ -197,6 +197,13 @@ class SequenceConstrainParams(C.Structure):
     _fields_ = [("flags", C.c_int), ("follows", fptr), ("tok_sep", C.c_int), ("logprob", fptr), ("dead_end", fptr), ("open_end", fptr)]
 
 
+class SequenceConstrainSampleParams(C.Structure):
+    _fields_ = [("num_samples", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("uniforms", fptr),
+                ("flags", C.c_int), ("follows", fptr), ("tok_sep", C.c_int), ("samples", fptr), ("logprob", fptr), ("scores", fptr),
+                ("dead_end", fptr), ("open_end", fptr), ("predict_logprob", fptr), ("predict_dead_end", fptr),
+                ("predict_open_end", fptr)]
+
+
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
 FF_CONSTRAIN_ONCE = 4         # ff_pointer_sequence_constrained / ff_decode_sequence_constrained only
@@ -375,6 +382,14 @@ SIGNATURES = {
     "ff_decode_sequence_constrained": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr, C.POINTER(C.c_int),
                                                  C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t, C.POINTER(SequenceConstrainParams),
                                                  fptr]),
+    "ff_pointer_sequence_constrained_sample": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int,
+                                                         C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                                         fptr, fptr, fptr, C.c_int, fptr, C.c_int, fptr, fptr, fptr, C.c_int, fptr,
+                                                         C.c_float, C.c_int, C.c_float, fptr]),
+    "ff_decode_sequence_constrained_sample_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
+    "ff_decode_sequence_constrained_sample": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                                        C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
+                                                        C.POINTER(SequenceConstrainSampleParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
     "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
                                fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
@@ -413,7 +428,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows and *_sequence_constrained ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows, *_sequence_constrained and *_sequence_constrained_sample ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

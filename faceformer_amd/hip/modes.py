@@ -635,6 +635,67 @@ SEQUENCE_CONSTRAIN = Mode(
     sequence=Sequence(sequence_constrain_flags, ("constrains", "constrain"), "the loop rule per face of the single-sequence model's row",
                       "row", _sequence_constrain_model_values, "last_constrain_stats", _sequence_constrain_early))
 
+def sequence_constrain_samples_value(sequence_constrain_samples, flags, sequence_samples=0, sequence_beams=0):
+    """The count of a `sequence_constrain_samples` value: None / 0 -> 0 (the option is off); else 1..SAMPLE_MAX,
+    only with `sequence_constrain` set (`flags`: sequence_constrain_flags of it) and not with sequence_samples or sequence_beams."""
+    if sequence_constrain_samples is None or (not isinstance(sequence_constrain_samples, bool) and sequence_constrain_samples == 0):
+        return 0
+    if isinstance(sequence_constrain_samples, bool) or not isinstance(sequence_constrain_samples, int) \
+            or not 1 <= sequence_constrain_samples <= SAMPLE_MAX:
+        raise ValueError("sequence_constrain_samples=%r: must be None, 0 or a count in 1..%d" % (sequence_constrain_samples, SAMPLE_MAX))
+    if flags is None:
+        raise ValueError("sequence_constrain_samples=%d needs sequence_constrain ('no_repeat', 'loops' or 'coedge_loops'): it is the "
+                         "sampling over the keys the face-loop rule allows" % sequence_constrain_samples)
+    if sequence_samples or sequence_beams:
+        raise ValueError("sequence_constrain_samples excludes sequence_samples and sequence_beams: they draw from / search the "
+                         "unconstrained row")
+    return int(sequence_constrain_samples)
+
+
+def _sequence_constrain_sample_values(o):
+    """sequence_constrain's value check and the sampled decode's on the count and the parameters."""
+    R = o["sequence_constrain_samples"]
+    if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= SAMPLE_MAX:
+        raise ValueError("sequence_constrain_samples=%r: must be in 1..%d" % (R, SAMPLE_MAX))
+    _sample_values(dict(o, num_samples=R))      # (temperature, top_k, top_p: the sampled decode's text)
+    _sequence_constrain_values(o)
+
+
+def _sequence_constrain_sample_operand(eng, o):
+    _constrain_operand(eng, o)
+    _sample_operand(eng, dict(o, F=1, num_samples=o["sequence_constrain_samples"]))
+
+
+def _sequence_constrain_sample_model_values(m, R, inputs):
+    _sample_values(dict(num_samples=R, temperature=m.sample_temperature, top_k=m.sample_top_k, top_p=m.sample_top_p))
+    u = inputs.get("sample_uniforms")
+    shape = (max(m.num_labels - 1, 1), inputs["input"].size(0) * R)
+    if u is not None and tuple(torch.as_tensor(u).shape) != shape:
+        raise ValueError("sample_uniforms must have shape [%d, %d]" % shape)
+
+
+# sequence_constrain with its option sequence_constrain_samples = R (DESIGN.md 33): R draws per wireframe from the row the
+# face-loop rule leaves.  Outside SEQUENCE_MODES (and MODES), as CONSTRAIN_SAMPLE is outside MODES: the option that switches the
+# mode on stays `sequence_constrain`, whose record reports every error without the option -- sequence_constrain with
+# sequence_samples stays the recorded refusal it is.  The outputs: the draws, and draw 0 under sequence_constrain's own keys.
+SEQUENCE_CONSTRAIN_SAMPLE = SEQUENCE_CONSTRAIN._replace(
+    subject="sequence_constrain_samples", entry="ff_decode_sequence_constrained_sample", per_anchor=True,
+    values=_sequence_constrain_sample_values, operand=_sequence_constrain_sample_operand,
+    own=(("follow_table", _I32), ("uniforms", _F32)),
+    outs=(("samples", "GT", _I64), ("sample_logprob", "GT", _F32), ("sample_scores", "G", _F32), ("sample_dead_end", "GT", _I32),
+          ("sample_open_end", "G", _I32)) + SEQUENCE_CONSTRAIN.outs,
+    tail=lambda o, ptrs, traced: (C.byref(_L.SequenceConstrainSampleParams(
+        o["sequence_constrain_samples"], float(o["temperature"]), int(o["top_k"]), float(o["top_p"]), _p(o["uniforms"]),
+        o["sequence_constrain"], _p(o["follow_table"]), int(o["tok_sep"]), *ptrs)),),
+    # (batch order, as the two records it combines: column w*R + k of the uniforms is draw k of wireframe w as given)
+    prepare=lambda m, R, inputs, dev, T, N, F, ni, order: dict(
+        SEQUENCE_CONSTRAIN.prepare(m, sequence_constrain_flags(m.sequence_constrain), inputs, dev, T, N, F, ni, order),
+        sequence_constrain_samples=R, temperature=float(m.sample_temperature), top_k=int(m.sample_top_k), top_p=float(m.sample_top_p),
+        uniforms=m._sample_uniforms(inputs, dev, T, N, F, R, order)),
+    sequence=SEQUENCE_CONSTRAIN.sequence._replace(parallel_has=("draws under the rule", "constrain_samples"), each="draw",
+                                                  model_has="draws per wireframe under the loop rule of the single-sequence model's row",
+                                                  model_values=_sequence_constrain_sample_model_values))
+
 # in the order the refusals name them; of several set together, decode() lets the last one's record report, SurfaceFormer the
 # first of SEQUENCE_MODEL_ORDER that is on (a record excludes every record before it in SEQUENCE_MODES, by its option's name)
 SEQUENCE_MODES = (SEQUENCE_SAMPLE, SEQUENCE_BEAM, SEQUENCE_CONSTRAIN)

@@ -649,6 +649,28 @@ def pointer_sequence_constrained(logits, fin, first, prev, visited, flags, ntok,
     with NO_REPEAT) among the flags.  SEP ends the current face (first = prev = none; the returned visited words are cleared
     unless ONCE), EOS alone finishes the row, a dead end re-opens SEP alone and the row goes on.  counter (optional, [1] int32)
     += the rows unfinished after the step.  Returns pointer_constrained's dict; dead_end is this step's flag."""
+    return _sequence_constrained_step(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows, memory, mask, kv_len,
+                                      seqs_per_group, want_rows, want_stats, counter, None)
+
+
+@_on_tensor_device
+def pointer_sequence_constrained_sample(logits, uniforms, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows=None,
+                                        temperature=1.0, top_k=0, top_p=1.0, row_id=None, memory=None, mask=None, kv_len=None,
+                                        seqs_per_group=1, want_rows=False, want_stats=False, counter=None):
+    """One constrained sampling step of the single-sequence model (ff_pointer_sequence_constrained_sample):
+    pointer_sequence_constrained's byte row and state update with pointer_sample's draw from the constrained masked row in place
+    of the argmax: uniforms [U] fp32, row b reads uniforms[row_id[b]] (None: b).  Returns pointer_sequence_constrained's dict;
+    logprob is (l[next] - max) - log sum exp(l - max) over the constrained row.  temperature=0 is pointer_sequence_constrained's
+    step, bit for bit; flags=0 is pointer_sequence_sample's with term_range = (tok_eos, tok_eos + 1)."""
+    return _sequence_constrained_step(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows, memory, mask, kv_len,
+                                      seqs_per_group, want_rows, want_stats, counter, (uniforms, row_id, temperature, top_k, top_p))
+
+
+def _sequence_constrained_step(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows, memory, mask, kv_len,
+                               seqs_per_group, want_rows, want_stats, counter, draw):
+    """pointer_sequence_constrained (draw None) and pointer_sequence_constrained_sample (draw = (uniforms, row_id, temperature,
+    top_k, top_p)): the checks, the outputs and the launch the two share."""
+    _dev(logits, "logits")
     out = {}
     B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
     flags, ntok, sep, eos = int(flags), int(ntok), int(tok_sep), int(tok_eos)
@@ -684,11 +706,36 @@ def pointer_sequence_constrained(logits, fin, first, prev, visited, flags, ntok,
     one = torch.zeros(1, device=dev, dtype=torch.int32)   # (L = 0: one word each so that the pointers are not null)
     vis = visited if fw else one
     fol = one if (follows is not None and not (L and fw)) else follows
-    _L.check(_L.load().ff_pointer_sequence_constrained(
+    entry, tail = "ff_pointer_sequence_constrained", ()
+    if draw is not None:
+        d = _draw_operands(draw, B)      # (`d` keeps a contiguous copy of row_id alive over the call)
+        entry, tail = "ff_pointer_sequence_constrained_sample", (_p(d[0]), d[1], _p(d[2])) + d[3:]
+    _L.check(getattr(_L.load(), entry)(
         _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(fol), L, flags, ntok, sep, eos, _p(fin), _p(first),
         _p(prev), _p(vis), _p(out["mask_rows"]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(out["dead_end"]),
-        _p(out["first"]), _p(out["prev"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter), _stream()), "ff_pointer_sequence_constrained")
+        _p(out["first"]), _p(out["prev"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter), *tail, _stream()), entry)
     return out
+
+
+def _draw_operands(draw, B):
+    """The checks of a step's draw = (uniforms, row_id, temperature, top_k, top_p) for B launch rows -> (uniforms, U, row_id made contiguous or
+    None, temperature, top_k, top_p): the entry's arguments, the two tensors still to be taken the address of."""
+    uniforms, row_id, temperature, top_k, top_p = draw
+    _dev(uniforms, "uniforms")
+    if uniforms.dim() != 1 or not uniforms.is_contiguous() or uniforms.numel() < 1:
+        raise ValueError("uniforms must be a contiguous non-empty 1-D tensor")
+    U = uniforms.numel()
+    t, k, pp = float(temperature), int(top_k), float(top_p)
+    if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
+        raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]")
+    if row_id is not None:
+        _dev(row_id, "row_id", torch.int32)
+        if row_id.dim() != 1 or row_id.numel() != B or (B and (int(row_id.min()) < 0 or int(row_id.max()) >= U)):
+            raise ValueError("row_id must hold one index in [0, %d) per row of logits" % U)
+        row_id = row_id.contiguous()
+    elif U < B:
+        raise ValueError("%d uniforms for %d rows" % (U, B))
+    return (uniforms, U, row_id, t, k, pp)
 
 
 def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, memory, mask, kv_len, seqs_per_group, term_range,
@@ -739,24 +786,10 @@ def _constrained_step(logits, fin, first, prev, visited, flags, ntok, follows, m
         form, close_dist, cycle_len, budget = _lookahead_operands(ahead, flags, S, L, nw, dev, what)
         entry, tail = "ff_" + what, ((_p(close_dist),) if form == 1 else ()) + (_p(cycle_len), budget)
     if draw is not None:
-        uniforms, row_id, temperature, top_k, top_p = draw
-        _dev(uniforms, "uniforms")
-        if uniforms.dim() != 1 or not uniforms.is_contiguous() or uniforms.numel() < 1:
-            raise ValueError("uniforms must be a contiguous non-empty 1-D tensor")
-        U = uniforms.numel()
-        t, k, pp = float(temperature), int(top_k), float(top_p)
-        if not (0.0 <= t < float("inf")) or k < 0 or not (0.0 < pp <= 1.0):
-            raise ValueError("sampling needs a finite temperature >= 0, top_k >= 0 and top_p in (0, 1]")
-        if row_id is not None:
-            _dev(row_id, "row_id", torch.int32)
-            if row_id.dim() != 1 or row_id.numel() != B or (B and (int(row_id.min()) < 0 or int(row_id.max()) >= U)):
-                raise ValueError("row_id must hold one index in [0, %d) per row of logits" % U)
-            row_id = row_id.contiguous()
-        elif U < B:
-            raise ValueError("%d uniforms for %d rows" % (U, B))
+        d = _draw_operands(draw, B)      # (`d` keeps a contiguous copy of row_id alive over the call)
         form = {"ff_pointer_constrained": 0, "ff_pointer_constrained_ahead": 1, "ff_pointer_constrained_exact": 2}[entry]
         tables = {0: (None, None, 0), 1: tail, 2: (None,) + tail}[form]      # (close_dist, cycle_len, budget)
-        entry, tail = "ff_pointer_constrained_sample", (_p(uniforms), U, _p(row_id), t, k, pp, form) + tuple(tables)
+        entry, tail = "ff_pointer_constrained_sample", (_p(d[0]), d[1], _p(d[2])) + d[3:] + (form,) + tuple(tables)
     _L.check(getattr(_L.load(), entry)(
         _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(fol), L, flags, ntok, lo, hi, _p(fin), _p(first),
         _p(prev), _p(vis), _p(out["mask_rows"]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(out["dead_end"]),

@@ -68,6 +68,14 @@ class SurfaceFormer(SurfaceFormerBase):
         loop is open after the last kept position); embedding as above; no pointer.  Not with sequence_samples, sequence_beams,
         return_logprob, an extra mask, stop_each_eos = True or the sub-module loop (ValueError).
 
+        sequence_constrain_samples = R in 1..64 (only with sequence_constrain; 0: the decode above): R independent
+        draws per wireframe from the row the rule leaves, under sample_temperature / sample_top_k / sample_top_p and with the
+        uniforms of sequence_samples (sample_seed, or inputs["sample_uniforms"] [T-1, N*R]).  Every draw carries its own state of
+        the rule and is finished by its own EOS.  Adds predict_samples, predict_sample_logprob, predict_sample_dead_end N x R x T,
+        predict_sample_scores, predict_sample_open_end N x R; predict, predict_logprob, predict_dead_end and predict_open_end are
+        draw 0; embedding as above; no pointer.  Refused wherever sequence_constrain is, and with sequence_samples or
+        sequence_beams (ValueError).
+
         sequence_faces = "parse" / "enclosed" (default False): also inputs["sequence_faces"], a dict of device
         tensors -- len, start, type, closed, loops, score, dup_of, take, row_best, rep, votes, best, major N x G x P, edges, loop_of
         N x G x T, set_bits N x G x P x ceil(L/32), count N x G, num_faces N -- made by two launches behind the decode from the rows
@@ -174,6 +182,13 @@ class SurfaceFormer(SurfaceFormerBase):
                 raise ValueError("%s excludes %s and %s" % (sw.attr, ", ".join(mode.model_excludes[:-1]), mode.model_excludes[-1]))
             mode.sequence.model_values(self, value, inputs)
             found = (mode, value)
+        # sequence_constrain's option: read behind the recorded refusals above, which keep their texts
+        R = _modes.sequence_constrain_samples_value(getattr(self, "sequence_constrain_samples", 0),
+                                                    found[1] if found[0] is _modes.SEQUENCE_CONSTRAIN else None,
+                                                    getattr(self, "sequence_samples", 0), getattr(self, "sequence_beams", 0))
+        if R:
+            found = (_modes.SEQUENCE_CONSTRAIN_SAMPLE, R)
+            found[0].sequence.model_values(self, R, inputs)
         return found
 
     def _forward_eval_sequence(self, inputs, eng, memory, mask, kv_len, T, mode, value, G):

@@ -1557,6 +1557,80 @@ int ff_decode_sequence_constrained(const ff_model* m, const ff_decode_params* p,
                                    void* workspace, size_t workspace_bytes, const ff_sequence_constrain_params* constrain,
                                    ff_stream_t stream);
 
+/* ---- sampling over the loop-constrained single-sequence decode (opt-in, FF_SEQ2SEQ; entries added within ABI 105) --
+ * The single-sequence reference decodes ONE greedy sequence per wireframe: select_next takes the argmax of the masked logit row
+ * (model.py:161-167) inside the loop of model.py:193-210, which starts every sequence from SOS (model.py:191).  These entries
+ * restate those call sites with the TWO changes of the sections above together: the row is masked by
+ * ff_pointer_sequence_constrained's rule (unchanged: one copy in device code) and the token is DRAWN from that row by
+ * ff_decode_sample's rule (steps 1-7, unchanged, bit for bit: one copy in device code); the loop carries num_samples = R
+ * independent draws per wireframe off one encoding and one set of cross-attention K | V.  No closure look-ahead.
+ *
+ * Layout.  ff_decode_sequence_sample's: N*R sequences, draw k of wireframe w is output row w*R + k, w = b / R.
+ * State.  Every draw carries its own (visited, first, prev), finished flag and per-position dead-end flag, and starts at tok_sos
+ *   with the rule's empty, closed state.
+ * A step of an unfinished draw:
+ *   1. the byte row of ff_pointer_sequence_constrained's rule (open: special tokens masked, SEP alone re-opened on a dead end;
+ *      closed: EOS opened, SEP masked while the face has no edge; ONCE keeps visited across SEP);
+ *   2. the logit row is masked and reduced with that byte row as the extra mask;
+ *   3. the token is drawn from the masked row: top-k and top-p act on the constrained row, and on a dead end the draw is SEP,
+ *      the only live key;
+ *   4. logprob = (l[tok] - m) - log sum exp(l - m) over the constrained row, saturated at -FLT_MAX: the model's distribution
+ *      renormalised over the keys the rule allows (ff_pointer_constrained_sample's expression; with temperature 0 it is
+ *      ff_pointer_sequence_constrained's -log sum, bit for bit);
+ *   5. the state update of ff_pointer_sequence_constrained.
+ * Finish and stop.  Own EOS finishes a draw; a finished draw appends 0 with log-probability 0.  Stop, *steps_done, step_counts
+ *   ("draws unfinished after the step") and the zero padding are ff_decode_sequence_sample's.
+ * Identities.  Temperature 0, any R: every draw is the ff_decode_sequence_constrained decode with the same flags.  All flag bits
+ *   clear: the ff_decode_sequence_sample decode with the same uniforms and parameters (the byte rows are zero).
+ *
+ * ff_pointer_sequence_constrained_sample: one step of B sequences; ff_pointer_sequence_constrained's arguments, then the draw's
+ *   (uniforms [num_uniforms] of this step, row_id [B] or NULL: launch row b reads uniforms[row_id[b]], temperature, top_k, top_p:
+ *   ff_pointer_sample's).
+ * ff_decode_sequence_constrained_sample: ff_decode_sequence_sample's argument list; predict [N, T] int64 is draw 0; then
+ *   ff_sequence_constrain_sample_params: num_samples, temperature, top_k, top_p, uniforms [max(T-1, 1), N*R] fp32 DEVICE; flags,
+ *   follows, tok_sep as ff_sequence_constrain_params; samples [N*R, T] int64, logprob [N*R, T] fp32, scores [N*R] fp32 (the kept
+ *   log-probabilities added in ascending position, fp64 accumulator, rounded once, saturated), dead_end [N*R, T] int32, open_end
+ *   [N*R] int32; draw 0 under ff_sequence_constrain_params' keys: predict_logprob [N, T], predict_dead_end [N, T],
+ *   predict_open_end [N].  trace_logits (optional) [T-1, N*R, S] indexed by decoded sequence (seq_of_row [N*R]): the CONSTRAINED
+ *   masked row of every draw unfinished before the step.  A micro-batch holds chunk_max_seqs / R wireframes (at least one).
+ * FF_ERR_ARG before any launch, every output untouched, for everything ff_decode_sequence_sample and
+ * ff_decode_sequence_constrained refuse, for num_samples outside 1..64 and for a NULL output.
+ * ff_decode_sequence_constrained_sample_workspace_bytes: ff_decode_sequence_constrained's records per sequence of the
+ * sequence-sampled plan, plus row_id; the visited words and the byte rows last (0 for what the entry refuses).  Every other entry
+ * launches and lays out what it did before these. */
+int ff_pointer_sequence_constrained_sample(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                           int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok, int tok_sep,
+                                           int tok_eos, const int* fin_in, const int* first_in, const int* prev_in,
+                                           unsigned int* visited, unsigned char* mask_rows, int* next_tok, float* logprob,
+                                           int* fin_out, int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
+                                           float* next_rows, int ldnext, float* next_stats, int* count_unfinished,
+                                           const float* uniforms, int num_uniforms, const int* row_id, float temperature, int top_k,
+                                           float top_p, ff_stream_t stream);
+typedef struct ff_sequence_constrain_sample_params {
+  int num_samples;
+  float temperature;
+  int top_k;
+  float top_p;
+  const float* uniforms;
+  int flags;
+  const unsigned int* follows;
+  int tok_sep;
+  int64_t* samples;
+  float* logprob;
+  float* scores;
+  int* dead_end;
+  int* open_end;
+  float* predict_logprob;
+  int* predict_dead_end;
+  int* predict_open_end;
+} ff_sequence_constrain_sample_params;
+size_t ff_decode_sequence_constrained_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples);
+int ff_decode_sequence_constrained_sample(const ff_model* m, const ff_decode_params* p,
+                                          const float* memory, const unsigned char* mask, const int* kv_len,
+                                          int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
+                                          void* workspace, size_t workspace_bytes,
+                                          const ff_sequence_constrain_sample_params* constrain_sample, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

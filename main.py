@@ -171,7 +171,7 @@ def score_batch(model, batch):
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
               constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None, sequence_beams=None,
-              sequence_device_faces=None, sequence_constrained=None):
+              sequence_device_faces=None, sequence_constrained=None, sequence_constrained_samples=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -209,7 +209,12 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     (faces.faces_of_seq_rows) instead of from pred, the draws and the beams, which are then not read.
     sequence_constrained (--sequence-constrain, single-sequence model; the dead-end flags [T] of this sample's row): the record
     also gets `pred_dead_ends`, the number of faces the constrained decode abandoned at a dead end (the sum of the row's flags),
-    and `pred_unclosed`, the number of parsed faces that do not pass the enclosure walk."""
+    and `pred_unclosed`, the number of parsed faces that do not pass the enclosure walk.
+    sequence_constrained_samples (--sequence-constrain-samples, single-sequence model; (tokens [R, T], log-probabilities [R, T],
+    dead-end flags [R, T]) of this sample): the record also gets `pred_sample_faces`, `pred_sample_face_scores` and
+    `pred_sample_face_votes` as under --sequence-samples, over the faces that were not abandoned at a dead end
+    (faces.parse_faces_constrained_samples_scored); `pred_faces` stays what draw 0 (pred) gives, and `pred_dead_ends` /
+    `pred_unclosed` are counted over ALL draws."""
     if sequence_device_faces is not None:
         return _record_of_sequence_device(cfg, raw, item, sequence_device_faces, logprob is not None, sequence_beams is not None,
                                           sequence_samples is not None)
@@ -303,6 +308,17 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["pred_dead_ends"] = int(np.asarray(sequence_constrained).astype(bool).sum())
         rec["pred_unclosed"] = sum(1 for _, idx in own
                                    if not FZ.is_face_enclosed(raw["edges"], idx, cfg.post_process.enclosedness_tol))
+    if sequence_constrained_samples is not None:
+        toks, lps, dead = (np.asarray(v) for v in sequence_constrained_samples)
+        sf = FZ.parse_faces_constrained_samples_scored(toks, lps, dead, len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(sf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_sample_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_sample_face_scores"] = [s for _, _, s, _ in ranked]
+        rec["pred_sample_face_votes"] = [int(v) for _, _, _, v in ranked]
+        own = [f for row in toks for f in FZ._seq_faces(row, cfg.model.token, len(raw["edges"]), True)]
+        rec["pred_dead_ends"] = int(dead.astype(bool).sum())
+        rec["pred_unclosed"] = sum(1 for _, idx in own
+                                   if not FZ.is_face_enclosed(raw["edges"], idx, cfg.post_process.enclosedness_tol))
     if sequence_beams is not None:
         bf = FZ.parse_faces_beams_scored(sequence_beams[0], sequence_beams[1], sequence_beams[2], len(raw["edges"]), cfg.model.token)
         ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
@@ -386,7 +402,7 @@ def _record_of_sequence_device(cfg, raw, item, rows, scored, beams, samples):
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
                     constrain_samples=0, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0, sequence_beam_stop="all",
-                    sequence_constrain=None):
+                    sequence_constrain=None, sequence_constrain_samples=0):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
@@ -398,7 +414,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     "exact"), `sequence_samples` draws per wireframe of the single-sequence model under temperature / top_k / top_p /
     seed, beam search with `sequence_beams` beams per wireframe of the single-sequence model under the stop rule
     `sequence_beam_stop`, the loop-constrained greedy decode of the single-sequence model (sequence_constrain
-    "no_repeat" / "loops" / "coedge_loops" with the end-point tolerance constrain_tol).
+    "no_repeat" / "loops" / "coedge_loops" with the end-point tolerance constrain_tol), `sequence_constrain_samples`
+    draws per wireframe from the keys that rule allows under temperature / top_k / top_p / seed.
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -439,6 +456,10 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.sequence_constrain = str(sequence_constrain)
         if constrain_tol is not None:
             model.constrain_tol = float(constrain_tol)
+    if sequence_constrain_samples:
+        model.sequence_constrain_samples = int(sequence_constrain_samples)
+        model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
+        model.sample_seed = int(seed)
     return model
 
 
@@ -446,7 +467,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
              constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0,
-             sequence_beam_stop="all", sequence_device_faces=False, sequence_constrain=None):
+             sequence_beam_stop="all", sequence_device_faces=False, sequence_constrain=None, sequence_constrain_samples=0):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -477,7 +498,22 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     made from those arrays -- the same records; sequence_constrain ("no_repeat" / "loops" / "coedge_loops", single-sequence model,
     single-rank runs only, not with scores, score_labels, sample, beam, constrain, sequence_samples, sequence_beams, device_faces
     or sequence_device_faces) decodes under the face-loop rule per face of the row with
-    cfg.post_process.enclosedness_tol as the end-point tolerance and adds pred_dead_ends / pred_unclosed."""
+    cfg.post_process.enclosedness_tol as the end-point tolerance and adds pred_dead_ends / pred_unclosed;
+    sequence_constrain_samples = R (1..64, only with sequence_constrain and refused with whatever it refuses, single-rank runs
+    only) draws R rows per wireframe from the keys that rule allows under temperature / top_k / top_p / seed and
+    adds pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes, with pred_dead_ends / pred_unclosed over all
+    draws; pred_faces stays draw 0's."""
+    if sequence_constrain_samples:
+        if isinstance(sequence_constrain_samples, bool) or not isinstance(sequence_constrain_samples, int) \
+                or not 1 <= sequence_constrain_samples <= 64:
+            raise ValueError("--sequence-constrain-samples must be a count in 1..64")
+        if cfg.model_class != "SurfaceFormer":
+            raise ValueError("--sequence-constrain-samples applies to SurfaceFormer only (SurfaceFormer_Parallel draws under its rule "
+                             "with --constrain-samples)")
+        if sequence_constrain is None:
+            raise ValueError("--sequence-constrain-samples requires --sequence-constrain")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--sequence-constrain-samples is not implemented for multi-rank runs")
     if sequence_constrain is not None:
         if sequence_constrain not in ("no_repeat", "loops", "coedge_loops"):
             raise ValueError("--sequence-constrain must be no_repeat, loops or coedge_loops")
@@ -575,6 +611,9 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
                     constrain_samples, constrain_beam_closure, sequence_samples, sequence_beams, sequence_beam_stop)
     if sequence_constrain:
         configure_model(model, sequence_constrain=sequence_constrain, constrain_tol=cfg.post_process.enclosedness_tol)
+    if sequence_constrain_samples:
+        configure_model(model, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                        sequence_constrain_samples=sequence_constrain_samples)
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
@@ -604,6 +643,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         wanted.append(("sequence_beams", ("predict_beams", "predict_beam_scores", "predict_beam_finished")))
     if sequence_constrain:
         wanted.append(("sequence_constrained", ("predict_dead_end",)))
+    if sequence_constrain_samples:
+        wanted.append(("sequence_constrained_samples", ("predict_samples", "predict_sample_logprob", "predict_sample_dead_end")))
     if device_faces:
         wanted.append(("device_faces", ("faces",)))
     if sequence_device_faces:
@@ -751,6 +792,13 @@ def build_parser():
                              "also never a co-edge an earlier face of the row holds; every JSON record gains pred_dead_ends / "
                              "pred_unclosed; single-process runs only, not with --scores, --score-labels, --sample, --beam, "
                              "--constrain, --sequence-samples, --sequence-beams, --device-faces or --sequence-device-faces")
+    parser.add_argument("--sequence-constrain-samples", type=int, default=0, metavar="R",
+                        help="with --sequence-constrain {no_repeat,loops,coedge_loops}: draw R (1..64) rows per wireframe from the keys "
+                             "the face-loop rule allows, under --temperature / --top-k / --top-p with uniforms from --seed "
+                             "(DESIGN.md 33); every JSON record gains pred_sample_faces / pred_sample_face_scores / "
+                             "pred_sample_face_votes (faces abandoned at a dead end left out), pred_dead_ends / pred_unclosed count "
+                             "over all draws, pred_faces stays draw 0's; single-process runs only, refused with whatever "
+                             "--sequence-constrain refuses")
     parser.add_argument("--constrain-beam-closure", choices=("lookahead", "exact"), default=None,
                         help="with --constrain loops --constrain-beams W: the beam search forms every beam's row under the closure "
                              "look-ahead (lookahead) or its exact form (exact), so that the W beams are searched among loops that "
@@ -780,7 +828,8 @@ def main(argv=None):
              constrain_samples=args.constrain_samples, device_faces=args.device_faces,
              constrain_beam_closure=args.constrain_beam_closure, sequence_samples=args.sequence_samples,
              sequence_beams=args.sequence_beams, sequence_beam_stop=args.sequence_beam_stop,
-             sequence_device_faces=args.sequence_device_faces, sequence_constrain=args.sequence_constrain)
+             sequence_device_faces=args.sequence_device_faces, sequence_constrain=args.sequence_constrain,
+             sequence_constrain_samples=args.sequence_constrain_samples)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
