@@ -217,6 +217,16 @@ int ff_sequence_constrain_sample_finalize(const int* tok, const float* lp, const
                                           float* scores, int* dead_end, int* open_end, int64_t* predict, float* predict_logprob,
                                           int* predict_dead_end, int* predict_open_end, int* seq_of_row, hipStream_t st);
 
+// Sequence-constrained beam decode (ff_constrain_seq.hip): `step` supplies the rule's and the beams' operands, io
+// the common ones (io.rows = groups * width); W beams per wireframe in the sequence beam decode's layout.
+int ff_beam_sequence_constrained_select_sync(const ff_step_io& io, const ff_beam_sequence_constrained_step* step, ff_stream_t stream);
+int ff_sequence_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* open, int* parent, int* first, int* prev,
+                                    unsigned* visited, int Bc, int W, int L, int sos, hipStream_t st);
+int ff_sequence_constrain_beam_finalize(const int* tok, const int* parent, const float* score, const int* fin, const int* dead,
+                                        const int* open, int Btot, int T, const int* steps_dev, int W, int w0, int nw, int b0,
+                                        int64_t* beams, float* scores, int* finished, int* beam_dead_end, int* beam_open_end,
+                                        int64_t* predict, int* dead_end, int* open_end, int* seq_of_row, hipStream_t st);
+
 // Constrained sampled decode (ff_constrain_sample.hip): the constrained step's operands and the draw's; R draws per
 // anchor in the sampled decode's layout, each with the constrained decode's state.
 int ff_pointer_constrained_sample_sync(const char* op, const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,

@@ -24,6 +24,16 @@
 // distribution renormalised over the keys the rule allows.  With temperature 0 the greedy expression -logf(lsum) stays, so
 // that the two forms agree bit for bit; with all flag bits clear the byte row is zero and the launch is
 // pointer_sample_kernel<true>'s.  Nothing of the rule or of the draw is restated; still no barrier and no further LDS.
+//
+// The beam form is a kernel of its own at the end of this file: beam_sequence_constrained_select_kernel<W, STOP>,
+// beam_constrained_select_kernel's shape (one wavefront per group, four per block) with this file's rule per beam.  For every
+// non-empty unfinished beam the wave writes the byte row as above through ff_sequence_write_row (ff_select.h: the plain rule with
+// [SEP, SEP + 1), then the two fix-ups of the closed state -- the kernel above keeps its own text of them, which is what keeps
+// its registers: DESIGN.md 33), masks and reduces the row, and keeps the W best LIVE keys at c_k + (l[s] - m) - log sum in ff_select.h's sorted list.  Lanes
+// 0..W-1 own one new beam each: parent, token, score, the finished flag, this step's dead-end flag, the loop-open flag and the
+// rule's update of the PARENT's (first, prev); the wave writes the W * fw words of visited_out from visited_in[parent] together.
+// All state is read from *_in and written to *_out.  STOP picks what the wave adds to the stop counter (DESIGN.md 30's "all" or
+// "best").  No LDS beyond the four counter words, no barrier.
 #include <float.h>
 
 #include "ff_common.h"
@@ -369,6 +379,262 @@ int ff_sequence_constrain_sample_finalize(const int* tok, const float* lp, const
   hipLaunchKernelGGL(sequence_constrain_sample_finalize_kernel, dim3(ff_cdiv(total, 256) < 1024 ? ff_cdiv(total, 256) : 1024), dim3(256), 0,
                      st, tok, lp, fin, dead, first, Btot, T, steps_dev, R, w0, nw, b0, samples, logprob, scores, dead_end, open_end,
                      predict, predict_logprob, predict_dead_end, predict_open_end, seq_of_row);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+// ==== beam search over the sequence-constrained decode ==================================================================
+namespace {
+// (the sampled form is instantiated here, where the end of this file used to be: in front of the kernels below, as it was in front
+// of nothing, its device code keeps the place and the local labels it had)
+template __global__ void pointer_sequence_constrained_kernel<SeqConstrainSampleArgs>(SeqConstrainSampleArgs);
+
+struct SeqConBeamArgs {
+  PointerArgs p;                 // as ConBeamArgs.p; p.term_lo / p.term_hi = [SEP, SEP + 1): what ff_loop_write_row re-opens
+  int groups;
+  unsigned char* rows;           // [B, S] out: the constraint byte row of every non-empty unfinished beam (1 = masked)
+  const unsigned* follows;       // [wireframes, L, fw] bits or null
+  int L, fw, flags, ntok, sep, eos;
+  const float* score_in; float* score_out;
+  const int *fin_in, *first_in, *prev_in;
+  const unsigned* visited_in;    // [B, fw]
+  int *fin_out, *dead_out, *open_out, *first_out, *prev_out;
+  unsigned* visited_out;         // [B, fw], not visited_in
+  int* parent; int* tok;         // [B] out
+};
+
+// STOP 0 ("all"): the counter is the non-empty beams unfinished after the step; STOP 1 ("best"): the groups whose rank 0 is.
+template <int W, int STOP>
+__global__ __launch_bounds__(256) void beam_sequence_constrained_select_kernel(SeqConBeamArgs a) {
+  const PointerArgs& pa = a.p;
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const float FILL = -FLT_MAX;
+  int ncount = 0;
+  if (g < a.groups) {   // (wave-uniform)
+    const int S = pa.S, ntok = a.ntok, b0 = g * W, fw = a.fw;
+    const int w = b0 / pa.spg;   // (the beams of a group share the wireframe)
+    int kv = S;
+    if (pa.kv_len) { const int k = ff_ldw(pa.kv_len + w); kv = k < kv ? k : kv; }
+    const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * S : nullptr;
+    // lane k < W holds beam k's state; the loops below broadcast it
+    const float my_c = lane < W ? a.score_in[b0 + lane] : -INFINITY;
+    const int my_f = lane < W ? a.fin_in[b0 + lane] : 0;
+    const int my_first = ff_loop_edge(lane < W ? a.first_in[b0 + lane] : -1, a.L);
+    const int my_prev = ff_loop_edge(lane < W ? a.prev_in[b0 + lane] : -1, a.L);
+    const FFLoopRule rule{a.follows, a.L, fw, a.flags, ntok, nullptr, nullptr, 0};
+    unsigned deadmask = 0u;   // bit k: beam k dead-ended at this step (wave-uniform)
+    float lsc[W];
+    int lix[W];
+    ff_beam_list_init<W>(lsc, lix);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float c = __shfl(my_c, k, FF_WAVE);
+      const int f = __shfl(my_f, k, FF_WAVE);
+      const int first = __shfl(my_first, k, FF_WAVE), prev = __shfl(my_prev, k, FF_WAVE);
+      if (c == -INFINITY) continue;                      // empty beam: no candidates (wave-uniform)
+      if (f) {                                           // finished: itself, token 0, score unchanged
+        if (lane == 0) ff_beam_insert<W>(lsc, lix, c, k * S);
+        continue;
+      }
+      const int b = b0 + k;
+      if (ff_sequence_write_row(pa, rule, lane, w, kv, mrow, first, prev, a.visited_in + (size_t)b * fw, a.rows + (size_t)b * S, a.sep,
+                                a.eos))
+        deadmask |= 1u << k;
+      float m, b2, lsum;
+      int i1;
+      ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &i1, &lsum);
+      const float logz = logf(lsum);
+      if (!(m > FILL)) {                                 // no live key: token 0 at c - log S (wave-uniform)
+        if (lane == 0) ff_beam_insert<W>(lsc, lix, fmaxf(c - logz, FILL), k * S);
+        continue;
+      }
+      // W = 1: the one kept candidate is the row maximum (l[s] = m, the lowest such key: i1), so the score is c + (-log sum), the
+      // greedy form's own expression -- identity (a) then holds bit for bit, the sign of a zero log-probability included
+      if constexpr (W == 1) {
+        if (lane == 0) ff_beam_insert<W>(lsc, lix, fmaxf(c + (-logz), FILL), k * S + i1);
+      } else {
+        ff_beam_walk<W, true>(lsc, lix, pa.logits + (size_t)b * pa.ldlogits, S, lane, k, c, m, logz);
+      }
+    }
+    ff_beam_merge<W>(lsc, lix);
+    float sc;
+    int ix;
+    ff_beam_rank<W>(lsc, lix, lane, &sc, &ix);
+    const bool some = lane < W && ix != FF_BEAM_NONE;
+    const int par = some ? ix / S : (lane < W ? lane : 0);
+    const int pfin = __shfl(my_f, par, FF_WAVE);
+    int first = __shfl(my_first, par, FF_WAVE), prev = __shfl(my_prev, par, FF_WAVE);
+    const bool grew = some && !pfin;                     // the parent was unfinished: tk is this step's token
+    const int tk = grew ? ix - par * S : 0;
+    const int dead_now = grew ? (int)((deadmask >> par) & 1u) : 0;
+    const int nfin = some ? ((pfin || tk == a.eos) ? 1 : 0) : 0;
+    const int e_new = (grew && tk >= ntok) ? tk - ntok : -1;
+    const bool at_sep = grew && tk == a.sep;
+    const int wipe = (at_sep && !(a.flags & FF_CONSTRAIN_ONCE)) ? 1 : 0;   // SEP clears the face's edges unless ONCE
+    if (e_new >= 0) ff_loop_advance(a.follows, w, a.L, fw, e_new, &first, &prev);   // (of the parent's first, prev)
+    if (at_sep) first = prev = -1;
+    const unsigned long long live = __ballot(some && !nfin);
+    ncount = STOP == 0 ? __popcll(live) : (int)(live & 1ull);
+    if (lane < W) {
+      a.parent[b0 + lane] = par;
+      a.tok[b0 + lane] = tk;
+      a.score_out[b0 + lane] = sc;
+      a.fin_out[b0 + lane] = nfin;
+      a.dead_out[b0 + lane] = dead_now;
+      a.open_out[b0 + lane] = (some && first >= 0) ? 1 : 0;
+      a.first_out[b0 + lane] = first;
+      a.prev_out[b0 + lane] = prev;
+    }
+    // visited_out[i] = SEP without ONCE: 0; else visited_in[parent[i]] | bit(edge): word (i, j) by lane i * fw + j (wave-uniform
+    // bound: the shuffles need every lane)
+    for (int i0 = 0; i0 < W * fw; i0 += 64) {
+      const int idx = i0 + lane;
+      const bool in = idx < W * fw;
+      const int i = in ? idx / fw : 0, j = idx - i * fw;
+      const int p = __shfl(par, i, FF_WAVE), e = __shfl(e_new, i, FF_WAVE), z = __shfl(wipe, i, FF_WAVE);
+      if (in) {
+        unsigned v = z ? 0u : a.visited_in[(size_t)(b0 + p) * fw + j];
+        if (e >= 0 && (e >> 5) == j) v |= 1u << (e & 31);
+        a.visited_out[(size_t)(b0 + i) * fw + j] = v;
+      }
+    }
+    if (pa.next_rows) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) ff_pointer_append_row(pa, w, b0 + k, __shfl(tk, k, FF_WAVE), lane);
+    }
+  }
+  ff_pointer_count_waves(pa, a.groups, ncount);
+}
+
+// Start state of one micro-batch of Bc = nw * W beams, beam k of the chunk's wl-th wireframe at i = wl * W + k: SOS
+// (model.py:191), unfinished, beam 0 with score 0 and the others empty (-inf), parent = k, the rule's state empty and closed
+// (first, prev, visited: half 0 of the ping-pong, which step 0 reads).
+__global__ void sequence_constrain_beam_init_kernel(int* tok, float* score, int* fin, int* dead, int* open, int* parent, int* first,
+                                                    int* prev, unsigned* visited, int Bc, int W, int fw, int sos) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bc) return;
+  const int k = i % W;
+  tok[i] = sos;
+  score[i] = k == 0 ? 0.f : -INFINITY;
+  fin[i] = 0;
+  dead[i] = 0;
+  open[i] = 0;
+  parent[i] = k;
+  first[i] = prev[i] = -1;
+  for (int j = 0; j < fw; ++j) visited[(size_t)i * fw + j] = 0u;
+}
+
+// beams[(w, k), :] and beam_dead_end[(w, k), :] from walking the parents back from the stop step through the per-step records
+// (tok, parent, dead: [T, Btot], row s = the state after s steps), scores / finished / open_end [(w, k)] from the stop step's
+// row, and beam 0 under the greedy constrained decode's keys: predict[w, :], dead_end[w, :], open_end[w].  Rows behind the stop
+// step are never looked at (the ping-pong state is not read at all), so the result does not depend on when the host saw the
+// stop.  A finished beam appends token 0 and no dead end, so every row is zero past its EOS.
+__global__ void sequence_constrain_beam_finalize_kernel(const int* __restrict__ tok, const int* __restrict__ parent,
+                                                        const float* __restrict__ score, const int* __restrict__ fin,
+                                                        const int* __restrict__ dead, const int* __restrict__ open, int Btot, int T,
+                                                        const int* __restrict__ steps_p, int W, int w0, int nw, int b0,
+                                                        int64_t* __restrict__ beams, float* __restrict__ scores,
+                                                        int* __restrict__ finished, int* __restrict__ beam_dead_end,
+                                                        int* __restrict__ beam_open_end, int64_t* __restrict__ predict,
+                                                        int* __restrict__ dead_end, int* __restrict__ open_end,
+                                                        int* __restrict__ seq_of_row) {
+  const int steps = *steps_p;
+  const int total = nw * W;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int k = i % W, wl = i / W;
+    const int grp = b0 + wl * W;
+    const size_t wf = (size_t)(w0 + wl), row = wf * W + k;
+    int64_t* out = beams + row * T;
+    int* ode = beam_dead_end + row * T;
+    const bool p0 = k == 0;
+    for (int j = steps + 1; j < T; ++j) {
+      out[j] = 0; ode[j] = 0;
+      if (p0) { predict[wf * T + j] = 0; dead_end[wf * T + j] = 0; }
+    }
+    int cur = k;
+    for (int s = steps; s >= 0; --s) {
+      const size_t r = (size_t)s * Btot + grp + cur;
+      const int v = tok[r], de = s > 0 ? dead[r] : 0;
+      out[s] = v; ode[s] = de;
+      if (p0) { predict[wf * T + s] = v; dead_end[wf * T + s] = de; }
+      cur = s > 0 ? parent[r] : cur;
+    }
+    const size_t last = (size_t)steps * Btot + grp + k;
+    scores[row] = score[last];
+    finished[row] = fin[last];
+    beam_open_end[row] = open[last];
+    if (p0) open_end[wf] = open[last];
+    if (seq_of_row) seq_of_row[row] = grp + k;
+  }
+}
+
+}  // namespace
+
+// The one launch behind ff_beam_sequence_constrained_select and the engine's step; `io` carries the common operands
+// (io.rows = groups * width; its terminator range is not read: the rule has its two tokens).
+int ff_beam_sequence_constrained_select_sync(const ff_step_io& io_in, const ff_beam_sequence_constrained_step* d, ff_stream_t stream) {
+  const char* op = "ff_beam_sequence_constrained_select";
+  const int S = io_in.S, W = d->width, groups = io_in.rows / W;
+  SeqConBeamArgs a;
+  memset(&a, 0, sizeof(a));
+  ff_step_io io = io_in;
+  io.term_lo = d->tok_sep; io.term_hi = d->tok_sep + 1;   // (what ff_loop_write_row leaves open with the loop closed and re-opens on a dead end)
+  FF_RETURN_IF(ff_step_args(&a.p, op, true, io));
+  FF_RETURN_IF(ff_sequence_rule_check(op, ff_loop_rule_io{d->follows, d->L, d->flags, d->ntok}, S, d->tok_sep, d->tok_eos));
+  FF_CHECK_ARG(d->stop_best == 0 || d->stop_best == 1, "%s: stop_best=%d must be 0 or 1", op, d->stop_best);
+  FF_CHECK_ARG(d->scores_in && d->scores_out && d->fin_in && d->fin_out && d->dead_out && d->open_out && d->first_in && d->first_out &&
+                   d->prev_in && d->prev_out && d->visited_in && d->visited_out && d->mask_rows && d->parent && d->next_tok,
+               "%s: null pointer", op);
+  FF_CHECK_ARG(d->visited_in != d->visited_out, "%s: visited_out must not be visited_in", op);
+  a.p.extra = d->mask_rows; a.p.ldextra = S;
+  a.groups = groups; a.rows = d->mask_rows; a.follows = d->follows; a.L = d->L; a.fw = (d->L + 31) >> 5; a.flags = d->flags; a.ntok = d->ntok;
+  a.sep = d->tok_sep; a.eos = d->tok_eos;
+  a.score_in = d->scores_in; a.score_out = d->scores_out;
+  a.fin_in = d->fin_in; a.first_in = d->first_in; a.prev_in = d->prev_in; a.visited_in = d->visited_in;
+  a.fin_out = d->fin_out; a.dead_out = d->dead_out; a.open_out = d->open_out; a.first_out = d->first_out; a.prev_out = d->prev_out;
+  a.visited_out = d->visited_out;
+  a.parent = d->parent; a.tok = d->next_tok;
+  hipStream_t st = (hipStream_t)stream;
+  FFProfScope prof(FF_CAT_POINTER, (double)io.rows * S * 14.0, st);
+  const dim3 grid(ff_cdiv(groups, 4)), block(256);
+  const int rc = ff_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(W, [&](auto w) {
+    return ff_dispatch<0, 1>(d->stop_best, [&](auto f) {
+      hipLaunchKernelGGL((beam_sequence_constrained_select_kernel<decltype(w)::value, decltype(f)::value>), grid, block, 0, st, a);
+      return FF_OK;
+    });
+  });
+  FF_RETURN_IF(rc);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+extern "C" int ff_beam_sequence_constrained_select(const ff_beam_sequence_constrained_step* d, ff_stream_t stream) {
+  const char* op = "ff_beam_sequence_constrained_select";
+  FF_CHECK_ARG(d != nullptr, "%s: null descriptor", op);
+  FF_RETURN_IF(ff_beam_check_sizes(op, d->groups, d->width, d->groups_per_wireframe, d->S));
+  return ff_beam_sequence_constrained_select_sync(
+      ff_step_io{d->logits, d->ldlogits, d->S, d->mask, d->kv_len, d->groups * d->width, d->groups_per_wireframe * d->width, 0, 0, d->ntok,
+                 d->memory, d->E, d->next_rows, d->ldnext, d->next_stats, d->count_unfinished, nullptr, nullptr},
+      d, stream);
+}
+
+int ff_sequence_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* open, int* parent, int* first, int* prev,
+                                    unsigned* visited, int Bc, int W, int L, int sos, hipStream_t st) {
+  hipLaunchKernelGGL(sequence_constrain_beam_init_kernel, dim3(ff_cdiv(Bc, 256)), dim3(256), 0, st, tok, score, fin, dead, open, parent,
+                     first, prev, visited, Bc, W, (L + 31) >> 5, sos);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+
+int ff_sequence_constrain_beam_finalize(const int* tok, const int* parent, const float* score, const int* fin, const int* dead,
+                                        const int* open, int Btot, int T, const int* steps_dev, int W, int w0, int nw, int b0,
+                                        int64_t* beams, float* scores, int* finished, int* beam_dead_end, int* beam_open_end,
+                                        int64_t* predict, int* dead_end, int* open_end, int* seq_of_row, hipStream_t st) {
+  const int total = nw * W;
+  hipLaunchKernelGGL(sequence_constrain_beam_finalize_kernel, dim3(ff_cdiv(total, 256) < 1024 ? ff_cdiv(total, 256) : 1024), dim3(256), 0,
+                     st, tok, parent, score, fin, dead, open, Btot, T, steps_dev, W, w0, nw, b0, beams, scores, finished, beam_dead_end,
+                     beam_open_end, predict, dead_end, open_end, seq_of_row);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }

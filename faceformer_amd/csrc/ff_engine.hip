@@ -271,6 +271,7 @@ struct DecodeBuffers {
   // row s = the state after s steps (row 0: the start state); the tokens are tok_all's rows:
   float* score;             // beam, constrained beam: the beams' scores; sample, constrain: the log-probability of the step's token
   int *finished, *parent, *dead; // finished (all four); parent beam (the beam modes); dead end (constrain), cumulative (constrained beam)
+  int* open;                // sequence-constrained beam: a loop is open after the step (the ping-pong state is overwritten past the stop)
   // The loop rule's state.  constrain: first, prev [T, Btot] per step; visited [Btot, ceil(L/32)] rewritten by every step.
   // constrained beam: two halves that the steps read and write alternately (first, prev: [2, Btot]; visited: [2, Btot, ceil(L/32)]:
   // step s reads half s & 1).  byte_rows [Btot, S]: the constraint byte rows, rewritten by every step.
@@ -373,7 +374,7 @@ int plan_streams(const ff_decode_params* p) {
 // What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
 // 1) and that kind's parameters (null in a size query, which needs the kind and G only).
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM, SEQ_CONSTRAIN, SEQ_CONSTRAIN_SAMPLE } kind;
+  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM, SEQ_CONSTRAIN, SEQ_CONSTRAIN_SAMPLE, SEQ_CONSTRAIN_BEAM } kind;
   int G;
   const void* prm;
   Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
@@ -392,7 +393,7 @@ struct Mode {
   const ff_constrain_beam_ahead_params* cbeam_ahead() const { return static_cast<const ff_constrain_beam_ahead_params*>(prm); }
   // (CONSTRAIN_BEAM and CONSTRAIN_BEAM_AHEAD: the parameters the two share)
   bool is_cbeam() const { return kind == CONSTRAIN_BEAM || kind == CONSTRAIN_BEAM_AHEAD; }
-  bool is_sequence() const { return kind == SEQ_SAMPLE || kind == SEQ_BEAM || kind == SEQ_CONSTRAIN || kind == SEQ_CONSTRAIN_SAMPLE; }   // (the ff_decode_sequence_* entries)
+  bool is_sequence() const { return kind == SEQ_SAMPLE || kind == SEQ_BEAM || kind == SEQ_CONSTRAIN || kind == SEQ_CONSTRAIN_SAMPLE || kind == SEQ_CONSTRAIN_BEAM; }   // (the ff_decode_sequence_* entries)
   ff_constrain_beam_params cbeam() const {
     if (kind != CONSTRAIN_BEAM_AHEAD) return *static_cast<const ff_constrain_beam_params*>(prm);
     const ff_constrain_beam_ahead_params* q = cbeam_ahead();
@@ -401,6 +402,7 @@ struct Mode {
   const ff_constrain_sample_params* csample() const { return static_cast<const ff_constrain_sample_params*>(prm); }
   const ff_sequence_constrain_params* seqcon() const { return static_cast<const ff_sequence_constrain_params*>(prm); }
   const ff_sequence_constrain_sample_params* seqcs() const { return static_cast<const ff_sequence_constrain_sample_params*>(prm); }
+  const ff_sequence_constrain_beam_params* seqcb() const { return static_cast<const ff_sequence_constrain_beam_params*>(prm); }
 };
 
 // The micro-batch plan of a mode: the default plan for greedy and constrain; without de-duplication for forced (the rows are
@@ -415,6 +417,7 @@ void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, con
     case Mode::SEQ_SAMPLE:   // (FF_SEQ2SEQ: a micro-batch is cut by sequences, chunk_max_seqs / R wireframes, at least one)
     case Mode::SEQ_BEAM:     // (likewise: chunk_max_seqs / W wireframes, at least one)
     case Mode::SEQ_CONSTRAIN_SAMPLE:   // (SEQ_SAMPLE's plan)
+    case Mode::SEQ_CONSTRAIN_BEAM:     // (SEQ_BEAM's plan)
     case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
     case Mode::FORCED: {
       ff_decode_params q = *p;
@@ -526,12 +529,14 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
     case Mode::BEAM:
     case Mode::SEQ_BEAM:
     case Mode::CONSTRAIN_BEAM:
+    case Mode::SEQ_CONSTRAIN_BEAM:     // (SEQ_BEAM's records, then the constrained beam's and the per-step open record)
     case Mode::CONSTRAIN_BEAM_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
       b.score = bp.take<float>(TB);
       b.finished = bp.take<int>(TB);
       b.parent = bp.take<int>(TB);
       if (mode.kind == Mode::BEAM || mode.kind == Mode::SEQ_BEAM) break;
       b.dead = bp.take<int>(TB);
+      if (mode.kind == Mode::SEQ_CONSTRAIN_BEAM) b.open = bp.take<int>(TB);
       b.first = bp.take<int>(2 * Btot);     // (the two halves)
       b.prev = bp.take<int>(2 * Btot);
       b.visited = bp.take<unsigned>(2 * vw);
@@ -1114,6 +1119,7 @@ struct DecodeRun {
       case Mode::CONSTRAIN_SAMPLE: follows = mode.csample()->follows; flags = mode.csample()->flags; break;
       case Mode::SEQ_CONSTRAIN: follows = mode.seqcon()->follows; flags = mode.seqcon()->flags; break;
       case Mode::SEQ_CONSTRAIN_SAMPLE: follows = mode.seqcs()->follows; flags = mode.seqcs()->flags; break;
+      case Mode::SEQ_CONSTRAIN_BEAM: follows = mode.seqcb()->follows; flags = mode.seqcb()->flags; break;
       default: follows = mode.con().follows; flags = mode.con().flags; break;
     }
     return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, flags};
@@ -1156,6 +1162,10 @@ struct DecodeRun {
         return ff_sequence_constrain_sample_init(tok, score, fin, buf.dead + c.b0, buf.first + c.b0, buf.prev + c.b0,
                                                  buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), buf.row_id + c.b0, c.Bc, G, c.w0, p->L,
                                                  p->tok_sos, st);
+      case Mode::SEQ_CONSTRAIN_BEAM:   // (Fc = W beams per wireframe, the rule's state empty and closed: half 0 of the ping-pong)
+        return ff_sequence_constrain_beam_init(tok, score, fin, buf.dead + c.b0, buf.open + c.b0, buf.parent + c.b0, buf.first + c.b0,
+                                               buf.prev + c.b0, buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), c.Bc, G, p->L, p->tok_sos,
+                                               st);
       case Mode::CONSTRAIN:
       case Mode::CONSTRAIN_AHEAD:
       case Mode::CONSTRAIN_EXACT:
@@ -1232,6 +1242,7 @@ struct DecodeRun {
     switch (mode.kind) {
       case Mode::BEAM:
       case Mode::SEQ_BEAM:
+      case Mode::SEQ_CONSTRAIN_BEAM:
       case Mode::CONSTRAIN_BEAM:
       case Mode::CONSTRAIN_BEAM_AHEAD: {
         // top-W selection, then the reorder of positions < t of x0 and qkv0 behind it on the same stream: the next decoder pass
@@ -1243,6 +1254,22 @@ struct DecodeRun {
           trace_parent = sq ? mode.seqbeam()->trace_parent : mode.beam()->trace_parent;
           FF_RETURN_IF(ff_beam_select_sync(sio, W, buf.score + in, buf.score + out, buf.finished + in, buf.finished + out, nullptr, 0, t,
                                            buf.parent + out, tok_out, st, sq ? (mode.seqbeam()->stop_best ? 2 : 1) : 0));
+        } else if (mode.kind == Mode::SEQ_CONSTRAIN_BEAM) {   // the sequence rule per beam: state half step & 1 -> half t & 1
+          const ff_sequence_constrain_beam_params* q = mode.seqcb();
+          trace_parent = q->trace_parent;
+          const Rule r = rule_of(c);
+          const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
+          ff_beam_sequence_constrained_step d;
+          memset(&d, 0, sizeof(d));
+          d.width = W; d.follows = r.follows; d.L = r.L; d.flags = r.flags; d.ntok = m->num_token;
+          d.tok_sep = q->tok_sep; d.tok_eos = p->tok_eos; d.stop_best = q->stop_best;
+          d.scores_in = buf.score + in; d.fin_in = buf.finished + in;
+          d.first_in = buf.first + hin; d.prev_in = buf.prev + hin; d.visited_in = buf.visited + hin * r.fw;
+          d.scores_out = buf.score + out; d.fin_out = buf.finished + out; d.dead_out = buf.dead + out; d.open_out = buf.open + out;
+          d.first_out = buf.first + hout; d.prev_out = buf.prev + hout; d.visited_out = buf.visited + hout * r.fw;
+          d.mask_rows = buf.byte_rows + (size_t)c.b0 * S;
+          d.parent = buf.parent + out; d.next_tok = tok_out;
+          FF_RETURN_IF(ff_beam_sequence_constrained_select_sync(sio, &d, st));
         } else {   // the constrained selection: state half step & 1 -> half t & 1 (the common operands come from sio)
           trace_parent = mode.cbeam().trace_parent;
           const Rule r = rule_of(c);
@@ -1509,6 +1536,12 @@ struct DecodeRun {
         const ff_sequence_beam_params* q = mode.seqbeam();
         return ff_beam_finalize(buf.tok_all, buf.parent, buf.score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G,
                                 c.f0, c.b0, q->beams, q->scores, io.predict, io.seq_of_row, main_st, buf.finished, q->finished);
+      }
+      case Mode::SEQ_CONSTRAIN_BEAM: {   // (F = 1, no de-duplication; tokens and dead flags along one walk, the rest from the stop step's row)
+        const ff_sequence_constrain_beam_params* q = mode.seqcb();
+        return ff_sequence_constrain_beam_finalize(buf.tok_all, buf.parent, buf.score, buf.finished, buf.dead, buf.open, Btot, T,
+                                                   buf.steps_dev, G, c.w0, c.nw, c.b0, q->beams, q->scores, q->finished, q->beam_dead_end,
+                                                   q->beam_open_end, io.predict, q->dead_end, q->open_end, io.seq_of_row, main_st);
       }
       case Mode::BEAM:
       case Mode::CONSTRAIN_BEAM:
@@ -1938,6 +1971,32 @@ extern "C" int ff_decode_sequence_constrained_sample(const ff_model* m, const ff
   FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{cs->uniforms, rows, nullptr, cs->temperature, cs->top_k, cs->top_p}, rows));
   return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
                       stream, Mode(Mode::SEQ_CONSTRAIN_SAMPLE, cs->num_samples, cs));
+}
+
+extern "C" size_t ff_decode_sequence_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width) {
+  if (width < 1 || width > 8 || !sequence_query_ok(p)) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_CONSTRAIN_BEAM, width));
+}
+
+// W beams per wireframe of the single-sequence decode (model.py:161-167, 191, 193-210) over the rows the face-loop rule leaves.
+extern "C" int ff_decode_sequence_constrained_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
+                                                   const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done,
+                                                   int* step_counts, float* trace_logits, int* seq_of_row, void* workspace,
+                                                   size_t workspace_bytes, const ff_sequence_constrain_beam_params* beam,
+                                                   ff_stream_t stream) {
+  const char* name = "ff_decode_sequence_constrained_beam";
+  FF_RETURN_IF(check_sequence(name, "constrain beam", "ff_decode_constrained_beam", m, p, beam));
+  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
+  FF_CHECK_ARG(beam->stop_best == 0 || beam->stop_best == 1, "%s: stop_best=%d must be 0 or 1", name, beam->stop_best);
+  FF_RETURN_IF(ff_sequence_rule_check(name, ff_loop_rule_io{beam->follows, p->L, beam->flags, m->num_token}, p->L + m->num_token,
+                                      beam->tok_sep, p->tok_eos));
+  FF_CHECK_ARG(beam->beams && beam->scores && beam->finished && beam->beam_dead_end && beam->beam_open_end && beam->dead_end &&
+                   beam->open_end && predict,
+               "%s: beams, scores, finished, beam_dead_end, beam_open_end, dead_end, open_end and predict are required", name);
+  FF_CHECK_ARG(p->N > 0 && (long long)p->N * beam->width < (1LL << 31), "%s: bad sizes", name);
+  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
+  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
+                      stream, Mode(Mode::SEQ_CONSTRAIN_BEAM, beam->width, beam));
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {

@@ -310,6 +310,23 @@ __device__ __forceinline__ bool ff_loop_write_row(const PointerArgs& pa, const F
   return true;
 }
 
+// The single-sequence model's byte row as one call, for the beam form: the plain rule with the
+// terminator range pa.term_lo / pa.term_hi = [SEP, SEP + 1) -- open: every special token masked, SEP re-opened on a dead end;
+// closed: every special token but SEP masked -- and then the two fix-ups of the closed state by the lanes that own the keys
+// (lane = key mod 64): EOS is opened, SEP is masked while the current face has no edge (prev == none).  Returns the dead-end bit.
+// pointer_sequence_constrained_kernel (ff_constrain_seq.hip) has the same lines in its own body and keeps them there: moving
+// them behind this call changed that kernel's register allocation.
+__device__ __forceinline__ bool ff_sequence_write_row(const PointerArgs& pa, const FFLoopRule& r, int lane, int w, int kv,
+                                                      const unsigned char* mrow, int first, int prev, const unsigned* vrow,
+                                                      unsigned char* xrow, int sep, int eos) {
+  const bool dead = ff_loop_write_row<FF_LOOP_PLAIN>(pa, r, lane, w, kv, mrow, first, prev, vrow, xrow);
+  if ((r.flags & FF_CONSTRAIN_CONNECT) && !(first >= 0 && prev >= 0)) {   // closed: EOS may end the row; no empty face
+    if (lane == (eos & 63)) xrow[eos] = 0;
+    if (prev < 0 && lane == (sep & 63)) xrow[sep] = 1;
+  }
+  return dead;
+}
+
 // (first, prev) after edge e of wireframe w was selected: e opens a loop when none is open, becomes prev, and closes the loop
 // when the first edge starts where e ends -- one word of the follow table (a one-edge loop closes on itself).
 __device__ __forceinline__ void ff_loop_advance(const unsigned* follows, int w, int L, int fw, int e, int* first, int* prev) {

@@ -297,6 +297,27 @@ def parse_faces_beams_scored(beams, scores, finished, num_edges, token):
     return list(best.values())
 
 
+def parse_faces_constrained_beams_scored(beams, scores, finished, dead_end, num_edges, token):
+    """The faces of a constrained beam decode of the single-sequence model (SurfaceFormer.sequence_constrain_beams):
+    beams and dead_end [W, T], scores and finished [W] (predict_beams[w] / predict_beam_dead_end[w] / predict_beam_scores[w] /
+    predict_beam_finished[w]).  parse_faces_beams_scored with the faces abandoned at a dead end left out -- a piece whose SEP
+    carries the dead-end flag ends in a separator the rule opened for want of an edge: its loop is open.  The pieces that stay
+    are read in place, as one row.  Returns [(0, (edge, ...), score)] in beam order, every face with its BEAM's score."""
+    rows = np.asarray(beams, dtype=np.int64)
+    dead = np.asarray(dead_end) != 0
+    if rows.ndim != 2 or dead.shape != rows.shape:
+        raise ValueError("beams and dead_end must both be [W, T]")
+    eos, sep = _tok(token, "EOS", 3), _tok(token, "SEP", 2)
+    kept = np.zeros_like(rows)
+    for i, (row, de) in enumerate(zip(rows, dead)):
+        n = _prefix_through_first(row, row == eos).size
+        cuts = np.flatnonzero(row[:n] == sep) + 1
+        pieces = [p for p, d in zip(np.split(row[:n], cuts), np.split(de[:n], cuts)) if not (p.size and d[-1])]
+        flat = np.concatenate(pieces) if pieces else row[:0]
+        kept[i, : flat.size] = flat
+    return parse_faces_beams_scored(kept, scores, finished, num_edges, token)
+
+
 def parse_parallel_beams_scored(beams, scores, num_edges, token):
     """The faces of a beam decode (the parallel model's beam_width): beams [..., W, T] tokens, scores [..., W] the
     beams' summed log-probabilities (-inf: an empty beam, skipped).  Every other beam is read as `_parallel_rows` reads a row --
@@ -667,6 +688,108 @@ def sequence_rule_sample_step(raw, pad, state, flags, ntok, sep, eos, u, tempera
         lp = max(float((row[tok] - m) - np.log(np.exp(row - m).sum())), SEQ_FILL)
     return dict(tok=tok, logprob=lp, row=row, masked=masked, dead=dead, fin=tok == eos,
                 state=sequence_rule_advance(state, tok, flags, ntok, sep, follows))
+
+
+def sequence_rule_beam_step(raw, pad, scores, fin, states, flags, ntok, sep, eos, follows=None):
+    """One step of ONE group (the W beams of one wireframe) of the beam form (ff_beam_sequence_constrained_select)
+    on RAW logits [W, S]: scores [W] (-inf: an empty beam, no candidates), fin [W], states [W] (sequence_rule_start's form), pad
+    [S] the wireframe's padding / kv_len keys.  An unfinished beam's row is sequence_rule_mask's; its candidates are the LIVE
+    keys only, each at score + (l[s] - max) - log sum exp(l - max) over the constrained row, saturated at SEQ_FILL (a row with no
+    live key: token 0 at score - log S); a finished beam is its own single candidate, token 0, score unchanged.  Order: higher
+    score first, then the lower flat index k * S + s.  -> dict(parent, tok, scores, fin, dead (this step's flag), open [W each],
+    states [W], rows [W, S] (the constrained masked rows, fp64; raw for empty / finished beams), masked [W, S] (the rule's own
+    byte rows), cand: the first W + 1 candidates (score, flat index) in order).  A rank past the number of candidates is empty:
+    parent = the rank, token 0, score -inf, flags clear, the state of the own index."""
+    raw = np.asarray(raw, dtype=np.float64)
+    W, S = raw.shape
+    pad = np.asarray(pad, dtype=bool)
+    rows, masks, dead_of = raw.copy(), np.zeros((W, S), dtype=bool), [False] * W
+    cand = []
+    for k in range(W):
+        if scores[k] == -np.inf:
+            continue
+        if fin[k]:
+            cand.append((float(scores[k]), k * S))
+            continue
+        masks[k], dead_of[k] = sequence_rule_mask(states[k], flags, S, ntok, sep, eos, follows, pad)
+        row = rows[k] = np.where(masks[k] | pad, SEQ_FILL, raw[k])
+        m = row.max()
+        logz = np.log(np.exp(row - m).sum())
+        live = np.flatnonzero(row > SEQ_FILL)
+        if not live.size:
+            cand.append((max(float(scores[k] - logz), SEQ_FILL), k * S))
+            continue
+        sc = np.maximum(scores[k] + ((row - m) - logz), SEQ_FILL)
+        cand.extend((float(sc[s]), k * S + int(s)) for s in live)
+    cand.sort(key=lambda c: (-c[0], c[1]))
+    out = dict(parent=np.arange(W), tok=np.zeros(W, dtype=np.int64), scores=np.full(W, -np.inf), fin=np.zeros(W, dtype=bool),
+               dead=np.zeros(W, dtype=bool), open=np.zeros(W, dtype=bool), states=list(states), rows=rows, masked=masks,
+               cand=cand[: W + 1])
+    for r, (sc, ix) in enumerate(cand[:W]):
+        k, s = divmod(ix, S)
+        out["parent"][r], out["scores"][r] = k, sc
+        if fin[k]:
+            out["fin"][r], out["states"][r] = True, states[k]
+        else:
+            out["tok"][r], out["fin"][r], out["dead"][r] = s, s == eos, dead_of[k]
+            out["states"][r] = sequence_rule_advance(states[k], s, flags, ntok, sep, follows)
+        out["open"][r] = out["states"][r][1] is not None
+    return out
+
+
+def sequence_rule_beam_decode(step_logits, pad, W, T, flags, ntok, sos, sep, eos, follows=None, stop="all"):
+    """The whole rule of the beam form as a loop over G = len(pad) wireframes.  step_logits(prefixes [G * W, j + 1], j) -> RAW
+    logits [G * W, S] of step j (rows of empty and finished beams are not read); pad [G, S]; follows: one table per wireframe
+    (or None).  Start: every beam at sos, beam 0 with score 0, the others empty, the rule's state empty and closed.  Stop: after
+    the first step that leaves `stop`'s counter at 0 ("all": the non-empty beams unfinished after the step; "best": the groups
+    whose rank 0 is), else after T - 1 steps.  -> dict(beams, dead_end [G * W, T] (walked back along the parents, zero past each
+    beam's EOS and past steps), scores, fin, open [G * W], steps, counts, all_counts, best_counts, parents, toks, deads, cands
+    (per step, per group), states)."""
+    if stop not in ("all", "best"):
+        raise ValueError("stop=%r: must be 'all' or 'best'" % (stop,))
+    pad = np.asarray(pad, dtype=bool)
+    G, B = len(pad), len(pad) * W
+    scores = np.where(np.arange(B) % W == 0, 0.0, -np.inf)
+    fin, opn = np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
+    states = [sequence_rule_start()] * B
+    toks, parents, deads, cands, alls, bests = [], [], [], [], [], []
+
+    def walk(cols):      # [B, len(cols[0..]) + 1]: column j of every beam through its parents; column 0 is given
+        res = np.zeros((B, len(toks) + 1), dtype=np.int64)
+        for b in range(B):
+            g, cur = b // W, b % W
+            for s in range(len(toks), 0, -1):
+                res[b, s] = cols[s - 1][g * W + cur]
+                cur = int(parents[s - 1][g * W + cur])
+        return res
+
+    steps = T - 1
+    for j in range(T - 1):
+        prefixes = walk(toks)
+        prefixes[:, 0] = sos
+        raw = np.asarray(step_logits(prefixes, j), dtype=np.float64)
+        res = [sequence_rule_beam_step(raw[g * W:(g + 1) * W], pad[g], scores[g * W:(g + 1) * W], fin[g * W:(g + 1) * W],
+                                       states[g * W:(g + 1) * W], flags, ntok, sep, eos, None if follows is None else follows[g])
+               for g in range(G)]
+        scores, fin, opn = (np.concatenate([r[k] for r in res]) for k in ("scores", "fin", "open"))
+        states = [s for r in res for s in r["states"]]
+        toks.append(np.concatenate([r["tok"] for r in res]))
+        parents.append(np.concatenate([r["parent"] for r in res]))
+        deads.append(np.concatenate([r["dead"] for r in res]).astype(np.int64))
+        cands.append([r["cand"] for r in res])
+        live = np.isfinite(scores) & ~fin
+        alls.append(int(live.sum()))
+        bests.append(int(live.reshape(G, W)[:, 0].sum()))
+        if (alls if stop == "all" else bests)[-1] == 0:
+            steps = j + 1
+            break
+    beams, dead_end = np.zeros((B, T), dtype=np.int64), np.zeros((B, T), dtype=np.int64)
+    beams[:, : steps + 1] = walk(toks)
+    beams[:, 0] = sos
+    dead_end[:, : steps + 1] = walk(deads)
+    return dict(beams=beams, dead_end=dead_end, scores=scores, fin=fin, open=opn, steps=steps,
+                counts=alls if stop == "all" else bests, all_counts=alls, best_counts=bests, parents=parents, toks=toks, deads=deads,
+                cands=cands, states=states)
 
 
 def is_face_enclosed(edges, face_indices, tol):

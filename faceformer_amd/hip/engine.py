@@ -376,7 +376,8 @@ class PathEngine:
                num_samples=None, temperature=1.0, top_k=0, top_p=1.0, uniforms=None, constrain=None, follow_table=None,
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
                constrain_samples=None, constrain_beam_closure=None, sequence_samples=None, sequence_beams=None,
-               sequence_beam_stop="all", sequence_constrain=None, tok_sep=None, sequence_constrain_samples=None):
+               sequence_beam_stop="all", sequence_constrain=None, tok_sep=None, sequence_constrain_samples=None,
+               sequence_constrain_beams=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -484,7 +485,20 @@ class PathEngine:
         renormalised over the keys the rule allows), `sample_scores` [N*R], `sample_dead_end` [N*R, T] int32 and `sample_open_end`
         [N*R] int32; `predict`, `logprob`, `dead_end` and `open_end` are draw 0; with trace=True `logits` [T-1, N*R, S] holds the
         constrained masked rows.  temperature=0 equals the sequence_constrain decode, R times; flag bits 0 equal the
-        sequence_samples decode."""
+        sequence_samples decode.
+
+        sequence_constrain_beams=W in 1..8, at most S (only with sequence_constrain, not with sequence_samples, sequence_beams or
+        sequence_constrain_samples; ff_decode_sequence_constrained_beam; None or 0: the sequence_constrain decode
+        above): the W best rows per WIREFRAME among the rows the rule leaves, every beam carrying its own state of the rule through
+        the parent permutation, scored by the model's distribution renormalised over the allowed keys; sequence_beam_stop "all" /
+        "best" as sequence_beams'.  Also `beams` [N*W, T] int64 (row w*W + k is rank k of wireframe w, best first), `beam_scores`,
+        `beam_finished` and `beam_open_end` [N*W], `beam_dead_end` [N*W, T] int32 (walked back along the tokens' parents);
+        `predict`, `dead_end` and `open_end` are beam 0; no `logprob`; with trace=True `logits` [T-1, N*W, S] holds the constrained
+        masked rows and `beam_parent` the parents.  W = 1 equals the sequence_constrain decode; flag bits 0 equal the
+        sequence_beams decode wherever every wireframe has W live keys."""
+        SCB = _modes.sequence_constrain_beams_value(sequence_constrain_beams, _modes.sequence_constrain_flags(sequence_constrain),
+                                                    sequence_samples, sequence_beams, sequence_constrain_samples) \
+            if sequence_constrain_beams else 0
         SCS = _modes.sequence_constrain_samples_value(sequence_constrain_samples, _modes.sequence_constrain_flags(sequence_constrain),
                                                       sequence_samples, sequence_beams) if sequence_constrain_samples else 0
         seq = dict(sequence_samples=sequence_samples, sequence_beams=sequence_beams, sequence_constrain=sequence_constrain)
@@ -499,6 +513,8 @@ class PathEngine:
                 o[mode.subject] = value
                 if SCS:      # (an option of sequence_constrain, the first record this loop looks at)
                     mode, o["sequence_constrain_samples"] = _modes.SEQUENCE_CONSTRAIN_SAMPLE, SCS
+                if SCB:      # (likewise)
+                    mode, o["sequence_constrain_beams"] = _modes.SEQUENCE_CONSTRAIN_BEAM, SCB
                 return self._decode_sequence(mode, memory, mask_u8, kv_len, variant, o,
                                              (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs, num_streams,
                                               chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows), sync_every, tok_sos)

@@ -204,6 +204,24 @@ class SequenceConstrainSampleParams(C.Structure):
                 ("predict_open_end", fptr)]
 
 
+class BeamSequenceConstrainedStep(C.Structure):
+    _fields_ = [("logits", fptr), ("ldlogits", C.c_int), ("S", C.c_int), ("mask", fptr), ("kv_len", fptr),
+                ("groups", C.c_int), ("width", C.c_int), ("groups_per_wireframe", C.c_int),
+                ("follows", fptr), ("L", C.c_int), ("flags", C.c_int), ("ntok", C.c_int), ("tok_sep", C.c_int), ("tok_eos", C.c_int),
+                ("stop_best", C.c_int),
+                ("scores_in", fptr), ("fin_in", fptr), ("first_in", fptr), ("prev_in", fptr), ("visited_in", fptr),
+                ("scores_out", fptr), ("fin_out", fptr), ("dead_out", fptr), ("open_out", fptr), ("first_out", fptr), ("prev_out", fptr),
+                ("visited_out", fptr), ("mask_rows", fptr), ("parent", fptr), ("next_tok", fptr),
+                ("memory", fptr), ("E", C.c_int), ("next_rows", fptr), ("ldnext", C.c_int), ("next_stats", fptr),
+                ("count_unfinished", fptr)]
+
+
+class SequenceConstrainBeamParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("stop_best", C.c_int), ("flags", C.c_int), ("follows", fptr), ("tok_sep", C.c_int),
+                ("beams", fptr), ("scores", fptr), ("finished", fptr), ("beam_dead_end", fptr), ("beam_open_end", fptr),
+                ("dead_end", fptr), ("open_end", fptr), ("trace_parent", fptr)]
+
+
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
 FF_CONSTRAIN_ONCE = 4         # ff_pointer_sequence_constrained / ff_decode_sequence_constrained only
@@ -390,6 +408,11 @@ SIGNATURES = {
     "ff_decode_sequence_constrained_sample": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
                                                         C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
                                                         C.POINTER(SequenceConstrainSampleParams), fptr]),
+    "ff_beam_sequence_constrained_select": (C.c_int, [C.POINTER(BeamSequenceConstrainedStep), fptr]),
+    "ff_decode_sequence_constrained_beam_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
+    "ff_decode_sequence_constrained_beam": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                                      C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
+                                                      C.POINTER(SequenceConstrainBeamParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
     "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
                                fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
@@ -428,7 +451,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows, *_sequence_constrained and *_sequence_constrained_sample ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows, *_sequence_constrained, *_sequence_constrained_sample and *_sequence_constrained_beam ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

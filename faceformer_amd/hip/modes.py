@@ -696,6 +696,62 @@ SEQUENCE_CONSTRAIN_SAMPLE = SEQUENCE_CONSTRAIN._replace(
                                                   model_has="draws per wireframe under the loop rule of the single-sequence model's row",
                                                   model_values=_sequence_constrain_sample_model_values))
 
+def sequence_constrain_beams_value(sequence_constrain_beams, flags, sequence_samples=0, sequence_beams=0, sequence_constrain_samples=0):
+    """The width of a `sequence_constrain_beams` value: None / 0 -> 0 (the option is off); else 1..8, only with
+    `sequence_constrain` set (`flags`: sequence_constrain_flags of it) and not with sequence_samples, sequence_beams or
+    sequence_constrain_samples."""
+    W = sequence_constrain_beams
+    if W is None or (not isinstance(W, bool) and W == 0):
+        return 0
+    if isinstance(W, bool) or not isinstance(W, int) or not 1 <= W <= 8:
+        raise ValueError("sequence_constrain_beams=%r: must be None, 0 or a width in 1..8" % (W,))
+    if flags is None:
+        raise ValueError("sequence_constrain_beams=%d needs sequence_constrain ('no_repeat', 'loops' or 'coedge_loops'): it is the "
+                         "beam search over the keys the face-loop rule allows" % W)
+    if sequence_samples or sequence_beams or sequence_constrain_samples:
+        raise ValueError("sequence_constrain_beams excludes sequence_samples, sequence_beams and sequence_constrain_samples: they draw "
+                         "from / search the unconstrained row, or draw under the rule")
+    return int(W)
+
+
+def _sequence_constrain_beam_values(o):
+    """sequence_constrain's value check and the sequence beam decode's on the width and the stop rule."""
+    W = o["sequence_constrain_beams"]
+    if isinstance(W, bool) or not isinstance(W, int) or not 1 <= W <= 8 or ("S" in o and W > o["S"]):
+        raise ValueError("sequence_constrain_beams=%r: must be in 1..8 and at most S%s" % (W, " = %d" % o["S"] if "S" in o else ""))
+    sequence_beam_stop_value(o.get("sequence_beam_stop", "all"))
+    _sequence_constrain_values(o)
+
+
+def _sequence_constrain_beam_tail(o, ptrs, traced):
+    return (C.byref(_L.SequenceConstrainBeamParams(
+        o["sequence_constrain_beams"], sequence_beam_stop_value(o["sequence_beam_stop"]), o["sequence_constrain"],
+        _p(o["follow_table"]), int(o["tok_sep"]), *ptrs, _beam_parent(o, traced))),)
+
+
+def _sequence_constrain_beam_model_values(m, W, inputs):
+    _sequence_constrain_beam_values(dict(sequence_constrain_beams=W, sequence_beam_stop=getattr(m, "sequence_beam_stop", "all"),
+                                         S=inputs["input"].size(1) + m.num_token, sequence_constrain=0, follow_table=None))
+
+
+# sequence_constrain with its option sequence_constrain_beams = W (DESIGN.md 34): the W best rows per wireframe among the rows
+# the face-loop rule leaves.  Outside SEQUENCE_MODES (and MODES), as SEQUENCE_CONSTRAIN_SAMPLE is: the option that switches the
+# mode on stays `sequence_constrain` -- sequence_constrain with sequence_beams stays the recorded refusal it is.  The outputs:
+# the beams, and beam 0 under sequence_constrain's own keys (no per-position log-probability: the beams carry scores).
+SEQUENCE_CONSTRAIN_BEAM = SEQUENCE_CONSTRAIN._replace(
+    subject="sequence_constrain_beams", entry="ff_decode_sequence_constrained_beam", per_anchor=True,
+    values=_sequence_constrain_beam_values,
+    outs=(("beams", "GT", _I64), ("beam_scores", "G", _F32), ("beam_finished", "G", _I32), ("beam_dead_end", "GT", _I32),
+          ("beam_open_end", "G", _I32), ("dead_end", "T", _I32), ("open_end", "", _I32)),
+    tail=_sequence_constrain_beam_tail,
+    # (batch order, as the record it extends: beam k of wireframe w as given is row w*W + k)
+    prepare=lambda m, W, inputs, dev, T, N, F, ni, order: dict(
+        SEQUENCE_CONSTRAIN.prepare(m, sequence_constrain_flags(m.sequence_constrain), inputs, dev, T, N, F, ni, order),
+        sequence_constrain_beams=W, sequence_beam_stop=m.sequence_beam_stop),
+    sequence=SEQUENCE_CONSTRAIN.sequence._replace(parallel_has=("searches under the rule", "constrain_beams"), each="beam",
+                                                  model_has="beams per wireframe under the loop rule of the single-sequence model's row",
+                                                  model_values=_sequence_constrain_beam_model_values))
+
 # in the order the refusals name them; of several set together, decode() lets the last one's record report, SurfaceFormer the
 # first of SEQUENCE_MODEL_ORDER that is on (a record excludes every record before it in SEQUENCE_MODES, by its option's name)
 SEQUENCE_MODES = (SEQUENCE_SAMPLE, SEQUENCE_BEAM, SEQUENCE_CONSTRAIN)

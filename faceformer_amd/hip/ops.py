@@ -1223,6 +1223,77 @@ def _beam_constrained_step(logits, scores, fin, dead, first, prev, visited, widt
 
 
 @_on_tensor_device
+def beam_sequence_constrained_select(logits, scores, fin, first, prev, visited, width, flags, ntok, tok_sep, tok_eos, follows=None,
+                                     stop="all", memory=None, mask=None, kv_len=None, groups_per_wireframe=None, want_rows=False,
+                                     want_stats=False, counter=None):
+    """One beam-search step over the rows the single-sequence model's loop rule leaves (ff_beam_sequence_constrained_select,
+    DESIGN.md 34): beam_constrained_select's operands with pointer_sequence_constrained's rule (tok_sep / tok_eos in place of a
+    terminator range, FF_CONSTRAIN_ONCE accepted) and beam_sequence_select's stop forms (stop "all" / "best": what `counter`
+    receives).  There is no cumulative dead flag: a dead end abandons the face, not the beam.  Returns dict(parent, next, fin,
+    dead_end (this step's flag), open (a loop is open after the step), first, prev [G * width] int32; scores fp32; visited;
+    mask_rows [G * width, S] uint8; [rows]; [stats]): the new beams in rank order, best first.  No operand is modified but logits."""
+    _dev(logits, "logits"), _dev(scores, "scores")
+    out = {}
+    if logits.dim() != 2:
+        raise ValueError("logits must be a 2-D tensor with unit inner stride")
+    B = logits.size(0)
+    width = int(width)
+    if not 1 <= width <= BEAM_MAX_WIDTH or width > logits.size(1) or B % width:
+        raise ValueError("beam width %d: must be in 1..%d, at most S = %d, and divide the %d rows"
+                         % (width, BEAM_MAX_WIDTH, logits.size(1), B))
+    if stop not in ("all", "best"):
+        raise ValueError("stop=%r: must be 'all' or 'best'" % (stop,))
+    G = B // width
+    gpw = max(G, 1) if groups_per_wireframe is None else int(groups_per_wireframe)
+    B, S, spg, nw, E, rows, stats = _step_operands(logits, gpw * width, mask, kv_len, memory, want_rows, want_stats, out)
+    flags, ntok, sep, eos = int(flags), int(ntok), int(tok_sep), int(tok_eos)
+    L = S - ntok
+    fw = (L + 31) // 32
+    if flags & ~(_L.FF_CONSTRAIN_NO_REPEAT | _L.FF_CONSTRAIN_CONNECT | _L.FF_CONSTRAIN_ONCE):
+        raise ValueError("unknown constraint flag bits %d" % flags)
+    if flags & _L.FF_CONSTRAIN_ONCE and not flags & _L.FF_CONSTRAIN_NO_REPEAT:
+        raise ValueError("FF_CONSTRAIN_ONCE needs FF_CONSTRAIN_NO_REPEAT")
+    if L < 0 or not (0 <= sep < ntok and 0 <= eos < ntok) or sep == eos:
+        raise ValueError("tok_sep and tok_eos must be two different tokens below ntok <= S")
+    if follows is None and flags & _L.FF_CONSTRAIN_CONNECT:
+        raise ValueError("FF_CONSTRAIN_CONNECT needs the follow table")
+    if scores.dim() != 1 or scores.numel() != B:
+        raise ValueError("scores must hold one fp32 per row of logits")
+    for x, name in ((fin, "fin"), (first, "first"), (prev, "prev")):
+        _dev(x, name, torch.int32)
+        if x.dim() != 1 or x.numel() != B:
+            raise ValueError("%s must hold one int32 per row of logits" % name)
+    scores, fin, first, prev = scores.contiguous(), fin.contiguous(), first.contiguous(), prev.contiguous()
+    _dev(visited, "visited", torch.int32)
+    if tuple(visited.shape) != (B, fw):
+        raise ValueError("visited must be [%d, %d]" % (B, fw))
+    visited = visited.contiguous()
+    if follows is not None:
+        _dev(follows, "follows", torch.int32)
+        if follows.dim() != 3 or not follows.is_contiguous() or follows.size(0) < nw or tuple(follows.shape[1:]) != (L, fw):
+            raise ValueError("follows must be a contiguous [>= %d, %d, %d] tensor" % (nw, L, fw))
+    dev = logits.device
+    i32 = lambda: torch.empty(B, device=dev, dtype=torch.int32)
+    out = dict({"parent": i32(), "next": i32(), "scores": torch.empty(B, device=dev, dtype=torch.float32), "fin": i32(),
+                "dead_end": i32(), "open": i32(), "first": i32(), "prev": i32(),
+                "visited": torch.empty((B, fw), device=dev, dtype=torch.int32),
+                "mask_rows": torch.zeros((B, S), device=dev, dtype=torch.uint8)}, **out)
+    if counter is not None:
+        _dev(counter, "counter", torch.int32)
+    # (L = 0: no edge key, nothing of the table or the visited words is read -- one word each so that the pointers are not null)
+    one, two = torch.zeros(1, device=dev, dtype=torch.int32), torch.zeros(1, device=dev, dtype=torch.int32)
+    fol = one if (follows is not None and not (L and fw)) else follows
+    d = _L.BeamSequenceConstrainedStep(
+        _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), G, width, gpw, _p(fol), L, flags, ntok, sep, eos,
+        1 if stop == "best" else 0, _p(scores), _p(fin), _p(first), _p(prev), _p(visited if fw else one),
+        _p(out["scores"]), _p(out["fin"]), _p(out["dead_end"]), _p(out["open"]), _p(out["first"]), _p(out["prev"]),
+        _p(out["visited"] if fw else two), _p(out["mask_rows"]), _p(out["parent"]), _p(out["next"]), _p(memory), E, _p(rows), E,
+        _p(stats), _p(counter))
+    _L.check(_L.load().ff_beam_sequence_constrained_select(C.byref(d), _stream()), "ff_beam_sequence_constrained_select")
+    return out
+
+
+@_on_tensor_device
 def gather_rows(memory, tok, seqs_per_group=1):
     _dev(memory, "memory"), _dev(tok, "tok", torch.int32)
     N, S, E = memory.shape

@@ -103,6 +103,8 @@ class SurfaceFormerBase(nn.Module):
                                        # built with constrain_tol; inputs["follow_table"] overrides it
         self.sequence_constrain_samples = 0   # ... with sequence_constrain: R in 1..64 = R independent draws per WIREFRAME from the row
                                        # the rule leaves, under sample_temperature / sample_top_k / sample_top_p; 0 = greedy
+        self.sequence_constrain_beams = 0     # ... with sequence_constrain: W in 1..8 = the W best rows per WIREFRAME among the rows the
+                                       # rule leaves, under sequence_beam_stop; 0 = greedy
         self.sequence_faces = False    # single-sequence model: "parse" / "enclosed" = the decoded rows also leave as faces, on the device
                                        # (inputs["sequence_faces"]: ops.face_seq_rows + ops.face_seq_votes behind the decode,
                                        # DESIGN.md 31); "enclosed" walks the enclosure rule on the follow table (constrain_tol) and
@@ -345,7 +347,7 @@ class SurfaceFormerBase(nn.Module):
         if P is not None and (isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= max(T // 2, 1)):
             raise ValueError("sequence_faces_slots=%r: must be None or in 1..max(label_seq_length // 2, 1) = %d" % (P, max(T // 2, 1)))
         G = max(int(getattr(self, "sequence_samples", 0) or 0), int(getattr(self, "sequence_beams", 0) or 0),
-                int(getattr(self, "sequence_constrain_samples", 0) or 0), 1)
+                int(getattr(self, "sequence_constrain_samples", 0) or 0), int(getattr(self, "sequence_constrain_beams", 0) or 0), 1)
         if G * (max(T // 2, 1) if P is None else P) > _faces.FACE_MAX_ROWS:
             raise ValueError("sequence_faces: %d rows x %d slots per wireframe are above %d; lower sequence_faces_slots" % (
                 G, max(T // 2, 1) if P is None else P, _faces.FACE_MAX_ROWS))
@@ -414,6 +416,10 @@ class SurfaceFormerBase(nn.Module):
                                  % ((mode.subject, mode.sequence.model_has) + mode.sequence.parallel_has))
         if parallel and getattr(self, "sequence_constrain_samples", 0):      # (an option of sequence_constrain, refused above)
             mode = _modes.SEQUENCE_CONSTRAIN_SAMPLE
+            raise ValueError("%s is a SurfaceFormer option (%s); SurfaceFormer_Parallel %s per anchor with %s"
+                             % ((mode.subject, mode.sequence.model_has) + mode.sequence.parallel_has))
+        if parallel and getattr(self, "sequence_constrain_beams", 0):        # (likewise)
+            mode = _modes.SEQUENCE_CONSTRAIN_BEAM
             raise ValueError("%s is a SurfaceFormer option (%s); SurfaceFormer_Parallel %s per anchor with %s"
                              % ((mode.subject, mode.sequence.model_has) + mode.sequence.parallel_has))
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
@@ -521,6 +527,8 @@ class SurfaceFormerBase(nn.Module):
             raise ValueError("score() excludes constrain_samples: set model.constrain_samples = 0 to score given paths")
         if getattr(self, "sequence_constrain_samples", 0):     # (likewise an option of sequence_constrain)
             raise ValueError("score() excludes sequence_constrain_samples: set model.sequence_constrain_samples = 0 to score given paths")
+        if getattr(self, "sequence_constrain_beams", 0):
+            raise ValueError("score() excludes sequence_constrain_beams: set model.sequence_constrain_beams = 0 to score given paths")
         if not self.engine_supported():
             raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
         eng, memory, mask, kv_len = self._encode(inputs)

@@ -76,6 +76,13 @@ class SurfaceFormer(SurfaceFormerBase):
         draw 0; embedding as above; no pointer.  Refused wherever sequence_constrain is, and with sequence_samples or
         sequence_beams (ValueError).
 
+        sequence_constrain_beams = W in 1..8 (only with sequence_constrain; 0: the decode above): the W best rows per
+        wireframe among the rows the rule leaves, under sequence_beam_stop ("all" / "best").  Every beam carries its own state of the
+        rule.  Adds predict_beams, predict_beam_dead_end N x W x T, predict_beam_scores, predict_beam_finished,
+        predict_beam_open_end N x W; predict, predict_dead_end and predict_open_end are beam 0 (no predict_logprob); embedding as
+        above; no pointer.  Refused wherever sequence_constrain is, and with sequence_samples, sequence_beams or
+        sequence_constrain_samples (ValueError).
+
         sequence_faces = "parse" / "enclosed" (default False): also inputs["sequence_faces"], a dict of device
         tensors -- len, start, type, closed, loops, score, dup_of, take, row_best, rep, votes, best, major N x G x P, edges, loop_of
         N x G x T, set_bits N x G x P x ceil(L/32), count N x G, num_faces N -- made by two launches behind the decode from the rows
@@ -183,12 +190,19 @@ class SurfaceFormer(SurfaceFormerBase):
             mode.sequence.model_values(self, value, inputs)
             found = (mode, value)
         # sequence_constrain's option: read behind the recorded refusals above, which keep their texts
-        R = _modes.sequence_constrain_samples_value(getattr(self, "sequence_constrain_samples", 0),
-                                                    found[1] if found[0] is _modes.SEQUENCE_CONSTRAIN else None,
+        SC = found[1] if found[0] is _modes.SEQUENCE_CONSTRAIN else None
+        R = _modes.sequence_constrain_samples_value(getattr(self, "sequence_constrain_samples", 0), SC,
                                                     getattr(self, "sequence_samples", 0), getattr(self, "sequence_beams", 0))
         if R:
             found = (_modes.SEQUENCE_CONSTRAIN_SAMPLE, R)
             found[0].sequence.model_values(self, R, inputs)
+        # sequence_constrain's other option, likewise behind the recorded refusals
+        W = _modes.sequence_constrain_beams_value(getattr(self, "sequence_constrain_beams", 0), SC,
+                                                  getattr(self, "sequence_samples", 0), getattr(self, "sequence_beams", 0),
+                                                  getattr(self, "sequence_constrain_samples", 0))
+        if W:
+            found = (_modes.SEQUENCE_CONSTRAIN_BEAM, W)
+            found[0].sequence.model_values(self, W, inputs)
         return found
 
     def _forward_eval_sequence(self, inputs, eng, memory, mask, kv_len, T, mode, value, G):

@@ -1631,6 +1631,113 @@ int ff_decode_sequence_constrained_sample(const ff_model* m, const ff_decode_par
                                           void* workspace, size_t workspace_bytes,
                                           const ff_sequence_constrain_sample_params* constrain_sample, ff_stream_t stream);
 
+/* ---- beam search over the loop-constrained single-sequence decode (opt-in, FF_SEQ2SEQ; entries added within ABI 105)
+ * The W best complete, loop-valid rows per wireframe in one pass, off one encoding and one set of cross-attention K | V:
+ * ff_decode_sequence_beam's search over the rows ff_pointer_sequence_constrained's rule leaves, every beam carrying the rule's
+ * state through the parent permutation as ff_decode_constrained_beam's beams do.  ff_pointer_sequence_constrained's rule and
+ * ff_decode_sequence_beam's search apply wherever this section does not restate them.
+ *
+ * Layout and state
+ *   - The decode runs N*W sequences.  Beam k of wireframe w is row w*W + k, so w = b / W.  One group is one wireframe.
+ *   - Start state: every beam holds SOS; beam 0 has score 0; the other beams are empty (-inf) and contribute no candidates; every
+ *     beam has the rule's empty, closed state.
+ *   - Each beam carries its own state: visited (fw words), first, prev; a finished flag; a loop-open flag; one dead-end flag per
+ *     position.
+ * Candidates per step and group
+ *   - An empty beam contributes none.
+ *   - A finished beam contributes itself: token 0, score unchanged.
+ *   - An unfinished beam forms the rule's byte row, exactly as ff_pointer_sequence_constrained does: the plain rule with the
+ *     range [SEP, SEP+1); SEP alone re-opened at a dead end; with the loop closed, EOS opened and SEP masked while prev == none;
+ *     ONCE keeps visited across SEP.  It then masks and reduces the logit row with that byte row as the extra mask.
+ *   - It contributes its live keys only (l[s] > -FLT_MAX), each at c_k + (l[s] - m) - log sum exp(l - m): fp32, saturated at
+ *     -FLT_MAX; the model's distribution renormalised over the keys the rule allows, as in ff_decode_constrained_beam.
+ *   - A masked key is never a candidate.
+ *   - A row with no live key contributes token 0 at c_k - log S (ff_decode_constrained_beam's clause).
+ *   - At a dead end the beam's only candidate is SEP, at its own score.
+ * Order, ties, empty ranks
+ *   - ff_decode_beam's / ff_decode_sequence_beam's rules: higher score first, then the lower flat index k*S + s.
+ *   - A group with fewer than W candidates leaves its last ranks empty: parent = own index, token 0, score -inf, flags clear,
+ *     (first, prev, visited) those of the own index.
+ * New beam i with parent p and token tk (p unfinished; a finished p hands everything on unchanged, with token 0)
+ *     tk               (first, prev)                         visited_out[i]
+ *     an edge          the rule's three-step update of p's   visited_in[p] | bit(tk)
+ *     SEP              both none                             visited_in[p] under ONCE, else 0
+ *     anything else    p's                                   copy of p's
+ *   - fin_out[i] = fin_in[p] | (tk == EOS).
+ *   - dead_now[i] = p was unfinished and dead-ended at this step.
+ *   - open[i] = a loop is open after the update (first != none).
+ *   - A dead end abandons the face, not the beam.  This differs from ff_decode_constrained_beam, and it is
+ *     ff_pointer_sequence_constrained's rule.
+ *   - All state is read from *_in arrays and written to *_out arrays (ping-pong).  No beam may read a sibling's overwritten
+ *     state: visited_out must not be visited_in.
+ * Stop
+ *   - ff_decode_sequence_beam's two rules; both are compile-time forms of the launch.
+ *   - stop_best = 0 ("all"): the counter is "non-empty beams unfinished after the step".
+ *   - stop_best = 1 ("best"): the counter is "groups whose rank 0 is unfinished after the step".  Exact for beam 0 as there:
+ *     every renormalised log-probability is <= 0.
+ * Outputs
+ *   - beams [N*W, T] int64: best first, walked back through the parents from the stop step, zero past each beam's EOS and past
+ *     the stop step.
+ *   - scores [N*W] fp32 and finished [N*W] int32.
+ *   - beam_dead_end [N*W, T] int32: the per-position flags walked back along the same parents as the tokens.
+ *   - beam_open_end [N*W] int32.
+ *   - predict [N, T] int64, dead_end [N, T] int32 and open_end [N] int32, all equal to beam 0's.
+ *   - *steps_done and step_counts; trace_parent (optional) [T-1, N*W] with trace_logits (optional) [T-1, N*W, S]: the CONSTRAINED
+ *     masked row of every non-empty beam unfinished before the step (seq_of_row [N*W]).
+ *   - No per-position log-probability is published.
+ * Identities
+ *   - W = 1, either stop rule: the ff_decode_sequence_constrained decode with the same flags (tokens, dead_end, open_end and steps
+ *     exact; |score - sum of its logprob| <= (T-1) * 2^-16).
+ *   - All flag bits clear: the ff_decode_sequence_beam decode with the same stop rule, wherever every group has at least W live
+ *     keys (beams, scores, finished, steps and step_counts bit for bit; the byte rows are zero; no dead end).
+ * A known property: renormalised scores favour beams that pass through tightly constrained states, and a dead-end step costs
+ * log-probability 0.  beam_dead_end is published so that a caller can filter.
+ *
+ * ff_beam_sequence_constrained_select: one step of every group, described by ff_beam_sequence_constrained_step
+ *   (ff_beam_constrained_step's members with tok_sep / tok_eos in place of the terminator range, stop_best, this step's dead_out
+ *   and open_out, and no dead_in).  count_unfinished (optional) += the counter of the chosen rule.
+ * ff_decode_sequence_constrained_beam: ff_decode_sequence_sample's argument list; then ff_sequence_constrain_beam_params.  A
+ *   micro-batch holds chunk_max_seqs / W wireframes (at least one).
+ * FF_ERR_ARG before any launch, every output untouched, for everything ff_decode_sequence_beam and ff_decode_sequence_constrained
+ * refuse, for W outside 1..8 or above S, for visited_out equal to visited_in and for a NULL output.
+ * ff_decode_sequence_constrained_beam_workspace_bytes: ff_decode_sequence_beam's workspace plus, taken last, the per-step dead and
+ * open records, the ping-pong state (first, prev [2, N*W]; visited [2, N*W, ceil(L/32)]; step s reads half s & 1) and the byte
+ * rows (0 for what the entry refuses).  Every other entry launches and lays out what it did before these. */
+typedef struct ff_beam_sequence_constrained_step {
+  float* logits; int ldlogits; int S;
+  const unsigned char* mask; const int* kv_len;
+  int groups, width, groups_per_wireframe;
+  const unsigned int* follows; int L, flags, ntok, tok_sep, tok_eos, stop_best;
+  const float* scores_in; const int *fin_in, *first_in, *prev_in; const unsigned int* visited_in;
+  float* scores_out; int *fin_out, *dead_out, *open_out, *first_out, *prev_out; unsigned int* visited_out;
+  unsigned char* mask_rows;
+  int *parent, *next_tok;
+  const float* memory; int E; float* next_rows; int ldnext; float* next_stats;
+  int* count_unfinished;
+} ff_beam_sequence_constrained_step;
+int ff_beam_sequence_constrained_select(const ff_beam_sequence_constrained_step* step, ff_stream_t stream);
+typedef struct ff_sequence_constrain_beam_params {
+  int width;
+  int stop_best;
+  int flags;
+  const unsigned int* follows;
+  int tok_sep;
+  int64_t* beams;
+  float* scores;
+  int* finished;
+  int* beam_dead_end;
+  int* beam_open_end;
+  int* dead_end;
+  int* open_end;
+  int* trace_parent;
+} ff_sequence_constrain_beam_params;
+size_t ff_decode_sequence_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width);
+int ff_decode_sequence_constrained_beam(const ff_model* m, const ff_decode_params* p,
+                                        const float* memory, const unsigned char* mask, const int* kv_len,
+                                        int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
+                                        void* workspace, size_t workspace_bytes, const ff_sequence_constrain_beam_params* beam,
+                                        ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,7 +171,8 @@ def score_batch(model, batch):
 
 def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_scores=None, samples=None, dead_end=None,
               constrained_beams=None, constrained_samples=None, device_faces=None, sequence_samples=None, sequence_beams=None,
-              sequence_device_faces=None, sequence_constrained=None, sequence_constrained_samples=None):
+              sequence_device_faces=None, sequence_constrained=None, sequence_constrained_samples=None,
+              sequence_constrained_beams=None):
     """(JSON text, (precision, recall, type accuracy)) of one decoded sample (reference trainer.py:118-136, 210-300).
     logprob (--scores; laid out like pred): the record also gets `pred_face_scores`, parallel to `pred_faces` -- for every
     de-duplicated face the best sum of log-probabilities among the decoded faces with its edge set (faces.py: *_scored).
@@ -214,7 +215,11 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
     dead-end flags [R, T]) of this sample): the record also gets `pred_sample_faces`, `pred_sample_face_scores` and
     `pred_sample_face_votes` as under --sequence-samples, over the faces that were not abandoned at a dead end
     (faces.parse_faces_constrained_samples_scored); `pred_faces` stays what draw 0 (pred) gives, and `pred_dead_ends` /
-    `pred_unclosed` are counted over ALL draws."""
+    `pred_unclosed` are counted over ALL draws.
+    sequence_constrained_beams (--sequence-constrain-beams, single-sequence model; (tokens [W, T], scores [W], finished flags [W],
+    dead-end flags [W, T]) of this sample): the record also gets `pred_beam_faces` and `pred_beam_face_scores` as under
+    --sequence-beams, over the faces that were not abandoned at a dead end (faces.parse_faces_constrained_beams_scored);
+    `pred_faces` stays what beam 0 (pred) gives, and `pred_dead_ends` / `pred_unclosed` are counted over beam 0."""
     if sequence_device_faces is not None:
         return _record_of_sequence_device(cfg, raw, item, sequence_device_faces, logprob is not None, sequence_beams is not None,
                                           sequence_samples is not None)
@@ -319,6 +324,12 @@ def record_of(cfg, raw, item, pred, parallel, logprob=None, beams=None, label_sc
         rec["pred_dead_ends"] = int(dead.astype(bool).sum())
         rec["pred_unclosed"] = sum(1 for _, idx in own
                                    if not FZ.is_face_enclosed(raw["edges"], idx, cfg.post_process.enclosedness_tol))
+    if sequence_constrained_beams is not None:
+        toks, bsc, bfin, dead = (np.asarray(v) for v in sequence_constrained_beams)
+        bf = FZ.parse_faces_constrained_beams_scored(toks, bsc, bfin, dead, len(raw["edges"]), cfg.model.token)
+        ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
+        rec["pred_beam_faces"] = FZ._plain([(t, idx) for t, idx, _, _ in ranked])
+        rec["pred_beam_face_scores"] = [s for _, _, s, _ in ranked]
     if sequence_beams is not None:
         bf = FZ.parse_faces_beams_scored(sequence_beams[0], sequence_beams[1], sequence_beams[2], len(raw["edges"]), cfg.model.token)
         ranked = sorted(FZ.unique_faces_with_scores(bf), key=lambda f: -f[2])       # (stable: first seen wins among equal scores)
@@ -402,7 +413,7 @@ def _record_of_sequence_device(cfg, raw, item, rows, scored, beams, samples):
 def configure_model(model, retire_finished=False, fp16=False, scores=False, beam=0, sample=0, temperature=1.0, top_k=0, top_p=1.0,
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
                     constrain_samples=0, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0, sequence_beam_stop="all",
-                    sequence_constrain=None, sequence_constrain_samples=0):
+                    sequence_constrain=None, sequence_constrain_samples=0, sequence_constrain_beams=0):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
@@ -415,7 +426,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     seed, beam search with `sequence_beams` beams per wireframe of the single-sequence model under the stop rule
     `sequence_beam_stop`, the loop-constrained greedy decode of the single-sequence model (sequence_constrain
     "no_repeat" / "loops" / "coedge_loops" with the end-point tolerance constrain_tol), `sequence_constrain_samples`
-    draws per wireframe from the keys that rule allows under temperature / top_k / top_p / seed.
+    draws per wireframe from the keys that rule allows under temperature / top_k / top_p / seed,
+    `sequence_constrain_beams` beams per wireframe over those keys under the stop rule `sequence_beam_stop`.
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -460,6 +472,9 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.sequence_constrain_samples = int(sequence_constrain_samples)
         model.sample_temperature, model.sample_top_k, model.sample_top_p = float(temperature), int(top_k), float(top_p)
         model.sample_seed = int(seed)
+    if sequence_constrain_beams:
+        model.sequence_constrain_beams = int(sequence_constrain_beams)
+        model.sequence_beam_stop = str(sequence_beam_stop)
     return model
 
 
@@ -467,7 +482,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
              retire_finished=False, fp16=False, scores=False, beam=0, score_labels=False, sample=0, temperature=1.0, top_k=0,
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
              constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0,
-             sequence_beam_stop="all", sequence_device_faces=False, sequence_constrain=None, sequence_constrain_samples=0):
+             sequence_beam_stop="all", sequence_device_faces=False, sequence_constrain=None, sequence_constrain_samples=0,
+             sequence_constrain_beams=0):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -502,7 +518,25 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     sequence_constrain_samples = R (1..64, only with sequence_constrain and refused with whatever it refuses, single-rank runs
     only) draws R rows per wireframe from the keys that rule allows under temperature / top_k / top_p / seed and
     adds pred_sample_faces / pred_sample_face_scores / pred_sample_face_votes, with pred_dead_ends / pred_unclosed over all
-    draws; pred_faces stays draw 0's."""
+    draws; pred_faces stays draw 0's; sequence_constrain_beams = W (1..8, only with sequence_constrain and refused with whatever it
+    refuses and with sequence_constrain_samples, single-rank runs only) searches the W best rows per wireframe over
+    the keys that rule allows under sequence_beam_stop and adds pred_beam_faces / pred_beam_face_scores, with pred_dead_ends /
+    pred_unclosed over beam 0; pred_faces stays beam 0's."""
+    if sequence_constrain_beams:
+        if isinstance(sequence_constrain_beams, bool) or not isinstance(sequence_constrain_beams, int) \
+                or not 1 <= sequence_constrain_beams <= 8:
+            raise ValueError("--sequence-constrain-beams must be a width in 1..8")
+        if sequence_beam_stop not in ("all", "best"):
+            raise ValueError("--sequence-beam-stop must be all or best")
+        if cfg.model_class != "SurfaceFormer":
+            raise ValueError("--sequence-constrain-beams applies to SurfaceFormer only (SurfaceFormer_Parallel searches under its rule "
+                             "with --constrain-beams)")
+        if sequence_constrain is None:
+            raise ValueError("--sequence-constrain-beams requires --sequence-constrain")
+        if sequence_constrain_samples:
+            raise ValueError("--sequence-constrain-beams does not combine with --sequence-constrain-samples")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--sequence-constrain-beams is not implemented for multi-rank runs")
     if sequence_constrain_samples:
         if isinstance(sequence_constrain_samples, bool) or not isinstance(sequence_constrain_samples, int) \
                 or not 1 <= sequence_constrain_samples <= 64:
@@ -614,6 +648,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     if sequence_constrain_samples:
         configure_model(model, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                         sequence_constrain_samples=sequence_constrain_samples)
+    if sequence_constrain_beams:
+        configure_model(model, sequence_beam_stop=sequence_beam_stop, sequence_constrain_beams=sequence_constrain_beams)
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
@@ -645,6 +681,9 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         wanted.append(("sequence_constrained", ("predict_dead_end",)))
     if sequence_constrain_samples:
         wanted.append(("sequence_constrained_samples", ("predict_samples", "predict_sample_logprob", "predict_sample_dead_end")))
+    if sequence_constrain_beams:
+        wanted.append(("sequence_constrained_beams", ("predict_beams", "predict_beam_scores", "predict_beam_finished",
+                                                      "predict_beam_dead_end")))
     if device_faces:
         wanted.append(("device_faces", ("faces",)))
     if sequence_device_faces:
@@ -799,6 +838,12 @@ def build_parser():
                              "pred_sample_face_votes (faces abandoned at a dead end left out), pred_dead_ends / pred_unclosed count "
                              "over all draws, pred_faces stays draw 0's; single-process runs only, refused with whatever "
                              "--sequence-constrain refuses")
+    parser.add_argument("--sequence-constrain-beams", type=int, default=0, metavar="W",
+                        help="with --sequence-constrain {no_repeat,loops,coedge_loops}: search the W (1..8) best rows per wireframe "
+                             "over the keys the face-loop rule allows, under --sequence-beam-stop (DESIGN.md 34); every JSON record "
+                             "gains pred_beam_faces / pred_beam_face_scores (faces abandoned at a dead end left out), pred_dead_ends / "
+                             "pred_unclosed count over beam 0, pred_faces stays beam 0's; single-process runs only, refused with "
+                             "whatever --sequence-constrain refuses and with --sequence-constrain-samples")
     parser.add_argument("--constrain-beam-closure", choices=("lookahead", "exact"), default=None,
                         help="with --constrain loops --constrain-beams W: the beam search forms every beam's row under the closure "
                              "look-ahead (lookahead) or its exact form (exact), so that the W beams are searched among loops that "
@@ -829,7 +874,7 @@ def main(argv=None):
              constrain_beam_closure=args.constrain_beam_closure, sequence_samples=args.sequence_samples,
              sequence_beams=args.sequence_beams, sequence_beam_stop=args.sequence_beam_stop,
              sequence_device_faces=args.sequence_device_faces, sequence_constrain=args.sequence_constrain,
-             sequence_constrain_samples=args.sequence_constrain_samples)
+             sequence_constrain_samples=args.sequence_constrain_samples, sequence_constrain_beams=args.sequence_constrain_beams)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 
