@@ -19,13 +19,14 @@
 // order) -- and every sync_every steps the host drops the finished sequences from it (compact_chunks below).  The slots of a
 // chunk keep the w = i / Fc structure with a smaller Fc, so attention, masks and kv_len are addressed as before.
 //
-// The opt-in decodes are the same run with another selection in place of the greedy pointer launch: a Mode (below) names the
-// kind, its sequences per anchor and its parameters; every kind is one case of the switches in layout_decode, init_state, select_step
-// and pack, behind one plan (plan_mode), one size query (decode_workspace_bytes) and one step head (step_head).  Their per-step
+// The opt-in decodes are the same run with another selection in place of the greedy pointer launch: a Mode (below) holds how a
+// token is picked, which rule masks the row, whether the call is a single-sequence entry, the sequences per anchor and the operands
+// and outputs; layout_decode, init_state, select_step and pack branch on those facts, behind one plan (plan_mode), one size query
+// (decode_workspace_bytes), one step head (step_head) and one check of the entries' arguments (check_entry).  Their per-step
 // records lie last in the workspace, named by role in DecodeBuffers (score, finished, parent, dead, first, prev, visited,
 // byte_rows, ...), and the output is packed from the records up to the stop step.  select_step fills ONE ff_step_io (ff_common.h:
-// what every selection launch takes) per step; a case adds its mode's records and parameters.  The cases of constrain and
-// constrained beam share the rule's operands (rule_of), those of beam and constrained beam the parent trace and the reorder.
+// what every selection launch takes) per step; a branch adds its records and operands.  The ruled branches share the rule's
+// operands (rule_of) and the look-ahead's, the beam branches the parent trace and the reorder.
 //   beam (ff_decode_beam): W sequences per anchor -- beam k of compact anchor a is chunk-local sequence a * W + k,
 //     so a chunk's Fc / Bc are W times its anchor counts and w = i / Fc holds.  ff_beam_select (+ ff_beam_reorder of the x0 /
 //     qkv0 prefixes); records (token, parent, score, finished).
@@ -371,61 +372,64 @@ int plan_streams(const ff_decode_params* p) {
   return p->num_streams < 1 ? 1 : (p->num_streams > FF_MAX_STREAMS ? FF_MAX_STREAMS : p->num_streams);
 }
 
-// What a decode call runs in place of the greedy pointer launch: the kind, the sequences per anchor (W beams, R samples, else
-// 1) and that kind's parameters (null in a size query, which needs the kind and G only).
+// What a decode call runs in place of the greedy pointer launch, as three independent facts -- how a token is picked, which rule
+// masks the row, whether the call is a single-sequence entry -- plus the sequences per anchor G (W beams, R samples, else 1) and
+// the operands and outputs that go with them.  Every entry resolves its own parameter struct into this ONCE per call; the engine
+// branches on the facts and reads the fields, never on which entry it was.  A size query fills pick, rule, sequence and G only.
+// A NEW MODE fills in: pick / rule / sequence / G; the operands of its rule (flags, follows, tok_sep), look-ahead (ahead,
+// close_dist, cycle_len) and draw (uniforms, temperature, top_k, top_p); `op`, the name its selection launch reports errors under;
+// every output pack() is to write (null: the mode has none).  Its entry also says in its Entry record whether all it requires is
+// there.  If the combination of facts is new, layout_decode, init_state, select_step and pack each get the one branch it needs.
 struct Mode {
-  enum Kind { GREEDY, BEAM, FORCED, SAMPLE, CONSTRAIN, CONSTRAIN_BEAM, CONSTRAIN_AHEAD, CONSTRAIN_EXACT, CONSTRAIN_SAMPLE, CONSTRAIN_BEAM_AHEAD, SEQ_SAMPLE, SEQ_BEAM, SEQ_CONSTRAIN, SEQ_CONSTRAIN_SAMPLE, SEQ_CONSTRAIN_BEAM } kind;
+  enum Pick { POINTER, FORCED, ARGMAX, DRAW, BEAM };   // the greedy pointer launch / the caller's token / the rule's arg-max / a draw / top-W
+  enum Rule { NONE, LOOP, SEQUENCE };                  // no rule / the parallel loop rule (terminator range) / the sequence rule (SEP, EOS)
+  Pick pick;
+  Rule rule;
+  bool sequence;   // a ff_decode_sequence_* entry: F = 1, every row from SOS, no num_input, stops at the first step whose counter is 0
   int G;
-  const void* prm;
-  Mode(Kind k = GREEDY, int g = 1, const void* params = nullptr) : kind(k), G(g), prm(params) {}
-  const ff_beam_params* beam() const { return static_cast<const ff_beam_params*>(prm); }          // (each for its own kind only)
-  const ff_sequence_beam_params* seqbeam() const { return static_cast<const ff_sequence_beam_params*>(prm); }
-  const ff_forced_params* forced() const { return static_cast<const ff_forced_params*>(prm); }
-  const ff_sample_params* sample() const { return static_cast<const ff_sample_params*>(prm); }   // (SAMPLE and SEQ_SAMPLE)
-  const ff_constrain_ahead_params* ahead() const { return static_cast<const ff_constrain_ahead_params*>(prm); }
-  const ff_constrain_exact_params* exact() const { return static_cast<const ff_constrain_exact_params*>(prm); }
-  // (CONSTRAIN, CONSTRAIN_AHEAD and CONSTRAIN_EXACT: the four parameters the three share)
-  ff_constrain_params con() const {
-    if (kind == CONSTRAIN_EXACT) return ff_constrain_params{exact()->flags, exact()->follows, exact()->logprob, exact()->dead_end};
-    if (kind != CONSTRAIN_AHEAD) return *static_cast<const ff_constrain_params*>(prm);
-    return ff_constrain_params{ahead()->flags, ahead()->follows, ahead()->logprob, ahead()->dead_end};
-  }
-  const ff_constrain_beam_ahead_params* cbeam_ahead() const { return static_cast<const ff_constrain_beam_ahead_params*>(prm); }
-  // (CONSTRAIN_BEAM and CONSTRAIN_BEAM_AHEAD: the parameters the two share)
-  bool is_cbeam() const { return kind == CONSTRAIN_BEAM || kind == CONSTRAIN_BEAM_AHEAD; }
-  bool is_sequence() const { return kind == SEQ_SAMPLE || kind == SEQ_BEAM || kind == SEQ_CONSTRAIN || kind == SEQ_CONSTRAIN_SAMPLE || kind == SEQ_CONSTRAIN_BEAM; }   // (the ff_decode_sequence_* entries)
-  ff_constrain_beam_params cbeam() const {
-    if (kind != CONSTRAIN_BEAM_AHEAD) return *static_cast<const ff_constrain_beam_params*>(prm);
-    const ff_constrain_beam_ahead_params* q = cbeam_ahead();
-    return ff_constrain_beam_params{q->width, q->flags, q->follows, q->beams, q->scores, q->dead_end, q->trace_parent};
-  }
-  const ff_constrain_sample_params* csample() const { return static_cast<const ff_constrain_sample_params*>(prm); }
-  const ff_sequence_constrain_params* seqcon() const { return static_cast<const ff_sequence_constrain_params*>(prm); }
-  const ff_sequence_constrain_sample_params* seqcs() const { return static_cast<const ff_sequence_constrain_sample_params*>(prm); }
-  const ff_sequence_constrain_beam_params* seqcb() const { return static_cast<const ff_sequence_constrain_beam_params*>(prm); }
+  int flags = 0, tok_sep = 0;         // the rule's operands
+  const unsigned* follows = nullptr;
+  int ahead = 0;                      // the look-ahead: 0 none, 1 the closure look-ahead, 2 the exact one; the whole batch's tables
+  const unsigned char *close_dist = nullptr, *cycle_len = nullptr;
+  const char* op = nullptr;           // the operator name the step's *_sync launch words its messages with
+  const float* uniforms = nullptr;    // the draw's operands
+  float temperature = 0.f, top_p = 0.f;
+  int top_k = 0;
+  int stop_best = 0;                  // the beam's operands
+  int* trace_parent = nullptr;
+  int64_t* rows = nullptr;            // the outputs: beams / samples ...
+  float *scores = nullptr, *logprob = nullptr, *predict_logprob = nullptr;
+  int *finished = nullptr, *dead_end = nullptr, *open_end = nullptr, *beam_dead_end = nullptr, *beam_open_end = nullptr,
+      *predict_dead_end = nullptr, *predict_open_end = nullptr;
+  const ff_forced_params* forced = nullptr;
+  Mode(Pick k = POINTER, Rule r = NONE, bool seq = false, int g = 1) : pick(k), rule(r), sequence(seq), G(g) {}
+  bool grouped() const { return pick == DRAW || pick == BEAM; }   // G sequences per anchor: the beam decode's plan and layout
 };
+// The groups of fields that several parameter structs spell alike, copied by name.
+template <typename Q> void take_rule(Mode& md, const Q* q) { md.flags = q->flags; md.follows = q->follows; }
+template <typename Q> void take_draw(Mode& md, const Q* q) {
+  md.G = q->num_samples; md.uniforms = q->uniforms; md.temperature = q->temperature; md.top_k = q->top_k; md.top_p = q->top_p;
+  md.rows = q->samples; md.logprob = q->logprob; md.scores = q->scores;
+}
+template <typename Q> void take_beam(Mode& md, const Q* q) {
+  md.G = q->width; md.rows = q->beams; md.scores = q->scores; md.trace_parent = q->trace_parent;
+}
+template <typename Q> void take_ahead(Mode& md, int form, const Q* q, const unsigned char* close_dist) {
+  md.ahead = form; md.close_dist = close_dist; md.cycle_len = q->cycle_len;
+}
 
-// The micro-batch plan of a mode: the default plan for greedy and constrain; without de-duplication for forced (the rows are
-// arbitrary paths: sequence b of the plan is row b); over the anchors, G times as wide, for beam and sample.
+// The micro-batch plan of a mode: over the anchors, G times as wide, where G sequences per anchor exist (with FF_SEQ2SEQ a
+// micro-batch is cut by sequences: chunk_max_seqs / G wireframes, at least one); without de-duplication for forced (the rows are
+// arbitrary paths: sequence b of the plan is row b); the default plan otherwise.
 void plan_mode(const ff_decode_params* p, const int* num_input_host, int ns, const Mode& mode, std::vector<Chunk>* out, int* btot,
                int* max_bc, int* nchunks = nullptr) {
-  switch (mode.kind) {
-    case Mode::BEAM:
-    case Mode::CONSTRAIN_BEAM:
-    case Mode::CONSTRAIN_BEAM_AHEAD:
-    case Mode::CONSTRAIN_SAMPLE:
-    case Mode::SEQ_SAMPLE:   // (FF_SEQ2SEQ: a micro-batch is cut by sequences, chunk_max_seqs / R wireframes, at least one)
-    case Mode::SEQ_BEAM:     // (likewise: chunk_max_seqs / W wireframes, at least one)
-    case Mode::SEQ_CONSTRAIN_SAMPLE:   // (SEQ_SAMPLE's plan)
-    case Mode::SEQ_CONSTRAIN_BEAM:     // (SEQ_BEAM's plan)
-    case Mode::SAMPLE: return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
-    case Mode::FORCED: {
-      ff_decode_params q = *p;
-      q.flags &= ~FF_DEDUP_PAD_ANCHORS;
-      return plan_chunks(&q, nullptr, ns, out, btot, max_bc, nchunks);
-    }
-    default: return plan_chunks(p, num_input_host, ns, out, btot, max_bc, nchunks);
+  if (mode.grouped()) return plan_beam_chunks(p, num_input_host, ns, mode.G, out, btot, max_bc, nchunks);
+  if (mode.pick == Mode::FORCED) {
+    ff_decode_params q = *p;
+    q.flags &= ~FF_DEDUP_PAD_ANCHORS;
+    return plan_chunks(&q, nullptr, ns, out, btot, max_bc, nchunks);
   }
+  return plan_chunks(p, num_input_host, ns, out, btot, max_bc, nchunks);
 }
 
 // The tuning knobs that shape a decode, read ONCE per ff_decode / ff_decode_workspace_bytes call: the workspace
@@ -465,8 +469,10 @@ bool can_fuse_layernorm(const ff_model* m, const ff_decode_params* prm) {
 
 // Workspace layout for `btot` compact sequences in micro-batches of at most `max_bc`.
 // want_lp: also the log-probability rows (ff_decode_lp) -- taken LAST, so that everything else lies where it lies without them.
-// mode: also the per-step records of a beam, forced, sampled (with its row_id array) or constrained (with its state) decode,
-// last as well.
+// mode: also its per-step records, last as well -- one ordered sequence of takes, each behind the fact that asks for it: score,
+// finished; parent under a beam; dead under a rule; open under a beam with the sequence rule; the rule's first and prev (per step,
+// or the two ping-pong halves under a beam); row_id for a draw; the rule's visited words (both halves under a beam) and byte rows.
+// Forced has three arrays of its own.
 size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineKnobs& kn, size_t Btot, size_t Bch, size_t nch,
                      Bump& bp, DecodeBuffers* out, const Mode& mode, bool want_lp = false) {
   const int E = m->E, FFd = m->FF, S = p->L + m->num_token, T = p->T;
@@ -525,60 +531,27 @@ size_t layout_decode(const ff_model* m, const ff_decode_params* p, const EngineK
   // (every mode's arrays in the order and sizes they always had: tests/test_workspace_layout.py holds the table)
   const size_t TB = (size_t)T * Btot;
   const size_t fw = (size_t)(p->L + 31) / 32, vw = Btot * (fw > 0 ? fw : 1);   // visited words; one word per sequence at L = 0, so that the array is never empty
-  switch (mode.kind) {
-    case Mode::BEAM:
-    case Mode::SEQ_BEAM:
-    case Mode::CONSTRAIN_BEAM:
-    case Mode::SEQ_CONSTRAIN_BEAM:     // (SEQ_BEAM's records, then the constrained beam's and the per-step open record)
-    case Mode::CONSTRAIN_BEAM_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
-      b.score = bp.take<float>(TB);
-      b.finished = bp.take<int>(TB);
-      b.parent = bp.take<int>(TB);
-      if (mode.kind == Mode::BEAM || mode.kind == Mode::SEQ_BEAM) break;
-      b.dead = bp.take<int>(TB);
-      if (mode.kind == Mode::SEQ_CONSTRAIN_BEAM) b.open = bp.take<int>(TB);
-      b.first = bp.take<int>(2 * Btot);     // (the two halves)
-      b.prev = bp.take<int>(2 * Btot);
-      b.visited = bp.take<unsigned>(2 * vw);
-      b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
-      break;
-    case Mode::FORCED: {
-      const size_t n = (size_t)(T - 1 > 0 ? T - 1 : 1) * Btot;
-      b.score = bp.take<float>(n);
-      b.greedy = bp.take<int>(n);
-      b.rank = bp.take<int>(n);
-      break;
+  const bool beam = mode.pick == Mode::BEAM, ruled = mode.rule != Mode::NONE;
+  if (mode.pick == Mode::FORCED) {
+    const size_t n = (size_t)(T - 1 > 0 ? T - 1 : 1) * Btot;
+    b.score = bp.take<float>(n);
+    b.greedy = bp.take<int>(n);
+    b.rank = bp.take<int>(n);
+  } else if (mode.pick != Mode::POINTER) {   // (the tables of a look-ahead are operands: nothing of it lies here)
+    b.score = bp.take<float>(TB);
+    b.finished = bp.take<int>(TB);
+    if (beam) b.parent = bp.take<int>(TB);
+    if (ruled) b.dead = bp.take<int>(TB);
+    if (beam && mode.rule == Mode::SEQUENCE) b.open = bp.take<int>(TB);
+    if (ruled) {   // (per step; under a beam the two halves)
+      b.first = bp.take<int>(beam ? 2 * Btot : TB);
+      b.prev = bp.take<int>(beam ? 2 * Btot : TB);
     }
-    case Mode::SAMPLE:
-    case Mode::SEQ_SAMPLE:
-      b.score = bp.take<float>(TB);
-      b.finished = bp.take<int>(TB);
-      b.row_id = bp.take<int>(Btot);
-      break;
-    case Mode::CONSTRAIN:
-    case Mode::SEQ_CONSTRAIN:     // (constrain's records with F = 1: one sequence per wireframe)
-    case Mode::CONSTRAIN_EXACT:
-    case Mode::CONSTRAIN_AHEAD:   // (the tables of the look-ahead are operands: nothing of it lies here)
-      b.score = bp.take<float>(TB);
-      b.finished = bp.take<int>(TB);
-      b.dead = bp.take<int>(TB);
-      b.first = bp.take<int>(TB);
-      b.prev = bp.take<int>(TB);
-      b.visited = bp.take<unsigned>(vw);
+    if (mode.pick == Mode::DRAW) b.row_id = bp.take<int>(Btot);
+    if (ruled) {
+      b.visited = bp.take<unsigned>(beam ? 2 * vw : vw);
       b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
-      break;
-    case Mode::SEQ_CONSTRAIN_SAMPLE:   // (likewise: SEQ_CONSTRAIN's records per sequence of SEQ_SAMPLE's plan)
-    case Mode::CONSTRAIN_SAMPLE:   // (constrain's records per sequence of the sampled plan; row_id, visited and the byte rows last)
-      b.score = bp.take<float>(TB);
-      b.finished = bp.take<int>(TB);
-      b.dead = bp.take<int>(TB);
-      b.first = bp.take<int>(TB);
-      b.prev = bp.take<int>(TB);
-      b.row_id = bp.take<int>(Btot);
-      b.visited = bp.take<unsigned>(vw);
-      b.byte_rows = bp.take<unsigned char>(Btot * (size_t)S);
-      break;
-    default: break;
+    }
   }
   if (out) *out = b;
   return bp.off;
@@ -902,7 +875,7 @@ struct DecodeRun {
   int forced_steps = 0;                       // ... and the largest of those
   int validate(const ff_model* m_, const ff_decode_params* p_, const DecodeIO& io_, const void* workspace) {
     m = m_; io = io_;
-    const bool forced = mode.kind == Mode::FORCED;
+    const bool forced = mode.pick == Mode::FORCED;
     FF_RETURN_IF(check_model(m));
     FF_CHECK_ARG(p_ != nullptr, "ff_decode: null params");
     FF_CHECK_ARG(p_->variant == FF_PARALLEL || p_->variant == FF_SEQ2SEQ, "ff_decode: bad variant");
@@ -963,10 +936,10 @@ struct DecodeRun {
     fin_dev = buf.fin;
     slots_per_step.reserve((size_t)T);   // (the loop below allocates nothing per step)
     tot.reserve((size_t)T);
-    if (mode.kind == Mode::FORCED) {   // (the plan has no de-duplication: sequence b0 + i of a chunk is row b0 + i of the paths)
+    if (mode.pick == Mode::FORCED) {   // (the plan has no de-duplication: sequence b0 + i of a chunk is row b0 + i of the paths)
       for (const Chunk& c : chunks) {
         int mx = 0;
-        for (int i = 0; i < c.Bc; ++i) mx = mode.forced()->lengths_host[c.b0 + i] > mx ? mode.forced()->lengths_host[c.b0 + i] : mx;
+        for (int i = 0; i < c.Bc; ++i) mx = mode.forced->lengths_host[c.b0 + i] > mx ? mode.forced->lengths_host[c.b0 + i] : mx;
         chunk_steps.push_back(mx);
         forced_steps = mx > forced_steps ? mx : forced_steps;
       }
@@ -1090,7 +1063,7 @@ struct DecodeRun {
     }
     // start tokens (anchors / SOS) and first decoder input rows of every micro-batch
     for (const Chunk& c : chunks) {
-      if (mode.kind != Mode::GREEDY) {
+      if (mode.pick != Mode::POINTER) {
         FF_RETURN_IF(init_state(c));
         FF_RETURN_IF(ff_gather_rows(memory + (size_t)c.w0 * S * E, S, E, buf.tok_all + c.b0, c.Bc, c.Fc, c.x0, E, sts[c.sid]));
         continue;
@@ -1106,86 +1079,52 @@ struct DecodeRun {
     }
     return FF_OK;
   }
-  // The loop rule's operands of one micro-batch in the constrained modes: the flags, the chunk's part of the follow table
-  // and the words per row of it (= per sequence of `visited`).
+  // The rule's operands of one micro-batch: the flags, the chunk's part of the follow table and the words per row of it (= per
+  // sequence of `visited`).
   struct Rule { const unsigned* follows; int L, fw, flags; };
   Rule rule_of(const Chunk& c) const {
     const int L = p->L, fw = (L + 31) / 32;
-    const unsigned* follows;
-    int flags;
-    switch (mode.kind) {
-      case Mode::CONSTRAIN_BEAM:
-      case Mode::CONSTRAIN_BEAM_AHEAD: follows = mode.cbeam().follows; flags = mode.cbeam().flags; break;
-      case Mode::CONSTRAIN_SAMPLE: follows = mode.csample()->follows; flags = mode.csample()->flags; break;
-      case Mode::SEQ_CONSTRAIN: follows = mode.seqcon()->follows; flags = mode.seqcon()->flags; break;
-      case Mode::SEQ_CONSTRAIN_SAMPLE: follows = mode.seqcs()->follows; flags = mode.seqcs()->flags; break;
-      case Mode::SEQ_CONSTRAIN_BEAM: follows = mode.seqcb()->follows; flags = mode.seqcb()->flags; break;
-      default: follows = mode.con().follows; flags = mode.con().flags; break;
-    }
-    return Rule{follows ? follows + (size_t)c.w0 * L * fw : nullptr, L, fw, flags};
+    return Rule{mode.follows ? mode.follows + (size_t)c.w0 * L * fw : nullptr, L, fw, mode.flags};
   }
-  // The look-ahead of the constrained greedy, sampled and beam modes: the form (0 none, 1 the closure look-ahead, 2 the
-  // exact one) and the whole batch's tables as the caller gave them.
-  struct Ahead { int form; const unsigned char *close_dist, *cycle_len; };
-  Ahead ahead_of() const {
-    switch (mode.kind) {
-      case Mode::CONSTRAIN_AHEAD: return Ahead{1, mode.ahead()->close_dist, mode.ahead()->cycle_len};
-      case Mode::CONSTRAIN_EXACT: return Ahead{2, nullptr, mode.exact()->cycle_len};
-      case Mode::CONSTRAIN_SAMPLE: return Ahead{mode.csample()->lookahead, mode.csample()->close_dist, mode.csample()->cycle_len};
-      case Mode::CONSTRAIN_BEAM_AHEAD:
-        return Ahead{mode.cbeam_ahead()->lookahead, mode.cbeam_ahead()->close_dist, mode.cbeam_ahead()->cycle_len};
-      default: return Ahead{0, nullptr, nullptr};
-    }
-  }
-  // Row 0 of the mode's per-step records and of the token array for one micro-batch: the start state of its sequences.
+  // Row 0 of the mode's per-step records and of the token array for one micro-batch: the start state of its sequences.  The
+  // parallel entries start at the anchors (Fc / G of them per wireframe); the sequence entries have Fc = G rows per wireframe,
+  // every one at SOS, the rule's state empty and closed.  Under a beam the rule's state is half 0 of the ping-pong: step 0 reads it.
   int init_state(const Chunk& c) {
     const int G = mode.G, pad_tok = m->num_token - 1;
     const int* ni = io.num_input ? io.num_input + c.w0 : nullptr;
     hipStream_t st = sts[c.sid];
-    if (mode.kind == Mode::FORCED) return FF_OK;   // (the start tokens are row 0 of the token array, forced_tokens() put the paths there)
+    if (mode.pick == Mode::FORCED) return FF_OK;   // (the start tokens are row 0 of the token array, forced_tokens() put the paths there)
+    const bool beam = mode.pick == Mode::BEAM, draw = mode.pick == Mode::DRAW, seq = mode.sequence;
     int* tok = buf.tok_all + c.b0;
     float* score = buf.score + c.b0;
     int* fin = buf.finished + c.b0;
-    switch (mode.kind) {
-      case Mode::BEAM:
-        return ff_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok, p->term_lo, p->term_hi, st);
-      case Mode::SAMPLE:
-        return ff_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F, ni, pad_tok, p->term_lo, p->term_hi, st);
-      case Mode::SEQ_BEAM:   // (Fc = W beams per wireframe)
-        return ff_sequence_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, G, p->tok_sos, st);
-      case Mode::SEQ_SAMPLE:   // (Fc = R draws per wireframe)
-        return ff_sequence_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, G, c.w0, p->tok_sos, st);
-      case Mode::SEQ_CONSTRAIN:   // (every sequence at SOS, the rule's state empty and closed)
-        return ff_sequence_constrain_init(tok, score, fin, buf.dead + c.b0, buf.first + c.b0, buf.prev + c.b0,
-                                          buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), c.Bc, p->L, p->tok_sos, st);
-      case Mode::SEQ_CONSTRAIN_SAMPLE:   // (Fc = R draws per wireframe, every one at SOS with the rule's state empty and closed)
-        return ff_sequence_constrain_sample_init(tok, score, fin, buf.dead + c.b0, buf.first + c.b0, buf.prev + c.b0,
-                                                 buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), buf.row_id + c.b0, c.Bc, G, c.w0, p->L,
-                                                 p->tok_sos, st);
-      case Mode::SEQ_CONSTRAIN_BEAM:   // (Fc = W beams per wireframe, the rule's state empty and closed: half 0 of the ping-pong)
-        return ff_sequence_constrain_beam_init(tok, score, fin, buf.dead + c.b0, buf.open + c.b0, buf.parent + c.b0, buf.first + c.b0,
-                                               buf.prev + c.b0, buf.visited + (size_t)c.b0 * ((p->L + 31) / 32), c.Bc, G, p->L, p->tok_sos,
-                                               st);
-      case Mode::CONSTRAIN:
-      case Mode::CONSTRAIN_AHEAD:
-      case Mode::CONSTRAIN_EXACT:
-      case Mode::CONSTRAIN_SAMPLE:
-      case Mode::CONSTRAIN_BEAM_AHEAD:
-      case Mode::CONSTRAIN_BEAM: {   // (constrained beam: half 0 of the ping-pong state, step 0 reads it)
-        const Rule r = rule_of(c);
-        int *dead = buf.dead + c.b0, *first = buf.first + c.b0, *prev = buf.prev + c.b0;
-        unsigned* visited = buf.visited + (size_t)c.b0 * r.fw;
-        if (mode.is_cbeam())
-          return ff_constrain_beam_init(tok, score, fin, dead, buf.parent + c.b0, first, prev, visited, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok,
-                                        p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
-        if (mode.kind == Mode::CONSTRAIN_SAMPLE)
-          return ff_constrain_sample_init(tok, score, fin, dead, first, prev, visited, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F,
-                                          ni, pad_tok, p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
-        return ff_constrain_init(tok, score, fin, dead, first, prev, visited, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo, p->term_hi,
-                                 m->num_token, r.follows, r.L, st);
-      }
-      default: return FF_OK;
+    if (mode.rule == Mode::NONE) {
+      if (beam)
+        return seq ? ff_sequence_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, G, p->tok_sos, st)
+                   : ff_beam_init(tok, score, fin, buf.parent + c.b0, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok, p->term_lo, p->term_hi, st);
+      return seq ? ff_sequence_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, G, c.w0, p->tok_sos, st)
+                 : ff_sample_init(tok, score, fin, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F, ni, pad_tok, p->term_lo, p->term_hi, st);
     }
+    const Rule r = rule_of(c);
+    int *dead = buf.dead + c.b0, *first = buf.first + c.b0, *prev = buf.prev + c.b0;
+    unsigned* visited = buf.visited + (size_t)c.b0 * r.fw;
+    if (seq) {
+      if (beam)
+        return ff_sequence_constrain_beam_init(tok, score, fin, dead, buf.open + c.b0, buf.parent + c.b0, first, prev, visited, c.Bc, G, p->L,
+                                               p->tok_sos, st);
+      if (draw)
+        return ff_sequence_constrain_sample_init(tok, score, fin, dead, first, prev, visited, buf.row_id + c.b0, c.Bc, G, c.w0, p->L,
+                                                 p->tok_sos, st);
+      return ff_sequence_constrain_init(tok, score, fin, dead, first, prev, visited, c.Bc, p->L, p->tok_sos, st);
+    }
+    if (beam)
+      return ff_constrain_beam_init(tok, score, fin, dead, buf.parent + c.b0, first, prev, visited, c.Bc, c.Fc / G, G, c.f0, ni, pad_tok,
+                                    p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
+    if (draw)
+      return ff_constrain_sample_init(tok, score, fin, dead, first, prev, visited, buf.row_id + c.b0, c.Bc, c.Fc / G, G, c.f0, c.w0, F,
+                                      ni, pad_tok, p->term_lo, p->term_hi, m->num_token, r.follows, r.L, st);
+    return ff_constrain_init(tok, score, fin, dead, first, prev, visited, c.Bc, c.Fc, c.f0, ni, pad_tok, p->term_lo, p->term_hi,
+                             m->num_token, r.follows, r.L, st);
   }
   // Decode step `step` (position t = step + 1) of every micro-batch that has slots left, on the chunk's stream: the slot set
   // decoded now is Fl / Bl wide (the chunk's Fc / Bc without retirement).
@@ -1203,7 +1142,7 @@ struct DecodeRun {
       // (retirement: the logits rows are in slot order; a traced step scatters them to the sequences' rows below)
       float* logits_dst = (io.trace_logits && !retire) ? io.trace_logits + trow * S : sc.logits;
       // (the greedy pointer launch makes its own dot products when the head is not folded)
-      if (mode.kind == Mode::GREEDY)
+      if (mode.pick == Mode::POINTER)
         FF_RETURN_IF(decoder_pass(m, p, kn, buf, sc, c, c.Fl, c.Bl, io.mask, io.kv_len, t, false, nullptr, st,
                                   folded_head ? logits_dst : nullptr));
       else
@@ -1222,6 +1161,22 @@ struct DecodeRun {
     return ff_gemm_f32_batched(sc.p, E, nullptr, 0, io.memory + (size_t)c.w0 * S * E, E, nullptr, nullptr, 0, logits_dst, S, Fc, S, E, 0,
                                0, c.nw, (long long)Fc * E, (long long)S * E, (long long)Fc * S, st);
   }
+  // What the two constrained-beam step descriptors have in common: the rule, the records of step `step` in and of position
+  // t = step + 1 out, the rule's state from half step & 1 to half t & 1, the byte rows, the parent and token rows.
+  template <typename D>
+  void fill_beam_step(D* d, const Chunk& c, const Rule& r, int step) const {
+    const int t = step + 1;
+    const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
+    const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
+    memset(d, 0, sizeof(*d));
+    d->width = mode.G; d->follows = r.follows; d->L = r.L; d->flags = r.flags; d->ntok = m->num_token;
+    d->scores_in = buf.score + in; d->fin_in = buf.finished + in;
+    d->first_in = buf.first + hin; d->prev_in = buf.prev + hin; d->visited_in = buf.visited + hin * r.fw;
+    d->scores_out = buf.score + out; d->fin_out = buf.finished + out; d->dead_out = buf.dead + out;
+    d->first_out = buf.first + hout; d->prev_out = buf.prev + hout; d->visited_out = buf.visited + hout * r.fw;
+    d->mask_rows = buf.byte_rows + (size_t)c.b0 * S;
+    d->parent = buf.parent + out; d->next_tok = buf.tok_all + out;
+  }
   // The selection of step `step` (position t = step + 1) of one micro-batch from its logits.  Every opt-in launch reads the
   // mode's state row `step` and writes row t, the chunk's next x0 rows (with their statistics) and -- but for the forced one,
   // which counts nothing -- the stop counter; a step enqueued past the stop writes rows that nothing reads.
@@ -1232,117 +1187,65 @@ struct DecodeRun {
     const int* kv_w = io.kv_len + c.w0;
     const size_t in = (size_t)step * Btot + c.b0, out = (size_t)t * Btot + c.b0;
     float* next_rows = c.x0 + (size_t)t * c.Bl * E;   // (Bl = Bc but under retirement, which every opt-in mode excludes)
-    const bool hand_over = lagged && mode.kind != Mode::FORCED;   // (a forced step counts nothing: its slot and trow are not used)
+    const bool forced = mode.pick == Mode::FORCED, beam = mode.pick == Mode::BEAM, draw = mode.pick == Mode::DRAW;
+    const bool hand_over = lagged && !forced;   // (a forced step counts nothing: its slot and trow are not used)
     int* arrive = hand_over ? buf.arrive + slot : nullptr;
     int* host_slot = hand_over ? pool->hpin_dev + slot : nullptr;
     // what every opt-in launch takes: the chunk's logits, masks and memory, its Bc rows, the next x0 rows and the stop counter
     const ff_step_io sio{logits_dst, S, S, mask_w, kv_w, c.Bc, c.Fc, p->term_lo, p->term_hi, m->num_token, mem_w, E, next_rows, E, c.x0stat,
-                         mode.kind != Mode::FORCED ? buf.cnt_ge + slot : nullptr, arrive, host_slot};
+                         !forced ? buf.cnt_ge + slot : nullptr, arrive, host_slot};
     int* tok_out = buf.tok_all + out;
-    switch (mode.kind) {
-      case Mode::BEAM:
-      case Mode::SEQ_BEAM:
-      case Mode::SEQ_CONSTRAIN_BEAM:
-      case Mode::CONSTRAIN_BEAM:
-      case Mode::CONSTRAIN_BEAM_AHEAD: {
-        // top-W selection, then the reorder of positions < t of x0 and qkv0 behind it on the same stream: the next decoder pass
-        // reads reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
-        const int W = mode.G;
-        int* trace_parent;
-        if (mode.kind == Mode::BEAM || mode.kind == Mode::SEQ_BEAM) {   // (SEQ_BEAM: the same launch in a sequence form, its counter "all" or "best")
-          const bool sq = mode.kind == Mode::SEQ_BEAM;
-          trace_parent = sq ? mode.seqbeam()->trace_parent : mode.beam()->trace_parent;
+    if (forced)   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
+      return ff_pointer_forced_sync(sio, tok_out, buf.score + in, buf.greedy + in, buf.rank + in, st);
+    if (mode.pick != Mode::POINTER) {   // (a draw or an arg-max arm returns from its launch; a beam arm goes on to the beam tail below)
+      const int W = mode.G, rows = N * F * mode.G;   // (rows: the uniforms of one step, read through the chunk's row_id)
+      if (mode.rule == Mode::NONE) {   // (a sequence entry: the same launch in its sequence form, which counts otherwise)
+        if (beam)
           FF_RETURN_IF(ff_beam_select_sync(sio, W, buf.score + in, buf.score + out, buf.finished + in, buf.finished + out, nullptr, 0, t,
-                                           buf.parent + out, tok_out, st, sq ? (mode.seqbeam()->stop_best ? 2 : 1) : 0));
-        } else if (mode.kind == Mode::SEQ_CONSTRAIN_BEAM) {   // the sequence rule per beam: state half step & 1 -> half t & 1
-          const ff_sequence_constrain_beam_params* q = mode.seqcb();
-          trace_parent = q->trace_parent;
-          const Rule r = rule_of(c);
-          const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
-          ff_beam_sequence_constrained_step d;
-          memset(&d, 0, sizeof(d));
-          d.width = W; d.follows = r.follows; d.L = r.L; d.flags = r.flags; d.ntok = m->num_token;
-          d.tok_sep = q->tok_sep; d.tok_eos = p->tok_eos; d.stop_best = q->stop_best;
-          d.scores_in = buf.score + in; d.fin_in = buf.finished + in;
-          d.first_in = buf.first + hin; d.prev_in = buf.prev + hin; d.visited_in = buf.visited + hin * r.fw;
-          d.scores_out = buf.score + out; d.fin_out = buf.finished + out; d.dead_out = buf.dead + out; d.open_out = buf.open + out;
-          d.first_out = buf.first + hout; d.prev_out = buf.prev + hout; d.visited_out = buf.visited + hout * r.fw;
-          d.mask_rows = buf.byte_rows + (size_t)c.b0 * S;
-          d.parent = buf.parent + out; d.next_tok = tok_out;
-          FF_RETURN_IF(ff_beam_sequence_constrained_select_sync(sio, &d, st));
-        } else {   // the constrained selection: state half step & 1 -> half t & 1 (the common operands come from sio)
-          trace_parent = mode.cbeam().trace_parent;
-          const Rule r = rule_of(c);
-          const size_t hin = (size_t)(step & 1) * Btot + c.b0, hout = (size_t)(t & 1) * Btot + c.b0;
-          ff_beam_constrained_step d;
-          memset(&d, 0, sizeof(d));
-          d.width = W; d.follows = r.follows; d.L = r.L; d.flags = r.flags; d.ntok = m->num_token;
-          d.scores_in = buf.score + in; d.fin_in = buf.finished + in; d.dead_in = buf.dead + in;
-          d.first_in = buf.first + hin; d.prev_in = buf.prev + hin; d.visited_in = buf.visited + hin * r.fw;
-          d.scores_out = buf.score + out; d.fin_out = buf.finished + out; d.dead_out = buf.dead + out;
-          d.first_out = buf.first + hout; d.prev_out = buf.prev + hout; d.visited_out = buf.visited + hout * r.fw;
-          d.mask_rows = buf.byte_rows + (size_t)c.b0 * S;
-          d.parent = buf.parent + out; d.next_tok = tok_out;
-          // the look-aheads: this step selects position t, so a loop has T - 1 - t further positions to close in
-          const Ahead la = ahead_of();
-          const ff_lookahead_io ahead{la.form == 1 ? la.close_dist + (size_t)c.w0 * r.L * r.L : nullptr,
-                                      la.form ? la.cycle_len + (size_t)c.w0 * r.L : nullptr, T - 1 - t, la.form == 2 ? 1 : 0};
-          FF_RETURN_IF(ff_beam_constrained_select_sync(la.form ? "ff_beam_constrained_select_ahead" : "ff_beam_constrained_select", sio,
-                                                       &d, la.form ? &ahead : nullptr, st));
-        }
-        if (trace_parent)
-          FF_CHECK_HIP(hipMemcpyAsync(trace_parent + trow, buf.parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
-        if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.parent + out, c.Bc / W, W, st));
-        return FF_OK;
-      }
-      case Mode::SEQ_SAMPLE:   // (the same launch in its sequence form: the counter is "rows unfinished after the step")
-      case Mode::SAMPLE: {   // (this step's uniforms are read through the chunk's row_id)
-        const ff_sample_params* sp = mode.sample();
-        const int rows = N * F * mode.G;
-        return ff_pointer_sample_sync(sio, sp->uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, buf.finished + in, sp->temperature,
-                                      sp->top_k, sp->top_p, tok_out, buf.score + out, buf.finished + out, st, mode.kind == Mode::SEQ_SAMPLE);
-      }
-      case Mode::CONSTRAIN:
-      case Mode::CONSTRAIN_EXACT:
-      case Mode::CONSTRAIN_AHEAD:
-      case Mode::CONSTRAIN_SAMPLE: {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
+                                           buf.parent + out, tok_out, st, mode.sequence ? (mode.stop_best ? 2 : 1) : 0));
+        else
+          return ff_pointer_sample_sync(sio, mode.uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, buf.finished + in,
+                                        mode.temperature, mode.top_k, mode.top_p, tok_out, buf.score + out, buf.finished + out, st,
+                                        mode.sequence);
+      } else {
         const Rule r = rule_of(c);
-        const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
-                                      buf.byte_rows + (size_t)c.b0 * S, tok_out, buf.score + out, buf.finished + out, buf.dead + out,
-                                      buf.first + out, buf.prev + out};
         const ff_loop_rule_io rio{r.follows, r.L, r.flags, m->num_token};
         // the look-aheads: this step selects position t, so a loop has T - 1 - t further positions to close in
-        const Ahead la = ahead_of();
-        const ff_lookahead_io ahead{la.form == 1 ? la.close_dist + (size_t)c.w0 * r.L * r.L : nullptr,
-                                    la.form ? la.cycle_len + (size_t)c.w0 * r.L : nullptr, T - 1 - t, la.form == 2 ? 1 : 0};
-        if (mode.kind == Mode::CONSTRAIN_SAMPLE) {   // (this step's uniforms are read through the chunk's row_id)
-          const ff_constrain_sample_params* q = mode.csample();
-          const int rows = N * F * mode.G;
-          const ff_sample_draw_io draw{q->uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, q->temperature, q->top_k, q->top_p};
-          return ff_pointer_constrained_sample_sync("ff_pointer_constrained_sample", sio, rio, cs, la.form ? &ahead : nullptr, draw, st);
+        const ff_lookahead_io ahead{mode.ahead == 1 ? mode.close_dist + (size_t)c.w0 * r.L * r.L : nullptr,
+                                    mode.ahead ? mode.cycle_len + (size_t)c.w0 * r.L : nullptr, T - 1 - t, mode.ahead == 2 ? 1 : 0};
+        const ff_lookahead_io* la = mode.ahead ? &ahead : nullptr;
+        if (beam) {   // the rule per beam: state half step & 1 -> half t & 1 (the common operands come from sio)
+          if (mode.sequence) {
+            ff_beam_sequence_constrained_step d;
+            fill_beam_step(&d, c, r, step);
+            d.tok_sep = mode.tok_sep; d.tok_eos = p->tok_eos; d.stop_best = mode.stop_best;
+            d.open_out = buf.open + out;
+            FF_RETURN_IF(ff_beam_sequence_constrained_select_sync(sio, &d, st));
+          } else {
+            ff_beam_constrained_step d;
+            fill_beam_step(&d, c, r, step);
+            d.dead_in = buf.dead + in;
+            FF_RETURN_IF(ff_beam_constrained_select_sync(mode.op, sio, &d, la, st));
+          }
+        } else {   // (the visited words and the byte rows belong to the sequence and are rewritten in stream order)
+          const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
+                                        buf.byte_rows + (size_t)c.b0 * S, tok_out, buf.score + out, buf.finished + out, buf.dead + out,
+                                        buf.first + out, buf.prev + out};
+          if (draw) {   // (this step's uniforms are read through the chunk's row_id)
+            const ff_sample_draw_io dio{mode.uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, mode.temperature, mode.top_k, mode.top_p};
+            return mode.sequence ? ff_pointer_sequence_constrained_sample_sync(sio, rio, cs, mode.tok_sep, p->tok_eos, dio, st)
+                                 : ff_pointer_constrained_sample_sync(mode.op, sio, rio, cs, la, dio, st);
+          }
+          return mode.sequence ? ff_pointer_sequence_constrained_sync(sio, rio, cs, mode.tok_sep, p->tok_eos, st)   // (SEP and EOS in place of a terminator range)
+                               : ff_pointer_constrained_sync(mode.op, sio, rio, cs, la, st);
         }
-        static const char* const op[3] = {"ff_pointer_constrained", "ff_pointer_constrained_ahead", "ff_pointer_constrained_exact"};
-        return ff_pointer_constrained_sync(op[la.form], sio, rio, cs, la.form ? &ahead : nullptr, st);
       }
-      case Mode::SEQ_CONSTRAIN_SAMPLE:
-      case Mode::SEQ_CONSTRAIN: {   // (constrain's state and records; the rule has SEP and EOS in place of a terminator range)
-        const Rule r = rule_of(c);
-        const ff_constrained_state cs{buf.finished + in, buf.first + in, buf.prev + in, buf.visited + (size_t)c.b0 * r.fw,
-                                      buf.byte_rows + (size_t)c.b0 * S, tok_out, buf.score + out, buf.finished + out, buf.dead + out,
-                                      buf.first + out, buf.prev + out};
-        if (mode.kind == Mode::SEQ_CONSTRAIN_SAMPLE) {   // (this step's uniforms are read through the chunk's row_id)
-          const ff_sequence_constrain_sample_params* q = mode.seqcs();
-          const int rows = N * mode.G;
-          const ff_sample_draw_io draw{q->uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, q->temperature, q->top_k, q->top_p};
-          return ff_pointer_sequence_constrained_sample_sync(sio, ff_loop_rule_io{r.follows, r.L, r.flags, m->num_token}, cs, q->tok_sep,
-                                                             p->tok_eos, draw, st);
-        }
-        return ff_pointer_sequence_constrained_sync(sio, ff_loop_rule_io{r.follows, r.L, r.flags, m->num_token}, cs, mode.seqcon()->tok_sep,
-                                                    p->tok_eos, st);
-      }
-      case Mode::FORCED:   // scores position t of the paths and appends THAT token's row; its records have T - 1 rows: row `step`
-        return ff_pointer_forced_sync(sio, tok_out, buf.score + in, buf.greedy + in, buf.rank + in, st);
-      default: break;
+      // the beam tail (only the beam arms above get here): behind a top-W selection, the reorder of positions < t of x0 and qkv0 on the same stream: the next decoder pass reads
+      // reordered prefixes only.  (Nothing reads the prefixes after the last step: no reorder there.)
+      if (mode.trace_parent)
+        FF_CHECK_HIP(hipMemcpyAsync(mode.trace_parent + trow, buf.parent + out, sizeof(int) * (size_t)c.Bc, hipMemcpyDeviceToDevice, st));
+      if (t < T - 1) FF_RETURN_IF(ff_beam_reorder(c.x0, E, c.qkv0, c.qkv0 ? 3 * E : 0, c.Bc, t, buf.parent + out, c.Bc / W, W, st));
+      return FF_OK;
     }
     ff_pointer_sync psync{each_eos ? buf.seen + c.b0 : nullptr, arrive, host_slot, p->variant == FF_PARALLEL ? 0 : 1, c.x0stat,
                           folded_head ? 1 : 0, c.slot, retire ? fin_dev + c.b0 : nullptr, t, p->term_lo, p->term_hi};
@@ -1358,7 +1261,7 @@ struct DecodeRun {
   }
   // ---- forced decode ------------------------------------------------------------------------------------------------------------
   // The caller's paths as the token array (main stream, in front of the prologue's fork: every stream sees them).
-  int forced_tokens() { return ff_forced_tokens(mode.forced()->paths, buf.tok_all, Btot, T, S, io.main_st); }
+  int forced_tokens() { return ff_forced_tokens(mode.forced->paths, buf.tok_all, Btot, T, S, io.main_st); }
   // Step `step` of every micro-batch that still has a row to score.  Nothing is read back, nothing is counted.
   int forced_loop() {
     for (int step = 0; step < forced_steps; ++step) {
@@ -1384,7 +1287,7 @@ struct DecodeRun {
         FF_CHECK_HIP(hipEventRecord(pool->join_ev[s], sts[s]));
         FF_CHECK_HIP(hipStreamWaitEvent(main_st, pool->join_ev[s], 0));
       }
-    const ff_forced_params* fp = mode.forced();
+    const ff_forced_params* fp = mode.forced;
     FF_RETURN_IF(ff_forced_finalize(buf.tok_all, buf.score, buf.greedy, buf.rank, fp->lengths, Btot, T, fp->logprob, fp->greedy,
                                     fp->rank, fp->seq_logprob, main_st));
     FF_CHECK_HIP(hipStreamSynchronize(main_st));   // (the caller may free or reuse the workspace next, as after ff_decode)
@@ -1395,7 +1298,7 @@ struct DecodeRun {
   // num_token of unfinished rows), for the sequence sample mode (rows unfinished after the step) and for the sequence beam mode
   // (non-empty beams, or rank-0 beams, unfinished after the step); cnt_eq and the cumulative EOS count otherwise.
   bool zero_rule() const {
-    return p->variant == FF_PARALLEL || mode.is_sequence();
+    return p->variant == FF_PARALLEL || mode.sequence;
   }
   // the stop rule over the first n steps' counters, per_chunk = [n][nch]
   bool stop_rule(const int* per_chunk, int n) {
@@ -1531,58 +1434,41 @@ struct DecodeRun {
   int pack(const Chunk& c) {
     const hipStream_t main_st = io.main_st;
     const int G = mode.G, dd = dedup ? 1 : 0;
-    switch (mode.kind) {
-      case Mode::SEQ_BEAM: {   // (F = 1, no de-duplication: num_input is not read; also the finished flags of the stop step's row)
-        const ff_sequence_beam_params* q = mode.seqbeam();
-        return ff_beam_finalize(buf.tok_all, buf.parent, buf.score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G,
-                                c.f0, c.b0, q->beams, q->scores, io.predict, io.seq_of_row, main_st, buf.finished, q->finished);
-      }
-      case Mode::SEQ_CONSTRAIN_BEAM: {   // (F = 1, no de-duplication; tokens and dead flags along one walk, the rest from the stop step's row)
-        const ff_sequence_constrain_beam_params* q = mode.seqcb();
+    const bool ruled = mode.rule != Mode::NONE;
+    // (the sequence entries: F = 1, no de-duplication, num_input is not read; forced: forced_epilogue packs all rows at once)
+    if (mode.pick == Mode::BEAM) {
+      if (mode.sequence && ruled)   // (tokens and dead flags along one walk, the rest from the stop step's row)
         return ff_sequence_constrain_beam_finalize(buf.tok_all, buf.parent, buf.score, buf.finished, buf.dead, buf.open, Btot, T,
-                                                   buf.steps_dev, G, c.w0, c.nw, c.b0, q->beams, q->scores, q->finished, q->beam_dead_end,
-                                                   q->beam_open_end, io.predict, q->dead_end, q->open_end, io.seq_of_row, main_st);
-      }
-      case Mode::BEAM:
-      case Mode::CONSTRAIN_BEAM:
-      case Mode::CONSTRAIN_BEAM_AHEAD: {
-        const bool con = mode.is_cbeam();
-        FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.parent, buf.score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
-                                      c.Fc / G, c.f0, c.b0, con ? mode.cbeam().beams : mode.beam()->beams,
-                                      con ? mode.cbeam().scores : mode.beam()->scores, io.predict, io.seq_of_row, main_st));
-        if (!con) return FF_OK;
-        return ff_constrain_beam_dead(buf.dead, Btot, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G, c.f0, c.b0,
-                                      mode.cbeam().dead_end, main_st);
-      }
-      case Mode::SEQ_SAMPLE:   // (F = 1, no de-duplication: num_input is not read)
-      case Mode::SAMPLE:
+                                                   buf.steps_dev, G, c.w0, c.nw, c.b0, mode.rows, mode.scores, mode.finished,
+                                                   mode.beam_dead_end, mode.beam_open_end, io.predict, mode.dead_end, mode.open_end,
+                                                   io.seq_of_row, main_st);
+      // (a sequence entry: also the finished flags of the stop step's row)
+      FF_RETURN_IF(ff_beam_finalize(buf.tok_all, buf.parent, buf.score, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G,
+                                    c.f0, c.b0, mode.rows, mode.scores, io.predict, io.seq_of_row, main_st,
+                                    mode.sequence ? buf.finished : nullptr, mode.finished));
+      if (!ruled) return FF_OK;
+      return ff_constrain_beam_dead(buf.dead, Btot, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw, c.Fc / G, c.f0, c.b0, mode.dead_end,
+                                    main_st);
+    }
+    if (mode.pick == Mode::DRAW) {
+      if (!ruled)
         return ff_sample_finalize(buf.tok_all, buf.score, buf.finished, Btot, T, buf.steps_dev, io.num_input, dd, F, G, c.w0, c.nw,
-                                  c.Fc / G, c.f0, c.b0, mode.sample()->samples, mode.sample()->logprob, mode.sample()->scores, io.predict,
-                                  io.seq_of_row, main_st);
-      case Mode::CONSTRAIN:
-      case Mode::CONSTRAIN_AHEAD:
-      case Mode::CONSTRAIN_EXACT:
-        return ff_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
-                                     c.nw, c.Fc, c.f0, c.b0, io.predict, mode.con().logprob, mode.con().dead_end, io.seq_of_row, main_st);
-      case Mode::SEQ_CONSTRAIN: {   // (F = 1, no de-duplication: num_input is not read)
-        const ff_sequence_constrain_params* q = mode.seqcon();
-        return ff_sequence_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, buf.first, Btot, T, buf.steps_dev, c.w0, c.nw,
-                                              c.b0, io.predict, q->logprob, q->dead_end, q->open_end, io.seq_of_row, main_st);
-      }
-      case Mode::SEQ_CONSTRAIN_SAMPLE: {   // (F = 1, no de-duplication: num_input is not read)
-        const ff_sequence_constrain_sample_params* q = mode.seqcs();
+                                  c.Fc / G, c.f0, c.b0, mode.rows, mode.logprob, mode.scores, io.predict, io.seq_of_row, main_st);
+      if (mode.sequence)
         return ff_sequence_constrain_sample_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, buf.first, Btot, T, buf.steps_dev, G,
-                                                     c.w0, c.nw, c.b0, q->samples, q->logprob, q->scores, q->dead_end, q->open_end,
-                                                     io.predict, q->predict_logprob, q->predict_dead_end, q->predict_open_end,
+                                                     c.w0, c.nw, c.b0, mode.rows, mode.logprob, mode.scores, mode.dead_end, mode.open_end,
+                                                     io.predict, mode.predict_logprob, mode.predict_dead_end, mode.predict_open_end,
                                                      io.seq_of_row, main_st);
-      }
-      case Mode::CONSTRAIN_SAMPLE: {
-        const ff_constrain_sample_params* q = mode.csample();
-        return ff_constrain_sample_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, G,
-                                            c.w0, c.nw, c.Fc / G, c.f0, c.b0, q->samples, q->logprob, q->scores, q->dead_end, io.predict,
-                                            q->predict_logprob, q->predict_dead_end, io.seq_of_row, main_st);
-      }
-      default: break;   // (forced: forced_epilogue packs all rows at once)
+      return ff_constrain_sample_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, G,
+                                          c.w0, c.nw, c.Fc / G, c.f0, c.b0, mode.rows, mode.logprob, mode.scores, mode.dead_end, io.predict,
+                                          mode.predict_logprob, mode.predict_dead_end, io.seq_of_row, main_st);
+    }
+    if (mode.pick == Mode::ARGMAX) {
+      if (mode.sequence)
+        return ff_sequence_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, buf.first, Btot, T, buf.steps_dev, c.w0, c.nw,
+                                              c.b0, io.predict, mode.logprob, mode.dead_end, mode.open_end, io.seq_of_row, main_st);
+      return ff_constrain_finalize(buf.tok_all, buf.score, buf.finished, buf.dead, Btot, T, buf.steps_dev, io.num_input, dd, F, c.w0,
+                                   c.nw, c.Fc, c.f0, c.b0, io.predict, mode.logprob, mode.dead_end, io.seq_of_row, main_st);
     }
     const long total = (long)c.nw * F * T;
     const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
@@ -1635,28 +1521,21 @@ struct DecodeRun {
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
                const Mode& mode);
 
-// What ff_decode_beam, ff_decode_sample and ff_decode_constrained (`name`; `subject`: the option as its message words it) have
-// in common: the combinations they exclude ...
-int check_opt_in(const char* name, const char* subject, const ff_decode_params* p, const unsigned char* extra_mask) {
-  FF_CHECK_ARG(p->variant == FF_PARALLEL, "%s: %s a parallel-variant option", name, subject);
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !extra_mask,
-               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask", name);
-  return FF_OK;
-}
-// ... a terminator range, their own outputs (`required`: their names; have: all given) and none of the greedy call's traces ...
-int check_opt_in_outputs(const char* name, const ff_decode_params* p, const char* required, bool have, const float* trace_best,
-                         const float* trace_second, const float* pointer_out) {
-  FF_CHECK_ARG(p->term_lo < p->term_hi, "%s: empty terminator range [%d, %d)", name, p->term_lo, p->term_hi);
-  FF_CHECK_ARG(have && !trace_best && !trace_second && !pointer_out, "%s: %s required; no best / second traces, no pointer_out", name,
-               required);
-  return FF_OK;
-}
-// ... the loop rule's operands in the three constrained decodes (the operators' own check: flags, follow table, terminator range) ...
-int check_loop_rule(const char* name, int flags, const unsigned* follows, const ff_model* m, const ff_decode_params* p) {
-  return ff_loop_rule_check(name, ff_loop_rule_io{follows, p->L, flags, m->num_token}, p->L + m->num_token, p->term_lo, p->term_hi);
-}
-// ... the look-ahead of a constrained decode (form 1: the closure look-ahead, 2: the exact one), beyond what the step checks:
-// the flag bits and tables of the form, and the limits of the budget's byte and of the exact search ...
+// ---- the opt-in entries --------------------------------------------------------------------------------------------------------
+// The wording of one entry's refusals, kept next to the entry: its name, the option as the variant message words it (parallel
+// entries), the parameter struct as the null message words it, the other variant's entry (sequence entries), the operands and
+// outputs it requires as their message names them.
+struct Entry {
+  const char *name, *subject, *noun, *sibling, *required;
+  int ahead_lo = -1;            // the lowest look-ahead form the caller may choose (0: sampled, 1: beam); -1: the entry fixes the form
+  bool own_draw_text = false;   // ff_decode_sample: temperature / top_k / top_p under its own text, in front of the outputs
+  bool given = false, have = false;   // filled by the entry: its parameter struct is not null; all it requires of it is there
+};
+// What a parallel entry takes from the greedy call's signature only to refuse it (the sequence entries have none of it: null).
+struct Refused { const unsigned char* extra_mask; const float *trace_best, *trace_second, *pointer_out; };
+
+// The look-ahead of a constrained decode (form 1: the closure look-ahead, 2: the exact one), beyond what the step checks: the
+// flag bits and tables of the form, and the limits of the budget's byte and of the exact search.
 int check_lookahead(const char* name, int form, int flags, const unsigned char* close_dist, const unsigned char* cycle_len,
                     const ff_model* m, const ff_decode_params* p) {
   if (form == 1) {
@@ -1673,50 +1552,88 @@ int check_lookahead(const char* name, int form, int flags, const unsigned char* 
   }
   return FF_OK;
 }
-// ... the width of a beam decode, and the staging area of its reorder: ff_beam_reorder stages a group's x0 (+ q|k|v) rows in
-// 64 KB of LDS ...
-int check_beam_width(const char* name, int width, const ff_model* m, const ff_decode_params* p) {
-  FF_CHECK_ARG(width >= 1 && width <= 8 && width <= p->L + m->num_token, "%s: width=%d outside 1..8 or above S=%d", name, width,
-               p->L + m->num_token);
+
+bool sequence_query_ok(const ff_decode_params* p) { return p && p->variant == FF_SEQ2SEQ && p->F == 1; }   // (what the sequence size queries refuse)
+
+// Every opt-in entry's checks, in THE order all of them keep (tests/test_entry_checks.py pins it); a check that the mode's facts
+// do not call for is skipped.
+int check_entry(const Entry& e, const Mode& md, const ff_model* m, const ff_decode_params* p, const Refused& no, const int64_t* predict) {
+  const char* name = e.name;
+  const bool beam = md.pick == Mode::BEAM, draw = md.pick == Mode::DRAW;
+  // 1. the three structs
+  FF_CHECK_ARG(m && p && e.given, "%s: null model, params or %s params", name, e.noun);
+  // 2. the variant, and the combinations the entry excludes
+  if (md.sequence) {
+    FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1, "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has %s",
+                 name, e.sibling);
+    FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
+                 "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
+  } else {
+    FF_CHECK_ARG(p->variant == FF_PARALLEL, "%s: %s a parallel-variant option", name, e.subject);
+    FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP)) && !p->stop_fn && !no.extra_mask,
+                 "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, a stop_fn and an extra mask", name);
+  }
+  const int S = p->L + m->num_token;
+  // 3. the sequences per anchor
+  if (beam) FF_CHECK_ARG(md.G >= 1 && md.G <= 8 && md.G <= S, "%s: width=%d outside 1..8 or above S=%d", name, md.G, S);
+  if (draw) FF_CHECK_ARG(md.G >= 1 && md.G <= 64, "%s: num_samples=%d outside 1..64", name, md.G);
+  if (e.own_draw_text)
+    FF_CHECK_ARG(md.temperature >= 0.f && md.temperature <= 3.402823466e+38f && md.top_k >= 0 && md.top_p > 0.f && md.top_p <= 1.f,
+                 "%s: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]", name, (double)md.temperature, md.top_k,
+                 (double)md.top_p);
+  // 4. the sequence beam's stop rule
+  if (beam && md.sequence) FF_CHECK_ARG(md.stop_best == 0 || md.stop_best == 1, "%s: stop_best=%d must be 0 or 1", name, md.stop_best);
+  // 5. the rule's operands (the operators' own checks: flags, follow table, terminator range or SEP / EOS)
+  const ff_loop_rule_io rio{md.follows, p->L, md.flags, m->num_token};
+  if (md.rule == Mode::LOOP) FF_RETURN_IF(ff_loop_rule_check(name, rio, S, p->term_lo, p->term_hi));
+  if (md.rule == Mode::SEQUENCE) FF_RETURN_IF(ff_sequence_rule_check(name, rio, S, md.tok_sep, p->tok_eos));
+  // 6. the look-ahead
+  if (e.ahead_lo == 0)
+    FF_CHECK_ARG(md.ahead >= 0 && md.ahead <= 2, "%s: lookahead=%d must be 0 (none), 1 (look-ahead) or 2 (exact)", name, md.ahead);
+  if (e.ahead_lo == 1) FF_CHECK_ARG(md.ahead == 1 || md.ahead == 2, "%s: lookahead=%d must be 1 (look-ahead) or 2 (exact)", name, md.ahead);
+  FF_RETURN_IF(check_lookahead(name, md.ahead, md.flags, md.close_dist, md.cycle_len, m, p));
+  // 7. what the entry requires; a parallel entry also a terminator range and none of the greedy call's traces
+  if (md.sequence) {
+    FF_CHECK_ARG(e.have && predict, "%s: %s are required", name, e.required);
+  } else {
+    FF_CHECK_ARG(p->term_lo < p->term_hi, "%s: empty terminator range [%d, %d)", name, p->term_lo, p->term_hi);
+    FF_CHECK_ARG(e.have && !no.trace_best && !no.trace_second && !no.pointer_out, "%s: %s required; no best / second traces, no pointer_out",
+                 name, e.required);
+  }
+  // 8. the sizes (the parallel beam entries have no such check)
+  if (draw || (beam && md.sequence))
+    FF_CHECK_ARG(p->N > 0 && p->F > 0 && (long long)p->N * p->F * md.G < (1LL << 31), "%s: bad sizes", name);
+  // 9. the draw's own check, with the step's text: the uniforms of one step
+  if (draw && !e.own_draw_text) {
+    const int rows = p->N * p->F * md.G;
+    FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{md.uniforms, rows, nullptr, md.temperature, md.top_k, md.top_p}, rows));
+  }
+  // 10. the staging area of a beam's reorder: ff_beam_reorder stages a group's x0 (+ q|k|v) rows in 64 KB of LDS
+  if (beam)
+    FF_CHECK_ARG((size_t)md.G * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
+                 "%s: width=%d at E=%d exceeds the reorder's staging area", name, md.G, m->E);
   return FF_OK;
-}
-int check_beam_staging(const char* name, int width, const ff_model* m, const ff_decode_params* p) {
-  FF_CHECK_ARG((size_t)width * ((p->flags & FF_REUSE_LAYER0_QKV) ? 4 : 1) * (size_t)m->E * sizeof(float) <= 65536,
-               "%s: width=%d at E=%d exceeds the reorder's staging area", name, width, m->E);
-  return FF_OK;
-}
-// ... and what they hand to the decode: no extra mask, no pointer_out, no best / second traces, no log-probabilities.
-DecodeIO opt_in_io(const float* memory, const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host,
-                   int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row, ff_stream_t stream) {
-  return DecodeIO{memory, mask, kv_len, num_input, num_input_host, nullptr, predict, steps_done, step_counts,
-                  nullptr, trace_logits, nullptr, nullptr, seq_of_row, (hipStream_t)stream, nullptr};
 }
 
+// What every decode entry's arguments have in common.  An opt-in entry hands on no extra mask, no pointer_out, no best / second
+// traces and no log-probabilities; a sequence entry has no num_input either.
+struct EntryArgs {
+  const float* memory; const unsigned char* mask; const int *kv_len, *num_input, *num_input_host;
+  int64_t* predict; int *steps_done, *step_counts; float* trace_logits; int* seq_of_row; void* workspace; size_t workspace_bytes;
+  ff_stream_t stream;
+};
 
-// The three single-sequence entries (ff_decode_sequence_*; `params`: the parameter struct as the message words it, `sibling`:
-// the parallel variant's entry): what their size queries refuse, the checks in front of their own ...
-bool sequence_query_ok(const ff_decode_params* p) { return p && p->variant == FF_SEQ2SEQ && p->F == 1; }
-int check_sequence(const char* name, const char* params, const char* sibling, const ff_model* m, const ff_decode_params* p,
-                   const void* prm) {
-  FF_CHECK_ARG(m && p && prm, "%s: null model, params or %s params", name, params);
-  FF_CHECK_ARG(p->variant == FF_SEQ2SEQ && p->F == 1, "%s: a single-sequence option (FF_SEQ2SEQ, F = 1); the parallel variant has %s",
-               name, sibling);
-  FF_CHECK_ARG(!(p->flags & (FF_RETIRE_FINISHED | FF_RETURN_POINTER | FF_NO_STOP | FF_STOP_EACH_EOS)) && !p->stop_fn,
-               "%s: excludes FF_RETIRE_FINISHED, FF_RETURN_POINTER, FF_NO_STOP, FF_STOP_EACH_EOS and a stop_fn", name);
-  return FF_OK;
+// An opt-in entry behind its mode: the checks, then the decode.  For a sequence entry the terminator range is the EOS token alone
+// (SEP and the other special tokens do not finish a draw, a beam or a row).
+int run_entry(const Entry& e, const Mode& md, const ff_model* m, const ff_decode_params* p, const Refused& no, const EntryArgs& a) {
+  FF_RETURN_IF(check_entry(e, md, m, p, no, a.predict));
+  ff_decode_params q;
+  if (md.sequence) { q = *p; q.term_lo = p->tok_eos; q.term_hi = p->tok_eos + 1; }
+  return run_decode(m, md.sequence ? &q : p, DecodeIO{a.memory, a.mask, a.kv_len, a.num_input, a.num_input_host, nullptr, a.predict, a.steps_done, a.step_counts,
+                                    nullptr, a.trace_logits, nullptr, nullptr, a.seq_of_row, (hipStream_t)a.stream, nullptr},
+                    a.workspace, a.workspace_bytes, md);
 }
-// ... and the decode behind them: the terminator range is the EOS token alone (SEP and the other special tokens do not finish a
-// draw, a beam or a row), and no num_input is read.
-int run_sequence(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask, const int* kv_len,
-                 int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row, void* workspace,
-                 size_t workspace_bytes, ff_stream_t stream, const Mode& mode) {
-  ff_decode_params q = *p;
-  q.term_lo = p->tok_eos;
-  q.term_hi = p->tok_eos + 1;
-  return run_decode(m, &q, opt_in_io(memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row,
-                                     stream),
-                    workspace, workspace_bytes, mode);
-}
+const Refused no_refused{nullptr, nullptr, nullptr, nullptr};
 
 }  // namespace
 
@@ -1785,6 +1702,8 @@ extern "C" int ff_encode(const ff_model* m, const float* input, const unsigned c
   return FF_OK;
 }
 
+// The size queries: their own refusals (a width outside 1..8, num_samples outside 1..64, a sequence query on other than FF_SEQ2SEQ
+// with F = 1), then decode_workspace_bytes for the mode's pick, rule, sequence and G.
 extern "C" size_t ff_decode_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
   return decode_workspace_bytes(m, p, num_input_host, Mode());
 }
@@ -1795,7 +1714,7 @@ extern "C" size_t ff_decode_lp_workspace_bytes(const ff_model* m, const ff_decod
 
 extern "C" size_t ff_decode_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host, int width) {
   if (width < 1 || width > 8) return 0;
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::BEAM, width));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::BEAM, Mode::NONE, false, width));
 }
 
 extern "C" int ff_decode(const ff_model* m, const ff_decode_params* p, const float* memory,
@@ -1819,25 +1738,29 @@ extern "C" int ff_decode_lp(const ff_model* m, const ff_decode_params* p, const 
                     workspace, workspace_bytes, Mode());
 }
 
+// ---- the opt-in entries: fill the mode from the entry's own parameter struct, then run_entry -----------------------------
+#define FF_PAR_ARGS EntryArgs{memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits, seq_of_row, \
+                              workspace, workspace_bytes, stream}
+#define FF_SEQ_ARGS EntryArgs{memory, mask, kv_len, nullptr, nullptr, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, \
+                              workspace_bytes, stream}
+#define FF_PAR_REFUSED Refused{extra_mask, trace_best, trace_second, pointer_out}
+
 extern "C" int ff_decode_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
-                              const unsigned char* mask, const int* kv_len, const int* num_input,
-                              const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                              int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                              float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                              size_t workspace_bytes, const ff_beam_params* beam, ff_stream_t stream) {
-  FF_CHECK_ARG(m && p && beam, "ff_decode_beam: null model, params or beam params");
-  FF_RETURN_IF(check_opt_in("ff_decode_beam", "beams are", p, extra_mask));
-  FF_RETURN_IF(check_beam_width("ff_decode_beam", beam->width, m, p));
-  FF_RETURN_IF(check_opt_in_outputs("ff_decode_beam", p, "beams and scores", beam->beams && beam->scores, trace_best, trace_second,
-                                    pointer_out));
-  FF_RETURN_IF(check_beam_staging("ff_decode_beam", beam->width, m, p));
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::BEAM, beam->width, beam));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_beam_params* beam, ff_stream_t stream) {
+  Entry e{"ff_decode_beam", "beams are", "beam", nullptr, "beams and scores"};
+  Mode md(Mode::BEAM, Mode::NONE, false);
+  if ((e.given = beam != nullptr)) {
+    take_beam(md, beam);
+    e.have = beam->beams && beam->scores;
+  }
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
 
+// Forced keeps checks of its own (other exclusions, the host lengths): it is no selection over the greedy call's arguments.
 extern "C" size_t ff_decode_forced_workspace_bytes(const ff_model* m, const ff_decode_params* p) {
-  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::FORCED, 1));
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::FORCED));
 }
 
 extern "C" int ff_decode_forced(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
@@ -1853,298 +1776,259 @@ extern "C" int ff_decode_forced(const ff_model* m, const ff_decode_params* p, co
   for (long long r = 0; r < (long long)p->N * p->F; ++r)
     FF_CHECK_ARG(forced->lengths_host[r] >= 0 && forced->lengths_host[r] <= p->T - 1, "ff_decode_forced: lengths[%lld]=%d outside 0..%d",
                  r, forced->lengths_host[r], p->T - 1);
+  Mode md(Mode::FORCED);
+  md.forced = forced;
   return run_decode(m, p, DecodeIO{memory, mask, kv_len, nullptr, nullptr, nullptr, nullptr, steps_done, nullptr, nullptr, trace_logits,
                                    nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr},
-                    workspace, workspace_bytes, Mode(Mode::FORCED, 1, forced));
+                    workspace, workspace_bytes, md);
 }
 
 extern "C" size_t ff_decode_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
                                                    int num_samples) {
   if (num_samples < 1 || num_samples > 64) return 0;
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::SAMPLE, num_samples));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::DRAW, Mode::NONE, false, num_samples));
 }
 
 extern "C" int ff_decode_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                const unsigned char* mask, const int* kv_len, const int* num_input,
-                                const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                                int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                                float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                                size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream) {
-  FF_CHECK_ARG(m && p && sample, "ff_decode_sample: null model, params or sample params");
-  FF_RETURN_IF(check_opt_in("ff_decode_sample", "sampling is", p, extra_mask));
-  FF_CHECK_ARG(sample->num_samples >= 1 && sample->num_samples <= 64, "ff_decode_sample: num_samples=%d outside 1..64", sample->num_samples);
-  FF_CHECK_ARG(sample->temperature >= 0.f && sample->temperature <= 3.402823466e+38f && sample->top_k >= 0 && sample->top_p > 0.f &&
-                   sample->top_p <= 1.f, "ff_decode_sample: temperature=%g must be finite and >= 0, top_k=%d >= 0, top_p=%g in (0, 1]",
-               (double)sample->temperature, sample->top_k, (double)sample->top_p);
-  FF_RETURN_IF(check_opt_in_outputs("ff_decode_sample", p, "uniforms, samples, logprob and scores",
-                                    sample->uniforms && sample->samples && sample->logprob && sample->scores, trace_best, trace_second,
-                                    pointer_out));
-  FF_CHECK_ARG(p->N > 0 && p->F > 0 && (long long)p->N * p->F * sample->num_samples < (1LL << 31), "ff_decode_sample: bad sizes");
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::SAMPLE, sample->num_samples, sample));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream) {
+  Entry e{"ff_decode_sample", "sampling is", "sample", nullptr, "uniforms, samples, logprob and scores", -1, true};
+  Mode md(Mode::DRAW, Mode::NONE, false);
+  if ((e.given = sample != nullptr)) {
+    take_draw(md, sample);
+    e.have = sample->uniforms && sample->samples && sample->logprob && sample->scores;
+  }
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
 
 extern "C" size_t ff_decode_sequence_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples) {
   if (num_samples < 1 || num_samples > 64 || !sequence_query_ok(p)) return 0;
-  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_SAMPLE, num_samples));
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::DRAW, Mode::NONE, true, num_samples));
 }
 
-extern "C" int ff_decode_sequence_sample(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
-                                         const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
-                                         int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sample_params* sample,
-                                         ff_stream_t stream) {
-  const char* name = "ff_decode_sequence_sample";
-  FF_RETURN_IF(check_sequence(name, "sample", "ff_decode_sample", m, p, sample));
-  FF_CHECK_ARG(sample->num_samples >= 1 && sample->num_samples <= 64, "%s: num_samples=%d outside 1..64", name, sample->num_samples);
-  FF_CHECK_ARG(sample->uniforms && sample->samples && sample->logprob && sample->scores && predict,
-               "%s: uniforms, samples, logprob, scores and predict are required", name);
-  FF_CHECK_ARG(p->N > 0 && (long long)p->N * sample->num_samples < (1LL << 31), "%s: bad sizes", name);
-  const int rows = p->N * sample->num_samples;   // (the draw's own check, with the step's text: the uniforms of one step)
-  FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{sample->uniforms, rows, nullptr, sample->temperature, sample->top_k,
-                                                            sample->top_p}, rows));
-  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
-                      stream, Mode(Mode::SEQ_SAMPLE, sample->num_samples, sample));
+extern "C" int ff_decode_sequence_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sample_params* sample, ff_stream_t stream) {
+  Entry e{"ff_decode_sequence_sample", nullptr, "sample", "ff_decode_sample", "uniforms, samples, logprob, scores and predict"};
+  Mode md(Mode::DRAW, Mode::NONE, true);
+  if ((e.given = sample != nullptr)) {
+    take_draw(md, sample);
+    e.have = sample->uniforms && sample->samples && sample->logprob && sample->scores;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
 }
 
 extern "C" size_t ff_decode_sequence_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width) {
   if (width < 1 || width > 8 || !sequence_query_ok(p)) return 0;
-  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_BEAM, width));
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::BEAM, Mode::NONE, true, width));
 }
 
-extern "C" int ff_decode_sequence_beam(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
-                                       const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
-                                       int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_beam_params* beam,
-                                       ff_stream_t stream) {
-  const char* name = "ff_decode_sequence_beam";
-  FF_RETURN_IF(check_sequence(name, "beam", "ff_decode_beam", m, p, beam));
-  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
-  FF_CHECK_ARG(beam->stop_best == 0 || beam->stop_best == 1, "%s: stop_best=%d must be 0 or 1", name, beam->stop_best);
-  FF_CHECK_ARG(beam->beams && beam->scores && beam->finished && predict, "%s: beams, scores, finished and predict are required", name);
-  FF_CHECK_ARG(p->N > 0 && (long long)p->N * beam->width < (1LL << 31), "%s: bad sizes", name);
-  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
-  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
-                      stream, Mode(Mode::SEQ_BEAM, beam->width, beam));
+extern "C" int ff_decode_sequence_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_beam_params* beam, ff_stream_t stream) {
+  Entry e{"ff_decode_sequence_beam", nullptr, "beam", "ff_decode_beam", "beams, scores, finished and predict"};
+  Mode md(Mode::BEAM, Mode::NONE, true);
+  if ((e.given = beam != nullptr)) {
+    take_beam(md, beam);
+    md.stop_best = beam->stop_best; md.finished = beam->finished;
+    e.have = beam->beams && beam->scores && beam->finished;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
 }
 
 extern "C" size_t ff_decode_sequence_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p) {
   if (!sequence_query_ok(p)) return 0;
-  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_CONSTRAIN, 1));
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::ARGMAX, Mode::SEQUENCE, true));
 }
 
 // The greedy single-sequence decode (model.py:161-167, 191, 193-210) under the face-loop rule.
-extern "C" int ff_decode_sequence_constrained(const ff_model* m, const ff_decode_params* p, const float* memory, const unsigned char* mask,
-                                              const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
-                                              int* seq_of_row, void* workspace, size_t workspace_bytes,
-                                              const ff_sequence_constrain_params* constrain, ff_stream_t stream) {
-  const char* name = "ff_decode_sequence_constrained";
-  FF_RETURN_IF(check_sequence(name, "constrain", "ff_decode_constrained", m, p, constrain));
-  FF_RETURN_IF(ff_sequence_rule_check(name, ff_loop_rule_io{constrain->follows, p->L, constrain->flags, m->num_token}, p->L + m->num_token,
-                                      constrain->tok_sep, p->tok_eos));
-  FF_CHECK_ARG(constrain->logprob && constrain->dead_end && constrain->open_end && predict,
-               "%s: logprob, dead_end, open_end and predict are required", name);
-  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
-                      stream, Mode(Mode::SEQ_CONSTRAIN, 1, constrain));
+extern "C" int ff_decode_sequence_constrained(const ff_model* m, const ff_decode_params* p, const float* memory,
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_constrain_params* constrain, ff_stream_t stream) {
+  Entry e{"ff_decode_sequence_constrained", nullptr, "constrain", "ff_decode_constrained", "logprob, dead_end, open_end and predict"};
+  Mode md(Mode::ARGMAX, Mode::SEQUENCE, true);
+  if ((e.given = constrain != nullptr)) {
+    take_rule(md, constrain);
+    md.tok_sep = constrain->tok_sep;
+    md.logprob = constrain->logprob; md.dead_end = constrain->dead_end; md.open_end = constrain->open_end;
+    e.have = constrain->logprob && constrain->dead_end && constrain->open_end;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
 }
 
 extern "C" size_t ff_decode_sequence_constrained_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples) {
   if (num_samples < 1 || num_samples > 64 || !sequence_query_ok(p)) return 0;
-  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_CONSTRAIN_SAMPLE, num_samples));
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::DRAW, Mode::SEQUENCE, true, num_samples));
 }
 
 // R draws per wireframe of the single-sequence decode (model.py:161-167, 191, 193-210) from the row the face-loop rule leaves.
 extern "C" int ff_decode_sequence_constrained_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                                     const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done,
-                                                     int* step_counts, float* trace_logits, int* seq_of_row, void* workspace,
-                                                     size_t workspace_bytes, const ff_sequence_constrain_sample_params* cs,
-                                                     ff_stream_t stream) {
-  const char* name = "ff_decode_sequence_constrained_sample";
-  FF_RETURN_IF(check_sequence(name, "constrain sample", "ff_decode_constrained_sample", m, p, cs));
-  FF_CHECK_ARG(cs->num_samples >= 1 && cs->num_samples <= 64, "%s: num_samples=%d outside 1..64", name, cs->num_samples);
-  FF_RETURN_IF(ff_sequence_rule_check(name, ff_loop_rule_io{cs->follows, p->L, cs->flags, m->num_token}, p->L + m->num_token, cs->tok_sep,
-                                      p->tok_eos));
-  FF_CHECK_ARG(cs->uniforms && cs->samples && cs->logprob && cs->scores && cs->dead_end && cs->open_end && cs->predict_logprob &&
-                   cs->predict_dead_end && cs->predict_open_end && predict,
-               "%s: uniforms, samples, logprob, scores, dead_end, open_end, the three predict_ outputs and predict are required", name);
-  FF_CHECK_ARG(p->N > 0 && (long long)p->N * cs->num_samples < (1LL << 31), "%s: bad sizes", name);
-  const int rows = p->N * cs->num_samples;   // (the draw's own check, with the step's text: the uniforms of one step)
-  FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{cs->uniforms, rows, nullptr, cs->temperature, cs->top_k, cs->top_p}, rows));
-  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
-                      stream, Mode(Mode::SEQ_CONSTRAIN_SAMPLE, cs->num_samples, cs));
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_constrain_sample_params* cs, ff_stream_t stream) {
+  Entry e{"ff_decode_sequence_constrained_sample", nullptr, "constrain sample", "ff_decode_constrained_sample",
+                "uniforms, samples, logprob, scores, dead_end, open_end, the three predict_ outputs and predict"};
+  Mode md(Mode::DRAW, Mode::SEQUENCE, true);
+  if ((e.given = cs != nullptr)) {
+    take_draw(md, cs);
+    take_rule(md, cs);
+    md.tok_sep = cs->tok_sep;
+    md.dead_end = cs->dead_end; md.open_end = cs->open_end;
+    md.predict_logprob = cs->predict_logprob; md.predict_dead_end = cs->predict_dead_end; md.predict_open_end = cs->predict_open_end;
+    e.have = cs->uniforms && cs->samples && cs->logprob && cs->scores && cs->dead_end && cs->open_end && cs->predict_logprob &&
+              cs->predict_dead_end && cs->predict_open_end;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
 }
 
 extern "C" size_t ff_decode_sequence_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width) {
   if (width < 1 || width > 8 || !sequence_query_ok(p)) return 0;
-  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::SEQ_CONSTRAIN_BEAM, width));
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::BEAM, Mode::SEQUENCE, true, width));
 }
 
 // W beams per wireframe of the single-sequence decode (model.py:161-167, 191, 193-210) over the rows the face-loop rule leaves.
 extern "C" int ff_decode_sequence_constrained_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                                   const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done,
-                                                   int* step_counts, float* trace_logits, int* seq_of_row, void* workspace,
-                                                   size_t workspace_bytes, const ff_sequence_constrain_beam_params* beam,
-                                                   ff_stream_t stream) {
-  const char* name = "ff_decode_sequence_constrained_beam";
-  FF_RETURN_IF(check_sequence(name, "constrain beam", "ff_decode_constrained_beam", m, p, beam));
-  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
-  FF_CHECK_ARG(beam->stop_best == 0 || beam->stop_best == 1, "%s: stop_best=%d must be 0 or 1", name, beam->stop_best);
-  FF_RETURN_IF(ff_sequence_rule_check(name, ff_loop_rule_io{beam->follows, p->L, beam->flags, m->num_token}, p->L + m->num_token,
-                                      beam->tok_sep, p->tok_eos));
-  FF_CHECK_ARG(beam->beams && beam->scores && beam->finished && beam->beam_dead_end && beam->beam_open_end && beam->dead_end &&
-                   beam->open_end && predict,
-               "%s: beams, scores, finished, beam_dead_end, beam_open_end, dead_end, open_end and predict are required", name);
-  FF_CHECK_ARG(p->N > 0 && (long long)p->N * beam->width < (1LL << 31), "%s: bad sizes", name);
-  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
-  return run_sequence(m, p, memory, mask, kv_len, predict, steps_done, step_counts, trace_logits, seq_of_row, workspace, workspace_bytes,
-                      stream, Mode(Mode::SEQ_CONSTRAIN_BEAM, beam->width, beam));
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_constrain_beam_params* beam, ff_stream_t stream) {
+  Entry e{"ff_decode_sequence_constrained_beam", nullptr, "constrain beam", "ff_decode_constrained_beam",
+                "beams, scores, finished, beam_dead_end, beam_open_end, dead_end, open_end and predict"};
+  Mode md(Mode::BEAM, Mode::SEQUENCE, true);
+  if ((e.given = beam != nullptr)) {
+    take_beam(md, beam);
+    take_rule(md, beam);
+    md.tok_sep = beam->tok_sep; md.stop_best = beam->stop_best;
+    md.finished = beam->finished; md.beam_dead_end = beam->beam_dead_end; md.beam_open_end = beam->beam_open_end;
+    md.dead_end = beam->dead_end; md.open_end = beam->open_end;
+    e.have = beam->beams && beam->scores && beam->finished && beam->beam_dead_end && beam->beam_open_end && beam->dead_end &&
+              beam->open_end;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
 }
 
 extern "C" size_t ff_decode_constrained_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN, 1));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::ARGMAX, Mode::LOOP, false));
+}
+
+// (ff_decode_constrained, _ahead and _exact: the parameters and the required outputs the three share)
+template <typename Q>
+static bool take_constrain(Entry& e, Mode& md, const Q* q, const char* op) {
+  if (!(e.given = q != nullptr)) return false;
+  take_rule(md, q);
+  md.op = op; md.logprob = q->logprob; md.dead_end = q->dead_end;
+  e.have = q->logprob && q->dead_end;
+  return true;
 }
 
 extern "C" int ff_decode_constrained(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                     const unsigned char* mask, const int* kv_len, const int* num_input,
-                                     const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                                     int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                                     float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                                     size_t workspace_bytes, const ff_constrain_params* constrain, ff_stream_t stream) {
-  FF_CHECK_ARG(m && p && constrain, "ff_decode_constrained: null model, params or constrain params");
-  FF_RETURN_IF(check_opt_in("ff_decode_constrained", "the constrained decode is", p, extra_mask));
-  FF_RETURN_IF(check_loop_rule("ff_decode_constrained", constrain->flags, constrain->follows, m, p));
-  FF_RETURN_IF(check_opt_in_outputs("ff_decode_constrained", p, "logprob and dead_end", constrain->logprob && constrain->dead_end,
-                                    trace_best, trace_second, pointer_out));
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN, 1, constrain));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_constrain_params* constrain, ff_stream_t stream) {
+  Entry e{"ff_decode_constrained", "the constrained decode is", "constrain", nullptr, "logprob and dead_end"};
+  Mode md(Mode::ARGMAX, Mode::LOOP, false);
+  take_constrain(e, md, constrain, "ff_pointer_constrained");
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
 
 extern "C" size_t ff_decode_constrained_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_AHEAD, 1));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::ARGMAX, Mode::LOOP, false));
 }
 
 extern "C" int ff_decode_constrained_ahead(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                           const unsigned char* mask, const int* kv_len, const int* num_input,
-                                           const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                                           int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                                           float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                                           size_t workspace_bytes, const ff_constrain_ahead_params* ahead, ff_stream_t stream) {
-  const char* name = "ff_decode_constrained_ahead";
-  FF_CHECK_ARG(m && p && ahead, "%s: null model, params or look-ahead params", name);
-  FF_RETURN_IF(check_opt_in(name, "the constrained decode with look-ahead is", p, extra_mask));
-  FF_RETURN_IF(check_loop_rule(name, ahead->flags, ahead->follows, m, p));
-  FF_RETURN_IF(check_lookahead(name, 1, ahead->flags, ahead->close_dist, ahead->cycle_len, m, p));
-  FF_RETURN_IF(check_opt_in_outputs(name, p, "logprob and dead_end", ahead->logprob && ahead->dead_end, trace_best, trace_second,
-                                    pointer_out));
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_AHEAD, 1, ahead));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_constrain_ahead_params* ahead, ff_stream_t stream) {
+  Entry e{"ff_decode_constrained_ahead", "the constrained decode with look-ahead is", "look-ahead", nullptr, "logprob and dead_end"};
+  Mode md(Mode::ARGMAX, Mode::LOOP, false);
+  if (take_constrain(e, md, ahead, "ff_pointer_constrained_ahead")) take_ahead(md, 1, ahead, ahead->close_dist);
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
 
 extern "C" size_t ff_decode_constrained_exact_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host) {
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_EXACT, 1));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::ARGMAX, Mode::LOOP, false));
 }
 
 extern "C" int ff_decode_constrained_exact(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                           const unsigned char* mask, const int* kv_len, const int* num_input,
-                                           const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                                           int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                                           float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                                           size_t workspace_bytes, const ff_constrain_exact_params* exact, ff_stream_t stream) {
-  const char* name = "ff_decode_constrained_exact";
-  FF_CHECK_ARG(m && p && exact, "%s: null model, params or exact look-ahead params", name);
-  FF_RETURN_IF(check_opt_in(name, "the constrained decode with exact look-ahead is", p, extra_mask));
-  FF_RETURN_IF(check_loop_rule(name, exact->flags, exact->follows, m, p));
-  FF_RETURN_IF(check_lookahead(name, 2, exact->flags, nullptr, exact->cycle_len, m, p));
-  FF_RETURN_IF(check_opt_in_outputs(name, p, "logprob and dead_end", exact->logprob && exact->dead_end, trace_best, trace_second,
-                                    pointer_out));
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_EXACT, 1, exact));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_constrain_exact_params* exact, ff_stream_t stream) {
+  Entry e{"ff_decode_constrained_exact", "the constrained decode with exact look-ahead is", "exact look-ahead", nullptr,
+                "logprob and dead_end"};
+  Mode md(Mode::ARGMAX, Mode::LOOP, false);
+  if (take_constrain(e, md, exact, "ff_pointer_constrained_exact")) take_ahead(md, 2, exact, nullptr);
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
 
 extern "C" size_t ff_decode_constrained_beam_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
                                                              int width) {
   if (width < 1 || width > 8) return 0;
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_BEAM, width));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::BEAM, Mode::LOOP, false, width));
+}
+
+// (ff_decode_constrained_beam and _beam_ahead: the parameters and the required outputs the two share)
+template <typename Q>
+static bool take_constrain_beam(Entry& e, Mode& md, const Q* q, const char* op) {
+  if (!(e.given = q != nullptr)) return false;
+  take_beam(md, q);
+  take_rule(md, q);
+  md.op = op; md.dead_end = q->dead_end;
+  e.have = q->beams && q->scores && q->dead_end;
+  return true;
 }
 
 extern "C" int ff_decode_constrained_beam(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                          const unsigned char* mask, const int* kv_len, const int* num_input,
-                                          const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                                          int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                                          float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                                          size_t workspace_bytes, const ff_constrain_beam_params* beam, ff_stream_t stream) {
-  const char* name = "ff_decode_constrained_beam";
-  FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
-  FF_RETURN_IF(check_opt_in(name, "the constrained beam decode is", p, extra_mask));
-  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
-  FF_RETURN_IF(check_loop_rule(name, beam->flags, beam->follows, m, p));
-  FF_RETURN_IF(check_opt_in_outputs(name, p, "beams, scores and dead_end", beam->beams && beam->scores && beam->dead_end, trace_best,
-                                    trace_second, pointer_out));
-  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM, beam->width, beam));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_constrain_beam_params* beam, ff_stream_t stream) {
+  Entry e{"ff_decode_constrained_beam", "the constrained beam decode is", "beam", nullptr, "beams, scores and dead_end"};
+  Mode md(Mode::BEAM, Mode::LOOP, false);
+  take_constrain_beam(e, md, beam, "ff_beam_constrained_select");
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
 
 extern "C" size_t ff_decode_constrained_beam_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p,
                                                                    const int* num_input_host, int width) {
   if (width < 1 || width > 8) return 0;
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_BEAM_AHEAD, width));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::BEAM, Mode::LOOP, false, width));
 }
 
 extern "C" int ff_decode_constrained_beam_ahead(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                                const unsigned char* mask, const int* kv_len, const int* num_input,
-                                                const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                                                int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                                                float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                                                size_t workspace_bytes, const ff_constrain_beam_ahead_params* beam,
-                                                ff_stream_t stream) {
-  const char* name = "ff_decode_constrained_beam_ahead";
-  FF_CHECK_ARG(m && p && beam, "%s: null model, params or beam params", name);
-  FF_RETURN_IF(check_opt_in(name, "the constrained beam decode with look-ahead is", p, extra_mask));
-  FF_RETURN_IF(check_beam_width(name, beam->width, m, p));
-  FF_RETURN_IF(check_loop_rule(name, beam->flags, beam->follows, m, p));
-  FF_CHECK_ARG(beam->lookahead == 1 || beam->lookahead == 2, "%s: lookahead=%d must be 1 (look-ahead) or 2 (exact)", name, beam->lookahead);
-  FF_RETURN_IF(check_lookahead(name, beam->lookahead, beam->flags, beam->close_dist, beam->cycle_len, m, p));
-  FF_RETURN_IF(check_opt_in_outputs(name, p, "beams, scores and dead_end", beam->beams && beam->scores && beam->dead_end, trace_best,
-                                    trace_second, pointer_out));
-  FF_RETURN_IF(check_beam_staging(name, beam->width, m, p));
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_BEAM_AHEAD, beam->width, beam));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_constrain_beam_ahead_params* beam, ff_stream_t stream) {
+  Entry e{"ff_decode_constrained_beam_ahead", "the constrained beam decode with look-ahead is", "beam", nullptr,
+                "beams, scores and dead_end", 1};
+  Mode md(Mode::BEAM, Mode::LOOP, false);
+  if (take_constrain_beam(e, md, beam, "ff_beam_constrained_select_ahead")) take_ahead(md, beam->lookahead, beam, beam->close_dist);
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
 
 extern "C" size_t ff_decode_constrained_sample_workspace_bytes(const ff_model* m, const ff_decode_params* p, const int* num_input_host,
                                                                int num_samples) {
   if (num_samples < 1 || num_samples > 64) return 0;
-  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::CONSTRAIN_SAMPLE, num_samples));
+  return decode_workspace_bytes(m, p, num_input_host, Mode(Mode::DRAW, Mode::LOOP, false, num_samples));
 }
 
 extern "C" int ff_decode_constrained_sample(const ff_model* m, const ff_decode_params* p, const float* memory,
-                                            const unsigned char* mask, const int* kv_len, const int* num_input,
-                                            const int* num_input_host, const unsigned char* extra_mask, int64_t* predict,
-                                            int* steps_done, int* step_counts, float* pointer_out, float* trace_logits,
-                                            float* trace_best, float* trace_second, int* seq_of_row, void* workspace,
-                                            size_t workspace_bytes, const ff_constrain_sample_params* cs, ff_stream_t stream) {
-  const char* name = "ff_decode_constrained_sample";
-  FF_CHECK_ARG(m && p && cs, "%s: null model, params or constrained sample params", name);
-  FF_RETURN_IF(check_opt_in(name, "the constrained sampled decode is", p, extra_mask));
-  FF_CHECK_ARG(cs->num_samples >= 1 && cs->num_samples <= 64, "%s: num_samples=%d outside 1..64", name, cs->num_samples);
-  FF_RETURN_IF(check_loop_rule(name, cs->flags, cs->follows, m, p));
-  FF_CHECK_ARG(cs->lookahead >= 0 && cs->lookahead <= 2, "%s: lookahead=%d must be 0 (none), 1 (look-ahead) or 2 (exact)", name, cs->lookahead);
-  FF_RETURN_IF(check_lookahead(name, cs->lookahead, cs->flags, cs->close_dist, cs->cycle_len, m, p));
-  FF_RETURN_IF(check_opt_in_outputs(name, p, "uniforms, samples, logprob, scores and dead_end",
-                                    cs->uniforms && cs->samples && cs->logprob && cs->scores && cs->dead_end, trace_best, trace_second,
-                                    pointer_out));
-  FF_CHECK_ARG(p->N > 0 && p->F > 0 && (long long)p->N * p->F * cs->num_samples < (1LL << 31), "%s: bad sizes", name);
-  const int rows = p->N * p->F * cs->num_samples;   // (the draw's own check, with the step's text: the uniforms of one step)
-  FF_RETURN_IF(ff_sample_draw_check(name, ff_sample_draw_io{cs->uniforms, rows, nullptr, cs->temperature, cs->top_k, cs->top_p}, rows));
-  return run_decode(m, p, opt_in_io(memory, mask, kv_len, num_input, num_input_host, predict, steps_done, step_counts, trace_logits,
-                                    seq_of_row, stream),
-                    workspace, workspace_bytes, Mode(Mode::CONSTRAIN_SAMPLE, cs->num_samples, cs));
+    const unsigned char* mask, const int* kv_len, const int* num_input, const int* num_input_host, const unsigned char* extra_mask,
+    int64_t* predict, int* steps_done, int* step_counts, float* pointer_out, float* trace_logits, float* trace_best, float* trace_second,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_constrain_sample_params* cs, ff_stream_t stream) {
+  Entry e{"ff_decode_constrained_sample", "the constrained sampled decode is", "constrained sample", nullptr,
+                "uniforms, samples, logprob, scores and dead_end", 0};
+  Mode md(Mode::DRAW, Mode::LOOP, false);
+  if ((e.given = cs != nullptr)) {
+    take_draw(md, cs);
+    take_rule(md, cs);
+    take_ahead(md, cs->lookahead, cs, cs->close_dist);
+    md.op = "ff_pointer_constrained_sample";
+    md.dead_end = cs->dead_end; md.predict_logprob = cs->predict_logprob; md.predict_dead_end = cs->predict_dead_end;
+    e.have = cs->uniforms && cs->samples && cs->logprob && cs->scores && cs->dead_end;
+  }
+  return run_entry(e, md, m, p, FF_PAR_REFUSED, FF_PAR_ARGS);
 }
+
+#undef FF_PAR_ARGS
+#undef FF_SEQ_ARGS
+#undef FF_PAR_REFUSED
 
 namespace {
 int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io, void* workspace, size_t workspace_bytes,
@@ -2160,7 +2044,7 @@ int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io,
   FF_RETURN_IF(r.bind_streams());
   FF_RETURN_IF(r.init_retirement());
   int rc = FF_OK;
-  if (mode.kind == Mode::FORCED) {   // (no row to score: the start tokens are packed, no decoder launch is made)
+  if (mode.pick == Mode::FORCED) {   // (no row to score: the start tokens are packed, no decoder launch is made)
     rc = r.forced_tokens();
     if (rc == FF_OK && r.forced_steps > 0) rc = r.prologue();
     if (rc == FF_OK) rc = r.forced_loop();
