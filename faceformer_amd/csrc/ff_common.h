@@ -198,8 +198,9 @@ int ff_constrain_finalize(const int* tok, const float* lp, const int* fin, const
 // Sequence-constrained decode (ff_constrain_seq.hip): the constrained step's operands with the two tokens of the
 // single-sequence rule in place of a terminator range (io's is not read); one sequence per wireframe, every one from SOS.
 int ff_sequence_rule_check(const char* op, const ff_loop_rule_io& r, int S, int tok_sep, int tok_eos);
+// `ahead`: the closure look-ahead's tables and budget, null = the plain launch.
 int ff_pointer_sequence_constrained_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st, int tok_sep,
-                                         int tok_eos, ff_stream_t stream);
+                                         int tok_eos, const ff_lookahead_io* ahead, ff_stream_t stream);
 int ff_sequence_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int L, int sos,
                                hipStream_t st);
 int ff_sequence_constrain_finalize(const int* tok, const float* lp, const int* fin, const int* dead, const int* first, int Btot, int T,
@@ -209,7 +210,8 @@ int ff_sequence_constrain_finalize(const int* tok, const float* lp, const int* f
 // Sequence-constrained sampled decode (ff_constrain_seq.hip): the sequence-constrained step's operands and
 // the draw's; R draws per wireframe in the sequence-sampled decode's layout, each with the sequence-constrained decode's state.
 int ff_pointer_sequence_constrained_sample_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& st,
-                                                int tok_sep, int tok_eos, const ff_sample_draw_io& draw, ff_stream_t stream);
+                                                int tok_sep, int tok_eos, const ff_lookahead_io* ahead, const ff_sample_draw_io& draw,
+                                                ff_stream_t stream);
 int ff_sequence_constrain_sample_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int* row_id,
                                       int Bc, int R, int w0, int L, int sos, hipStream_t st);
 int ff_sequence_constrain_sample_finalize(const int* tok, const float* lp, const int* fin, const int* dead, const int* first, int Btot,

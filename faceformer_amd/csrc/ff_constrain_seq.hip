@@ -67,7 +67,22 @@ struct SeqConstrainSampleArgs : SeqConstrainArgs {
   static constexpr bool DRAW = true;
 };
 
-template <class Args>
+// The closure forms' operands: either of the above, and what ff_loop_write_row<FF_LOOP_AHEAD | FF_LOOP_EXACT> reads.
+// Structs of their own: the plain forms' argument layout, and with it their device code, stays what it was.
+template <class Plain>
+struct SeqClosureArgs : Plain {
+  const unsigned char* close_dist;   // FF_LOOP_AHEAD only: [wireframes, L, L] bytes
+  const unsigned char* cycle_len;    // FF_LOOP_AHEAD, FF_LOOP_EXACT: [wireframes, L] bytes
+  int budget;                        // the step's: min(T - 1 - position, 254)
+};
+// (their launch is defined at the end of this file, behind every kernel that was there before, which keeps those in their places)
+template <class Plain>
+int seq_constrain_closure_launch(const Plain& plain, const ff_lookahead_io& la, int B, hipStream_t st);
+
+// FORM: FF_LOOP_PLAIN, or one of the closure look-aheads of ff_loop_write_row -- the argument struct then carries
+// the two distance tables and the step's budget (SeqClosureArgs<> of the greedy or of the sampled struct).  The rule, the search
+// and the two fix-ups are the plain form's lines: nothing is restated.
+template <class Args, int FORM = FF_LOOP_PLAIN>
 __global__ __launch_bounds__(256) void pointer_sequence_constrained_kernel(Args a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
@@ -86,8 +101,12 @@ __global__ __launch_bounds__(256) void pointer_sequence_constrained_kernel(Args 
       const unsigned char* mrow = pa.mask ? pa.mask + (size_t)w * pa.S : nullptr;
       unsigned* vrow = a.visited + (size_t)b * a.fw;
       unsigned char* xrow = a.rows + (size_t)b * pa.S;
-      const FFLoopRule rule{a.follows, a.L, a.fw, a.flags, ntok, nullptr, nullptr, 0};
-      dead = ff_loop_write_row<FF_LOOP_PLAIN>(pa, rule, lane, w, kv, mrow, first, prev, vrow, xrow) ? 1 : 0;
+      FFLoopRule rule{a.follows, a.L, a.fw, a.flags, ntok, nullptr, nullptr, 0};
+      if constexpr (FORM != FF_LOOP_PLAIN) { rule.close_dist = a.close_dist; rule.cycle_len = a.cycle_len; rule.budget = a.budget; }
+      if constexpr (FORM == FF_LOOP_PLAIN)   // (the plain forms keep the line they had)
+        dead = ff_loop_write_row<FF_LOOP_PLAIN>(pa, rule, lane, w, kv, mrow, first, prev, vrow, xrow) ? 1 : 0;
+      else
+        dead = ff_loop_write_row<FORM>(pa, rule, lane, w, kv, mrow, first, prev, vrow, xrow) ? 1 : 0;
       if ((a.flags & FF_CONSTRAIN_CONNECT) && !(first >= 0 && prev >= 0)) {   // closed: EOS may end the row; no empty face
         if (lane == (a.eos & 63)) xrow[a.eos] = 0;
         if (prev < 0 && lane == (a.sep & 63)) xrow[a.sep] = 1;
@@ -277,36 +296,43 @@ static int seq_constrain_args(SeqConstrainArgs& a, const char* op, const ff_step
   return FF_OK;
 }
 
-// The one launch behind ff_pointer_sequence_constrained and the engine's step.
+// The one launch behind ff_pointer_sequence_constrained, ff_pointer_sequence_constrained_ahead (ahead: the closure form's tables
+// and budget, checked by ff_lookahead_check; null: the plain launch) and the engine's step.
 int ff_pointer_sequence_constrained_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& s, int tok_sep,
-                                         int tok_eos, ff_stream_t stream) {
+                                         int tok_eos, const ff_lookahead_io* ahead, ff_stream_t stream) {
+  const char* op = ahead ? "ff_pointer_sequence_constrained_ahead" : "ff_pointer_sequence_constrained";
   const int B = io.rows, S = io.S;
   if (B == 0) return FF_OK;
   SeqConstrainArgs a;
   memset(&a, 0, sizeof(a));
-  FF_RETURN_IF(seq_constrain_args(a, "ff_pointer_sequence_constrained", io, rule, s, tok_sep, tok_eos));
+  FF_RETURN_IF(seq_constrain_args(a, op, io, rule, s, tok_sep, tok_eos));
+  if (ahead) FF_RETURN_IF(ff_lookahead_check(op, rule, S, *ahead));
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 4.0, st);
+  if (ahead) return seq_constrain_closure_launch(a, *ahead, B, st);
   hipLaunchKernelGGL(pointer_sequence_constrained_kernel<SeqConstrainArgs>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
 
-// The one launch behind ff_pointer_sequence_constrained_sample and the engine's sampled step: the checks above and
-// ff_pointer_sample_sync's (ff_sample_draw_check).
+// The one launch behind ff_pointer_sequence_constrained_sample, ff_pointer_sequence_constrained_sample_ahead and the engine's
+// sampled step: the checks above and ff_pointer_sample_sync's (ff_sample_draw_check).
 int ff_pointer_sequence_constrained_sample_sync(const ff_step_io& io, const ff_loop_rule_io& rule, const ff_constrained_state& s,
-                                                int tok_sep, int tok_eos, const ff_sample_draw_io& d, ff_stream_t stream) {
-  const char* op = "ff_pointer_sequence_constrained_sample";
+                                                int tok_sep, int tok_eos, const ff_lookahead_io* ahead, const ff_sample_draw_io& d,
+                                                ff_stream_t stream) {
+  const char* op = ahead ? "ff_pointer_sequence_constrained_sample_ahead" : "ff_pointer_sequence_constrained_sample";
   const int B = io.rows, S = io.S;
   if (B == 0) return FF_OK;
   SeqConstrainSampleArgs a;
   memset(&a, 0, sizeof(a));
   FF_RETURN_IF(seq_constrain_args(a, op, io, rule, s, tok_sep, tok_eos));
   FF_RETURN_IF(ff_sample_draw_check(op, d, B));
+  if (ahead) FF_RETURN_IF(ff_lookahead_check(op, rule, S, *ahead));
   a.uniforms = d.uniforms; a.num_uniforms = d.num_uniforms; a.row_id = d.row_id;
   a.temperature = d.temperature; a.top_k = d.top_k; a.top_p = d.top_p;
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)B * S * 16.0, st);
+  if (ahead) return seq_constrain_closure_launch(a, *ahead, B, st);
   hipLaunchKernelGGL(pointer_sequence_constrained_kernel<SeqConstrainSampleArgs>, dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   FF_CHECK_LAUNCH();
   return FF_OK;
@@ -325,7 +351,35 @@ extern "C" int ff_pointer_sequence_constrained(float* logits, int ldlogits, int 
                  count_unfinished, nullptr, nullptr},
       ff_loop_rule_io{follows, L, flags, ntok},
       ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
-      tok_sep, tok_eos, stream);
+      tok_sep, tok_eos, nullptr, stream);
+}
+
+// The form of a closure entry as the launches take it: 1 = the closure look-ahead, 2 = the exact one (which reads no close_dist).
+static int seq_closure_form(const char* op, int form, const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                            ff_lookahead_io* out) {
+  FF_CHECK_ARG(form == 1 || form == 2, "%s: form=%d must be 1 (look-ahead) or 2 (exact)", op, form);
+  *out = ff_lookahead_io{form == 1 ? close_dist : nullptr, cycle_len, budget, form == 2 ? 1 : 0};
+  return FF_OK;
+}
+
+// Restates select_next (model.py:161-167) under the rule with a closure look-ahead, for the loop of model.py:193-210 that starts at
+// SOS (model.py:191).
+extern "C" int ff_pointer_sequence_constrained_ahead(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len,
+                                                     int B, int seqs_per_group, const unsigned* follows, int L, int flags, int ntok,
+                                                     int tok_sep, int tok_eos, const int* fin_in, const int* first_in,
+                                                     const int* prev_in, unsigned* visited, unsigned char* mask_rows, int* next_tok,
+                                                     float* logprob, int* fin_out, int* dead_end, int* first_out, int* prev_out,
+                                                     const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                                                     int* count_unfinished, int form, const unsigned char* close_dist,
+                                                     const unsigned char* cycle_len, int budget, ff_stream_t stream) {
+  ff_lookahead_io ahead;
+  FF_RETURN_IF(seq_closure_form("ff_pointer_sequence_constrained_ahead", form, close_dist, cycle_len, budget, &ahead));
+  return ff_pointer_sequence_constrained_sync(
+      ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, 0, 0, ntok, memory, E, next_rows, ldnext, next_stats,
+                 count_unfinished, nullptr, nullptr},
+      ff_loop_rule_io{follows, L, flags, ntok},
+      ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
+      tok_sep, tok_eos, &ahead, stream);
 }
 
 int ff_sequence_constrain_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int Bc, int L, int sos,
@@ -360,7 +414,30 @@ extern "C" int ff_pointer_sequence_constrained_sample(float* logits, int ldlogit
                  count_unfinished, nullptr, nullptr},
       ff_loop_rule_io{follows, L, flags, ntok},
       ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
-      tok_sep, tok_eos, ff_sample_draw_io{uniforms, num_uniforms, row_id, temperature, top_k, top_p}, stream);
+      tok_sep, tok_eos, nullptr, ff_sample_draw_io{uniforms, num_uniforms, row_id, temperature, top_k, top_p}, stream);
+}
+
+// Restates select_next (model.py:161-167) under the rule with a closure look-ahead and with the draw, for the loop of
+// model.py:193-210 that starts at SOS (model.py:191).
+extern "C" int ff_pointer_sequence_constrained_sample_ahead(float* logits, int ldlogits, int S, const unsigned char* mask,
+                                                            const int* kv_len, int B, int seqs_per_group, const unsigned* follows, int L,
+                                                            int flags, int ntok, int tok_sep, int tok_eos, const int* fin_in,
+                                                            const int* first_in, const int* prev_in, unsigned* visited,
+                                                            unsigned char* mask_rows, int* next_tok, float* logprob, int* fin_out,
+                                                            int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
+                                                            float* next_rows, int ldnext, float* next_stats, int* count_unfinished,
+                                                            const float* uniforms, int num_uniforms, const int* row_id,
+                                                            float temperature, int top_k, float top_p, int form,
+                                                            const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                                                            ff_stream_t stream) {
+  ff_lookahead_io ahead;
+  FF_RETURN_IF(seq_closure_form("ff_pointer_sequence_constrained_sample_ahead", form, close_dist, cycle_len, budget, &ahead));
+  return ff_pointer_sequence_constrained_sample_sync(
+      ff_step_io{logits, ldlogits, S, mask, kv_len, B, seqs_per_group, 0, 0, ntok, memory, E, next_rows, ldnext, next_stats,
+                 count_unfinished, nullptr, nullptr},
+      ff_loop_rule_io{follows, L, flags, ntok},
+      ff_constrained_state{fin_in, first_in, prev_in, visited, mask_rows, next_tok, logprob, fin_out, dead_end, first_out, prev_out},
+      tok_sep, tok_eos, &ahead, ff_sample_draw_io{uniforms, num_uniforms, row_id, temperature, top_k, top_p}, stream);
 }
 
 int ff_sequence_constrain_sample_init(int* tok, float* lp, int* fin, int* dead, int* first, int* prev, unsigned* visited, int* row_id,
@@ -638,3 +715,30 @@ int ff_sequence_constrain_beam_finalize(const int* tok, const int* parent, const
   FF_CHECK_LAUNCH();
   return FF_OK;
 }
+
+// ==== the closure look-aheads of the sequence-constrained step ===========================================================
+namespace {
+// (the four closure forms are instantiated here, behind the two plain forms and the engine-side kernels, which keep their places;
+// the beam kernels, which the compiler instantiates at the end of the translation unit, follow them with their code unchanged)
+template __global__ void pointer_sequence_constrained_kernel<SeqClosureArgs<SeqConstrainArgs>, FF_LOOP_AHEAD>(SeqClosureArgs<SeqConstrainArgs>);
+template __global__ void pointer_sequence_constrained_kernel<SeqClosureArgs<SeqConstrainArgs>, FF_LOOP_EXACT>(SeqClosureArgs<SeqConstrainArgs>);
+template __global__ void pointer_sequence_constrained_kernel<SeqClosureArgs<SeqConstrainSampleArgs>, FF_LOOP_AHEAD>(
+    SeqClosureArgs<SeqConstrainSampleArgs>);
+template __global__ void pointer_sequence_constrained_kernel<SeqClosureArgs<SeqConstrainSampleArgs>, FF_LOOP_EXACT>(
+    SeqClosureArgs<SeqConstrainSampleArgs>);
+
+// The plain form's operands (checked and filled by the caller) with the look-ahead's, launched in the form `la` names.
+template <class Plain>
+int seq_constrain_closure_launch(const Plain& plain, const ff_lookahead_io& la, int B, hipStream_t st) {
+  SeqClosureArgs<Plain> a;
+  memset(&a, 0, sizeof(a));
+  static_cast<Plain&>(a) = plain;
+  a.close_dist = la.exact ? nullptr : la.close_dist; a.cycle_len = la.cycle_len; a.budget = la.budget;
+  if (la.exact)
+    hipLaunchKernelGGL((pointer_sequence_constrained_kernel<SeqClosureArgs<Plain>, FF_LOOP_EXACT>), dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((pointer_sequence_constrained_kernel<SeqClosureArgs<Plain>, FF_LOOP_AHEAD>), dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+}  // namespace

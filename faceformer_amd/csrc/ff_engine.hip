@@ -1210,9 +1210,11 @@ struct DecodeRun {
       } else {
         const Rule r = rule_of(c);
         const ff_loop_rule_io rio{r.follows, r.L, r.flags, m->num_token};
-        // the look-aheads: this step selects position t, so a loop has T - 1 - t further positions to close in
+        // the look-aheads: this step selects position t, so a loop has T - 1 - t further positions to close in; a sequence row
+        // is longer than the tables' byte reaches (config A: T = 259), so under the sequence rule the budget is clamped to 254
+        const int budget = mode.rule == Mode::SEQUENCE && T - 1 - t > 254 ? 254 : T - 1 - t;
         const ff_lookahead_io ahead{mode.ahead == 1 ? mode.close_dist + (size_t)c.w0 * r.L * r.L : nullptr,
-                                    mode.ahead ? mode.cycle_len + (size_t)c.w0 * r.L : nullptr, T - 1 - t, mode.ahead == 2 ? 1 : 0};
+                                    mode.ahead ? mode.cycle_len + (size_t)c.w0 * r.L : nullptr, budget, mode.ahead == 2 ? 1 : 0};
         const ff_lookahead_io* la = mode.ahead ? &ahead : nullptr;
         if (beam) {   // the rule per beam: state half step & 1 -> half t & 1 (the common operands come from sio)
           if (mode.sequence) {
@@ -1233,10 +1235,10 @@ struct DecodeRun {
                                         buf.first + out, buf.prev + out};
           if (draw) {   // (this step's uniforms are read through the chunk's row_id)
             const ff_sample_draw_io dio{mode.uniforms + (size_t)step * rows, rows, buf.row_id + c.b0, mode.temperature, mode.top_k, mode.top_p};
-            return mode.sequence ? ff_pointer_sequence_constrained_sample_sync(sio, rio, cs, mode.tok_sep, p->tok_eos, dio, st)
+            return mode.sequence ? ff_pointer_sequence_constrained_sample_sync(sio, rio, cs, mode.tok_sep, p->tok_eos, la, dio, st)
                                  : ff_pointer_constrained_sample_sync(mode.op, sio, rio, cs, la, dio, st);
           }
-          return mode.sequence ? ff_pointer_sequence_constrained_sync(sio, rio, cs, mode.tok_sep, p->tok_eos, st)   // (SEP and EOS in place of a terminator range)
+          return mode.sequence ? ff_pointer_sequence_constrained_sync(sio, rio, cs, mode.tok_sep, p->tok_eos, la, st)   // (SEP and EOS in place of a terminator range)
                                : ff_pointer_constrained_sync(mode.op, sio, rio, cs, la, st);
         }
       }
@@ -1527,7 +1529,7 @@ int run_decode(const ff_model* m, const ff_decode_params* p, const DecodeIO& io,
 // outputs it requires as their message names them.
 struct Entry {
   const char *name, *subject, *noun, *sibling, *required;
-  int ahead_lo = -1;            // the lowest look-ahead form the caller may choose (0: sampled, 1: beam); -1: the entry fixes the form
+  int ahead_lo = -1;            // the lowest look-ahead form the caller may choose (0: sampled, 1: beam, 2: 1 under the sequence entries' text); -1: the entry fixes the form
   bool own_draw_text = false;   // ff_decode_sample: temperature / top_k / top_p under its own text, in front of the outputs
   bool given = false, have = false;   // filled by the entry: its parameter struct is not null; all it requires of it is there
 };
@@ -1537,16 +1539,16 @@ struct Refused { const unsigned char* extra_mask; const float *trace_best, *trac
 // The look-ahead of a constrained decode (form 1: the closure look-ahead, 2: the exact one), beyond what the step checks: the
 // flag bits and tables of the form, and the limits of the budget's byte and of the exact search.
 int check_lookahead(const char* name, int form, int flags, const unsigned char* close_dist, const unsigned char* cycle_len,
-                    const ff_model* m, const ff_decode_params* p) {
+                    const ff_model* m, const ff_decode_params* p, bool clamped = false) {
   if (form == 1) {
     FF_CHECK_ARG(flags & FF_CONSTRAIN_CONNECT, "%s: the look-ahead needs FF_CONSTRAIN_CONNECT", name);
     FF_CHECK_ARG(close_dist && cycle_len, "%s: close_dist and cycle_len are required", name);
-    FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the tables' byte)", name, p->T);
+    FF_CHECK_ARG(clamped || p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the tables' byte)", name, p->T);
   } else if (form == 2) {
     FF_CHECK_ARG((flags & FF_CONSTRAIN_CONNECT) && (flags & FF_CONSTRAIN_NO_REPEAT),
                  "%s: the exact look-ahead needs FF_CONSTRAIN_NO_REPEAT | FF_CONSTRAIN_CONNECT", name);
     FF_CHECK_ARG(cycle_len, "%s: cycle_len is required", name);
-    FF_CHECK_ARG(p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the table's byte)", name, p->T);
+    FF_CHECK_ARG(clamped || p->T <= 256, "%s: T=%d above 256 (the budget T - 2 must fit the table's byte)", name, p->T);
     FF_CHECK_ARG(p->L + m->num_token <= FF_EXACT_MAX_S, "%s: L=%d above %d (L + num_token keys at most %d)", name, p->L,
                  FF_EXACT_MAX_S - m->num_token, FF_EXACT_MAX_S);
   }
@@ -1591,7 +1593,9 @@ int check_entry(const Entry& e, const Mode& md, const ff_model* m, const ff_deco
   if (e.ahead_lo == 0)
     FF_CHECK_ARG(md.ahead >= 0 && md.ahead <= 2, "%s: lookahead=%d must be 0 (none), 1 (look-ahead) or 2 (exact)", name, md.ahead);
   if (e.ahead_lo == 1) FF_CHECK_ARG(md.ahead == 1 || md.ahead == 2, "%s: lookahead=%d must be 1 (look-ahead) or 2 (exact)", name, md.ahead);
-  FF_RETURN_IF(check_lookahead(name, md.ahead, md.flags, md.close_dist, md.cycle_len, m, p));
+  if (e.ahead_lo == 2) FF_CHECK_ARG(md.ahead == 1 || md.ahead == 2, "%s: form=%d must be 1 (look-ahead) or 2 (exact)", name, md.ahead);
+  // (a sequence entry's step clamps the budget to the tables' byte: a row longer than 256 positions is accepted)
+  FF_RETURN_IF(check_lookahead(name, md.ahead, md.flags, md.close_dist, md.cycle_len, m, p, md.rule == Mode::SEQUENCE));
   // 7. what the entry requires; a parallel entry also a terminator range and none of the greedy call's traces
   if (md.sequence) {
     FF_CHECK_ARG(e.have && predict, "%s: %s are required", name, e.required);
@@ -1872,6 +1876,56 @@ extern "C" int ff_decode_sequence_constrained_sample(const ff_model* m, const ff
   if ((e.given = cs != nullptr)) {
     take_draw(md, cs);
     take_rule(md, cs);
+    md.tok_sep = cs->tok_sep;
+    md.dead_end = cs->dead_end; md.open_end = cs->open_end;
+    md.predict_logprob = cs->predict_logprob; md.predict_dead_end = cs->predict_dead_end; md.predict_open_end = cs->predict_open_end;
+    e.have = cs->uniforms && cs->samples && cs->logprob && cs->scores && cs->dead_end && cs->open_end && cs->predict_logprob &&
+              cs->predict_dead_end && cs->predict_open_end;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
+}
+
+// (nothing of a closure look-ahead lies in the workspace: the tables are operands)
+extern "C" size_t ff_sequence_decode_constrained_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p) {
+  if (!sequence_query_ok(p)) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::ARGMAX, Mode::SEQUENCE, true));
+}
+
+// The greedy single-sequence decode (model.py:161-167, 191, 193-210) under the face-loop rule with a closure look-ahead.
+extern "C" int ff_sequence_decode_constrained_ahead(const ff_model* m, const ff_decode_params* p, const float* memory,
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_constrain_ahead_params* ahead, ff_stream_t stream) {
+  Entry e{"ff_sequence_decode_constrained_ahead", nullptr, "look-ahead", "ff_decode_constrained_ahead",
+          "logprob, dead_end, open_end and predict", 2};
+  Mode md(Mode::ARGMAX, Mode::SEQUENCE, true);
+  if ((e.given = ahead != nullptr)) {
+    take_rule(md, ahead);
+    take_ahead(md, ahead->form, ahead, ahead->form == 1 ? ahead->close_dist : nullptr);
+    md.tok_sep = ahead->tok_sep;
+    md.logprob = ahead->logprob; md.dead_end = ahead->dead_end; md.open_end = ahead->open_end;
+    e.have = ahead->logprob && ahead->dead_end && ahead->open_end;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
+}
+
+extern "C" size_t ff_sequence_decode_constrained_sample_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p,
+                                                                              int num_samples) {
+  if (num_samples < 1 || num_samples > 64 || !sequence_query_ok(p)) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::DRAW, Mode::SEQUENCE, true, num_samples));
+}
+
+// R draws per wireframe of the single-sequence decode (model.py:161-167, 191, 193-210) from the row the face-loop rule with a
+// closure look-ahead leaves.
+extern "C" int ff_sequence_decode_constrained_sample_ahead(const ff_model* m, const ff_decode_params* p, const float* memory,
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_constrain_sample_ahead_params* cs, ff_stream_t stream) {
+  Entry e{"ff_sequence_decode_constrained_sample_ahead", nullptr, "look-ahead sample", "ff_decode_constrained_sample",
+          "uniforms, samples, logprob, scores, dead_end, open_end, the three predict_ outputs and predict", 2};
+  Mode md(Mode::DRAW, Mode::SEQUENCE, true);
+  if ((e.given = cs != nullptr)) {
+    take_draw(md, cs);
+    take_rule(md, cs);
+    take_ahead(md, cs->form, cs, cs->form == 1 ? cs->close_dist : nullptr);
     md.tok_sep = cs->tok_sep;
     md.dead_end = cs->dead_end; md.open_end = cs->open_end;
     md.predict_logprob = cs->predict_logprob; md.predict_dead_end = cs->predict_dead_end; md.predict_open_end = cs->predict_open_end;

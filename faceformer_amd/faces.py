@@ -609,9 +609,24 @@ def sequence_rule_advance(state, tok, flags, ntok, sep, follows=None):
     return state
 
 
-def sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad):
+def sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad, closure=None, budget=None, close_dist=None, cycle_len=None):
     """-> (masked [S] bool: the keys the RULE masks, padding not included; dead_end).  pad [S] bool: the keys masked by padding /
-    kv_len, which the dead-end vote has to see."""
+    kv_len, which the dead-end vote has to see.
+
+    closure (None: the rule above, unchanged): under CONNECT one more edge mask in front of the dead-end vote, against
+    budget = min(T - 1 - position, 254) in 0..254.  "lookahead": with the loop open edge b is masked when close_dist[first][b] >
+    budget, with it closed when cycle_len[b] > budget (one wireframe's follow_distance tables, [L, L] and [L] uint8).  "exact"
+    (NO_REPEAT as well): with the loop open when D_V(b -> first) > budget -- closure_distance over the edges that are neither
+    padded nor visited (under ONCE: the edges of every face so far) -- with it closed the cycle_len rule; close_dist is not read.
+    The two fix-ups of the closed state are unchanged, so a closed row whose edges are all masked keeps SEP or EOS live and is
+    no dead end."""
+    if closure is not None:
+        if closure not in ("lookahead", "exact"):
+            raise ValueError("closure=%r: must be None, 'lookahead' or 'exact'" % (closure,))
+        if not flags & SEQ_CONNECT or (closure == "exact" and not flags & SEQ_NO_REPEAT):
+            raise ValueError("closure=%r needs SEQ_CONNECT%s" % (closure, " | SEQ_NO_REPEAT" if closure == "exact" else ""))
+        if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) or not 0 <= budget <= 254:
+            raise ValueError("budget=%r: must be in 0..254" % (budget,))
     visited, first, prev = state
     masked = np.zeros(S, dtype=bool)
     connect = bool(flags & SEQ_CONNECT)
@@ -624,6 +639,16 @@ def sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad):
     if flags & SEQ_NO_REPEAT:
         for e in visited:
             masked[ntok + e] = True
+    if closure is not None:
+        L = S - ntok
+        if is_open and closure == "exact":
+            vis = np.zeros(L, dtype=bool)
+            vis[sorted(visited)] = True
+            dist = closure_distance(np.asarray(follows, dtype=bool)[:L, :L], vis, first, hmax=min(max(int(budget), 1), 254),
+                                    pad=np.asarray(pad, dtype=bool)[ntok:])
+        else:
+            dist = np.asarray(close_dist[first] if is_open else cycle_len)[:L]
+        masked[ntok:] |= dist.astype(np.int64) > int(budget)
     dead = False
     if is_open:
         masked[ntok:] |= ~np.asarray(follows[prev][: S - ntok], dtype=bool)
@@ -633,8 +658,8 @@ def sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad):
     return masked, dead
 
 
-def sequence_rule_step(raw, pad, state, flags, ntok, sep, eos, follows=None, finished=False):
-    """One row of one step on RAW logits.  -> dict(tok, logprob, row (the constrained masked row, fp64), masked (the rule's own
+def sequence_rule_step(raw, pad, state, flags, ntok, sep, eos, follows=None, finished=False, **closure):
+    """One row of one step on RAW logits; **closure: sequence_rule_mask's closure, budget, close_dist and cycle_len.  -> dict(tok, logprob, row (the constrained masked row, fp64), masked (the rule's own
     byte row), dead, fin (finished after the step), state (after the step)).  A finished row appends token 0 with log-probability
     0 and keeps its state; a row with no live key gives token 0 and -log S."""
     raw = np.asarray(raw, dtype=np.float64)
@@ -642,7 +667,7 @@ def sequence_rule_step(raw, pad, state, flags, ntok, sep, eos, follows=None, fin
     if finished:
         return dict(tok=0, logprob=0.0, row=raw, masked=np.zeros(S, bool), dead=False, fin=True, state=state)
     pad = np.asarray(pad, dtype=bool)
-    masked, dead = sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad)
+    masked, dead = sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad, **closure)
     row = np.where(masked | pad, SEQ_FILL, raw)
     tok = int(np.argmax(row))                    # (lowest index on ties)
     lp = -float(np.log(np.exp(row - row[tok]).sum()))
@@ -651,7 +676,7 @@ def sequence_rule_step(raw, pad, state, flags, ntok, sep, eos, follows=None, fin
 
 
 def sequence_rule_sample_step(raw, pad, state, flags, ntok, sep, eos, u, temperature=1.0, top_k=0, top_p=1.0, follows=None,
-                              finished=False):
+                              finished=False, **closure):
     """One row of one step of the sampled form (ff_pointer_sequence_constrained_sample) on RAW logits:
     sequence_rule_mask's row, then the sampling rule of DESIGN.md 15 on it with the uniform u -- top-k and top-p act on the
     constrained row, and at a dead end SEP, the only live key, is drawn whatever u is.  -> sequence_rule_step's dict.  logprob:
@@ -661,7 +686,7 @@ def sequence_rule_sample_step(raw, pad, state, flags, ntok, sep, eos, u, tempera
     if finished:
         return dict(tok=0, logprob=0.0, row=raw, masked=np.zeros(S, bool), dead=False, fin=True, state=state)
     pad = np.asarray(pad, dtype=bool)
-    masked, dead = sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad)
+    masked, dead = sequence_rule_mask(state, flags, S, ntok, sep, eos, follows, pad, **closure)      # (DESIGN.md 35's closure keywords)
     row = np.where(masked | pad, SEQ_FILL, raw)
     live = row > SEQ_FILL
     m = row.max()

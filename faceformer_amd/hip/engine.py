@@ -377,7 +377,7 @@ class PathEngine:
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
                constrain_samples=None, constrain_beam_closure=None, sequence_samples=None, sequence_beams=None,
                sequence_beam_stop="all", sequence_constrain=None, tok_sep=None, sequence_constrain_samples=None,
-               sequence_constrain_beams=None):
+               sequence_constrain_beams=None, sequence_constrain_closure=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -495,12 +495,25 @@ class PathEngine:
         `beam_finished` and `beam_open_end` [N*W], `beam_dead_end` [N*W, T] int32 (walked back along the tokens' parents);
         `predict`, `dead_end` and `open_end` are beam 0; no `logprob`; with trace=True `logits` [T-1, N*W, S] holds the constrained
         masked rows and `beam_parent` the parents.  W = 1 equals the sequence_constrain decode; flag bits 0 equal the
-        sequence_beams decode wherever every wireframe has W live keys."""
+        sequence_beams decode wherever every wireframe has W live keys.
+
+        sequence_constrain_closure="lookahead" / "exact" (only with sequence_constrain "loops" / "coedge_loops" or the flag bits 3 /
+        7 -- "lookahead" also with CONNECT alone -- alone or with sequence_constrain_samples, not with sequence_constrain_beams;
+        ff_sequence_decode_constrained_ahead / ff_sequence_decode_constrained_sample_ahead; None: the decodes above):
+        the step that selects position p also masks every edge from which the current loop cannot close within budget =
+        min(T - 1 - p, 254) further positions -- "lookahead" by close_dist [N, L, L] / cycle_len [N, L] uint8 on the device
+        (ops.follow_distance of follow_table, both required), "exact" by one search per open row and step over the edges that are
+        neither padded nor in the row's visited words (cycle_len required, at most 2048 keys).  T may exceed 256: the budget is
+        clamped, so a loop of more than 254 edges counts as not closable.  Outputs are the plain decode's under the same keys;
+        `open_end` is then 0 everywhere and `dead_end` also means "cannot close within the row".  "lookahead" with both tables
+        zero equals the plain decode, bit for bit."""
         SCB = _modes.sequence_constrain_beams_value(sequence_constrain_beams, _modes.sequence_constrain_flags(sequence_constrain),
                                                     sequence_samples, sequence_beams, sequence_constrain_samples) \
             if sequence_constrain_beams else 0
         SCS = _modes.sequence_constrain_samples_value(sequence_constrain_samples, _modes.sequence_constrain_flags(sequence_constrain),
                                                       sequence_samples, sequence_beams) if sequence_constrain_samples else 0
+        SCC = _modes.sequence_constrain_closure_value(sequence_constrain_closure, _modes.sequence_constrain_flags(sequence_constrain),
+                                                      sequence_constrain_beams) if sequence_constrain_closure is not None else None
         seq = dict(sequence_samples=sequence_samples, sequence_beams=sequence_beams, sequence_constrain=sequence_constrain)
         for mode in reversed(_modes.SEQUENCE_MODES):      # (of several set together, the last one's record reports)
             value = mode.sequence.value(seq[mode.subject])
@@ -509,10 +522,14 @@ class PathEngine:
                          extra_mask=extra_mask, logprob=logprob, beam_width=int(beam_width or 0), num_samples=int(num_samples or 0),
                          constrain=constrain is not None, temperature=temperature, top_k=top_k, top_p=top_p, uniforms=uniforms,
                          sequence_beam_stop=sequence_beam_stop, follow_table=follow_table, tok_sep=tok_sep, tok_eos=tok_eos,
-                         trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T)
+                         trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T, sequence_constrain_closure=SCC,
+                         close_dist=close_dist, cycle_len=cycle_len)
                 o[mode.subject] = value
+                if SCC and mode is _modes.SEQUENCE_CONSTRAIN:      # (an option of sequence_constrain and of its sampled form)
+                    mode = _modes.SEQUENCE_CONSTRAIN_AHEAD
                 if SCS:      # (an option of sequence_constrain, the first record this loop looks at)
-                    mode, o["sequence_constrain_samples"] = _modes.SEQUENCE_CONSTRAIN_SAMPLE, SCS
+                    mode, o["sequence_constrain_samples"] = (_modes.SEQUENCE_CONSTRAIN_SAMPLE_AHEAD if SCC else
+                                                             _modes.SEQUENCE_CONSTRAIN_SAMPLE), SCS
                 if SCB:      # (likewise)
                     mode, o["sequence_constrain_beams"] = _modes.SEQUENCE_CONSTRAIN_BEAM, SCB
                 return self._decode_sequence(mode, memory, mask_u8, kv_len, variant, o,

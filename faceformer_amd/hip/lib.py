@@ -204,6 +204,14 @@ class SequenceConstrainSampleParams(C.Structure):
                 ("predict_open_end", fptr)]
 
 
+class SequenceConstrainAheadParams(C.Structure):
+    _fields_ = SequenceConstrainParams._fields_ + [("form", C.c_int), ("close_dist", fptr), ("cycle_len", fptr)]
+
+
+class SequenceConstrainSampleAheadParams(C.Structure):
+    _fields_ = SequenceConstrainSampleParams._fields_ + [("form", C.c_int), ("close_dist", fptr), ("cycle_len", fptr)]
+
+
 class BeamSequenceConstrainedStep(C.Structure):
     _fields_ = [("logits", fptr), ("ldlogits", C.c_int), ("S", C.c_int), ("mask", fptr), ("kv_len", fptr),
                 ("groups", C.c_int), ("width", C.c_int), ("groups_per_wireframe", C.c_int),
@@ -408,6 +416,23 @@ SIGNATURES = {
     "ff_decode_sequence_constrained_sample": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
                                                         C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
                                                         C.POINTER(SequenceConstrainSampleParams), fptr]),
+    "ff_pointer_sequence_constrained_ahead": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int, C.c_int,
+                                                        C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                                        fptr, fptr, fptr, C.c_int, fptr, C.c_int, fptr, fptr, C.c_int, fptr, fptr,
+                                                        C.c_int, fptr]),
+    "ff_pointer_sequence_constrained_sample_ahead": (C.c_int, [fptr, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, fptr, C.c_int,
+                                                               C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr,
+                                                               fptr, fptr, fptr, fptr, fptr, fptr, C.c_int, fptr, C.c_int, fptr, fptr,
+                                                               fptr, C.c_int, fptr, C.c_float, C.c_int, C.c_float, C.c_int, fptr, fptr,
+                                                               C.c_int, fptr]),
+    "ff_sequence_decode_constrained_ahead_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams)]),
+    "ff_sequence_decode_constrained_ahead": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
+                                                       C.POINTER(SequenceConstrainAheadParams), fptr]),
+    "ff_sequence_decode_constrained_sample_ahead_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
+    "ff_sequence_decode_constrained_sample_ahead": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                                              C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
+                                                              C.POINTER(SequenceConstrainSampleAheadParams), fptr]),
     "ff_beam_sequence_constrained_select": (C.c_int, [C.POINTER(BeamSequenceConstrainedStep), fptr]),
     "ff_decode_sequence_constrained_beam_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
     "ff_decode_sequence_constrained_beam": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
@@ -451,7 +476,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows, *_sequence_constrained, *_sequence_constrained_sample and *_sequence_constrained_beam ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows, *_sequence_constrained, *_sequence_constrained_sample, *_sequence_constrained_beam and *_sequence_constrained*_ahead ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

@@ -667,9 +667,10 @@ def pointer_sequence_constrained_sample(logits, uniforms, fin, first, prev, visi
 
 
 def _sequence_constrained_step(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows, memory, mask, kv_len,
-                               seqs_per_group, want_rows, want_stats, counter, draw):
+                               seqs_per_group, want_rows, want_stats, counter, draw, ahead=None):
     """pointer_sequence_constrained (draw None) and pointer_sequence_constrained_sample (draw = (uniforms, row_id, temperature,
-    top_k, top_p)): the checks, the outputs and the launch the two share."""
+    top_k, top_p)): the checks, the outputs and the launch the two share; ahead (as _lookahead_operands takes it): their closure
+    forms, pointer_sequence_constrained_ahead and pointer_sequence_constrained_sample_ahead."""
     _dev(logits, "logits")
     out = {}
     B, S, spg, nw, E, rows, stats = _step_operands(logits, seqs_per_group, mask, kv_len, memory, want_rows, want_stats, out)
@@ -710,11 +711,54 @@ def _sequence_constrained_step(logits, fin, first, prev, visited, flags, ntok, t
     if draw is not None:
         d = _draw_operands(draw, B)      # (`d` keeps a contiguous copy of row_id alive over the call)
         entry, tail = "ff_pointer_sequence_constrained_sample", (_p(d[0]), d[1], _p(d[2])) + d[3:]
+    if ahead is not None:      # (ONCE is this rule's own bit: the look-aheads' flag checks are about the other two)
+        form, close_dist, cycle_len, budget = _lookahead_operands(ahead, flags & ~_L.FF_CONSTRAIN_ONCE, S, L, nw, dev,
+                                                                  entry[3:] + "_ahead")
+        entry, tail = entry + "_ahead", tail + (form, _p(close_dist), _p(cycle_len), budget)
     _L.check(getattr(_L.load(), entry)(
         _p(logits), logits.stride(0), S, _p(mask), _p(kv_len), B, spg, _p(fol), L, flags, ntok, sep, eos, _p(fin), _p(first),
         _p(prev), _p(vis), _p(out["mask_rows"]), _p(out["next"]), _p(out["logprob"]), _p(out["fin"]), _p(out["dead_end"]),
         _p(out["first"]), _p(out["prev"]), _p(memory), E, _p(rows), E, _p(stats), _p(counter), *tail, _stream()), entry)
     return out
+
+
+SEQUENCE_CLOSURES = {"lookahead": "ahead", "exact": "exact"}      # sequence_constrain_closure -> _lookahead_operands' form
+
+
+def _sequence_closure(closure, close_dist, cycle_len, budget):
+    if closure not in SEQUENCE_CLOSURES:
+        raise ValueError("closure=%r: must be 'lookahead' or 'exact'" % (closure,))
+    return ("exact", cycle_len, budget) if closure == "exact" else ("ahead", close_dist, cycle_len, budget)
+
+
+@_on_tensor_device
+def pointer_sequence_constrained_ahead(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows, closure, cycle_len,
+                                       budget, close_dist=None, memory=None, mask=None, kv_len=None, seqs_per_group=1,
+                                       want_rows=False, want_stats=False, counter=None):
+    """pointer_sequence_constrained with a closure look-ahead (ff_pointer_sequence_constrained_ahead).  closure
+    "lookahead": under CONNECT an edge b is also masked when close_dist[w][first][b] > budget (loop open) or cycle_len[w][b] >
+    budget (loop closed); "exact" (NO_REPEAT as well, at most 2048 keys): with the loop open when no path of at most `budget`
+    hops leads from b to the loop's first edge through edges that are neither padded nor in the row's visited words (under ONCE:
+    the edges of every face so far), with it closed the cycle_len rule; close_dist is not read.  close_dist [W, L, L] / cycle_len
+    [W, L] uint8 (ops.follow_distance), budget in 0..254.  The dead-end vote runs after these masks; the two fix-ups of the closed
+    state are unchanged.  Operands and results are pointer_sequence_constrained's; "lookahead" with both tables zero gives them
+    bit for bit."""
+    return _sequence_constrained_step(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows, memory, mask, kv_len,
+                                      seqs_per_group, want_rows, want_stats, counter, None,
+                                      _sequence_closure(closure, close_dist, cycle_len, budget))
+
+
+@_on_tensor_device
+def pointer_sequence_constrained_sample_ahead(logits, uniforms, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows,
+                                              closure, cycle_len, budget, close_dist=None, temperature=1.0, top_k=0, top_p=1.0,
+                                              row_id=None, memory=None, mask=None, kv_len=None, seqs_per_group=1, want_rows=False,
+                                              want_stats=False, counter=None):
+    """pointer_sequence_constrained_sample with a closure look-ahead (ff_pointer_sequence_constrained_sample_ahead):
+    pointer_sequence_constrained_ahead's byte row with pointer_sequence_constrained_sample's draw from it.  temperature=0 is
+    pointer_sequence_constrained_ahead's step, bit for bit."""
+    return _sequence_constrained_step(logits, fin, first, prev, visited, flags, ntok, tok_sep, tok_eos, follows, memory, mask, kv_len,
+                                      seqs_per_group, want_rows, want_stats, counter, (uniforms, row_id, temperature, top_k, top_p),
+                                      _sequence_closure(closure, close_dist, cycle_len, budget))
 
 
 def _draw_operands(draw, B):

@@ -105,6 +105,10 @@ class SurfaceFormerBase(nn.Module):
                                        # the rule leaves, under sample_temperature / sample_top_k / sample_top_p; 0 = greedy
         self.sequence_constrain_beams = 0     # ... with sequence_constrain: W in 1..8 = the W best rows per WIREFRAME among the rows the
                                        # rule leaves, under sequence_beam_stop; 0 = greedy
+        self.sequence_constrain_closure = None   # ... with sequence_constrain "loops" / "coedge_loops", alone or with
+                                       # sequence_constrain_samples: "lookahead" / "exact" = the closure look-ahead of the rule (DESIGN.md
+                                       # 35): an edge from which the loop cannot close inside the row is masked; the tables are built
+                                       # with ops.follow_distance; inputs["close_dist"] / inputs["cycle_len"] override them; None = off
         self.sequence_faces = False    # single-sequence model: "parse" / "enclosed" = the decoded rows also leave as faces, on the device
                                        # (inputs["sequence_faces"]: ops.face_seq_rows + ops.face_seq_votes behind the decode,
                                        # DESIGN.md 31); "enclosed" walks the enclosure rule on the follow table (constrain_tol) and
@@ -422,6 +426,10 @@ class SurfaceFormerBase(nn.Module):
             mode = _modes.SEQUENCE_CONSTRAIN_BEAM
             raise ValueError("%s is a SurfaceFormer option (%s); SurfaceFormer_Parallel %s per anchor with %s"
                              % ((mode.subject, mode.sequence.model_has) + mode.sequence.parallel_has))
+        if parallel and getattr(self, "sequence_constrain_closure", None) is not None:      # (likewise)
+            raise ValueError("sequence_constrain_closure is a SurfaceFormer option (the closure look-ahead of the loop rule of the "
+                             "single-sequence model's row); SurfaceFormer_Parallel looks ahead per anchor with constrain_lookahead / "
+                             "constrain_exact")
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
@@ -529,6 +537,9 @@ class SurfaceFormerBase(nn.Module):
             raise ValueError("score() excludes sequence_constrain_samples: set model.sequence_constrain_samples = 0 to score given paths")
         if getattr(self, "sequence_constrain_beams", 0):
             raise ValueError("score() excludes sequence_constrain_beams: set model.sequence_constrain_beams = 0 to score given paths")
+        if getattr(self, "sequence_constrain_closure", None) is not None:
+            raise ValueError("score() excludes sequence_constrain_closure: set model.sequence_constrain_closure = None to score given "
+                             "paths")
         if not self.engine_supported():
             raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
         eng, memory, mask, kv_len = self._encode(inputs)

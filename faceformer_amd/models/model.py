@@ -203,6 +203,11 @@ class SurfaceFormer(SurfaceFormerBase):
         if W:
             found = (_modes.SEQUENCE_CONSTRAIN_BEAM, W)
             found[0].sequence.model_values(self, W, inputs)
+        # the closure look-ahead of sequence_constrain and of its sampled form, likewise behind the recorded refusals
+        closure = _modes.sequence_constrain_closure_value(getattr(self, "sequence_constrain_closure", None), SC, W)
+        if closure is not None:
+            found = ((_modes.SEQUENCE_CONSTRAIN_SAMPLE_AHEAD, R) if R else (_modes.SEQUENCE_CONSTRAIN_AHEAD, SC))
+            found[0].sequence.model_values(self, found[1], inputs)
         return found
 
     def _forward_eval_sequence(self, inputs, eng, memory, mask, kv_len, T, mode, value, G):

@@ -1631,6 +1631,131 @@ int ff_decode_sequence_constrained_sample(const ff_model* m, const ff_decode_par
                                           void* workspace, size_t workspace_bytes,
                                           const ff_sequence_constrain_sample_params* constrain_sample, ff_stream_t stream);
 
+/* ---- closure look-ahead of the loop-constrained single-sequence decode (opt-in, FF_SEQ2SEQ; entries added within ABI 105;
+ * DESIGN.md 35) ---------------------------------------------------------------------------------------------------------------------
+ * The single-sequence reference decodes ONE greedy sequence per wireframe: select_next takes the argmax of the masked logit row
+ * (model.py:161-167) inside the loop of model.py:193-210, which starts every sequence from SOS (model.py:191).  These entries
+ * restate those call sites under ff_pointer_sequence_constrained's rule (greedy) and ff_pointer_sequence_constrained_sample's draw
+ * with ONE more mask in front of the dead-end vote: an edge from which the current loop can no longer close inside the row is
+ * masked.  form 1 = the closure look-ahead ("lookahead"), form 2 = the exact one ("exact").  ff_pointer_sequence_constrained's
+ * rule and ff_pointer_sequence_constrained_sample's draw hold wherever they are not restated here.
+ *
+ * The contract.
+ * Distances and tables are ff_follow_distance's (the look-ahead of ff_pointer_constrained_ahead):
+ *   - close_dist[w][f][b] = D(b -> f), shape [N, L, L], uint8.
+ *   - cycle_len[w][b] = D(b -> b), shape [N, L], uint8.
+ *   - 255 means unreachable or more than hmax hops.
+ *   - ff_follow_distance builds them, unchanged.
+ * Budget.  The step that selects position p has budget = min(T - 1 - p, 254).
+ *   - An edge chosen at p that closes the loop D - 1 edges later leaves room for SEP at position p + D <= T - 1.
+ *   - This model's T exceeds 256 (config A: 259), so the engine clamps.  ff_decode_constrained_ahead's T <= 256 refusal does not
+ *     apply to these entries.
+ *   - The consequence is part of the contract: a loop of more than 254 edges counts as not closable.
+ *   - The step operators keep taking budget in 0..254 and keep refusing anything else.
+ *   - The model builds the tables with hmax = min(max(T - 2, 1), 254).
+ * form 1 ("lookahead").  For an unfinished row under CONNECT, on top of ff_pointer_sequence_constrained's masks:
+ *   - with the loop open, edge b is also masked when close_dist[w][first][b] > budget;
+ *   - with the loop closed (with or without an edge in the current face), edge b is also masked when cycle_len[w][b] > budget.
+ * form 2 ("exact") needs NO_REPEAT as well.
+ *   - With the loop open, edge b is also masked when D_V(b -> first) > budget.  D_V is ff_pointer_constrained_exact's search over
+ *     the edges that are neither padded nor in the row's visited words.
+ *   - Under FF_CONSTRAIN_ONCE those words hold the edges of every face so far.  That is the intended meaning: an edge an earlier
+ *     face used cannot carry this loop home.
+ *   - With the loop closed, the static cycle_len rule applies, as in ff_pointer_constrained_exact.
+ * Dead ends and specials.
+ *   - The dead-end vote runs after these masks.  It can only fire with the loop open, it re-opens SEP alone, and
+ *     dead_end[row, p] = 1 now also means "cannot close within the row".
+ *   - The two closed-state fix-ups (EOS opened; SEP masked while prev == none) are unchanged.  A closed row whose edges are all
+ *     masked therefore selects SEP or EOS, and that is not a dead end.
+ * Unchanged from ff_pointer_sequence_constrained / ff_pointer_sequence_constrained_sample: argmax and ties, the log-probability
+ * (renormalised over the row after all masks), the draw (top-k and top-p act on that row), the state update, finish, the stop
+ * rule, steps, step_counts and the zero padding.
+ * Identities.
+ *   (a) form 1 with both tables all zero equals the plain decode of the same flags, bit for bit (greedy and sampled, operator and
+ *       engine).
+ *   (b) For every row and step, the edge keys form 2 masks contain those form 1 masks with the same cycle_len and
+ *       ff_follow_distance's close_dist.
+ *   (c) Temperature 0 at any R: every draw equals the greedy decode of the same form and flags.  Tokens, log-probability bits,
+ *       dead flags, open_end and steps all match.
+ *   (d) A row in a closed state has the same byte row under both forms.
+ * Guarantees, exact given the tables.
+ *   (g1) Under either form open_end == 0 for every row and draw.
+ *   (g2) Under form 2, dead_end is raised only at a position whose previous position opened the current loop.
+ *   (g3) ff_decode_sequence_constrained's guarantee that every complete face of a row is a loop of the table still holds.
+ * Unused, nothing changes.  Every other entry launches and lays out what it did before these.
+ *
+ * ff_pointer_sequence_constrained_ahead / ff_pointer_sequence_constrained_sample_ahead: one step of B sequences; the plain
+ *   operator's arguments, then form, close_dist [wireframes, L, L] (read by form 1 only), cycle_len [wireframes, L], budget.
+ * ff_sequence_decode_constrained_ahead / ff_sequence_decode_constrained_sample_ahead (named outside the ff_decode prefix, whose
+ *   entries have recorded refusal and size tables that predate these): the plain entry's argument list; the
+ *   parameter structs add form, close_dist and cycle_len (DEVICE, the whole batch's).  Nothing new lies in the workspace: the size
+ *   queries equal ff_decode_sequence_constrained_workspace_bytes / ff_decode_sequence_constrained_sample_workspace_bytes.
+ * FF_ERR_ARG before any launch, every output untouched, for everything ff_decode_sequence_constrained /
+ * ff_decode_sequence_constrained_sample refuse, for CONNECT clear, form 2 without NO_REPEAT, a NULL required table (form 2 needs
+ * only cycle_len), a form outside 1..2, and more than 2048 keys (L + ntok) under form 2. */
+int ff_pointer_sequence_constrained_ahead(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len, int B,
+                                          int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok, int tok_sep,
+                                          int tok_eos, const int* fin_in, const int* first_in, const int* prev_in,
+                                          unsigned int* visited, unsigned char* mask_rows, int* next_tok, float* logprob,
+                                          int* fin_out, int* dead_end, int* first_out, int* prev_out, const float* memory, int E,
+                                          float* next_rows, int ldnext, float* next_stats, int* count_unfinished, int form,
+                                          const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                                          ff_stream_t stream);
+int ff_pointer_sequence_constrained_sample_ahead(float* logits, int ldlogits, int S, const unsigned char* mask, const int* kv_len,
+                                                 int B, int seqs_per_group, const unsigned int* follows, int L, int flags, int ntok,
+                                                 int tok_sep, int tok_eos, const int* fin_in, const int* first_in,
+                                                 const int* prev_in, unsigned int* visited, unsigned char* mask_rows, int* next_tok,
+                                                 float* logprob, int* fin_out, int* dead_end, int* first_out, int* prev_out,
+                                                 const float* memory, int E, float* next_rows, int ldnext, float* next_stats,
+                                                 int* count_unfinished, const float* uniforms, int num_uniforms, const int* row_id,
+                                                 float temperature, int top_k, float top_p, int form,
+                                                 const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                                                 ff_stream_t stream);
+typedef struct ff_sequence_constrain_ahead_params {
+  int flags;
+  const unsigned int* follows;
+  int tok_sep;
+  float* logprob;
+  int* dead_end;
+  int* open_end;
+  int form;
+  const unsigned char* close_dist;
+  const unsigned char* cycle_len;
+} ff_sequence_constrain_ahead_params;
+size_t ff_sequence_decode_constrained_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p);
+int ff_sequence_decode_constrained_ahead(const ff_model* m, const ff_decode_params* p,
+                                         const float* memory, const unsigned char* mask, const int* kv_len,
+                                         int64_t* predict, int* steps_done, int* step_counts, float* trace_logits, int* seq_of_row,
+                                         void* workspace, size_t workspace_bytes, const ff_sequence_constrain_ahead_params* ahead,
+                                         ff_stream_t stream);
+typedef struct ff_sequence_constrain_sample_ahead_params {
+  int num_samples;
+  float temperature;
+  int top_k;
+  float top_p;
+  const float* uniforms;
+  int flags;
+  const unsigned int* follows;
+  int tok_sep;
+  int64_t* samples;
+  float* logprob;
+  float* scores;
+  int* dead_end;
+  int* open_end;
+  float* predict_logprob;
+  int* predict_dead_end;
+  int* predict_open_end;
+  int form;
+  const unsigned char* close_dist;
+  const unsigned char* cycle_len;
+} ff_sequence_constrain_sample_ahead_params;
+size_t ff_sequence_decode_constrained_sample_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p, int num_samples);
+int ff_sequence_decode_constrained_sample_ahead(const ff_model* m, const ff_decode_params* p,
+                                                const float* memory, const unsigned char* mask, const int* kv_len,
+                                                int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+                                                int* seq_of_row, void* workspace, size_t workspace_bytes,
+                                                const ff_sequence_constrain_sample_ahead_params* constrain_sample, ff_stream_t stream);
+
 /* ---- beam search over the loop-constrained single-sequence decode (opt-in, FF_SEQ2SEQ; entries added within ABI 105)
  * The W best complete, loop-valid rows per wireframe in one pass, off one encoding and one set of cross-attention K | V:
  * ff_decode_sequence_beam's search over the rows ff_pointer_sequence_constrained's rule leaves, every beam carrying the rule's

@@ -7,7 +7,11 @@ Every file of build.SOURCES is compiled with build.FLAGS + --cuda-device-only -S
 Printed per file: the kernel count and the sha256 of the per-kernel texts sorted by symbol.  With --against, the same for the
 other checkout's sources (compiled with THIS checkout's flags), and whether the symbol sets, every kernel's text and the order
 of the kernels are equal; the kernels that differ are named and the exit status is 1.  A file of build.SOURCES that the other
-checkout does not have is listed with its own count and digest and compared with nothing."""
+checkout does not have is listed with its own count and digest and compared with nothing.  With --renamed as well, a file that
+differs is compared once more kernel by kernel after renaming: the symbol itself, a trailing default template argument a kernel
+template gained (`Li0E`), the function number in local labels (.LBB<n>_, .Lfunc_end<n>) and the assembly comments (which name
+blocks by function number) are taken out, and the other checkout's kernels are listed as `same` / `DIFF` with the new symbols and
+whether the old ones kept their order."""
 import argparse
 import hashlib
 import os
@@ -39,6 +43,17 @@ def kernels(root, src, tmp):
     return res
 
 
+def renamed(ks):
+    """{symbol without an added default template argument: text with symbol, label numbers and comments taken out}, order."""
+    out, order = {}, []
+    for sym, t in ks:
+        name = re.sub(r"ELi0EEEvT_$", "EEEvT_", sym)
+        t = re.sub(r"\.(LBB|Lfunc_end|Lfunc_begin)\d+", r".\1n", t.replace(sym, "SYM"))
+        out[name] = "\n".join(re.sub(r"\s*;.*$", "", line).rstrip() for line in t.splitlines())
+        order.append(name)
+    return out, order
+
+
 def digest(ks):   # (symbol, newline, text -- the form whose digests profiles/launch_layer/device_code.txt recorded)
     return hashlib.sha256("".join(k + "\n" + t for k, t in sorted(ks)).encode()).hexdigest()
 
@@ -46,6 +61,7 @@ def digest(ks):   # (symbol, newline, text -- the form whose digests profiles/la
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--against", metavar="CHECKOUT", help="compare with the sources of another checkout of this repository")
+    ap.add_argument("--renamed", action="store_true", help="with --against: compare a differing file again after renaming")
     args = ap.parse_args()
     roots = [ROOT] + ([os.path.abspath(args.against)] if args.against else [])
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
@@ -73,6 +89,12 @@ def main():
         print("  sha256 other %s\n  sha256 here  %s" % (digest(old), digest(new)))
         for k in differ:
             print("  differs: " + k)
+        if args.renamed and not ok:
+            (rn, on), (ro, oo) = renamed(new), renamed(old)
+            for k in oo:
+                print("  after renaming: %s  %s" % ("same" if rn.get(k) == ro[k] else "DIFF", k))
+            print("  after renaming: %d new symbols; the other checkout's kernels keep their order: %s"
+                  % (len([k for k in on if k not in ro]), [k for k in on if k in ro] == oo))
     return 1 if bad else 0
 
 
