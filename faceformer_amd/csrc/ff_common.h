@@ -221,7 +221,9 @@ int ff_sequence_constrain_sample_finalize(const int* tok, const float* lp, const
 
 // Sequence-constrained beam decode (ff_constrain_seq.hip): `step` supplies the rule's and the beams' operands, io
 // the common ones (io.rows = groups * width); W beams per wireframe in the sequence beam decode's layout.
-int ff_beam_sequence_constrained_select_sync(const ff_step_io& io, const ff_beam_sequence_constrained_step* step, ff_stream_t stream);
+// `ahead`: the closure look-ahead's tables and budget, null = the plain launch.
+int ff_beam_sequence_constrained_select_sync(const ff_step_io& io, const ff_beam_sequence_constrained_step* step,
+                                             const ff_lookahead_io* ahead, ff_stream_t stream);
 int ff_sequence_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* open, int* parent, int* first, int* prev,
                                     unsigned* visited, int Bc, int W, int L, int sos, hipStream_t st);
 int ff_sequence_constrain_beam_finalize(const int* tok, const int* parent, const float* score, const int* fin, const int* dead,

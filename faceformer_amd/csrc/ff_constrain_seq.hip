@@ -34,6 +34,11 @@
 // rule's update of the PARENT's (first, prev); the wave writes the W * fw words of visited_out from visited_in[parent] together.
 // All state is read from *_in and written to *_out.  STOP picks what the wave adds to the stop counter (DESIGN.md 30's "all" or
 // "best").  No LDS beyond the four counter words, no barrier.
+//
+// The beam form's closure look-aheads are compile-time forms of that kernel, <W, STOP, FORM>: the argument struct
+// then carries the wireframes' two distance tables and the launch's one budget, and ff_sequence_write_row<FORM> masks every
+// unfinished non-empty beam's row from that beam's own (first, prev) and visited_in words -- under FF_LOOP_EXACT one search per
+// such beam, W in a row on the one wave.  Candidates, scores, order, the state update and the counters are the plain form's lines.
 #include <float.h>
 
 #include "ff_common.h"
@@ -480,9 +485,28 @@ struct SeqConBeamArgs {
   int* parent; int* tok;         // [B] out
 };
 
+// The closure forms' operands: the above, and what ff_loop_write_row<FF_LOOP_AHEAD | FF_LOOP_EXACT> reads.  A struct
+// of its own: the plain forms' argument layout, and with it their device code, stays what it was.  The tables are per wireframe
+// and shared by its W beams; all beams of a launch sit at the same position, so there is one budget.
+struct SeqConBeamClosureArgs : SeqConBeamArgs {
+  const unsigned char* close_dist;   // FF_LOOP_AHEAD only: [wireframes, L, L] bytes
+  const unsigned char* cycle_len;    // FF_LOOP_AHEAD, FF_LOOP_EXACT: [wireframes, L] bytes
+  int budget;                        // the step's: min(T - 1 - position, 254)
+};
+template <int FORM> struct SeqConBeamArgsOf { using type = SeqConBeamClosureArgs; };
+template <> struct SeqConBeamArgsOf<FF_LOOP_PLAIN> { using type = SeqConBeamArgs; };
+
+// (the closure forms' launch is defined at the end of this file, behind every kernel that was there before)
+int seq_beam_closure_launch(const SeqConBeamArgs& plain, const ff_lookahead_io& la, int W, int stop_best, dim3 grid, dim3 block,
+                            hipStream_t st);
+
 // STOP 0 ("all"): the counter is the non-empty beams unfinished after the step; STOP 1 ("best"): the groups whose rank 0 is.
-template <int W, int STOP>
-__global__ __launch_bounds__(256) void beam_sequence_constrained_select_kernel(SeqConBeamArgs a) {
+// FORM: FF_LOOP_PLAIN, or one of the closure look-aheads -- every unfinished non-empty beam then forms its byte row
+// from its OWN (first, prev) and its OWN visited words against the wireframe's tables and the launch's budget; under FF_LOOP_EXACT
+// that is one search per such beam, W in a row on the one wave.  The search, the scores and the state update are the plain form's
+// lines: nothing is restated.
+template <int W, int STOP, int FORM = FF_LOOP_PLAIN>
+__global__ __launch_bounds__(256) void beam_sequence_constrained_select_kernel(typename SeqConBeamArgsOf<FORM>::type a) {
   const PointerArgs& pa = a.p;
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -499,7 +523,8 @@ __global__ __launch_bounds__(256) void beam_sequence_constrained_select_kernel(S
     const int my_f = lane < W ? a.fin_in[b0 + lane] : 0;
     const int my_first = ff_loop_edge(lane < W ? a.first_in[b0 + lane] : -1, a.L);
     const int my_prev = ff_loop_edge(lane < W ? a.prev_in[b0 + lane] : -1, a.L);
-    const FFLoopRule rule{a.follows, a.L, fw, a.flags, ntok, nullptr, nullptr, 0};
+    FFLoopRule rule{a.follows, a.L, fw, a.flags, ntok, nullptr, nullptr, 0};
+    if constexpr (FORM != FF_LOOP_PLAIN) { rule.close_dist = a.close_dist; rule.cycle_len = a.cycle_len; rule.budget = a.budget; }
     unsigned deadmask = 0u;   // bit k: beam k dead-ended at this step (wave-uniform)
     float lsc[W];
     int lix[W];
@@ -515,9 +540,14 @@ __global__ __launch_bounds__(256) void beam_sequence_constrained_select_kernel(S
         continue;
       }
       const int b = b0 + k;
-      if (ff_sequence_write_row(pa, rule, lane, w, kv, mrow, first, prev, a.visited_in + (size_t)b * fw, a.rows + (size_t)b * S, a.sep,
-                                a.eos))
-        deadmask |= 1u << k;
+      bool dead;
+      if constexpr (FORM == FF_LOOP_PLAIN)   // (the plain forms keep the line they had)
+        dead = ff_sequence_write_row(pa, rule, lane, w, kv, mrow, first, prev, a.visited_in + (size_t)b * fw, a.rows + (size_t)b * S, a.sep,
+                                     a.eos);
+      else
+        dead = ff_sequence_write_row<FORM>(pa, rule, lane, w, kv, mrow, first, prev, a.visited_in + (size_t)b * fw,
+                                           a.rows + (size_t)b * S, a.sep, a.eos);
+      if (dead) deadmask |= 1u << k;
       float m, b2, lsum;
       int i1;
       ff_pointer_mask_reduce<true>(pa, b, lane, &m, &b2, &i1, &lsum);
@@ -650,8 +680,10 @@ __global__ void sequence_constrain_beam_finalize_kernel(const int* __restrict__ 
 
 // The one launch behind ff_beam_sequence_constrained_select and the engine's step; `io` carries the common operands
 // (io.rows = groups * width; its terminator range is not read: the rule has its two tokens).
-int ff_beam_sequence_constrained_select_sync(const ff_step_io& io_in, const ff_beam_sequence_constrained_step* d, ff_stream_t stream) {
-  const char* op = "ff_beam_sequence_constrained_select";
+// `ahead`: the closure forms' tables and budget, checked by ff_lookahead_check; null: the plain launch.
+int ff_beam_sequence_constrained_select_sync(const ff_step_io& io_in, const ff_beam_sequence_constrained_step* d,
+                                             const ff_lookahead_io* ahead, ff_stream_t stream) {
+  const char* op = ahead ? "ff_beam_sequence_constrained_select_ahead" : "ff_beam_sequence_constrained_select";
   const int S = io_in.S, W = d->width, groups = io_in.rows / W;
   SeqConBeamArgs a;
   memset(&a, 0, sizeof(a));
@@ -664,6 +696,8 @@ int ff_beam_sequence_constrained_select_sync(const ff_step_io& io_in, const ff_b
                    d->prev_in && d->prev_out && d->visited_in && d->visited_out && d->mask_rows && d->parent && d->next_tok,
                "%s: null pointer", op);
   FF_CHECK_ARG(d->visited_in != d->visited_out, "%s: visited_out must not be visited_in", op);
+  // (ONCE is this rule's own bit: the look-aheads' flag checks are about the other two)
+  if (ahead) FF_RETURN_IF(ff_lookahead_check(op, ff_loop_rule_io{d->follows, d->L, d->flags, d->ntok}, S, *ahead));
   a.p.extra = d->mask_rows; a.p.ldextra = S;
   a.groups = groups; a.rows = d->mask_rows; a.follows = d->follows; a.L = d->L; a.fw = (d->L + 31) >> 5; a.flags = d->flags; a.ntok = d->ntok;
   a.sep = d->tok_sep; a.eos = d->tok_eos;
@@ -675,6 +709,7 @@ int ff_beam_sequence_constrained_select_sync(const ff_step_io& io_in, const ff_b
   hipStream_t st = (hipStream_t)stream;
   FFProfScope prof(FF_CAT_POINTER, (double)io.rows * S * 14.0, st);
   const dim3 grid(ff_cdiv(groups, 4)), block(256);
+  if (ahead) return seq_beam_closure_launch(a, *ahead, W, d->stop_best, grid, block, st);
   const int rc = ff_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(W, [&](auto w) {
     return ff_dispatch<0, 1>(d->stop_best, [&](auto f) {
       hipLaunchKernelGGL((beam_sequence_constrained_select_kernel<decltype(w)::value, decltype(f)::value>), grid, block, 0, st, a);
@@ -693,7 +728,23 @@ extern "C" int ff_beam_sequence_constrained_select(const ff_beam_sequence_constr
   return ff_beam_sequence_constrained_select_sync(
       ff_step_io{d->logits, d->ldlogits, d->S, d->mask, d->kv_len, d->groups * d->width, d->groups_per_wireframe * d->width, 0, 0, d->ntok,
                  d->memory, d->E, d->next_rows, d->ldnext, d->next_stats, d->count_unfinished, nullptr, nullptr},
-      d, stream);
+      d, nullptr, stream);
+}
+
+// One step of the beam search under the rule with a closure look-ahead: the step descriptor above, unchanged, then the
+// form (1 = the closure look-ahead, 2 = the exact one, which reads no close_dist), the wireframes' tables and the step's budget.
+extern "C" int ff_beam_sequence_constrained_select_ahead(const ff_beam_sequence_constrained_step* d, int form,
+                                                         const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                                                         ff_stream_t stream) {
+  const char* op = "ff_beam_sequence_constrained_select_ahead";
+  FF_CHECK_ARG(d != nullptr, "%s: null descriptor", op);
+  FF_RETURN_IF(ff_beam_check_sizes(op, d->groups, d->width, d->groups_per_wireframe, d->S));
+  ff_lookahead_io ahead;
+  FF_RETURN_IF(seq_closure_form(op, form, close_dist, cycle_len, budget, &ahead));
+  return ff_beam_sequence_constrained_select_sync(
+      ff_step_io{d->logits, d->ldlogits, d->S, d->mask, d->kv_len, d->groups * d->width, d->groups_per_wireframe * d->width, 0, 0, d->ntok,
+                 d->memory, d->E, d->next_rows, d->ldnext, d->next_stats, d->count_unfinished, nullptr, nullptr},
+      d, &ahead, stream);
 }
 
 int ff_sequence_constrain_beam_init(int* tok, float* score, int* fin, int* dead, int* open, int* parent, int* first, int* prev,
@@ -738,6 +789,31 @@ int seq_constrain_closure_launch(const Plain& plain, const ff_lookahead_io& la, 
     hipLaunchKernelGGL((pointer_sequence_constrained_kernel<SeqClosureArgs<Plain>, FF_LOOP_EXACT>), dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((pointer_sequence_constrained_kernel<SeqClosureArgs<Plain>, FF_LOOP_AHEAD>), dim3(ff_cdiv(B, 4)), dim3(256), 0, st, a);
+  FF_CHECK_LAUNCH();
+  return FF_OK;
+}
+}  // namespace
+
+// ==== the closure look-aheads of the sequence-constrained beam step =======================================================
+namespace {
+// The plain form's operands (checked and filled by the caller) with the look-ahead's, launched in the form `la` names.  The 32
+// closure forms are instantiated here, behind everything the file had, so that every kernel before them keeps its code.
+int seq_beam_closure_launch(const SeqConBeamArgs& plain, const ff_lookahead_io& la, int W, int stop_best, dim3 grid, dim3 block,
+                            hipStream_t st) {
+  SeqConBeamClosureArgs a;
+  memset(&a, 0, sizeof(a));
+  static_cast<SeqConBeamArgs&>(a) = plain;
+  a.close_dist = la.exact ? nullptr : la.close_dist; a.cycle_len = la.cycle_len; a.budget = la.budget;
+  const int rc = ff_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(W, [&](auto w) {
+    return ff_dispatch<0, 1>(stop_best, [&](auto f) {
+      return ff_dispatch<FF_LOOP_AHEAD, FF_LOOP_EXACT>(la.exact ? FF_LOOP_EXACT : FF_LOOP_AHEAD, [&](auto form) {
+        hipLaunchKernelGGL((beam_sequence_constrained_select_kernel<decltype(w)::value, decltype(f)::value, decltype(form)::value>), grid,
+                           block, 0, st, a);
+        return FF_OK;
+      });
+    });
+  });
+  FF_RETURN_IF(rc);
   FF_CHECK_LAUNCH();
   return FF_OK;
 }

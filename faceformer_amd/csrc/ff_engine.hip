@@ -1222,7 +1222,7 @@ struct DecodeRun {
             fill_beam_step(&d, c, r, step);
             d.tok_sep = mode.tok_sep; d.tok_eos = p->tok_eos; d.stop_best = mode.stop_best;
             d.open_out = buf.open + out;
-            FF_RETURN_IF(ff_beam_sequence_constrained_select_sync(sio, &d, st));
+            FF_RETURN_IF(ff_beam_sequence_constrained_select_sync(sio, &d, la, st));
           } else {
             ff_beam_constrained_step d;
             fill_beam_step(&d, c, r, step);
@@ -1950,6 +1950,33 @@ extern "C" int ff_decode_sequence_constrained_beam(const ff_model* m, const ff_d
   if ((e.given = beam != nullptr)) {
     take_beam(md, beam);
     take_rule(md, beam);
+    md.tok_sep = beam->tok_sep; md.stop_best = beam->stop_best;
+    md.finished = beam->finished; md.beam_dead_end = beam->beam_dead_end; md.beam_open_end = beam->beam_open_end;
+    md.dead_end = beam->dead_end; md.open_end = beam->open_end;
+    e.have = beam->beams && beam->scores && beam->finished && beam->beam_dead_end && beam->beam_open_end && beam->dead_end &&
+              beam->open_end;
+  }
+  return run_entry(e, md, m, p, no_refused, FF_SEQ_ARGS);
+}
+
+// (nothing of a closure look-ahead lies in the workspace: the tables are operands)
+extern "C" size_t ff_sequence_decode_constrained_beam_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width) {
+  if (width < 1 || width > 8 || !sequence_query_ok(p)) return 0;
+  return decode_workspace_bytes(m, p, nullptr, Mode(Mode::BEAM, Mode::SEQUENCE, true, width));
+}
+
+// W beams per wireframe of the single-sequence decode (model.py:161-167, 191, 193-210) over the rows the face-loop rule with a
+// closure look-ahead leaves.
+extern "C" int ff_sequence_decode_constrained_beam_ahead(const ff_model* m, const ff_decode_params* p, const float* memory,
+    const unsigned char* mask, const int* kv_len, int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+    int* seq_of_row, void* workspace, size_t workspace_bytes, const ff_sequence_constrain_beam_ahead_params* beam, ff_stream_t stream) {
+  Entry e{"ff_sequence_decode_constrained_beam_ahead", nullptr, "look-ahead beam", "ff_decode_constrained_beam_ahead",
+          "beams, scores, finished, beam_dead_end, beam_open_end, dead_end, open_end and predict", 2};
+  Mode md(Mode::BEAM, Mode::SEQUENCE, true);
+  if ((e.given = beam != nullptr)) {
+    take_beam(md, beam);
+    take_rule(md, beam);
+    take_ahead(md, beam->form, beam, beam->form == 1 ? beam->close_dist : nullptr);
     md.tok_sep = beam->tok_sep; md.stop_best = beam->stop_best;
     md.finished = beam->finished; md.beam_dead_end = beam->beam_dead_end; md.beam_open_end = beam->beam_open_end;
     md.dead_end = beam->dead_end; md.open_end = beam->open_end;

@@ -316,10 +316,13 @@ __device__ __forceinline__ bool ff_loop_write_row(const PointerArgs& pa, const F
 // (lane = key mod 64): EOS is opened, SEP is masked while the current face has no edge (prev == none).  Returns the dead-end bit.
 // pointer_sequence_constrained_kernel (ff_constrain_seq.hip) has the same lines in its own body and keeps them there: moving
 // them behind this call changed that kernel's register allocation.
+// FORM: ff_loop_write_row's compile-time form; the closure forms read r.close_dist / r.cycle_len / r.budget in front
+// of the dead-end vote, the two fix-ups stay what they are.
+template <int FORM = FF_LOOP_PLAIN>
 __device__ __forceinline__ bool ff_sequence_write_row(const PointerArgs& pa, const FFLoopRule& r, int lane, int w, int kv,
                                                       const unsigned char* mrow, int first, int prev, const unsigned* vrow,
                                                       unsigned char* xrow, int sep, int eos) {
-  const bool dead = ff_loop_write_row<FF_LOOP_PLAIN>(pa, r, lane, w, kv, mrow, first, prev, vrow, xrow);
+  const bool dead = ff_loop_write_row<FORM>(pa, r, lane, w, kv, mrow, first, prev, vrow, xrow);
   if ((r.flags & FF_CONSTRAIN_CONNECT) && !(first >= 0 && prev >= 0)) {   // closed: EOS may end the row; no empty face
     if (lane == (eos & 63)) xrow[eos] = 0;
     if (prev < 0 && lane == (sep & 63)) xrow[sep] = 1;

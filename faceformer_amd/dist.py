@@ -231,6 +231,9 @@ def decode_sharded(model, inputs, dist_mod, group=None, local_shard=False, contr
     if getattr(model, "sequence_constrain_closure", None) is not None:       # (likewise)
         raise ValueError("decode_sharded does not implement sequence_constrain_closure (%s)"
                          % _modes.SEQUENCE_CONSTRAIN.switches[0].sharded)
+    if getattr(model, "sequence_constrain_beam_closure", None) is not None:       # (likewise)
+        raise ValueError("decode_sharded does not implement sequence_constrain_beam_closure (%s)"
+                         % _modes.SEQUENCE_CONSTRAIN_BEAM.switches[0].sharded)
     if getattr(model, "constrain_samples", 0):
         raise ValueError("decode_sharded does not implement constrain_samples (%s)" % _modes.SWITCH["constrain"].sharded)
     for mode in reversed(_modes.MODES):

@@ -715,7 +715,8 @@ def sequence_rule_sample_step(raw, pad, state, flags, ntok, sep, eos, u, tempera
                 state=sequence_rule_advance(state, tok, flags, ntok, sep, follows))
 
 
-def sequence_rule_beam_step(raw, pad, scores, fin, states, flags, ntok, sep, eos, follows=None):
+def sequence_rule_beam_step(raw, pad, scores, fin, states, flags, ntok, sep, eos, follows=None, closure=None, budget=None,
+                            close_dist=None, cycle_len=None):
     """One step of ONE group (the W beams of one wireframe) of the beam form (ff_beam_sequence_constrained_select)
     on RAW logits [W, S]: scores [W] (-inf: an empty beam, no candidates), fin [W], states [W] (sequence_rule_start's form), pad
     [S] the wireframe's padding / kv_len keys.  An unfinished beam's row is sequence_rule_mask's; its candidates are the LIVE
@@ -724,7 +725,12 @@ def sequence_rule_beam_step(raw, pad, scores, fin, states, flags, ntok, sep, eos
     score first, then the lower flat index k * S + s.  -> dict(parent, tok, scores, fin, dead (this step's flag), open [W each],
     states [W], rows [W, S] (the constrained masked rows, fp64; raw for empty / finished beams), masked [W, S] (the rule's own
     byte rows), cand: the first W + 1 candidates (score, flat index) in order).  A rank past the number of candidates is empty:
-    parent = the rank, token 0, score -inf, flags clear, the state of the own index."""
+    parent = the rank, token 0, score -inf, flags clear, the state of the own index.
+
+    closure, budget, close_dist, cycle_len (closure None: the rule above, unchanged): sequence_rule_mask's closure
+    keywords, handed to every unfinished non-empty beam's own mask -- the wireframe's tables ([L, L] and [L] uint8) are shared by
+    its beams, the budget is the step's, and each beam is looked ahead from its OWN (first, prev) and visited set."""
+    ahead = {} if closure is None else dict(closure=closure, budget=budget, close_dist=close_dist, cycle_len=cycle_len)
     raw = np.asarray(raw, dtype=np.float64)
     W, S = raw.shape
     pad = np.asarray(pad, dtype=bool)
@@ -736,7 +742,7 @@ def sequence_rule_beam_step(raw, pad, scores, fin, states, flags, ntok, sep, eos
         if fin[k]:
             cand.append((float(scores[k]), k * S))
             continue
-        masks[k], dead_of[k] = sequence_rule_mask(states[k], flags, S, ntok, sep, eos, follows, pad)
+        masks[k], dead_of[k] = sequence_rule_mask(states[k], flags, S, ntok, sep, eos, follows, pad, **ahead)
         row = rows[k] = np.where(masks[k] | pad, SEQ_FILL, raw[k])
         m = row.max()
         logz = np.log(np.exp(row - m).sum())
@@ -762,14 +768,19 @@ def sequence_rule_beam_step(raw, pad, scores, fin, states, flags, ntok, sep, eos
     return out
 
 
-def sequence_rule_beam_decode(step_logits, pad, W, T, flags, ntok, sos, sep, eos, follows=None, stop="all"):
+def sequence_rule_beam_decode(step_logits, pad, W, T, flags, ntok, sos, sep, eos, follows=None, stop="all", closure=None,
+                              close_dist=None, cycle_len=None):
     """The whole rule of the beam form as a loop over G = len(pad) wireframes.  step_logits(prefixes [G * W, j + 1], j) -> RAW
     logits [G * W, S] of step j (rows of empty and finished beams are not read); pad [G, S]; follows: one table per wireframe
     (or None).  Start: every beam at sos, beam 0 with score 0, the others empty, the rule's state empty and closed.  Stop: after
     the first step that leaves `stop`'s counter at 0 ("all": the non-empty beams unfinished after the step; "best": the groups
     whose rank 0 is), else after T - 1 steps.  -> dict(beams, dead_end [G * W, T] (walked back along the parents, zero past each
     beam's EOS and past steps), scores, fin, open [G * W], steps, counts, all_counts, best_counts, parents, toks, deads, cands
-    (per step, per group), states)."""
+    (per step, per group), states).
+
+    closure (None: the rule above, unchanged) with close_dist [G, L, L] / cycle_len [G, L] (one pair of
+    follow_distance tables per wireframe; "exact" reads cycle_len only): sequence_rule_beam_step's look-ahead, the step that
+    selects position p under budget = min(T - 1 - p, 254)."""
     if stop not in ("all", "best"):
         raise ValueError("stop=%r: must be 'all' or 'best'" % (stop,))
     pad = np.asarray(pad, dtype=bool)
@@ -793,8 +804,12 @@ def sequence_rule_beam_decode(step_logits, pad, W, T, flags, ntok, sos, sep, eos
         prefixes = walk(toks)
         prefixes[:, 0] = sos
         raw = np.asarray(step_logits(prefixes, j), dtype=np.float64)
+        ahead = lambda g: {} if closure is None else dict(      # (step j selects position j + 1)
+            closure=closure, budget=min(T - 2 - j, 254), close_dist=None if close_dist is None else close_dist[g],
+            cycle_len=None if cycle_len is None else cycle_len[g])
         res = [sequence_rule_beam_step(raw[g * W:(g + 1) * W], pad[g], scores[g * W:(g + 1) * W], fin[g * W:(g + 1) * W],
-                                       states[g * W:(g + 1) * W], flags, ntok, sep, eos, None if follows is None else follows[g])
+                                       states[g * W:(g + 1) * W], flags, ntok, sep, eos, None if follows is None else follows[g],
+                                       **ahead(g))
                for g in range(G)]
         scores, fin, opn = (np.concatenate([r[k] for r in res]) for k in ("scores", "fin", "open"))
         states = [s for r in res for s in r["states"]]

@@ -377,7 +377,7 @@ class PathEngine:
                constrain_beams=None, constrain_lookahead=False, close_dist=None, cycle_len=None, constrain_exact=False,
                constrain_samples=None, constrain_beam_closure=None, sequence_samples=None, sequence_beams=None,
                sequence_beam_stop="all", sequence_constrain=None, tok_sep=None, sequence_constrain_samples=None,
-               sequence_constrain_beams=None, sequence_constrain_closure=None):
+               sequence_constrain_beams=None, sequence_constrain_closure=None, sequence_constrain_beam_closure=None):
         """Greedy decode. Returns dict(predict [N*F, T] int64, steps, decoded_seqs, [pointer], [trace
         tensors indexed like predict's rows], slots_per_step, slot_rows, [logprob]).  The opt-in modes below are parallel-variant
         options that need term_range; what each excludes is its record's list in modes.py (ValueError before anything is launched).
@@ -506,7 +506,16 @@ class PathEngine:
         neither padded nor in the row's visited words (cycle_len required, at most 2048 keys).  T may exceed 256: the budget is
         clamped, so a loop of more than 254 edges counts as not closable.  Outputs are the plain decode's under the same keys;
         `open_end` is then 0 everywhere and `dead_end` also means "cannot close within the row".  "lookahead" with both tables
-        zero equals the plain decode, bit for bit."""
+        zero equals the plain decode, bit for bit.
+
+        sequence_constrain_beam_closure="lookahead" / "exact" (only with sequence_constrain_beams >= 1 and sequence_constrain "loops" /
+        "coedge_loops" or the flag bits 3 / 7 -- "lookahead" also with CONNECT alone; not with sequence_constrain_closure, which stays
+        refused with beams; ff_sequence_decode_constrained_beam_ahead; None: the beam decode above): every beam forms
+        its byte row under sequence_constrain_closure's masks from its OWN (first, prev) and visited words, against its wireframe's
+        close_dist [N, L, L] / cycle_len [N, L] uint8 on the device ("exact": cycle_len only, at most 2048 keys) and the step's one
+        budget min(T - 1 - p, 254).  The search, the scores and the outputs are sequence_constrain_beams'; `beam_open_end` is then 0
+        on every non-empty beam.  W = 1 equals the sequence_constrain_closure greedy decode; "lookahead" with both tables zero equals
+        the plain beam decode, bit for bit."""
         SCB = _modes.sequence_constrain_beams_value(sequence_constrain_beams, _modes.sequence_constrain_flags(sequence_constrain),
                                                     sequence_samples, sequence_beams, sequence_constrain_samples) \
             if sequence_constrain_beams else 0
@@ -514,6 +523,9 @@ class PathEngine:
                                                       sequence_samples, sequence_beams) if sequence_constrain_samples else 0
         SCC = _modes.sequence_constrain_closure_value(sequence_constrain_closure, _modes.sequence_constrain_flags(sequence_constrain),
                                                       sequence_constrain_beams) if sequence_constrain_closure is not None else None
+        SCBC = _modes.sequence_constrain_beam_closure_value(
+            sequence_constrain_beam_closure, _modes.sequence_constrain_flags(sequence_constrain), SCB, sequence_constrain_closure,
+            sequence_constrain_samples) if sequence_constrain_beam_closure is not None else None
         seq = dict(sequence_samples=sequence_samples, sequence_beams=sequence_beams, sequence_constrain=sequence_constrain)
         for mode in reversed(_modes.SEQUENCE_MODES):      # (of several set together, the last one's record reports)
             value = mode.sequence.value(seq[mode.subject])
@@ -523,7 +535,7 @@ class PathEngine:
                          constrain=constrain is not None, temperature=temperature, top_k=top_k, top_p=top_p, uniforms=uniforms,
                          sequence_beam_stop=sequence_beam_stop, follow_table=follow_table, tok_sep=tok_sep, tok_eos=tok_eos,
                          trace=trace, N=memory.shape[0], S=memory.shape[1], F=F, T=T, sequence_constrain_closure=SCC,
-                         close_dist=close_dist, cycle_len=cycle_len)
+                         sequence_constrain_beam_closure=SCBC, close_dist=close_dist, cycle_len=cycle_len)
                 o[mode.subject] = value
                 if SCC and mode is _modes.SEQUENCE_CONSTRAIN:      # (an option of sequence_constrain and of its sampled form)
                     mode = _modes.SEQUENCE_CONSTRAIN_AHEAD
@@ -531,7 +543,8 @@ class PathEngine:
                     mode, o["sequence_constrain_samples"] = (_modes.SEQUENCE_CONSTRAIN_SAMPLE_AHEAD if SCC else
                                                              _modes.SEQUENCE_CONSTRAIN_SAMPLE), SCS
                 if SCB:      # (likewise)
-                    mode, o["sequence_constrain_beams"] = _modes.SEQUENCE_CONSTRAIN_BEAM, SCB
+                    mode, o["sequence_constrain_beams"] = (_modes.SEQUENCE_CONSTRAIN_BEAM_AHEAD if SCBC else
+                                                           _modes.SEQUENCE_CONSTRAIN_BEAM), SCB
                 return self._decode_sequence(mode, memory, mask_u8, kv_len, variant, o,
                                              (variant, memory.shape[0], memory.shape[1], F, T, chunk_wireframes, chunk_seqs, num_streams,
                                               chunk_max_seqs, ln_fuse_max_rows, flags, x3_min_rows), sync_every, tok_sos)

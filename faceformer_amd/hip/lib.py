@@ -230,6 +230,10 @@ class SequenceConstrainBeamParams(C.Structure):
                 ("dead_end", fptr), ("open_end", fptr), ("trace_parent", fptr)]
 
 
+class SequenceConstrainBeamAheadParams(C.Structure):
+    _fields_ = SequenceConstrainBeamParams._fields_ + [("form", C.c_int), ("close_dist", fptr), ("cycle_len", fptr)]
+
+
 FF_CONSTRAIN_NO_REPEAT = 1
 FF_CONSTRAIN_CONNECT = 2
 FF_CONSTRAIN_ONCE = 4         # ff_pointer_sequence_constrained / ff_decode_sequence_constrained only
@@ -438,6 +442,12 @@ SIGNATURES = {
     "ff_decode_sequence_constrained_beam": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
                                                       C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
                                                       C.POINTER(SequenceConstrainBeamParams), fptr]),
+    "ff_beam_sequence_constrained_select_ahead": (C.c_int, [C.POINTER(BeamSequenceConstrainedStep), C.c_int, fptr, fptr, C.c_int,
+                                                            fptr]),
+    "ff_sequence_decode_constrained_beam_ahead_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(DecodeParams), C.c_int]),
+    "ff_sequence_decode_constrained_beam_ahead": (C.c_int, [C.POINTER(Model), C.POINTER(DecodeParams), fptr, fptr, fptr, fptr,
+                                                            C.POINTER(C.c_int), C.POINTER(C.c_int), fptr, fptr, fptr, C.c_size_t,
+                                                            C.POINTER(SequenceConstrainBeamAheadParams), fptr]),
     "ff_gemm_prepare_stream": (C.c_int, [fptr]),
     "ff_face_rows": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr,
                                fptr, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
@@ -476,7 +486,7 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows, *_sequence_constrained, *_sequence_constrained_sample, *_sequence_constrained_beam and *_sequence_constrained*_ahead ones of 105 -- so the version check below cannot stand in)
+            # (entries are also added WITHIN an ABI version -- the *_lp, *_beam*, *_forced*, *_sample*, *_constrain*, *_ahead / ff_follow_distance, *_exact, ff_face_*, *_beam*_ahead, ff_face_seq_rows, *_sequence_constrained, *_sequence_constrained_sample, *_sequence_constrained_beam, *_sequence_constrained*_ahead and *_sequence_constrained_beam*_ahead ones of 105 -- so the version check below cannot stand in)
             raise HipExtensionError("%s does not export %s (stale build): rebuild it "
                                     "(python -m faceformer_amd.hip.build --force)" % (LIB_PATH, name))
         fn.restype = res

@@ -778,40 +778,40 @@ def sequence_constrain_closure_value(closure, flags, sequence_constrain_beams=0)
     return closure
 
 
-def _sequence_closure_values(o):
-    closure = o["sequence_constrain_closure"]
+def _sequence_closure_values(o, option="sequence_constrain_closure"):
+    closure = o[option]
     exact = closure == "exact"
     for name in ("cycle_len",) if exact else ("close_dist", "cycle_len"):
         if o[name] is None:
-            raise ValueError("sequence_constrain_closure=%r needs %s (ops.follow_distance)"
-                             % (closure, "cycle_len" if exact else "close_dist and cycle_len"))
+            raise ValueError("%s=%r needs %s (ops.follow_distance)"
+                             % (option, closure, "cycle_len" if exact else "close_dist and cycle_len"))
 
 
-def _sequence_closure_operand(eng, o):
+def _sequence_closure_operand(eng, o, option="sequence_constrain_closure"):
     L = o["S"] - eng.num_token
-    exact = o["sequence_constrain_closure"] == "exact"
+    exact = o[option] == "exact"
     if exact and o["S"] > EXACT_MAX_KEYS:
-        raise ValueError("sequence_constrain_closure='exact' takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
-                         % (EXACT_MAX_KEYS - eng.num_token, L, EXACT_MAX_KEYS))
+        raise ValueError("%s='exact' takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
+                         % (option, EXACT_MAX_KEYS - eng.num_token, L, EXACT_MAX_KEYS))
     for name, shape in (("cycle_len", (o["N"], L)),) if exact else (("close_dist", (o["N"], L, L)), ("cycle_len", (o["N"], L))):
         t = o[name]
         if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != shape:
             raise ValueError("%s must be a uint8 tensor of shape [%s]" % (name, ", ".join(str(v) for v in shape)))
 
 
-def _sequence_closure_tail(o):
+def _sequence_closure_tail(o, option="sequence_constrain_closure"):
     """(form, close_dist, cycle_len): what the closure entries' parameter structs add."""
-    form = SEQUENCE_CLOSURES[o["sequence_constrain_closure"]]
+    form = SEQUENCE_CLOSURES[o[option]]
     return (form, _p(o["close_dist"]) if form == 1 else None, _p(o["cycle_len"]))
 
 
-def _sequence_closure_prepare(base, m, value, inputs, dev, T, N, F, ni, order):
+def _sequence_closure_prepare(base, option, m, value, inputs, dev, T, N, F, ni, order):
     """The plain record's keyword arguments, and the tables: built on the device from the follow table (hmax = min(max(T - 2, 1),
     254), the largest budget a step compares against) or taken from inputs["close_dist"] / inputs["cycle_len"]; "exact" builds and
     reads cycle_len only.  Batch order, as the follow table."""
     from . import ops as _ops
     kw = base.prepare(m, value, inputs, dev, T, N, F, ni, order)
-    closure = m.sequence_constrain_closure
+    closure = getattr(m, option)
     names = ("cycle_len",) if closure == "exact" else ("close_dist", "cycle_len")
     given = {name: inputs.get(name) for name in names}
     if all(t is None for t in given.values()):
@@ -821,17 +821,17 @@ def _sequence_closure_prepare(base, m, value, inputs, dev, T, N, F, ni, order):
         raise ValueError("inputs['close_dist'] and inputs['cycle_len'] are given together")
     else:      # (model_values has checked shape and dtype)
         tables = {name: torch.as_tensor(t).to(dev).contiguous() for name, t in given.items()}
-    return dict(kw, sequence_constrain_closure=closure, **{name: tables[name] for name in names})
+    return dict(kw, **{option: closure}, **{name: tables[name] for name in names})
 
 
-def _sequence_closure_model_values(base):
+def _sequence_closure_model_values(base, option="sequence_constrain_closure"):
     def check(m, value, inputs):
         base.sequence.model_values(m, value, inputs)
         N, L = inputs["input"].size(0), inputs["input"].size(1)
-        closure = m.sequence_constrain_closure
+        closure = getattr(m, option)
         if closure == "exact" and L + m.num_token > EXACT_MAX_KEYS:      # (before the encoder runs)
-            raise ValueError("sequence_constrain_closure='exact' takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
-                             % (EXACT_MAX_KEYS - m.num_token, L, EXACT_MAX_KEYS))
+            raise ValueError("%s='exact' takes at most %d edges per wireframe (got %d): L + num_token <= %d keys"
+                             % (option, EXACT_MAX_KEYS - m.num_token, L, EXACT_MAX_KEYS))
         for name, shape in (("close_dist", (N, L, L)), ("cycle_len", (N, L))):
             t = inputs.get(name)
             if t is not None and (torch.as_tensor(t).dtype != torch.uint8 or tuple(torch.as_tensor(t).shape) != shape):
@@ -839,24 +839,25 @@ def _sequence_closure_model_values(base):
     return check
 
 
-def _sequence_closure_record(base, params, entry):
-    """`base` (SEQUENCE_CONSTRAIN or SEQUENCE_CONSTRAIN_SAMPLE) with sequence_constrain_closure on: the same outputs under the same
-    keys from the `_ahead` entry, whose parameter struct ends in (form, close_dist, cycle_len)."""
+def _sequence_closure_record(base, params, entry, option="sequence_constrain_closure"):
+    """`base` (SEQUENCE_CONSTRAIN, SEQUENCE_CONSTRAIN_SAMPLE or SEQUENCE_CONSTRAIN_BEAM) with `option` (sequence_constrain_closure;
+    the beam record's: sequence_constrain_beam_closure) on: the same outputs under the same keys from the `_ahead` entry, whose
+    parameter struct ends in (form, close_dist, cycle_len)."""
     def values(o):
         base.values(o)
-        _sequence_closure_values(o)
+        _sequence_closure_values(o, option)
 
     def operand(eng, o):
         base.operand(eng, o)
-        _sequence_closure_operand(eng, o)
+        _sequence_closure_operand(eng, o, option)
 
     def tail(o, ptrs, traced):
         plain = base.tail(o, ptrs, traced)[0]._obj      # (the plain struct, filled as the plain record fills it)
-        return (C.byref(params(*[getattr(plain, f) for f, _ in plain._fields_], *_sequence_closure_tail(o))),)
+        return (C.byref(params(*[getattr(plain, f) for f, _ in plain._fields_], *_sequence_closure_tail(o, option))),)
     return base._replace(
         entry=entry, values=values, operand=operand, own=base.own + (("close_dist", torch.uint8), ("cycle_len", torch.uint8)), tail=tail,
-        prepare=lambda *a: _sequence_closure_prepare(base, *a),
-        sequence=base.sequence._replace(model_values=_sequence_closure_model_values(base)))
+        prepare=lambda *a: _sequence_closure_prepare(base, option, *a),
+        sequence=base.sequence._replace(model_values=_sequence_closure_model_values(base, option)))
 
 
 # sequence_constrain ('loops' / 'coedge_loops') with its option sequence_constrain_closure (DESIGN.md 35): the same greedy / sampled
@@ -867,6 +868,47 @@ SEQUENCE_CONSTRAIN_AHEAD = _sequence_closure_record(
         subject="sequence_constrain_closure")
 SEQUENCE_CONSTRAIN_SAMPLE_AHEAD = _sequence_closure_record(
     SEQUENCE_CONSTRAIN_SAMPLE, _L.SequenceConstrainSampleAheadParams, "ff_sequence_decode_constrained_sample_ahead")
+
+
+
+def sequence_constrain_beam_closure_value(closure, flags, sequence_constrain_beams=0, sequence_constrain_closure=None,
+                                          sequence_constrain_samples=0):
+    """The form of a `sequence_constrain_beam_closure` value: None -> None (the option is off); else "lookahead" or
+    "exact", only with sequence_constrain_beams >= 1 and `sequence_constrain` set to a form that has FF_CONSTRAIN_CONNECT (`flags`:
+    sequence_constrain_flags of it; "exact" needs FF_CONSTRAIN_NO_REPEAT as well), and not with sequence_constrain_closure (the
+    greedy and the sampled decode's option, which stays refused with beams) or sequence_constrain_samples."""
+    if closure is None:
+        return None
+    if not isinstance(closure, str) or closure not in SEQUENCE_CLOSURES:
+        raise ValueError("sequence_constrain_beam_closure=%r: must be None, 'lookahead' or 'exact'" % (closure,))
+    if sequence_constrain_closure is not None:
+        raise ValueError("sequence_constrain_beam_closure excludes sequence_constrain_closure: that is the look-ahead of the greedy and "
+                         "the sampled decode; under sequence_constrain_beams set sequence_constrain_beam_closure alone")
+    if sequence_constrain_samples:
+        raise ValueError("sequence_constrain_beam_closure excludes sequence_constrain_samples: the sampled decode looks ahead with "
+                         "sequence_constrain_closure")
+    if not sequence_constrain_beams:
+        raise ValueError("sequence_constrain_beam_closure=%r needs sequence_constrain_beams >= 1: it is the closure look-ahead of the "
+                         "beam search over the rows the face-loop rule leaves (the greedy decode's is sequence_constrain_closure)"
+                         % closure)
+    if flags is None:
+        raise ValueError("sequence_constrain_beam_closure=%r needs sequence_constrain ('loops' or 'coedge_loops'): it is the closure "
+                         "look-ahead of the face-loop rule" % closure)
+    if not flags & _L.FF_CONSTRAIN_CONNECT:
+        raise ValueError("sequence_constrain_beam_closure=%r needs sequence_constrain with FF_CONSTRAIN_CONNECT ('loops', "
+                         "'coedge_loops' or the flag bits 3 / 7): without it no loop is tracked" % closure)
+    if closure == "exact" and not flags & _L.FF_CONSTRAIN_NO_REPEAT:
+        raise ValueError("sequence_constrain_beam_closure='exact' needs FF_CONSTRAIN_NO_REPEAT as well: without it there is no visited "
+                         "set to be exact about")
+    return closure
+
+
+# sequence_constrain_beams with its option sequence_constrain_beam_closure (DESIGN.md 36): the same beam search with the closure
+# look-ahead, or the exact one, per beam in the selection launch.  Outside SEQUENCE_MODES (and MODES), as SEQUENCE_CONSTRAIN_BEAM
+# is; the tables are operands beside follow_table, per wireframe and shared by its beams; the published keys are the plain record's.
+SEQUENCE_CONSTRAIN_BEAM_AHEAD = _sequence_closure_record(
+    SEQUENCE_CONSTRAIN_BEAM, _L.SequenceConstrainBeamAheadParams, "ff_sequence_decode_constrained_beam_ahead",
+    "sequence_constrain_beam_closure")
 
 # in the order the refusals name them; of several set together, decode() lets the last one's record report, SurfaceFormer the
 # first of SEQUENCE_MODEL_ORDER that is on (a record excludes every record before it in SEQUENCE_MODES, by its option's name)

@@ -1276,6 +1276,32 @@ def beam_sequence_constrained_select(logits, scores, fin, first, prev, visited, 
     receives).  There is no cumulative dead flag: a dead end abandons the face, not the beam.  Returns dict(parent, next, fin,
     dead_end (this step's flag), open (a loop is open after the step), first, prev [G * width] int32; scores fp32; visited;
     mask_rows [G * width, S] uint8; [rows]; [stats]): the new beams in rank order, best first.  No operand is modified but logits."""
+    return _beam_sequence_constrained_step(logits, scores, fin, first, prev, visited, width, flags, ntok, tok_sep, tok_eos, follows,
+                                           stop, memory, mask, kv_len, groups_per_wireframe, want_rows, want_stats, counter, None)
+
+
+@_on_tensor_device
+def beam_sequence_constrained_select_ahead(logits, scores, fin, first, prev, visited, width, flags, ntok, tok_sep, tok_eos, follows,
+                                           closure, cycle_len, budget, close_dist=None, stop="all", memory=None, mask=None,
+                                           kv_len=None, groups_per_wireframe=None, want_rows=False, want_stats=False, counter=None):
+    """beam_sequence_constrained_select with a closure look-ahead (ff_beam_sequence_constrained_select_ahead): every
+    unfinished non-empty beam forms pointer_sequence_constrained_ahead's byte row from its OWN (first, prev) and visited words --
+    closure "lookahead": under CONNECT an edge b is also masked when close_dist[w][first_k][b] > budget (loop open) or
+    cycle_len[w][b] > budget (loop closed); "exact" (NO_REPEAT as well, at most 2048 keys): with the loop open when no path of at
+    most `budget` hops leads from b to the beam's first edge through edges that are neither padded nor in the beam's visited words,
+    with it closed the cycle_len rule; close_dist is not read.  close_dist [W, L, L] / cycle_len [W, L] uint8 per wireframe
+    (ops.follow_distance), shared by its beams; one budget in 0..254 per launch.  Everything else, operands and results included,
+    is beam_sequence_constrained_select's; "lookahead" with both tables zero gives them bit for bit, width 1
+    pointer_sequence_constrained_ahead's."""
+    return _beam_sequence_constrained_step(logits, scores, fin, first, prev, visited, width, flags, ntok, tok_sep, tok_eos, follows,
+                                           stop, memory, mask, kv_len, groups_per_wireframe, want_rows, want_stats, counter,
+                                           _sequence_closure(closure, close_dist, cycle_len, budget))
+
+
+def _beam_sequence_constrained_step(logits, scores, fin, first, prev, visited, width, flags, ntok, tok_sep, tok_eos, follows, stop,
+                                    memory, mask, kv_len, groups_per_wireframe, want_rows, want_stats, counter, ahead):
+    """beam_sequence_constrained_select (ahead None) and beam_sequence_constrained_select_ahead (ahead as _lookahead_operands takes
+    it): the checks, the outputs and the launch the two share."""
     _dev(logits, "logits"), _dev(scores, "scores")
     out = {}
     if logits.dim() != 2:
@@ -1333,7 +1359,14 @@ def beam_sequence_constrained_select(logits, scores, fin, first, prev, visited, 
         _p(out["scores"]), _p(out["fin"]), _p(out["dead_end"]), _p(out["open"]), _p(out["first"]), _p(out["prev"]),
         _p(out["visited"] if fw else two), _p(out["mask_rows"]), _p(out["parent"]), _p(out["next"]), _p(memory), E, _p(rows), E,
         _p(stats), _p(counter))
-    _L.check(_L.load().ff_beam_sequence_constrained_select(C.byref(d), _stream()), "ff_beam_sequence_constrained_select")
+    if ahead is None:
+        _L.check(_L.load().ff_beam_sequence_constrained_select(C.byref(d), _stream()), "ff_beam_sequence_constrained_select")
+        return out
+    # (ONCE is this rule's own bit: the look-aheads' flag checks are about the other two)
+    form, close_dist, cycle_len, budget = _lookahead_operands(ahead, flags & ~_L.FF_CONSTRAIN_ONCE, S, L, nw, dev,
+                                                              "beam_sequence_constrained_select_ahead")
+    _L.check(_L.load().ff_beam_sequence_constrained_select_ahead(C.byref(d), form, _p(close_dist), _p(cycle_len), budget, _stream()),
+             "ff_beam_sequence_constrained_select_ahead")
     return out
 
 

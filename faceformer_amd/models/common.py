@@ -109,6 +109,9 @@ class SurfaceFormerBase(nn.Module):
                                        # sequence_constrain_samples: "lookahead" / "exact" = the closure look-ahead of the rule (DESIGN.md
                                        # 35): an edge from which the loop cannot close inside the row is masked; the tables are built
                                        # with ops.follow_distance; inputs["close_dist"] / inputs["cycle_len"] override them; None = off
+        self.sequence_constrain_beam_closure = None   # ... with sequence_constrain_beams and sequence_constrain "loops" /
+                                       # "coedge_loops": "lookahead" / "exact" = that look-ahead per beam of the beam search (DESIGN.md
+                                       # 36), every beam against its own (first, prev) and visited edges; tables as above; None = off
         self.sequence_faces = False    # single-sequence model: "parse" / "enclosed" = the decoded rows also leave as faces, on the device
                                        # (inputs["sequence_faces"]: ops.face_seq_rows + ops.face_seq_votes behind the decode,
                                        # DESIGN.md 31); "enclosed" walks the enclosure rule on the follow table (constrain_tol) and
@@ -430,6 +433,10 @@ class SurfaceFormerBase(nn.Module):
             raise ValueError("sequence_constrain_closure is a SurfaceFormer option (the closure look-ahead of the loop rule of the "
                              "single-sequence model's row); SurfaceFormer_Parallel looks ahead per anchor with constrain_lookahead / "
                              "constrain_exact")
+        if parallel and getattr(self, "sequence_constrain_beam_closure", None) is not None:      # (likewise)
+            raise ValueError("sequence_constrain_beam_closure is a SurfaceFormer option (the closure look-ahead of the beam search "
+                             "under the loop rule of the single-sequence model's row); SurfaceFormer_Parallel looks ahead per anchor "
+                             "with constrain_beam_closure")
         CF = _modes.constrain_flags(getattr(self, "constrain", None))
         CB = _modes.constrain_beams_value(getattr(self, "constrain_beams", 0), CF if parallel else 0)     # (read next to constrain_tol: no Switch)
         look = getattr(self, "constrain_lookahead", False)      # (read next to constrain_tol as well)
@@ -540,6 +547,9 @@ class SurfaceFormerBase(nn.Module):
         if getattr(self, "sequence_constrain_closure", None) is not None:
             raise ValueError("score() excludes sequence_constrain_closure: set model.sequence_constrain_closure = None to score given "
                              "paths")
+        if getattr(self, "sequence_constrain_beam_closure", None) is not None:
+            raise ValueError("score() excludes sequence_constrain_beam_closure: set model.sequence_constrain_beam_closure = None to "
+                             "score given paths")
         if not self.engine_supported():
             raise ValueError("score() needs the native engine: this model's constructor arguments take the sub-module loop")
         eng, memory, mask, kv_len = self._encode(inputs)

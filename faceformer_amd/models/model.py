@@ -208,6 +208,12 @@ class SurfaceFormer(SurfaceFormerBase):
         if closure is not None:
             found = ((_modes.SEQUENCE_CONSTRAIN_SAMPLE_AHEAD, R) if R else (_modes.SEQUENCE_CONSTRAIN_AHEAD, SC))
             found[0].sequence.model_values(self, found[1], inputs)
+        # the closure look-ahead of the beam search, a name of its own, likewise behind the recorded refusals
+        beam_closure = _modes.sequence_constrain_beam_closure_value(
+            getattr(self, "sequence_constrain_beam_closure", None), SC, W, getattr(self, "sequence_constrain_closure", None), R)
+        if beam_closure is not None:
+            found = (_modes.SEQUENCE_CONSTRAIN_BEAM_AHEAD, W)
+            found[0].sequence.model_values(self, W, inputs)
         return found
 
     def _forward_eval_sequence(self, inputs, eng, memory, mask, kv_len, T, mode, value, G):

@@ -1863,6 +1863,80 @@ int ff_decode_sequence_constrained_beam(const ff_model* m, const ff_decode_param
                                         void* workspace, size_t workspace_bytes, const ff_sequence_constrain_beam_params* beam,
                                         ff_stream_t stream);
 
+/* ---- closure look-ahead of the sequence-constrained beam search (opt-in, FF_SEQ2SEQ; entries added within ABI 105)
+ * ff_decode_sequence_constrained_beam's search with the masks of ff_pointer_sequence_constrained_ahead per beam.  It is that
+ * search and those masks wherever this section does not restate them.
+ * Budget.  The step that selects position p runs every beam under budget = min(T - 1 - p, 254).  All beams of a launch sit at the
+ *   same position, so there is one budget per launch.
+ * Tables.  The tables are ff_follow_distance's.
+ *   - close_dist [N, L, L] and cycle_len [N, L], uint8.
+ *   - They are built by ff_follow_distance with hmax = min(max(T - 2, 1), 254).
+ *   - They are per wireframe and shared by its W beams.
+ * Row formation.  An unfinished non-empty beam forms its byte row from its OWN (first, prev) and its OWN visited words.
+ *   - form 1 ("lookahead"):
+ *       Loop open: edge b is also masked when close_dist[w][first_k][b] > budget.
+ *       Loop closed: edge b is masked when cycle_len[w][b] > budget.
+ *   - form 2 ("exact"):
+ *       Loop open: edge b is masked when D_V(b -> first_k) > budget.  This is one backward search over the edges that are neither
+ *       padded nor in beam k's visited.  Under ONCE those words hold every earlier face's edges.
+ *       Loop closed: the cycle_len rule.
+ *   - The dead-end vote runs after these masks and re-opens SEP alone.
+ *   - ff_pointer_sequence_constrained's two closed-state fix-ups are unchanged.
+ * Everything else is ff_decode_sequence_constrained_beam's, bit for bit: candidates are live keys only; the renormalised score; the
+ *   c_k - log S clause; order and ties; the state update through the parent permutation; ping-pong state; both stop forms;
+ *   outputs and keys; the trace_parent trace.
+ * Identities.
+ *   (a) W = 1, either stop rule: the ff_sequence_decode_constrained_ahead greedy decode of the same form and flags.  Tokens,
+ *       dead_end, open_end and steps are exact; |score - sum of its logprob| <= (T-1) * 2^-16.  In the operator every output is
+ *       bit-equal to ff_pointer_sequence_constrained_ahead's (the W = 1 form scores c + (-log sum), the greedy expression).
+ *   (b) form 1 with both tables zero: the plain ff_decode_sequence_constrained_beam decode, bit for bit, in the operator and in
+ *       the engine.
+ *   (c) Per beam row and step, the edge keys form 2 masks contain those form 1 masks.
+ *   (d) A closed beam has the same byte row under both forms.
+ *   (e) ff_decode_sequence_constrained_beam's "best"-against-"all" identity, unchanged.
+ * Guarantees, exact given the tables, on every non-empty final beam.
+ *   (g1) beam_open_end == 0.
+ *   (g2) Under form 2, a dead-end flag sits only at a position whose previous position, along that beam's own back-tracked path,
+ *        opened the loop.
+ *   (g3) ff_decode_sequence_constrained_beam's guarantee: every complete face of a beam is a loop of the table.
+ * Unused, nothing changes.  Every other entry launches and lays out what it did before these.
+ *
+ * ff_beam_sequence_constrained_select_ahead: one step of every group; ff_beam_sequence_constrained_step, unchanged, then form,
+ *   close_dist [wireframes, L, L] (read by form 1 only), cycle_len [wireframes, L], budget, then the stream.
+ * ff_sequence_decode_constrained_beam_ahead (named outside the ff_decode prefix, as ff_sequence_decode_constrained_ahead is):
+ *   ff_decode_sequence_constrained_beam's argument list; the parameter struct adds form, close_dist and cycle_len (DEVICE, the
+ *   whole batch's).  Nothing new lies in the workspace: the size query equals ff_decode_sequence_constrained_beam_workspace_bytes.
+ * FF_ERR_ARG before any launch, every output untouched, for everything ff_decode_sequence_constrained_beam /
+ * ff_beam_sequence_constrained_select refuse, for CONNECT clear, form 2 without NO_REPEAT, a NULL required table (form 2 needs
+ * only cycle_len), a form outside 1..2, a budget outside 0..254, and more than 2048 keys (L + ntok) under form 2. */
+int ff_beam_sequence_constrained_select_ahead(const ff_beam_sequence_constrained_step* step, int form,
+                                              const unsigned char* close_dist, const unsigned char* cycle_len, int budget,
+                                              ff_stream_t stream);
+typedef struct ff_sequence_constrain_beam_ahead_params {
+  int width;
+  int stop_best;
+  int flags;
+  const unsigned int* follows;
+  int tok_sep;
+  int64_t* beams;
+  float* scores;
+  int* finished;
+  int* beam_dead_end;
+  int* beam_open_end;
+  int* dead_end;
+  int* open_end;
+  int* trace_parent;
+  int form;
+  const unsigned char* close_dist;
+  const unsigned char* cycle_len;
+} ff_sequence_constrain_beam_ahead_params;
+size_t ff_sequence_decode_constrained_beam_ahead_workspace_bytes(const ff_model* m, const ff_decode_params* p, int width);
+int ff_sequence_decode_constrained_beam_ahead(const ff_model* m, const ff_decode_params* p,
+                                              const float* memory, const unsigned char* mask, const int* kv_len,
+                                              int64_t* predict, int* steps_done, int* step_counts, float* trace_logits,
+                                              int* seq_of_row, void* workspace, size_t workspace_bytes,
+                                              const ff_sequence_constrain_beam_ahead_params* beam, ff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

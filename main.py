@@ -414,7 +414,7 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
                     seed=0, constrain=None, constrain_tol=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
                     constrain_samples=0, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0, sequence_beam_stop="all",
                     sequence_constrain=None, sequence_constrain_samples=0, sequence_constrain_beams=0,
-                    sequence_constrain_closure=None):
+                    sequence_constrain_closure=None, sequence_constrain_beam_closure=None):
     """The CLI's decode options on a built model: retirement of finished face loops, the opt-in one-fp16-product
     projections and cross-attention (split_kind "fp16"), and the log-probabilities of the selections
     (return_logprob), beam search with `beam` beams per anchor (beam_width), `sample` draws per anchor
@@ -429,7 +429,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
     "no_repeat" / "loops" / "coedge_loops" with the end-point tolerance constrain_tol), `sequence_constrain_samples`
     draws per wireframe from the keys that rule allows under temperature / top_k / top_p / seed,
     `sequence_constrain_beams` beams per wireframe over those keys under the stop rule `sequence_beam_stop`, the
-    closure look-ahead of that rule and of its sampled form (sequence_constrain_closure "lookahead" / "exact").
+    closure look-ahead of that rule and of its sampled form (sequence_constrain_closure "lookahead" / "exact") and of
+    its beam search (sequence_constrain_beam_closure).
     Without them the model keeps its defaults."""
     if retire_finished:
         model.retire_finished = True
@@ -479,6 +480,8 @@ def configure_model(model, retire_finished=False, fp16=False, scores=False, beam
         model.sequence_beam_stop = str(sequence_beam_stop)
     if sequence_constrain_closure:
         model.sequence_constrain_closure = str(sequence_constrain_closure)
+    if sequence_constrain_beam_closure:
+        model.sequence_constrain_beam_closure = str(sequence_constrain_beam_closure)
     return model
 
 
@@ -487,7 +490,7 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
              top_p=1.0, seed=0, constrain=None, constrain_beams=0, constrain_lookahead=False, constrain_exact=False,
              constrain_samples=0, device_faces=False, constrain_beam_closure=None, sequence_samples=0, sequence_beams=0,
              sequence_beam_stop="all", sequence_device_faces=False, sequence_constrain=None, sequence_constrain_samples=0,
-             sequence_constrain_beams=0, sequence_constrain_closure=None):
+             sequence_constrain_beams=0, sequence_constrain_closure=None, sequence_constrain_beam_closure=None):
     """Decode cfg.datasets_test and write the per-sample JSON files; returns the output directory.
     dist_mod: an initialised torch.distributed (or None): the samples are sharded over its ranks, the records gathered,
     rank 0 writes.  model: a ready model object (tests), else built from cfg + checkpoint.
@@ -528,7 +531,26 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
     pred_unclosed over beam 0; pred_faces stays beam 0's; sequence_constrain_closure ("lookahead" / "exact", only with
     sequence_constrain "loops" / "coedge_loops", alone or with sequence_constrain_samples, not with sequence_constrain_beams,
     single-rank runs only) also masks the edges from which a loop cannot close inside the row -- the record keys
-    stay sequence_constrain's / sequence_constrain_samples'."""
+    stay sequence_constrain's / sequence_constrain_samples'; sequence_constrain_beam_closure ("lookahead" / "exact", only with
+    sequence_constrain "loops" / "coedge_loops" and sequence_constrain_beams, single-rank runs only) is that
+    look-ahead per beam of the beam search -- the record keys stay sequence_constrain_beams'."""
+    if sequence_constrain_beam_closure is not None:
+        if sequence_constrain_beam_closure not in ("lookahead", "exact"):
+            raise ValueError("--sequence-constrain-beam-closure must be lookahead or exact")
+        if sequence_constrain_closure is not None:
+            raise ValueError("--sequence-constrain-beam-closure is not implemented with --sequence-constrain-closure: that is the "
+                             "greedy and the sampled decode's look-ahead")
+        if sequence_constrain_samples:
+            raise ValueError("--sequence-constrain-beam-closure is not implemented with --sequence-constrain-samples")
+        if not sequence_constrain_beams:
+            raise ValueError("--sequence-constrain-beam-closure requires --sequence-constrain-beams W")
+        if sequence_constrain is None:
+            raise ValueError("--sequence-constrain-beam-closure requires --sequence-constrain {loops,coedge_loops}")
+        if sequence_constrain == "no_repeat":
+            raise ValueError("--sequence-constrain-beam-closure requires --sequence-constrain loops or coedge_loops: no_repeat tracks "
+                             "no loop")
+        if dist_mod is not None and dist_mod.get_world_size() > 1:
+            raise ValueError("--sequence-constrain-beam-closure is not implemented for multi-rank runs")
     if sequence_constrain_closure is not None:
         if sequence_constrain_closure not in ("lookahead", "exact"):
             raise ValueError("--sequence-constrain-closure must be lookahead or exact")
@@ -670,6 +692,8 @@ def run_test(cfg, ckpt_path, out_dir=None, device="cuda", limit=None, batch_size
         configure_model(model, sequence_beam_stop=sequence_beam_stop, sequence_constrain_beams=sequence_constrain_beams)
     if sequence_constrain_closure:
         configure_model(model, sequence_constrain_closure=sequence_constrain_closure)
+    if sequence_constrain_beam_closure:
+        configure_model(model, sequence_constrain_beam_closure=sequence_constrain_beam_closure)
     if device_faces:
         model.extract_faces = "enclosed" if cfg.post_process.is_coedge or constrain else "parse"
         model.constrain_tol = float(cfg.post_process.enclosedness_tol)
@@ -863,6 +887,12 @@ def build_parser():
                              "every edge from which the current loop cannot close inside the row (DESIGN.md 35) -- lookahead: by the "
                              "follow table's closing distances; exact: by a search over the edges the row has not used; the record "
                              "keys stay --sequence-constrain's; single-process runs only, refused with --sequence-constrain-beams")
+    parser.add_argument("--sequence-constrain-beam-closure", choices=["lookahead", "exact"], default=None,
+                        help="with --sequence-constrain {loops,coedge_loops} --sequence-constrain-beams W: every beam also masks the "
+                             "edges from which its current loop cannot close inside the row (DESIGN.md 36) -- lookahead: by the follow "
+                             "table's closing distances; exact: by a search over the edges the beam has not used; the record keys "
+                             "stay --sequence-constrain-beams'; single-process runs only, refused with --sequence-constrain-closure "
+                             "and --sequence-constrain-samples")
     parser.add_argument("--sequence-constrain-beams", type=int, default=0, metavar="W",
                         help="with --sequence-constrain {no_repeat,loops,coedge_loops}: search the W (1..8) best rows per wireframe "
                              "over the keys the face-loop rule allows, under --sequence-beam-stop (DESIGN.md 34); every JSON record "
@@ -900,7 +930,8 @@ def main(argv=None):
              sequence_beams=args.sequence_beams, sequence_beam_stop=args.sequence_beam_stop,
              sequence_device_faces=args.sequence_device_faces, sequence_constrain=args.sequence_constrain,
              sequence_constrain_samples=args.sequence_constrain_samples, sequence_constrain_beams=args.sequence_constrain_beams,
-             sequence_constrain_closure=args.sequence_constrain_closure)
+             sequence_constrain_closure=args.sequence_constrain_closure,
+             sequence_constrain_beam_closure=args.sequence_constrain_beam_closure)
     if dist_mod is not None:
         dist_mod.destroy_process_group()
 

@@ -9,7 +9,7 @@ other checkout's sources (compiled with THIS checkout's flags), and whether the 
 of the kernels are equal; the kernels that differ are named and the exit status is 1.  A file of build.SOURCES that the other
 checkout does not have is listed with its own count and digest and compared with nothing.  With --renamed as well, a file that
 differs is compared once more kernel by kernel after renaming: the symbol itself, a trailing default template argument a kernel
-template gained (`Li0E`), the function number in local labels (.LBB<n>_, .Lfunc_end<n>) and the assembly comments (which name
+template gained (`Li0E`, and with it an argument type that depends on it), the function number in local labels (.LBB<n>_, .Lfunc_end<n>) and the assembly comments (which name
 blocks by function number) are taken out, and the other checkout's kernels are listed as `same` / `DIFF` with the new symbols and
 whether the old ones kept their order."""
 import argparse
@@ -48,6 +48,8 @@ def renamed(ks):
     out, order = {}, []
     for sym, t in ks:
         name = re.sub(r"ELi0EEEvT_$", "EEEvT_", sym)
+        # (a kernel whose argument struct now depends on the added argument: `<W, STOP, FORM = 0>(SeqConBeamArgsOf<FORM>::type)`)
+        name = re.sub(r"ELi0EEEvNS_16SeqConBeamArgsOfIXT1_EE4typeE$", "EEEvNS_14SeqConBeamArgsE", name)
         t = re.sub(r"\.(LBB|Lfunc_end|Lfunc_begin)\d+", r".\1n", t.replace(sym, "SYM"))
         out[name] = "\n".join(re.sub(r"\s*;.*$", "", line).rstrip() for line in t.splitlines())
         order.append(name)
